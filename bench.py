@@ -23,6 +23,11 @@ The output bytes of frame 0 on rank 0 are the SURVEY 8c known-answer frame: thei
 md5 is checked against tests/golden/known_md5.json after the timed loop
 ("verified"); a mismatch fails the run.
 
+--dump-outputs DIR writes what the timed path computed in its last step -- the output frames a caller of
+h2y_convert_batch receives -- as DIR/*.npy (float32 code values), so that two builds can be compared output for
+output on the same inputs (the synthetic frames depend on the arguments alone).  All of the frames when they fit
+in 64 MB, else a fixed seeded sample of their samples with its indices (dump_plan).
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -60,16 +65,25 @@ for _name, (_s, _d, _n) in TF_PAIRS.items():
     WORKLOADS[_name] = (dict(width=3840, height=2160, dst_depth=12, dst_matrix=9, src_transfer=_s, dst_transfer=_d), 15.0,
                         f"3840x2160 fp32 RGB, transfer {_s} -> {_d} ({_n} table stage{'s' if _n > 1 else ''}) -> 12-bit BT.2020nc YCbCr 4:2:0", None)
 TRAFFIC_FILE = os.path.join("profiles", "r03_pmc_traffic.json")
+DUMP_BYTES = 64_000_000  # --dump-outputs: the files of all ranks together, .npy headers included
+DUMP_SEED = 20261015
+
+
+def positive_int(text):
+    v = int(text)
+    if v < 1:
+        raise argparse.ArgumentTypeError(f"must be at least 1, not {v}")
+    return v
 
 
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=positive_int, default=20, help="timed steps of the main measurement (ms_per_step is their mean)")
     ap.add_argument("--warmup", type=int, default=10)  # the card clocks up during the first ~10 launches
     ap.add_argument("--frames", type=int, default=128, help="frames per GPU per step (128 x 124 MB = 16 GB of the 288; one launch: the library splits "
                     "longer batches.  Rounds 1-3 measured 64: a launch's fixed costs -- tables staged per block, the blocks' finish spread, "
-                    "the FIR path's row segments -- weigh half as much at 128: box +0.5 % on the kernel and +1.2 % on value, FIR +1.5 % / +1.8 %)")
+                    "the FIR path's row segments -- weigh half as much at 128: box +0.5 %% on the kernel and +1.2 %% on value, FIR +1.5 %% / +1.8 %%)")
     ap.add_argument("--workload", default="C2", choices=sorted(WORKLOADS))
     ap.add_argument("--resampler", default="box", choices=["box", "fir"])
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -90,6 +104,9 @@ def parse(argv=None):
                          "layout); separate (default): one allocation per plane / frame.  Where the planes lie decides how often the kernels' streams meet in "
                          "a DRAM bank: either way a launch's time moves by several per cent from process to process (DESIGN.md 7.2)")
     ap.add_argument("--no-pipeline", action="store_true", help="finish every step before the next is enqueued (A/B against two batches in flight)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the main measurement's output frames of its last step to DIR/*.npy (float32; all "
+                         "of them when they fit in 64 MB, else a fixed seeded sample of their samples with the samples' indices)")
     ap.add_argument("--rehearse", action="store_true",
                     help="CPU rehearsal of the N-rank launch: ranks rendezvous (gloo), shard the frame indices and reduce made-up counters; "
                          "no device, no conversion, nothing measured")
@@ -177,6 +194,46 @@ class DeviceSynth:
             q[0], q[1] = 0.0, 1.0
             planes.append(q.view(torch.int16) if f16 else q)
         return planes
+
+
+def dump_plan(n_frames, frame_samples, budget_bytes):
+    """Which output samples --dump-outputs writes: None = every one ((n_frames, frame_samples) float32 fits the budget), else
+    the sorted global indices (frame * frame_samples + offset) of a fixed seeded sample, sized so that its values (float32) and
+    its indices (float64) fit together.  Depends on its arguments alone: two runs with the same arguments write the same samples."""
+    import numpy as np
+
+    total = n_frames * frame_samples
+    if total * 4 + 4096 <= budget_bytes:
+        return None
+    n = (budget_bytes - 8192) // 12
+    return np.unique(np.random.default_rng(DUMP_SEED).integers(0, total, n, dtype=np.int64))
+
+
+def dump_frames(dirname, outs_t, frame_samples, budget_bytes, prefix=""):
+    """Write the output frames `outs_t` (device int16 tensors of uint16 code values) as dump_plan says; returns what was written."""
+    import numpy as np
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    idx = dump_plan(len(outs_t), frame_samples, budget_bytes)
+    if idx is None:
+        vals = np.stack([t.cpu().numpy().view(np.uint16) for t in outs_t]).astype(np.float32)
+        files = {f"{prefix}yuv_frames": vals}
+    else:
+        parts = []
+        for f, t in enumerate(outs_t):
+            lo, hi = np.searchsorted(idx, [f * frame_samples, (f + 1) * frame_samples])
+            if hi > lo:
+                offs = torch.from_numpy(idx[lo:hi] - f * frame_samples).to(t.device)
+                parts.append(t.index_select(0, offs).cpu().numpy().view(np.uint16))
+        vals = np.concatenate(parts).astype(np.float32)
+        files = {f"{prefix}yuv_sample": vals, f"{prefix}yuv_sample_index": idx.astype(np.float64)}
+    for name, a in files.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return {"dir": dirname, "files": sorted(n + ".npy" for n in files), "frames": len(outs_t), "samples_per_frame": frame_samples,
+            "samples": int(vals.size), "of_samples": len(outs_t) * frame_samples, "seed": None if idx is None else DUMP_SEED,
+            "what": "output frames of the main measurement's last timed step as float32 code values" +
+                    ("" if idx is None else ", a fixed seeded sample; yuv_sample_index = frame * samples_per_frame + offset in the frame")}
 
 
 def run_steps(ctx, d, n_frames, ins, outs, steps, warmup, barrier, pipeline=True):
@@ -419,10 +476,11 @@ def main() -> int:
         arena = torch.empty(len(indices) * 3 * n, dtype=torch.float16 if f16 else torch.float32, device=dev)
         return [synth_cache[key].frame(w, hh, k, f16, into=[arena[(i * 3 + c) * n:(i * 3 + c + 1) * n] for c in range(3)]) for i, k in enumerate(indices)]
 
-    def measure(wl, resampler, frames_in, F, steps, warmup, check=(), known=True):
+    def measure(wl, resampler, frames_in, F, steps, warmup, check=(), known=True, dump_dir=None):
         """One timed pass of workload `wl` over F frames per step (frames_in may hold fewer DISTINCT inputs: they repeat;
         every frame has its own output).  Returns a dict of figures; all ranks call it together.  `check`: output frames whose
-        md5 rank 0 takes after the timed loop (r["md5_frames"]), to be held against the CPU reference's frames of the same index."""
+        md5 rank 0 takes after the timed loop (r["md5_frames"]), to be held against the CPU reference's frames of the same index.
+        `dump_dir`: every rank writes its output frames of the last timed step there (dump_frames; r["dump"])."""
         desc_kw, bytes_per_px, wl_name, stem = WORKLOADS[wl]
         is420 = desc_kw.get("chroma", 1) == 1
         w, hh = desc_kw["width"], desc_kw["height"]
@@ -461,6 +519,9 @@ def main() -> int:
             for f in check:
                 if 0 <= f < F and f < len(frames_in):  # (output f was made from the generator's frame f)
                     md5_frames[f] = hashlib.md5(outs_t[f].cpu().numpy().tobytes()).hexdigest()
+        dump = None
+        if dump_dir is not None:
+            dump = dump_frames(dump_dir, outs_t, nb // 2, DUMP_BYTES // world, f"rank{rank}_" if world > 1 else "")
         del outs_t
         alg_bytes = bytes_per_px * w * hh * F  # per step
         ach_kernel = alg_bytes / (kernel_ms / 1e3) / 1e9 if kernel_ms > 0 else 0.0
@@ -468,7 +529,7 @@ def main() -> int:
         return dict(workload=wl, text=wl_name, resampler=resampler if is420 else "none", is420=is420, secs=tmax, pixels=total_px, steps=steps,
                     per_rank=[float(t[1]) / float(t[0]) / 1e6 for t in allr], kernel_ms=kernel_ms, launches=launches, redone=redone,
                     kernel=kernel, variant=variant, verified=verified, verify_case=vname, md5=got_md5, alg_bytes=alg_bytes,
-                    ach_kernel=ach_kernel, ach_wall=ach_wall, w=w, h=hh, frames=F, per_step=per_step, md5_frames=md5_frames)
+                    ach_kernel=ach_kernel, ach_wall=ach_wall, w=w, h=hh, frames=F, per_step=per_step, md5_frames=md5_frames, dump=dump)
 
     def roofline_of(r, traffic=None, traffic_source=None):
         """Dominant kernel of the pass.  Box / 4:4:4 and the fused FIR path run ONE kernel per launch: `achieved` is its
@@ -533,7 +594,7 @@ def main() -> int:
     # every block's slice range, the first and the last launch split
     do_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
     check = sorted(set(range(min(8, F))) | {8 + (i * (F - 9)) // 31 for i in range(32) if F > 9}) if do_cpu and args.content == "uniform" else []
-    main_r = measure(args.workload, args.resampler, frames_in, F, args.steps, args.warmup, check)
+    main_r = measure(args.workload, args.resampler, frames_in, F, args.steps, args.warmup, check, dump_dir=args.dump_outputs)
     value = main_r["pixels"] / main_r["secs"] / 1e6
     ms_per_step = main_r["secs"] / args.steps * 1e3
 
@@ -588,6 +649,8 @@ def main() -> int:
     out["roofline"] = roofline_of(main_r, traffic, traffic_source)
     out["roofline"]["device_copy_gbs"] = None if copy_gbs is None else round(copy_gbs, 1)
     out["frames_redone"] = main_r["redone"]
+    if main_r["dump"] is not None:
+        out["dump_outputs"] = main_r["dump"]
     failed = main_r["verified"] is False
 
     # ---- secondary passes (N = 1): the other resampler and the other BASELINE configs -------

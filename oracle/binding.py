@@ -6,10 +6,14 @@ The product package (hdr2yuv_amd) must never import this module.
 `Oracle`  -> oracle/liboracle.so      our CPU restatement (h2y_oracle.c)
 `Ref`     -> oracle/_ref/libh2y_ref.so the reference's own convert.cpp/common.cpp
              object code behind ref_shim.cpp (built in the container only).
+`RecordedRef` -> tests/golden/ref_answers.npz  digests of Ref's answers to the tests' calls,
+             recorded from it: what the tests compare with where oracle/_ref
+             cannot be built.
 """
 from __future__ import annotations
 
 import ctypes as C
+import hashlib
 import os
 import subprocess
 
@@ -228,6 +232,10 @@ class Ref:
     def pq(self, x: float) -> float:
         return float(self.lib.h2y_ref_pq10000_r(float(x)))
 
+    def pq_bits(self, xs) -> np.ndarray:
+        """PQ10000_r of every float32 of `xs`: the bits of the float32 results."""
+        return np.array([np.float32(self.pq(float(x))).view(np.uint32) for x in np.asarray(xs, np.float32)], np.uint32)
+
     def up444(self, src: np.ndarray, width: int, height: int, algorithm: int, min_cv: int, max_cv: int, fill: int = 0) -> np.ndarray:
         src = np.ascontiguousarray(src, dtype=np.uint16).reshape(height >> 1, width >> 1)
         dst = np.full((height, width), fill, dtype=np.uint16)
@@ -266,3 +274,118 @@ class Ref:
 
 def ref_available() -> bool:
     return os.path.exists(os.path.join(HERE, "_ref", "libh2y_ref.so")) or os.path.isdir(REF_SRC)
+
+
+REF_ANSWERS = os.path.join(os.path.dirname(HERE), "tests", "golden", "ref_answers.npz")
+
+
+def _md5(a: np.ndarray) -> str:
+    return hashlib.md5(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+class RecordedArray:
+    """What is kept of an array the reference returned: its shape, dtype and the md5 of its bytes."""
+
+    def __init__(self, shape, dtype, md5):
+        self.shape, self.dtype, self.md5 = tuple(shape), np.dtype(dtype), md5
+
+    @classmethod
+    def of(cls, a: np.ndarray) -> "RecordedArray":
+        return cls(a.shape, a.dtype, _md5(a))
+
+    def matches(self, a) -> bool:
+        """True when `a` holds the recorded array's values in its shape (as np.array_equal would find against it)."""
+        a = np.asarray(a)
+        if a.shape != self.shape:
+            return False
+        b = a.astype(self.dtype)
+        return np.array_equal(a, b) and _md5(b) == self.md5
+
+    def __repr__(self):
+        return f"RecordedArray(shape={self.shape}, dtype={self.dtype}, md5={self.md5})"
+
+
+class RecordedRef:
+    """The reference's answers to the calls the tests make, recorded from its object code
+    (tests/golden/make_ref_answers.py), with the same methods as `Ref`.  Every call is keyed by an md5 of its
+    method and its complete input (descriptor bytes, input planes, scalars); what is kept of an array answer is
+    its shape, dtype and md5 (RecordedArray).
+
+    mode "replay": answer from the file alone (anywhere oracle/_ref cannot be built): arrays come back as RecordedArray.
+    mode "check":  answer from `live` (a Ref), failing if that differs from the file or the file has no answer.
+    mode "record": answer from `live` and keep the answer; save() writes the file."""
+
+    def __init__(self, path: str = REF_ANSWERS, live: "Ref | None" = None, mode: str = "replay"):
+        assert mode in ("replay", "check", "record") and (live is not None) == (mode != "replay")
+        self.path, self.live, self.mode = path, live, mode
+        self.answers = {}
+        if mode != "record":
+            with np.load(path) as z:
+                for k, shape, dtype, md5 in zip(*(np.char.decode(z[n]).tolist() for n in ("keys", "shapes", "dtypes", "md5s"))):
+                    self.answers[k] = RecordedArray([int(n) for n in shape.split("x") if n], dtype, md5)
+
+    @staticmethod
+    def _key(method, *parts):
+        hsh = hashlib.md5(method.encode())
+        for p in parts:
+            if isinstance(p, np.ndarray):
+                hsh.update(f"|{p.dtype.str}{p.shape}|".encode() + np.ascontiguousarray(p).tobytes())
+            elif isinstance(p, H2YDesc):
+                hsh.update(b"|desc|" + bytes(p))
+            else:
+                hsh.update(f"|{int(p)}".encode())
+        return f"{method}_{hsh.hexdigest()}"
+
+    def _answer(self, key, compute):
+        if self.mode == "record":
+            got = np.asarray(compute())
+            self.answers[key] = RecordedArray.of(got)
+            return got
+        if key not in self.answers:
+            raise KeyError(f"{os.path.relpath(self.path)} has no recorded answer for this call ({key}): "
+                           "run tests/golden/make_ref_answers.py where oracle/_ref can be built")
+        want = self.answers[key]
+        if self.mode == "replay":
+            return want
+        got = np.asarray(compute())
+        if not (got.dtype == want.dtype and want.matches(got)):
+            raise AssertionError(f"oracle/_ref's answer to {key} differs from the one recorded in {os.path.relpath(self.path)}")
+        return got
+
+    def save(self) -> None:
+        keys = sorted(self.answers)
+        cols = {"keys": keys, "md5s": [self.answers[k].md5 for k in keys], "dtypes": [self.answers[k].dtype.str for k in keys],
+                "shapes": ["x".join(str(n) for n in self.answers[k].shape) for k in keys]}
+        np.savez_compressed(self.path, **{n: np.char.encode(np.array(v)) for n, v in cols.items()})
+
+    def pq_bits(self, xs):
+        key = self._key("pq_bits", np.asarray(xs, np.float32))
+        return self._answer(key, lambda: self.live.pq_bits(xs))
+
+    def convert_frame(self, d: H2YDesc, planes, want_444: bool = False):
+        if want_444:
+            raise NotImplementedError("recorded answers hold the .yuv samples only")
+        dt = _np_dtype(d.in_sample_type)
+        key = self._key("convert_frame", d, *[np.ascontiguousarray(p, dtype=dt).reshape(-1) for p in planes])
+        return self._answer(key, lambda: self.live.convert_frame(d, planes))
+
+    def sub420(self, src: np.ndarray, bit_depth: int, fir: bool):
+        key = self._key("sub420", np.ascontiguousarray(src, dtype=np.uint16), bit_depth, fir)
+        return self._answer(key, lambda: self.live.sub420(src, bit_depth, fir))
+
+    def up444(self, src: np.ndarray, width: int, height: int, algorithm: int, min_cv: int, max_cv: int, fill: int = 0):
+        key = self._key("up444", np.ascontiguousarray(src, dtype=np.uint16).reshape(-1), width, height, algorithm, min_cv, max_cv, fill)
+        return self._answer(key, lambda: self.live.up444(src, width, height, algorithm, min_cv, max_cv, fill))
+
+    def matrix_inverse(self, width, height, in_depth, in_full_range, in_matrix, out_depth, planes):
+        """One answer per output plane (a list of three, as Ref gives)."""
+        src = [np.ascontiguousarray(p, dtype=np.uint16).reshape(-1) for p in planes]
+        key = self._key("matrix_inverse", width, height, in_depth, in_full_range, in_matrix, out_depth, *src)
+        live = {}
+
+        def plane(c):
+            if "out" not in live:
+                live["out"] = self.live.matrix_inverse(width, height, in_depth, in_full_range, in_matrix, out_depth, planes)
+            return live["out"][c]
+
+        return [self._answer(f"{key}_{c}", lambda c=c: plane(c)) for c in range(3)]

@@ -79,7 +79,7 @@ def test_context_fails_loudly_without_gpu():
     assert e.value.code == 3 and "no CPU path" in str(e.value)
 
 
-def test_cli_built_and_fails_loudly_without_gpu():
+def test_cli_built_and_fails_loudly_without_gpu(tmp_path):
     import torch
 
     exe = os.path.join(ROOT, "hdr2yuv_amd", "hdr2yuv")
@@ -89,7 +89,7 @@ def test_cli_built_and_fails_loudly_without_gpu():
     assert r.returncode == 0 and "--dst_matrix_coeffs" in r.stdout and "--chroma_resampler_type" in r.stdout
     if not torch.cuda.is_available():
         r = subprocess.run([exe, "--synthetic", "0", "--src_pic_width", "64", "--src_pic_height", "32", "--dst_filename",
-                            "/tmp/_h2y_never.yuv", "--src_bit_depth", "32", "--dst_bit_depth", "10", "--src_transfer_characteristics", "8", "--dst_transfer_characteristics", "16", "--dst_matrix_coeffs", "9",
+                            str(tmp_path / "never.yuv"), "--src_bit_depth", "32", "--dst_bit_depth", "10", "--src_transfer_characteristics", "8", "--dst_transfer_characteristics", "16", "--dst_matrix_coeffs", "9",
                             "--dst_chroma_format_idc", "1", "--dst_video_full_range_flag", "0"], capture_output=True, text=True)
         assert r.returncode == 1 and "no CPU path" in r.stdout
 

@@ -1069,6 +1069,32 @@ def test_bench_device_generator_matches_host_generator():
                 assert np.array_equal(got[c].view(np.uint16) if f16 else got[c].view(np.uint32), want[c].view(np.uint16) if f16 else want[c].view(np.uint32)), (w, hh, f16, k, c)
 
 
+def test_bench_dump_outputs_are_the_frames_it_computed(tmp_path, oracle):
+    """bench.py --dump-outputs: after its timed steps (exactly --steps of them) it writes the output frames of the last step --
+    here a seeded sample of two 4K frames, as float32 -- and those are the oracle's conversion of the same synthetic frames."""
+    import subprocess
+    import sys
+
+    from hdr2yuv_amd.synth import synth_frame
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--no-extra", "--no-cpu-baseline", "--frames", "2", "--steps", "3",
+                        "--warmup", "1", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["verified"] is True
+    files = sorted(os.listdir(tmp_path))
+    assert files == out["dump_outputs"]["files"] == ["yuv_sample.npy", "yuv_sample_index.npy"]
+    assert sum(os.path.getsize(tmp_path / f) for f in files) <= 64_000_000
+    vals, idx = np.load(tmp_path / "yuv_sample.npy"), np.load(tmp_path / "yuv_sample_index.npy")
+    assert vals.dtype == np.float32 and idx.dtype == np.float64 and vals.shape == idx.shape and vals.size == out["dump_outputs"]["samples"]
+    d = ob.make_desc(3840, 2160, dst_depth=12, dst_matrix=ob.MATRIX_BT2020NC, resampler=0)  # bench.py's headline: C2, box
+    want = np.concatenate([oracle.convert_frame(d, synth_frame(3840, 2160, k)) for k in range(2)])
+    assert want.size == out["dump_outputs"]["of_samples"]
+    assert np.array_equal(vals, want[idx.astype(np.int64)].astype(np.float32))
+
+
 @pytest.mark.parametrize("w,hh", [(2, 2), (4, 2), (6, 10), (64, 32), (130, 18), (258, 70), (1920, 1080)])
 def test_upsample_444(ctx, oracle, w, hh):
     """h2y_upsample_444 (Subsample420to444, convert.cpp:1869-1986) vs the oracle, itself pinned to the

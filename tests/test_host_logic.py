@@ -127,6 +127,23 @@ def test_bench_refuses_fewer_gpus_than_asked():
     assert r.returncode != 0 and out is None and "refusing" in r.stderr
 
 
+def test_bench_dump_plan_is_fixed_and_fits():
+    """--dump-outputs: the samples written depend on the arguments alone and fit in 64 MB (float32 values + float64 indices);
+    outputs that fit whole are written whole.  --steps below 1 is refused."""
+    import importlib
+
+    bench = importlib.import_module("bench")
+    spf = 3840 * 2160 * 3 // 2  # one 4K 4:2:0 frame
+    a = bench.dump_plan(128, spf, bench.DUMP_BYTES)
+    b = bench.dump_plan(128, spf, bench.DUMP_BYTES)
+    assert np.array_equal(a, b) and np.all(np.diff(a) > 0) and a[0] >= 0 and a[-1] < 128 * spf
+    assert a.size * (4 + 8) + 2 * 128 <= bench.DUMP_BYTES and a.size > bench.DUMP_BYTES // 13
+    assert bench.dump_plan(4, 64 * 32 * 3 // 2, bench.DUMP_BYTES) is None
+    assert bench.parse(["--steps", "7"]).steps == 7
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+
+
 # ---- the command line: how unset attributes resolve (hdr2yuv.cpp:61-62, :265-318, :765-766; read_file) -------------
 
 def _cli_dry(args):
