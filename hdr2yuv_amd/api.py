@@ -29,6 +29,7 @@ EXPORTS = [
     "h2y_last_error", "h2y_ctx_set_stream", "h2y_convert_frame", "h2y_convert_batch", "h2y_convert_batch_enqueue",
     "h2y_batch_finish", "h2y_pic_stats", "h2y_matrix_convert", "h2y_subsample_420", "h2y_last_kernel_ms", "h2y_last_kernel_name", "h2y_last_kernel_variant",
     "h2y_matrix_inverse", "h2y_upsample_444", "h2y_inverse_420", "h2y_inverse_frame", "h2y_ctx_set_option", "h2y_stream_open", "h2y_stream_input", "h2y_stream_submit", "h2y_stream_output", "h2y_stream_close",
+    "h2y_inverse_batch", "h2y_inverse_stream_open",
 ]
 
 
@@ -172,6 +173,10 @@ def load_library():
     L.h2y_inverse_420.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.h2y_inverse_frame.restype = C.c_int
     L.h2y_inverse_frame.argtypes = [C.c_void_p] + [C.c_int] * 8 + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.h2y_inverse_batch.restype = C.c_int
+    L.h2y_inverse_batch.argtypes = [C.c_void_p] + [C.c_int] * 9 + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.h2y_inverse_stream_open.restype = C.c_int
+    L.h2y_inverse_stream_open.argtypes = [C.c_void_p] + [C.c_int] * 9
     L.h2y_stream_open.restype = C.c_int
     L.h2y_stream_open.argtypes = [C.c_void_p, C.POINTER(H2YDesc), C.c_int]
     L.h2y_stream_input.restype = C.c_int
@@ -335,10 +340,31 @@ class Context:
         self._check(self.lib.h2y_inverse_frame(self.h, width, height, in_chroma, in_depth, in_full_range, in_matrix, out_depth, algorithm, ip, op))
         return outs
 
+    def inverse_batch(self, width, height, in_chroma, in_depth, in_full_range, in_matrix, out_depth, algorithm, frames_in, frames_out) -> None:
+        """Device U16 planes of many frames: frames_in[f] = (Y, Cb/Dz, Cr/Dx), frames_out[f] = (G, B, R), tensors or pointers."""
+        n = len(frames_in)
+        if len(frames_out) != n:
+            raise ValueError("frames_in and frames_out differ in length")
+        ins = (C.c_void_p * (3 * n))()
+        outs = (C.c_void_p * (3 * n))()
+        for f in range(n):
+            for c in range(3):
+                ins[3 * f + c] = self._ptr(frames_in[f][c])
+                outs[3 * f + c] = self._ptr(frames_out[f][c])
+        self._check(self.lib.h2y_inverse_batch(self.h, width, height, in_chroma, in_depth, in_full_range, in_matrix, out_depth, algorithm,
+                                               n, ins, outs))
+
     # ---- host <-> device pipeline -----------------------------------------------------------
     def stream_open(self, d, depth=3) -> None:
         self._check(self.lib.h2y_stream_open(self.h, C.byref(d), depth))
         self._stream_desc = d
+        self._stream_inverse = None
+
+    def inverse_stream_open(self, width, height, in_chroma, in_depth, in_full_range, in_matrix, out_depth, algorithm, depth=3) -> None:
+        """The pinned ring for the .yuv -> G,B,R flow: stream_input gives Y, Cb/Dz, Cr/Dx, stream_output G, B, R."""
+        self._check(self.lib.h2y_inverse_stream_open(self.h, width, height, in_chroma, in_depth, in_full_range, in_matrix, out_depth,
+                                                     algorithm, depth))
+        self._stream_inverse = (width, height, in_chroma)
 
     def stream_input(self):
         """The three pinned input planes of the next slot, as numpy views to fill in place."""
@@ -346,6 +372,10 @@ class Context:
 
         ptrs = (C.c_void_p * 3)()
         self._check(self.lib.h2y_stream_input(self.h, ptrs))
+        if getattr(self, "_stream_inverse", None):
+            w, h, chroma = self._stream_inverse
+            nc = (w // 2) * (h // 2) if chroma == CHROMA_420 else w * h
+            return [np.ctypeslib.as_array(C.cast(ptrs[c], C.POINTER(C.c_uint16)), shape=(nc if c else w * h,)) for c in range(3)]
         d = self._stream_desc
         n = d.width * d.height
         dt = np.float32 if d.in_sample_type == SAMPLE_F32 else np.uint16
@@ -355,15 +385,20 @@ class Context:
         self._check(self.lib.h2y_stream_submit(self.h))
 
     def stream_output(self):
-        """The oldest frame in flight (a numpy view of pinned memory, valid until the next stream_output)."""
+        """The oldest frame in flight (a numpy view of pinned memory, valid until the next stream_output).  On an inverse
+        stream: shape (3, width*height), rows G, B, R (``.reshape(-1)`` for the three planes as one)."""
         import numpy as np
 
         p = C.POINTER(C.c_uint16)()
         self._check(self.lib.h2y_stream_output(self.h, C.byref(p)))
+        if getattr(self, "_stream_inverse", None):
+            w, h, _ = self._stream_inverse
+            return np.ctypeslib.as_array(p, shape=(3, w * h))
         return np.ctypeslib.as_array(p, shape=(frame_bytes(self._stream_desc) // 2,))
 
     def stream_close(self) -> None:
         self._check(self.lib.h2y_stream_close(self.h))
+        self._stream_inverse = None
 
     def last_kernel_name(self) -> str:
         return (self.lib.h2y_last_kernel_name(self.h) or b"").decode()

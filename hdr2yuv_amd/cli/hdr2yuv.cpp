@@ -148,14 +148,14 @@ static void run_block(const cli_args &a, const h2y_desc &d, int fd_out, off_t ba
     h2y_ctx_destroy(ctx);
 }
 
-/* .yuv -> RGB (matrix_inverse), frame by frame on the host-buffer entry */
+/* .yuv -> RGB (matrix_inverse): frames [first, first+count) through one context's pinned inverse ring, as run_block */
 static void run_block_inverse(const cli_args &a, int fd_out, off_t base, block *b)
 {
     h2y_ctx *ctx = nullptr;
     FILE *fin = nullptr;
     auto fail = [&](const std::string &m) {
         b->err = m;
-        if (ctx) h2y_ctx_destroy(ctx);
+        if (ctx) { h2y_stream_close(ctx); h2y_ctx_destroy(ctx); }
         if (fin) fclose(fin);
     };
     if (b->count < 1) return;
@@ -163,21 +163,42 @@ static void run_block_inverse(const cli_args &a, int fd_out, off_t base, block *
     const size_t n = (size_t)a.in.width * a.in.height;
     const bool sub = a.in.chroma_format_idc == H2Y_CHROMA_420;
     const size_t nc = sub ? (size_t)(a.in.width / 2) * (a.in.height / 2) : n, in_frame = (n + 2 * nc) * 2, out_frame = 3 * n * 2;
-    std::vector<uint16_t> in(n + 2 * nc), out(3 * n);
     fin = fopen(a.src, "rb");
     if (!fin) return fail(std::string("unable to open file ") + a.src);
     if (fseeko(fin, (off_t)in_frame * (off_t)(a.start_frame + b->first), SEEK_SET)) return fail("seek failed");
-    for (long f = 0; f < b->count; f++) {
-        if (fread(in.data(), 1, in_frame, fin) != in_frame) return fail(std::string("short read from ") + a.src);
-        const uint16_t *ip[3] = {in.data(), in.data() + n, in.data() + n + nc};
-        uint16_t *op[3] = {out.data() + n, out.data() + 2 * n, out.data()}; /* planes G,B,R -> file order R,G,B (write_tiff: R,G,B per pixel) */
-        if (h2y_inverse_frame(ctx, a.in.width, a.in.height, a.in.chroma_format_idc, a.in.bit_depth, a.in.video_full_range_flag,
-                              a.in.matrix_coeffs, a.out.bit_depth, a.resampler, ip, op))
-            return fail(h2y_last_error(ctx));
-        const long k = b->first + f;
-        if (!write_at(fd_out, out.data(), out_frame, base + (off_t)k * (off_t)out_frame)) return fail(std::string("short write to ") + a.dst);
+    const int depth = 3;
+    if (h2y_inverse_stream_open(ctx, a.in.width, a.in.height, a.in.chroma_format_idc, a.in.bit_depth, a.in.video_full_range_flag,
+                                a.in.matrix_coeffs, a.out.bit_depth, a.resampler, depth))
+        return fail(h2y_last_error(ctx));
+    long in_flight = 0;
+    auto drain_one = [&]() -> bool {
+        const uint16_t *gbr = nullptr;
+        if (h2y_stream_output(ctx, &gbr)) { fail(h2y_last_error(ctx)); return false; }
+        const long k = b->first + b->done;
+        const off_t at = base + (off_t)k * (off_t)out_frame;
+        /* planes G, B, R -> file order R, G, B (write_tiff: R, G, B per pixel) */
+        if (!write_at(fd_out, gbr + 2 * n, 2 * n, at) || !write_at(fd_out, gbr, 4 * n, at + (off_t)(2 * n))) {
+            fail(std::string("short write to ") + a.dst);
+            return false;
+        }
         b->done++;
+        in_flight--;
+        return true;
+    };
+    for (long f = 0; f < b->count; f++) {
+        void *planes[3];
+        if (h2y_stream_input(ctx, planes)) return fail(h2y_last_error(ctx));
+        size_t got = fread(planes[0], 1, 2 * n, fin);
+        got += fread(planes[1], 1, 2 * nc, fin);
+        got += fread(planes[2], 1, 2 * nc, fin);
+        if (got != in_frame) return fail(std::string("short read from ") + a.src);
+        if (h2y_stream_submit(ctx)) return fail(h2y_last_error(ctx));
+        in_flight++;
+        if (in_flight == depth - 1 && !drain_one()) return;
     }
+    while (in_flight > 0)
+        if (!drain_one()) return;
+    h2y_stream_close(ctx);
     fclose(fin);
     h2y_ctx_destroy(ctx);
 }

@@ -72,6 +72,11 @@ const int kFirSubBatch = 32; /* frames per fused launch on the FIR path: every l
 
 } // namespace
 
+/* The parameters of one .yuv -> G,B,R flow (h2y_inverse_batch, h2y_inverse_stream_open) */
+struct inv_params {
+    int width, height, chroma, in_depth, in_full_range, matrix, out_depth, algorithm;
+};
+
 /* Everything one batch in flight owns: two of them let h2y_convert_batch_enqueue() queue batch k+1 behind batch k
  * before h2y_batch_finish() has looked at k (the 35 us between two launches -- the statistics kernel, one copy, the
  * host's turn-around -- disappear behind the running kernel). */
@@ -175,6 +180,9 @@ struct h2y_ctx {
     double fir_flag_share = 0.0; /* share of the last k_fir_fused batch's pixels (in tiles of eight) the first tier could not settle */
     uint16_t *d_tmp = nullptr;
     size_t tmp_cap = 0;
+    /* h2y_inverse_batch: the frame table (pinned on the host, and its device copy the kernels read) */
+    inv_frame *d_inv_frames = nullptr, *h_inv_frames = nullptr;
+    size_t d_inv_cap = 0, h_inv_cap = 0; /* bytes */
 
     /* staging for the host-buffer entry */
     void *d_in = nullptr;
@@ -187,8 +195,8 @@ struct h2y_ctx {
     int32_t hint_floor[3] = {0, 0, 0}, hint_ceil[3] = {0, 0, 0};
     /* streaming pipeline (h2y_stream_*): a ring of pinned host slots with device twins */
     struct stream_slot {
-        char *h_in = nullptr;      /* pinned: three planes, each plane_al bytes apart */
-        uint16_t *h_out = nullptr; /* pinned: one .yuv frame */
+        char *h_in = nullptr;      /* pinned: three planes, at s_in_off[0..2] */
+        uint16_t *h_out = nullptr; /* pinned: one .yuv frame (an inverse stream: G | B | R) */
         char *d_in = nullptr;
         uint16_t *d_out = nullptr;
         hipEvent_t ev_h2d = nullptr, ev_conv = nullptr, ev_done = nullptr;
@@ -200,6 +208,12 @@ struct h2y_ctx {
     size_t s_plane_al = 0;
     int s_head = 0, s_tail = 0, s_lent = -1;
     bool streaming = false;
+    /* an inverse stream (h2y_inverse_stream_open): the flow's parameters, where the slot's input planes lie, the bytes of one
+     * H2D copy, and the distance between the G, B, R planes in the slot's device output (one plane's bytes, or 256-byte aligned
+     * when that would leave a plane misaligned for the kernel) */
+    bool s_inverse = false;
+    inv_params s_inv{};
+    size_t s_in_off[3] = {0, 0, 0}, s_in_bytes = 0, s_out_stride = 0;
     int slot_base = 0; /* run_frames(): first entry of d_frames/h_frames to use (one per stream slot) */
     float last_ms = 0.f;
     const char *last_name = "";
@@ -1322,6 +1336,8 @@ void h2y_ctx_destroy(h2y_ctx *ctx)
     (void)hipFree(ctx->d_table1);
     (void)hipFree(ctx->d_table_ext);
     (void)hipFree(ctx->d_tmp);
+    (void)hipFree(ctx->d_inv_frames);
+    (void)hipHostFree(ctx->h_inv_frames);
     (void)hipFree(ctx->d_in);
     (void)hipFree(ctx->d_out);
     if (ctx->fir_stream) {
@@ -1568,6 +1584,34 @@ int h2y_convert_frame(h2y_ctx *ctx, const h2y_desc *d, const void *const in_plan
     return H2Y_OK;
 }
 
+/* matrix_inverse()'s scalars (convert.cpp:1320-1867): everything of inverse_args but the plane pointers */
+static void inverse_setup(inverse_args &a, int width, int height, int in_bit_depth, int in_full_range, int in_matrix_coeffs, int out_bit_depth)
+{
+    const clip_limits ic = make_clip(in_bit_depth, in_full_range);
+    a.npix = (uint32_t)width * (uint32_t)height;
+    a.d709 = in_matrix_coeffs == H2Y_MATRIX_BT709;
+    a.minVR = ic.minVR;
+    a.maxVR = ic.maxVR;
+    a.shift_right = in_bit_depth > out_bit_depth;
+    a.shift = a.shift_right ? in_bit_depth - out_bit_depth : out_bit_depth - in_bit_depth;
+}
+
+/* ... and those of the 4:2:0 flow (yuv2tiff.cpp:92-93,142-154: minCV 0, maxCV 2^depth - 1 for the upsampling) */
+static void inverse420_setup(inv420_args &a, int width, int height, int in_bit_depth, int in_full_range, int in_matrix_coeffs,
+                             int out_bit_depth, int algorithm)
+{
+    a.up.src0 = a.up.src1 = nullptr;
+    a.up.dst0 = a.up.dst1 = nullptr;
+    a.up.width = width; a.up.height = height;
+    a.up.algorithm = algorithm;
+    a.up.fmin = 0.0f; a.up.fmax = (float)((1u << in_bit_depth) - 1u);
+    for (int c = 0; c < 3; c++) {
+        a.inv.in[c] = nullptr;
+        a.inv.out[c] = nullptr;
+    }
+    inverse_setup(a.inv, width, height, in_bit_depth, in_full_range, in_matrix_coeffs, out_bit_depth);
+}
+
 int h2y_matrix_inverse(h2y_ctx *ctx, int width, int height, int in_bit_depth, int in_full_range, int in_matrix_coeffs,
                        int out_bit_depth, const uint16_t *const d_in[3], uint16_t *const d_out[3])
 {
@@ -1585,13 +1629,7 @@ int h2y_matrix_inverse(h2y_ctx *ctx, int width, int height, int in_bit_depth, in
         a.in[c] = d_in[c];
         a.out[c] = d_out[c];
     }
-    const clip_limits ic = make_clip(in_bit_depth, in_full_range);
-    a.npix = (uint32_t)width * (uint32_t)height;
-    a.d709 = in_matrix_coeffs == H2Y_MATRIX_BT709;
-    a.minVR = ic.minVR;
-    a.maxVR = ic.maxVR;
-    a.shift_right = in_bit_depth > out_bit_depth;
-    a.shift = a.shift_right ? in_bit_depth - out_bit_depth : out_bit_depth - in_bit_depth;
+    inverse_setup(a, width, height, in_bit_depth, in_full_range, in_matrix_coeffs, out_bit_depth);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     uint32_t blocks = (a.npix / 4 + 255) / 256;
     if (blocks > (uint32_t)ctx->n_cu * 16u) blocks = (uint32_t)ctx->n_cu * 16u;
@@ -1659,19 +1697,10 @@ int h2y_inverse_420(h2y_ctx *ctx, int width, int height, int in_bit_depth, int i
     /* one pass: both chroma planes upsampled inside the blocks (yuv2tiff.cpp:92-93,142-154: minCV 0, maxCV 2^depth - 1), then
      * matrix_inverse's pixel; the 4:4:4 chroma never reaches memory (k_inverse420, h2y_resample.hip) */
     inv420_args a;
-    a.up.src0 = d_in[1]; a.up.src1 = d_in[2]; a.up.dst0 = a.up.dst1 = nullptr;
-    a.up.width = width; a.up.height = height;
-    a.up.algorithm = algorithm;
-    a.up.fmin = 0.0f; a.up.fmax = (float)((1u << in_bit_depth) - 1u);
-    const clip_limits ic = make_clip(in_bit_depth, in_full_range);
-    a.inv.in[0] = d_in[0]; a.inv.in[1] = a.inv.in[2] = nullptr;
+    inverse420_setup(a, width, height, in_bit_depth, in_full_range, in_matrix_coeffs, out_bit_depth, algorithm);
+    a.up.src0 = d_in[1]; a.up.src1 = d_in[2];
+    a.inv.in[0] = d_in[0];
     for (int c = 0; c < 3; c++) a.inv.out[c] = d_out[c];
-    a.inv.npix = (uint32_t)width * (uint32_t)height;
-    a.inv.d709 = in_matrix_coeffs == H2Y_MATRIX_BT709;
-    a.inv.minVR = ic.minVR;
-    a.inv.maxVR = ic.maxVR;
-    a.inv.shift_right = in_bit_depth > out_bit_depth;
-    a.inv.shift = a.inv.shift_right ? in_bit_depth - out_bit_depth : out_bit_depth - in_bit_depth;
     ctx->b->n_ev = 0;
     HIP_TRY(ctx, hipEventRecord(ctx->b->ev[0][0], ctx->stream));
     HIP_TRY(ctx, h2y_launch_inverse420(ctx->stream, a));
@@ -1720,6 +1749,92 @@ int h2y_inverse_frame(h2y_ctx *ctx, int width, int height, int in_chroma_format_
     return H2Y_OK;
 }
 
+/* What h2y_inverse_batch and h2y_inverse_stream_open accept: the checks of h2y_inverse_420 (4:2:0) or h2y_matrix_inverse (4:4:4) */
+static int inverse_check(h2y_ctx *ctx, const inv_params &p)
+{
+    if (p.chroma != H2Y_CHROMA_444 && p.chroma != H2Y_CHROMA_420)
+        return fail(ctx, H2Y_EUNSUPPORTED, "inverse flow: input chroma_format_idc must be 3 (4:4:4) or 1 (4:2:0)");
+    if (p.chroma == H2Y_CHROMA_420) {
+        if (p.width < 2 || p.height < 2 || (p.width & 3) || (p.height & 1) || p.width > 32766 || p.height > 32766)
+            return fail(ctx, H2Y_EINVAL, "4:2:0 inverse: width a multiple of 4 and height even, up to 32766");
+    } else if (p.width < 1 || p.height < 1 || (uint64_t)p.width * p.height >= (1ull << 28))
+        return fail(ctx, H2Y_EINVAL, "bad picture size");
+    if (p.in_depth < 8 || p.in_depth > 16 || p.out_depth < 8 || p.out_depth > 16) return fail(ctx, H2Y_EINVAL, "bit depths must be 8..16");
+    if (p.matrix == H2Y_MATRIX_GBR) return fail(ctx, H2Y_EUNSUPPORTED, "matrix_coeffs 0 (GBR) has no inverse in the reference (it exits)");
+    return H2Y_OK;
+}
+
+int h2y_inverse_batch(h2y_ctx *ctx, int width, int height, int in_chroma_format_idc, int in_bit_depth, int in_full_range,
+                      int in_matrix_coeffs, int out_bit_depth, int algorithm, int n_frames, const uint16_t *const *d_in,
+                      uint16_t *const *d_out)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
+    const inv_params p{width, height, in_chroma_format_idc, in_bit_depth, in_full_range, in_matrix_coeffs, out_bit_depth, algorithm};
+    int rc = inverse_check(ctx, p);
+    if (rc) return rc;
+    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
+    if (!d_in || !d_out) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
+    const bool sub = in_chroma_format_idc == H2Y_CHROMA_420;
+    const uintptr_t align = sub ? 4 : 8; /* k_inverse420_batch: 4-byte accesses at least; k_inverse_batch: 8-byte ones */
+    for (int f = 0; f < n_frames; f++)
+        for (int c = 0; c < 3; c++) {
+            const uint16_t *i = d_in[3 * f + c], *o = d_out[3 * f + c];
+            if (!i || !o) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is null", f, c);
+            if (((uintptr_t)i | (uintptr_t)o) & (align - 1)) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is not %d-byte aligned", f, c, (int)align);
+        }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    /* the whole table is uploaded once, every launch reads its own part of it */
+    const size_t tb = (size_t)n_frames * sizeof(inv_frame);
+    rc = ensure(ctx, ctx->d_inv_frames, ctx->d_inv_cap, tb);
+    if (rc) return rc;
+    if (ctx->h_inv_cap < tb) {
+        if (ctx->h_inv_frames) HIP_TRY(ctx, hipHostFree(ctx->h_inv_frames));
+        ctx->h_inv_frames = nullptr;
+        ctx->h_inv_cap = 0;
+        hipError_t e = hipHostMalloc((void **)&ctx->h_inv_frames, tb, hipHostMallocDefault);
+        if (e != hipSuccess) return fail(ctx, H2Y_ENOMEM, "hipHostMalloc(%zu): %s", tb, hipGetErrorString(e));
+        ctx->h_inv_cap = tb;
+    }
+    for (int f = 0; f < n_frames; f++)
+        for (int c = 0; c < 3; c++) {
+            ctx->h_inv_frames[f].in[c] = d_in[3 * f + c];
+            ctx->h_inv_frames[f].out[c] = d_out[3 * f + c];
+        }
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_inv_frames, ctx->h_inv_frames, tb, hipMemcpyHostToDevice, ctx->stream));
+    inv420_args a;
+    inverse420_setup(a, width, height, in_bit_depth, in_full_range, in_matrix_coeffs, out_bit_depth, algorithm);
+    /* units of one frame: k_inverse420's tiles, or k_inverse's chunks of 256 quads (+ the npix % 4 single samples) */
+    const uint32_t n4 = a.inv.npix >> 2;
+    const uint32_t per_frame = sub ? (uint32_t)h2y_inverse420_tiles(width, height) : (n4 + (a.inv.npix & 3u) + 255) / 256;
+    const uint32_t max_grid = (uint32_t)ctx->n_cu * (sub ? 8u : 16u); /* as k_inverse420 (eight blocks of 256 per CU) and k_inverse */
+    int launches = 0;
+    for (int f0 = 0; f0 < n_frames; f0 += H2Y_INVERSE_FRAMES_PER_LAUNCH, launches++) {
+        const int nf = n_frames - f0 < H2Y_INVERSE_FRAMES_PER_LAUNCH ? n_frames - f0 : H2Y_INVERSE_FRAMES_PER_LAUNCH;
+        const uint64_t units = (uint64_t)nf * per_frame;
+        const int grid = (int)(units < max_grid ? units : max_grid);
+        /* launches past the last event pair are timed by it: it then spans them all */
+        const int e = launches < kMaxEvents ? launches : kMaxEvents - 1;
+        if (launches < kMaxEvents) HIP_TRY(ctx, hipEventRecord(ctx->b->ev[e][0], ctx->stream));
+        if (sub) HIP_TRY(ctx, h2y_launch_inverse420_batch(grid, ctx->stream, a, ctx->d_inv_frames + f0, nf));
+        else HIP_TRY(ctx, h2y_launch_inverse_batch(grid, ctx->stream, a.inv, ctx->d_inv_frames + f0, nf));
+        HIP_TRY(ctx, hipEventRecord(ctx->b->ev[e][1], ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->b->n_ev = launches < kMaxEvents ? launches : kMaxEvents;
+    float ms = 0.f;
+    for (int i = 0; i < ctx->b->n_ev; i++) {
+        float t = 0.f;
+        HIP_TRY(ctx, hipEventElapsedTime(&t, ctx->b->ev[i][0], ctx->b->ev[i][1]));
+        ms += t;
+    }
+    ctx->last_ms = ms;
+    ctx->last_launches = launches;
+    ctx->last_name = sub ? "k_inverse420_batch" : "k_inverse_batch";
+    ctx->last_variant = sub ? (algorithm ? "k_inverse420_batch<FIR>" : "k_inverse420_batch<REPLICATE>") : "k_inverse_batch";
+    return H2Y_OK;
+}
+
 /* ---- streaming pipeline ------------------------------------------------------
  * H2D of frame k+1, conversion of frame k and D2H of frame k-1 overlap: three streams, a ring of
  * pinned host slots the caller fills and drains in place.  Every frame is converted in the
@@ -1741,8 +1856,32 @@ static void stream_free(h2y_ctx *ctx)
     if (ctx->s_d2h) (void)hipStreamDestroy(ctx->s_d2h);
     ctx->s_h2d = ctx->s_d2h = nullptr;
     ctx->streaming = false;
+    ctx->s_inverse = false;
     ctx->s_head = ctx->s_tail = 0;
     ctx->s_lent = -1;
+}
+
+/* the ring's streams and `depth` slots: pinned input / output and their device twins */
+static int stream_alloc(h2y_ctx *ctx, int depth, size_t in_bytes, size_t h_out_bytes, size_t d_out_bytes)
+{
+    ctx->ss.assign(depth, h2y_ctx::stream_slot());
+    ctx->streaming = true;
+    hipError_t e = hipStreamCreateWithFlags(&ctx->s_h2d, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->s_d2h, hipStreamNonBlocking);
+    for (auto &s : ctx->ss) {
+        if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_in, in_bytes, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_out, h_out_bytes, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipMalloc((void **)&s.d_in, in_bytes);
+        if (e == hipSuccess) e = hipMalloc((void **)&s.d_out, d_out_bytes);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&s.ev_h2d, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&s.ev_conv, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&s.ev_done, hipEventDisableTiming);
+    }
+    if (e != hipSuccess) {
+        stream_free(ctx);
+        return fail(ctx, H2Y_ENOMEM, "stream buffers: %s", hipGetErrorString(e));
+    }
+    return H2Y_OK;
 }
 
 int h2y_stream_open(h2y_ctx *ctx, const h2y_desc *d, int depth)
@@ -1759,23 +1898,74 @@ int h2y_stream_open(h2y_ctx *ctx, const h2y_desc *d, int depth)
     const size_t pb = h2y_plane_bytes(d), ob = h2y_frame_bytes(d);
     ctx->s_plane_al = (pb + 255) & ~(size_t)255;
     ctx->s_desc = *d;
-    ctx->ss.assign(depth, h2y_ctx::stream_slot());
-    ctx->streaming = true;
-    hipError_t e = hipStreamCreateWithFlags(&ctx->s_h2d, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->s_d2h, hipStreamNonBlocking);
-    for (auto &s : ctx->ss) {
-        if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_in, 3 * ctx->s_plane_al, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_out, ob, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipMalloc((void **)&s.d_in, 3 * ctx->s_plane_al);
-        if (e == hipSuccess) e = hipMalloc((void **)&s.d_out, ob);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&s.ev_h2d, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&s.ev_conv, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&s.ev_done, hipEventDisableTiming);
+    for (int c = 0; c < 3; c++) ctx->s_in_off[c] = c * ctx->s_plane_al;
+    return stream_alloc(ctx, depth, 3 * ctx->s_plane_al, ob, ob);
+}
+
+/* The same ring for the .yuv -> G,B,R flow: a slot's input is Y, Cb/Dz, Cr/Dx one after the other (each 256-byte aligned; one
+ * H2D copy), its output G | B | R, width x height each, contiguous on the host (one D2H copy where the device planes are too) */
+int h2y_inverse_stream_open(h2y_ctx *ctx, int width, int height, int in_chroma_format_idc, int in_bit_depth, int in_full_range,
+                            int in_matrix_coeffs, int out_bit_depth, int algorithm, int depth)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is already open");
+    const inv_params p{width, height, in_chroma_format_idc, in_bit_depth, in_full_range, in_matrix_coeffs, out_bit_depth, algorithm};
+    int rc = inverse_check(ctx, p);
+    if (rc) return rc;
+    if (depth < 2 || depth > 16) return fail(ctx, H2Y_EINVAL, "depth must be 2..16");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t pb = (size_t)width * height * sizeof(uint16_t), pb_al = (pb + 255) & ~(size_t)255;
+    const size_t cb = in_chroma_format_idc == H2Y_CHROMA_420 ? (size_t)(width >> 1) * (height >> 1) * sizeof(uint16_t) : pb;
+    const size_t cb_al = (cb + 255) & ~(size_t)255;
+    ctx->s_in_off[0] = 0;
+    ctx->s_in_off[1] = pb_al;
+    ctx->s_in_off[2] = pb_al + cb_al;
+    ctx->s_in_bytes = pb_al + cb_al + cb;
+    ctx->s_out_stride = (pb & 15) ? pb_al : pb; /* 4:2:0 planes are always a multiple of 16 bytes */
+    ctx->s_inv = p;
+    rc = stream_alloc(ctx, depth, ctx->s_in_bytes, 3 * pb, 2 * ctx->s_out_stride + pb);
+    if (rc) return rc;
+    ctx->s_inverse = true;
+    return H2Y_OK;
+}
+
+/* one frame of an inverse stream: H2D of its planes, k_inverse420 / k_inverse on the context's stream, D2H of G, B, R */
+static int inverse_stream_submit(h2y_ctx *ctx, int slot)
+{
+    h2y_ctx::stream_slot &s = ctx->ss[slot];
+    const inv_params &p = ctx->s_inv;
+    const size_t pb = (size_t)p.width * p.height * sizeof(uint16_t), so = ctx->s_out_stride;
+    HIP_TRY(ctx, hipMemcpyAsync(s.d_in, s.h_in, ctx->s_in_bytes, hipMemcpyHostToDevice, ctx->s_h2d));
+    HIP_TRY(ctx, hipEventRecord(s.ev_h2d, ctx->s_h2d));
+    HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s.ev_h2d, 0));
+    /* every plane starts on a 16-byte boundary here: the single-frame kernels' wide accesses are safe */
+    inv420_args a;
+    inverse420_setup(a, p.width, p.height, p.in_depth, p.in_full_range, p.matrix, p.out_depth, p.algorithm);
+    for (int c = 0; c < 3; c++) {
+        a.inv.in[c] = s.d_in + ctx->s_in_off[c];
+        a.inv.out[c] = reinterpret_cast<char *>(s.d_out) + c * so;
     }
-    if (e != hipSuccess) {
-        stream_free(ctx);
-        return fail(ctx, H2Y_ENOMEM, "stream buffers: %s", hipGetErrorString(e));
+    if (p.chroma == H2Y_CHROMA_420) {
+        a.up.src0 = static_cast<const uint16_t *>(a.inv.in[1]);
+        a.up.src1 = static_cast<const uint16_t *>(a.inv.in[2]);
+        a.inv.in[1] = a.inv.in[2] = nullptr;
+        HIP_TRY(ctx, h2y_launch_inverse420(ctx->stream, a));
+    } else {
+        uint32_t blocks = (a.inv.npix / 4 + 255) / 256; /* as h2y_matrix_inverse */
+        if (blocks > (uint32_t)ctx->n_cu * 16u) blocks = (uint32_t)ctx->n_cu * 16u;
+        if (blocks < 1) blocks = 1;
+        HIP_TRY(ctx, h2y_launch_inverse((int)blocks, ctx->stream, a.inv));
     }
+    HIP_TRY(ctx, hipEventRecord(s.ev_conv, ctx->stream));
+    HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_d2h, s.ev_conv, 0));
+    if (so == pb) HIP_TRY(ctx, hipMemcpyAsync(s.h_out, s.d_out, 3 * pb, hipMemcpyDeviceToHost, ctx->s_d2h));
+    else
+        for (int c = 0; c < 3; c++)
+            HIP_TRY(ctx, hipMemcpyAsync(reinterpret_cast<char *>(s.h_out) + c * pb, reinterpret_cast<char *>(s.d_out) + c * so, pb,
+                                        hipMemcpyDeviceToHost, ctx->s_d2h));
+    HIP_TRY(ctx, hipEventRecord(s.ev_done, ctx->s_d2h));
+    s.state = 2;
+    ctx->s_tail = (slot + 1) % (int)ctx->ss.size();
     return H2Y_OK;
 }
 
@@ -1787,7 +1977,7 @@ int h2y_stream_input(h2y_ctx *ctx, void *planes[3])
     if (s.state == 1) { /* asked twice without a submit: same buffers again */
     } else if (s.state != 0) return fail(ctx, H2Y_EINVAL, "all %d slots are in flight: take an output first", (int)ctx->ss.size());
     s.state = 1;
-    for (int c = 0; c < 3; c++) planes[c] = s.h_in + c * ctx->s_plane_al;
+    for (int c = 0; c < 3; c++) planes[c] = s.h_in + ctx->s_in_off[c];
     return H2Y_OK;
 }
 
@@ -1800,6 +1990,7 @@ int h2y_stream_submit(h2y_ctx *ctx)
     if (s.state != 1) return fail(ctx, H2Y_EINVAL, "nothing to submit: call h2y_stream_input first");
     const h2y_desc *d = &ctx->s_desc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (ctx->s_inverse) return inverse_stream_submit(ctx, slot);
     const size_t pb = h2y_plane_bytes(d), ob = h2y_frame_bytes(d);
     frame_io io;
     for (int c = 0; c < 3; c++) io.in[c] = s.d_in + c * ctx->s_plane_al;

@@ -183,6 +183,12 @@ struct inv420_args { /* k_inverse420: Subsample420to444 of both chroma planes an
     inverse_args inv; /* in[0] = the luma plane (in[1], in[2] unused), out[3] = G, B, R */
 };
 
+/* one frame of k_inverse420_batch / k_inverse_batch: Y, Cb/Dz, Cr/Dx in (chroma at half size each way for 4:2:0), G, B, R out */
+struct inv_frame {
+    const uint16_t *in[3];
+    uint16_t *out[3];
+};
+
 /* k_fir_fused: lanes of a wave that own chroma columns (the others, half on either side, only feed the horizontal taps):
  * a strip is 4 x this many picture columns */
 #ifndef H2Y_FF_OWN_LANES
@@ -208,6 +214,10 @@ static inline uint32_t h2y_firf_vblock(uint32_t b) { return (b & ~6u) | ((b & 2u
 hipError_t h2y_launch_fir_fused(int in_kind, int mode, bool ident, bool lut16, int grid, hipStream_t st, const firf_args &a);
 hipError_t h2y_launch_up444(hipStream_t st, const up_args &a);
 hipError_t h2y_launch_inverse420(hipStream_t st, const inv420_args &a);
+/* the batch forms: frames[n_frames] in device memory; every frame takes base's sizes and arithmetic, its own planes */
+hipError_t h2y_launch_inverse420_batch(int grid, hipStream_t st, const inv420_args &base, const inv_frame *frames, int n_frames);
+hipError_t h2y_launch_inverse_batch(int grid, hipStream_t st, const inverse_args &base, const inv_frame *frames, int n_frames);
+int h2y_inverse420_tiles(int width, int height); /* k_inverse420(_batch) tiles of one frame */
 hipError_t h2y_launch_box420(hipStream_t st, const uint16_t *src, uint16_t *dst, int W, int H);
 
 #endif

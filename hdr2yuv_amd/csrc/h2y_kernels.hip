@@ -13,6 +13,7 @@
  *   k_fir420       Subsample444to420_FIR  convert.cpp:261-383 + write_yuv clamp
  *   k_box420       Subsample444to420_box  convert.cpp:91-172 (stage entry only)
  *   k_inverse      matrix_inverse()       convert.cpp:1320-1867
+ *   k_inverse_batch  the same over many frames in one launch (h2y_inverse_batch)
  *   k_stats_final  (int) floor/ceiling    common.cpp:135-136, and the check of
  *                  the values the fused kernel assumed against the ones it measured
  *
@@ -1705,30 +1706,57 @@ __global__ __launch_bounds__(256) void k_fir420(fir_args a)
  * (the test at convert.cpp:1391 compares matrix_coeffs with booleans), everything else Y'DzDx; the
  * video-range clamp always runs, with the input picture's limits.
  */
+/* samples 4i .. 4i+3 of every plane */
+__device__ __forceinline__ void inverse_quad(const inverse_args &a, uint32_t i)
+{
+    const u32x2 y = gload<u32x2>(a.in[0], i), cb = gload<u32x2>(a.in[1], i), cr = gload<u32x2>(a.in[2], i);
+    uint32_t G[4], B[4], R[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const uint32_t wy = j & 2 ? y.y : y.x, wb = j & 2 ? cb.y : cb.x, wr = j & 2 ? cr.y : cr.x;
+        inverse_pixel(a, j & 1 ? wy >> 16 : wy & 0xFFFFu, j & 1 ? wb >> 16 : wb & 0xFFFFu, j & 1 ? wr >> 16 : wr & 0xFFFFu, G[j], B[j], R[j]);
+    }
+    gstore<u32x2>(a.out[0], i, u32x2{G[0] | (G[1] << 16), G[2] | (G[3] << 16)});
+    gstore<u32x2>(a.out[1], i, u32x2{B[0] | (B[1] << 16), B[2] | (B[3] << 16)});
+    gstore<u32x2>(a.out[2], i, u32x2{R[0] | (R[1] << 16), R[2] | (R[3] << 16)});
+}
+
+/* sample i of every plane (one of the last npix % 4) */
+__device__ __forceinline__ void inverse_one(const inverse_args &a, uint32_t i)
+{
+    uint32_t G, B, R;
+    inverse_pixel(a, gload<uint16_t>(a.in[0], i), gload<uint16_t>(a.in[1], i), gload<uint16_t>(a.in[2], i), G, B, R);
+    gstore<uint16_t>(a.out[0], i, (uint16_t)G);
+    gstore<uint16_t>(a.out[1], i, (uint16_t)B);
+    gstore<uint16_t>(a.out[2], i, (uint16_t)R);
+}
+
 __global__ __launch_bounds__(256) void k_inverse(inverse_args a)
 {
     const uint32_t n4 = a.npix >> 2;
-    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
-        const u32x2 y = gload<u32x2>(a.in[0], i), cb = gload<u32x2>(a.in[1], i), cr = gload<u32x2>(a.in[2], i);
-        uint32_t G[4], B[4], R[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const uint32_t wy = j & 2 ? y.y : y.x, wb = j & 2 ? cb.y : cb.x, wr = j & 2 ? cr.y : cr.x;
-            inverse_pixel(a, j & 1 ? wy >> 16 : wy & 0xFFFFu, j & 1 ? wb >> 16 : wb & 0xFFFFu, j & 1 ? wr >> 16 : wr & 0xFFFFu, G[j], B[j], R[j]);
-        }
-        gstore<u32x2>(a.out[0], i, u32x2{G[0] | (G[1] << 16), G[2] | (G[3] << 16)});
-        gstore<u32x2>(a.out[1], i, u32x2{B[0] | (B[1] << 16), B[2] | (B[3] << 16)});
-        gstore<u32x2>(a.out[2], i, u32x2{R[0] | (R[1] << 16), R[2] | (R[3] << 16)});
-    }
+    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) inverse_quad(a, i);
     /* the last npix % 4 samples */
     const uint32_t tail = a.npix & 3u;
-    if (blockIdx.x == 0 && threadIdx.x < tail) {
-        const uint32_t i = (n4 << 2) + threadIdx.x;
-        uint32_t G, B, R;
-        inverse_pixel(a, gload<uint16_t>(a.in[0], i), gload<uint16_t>(a.in[1], i), gload<uint16_t>(a.in[2], i), G, B, R);
-        gstore<uint16_t>(a.out[0], i, (uint16_t)G);
-        gstore<uint16_t>(a.out[1], i, (uint16_t)B);
-        gstore<uint16_t>(a.out[2], i, (uint16_t)R);
+    if (blockIdx.x == 0 && threadIdx.x < tail) inverse_one(a, (n4 << 2) + threadIdx.x);
+}
+
+/* k_inverse over n_frames frames of one size in one launch (h2y_inverse_batch): grid-stride over (frame, chunk of 256 quads)
+ * units, the last chunk of a frame also taking its npix % 4 single samples.  The frame is block-uniform: its plane pointers
+ * are scalar loads from the table.  Planes 8-byte aligned, as for k_inverse. */
+__global__ __launch_bounds__(256) void k_inverse_batch(inverse_args base, const inv_frame *__restrict__ frames, int n_frames)
+{
+    const uint32_t n4 = base.npix >> 2, tail = base.npix & 3u;
+    const uint32_t chunks = (n4 + tail + 255) / 256, units = (uint32_t)n_frames * chunks;
+    for (uint32_t unit = blockIdx.x; unit < units; unit += gridDim.x) {
+        const uint32_t f = unit / chunks, i = (unit - f * chunks) * 256 + threadIdx.x;
+        const inv_frame fr = frames[f];
+        inverse_args a = base;
+        for (int c = 0; c < 3; c++) {
+            a.in[c] = fr.in[c];
+            a.out[c] = fr.out[c];
+        }
+        if (i < n4) inverse_quad(a, i);
+        else if (i < n4 + tail) inverse_one(a, (n4 << 2) + (i - n4));
     }
 }
 
@@ -1861,6 +1889,12 @@ hipError_t h2y_launch_stats_final(int n_frames, hipStream_t st, const final_args
 hipError_t h2y_launch_inverse(int grid, hipStream_t st, const inverse_args &a)
 {
     hipLaunchKernelGGL(k_inverse, dim3(grid), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t h2y_launch_inverse_batch(int grid, hipStream_t st, const inverse_args &base, const inv_frame *frames, int n_frames)
+{
+    hipLaunchKernelGGL(k_inverse_batch, dim3(grid), dim3(256), 0, st, base, frames, n_frames);
     return hipGetLastError();
 }
 

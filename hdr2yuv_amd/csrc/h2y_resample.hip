@@ -12,6 +12,9 @@
  *             intermediate in LDS), the 4:4:4 chroma never written: 3 B/px read, 6 B/px written, against 17 B/px for
  *             k_up444 followed by k_inverse.
  *
+ *   k_inverse420_batch  the same over many frames in one launch (h2y_inverse_batch): (frame, tile) units dealt over a
+ *             persistent grid, the frames' plane pointers from a table in device memory.
+ *
  * HBM-bound stencil work (0.5 B/px read, 2 B/px written per plane): no MFMA.  Built -ffp-contract=off: the
  * products and sums round one by one, as the reference's do.
  */
@@ -91,17 +94,14 @@ __global__ __launch_bounds__(256) void k_up444(up_args a)
 #define IV_SH (IV_TH + 6)
 typedef uint32_t iv_u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t iv_u32x4 __attribute__((ext_vector_type(4)));
+/* One tile of k_inverse420 / k_inverse420_batch.  vec16: the luma and the G, B, R planes all start on a 16-byte boundary (the
+ * 16-byte loads and stores of the last stage are taken only then; otherwise 4-byte ones) */
 template <bool FIR>
-__global__ __launch_bounds__(256) void k_inverse420(inv420_args a)
+__device__ __forceinline__ void inverse420_tile(const inv420_args &a, int tile, int tiles_x, bool vec16,
+                                                float (&s_src)[2][FIR ? IV_SH : 1][IV_LW], float (&s_mid)[2][FIR ? 2 * IV_TH : 1][IV_LW])
 {
     const up_args &u = a.up;
     const int W = u.width, w2 = W >> 1, h2 = u.height >> 1;
-    const int tiles_x = (w2 + UP_TW - 1) / UP_TW, tiles = tiles_x * ((h2 + IV_TH - 1) / IV_TH);
-    /* both stages' samples are kept as floats in LDS (every one of them is an integer below 2^16: exact), converted once where
-     * they are produced instead of at each of their seven (vertical) or six (horizontal) uses */
-    __shared__ __attribute__((aligned(16))) float s_src[2][FIR ? IV_SH : 1][IV_LW];
-    __shared__ __attribute__((aligned(16))) float s_mid[2][FIR ? 2 * IV_TH : 1][IV_LW];
-    for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
     const int ty = tile / tiles_x, c0 = (tile - ty * tiles_x) * UP_TW, r0 = ty * IV_TH;
     if (FIR) {
         __syncthreads(); /* the previous tile's last stage has read s_mid */
@@ -177,7 +177,7 @@ __global__ __launch_bounds__(256) void k_inverse420(inv420_args a)
         const size_t p0 = (size_t)y * w2 + x; /* index of the first pixel pair; W a multiple of 4: x + 3 < w2 or x + 1 < w2 */
         const bool whole = x + 3 < w2;
         uint32_t yy[4];
-        if (whole && ((p0 & 3u) == 0)) {
+        if (vec16 && whole && ((p0 & 3u) == 0)) {
             const iv_u32x4 v = reinterpret_cast<const iv_u32x4 *>(a.inv.in[0])[p0 >> 2];
             yy[0] = v.x; yy[1] = v.y; yy[2] = v.z; yy[3] = v.w;
         } else {
@@ -192,7 +192,7 @@ __global__ __launch_bounds__(256) void k_inverse420(inv420_args a)
             inverse_pixel(a.inv, yy[q] >> 16, co[0][q], co[1][q], g1, b1, r1);
             G[q] = g0 | (g1 << 16); B[q] = b0 | (b1 << 16); R[q] = r0_ | (r1 << 16);
         }
-        if (whole && ((p0 & 3u) == 0)) {
+        if (vec16 && whole && ((p0 & 3u) == 0)) {
             reinterpret_cast<iv_u32x4 *>(a.inv.out[0])[p0 >> 2] = iv_u32x4{G[0], G[1], G[2], G[3]};
             reinterpret_cast<iv_u32x4 *>(a.inv.out[1])[p0 >> 2] = iv_u32x4{B[0], B[1], B[2], B[3]};
             reinterpret_cast<iv_u32x4 *>(a.inv.out[2])[p0 >> 2] = iv_u32x4{R[0], R[1], R[2], R[3]};
@@ -206,6 +206,42 @@ __global__ __launch_bounds__(256) void k_inverse420(inv420_args a)
                 }
         }
     }
+}
+
+template <bool FIR>
+__global__ __launch_bounds__(256) void k_inverse420(inv420_args a)
+{
+    const int w2 = a.up.width >> 1, h2 = a.up.height >> 1;
+    const int tiles_x = (w2 + UP_TW - 1) / UP_TW, tiles = tiles_x * ((h2 + IV_TH - 1) / IV_TH);
+    /* both stages' samples are kept as floats in LDS (every one of them is an integer below 2^16: exact), converted once where
+     * they are produced instead of at each of their seven (vertical) or six (horizontal) uses */
+    __shared__ __attribute__((aligned(16))) float s_src[2][FIR ? IV_SH : 1][IV_LW];
+    __shared__ __attribute__((aligned(16))) float s_mid[2][FIR ? 2 * IV_TH : 1][IV_LW];
+    for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) inverse420_tile<FIR>(a, tile, tiles_x, true, s_src, s_mid);
+}
+
+/* k_inverse420 over n_frames frames of one size in one launch: a persistent grid deals (frame, tile) units over all of them, so
+ * that no frame boundary leaves CUs idle.  The frame of a unit is block-uniform: its six plane pointers are scalar loads from
+ * the table (__restrict__ const: nothing the kernel stores can alias it).  Unlike k_inverse420 the planes need only be 4-byte
+ * aligned: the 16-byte accesses are taken per frame, where its four full-size planes allow them. */
+template <bool FIR>
+__global__ __launch_bounds__(256) void k_inverse420_batch(inv420_args base, const inv_frame *__restrict__ frames, int n_frames)
+{
+    const int w2 = base.up.width >> 1, h2 = base.up.height >> 1;
+    const int tiles_x = (w2 + UP_TW - 1) / UP_TW, tiles = tiles_x * ((h2 + IV_TH - 1) / IV_TH);
+    __shared__ __attribute__((aligned(16))) float s_src[2][FIR ? IV_SH : 1][IV_LW];
+    __shared__ __attribute__((aligned(16))) float s_mid[2][FIR ? 2 * IV_TH : 1][IV_LW];
+    const int units = n_frames * tiles;
+    for (int unit = blockIdx.x; unit < units; unit += gridDim.x) {
+        const int f = unit / tiles, tile = unit - f * tiles;
+        const inv_frame fr = frames[f];
+        inv420_args a = base;
+        a.up.src0 = fr.in[1];
+        a.up.src1 = fr.in[2];
+        a.inv.in[0] = fr.in[0];
+        for (int c = 0; c < 3; c++) a.inv.out[c] = fr.out[c];
+        const bool vec16 = (((uintptr_t)fr.in[0] | (uintptr_t)fr.out[0] | (uintptr_t)fr.out[1] | (uintptr_t)fr.out[2]) & 15u) == 0;
+        inverse420_tile<FIR>(a, tile, tiles_x, vec16, s_src, s_mid);
     }
 }
 
@@ -217,6 +253,19 @@ hipError_t h2y_launch_inverse420(hipStream_t st, const inv420_args &a)
     if (a.up.algorithm == 0) hipLaunchKernelGGL(k_inverse420<false>, grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL(k_inverse420<true>, grid, dim3(256), 0, st, a);
     return hipGetLastError();
+}
+
+hipError_t h2y_launch_inverse420_batch(int grid, hipStream_t st, const inv420_args &base, const inv_frame *frames, int n_frames)
+{
+    if (base.up.algorithm == 0) hipLaunchKernelGGL(k_inverse420_batch<false>, dim3(grid), dim3(256), 0, st, base, frames, n_frames);
+    else hipLaunchKernelGGL(k_inverse420_batch<true>, dim3(grid), dim3(256), 0, st, base, frames, n_frames);
+    return hipGetLastError();
+}
+
+int h2y_inverse420_tiles(int width, int height)
+{
+    const int w2 = width >> 1, h2 = height >> 1;
+    return ((w2 + UP_TW - 1) / UP_TW) * ((h2 + IV_TH - 1) / IV_TH);
 }
 
 hipError_t h2y_launch_up444(hipStream_t st, const up_args &a)

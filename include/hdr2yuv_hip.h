@@ -226,6 +226,22 @@ int h2y_inverse_frame(h2y_ctx *ctx, int width, int height, int in_chroma_format_
                       int in_matrix_coeffs, int out_bit_depth, int algorithm, const uint16_t *const in_planes[3],
                       uint16_t *const out_planes[3]);
 
+/* Frames per launch of h2y_inverse_batch: longer batches are split into launches of at most this many frames. */
+#define H2Y_INVERSE_FRAMES_PER_LAUNCH 64
+
+/* The .yuv -> G,B,R flow of h2y_inverse_420 (in_chroma_format_idc 1) or h2y_matrix_inverse (3) on n_frames frames of one size in
+ * one call, device buffers: what main() does per frame between read_planar_integer_file() (hdr2yuv.cpp:582-656) and write_tiff()
+ * (hdr2yuv.cpp:818-819), for a whole sequence.
+ *   d_in[f*3 + c]   Y, Cb/Dz, Cr/Dx of frame f (chroma width/2 x height/2 for in_chroma_format_idc 1)
+ *   d_out[f*3 + c]  G, B, R of frame f, width x height each
+ * The arrays of pointers themselves are host memory; each frame's planes may lie anywhere.  Limits as the single-frame entries:
+ * width a multiple of 4 and height even for 4:2:0, planes 4-byte (4:2:0) or 8-byte (4:4:4) aligned.  The frames run in
+ * launches of up to H2Y_INVERSE_FRAMES_PER_LAUNCH (k_inverse420_batch / k_inverse_batch: every launch deals all its frames'
+ * tiles over one persistent grid); h2y_last_kernel_ms() sums them.  Synchronous: every frame is final on return. */
+int h2y_inverse_batch(h2y_ctx *ctx, int width, int height, int in_chroma_format_idc, int in_bit_depth, int in_full_range,
+                      int in_matrix_coeffs, int out_bit_depth, int algorithm, int n_frames, const uint16_t *const *d_in,
+                      uint16_t *const *d_out);
+
 /* ---- host <-> device pipeline --------------------------------------------
  * The reference reads a frame, converts it and appends it to the .yuv, one after the other
  * (hdr2yuv.cpp:582-656 reader, :797-928, tiff.cpp:457-551 writer).  Here the upload of frame
@@ -243,18 +259,26 @@ int h2y_inverse_frame(h2y_ctx *ctx, int width, int height, int in_chroma_format_
  * returns stays valid until the next h2y_stream_output / h2y_stream_close.  Frames come out in
  * submission order.  No other entry of the context may be used while a stream is open. */
 int h2y_stream_open(h2y_ctx *ctx, const h2y_desc *d, int depth /* 2..16 slots */);
+/* The same ring for the .yuv -> G,B,R flow (h2y_inverse_frame's arguments; hdr2yuv.cpp:818-819 frame after frame): each slot
+ * does one H2D copy of its three input planes, the kernel, one D2H copy of its three output planes.  h2y_stream_input hands out
+ * Y, Cb/Dz, Cr/Dx (chroma width/2 x height/2 for in_chroma_format_idc 1, else width x height), h2y_stream_output returns
+ * G | B | R, width x height uint16 each, contiguous in that order.  h2y_stream_submit / _close as above; while it is open,
+ * h2y_stream_open and every other entry are refused, as they are while a forward stream is open. */
+int h2y_inverse_stream_open(h2y_ctx *ctx, int width, int height, int in_chroma_format_idc, int in_bit_depth, int in_full_range,
+                            int in_matrix_coeffs, int out_bit_depth, int algorithm, int depth /* 2..16 slots */);
 int h2y_stream_input(h2y_ctx *ctx, void *planes[3]);
 int h2y_stream_submit(h2y_ctx *ctx);
 int h2y_stream_output(h2y_ctx *ctx, const uint16_t **yuv);
 int h2y_stream_close(h2y_ctx *ctx);
 
-/* Timing of the last h2y_convert_batch*() call measured with HIP events on
+/* Timing of the last h2y_convert_batch*() (or h2y_inverse_*) call measured with HIP events on
  * the stream the kernels ran on: total ms over the main kernels and how many
  * launches that covered. */
 int h2y_last_kernel_ms(const h2y_ctx *ctx, float *ms, int *launches);
 
 /* Name of the kernel those launches ran ("k_fused", "k_fused_t1", "k_fused_lut16",
- * "k_fused_narrow"): the name to look for in a rocprofv3 kernel trace. */
+ * "k_fused_narrow"; of the inverse entries "k_inverse", "k_inverse420", "k_inverse_batch", "k_inverse420_batch"): the name to
+ * look for in a rocprofv3 kernel trace. */
 const char *h2y_last_kernel_name(const h2y_ctx *ctx);
 /* The same with its template arguments and launch shape, e.g. "k_fused_t1<F32,420BOX,YCBCR,PQ_IDENT> groups=8 xcd=1";
  * "+k_fir420" after the '>' when the chroma went through the two-pass FIR form.  Tests assert on it: which
