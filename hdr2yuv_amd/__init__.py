@@ -11,6 +11,7 @@ from .api import (  # noqa: F401
     CHROMA_420,
     CHROMA_444,
     H2YDesc,
+    H2YDpxInfo,
     H2YError,
     MATRIX_BT2020NC,
     MATRIX_BT709,
@@ -30,5 +31,6 @@ from .api import (  # noqa: F401
     library_path,
     load_library,
     make_desc,
+    parse_dpx,
     set_library_path,
 )

@@ -29,7 +29,7 @@ EXPORTS = [
     "h2y_last_error", "h2y_ctx_set_stream", "h2y_convert_frame", "h2y_convert_batch", "h2y_convert_batch_enqueue",
     "h2y_batch_finish", "h2y_pic_stats", "h2y_matrix_convert", "h2y_subsample_420", "h2y_last_kernel_ms", "h2y_last_kernel_name", "h2y_last_kernel_variant",
     "h2y_matrix_inverse", "h2y_upsample_444", "h2y_inverse_420", "h2y_inverse_frame", "h2y_ctx_set_option", "h2y_stream_open", "h2y_stream_input", "h2y_stream_submit", "h2y_stream_output", "h2y_stream_close",
-    "h2y_inverse_batch", "h2y_inverse_stream_open",
+    "h2y_inverse_batch", "h2y_inverse_stream_open", "h2y_dpx_parse", "h2y_dpx_decode_batch", "h2y_dpx_stream_open",
 ]
 
 
@@ -52,6 +52,19 @@ class H2YDesc(C.Structure):
         ("chroma_resampler_type", C.c_int32), ("stats_override", C.c_int32),
         ("floor", C.c_int32 * 3), ("ceiling", C.c_int32 * 3),
     ]
+
+
+class H2YDpxInfo(C.Structure):
+    """h2y_dpx_info, include/hdr2yuv_hip.h: what h2y_dpx_parse read from a DPX header."""
+
+    _fields_ = [
+        ("width", C.c_int32), ("height", C.c_int32), ("bit_size", C.c_int32), ("swap", C.c_int32),
+        ("data_offset", C.c_uint64), ("payload_bytes", C.c_uint64),
+    ]
+
+    def __repr__(self):
+        return (f"H2YDpxInfo(width={self.width}, height={self.height}, bit_size={self.bit_size}, swap={self.swap}, "
+                f"data_offset={self.data_offset}, payload_bytes={self.payload_bytes})")
 
 
 def make_desc(width, height, *, sample=SAMPLE_F32, src_depth=32, dst_depth=10, src_transfer=TRANSFER_LINEAR,
@@ -177,6 +190,12 @@ def load_library():
     L.h2y_inverse_batch.argtypes = [C.c_void_p] + [C.c_int] * 9 + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.h2y_inverse_stream_open.restype = C.c_int
     L.h2y_inverse_stream_open.argtypes = [C.c_void_p] + [C.c_int] * 9
+    L.h2y_dpx_parse.restype = C.c_int
+    L.h2y_dpx_parse.argtypes = [C.c_void_p, C.c_size_t, C.c_uint64, C.POINTER(H2YDpxInfo), C.POINTER(C.c_char_p)]
+    L.h2y_dpx_decode_batch.restype = C.c_int
+    L.h2y_dpx_decode_batch.argtypes = [C.c_void_p, C.POINTER(H2YDpxInfo), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.h2y_dpx_stream_open.restype = C.c_int
+    L.h2y_dpx_stream_open.argtypes = [C.c_void_p, C.POINTER(H2YDesc), C.POINTER(H2YDpxInfo), C.c_int]
     L.h2y_stream_open.restype = C.c_int
     L.h2y_stream_open.argtypes = [C.c_void_p, C.POINTER(H2YDesc), C.c_int]
     L.h2y_stream_input.restype = C.c_int
@@ -205,6 +224,18 @@ def desc_check(d: H2YDesc):
     why = C.c_char_p()
     rc = load_library().h2y_desc_check(C.byref(d), C.byref(why))
     return rc, (why.value or b"").decode()
+
+
+def parse_dpx(header_bytes: bytes, file_bytes: int) -> H2YDpxInfo:
+    """h2y_dpx_parse on the host (no device needed): header_bytes = the file's first bytes (2048 at least), file_bytes = its
+    size.  Raises ValueError with the library's reason where the file is refused."""
+    buf = bytes(header_bytes)
+    info = H2YDpxInfo()
+    why = C.c_char_p()
+    rc = load_library().h2y_dpx_parse(buf, len(buf), int(file_bytes), C.byref(info), C.byref(why))
+    if rc != H2Y_OK:
+        raise ValueError((why.value or b"").decode())
+    return info
 
 
 def _np_dtype(sample):
@@ -354,24 +385,49 @@ class Context:
         self._check(self.lib.h2y_inverse_batch(self.h, width, height, in_chroma, in_depth, in_full_range, in_matrix, out_depth, algorithm,
                                                n, ins, outs))
 
+    def dpx_decode_batch(self, info: H2YDpxInfo, payloads, planes_out) -> None:
+        """DPX payloads on the device (payloads[f]: info.payload_bytes each) -> float planes planes_out[f] = (G, B, R), tensors or
+        pointers: dpx_read()'s per-pixel loop and the demux, many frames per launch."""
+        n = len(payloads)
+        if len(planes_out) != n:
+            raise ValueError("payloads and planes_out differ in length")
+        pay = (C.c_void_p * n)(*[self._ptr(p) for p in payloads])
+        outs = (C.c_void_p * (3 * n))()
+        for f in range(n):
+            for c in range(3):
+                outs[3 * f + c] = self._ptr(planes_out[f][c])
+        self._check(self.lib.h2y_dpx_decode_batch(self.h, C.byref(info), n, pay, outs))
+
     # ---- host <-> device pipeline -----------------------------------------------------------
     def stream_open(self, d, depth=3) -> None:
         self._check(self.lib.h2y_stream_open(self.h, C.byref(d), depth))
         self._stream_desc = d
         self._stream_inverse = None
+        self._stream_dpx = None
+
+    def dpx_stream_open(self, d, info: H2YDpxInfo, depth=3) -> None:
+        """The forward ring on DPX payloads: stream_input gives one uint8 view of the pinned payload (info.payload_bytes) to fill
+        with the file's bytes from info.data_offset on; stream_output gives the .yuv frame as on a forward stream."""
+        self._check(self.lib.h2y_dpx_stream_open(self.h, C.byref(d), C.byref(info), depth))
+        self._stream_desc = d
+        self._stream_inverse = None
+        self._stream_dpx = int(info.payload_bytes)
 
     def inverse_stream_open(self, width, height, in_chroma, in_depth, in_full_range, in_matrix, out_depth, algorithm, depth=3) -> None:
         """The pinned ring for the .yuv -> G,B,R flow: stream_input gives Y, Cb/Dz, Cr/Dx, stream_output G, B, R."""
         self._check(self.lib.h2y_inverse_stream_open(self.h, width, height, in_chroma, in_depth, in_full_range, in_matrix, out_depth,
                                                      algorithm, depth))
         self._stream_inverse = (width, height, in_chroma)
+        self._stream_dpx = None
 
     def stream_input(self):
-        """The three pinned input planes of the next slot, as numpy views to fill in place."""
+        """The three pinned input planes of the next slot, as numpy views to fill in place (on a DPX stream: [payload], uint8)."""
         import numpy as np
 
         ptrs = (C.c_void_p * 3)()
         self._check(self.lib.h2y_stream_input(self.h, ptrs))
+        if getattr(self, "_stream_dpx", None):
+            return [np.ctypeslib.as_array(C.cast(ptrs[0], C.POINTER(C.c_uint8)), shape=(self._stream_dpx,))]
         if getattr(self, "_stream_inverse", None):
             w, h, chroma = self._stream_inverse
             nc = (w // 2) * (h // 2) if chroma == CHROMA_420 else w * h
@@ -399,6 +455,7 @@ class Context:
     def stream_close(self) -> None:
         self._check(self.lib.h2y_stream_close(self.h))
         self._stream_inverse = None
+        self._stream_dpx = None
 
     def last_kernel_name(self) -> str:
         return (self.lib.h2y_last_kernel_name(self.h) or b"").decode()

@@ -16,6 +16,9 @@
  *   read_file :662-756: .rgb forces the input matrix to GBR (:677-680); .dpx forces GBR, 4:4:4, 32 bits (:729-734); .exr forces
  *             4:4:4, 32 bits, GBR and FULL RANGE on the input picture (exr.cpp:172-183).  The destination keeps what :265-318 gave it.
  *   read_planar_integer_file :592-610: integer input needs a depth in [10,16]
+ *   .dpx: dpx_read() (dpx.cpp:209-520) aborts on --src_half_float_flag 1 (:232-236); the picture's size comes from the header,
+ *             and main() refuses a header size that differs from --src_pic_width/--src_pic_height (the reference would hand
+ *             convert() two different sizes)
  * Only user_args_t.chroma_resampler_type has no defined default there (never initialised): FIR here, as in
  * make.sh's example.  The reference calls exit(0) on its argument errors; this program returns 1.
  */
@@ -31,7 +34,7 @@
 
 #include "../../include/hdr2yuv_hip.h"
 
-enum { CLI_IN_NONE = 0, CLI_IN_YUV, CLI_IN_RGB, CLI_IN_F32, CLI_IN_F16, CLI_IN_SYNTH, CLI_IN_CODEC };
+enum { CLI_IN_NONE = 0, CLI_IN_YUV, CLI_IN_RGB, CLI_IN_F32, CLI_IN_F16, CLI_IN_SYNTH, CLI_IN_CODEC, CLI_IN_DPX };
 enum { CLI_OUT_NONE = 0, CLI_OUT_YUV, CLI_OUT_RGB, CLI_OUT_CODEC };
 
 struct cli_pic { /* the attribute set of pic_t that the command line fills (hdr.h:363-378) */
@@ -58,6 +61,34 @@ static inline const char *cli_ext_of(const char *fn)
     return dot ? dot + 1 : "";
 }
 
+/* A --src_filename with one printf integer conversion (%d, %i or %u, optionally with a 0 flag and a width: shot.%06d.dpx)
+ * numbers a sequence of .dpx files.  1: one such conversion and no other (a literal %% aside); 0: no conversion; -1: any
+ * other use of '%' (the name is then refused rather than handed to printf). */
+static inline int cli_frame_pattern(const char *fn)
+{
+    int convs = 0;
+    for (const char *p = fn ? fn : ""; *p; p++) {
+        if (*p != '%') continue;
+        if (p[1] == '%') { p++; continue; }
+        const char *q = p + 1;
+        if (*q == '0') q++;
+        while (*q >= '0' && *q <= '9') q++;
+        if ((*q != 'd' && *q != 'i' && *q != 'u') || q - p > 4) return -1;
+        convs++;
+        p = q;
+    }
+    return convs == 0 ? 0 : convs == 1 ? 1 : -1;
+}
+
+/* the file name of frame k of a numbered sequence (cli_frame_pattern(fn) == 1), or fn itself */
+static inline std::string cli_frame_name(const char *fn, long k)
+{
+    if (cli_frame_pattern(fn) != 1) return fn;
+    char buf[4096];
+    snprintf(buf, sizeof buf, fn, (int)k);
+    return buf;
+}
+
 static inline void cli_help()
 {
     printf("hdr2yuv (gfx950): --src_filename F --dst_filename F.yuv --src_pic_width W --src_pic_height H --src_bit_depth N\n"
@@ -69,7 +100,9 @@ static inline void cli_help()
            "  unset source attributes are 0, unset destination attributes take the source's (as the reference resolves them)\n"
            "  additional: [--synthetic SEEDFRAME] [--device D] [--gpus N [--devices d0,d1,..]] [--dry_run 1]\n"
            "input by extension: .yuv .rgb (16-bit planar), .f32 .f16 (raw planar float / half, plane order G,B,R: what\n"
-           "  dpx_read() / read_exr() leave in memory); output: .yuv, or .rgb (planar R,G,B) from .yuv input = the .yuv -> .tiff flow\n");
+           "  dpx_read() / read_exr() leave in memory), .dpx (10-bit, 16-bit or float DPX, decoded on the GPU; one file per frame,\n"
+           "  shot.%%06d.dpx numbers them from --src_start_frame on); output: .yuv, or .rgb (planar R,G,B) from .yuv input = the\n"
+           "  .yuv -> .tiff flow\n");
 }
 
 /* hdr2yuv.cpp:73-263 */
@@ -145,12 +178,13 @@ static inline int cli_resolve(cli_args &a)
     else if (!strcasecmp(ext, "rgb")) a.in_type = CLI_IN_RGB;
     else if (!strcasecmp(ext, "f32")) a.in_type = CLI_IN_F32;
     else if (!strcasecmp(ext, "f16")) a.in_type = CLI_IN_F16;
-    else if (!strcasecmp(ext, "exr") || !strcasecmp(ext, "dpx") || !strcasecmp(ext, "tiff")) a.in_type = CLI_IN_CODEC;
+    else if (!strcasecmp(ext, "dpx")) a.in_type = CLI_IN_DPX;
+    else if (!strcasecmp(ext, "exr") || !strcasecmp(ext, "tiff")) a.in_type = CLI_IN_CODEC;
     if (a.in_type == CLI_IN_NONE) {
         printf("WARNING: input file (%s) type extension (%s) is either not recongized or not supported\n", a.src ? a.src : "(none)", ext);
         arg_errors++;
     } else if (a.in_type == CLI_IN_CODEC) {
-        printf("WARNING: input file (%s): .%s decoding stays with the reference's host I/O (exr.cpp / dpx.cpp / tiff.cpp);\n"
+        printf("WARNING: input file (%s): .%s decoding stays with the reference's host I/O (exr.cpp / tiff.cpp);\n"
                "         this program takes the planes they leave in memory as .f16 / .f32 / .rgb\n", a.src, ext);
         arg_errors++;
     }
@@ -184,7 +218,8 @@ static inline int cli_resolve(cli_args &a)
         arg_errors++;
     }
 
-    if (a.start_frame != 0 && !int_in && a.in_type != CLI_IN_F32 && a.in_type != CLI_IN_F16 && a.in_type != CLI_IN_SYNTH)
+    const bool numbered_dpx = a.in_type == CLI_IN_DPX && cli_frame_pattern(a.src) == 1;
+    if (a.start_frame != 0 && !int_in && a.in_type != CLI_IN_F32 && a.in_type != CLI_IN_F16 && a.in_type != CLI_IN_SYNTH && !numbered_dpx)
         printf("WARNING: start_frame(%d) only makes sense when file type is .yuv, .rgb, or .y4m\n", a.start_frame);
 
     /* :472-507: what was resolved */
@@ -212,7 +247,15 @@ static inline int cli_resolve(cli_args &a)
     if (a.out.width < 2 || a.out.width > 10000) { printf("WARNING: pic_width(%d) outside range [0,10000]\n", a.out.width); arg_errors++; }
     if (a.out.height < 2 || a.out.height > 10000) { printf("WARNING: pic_height(%d) outside range [0,10000]\n", a.out.height); arg_errors++; }
     if (a.out.bit_depth < 8 || a.out.bit_depth > 32) { printf("WARNING: dst bit_depth(%d) outside range [32]\n", a.out.bit_depth); arg_errors++; }
+    if (a.in_type == CLI_IN_DPX && cli_frame_pattern(a.src) < 0) {
+        printf("WARNING: input file name (%s): '%%' other than one integer conversion (%%d, %%0Nd) numbering the frames\n", a.src);
+        arg_errors++;
+    }
     if (arg_errors) return arg_errors;
+    if (a.in_type == CLI_IN_DPX && a.in.half_float_flag == 1) { /* dpx.cpp:232-236 */
+        printf(" %s half-float reading not supported for dpx files in this version, aborting\n", a.src);
+        return 1;
+    }
 
     /* read_file(): what the readers force on the INPUT picture (the destination's copies were taken above) */
     if (a.in_type == CLI_IN_RGB && a.in.matrix_coeffs != H2Y_MATRIX_GBR) {
@@ -224,7 +267,7 @@ static inline int cli_resolve(cli_args &a)
         a.in.matrix_coeffs = H2Y_MATRIX_GBR;
         a.in.chroma_format_idc = H2Y_CHROMA_444;
         a.in.bit_depth = 32;
-        if (a.in_type != CLI_IN_F32) a.in.video_full_range_flag = 1; /* read_exr() only; dpx keeps the flag (:712-713 prints, does not set) */
+        if (a.in_type != CLI_IN_F32 && a.in_type != CLI_IN_DPX) a.in.video_full_range_flag = 1; /* read_exr() only; dpx keeps the flag (:712-713 prints, does not set) */
     }
     if (int_in && (a.in.bit_depth < 10 || a.in.bit_depth > 16)) { /* :592-610 */
         printf("read_planar_integer_file(), WARNING: bit_depth(%d) outside supported range [10,16]\n", a.in.bit_depth);
@@ -240,7 +283,8 @@ static inline void cli_make_desc(const cli_args &a, h2y_desc *d)
     d->width = a.in.width;
     d->height = a.in.height;
     switch (a.in_type) {
-    case CLI_IN_F32: d->in_sample_type = H2Y_SAMPLE_F32; break;
+    case CLI_IN_F32:
+    case CLI_IN_DPX: d->in_sample_type = H2Y_SAMPLE_F32; break;
     case CLI_IN_F16: d->in_sample_type = H2Y_SAMPLE_F16; break;
     case CLI_IN_SYNTH: d->in_sample_type = a.in.half_float_flag ? H2Y_SAMPLE_F16 : H2Y_SAMPLE_F32; break;
     default: d->in_sample_type = H2Y_SAMPLE_U16; break;

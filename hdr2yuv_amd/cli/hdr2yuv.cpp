@@ -4,11 +4,14 @@
  * planes to the C-ABI (include/hdr2yuv_hip.h) and writes the .yuv frames where write_yuv() would append them
  * (tiff.cpp:440: the file is opened in append mode; planes Y, Cb, Cr, little-endian 16-bit).
  *
- * File decoding stays where the reference has it (exr.cpp / tiff.cpp / dpx.cpp need OpenEXR and libtiff): this binary
- * takes the formats that need no codec:
+ * File decoding stays where the reference has it (exr.cpp / tiff.cpp need OpenEXR and libtiff): this binary takes the
+ * formats that need no codec:
  *   .yuv / .rgb  16-bit planar integer (hdr2yuv.cpp:582-656; .rgb is R,G,B in the file, planes 2,0,1 in memory)
  *   .f32 / .f16  raw planar float / half in G,B,R plane order -- what dpx_read() or read_exr() (exr.cpp:233-235) leave in
  *                memory; the attributes those readers force on the input picture are forced here too
+ *   .dpx         10-bit, 16-bit or float DPX (dpx_read(), dpx.cpp:209-520): the header is parsed here (h2y_dpx_parse), the
+ *                payload read straight into the pinned slot of the DPX ring and decoded on the device; one file is one
+ *                frame, and a name with one integer conversion (shot.%06d.dpx) numbers the files of a sequence
  *   --synthetic N  the seeded test frame of SURVEY 8c (no input file), treated as an .exr-like float input
  * and, from .yuv input, .rgb output: the .yuv -> .tiff flow (hdr2yuv.cpp:818-819, matrix_inverse) with the samples
  * write_tiff() would interleave written as planes R, G, B instead (no libtiff here).
@@ -86,6 +89,57 @@ static bool write_at(int fd, const void *buf, size_t n, off_t at)
     return true;
 }
 
+/* one .dpx file of the run: its name and where its payload starts */
+struct dpx_src {
+    std::string path;
+    uint64_t offset;
+};
+
+/* The .dpx files of the run -- --src_filename itself, or the files numbered --src_start_frame .. + want - 1 of a sequence (as
+ * many of them as exist in a row) -- parsed, checked against the command line's size and against the first file's geometry
+ * and format.  Returns 0 and fills info and files, or prints the first problem and returns 1. */
+static int dpx_scan(const cli_args &a, long want, h2y_dpx_info &info, std::vector<dpx_src> &files)
+{
+    const bool seq = cli_frame_pattern(a.src) == 1;
+    for (long k = 0; k < (seq ? want : 1); k++) {
+        const std::string path = cli_frame_name(a.src, a.start_frame + k);
+        struct stat st;
+        if (stat(path.c_str(), &st)) {
+            if (k) break; /* the sequence ends here */
+            printf("ERROR: unable to open file %s\n", path.c_str());
+            return 1;
+        }
+        unsigned char hdr[2048];
+        FILE *f = fopen(path.c_str(), "rb");
+        if (!f) { printf("ERROR: unable to open file %s\n", path.c_str()); return 1; }
+        const size_t got = fread(hdr, 1, sizeof hdr, f);
+        fclose(f);
+        h2y_dpx_info di;
+        const char *why = nullptr;
+        if (h2y_dpx_parse(hdr, got, (uint64_t)st.st_size, &di, &why)) { printf("ERROR: %s: %s\n", path.c_str(), why); return 1; }
+        if (di.width != a.in.width || di.height != a.in.height) {
+            printf("ERROR: %s is %dx%d, --src_pic_width/--src_pic_height say %dx%d: resizing is not part of convert() (cv.cpp is "
+                   "compiled out in the reference)\n", path.c_str(), di.width, di.height, a.in.width, a.in.height);
+            return 1;
+        }
+        if (k && (di.width != info.width || di.height != info.height || di.bit_size != info.bit_size || di.swap != info.swap)) {
+            printf("ERROR: %s is %dx%d %d-bit %s-endian, %s %dx%d %d-bit %s-endian: every file of a sequence must have the same\n",
+                   path.c_str(), di.width, di.height, di.bit_size, di.swap ? "big" : "little", files[0].path.c_str(), info.width,
+                   info.height, info.bit_size, info.swap ? "big" : "little");
+            return 1;
+        }
+        /* fields dpx_read() ignores: the image element's descriptor (byte 800) and packing (u16 at 804) */
+        const unsigned descriptor = hdr[800], packing = di.swap ? (unsigned)hdr[804] << 8 | hdr[805] : (unsigned)hdr[805] << 8 | hdr[804];
+        if (descriptor != 50) printf("WARNING: %s: descriptor %u is not 50 (RGB); decoded as R,G,B, as dpx_read() does\n", path.c_str(), descriptor);
+        if (di.bit_size == 10 && packing != 1)
+            printf("WARNING: %s: 10-bit packing %u is not 1 (filled to 32-bit words, method A); decoded as packing 1, as dpx_read() does\n",
+                   path.c_str(), packing);
+        if (!k) info = di;
+        files.push_back({path, di.data_offset});
+    }
+    return 0;
+}
+
 struct block { /* one thread's share: frames [first, first + count) of the run, on `device` */
     int device = 0;
     long first = 0, count = 0;
@@ -93,8 +147,10 @@ struct block { /* one thread's share: frames [first, first + count) of the run, 
     long done = 0;
 };
 
-/* forward path: frames [first, first+count) through one context's pinned ring */
-static void run_block(const cli_args &a, const h2y_desc &d, int fd_out, off_t base, block *b)
+/* forward path: frames [first, first+count) through one context's pinned ring (dpx: frame k is file dpx[k], decoded on the
+ * device -- the ring of h2y_dpx_stream_open) */
+static void run_block(const cli_args &a, const h2y_desc &d, const std::vector<dpx_src> &dpx, const h2y_dpx_info &di, int fd_out,
+                      off_t base, block *b)
 {
     h2y_ctx *ctx = nullptr;
     FILE *fin = nullptr;
@@ -106,7 +162,7 @@ static void run_block(const cli_args &a, const h2y_desc &d, int fd_out, off_t ba
     if (b->count < 1) return;
     if (h2y_ctx_create(b->device, &ctx)) return fail(h2y_last_error(nullptr));
     const size_t pb = h2y_plane_bytes(&d), ob = h2y_frame_bytes(&d);
-    if (a.in_type != CLI_IN_SYNTH) {
+    if (a.in_type != CLI_IN_SYNTH && a.in_type != CLI_IN_DPX) {
         fin = fopen(a.src, "rb");
         if (!fin) return fail(std::string("unable to open file ") + a.src);
         if (fseeko(fin, (off_t)(3 * pb) * (off_t)(a.start_frame + b->first), SEEK_SET)) return fail("seek failed"); /* hdr2yuv.cpp:624 */
@@ -114,7 +170,7 @@ static void run_block(const cli_args &a, const h2y_desc &d, int fd_out, off_t ba
     /* The reader fills the pinned slot of the pipeline directly, the writer drains what comes out of it two frames
      * later: upload, conversion and download of neighbouring frames overlap. */
     const int depth = 3;
-    if (h2y_stream_open(ctx, &d, depth)) return fail(h2y_last_error(ctx));
+    if (a.in_type == CLI_IN_DPX ? h2y_dpx_stream_open(ctx, &d, &di, depth) : h2y_stream_open(ctx, &d, depth)) return fail(h2y_last_error(ctx));
     long in_flight = 0;
     auto drain_one = [&]() -> bool {
         const uint16_t *yuv = nullptr;
@@ -129,7 +185,15 @@ static void run_block(const cli_args &a, const h2y_desc &d, int fd_out, off_t ba
     for (long f = 0; f < b->count; f++) {
         void *planes[3];
         if (h2y_stream_input(ctx, planes)) return fail(h2y_last_error(ctx));
-        if (fin) {
+        if (a.in_type == CLI_IN_DPX) { /* the payload as the file holds it, straight into the pinned slot */
+            const dpx_src &src = dpx[b->first + f];
+            FILE *fd = fopen(src.path.c_str(), "rb");
+            if (!fd) return fail("unable to open file " + src.path);
+            size_t got = 0;
+            if (!fseeko(fd, (off_t)src.offset, SEEK_SET)) got = fread(planes[0], 1, di.payload_bytes, fd);
+            fclose(fd);
+            if (got != di.payload_bytes) return fail("only " + std::to_string(got) + " payload bytes read from " + src.path);
+        } else if (fin) {
             /* file plane order -> memory planes (0=G/Y, 1=B/Cb, 2=R/Cr); .rgb holds R,G,B (hdr2yuv.cpp:635-637) */
             const int order_rgb[3] = {2, 0, 1}, order_nat[3] = {0, 1, 2};
             const int *ord = a.in_type == CLI_IN_RGB ? order_rgb : order_nat;
@@ -242,7 +306,18 @@ int main(int argc, char **argv)
     /* how many frames there are to do: --n_frames, or what the file holds from --src_start_frame on if that is fewer */
     long frames = a.n_frames > 0 ? a.n_frames : 1;
     struct stat st;
-    if (a.in_type != CLI_IN_SYNTH && !(a.dry_run && stat(a.src, &st))) { /* (a dry run may name a file that is not there) */
+    std::vector<dpx_src> dpx;
+    h2y_dpx_info di{};
+    if (a.in_type == CLI_IN_DPX) { /* one file per frame; a dry run may name a file that is not there */
+        if (!(a.dry_run && stat(cli_frame_name(a.src, a.start_frame).c_str(), &st))) {
+            if (dpx_scan(a, frames, di, dpx)) return 1;
+            frames = (long)dpx.size();
+            printf("dpx: %dx%d %d-bit %s-endian, payload %llu bytes\n", di.width, di.height, di.bit_size, di.swap ? "big" : "little",
+                   (unsigned long long)di.payload_bytes);
+        }
+        printf("src_picture: matrix_coeffs %d chroma_format_idc %d bit_depth %d video_full_range_flag %d\n", a.in.matrix_coeffs,
+               a.in.chroma_format_idc, a.in.bit_depth, a.in.video_full_range_flag);
+    } else if (a.in_type != CLI_IN_SYNTH && !(a.dry_run && stat(a.src, &st))) { /* (a dry run may name a file that is not there) */
         if (stat(a.src, &st)) { printf("ERROR: unable to open file %s\n", a.src); return 1; }
         const long have = (long)((st.st_size - (off_t)in_frame_bytes * a.start_frame) / (off_t)in_frame_bytes);
         if (st.st_size < (off_t)in_frame_bytes * (a.start_frame + 1)) {
@@ -276,7 +351,7 @@ int main(int argc, char **argv)
         blocks[r].count = frames / a.gpus + (r < frames % a.gpus ? 1 : 0);
         at += blocks[r].count;
     }
-    auto work = [&](block *b) { a.inverse ? run_block_inverse(a, fd, base, b) : run_block(a, d, fd, base, b); };
+    auto work = [&](block *b) { a.inverse ? run_block_inverse(a, fd, base, b) : run_block(a, d, dpx, di, fd, base, b); };
     if (a.gpus == 1) work(&blocks[0]);
     else {
         std::vector<std::thread> th;

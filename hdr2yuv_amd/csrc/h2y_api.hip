@@ -183,6 +183,9 @@ struct h2y_ctx {
     /* h2y_inverse_batch: the frame table (pinned on the host, and its device copy the kernels read) */
     inv_frame *d_inv_frames = nullptr, *h_inv_frames = nullptr;
     size_t d_inv_cap = 0, h_inv_cap = 0; /* bytes */
+    /* h2y_dpx_decode_batch's frame table, likewise; a DPX stream keeps one entry per slot in d_dpx_frames */
+    dpx_frame *d_dpx_frames = nullptr, *h_dpx_frames = nullptr;
+    size_t d_dpx_cap = 0, h_dpx_cap = 0; /* bytes */
 
     /* staging for the host-buffer entry */
     void *d_in = nullptr;
@@ -213,6 +216,11 @@ struct h2y_ctx {
      * when that would leave a plane misaligned for the kernel) */
     bool s_inverse = false;
     inv_params s_inv{};
+    /* a DPX stream (h2y_dpx_stream_open): the pinned slot holds the payload, its device twin the three float planes (at
+     * s_in_off[0..2]) and then the payload at s_dpx_off */
+    bool s_dpx = false;
+    h2y_dpx_info s_dpx_info{};
+    size_t s_dpx_off = 0;
     size_t s_in_off[3] = {0, 0, 0}, s_in_bytes = 0, s_out_stride = 0;
     int slot_base = 0; /* run_frames(): first entry of d_frames/h_frames to use (one per stream slot) */
     float last_ms = 0.f;
@@ -1338,6 +1346,8 @@ void h2y_ctx_destroy(h2y_ctx *ctx)
     (void)hipFree(ctx->d_tmp);
     (void)hipFree(ctx->d_inv_frames);
     (void)hipHostFree(ctx->h_inv_frames);
+    (void)hipFree(ctx->d_dpx_frames);
+    (void)hipHostFree(ctx->h_dpx_frames);
     (void)hipFree(ctx->d_in);
     (void)hipFree(ctx->d_out);
     if (ctx->fir_stream) {
@@ -1835,6 +1845,130 @@ int h2y_inverse_batch(h2y_ctx *ctx, int width, int height, int in_chroma_format_
     return H2Y_OK;
 }
 
+/* ---- DPX input (dpx_read(), dpx.cpp:209-520; muxed_dpx_to_planar_float_buf(), common.cpp:14-27) -------------------- */
+
+static int dpx_fmt_of(int bit_size) { return bit_size == 10 ? H2Y_DPX_10 : bit_size == 16 ? H2Y_DPX_16 : H2Y_DPX_F32; }
+static uint64_t dpx_pixel_bytes(int bit_size) { return bit_size == 10 ? 4 : bit_size == 16 ? 6 : 12; }
+
+/* k_dpx_decode's grid for n frames: one block per unit of 256 threads, eight blocks of 256 per CU at most */
+static int dpx_grid(const h2y_ctx *ctx, const h2y_dpx_info &di, int n)
+{
+    const uint64_t units = (uint64_t)n * h2y_dpx_chunks(dpx_fmt_of(di.bit_size), (uint32_t)di.width * (uint32_t)di.height);
+    const uint64_t max_grid = (uint64_t)ctx->n_cu * 8u;
+    return (int)(units < max_grid ? (units ? units : 1) : max_grid);
+}
+
+/* what h2y_dpx_parse can return, and nothing else */
+static int dpx_info_check(h2y_ctx *ctx, const h2y_dpx_info *di)
+{
+    if (!di) return fail(ctx, H2Y_EINVAL, "null h2y_dpx_info");
+    if (di->bit_size != 10 && di->bit_size != 16 && di->bit_size != 32) return fail(ctx, H2Y_EINVAL, "DPX bit_size must be 10, 16 or 32");
+    if (di->width < 1 || di->width > 32767 || di->height < 1 || di->height > 32767) return fail(ctx, H2Y_EINVAL, "DPX width and height must be 1..32767");
+    if (di->swap != 0 && di->swap != 1) return fail(ctx, H2Y_EINVAL, "DPX swap must be 0 or 1");
+    if (di->payload_bytes != (uint64_t)di->width * (uint64_t)di->height * dpx_pixel_bytes(di->bit_size))
+        return fail(ctx, H2Y_EINVAL, "DPX payload_bytes is not width x height x bytes per pixel");
+    return H2Y_OK;
+}
+
+static uint32_t dpx_u32(const unsigned char *p, bool swap) /* the reference's native (little-endian) read, INT_SW when swapping */
+{
+    const uint32_t v = (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
+    return swap ? __builtin_bswap32(v) : v;
+}
+
+int h2y_dpx_parse(const void *header, size_t n, uint64_t file_bytes, h2y_dpx_info *out, const char **why)
+{
+    const char *w = nullptr;
+    const unsigned char *h = static_cast<const unsigned char *>(header);
+    h2y_dpx_info di{};
+    if (!header || !out) w = "null argument";
+    else if (n < 2048) w = "DPX header shorter than 2048 bytes"; /* dpx.cpp:283 reads 2048 and never checks how many came */
+    else {
+        const uint32_t magic = dpx_u32(h, false);
+        if (magic != 0x53445058u && magic != 0x58504453u) w = "bad magic number in dpx header"; /* dpx.cpp:285-298 */
+        else {
+            di.swap = magic == 0x58504453u;
+            di.width = (int16_t)(uint16_t)dpx_u32(h + 772, di.swap); /* `wide = tmp;` uint to short, dpx.cpp:300-310 */
+            di.height = (int16_t)(uint16_t)dpx_u32(h + 776, di.swap);
+            di.bit_size = (signed char)h[803];
+            di.data_offset = dpx_u32(h + 4, di.swap); /* dpx.cpp:343-347 */
+            if (di.bit_size == 12) w = "dpx packing is 12-bit, which is not supported"; /* dpx.cpp:330-333 */
+            else if (di.bit_size != 10 && di.bit_size != 16 && di.bit_size != 32) w = "dpx element bit size is not 10, 16 or 32";
+            else if (di.width < 1 || di.height < 1) w = "dpx width or height (narrowed to short) is outside 1..32767";
+            else {
+                di.payload_bytes = (uint64_t)di.width * (uint64_t)di.height * dpx_pixel_bytes(di.bit_size);
+                if (di.data_offset + di.payload_bytes > file_bytes) w = "dpx payload runs past the end of the file";
+            }
+        }
+    }
+    if (why) *why = w ? w : "";
+    if (w) return fail(nullptr, H2Y_EINVAL, "%s", w);
+    *out = di;
+    return H2Y_OK;
+}
+
+int h2y_dpx_decode_batch(h2y_ctx *ctx, const h2y_dpx_info *info, int n_frames, const void *const *d_payload, float *const *d_planes)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
+    int rc = dpx_info_check(ctx, info);
+    if (rc) return rc;
+    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
+    if (!d_payload || !d_planes) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
+    for (int f = 0; f < n_frames; f++) {
+        if (!d_payload[f]) return fail(ctx, H2Y_EINVAL, "frame %d: payload is null", f);
+        if ((uintptr_t)d_payload[f] & 3u) return fail(ctx, H2Y_EINVAL, "frame %d: payload is not 4-byte aligned", f);
+        for (int c = 0; c < 3; c++) {
+            const float *p = d_planes[3 * f + c];
+            if (!p) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is null", f, c);
+            if ((uintptr_t)p & 3u) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is not 4-byte aligned", f, c);
+        }
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    /* the whole table is uploaded once, every launch reads its own part of it */
+    const size_t tb = (size_t)n_frames * sizeof(dpx_frame);
+    rc = ensure(ctx, ctx->d_dpx_frames, ctx->d_dpx_cap, tb);
+    if (rc) return rc;
+    if (ctx->h_dpx_cap < tb) {
+        if (ctx->h_dpx_frames) HIP_TRY(ctx, hipHostFree(ctx->h_dpx_frames));
+        ctx->h_dpx_frames = nullptr;
+        ctx->h_dpx_cap = 0;
+        hipError_t e = hipHostMalloc((void **)&ctx->h_dpx_frames, tb, hipHostMallocDefault);
+        if (e != hipSuccess) return fail(ctx, H2Y_ENOMEM, "hipHostMalloc(%zu): %s", tb, hipGetErrorString(e));
+        ctx->h_dpx_cap = tb;
+    }
+    for (int f = 0; f < n_frames; f++) {
+        ctx->h_dpx_frames[f].payload = d_payload[f];
+        for (int c = 0; c < 3; c++) ctx->h_dpx_frames[f].plane[c] = d_planes[3 * f + c];
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_dpx_frames, ctx->h_dpx_frames, tb, hipMemcpyHostToDevice, ctx->stream));
+    const int fmt = dpx_fmt_of(info->bit_size);
+    const uint32_t npix = (uint32_t)info->width * (uint32_t)info->height;
+    int launches = 0;
+    for (int f0 = 0; f0 < n_frames; f0 += H2Y_DPX_FRAMES_PER_LAUNCH, launches++) {
+        const int nf = n_frames - f0 < H2Y_DPX_FRAMES_PER_LAUNCH ? n_frames - f0 : H2Y_DPX_FRAMES_PER_LAUNCH;
+        /* launches past the last event pair are timed by it: it then spans them all */
+        const int e = launches < kMaxEvents ? launches : kMaxEvents - 1;
+        if (launches < kMaxEvents) HIP_TRY(ctx, hipEventRecord(ctx->b->ev[e][0], ctx->stream));
+        HIP_TRY(ctx, h2y_launch_dpx_decode(fmt, info->swap != 0, dpx_grid(ctx, *info, nf), ctx->stream, npix, ctx->d_dpx_frames + f0, nf));
+        HIP_TRY(ctx, hipEventRecord(ctx->b->ev[e][1], ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->b->n_ev = launches < kMaxEvents ? launches : kMaxEvents;
+    float ms = 0.f;
+    for (int i = 0; i < ctx->b->n_ev; i++) {
+        float t = 0.f;
+        HIP_TRY(ctx, hipEventElapsedTime(&t, ctx->b->ev[i][0], ctx->b->ev[i][1]));
+        ms += t;
+    }
+    ctx->last_ms = ms;
+    ctx->last_launches = launches;
+    ctx->last_name = "k_dpx_decode";
+    ctx->last_variant = std::string("k_dpx_decode<") + (fmt == H2Y_DPX_10 ? "10" : fmt == H2Y_DPX_16 ? "16" : "F32") +
+                        (info->swap ? ",SWAP>" : ",NOSWAP>");
+    return H2Y_OK;
+}
+
 /* ---- streaming pipeline ------------------------------------------------------
  * H2D of frame k+1, conversion of frame k and D2H of frame k-1 overlap: three streams, a ring of
  * pinned host slots the caller fills and drains in place.  Every frame is converted in the
@@ -1857,21 +1991,22 @@ static void stream_free(h2y_ctx *ctx)
     ctx->s_h2d = ctx->s_d2h = nullptr;
     ctx->streaming = false;
     ctx->s_inverse = false;
+    ctx->s_dpx = false;
     ctx->s_head = ctx->s_tail = 0;
     ctx->s_lent = -1;
 }
 
 /* the ring's streams and `depth` slots: pinned input / output and their device twins */
-static int stream_alloc(h2y_ctx *ctx, int depth, size_t in_bytes, size_t h_out_bytes, size_t d_out_bytes)
+static int stream_alloc(h2y_ctx *ctx, int depth, size_t h_in_bytes, size_t d_in_bytes, size_t h_out_bytes, size_t d_out_bytes)
 {
     ctx->ss.assign(depth, h2y_ctx::stream_slot());
     ctx->streaming = true;
     hipError_t e = hipStreamCreateWithFlags(&ctx->s_h2d, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->s_d2h, hipStreamNonBlocking);
     for (auto &s : ctx->ss) {
-        if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_in, in_bytes, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_in, h_in_bytes, hipHostMallocDefault);
         if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_out, h_out_bytes, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipMalloc((void **)&s.d_in, in_bytes);
+        if (e == hipSuccess) e = hipMalloc((void **)&s.d_in, d_in_bytes);
         if (e == hipSuccess) e = hipMalloc((void **)&s.d_out, d_out_bytes);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&s.ev_h2d, hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&s.ev_conv, hipEventDisableTiming);
@@ -1899,7 +2034,7 @@ int h2y_stream_open(h2y_ctx *ctx, const h2y_desc *d, int depth)
     ctx->s_plane_al = (pb + 255) & ~(size_t)255;
     ctx->s_desc = *d;
     for (int c = 0; c < 3; c++) ctx->s_in_off[c] = c * ctx->s_plane_al;
-    return stream_alloc(ctx, depth, 3 * ctx->s_plane_al, ob, ob);
+    return stream_alloc(ctx, depth, 3 * ctx->s_plane_al, 3 * ctx->s_plane_al, ob, ob);
 }
 
 /* The same ring for the .yuv -> G,B,R flow: a slot's input is Y, Cb/Dz, Cr/Dx one after the other (each 256-byte aligned; one
@@ -1923,9 +2058,52 @@ int h2y_inverse_stream_open(h2y_ctx *ctx, int width, int height, int in_chroma_f
     ctx->s_in_bytes = pb_al + cb_al + cb;
     ctx->s_out_stride = (pb & 15) ? pb_al : pb; /* 4:2:0 planes are always a multiple of 16 bytes */
     ctx->s_inv = p;
-    rc = stream_alloc(ctx, depth, ctx->s_in_bytes, 3 * pb, 2 * ctx->s_out_stride + pb);
+    rc = stream_alloc(ctx, depth, ctx->s_in_bytes, ctx->s_in_bytes, 3 * pb, 2 * ctx->s_out_stride + pb);
     if (rc) return rc;
     ctx->s_inverse = true;
+    return H2Y_OK;
+}
+
+/* The same ring on DPX payloads: the pinned slot holds payload_bytes, its device twin the three float planes (each 256-byte
+ * aligned, as h2y_stream_open lays them out) and then the payload; each slot's k_dpx_decode table entry is uploaded here once */
+int h2y_dpx_stream_open(h2y_ctx *ctx, const h2y_desc *d, const h2y_dpx_info *info, int depth)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is already open");
+    int rc = dpx_info_check(ctx, info);
+    if (rc) return rc;
+    const char *why;
+    rc = h2y_desc_check(d, &why);
+    if (rc) return fail(ctx, rc, "descriptor: %s", why);
+    if (d->in_sample_type != H2Y_SAMPLE_F32) return fail(ctx, H2Y_EINVAL, "a DPX stream decodes to F32 planes: in_sample_type must be H2Y_SAMPLE_F32");
+    if (d->width != info->width || d->height != info->height)
+        return fail(ctx, H2Y_EINVAL, "DPX picture is %dx%d, the descriptor %dx%d (resizing is not part of convert())", info->width, info->height,
+                    d->width, d->height);
+    if (depth < 2 || depth > 16) return fail(ctx, H2Y_EINVAL, "depth must be 2..16");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = reserve_batch(ctx, 64);
+    if (rc) return rc;
+    rc = ensure(ctx, ctx->d_dpx_frames, ctx->d_dpx_cap, (size_t)depth * sizeof(dpx_frame));
+    if (rc) return rc;
+    const size_t pb = h2y_plane_bytes(d), ob = h2y_frame_bytes(d);
+    ctx->s_plane_al = (pb + 255) & ~(size_t)255;
+    ctx->s_desc = *d;
+    for (int c = 0; c < 3; c++) ctx->s_in_off[c] = c * ctx->s_plane_al;
+    ctx->s_dpx_off = 3 * ctx->s_plane_al;
+    rc = stream_alloc(ctx, depth, info->payload_bytes, ctx->s_dpx_off + info->payload_bytes, ob, ob);
+    if (rc) return rc;
+    std::vector<dpx_frame> tab(depth);
+    for (int k = 0; k < depth; k++) {
+        tab[k].payload = ctx->ss[k].d_in + ctx->s_dpx_off;
+        for (int c = 0; c < 3; c++) tab[k].plane[c] = reinterpret_cast<float *>(ctx->ss[k].d_in + ctx->s_in_off[c]);
+    }
+    hipError_t e = hipMemcpy(ctx->d_dpx_frames, tab.data(), tab.size() * sizeof(dpx_frame), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        stream_free(ctx);
+        return fail(ctx, H2Y_EHIP, "hipMemcpy of the DPX slot table: %s", hipGetErrorString(e));
+    }
+    ctx->s_dpx = true;
+    ctx->s_dpx_info = *info;
     return H2Y_OK;
 }
 
@@ -1977,6 +2155,11 @@ int h2y_stream_input(h2y_ctx *ctx, void *planes[3])
     if (s.state == 1) { /* asked twice without a submit: same buffers again */
     } else if (s.state != 0) return fail(ctx, H2Y_EINVAL, "all %d slots are in flight: take an output first", (int)ctx->ss.size());
     s.state = 1;
+    if (ctx->s_dpx) { /* the payload, as the file holds it */
+        planes[0] = s.h_in;
+        planes[1] = planes[2] = nullptr;
+        return H2Y_OK;
+    }
     for (int c = 0; c < 3; c++) planes[c] = s.h_in + ctx->s_in_off[c];
     return H2Y_OK;
 }
@@ -1994,12 +2177,19 @@ int h2y_stream_submit(h2y_ctx *ctx)
     const size_t pb = h2y_plane_bytes(d), ob = h2y_frame_bytes(d);
     frame_io io;
     for (int c = 0; c < 3; c++) io.in[c] = s.d_in + c * ctx->s_plane_al;
-    /* the slot's three planes lie one after the other (each padded to 256 bytes): one copy command, not three */
-    HIP_TRY(ctx, hipMemcpyAsync(s.d_in, s.h_in, 2 * ctx->s_plane_al + pb, hipMemcpyHostToDevice, ctx->s_h2d));
+    if (ctx->s_dpx) /* the payload goes up; k_dpx_decode writes the three planes below */
+        HIP_TRY(ctx, hipMemcpyAsync(s.d_in + ctx->s_dpx_off, s.h_in, ctx->s_dpx_info.payload_bytes, hipMemcpyHostToDevice, ctx->s_h2d));
+    else /* the slot's three planes lie one after the other (each padded to 256 bytes): one copy command, not three */
+        HIP_TRY(ctx, hipMemcpyAsync(s.d_in, s.h_in, 2 * ctx->s_plane_al + pb, hipMemcpyHostToDevice, ctx->s_h2d));
     io.out = s.d_out;
     io.tmp_cb = io.tmp_cr = nullptr;
     HIP_TRY(ctx, hipEventRecord(s.ev_h2d, ctx->s_h2d));
     HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s.ev_h2d, 0));
+    if (ctx->s_dpx) {
+        const h2y_dpx_info &di = ctx->s_dpx_info;
+        HIP_TRY(ctx, h2y_launch_dpx_decode(dpx_fmt_of(di.bit_size), di.swap != 0, dpx_grid(ctx, di, 1), ctx->stream,
+                                           (uint32_t)di.width * (uint32_t)di.height, ctx->d_dpx_frames + slot, 1));
+    }
     const bool needs_stats = d->src_transfer != d->dst_transfer;
     int rc;
     if (needs_stats && !d->stats_override) {

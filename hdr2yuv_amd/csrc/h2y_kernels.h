@@ -220,4 +220,14 @@ hipError_t h2y_launch_inverse_batch(int grid, hipStream_t st, const inverse_args
 int h2y_inverse420_tiles(int width, int height); /* k_inverse420(_batch) tiles of one frame */
 hipError_t h2y_launch_box420(hipStream_t st, const uint16_t *src, uint16_t *dst, int W, int H);
 
+/* k_dpx_decode (h2y_dpx.hip): dpx_read()'s per-pixel loop on the device */
+enum { H2Y_DPX_10 = 0, H2Y_DPX_16 = 1, H2Y_DPX_F32 = 2 };
+/* one frame: its interleaved R,G,B payload in, the planes G, B, R out (muxed_dpx_to_planar_float_buf's order) */
+struct dpx_frame {
+    const void *payload;
+    float *plane[3];
+};
+uint32_t h2y_dpx_chunks(int fmt, uint32_t npix); /* k_dpx_decode's units of 256 threads per frame */
+hipError_t h2y_launch_dpx_decode(int fmt, bool swap, int grid, hipStream_t st, uint32_t npix, const dpx_frame *frames, int n_frames);
+
 #endif

@@ -271,13 +271,58 @@ int h2y_stream_submit(h2y_ctx *ctx);
 int h2y_stream_output(h2y_ctx *ctx, const uint16_t **yuv);
 int h2y_stream_close(h2y_ctx *ctx);
 
-/* Timing of the last h2y_convert_batch*() (or h2y_inverse_*) call measured with HIP events on
+/* ---- DPX input (dpx_read(), dpx.cpp:209-520, then muxed_dpx_to_planar_float_buf(), common.cpp:14-27) ------------------
+ * The header and the file read stay on the host; the per-pixel loop runs on the device (k_dpx_decode).  What a DPX file is
+ * to the reference: 2048 header bytes; the first four read as a native little-endian int are 0x53445058 (bytes "XPDS": no byte
+ * swap) or 0x58504453 ("SDPX": every 32-bit word, or every 16-bit word of a 16-bit file, byte-swapped); the pixels start at
+ * the u32 at byte 4; width and height are the u32 at 772 and 776, narrowed to short; the element bit size is the byte at 803
+ * (10: one 32-bit word per pixel, R = w >> 22, G = (w >> 12) & 1023, B = (w >> 2) & 1023, each (float)(c / 1023.0); 16: R, G,
+ * B u16, (float)(u / 65535.0); 32: R, G, B binary32, copied as they are).  Descriptor, packing and end-of-line padding are
+ * ignored: the payload is width x height interleaved R,G,B pixels in one block.  The decoded planes are G, B, R (the
+ * reference's fbuf[0..2]) of an F32 4:4:4 picture. */
+typedef struct h2y_dpx_info {
+    int32_t width;          /* 1..32767 */
+    int32_t height;         /* 1..32767 */
+    int32_t bit_size;       /* 10, 16 or 32 */
+    int32_t swap;           /* 1: big-endian file ("SDPX"), words byte-swapped */
+    uint64_t data_offset;   /* first payload byte in the file */
+    uint64_t payload_bytes; /* width * height * (4, 6 or 12) */
+} h2y_dpx_info;
+
+/* Parse a DPX header: `header` holds the file's first n bytes, file_bytes is the file's size.  Host only: no device, no
+ * context.  Refuses (H2Y_EINVAL, `why` a static string) where the reference aborts -- a bad magic, a bit size other than 10,
+ * 16 or 32 -- and, where the reference would read memory it never initialised, a header shorter than 2048 bytes and a payload
+ * that runs past the end of the file (data_offset + payload_bytes > file_bytes); also a width or height outside 1..32767
+ * after the narrowing to short. */
+int h2y_dpx_parse(const void *header, size_t n, uint64_t file_bytes, h2y_dpx_info *out, const char **why);
+
+/* Frames per launch of h2y_dpx_decode_batch: longer batches are split into launches of at most this many frames. */
+#define H2Y_DPX_FRAMES_PER_LAUNCH 64
+
+/* The per-pixel loop of dpx_read() and the demux on n_frames payloads of one geometry and format, device buffers:
+ *   d_payload[f]       device pointer to frame f's payload_bytes, 4-byte aligned
+ *   d_planes[f*3 + c]  device pointers to frame f's float planes G, B, R (width x height each), 4-byte aligned
+ * The arrays of pointers themselves are host memory.  16-byte accesses where a frame's payload and planes allow them.  Runs in
+ * launches of up to H2Y_DPX_FRAMES_PER_LAUNCH; synchronous: every plane is final on return.  Chain it with h2y_convert_batch
+ * (d->in_sample_type H2Y_SAMPLE_F32) for the whole .dpx -> .yuv flow on device buffers. */
+int h2y_dpx_decode_batch(h2y_ctx *ctx, const h2y_dpx_info *info, int n_frames, const void *const *d_payload,
+                         float *const *d_planes);
+
+/* The h2y_stream_* ring of h2y_stream_open on DPX payloads: each slot does one H2D copy of payload_bytes, k_dpx_decode into the
+ * slot's device float planes, the forward conversion of d (in_sample_type H2Y_SAMPLE_F32, width and height those of info), and
+ * one D2H copy of the .yuv frame.  h2y_stream_input hands out planes[0] = the pinned payload (payload_bytes; fill it with the
+ * file's bytes from data_offset on), planes[1] = planes[2] = NULL; h2y_stream_submit / _output / _close and the exclusivity
+ * rules are those of the forward stream. */
+int h2y_dpx_stream_open(h2y_ctx *ctx, const h2y_desc *d, const h2y_dpx_info *info, int depth /* 2..16 slots */);
+
+/* Timing of the last h2y_convert_batch*() (or h2y_inverse_*, h2y_dpx_decode_batch) call measured with HIP events on
  * the stream the kernels ran on: total ms over the main kernels and how many
  * launches that covered. */
 int h2y_last_kernel_ms(const h2y_ctx *ctx, float *ms, int *launches);
 
 /* Name of the kernel those launches ran ("k_fused", "k_fused_t1", "k_fused_lut16",
- * "k_fused_narrow"; of the inverse entries "k_inverse", "k_inverse420", "k_inverse_batch", "k_inverse420_batch"): the name to
+ * "k_fused_narrow"; of the inverse entries "k_inverse", "k_inverse420", "k_inverse_batch", "k_inverse420_batch"; of
+ * h2y_dpx_decode_batch "k_dpx_decode"): the name to
  * look for in a rocprofv3 kernel trace. */
 const char *h2y_last_kernel_name(const h2y_ctx *ctx);
 /* The same with its template arguments and launch shape, e.g. "k_fused_t1<F32,420BOX,YCBCR,PQ_IDENT> groups=8 xcd=1";

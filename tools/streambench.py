@@ -9,6 +9,14 @@ pinned ring of h2y_stream_* (the three overlapped).
      h2y_inverse_batch at 64 frames per call, next to the single-frame entries (h2y_inverse_420 / h2y_matrix_inverse) called
      64 times, in the same process: 4:2:0 FIR, 4:2:0 replication, 4:4:4;
   2. frames/s from host memory, 4:2:0 FIR: h2y_inverse_frame (pageable, serial) against the inverse stream (depth 3).
+Prints one line per figure, then one JSON line with all of them.
+
+`streambench.py dpx`: DPX input on 4K pictures, for each of 10-bit, 16-bit and float DPX:
+  1. ms/frame and frames/s from host memory of the DPX ring (h2y_dpx_stream_open: the payload goes up, k_dpx_decode, the
+     forward conversion) against the .f32 ring (h2y_stream_open) on the same decoded pictures, both at depth 3, each frame
+     copied into its pinned slot by the host (a memcpy standing in for the file read);
+  2. the kernel time of h2y_dpx_decode_batch over 64 frames (HIP events, median of reps), the bytes it moves -- the payload
+     plus 12 B/pixel of float planes -- over that time, and their share of the 8 TB/s HBM peak.
 Prints one line per figure, then one JSON line with all of them."""
 import os
 import sys
@@ -100,6 +108,92 @@ def inverse_main():
     print(json.dumps({"streambench_inverse": res}), flush=True)
 
 
+def dpx_main():
+    import json
+
+    import torch
+
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    from dpx_files import pack_pixels, read_dpx, write_dpx
+
+    w, hh, nb, reps = 3840, 2160, 64, 5
+    n = w * hh
+    nf = int(os.environ.get("N", "60"))
+    depth = 3
+    rng = np.random.default_rng(10)
+    ctx = h.Context(0)
+    d = h.make_desc(w, hh, dst_depth=10, dst_matrix=h.MATRIX_BT2020NC, resampler=0)
+    res = {"width": w, "height": hh, "frames_per_call": nb, "reps": reps, "ring_frames": nf, "ring_depth": depth,
+           "desc": "F32 GBR linear -> PQ BT.2020nc 10-bit 4:2:0 box", "hbm_peak_tbs": 8.0}
+    for bits in (10, 16, 32):
+        if bits == 32:
+            rgb = [rng.random(n, dtype=np.float32).view(np.uint32) for _ in range(3)]
+        else:
+            rgb = [rng.integers(0, 1 << bits if bits == 16 else 1024, n, dtype=np.uint64) for _ in range(3)]
+        data = write_dpx(w, hh, bits, pack_pixels(*rgb, bits), big_endian=True)
+        info = h.parse_dpx(data[:2048], len(data))
+        payload = np.frombuffer(data, np.uint8, count=info.payload_bytes, offset=info.data_offset)
+        planes = read_dpx(data)[1]
+        r = {"payload_mb": round(info.payload_bytes / 1e6, 1)}
+
+        # 1. host memory: the DPX ring against the .f32 ring on the same pictures
+        def ring(open_fn, fill):
+            open_fn()
+            inflight = 0
+            t0 = time.perf_counter()
+            for _ in range(nf):
+                fill(ctx.stream_input())
+                ctx.stream_submit()
+                inflight += 1
+                if inflight == depth - 1:
+                    ctx.stream_output()
+                    inflight -= 1
+            while inflight:
+                ctx.stream_output()
+                inflight -= 1
+            dt = (time.perf_counter() - t0) / nf
+            ctx.stream_close()
+            return dt
+
+        def fill_dpx(slot):
+            slot[0][:] = payload
+
+        def fill_f32(slot):
+            for c in range(3):
+                slot[c][:] = planes[c]
+
+        ring(lambda: ctx.dpx_stream_open(d, info, depth), fill_dpx)  # warm-up
+        t_dpx = ring(lambda: ctx.dpx_stream_open(d, info, depth), fill_dpx)
+        ring(lambda: ctx.stream_open(d, depth), fill_f32)
+        t_f32 = ring(lambda: ctx.stream_open(d, depth), fill_f32)
+        r.update(dpx_ring_ms=round(t_dpx * 1e3, 2), dpx_ring_fps=round(1 / t_dpx, 1), f32_ring_ms=round(t_f32 * 1e3, 2),
+                 f32_ring_fps=round(1 / t_f32, 1), ring_speedup=round(t_f32 / t_dpx, 2))
+        print(f"{bits:2d}-bit DPX  ring from host memory: dpx {t_dpx*1e3:6.2f} ms/frame {1/t_dpx:6.1f} frames/s   "
+              f".f32 {t_f32*1e3:6.2f} ms/frame {1/t_f32:6.1f} frames/s   ({t_f32/t_dpx:4.2f}x)", flush=True)
+
+        # 2. the decode kernel over 64 frames on the device: 64 distinct payloads and 64 distinct sets of planes
+        pays = [torch.randint(-(1 << 31), (1 << 31) - 1, (info.payload_bytes // 4,), dtype=torch.int32, device="cuda") for _ in range(nb)]
+        outs = [[torch.empty(n, dtype=torch.float32, device="cuda") for _ in range(3)] for _ in range(nb)]
+        torch.cuda.synchronize()
+        ks = []
+        for rep in range(reps + 1):  # rep 0 warms up
+            ctx.dpx_decode_batch(info, pays, outs)
+            if rep:
+                ks.append(ctx.last_kernel_ms()[0] / nb)
+        k_ms = float(np.median(ks))
+        moved = info.payload_bytes + 12 * n
+        tbs = moved / (k_ms * 1e-3) / 1e12
+        r.update(kernel_us_per_frame=round(k_ms * 1e3, 1), bytes_per_frame=moved, kernel_tbs=round(tbs, 2),
+                 hbm_peak_fraction=round(tbs / 8.0, 3))
+        print(f"{bits:2d}-bit DPX  k_dpx_decode, {nb} frames per call: {k_ms*1e3:6.1f} us/frame  {moved/1e6:6.1f} MB/frame  "
+              f"{tbs:5.2f} TB/s = {tbs/8.0*100:4.1f} % of 8 TB/s", flush=True)
+        res[f"dpx{bits}"] = r
+        del pays, outs
+        torch.cuda.empty_cache()
+    ctx.close()
+    print(json.dumps({"streambench_dpx": res}), flush=True)
+
+
 def main():
     n = int(os.environ.get("N", "200"))  # long enough for the start-up (three slots filled by host copies) not to weigh
     depth = int(os.environ.get("DEPTH", "3"))
@@ -143,4 +237,9 @@ def main():
 
 
 if __name__ == "__main__":
-    inverse_main() if sys.argv[1:] == ["inverse"] else main()
+    if sys.argv[1:] == ["inverse"]:
+        inverse_main()
+    elif sys.argv[1:] == ["dpx"]:
+        dpx_main()
+    else:
+        main()
