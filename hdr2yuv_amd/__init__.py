@@ -13,6 +13,7 @@ from .api import (  # noqa: F401
     H2YDesc,
     H2YDpxInfo,
     H2YError,
+    H2YTiffInfo,
     MATRIX_BT2020NC,
     MATRIX_BT709,
     MATRIX_GBR,
@@ -32,5 +33,7 @@ from .api import (  # noqa: F401
     load_library,
     make_desc,
     parse_dpx,
+    parse_tiff,
     set_library_path,
+    tiff_layout,
 )

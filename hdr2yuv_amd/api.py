@@ -30,6 +30,8 @@ EXPORTS = [
     "h2y_batch_finish", "h2y_pic_stats", "h2y_matrix_convert", "h2y_subsample_420", "h2y_last_kernel_ms", "h2y_last_kernel_name", "h2y_last_kernel_variant",
     "h2y_matrix_inverse", "h2y_upsample_444", "h2y_inverse_420", "h2y_inverse_frame", "h2y_ctx_set_option", "h2y_stream_open", "h2y_stream_input", "h2y_stream_submit", "h2y_stream_output", "h2y_stream_close",
     "h2y_inverse_batch", "h2y_inverse_stream_open", "h2y_dpx_parse", "h2y_dpx_decode_batch", "h2y_dpx_stream_open",
+    "h2y_tiff_parse", "h2y_tiff_layout", "h2y_tiff_decode_batch", "h2y_rgb_interleave_batch", "h2y_tiff_stream_open",
+    "h2y_tiff_inverse_stream_open",
 ]
 
 
@@ -65,6 +67,27 @@ class H2YDpxInfo(C.Structure):
     def __repr__(self):
         return (f"H2YDpxInfo(width={self.width}, height={self.height}, bit_size={self.bit_size}, swap={self.swap}, "
                 f"data_offset={self.data_offset}, payload_bytes={self.payload_bytes})")
+
+
+TIFF_CUTOUT_HD = 1
+TIFF_CUTOUT_QHD = 2
+TIFF_FRAMES_PER_LAUNCH = 64
+
+
+class H2YTiffInfo(C.Structure):
+    """h2y_tiff_info, include/hdr2yuv_hip.h: what h2y_tiff_parse read from a TIFF and the picture read_tiff decodes from it."""
+
+    _fields_ = [
+        ("file_width", C.c_int32), ("file_height", C.c_int32), ("rows_per_strip", C.c_int32), ("swap", C.c_int32),
+        ("width", C.c_int32), ("height", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32),
+        ("row_bytes", C.c_uint64), ("payload_bytes", C.c_uint64), ("data_offset", C.c_uint64),
+        ("contiguous", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+    def __repr__(self):
+        return (f"H2YTiffInfo(file={self.file_width}x{self.file_height} rps={self.rows_per_strip} swap={self.swap}, "
+                f"decoded={self.width}x{self.height} at ({self.x0}, {self.y0}), row_bytes={self.row_bytes}, "
+                f"payload_bytes={self.payload_bytes}, data_offset={self.data_offset}, contiguous={self.contiguous})")
 
 
 def make_desc(width, height, *, sample=SAMPLE_F32, src_depth=32, dst_depth=10, src_transfer=TRANSFER_LINEAR,
@@ -196,6 +219,20 @@ def load_library():
     L.h2y_dpx_decode_batch.argtypes = [C.c_void_p, C.POINTER(H2YDpxInfo), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.h2y_dpx_stream_open.restype = C.c_int
     L.h2y_dpx_stream_open.argtypes = [C.c_void_p, C.POINTER(H2YDesc), C.POINTER(H2YDpxInfo), C.c_int]
+    L.h2y_tiff_parse.restype = C.c_int
+    L.h2y_tiff_parse.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.POINTER(H2YTiffInfo), C.POINTER(C.c_uint64), C.c_int,
+                                 C.POINTER(C.c_char_p)]
+    L.h2y_tiff_layout.restype = C.c_int
+    L.h2y_tiff_layout.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]
+    L.h2y_tiff_decode_batch.restype = C.c_int
+    L.h2y_tiff_decode_batch.argtypes = [C.c_void_p, C.POINTER(H2YTiffInfo), C.c_int, C.c_int, C.POINTER(C.c_void_p),
+                                        C.POINTER(C.c_void_p)]
+    L.h2y_rgb_interleave_batch.restype = C.c_int
+    L.h2y_rgb_interleave_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.h2y_tiff_stream_open.restype = C.c_int
+    L.h2y_tiff_stream_open.argtypes = [C.c_void_p, C.POINTER(H2YDesc), C.POINTER(H2YTiffInfo), C.c_int, C.c_int]
+    L.h2y_tiff_inverse_stream_open.restype = C.c_int
+    L.h2y_tiff_inverse_stream_open.argtypes = [C.c_void_p] + [C.c_int] * 9
     L.h2y_stream_open.restype = C.c_int
     L.h2y_stream_open.argtypes = [C.c_void_p, C.POINTER(H2YDesc), C.c_int]
     L.h2y_stream_input.restype = C.c_int
@@ -236,6 +273,45 @@ def parse_dpx(header_bytes: bytes, file_bytes: int) -> H2YDpxInfo:
     if rc != H2Y_OK:
         raise ValueError((why.value or b"").decode())
     return info
+
+
+def parse_tiff(data, cutout=0):
+    """h2y_tiff_parse on the host (no device needed): data = the whole file (bytes or a uint8 array), cutout = TIFF_CUTOUT_*
+    bits.  Returns (info, row_offsets): the file offset of each decoded row as a uint64 array.  Raises ValueError with the
+    library's reason where the file is refused; warns where an "MM" file is decoded byte-swapped (the reference would not)."""
+    import numpy as np
+
+    buf = np.frombuffer(data, np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, np.uint8)
+    lib = load_library()
+    info = H2YTiffInfo()
+    why = C.c_char_p()
+    ptr = buf.ctypes.data_as(C.c_void_p)
+    if lib.h2y_tiff_parse(ptr, buf.size, int(cutout), C.byref(info), None, 0, C.byref(why)) != H2Y_OK:
+        raise ValueError((why.value or b"").decode())
+    rows = np.zeros(info.height, np.uint64)
+    rc = lib.h2y_tiff_parse(ptr, buf.size, int(cutout), C.byref(info), rows.ctypes.data_as(C.POINTER(C.c_uint64)), rows.size, C.byref(why))
+    if rc != H2Y_OK:
+        raise ValueError((why.value or b"").decode())
+    if info.swap:
+        import warnings
+
+        warnings.warn("big-endian (MM) TIFF: decoded with the bytes of each sample exchanged; the reference reads them unswapped",
+                      stacklevel=2)
+    return info, rows
+
+
+def tiff_layout(width, height):
+    """h2y_tiff_layout: (head, tail) -- the bytes before and after the 6 x width x height bytes of interleaved R,G,B u16 samples
+    in the file libtiff 4.3 writes for write_tiff()."""
+    lib = load_library()
+    head = (C.c_uint8 * 8)()
+    n = C.c_size_t(0)
+    if lib.h2y_tiff_layout(width, height, head, None, C.byref(n)) != H2Y_OK:
+        raise ValueError((lib.h2y_last_error(None) or b"").decode())
+    tail = (C.c_uint8 * n.value)()
+    if lib.h2y_tiff_layout(width, height, head, tail, C.byref(n)) != H2Y_OK:
+        raise ValueError((lib.h2y_last_error(None) or b"").decode())
+    return bytes(head), bytes(tail)
 
 
 def _np_dtype(sample):
@@ -398,12 +474,57 @@ class Context:
                 outs[3 * f + c] = self._ptr(planes_out[f][c])
         self._check(self.lib.h2y_dpx_decode_batch(self.h, C.byref(info), n, pay, outs))
 
+    def tiff_decode_batch(self, info: H2YTiffInfo, clamp_video_range, payloads, planes_out) -> None:
+        """TIFF rows on the device (payloads[f]: info.payload_bytes each, the decoded rows whole, one after the other) -> u16
+        planes planes_out[f] = (G, B, R), tensors or pointers: read_tiff()'s per-pixel loop, many frames per launch."""
+        n = len(payloads)
+        if len(planes_out) != n:
+            raise ValueError("payloads and planes_out differ in length")
+        pay = (C.c_void_p * n)(*[self._ptr(p) for p in payloads])
+        outs = (C.c_void_p * (3 * n))()
+        for f in range(n):
+            for c in range(3):
+                outs[3 * f + c] = self._ptr(planes_out[f][c])
+        self._check(self.lib.h2y_tiff_decode_batch(self.h, C.byref(info), int(clamp_video_range), n, pay, outs))
+
+    def rgb_interleave_batch(self, width, height, planes_in, rgb_out) -> None:
+        """u16 planes planes_in[f] = (G, B, R) on the device -> rgb_out[f], 3 x width x height u16, R, G, B per pixel."""
+        n = len(planes_in)
+        if len(rgb_out) != n:
+            raise ValueError("planes_in and rgb_out differ in length")
+        ins = (C.c_void_p * (3 * n))()
+        for f in range(n):
+            for c in range(3):
+                ins[3 * f + c] = self._ptr(planes_in[f][c])
+        outs = (C.c_void_p * n)(*[self._ptr(p) for p in rgb_out])
+        self._check(self.lib.h2y_rgb_interleave_batch(self.h, width, height, n, ins, outs))
+
     # ---- host <-> device pipeline -----------------------------------------------------------
     def stream_open(self, d, depth=3) -> None:
         self._check(self.lib.h2y_stream_open(self.h, C.byref(d), depth))
         self._stream_desc = d
         self._stream_inverse = None
         self._stream_dpx = None
+        self._stream_rgb = False
+
+    def tiff_stream_open(self, d, info: H2YTiffInfo, clamp_video_range, depth=3) -> None:
+        """The forward ring on TIFF rows: stream_input gives one uint8 view of the pinned slot (info.payload_bytes) to fill with
+        the decoded rows; stream_output gives the .yuv frame as on a forward stream."""
+        self._check(self.lib.h2y_tiff_stream_open(self.h, C.byref(d), C.byref(info), int(clamp_video_range), depth))
+        self._stream_desc = d
+        self._stream_inverse = None
+        self._stream_dpx = int(info.payload_bytes)
+        self._stream_rgb = False
+
+    def tiff_inverse_stream_open(self, width, height, in_chroma, in_depth, in_full_range, in_matrix, out_depth, algorithm,
+                                 depth=3) -> None:
+        """The inverse ring with write_tiff's interleave: stream_input gives Y, Cb/Dz, Cr/Dx, stream_output a (height, width, 3)
+        u16 view, R, G, B per pixel (the samples between tiff_layout's head and tail)."""
+        self._check(self.lib.h2y_tiff_inverse_stream_open(self.h, width, height, in_chroma, in_depth, in_full_range, in_matrix,
+                                                          out_depth, algorithm, depth))
+        self._stream_inverse = (width, height, in_chroma)
+        self._stream_dpx = None
+        self._stream_rgb = True
 
     def dpx_stream_open(self, d, info: H2YDpxInfo, depth=3) -> None:
         """The forward ring on DPX payloads: stream_input gives one uint8 view of the pinned payload (info.payload_bytes) to fill
@@ -412,6 +533,7 @@ class Context:
         self._stream_desc = d
         self._stream_inverse = None
         self._stream_dpx = int(info.payload_bytes)
+        self._stream_rgb = False
 
     def inverse_stream_open(self, width, height, in_chroma, in_depth, in_full_range, in_matrix, out_depth, algorithm, depth=3) -> None:
         """The pinned ring for the .yuv -> G,B,R flow: stream_input gives Y, Cb/Dz, Cr/Dx, stream_output G, B, R."""
@@ -419,9 +541,11 @@ class Context:
                                                      algorithm, depth))
         self._stream_inverse = (width, height, in_chroma)
         self._stream_dpx = None
+        self._stream_rgb = False
 
     def stream_input(self):
-        """The three pinned input planes of the next slot, as numpy views to fill in place (on a DPX stream: [payload], uint8)."""
+        """The three pinned input planes of the next slot, as numpy views to fill in place (on a DPX or TIFF stream: [payload],
+        uint8)."""
         import numpy as np
 
         ptrs = (C.c_void_p * 3)()
@@ -449,6 +573,8 @@ class Context:
         self._check(self.lib.h2y_stream_output(self.h, C.byref(p)))
         if getattr(self, "_stream_inverse", None):
             w, h, _ = self._stream_inverse
+            if getattr(self, "_stream_rgb", False):
+                return np.ctypeslib.as_array(p, shape=(h, w, 3))
             return np.ctypeslib.as_array(p, shape=(3, w * h))
         return np.ctypeslib.as_array(p, shape=(frame_bytes(self._stream_desc) // 2,))
 
@@ -456,6 +582,7 @@ class Context:
         self._check(self.lib.h2y_stream_close(self.h))
         self._stream_inverse = None
         self._stream_dpx = None
+        self._stream_rgb = False
 
     def last_kernel_name(self) -> str:
         return (self.lib.h2y_last_kernel_name(self.h) or b"").decode()

@@ -19,6 +19,10 @@
  *   .dpx: dpx_read() (dpx.cpp:209-520) aborts on --src_half_float_flag 1 (:232-236); the picture's size comes from the header,
  *             and main() refuses a header size that differs from --src_pic_width/--src_pic_height (the reference would hand
  *             convert() two different sizes)
+ *   .tiff: an integer input type at :321-372; read_tiff() (tiff.cpp:54-362) then forces bit depth 16, 4:4:4 and GBR on the
+ *             input picture with a warning each, keeps the range flag, and applies --cutout_hd / --cutout_qhd (ignored for every
+ *             other input, as there); the decoded size must be the command line's, as for .dpx
+ *   .tiff output: write_tiff() (tiff.cpp:559-652) from .yuv input only (hdr2yuv.cpp:818-819, 931-933); the file is opened "w"
  * Only user_args_t.chroma_resampler_type has no defined default there (never initialised): FIR here, as in
  * make.sh's example.  The reference calls exit(0) on its argument errors; this program returns 1.
  */
@@ -34,8 +38,8 @@
 
 #include "../../include/hdr2yuv_hip.h"
 
-enum { CLI_IN_NONE = 0, CLI_IN_YUV, CLI_IN_RGB, CLI_IN_F32, CLI_IN_F16, CLI_IN_SYNTH, CLI_IN_CODEC, CLI_IN_DPX };
-enum { CLI_OUT_NONE = 0, CLI_OUT_YUV, CLI_OUT_RGB, CLI_OUT_CODEC };
+enum { CLI_IN_NONE = 0, CLI_IN_YUV, CLI_IN_RGB, CLI_IN_F32, CLI_IN_F16, CLI_IN_SYNTH, CLI_IN_CODEC, CLI_IN_DPX, CLI_IN_TIFF };
+enum { CLI_OUT_NONE = 0, CLI_OUT_YUV, CLI_OUT_RGB, CLI_OUT_CODEC, CLI_OUT_TIFF };
 
 struct cli_pic { /* the attribute set of pic_t that the command line fills (hdr.h:363-378) */
     int width, height, bit_depth, half_float_flag, chroma_format_idc, video_full_range_flag;
@@ -47,12 +51,13 @@ struct cli_args {
     cli_pic in{}, out{};
     int start_frame = 0, n_frames = 1, verbose = 0;
     int resampler = 1;
+    int cutout = 0; /* H2Y_TIFF_CUTOUT_* bits of --cutout_hd / --cutout_qhd (read_tiff only) */
     /* additional flags of this build */
     int synthetic = -1, device = 0, gpus = 1, dry_run = 0, help = 0;
     std::vector<int> devices;
     /* resolved */
     int in_type = CLI_IN_NONE, out_type = CLI_OUT_NONE;
-    bool inverse = false; /* .yuv -> RGB: matrix_inverse() instead of matrix_convert() (hdr2yuv.cpp:818-819) */
+    bool inverse = false; /* .yuv -> RGB (.rgb or .tiff): matrix_inverse() instead of matrix_convert() (hdr2yuv.cpp:818-819) */
 };
 
 static inline const char *cli_ext_of(const char *fn)
@@ -61,9 +66,9 @@ static inline const char *cli_ext_of(const char *fn)
     return dot ? dot + 1 : "";
 }
 
-/* A --src_filename with one printf integer conversion (%d, %i or %u, optionally with a 0 flag and a width: shot.%06d.dpx)
- * numbers a sequence of .dpx files.  1: one such conversion and no other (a literal %% aside); 0: no conversion; -1: any
- * other use of '%' (the name is then refused rather than handed to printf). */
+/* A file name with one printf integer conversion (%d, %i or %u, optionally with a 0 flag and a width: shot.%06d.dpx)
+ * numbers a sequence of files (.dpx or .tiff input, .tiff output).  1: one such conversion and no other (a literal %% aside);
+ * 0: no conversion; -1: any other use of '%' (the name is then refused rather than handed to printf). */
 static inline int cli_frame_pattern(const char *fn)
 {
     int convs = 0;
@@ -100,9 +105,10 @@ static inline void cli_help()
            "  unset source attributes are 0, unset destination attributes take the source's (as the reference resolves them)\n"
            "  additional: [--synthetic SEEDFRAME] [--device D] [--gpus N [--devices d0,d1,..]] [--dry_run 1]\n"
            "input by extension: .yuv .rgb (16-bit planar), .f32 .f16 (raw planar float / half, plane order G,B,R: what\n"
-           "  dpx_read() / read_exr() leave in memory), .dpx (10-bit, 16-bit or float DPX, decoded on the GPU; one file per frame,\n"
-           "  shot.%%06d.dpx numbers them from --src_start_frame on); output: .yuv, or .rgb (planar R,G,B) from .yuv input = the\n"
-           "  .yuv -> .tiff flow\n");
+           "  dpx_read() / read_exr() leave in memory), .dpx (10-bit, 16-bit or float DPX) and .tiff (16-bit R,G,B, uncompressed; centre-cropped\n"
+           "  to 3840 wide, [--cutout_hd 1] 1920x1080, [--cutout_qhd 1] 960x540), both decoded on the GPU, one file per frame,\n"
+           "  shot.%%06d.dpx / .tiff numbering them from --src_start_frame on; output: .yuv, or from .yuv input .tiff (16-bit R,G,B;\n"
+           "  one file per frame, shot.%%06d.tiff for several) or .rgb (planar R,G,B: the .tiff's samples)\n");
 }
 
 /* hdr2yuv.cpp:73-263 */
@@ -118,7 +124,9 @@ static inline void cli_parse(cli_args &a, int argc, char **argv)
         if (is("--help")) { cli_help(); a.help = 1; } /* :82-85: prints and carries on */
         else if (is("--src_filename")) a.src = val();
         else if (is("--dst_filename")) a.dst = val();
-        else if (is("--ref_filename") || is("--sigma_compare") || is("--alpha_channel") || is("--cutout_hd") || is("--cutout_qhd")) (void)val();
+        else if (is("--ref_filename") || is("--sigma_compare") || is("--alpha_channel")) (void)val(); /* (read_tiff ignores alpha too) */
+        else if (is("--cutout_hd")) a.cutout = atoi(val()) ? (a.cutout | H2Y_TIFF_CUTOUT_HD) : (a.cutout & ~H2Y_TIFF_CUTOUT_HD);
+        else if (is("--cutout_qhd")) a.cutout = atoi(val()) ? (a.cutout | H2Y_TIFF_CUTOUT_QHD) : (a.cutout & ~H2Y_TIFF_CUTOUT_QHD);
         else if (is("--src_pic_width")) a.in.width = atoi(val());
         else if (is("--src_pic_height")) a.in.height = atoi(val());
         else if (is("--dst_pic_width")) a.out.width = atoi(val());
@@ -179,16 +187,17 @@ static inline int cli_resolve(cli_args &a)
     else if (!strcasecmp(ext, "f32")) a.in_type = CLI_IN_F32;
     else if (!strcasecmp(ext, "f16")) a.in_type = CLI_IN_F16;
     else if (!strcasecmp(ext, "dpx")) a.in_type = CLI_IN_DPX;
-    else if (!strcasecmp(ext, "exr") || !strcasecmp(ext, "tiff")) a.in_type = CLI_IN_CODEC;
+    else if (!strcasecmp(ext, "tiff")) a.in_type = CLI_IN_TIFF; /* not .tif: the reference's input_file_types name .tiff only */
+    else if (!strcasecmp(ext, "exr")) a.in_type = CLI_IN_CODEC;
     if (a.in_type == CLI_IN_NONE) {
         printf("WARNING: input file (%s) type extension (%s) is either not recongized or not supported\n", a.src ? a.src : "(none)", ext);
         arg_errors++;
     } else if (a.in_type == CLI_IN_CODEC) {
-        printf("WARNING: input file (%s): .%s decoding stays with the reference's host I/O (exr.cpp / tiff.cpp);\n"
-               "         this program takes the planes they leave in memory as .f16 / .f32 / .rgb\n", a.src, ext);
+        printf("WARNING: input file (%s): .%s decoding stays with the reference's host I/O (exr.cpp);\n"
+               "         this program takes the planes it leaves in memory as .f16 / .f32\n", a.src, ext);
         arg_errors++;
     }
-    const bool int_in = a.in_type == CLI_IN_YUV || a.in_type == CLI_IN_RGB;
+    const bool int_in = a.in_type == CLI_IN_YUV || a.in_type == CLI_IN_RGB || a.in_type == CLI_IN_TIFF; /* :336 */
     if (int_in) {
         if (a.in.bit_depth < 10 || a.in.bit_depth > 16)
             printf("WARNING: src bit_depth(%d) outside range [10,16] for integer input file type(%s)\n", a.in.bit_depth, ext);
@@ -201,25 +210,31 @@ static inline int cli_resolve(cli_args &a)
     ext = cli_ext_of(a.dst);
     if (!strcasecmp(ext, "yuv")) a.out_type = CLI_OUT_YUV;
     else if (!strcasecmp(ext, "rgb")) a.out_type = CLI_OUT_RGB;
-    else if (!strcasecmp(ext, "exr") || !strcasecmp(ext, "dpx") || !strcasecmp(ext, "tiff")) a.out_type = CLI_OUT_CODEC;
+    else if (!strcasecmp(ext, "tiff")) a.out_type = CLI_OUT_TIFF;
+    else if (!strcasecmp(ext, "exr") || !strcasecmp(ext, "dpx")) a.out_type = CLI_OUT_CODEC;
     if (a.out_type == CLI_OUT_NONE) {
         printf("WARNING: output file (%s) type extension (%s) is either not recongized or not supported\n", a.dst ? a.dst : "(none)", ext);
         arg_errors++;
     } else if (a.out_type == CLI_OUT_CODEC) {
-        printf("WARNING: output file (%s): the .%s writers stay with the reference's host I/O; this program writes .yuv, and the\n"
-               "         .yuv -> .tiff flow's samples as planar .rgb\n", a.dst, ext);
+        printf("WARNING: output file (%s): the .%s writers stay with the reference's host I/O; this program writes .yuv, and\n"
+               "         from .yuv input .tiff (or its samples as planar .rgb)\n", a.dst, ext);
         arg_errors++;
     } else if (a.out.bit_depth < 10 || a.out.bit_depth > 16)
         printf("WARNING: dst bit_depth(%d) outside range [10,16] for integer input file type(%s)\n", a.out.bit_depth, ext);
-    /* hdr2yuv.cpp:818: a .yuv read for a .tiff goes through matrix_inverse(); planar .rgb stands in for the .tiff's samples */
-    a.inverse = a.in_type == CLI_IN_YUV && a.out_type == CLI_OUT_RGB;
+    /* hdr2yuv.cpp:818: a .yuv read for a .tiff goes through matrix_inverse(); planar .rgb holds the same samples */
+    a.inverse = a.in_type == CLI_IN_YUV && (a.out_type == CLI_OUT_RGB || a.out_type == CLI_OUT_TIFF);
     if (a.out_type == CLI_OUT_RGB && !a.inverse) {
         printf("WARNING: .rgb output is the .yuv -> RGB flow's (matrix_inverse); the reference writes no .rgb either\n");
         arg_errors++;
     }
+    if (a.out_type == CLI_OUT_TIFF && !a.inverse) { /* the reference would hand write_tiff() the converted 4:2:0 / YCbCr planes */
+        printf("WARNING: .tiff output is the .yuv -> RGB flow's (matrix_inverse): it takes .yuv input only\n");
+        arg_errors++;
+    }
 
-    const bool numbered_dpx = a.in_type == CLI_IN_DPX && cli_frame_pattern(a.src) == 1;
-    if (a.start_frame != 0 && !int_in && a.in_type != CLI_IN_F32 && a.in_type != CLI_IN_F16 && a.in_type != CLI_IN_SYNTH && !numbered_dpx)
+    const bool numbered = (a.in_type == CLI_IN_DPX || a.in_type == CLI_IN_TIFF) && cli_frame_pattern(a.src) == 1;
+    if (a.start_frame != 0 && (!int_in || a.in_type == CLI_IN_TIFF) && a.in_type != CLI_IN_F32 && a.in_type != CLI_IN_F16 &&
+        a.in_type != CLI_IN_SYNTH && !numbered)
         printf("WARNING: start_frame(%d) only makes sense when file type is .yuv, .rgb, or .y4m\n", a.start_frame);
 
     /* :472-507: what was resolved */
@@ -247,8 +262,12 @@ static inline int cli_resolve(cli_args &a)
     if (a.out.width < 2 || a.out.width > 10000) { printf("WARNING: pic_width(%d) outside range [0,10000]\n", a.out.width); arg_errors++; }
     if (a.out.height < 2 || a.out.height > 10000) { printf("WARNING: pic_height(%d) outside range [0,10000]\n", a.out.height); arg_errors++; }
     if (a.out.bit_depth < 8 || a.out.bit_depth > 32) { printf("WARNING: dst bit_depth(%d) outside range [32]\n", a.out.bit_depth); arg_errors++; }
-    if (a.in_type == CLI_IN_DPX && cli_frame_pattern(a.src) < 0) {
+    if ((a.in_type == CLI_IN_DPX || a.in_type == CLI_IN_TIFF) && cli_frame_pattern(a.src) < 0) {
         printf("WARNING: input file name (%s): '%%' other than one integer conversion (%%d, %%0Nd) numbering the frames\n", a.src);
+        arg_errors++;
+    }
+    if (a.out_type == CLI_OUT_TIFF && cli_frame_pattern(a.dst) < 0) {
+        printf("WARNING: output file name (%s): '%%' other than one integer conversion (%%d, %%0Nd) numbering the frames\n", a.dst);
         arg_errors++;
     }
     if (arg_errors) return arg_errors;
@@ -261,6 +280,20 @@ static inline int cli_resolve(cli_args &a)
     if (a.in_type == CLI_IN_RGB && a.in.matrix_coeffs != H2Y_MATRIX_GBR) {
         printf("WARNING: RGB src matrix_coefs(%d) being overriden to MATRIX_GBR (%d)\n", a.in.matrix_coeffs, H2Y_MATRIX_GBR); /* :677-680 */
         a.in.matrix_coeffs = H2Y_MATRIX_GBR;
+    }
+    if (a.in_type == CLI_IN_TIFF) { /* read_tiff, tiff.cpp:214-225; the range flag stays the command line's */
+        if (a.in.bit_depth != 16) {
+            printf("WARNING, read_tiff(): bit_depth(%d) != 16-bit precision assumed for tiff input samples\n", a.in.bit_depth);
+            a.in.bit_depth = 16;
+        }
+        if (a.in.chroma_format_idc != H2Y_CHROMA_444) {
+            printf("WARNING, read_tiff(): chroma_format_idc(%d) != CHROMA_444 assumed for tiff input\n", a.in.chroma_format_idc);
+            a.in.chroma_format_idc = H2Y_CHROMA_444;
+        }
+        if (a.in.matrix_coeffs != H2Y_MATRIX_GBR) {
+            printf("WARNING, read_tiff(): matrix_coefs(%d) != MATRIX_GBR assumed for tiff input\n", a.in.matrix_coeffs);
+            a.in.matrix_coeffs = H2Y_MATRIX_GBR;
+        }
     }
     if (!int_in) { /* .dpx :729-734, .exr exr.cpp:172-183 */
         if (a.in.matrix_coeffs != H2Y_MATRIX_GBR) printf("overriding matrix_coeffs(%d) to MATRIX_GBR(%d)\n", a.in.matrix_coeffs, H2Y_MATRIX_GBR);

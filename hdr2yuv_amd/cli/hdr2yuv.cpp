@@ -4,17 +4,20 @@
  * planes to the C-ABI (include/hdr2yuv_hip.h) and writes the .yuv frames where write_yuv() would append them
  * (tiff.cpp:440: the file is opened in append mode; planes Y, Cb, Cr, little-endian 16-bit).
  *
- * File decoding stays where the reference has it (exr.cpp / tiff.cpp need OpenEXR and libtiff): this binary takes the
- * formats that need no codec:
+ * .exr decoding stays where the reference has it (exr.cpp needs OpenEXR): this binary takes the formats that need no codec:
  *   .yuv / .rgb  16-bit planar integer (hdr2yuv.cpp:582-656; .rgb is R,G,B in the file, planes 2,0,1 in memory)
  *   .f32 / .f16  raw planar float / half in G,B,R plane order -- what dpx_read() or read_exr() (exr.cpp:233-235) leave in
  *                memory; the attributes those readers force on the input picture are forced here too
  *   .dpx         10-bit, 16-bit or float DPX (dpx_read(), dpx.cpp:209-520): the header is parsed here (h2y_dpx_parse), the
  *                payload read straight into the pinned slot of the DPX ring and decoded on the device; one file is one
  *                frame, and a name with one integer conversion (shot.%06d.dpx) numbers the files of a sequence
+ *   .tiff        16-bit R,G,B TIFF (read_tiff(), tiff.cpp:54-362): the file is mapped and its IFD parsed here
+ *                (h2y_tiff_parse), the decoded rows read into the pinned slot of the TIFF ring and de-interleaved on the
+ *                device; numbered like .dpx
  *   --synthetic N  the seeded test frame of SURVEY 8c (no input file), treated as an .exr-like float input
- * and, from .yuv input, .rgb output: the .yuv -> .tiff flow (hdr2yuv.cpp:818-819, matrix_inverse) with the samples
- * write_tiff() would interleave written as planes R, G, B instead (no libtiff here).
+ * and, from .yuv input, the .yuv -> .tiff flow (hdr2yuv.cpp:818-819, matrix_inverse): .tiff output (write_tiff(),
+ * tiff.cpp:559-652; the samples interleaved on the device, the file bytes libtiff would write around them, one truncated
+ * file per frame, numbered through a name like shot.%06d.tiff) or the same samples as planes R, G, B in one .rgb.
  *
  * Several GPUs (--gpus N, an addition: the reference converts one frame per process): one host thread per GPU, each with
  * its own context and pinned ring; thread r takes a contiguous block of the frame indices (the split of
@@ -28,6 +31,7 @@
 #include <cstring>
 #include <fcntl.h>
 #include <string>
+#include <sys/mman.h>
 #include <sys/stat.h>
 #include <thread>
 #include <unistd.h>
@@ -140,6 +144,77 @@ static int dpx_scan(const cli_args &a, long want, h2y_dpx_info &info, std::vecto
     return 0;
 }
 
+/* one .tiff file of the run: its name and where its decoded rows lie */
+struct tiff_src {
+    std::string path;
+    std::vector<uint64_t> rows; /* file offset of each decoded row */
+    bool contiguous;
+};
+
+/* The .tiff files of the run, as dpx_scan: each mapped, its IFD parsed for read_tiff's geometry with the command line's
+ * cutouts, checked against the command line's size and against the first file's geometry and byte order. */
+static int tiff_scan(const cli_args &a, long want, h2y_tiff_info &info, std::vector<tiff_src> &files)
+{
+    const bool seq = cli_frame_pattern(a.src) == 1;
+    for (long k = 0; k < (seq ? want : 1); k++) {
+        const std::string path = cli_frame_name(a.src, a.start_frame + k);
+        const int fd = open(path.c_str(), O_RDONLY);
+        if (fd < 0) {
+            if (k) break; /* the sequence ends here */
+            printf("ERROR: unable to open file %s\n", path.c_str());
+            return 1;
+        }
+        struct stat st;
+        void *map = MAP_FAILED;
+        if (!fstat(fd, &st) && st.st_size > 0) map = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+        close(fd);
+        if (map == MAP_FAILED) { printf("ERROR: unable to map file %s\n", path.c_str()); return 1; }
+        h2y_tiff_info ti;
+        const char *why = nullptr;
+        int rc = h2y_tiff_parse(map, (size_t)st.st_size, a.cutout, &ti, nullptr, 0, &why);
+        tiff_src src{path, {}, false};
+        if (!rc) {
+            src.rows.resize((size_t)ti.height);
+            rc = h2y_tiff_parse(map, (size_t)st.st_size, a.cutout, &ti, src.rows.data(), ti.height, &why);
+        }
+        munmap(map, (size_t)st.st_size);
+        if (rc) { printf("ERROR: %s: %s\n", path.c_str(), why); return 1; }
+        if (ti.width != a.in.width || ti.height != a.in.height) {
+            printf("ERROR: %s decodes to %dx%d, --src_pic_width/--src_pic_height say %dx%d: resizing is not part of convert() (cv.cpp "
+                   "is compiled out in the reference)\n", path.c_str(), ti.width, ti.height, a.in.width, a.in.height);
+            return 1;
+        }
+        if (k && (ti.file_width != info.file_width || ti.file_height != info.file_height || ti.swap != info.swap)) {
+            printf("ERROR: %s is %dx%d %s-endian, %s %dx%d %s-endian: every file of a sequence must have the same\n", path.c_str(),
+                   ti.file_width, ti.file_height, ti.swap ? "big" : "little", files[0].path.c_str(), info.file_width, info.file_height,
+                   info.swap ? "big" : "little");
+            return 1;
+        }
+        if (!k && ti.swap)
+            printf("WARNING: %s is big-endian (MM): decoded with the bytes of each sample exchanged; the reference reads them unswapped\n",
+                   path.c_str());
+        src.contiguous = ti.contiguous != 0;
+        if (!k) info = ti;
+        files.push_back(std::move(src));
+    }
+    return 0;
+}
+
+/* n bytes at `at` of the open file fd into buf */
+static bool read_at(int fd, void *buf, size_t n, off_t at)
+{
+    char *p = (char *)buf;
+    while (n) {
+        ssize_t r = pread(fd, p, n, at);
+        if (r < 0 && errno == EINTR) continue;
+        if (r <= 0) return false;
+        p += r;
+        at += r;
+        n -= (size_t)r;
+    }
+    return true;
+}
+
 struct block { /* one thread's share: frames [first, first + count) of the run, on `device` */
     int device = 0;
     long first = 0, count = 0;
@@ -148,9 +223,9 @@ struct block { /* one thread's share: frames [first, first + count) of the run, 
 };
 
 /* forward path: frames [first, first+count) through one context's pinned ring (dpx: frame k is file dpx[k], decoded on the
- * device -- the ring of h2y_dpx_stream_open) */
-static void run_block(const cli_args &a, const h2y_desc &d, const std::vector<dpx_src> &dpx, const h2y_dpx_info &di, int fd_out,
-                      off_t base, block *b)
+ * device -- the ring of h2y_dpx_stream_open; tiff likewise, file tiff[k] through h2y_tiff_stream_open) */
+static void run_block(const cli_args &a, const h2y_desc &d, const std::vector<dpx_src> &dpx, const h2y_dpx_info &di,
+                      const std::vector<tiff_src> &tiff, const h2y_tiff_info &ti, int fd_out, off_t base, block *b)
 {
     h2y_ctx *ctx = nullptr;
     FILE *fin = nullptr;
@@ -162,7 +237,7 @@ static void run_block(const cli_args &a, const h2y_desc &d, const std::vector<dp
     if (b->count < 1) return;
     if (h2y_ctx_create(b->device, &ctx)) return fail(h2y_last_error(nullptr));
     const size_t pb = h2y_plane_bytes(&d), ob = h2y_frame_bytes(&d);
-    if (a.in_type != CLI_IN_SYNTH && a.in_type != CLI_IN_DPX) {
+    if (a.in_type != CLI_IN_SYNTH && a.in_type != CLI_IN_DPX && a.in_type != CLI_IN_TIFF) {
         fin = fopen(a.src, "rb");
         if (!fin) return fail(std::string("unable to open file ") + a.src);
         if (fseeko(fin, (off_t)(3 * pb) * (off_t)(a.start_frame + b->first), SEEK_SET)) return fail("seek failed"); /* hdr2yuv.cpp:624 */
@@ -170,7 +245,10 @@ static void run_block(const cli_args &a, const h2y_desc &d, const std::vector<dp
     /* The reader fills the pinned slot of the pipeline directly, the writer drains what comes out of it two frames
      * later: upload, conversion and download of neighbouring frames overlap. */
     const int depth = 3;
-    if (a.in_type == CLI_IN_DPX ? h2y_dpx_stream_open(ctx, &d, &di, depth) : h2y_stream_open(ctx, &d, depth)) return fail(h2y_last_error(ctx));
+    const int open_rc = a.in_type == CLI_IN_DPX    ? h2y_dpx_stream_open(ctx, &d, &di, depth)
+                        : a.in_type == CLI_IN_TIFF ? h2y_tiff_stream_open(ctx, &d, &ti, a.in.video_full_range_flag == 0, depth)
+                                                   : h2y_stream_open(ctx, &d, depth);
+    if (open_rc) return fail(h2y_last_error(ctx));
     long in_flight = 0;
     auto drain_one = [&]() -> bool {
         const uint16_t *yuv = nullptr;
@@ -193,6 +271,17 @@ static void run_block(const cli_args &a, const h2y_desc &d, const std::vector<dp
             if (!fseeko(fd, (off_t)src.offset, SEEK_SET)) got = fread(planes[0], 1, di.payload_bytes, fd);
             fclose(fd);
             if (got != di.payload_bytes) return fail("only " + std::to_string(got) + " payload bytes read from " + src.path);
+        } else if (a.in_type == CLI_IN_TIFF) { /* the decoded rows, whole: one read when they lie back to back, else one per row */
+            const tiff_src &src = tiff[b->first + f];
+            const int fd = open(src.path.c_str(), O_RDONLY);
+            if (fd < 0) return fail("unable to open file " + src.path);
+            bool ok = true;
+            char *dst = static_cast<char *>(planes[0]);
+            if (src.contiguous) ok = read_at(fd, dst, ti.payload_bytes, (off_t)src.rows[0]);
+            else
+                for (size_t r = 0; ok && r < src.rows.size(); r++) ok = read_at(fd, dst + r * ti.row_bytes, ti.row_bytes, (off_t)src.rows[r]);
+            close(fd);
+            if (!ok) return fail("short read from " + src.path);
         } else if (fin) {
             /* file plane order -> memory planes (0=G/Y, 1=B/Cb, 2=R/Cr); .rgb holds R,G,B (hdr2yuv.cpp:635-637) */
             const int order_rgb[3] = {2, 0, 1}, order_nat[3] = {0, 1, 2};
@@ -212,8 +301,15 @@ static void run_block(const cli_args &a, const h2y_desc &d, const std::vector<dp
     h2y_ctx_destroy(ctx);
 }
 
-/* .yuv -> RGB (matrix_inverse): frames [first, first+count) through one context's pinned inverse ring, as run_block */
-static void run_block_inverse(const cli_args &a, int fd_out, off_t base, block *b)
+/* the bytes libtiff writes around write_tiff()'s samples (h2y_tiff_layout) */
+struct tiff_wrap {
+    uint8_t head[8];
+    std::vector<uint8_t> tail;
+};
+
+/* .yuv -> RGB (matrix_inverse): frames [first, first+count) through one context's pinned inverse ring, as run_block; .tiff
+ * output: the ring with the interleave (h2y_tiff_inverse_stream_open), frame k into its own file, head + samples + tail */
+static void run_block_inverse(const cli_args &a, const tiff_wrap &tw, int fd_out, off_t base, block *b)
 {
     h2y_ctx *ctx = nullptr;
     FILE *fin = nullptr;
@@ -231,14 +327,27 @@ static void run_block_inverse(const cli_args &a, int fd_out, off_t base, block *
     if (!fin) return fail(std::string("unable to open file ") + a.src);
     if (fseeko(fin, (off_t)in_frame * (off_t)(a.start_frame + b->first), SEEK_SET)) return fail("seek failed");
     const int depth = 3;
-    if (h2y_inverse_stream_open(ctx, a.in.width, a.in.height, a.in.chroma_format_idc, a.in.bit_depth, a.in.video_full_range_flag,
-                                a.in.matrix_coeffs, a.out.bit_depth, a.resampler, depth))
+    const bool tiff = a.out_type == CLI_OUT_TIFF;
+    if ((tiff ? h2y_tiff_inverse_stream_open : h2y_inverse_stream_open)(ctx, a.in.width, a.in.height, a.in.chroma_format_idc,
+                                                                       a.in.bit_depth, a.in.video_full_range_flag, a.in.matrix_coeffs,
+                                                                       a.out.bit_depth, a.resampler, depth))
         return fail(h2y_last_error(ctx));
     long in_flight = 0;
     auto drain_one = [&]() -> bool {
         const uint16_t *gbr = nullptr;
         if (h2y_stream_output(ctx, &gbr)) { fail(h2y_last_error(ctx)); return false; }
         const long k = b->first + b->done;
+        if (tiff) { /* TIFFOpen(filename, "w"): a new file */
+            const std::string path = cli_frame_name(a.dst, a.start_frame + k);
+            const int fd = open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+            const bool ok = fd >= 0 && write_at(fd, tw.head, sizeof tw.head, 0) && write_at(fd, gbr, out_frame, sizeof tw.head) &&
+                            write_at(fd, tw.tail.data(), tw.tail.size(), (off_t)(sizeof tw.head + out_frame));
+            if (fd >= 0) close(fd);
+            if (!ok) { fail("unable to write " + path); return false; }
+            b->done++;
+            in_flight--;
+            return true;
+        }
         const off_t at = base + (off_t)k * (off_t)out_frame;
         /* planes G, B, R -> file order R, G, B (write_tiff: R, G, B per pixel) */
         if (!write_at(fd_out, gbr + 2 * n, 2 * n, at) || !write_at(fd_out, gbr, 4 * n, at + (off_t)(2 * n))) {
@@ -308,7 +417,19 @@ int main(int argc, char **argv)
     struct stat st;
     std::vector<dpx_src> dpx;
     h2y_dpx_info di{};
-    if (a.in_type == CLI_IN_DPX) { /* one file per frame; a dry run may name a file that is not there */
+    std::vector<tiff_src> tiff;
+    h2y_tiff_info ti{};
+    if (a.in_type == CLI_IN_TIFF) { /* as .dpx */
+        if (!(a.dry_run && stat(cli_frame_name(a.src, a.start_frame).c_str(), &st))) {
+            if (tiff_scan(a, frames, ti, tiff)) return 1;
+            frames = (long)tiff.size();
+            printf("tiff: %dx%d %s-endian, %d rows per strip, decoded %dx%d from (%d, %d), rows %s\n", ti.file_width, ti.file_height,
+                   ti.swap ? "big" : "little", ti.rows_per_strip, ti.width, ti.height, ti.x0, ti.y0,
+                   ti.contiguous ? "contiguous" : "scattered");
+        }
+        printf("src_picture: matrix_coeffs %d chroma_format_idc %d bit_depth %d video_full_range_flag %d\n", a.in.matrix_coeffs,
+               a.in.chroma_format_idc, a.in.bit_depth, a.in.video_full_range_flag);
+    } else if (a.in_type == CLI_IN_DPX) { /* one file per frame; a dry run may name a file that is not there */
         if (!(a.dry_run && stat(cli_frame_name(a.src, a.start_frame).c_str(), &st))) {
             if (dpx_scan(a, frames, di, dpx)) return 1;
             frames = (long)dpx.size();
@@ -335,12 +456,29 @@ int main(int argc, char **argv)
     printf("gpus: %d (devices", a.gpus);
     for (int dv : a.devices) printf(" %d", dv);
     printf(")\nframes: %ld\nframe_bytes: %zu\n", frames, out_frame_bytes);
+    tiff_wrap tw;
+    if (a.out_type == CLI_OUT_TIFF) {
+        if (frames > 1 && cli_frame_pattern(a.dst) != 1) {
+            printf("ERROR: %ld frames into one .tiff: a .tiff holds one frame; name them with one integer conversion (shot.%%06d.tiff)\n",
+                   frames);
+            return 1;
+        }
+        size_t tb = 0;
+        if (h2y_tiff_layout(a.in.width, a.in.height, tw.head, nullptr, &tb)) { printf("ERROR: %s\n", h2y_last_error(nullptr)); return 1; }
+        tw.tail.resize(tb);
+        if (h2y_tiff_layout(a.in.width, a.in.height, tw.head, tw.tail.data(), &tb)) { printf("ERROR: %s\n", h2y_last_error(nullptr)); return 1; }
+        printf("tiff_file_bytes: %zu\n", sizeof tw.head + out_frame_bytes + tb);
+    }
     if (a.dry_run) return 0;
 
-    /* tiff.cpp:440 opens ios::ate | ios::app: what is in the file stays, frames go behind it */
-    int fd = open(a.dst, O_WRONLY | O_CREAT, 0644);
-    if (fd < 0) { printf("ERROR: unable to open %s\n", a.dst); return 1; }
-    const off_t base = lseek(fd, 0, SEEK_END);
+    /* tiff.cpp:440 opens ios::ate | ios::app: what is in the file stays, frames go behind it (.tiff: one file per frame, below) */
+    int fd = -1;
+    off_t base = 0;
+    if (a.out_type != CLI_OUT_TIFF) {
+        fd = open(a.dst, O_WRONLY | O_CREAT, 0644);
+        if (fd < 0) { printf("ERROR: unable to open %s\n", a.dst); return 1; }
+        base = lseek(fd, 0, SEEK_END);
+    }
 
     /* contiguous blocks of frame indices, the first `frames % gpus` one longer (hdr2yuv_amd/shard.py) */
     std::vector<block> blocks(a.gpus);
@@ -351,14 +489,14 @@ int main(int argc, char **argv)
         blocks[r].count = frames / a.gpus + (r < frames % a.gpus ? 1 : 0);
         at += blocks[r].count;
     }
-    auto work = [&](block *b) { a.inverse ? run_block_inverse(a, fd, base, b) : run_block(a, d, dpx, di, fd, base, b); };
+    auto work = [&](block *b) { a.inverse ? run_block_inverse(a, tw, fd, base, b) : run_block(a, d, dpx, di, tiff, ti, fd, base, b); };
     if (a.gpus == 1) work(&blocks[0]);
     else {
         std::vector<std::thread> th;
         for (int r = 0; r < a.gpus; r++) th.emplace_back(work, &blocks[r]);
         for (auto &t : th) t.join();
     }
-    close(fd);
+    if (fd >= 0) close(fd);
     int rc = 0;
     for (int r = 0; r < a.gpus; r++)
         if (!blocks[r].err.empty()) {

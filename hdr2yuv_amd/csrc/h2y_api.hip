@@ -186,6 +186,11 @@ struct h2y_ctx {
     /* h2y_dpx_decode_batch's frame table, likewise; a DPX stream keeps one entry per slot in d_dpx_frames */
     dpx_frame *d_dpx_frames = nullptr, *h_dpx_frames = nullptr;
     size_t d_dpx_cap = 0, h_dpx_cap = 0; /* bytes */
+    /* h2y_tiff_decode_batch's and h2y_rgb_interleave_batch's frame tables, likewise; the TIFF rings keep one entry per slot */
+    tiff_frame *d_tiff_frames = nullptr, *h_tiff_frames = nullptr;
+    size_t d_tiff_cap = 0, h_tiff_cap = 0; /* bytes */
+    rgb_frame *d_rgb_frames = nullptr, *h_rgb_frames = nullptr;
+    size_t d_rgb_cap = 0, h_rgb_cap = 0; /* bytes */
 
     /* staging for the host-buffer entry */
     void *d_in = nullptr;
@@ -221,6 +226,14 @@ struct h2y_ctx {
     bool s_dpx = false;
     h2y_dpx_info s_dpx_info{};
     size_t s_dpx_off = 0;
+    /* a TIFF stream (h2y_tiff_stream_open): laid out as a DPX stream, u16 planes, the packed rows at s_tiff_off */
+    bool s_tiff = false, s_tiff_clamp = false;
+    h2y_tiff_info s_tiff_info{};
+    size_t s_tiff_off = 0;
+    /* a TIFF inverse stream (h2y_tiff_inverse_stream_open): an inverse stream whose slot output holds, at s_rgb_off after the
+     * G, B, R planes, the interleaved R,G,B samples that go down */
+    bool s_rgb = false;
+    size_t s_rgb_off = 0;
     size_t s_in_off[3] = {0, 0, 0}, s_in_bytes = 0, s_out_stride = 0;
     int slot_base = 0; /* run_frames(): first entry of d_frames/h_frames to use (one per stream slot) */
     float last_ms = 0.f;
@@ -1348,6 +1361,10 @@ void h2y_ctx_destroy(h2y_ctx *ctx)
     (void)hipHostFree(ctx->h_inv_frames);
     (void)hipFree(ctx->d_dpx_frames);
     (void)hipHostFree(ctx->h_dpx_frames);
+    (void)hipFree(ctx->d_tiff_frames);
+    (void)hipHostFree(ctx->h_tiff_frames);
+    (void)hipFree(ctx->d_rgb_frames);
+    (void)hipHostFree(ctx->h_rgb_frames);
     (void)hipFree(ctx->d_in);
     (void)hipFree(ctx->d_out);
     if (ctx->fir_stream) {
@@ -1992,6 +2009,8 @@ static void stream_free(h2y_ctx *ctx)
     ctx->streaming = false;
     ctx->s_inverse = false;
     ctx->s_dpx = false;
+    ctx->s_tiff = false;
+    ctx->s_rgb = false;
     ctx->s_head = ctx->s_tail = 0;
     ctx->s_lent = -1;
 }
@@ -2107,6 +2126,457 @@ int h2y_dpx_stream_open(h2y_ctx *ctx, const h2y_desc *d, const h2y_dpx_info *inf
     return H2Y_OK;
 }
 
+/* ---- 16-bit RGB TIFF (read_tiff(), tiff.cpp:54-362; write_tiff(), tiff.cpp:559-652) ------------------------------------- */
+
+namespace {
+
+struct tiff_reader { /* a classic TIFF in memory, in its byte order */
+    const unsigned char *p;
+    size_t n;
+    bool mm;
+    uint32_t u16(size_t at) const { return mm ? (uint32_t)p[at] << 8 | p[at + 1] : (uint32_t)p[at + 1] << 8 | p[at]; }
+    uint32_t u32(size_t at) const
+    {
+        return mm ? (uint32_t)p[at] << 24 | (uint32_t)p[at + 1] << 16 | (uint32_t)p[at + 2] << 8 | p[at + 3]
+                  : (uint32_t)p[at + 3] << 24 | (uint32_t)p[at + 2] << 16 | (uint32_t)p[at + 1] << 8 | p[at];
+    }
+};
+
+struct tiff_field { /* one IFD entry the decoder reads: SHORT or LONG values, inline or at `at` */
+    bool present = false;
+    uint32_t type = 0, count = 0;
+    size_t at = 0;
+    uint32_t get(const tiff_reader &r, uint32_t k) const { return type == 3 ? r.u16(at + 2 * (size_t)k) : r.u32(at + 4 * (size_t)k); }
+};
+
+} // namespace
+
+int h2y_tiff_parse(const void *file, size_t file_bytes, int cutout, h2y_tiff_info *out, uint64_t *row_offsets, int row_capacity,
+                   const char **why)
+{
+    const char *w = nullptr;
+    h2y_tiff_info ti{};
+    tiff_reader r{static_cast<const unsigned char *>(file), file_bytes, false};
+    tiff_field fw, fh, fbps, fcomp, fso, fspp, frps, fsbc, fplanar, ffmt;
+    auto parse = [&]() -> const char * {
+        if (!file || !out) return "null argument";
+        if (cutout & ~(H2Y_TIFF_CUTOUT_HD | H2Y_TIFF_CUTOUT_QHD)) return "cutout must be a combination of H2Y_TIFF_CUTOUT_HD and _QHD";
+        if (file_bytes < 8) return "not a TIFF: shorter than its 8-byte header";
+        if (r.p[0] == 'I' && r.p[1] == 'I') r.mm = false;
+        else if (r.p[0] == 'M' && r.p[1] == 'M') r.mm = true;
+        else return "not a TIFF: the byte order mark is neither II nor MM";
+        const uint32_t version = r.u16(2);
+        if (version == 43) return "BigTIFF is not supported (classic TIFF only)";
+        if (version != 42) return "not a TIFF: version is not 42";
+        const uint64_t ifd = r.u32(4);
+        if (ifd < 8 || ifd + 2 > file_bytes) return "truncated IFD: its offset is past the end of the file";
+        const uint32_t entries = r.u16((size_t)ifd);
+        if (ifd + 2 + 12ull * entries > file_bytes) return "truncated IFD: its entries run past the end of the file";
+        for (uint32_t e = 0; e < entries; e++) {
+            const size_t at = (size_t)ifd + 2 + 12 * (size_t)e;
+            tiff_field *f = nullptr;
+            switch (r.u16(at)) {
+            case 256: f = &fw; break;
+            case 257: f = &fh; break;
+            case 258: f = &fbps; break;
+            case 259: f = &fcomp; break;
+            case 273: f = &fso; break;
+            case 277: f = &fspp; break;
+            case 278: f = &frps; break;
+            case 279: f = &fsbc; break;
+            case 284: f = &fplanar; break;
+            case 339: f = &ffmt; break;
+            default: continue; /* tags read_tiff does not look at */
+            }
+            f->present = true;
+            f->type = r.u16(at + 2);
+            f->count = r.u32(at + 4);
+            if (f->type != 3 && f->type != 4) return "a tag the decoder reads is neither SHORT nor LONG";
+            if (f->count < 1) return "a tag the decoder reads has no value";
+            const uint64_t bytes = (uint64_t)f->count * (f->type == 3 ? 2 : 4);
+            f->at = bytes <= 4 ? at + 8 : (size_t)r.u32(at + 8);
+            if (bytes > 4 && (uint64_t)f->at + bytes > file_bytes) return "an array runs past the end of the file";
+        }
+        if (!fw.present || !fh.present || !fso.present || !fsbc.present)
+            return "ImageWidth, ImageLength, StripOffsets or StripByteCounts is missing";
+        if (fcomp.present && fcomp.get(r, 0) != 1) return "Compression is not 1 (uncompressed strips only)";
+        const uint32_t spp = fspp.present ? fspp.get(r, 0) : 1;
+        if (spp != 3) return "SamplesPerPixel is not 3 (R, G, B)";
+        if (!fbps.present) return "BitsPerSample is not 16";
+        for (uint32_t k = 0; k < spp; k++)
+            if (fbps.get(r, fbps.count < spp ? 0 : k) != 16) return "BitsPerSample is not 16";
+        const uint32_t planar = fplanar.present ? fplanar.get(r, 0) : 1;
+        if (planar == 2) return "PlanarConfig 2 (separate planes) is not supported";
+        if (planar != 1) return "PlanarConfig is not 1";
+        if (ffmt.present)
+            for (uint32_t k = 0; k < spp; k++)
+                if (ffmt.get(r, ffmt.count < spp ? 0 : k) != 1) return "SampleFormat is not 1 (unsigned integer)";
+        const uint32_t W = fw.get(r, 0), H = fh.get(r, 0);
+        if (W < 1 || H < 1 || W > (1u << 20) || H > (1u << 20)) return "ImageWidth or ImageLength is outside 1..1048576";
+        uint32_t rps = frps.present ? frps.get(r, 0) : H;
+        if (rps < 1) return "RowsPerStrip is 0";
+        if (rps > H) rps = H;
+        const uint32_t strips = (H + rps - 1) / rps;
+        if (fso.count != strips || fsbc.count != strips) return "StripOffsets or StripByteCounts does not have one entry per strip";
+        const uint64_t rb = 6ull * W;
+        for (uint32_t s = 0; s < strips; s++) {
+            const uint64_t rows = s + 1 < strips ? rps : H - (uint64_t)s * rps, bc = fsbc.get(r, s), off = fso.get(r, s);
+            if (rows == 1 && bc != rb) return "a one-row strip's byte count is not 6 x ImageWidth";
+            if (bc < rows * rb) return "a strip's byte count is less than its rows x 6 x ImageWidth";
+            if (off + bc > file_bytes) return "a strip runs past the end of the file";
+        }
+        /* read_tiff's geometry, in its uint32 arithmetic (stripsize = bc[0] = 6 W here) */
+        const uint32_t stripsize = (uint32_t)rb;
+        uint32_t start = 0;
+        if (stripsize > 960u * 6u) {
+            start = (stripsize - 3840u * 6u) / 2u;
+            if (start >= stripsize) start = 0; /* the reference's "bug fix" */
+            if (cutout & H2Y_TIFF_CUTOUT_HD) start = (stripsize - 1920u * 6u) / 2u;
+            if (cutout & H2Y_TIFF_CUTOUT_QHD) start = (stripsize - 960u * 6u) / 2u;
+        }
+        if (2ull * start >= stripsize) return "the cutout is wider than the picture (the reference's uint32 arithmetic wraps)";
+        if (start % 6u) return "the horizontal crop starts inside a pixel (odd ImageWidth): the reference misaligns the channels";
+        int strip_start = 0;
+        if (cutout & H2Y_TIFF_CUTOUT_HD) strip_start = ((int)H - 1080) / 2;
+        if (cutout & H2Y_TIFF_CUTOUT_QHD) strip_start = ((int)H - 540) / 2;
+        if (strip_start < 0) return "the cutout is taller than the picture";
+        ti.file_width = (int32_t)W;
+        ti.file_height = (int32_t)H;
+        ti.rows_per_strip = (int32_t)rps;
+        ti.swap = r.mm;
+        ti.x0 = (int32_t)(start / 6u);
+        ti.y0 = strip_start;
+        ti.width = (int32_t)((stripsize - start) / 6u - start / 6u);
+        ti.height = (int32_t)H - 2 * strip_start;
+        if (ti.width < 1 || ti.height < 1) return "the decoded picture is empty";
+        if ((uint64_t)ti.width * (uint64_t)ti.height >= (1ull << 28)) return "the decoded picture has 2^28 pixels or more";
+        ti.row_bytes = rb;
+        ti.payload_bytes = (uint64_t)ti.height * rb;
+        if (row_offsets && row_capacity < ti.height) return "row_capacity is less than the decoded height";
+        ti.contiguous = 1;
+        for (int32_t k = 0; k < ti.height; k++) {
+            const uint32_t y = (uint32_t)(ti.y0 + k);
+            const uint64_t off = (uint64_t)fso.get(r, y / rps) + (uint64_t)(y % rps) * rb;
+            if (!k) ti.data_offset = off;
+            else if (off != ti.data_offset + (uint64_t)k * rb) ti.contiguous = 0;
+            if (row_offsets) row_offsets[k] = off;
+        }
+        return nullptr;
+    };
+    w = parse();
+    if (why) *why = w ? w : "";
+    if (w) return fail(nullptr, H2Y_EINVAL, "%s", w);
+    *out = ti;
+    return H2Y_OK;
+}
+
+int h2y_tiff_layout(int width, int height, uint8_t head[8], uint8_t *tail, size_t *tail_bytes)
+{
+    if (!head || !tail_bytes) return fail(nullptr, H2Y_EINVAL, "null argument");
+    if (width < 1 || height < 1) return fail(nullptr, H2Y_EINVAL, "width and height must be >= 1");
+    const uint64_t W = (uint64_t)width, H = (uint64_t)height, rb = 6 * W, ifd = 8 + rb * H;
+    /* libtiff 4.3's choices for write_tiff's tags: sizes SHORT up to 65535; StripByteCounts LONG for one strip, else SHORT
+     * while a row fits in 16 bits; StripOffsets LONG; arrays of more than 4 bytes out of line, after the IFD, in the order
+     * BitsPerSample, StripByteCounts, StripOffsets */
+    const int sbc_type = H == 1 || rb > 65535 ? 4 : 3;
+    const uint64_t sbc_bytes = H * (sbc_type == 3 ? 2 : 4), so_bytes = 4 * H;
+    const uint64_t bps_at = ifd + 2 + 10 * 12 + 4, sbc_at = bps_at + 6, so_at = sbc_at + (sbc_bytes > 4 ? sbc_bytes : 0);
+    const uint64_t end = so_at + (so_bytes > 4 ? so_bytes : 0);
+    if (end > 0xFFFFFFFFull) return fail(nullptr, H2Y_EINVAL, "a %dx%d TIFF needs 4 GiB or more (BigTIFF)", width, height);
+    const size_t need = (size_t)(end - ifd);
+    head[0] = head[1] = 'I';
+    head[2] = 42;
+    head[3] = 0;
+    for (int k = 0; k < 4; k++) head[4 + k] = (uint8_t)(ifd >> (8 * k));
+    if (!tail) {
+        *tail_bytes = need;
+        return H2Y_OK;
+    }
+    if (*tail_bytes < need) return fail(nullptr, H2Y_EINVAL, "tail needs %zu bytes, has %zu", need, *tail_bytes);
+    *tail_bytes = need;
+    memset(tail, 0, need);
+    auto put = [&](uint64_t at, uint64_t v, int bytes) {
+        for (int k = 0; k < bytes; k++) tail[at - ifd + k] = (uint8_t)(v >> (8 * k));
+    };
+    put(ifd, 10, 2);
+    uint64_t e = ifd + 2;
+    auto entry = [&](int tag, int type, uint64_t count, uint64_t value_or_offset) {
+        put(e, tag, 2);
+        put(e + 2, type, 2);
+        put(e + 4, count, 4);
+        put(e + 8, value_or_offset, type == 3 && count == 1 ? 2 : 4);
+        e += 12;
+    };
+    entry(256, W > 65535 ? 4 : 3, 1, W);
+    entry(257, H > 65535 ? 4 : 3, 1, H);
+    entry(258, 3, 3, bps_at);
+    entry(259, 3, 1, 1);
+    entry(262, 3, 1, 2);
+    entry(273, 4, H, H == 1 ? 8 : so_at);
+    entry(277, 3, 1, 3);
+    entry(278, 3, 1, 1);
+    if (sbc_bytes <= 4) { /* one LONG, or two SHORTs, inline */
+        put(e, 279, 2);
+        put(e + 2, sbc_type, 2);
+        put(e + 4, H, 4);
+        for (uint64_t k = 0; k < H; k++) put(e + 8 + k * (sbc_type == 3 ? 2 : 4), rb, sbc_type == 3 ? 2 : 4);
+        e += 12;
+    } else entry(279, sbc_type, H, sbc_at);
+    entry(284, 3, 1, 1);
+    put(e, 0, 4); /* no next IFD */
+    for (int k = 0; k < 3; k++) put(bps_at + 2 * k, 16, 2);
+    if (sbc_bytes > 4)
+        for (uint64_t k = 0; k < H; k++) put(sbc_at + k * (sbc_type == 3 ? 2 : 4), rb, sbc_type == 3 ? 2 : 4);
+    if (so_bytes > 4)
+        for (uint64_t k = 0; k < H; k++) put(so_at + 4 * k, 8 + k * rb, 4);
+    return H2Y_OK;
+}
+
+/* what h2y_tiff_parse can return, and nothing else */
+static int tiff_info_check(h2y_ctx *ctx, const h2y_tiff_info *ti)
+{
+    if (!ti) return fail(ctx, H2Y_EINVAL, "null h2y_tiff_info");
+    if (ti->file_width < 1 || ti->file_width > (1 << 20) || ti->file_height < 1 || ti->file_height > (1 << 20))
+        return fail(ctx, H2Y_EINVAL, "TIFF file_width and file_height must be 1..1048576");
+    if (ti->width < 1 || ti->height < 1 || ti->x0 < 0 || ti->y0 < 0 || ti->x0 + ti->width > ti->file_width ||
+        ti->y0 + ti->height > ti->file_height)
+        return fail(ctx, H2Y_EINVAL, "TIFF decoded picture (x0, y0, width, height) lies outside the file's");
+    if ((uint64_t)ti->width * (uint64_t)ti->height >= (1ull << 28)) return fail(ctx, H2Y_EINVAL, "TIFF decoded picture has 2^28 pixels or more");
+    if (ti->swap != 0 && ti->swap != 1) return fail(ctx, H2Y_EINVAL, "TIFF swap must be 0 or 1");
+    if (ti->row_bytes != 6ull * (uint64_t)ti->file_width) return fail(ctx, H2Y_EINVAL, "TIFF row_bytes is not 6 x file_width");
+    if (ti->payload_bytes != (uint64_t)ti->height * ti->row_bytes) return fail(ctx, H2Y_EINVAL, "TIFF payload_bytes is not height x row_bytes");
+    return H2Y_OK;
+}
+
+static tiff_geom tiff_geom_of(const h2y_tiff_info &ti)
+{
+    return tiff_geom{(uint32_t)ti.width, (uint32_t)ti.height, (uint32_t)ti.x0, (uint32_t)ti.row_bytes};
+}
+
+/* a grid of one block per unit of 256 threads, eight blocks of 256 per CU at most */
+static int unit_grid(const h2y_ctx *ctx, uint64_t units)
+{
+    const uint64_t max_grid = (uint64_t)ctx->n_cu * 8u;
+    return (int)(units < max_grid ? (units ? units : 1) : max_grid);
+}
+
+extern "C++" {
+
+/* the pinned host table of n entries and its device copy, grown as needed */
+template <typename T> static int frame_table(h2y_ctx *ctx, T *&d, size_t &dcap, T *&h, size_t &hcap, int n)
+{
+    const size_t tb = (size_t)n * sizeof(T);
+    int rc = ensure(ctx, d, dcap, tb);
+    if (rc) return rc;
+    if (hcap < tb) {
+        if (h) HIP_TRY(ctx, hipHostFree(h));
+        h = nullptr;
+        hcap = 0;
+        hipError_t e = hipHostMalloc((void **)&h, tb, hipHostMallocDefault);
+        if (e != hipSuccess) return fail(ctx, H2Y_ENOMEM, "hipHostMalloc(%zu): %s", tb, hipGetErrorString(e));
+        hcap = tb;
+    }
+    return H2Y_OK;
+}
+
+/* n_frames in launches of H2Y_TIFF_FRAMES_PER_LAUNCH, each timed with an event pair (launches past the last pair are timed by
+ * it), then a synchronisation; launch(f0, nf) enqueues one launch */
+template <typename F> static int timed_launches(h2y_ctx *ctx, int n_frames, const char *name, F launch)
+{
+    int launches = 0;
+    for (int f0 = 0; f0 < n_frames; f0 += H2Y_TIFF_FRAMES_PER_LAUNCH, launches++) {
+        const int nf = n_frames - f0 < H2Y_TIFF_FRAMES_PER_LAUNCH ? n_frames - f0 : H2Y_TIFF_FRAMES_PER_LAUNCH;
+        const int e = launches < kMaxEvents ? launches : kMaxEvents - 1;
+        if (launches < kMaxEvents) HIP_TRY(ctx, hipEventRecord(ctx->b->ev[e][0], ctx->stream));
+        HIP_TRY(ctx, launch(f0, nf));
+        HIP_TRY(ctx, hipEventRecord(ctx->b->ev[e][1], ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->b->n_ev = launches < kMaxEvents ? launches : kMaxEvents;
+    float ms = 0.f;
+    for (int i = 0; i < ctx->b->n_ev; i++) {
+        float t = 0.f;
+        HIP_TRY(ctx, hipEventElapsedTime(&t, ctx->b->ev[i][0], ctx->b->ev[i][1]));
+        ms += t;
+    }
+    ctx->last_ms = ms;
+    ctx->last_launches = launches;
+    ctx->last_name = name;
+    return H2Y_OK;
+}
+
+} // extern "C++"
+
+int h2y_tiff_decode_batch(h2y_ctx *ctx, const h2y_tiff_info *info, int clamp_video_range, int n_frames, const void *const *d_payload,
+                          uint16_t *const *d_planes)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
+    int rc = tiff_info_check(ctx, info);
+    if (rc) return rc;
+    if (clamp_video_range != 0 && clamp_video_range != 1) return fail(ctx, H2Y_EINVAL, "clamp_video_range must be 0 or 1");
+    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
+    if (!d_payload || !d_planes) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
+    for (int f = 0; f < n_frames; f++) {
+        if (!d_payload[f]) return fail(ctx, H2Y_EINVAL, "frame %d: payload is null", f);
+        if ((uintptr_t)d_payload[f] & 1u) return fail(ctx, H2Y_EINVAL, "frame %d: payload is not 2-byte aligned", f);
+        for (int c = 0; c < 3; c++) {
+            const uint16_t *p = d_planes[3 * f + c];
+            if (!p) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is null", f, c);
+            if ((uintptr_t)p & 1u) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is not 2-byte aligned", f, c);
+        }
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = frame_table(ctx, ctx->d_tiff_frames, ctx->d_tiff_cap, ctx->h_tiff_frames, ctx->h_tiff_cap, n_frames);
+    if (rc) return rc;
+    for (int f = 0; f < n_frames; f++) {
+        ctx->h_tiff_frames[f].payload = d_payload[f];
+        for (int c = 0; c < 3; c++) ctx->h_tiff_frames[f].plane[c] = d_planes[3 * f + c];
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_tiff_frames, ctx->h_tiff_frames, (size_t)n_frames * sizeof(tiff_frame), hipMemcpyHostToDevice,
+                                ctx->stream));
+    const tiff_geom g = tiff_geom_of(*info);
+    const uint64_t per_frame = h2y_tiff_chunks(g.width, g.height);
+    rc = timed_launches(ctx, n_frames, "k_tiff_decode", [&](int f0, int nf) {
+        return h2y_launch_tiff_decode(info->swap != 0, clamp_video_range != 0, unit_grid(ctx, per_frame * nf), ctx->stream, g,
+                                      ctx->d_tiff_frames + f0, nf);
+    });
+    if (rc) return rc;
+    ctx->last_variant = std::string("k_tiff_decode<") + (info->swap ? "SWAP" : "NOSWAP") + (clamp_video_range ? ",CLAMP>" : ",NOCLAMP>");
+    return H2Y_OK;
+}
+
+static int rgb_size_check(h2y_ctx *ctx, int width, int height)
+{
+    if (width < 1 || height < 1 || (uint64_t)width * (uint64_t)height >= (1ull << 28)) return fail(ctx, H2Y_EINVAL, "bad picture size");
+    return H2Y_OK;
+}
+
+int h2y_rgb_interleave_batch(h2y_ctx *ctx, int width, int height, int n_frames, const uint16_t *const *d_planes, uint16_t *const *d_rgb)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
+    int rc = rgb_size_check(ctx, width, height);
+    if (rc) return rc;
+    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
+    if (!d_planes || !d_rgb) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
+    for (int f = 0; f < n_frames; f++) {
+        if (!d_rgb[f]) return fail(ctx, H2Y_EINVAL, "frame %d: output is null", f);
+        if ((uintptr_t)d_rgb[f] & 1u) return fail(ctx, H2Y_EINVAL, "frame %d: output is not 2-byte aligned", f);
+        for (int c = 0; c < 3; c++) {
+            const uint16_t *p = d_planes[3 * f + c];
+            if (!p) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is null", f, c);
+            if ((uintptr_t)p & 1u) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is not 2-byte aligned", f, c);
+        }
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = frame_table(ctx, ctx->d_rgb_frames, ctx->d_rgb_cap, ctx->h_rgb_frames, ctx->h_rgb_cap, n_frames);
+    if (rc) return rc;
+    for (int f = 0; f < n_frames; f++) {
+        for (int c = 0; c < 3; c++) ctx->h_rgb_frames[f].plane[c] = d_planes[3 * f + c];
+        ctx->h_rgb_frames[f].rgb = d_rgb[f];
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_rgb_frames, ctx->h_rgb_frames, (size_t)n_frames * sizeof(rgb_frame), hipMemcpyHostToDevice,
+                                ctx->stream));
+    const uint32_t npix = (uint32_t)width * (uint32_t)height;
+    const uint64_t per_frame = h2y_rgb_chunks(npix);
+    rc = timed_launches(ctx, n_frames, "k_rgb_interleave", [&](int f0, int nf) {
+        return h2y_launch_rgb_interleave(unit_grid(ctx, per_frame * nf), ctx->stream, npix, ctx->d_rgb_frames + f0, nf);
+    });
+    if (rc) return rc;
+    ctx->last_variant = "k_rgb_interleave";
+    return H2Y_OK;
+}
+
+/* The forward ring on TIFF rows: as h2y_dpx_stream_open, with the slot's device twin holding three u16 planes (each 256-byte
+ * aligned) and then the packed rows; each slot's k_tiff_decode table entry is uploaded here once */
+int h2y_tiff_stream_open(h2y_ctx *ctx, const h2y_desc *d, const h2y_tiff_info *info, int clamp_video_range, int depth)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is already open");
+    int rc = tiff_info_check(ctx, info);
+    if (rc) return rc;
+    if (clamp_video_range != 0 && clamp_video_range != 1) return fail(ctx, H2Y_EINVAL, "clamp_video_range must be 0 or 1");
+    const char *why;
+    rc = h2y_desc_check(d, &why);
+    if (rc) return fail(ctx, rc, "descriptor: %s", why);
+    if (d->in_sample_type != H2Y_SAMPLE_U16 || d->src_bit_depth != 16)
+        return fail(ctx, H2Y_EINVAL, "a TIFF stream decodes to 16-bit planes: in_sample_type must be H2Y_SAMPLE_U16, src_bit_depth 16");
+    if (d->width != info->width || d->height != info->height)
+        return fail(ctx, H2Y_EINVAL, "TIFF picture is %dx%d, the descriptor %dx%d (resizing is not part of convert())", info->width,
+                    info->height, d->width, d->height);
+    if (depth < 2 || depth > 16) return fail(ctx, H2Y_EINVAL, "depth must be 2..16");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = reserve_batch(ctx, 64);
+    if (rc) return rc;
+    rc = ensure(ctx, ctx->d_tiff_frames, ctx->d_tiff_cap, (size_t)depth * sizeof(tiff_frame));
+    if (rc) return rc;
+    const size_t pb = h2y_plane_bytes(d), ob = h2y_frame_bytes(d);
+    ctx->s_plane_al = (pb + 255) & ~(size_t)255;
+    ctx->s_desc = *d;
+    for (int c = 0; c < 3; c++) ctx->s_in_off[c] = c * ctx->s_plane_al;
+    ctx->s_tiff_off = 3 * ctx->s_plane_al;
+    rc = stream_alloc(ctx, depth, info->payload_bytes, ctx->s_tiff_off + info->payload_bytes, ob, ob);
+    if (rc) return rc;
+    std::vector<tiff_frame> tab(depth);
+    for (int k = 0; k < depth; k++) {
+        tab[k].payload = ctx->ss[k].d_in + ctx->s_tiff_off;
+        for (int c = 0; c < 3; c++) tab[k].plane[c] = reinterpret_cast<uint16_t *>(ctx->ss[k].d_in + ctx->s_in_off[c]);
+    }
+    hipError_t e = hipMemcpy(ctx->d_tiff_frames, tab.data(), tab.size() * sizeof(tiff_frame), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        stream_free(ctx);
+        return fail(ctx, H2Y_EHIP, "hipMemcpy of the TIFF slot table: %s", hipGetErrorString(e));
+    }
+    ctx->s_tiff = true;
+    ctx->s_tiff_clamp = clamp_video_range != 0;
+    ctx->s_tiff_info = *info;
+    return H2Y_OK;
+}
+
+/* The inverse ring with write_tiff's interleave: the slot's device output holds the G, B, R planes (as an inverse stream lays
+ * them out) and then, 256-byte aligned, the interleaved samples; only those go down.  Each slot's k_rgb_interleave table entry
+ * is uploaded here once. */
+int h2y_tiff_inverse_stream_open(h2y_ctx *ctx, int width, int height, int in_chroma_format_idc, int in_bit_depth, int in_full_range,
+                                 int in_matrix_coeffs, int out_bit_depth, int algorithm, int depth)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is already open");
+    const inv_params p{width, height, in_chroma_format_idc, in_bit_depth, in_full_range, in_matrix_coeffs, out_bit_depth, algorithm};
+    int rc = inverse_check(ctx, p);
+    if (rc) return rc;
+    if (depth < 2 || depth > 16) return fail(ctx, H2Y_EINVAL, "depth must be 2..16");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = ensure(ctx, ctx->d_rgb_frames, ctx->d_rgb_cap, (size_t)depth * sizeof(rgb_frame));
+    if (rc) return rc;
+    const size_t pb = (size_t)width * height * sizeof(uint16_t), pb_al = (pb + 255) & ~(size_t)255;
+    const size_t cb = in_chroma_format_idc == H2Y_CHROMA_420 ? (size_t)(width >> 1) * (height >> 1) * sizeof(uint16_t) : pb;
+    const size_t cb_al = (cb + 255) & ~(size_t)255;
+    ctx->s_in_off[0] = 0;
+    ctx->s_in_off[1] = pb_al;
+    ctx->s_in_off[2] = pb_al + cb_al;
+    ctx->s_in_bytes = pb_al + cb_al + cb;
+    ctx->s_out_stride = (pb & 15) ? pb_al : pb;
+    ctx->s_rgb_off = (2 * ctx->s_out_stride + pb + 255) & ~(size_t)255;
+    ctx->s_inv = p;
+    rc = stream_alloc(ctx, depth, ctx->s_in_bytes, ctx->s_in_bytes, 3 * pb, ctx->s_rgb_off + 3 * pb);
+    if (rc) return rc;
+    std::vector<rgb_frame> tab(depth);
+    for (int k = 0; k < depth; k++) {
+        char *o = reinterpret_cast<char *>(ctx->ss[k].d_out);
+        for (int c = 0; c < 3; c++) tab[k].plane[c] = reinterpret_cast<const uint16_t *>(o + c * ctx->s_out_stride);
+        tab[k].rgb = reinterpret_cast<uint16_t *>(o + ctx->s_rgb_off);
+    }
+    hipError_t e = hipMemcpy(ctx->d_rgb_frames, tab.data(), tab.size() * sizeof(rgb_frame), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        stream_free(ctx);
+        return fail(ctx, H2Y_EHIP, "hipMemcpy of the TIFF inverse slot table: %s", hipGetErrorString(e));
+    }
+    ctx->s_inverse = true;
+    ctx->s_rgb = true;
+    return H2Y_OK;
+}
+
 /* one frame of an inverse stream: H2D of its planes, k_inverse420 / k_inverse on the context's stream, D2H of G, B, R */
 static int inverse_stream_submit(h2y_ctx *ctx, int slot)
 {
@@ -2134,9 +2604,15 @@ static int inverse_stream_submit(h2y_ctx *ctx, int slot)
         if (blocks < 1) blocks = 1;
         HIP_TRY(ctx, h2y_launch_inverse((int)blocks, ctx->stream, a.inv));
     }
+    if (ctx->s_rgb) { /* write_tiff's interleave into the slot's device output behind the planes */
+        const uint32_t npix = (uint32_t)p.width * (uint32_t)p.height;
+        HIP_TRY(ctx, h2y_launch_rgb_interleave(unit_grid(ctx, h2y_rgb_chunks(npix)), ctx->stream, npix, ctx->d_rgb_frames + slot, 1));
+    }
     HIP_TRY(ctx, hipEventRecord(s.ev_conv, ctx->stream));
     HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_d2h, s.ev_conv, 0));
-    if (so == pb) HIP_TRY(ctx, hipMemcpyAsync(s.h_out, s.d_out, 3 * pb, hipMemcpyDeviceToHost, ctx->s_d2h));
+    if (ctx->s_rgb)
+        HIP_TRY(ctx, hipMemcpyAsync(s.h_out, reinterpret_cast<char *>(s.d_out) + ctx->s_rgb_off, 3 * pb, hipMemcpyDeviceToHost, ctx->s_d2h));
+    else if (so == pb) HIP_TRY(ctx, hipMemcpyAsync(s.h_out, s.d_out, 3 * pb, hipMemcpyDeviceToHost, ctx->s_d2h));
     else
         for (int c = 0; c < 3; c++)
             HIP_TRY(ctx, hipMemcpyAsync(reinterpret_cast<char *>(s.h_out) + c * pb, reinterpret_cast<char *>(s.d_out) + c * so, pb,
@@ -2155,7 +2631,7 @@ int h2y_stream_input(h2y_ctx *ctx, void *planes[3])
     if (s.state == 1) { /* asked twice without a submit: same buffers again */
     } else if (s.state != 0) return fail(ctx, H2Y_EINVAL, "all %d slots are in flight: take an output first", (int)ctx->ss.size());
     s.state = 1;
-    if (ctx->s_dpx) { /* the payload, as the file holds it */
+    if (ctx->s_dpx || ctx->s_tiff) { /* the payload, as the file holds it (TIFF: the decoded rows, packed) */
         planes[0] = s.h_in;
         planes[1] = planes[2] = nullptr;
         return H2Y_OK;
@@ -2179,6 +2655,8 @@ int h2y_stream_submit(h2y_ctx *ctx)
     for (int c = 0; c < 3; c++) io.in[c] = s.d_in + c * ctx->s_plane_al;
     if (ctx->s_dpx) /* the payload goes up; k_dpx_decode writes the three planes below */
         HIP_TRY(ctx, hipMemcpyAsync(s.d_in + ctx->s_dpx_off, s.h_in, ctx->s_dpx_info.payload_bytes, hipMemcpyHostToDevice, ctx->s_h2d));
+    else if (ctx->s_tiff) /* likewise the rows for k_tiff_decode */
+        HIP_TRY(ctx, hipMemcpyAsync(s.d_in + ctx->s_tiff_off, s.h_in, ctx->s_tiff_info.payload_bytes, hipMemcpyHostToDevice, ctx->s_h2d));
     else /* the slot's three planes lie one after the other (each padded to 256 bytes): one copy command, not three */
         HIP_TRY(ctx, hipMemcpyAsync(s.d_in, s.h_in, 2 * ctx->s_plane_al + pb, hipMemcpyHostToDevice, ctx->s_h2d));
     io.out = s.d_out;
@@ -2189,6 +2667,12 @@ int h2y_stream_submit(h2y_ctx *ctx)
         const h2y_dpx_info &di = ctx->s_dpx_info;
         HIP_TRY(ctx, h2y_launch_dpx_decode(dpx_fmt_of(di.bit_size), di.swap != 0, dpx_grid(ctx, di, 1), ctx->stream,
                                            (uint32_t)di.width * (uint32_t)di.height, ctx->d_dpx_frames + slot, 1));
+    }
+    if (ctx->s_tiff) {
+        const h2y_tiff_info &ti = ctx->s_tiff_info;
+        const tiff_geom g = tiff_geom_of(ti);
+        HIP_TRY(ctx, h2y_launch_tiff_decode(ti.swap != 0, ctx->s_tiff_clamp, unit_grid(ctx, h2y_tiff_chunks(g.width, g.height)), ctx->stream,
+                                            g, ctx->d_tiff_frames + slot, 1));
     }
     const bool needs_stats = d->src_transfer != d->dst_transfer;
     int rc;

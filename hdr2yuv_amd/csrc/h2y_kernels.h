@@ -230,4 +230,23 @@ struct dpx_frame {
 uint32_t h2y_dpx_chunks(int fmt, uint32_t npix); /* k_dpx_decode's units of 256 threads per frame */
 hipError_t h2y_launch_dpx_decode(int fmt, bool swap, int grid, hipStream_t st, uint32_t npix, const dpx_frame *frames, int n_frames);
 
+/* k_tiff_decode and k_rgb_interleave (h2y_tiff.hip): read_tiff()'s and write_tiff()'s per-pixel work on the device */
+struct tiff_geom { /* the decoded picture within `height` packed rows of row_bytes */
+    uint32_t width, height, x0, row_bytes;
+};
+/* one frame: its packed rows of interleaved R,G,B u16 in, the planes G, B, R out */
+struct tiff_frame {
+    const void *payload;
+    uint16_t *plane[3];
+};
+/* one frame: planes G, B, R in, interleaved R,G,B u16 out */
+struct rgb_frame {
+    const uint16_t *plane[3];
+    uint16_t *rgb;
+};
+uint32_t h2y_tiff_chunks(uint32_t width, uint32_t height); /* k_tiff_decode's units of 256 threads per frame */
+uint32_t h2y_rgb_chunks(uint32_t npix);                    /* k_rgb_interleave's */
+hipError_t h2y_launch_tiff_decode(bool swap, bool clamp, int grid, hipStream_t st, const tiff_geom &g, const tiff_frame *frames, int n_frames);
+hipError_t h2y_launch_rgb_interleave(int grid, hipStream_t st, uint32_t npix, const rgb_frame *frames, int n_frames);
+
 #endif

@@ -315,14 +315,96 @@ int h2y_dpx_decode_batch(h2y_ctx *ctx, const h2y_dpx_info *info, int n_frames, c
  * rules are those of the forward stream. */
 int h2y_dpx_stream_open(h2y_ctx *ctx, const h2y_desc *d, const h2y_dpx_info *info, int depth /* 2..16 slots */);
 
-/* Timing of the last h2y_convert_batch*() (or h2y_inverse_*, h2y_dpx_decode_batch) call measured with HIP events on
+/* ---- 16-bit RGB TIFF input and output (read_tiff(), tiff.cpp:54-362; write_tiff(), tiff.cpp:559-652) -----------------------
+ * The IFD and the file I/O stay on the host; the per-pixel work runs on the device (k_tiff_decode, k_rgb_interleave).  What a
+ * TIFF is to read_tiff: uncompressed strips of interleaved u16 R, G, B read raw (TIFFReadRawStrip), strip s = row s; a row is
+ * bc[0] = 6 x ImageWidth bytes.  Geometry, with stripsize = bc[0] in uint32 arithmetic:
+ *   start = 0; if stripsize > 960*6: start = (stripsize - 3840*6)/2, 0 when that wraps past stripsize; then --cutout_hd:
+ *   (stripsize - 1920*6)/2, --cutout_qhd: (stripsize - 960*6)/2 (qhd wins); rows: stripStart = (N - 1080)/2 (hd) or
+ *   (N - 540)/2 (qhd) of the N rows; width = (stripsize - start)/6 - start/6, height = N - 2 stripStart.
+ * A picture wider than 3840 is centre-cropped to 3840; the cutouts centre-crop to 1920x1080 / 960x540.  Each sample is
+ * clamped to [4096, 60160] when the input picture is video range; planes G, B, R.  Extensions over the reference: any number of
+ * rows (it exits unless N is 1080 or 2160), RowsPerStrip > 1 (row r at StripOffsets[r / RPS] + (r % RPS) x 6W), and "MM" files
+ * decoded with the bytes of each sample exchanged (the reference reads them unswapped). */
+#define H2Y_TIFF_CUTOUT_HD 1  /* --cutout_hd 1 */
+#define H2Y_TIFF_CUTOUT_QHD 2 /* --cutout_qhd 1; with both bits set qhd wins, as in read_tiff */
+
+typedef struct h2y_tiff_info {
+    int32_t file_width;     /* ImageWidth */
+    int32_t file_height;    /* ImageLength */
+    int32_t rows_per_strip; /* RowsPerStrip (ImageLength where the tag is absent or larger) */
+    int32_t swap;           /* 1: an "MM" (big-endian) file: the bytes of every sample are exchanged */
+    int32_t width;          /* the decoded picture: pixels x0 .. x0 + width - 1 of rows y0 .. y0 + height - 1 */
+    int32_t height;
+    int32_t x0;
+    int32_t y0;
+    uint64_t row_bytes;     /* 6 x file_width: one file row */
+    uint64_t payload_bytes; /* height x row_bytes: the decoded rows, whole, one after the other */
+    uint64_t data_offset;   /* file offset of row y0 */
+    int32_t contiguous;     /* 1: the decoded rows lie back to back in the file from data_offset on (one read fills a slot) */
+    int32_t reserved;       /* 0 */
+} h2y_tiff_info;
+
+/* Parse a classic TIFF held whole in memory (file: file_bytes bytes) for read_tiff's decode with `cutout` (H2Y_TIFF_CUTOUT_*
+ * bits).  Host only: no device, no context.  row_offsets (may be NULL) receives the file offset of each decoded row; it needs
+ * room for info.height entries (row_capacity).  Refuses (H2Y_EINVAL, `why` a static string): a file that is not a classic TIFF,
+ * BigTIFF, Compression other than 1, BitsPerSample other than 16 for any sample, SamplesPerPixel other than 3, PlanarConfig
+ * 2, SampleFormat other than 1, a strip or an array past the end of the file, a truncated IFD, a one-row strip whose byte count
+ * is not 6 x ImageWidth, a horizontal crop that starts inside a pixel (odd ImageWidth: the reference misaligns the channels),
+ * and a cutout larger than the picture (the reference's uint32 arithmetic wraps). */
+int h2y_tiff_parse(const void *file, size_t file_bytes, int cutout, h2y_tiff_info *out, uint64_t *row_offsets, int row_capacity,
+                   const char **why);
+
+/* The bytes of a TIFF file that go before (head: 8) and after (tail: *tail_bytes) the 6 x width x height bytes of interleaved
+ * R,G,B u16 samples: head + samples + tail is, byte for byte, the file libtiff 4.3 writes for write_tiff's call sequence
+ * (SamplesPerPixel 3, BitsPerSample 16, PlanarConfig 1, ImageWidth, ImageLength, RowsPerStrip 1, Photometric 2, one raw strip
+ * per row): the strips from offset 8 on, then the IFD with its ten entries (Compression 1 included) and its out-of-line
+ * arrays.  tail NULL: *tail_bytes receives the size only; otherwise *tail_bytes is tail's capacity on entry and the size on
+ * return.  Refuses a size < 1 and a file that would need BigTIFF (4 GiB or more). */
+int h2y_tiff_layout(int width, int height, uint8_t head[8], uint8_t *tail, size_t *tail_bytes);
+
+/* Frames per launch of h2y_tiff_decode_batch and h2y_rgb_interleave_batch. */
+#define H2Y_TIFF_FRAMES_PER_LAUNCH 64
+
+/* read_tiff's per-pixel loop on n_frames payloads of one geometry, device buffers:
+ *   d_payload[f]       device pointer to frame f's payload_bytes (the decoded rows, whole, as h2y_tiff_parse laid them out),
+ *                      2-byte aligned
+ *   d_planes[f*3 + c]  device pointers to frame f's u16 planes G, B, R (width x height each), 2-byte aligned
+ * clamp_video_range: 1 for a video-range input picture ([4096, 60160]), 0 to keep the samples.  16-byte accesses where a
+ * frame's payload, row_bytes and x0 (and its planes) allow them.  Synchronous.  Chain it with h2y_convert_batch
+ * (in_sample_type H2Y_SAMPLE_U16, src_bit_depth 16) for the .tiff -> .yuv flow on device buffers. */
+int h2y_tiff_decode_batch(h2y_ctx *ctx, const h2y_tiff_info *info, int clamp_video_range, int n_frames,
+                          const void *const *d_payload, uint16_t *const *d_planes);
+
+/* write_tiff's interleave on n_frames of width x height: d_planes[f*3 + c] = frame f's u16 planes G, B, R, d_rgb[f] its
+ * 3 x width x height interleaved R,G,B u16 output (device pointers, 2-byte aligned).  Synchronous. */
+int h2y_rgb_interleave_batch(h2y_ctx *ctx, int width, int height, int n_frames, const uint16_t *const *d_planes,
+                             uint16_t *const *d_rgb);
+
+/* The h2y_stream_* ring of h2y_stream_open on TIFF rows: each slot does one H2D copy of payload_bytes, k_tiff_decode into the
+ * slot's device u16 planes, the forward conversion of d (in_sample_type H2Y_SAMPLE_U16, src_bit_depth 16, width and height
+ * the info's decoded ones) and one D2H copy of the .yuv frame.  clamp_video_range as for h2y_tiff_decode_batch (the input
+ * picture's range flag: h2y_desc has none).  h2y_stream_input hands out planes[0] = the pinned payload (fill it with the
+ * decoded rows: payload_bytes from data_offset when contiguous, else row by row from the parse's row offsets), planes[1] =
+ * planes[2] = NULL; the rest and the exclusivity rules are those of the forward stream. */
+int h2y_tiff_stream_open(h2y_ctx *ctx, const h2y_desc *d, const h2y_tiff_info *info, int clamp_video_range,
+                         int depth /* 2..16 slots */);
+
+/* The inverse ring of h2y_inverse_stream_open with write_tiff's interleave after the inverse kernel: h2y_stream_output returns
+ * width x height x 3 u16, R, G, B per pixel -- the samples between h2y_tiff_layout's head and tail. */
+int h2y_tiff_inverse_stream_open(h2y_ctx *ctx, int width, int height, int in_chroma_format_idc, int in_bit_depth, int in_full_range,
+                                 int in_matrix_coeffs, int out_bit_depth, int algorithm, int depth);
+
+/* Timing of the last h2y_convert_batch*() (or h2y_inverse_*, h2y_dpx_decode_batch, h2y_tiff_decode_batch,
+ * h2y_rgb_interleave_batch) call measured with HIP events on
  * the stream the kernels ran on: total ms over the main kernels and how many
  * launches that covered. */
 int h2y_last_kernel_ms(const h2y_ctx *ctx, float *ms, int *launches);
 
 /* Name of the kernel those launches ran ("k_fused", "k_fused_t1", "k_fused_lut16",
  * "k_fused_narrow"; of the inverse entries "k_inverse", "k_inverse420", "k_inverse_batch", "k_inverse420_batch"; of
- * h2y_dpx_decode_batch "k_dpx_decode"): the name to
+ * h2y_dpx_decode_batch "k_dpx_decode"; of h2y_tiff_decode_batch "k_tiff_decode", of h2y_rgb_interleave_batch
+ * "k_rgb_interleave"): the name to
  * look for in a rocprofv3 kernel trace. */
 const char *h2y_last_kernel_name(const h2y_ctx *ctx);
 /* The same with its template arguments and launch shape, e.g. "k_fused_t1<F32,420BOX,YCBCR,PQ_IDENT> groups=8 xcd=1";

@@ -17,6 +17,14 @@ Prints one line per figure, then one JSON line with all of them.
      copied into its pinned slot by the host (a memcpy standing in for the file read);
   2. the kernel time of h2y_dpx_decode_batch over 64 frames (HIP events, median of reps), the bytes it moves -- the payload
      plus 12 B/pixel of float planes -- over that time, and their share of the 8 TB/s HBM peak.
+Prints one line per figure, then one JSON line with all of them.
+
+`streambench.py tiff`: 16-bit RGB TIFF on 4K pictures:
+  1. ms/frame and frames/s from host memory of the TIFF ring (h2y_tiff_stream_open: the rows go up, k_tiff_decode, the forward
+     conversion) against the .rgb ring (h2y_stream_open, U16 planes) on the same samples, both at depth 3: the same PCIe bytes;
+  2. the TIFF inverse ring (h2y_tiff_inverse_stream_open: the inverse kernel, then k_rgb_interleave) against the inverse ring;
+  3. the kernel time of h2y_tiff_decode_batch and h2y_rgb_interleave_batch over 64 frames (HIP events, median of reps), and the
+     12 B/pixel each moves over that time as a share of the 8 TB/s HBM peak.
 Prints one line per figure, then one JSON line with all of them."""
 import os
 import sys
@@ -194,6 +202,103 @@ def dpx_main():
     print(json.dumps({"streambench_dpx": res}), flush=True)
 
 
+def tiff_main():
+    import json
+
+    import torch
+
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    from tiff_files import read_tiff, write_tiff
+
+    w, hh, nb, reps = 3840, 2160, 64, 5
+    n = w * hh
+    nf = int(os.environ.get("N", "60"))
+    depth = 3
+    rng = np.random.default_rng(16)
+    ctx = h.Context(0)
+    res = {"width": w, "height": hh, "frames_per_call": nb, "reps": reps, "ring_frames": nf, "ring_depth": depth, "hbm_peak_tbs": 8.0}
+
+    def ring(open_fn, fill):
+        open_fn()
+        inflight = 0
+        t0 = time.perf_counter()
+        for _ in range(nf):
+            fill(ctx.stream_input())
+            ctx.stream_submit()
+            inflight += 1
+            if inflight == depth - 1:
+                ctx.stream_output()
+                inflight -= 1
+        while inflight:
+            ctx.stream_output()
+            inflight -= 1
+        dt = (time.perf_counter() - t0) / nf
+        ctx.stream_close()
+        return dt
+
+    # 1. forward: GBR 16-bit video range -> BT.2020nc 10-bit 4:2:0 FIR, the samples of one picture
+    rgb = rng.integers(0, 65536, (hh, w, 3), dtype=np.uint16)
+    info, _ = h.parse_tiff(write_tiff(rgb))
+    payload = np.ascontiguousarray(rgb).view(np.uint8).reshape(-1)
+    planes = read_tiff(rgb)[0]  # the .rgb ring gets the clamped planes: the same .yuv
+    d = h.make_desc(w, hh, sample=h.SAMPLE_U16, src_depth=16, dst_depth=10, src_transfer=1, dst_transfer=1, src_primaries=1,
+                    dst_primaries=1, dst_matrix=h.MATRIX_BT2020NC, resampler=1)
+
+    def fill_tiff(slot):
+        slot[0][:] = payload
+
+    def fill_rgb(slot):
+        for c in range(3):
+            slot[c][:] = planes[c]
+
+    ring(lambda: ctx.tiff_stream_open(d, info, 1, depth), fill_tiff)  # warm-up
+    t_tiff = ring(lambda: ctx.tiff_stream_open(d, info, 1, depth), fill_tiff)
+    ring(lambda: ctx.stream_open(d, depth), fill_rgb)
+    t_rgb = ring(lambda: ctx.stream_open(d, depth), fill_rgb)
+    res["forward"] = dict(tiff_ring_ms=round(t_tiff * 1e3, 2), tiff_ring_fps=round(1 / t_tiff, 1), rgb_ring_ms=round(t_rgb * 1e3, 2),
+                          rgb_ring_fps=round(1 / t_rgb, 1), ratio=round(t_rgb / t_tiff, 2))
+    print(f"forward ring from host memory: tiff {t_tiff*1e3:6.2f} ms/frame {1/t_tiff:6.1f} frames/s   "
+          f".rgb {t_rgb*1e3:6.2f} ms/frame {1/t_rgb:6.1f} frames/s   ({t_rgb/t_tiff:4.2f}x)", flush=True)
+
+    # 2. inverse: 12-bit BT.709 4:2:0 FIR -> 16-bit R,G,B
+    yuv = [rng.integers(0, 4096, m).astype(np.uint16) for m in (n, n // 4, n // 4)]
+
+    def fill_yuv(slot):
+        for c in range(3):
+            slot[c][:] = yuv[c]
+
+    args = (w, hh, 1, 12, 0, 1, 16, 1, depth)
+    ring(lambda: ctx.tiff_inverse_stream_open(*args), fill_yuv)
+    t_ti = ring(lambda: ctx.tiff_inverse_stream_open(*args), fill_yuv)
+    ring(lambda: ctx.inverse_stream_open(*args), fill_yuv)
+    t_inv = ring(lambda: ctx.inverse_stream_open(*args), fill_yuv)
+    res["inverse"] = dict(tiff_inverse_ring_ms=round(t_ti * 1e3, 2), tiff_inverse_ring_fps=round(1 / t_ti, 1),
+                          inverse_ring_ms=round(t_inv * 1e3, 2), inverse_ring_fps=round(1 / t_inv, 1), ratio=round(t_inv / t_ti, 2))
+    print(f"inverse ring from host memory: tiff {t_ti*1e3:6.2f} ms/frame {1/t_ti:6.1f} frames/s   "
+          f"planar {t_inv*1e3:6.2f} ms/frame {1/t_inv:6.1f} frames/s   ({t_inv/t_ti:4.2f}x)", flush=True)
+
+    # 3. the kernels over 64 frames on the device: 64 distinct inputs and outputs
+    pays = [torch.randint(-(1 << 15), (1 << 15) - 1, (info.payload_bytes // 2,), dtype=torch.int16, device="cuda") for _ in range(nb)]
+    outs = [[torch.empty(n, dtype=torch.int16, device="cuda") for _ in range(3)] for _ in range(nb)]
+    rgbs = [torch.empty(3 * n, dtype=torch.int16, device="cuda") for _ in range(nb)]
+    torch.cuda.synchronize()
+    for name, call in (("k_tiff_decode", lambda: ctx.tiff_decode_batch(info, 1, pays, outs)),
+                       ("k_rgb_interleave", lambda: ctx.rgb_interleave_batch(w, hh, outs, rgbs))):
+        ks = []
+        for rep in range(reps + 1):  # rep 0 warms up
+            call()
+            if rep:
+                ks.append(ctx.last_kernel_ms()[0] / nb)
+        k_ms = float(np.median(ks))
+        tbs = 12 * n / (k_ms * 1e-3) / 1e12
+        res[name] = dict(kernel_us_per_frame=round(k_ms * 1e3, 1), bytes_per_frame=12 * n, kernel_tbs=round(tbs, 2),
+                         hbm_peak_fraction=round(tbs / 8.0, 3), variant=ctx.last_kernel_variant())
+        print(f"{name:16s} {nb} frames per call: {k_ms*1e3:6.1f} us/frame  {12*n/1e6:6.1f} MB/frame  {tbs:5.2f} TB/s = "
+              f"{tbs/8.0*100:4.1f} % of 8 TB/s", flush=True)
+    ctx.close()
+    print(json.dumps({"streambench_tiff": res}), flush=True)
+
+
 def main():
     n = int(os.environ.get("N", "200"))  # long enough for the start-up (three slots filled by host copies) not to weigh
     depth = int(os.environ.get("DEPTH", "3"))
@@ -241,5 +346,7 @@ if __name__ == "__main__":
         inverse_main()
     elif sys.argv[1:] == ["dpx"]:
         dpx_main()
+    elif sys.argv[1:] == ["tiff"]:
+        tiff_main()
     else:
         main()
