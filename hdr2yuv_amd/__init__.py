@@ -20,6 +20,7 @@ from .api import (  # noqa: F401
     MATRIX_Y100,
     MATRIX_Y500,
     MATRIX_YDZDX,
+    MATRIX_YUVPRIME2,
     SAMPLE_F16,
     SAMPLE_F32,
     SAMPLE_U16,

@@ -21,6 +21,7 @@ SAMPLE_U16, SAMPLE_F32, SAMPLE_F16 = 1, 2, 3
 CHROMA_420, CHROMA_444 = 1, 3
 TRANSFER_LINEAR, TRANSFER_PQ = 8, 16
 MATRIX_GBR, MATRIX_BT709, MATRIX_BT2020NC, MATRIX_YDZDX, MATRIX_Y500, MATRIX_Y100 = 0, 1, 9, 11, 12, 13
+MATRIX_YUVPRIME2 = 15  # destination only: Y'u'v' (include/hdr2yuv_hip.h)
 
 H2Y_OK, H2Y_EINVAL, H2Y_EUNSUPPORTED, H2Y_EHIP, H2Y_ENOMEM = 0, 1, 2, 3, 4
 

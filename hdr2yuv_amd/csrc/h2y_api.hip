@@ -180,6 +180,7 @@ struct h2y_ctx {
     double fir_flag_share = 0.0; /* share of the last k_fir_fused batch's pixels (in tiles of eight) the first tier could not settle */
     uint16_t *d_tmp = nullptr;
     size_t tmp_cap = 0;
+    uint16_t *d_lin = nullptr; /* k_yuvp2_420: lin(Y') of every u16 code (h2y_yuvp2_lin_table), built when first needed */
     /* h2y_inverse_batch: the frame table (pinned on the host, and its device copy the kernels read) */
     inv_frame *d_inv_frames = nullptr, *h_inv_frames = nullptr;
     size_t d_inv_cap = 0, h_inv_cap = 0; /* bytes */
@@ -329,6 +330,7 @@ void derive_params(const h2y_desc *d, pix_params *pp, bool stage_matrix_only)
     /* convert.cpp:1159-1198 */
     if (d->dst_matrix == d->src_matrix && d->dst_primaries == d->src_primaries) pp->mode = H2Y_MODE_IDENTITY;
     else if (d->dst_matrix == H2Y_MATRIX_YDZDX) pp->mode = H2Y_MODE_YDZDX;
+    else if (d->dst_matrix == H2Y_MATRIX_YUVPRIME2) pp->mode = H2Y_MODE_YUVP2; /* convert.cpp:1191-1194 */
     else if (d->dst_matrix == H2Y_MATRIX_BT2020NC) {
         pp->mode = H2Y_MODE_YCBCR;
         pp->kr = 0.2627; pp->kg = 0.6780; pp->kb = 0.0593; pp->dcb = 1.8814; pp->dcr = 1.4746;
@@ -446,14 +448,17 @@ fused_variant pick_variant(const h2y_ctx *ctx, const h2y_desc *d, const pix_para
     v.even_h = (d->height & 1) == 0;
     v.pipe = 0;
     /* equal transfers (the 16-bit .tiff / .yuv flows): samples straight into the matrix */
-    if (!pp.convert_transfer && !v.narrow && v.even_h && (pp.mode == H2Y_MODE_YCBCR || pp.mode == H2Y_MODE_YDZDX)) v.pipe = 6;
+    /* k_fused2 has YUVP2 compiled in for 4:4:4 output, which is all that mode ever writes (the 4:2:0 form too: tmp_pic first) */
+    const bool loop_mode = pp.mode == H2Y_MODE_YCBCR || pp.mode == H2Y_MODE_YDZDX || (pp.mode == H2Y_MODE_YUVP2 && out_kind == H2Y_OUT_444);
+    if (!pp.convert_transfer && !v.narrow && v.even_h && loop_mode) v.pipe = 6;
     if (pp.convert_transfer && !v.narrow) {
         bool ident = known != nullptr;
         for (int c = 0; c < 3 && ident; c++) ident = known->floor_[c] == 0 && known->ceil_[c] == 1;
         v.pipe = ident ? 1 : 2; /* 2 is always valid: (x - 0) / 1 == x exactly */
         if (pp.convert_transfer == 2) /* generic transfer pair: its two stages' tables, in the loop form where that exists */
-            v.pipe = (v.even_h && (pp.mode == H2Y_MODE_YCBCR || pp.mode == H2Y_MODE_YDZDX)) ? 7 /* H2Y_PIPE_TFN */ : 0;
-        /* binary32 first tier where few pixels would fall through it (moderate bit depths) */
+            v.pipe = (v.even_h && loop_mode) ? 7 /* H2Y_PIPE_TFN */ : 0;
+        /* binary32 first tier where few pixels would fall through it (moderate bit depths); t1_bounds() holds for YCbCr and
+         * Y'DzDx only, so the other modes never reach k_fused_t1 or k_fir_fused */
         if ((v.pipe == 1 || v.pipe == 2) && v.in_kind != H2Y_IN_U16 && (d->height & 1) == 0 && ctx->opt_t1 && t1_bounds(pp, sn)) {
             v.pipe += 3;
             v.t1_ok = true;
@@ -541,6 +546,19 @@ int ensure_tfn(h2y_ctx *ctx, int fn)
     return 0;
 }
 
+/* k_yuvp2_420's table, once per context */
+int ensure_lin(h2y_ctx *ctx)
+{
+    if (ctx->d_lin) return 0;
+    std::vector<uint16_t> lin(65536);
+    h2y_yuvp2_lin_table(lin.data());
+    uint16_t *t = nullptr;
+    HIP_TRY(ctx, hipMalloc((void **)&t, lin.size() * sizeof(uint16_t)));
+    ctx->d_lin = t;
+    HIP_TRY(ctx, hipMemcpy(t, lin.data(), lin.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    return 0;
+}
+
 /* after a k_fir_fused launch whose block clocks came back: speed of each XCD = steps a wave of it had / time it took */
 void ffb_update(h2y_ctx *ctx)
 {
@@ -566,10 +584,18 @@ void ffb_update(h2y_ctx *ctx)
 int run_frames(h2y_ctx *ctx, const h2y_desc *d, const frame_io *frames, int n, const assumed_stats *d_assumed,
                const assumed_stats *known, bool check, int fstats_offset, bool time_it)
 {
+    /* Y'u'v' 4:2:0 (dst_matrix_coeffs 15): the fused kernel writes tmp_pic as it is -- 4:4:4, neither shifted nor clamped to the
+     * output's range -- into scratch, and k_yuvp2_420 makes the .yuv frame of it (h2y_yuvp2.hip) */
+    const bool yuvp2 = d->dst_matrix == H2Y_MATRIX_YUVPRIME2 && d->dst_chroma_format_idc == H2Y_CHROMA_420;
     pix_params pp;
-    derive_params(d, &pp, false);
+    derive_params(d, &pp, yuvp2);
     pp.pq_ext = ctx->d_table_ext;
-    const int out_kind = out_kind_of(d);
+    const int out_kind = yuvp2 ? H2Y_OUT_444 : out_kind_of(d);
+    const bool scratch = out_kind == H2Y_OUT_444TMP || yuvp2; /* a second pass reads what the fused kernel leaves in d_tmp */
+    if (yuvp2) {
+        const int rc = ensure_lin(ctx);
+        if (rc) return rc;
+    }
     t1_sens sn;
     fused_variant var = pick_variant(ctx, d, pp, out_kind, known, &sn);
     /* k_fused_t1's redo list numbers tiles as frame * tiles + tile in 32 bits */
@@ -777,7 +803,7 @@ int run_frames(h2y_ctx *ctx, const h2y_desc *d, const frame_io *frames, int n, c
      * per frame of their group (H2Y_CLAIM_FRAMES of them) */
     /* (with frame groups the bound is per GROUP: a launch of g groups takes up to g x 128 frames -- sub_batch() below) */
     auto sub_batch = [&](int left) -> int {
-        if (out_kind == H2Y_OUT_444TMP) return left < kFirSubBatch ? left : kFirSubBatch;
+        if (scratch) return left < kFirSubBatch ? left : kFirSubBatch;
         if (left <= kMaxFramesPerLaunch || !h2y_fused_grouped(var)) return left < kMaxFramesPerLaunch ? left : kMaxFramesPerLaunch;
         const int gridf = grid_for(ctx, var, (uint64_t)g.chunks * left);
         for (int ng = groups_cap(ctx, g.tiles, gridf); ng > 1; ng >>= 1)
@@ -792,18 +818,20 @@ int run_frames(h2y_ctx *ctx, const h2y_desc *d, const frame_io *frames, int n, c
      * has more than one sub-batch (sub-batch i writes half i % 2 while the FIR pass still reads the other).  A single
      * frame (h2y_convert_frame, the CLI's ring) takes 33 MB at 4K, not the 2.1 GB of a full double sub-batch. */
     const int fir_sub = n < kFirSubBatch ? n : kFirSubBatch;
-    if (out_kind == H2Y_OUT_444TMP) {
+    /* a frame's scratch: Cb and Cr (the FIR), or all of tmp_pic in 256-byte aligned frames (Y'u'v') */
+    const size_t tmp_stride = yuvp2 ? (3 * npix + 127) & ~(size_t)127 : 2 * npix;
+    if (scratch) {
         /* earlier calls may have laid their halves out differently: nothing of theirs may still be reading */
         for (int hlf = 0; hlf < 2; hlf++)
             if (ctx->fir_used[hlf]) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_fir[hlf], 0));
-        int rc = ensure(ctx, ctx->d_tmp, ctx->tmp_cap, (size_t)(n > kFirSubBatch ? 2 : 1) * fir_sub * 2 * npix * sizeof(uint16_t));
+        int rc = ensure(ctx, ctx->d_tmp, ctx->tmp_cap, (size_t)(n > kFirSubBatch ? 2 : 1) * fir_sub * tmp_stride * sizeof(uint16_t));
         if (rc) return rc;
     }
     int sub = 0;
     for (int f0 = 0, nf = 0; f0 < n; f0 += nf, sub++) {
         nf = sub_batch(n - f0);
         const int half = sub & 1;
-        if (out_kind == H2Y_OUT_444TMP && ctx->fir_used[half]) /* scratch half still being read by an earlier FIR pass? */
+        if (scratch && ctx->fir_used[half]) /* scratch half still being read by an earlier FIR pass? */
             HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_fir[half], 0));
         /* frame descriptors: host -> device (tiny) -- unless the device already holds exactly these (a caller
          * cycling through the same buffers): one stream operation less in front of the kernel */
@@ -812,8 +840,12 @@ int run_frames(h2y_ctx *ctx, const h2y_desc *d, const frame_io *frames, int n, c
         for (int i = 0; i < nf; i++) {
             frame_io io = frames[f0 + i];
             if (out_kind == H2Y_OUT_444TMP) {
-                io.tmp_cb = ctx->d_tmp + ((size_t)half * fir_sub + i) * 2 * npix;
+                io.tmp_cb = ctx->d_tmp + ((size_t)half * fir_sub + i) * tmp_stride;
                 io.tmp_cr = io.tmp_cb + npix;
+            } else if (yuvp2) { /* the fused kernel writes tmp_pic where the .yuv frame would go; k_yuvp2_420 reads it */
+                io.yuv = io.out;
+                io.out = ctx->d_tmp + ((size_t)half * fir_sub + i) * tmp_stride;
+                io.tmp_cr = nullptr;
             }
             const size_t idx = (size_t)ctx->slot_base + f0 + i;
             on_device = on_device && memcmp(&ctx->b->dev_frames[idx], &io, sizeof io) == 0;
@@ -991,10 +1023,11 @@ int run_frames(h2y_ctx *ctx, const h2y_desc *d, const frame_io *frames, int n, c
             ctx->last_name = h2y_fused_name(var);
             static const char *const kIn[] = {"F32", "F16", "U16"}, *const kOut[] = {"420BOX", "444", "444TMP"};
             static const char *const kPipe[] = {"RUNTIME", "PQ_IDENT", "PQ_NORM", "LUT16", "PQ_IDENT", "PQ_NORM", "NONE", "TFN"};
-            const char *mode = var.mode == H2Y_MODE_YCBCR ? "YCBCR" : var.mode == H2Y_MODE_YDZDX ? "YDZDX" : var.mode == H2Y_MODE_IDENTITY ? "IDENTITY" : "YPQRS";
+            const char *mode = var.mode == H2Y_MODE_YCBCR ? "YCBCR" : var.mode == H2Y_MODE_YDZDX ? "YDZDX" : var.mode == H2Y_MODE_IDENTITY ? "IDENTITY"
+                             : var.mode == H2Y_MODE_YUVP2 ? "YUVP2" : "YPQRS";
             char buf[192];
             snprintf(buf, sizeof buf, "%s<%s,%s,%s,%s%s>%s groups=%d xcd=%d%s", ctx->last_name, kIn[var.in_kind], kOut[var.out_kind], mode,
-                     kPipe[var.pipe], var.cols8 ? ",COLS8" : "", out_kind == H2Y_OUT_444TMP ? "+k_fir420" : "", groups, xcd_layout ? 1 : 0,
+                     kPipe[var.pipe], var.cols8 ? ",COLS8" : "", out_kind == H2Y_OUT_444TMP ? "+k_fir420" : yuvp2 ? (d->chroma_resampler_type ? "+k_yuvp2_420<FIR>" : "+k_yuvp2_420<BOX>") : "", groups, xcd_layout ? 1 : 0,
                      a.tail_ctr ? " tail=1" : "");
             ctx->last_variant = buf;
         }
@@ -1030,6 +1063,21 @@ int run_frames(h2y_ctx *ctx, const h2y_desc *d, const frame_io *frames, int n, c
             ctx->b->bal_groups = groups;
             ctx->b->bal_bwork = bwork;
         }
+        if (yuvp2) {
+            HIP_TRY(ctx, hipEventRecord(ctx->ev_fused[half], ctx->stream));
+            HIP_TRY(ctx, hipStreamWaitEvent(ctx->fir_stream, ctx->ev_fused[half], 0));
+            yuvp2_args ya;
+            ya.frames = ctx->b->d_frames + ctx->slot_base + f0;
+            ya.n_frames = nf;
+            ya.width = d->width;
+            ya.height = d->height;
+            ya.lin = ctx->d_lin;
+            ya.fir_max = pp.fir_max;
+            derive_params(d, &ya.pp, false); /* the output picture's write_yuv step */
+            HIP_TRY(ctx, h2y_launch_yuvp2_420(d->chroma_resampler_type == 1, ctx->fir_stream, ya));
+            HIP_TRY(ctx, hipEventRecord(ctx->ev_fir[half], ctx->fir_stream));
+            ctx->fir_used[half] = true;
+        }
         if (out_kind == H2Y_OUT_444TMP) {
             HIP_TRY(ctx, hipEventRecord(ctx->ev_fused[half], ctx->stream));
             HIP_TRY(ctx, hipStreamWaitEvent(ctx->fir_stream, ctx->ev_fused[half], 0));
@@ -1048,7 +1096,7 @@ int run_frames(h2y_ctx *ctx, const h2y_desc *d, const frame_io *frames, int n, c
             ctx->fir_used[half] = true;
         }
     }
-    if (out_kind == H2Y_OUT_444TMP) /* everything queued after this call on the main stream sees finished chroma */
+    if (scratch) /* everything queued after this call on the main stream sees finished chroma */
         for (int hlf = 0; hlf < 2; hlf++)
             if (ctx->fir_used[hlf]) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_fir[hlf], 0));
     return 0;
@@ -1156,10 +1204,15 @@ int h2y_desc_check(const h2y_desc *d, const char **why)
     if (!(d->dst_matrix == d->src_matrix && d->dst_primaries == d->src_primaries)) {
         switch (d->dst_matrix) {
         case H2Y_MATRIX_YDZDX: case H2Y_MATRIX_BT2020NC: case H2Y_MATRIX_BT709:
-        case H2Y_MATRIX_YDZDX_Y100: case H2Y_MATRIX_YDZDX_Y500: break;
+        case H2Y_MATRIX_YDZDX_Y100: case H2Y_MATRIX_YDZDX_Y500: case H2Y_MATRIX_YUVPRIME2: break;
         default: BAD(H2Y_EUNSUPPORTED, "can't determine color difference to use"); /* convert.cpp:1195-1197 */
         }
     }
+    /* convert.cpp:600-630: the Y'u'v' branch subsamples only for resampler 1 (FIR) or 0 (box); any other value leaves
+     * its planes uninitialised */
+    if (d->dst_matrix == H2Y_MATRIX_YUVPRIME2 && d->dst_chroma_format_idc == H2Y_CHROMA_420 && d->chroma_resampler_type != 0 &&
+        d->chroma_resampler_type != 1)
+        BAD(H2Y_EUNSUPPORTED, "dst_matrix_coeffs 15 with 4:2:0 takes chroma_resampler_type 0 or 1 only");
     if (d->stats_override)
         for (int c = 0; c < 3; c++)
             if (d->src_transfer != d->dst_transfer && d->ceiling[c] == d->floor[c])
@@ -1357,6 +1410,7 @@ void h2y_ctx_destroy(h2y_ctx *ctx)
     (void)hipFree(ctx->d_table1);
     (void)hipFree(ctx->d_table_ext);
     (void)hipFree(ctx->d_tmp);
+    (void)hipFree(ctx->d_lin);
     (void)hipFree(ctx->d_inv_frames);
     (void)hipHostFree(ctx->h_inv_frames);
     (void)hipFree(ctx->d_dpx_frames);

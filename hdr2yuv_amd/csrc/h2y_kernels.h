@@ -29,8 +29,11 @@ enum { H2Y_OUT_420BOX = 0, H2Y_OUT_444 = 1, H2Y_OUT_444TMP = 2 };
 /* one frame's buffers (device pointers) */
 struct frame_io {
     const void *in[3]; /* planes G,B,R (convert.cpp:980-982) */
-    uint16_t *out;     /* .yuv frame: Y | Cb | Cr */
-    uint16_t *tmp_cb;  /* H2Y_OUT_444TMP only: 4:4:4 matrix_convert output */
+    uint16_t *out;     /* .yuv frame: Y | Cb | Cr (the Y'u'v' 4:2:0 form: the scratch 4:4:4 tmp_pic, Y' | Z | X) */
+    union {
+        uint16_t *tmp_cb; /* H2Y_OUT_444TMP only: 4:4:4 matrix_convert output */
+        uint16_t *yuv;    /* the Y'u'v' 4:2:0 form only: the .yuv frame k_yuvp2_420 writes from tmp_pic */
+    };
     uint16_t *tmp_cr;
 };
 
@@ -134,6 +137,16 @@ struct fir_args {
     h2y::pix_params pp;
 };
 
+/* k_yuvp2_420 (h2y_yuvp2.hip): convert()'s Y'u'v' 4:2:0 branch, convert.cpp:533-800, then write_yuv */
+struct yuvp2_args {
+    const frame_io *frames; /* n_frames entries: out = tmp_pic (Y' | Z | X, 4:4:4), yuv = the .yuv frame */
+    int n_frames;
+    int width, height;
+    const uint16_t *lin;    /* [65536]: (unsigned short)(RHO_GAMMA_f(c / 65535.0) * 65535.0), convert.cpp:587-592 */
+    float fir_max;          /* (float)maxCV of tmp_pic: the FIR's clip (convert.cpp:520, in_pic->clip) */
+    h2y::pix_params pp;     /* write_yuv's shift and range clamp of the output picture */
+};
+
 struct inverse_args {
     const void *in[3]; /* Y, Cb/Dz, Cr/Dx: U16 4:4:4 planes, 8-byte aligned */
     void *out[3];      /* G, B, R */
@@ -218,6 +231,8 @@ hipError_t h2y_launch_inverse420(hipStream_t st, const inv420_args &a);
 hipError_t h2y_launch_inverse420_batch(int grid, hipStream_t st, const inv420_args &base, const inv_frame *frames, int n_frames);
 hipError_t h2y_launch_inverse_batch(int grid, hipStream_t st, const inverse_args &base, const inv_frame *frames, int n_frames);
 int h2y_inverse420_tiles(int width, int height); /* k_inverse420(_batch) tiles of one frame */
+hipError_t h2y_launch_yuvp2_420(bool fir, hipStream_t st, const yuvp2_args &a);
+void h2y_yuvp2_lin_table(uint16_t *lin); /* host: the 65 536 entries of yuvp2_args.lin */
 hipError_t h2y_launch_box420(hipStream_t st, const uint16_t *src, uint16_t *dst, int W, int H);
 
 /* k_dpx_decode (h2y_dpx.hip): dpx_read()'s per-pixel loop on the device */

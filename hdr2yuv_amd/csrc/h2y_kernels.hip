@@ -1773,11 +1773,27 @@ template <int IN_KIND, int OUT_KIND, int MODE> static fused_fn pick_pipe(int pip
     default: return k_fused<IN_KIND, OUT_KIND, MODE, H2Y_PIPE_RUNTIME>;
     }
 }
+/* YUVP2 (dst_matrix_coeffs 15): the loop form for even heights, 4:4:4 output only -- the only output that mode has (its 4:2:0
+ * form writes tmp_pic as 4:4:4 for k_yuvp2_420); everything else through the generic kernel */
+template <int IN_KIND> static fused_fn pick_yuvp2(int pipe, bool even_h)
+{
+    if (even_h) switch (pipe) {
+        case H2Y_PIPE_PQ_IDENT: return k_fused2<IN_KIND, H2Y_OUT_444, H2Y_MODE_YUVP2, H2Y_PIPE_PQ_IDENT>;
+        case H2Y_PIPE_PQ_NORM: return k_fused2<IN_KIND, H2Y_OUT_444, H2Y_MODE_YUVP2, H2Y_PIPE_PQ_NORM>;
+        case H2Y_PIPE_NONE: return k_fused2<IN_KIND, H2Y_OUT_444, H2Y_MODE_YUVP2, H2Y_PIPE_NONE>;
+        case H2Y_PIPE_TFN: return k_fused2<IN_KIND, H2Y_OUT_444, H2Y_MODE_YUVP2, H2Y_PIPE_TFN>;
+        default: break;
+        }
+    return k_fused<IN_KIND, H2Y_OUT_444, H2Y_MODE_RUNTIME, H2Y_PIPE_RUNTIME>;
+}
 template <int IN_KIND, int OUT_KIND> static fused_fn pick_mode(int mode, int pipe, bool even_h)
 {
     switch (mode) {
     case H2Y_MODE_YCBCR: return pick_pipe<IN_KIND, OUT_KIND, H2Y_MODE_YCBCR>(pipe, even_h);
     case H2Y_MODE_YDZDX: return pick_pipe<IN_KIND, OUT_KIND, H2Y_MODE_YDZDX>(pipe, even_h);
+    case H2Y_MODE_YUVP2:
+        if (OUT_KIND == H2Y_OUT_444) return pick_yuvp2<IN_KIND>(pipe, even_h);
+        return k_fused<IN_KIND, OUT_KIND, H2Y_MODE_RUNTIME, H2Y_PIPE_RUNTIME>;
     default: return k_fused<IN_KIND, OUT_KIND, H2Y_MODE_RUNTIME, H2Y_PIPE_RUNTIME>; /* identity / Y100 / Y500: generic */
     }
 }
@@ -1815,7 +1831,8 @@ const char *h2y_fused_name(const fused_variant &v)
     if (v.pipe == 3) return "k_fused_lut16";
     if (v.pipe == 4 || v.pipe == 5) return "k_fused_t1";
     if (v.pipe == H2Y_PIPE_TFN) return "k_fused2";
-    return ((v.pipe == 1 || v.pipe == 2 || v.pipe == H2Y_PIPE_NONE) && v.even_h && (v.mode == H2Y_MODE_YCBCR || v.mode == H2Y_MODE_YDZDX)) ? "k_fused2" : "k_fused";
+    const bool loop_mode = v.mode == H2Y_MODE_YCBCR || v.mode == H2Y_MODE_YDZDX || (v.mode == H2Y_MODE_YUVP2 && v.out_kind == H2Y_OUT_444);
+    return ((v.pipe == 1 || v.pipe == 2 || v.pipe == H2Y_PIPE_NONE) && v.even_h && loop_mode) ? "k_fused2" : "k_fused";
 }
 bool h2y_fused_grouped(const fused_variant &v)
 {

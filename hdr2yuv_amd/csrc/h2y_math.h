@@ -1041,7 +1041,7 @@ inline void pq_build_table1(pq_rec1 *T)
 /* ------------------------------------------------------------------------
  * Per-frame constants handed to the kernels.
  * ---------------------------------------------------------------------- */
-enum : int { H2Y_MODE_IDENTITY = 0, H2Y_MODE_YDZDX = 1, H2Y_MODE_YCBCR = 2, H2Y_MODE_YPQRS = 3 };
+enum : int { H2Y_MODE_IDENTITY = 0, H2Y_MODE_YDZDX = 1, H2Y_MODE_YCBCR = 2, H2Y_MODE_YPQRS = 3, H2Y_MODE_YUVP2 = 4 };
 
 struct pix_params {
     /* matrix_convert */
@@ -1183,6 +1183,16 @@ H2Y_FN void pix_matrix(const pix_params &pp, float G, float B, float R, uint32_t
         Yo = f2u_clamped(G, pp.maxCV);
         Cbo = f2u_clamped(B, pp.maxCV);
         Cro = f2u_clamped(R, pp.maxCV);
+        return;
+    }
+    if (mode == H2Y_MODE_YUVP2) {
+        /* convert.cpp:1191-1194: Cb = (unsigned int)B, a long, then + Half - 1 and the unsigned compare with maxCV -- all
+         * in 64 bits, so a B <= -1 (whose low word is huge) clamps to maxCV rather than wrapping round as
+         * chroma_clamped()'s 32-bit sum would */
+        Yo = f2u_clamped(G, pp.maxCV);
+        const uint32_t ub = (uint32_t)sat_i32_f32(B), ur = (uint32_t)sat_i32_f32(R), top = pp.maxCV - pp.half_m1;
+        Cbo = ub < top ? ub + pp.half_m1 : pp.maxCV;
+        Cro = ur < top ? ur + pp.half_m1 : pp.maxCV;
         return;
     }
     int32_t cb, cr;

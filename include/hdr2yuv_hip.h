@@ -58,6 +58,16 @@ extern "C" {
 #define H2Y_MATRIX_YDZDX 11
 #define H2Y_MATRIX_YDZDX_Y500 12
 #define H2Y_MATRIX_YDZDX_Y100 13
+/* "YUVPrime2" (hdr.h:190), destination only.  The reference's experimental Y'u'v' coding:
+ *  - 4:4:4: matrix_convert() passes G, B, R through (convert.cpp:1191-1194), adds Half - 1 to the two
+ *    chroma planes (:1200-1201) unless source and destination matrices are equal, and clamps to maxCV.
+ *  - 4:2:0 (convert.cpp:533-800): Y' is copied; per 4:2:0 site the chroma planes carry CIE 1976 u', v'
+ *    of X = Cr, Z = Cb and Y = the linearised Y' (RHO_GAMMA_f), each subsampled by the box or the FIR,
+ *    clipped to [0, 1] and written as (unsigned short)(u' * 65535.0) whatever the bit depth.  The
+ *    reference computes u''v'' and then overwrites them with u'v' (its "HACK", :732-734); that is what
+ *    it emits.  Chroma resamplers 0 and 1 only: with any other value the reference reads uninitialised
+ *    memory, and the descriptor is refused. */
+#define H2Y_MATRIX_YUVPRIME2 15
 
 /* error codes */
 #define H2Y_OK 0
