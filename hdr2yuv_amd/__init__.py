@@ -13,6 +13,8 @@ from .api import (  # noqa: F401
     H2YDesc,
     H2YDpxInfo,
     H2YError,
+    H2YExrChunk,
+    H2YExrInfo,
     H2YTiffInfo,
     MATRIX_BT2020NC,
     MATRIX_BT709,
@@ -29,11 +31,13 @@ from .api import (  # noqa: F401
     Context,
     build_library,
     desc_check,
+    exr_unpack,
     frame_bytes,
     library_path,
     load_library,
     make_desc,
     parse_dpx,
+    parse_exr,
     parse_tiff,
     set_library_path,
     tiff_layout,

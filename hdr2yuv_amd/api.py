@@ -32,7 +32,7 @@ EXPORTS = [
     "h2y_matrix_inverse", "h2y_upsample_444", "h2y_inverse_420", "h2y_inverse_frame", "h2y_ctx_set_option", "h2y_stream_open", "h2y_stream_input", "h2y_stream_submit", "h2y_stream_output", "h2y_stream_close",
     "h2y_inverse_batch", "h2y_inverse_stream_open", "h2y_dpx_parse", "h2y_dpx_decode_batch", "h2y_dpx_stream_open",
     "h2y_tiff_parse", "h2y_tiff_layout", "h2y_tiff_decode_batch", "h2y_rgb_interleave_batch", "h2y_tiff_stream_open",
-    "h2y_tiff_inverse_stream_open",
+    "h2y_tiff_inverse_stream_open", "h2y_exr_parse", "h2y_exr_unpack", "h2y_exr_decode_batch", "h2y_exr_stream_open",
 ]
 
 
@@ -89,6 +89,36 @@ class H2YTiffInfo(C.Structure):
         return (f"H2YTiffInfo(file={self.file_width}x{self.file_height} rps={self.rows_per_strip} swap={self.swap}, "
                 f"decoded={self.width}x{self.height} at ({self.x0}, {self.y0}), row_bytes={self.row_bytes}, "
                 f"payload_bytes={self.payload_bytes}, data_offset={self.data_offset}, contiguous={self.contiguous})")
+
+
+EXR_NONE, EXR_RLE, EXR_ZIPS, EXR_ZIP = 0, 1, 2, 3
+EXR_UINT, EXR_HALF, EXR_FLOAT, EXR_MISSING = 0, 1, 2, -1
+EXR_CHUNK_RAW, EXR_CHUNK_ENCODED = 0, 1
+EXR_FRAMES_PER_LAUNCH = 64
+
+
+class H2YExrInfo(C.Structure):
+    """h2y_exr_info, include/hdr2yuv_hip.h: what h2y_exr_parse read from a scanline OpenEXR file.  channel_type and
+    channel_offset are indexed by plane: 0 = G, 1 = B, 2 = R."""
+
+    _fields_ = [
+        ("width", C.c_int32), ("height", C.c_int32), ("x_min", C.c_int32), ("y_min", C.c_int32),
+        ("compression", C.c_int32), ("line_order", C.c_int32), ("lines_per_chunk", C.c_int32), ("n_chunks", C.c_int32),
+        ("n_channels", C.c_int32), ("all_half", C.c_int32), ("channel_type", C.c_int32 * 3), ("channel_offset", C.c_int32 * 3),
+        ("line_bytes", C.c_int32), ("reserved", C.c_int32), ("flags_bytes", C.c_uint64), ("payload_bytes", C.c_uint64),
+    ]
+
+    def __repr__(self):
+        return (f"H2YExrInfo({self.width}x{self.height} at ({self.x_min}, {self.y_min}), compression={self.compression}, "
+                f"line_order={self.line_order}, chunks={self.n_chunks}x{self.lines_per_chunk}, channels={self.n_channels}, "
+                f"all_half={self.all_half}, types={list(self.channel_type)}, offsets={list(self.channel_offset)}, "
+                f"line_bytes={self.line_bytes}, payload_bytes={self.payload_bytes})")
+
+
+class H2YExrChunk(C.Structure):
+    """h2y_exr_chunk: one checked entry of the offset table."""
+
+    _fields_ = [("offset", C.c_uint64), ("packed_bytes", C.c_uint32), ("row", C.c_int32)]
 
 
 def make_desc(width, height, *, sample=SAMPLE_F32, src_depth=32, dst_depth=10, src_transfer=TRANSFER_LINEAR,
@@ -234,6 +264,15 @@ def load_library():
     L.h2y_tiff_stream_open.argtypes = [C.c_void_p, C.POINTER(H2YDesc), C.POINTER(H2YTiffInfo), C.c_int, C.c_int]
     L.h2y_tiff_inverse_stream_open.restype = C.c_int
     L.h2y_tiff_inverse_stream_open.argtypes = [C.c_void_p] + [C.c_int] * 9
+    L.h2y_exr_parse.restype = C.c_int
+    L.h2y_exr_parse.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(H2YExrInfo), C.POINTER(H2YExrChunk), C.c_int, C.POINTER(C.c_char_p)]
+    L.h2y_exr_unpack.restype = C.c_int
+    L.h2y_exr_unpack.argtypes = [C.POINTER(H2YExrInfo), C.POINTER(H2YExrChunk), C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                 C.POINTER(C.c_char_p)]
+    L.h2y_exr_decode_batch.restype = C.c_int
+    L.h2y_exr_decode_batch.argtypes = [C.c_void_p, C.POINTER(H2YExrInfo), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.h2y_exr_stream_open.restype = C.c_int
+    L.h2y_exr_stream_open.argtypes = [C.c_void_p, C.POINTER(H2YDesc), C.POINTER(H2YExrInfo), C.c_int]
     L.h2y_stream_open.restype = C.c_int
     L.h2y_stream_open.argtypes = [C.c_void_p, C.POINTER(H2YDesc), C.c_int]
     L.h2y_stream_input.restype = C.c_int
@@ -313,6 +352,44 @@ def tiff_layout(width, height):
     if lib.h2y_tiff_layout(width, height, head, tail, C.byref(n)) != H2Y_OK:
         raise ValueError((lib.h2y_last_error(None) or b"").decode())
     return bytes(head), bytes(tail)
+
+
+def parse_exr(data):
+    """h2y_exr_parse on the host (no device needed): data = the whole file (bytes or a uint8 array).  Returns (info, chunks):
+    chunks is a ctypes array of H2YExrChunk, one per offset-table entry in increasing y.  Raises ValueError with the library's
+    reason where the file is refused."""
+    import numpy as np
+
+    buf = np.frombuffer(data, np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, np.uint8)
+    lib = load_library()
+    info = H2YExrInfo()
+    why = C.c_char_p()
+    ptr = buf.ctypes.data_as(C.c_void_p)
+    if lib.h2y_exr_parse(ptr, buf.size, C.byref(info), None, 0, C.byref(why)) != H2Y_OK:
+        raise ValueError((why.value or b"").decode())
+    chunks = (H2YExrChunk * info.n_chunks)()
+    if lib.h2y_exr_parse(ptr, buf.size, C.byref(info), chunks, info.n_chunks, C.byref(why)) != H2Y_OK:
+        raise ValueError((why.value or b"").decode())
+    return info, chunks
+
+
+def exr_unpack(info, chunks, data, payload=None, first=0, count=None):
+    """h2y_exr_unpack: chunks [first, first + count) of the file `data` into payload (a uint8 array of info.payload_bytes,
+    made when None).  Returns the payload.  Raises ValueError with the library's reason."""
+    import numpy as np
+
+    buf = np.frombuffer(data, np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, np.uint8)
+    if payload is None:
+        payload = np.zeros(info.payload_bytes, np.uint8)
+    if payload.dtype != np.uint8 or payload.size < info.payload_bytes or not payload.flags.c_contiguous:
+        raise ValueError("payload must be a contiguous uint8 array of info.payload_bytes")
+    count = info.n_chunks - first if count is None else count
+    why = C.c_char_p()
+    lib = load_library()
+    if lib.h2y_exr_unpack(C.byref(info), chunks, buf.ctypes.data_as(C.c_void_p), first, count,
+                          payload.ctypes.data_as(C.c_void_p), C.byref(why)) != H2Y_OK:
+        raise ValueError((why.value or b"").decode())
+    return payload
 
 
 def _np_dtype(sample):
@@ -500,6 +577,19 @@ class Context:
         outs = (C.c_void_p * n)(*[self._ptr(p) for p in rgb_out])
         self._check(self.lib.h2y_rgb_interleave_batch(self.h, width, height, n, ins, outs))
 
+    def exr_decode_batch(self, info: H2YExrInfo, payloads, planes_out) -> None:
+        """EXR payloads on the device (payloads[f]: info.payload_bytes each, exr_unpack's layout) -> half planes
+        planes_out[f] = (G, B, R), tensors or pointers: read_exr()'s scanline decode, many frames per launch."""
+        n = len(payloads)
+        if len(planes_out) != n:
+            raise ValueError("payloads and planes_out differ in length")
+        pay = (C.c_void_p * n)(*[self._ptr(p) for p in payloads])
+        outs = (C.c_void_p * (3 * n))()
+        for f in range(n):
+            for c in range(3):
+                outs[3 * f + c] = self._ptr(planes_out[f][c])
+        self._check(self.lib.h2y_exr_decode_batch(self.h, C.byref(info), n, pay, outs))
+
     # ---- host <-> device pipeline -----------------------------------------------------------
     def stream_open(self, d, depth=3) -> None:
         self._check(self.lib.h2y_stream_open(self.h, C.byref(d), depth))
@@ -512,6 +602,15 @@ class Context:
         """The forward ring on TIFF rows: stream_input gives one uint8 view of the pinned slot (info.payload_bytes) to fill with
         the decoded rows; stream_output gives the .yuv frame as on a forward stream."""
         self._check(self.lib.h2y_tiff_stream_open(self.h, C.byref(d), C.byref(info), int(clamp_video_range), depth))
+        self._stream_desc = d
+        self._stream_inverse = None
+        self._stream_dpx = int(info.payload_bytes)
+        self._stream_rgb = False
+
+    def exr_stream_open(self, d, info: H2YExrInfo, depth=3) -> None:
+        """The forward ring on EXR payloads: stream_input gives one uint8 view of the pinned slot (info.payload_bytes) to fill
+        with exr_unpack; stream_output gives the .yuv frame as on a forward stream."""
+        self._check(self.lib.h2y_exr_stream_open(self.h, C.byref(d), C.byref(info), depth))
         self._stream_desc = d
         self._stream_inverse = None
         self._stream_dpx = int(info.payload_bytes)
@@ -545,8 +644,8 @@ class Context:
         self._stream_rgb = False
 
     def stream_input(self):
-        """The three pinned input planes of the next slot, as numpy views to fill in place (on a DPX or TIFF stream: [payload],
-        uint8)."""
+        """The three pinned input planes of the next slot, as numpy views to fill in place (on a DPX, TIFF or EXR stream:
+        [payload], uint8)."""
         import numpy as np
 
         ptrs = (C.c_void_p * 3)()

@@ -22,6 +22,8 @@
  *   .tiff: an integer input type at :321-372; read_tiff() (tiff.cpp:54-362) then forces bit depth 16, 4:4:4 and GBR on the
  *             input picture with a warning each, keeps the range flag, and applies --cutout_hd / --cutout_qhd (ignored for every
  *             other input, as there); the decoded size must be the command line's, as for .dpx
+ *   .exr: read_exr() (exr.cpp:138-255) takes the size from the data window (refused here when it differs from
+ *             --src_pic_width/--src_pic_height, also under --dry_run) and forces the input picture as above
  *   .tiff output: write_tiff() (tiff.cpp:559-652) from .yuv input only (hdr2yuv.cpp:818-819, 931-933); the file is opened "w"
  * Only user_args_t.chroma_resampler_type has no defined default there (never initialised): FIR here, as in
  * make.sh's example.  The reference calls exit(0) on its argument errors; this program returns 1.
@@ -38,7 +40,7 @@
 
 #include "../../include/hdr2yuv_hip.h"
 
-enum { CLI_IN_NONE = 0, CLI_IN_YUV, CLI_IN_RGB, CLI_IN_F32, CLI_IN_F16, CLI_IN_SYNTH, CLI_IN_CODEC, CLI_IN_DPX, CLI_IN_TIFF };
+enum { CLI_IN_NONE = 0, CLI_IN_YUV, CLI_IN_RGB, CLI_IN_F32, CLI_IN_F16, CLI_IN_SYNTH, CLI_IN_DPX, CLI_IN_TIFF, CLI_IN_EXR };
 enum { CLI_OUT_NONE = 0, CLI_OUT_YUV, CLI_OUT_RGB, CLI_OUT_CODEC, CLI_OUT_TIFF };
 
 struct cli_pic { /* the attribute set of pic_t that the command line fills (hdr.h:363-378) */
@@ -106,8 +108,9 @@ static inline void cli_help()
            "  additional: [--synthetic SEEDFRAME] [--device D] [--gpus N [--devices d0,d1,..]] [--dry_run 1]\n"
            "input by extension: .yuv .rgb (16-bit planar), .f32 .f16 (raw planar float / half, plane order G,B,R: what\n"
            "  dpx_read() / read_exr() leave in memory), .dpx (10-bit, 16-bit or float DPX) and .tiff (16-bit R,G,B, uncompressed; centre-cropped\n"
-           "  to 3840 wide, [--cutout_hd 1] 1920x1080, [--cutout_qhd 1] 960x540), both decoded on the GPU, one file per frame,\n"
-           "  shot.%%06d.dpx / .tiff numbering them from --src_start_frame on; output: .yuv, or from .yuv input .tiff (16-bit R,G,B;\n"
+           "  to 3840 wide, [--cutout_hd 1] 1920x1080, [--cutout_qhd 1] 960x540) and .exr (scanline OpenEXR: NONE, RLE, ZIPS or ZIP;\n"
+           "  half, float or uint R, G, B), decoded on the GPU, one file per frame, shot.%%06d.dpx / .tiff / .exr numbering them\n"
+           "  from --src_start_frame on; output: .yuv, or from .yuv input .tiff (16-bit R,G,B;\n"
            "  one file per frame, shot.%%06d.tiff for several) or .rgb (planar R,G,B: the .tiff's samples)\n");
 }
 
@@ -188,13 +191,9 @@ static inline int cli_resolve(cli_args &a)
     else if (!strcasecmp(ext, "f16")) a.in_type = CLI_IN_F16;
     else if (!strcasecmp(ext, "dpx")) a.in_type = CLI_IN_DPX;
     else if (!strcasecmp(ext, "tiff")) a.in_type = CLI_IN_TIFF; /* not .tif: the reference's input_file_types name .tiff only */
-    else if (!strcasecmp(ext, "exr")) a.in_type = CLI_IN_CODEC;
+    else if (!strcasecmp(ext, "exr")) a.in_type = CLI_IN_EXR;
     if (a.in_type == CLI_IN_NONE) {
         printf("WARNING: input file (%s) type extension (%s) is either not recongized or not supported\n", a.src ? a.src : "(none)", ext);
-        arg_errors++;
-    } else if (a.in_type == CLI_IN_CODEC) {
-        printf("WARNING: input file (%s): .%s decoding stays with the reference's host I/O (exr.cpp);\n"
-               "         this program takes the planes it leaves in memory as .f16 / .f32\n", a.src, ext);
         arg_errors++;
     }
     const bool int_in = a.in_type == CLI_IN_YUV || a.in_type == CLI_IN_RGB || a.in_type == CLI_IN_TIFF; /* :336 */
@@ -232,7 +231,7 @@ static inline int cli_resolve(cli_args &a)
         arg_errors++;
     }
 
-    const bool numbered = (a.in_type == CLI_IN_DPX || a.in_type == CLI_IN_TIFF) && cli_frame_pattern(a.src) == 1;
+    const bool numbered = (a.in_type == CLI_IN_DPX || a.in_type == CLI_IN_TIFF || a.in_type == CLI_IN_EXR) && cli_frame_pattern(a.src) == 1;
     if (a.start_frame != 0 && (!int_in || a.in_type == CLI_IN_TIFF) && a.in_type != CLI_IN_F32 && a.in_type != CLI_IN_F16 &&
         a.in_type != CLI_IN_SYNTH && !numbered)
         printf("WARNING: start_frame(%d) only makes sense when file type is .yuv, .rgb, or .y4m\n", a.start_frame);
@@ -262,7 +261,7 @@ static inline int cli_resolve(cli_args &a)
     if (a.out.width < 2 || a.out.width > 10000) { printf("WARNING: pic_width(%d) outside range [0,10000]\n", a.out.width); arg_errors++; }
     if (a.out.height < 2 || a.out.height > 10000) { printf("WARNING: pic_height(%d) outside range [0,10000]\n", a.out.height); arg_errors++; }
     if (a.out.bit_depth < 8 || a.out.bit_depth > 32) { printf("WARNING: dst bit_depth(%d) outside range [32]\n", a.out.bit_depth); arg_errors++; }
-    if ((a.in_type == CLI_IN_DPX || a.in_type == CLI_IN_TIFF) && cli_frame_pattern(a.src) < 0) {
+    if ((a.in_type == CLI_IN_DPX || a.in_type == CLI_IN_TIFF || a.in_type == CLI_IN_EXR) && cli_frame_pattern(a.src) < 0) {
         printf("WARNING: input file name (%s): '%%' other than one integer conversion (%%d, %%0Nd) numbering the frames\n", a.src);
         arg_errors++;
     }
@@ -318,7 +317,8 @@ static inline void cli_make_desc(const cli_args &a, h2y_desc *d)
     switch (a.in_type) {
     case CLI_IN_F32:
     case CLI_IN_DPX: d->in_sample_type = H2Y_SAMPLE_F32; break;
-    case CLI_IN_F16: d->in_sample_type = H2Y_SAMPLE_F16; break;
+    case CLI_IN_F16:
+    case CLI_IN_EXR: d->in_sample_type = H2Y_SAMPLE_F16; break;
     case CLI_IN_SYNTH: d->in_sample_type = a.in.half_float_flag ? H2Y_SAMPLE_F16 : H2Y_SAMPLE_F32; break;
     default: d->in_sample_type = H2Y_SAMPLE_U16; break;
     }

@@ -4,7 +4,7 @@
  * planes to the C-ABI (include/hdr2yuv_hip.h) and writes the .yuv frames where write_yuv() would append them
  * (tiff.cpp:440: the file is opened in append mode; planes Y, Cb, Cr, little-endian 16-bit).
  *
- * .exr decoding stays where the reference has it (exr.cpp needs OpenEXR): this binary takes the formats that need no codec:
+ * Input formats:
  *   .yuv / .rgb  16-bit planar integer (hdr2yuv.cpp:582-656; .rgb is R,G,B in the file, planes 2,0,1 in memory)
  *   .f32 / .f16  raw planar float / half in G,B,R plane order -- what dpx_read() or read_exr() (exr.cpp:233-235) leave in
  *                memory; the attributes those readers force on the input picture are forced here too
@@ -14,6 +14,11 @@
  *   .tiff        16-bit R,G,B TIFF (read_tiff(), tiff.cpp:54-362): the file is mapped and its IFD parsed here
  *                (h2y_tiff_parse), the decoded rows read into the pinned slot of the TIFF ring and de-interleaved on the
  *                device; numbered like .dpx
+ *   .exr         scanline OpenEXR (read_exr(), exr.cpp:138-255; NONE, RLE, ZIPS or ZIP): the file is mapped, its header and
+ *                offset table parsed here (h2y_exr_parse), its chunks inflated or copied straight into the pinned slot of the
+ *                EXR ring by a pool of unpack threads (at most 16 across all GPU threads), the predictor, reorder and
+ *                scanline-to-plane work done on the device; numbered like .dpx.  Its size is checked against the command
+ *                line before anything else, also under --dry_run, as read_exr() takes it from the file
  *   --synthetic N  the seeded test frame of SURVEY 8c (no input file), treated as an .exr-like float input
  * and, from .yuv input, the .yuv -> .tiff flow (hdr2yuv.cpp:818-819, matrix_inverse): .tiff output (write_tiff(),
  * tiff.cpp:559-652; the samples interleaved on the device, the file bytes libtiff would write around them, one truncated
@@ -24,12 +29,17 @@
  * hdr2yuv_amd/shard.py), reads frame k at its offset in the source (hdr2yuv.cpp:624) and writes it at
  * `size of the file at start + k x frame bytes` -- the bytes N appending runs in frame order would have left (tiff.cpp:440).
  */
+#include <algorithm>
+#include <atomic>
 #include <cerrno>
+#include <condition_variable>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fcntl.h>
+#include <memory>
+#include <mutex>
 #include <string>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -200,6 +210,146 @@ static int tiff_scan(const cli_args &a, long want, h2y_tiff_info &info, std::vec
     return 0;
 }
 
+/* a whole file mapped read-only */
+struct mapped_file {
+    void *p = MAP_FAILED;
+    size_t n = 0;
+    bool open(const std::string &path)
+    {
+        const int fd = ::open(path.c_str(), O_RDONLY);
+        if (fd < 0) return false;
+        struct stat st;
+        if (!fstat(fd, &st) && st.st_size > 0) {
+            n = (size_t)st.st_size;
+            p = mmap(nullptr, n, PROT_READ, MAP_PRIVATE, fd, 0);
+        }
+        close(fd);
+        return p != MAP_FAILED;
+    }
+    ~mapped_file()
+    {
+        if (p != MAP_FAILED) munmap(p, n);
+    }
+};
+
+/* The .exr files of the run, as dpx_scan: each mapped and parsed, its data window checked against the command line and its
+ * header against the first file's (every file of a sequence has one h2y_exr_info).  Messages cite read_exr(). */
+static int exr_scan(const cli_args &a, long want, h2y_exr_info &info, std::vector<std::string> &files)
+{
+    const bool seq = cli_frame_pattern(a.src) == 1;
+    for (long k = 0; k < (seq ? want : 1); k++) {
+        const std::string path = cli_frame_name(a.src, a.start_frame + k);
+        mapped_file m;
+        if (!m.open(path)) {
+            if (k) break; /* the sequence ends here */
+            printf("ERROR: read_exr() (exr.cpp:146): unable to open or read file %s\n", path.c_str());
+            return 1;
+        }
+        h2y_exr_info xi;
+        const char *why = nullptr;
+        if (h2y_exr_parse(m.p, m.n, &xi, nullptr, 0, &why)) {
+            printf("ERROR: read_exr() (exr.cpp): %s: %s\n", path.c_str(), why);
+            return 1;
+        }
+        if (xi.width != a.in.width || xi.height != a.in.height) {
+            printf("ERROR: read_exr() (exr.cpp:149-153): %s has a %dx%d data window, --src_pic_width/--src_pic_height say %dx%d: "
+                   "resizing is not part of convert() (cv.cpp is compiled out in the reference)\n", path.c_str(), xi.width, xi.height,
+                   a.in.width, a.in.height);
+            return 1;
+        }
+        if (k && memcmp(&xi, &info, sizeof xi)) {
+            printf("ERROR: read_exr() (exr.cpp): %s differs from %s in its data window, compression or channels: every file of a "
+                   "sequence must have the same\n", path.c_str(), files[0].c_str());
+            return 1;
+        }
+        if (!k) info = xi;
+        files.push_back(path);
+    }
+    return 0;
+}
+
+/* The unpack threads of one GPU thread: h2y_exr_unpack of one frame's chunks, in ranges taken by the pool's threads and the
+ * caller alike.  n counts the caller. */
+class unpack_pool {
+  public:
+    explicit unpack_pool(int n)
+    {
+        for (int i = 1; i < n; i++) th_.emplace_back([this] { work(); });
+    }
+    ~unpack_pool()
+    {
+        {
+            std::lock_guard<std::mutex> lk(m_);
+            quit_ = true;
+        }
+        cv_.notify_all();
+        for (auto &t : th_) t.join();
+    }
+    int threads() const { return (int)th_.size() + 1; }
+    /* the whole frame into payload: "" or the first error */
+    std::string run(const h2y_exr_info &xi, const h2y_exr_chunk *chunks, const void *file, void *payload)
+    {
+        {
+            std::lock_guard<std::mutex> lk(m_);
+            xi_ = &xi, chunks_ = chunks, file_ = file, payload_ = payload;
+            step_ = std::max(1, xi.n_chunks / (4 * threads()));
+            next_ = 0;
+            err_.clear();
+            busy_ = (int)th_.size();
+            gen_++;
+        }
+        cv_.notify_all();
+        take();
+        std::unique_lock<std::mutex> lk(m_);
+        done_.wait(lk, [&] { return busy_ == 0; });
+        return err_;
+    }
+
+  private:
+    void take()
+    {
+        for (;;) {
+            const int c0 = next_.fetch_add(step_);
+            if (c0 >= xi_->n_chunks) return;
+            const char *why = nullptr;
+            if (h2y_exr_unpack(xi_, chunks_, file_, c0, std::min(step_, xi_->n_chunks - c0), payload_, &why)) {
+                std::lock_guard<std::mutex> lk(m_);
+                if (err_.empty()) err_ = why;
+            }
+        }
+    }
+    void work()
+    {
+        uint64_t seen = 0;
+        for (;;) {
+            {
+                std::unique_lock<std::mutex> lk(m_);
+                cv_.wait(lk, [&] { return quit_ || gen_ != seen; });
+                if (quit_) return;
+                seen = gen_;
+            }
+            take();
+            std::lock_guard<std::mutex> lk(m_);
+            if (--busy_ == 0) done_.notify_one();
+        }
+    }
+    std::vector<std::thread> th_;
+    std::mutex m_;
+    std::condition_variable cv_, done_;
+    bool quit_ = false;
+    uint64_t gen_ = 0;
+    int busy_ = 0, step_ = 1;
+    std::atomic<int> next_{0};
+    const h2y_exr_info *xi_ = nullptr;
+    const h2y_exr_chunk *chunks_ = nullptr;
+    const void *file_ = nullptr;
+    void *payload_ = nullptr;
+    std::string err_;
+};
+
+/* at most this many unpack threads in the whole process, the GPU threads that unpack included */
+static constexpr int kUnpackThreads = 16;
+
 /* n bytes at `at` of the open file fd into buf */
 static bool read_at(int fd, void *buf, size_t n, off_t at)
 {
@@ -225,7 +375,8 @@ struct block { /* one thread's share: frames [first, first + count) of the run, 
 /* forward path: frames [first, first+count) through one context's pinned ring (dpx: frame k is file dpx[k], decoded on the
  * device -- the ring of h2y_dpx_stream_open; tiff likewise, file tiff[k] through h2y_tiff_stream_open) */
 static void run_block(const cli_args &a, const h2y_desc &d, const std::vector<dpx_src> &dpx, const h2y_dpx_info &di,
-                      const std::vector<tiff_src> &tiff, const h2y_tiff_info &ti, int fd_out, off_t base, block *b)
+                      const std::vector<tiff_src> &tiff, const h2y_tiff_info &ti, const std::vector<std::string> &exr,
+                      const h2y_exr_info &xi, int fd_out, off_t base, block *b)
 {
     h2y_ctx *ctx = nullptr;
     FILE *fin = nullptr;
@@ -237,7 +388,7 @@ static void run_block(const cli_args &a, const h2y_desc &d, const std::vector<dp
     if (b->count < 1) return;
     if (h2y_ctx_create(b->device, &ctx)) return fail(h2y_last_error(nullptr));
     const size_t pb = h2y_plane_bytes(&d), ob = h2y_frame_bytes(&d);
-    if (a.in_type != CLI_IN_SYNTH && a.in_type != CLI_IN_DPX && a.in_type != CLI_IN_TIFF) {
+    if (a.in_type != CLI_IN_SYNTH && a.in_type != CLI_IN_DPX && a.in_type != CLI_IN_TIFF && a.in_type != CLI_IN_EXR) {
         fin = fopen(a.src, "rb");
         if (!fin) return fail(std::string("unable to open file ") + a.src);
         if (fseeko(fin, (off_t)(3 * pb) * (off_t)(a.start_frame + b->first), SEEK_SET)) return fail("seek failed"); /* hdr2yuv.cpp:624 */
@@ -247,8 +398,15 @@ static void run_block(const cli_args &a, const h2y_desc &d, const std::vector<dp
     const int depth = 3;
     const int open_rc = a.in_type == CLI_IN_DPX    ? h2y_dpx_stream_open(ctx, &d, &di, depth)
                         : a.in_type == CLI_IN_TIFF ? h2y_tiff_stream_open(ctx, &d, &ti, a.in.video_full_range_flag == 0, depth)
+                        : a.in_type == CLI_IN_EXR  ? h2y_exr_stream_open(ctx, &d, &xi, depth)
                                                    : h2y_stream_open(ctx, &d, depth);
     if (open_rc) return fail(h2y_last_error(ctx));
+    std::unique_ptr<unpack_pool> pool;
+    std::vector<h2y_exr_chunk> chunks;
+    if (a.in_type == CLI_IN_EXR) {
+        pool.reset(new unpack_pool(std::max(1, kUnpackThreads / std::max(1, a.gpus))));
+        chunks.resize((size_t)xi.n_chunks);
+    }
     long in_flight = 0;
     auto drain_one = [&]() -> bool {
         const uint16_t *yuv = nullptr;
@@ -282,6 +440,16 @@ static void run_block(const cli_args &a, const h2y_desc &d, const std::vector<dp
                 for (size_t r = 0; ok && r < src.rows.size(); r++) ok = read_at(fd, dst + r * ti.row_bytes, ti.row_bytes, (off_t)src.rows[r]);
             close(fd);
             if (!ok) return fail("short read from " + src.path);
+        } else if (a.in_type == CLI_IN_EXR) { /* parsed again (the file may have changed since the scan), unpacked into the slot */
+            const std::string &path = exr[b->first + f];
+            mapped_file m;
+            if (!m.open(path)) return fail("read_exr() (exr.cpp:146): unable to open or read file " + path);
+            h2y_exr_info x2;
+            const char *why = nullptr;
+            if (h2y_exr_parse(m.p, m.n, &x2, chunks.data(), xi.n_chunks, &why)) return fail("read_exr() (exr.cpp): " + path + ": " + why);
+            if (memcmp(&x2, &xi, sizeof xi)) return fail("read_exr() (exr.cpp): " + path + " no longer has the header the run started with");
+            const std::string err = pool->run(xi, chunks.data(), m.p, planes[0]);
+            if (!err.empty()) return fail("read_exr() (exr.cpp): " + path + ": " + err);
         } else if (fin) {
             /* file plane order -> memory planes (0=G/Y, 1=B/Cb, 2=R/Cr); .rgb holds R,G,B (hdr2yuv.cpp:635-637) */
             const int order_rgb[3] = {2, 0, 1}, order_nat[3] = {0, 1, 2};
@@ -388,6 +556,18 @@ int main(int argc, char **argv)
         printf("TOO MANY ARGUMENT ERRORS. ABORTING PROGRAM. --help to show options\n\n"); /* hdr2yuv.cpp:567-572 (which exits 0) */
         return 1;
     }
+    /* read_exr() runs before anything else is checked and takes the size from the file: a dry run reads the .exr too */
+    std::vector<std::string> exr;
+    h2y_exr_info xi{};
+    if (a.in_type == CLI_IN_EXR) {
+        if (exr_scan(a, a.n_frames > 0 ? a.n_frames : 1, xi, exr)) return 1;
+        static const char *const kComp[] = {"NONE", "RLE", "ZIPS", "ZIP"};
+        printf("exr: %dx%d data window at (%d, %d), %s, %s y, %d channels, %d unpack threads per GPU\n", xi.width, xi.height, xi.x_min,
+               xi.y_min, kComp[xi.compression], xi.line_order ? "decreasing" : "increasing", xi.n_channels,
+               std::max(1, kUnpackThreads / std::max(1, a.gpus)));
+        printf("src_picture: matrix_coeffs %d chroma_format_idc %d bit_depth %d video_full_range_flag %d\n", a.in.matrix_coeffs,
+               a.in.chroma_format_idc, a.in.bit_depth, a.in.video_full_range_flag);
+    }
     if (a.out.width != a.in.width || a.out.height != a.in.height) {
         printf("ERROR: resizing is not part of convert() (cv.cpp is compiled out in the reference)\n");
         return 1;
@@ -419,7 +599,8 @@ int main(int argc, char **argv)
     h2y_dpx_info di{};
     std::vector<tiff_src> tiff;
     h2y_tiff_info ti{};
-    if (a.in_type == CLI_IN_TIFF) { /* as .dpx */
+    if (a.in_type == CLI_IN_EXR) frames = (long)exr.size();
+    else if (a.in_type == CLI_IN_TIFF) { /* as .dpx */
         if (!(a.dry_run && stat(cli_frame_name(a.src, a.start_frame).c_str(), &st))) {
             if (tiff_scan(a, frames, ti, tiff)) return 1;
             frames = (long)tiff.size();
@@ -489,7 +670,7 @@ int main(int argc, char **argv)
         blocks[r].count = frames / a.gpus + (r < frames % a.gpus ? 1 : 0);
         at += blocks[r].count;
     }
-    auto work = [&](block *b) { a.inverse ? run_block_inverse(a, tw, fd, base, b) : run_block(a, d, dpx, di, tiff, ti, fd, base, b); };
+    auto work = [&](block *b) { a.inverse ? run_block_inverse(a, tw, fd, base, b) : run_block(a, d, dpx, di, tiff, ti, exr, xi, fd, base, b); };
     if (a.gpus == 1) work(&blocks[0]);
     else {
         std::vector<std::thread> th;

@@ -11,6 +11,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
+#include <algorithm>
 #include <cstring>
 #include <new>
 #include <string>
@@ -20,6 +21,8 @@
 #include "h2y_kernels.h"
 #include "h2y_math.h"
 #include "h2y_walk.h"
+
+#include <zlib.h>
 
 using namespace h2y;
 
@@ -190,6 +193,9 @@ struct h2y_ctx {
     /* h2y_tiff_decode_batch's and h2y_rgb_interleave_batch's frame tables, likewise; the TIFF rings keep one entry per slot */
     tiff_frame *d_tiff_frames = nullptr, *h_tiff_frames = nullptr;
     size_t d_tiff_cap = 0, h_tiff_cap = 0; /* bytes */
+    /* h2y_exr_decode_batch's frame table, likewise; an EXR stream keeps one entry per slot */
+    exr_frame *d_exr_frames = nullptr, *h_exr_frames = nullptr;
+    size_t d_exr_cap = 0, h_exr_cap = 0; /* bytes */
     rgb_frame *d_rgb_frames = nullptr, *h_rgb_frames = nullptr;
     size_t d_rgb_cap = 0, h_rgb_cap = 0; /* bytes */
 
@@ -231,6 +237,10 @@ struct h2y_ctx {
     bool s_tiff = false, s_tiff_clamp = false;
     h2y_tiff_info s_tiff_info{};
     size_t s_tiff_off = 0;
+    /* an EXR stream (h2y_exr_stream_open): laid out as a TIFF stream, half planes, the payload at s_exr_off */
+    bool s_exr = false;
+    h2y_exr_info s_exr_info{};
+    size_t s_exr_off = 0;
     /* a TIFF inverse stream (h2y_tiff_inverse_stream_open): an inverse stream whose slot output holds, at s_rgb_off after the
      * G, B, R planes, the interleaved R,G,B samples that go down */
     bool s_rgb = false;
@@ -1417,6 +1427,8 @@ void h2y_ctx_destroy(h2y_ctx *ctx)
     (void)hipHostFree(ctx->h_dpx_frames);
     (void)hipFree(ctx->d_tiff_frames);
     (void)hipHostFree(ctx->h_tiff_frames);
+    (void)hipFree(ctx->d_exr_frames);
+    (void)hipHostFree(ctx->h_exr_frames);
     (void)hipFree(ctx->d_rgb_frames);
     (void)hipHostFree(ctx->h_rgb_frames);
     (void)hipFree(ctx->d_in);
@@ -2064,6 +2076,7 @@ static void stream_free(h2y_ctx *ctx)
     ctx->s_inverse = false;
     ctx->s_dpx = false;
     ctx->s_tiff = false;
+    ctx->s_exr = false;
     ctx->s_rgb = false;
     ctx->s_head = ctx->s_tail = 0;
     ctx->s_lent = -1;
@@ -2631,6 +2644,373 @@ int h2y_tiff_inverse_stream_open(h2y_ctx *ctx, int width, int height, int in_chr
     return H2Y_OK;
 }
 
+/* ---- scanline OpenEXR (read_exr(), exr.cpp:138-255) -------------------------------------------------------------------- */
+
+namespace {
+
+struct exr_reader { /* a little-endian file in memory */
+    const unsigned char *p;
+    size_t n;
+    uint32_t u32(size_t at) const { return (uint32_t)p[at] | (uint32_t)p[at + 1] << 8 | (uint32_t)p[at + 2] << 16 | (uint32_t)p[at + 3] << 24; }
+    int32_t i32(size_t at) const { return (int32_t)u32(at); }
+    uint64_t u64(size_t at) const { return (uint64_t)u32(at) | (uint64_t)u32(at + 4) << 32; }
+    /* the NUL-terminated string at `at`: its length, or -1 when it runs past the end */
+    long str(size_t at) const
+    {
+        for (size_t k = at; k < n; k++)
+            if (!p[k]) return (long)(k - at);
+        return -1;
+    }
+};
+
+struct exr_channel {
+    std::string name;
+    int32_t type;
+    size_t size;
+};
+
+} // namespace
+
+int h2y_exr_parse(const void *file, size_t file_bytes, h2y_exr_info *out, h2y_exr_chunk *chunks, int capacity, const char **why)
+{
+    h2y_exr_info xi{};
+    const exr_reader r{static_cast<const unsigned char *>(file), file_bytes};
+    auto parse = [&]() -> const char * {
+        if (!file || !out) return "null argument";
+        if (file_bytes < 8 || r.u32(0) != 20000630u) return "not an OpenEXR file: the magic number 20000630 is missing";
+        const uint32_t version = r.u32(4);
+        if (version & 0x200u) return "tiled OpenEXR files are not supported (scanline only)";
+        if (version & 0x1000u) return "multi-part OpenEXR files are not supported (single part only)";
+        if (version & 0x800u) return "deep OpenEXR files are not supported";
+        if ((version & 0xFFu) != 2u) return "OpenEXR format version is not 2";
+        if (version & ~0x4FFu) return "unknown OpenEXR version flags";
+        /* the header: attributes name\0 type\0 int32 size, value; a NUL ends it */
+        std::vector<exr_channel> ch;
+        bool have_ch = false, have_comp = false, have_dw = false, have_lo = false;
+        int32_t dw[4] = {0, 0, 0, 0};
+        size_t at = 8;
+        for (;;) {
+            if (at >= file_bytes) return "truncated header";
+            if (!r.p[at]) {
+                at++;
+                break;
+            }
+            const long nl = r.str(at);
+            if (nl < 0) return "truncated header";
+            const std::string name(reinterpret_cast<const char *>(r.p + at), (size_t)nl);
+            at += (size_t)nl + 1;
+            const long tl = at < file_bytes ? r.str(at) : -1;
+            if (tl < 0) return "truncated header";
+            const std::string type(reinterpret_cast<const char *>(r.p + at), (size_t)tl);
+            at += (size_t)tl + 1;
+            if (at + 4 > file_bytes) return "truncated header";
+            const int32_t size = r.i32(at);
+            at += 4;
+            if (size < 0 || (uint64_t)at + (uint64_t)size > file_bytes) return "truncated header: an attribute runs past the end of the file";
+            const size_t end = at + (size_t)size;
+            if (name == "channels") {
+                if (type != "chlist") return "the channels attribute is not a chlist";
+                have_ch = true;
+                size_t q = at;
+                for (;;) { /* name\0 int32 pixel_type, uint8 pLinear, 3 reserved, int32 xSampling, int32 ySampling; a NUL ends it */
+                    if (q >= end) return "truncated channel list";
+                    if (!r.p[q]) break;
+                    const long cl = r.str(q);
+                    if (cl < 0 || q + (size_t)cl + 1 + 16 > end) return "truncated channel list";
+                    exr_channel c{std::string(reinterpret_cast<const char *>(r.p + q), (size_t)cl), r.i32(q + (size_t)cl + 1), 0};
+                    const int32_t xs = r.i32(q + (size_t)cl + 9), ys = r.i32(q + (size_t)cl + 13);
+                    q += (size_t)cl + 17;
+                    if (c.type < 0 || c.type > 2) return "a channel's pixel type is not UINT, HALF or FLOAT";
+                    if (xs != 1 || ys != 1) return "a channel has x or y sampling other than 1 (subsampled channels are not supported)";
+                    if (c.name == "Y" || c.name == "RY" || c.name == "BY")
+                        return "luminance/chroma channels (Y, RY, BY) are not supported: RgbaInputFile would convert them through the "
+                               "chromaticities";
+                    c.size = c.type == H2Y_EXR_HALF ? 2 : 4;
+                    ch.push_back(c);
+                }
+            } else if (name == "compression") {
+                if (type != "compression" || size != 1) return "the compression attribute is malformed";
+                have_comp = true;
+                xi.compression = r.p[at];
+            } else if (name == "dataWindow") {
+                if (type != "box2i" || size != 16) return "the dataWindow attribute is malformed";
+                have_dw = true;
+                for (int k = 0; k < 4; k++) dw[k] = r.i32(at + 4 * (size_t)k);
+            } else if (name == "lineOrder") {
+                if (type != "lineOrder" || size != 1) return "the lineOrder attribute is malformed";
+                have_lo = true;
+                xi.line_order = r.p[at];
+            }
+            at = end;
+        }
+        if (!have_ch || !have_comp || !have_dw || !have_lo) return "a required attribute (channels, compression, dataWindow, lineOrder) is missing";
+        static const char *const kCodec[] = {"NONE", "RLE", "ZIPS", "ZIP", "PIZ", "PXR24", "B44", "B44A", "DWAA", "DWAB"};
+        if (xi.compression > H2Y_EXR_ZIP) {
+            static char msg[10][64];
+            if (xi.compression > 9) return "unknown compression";
+            snprintf(msg[xi.compression], sizeof msg[0], "%s compression is not supported (NONE, RLE, ZIPS, ZIP only)", kCodec[xi.compression]);
+            return msg[xi.compression];
+        }
+        if (xi.line_order != 0 && xi.line_order != 1) return "lineOrder is neither INCREASING_Y nor DECREASING_Y";
+        if (ch.empty()) return "the file has no channels";
+        /* OpenEXR keeps the channel list in a map: a line holds the channels in the order of their names */
+        std::sort(ch.begin(), ch.end(), [](const exr_channel &a, const exr_channel &b) { return a.name < b.name; });
+        for (size_t k = 1; k < ch.size(); k++)
+            if (ch[k].name == ch[k - 1].name) return "a channel name appears twice";
+        const int64_t w = (int64_t)dw[2] - dw[0] + 1, h = (int64_t)dw[3] - dw[1] + 1;
+        if (w < 1 || h < 1 || w > (1 << 20) || h > (1 << 20)) return "the data window's width or height is outside 1..1048576";
+        if (w * h >= (1ll << 28)) return "the data window has 2^28 pixels or more";
+        xi.width = (int32_t)w;
+        xi.height = (int32_t)h;
+        xi.x_min = dw[0];
+        xi.y_min = dw[1];
+        xi.lines_per_chunk = xi.compression == H2Y_EXR_ZIP ? 16 : 1;
+        xi.n_chunks = (int32_t)((h + xi.lines_per_chunk - 1) / xi.lines_per_chunk);
+        xi.n_channels = (int32_t)ch.size();
+        xi.all_half = 1;
+        for (int c = 0; c < 3; c++) xi.channel_type[c] = H2Y_EXR_MISSING, xi.channel_offset[c] = -1;
+        uint64_t lb = 0;
+        for (const exr_channel &c : ch) {
+            const int plane = c.name == "G" ? 0 : c.name == "B" ? 1 : c.name == "R" ? 2 : -1; /* "A" and the rest: skipped */
+            if (plane >= 0) xi.channel_type[plane] = c.type, xi.channel_offset[plane] = (int32_t)lb;
+            if (c.type != H2Y_EXR_HALF) xi.all_half = 0;
+            lb += (uint64_t)w * c.size;
+            if (lb * (uint64_t)xi.lines_per_chunk >= (1ull << 31)) return "a chunk would hold 2 GiB or more";
+        }
+        xi.line_bytes = (int32_t)lb;
+        xi.flags_bytes = ((uint64_t)xi.n_chunks + 255) & ~(uint64_t)255;
+        xi.payload_bytes = xi.flags_bytes + (uint64_t)h * lb;
+        if (chunks && capacity < xi.n_chunks) return "capacity is less than the number of chunks";
+        /* the offset table: n_chunks uint64, indexed by increasing y whatever the line order */
+        if ((uint64_t)at + 8ull * (uint64_t)xi.n_chunks > file_bytes) return "truncated offset table";
+        const uint64_t table_end = (uint64_t)at + 8ull * (uint64_t)xi.n_chunks;
+        for (int32_t k = 0; k < xi.n_chunks; k++) {
+            const uint64_t off = r.u64(at + 8 * (size_t)k);
+            if (off < table_end || off + 8 > file_bytes)
+                return "broken offset table: an entry points outside the chunk area (OpenEXR would rebuild the table by scanning; "
+                       "refused here)";
+            const int32_t row = k * xi.lines_per_chunk;
+            if ((int64_t)r.i32((size_t)off) != (int64_t)xi.y_min + row) return "broken offset table: a chunk's y is not that of its table slot";
+            const int32_t size = r.i32((size_t)off + 4);
+            const uint64_t lines = (uint64_t)(xi.height - row < xi.lines_per_chunk ? xi.height - row : xi.lines_per_chunk);
+            if (size < 1 || off + 8 + (uint64_t)size > file_bytes) return "a chunk runs past the end of the file";
+            if ((uint64_t)size > lines * lb) return "a chunk's packed size exceeds its uncompressed size (corrupt file)";
+            if (xi.compression == H2Y_EXR_NONE && (uint64_t)size != lines * lb) return "an uncompressed chunk's size is not its lines' bytes";
+            if (chunks) chunks[k] = h2y_exr_chunk{off, (uint32_t)size, row};
+        }
+        return nullptr;
+    };
+    const char *w = parse();
+    if (why) *why = w ? w : "";
+    if (w) return fail(nullptr, H2Y_EINVAL, "%s", w);
+    *out = xi;
+    return H2Y_OK;
+}
+
+/* what h2y_exr_parse can return, and nothing else */
+static const char *exr_info_check(const h2y_exr_info *xi)
+{
+    if (!xi) return "null h2y_exr_info";
+    if (xi->width < 1 || xi->width > (1 << 20) || xi->height < 1 || xi->height > (1 << 20) ||
+        (uint64_t)xi->width * (uint64_t)xi->height >= (1ull << 28))
+        return "EXR width and height must be 1..1048576, below 2^28 pixels";
+    if (xi->compression < H2Y_EXR_NONE || xi->compression > H2Y_EXR_ZIP) return "EXR compression must be NONE, RLE, ZIPS or ZIP";
+    if (xi->lines_per_chunk != (xi->compression == H2Y_EXR_ZIP ? 16 : 1)) return "EXR lines_per_chunk does not match the compression";
+    if (xi->n_chunks != (xi->height + xi->lines_per_chunk - 1) / xi->lines_per_chunk) return "EXR n_chunks is not ceil(height / lines_per_chunk)";
+    if (xi->n_channels < 1 || xi->line_bytes < 2 * xi->width || xi->line_bytes % 2 ||
+        (uint64_t)xi->line_bytes * (uint64_t)xi->lines_per_chunk >= (1ull << 31))
+        return "EXR line_bytes is out of range";
+    bool half_only = true;
+    for (int c = 0; c < 3; c++) {
+        const int t = xi->channel_type[c];
+        if (t == H2Y_EXR_MISSING) {
+            if (xi->channel_offset[c] != -1) return "EXR channel_offset of a missing channel must be -1";
+            continue;
+        }
+        if (t < H2Y_EXR_UINT || t > H2Y_EXR_FLOAT) return "EXR channel_type must be UINT, HALF, FLOAT or MISSING";
+        const int64_t size = t == H2Y_EXR_HALF ? 2 : 4;
+        if (t != H2Y_EXR_HALF) half_only = false;
+        if (xi->channel_offset[c] < 0 || xi->channel_offset[c] + size * xi->width > xi->line_bytes || xi->channel_offset[c] % 2)
+            return "EXR channel_offset lies outside the line";
+        if (xi->all_half && xi->channel_offset[c] % (2 * xi->width)) return "EXR channel_offset of an all-half file is not a channel's";
+    }
+    if (xi->all_half != 0 && xi->all_half != 1) return "EXR all_half must be 0 or 1";
+    if (xi->all_half && (!half_only || xi->line_bytes != 2 * xi->width * xi->n_channels)) return "EXR all_half does not match the channels";
+    if (xi->flags_bytes != (((uint64_t)xi->n_chunks + 255) & ~(uint64_t)255)) return "EXR flags_bytes is not n_chunks rounded up to 256";
+    if (xi->payload_bytes != xi->flags_bytes + (uint64_t)xi->height * (uint64_t)xi->line_bytes)
+        return "EXR payload_bytes is not flags_bytes + height x line_bytes";
+    return nullptr;
+}
+
+/* OpenEXR's rleUncompress: a count byte c < 0 copies the next -c bytes, c >= 0 repeats the next byte c + 1 times.  Whether
+ * it filled `out` exactly. */
+static bool exr_rle_expand(const unsigned char *in, size_t in_bytes, unsigned char *out, size_t out_bytes)
+{
+    size_t i = 0, o = 0;
+    while (i < in_bytes) {
+        const int c = (signed char)in[i++];
+        if (c < 0) {
+            const size_t k = (size_t)-c;
+            if (i + k > in_bytes || o + k > out_bytes) return false;
+            memcpy(out + o, in + i, k);
+            i += k;
+            o += k;
+        } else {
+            const size_t k = (size_t)c + 1;
+            if (i >= in_bytes || o + k > out_bytes) return false;
+            memset(out + o, in[i++], k);
+            o += k;
+        }
+    }
+    return o == out_bytes;
+}
+
+int h2y_exr_unpack(const h2y_exr_info *info, const h2y_exr_chunk *chunks, const void *file, int first_chunk, int n_chunks,
+                   void *payload, const char **why)
+{
+    const char *w = exr_info_check(info);
+    if (!w && (!chunks || !file || !payload)) w = "null argument";
+    if (!w && (first_chunk < 0 || n_chunks < 0 || first_chunk > info->n_chunks - n_chunks)) w = "chunk range outside the file's chunks";
+    static thread_local char msg[160];
+    if (!w) {
+        unsigned char *pay = static_cast<unsigned char *>(payload);
+        const unsigned char *src = static_cast<const unsigned char *>(file);
+        const uint64_t lb = (uint64_t)info->line_bytes;
+        if (first_chunk == 0) memset(pay + info->n_chunks, 0, (size_t)(info->flags_bytes - (uint64_t)info->n_chunks));
+        for (int c = first_chunk; c < first_chunk + n_chunks && !w; c++) {
+            const h2y_exr_chunk &k = chunks[c];
+            if (k.row != c * info->lines_per_chunk) {
+                w = "a chunk record's row is not that of its slot";
+                break;
+            }
+            const uint64_t lines = (uint64_t)(info->height - k.row < info->lines_per_chunk ? info->height - k.row : info->lines_per_chunk);
+            const size_t raw = (size_t)(lines * lb);
+            unsigned char *dst = pay + info->flags_bytes + (uint64_t)k.row * lb;
+            const unsigned char *in = src + k.offset + 8;
+            if (k.packed_bytes > raw || (info->compression == H2Y_EXR_NONE && k.packed_bytes != raw)) {
+                w = "a chunk's packed size exceeds its uncompressed size (corrupt file)";
+                break;
+            }
+            if (k.packed_bytes == raw) { /* NONE, or stored raw because compression did not help */
+                memcpy(dst, in, raw);
+                pay[c] = H2Y_EXR_CHUNK_RAW;
+                continue;
+            }
+            if (info->compression == H2Y_EXR_RLE) {
+                if (!exr_rle_expand(in, k.packed_bytes, dst, raw)) {
+                    snprintf(msg, sizeof msg, "chunk %d (y %d): RLE data does not expand to its %zu bytes", c, info->y_min + k.row, raw);
+                    w = msg;
+                }
+            } else {
+                uLongf got = (uLongf)raw;
+                const int zr = uncompress(dst, &got, in, (uLong)k.packed_bytes);
+                if (zr != Z_OK || got != raw) {
+                    snprintf(msg, sizeof msg, "chunk %d (y %d): zlib data does not inflate to its %zu bytes (zlib %d, %lu bytes)", c,
+                             info->y_min + k.row, raw, zr, (unsigned long)got);
+                    w = msg;
+                }
+            }
+            pay[c] = H2Y_EXR_CHUNK_ENCODED;
+        }
+    }
+    if (why) *why = w ? w : "";
+    if (w) return fail(nullptr, H2Y_EINVAL, "%s", w);
+    return H2Y_OK;
+}
+
+static exr_geom exr_geom_of(const h2y_exr_info &xi)
+{
+    exr_geom g{};
+    g.width = (uint32_t)xi.width;
+    g.height = (uint32_t)xi.height;
+    g.lines_per_chunk = (uint32_t)xi.lines_per_chunk;
+    g.n_chunks = (uint32_t)xi.n_chunks;
+    g.n_channels = (uint32_t)xi.n_channels;
+    g.line_bytes = (uint32_t)xi.line_bytes;
+    g.flags_bytes = (uint32_t)xi.flags_bytes;
+    g.all_half = (uint32_t)xi.all_half;
+    for (int c = 0; c < 3; c++) g.type[c] = xi.channel_type[c], g.offset[c] = xi.channel_offset[c];
+    return g;
+}
+
+int h2y_exr_decode_batch(h2y_ctx *ctx, const h2y_exr_info *info, int n_frames, const void *const *d_payload, uint16_t *const *d_planes)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
+    if (const char *w = exr_info_check(info)) return fail(ctx, H2Y_EINVAL, "%s", w);
+    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
+    if (!d_payload || !d_planes) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
+    for (int f = 0; f < n_frames; f++) {
+        if (!d_payload[f]) return fail(ctx, H2Y_EINVAL, "frame %d: payload is null", f);
+        if ((uintptr_t)d_payload[f] & 1u) return fail(ctx, H2Y_EINVAL, "frame %d: payload is not 2-byte aligned", f);
+        for (int c = 0; c < 3; c++) {
+            const uint16_t *p = d_planes[3 * f + c];
+            if (!p) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is null", f, c);
+            if ((uintptr_t)p & 1u) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is not 2-byte aligned", f, c);
+        }
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = frame_table(ctx, ctx->d_exr_frames, ctx->d_exr_cap, ctx->h_exr_frames, ctx->h_exr_cap, n_frames);
+    if (rc) return rc;
+    for (int f = 0; f < n_frames; f++) {
+        ctx->h_exr_frames[f].payload = d_payload[f];
+        for (int c = 0; c < 3; c++) ctx->h_exr_frames[f].plane[c] = d_planes[3 * f + c];
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_exr_frames, ctx->h_exr_frames, (size_t)n_frames * sizeof(exr_frame), hipMemcpyHostToDevice,
+                                ctx->stream));
+    const exr_geom g = exr_geom_of(*info);
+    static_assert(H2Y_EXR_FRAMES_PER_LAUNCH == H2Y_TIFF_FRAMES_PER_LAUNCH, "timed_launches splits by H2Y_TIFF_FRAMES_PER_LAUNCH");
+    rc = timed_launches(ctx, n_frames, "k_exr_decode", [&](int f0, int nf) {
+        return h2y_launch_exr_decode(unit_grid(ctx, (uint64_t)info->n_chunks * nf), ctx->stream, g, ctx->d_exr_frames + f0, nf);
+    });
+    if (rc) return rc;
+    static const char *const kComp[] = {"NONE", "RLE", "ZIPS", "ZIP"};
+    ctx->last_variant = std::string("k_exr_decode<") + kComp[info->compression] + (info->all_half ? ",ALL_HALF>" : ",GENERAL>");
+    return H2Y_OK;
+}
+
+/* The forward ring on EXR payloads: as h2y_tiff_stream_open, with half planes; each slot's k_exr_decode table entry is uploaded
+ * here once */
+int h2y_exr_stream_open(h2y_ctx *ctx, const h2y_desc *d, const h2y_exr_info *info, int depth)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is already open");
+    if (const char *w = exr_info_check(info)) return fail(ctx, H2Y_EINVAL, "%s", w);
+    const char *why;
+    int rc = h2y_desc_check(d, &why);
+    if (rc) return fail(ctx, rc, "descriptor: %s", why);
+    if (d->in_sample_type != H2Y_SAMPLE_F16) return fail(ctx, H2Y_EINVAL, "an EXR stream decodes to half planes: in_sample_type must be H2Y_SAMPLE_F16");
+    if (d->width != info->width || d->height != info->height)
+        return fail(ctx, H2Y_EINVAL, "EXR data window is %dx%d, the descriptor %dx%d (resizing is not part of convert())", info->width,
+                    info->height, d->width, d->height);
+    if (depth < 2 || depth > 16) return fail(ctx, H2Y_EINVAL, "depth must be 2..16");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = reserve_batch(ctx, 64);
+    if (rc) return rc;
+    rc = ensure(ctx, ctx->d_exr_frames, ctx->d_exr_cap, (size_t)depth * sizeof(exr_frame));
+    if (rc) return rc;
+    const size_t pb = h2y_plane_bytes(d), ob = h2y_frame_bytes(d);
+    ctx->s_plane_al = (pb + 255) & ~(size_t)255;
+    ctx->s_desc = *d;
+    for (int c = 0; c < 3; c++) ctx->s_in_off[c] = c * ctx->s_plane_al;
+    ctx->s_exr_off = 3 * ctx->s_plane_al;
+    rc = stream_alloc(ctx, depth, info->payload_bytes, ctx->s_exr_off + info->payload_bytes, ob, ob);
+    if (rc) return rc;
+    std::vector<exr_frame> tab(depth);
+    for (int k = 0; k < depth; k++) {
+        tab[k].payload = ctx->ss[k].d_in + ctx->s_exr_off;
+        for (int c = 0; c < 3; c++) tab[k].plane[c] = reinterpret_cast<uint16_t *>(ctx->ss[k].d_in + ctx->s_in_off[c]);
+    }
+    hipError_t e = hipMemcpy(ctx->d_exr_frames, tab.data(), tab.size() * sizeof(exr_frame), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        stream_free(ctx);
+        return fail(ctx, H2Y_EHIP, "hipMemcpy of the EXR slot table: %s", hipGetErrorString(e));
+    }
+    ctx->s_exr = true;
+    ctx->s_exr_info = *info;
+    return H2Y_OK;
+}
+
 /* one frame of an inverse stream: H2D of its planes, k_inverse420 / k_inverse on the context's stream, D2H of G, B, R */
 static int inverse_stream_submit(h2y_ctx *ctx, int slot)
 {
@@ -2685,7 +3065,7 @@ int h2y_stream_input(h2y_ctx *ctx, void *planes[3])
     if (s.state == 1) { /* asked twice without a submit: same buffers again */
     } else if (s.state != 0) return fail(ctx, H2Y_EINVAL, "all %d slots are in flight: take an output first", (int)ctx->ss.size());
     s.state = 1;
-    if (ctx->s_dpx || ctx->s_tiff) { /* the payload, as the file holds it (TIFF: the decoded rows, packed) */
+    if (ctx->s_dpx || ctx->s_tiff || ctx->s_exr) { /* the payload, as the file holds it (TIFF: the decoded rows, packed; EXR: unpacked) */
         planes[0] = s.h_in;
         planes[1] = planes[2] = nullptr;
         return H2Y_OK;
@@ -2711,6 +3091,8 @@ int h2y_stream_submit(h2y_ctx *ctx)
         HIP_TRY(ctx, hipMemcpyAsync(s.d_in + ctx->s_dpx_off, s.h_in, ctx->s_dpx_info.payload_bytes, hipMemcpyHostToDevice, ctx->s_h2d));
     else if (ctx->s_tiff) /* likewise the rows for k_tiff_decode */
         HIP_TRY(ctx, hipMemcpyAsync(s.d_in + ctx->s_tiff_off, s.h_in, ctx->s_tiff_info.payload_bytes, hipMemcpyHostToDevice, ctx->s_h2d));
+    else if (ctx->s_exr) /* likewise the unpacked chunks for k_exr_decode */
+        HIP_TRY(ctx, hipMemcpyAsync(s.d_in + ctx->s_exr_off, s.h_in, ctx->s_exr_info.payload_bytes, hipMemcpyHostToDevice, ctx->s_h2d));
     else /* the slot's three planes lie one after the other (each padded to 256 bytes): one copy command, not three */
         HIP_TRY(ctx, hipMemcpyAsync(s.d_in, s.h_in, 2 * ctx->s_plane_al + pb, hipMemcpyHostToDevice, ctx->s_h2d));
     io.out = s.d_out;
@@ -2727,6 +3109,10 @@ int h2y_stream_submit(h2y_ctx *ctx)
         const tiff_geom g = tiff_geom_of(ti);
         HIP_TRY(ctx, h2y_launch_tiff_decode(ti.swap != 0, ctx->s_tiff_clamp, unit_grid(ctx, h2y_tiff_chunks(g.width, g.height)), ctx->stream,
                                             g, ctx->d_tiff_frames + slot, 1));
+    }
+    if (ctx->s_exr) {
+        const h2y_exr_info &xi = ctx->s_exr_info;
+        HIP_TRY(ctx, h2y_launch_exr_decode(unit_grid(ctx, (uint64_t)xi.n_chunks), ctx->stream, exr_geom_of(xi), ctx->d_exr_frames + slot, 1));
     }
     const bool needs_stats = d->src_transfer != d->dst_transfer;
     int rc;

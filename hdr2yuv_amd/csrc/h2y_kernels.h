@@ -264,4 +264,16 @@ uint32_t h2y_rgb_chunks(uint32_t npix);                    /* k_rgb_interleave's
 hipError_t h2y_launch_tiff_decode(bool swap, bool clamp, int grid, hipStream_t st, const tiff_geom &g, const tiff_frame *frames, int n_frames);
 hipError_t h2y_launch_rgb_interleave(int grid, hipStream_t st, uint32_t npix, const rgb_frame *frames, int n_frames);
 
+/* k_exr_decode (h2y_exr.hip): read_exr()'s scanline decode on the device, from h2y_exr_unpack's payload */
+struct exr_geom { /* what k_exr_decode takes of an h2y_exr_info */
+    uint32_t width, height, lines_per_chunk, n_chunks, n_channels, line_bytes, flags_bytes, all_half;
+    int32_t type[3], offset[3]; /* planes G, B, R: H2Y_EXR_* pixel type (-1 missing), byte offset within a line */
+};
+/* one frame: its payload in, the half planes G, B, R out */
+struct exr_frame {
+    const void *payload;
+    uint16_t *plane[3];
+};
+hipError_t h2y_launch_exr_decode(int grid, hipStream_t st, const exr_geom &g, const exr_frame *frames, int n_frames);
+
 #endif

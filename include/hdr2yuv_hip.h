@@ -405,8 +405,88 @@ int h2y_tiff_stream_open(h2y_ctx *ctx, const h2y_desc *d, const h2y_tiff_info *i
 int h2y_tiff_inverse_stream_open(h2y_ctx *ctx, int width, int height, int in_chroma_format_idc, int in_bit_depth, int in_full_range,
                                  int in_matrix_coeffs, int out_bit_depth, int algorithm, int depth);
 
+/* ---- scanline OpenEXR input (read_exr(), exr.cpp:138-255) ---------------------------------------------------------------
+ * read_exr() opens an RgbaInputFile, takes the size from the data window and stores every pixel's half R, G, B as planes
+ * G, B, R (alpha ignored).  Half -> float is exact, so the picture is three half planes for the H2Y_SAMPLE_F16 forward path.
+ * The container and the decompression stay on the host (h2y_exr_parse, h2y_exr_unpack: zlib, RLE); the predictor, the byte
+ * reorder and the scanline-to-plane decode run on the device (k_exr_decode).  What the subset is, as RgbaInputFile (OpenEXR
+ * 2.x) reads it:
+ *   channels  R, G, B are read (A and every other channel take their space in each line and are skipped); a missing R, G or
+ *             B reads +0.0.  A line holds `width` samples of each channel, in the order of the channel names (sorted).
+ *   types     HALF is taken bit for bit; FLOAT through floatToHalf (a finite |f| > 65504 becomes +-inf before rounding,
+ *             otherwise round to nearest even; a NaN keeps its top 10 mantissa bits, 1 if they are all 0); UINT through
+ *             uintToHalf (u > 65504: +inf, otherwise half((float)u)).
+ *   chunks    NONE, RLE, ZIPS: one line each, ZIP: 16 (the last one may hold fewer).  A chunk whose size is its lines'
+ *             uncompressed bytes is stored raw, whatever the compression.
+ * Refused (H2Y_EINVAL, `why` naming the cause): tiled, multi-part and deep files; PIZ, PXR24, B44, B44A, DWAA, DWAB;
+ * luminance/chroma files (Y, RY, BY); a channel with x or y sampling other than 1; an offset table that is broken or points
+ * past the end of the file (OpenEXR would rebuild it by scanning the chunks); a chunk whose y is not its table slot's, or whose
+ * size exceeds its uncompressed bytes. */
+#define H2Y_EXR_NONE 0 /* the file's compression codes this reader takes */
+#define H2Y_EXR_RLE 1
+#define H2Y_EXR_ZIPS 2
+#define H2Y_EXR_ZIP 3
+#define H2Y_EXR_UINT 0 /* pixel types */
+#define H2Y_EXR_HALF 1
+#define H2Y_EXR_FLOAT 2
+#define H2Y_EXR_MISSING (-1)
+#define H2Y_EXR_CHUNK_RAW 0     /* payload flag byte of a chunk: its lines as the file would hold them uncompressed */
+#define H2Y_EXR_CHUNK_ENCODED 1 /* its bytes before the predictor and the reorder (RLE or ZIP expanded) */
+#define H2Y_EXR_FRAMES_PER_LAUNCH 64
+
+typedef struct h2y_exr_info {
+    int32_t width;           /* the data window: width x height pixels from (x_min, y_min) */
+    int32_t height;
+    int32_t x_min;
+    int32_t y_min;
+    int32_t compression;     /* H2Y_EXR_NONE .. H2Y_EXR_ZIP */
+    int32_t line_order;      /* 0 INCREASING_Y, 1 DECREASING_Y (the chunks' order in the file only) */
+    int32_t lines_per_chunk; /* 1, 16 for ZIP */
+    int32_t n_chunks;        /* ceil(height / lines_per_chunk): the offset table's entries */
+    int32_t n_channels;      /* every channel of the file, the skipped ones included */
+    int32_t all_half;        /* 1: every channel is HALF (k_exr_decode's fast path) */
+    int32_t channel_type[3]; /* planes G, B, R (channels G, B, R): H2Y_EXR_UINT/HALF/FLOAT, or H2Y_EXR_MISSING */
+    int32_t channel_offset[3]; /* planes G, B, R: byte offset of the channel's `width` samples within a line; -1 missing */
+    int32_t line_bytes;      /* one line of every channel */
+    int32_t reserved;        /* 0 */
+    uint64_t flags_bytes;    /* the payload's head: one flag byte per chunk, padded to 256 bytes */
+    uint64_t payload_bytes;  /* flags_bytes + height x line_bytes: the unpacked lines follow the flags in row order */
+} h2y_exr_info;
+
+typedef struct h2y_exr_chunk { /* one entry of the offset table, checked */
+    uint64_t offset;       /* file offset of the chunk: int32 y, int32 size, then `size` packed bytes */
+    uint32_t packed_bytes; /* its size field */
+    int32_t row;           /* its first line: y - y_min */
+} h2y_exr_chunk;
+
+/* Parse a scanline OpenEXR file held whole in memory (file: file_bytes bytes).  Host only: no device, no context.  chunks
+ * (may be NULL) receives the n_chunks checked table entries, indexed by increasing y; it needs room for info.n_chunks
+ * (capacity).  Refuses what the block above lists, and a truncated header or table. */
+int h2y_exr_parse(const void *file, size_t file_bytes, h2y_exr_info *out, h2y_exr_chunk *chunks, int capacity, const char **why);
+
+/* Unpack chunks [first_chunk, first_chunk + n_chunks) of a parsed file into payload (info.payload_bytes, host memory): chunk c's
+ * lines go to flags_bytes + chunks[c].row x line_bytes and its flag to payload[c].  A NONE chunk or one stored raw is copied
+ * (H2Y_EXR_CHUNK_RAW); an RLE, ZIPS or ZIP chunk is expanded (H2Y_EXR_CHUNK_ENCODED) and must fill its lines exactly.  The
+ * bytes between the flags and flags_bytes are zeroed by the call that unpacks chunk 0.  Host only; disjoint ranges of one
+ * frame may run on separate threads. */
+int h2y_exr_unpack(const h2y_exr_info *info, const h2y_exr_chunk *chunks, const void *file, int first_chunk, int n_chunks,
+                   void *payload, const char **why);
+
+/* k_exr_decode on n_frames payloads of one info, device buffers, in launches of H2Y_EXR_FRAMES_PER_LAUNCH:
+ *   d_payload[f]       device pointer to frame f's payload (h2y_exr_unpack's layout), 2-byte aligned
+ *   d_planes[f*3 + c]  device pointers to frame f's half planes G, B, R (width x height u16 each), 2-byte aligned
+ * Synchronous.  Chain it with h2y_convert_batch (in_sample_type H2Y_SAMPLE_F16) for the .exr -> .yuv flow on device buffers. */
+int h2y_exr_decode_batch(h2y_ctx *ctx, const h2y_exr_info *info, int n_frames, const void *const *d_payload,
+                         uint16_t *const *d_planes);
+
+/* The h2y_stream_* ring of h2y_stream_open on EXR payloads: each slot does one H2D copy of payload_bytes, k_exr_decode into
+ * the slot's device half planes, the forward conversion of d (in_sample_type H2Y_SAMPLE_F16, width and height the data
+ * window's) and one D2H copy of the .yuv frame.  h2y_stream_input hands out planes[0] = the pinned payload (fill it with
+ * h2y_exr_unpack), planes[1] = planes[2] = NULL; the rest and the exclusivity rules are those of the forward stream. */
+int h2y_exr_stream_open(h2y_ctx *ctx, const h2y_desc *d, const h2y_exr_info *info, int depth /* 2..16 slots */);
+
 /* Timing of the last h2y_convert_batch*() (or h2y_inverse_*, h2y_dpx_decode_batch, h2y_tiff_decode_batch,
- * h2y_rgb_interleave_batch) call measured with HIP events on
+ * h2y_rgb_interleave_batch, h2y_exr_decode_batch) call measured with HIP events on
  * the stream the kernels ran on: total ms over the main kernels and how many
  * launches that covered. */
 int h2y_last_kernel_ms(const h2y_ctx *ctx, float *ms, int *launches);
@@ -414,7 +494,7 @@ int h2y_last_kernel_ms(const h2y_ctx *ctx, float *ms, int *launches);
 /* Name of the kernel those launches ran ("k_fused", "k_fused_t1", "k_fused_lut16",
  * "k_fused_narrow"; of the inverse entries "k_inverse", "k_inverse420", "k_inverse_batch", "k_inverse420_batch"; of
  * h2y_dpx_decode_batch "k_dpx_decode"; of h2y_tiff_decode_batch "k_tiff_decode", of h2y_rgb_interleave_batch
- * "k_rgb_interleave"): the name to
+ * "k_rgb_interleave"; of h2y_exr_decode_batch "k_exr_decode"): the name to
  * look for in a rocprofv3 kernel trace. */
 const char *h2y_last_kernel_name(const h2y_ctx *ctx);
 /* The same with its template arguments and launch shape, e.g. "k_fused_t1<F32,420BOX,YCBCR,PQ_IDENT> groups=8 xcd=1";

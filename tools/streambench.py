@@ -25,6 +25,16 @@ Prints one line per figure, then one JSON line with all of them.
   2. the TIFF inverse ring (h2y_tiff_inverse_stream_open: the inverse kernel, then k_rgb_interleave) against the inverse ring;
   3. the kernel time of h2y_tiff_decode_batch and h2y_rgb_interleave_batch over 64 frames (HIP events, median of reps), and the
      12 B/pixel each moves over that time as a share of the 8 TB/s HBM peak.
+Prints one line per figure, then one JSON line with all of them.
+
+`streambench.py exr`: scanline OpenEXR on 4K half R,G,B pictures, NONE and ZIP:
+  1. ms/frame and frames/s from host memory of the EXR ring (h2y_exr_stream_open: the unpacked payload goes up, k_exr_decode,
+     the forward conversion), each frame unpacked into its pinned slot by UNPACK_THREADS (16) host threads, against the .f16
+     ring (h2y_stream_open) on the same half planes, both at depth 3;
+  2. the kernel time of h2y_exr_decode_batch over 64 frames (HIP events, median of reps), raw (NONE) and encoded (ZIP) chunks,
+     and the algorithmic bytes over that time as a share of the 8 TB/s HBM peak: 6 B/pixel read and 6 written raw, 9 read
+     (the first half of each chunk twice) and 6 written encoded;
+  3. host unpack ms per frame (h2y_exr_unpack, the file already in memory) with that many threads.
 Prints one line per figure, then one JSON line with all of them."""
 import os
 import sys
@@ -341,6 +351,105 @@ def main():
     ctx.close()
 
 
+def exr_main():
+    import json
+    from concurrent.futures import ThreadPoolExecutor
+
+    import torch
+
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    from exr_files import HALF, NONE, ZIP, read_exr, smooth_half, write_exr
+
+    w, hh, nb, reps = 3840, 2160, 64, 5
+    n = w * hh
+    nf = int(os.environ.get("N", "60"))
+    threads = int(os.environ.get("UNPACK_THREADS", "16"))
+    depth = 3
+    ctx = h.Context(0)
+    pool = ThreadPoolExecutor(threads)
+    res = {"width": w, "height": hh, "frames_per_call": nb, "reps": reps, "ring_frames": nf, "ring_depth": depth,
+           "unpack_threads": threads, "hbm_peak_tbs": 8.0}
+
+    def ring(open_fn, fill):
+        open_fn()
+        inflight = 0
+        t0 = time.perf_counter()
+        for _ in range(nf):
+            fill(ctx.stream_input())
+            ctx.stream_submit()
+            inflight += 1
+            if inflight == depth - 1:
+                ctx.stream_output()
+                inflight -= 1
+        while inflight:
+            ctx.stream_output()
+            inflight -= 1
+        dt = (time.perf_counter() - t0) / nf
+        ctx.stream_close()
+        return dt
+
+    def unpack(info, chunks, data, payload):
+        step = max(1, info.n_chunks // (4 * threads))
+        list(pool.map(lambda c0: h.exr_unpack(info, chunks, data, payload, c0, min(step, info.n_chunks - c0)),
+                      range(0, info.n_chunks, step)))
+
+    ch = {name: (HALF, smooth_half(hh, w, 101 * k)) for k, name in enumerate("RGB")}
+    d = h.make_desc(w, hh, sample=h.SAMPLE_F16, dst_depth=10, src_transfer=8, dst_transfer=16, dst_matrix=h.MATRIX_BT2020NC, resampler=1)
+    for comp, cname in ((NONE, "none"), (ZIP, "zip")):
+        data, _ = write_exr(ch, comp)
+        buf = np.frombuffer(data, np.uint8)
+        info, chunks = h.parse_exr(buf)
+        planes = [p.reshape(-1) for p in read_exr(data)]
+
+        def fill_exr(slot):
+            unpack(info, chunks, buf, slot[0])
+
+        def fill_f16(slot):
+            for c in range(3):
+                slot[c][:] = planes[c]
+
+        ring(lambda: ctx.exr_stream_open(d, info, depth), fill_exr)  # warm-up
+        t_exr = ring(lambda: ctx.exr_stream_open(d, info, depth), fill_exr)
+        ring(lambda: ctx.stream_open(d, depth), fill_f16)
+        t_f16 = ring(lambda: ctx.stream_open(d, depth), fill_f16)
+        payload = np.zeros(info.payload_bytes, np.uint8)
+        unpack(info, chunks, buf, payload)
+        t0 = time.perf_counter()
+        for _ in range(10):
+            unpack(info, chunks, buf, payload)
+        t_un = (time.perf_counter() - t0) / 10
+        res[cname] = dict(file_mb=round(len(data) / 1e6, 1), exr_ring_ms=round(t_exr * 1e3, 2), exr_ring_fps=round(1 / t_exr, 1),
+                          f16_ring_ms=round(t_f16 * 1e3, 2), f16_ring_fps=round(1 / t_f16, 1), ratio=round(t_f16 / t_exr, 2),
+                          unpack_ms=round(t_un * 1e3, 2))
+        print(f"{cname:4s} ({len(data)/1e6:5.1f} MB file): exr ring {t_exr*1e3:6.2f} ms/frame {1/t_exr:6.1f} frames/s   "
+              f".f16 ring {t_f16*1e3:6.2f} ms/frame {1/t_f16:6.1f} frames/s   ({t_f16/t_exr:4.2f}x)   "
+              f"host unpack {t_un*1e3:6.2f} ms/frame with {threads} threads", flush=True)
+
+        # the kernel over 64 frames on the device: 64 distinct payloads and outputs
+        dev = torch.from_numpy(payload).cuda()
+        pays = [dev.clone() for _ in range(nb)]
+        outs = [[torch.empty(n, dtype=torch.int16, device="cuda") for _ in range(3)] for _ in range(nb)]
+        torch.cuda.synchronize()
+        ks = []
+        for rep in range(reps + 1):  # rep 0 warms up
+            ctx.exr_decode_batch(info, pays, outs)
+            if rep:
+                ks.append(ctx.last_kernel_ms()[0] / nb)
+        k_ms = float(np.median(ks))
+        nbytes = (12 if comp == NONE else 15) * n
+        tbs = nbytes / (k_ms * 1e-3) / 1e12
+        got = [o.cpu().numpy().view(np.uint16) for o in outs[nb - 1]]
+        assert all(np.array_equal(g, p) for g, p in zip(got, planes)), "k_exr_decode differs from read_exr"
+        res[cname].update(kernel_us_per_frame=round(k_ms * 1e3, 1), bytes_per_frame=nbytes, kernel_tbs=round(tbs, 2),
+                          hbm_peak_fraction=round(tbs / 8.0, 3), variant=ctx.last_kernel_variant())
+        print(f"k_exr_decode {cname:4s} {nb} frames per call: {k_ms*1e3:6.1f} us/frame  {nbytes/1e6:6.1f} MB/frame  {tbs:5.2f} TB/s = "
+              f"{tbs/8.0*100:4.1f} % of 8 TB/s", flush=True)
+        del pays, outs, dev
+    pool.shutdown()
+    ctx.close()
+    print(json.dumps({"streambench_exr": res}), flush=True)
+
+
 if __name__ == "__main__":
     if sys.argv[1:] == ["inverse"]:
         inverse_main()
@@ -348,5 +457,7 @@ if __name__ == "__main__":
         dpx_main()
     elif sys.argv[1:] == ["tiff"]:
         tiff_main()
+    elif sys.argv[1:] == ["exr"]:
+        exr_main()
     else:
         main()
