@@ -10,6 +10,7 @@ a :class:`Context` needs a HIP device and the built library.
 from .api import (  # noqa: F401
     CHROMA_420,
     CHROMA_444,
+    H2YCompareStats,
     H2YDesc,
     H2YDpxInfo,
     H2YError,

@@ -33,7 +33,10 @@ EXPORTS = [
     "h2y_inverse_batch", "h2y_inverse_stream_open", "h2y_dpx_parse", "h2y_dpx_decode_batch", "h2y_dpx_stream_open",
     "h2y_tiff_parse", "h2y_tiff_layout", "h2y_tiff_decode_batch", "h2y_rgb_interleave_batch", "h2y_tiff_stream_open",
     "h2y_tiff_inverse_stream_open", "h2y_exr_parse", "h2y_exr_unpack", "h2y_exr_decode_batch", "h2y_exr_stream_open",
+    "h2y_compare_batch", "h2y_stream_compare", "h2y_stream_reference", "h2y_stream_compare_result", "h2y_compare_stream_open",
 ]
+
+COMPARE_FRAMES_PER_LAUNCH = 64
 
 
 class H2YError(RuntimeError):
@@ -119,6 +122,24 @@ class H2YExrChunk(C.Structure):
     """h2y_exr_chunk: one checked entry of the offset table."""
 
     _fields_ = [("offset", C.c_uint64), ("packed_bytes", C.c_uint32), ("row", C.c_int32)]
+
+
+class H2YCompareStats(C.Structure):
+    """h2y_compare_stats: per plane (0, 1, 2 = Y, Cb, Cr or G, B, R) the samples compared, the sums of squared and absolute
+    differences, the count of |a - b| > sigma and the plane index of the first of them (-1: none), max |a - b|, and a and b
+    at that first sample."""
+
+    _fields_ = [
+        ("samples", C.c_uint64 * 3), ("sse", C.c_uint64 * 3), ("sad", C.c_uint64 * 3), ("over", C.c_uint64 * 3),
+        ("first_over", C.c_int64 * 3), ("max_abs", C.c_uint32 * 3), ("first_a", C.c_uint32 * 3), ("first_b", C.c_uint32 * 3),
+        ("reserved", C.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {k: list(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
+
+    def __repr__(self):
+        return f"H2YCompareStats({self.as_dict()})"
 
 
 def make_desc(width, height, *, sample=SAMPLE_F32, src_depth=32, dst_depth=10, src_transfer=TRANSFER_LINEAR,
@@ -274,6 +295,17 @@ def load_library():
     L.h2y_exr_stream_open.restype = C.c_int
     L.h2y_exr_stream_open.argtypes = [C.c_void_p, C.POINTER(H2YDesc), C.POINTER(H2YExrInfo), C.c_int]
     L.h2y_stream_open.restype = C.c_int
+    L.h2y_compare_batch.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                                                     C.POINTER(H2YCompareStats)]
+    L.h2y_compare_batch.restype = C.c_int
+    L.h2y_stream_compare.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.h2y_stream_compare.restype = C.c_int
+    L.h2y_stream_reference.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    L.h2y_stream_reference.restype = C.c_int
+    L.h2y_stream_compare_result.argtypes = [C.c_void_p, C.POINTER(H2YCompareStats)]
+    L.h2y_stream_compare_result.restype = C.c_int
+    L.h2y_compare_stream_open.argtypes = [C.c_void_p] + [C.c_int] * 5
+    L.h2y_compare_stream_open.restype = C.c_int
     L.h2y_stream_open.argtypes = [C.c_void_p, C.POINTER(H2YDesc), C.c_int]
     L.h2y_stream_input.restype = C.c_int
     L.h2y_stream_input.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
@@ -590,7 +622,50 @@ class Context:
                 outs[3 * f + c] = self._ptr(planes_out[f][c])
         self._check(self.lib.h2y_exr_decode_batch(self.h, C.byref(info), n, pay, outs))
 
+    def compare_batch(self, width, height, chroma, sigma, frames_a, frames_b):
+        """k_compare on device frame pairs (tensors or pointers, each frame's planes contiguous from a 16-byte aligned base):
+        one H2YCompareStats per frame."""
+        n = len(frames_a)
+        if len(frames_b) != n:
+            raise ValueError("frames_a and frames_b differ in length")
+        pa = (C.c_void_p * n)(*[self._ptr(x) for x in frames_a])
+        pb = (C.c_void_p * n)(*[self._ptr(x) for x in frames_b])
+        out = (H2YCompareStats * max(n, 1))()
+        self._check(self.lib.h2y_compare_batch(self.h, width, height, chroma, sigma, n, pa, pb, out))
+        return list(out[:n])
+
     # ---- host <-> device pipeline -----------------------------------------------------------
+    def stream_compare(self, sigma, keep_output=1) -> None:
+        """Arm the open ring: every frame is compared with the reference stream_reference lends for it."""
+        self._check(self.lib.h2y_stream_compare(self.h, sigma, keep_output))
+        if getattr(self, "_stream_inverse", None):
+            w, h, _ = self._stream_inverse
+            self._stream_ref_shape = (3 * w * h,)
+        else:
+            self._stream_ref_shape = (frame_bytes(self._stream_desc) // 2,)
+
+    def stream_reference(self):
+        """The pinned reference slot of the frame about to be submitted, a uint16 view to fill in place (a .yuv frame on the
+        forward rings, G | B | R on the inverse rings, the three planes of a compare-only ring)."""
+        p = C.c_void_p()
+        self._check(self.lib.h2y_stream_reference(self.h, C.byref(p)))
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint16)), shape=self._stream_ref_shape)
+
+    def stream_compare_result(self) -> H2YCompareStats:
+        st = H2YCompareStats()
+        self._check(self.lib.h2y_stream_compare_result(self.h, C.byref(st)))
+        return st
+
+    def compare_stream_open(self, width, height, chroma, sigma, depth=3) -> None:
+        """A ring that only compares: stream_input lends A's three planes, stream_reference B's frame in the same layout."""
+        self._check(self.lib.h2y_compare_stream_open(self.h, width, height, chroma, sigma, depth))
+        nc = (width >> 1) * (height >> 1) if chroma == CHROMA_420 else width * height
+        self._stream_inverse = None
+        self._stream_dpx = None
+        self._stream_rgb = False
+        self._stream_cmp_planes = (width * height, nc, nc)
+        self._stream_ref_shape = (width * height + 2 * nc,)
+
     def stream_open(self, d, depth=3) -> None:
         self._check(self.lib.h2y_stream_open(self.h, C.byref(d), depth))
         self._stream_desc = d
@@ -650,6 +725,8 @@ class Context:
 
         ptrs = (C.c_void_p * 3)()
         self._check(self.lib.h2y_stream_input(self.h, ptrs))
+        if getattr(self, "_stream_cmp_planes", None):
+            return [np.ctypeslib.as_array(C.cast(ptrs[c], C.POINTER(C.c_uint16)), shape=(n,)) for c, n in enumerate(self._stream_cmp_planes)]
         if getattr(self, "_stream_dpx", None):
             return [np.ctypeslib.as_array(C.cast(ptrs[0], C.POINTER(C.c_uint8)), shape=(self._stream_dpx,))]
         if getattr(self, "_stream_inverse", None):
@@ -671,6 +748,8 @@ class Context:
 
         p = C.POINTER(C.c_uint16)()
         self._check(self.lib.h2y_stream_output(self.h, C.byref(p)))
+        if not p:  # an armed ring with keep_output 0, or a compare-only ring: the frame stayed on the device
+            return None
         if getattr(self, "_stream_inverse", None):
             w, h, _ = self._stream_inverse
             if getattr(self, "_stream_rgb", False):
@@ -680,6 +759,7 @@ class Context:
 
     def stream_close(self) -> None:
         self._check(self.lib.h2y_stream_close(self.h))
+        self._stream_cmp_planes = None
         self._stream_inverse = None
         self._stream_dpx = None
         self._stream_rgb = False

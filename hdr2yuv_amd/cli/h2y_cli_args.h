@@ -25,6 +25,14 @@
  *   .exr: read_exr() (exr.cpp:138-255) takes the size from the data window (refused here when it differs from
  *             --src_pic_width/--src_pic_height, also under --dry_run) and forces the input picture as above
  *   .tiff output: write_tiff() (tiff.cpp:559-652) from .yuv input only (hdr2yuv.cpp:818-819, 931-933); the file is opened "w"
+ * --ref_filename R / --sigma_compare S (hdr2yuv.cpp:91-100 parses them, :442-457 types R, :827-833 leaves the comparison a TODO):
+ *             R holds what the run produces -- .yuv for .yuv output (the destination's size, chroma format and depth), planar
+ *             .rgb (R, G, B planes, as this program writes .rgb) for .rgb or .tiff output -- and output frame k is compared with
+ *             frame k of R on the device.  Refused before anything runs (exit 1): R a .tiff, .exr or .dpx, R of another type than
+ *             the output, R holding fewer frames than the run produces or not a whole number of frames.  With R the destination
+ *             may be left out: the run converts and compares and writes nothing, its output type taken from R.
+ *             --compare_only 1 (an addition) compares --src_filename (.yuv or .rgb, read with the --src_* size, depth and chroma
+ *             format -- 1 or 3 for .yuv, 3 for .rgb --, from --src_start_frame on) with R (same layout, from its frame 0), --n_frames of each; no conversion.
  * Only user_args_t.chroma_resampler_type has no defined default there (never initialised): FIR here, as in
  * make.sh's example.  The reference calls exit(0) on its argument errors; this program returns 1.
  */
@@ -56,6 +64,10 @@ struct cli_args {
     int cutout = 0; /* H2Y_TIFF_CUTOUT_* bits of --cutout_hd / --cutout_qhd (read_tiff only) */
     /* additional flags of this build */
     int synthetic = -1, device = 0, gpus = 1, dry_run = 0, help = 0;
+    /* the comparison: --ref_filename, --sigma_compare (exit status 3 on a sample beyond it only when it was given), --compare_only */
+    const char *ref = nullptr;
+    int sigma = 0, compare_only = 0;
+    bool sigma_given = false;
     std::vector<int> devices;
     /* resolved */
     int in_type = CLI_IN_NONE, out_type = CLI_OUT_NONE;
@@ -106,6 +118,8 @@ static inline void cli_help()
            "  [--src_video_full_range_flag 0|1] [--dst_video_full_range_flag 0|1] [--chroma_resampler_type 0|1]\n"
            "  unset source attributes are 0, unset destination attributes take the source's (as the reference resolves them)\n"
            "  additional: [--synthetic SEEDFRAME] [--device D] [--gpus N [--devices d0,d1,..]] [--dry_run 1]\n"
+           "  compare: [--ref_filename R.yuv|R.rgb [--sigma_compare S]] (the output against R, frame by frame; without\n"
+           "  --dst_filename nothing is written), [--compare_only 1] (--src_filename against R, no conversion)\n"
            "input by extension: .yuv .rgb (16-bit planar), .f32 .f16 (raw planar float / half, plane order G,B,R: what\n"
            "  dpx_read() / read_exr() leave in memory), .dpx (10-bit, 16-bit or float DPX) and .tiff (16-bit R,G,B, uncompressed; centre-cropped\n"
            "  to 3840 wide, [--cutout_hd 1] 1920x1080, [--cutout_qhd 1] 960x540) and .exr (scanline OpenEXR: NONE, RLE, ZIPS or ZIP;\n"
@@ -127,7 +141,10 @@ static inline void cli_parse(cli_args &a, int argc, char **argv)
         if (is("--help")) { cli_help(); a.help = 1; } /* :82-85: prints and carries on */
         else if (is("--src_filename")) a.src = val();
         else if (is("--dst_filename")) a.dst = val();
-        else if (is("--ref_filename") || is("--sigma_compare") || is("--alpha_channel")) (void)val(); /* (read_tiff ignores alpha too) */
+        else if (is("--ref_filename")) a.ref = val();
+        else if (is("--sigma_compare")) { a.sigma = atoi(val()); a.sigma_given = true; }
+        else if (is("--compare_only")) a.compare_only = atoi(val());
+        else if (is("--alpha_channel")) (void)val(); /* (read_tiff ignores alpha too) */
         else if (is("--cutout_hd")) a.cutout = atoi(val()) ? (a.cutout | H2Y_TIFF_CUTOUT_HD) : (a.cutout & ~H2Y_TIFF_CUTOUT_HD);
         else if (is("--cutout_qhd")) a.cutout = atoi(val()) ? (a.cutout | H2Y_TIFF_CUTOUT_QHD) : (a.cutout & ~H2Y_TIFF_CUTOUT_QHD);
         else if (is("--src_pic_width")) a.in.width = atoi(val());
@@ -168,9 +185,61 @@ static inline void cli_parse(cli_args &a, int argc, char **argv)
     }
 }
 
+/* The reference file's type against the output's: 0, or a warning printed and 1 */
+static inline int cli_ref_check(const cli_args &a)
+{
+    const char *ext = cli_ext_of(a.ref);
+    if (!strcasecmp(ext, "tiff") || !strcasecmp(ext, "exr") || !strcasecmp(ext, "dpx")) {
+        printf("WARNING: reference file (%s): .%s is not read for a comparison; give the samples as .rgb (planar R, G, B)\n", a.ref, ext);
+        return 1;
+    }
+    const bool yuv = a.compare_only ? a.in_type == CLI_IN_YUV : a.out_type == CLI_OUT_YUV;
+    if (strcasecmp(ext, yuv ? "yuv" : "rgb")) {
+        printf("WARNING: reference file (%s) must be a .%s: it holds frames in the layout of the %s\n", a.ref, yuv ? "yuv" : "rgb",
+               a.compare_only ? "source" : "output");
+        return 1;
+    }
+    return 0;
+}
+
+/* --compare_only 1: two files of one layout, no conversion; returns the number of argument errors */
+static inline int cli_resolve_compare(cli_args &a)
+{
+    int arg_errors = 0;
+    const char *ext = cli_ext_of(a.src);
+    if (!strcasecmp(ext, "yuv")) a.in_type = CLI_IN_YUV;
+    else if (!strcasecmp(ext, "rgb")) a.in_type = CLI_IN_RGB;
+    else {
+        printf("WARNING: --compare_only reads .yuv or .rgb; source file (%s) is a .%s\n", a.src ? a.src : "(none)", ext);
+        arg_errors++;
+    }
+    if (a.dst) { printf("WARNING: --compare_only writes nothing: leave out --dst_filename\n"); arg_errors++; }
+    if (!a.ref) { printf("WARNING: --compare_only needs --ref_filename\n"); arg_errors++; }
+    else if (a.in_type != CLI_IN_NONE) arg_errors += cli_ref_check(a);
+    printf("compare_only: 1\nsrc_filename: %s\nref_filename: %s\n", a.src ? a.src : "(none)", a.ref ? a.ref : "(none)");
+    printf("src_pic_width: %d\nsrc_pic_height: %d\nsrc_chroma_format_idc: %d\nsrc_bit_depth: %d\nsrc_start_frame: %d\nn_frames: %d\n",
+           a.in.width, a.in.height, a.in.chroma_format_idc, a.in.bit_depth, a.start_frame, a.n_frames);
+    printf("sigma_compare: %d%s\n", a.sigma, a.sigma_given ? "" : " (default)");
+    if (a.in.width < 1 || a.in.width > 10000) { printf("WARNING: pic_width(%d) outside range [1,10000]\n", a.in.width); arg_errors++; }
+    if (a.in.height < 1 || a.in.height > 10000) { printf("WARNING: pic_height(%d) outside range [1,10000]\n", a.in.height); arg_errors++; }
+    if (a.in.bit_depth < 8 || a.in.bit_depth > 16) { printf("WARNING: src bit_depth(%d) outside range [8,16]\n", a.in.bit_depth); arg_errors++; }
+    if (a.in.chroma_format_idc != H2Y_CHROMA_420 && a.in.chroma_format_idc != H2Y_CHROMA_444) {
+        printf("WARNING: chroma_format_idc(%d) not %d or %d\n", a.in.chroma_format_idc, H2Y_CHROMA_420, H2Y_CHROMA_444);
+        arg_errors++;
+    } else if (a.in_type == CLI_IN_RGB && a.in.chroma_format_idc != H2Y_CHROMA_444) { /* three full planes R, G, B */
+        printf("WARNING: a .rgb holds three planes of width x height: --compare_only of .rgb files takes chroma_format_idc %d, not %d\n",
+               H2Y_CHROMA_444, a.in.chroma_format_idc);
+        arg_errors++;
+    }
+    if (a.sigma < 0) { printf("WARNING: sigma_compare(%d) is negative\n", a.sigma); arg_errors++; }
+    a.out = a.in;
+    return arg_errors;
+}
+
 /* hdr2yuv.cpp:265-572 and the attribute overrides of read_file(); returns the number of argument errors */
 static inline int cli_resolve(cli_args &a)
 {
+    if (a.compare_only) return cli_resolve_compare(a);
     int arg_errors = 0;
     /* :265-318: unset destination attributes <- the source's, as parsed */
     if (a.out.bit_depth == 0) a.out.bit_depth = a.in.bit_depth;
@@ -205,8 +274,8 @@ static inline int cli_resolve(cli_args &a)
         a.in.chroma_format_idc = H2Y_CHROMA_444; /* :351-355: after the destination took its copy */
     }
 
-    /* :386-440 output type */
-    ext = cli_ext_of(a.dst);
+    /* :386-440 output type (without a destination: the reference file's) */
+    ext = cli_ext_of(a.dst ? a.dst : a.ref);
     if (!strcasecmp(ext, "yuv")) a.out_type = CLI_OUT_YUV;
     else if (!strcasecmp(ext, "rgb")) a.out_type = CLI_OUT_RGB;
     else if (!strcasecmp(ext, "tiff")) a.out_type = CLI_OUT_TIFF;
@@ -214,6 +283,8 @@ static inline int cli_resolve(cli_args &a)
     if (a.out_type == CLI_OUT_NONE) {
         printf("WARNING: output file (%s) type extension (%s) is either not recongized or not supported\n", a.dst ? a.dst : "(none)", ext);
         arg_errors++;
+    } else if (!a.dst && (a.out_type == CLI_OUT_TIFF || a.out_type == CLI_OUT_CODEC)) { /* the reference names the output type */
+        arg_errors += cli_ref_check(a);
     } else if (a.out_type == CLI_OUT_CODEC) {
         printf("WARNING: output file (%s): the .%s writers stay with the reference's host I/O; this program writes .yuv, and\n"
                "         from .yuv input .tiff (or its samples as planar .rgb)\n", a.dst, ext);
@@ -230,6 +301,8 @@ static inline int cli_resolve(cli_args &a)
         printf("WARNING: .tiff output is the .yuv -> RGB flow's (matrix_inverse): it takes .yuv input only\n");
         arg_errors++;
     }
+    if (a.ref && a.dst && a.out_type != CLI_OUT_NONE && a.out_type != CLI_OUT_CODEC) arg_errors += cli_ref_check(a);
+    if (a.sigma < 0) { printf("WARNING: sigma_compare(%d) is negative\n", a.sigma); arg_errors++; }
 
     const bool numbered = (a.in_type == CLI_IN_DPX || a.in_type == CLI_IN_TIFF || a.in_type == CLI_IN_EXR) && cli_frame_pattern(a.src) == 1;
     if (a.start_frame != 0 && (!int_in || a.in_type == CLI_IN_TIFF) && a.in_type != CLI_IN_F32 && a.in_type != CLI_IN_F16 &&
@@ -243,6 +316,7 @@ static inline int cli_resolve(cli_args &a)
     printf("src_full_range_video_flag: %d\nsrc_colour_primaries: %d\nsrc_transfer_characteristics: %d\nsrc_matrix_coeffs: %d\n",
            a.in.video_full_range_flag, a.in.colour_primaries, a.in.transfer_characteristics, a.in.matrix_coeffs);
     printf("dst_filename: %s\n", a.dst ? a.dst : "(none)");
+    if (a.ref) printf("ref_filename: %s\nsigma_compare: %d%s\n", a.ref, a.sigma, a.sigma_given ? "" : " (default)");
     printf("dst_pic_width: %d\ndst_pic_height: %d\ndst_chroma_format_idc: %d\ndst_bit_depth: %d\ndst_half_float_flag: %d\n",
            a.out.width, a.out.height, a.out.chroma_format_idc, a.out.bit_depth, a.out.half_float_flag);
     printf("dst_video_full_range_flag: %d\ndst_colour_primaries: %d\ndst_transfer_characteristics: %d\ndst_matrix_coeffs: %d\n",

@@ -28,6 +28,20 @@
  * its own context and pinned ring; thread r takes a contiguous block of the frame indices (the split of
  * hdr2yuv_amd/shard.py), reads frame k at its offset in the source (hdr2yuv.cpp:624) and writes it at
  * `size of the file at start + k x frame bytes` -- the bytes N appending runs in frame order would have left (tiff.cpp:440).
+ *
+ * Comparison (--ref_filename R [--sigma_compare S], or --compare_only 1; h2y_cli_args.h): each GPU thread arms its ring
+ * (h2y_stream_compare; with no destination the frames stay on the device) or opens a compare-only ring, reads frame k of R into
+ * the reference slot beside the input, and keeps the stats of frame k by its index; the report is printed once every thread is
+ * done, so it is the same for any --gpus.  Report on stdout, planes Y Cb Cr for .yuv and G B R for .rgb / .tiff, maxv =
+ * 2^bit_depth - 1 of the compared frames (the destination's, or the source's under --compare_only), PSNR of n samples with a sum
+ * of squared differences sse printed "%.4f" of 10 * log10((double)maxv * maxv * n / sse) in double arithmetic, or "inf" for
+ * sse 0:
+ *   frame <k> psnr <P0> <psnr> <P1> <psnr> <P2> <psnr> max_abs <m0> <m1> <m2> over <o0> <o1> <o2>     one line per frame, in order
+ *   summary frames <N> mean_psnr <P0> <m> <P1> <m> <P2> <m> global_psnr <P0> <g> <P1> <g> <P2> <g> max_abs <m0> <m1> <m2> over <o0> <o1> <o2>
+ *   first_over frame <k> plane <P> x <x> y <y> a <a> b <b>       (or "first_over none")
+ * mean_psnr: the mean over frames of the per-frame value, a frame with sse 0 counting 99.99; global_psnr: from the summed sse
+ * and samples; max_abs the largest |a - b|, over the count of |a - b| > S (S 0 by default); first_over the first such sample in
+ * frame, plane and raster order, a the output's (the source's) sample, b R's.  Exit status 3 when S was given and over > 0.
  */
 #include <algorithm>
 #include <atomic>
@@ -37,6 +51,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <cmath>
 #include <fcntl.h>
 #include <memory>
 #include <mutex>
@@ -372,11 +387,42 @@ struct block { /* one thread's share: frames [first, first + count) of the run, 
     long done = 0;
 };
 
+/* frame k of the reference file into a ring's reference slot: the whole frame as the file holds it, or, for a .rgb (planes
+ * R, G, B in the file), into the slot's G | B | R order */
+static bool read_ref(FILE *f, bool rgb, size_t plane_bytes, size_t frame_bytes, void *ref)
+{
+    if (!rgb) return fread(ref, 1, frame_bytes, f) == frame_bytes;
+    if (frame_bytes != 3 * plane_bytes) return false; /* a .rgb frame is three full planes: nothing else fits the slot */
+    char *p = static_cast<char *>(ref);
+    return fread(p + 2 * plane_bytes, 1, plane_bytes, f) == plane_bytes && fread(p, 1, 2 * plane_bytes, f) == 2 * plane_bytes;
+}
+
+/* the comparison side of one GPU thread: R opened at its frame `first`, the stats kept by frame index */
+struct compare_io {
+    std::vector<h2y_compare_stats> *stats = nullptr;
+    FILE *ref = nullptr;
+    bool rgb = false;
+    size_t plane_bytes = 0, frame_bytes = 0;
+    bool open(const cli_args &a, long first, size_t plane_b, size_t frame_b, std::vector<h2y_compare_stats> *st)
+    {
+        stats = st;
+        if (!a.ref) return true;
+        rgb = !strcasecmp(cli_ext_of(a.ref), "rgb");
+        plane_bytes = plane_b, frame_bytes = frame_b;
+        ref = fopen(a.ref, "rb");
+        return ref && !fseeko(ref, (off_t)frame_b * (off_t)first, SEEK_SET);
+    }
+    ~compare_io()
+    {
+        if (ref) fclose(ref);
+    }
+};
+
 /* forward path: frames [first, first+count) through one context's pinned ring (dpx: frame k is file dpx[k], decoded on the
  * device -- the ring of h2y_dpx_stream_open; tiff likewise, file tiff[k] through h2y_tiff_stream_open) */
 static void run_block(const cli_args &a, const h2y_desc &d, const std::vector<dpx_src> &dpx, const h2y_dpx_info &di,
                       const std::vector<tiff_src> &tiff, const h2y_tiff_info &ti, const std::vector<std::string> &exr,
-                      const h2y_exr_info &xi, int fd_out, off_t base, block *b)
+                      const h2y_exr_info &xi, int fd_out, off_t base, std::vector<h2y_compare_stats> *stats, block *b)
 {
     h2y_ctx *ctx = nullptr;
     FILE *fin = nullptr;
@@ -401,6 +447,9 @@ static void run_block(const cli_args &a, const h2y_desc &d, const std::vector<dp
                         : a.in_type == CLI_IN_EXR  ? h2y_exr_stream_open(ctx, &d, &xi, depth)
                                                    : h2y_stream_open(ctx, &d, depth);
     if (open_rc) return fail(h2y_last_error(ctx));
+    compare_io cmp;
+    if (!cmp.open(a, b->first, 0, ob, stats)) return fail(std::string("unable to read ") + a.ref);
+    if (cmp.ref && h2y_stream_compare(ctx, a.sigma, a.dst ? 1 : 0)) return fail(h2y_last_error(ctx));
     std::unique_ptr<unpack_pool> pool;
     std::vector<h2y_exr_chunk> chunks;
     if (a.in_type == CLI_IN_EXR) {
@@ -412,8 +461,9 @@ static void run_block(const cli_args &a, const h2y_desc &d, const std::vector<dp
         const uint16_t *yuv = nullptr;
         if (h2y_stream_output(ctx, &yuv)) { fail(h2y_last_error(ctx)); return false; }
         const long k = b->first + b->done;
-        if (!write_at(fd_out, yuv, ob, base + (off_t)k * (off_t)ob)) { fail(std::string("short write to ") + a.dst); return false; }
-        if (a.verbose > 0) printf("frame %ld: %zu bytes written to %s (device %d)\n", k, ob, a.dst, b->device);
+        if (cmp.ref && h2y_stream_compare_result(ctx, &(*cmp.stats)[k])) { fail(h2y_last_error(ctx)); return false; }
+        if (a.dst && !write_at(fd_out, yuv, ob, base + (off_t)k * (off_t)ob)) { fail(std::string("short write to ") + a.dst); return false; }
+        if (a.verbose > 0 && a.dst) printf("frame %ld: %zu bytes written to %s (device %d)\n", k, ob, a.dst, b->device);
         b->done++;
         in_flight--;
         return true;
@@ -458,6 +508,11 @@ static void run_block(const cli_args &a, const h2y_desc &d, const std::vector<dp
             for (int k = 0; k < 3; k++) got += fread(planes[ord[k]], 1, pb, fin);
             if (got != 3 * pb) return fail("only " + std::to_string(got) + " bytes read from " + a.src + ", expecting " + std::to_string(3 * pb));
         } else synth_fill(d, planes, 12345u + (uint32_t)(a.synthetic + a.start_frame + b->first + f));
+        if (cmp.ref) {
+            void *ref = nullptr;
+            if (h2y_stream_reference(ctx, &ref)) return fail(h2y_last_error(ctx));
+            if (!read_ref(cmp.ref, false, 0, ob, ref)) return fail(std::string("short read from ") + a.ref);
+        }
         if (h2y_stream_submit(ctx)) return fail(h2y_last_error(ctx));
         in_flight++;
         if (in_flight == depth - 1 && !drain_one()) return;
@@ -477,7 +532,7 @@ struct tiff_wrap {
 
 /* .yuv -> RGB (matrix_inverse): frames [first, first+count) through one context's pinned inverse ring, as run_block; .tiff
  * output: the ring with the interleave (h2y_tiff_inverse_stream_open), frame k into its own file, head + samples + tail */
-static void run_block_inverse(const cli_args &a, const tiff_wrap &tw, int fd_out, off_t base, block *b)
+static void run_block_inverse(const cli_args &a, const tiff_wrap &tw, int fd_out, off_t base, std::vector<h2y_compare_stats> *stats, block *b)
 {
     h2y_ctx *ctx = nullptr;
     FILE *fin = nullptr;
@@ -500,11 +555,20 @@ static void run_block_inverse(const cli_args &a, const tiff_wrap &tw, int fd_out
                                                                        a.in.bit_depth, a.in.video_full_range_flag, a.in.matrix_coeffs,
                                                                        a.out.bit_depth, a.resampler, depth))
         return fail(h2y_last_error(ctx));
+    compare_io cmp;
+    if (!cmp.open(a, b->first, 2 * n, out_frame, stats)) return fail(std::string("unable to read ") + a.ref);
+    if (cmp.ref && h2y_stream_compare(ctx, a.sigma, a.dst ? 1 : 0)) return fail(h2y_last_error(ctx));
     long in_flight = 0;
     auto drain_one = [&]() -> bool {
         const uint16_t *gbr = nullptr;
         if (h2y_stream_output(ctx, &gbr)) { fail(h2y_last_error(ctx)); return false; }
         const long k = b->first + b->done;
+        if (cmp.ref && h2y_stream_compare_result(ctx, &(*cmp.stats)[k])) { fail(h2y_last_error(ctx)); return false; }
+        if (!a.dst) {
+            b->done++;
+            in_flight--;
+            return true;
+        }
         if (tiff) { /* TIFFOpen(filename, "w"): a new file */
             const std::string path = cli_frame_name(a.dst, a.start_frame + k);
             const int fd = open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
@@ -533,6 +597,11 @@ static void run_block_inverse(const cli_args &a, const tiff_wrap &tw, int fd_out
         got += fread(planes[1], 1, 2 * nc, fin);
         got += fread(planes[2], 1, 2 * nc, fin);
         if (got != in_frame) return fail(std::string("short read from ") + a.src);
+        if (cmp.ref) {
+            void *ref = nullptr;
+            if (h2y_stream_reference(ctx, &ref)) return fail(h2y_last_error(ctx));
+            if (!read_ref(cmp.ref, true, 2 * n, out_frame, ref)) return fail(std::string("short read from ") + a.ref);
+        }
         if (h2y_stream_submit(ctx)) return fail(h2y_last_error(ctx));
         in_flight++;
         if (in_flight == depth - 1 && !drain_one()) return;
@@ -544,11 +613,105 @@ static void run_block_inverse(const cli_args &a, const tiff_wrap &tw, int fd_out
     h2y_ctx_destroy(ctx);
 }
 
+/* --compare_only: frames [first, first+count) of the source against the same frames of R through one compare-only ring */
+static void run_block_compare(const cli_args &a, size_t plane_bytes, size_t frame_bytes, std::vector<h2y_compare_stats> *stats, block *b)
+{
+    h2y_ctx *ctx = nullptr;
+    FILE *fin = nullptr;
+    auto fail = [&](const std::string &m) {
+        b->err = m;
+        if (ctx) { h2y_stream_close(ctx); h2y_ctx_destroy(ctx); }
+        if (fin) fclose(fin);
+    };
+    if (b->count < 1) return;
+    if (h2y_ctx_create(b->device, &ctx)) return fail(h2y_last_error(nullptr));
+    fin = fopen(a.src, "rb");
+    if (!fin) return fail(std::string("unable to open file ") + a.src);
+    if (fseeko(fin, (off_t)frame_bytes * (off_t)(a.start_frame + b->first), SEEK_SET)) return fail("seek failed");
+    compare_io cmp;
+    if (!cmp.open(a, b->first, plane_bytes, frame_bytes, stats)) return fail(std::string("unable to read ") + a.ref);
+    const int depth = 3;
+    if (h2y_compare_stream_open(ctx, a.in.width, a.in.height, a.in.chroma_format_idc, a.sigma, depth)) return fail(h2y_last_error(ctx));
+    long in_flight = 0;
+    auto drain_one = [&]() -> bool {
+        const uint16_t *none = nullptr;
+        const long k = b->first + b->done;
+        if (h2y_stream_output(ctx, &none) || h2y_stream_compare_result(ctx, &(*stats)[k])) { fail(h2y_last_error(ctx)); return false; }
+        b->done++;
+        in_flight--;
+        return true;
+    };
+    for (long f = 0; f < b->count; f++) {
+        void *planes[3], *ref = nullptr;
+        if (h2y_stream_input(ctx, planes) || h2y_stream_reference(ctx, &ref)) return fail(h2y_last_error(ctx));
+        /* the slot's planes lie one after the other: a frame is one read, a .rgb one with its planes put in G, B, R order */
+        if (!read_ref(fin, cmp.rgb, plane_bytes, frame_bytes, planes[0])) return fail(std::string("short read from ") + a.src);
+        if (!read_ref(cmp.ref, cmp.rgb, plane_bytes, frame_bytes, ref)) return fail(std::string("short read from ") + a.ref);
+        if (h2y_stream_submit(ctx)) return fail(h2y_last_error(ctx));
+        in_flight++;
+        if (in_flight == depth - 1 && !drain_one()) return;
+    }
+    while (in_flight > 0)
+        if (!drain_one()) return;
+    h2y_stream_close(ctx);
+    fclose(fin);
+    h2y_ctx_destroy(ctx);
+}
+
+static std::string psnr_str(uint64_t maxv, uint64_t n, uint64_t sse)
+{
+    if (sse == 0) return "inf";
+    char buf[64];
+    snprintf(buf, sizeof buf, "%.4f", 10.0 * log10((double)maxv * maxv * n / sse));
+    return buf;
+}
+
+/* the report of the header comment; returns the exit status (3: over-sigma samples with --sigma_compare given) */
+static int compare_report(const cli_args &a, bool yuv, int bit_depth, const std::vector<h2y_compare_stats> &st)
+{
+    static const char *const kYuv[3] = {"Y", "Cb", "Cr"}, *const kRgb[3] = {"G", "B", "R"};
+    const char *const *name = yuv ? kYuv : kRgb;
+    const uint64_t maxv = (1ull << bit_depth) - 1;
+    uint64_t n[3] = {0, 0, 0}, sse[3] = {0, 0, 0}, over[3] = {0, 0, 0};
+    uint32_t mx[3] = {0, 0, 0};
+    double mean[3] = {0, 0, 0};
+    long first_f = -1;
+    int first_p = -1;
+    for (size_t k = 0; k < st.size(); k++) {
+        const h2y_compare_stats &s = st[k];
+        printf("frame %zu psnr", k);
+        for (int p = 0; p < 3; p++) printf(" %s %s", name[p], psnr_str(maxv, s.samples[p], s.sse[p]).c_str());
+        printf(" max_abs %u %u %u over %llu %llu %llu\n", s.max_abs[0], s.max_abs[1], s.max_abs[2], (unsigned long long)s.over[0],
+               (unsigned long long)s.over[1], (unsigned long long)s.over[2]);
+        for (int p = 0; p < 3; p++) {
+            n[p] += s.samples[p], sse[p] += s.sse[p], over[p] += s.over[p];
+            mx[p] = std::max(mx[p], s.max_abs[p]);
+            mean[p] += s.sse[p] ? 10.0 * log10((double)maxv * maxv * s.samples[p] / s.sse[p]) : 99.99;
+            if (first_f < 0 && s.over[p]) first_f = (long)k, first_p = p;
+        }
+    }
+    printf("summary frames %zu mean_psnr", st.size());
+    for (int p = 0; p < 3; p++) printf(" %s %.4f", name[p], st.empty() ? 0.0 : mean[p] / (double)st.size());
+    printf(" global_psnr");
+    for (int p = 0; p < 3; p++) printf(" %s %s", name[p], psnr_str(maxv, n[p], sse[p]).c_str());
+    printf(" max_abs %u %u %u over %llu %llu %llu\n", mx[0], mx[1], mx[2], (unsigned long long)over[0], (unsigned long long)over[1],
+           (unsigned long long)over[2]);
+    if (first_f < 0) printf("first_over none\n");
+    else {
+        const h2y_compare_stats &s = st[(size_t)first_f];
+        const bool sub = yuv && a.out.chroma_format_idc == H2Y_CHROMA_420 && first_p > 0;
+        const uint64_t w = sub ? (uint64_t)(a.out.width >> 1) : (uint64_t)a.out.width, i = (uint64_t)s.first_over[first_p];
+        printf("first_over frame %ld plane %s x %llu y %llu a %u b %u\n", first_f, name[first_p], (unsigned long long)(i % w),
+               (unsigned long long)(i / w), s.first_a[first_p], s.first_b[first_p]);
+    }
+    return a.sigma_given && first_f >= 0 ? 3 : 0;
+}
+
 int main(int argc, char **argv)
 {
     cli_args a;
     cli_parse(a, argc, argv);
-    if (!a.dst || (!a.src && a.synthetic < 0)) {
+    if ((!a.dst && !a.ref) || (!a.src && a.synthetic < 0)) {
         if (!a.help) cli_help();
         return a.help ? 0 : 1;
     }
@@ -575,7 +738,11 @@ int main(int argc, char **argv)
     h2y_desc d;
     cli_make_desc(a, &d);
     size_t in_frame_bytes, out_frame_bytes;
-    if (a.inverse) {
+    if (a.compare_only) { /* two files of one layout */
+        const size_t n = (size_t)a.in.width * a.in.height;
+        const size_t nc = a.in.chroma_format_idc == H2Y_CHROMA_420 ? (size_t)(a.in.width / 2) * (a.in.height / 2) : n;
+        in_frame_bytes = out_frame_bytes = (n + 2 * nc) * 2;
+    } else if (a.inverse) {
         if (a.out.bit_depth > 16 || a.in.bit_depth > 16) { printf("ERROR: bit depths must be 8..16 on the inverse flow\n"); return 1; }
         if (a.out.bit_depth < a.in.bit_depth) { /* tiff.cpp:564: SR = dst - src depth, then `R << SR` */
             printf("ERROR: dst bit_depth(%d) < src bit_depth(%d): write_tiff() would shift by a negative count (undefined in the reference)\n", a.out.bit_depth, a.in.bit_depth);
@@ -637,6 +804,25 @@ int main(int argc, char **argv)
     printf("gpus: %d (devices", a.gpus);
     for (int dv : a.devices) printf(" %d", dv);
     printf(")\nframes: %ld\nframe_bytes: %zu\n", frames, out_frame_bytes);
+    /* R in the layout of what the run produces: a whole number of frames, at least as many as the run has */
+    const bool cmp_yuv = a.compare_only ? a.in_type == CLI_IN_YUV : a.out_type == CLI_OUT_YUV;
+    if (a.ref) {
+        if (!stat(a.ref, &st)) {
+            if (st.st_size % (off_t)out_frame_bytes) {
+                printf("WARNING: reference file (%s): %lld bytes is not a whole number of %zu-byte frames\n", a.ref, (long long)st.st_size,
+                       out_frame_bytes);
+                return 1;
+            }
+            if (st.st_size / (off_t)out_frame_bytes < frames) {
+                printf("WARNING: reference file (%s) holds %lld frames, the run produces %ld\n", a.ref,
+                       (long long)(st.st_size / (off_t)out_frame_bytes), frames);
+                return 1;
+            }
+        } else if (!a.dry_run) { printf("ERROR: unable to open file %s\n", a.ref); return 1; }
+        printf("compare: %s %dx%d chroma_format_idc %d bit_depth %d planes %s, %ld frames against %s, sigma %d, output %s\n",
+               cmp_yuv ? "yuv" : "rgb", a.out.width, a.out.height, cmp_yuv ? a.out.chroma_format_idc : H2Y_CHROMA_444, a.out.bit_depth,
+               cmp_yuv ? "Y,Cb,Cr" : "G,B,R", frames, a.ref, a.sigma, a.compare_only ? "none (compare only)" : a.dst ? "kept" : "none (not written)");
+    }
     tiff_wrap tw;
     if (a.out_type == CLI_OUT_TIFF) {
         if (frames > 1 && cli_frame_pattern(a.dst) != 1) {
@@ -655,7 +841,7 @@ int main(int argc, char **argv)
     /* tiff.cpp:440 opens ios::ate | ios::app: what is in the file stays, frames go behind it (.tiff: one file per frame, below) */
     int fd = -1;
     off_t base = 0;
-    if (a.out_type != CLI_OUT_TIFF) {
+    if (a.dst && a.out_type != CLI_OUT_TIFF) {
         fd = open(a.dst, O_WRONLY | O_CREAT, 0644);
         if (fd < 0) { printf("ERROR: unable to open %s\n", a.dst); return 1; }
         base = lseek(fd, 0, SEEK_END);
@@ -670,7 +856,12 @@ int main(int argc, char **argv)
         blocks[r].count = frames / a.gpus + (r < frames % a.gpus ? 1 : 0);
         at += blocks[r].count;
     }
-    auto work = [&](block *b) { a.inverse ? run_block_inverse(a, tw, fd, base, b) : run_block(a, d, dpx, di, tiff, ti, exr, xi, fd, base, b); };
+    std::vector<h2y_compare_stats> stats(a.ref ? (size_t)frames : 0);
+    auto work = [&](block *b) {
+        if (a.compare_only) run_block_compare(a, (size_t)a.in.width * a.in.height * 2, in_frame_bytes, &stats, b);
+        else if (a.inverse) run_block_inverse(a, tw, fd, base, &stats, b);
+        else run_block(a, d, dpx, di, tiff, ti, exr, xi, fd, base, &stats, b);
+    };
     if (a.gpus == 1) work(&blocks[0]);
     else {
         std::vector<std::thread> th;
@@ -684,5 +875,6 @@ int main(int argc, char **argv)
             printf("ERROR (device %d, frames %ld..%ld): %s\n", blocks[r].device, blocks[r].first, blocks[r].first + blocks[r].count - 1, blocks[r].err.c_str());
             rc = 1;
         }
+    if (!rc && a.ref) rc = compare_report(a, cmp_yuv, a.out.bit_depth, stats);
     return rc;
 }

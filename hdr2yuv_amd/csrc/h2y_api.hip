@@ -198,6 +198,14 @@ struct h2y_ctx {
     size_t d_exr_cap = 0, h_exr_cap = 0; /* bytes */
     rgb_frame *d_rgb_frames = nullptr, *h_rgb_frames = nullptr;
     size_t d_rgb_cap = 0, h_rgb_cap = 0; /* bytes */
+    /* h2y_compare_batch's frame table likewise (an armed ring keeps one entry per slot), k_compare's partials, and the batch's
+     * device stats */
+    cmp_frame *d_cmp_frames = nullptr, *h_cmp_frames = nullptr;
+    size_t d_cmp_cap = 0, h_cmp_cap = 0; /* bytes */
+    cmp_partial *d_cmp_part = nullptr;
+    size_t cmp_part_cap = 0;
+    h2y_compare_stats *d_cmp_stats = nullptr;
+    size_t cmp_stats_cap = 0;
 
     /* staging for the host-buffer entry */
     void *d_in = nullptr;
@@ -216,6 +224,10 @@ struct h2y_ctx {
         uint16_t *d_out = nullptr;
         hipEvent_t ev_h2d = nullptr, ev_conv = nullptr, ev_done = nullptr;
         int state = 0; /* 0 free, 1 handed out for filling, 2 submitted, 3 output lent to the caller */
+        /* an armed ring (h2y_stream_compare): the reference frame (pinned, and its device twin followed by the frame's stats) */
+        char *h_ref = nullptr, *d_ref = nullptr;
+        h2y_compare_stats *h_stats = nullptr;
+        bool ref_lent = false;
     };
     std::vector<stream_slot> ss;
     hipStream_t s_h2d = nullptr, s_d2h = nullptr;
@@ -246,6 +258,12 @@ struct h2y_ctx {
     bool s_rgb = false;
     size_t s_rgb_off = 0;
     size_t s_in_off[3] = {0, 0, 0}, s_in_bytes = 0, s_out_stride = 0;
+    /* an armed ring (h2y_stream_compare) or a compare-only ring (h2y_compare_stream_open): k_compare's geometry (A the slot's
+     * device output, or its input on a compare-only ring; B its reference), the reference's bytes, whether the frame goes down */
+    bool s_started = false; /* an input was handed out: too late to arm */
+    bool s_cmp = false, s_cmp_keep = true, s_cmp_only = false;
+    cmp_geom s_cmp_geom{};
+    size_t s_ref_bytes = 0, s_ref_stats_off = 0; /* the pinned reference's bytes; where the stats lie in its device twin */
     int slot_base = 0; /* run_frames(): first entry of d_frames/h_frames to use (one per stream slot) */
     float last_ms = 0.f;
     const char *last_name = "";
@@ -1431,6 +1449,10 @@ void h2y_ctx_destroy(h2y_ctx *ctx)
     (void)hipHostFree(ctx->h_exr_frames);
     (void)hipFree(ctx->d_rgb_frames);
     (void)hipHostFree(ctx->h_rgb_frames);
+    (void)hipFree(ctx->d_cmp_frames);
+    (void)hipHostFree(ctx->h_cmp_frames);
+    (void)hipFree(ctx->d_cmp_part);
+    (void)hipFree(ctx->d_cmp_stats);
     (void)hipFree(ctx->d_in);
     (void)hipFree(ctx->d_out);
     if (ctx->fir_stream) {
@@ -2067,6 +2089,9 @@ static void stream_free(h2y_ctx *ctx)
         if (s.ev_h2d) (void)hipEventDestroy(s.ev_h2d);
         if (s.ev_conv) (void)hipEventDestroy(s.ev_conv);
         if (s.ev_done) (void)hipEventDestroy(s.ev_done);
+        if (s.h_ref) (void)hipHostFree(s.h_ref);
+        if (s.d_ref) (void)hipFree(s.d_ref);
+        if (s.h_stats) (void)hipHostFree(s.h_stats);
     }
     ctx->ss.clear();
     if (ctx->s_h2d) (void)hipStreamDestroy(ctx->s_h2d);
@@ -2078,6 +2103,8 @@ static void stream_free(h2y_ctx *ctx)
     ctx->s_tiff = false;
     ctx->s_exr = false;
     ctx->s_rgb = false;
+    ctx->s_started = ctx->s_cmp = ctx->s_cmp_only = false;
+    ctx->s_cmp_keep = true;
     ctx->s_head = ctx->s_tail = 0;
     ctx->s_lent = -1;
 }
@@ -3011,6 +3038,254 @@ int h2y_exr_stream_open(h2y_ctx *ctx, const h2y_desc *d, const h2y_exr_info *inf
     return H2Y_OK;
 }
 
+/* ---- comparison with a reference (--ref_filename, hdr2yuv.cpp:91-100, :827-833) ---------------------------------------- */
+
+/* k_compare's geometry: planes of n[p] samples (4:2:0: Y, then two chroma planes of (width >> 1) x (height >> 1)) starting at
+ * a_off / b_off samples from the two frames' bases */
+static cmp_geom cmp_geom_of(int width, int height, int chroma, int sigma, const uint32_t a_off[3], const uint32_t b_off[3])
+{
+    cmp_geom g{};
+    const bool sub = chroma == H2Y_CHROMA_420;
+    for (int p = 0; p < 3; p++) {
+        const uint32_t w = p && sub ? (uint32_t)(width >> 1) : (uint32_t)width, h = p && sub ? (uint32_t)(height >> 1) : (uint32_t)height;
+        g.n[p] = w * h;
+        g.width[p] = w;
+        g.a_off[p] = a_off[p];
+        g.b_off[p] = b_off[p];
+        const bool vec = (a_off[p] & 7u) == (b_off[p] & 7u);
+        g.shift[p] = vec ? a_off[p] & 7u : 0u;
+        g.vec |= vec ? 1u << p : 0u;
+        g.chunks[p] = h2y_compare_chunks(g.n[p], g.shift[p]);
+    }
+    g.sigma = (uint32_t)sigma;
+    return g;
+}
+
+/* the offsets of three planes one after the other */
+static void cmp_contiguous(int width, int height, int chroma, uint32_t off[3])
+{
+    const uint32_t n = (uint32_t)width * (uint32_t)height, nc = chroma == H2Y_CHROMA_420 ? (uint32_t)(width >> 1) * (uint32_t)(height >> 1) : n;
+    off[0] = 0, off[1] = n, off[2] = n + nc;
+}
+
+static int cmp_check(h2y_ctx *ctx, int width, int height, int chroma, int sigma)
+{
+    if (width < 1 || height < 1 || (uint64_t)width * (uint64_t)height >= (1ull << 28)) return fail(ctx, H2Y_EINVAL, "bad picture size");
+    if (chroma != H2Y_CHROMA_420 && chroma != H2Y_CHROMA_444) return fail(ctx, H2Y_EINVAL, "chroma_format_idc must be 1 or 3");
+    if (sigma < 0) return fail(ctx, H2Y_EINVAL, "sigma must be >= 0");
+    return H2Y_OK;
+}
+
+/* k_compare's partials for n_frames frames of g */
+static int cmp_partials(h2y_ctx *ctx, const cmp_geom &g, int n_frames)
+{
+    return ensure(ctx, ctx->d_cmp_part, ctx->cmp_part_cap,
+                  std::max<size_t>(1, (size_t)n_frames * (g.chunks[0] + g.chunks[1] + g.chunks[2])) * sizeof(cmp_partial));
+}
+
+static int cmp_grid(const h2y_ctx *ctx, const cmp_geom &g, int n_frames)
+{
+    return unit_grid(ctx, (uint64_t)n_frames * (g.chunks[0] + g.chunks[1] + g.chunks[2]));
+}
+
+int h2y_compare_batch(h2y_ctx *ctx, int width, int height, int chroma_format_idc, int sigma, int n_frames, const uint16_t *const *d_a,
+                      const uint16_t *const *d_b, h2y_compare_stats *out)
+{
+    static_assert(H2Y_COMPARE_FRAMES_PER_LAUNCH == H2Y_TIFF_FRAMES_PER_LAUNCH, "timed_launches deals launches of this many frames");
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
+    int rc = cmp_check(ctx, width, height, chroma_format_idc, sigma);
+    if (rc) return rc;
+    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
+    if (!d_a || !d_b || !out) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
+    for (int f = 0; f < n_frames; f++) {
+        if (!d_a[f] || !d_b[f]) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is null", f);
+        if (((uintptr_t)d_a[f] | (uintptr_t)d_b[f]) & 15u) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is not 16-byte aligned", f);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    uint32_t off[3];
+    cmp_contiguous(width, height, chroma_format_idc, off);
+    const cmp_geom g = cmp_geom_of(width, height, chroma_format_idc, sigma, off, off);
+    const int per_launch = std::min(n_frames, H2Y_COMPARE_FRAMES_PER_LAUNCH);
+    rc = frame_table(ctx, ctx->d_cmp_frames, ctx->d_cmp_cap, ctx->h_cmp_frames, ctx->h_cmp_cap, n_frames);
+    if (!rc) rc = cmp_partials(ctx, g, per_launch);
+    if (!rc) rc = ensure(ctx, ctx->d_cmp_stats, ctx->cmp_stats_cap, (size_t)n_frames * sizeof(h2y_compare_stats));
+    if (rc) return rc;
+    for (int f = 0; f < n_frames; f++) ctx->h_cmp_frames[f] = cmp_frame{d_a[f], d_b[f]};
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_cmp_frames, ctx->h_cmp_frames, (size_t)n_frames * sizeof(cmp_frame), hipMemcpyHostToDevice, ctx->stream));
+    rc = timed_launches(ctx, n_frames, "k_compare", [&](int f0, int nf) {
+        return h2y_launch_compare(cmp_grid(ctx, g, nf), ctx->stream, g, ctx->d_cmp_frames + f0, nf, ctx->d_cmp_part, ctx->d_cmp_stats + f0);
+    });
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpy(out, ctx->d_cmp_stats, (size_t)n_frames * sizeof(h2y_compare_stats), hipMemcpyDeviceToHost));
+    ctx->last_variant = std::string("k_compare<") + (chroma_format_idc == H2Y_CHROMA_420 ? "420" : "444") + ">";
+    return H2Y_OK;
+}
+
+/* Arm the open ring for frames of width x height and `chroma` whose A planes start at a_off samples from the slot's A base:
+ * per slot a pinned reference (the planes one after the other), its device twin laid out as A (so both sides share each
+ * plane's alignment and k_compare keeps its 16-byte loads) with the frame's stats behind it (256-byte aligned), pinned stats,
+ * and the slot's k_compare table entry (A: the slot's device output -- its input on a compare-only ring --, B: the device
+ * reference), uploaded here once */
+static int cmp_arm(h2y_ctx *ctx, int width, int height, int chroma, const uint32_t a_off[3], int sigma, int keep_output)
+{
+    int rc = cmp_check(ctx, width, height, chroma, sigma);
+    if (rc) return rc;
+    const cmp_geom g = cmp_geom_of(width, height, chroma, sigma, a_off, a_off);
+    const int depth = (int)ctx->ss.size();
+    const size_t ref_bytes = ((size_t)g.n[0] + g.n[1] + g.n[2]) * sizeof(uint16_t);
+    const size_t dev_al = (((size_t)a_off[2] + g.n[2]) * sizeof(uint16_t) + 255) & ~(size_t)255;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = ensure(ctx, ctx->d_cmp_frames, ctx->d_cmp_cap, (size_t)depth * sizeof(cmp_frame));
+    if (!rc) rc = cmp_partials(ctx, g, 1);
+    if (rc) return rc;
+    std::vector<cmp_frame> tab(depth);
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < depth && e == hipSuccess; k++) {
+        h2y_ctx::stream_slot &s = ctx->ss[k];
+        e = hipHostMalloc((void **)&s.h_ref, ref_bytes, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_stats, sizeof(h2y_compare_stats), hipHostMallocDefault);
+        if (e == hipSuccess) e = hipMalloc((void **)&s.d_ref, dev_al + sizeof(h2y_compare_stats));
+        tab[k].a = reinterpret_cast<const uint16_t *>(ctx->s_cmp_only ? (char *)s.d_in : (char *)s.d_out);
+        tab[k].b = reinterpret_cast<const uint16_t *>(s.d_ref);
+    }
+    if (e == hipSuccess) e = hipMemcpy(ctx->d_cmp_frames, tab.data(), tab.size() * sizeof(cmp_frame), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { /* the ring stays open, unarmed */
+        for (auto &s : ctx->ss) {
+            if (s.h_ref) (void)hipHostFree(s.h_ref);
+            if (s.h_stats) (void)hipHostFree(s.h_stats);
+            if (s.d_ref) (void)hipFree(s.d_ref);
+            s.h_ref = s.d_ref = nullptr;
+            s.h_stats = nullptr;
+        }
+        return fail(ctx, H2Y_ENOMEM, "compare buffers: %s", hipGetErrorString(e));
+    }
+    ctx->s_cmp_geom = g;
+    ctx->s_ref_bytes = ref_bytes;
+    ctx->s_ref_stats_off = dev_al;
+    ctx->s_cmp = true;
+    ctx->s_cmp_keep = keep_output != 0;
+    return H2Y_OK;
+}
+
+int h2y_stream_compare(h2y_ctx *ctx, int sigma, int keep_output)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    if (ctx->s_cmp) return fail(ctx, H2Y_EINVAL, "the ring is armed already");
+    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    if (keep_output != 0 && keep_output != 1) return fail(ctx, H2Y_EINVAL, "keep_output must be 0 or 1");
+    uint32_t a_off[3];
+    if (ctx->s_inverse) { /* the G, B, R planes the inverse kernel writes, s_out_stride bytes apart */
+        for (int c = 0; c < 3; c++) a_off[c] = (uint32_t)(c * ctx->s_out_stride / sizeof(uint16_t));
+        return cmp_arm(ctx, ctx->s_inv.width, ctx->s_inv.height, H2Y_CHROMA_444, a_off, sigma, keep_output);
+    }
+    const h2y_desc &d = ctx->s_desc; /* the .yuv frame of a forward ring */
+    cmp_contiguous(d.width, d.height, d.dst_chroma_format_idc, a_off);
+    return cmp_arm(ctx, d.width, d.height, d.dst_chroma_format_idc, a_off, sigma, keep_output);
+}
+
+int h2y_stream_reference(h2y_ctx *ctx, void **ref)
+{
+    if (!ctx || !ref) return fail(ctx, H2Y_EINVAL, "null argument");
+    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    if (!ctx->s_cmp) return fail(ctx, H2Y_EINVAL, "the ring is not armed: h2y_stream_compare first");
+    h2y_ctx::stream_slot &s = ctx->ss[ctx->s_tail];
+    if (s.state != 0 && s.state != 1) return fail(ctx, H2Y_EINVAL, "all %d slots are in flight: take an output first", (int)ctx->ss.size());
+    s.ref_lent = true;
+    *ref = s.h_ref;
+    return H2Y_OK;
+}
+
+int h2y_stream_compare_result(h2y_ctx *ctx, h2y_compare_stats *out)
+{
+    if (!ctx || !out) return fail(ctx, H2Y_EINVAL, "null argument");
+    if (!ctx->streaming || !ctx->s_cmp) return fail(ctx, H2Y_EINVAL, "no armed stream open");
+    if (ctx->s_lent < 0) return fail(ctx, H2Y_EINVAL, "no output taken yet: h2y_stream_output first");
+    *out = *ctx->ss[ctx->s_lent].h_stats;
+    return H2Y_OK;
+}
+
+/* A ring that only compares: the slot's input is A's three planes one after the other (one H2D copy), the device output unused */
+int h2y_compare_stream_open(h2y_ctx *ctx, int width, int height, int chroma_format_idc, int sigma, int depth)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is already open");
+    int rc = cmp_check(ctx, width, height, chroma_format_idc, sigma);
+    if (rc) return rc;
+    if (depth < 2 || depth > 16) return fail(ctx, H2Y_EINVAL, "depth must be 2..16");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    uint32_t off[3];
+    cmp_contiguous(width, height, chroma_format_idc, off);
+    for (int c = 0; c < 3; c++) ctx->s_in_off[c] = off[c] * sizeof(uint16_t);
+    ctx->s_in_bytes = ((size_t)off[2] + (off[2] - off[1])) * sizeof(uint16_t); /* the last plane is as long as the second */
+    rc = stream_alloc(ctx, depth, ctx->s_in_bytes, ctx->s_in_bytes, 16, 16);
+    if (rc) return rc;
+    ctx->s_cmp_only = true;
+    rc = cmp_arm(ctx, width, height, chroma_format_idc, off, sigma, 0);
+    if (rc) {
+        stream_free(ctx);
+        return rc;
+    }
+    return H2Y_OK;
+}
+
+/* an armed slot's reference goes up on the upload stream (before the slot's ev_h2d is recorded) */
+static int cmp_upload(h2y_ctx *ctx, h2y_ctx::stream_slot &s)
+{
+    if (!s.ref_lent) return fail(ctx, H2Y_EINVAL, "the ring is armed: h2y_stream_reference before each submit");
+    const cmp_geom &g = ctx->s_cmp_geom;
+    if (g.b_off[1] == g.n[0] && g.b_off[2] == g.n[0] + g.n[1]) /* the device twin is contiguous too: one copy */
+        HIP_TRY(ctx, hipMemcpyAsync(s.d_ref, s.h_ref, ctx->s_ref_bytes, hipMemcpyHostToDevice, ctx->s_h2d));
+    else /* padded apart as the inverse ring's output planes */
+        for (size_t c = 0, h_off = 0; c < 3; h_off += g.n[c] * sizeof(uint16_t), c++)
+            HIP_TRY(ctx, hipMemcpyAsync(s.d_ref + g.b_off[c] * sizeof(uint16_t), s.h_ref + h_off, g.n[c] * sizeof(uint16_t),
+                                        hipMemcpyHostToDevice, ctx->s_h2d));
+    s.ref_lent = false;
+    return H2Y_OK;
+}
+
+/* k_compare on the context's stream after the slot's conversion; the stats land behind the slot's device reference */
+static h2y_compare_stats *cmp_dev_stats(const h2y_ctx *ctx, const h2y_ctx::stream_slot &s)
+{
+    return reinterpret_cast<h2y_compare_stats *>(s.d_ref + ctx->s_ref_stats_off);
+}
+
+static int cmp_run(h2y_ctx *ctx, int slot)
+{
+    const cmp_geom &g = ctx->s_cmp_geom;
+    HIP_TRY(ctx, h2y_launch_compare(cmp_grid(ctx, g, 1), ctx->stream, g, ctx->d_cmp_frames + slot, 1, ctx->d_cmp_part, cmp_dev_stats(ctx, ctx->ss[slot])));
+    return H2Y_OK;
+}
+
+/* the stats go down on the download stream, after the frame (when it goes down at all) */
+static int cmp_download(h2y_ctx *ctx, h2y_ctx::stream_slot &s)
+{
+    HIP_TRY(ctx, hipMemcpyAsync(s.h_stats, cmp_dev_stats(ctx, s), sizeof(h2y_compare_stats), hipMemcpyDeviceToHost, ctx->s_d2h));
+    return H2Y_OK;
+}
+
+/* one frame of a compare-only ring: H2D of A and B, k_compare, D2H of the stats */
+static int compare_stream_submit(h2y_ctx *ctx, int slot)
+{
+    h2y_ctx::stream_slot &s = ctx->ss[slot];
+    HIP_TRY(ctx, hipMemcpyAsync(s.d_in, s.h_in, ctx->s_in_bytes, hipMemcpyHostToDevice, ctx->s_h2d));
+    int rc = cmp_upload(ctx, s);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipEventRecord(s.ev_h2d, ctx->s_h2d));
+    HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s.ev_h2d, 0));
+    rc = cmp_run(ctx, slot);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipEventRecord(s.ev_conv, ctx->stream));
+    HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_d2h, s.ev_conv, 0));
+    rc = cmp_download(ctx, s);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipEventRecord(s.ev_done, ctx->s_d2h));
+    s.state = 2;
+    ctx->s_tail = (slot + 1) % (int)ctx->ss.size();
+    return H2Y_OK;
+}
+
 /* one frame of an inverse stream: H2D of its planes, k_inverse420 / k_inverse on the context's stream, D2H of G, B, R */
 static int inverse_stream_submit(h2y_ctx *ctx, int slot)
 {
@@ -3018,6 +3293,8 @@ static int inverse_stream_submit(h2y_ctx *ctx, int slot)
     const inv_params &p = ctx->s_inv;
     const size_t pb = (size_t)p.width * p.height * sizeof(uint16_t), so = ctx->s_out_stride;
     HIP_TRY(ctx, hipMemcpyAsync(s.d_in, s.h_in, ctx->s_in_bytes, hipMemcpyHostToDevice, ctx->s_h2d));
+    int rc = ctx->s_cmp ? cmp_upload(ctx, s) : H2Y_OK;
+    if (rc) return rc;
     HIP_TRY(ctx, hipEventRecord(s.ev_h2d, ctx->s_h2d));
     HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s.ev_h2d, 0));
     /* every plane starts on a 16-byte boundary here: the single-frame kernels' wide accesses are safe */
@@ -3038,19 +3315,29 @@ static int inverse_stream_submit(h2y_ctx *ctx, int slot)
         if (blocks < 1) blocks = 1;
         HIP_TRY(ctx, h2y_launch_inverse((int)blocks, ctx->stream, a.inv));
     }
-    if (ctx->s_rgb) { /* write_tiff's interleave into the slot's device output behind the planes */
+    const bool keep = !ctx->s_cmp || ctx->s_cmp_keep;
+    if (ctx->s_rgb && keep) { /* write_tiff's interleave into the slot's device output behind the planes */
         const uint32_t npix = (uint32_t)p.width * (uint32_t)p.height;
         HIP_TRY(ctx, h2y_launch_rgb_interleave(unit_grid(ctx, h2y_rgb_chunks(npix)), ctx->stream, npix, ctx->d_rgb_frames + slot, 1));
     }
+    if (ctx->s_cmp) { /* on the G, B, R planes (before the interleave) */
+        rc = cmp_run(ctx, slot);
+        if (rc) return rc;
+    }
     HIP_TRY(ctx, hipEventRecord(s.ev_conv, ctx->stream));
     HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_d2h, s.ev_conv, 0));
-    if (ctx->s_rgb)
+    if (!keep) {
+    } else if (ctx->s_rgb)
         HIP_TRY(ctx, hipMemcpyAsync(s.h_out, reinterpret_cast<char *>(s.d_out) + ctx->s_rgb_off, 3 * pb, hipMemcpyDeviceToHost, ctx->s_d2h));
     else if (so == pb) HIP_TRY(ctx, hipMemcpyAsync(s.h_out, s.d_out, 3 * pb, hipMemcpyDeviceToHost, ctx->s_d2h));
     else
         for (int c = 0; c < 3; c++)
             HIP_TRY(ctx, hipMemcpyAsync(reinterpret_cast<char *>(s.h_out) + c * pb, reinterpret_cast<char *>(s.d_out) + c * so, pb,
                                         hipMemcpyDeviceToHost, ctx->s_d2h));
+    if (ctx->s_cmp) {
+        rc = cmp_download(ctx, s);
+        if (rc) return rc;
+    }
     HIP_TRY(ctx, hipEventRecord(s.ev_done, ctx->s_d2h));
     s.state = 2;
     ctx->s_tail = (slot + 1) % (int)ctx->ss.size();
@@ -3065,6 +3352,7 @@ int h2y_stream_input(h2y_ctx *ctx, void *planes[3])
     if (s.state == 1) { /* asked twice without a submit: same buffers again */
     } else if (s.state != 0) return fail(ctx, H2Y_EINVAL, "all %d slots are in flight: take an output first", (int)ctx->ss.size());
     s.state = 1;
+    ctx->s_started = true;
     if (ctx->s_dpx || ctx->s_tiff || ctx->s_exr) { /* the payload, as the file holds it (TIFF: the decoded rows, packed; EXR: unpacked) */
         planes[0] = s.h_in;
         planes[1] = planes[2] = nullptr;
@@ -3081,8 +3369,10 @@ int h2y_stream_submit(h2y_ctx *ctx)
     const int slot = ctx->s_tail;
     h2y_ctx::stream_slot &s = ctx->ss[slot];
     if (s.state != 1) return fail(ctx, H2Y_EINVAL, "nothing to submit: call h2y_stream_input first");
+    if (ctx->s_cmp && !s.ref_lent) return fail(ctx, H2Y_EINVAL, "the ring is armed: h2y_stream_reference before each submit");
     const h2y_desc *d = &ctx->s_desc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (ctx->s_cmp_only) return compare_stream_submit(ctx, slot);
     if (ctx->s_inverse) return inverse_stream_submit(ctx, slot);
     const size_t pb = h2y_plane_bytes(d), ob = h2y_frame_bytes(d);
     frame_io io;
@@ -3095,6 +3385,10 @@ int h2y_stream_submit(h2y_ctx *ctx)
         HIP_TRY(ctx, hipMemcpyAsync(s.d_in + ctx->s_exr_off, s.h_in, ctx->s_exr_info.payload_bytes, hipMemcpyHostToDevice, ctx->s_h2d));
     else /* the slot's three planes lie one after the other (each padded to 256 bytes): one copy command, not three */
         HIP_TRY(ctx, hipMemcpyAsync(s.d_in, s.h_in, 2 * ctx->s_plane_al + pb, hipMemcpyHostToDevice, ctx->s_h2d));
+    if (ctx->s_cmp) {
+        const int rc = cmp_upload(ctx, s);
+        if (rc) return rc;
+    }
     io.out = s.d_out;
     io.tmp_cb = io.tmp_cr = nullptr;
     HIP_TRY(ctx, hipEventRecord(s.ev_h2d, ctx->s_h2d));
@@ -3136,9 +3430,17 @@ int h2y_stream_submit(h2y_ctx *ctx)
     rc = run_frames(ctx, d, &io, 1, ctx->b->d_assumed, nullptr, false, slot, false);
     ctx->slot_base = 0;
     if (rc) return rc;
+    if (ctx->s_cmp) {
+        rc = cmp_run(ctx, slot);
+        if (rc) return rc;
+    }
     HIP_TRY(ctx, hipEventRecord(s.ev_conv, ctx->stream));
     HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_d2h, s.ev_conv, 0));
-    HIP_TRY(ctx, hipMemcpyAsync(s.h_out, s.d_out, ob, hipMemcpyDeviceToHost, ctx->s_d2h));
+    if (!ctx->s_cmp || ctx->s_cmp_keep) HIP_TRY(ctx, hipMemcpyAsync(s.h_out, s.d_out, ob, hipMemcpyDeviceToHost, ctx->s_d2h));
+    if (ctx->s_cmp) {
+        rc = cmp_download(ctx, s);
+        if (rc) return rc;
+    }
     HIP_TRY(ctx, hipEventRecord(s.ev_done, ctx->s_d2h));
     s.state = 2;
     ctx->s_tail = (slot + 1) % (int)ctx->ss.size();
@@ -3157,7 +3459,7 @@ int h2y_stream_output(h2y_ctx *ctx, const uint16_t **yuv)
     if (s.state != 2) return fail(ctx, H2Y_EINVAL, "no submitted frame is waiting");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipEventSynchronize(s.ev_done));
-    *yuv = s.h_out;
+    *yuv = ctx->s_cmp && !ctx->s_cmp_keep ? nullptr : s.h_out;
     s.state = 3;
     ctx->s_lent = ctx->s_head;
     ctx->s_head = (ctx->s_head + 1) % (int)ctx->ss.size();

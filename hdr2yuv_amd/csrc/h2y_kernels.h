@@ -276,4 +276,27 @@ struct exr_frame {
 };
 hipError_t h2y_launch_exr_decode(int grid, hipStream_t st, const exr_geom &g, const exr_frame *frames, int n_frames);
 
+/* k_compare and k_compare_sum (h2y_compare.hip): two frames of u16 planes reduced per plane to exact integer stats */
+struct cmp_geom {
+    uint32_t n[3];              /* samples per plane */
+    uint32_t width[3];          /* plane width (first_over's x, y are the host's) */
+    uint32_t a_off[3], b_off[3]; /* plane start in samples from the frame base, per side */
+    uint32_t shift[3];          /* a_off & 7 where both sides share it (16-byte groups), else 0 */
+    uint32_t vec;               /* bit p: plane p takes 16-byte loads */
+    uint32_t chunks[3];         /* k_compare's units per frame and plane */
+    uint32_t sigma;
+};
+struct cmp_frame { /* one pair; bases 16-byte aligned */
+    const uint16_t *a, *b;
+};
+struct cmp_partial { /* one k_compare unit (at most 16384 samples: its sad and over fit 32 bits) */
+    uint64_t sse;
+    uint32_t sad, max_abs, over, first; /* first: plane index of the unit's first over-sigma sample, 0xFFFFFFFF when none */
+};
+struct h2y_compare_stats;
+uint32_t h2y_compare_chunks(uint32_t n, uint32_t shift); /* k_compare's units for a plane of n samples */
+/* k_compare over (frame, plane, chunk) units into partials[frame x units per frame + unit], then k_compare_sum into stats[frame] */
+hipError_t h2y_launch_compare(int grid, hipStream_t st, const cmp_geom &g, const cmp_frame *frames, int n_frames, cmp_partial *partials,
+                              h2y_compare_stats *stats);
+
 #endif

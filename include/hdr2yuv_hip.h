@@ -485,8 +485,52 @@ int h2y_exr_decode_batch(h2y_ctx *ctx, const h2y_exr_info *info, int n_frames, c
  * h2y_exr_unpack), planes[1] = planes[2] = NULL; the rest and the exclusivity rules are those of the forward stream. */
 int h2y_exr_stream_open(h2y_ctx *ctx, const h2y_desc *d, const h2y_exr_info *info, int depth /* 2..16 slots */);
 
+/* ---- comparison with a reference (--ref_filename / --sigma_compare; hdr2yuv.cpp:91-100, :827-833 leaves it a TODO) ------
+ * Two frames A and B of u16 samples, three planes each, reduced per plane to exact integers: how many samples, the sum of
+ * squared and of absolute differences, the largest |a - b|, how many samples have |a - b| > sigma and where the first of them
+ * is.  Plane geometry: 4:2:0 (chroma_format_idc 1) Y width x height, Cb and Cr (width >> 1) x (height >> 1), the planes one
+ * after the other as h2y_frame_bytes lays them out; 4:4:4 (3, also the G | B | R planes of the inverse flow) three planes of
+ * width x height.  The reductions run on the device (k_compare, then k_compare_sum over its per-block partials: no atomics,
+ * so every figure is independent of the order of the work). */
+#define H2Y_COMPARE_FRAMES_PER_LAUNCH 64
+
+typedef struct h2y_compare_stats {
+    uint64_t samples[3];    /* per plane: samples compared */
+    uint64_t sse[3];        /* sum of (a - b)^2 */
+    uint64_t sad[3];        /* sum of |a - b| */
+    uint64_t over[3];       /* samples with |a - b| > sigma */
+    int64_t first_over[3];  /* plane index y x plane_width + x of the first such sample in raster order, -1 when none */
+    uint32_t max_abs[3];    /* largest |a - b| */
+    uint32_t first_a[3];    /* a and b at first_over (0 when none) */
+    uint32_t first_b[3];
+    uint32_t reserved;      /* 0 */
+} h2y_compare_stats;
+
+/* n_frames pairs of device frames, each frame's three planes contiguous from a 16-byte aligned base (H2Y_EINVAL otherwise):
+ * out[f] (host memory) receives the stats of d_a[f] against d_b[f].  chroma_format_idc 1 or 3, sigma >= 0.  Launches of up to
+ * H2Y_COMPARE_FRAMES_PER_LAUNCH frames (h2y_last_kernel_ms sums them); synchronous. */
+int h2y_compare_batch(h2y_ctx *ctx, int width, int height, int chroma_format_idc, int sigma, int n_frames,
+                      const uint16_t *const *d_a, const uint16_t *const *d_b, h2y_compare_stats *out);
+
+/* Arm an open ring (forward, DPX, TIFF, EXR, inverse, TIFF inverse) after its *_stream_open and before its first input: every
+ * submitted frame is then compared on the device with a reference frame the caller supplies.  The reference is laid out as the
+ * ring's output: a .yuv frame (h2y_frame_bytes) on the forward rings, the G | B | R planes (width x height each) on the inverse
+ * rings -- on the TIFF inverse ring the planes before the interleave.  keep_output 0: the frame itself stays on the device (no
+ * download; the TIFF inverse ring skips the interleave too) and h2y_stream_output returns *yuv = NULL. */
+int h2y_stream_compare(h2y_ctx *ctx, int sigma, int keep_output);
+/* The pinned slot that receives the reference of the frame about to be submitted (call it before each h2y_stream_submit of an
+ * armed ring); h2y_stream_submit uploads it on the upload stream and runs k_compare on the slot's device output after the
+ * conversion. */
+int h2y_stream_reference(h2y_ctx *ctx, void **ref);
+/* The stats of the frame that h2y_stream_output returned last. */
+int h2y_stream_compare_result(h2y_ctx *ctx, h2y_compare_stats *out);
+/* A compare-only ring: no conversion.  h2y_stream_input lends A's three planes (planes of the geometry above, one after the
+ * other), h2y_stream_reference B's frame in the same layout; h2y_stream_output returns *yuv = NULL and
+ * h2y_stream_compare_result the stats. */
+int h2y_compare_stream_open(h2y_ctx *ctx, int width, int height, int chroma_format_idc, int sigma, int depth /* 2..16 slots */);
+
 /* Timing of the last h2y_convert_batch*() (or h2y_inverse_*, h2y_dpx_decode_batch, h2y_tiff_decode_batch,
- * h2y_rgb_interleave_batch, h2y_exr_decode_batch) call measured with HIP events on
+ * h2y_rgb_interleave_batch, h2y_exr_decode_batch, h2y_compare_batch) call measured with HIP events on
  * the stream the kernels ran on: total ms over the main kernels and how many
  * launches that covered. */
 int h2y_last_kernel_ms(const h2y_ctx *ctx, float *ms, int *launches);
@@ -494,7 +538,7 @@ int h2y_last_kernel_ms(const h2y_ctx *ctx, float *ms, int *launches);
 /* Name of the kernel those launches ran ("k_fused", "k_fused_t1", "k_fused_lut16",
  * "k_fused_narrow"; of the inverse entries "k_inverse", "k_inverse420", "k_inverse_batch", "k_inverse420_batch"; of
  * h2y_dpx_decode_batch "k_dpx_decode"; of h2y_tiff_decode_batch "k_tiff_decode", of h2y_rgb_interleave_batch
- * "k_rgb_interleave"; of h2y_exr_decode_batch "k_exr_decode"): the name to
+ * "k_rgb_interleave"; of h2y_exr_decode_batch "k_exr_decode"; of h2y_compare_batch "k_compare"): the name to
  * look for in a rocprofv3 kernel trace. */
 const char *h2y_last_kernel_name(const h2y_ctx *ctx);
 /* The same with its template arguments and launch shape, e.g. "k_fused_t1<F32,420BOX,YCBCR,PQ_IDENT> groups=8 xcd=1";

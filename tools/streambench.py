@@ -35,6 +35,15 @@ Prints one line per figure, then one JSON line with all of them.
      and the algorithmic bytes over that time as a share of the 8 TB/s HBM peak: 6 B/pixel read and 6 written raw, 9 read
      (the first half of each chunk twice) and 6 written encoded;
   3. host unpack ms per frame (h2y_exr_unpack, the file already in memory) with that many threads.
+Prints one line per figure, then one JSON line with all of them.
+
+`streambench.py compare`: the comparison with a reference on 4K 4:2:0 10-bit frames:
+  1. the kernel time of h2y_compare_batch (k_compare and k_compare_sum) over 64 frame pairs (HIP events, median of reps), the
+     49.8 MB per frame it reads over that time, and their share of the 8 TB/s HBM peak;
+  2. frames/s from host memory of the forward ring (16-bit G,B,R planes in, BT.2020nc 10-bit 4:2:0 box out, depth 3) unarmed,
+     armed with keep_output 1 (the reference goes up, the frame comes down) and armed with keep_output 0 (only the stats come
+     down), on the same pictures;
+  3. frames/s of the compare-only ring (both frames go up, the stats come down).
 Prints one line per figure, then one JSON line with all of them."""
 import os
 import sys
@@ -450,6 +459,105 @@ def exr_main():
     print(json.dumps({"streambench_exr": res}), flush=True)
 
 
+def compare_main():
+    import json
+
+    import torch
+
+    w, hh, nb, reps = 3840, 2160, 64, 5
+    n, nc = w * hh, (w // 2) * (hh // 2)
+    total = n + 2 * nc
+    nf = int(os.environ.get("N", "60"))
+    depth = 3
+    rng = np.random.default_rng(17)
+    ctx = h.Context(0)
+    res = {"width": w, "height": hh, "frames_per_call": nb, "reps": reps, "ring_frames": nf, "ring_depth": depth, "hbm_peak_tbs": 8.0}
+
+    # 1. the kernels over 64 distinct frame pairs on the device
+    a = [torch.randint(0, 1024, (total,), dtype=torch.int16, device="cuda") for _ in range(nb)]
+    b = [x + torch.randint(-2, 3, (total,), dtype=torch.int16, device="cuda") for x in a]
+    torch.cuda.synchronize()
+    ks = []
+    for rep in range(reps + 1):  # rep 0 warms up
+        ctx.compare_batch(w, hh, h.CHROMA_420, 0, a, b)
+        if rep:
+            ks.append(ctx.last_kernel_ms()[0] / nb)
+    k_ms = float(np.median(ks))
+    nbytes = 2 * 2 * total
+    tbs = nbytes / (k_ms * 1e-3) / 1e12
+    res["k_compare"] = dict(kernel_us_per_frame=round(k_ms * 1e3, 2), bytes_per_frame=nbytes, kernel_tbs=round(tbs, 2),
+                            hbm_peak_fraction=round(tbs / 8.0, 3), variant=ctx.last_kernel_variant())
+    print(f"k_compare        {nb} frames per call: {k_ms*1e3:6.2f} us/frame  {nbytes/1e6:6.1f} MB/frame  {tbs:5.2f} TB/s = "
+          f"{tbs/8.0*100:4.1f} % of 8 TB/s", flush=True)
+    del a, b
+    torch.cuda.empty_cache()
+
+    def ring(open_fn, fill, ref=None, keep=1):
+        open_fn()
+        if ref is not None and open_fn is not open_cmp:
+            ctx.stream_compare(0, keep)
+        inflight = 0
+        t0 = time.perf_counter()
+        for _ in range(nf):
+            fill(ctx.stream_input())
+            if ref is not None:
+                ctx.stream_reference()[:] = ref
+            ctx.stream_submit()
+            inflight += 1
+            if inflight == depth - 1:
+                ctx.stream_output()
+                if ref is not None:
+                    ctx.stream_compare_result()
+                inflight -= 1
+        while inflight:
+            ctx.stream_output()
+            if ref is not None:
+                ctx.stream_compare_result()
+            inflight -= 1
+        dt = (time.perf_counter() - t0) / nf
+        ctx.stream_close()
+        return dt
+
+    # 2. the forward ring: 16-bit G,B,R -> BT.2020nc 10-bit 4:2:0 box, unarmed and armed
+    planes = [rng.integers(0, 65536, n, dtype=np.uint16) for _ in range(3)]
+    d = h.make_desc(w, hh, sample=h.SAMPLE_U16, src_depth=16, dst_depth=10, src_transfer=1, dst_transfer=1, src_primaries=1,
+                    dst_primaries=1, dst_matrix=h.MATRIX_BT2020NC, resampler=0)
+    yuv_ref = ctx.convert_frame(d, planes)
+
+    def fill_planes(slot):
+        for c in range(3):
+            slot[c][:] = planes[c]
+
+    def open_fwd():
+        ctx.stream_open(d, depth)
+
+    def open_cmp():
+        ctx.compare_stream_open(w, hh, h.CHROMA_420, 0, depth)
+
+    ring(open_fwd, fill_planes)  # warm-up
+    t_plain = ring(open_fwd, fill_planes)
+    t_keep = ring(open_fwd, fill_planes, yuv_ref, 1)
+    t_none = ring(open_fwd, fill_planes, yuv_ref, 0)
+    res["forward_ring"] = dict(unarmed_fps=round(1 / t_plain, 1), armed_keep1_fps=round(1 / t_keep, 1), armed_keep0_fps=round(1 / t_none, 1),
+                               unarmed_ms=round(t_plain * 1e3, 2), armed_keep1_ms=round(t_keep * 1e3, 2), armed_keep0_ms=round(t_none * 1e3, 2))
+    print(f"forward ring from host memory: unarmed {1/t_plain:6.1f} frames/s   armed keep_output 1 {1/t_keep:6.1f} frames/s   "
+          f"keep_output 0 {1/t_none:6.1f} frames/s", flush=True)
+
+    # 3. the compare-only ring
+    yuv_a = [yuv_ref[:n], yuv_ref[n:n + nc], yuv_ref[n + nc:]]
+
+    def fill_a(slot):
+        for c in range(3):
+            slot[c][:] = yuv_a[c]
+
+    ring(open_cmp, fill_a, yuv_ref)
+    t_cmp = ring(open_cmp, fill_a, yuv_ref)
+    res["compare_only_ring"] = dict(fps=round(1 / t_cmp, 1), ms=round(t_cmp * 1e3, 2))
+    print(f"compare-only ring from host memory: {1/t_cmp:6.1f} frames/s ({t_cmp*1e3:6.2f} ms/frame)", flush=True)
+    ctx.close()
+    print(json.dumps({"streambench_compare": res}), flush=True)
+
+
 if __name__ == "__main__":
     if sys.argv[1:] == ["inverse"]:
         inverse_main()
@@ -459,5 +567,7 @@ if __name__ == "__main__":
         tiff_main()
     elif sys.argv[1:] == ["exr"]:
         exr_main()
+    elif sys.argv[1:] == ["compare"]:
+        compare_main()
     else:
         main()
