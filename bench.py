@@ -1,16 +1,22 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the hdr2yuv convert hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 A *step* is one pass of the hot path (pic_stats -> matrix_convert/PQ -> convert
 -> write_yuv arithmetic) over one batch of --frames synthetic frames per GPU,
 inputs already resident in HBM, outputs left in HBM in .yuv layout.  Workload =
 BASELINE.json configs[1] ("C2"): 3840x2160 fp32 RGB -> PQ -> 12-bit BT.2020nc
 YCbCr 4:2:0 (video range), chroma by the 2x2 box (the north_star's fused kernel).
-Beside it, at N = 1, shorter passes over the FIR resampler (make.sh's example, the
-CLI's default) and over configs[0] / [2] / [3] (C1, C3, C4), each with its own
-roofline fraction and md5 self-check.
+
+A plain run does only what the headline needs: it sets up, warms up, times the K
+steps, checks frame 0 against its known answer, writes --dump-outputs and prints
+the line.  --full adds everything else: a device-to-device copy for context, at
+N = 1 shorter passes over the FIR resampler (make.sh's example, the CLI's default),
+configs[0] / [2] / [3] (C1, C3, C4), the other transfer pairs, the inverse flow
+and darker / letterboxed pictures, each with its own roofline fraction and md5
+self-check, and the CPU baseline, whose frames 40 of the GPU's output frames are
+compared with.
 
 N > 1: one process per GPU.  Started under `python -m torch.distributed.run` the
 ranks come from the environment; started as plain `python bench.py --gpus N` this
@@ -86,8 +92,10 @@ def parse(argv=None):
                     "the FIR path's row segments -- weigh half as much at 128: box +0.5 %% on the kernel and +1.2 %% on value, FIR +1.5 %% / +1.8 %%)")
     ap.add_argument("--workload", default="C2", choices=sorted(WORKLOADS))
     ap.add_argument("--resampler", default="box", choices=["box", "fir"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary measurements (other resampler, C1/C3/C4)")
+    ap.add_argument("--full", action="store_true", help="besides the headline, measure and check everything else: the device copy figure, "
+                    "the secondary passes and the CPU baseline (a plain run does none of them)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the comparison of frames with it")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the secondary measurements (other resampler, C1/C3/C4, ...)")
     ap.add_argument("--cpu-frames", type=int, default=0, help="frames for the CPU baseline sample (0 = auto ~15 s)")
     ap.add_argument("--lib", default=None, help="load this build of libhdr2yuv_hip.so instead of the in-tree one (recorded in the JSON)")
     ap.add_argument("--allow-experiment", action="store_true", help="with --lib: accept a -DH2Y_EXPERIMENT build (timing variants that may write wrong "
@@ -98,7 +106,7 @@ def parse(argv=None):
     ap.add_argument("--content", default="uniform", choices=["uniform", "bars", "squared", "pow3", "pow4", "pow6"],
                     help="synthetic picture content (fp32 workloads): uniform = the SURVEY 8c generator (the headline; md5-checked); bars = the same "
                          "with the top and bottom 12.8 %% of the rows exactly zero (a 2.39:1 picture letterboxed in 16:9); squared = every sample "
-                         "squared (darker).  Not md5-checked; implies --no-extra")
+                         "squared (darker).  Not md5-checked; no secondary passes even with --full")
     ap.add_argument("--placement", default="separate", choices=["arena", "separate"],
                     help="arena: the batch's input planes in one allocation back to back and its output frames in another (the .yuv's own "
                          "layout); separate (default): one allocation per plane / frame.  Where the planes lie decides how often the kernels' streams meet in "
@@ -571,20 +579,23 @@ def main() -> int:
                     p[bar * w + 1] = 1.0  # (the planted 1.0 of the generator sat in the first row: ceiling 1 again)
     torch.cuda.synchronize()
 
-    # a plain device-to-device copy of 1 GiB on this very box (30 times): context only, it swings by +-10 % between runs
+    # --full: a plain device-to-device copy of 1 GiB on this very box (30 times): context only, it swings by +-10 % between runs.
+    # A plain run takes and frees the same two buffers without copying: the main pass's output frames are then cut from the
+    # same two cached blocks either way, and where the frames lie moves a launch's time by several per cent
     copy_gbs = None
     try:
         src_t = torch.empty(1 << 28, dtype=torch.float32, device=dev)
         dst_t = torch.empty_like(src_t)
-        for _ in range(2):
-            dst_t.copy_(src_t)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(30):
-            dst_t.copy_(src_t)
-        e1.record()
-        torch.cuda.synchronize()
-        copy_gbs = 30 * 2 * src_t.numel() * 4 / (e0.elapsed_time(e1) / 1e3) / 1e9
+        if args.full:
+            for _ in range(2):
+                dst_t.copy_(src_t)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(30):
+                dst_t.copy_(src_t)
+            e1.record()
+            torch.cuda.synchronize()
+            copy_gbs = 30 * 2 * src_t.numel() * 4 / (e0.elapsed_time(e1) / 1e3) / 1e9
         del src_t, dst_t
     except Exception:
         copy_gbs = None
@@ -592,7 +603,8 @@ def main() -> int:
     # frames whose bytes are compared with the CPU reference's (N = 1): 0..7 (the single-thread baseline converts those anyway) and 32
     # more spread over the rest of the batch, the last one included (the frame-parallel baseline converts those): both frame groups,
     # every block's slice range, the first and the last launch split
-    do_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
+    do_cpu = rank == 0 and world == 1 and args.full and not args.no_cpu_baseline
+    extras = world == 1 and args.full and not args.no_extra
     check = sorted(set(range(min(8, F))) | {8 + (i * (F - 9)) // 31 for i in range(32) if F > 9}) if do_cpu and args.content == "uniform" else []
     main_r = measure(args.workload, args.resampler, frames_in, F, args.steps, args.warmup, check, dump_dir=args.dump_outputs)
     value = main_r["pixels"] / main_r["secs"] / 1e6
@@ -624,7 +636,7 @@ def main() -> int:
         "verified": main_r["verified"],
         "verified_frames": [],
         "verify": {"case": main_r["verify_case"], "md5": main_r["md5"],
-                   "what": "md5 of rank 0's output frame 0 after the timed loop vs tests/golden/known_md5.json; verified_frames: output frames whose md5 "
+                   "what": "md5 of rank 0's output frame 0 after the timed loop vs tests/golden/known_md5.json; verified_frames (--full): output frames whose md5 "
                            "equals the CPU reference's frame of the same index, converted in this run (cpu_baseline)"},
         "library": {"path": os.path.relpath(lib_path, ROOT) if lib_path.startswith(ROOT) else lib_path, "sha256": lib_sha,
                     "sources_sha256": sources_sha256()},
@@ -647,14 +659,15 @@ def main() -> int:
         except Exception:
             traffic = None
     out["roofline"] = roofline_of(main_r, traffic, traffic_source)
-    out["roofline"]["device_copy_gbs"] = None if copy_gbs is None else round(copy_gbs, 1)
+    if args.full:
+        out["roofline"]["device_copy_gbs"] = None if copy_gbs is None else round(copy_gbs, 1)
     out["frames_redone"] = main_r["redone"]
     if main_r["dump"] is not None:
         out["dump_outputs"] = main_r["dump"]
     failed = main_r["verified"] is False
 
-    # ---- secondary passes (N = 1): the other resampler and the other BASELINE configs -------
-    if world == 1 and not args.no_extra:
+    # ---- secondary passes (--full, N = 1): the other resampler and the other BASELINE configs -------
+    if extras:
         others = {}
         other_md5 = {}
         sec_steps, sec_warm = max(10, args.steps // 2), max(8, args.warmup)  # (the XCD weights settle within the first few launches)
@@ -809,7 +822,7 @@ def main() -> int:
                 out["verified"] = False
                 out["verify"]["mismatched_frames"] = bad
                 failed = True
-            for key, (res, gmd5, okw) in (other_md5 if world == 1 and not args.no_extra else {}).items():
+            for key, (res, gmd5, okw) in (other_md5 if extras else {}).items():
                 par, par_md5 = cpu_baseline_parallel(okw, res, sorted(gmd5))
                 good, bad = compare(gmd5, par_md5)
                 out["others"][key]["verified_frames"] = good

@@ -1095,6 +1095,27 @@ def test_bench_dump_outputs_are_the_frames_it_computed(tmp_path, oracle):
     assert np.array_equal(vals, want[idx.astype(np.int64)].astype(np.float32))
 
 
+def test_bench_plain_run_is_the_headline_alone():
+    """bench.py without --full: the headline line, frame 0 checked against its known answer, and nothing measured or
+    checked beside it -- no secondary passes, no CPU baseline, no device copy figure."""
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--frames", "2", "--steps", "2", "--warmup", "1"],
+                       capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert out["unit"] == "Mpixels/s" and out["higher_is_better"] is True and out["dtype"] == "f32+f64"
+    assert out["verified"] is True and out["verified_frames"] == []
+    assert "others" not in out and "cpu_baseline" not in out and "cpu_baseline_all_cores" not in out
+    assert "device_copy_gbs" not in out["roofline"]
+
+
 @pytest.mark.parametrize("w,hh", [(2, 2), (4, 2), (6, 10), (64, 32), (130, 18), (258, 70), (1920, 1080)])
 def test_upsample_444(ctx, oracle, w, hh):
     """h2y_upsample_444 (Subsample420to444, convert.cpp:1869-1986) vs the oracle, itself pinned to the

@@ -144,6 +144,16 @@ def test_bench_dump_plan_is_fixed_and_fits():
         bench.parse(["--steps", "0"])
 
 
+def test_bench_full_is_opt_in():
+    """Everything beside the headline (secondary passes, CPU baseline, device copy) runs only when --full is given."""
+    import importlib
+
+    bench = importlib.import_module("bench")
+    assert bench.parse([]).full is False
+    assert bench.parse(["--steps", "3", "--warmup", "1"]).full is False
+    assert bench.parse(["--full"]).full is True
+
+
 # ---- the command line: how unset attributes resolve (hdr2yuv.cpp:61-62, :265-318, :765-766; read_file) -------------
 
 def _cli_dry(args):

@@ -1,7 +1,7 @@
 #!/bin/bash
 # tools/collect_profiles.sh ROUND  (GPU box, from the repo root) -- the evidence bench.py's figures rest on, into
 # gpurun_out/profiles_ROUND/ (tools/publish_profiles.sh copies what is to be judged into profiles/):
-#   bench.json                      the plain bench line (unprofiled)
+#   bench.json                      the full bench line (--full, unprofiled)
 #   c2box/ c2fir/ c3/ c4/ c4fir/ c1/  rocprofv3 --kernel-trace --stats of the bench command for each workload, then the
 #                                   PMC passes (separate runs: counters are never combined with tracing)
 #   summary_*.txt                   tools/pmc_summary.py over each
@@ -12,7 +12,7 @@ R=${1:-r03}
 ROOT=$PWD
 OUT=$ROOT/gpurun_out/profiles_$R
 mkdir -p "$OUT"
-python3 bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+python3 bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 prof() { # name, bench args...
   local name=$1; shift
   tools/prof.sh "$OUT/$name" -- python3 "$ROOT/bench.py" --no-extra --no-cpu-baseline "$@" > /dev/null 2>&1

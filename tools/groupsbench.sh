@@ -1,9 +1,9 @@
 # tools/groupsbench.sh -- the full bench line with the frame groups chosen by frame size (default), eight and one, three rounds alternating
 o=gpurun_out/r2q; mkdir -p $o
 for r in 1 2 3; do
-  python bench.py --no-cpu-baseline > $o/auto_$r.json 2>/dev/null || echo FAILED auto
-  python bench.py --no-cpu-baseline --option groups=8 > $o/g8_$r.json 2>/dev/null || echo FAILED g8
-  python bench.py --no-cpu-baseline --option groups=1 > $o/g1_$r.json 2>/dev/null || echo FAILED g1
+  python bench.py --full --no-cpu-baseline > $o/auto_$r.json 2>/dev/null || echo FAILED auto
+  python bench.py --full --no-cpu-baseline --option groups=8 > $o/g8_$r.json 2>/dev/null || echo FAILED g8
+  python bench.py --full --no-cpu-baseline --option groups=1 > $o/g1_$r.json 2>/dev/null || echo FAILED g1
 done
 python - <<'PY'
 import glob, json, os
