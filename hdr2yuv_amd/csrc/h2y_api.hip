@@ -80,6 +80,28 @@ struct inv_params {
     int width, height, chroma, in_depth, in_full_range, matrix, out_depth, algorithm;
 };
 
+/* What a decode batch entry or a forward ring decodes: nothing (a ring's caller fills the planes), or one format's payload
+ * described by the info its parser returned.  Each format's launch and variant lie beside its parser. */
+struct decode_src {
+    enum kind_t { NONE, DPX, TIFF, EXR } kind = NONE;
+    bool has_info = true; /* false: the caller passed a null info, which check() refuses */
+    int clamp = 0;        /* TIFF: clamp_video_range */
+    h2y_dpx_info dpx{};
+    h2y_tiff_info tiff{};
+    h2y_exr_info exr{};
+    decode_src() = default;
+    explicit decode_src(const h2y_dpx_info *i) : kind(DPX), has_info(i != nullptr) { if (i) dpx = *i; }
+    decode_src(const h2y_tiff_info *i, int clamp_video_range) : kind(TIFF), has_info(i != nullptr), clamp(clamp_video_range) { if (i) tiff = *i; }
+    explicit decode_src(const h2y_exr_info *i) : kind(EXR), has_info(i != nullptr) { if (i) exr = *i; }
+    int check(h2y_ctx *ctx) const;                           /* the info is one the parser can return (TIFF: and clamp is 0 or 1) */
+    int planes_check(h2y_ctx *ctx, const h2y_desc *d) const; /* d's input planes are the decode's: its sample type, the picture's size */
+    uint64_t payload_bytes() const;
+    uintptr_t align() const; /* what the payload and the planes must be aligned to, in bytes */
+    hipError_t launch(const h2y_ctx *ctx, const payload_frame *frames, int n) const; /* the decode of n frames of a table */
+    const char *kernel() const;
+    std::string variant() const;
+};
+
 /* Everything one batch in flight owns: two of them let h2y_convert_batch_enqueue() queue batch k+1 behind batch k
  * before h2y_batch_finish() has looked at k (the 35 us between two launches -- the statistics kernel, one copy, the
  * host's turn-around -- disappear behind the running kernel). */
@@ -184,24 +206,11 @@ struct h2y_ctx {
     uint16_t *d_tmp = nullptr;
     size_t tmp_cap = 0;
     uint16_t *d_lin = nullptr; /* k_yuvp2_420: lin(Y') of every u16 code (h2y_yuvp2_lin_table), built when first needed */
-    /* h2y_inverse_batch: the frame table (pinned on the host, and its device copy the kernels read) */
-    inv_frame *d_inv_frames = nullptr, *h_inv_frames = nullptr;
-    size_t d_inv_cap = 0, h_inv_cap = 0; /* bytes */
-    /* h2y_dpx_decode_batch's frame table, likewise; a DPX stream keeps one entry per slot in d_dpx_frames */
-    dpx_frame *d_dpx_frames = nullptr, *h_dpx_frames = nullptr;
-    size_t d_dpx_cap = 0, h_dpx_cap = 0; /* bytes */
-    /* h2y_tiff_decode_batch's and h2y_rgb_interleave_batch's frame tables, likewise; the TIFF rings keep one entry per slot */
-    tiff_frame *d_tiff_frames = nullptr, *h_tiff_frames = nullptr;
-    size_t d_tiff_cap = 0, h_tiff_cap = 0; /* bytes */
-    /* h2y_exr_decode_batch's frame table, likewise; an EXR stream keeps one entry per slot */
-    exr_frame *d_exr_frames = nullptr, *h_exr_frames = nullptr;
-    size_t d_exr_cap = 0, h_exr_cap = 0; /* bytes */
-    rgb_frame *d_rgb_frames = nullptr, *h_rgb_frames = nullptr;
-    size_t d_rgb_cap = 0, h_rgb_cap = 0; /* bytes */
-    /* h2y_compare_batch's frame table likewise (an armed ring keeps one entry per slot), k_compare's partials, and the batch's
-     * device stats */
-    cmp_frame *d_cmp_frames = nullptr, *h_cmp_frames = nullptr;
-    size_t d_cmp_cap = 0, h_cmp_cap = 0; /* bytes */
+    /* the frame table of whichever synchronous batch entry runs (h2y_inverse_batch, the decode and compare batches; none runs
+     * beside another batch or a stream): pinned on the host, and its device copy the kernels read (frame_table) */
+    void *d_tab = nullptr, *h_tab = nullptr;
+    size_t d_tab_cap = 0, h_tab_cap = 0; /* bytes */
+    /* k_compare's partials (h2y_compare_batch and an armed ring), and h2y_compare_batch's device stats */
     cmp_partial *d_cmp_part = nullptr;
     size_t cmp_part_cap = 0;
     h2y_compare_stats *d_cmp_stats = nullptr;
@@ -235,33 +244,28 @@ struct h2y_ctx {
     size_t s_plane_al = 0;
     int s_head = 0, s_tail = 0, s_lent = -1;
     bool streaming = false;
-    /* an inverse stream (h2y_inverse_stream_open): the flow's parameters, where the slot's input planes lie, the bytes of one
-     * H2D copy, and the distance between the G, B, R planes in the slot's device output (one plane's bytes, or 256-byte aligned
-     * when that would leave a plane misaligned for the kernel) */
-    bool s_inverse = false;
+    /* what the ring does with a frame: the forward conversion (open_forward_ring), the .yuv -> G,B,R flow (open_inverse_ring),
+     * or a comparison alone (h2y_compare_stream_open) */
+    enum ring_kind { RING_FORWARD, RING_INVERSE, RING_COMPARE } s_kind = RING_FORWARD;
+    /* a forward ring's decode: with one, the pinned slot holds the payload, its device twin the three planes (at s_in_off[0..2])
+     * and then the payload at s_pay_off */
+    decode_src s_src;
+    /* an inverse ring: the flow's parameters, where the slot's input planes lie, the bytes of one H2D copy, and the distance
+     * between the G, B, R planes in the slot's device output (one plane's bytes, or 256-byte aligned when that would leave a plane
+     * misaligned for the kernel); with s_interleave (h2y_tiff_inverse_stream_open) the device output holds, at s_pay_off after
+     * the planes, write_tiff's interleaved R,G,B samples, and only they go down */
     inv_params s_inv{};
-    /* a DPX stream (h2y_dpx_stream_open): the pinned slot holds the payload, its device twin the three float planes (at
-     * s_in_off[0..2]) and then the payload at s_dpx_off */
-    bool s_dpx = false;
-    h2y_dpx_info s_dpx_info{};
-    size_t s_dpx_off = 0;
-    /* a TIFF stream (h2y_tiff_stream_open): laid out as a DPX stream, u16 planes, the packed rows at s_tiff_off */
-    bool s_tiff = false, s_tiff_clamp = false;
-    h2y_tiff_info s_tiff_info{};
-    size_t s_tiff_off = 0;
-    /* an EXR stream (h2y_exr_stream_open): laid out as a TIFF stream, half planes, the payload at s_exr_off */
-    bool s_exr = false;
-    h2y_exr_info s_exr_info{};
-    size_t s_exr_off = 0;
-    /* a TIFF inverse stream (h2y_tiff_inverse_stream_open): an inverse stream whose slot output holds, at s_rgb_off after the
-     * G, B, R planes, the interleaved R,G,B samples that go down */
-    bool s_rgb = false;
-    size_t s_rgb_off = 0;
+    bool s_interleave = false;
+    size_t s_pay_off = 0;
     size_t s_in_off[3] = {0, 0, 0}, s_in_bytes = 0, s_out_stride = 0;
+    /* one entry per slot, uploaded when the ring is opened or armed: the decode's or the interleave's (payload_frame, rgb_frame),
+     * and k_compare's of an armed ring; stream_free releases them */
+    void *s_tab = nullptr;
+    cmp_frame *s_cmp_tab = nullptr;
     /* an armed ring (h2y_stream_compare) or a compare-only ring (h2y_compare_stream_open): k_compare's geometry (A the slot's
      * device output, or its input on a compare-only ring; B its reference), the reference's bytes, whether the frame goes down */
     bool s_started = false; /* an input was handed out: too late to arm */
-    bool s_cmp = false, s_cmp_keep = true, s_cmp_only = false;
+    bool s_cmp = false, s_cmp_keep = true;
     cmp_geom s_cmp_geom{};
     size_t s_ref_bytes = 0, s_ref_stats_off = 0; /* the pinned reference's bytes; where the stats lie in its device twin */
     int slot_base = 0; /* run_frames(): first entry of d_frames/h_frames to use (one per stream slot) */
@@ -1439,18 +1443,8 @@ void h2y_ctx_destroy(h2y_ctx *ctx)
     (void)hipFree(ctx->d_table_ext);
     (void)hipFree(ctx->d_tmp);
     (void)hipFree(ctx->d_lin);
-    (void)hipFree(ctx->d_inv_frames);
-    (void)hipHostFree(ctx->h_inv_frames);
-    (void)hipFree(ctx->d_dpx_frames);
-    (void)hipHostFree(ctx->h_dpx_frames);
-    (void)hipFree(ctx->d_tiff_frames);
-    (void)hipHostFree(ctx->h_tiff_frames);
-    (void)hipFree(ctx->d_exr_frames);
-    (void)hipHostFree(ctx->h_exr_frames);
-    (void)hipFree(ctx->d_rgb_frames);
-    (void)hipHostFree(ctx->h_rgb_frames);
-    (void)hipFree(ctx->d_cmp_frames);
-    (void)hipHostFree(ctx->h_cmp_frames);
+    (void)hipFree(ctx->d_tab);
+    (void)hipHostFree(ctx->h_tab);
     (void)hipFree(ctx->d_cmp_part);
     (void)hipFree(ctx->d_cmp_stats);
     (void)hipFree(ctx->d_in);
@@ -1879,6 +1873,101 @@ static int inverse_check(h2y_ctx *ctx, const inv_params &p)
     return H2Y_OK;
 }
 
+/* a grid of one block per unit of 256 threads, eight blocks of 256 per CU at most */
+static int unit_grid(const h2y_ctx *ctx, uint64_t units)
+{
+    const uint64_t max_grid = (uint64_t)ctx->n_cu * 8u;
+    return (int)(units < max_grid ? (units ? units : 1) : max_grid);
+}
+
+extern "C++" {
+
+/* A synchronous batch entry's frame table of n entries of T: the context's pinned host table h, and its device copy, grown as
+ * needed.  One pair serves every entry: none runs beside another batch or a stream. */
+template <typename T> static int frame_table(h2y_ctx *ctx, int n, T *&h)
+{
+    const size_t tb = (size_t)n * sizeof(T);
+    int rc = ensure(ctx, ctx->d_tab, ctx->d_tab_cap, tb);
+    if (rc) return rc;
+    if (ctx->h_tab_cap < tb) {
+        if (ctx->h_tab) HIP_TRY(ctx, hipHostFree(ctx->h_tab));
+        ctx->h_tab = nullptr;
+        ctx->h_tab_cap = 0;
+        hipError_t e = hipHostMalloc(&ctx->h_tab, tb, hipHostMallocDefault);
+        if (e != hipSuccess) return fail(ctx, H2Y_ENOMEM, "hipHostMalloc(%zu): %s", tb, hipGetErrorString(e));
+        ctx->h_tab_cap = tb;
+    }
+    h = static_cast<T *>(ctx->h_tab);
+    return H2Y_OK;
+}
+
+/* The table h of n_frames entries (frame_table's) goes up once, then launch(frames, f0, nf) enqueues one launch on the device
+ * entries [f0, f0 + nf), in launches of up to per_launch frames, each timed with an event pair (launches past the last pair are
+ * timed by it); then a synchronisation, and last_ms, last_launches and last_name are the batch's */
+template <typename T, typename F>
+static int timed_launches(h2y_ctx *ctx, const T *h, int n_frames, int per_launch, const char *name, F launch)
+{
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_tab, h, (size_t)n_frames * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+    const T *frames = static_cast<const T *>(ctx->d_tab);
+    int launches = 0;
+    for (int f0 = 0; f0 < n_frames; f0 += per_launch, launches++) {
+        const int nf = n_frames - f0 < per_launch ? n_frames - f0 : per_launch;
+        const int e = launches < kMaxEvents ? launches : kMaxEvents - 1;
+        if (launches < kMaxEvents) HIP_TRY(ctx, hipEventRecord(ctx->b->ev[e][0], ctx->stream));
+        HIP_TRY(ctx, launch(frames + f0, f0, nf));
+        HIP_TRY(ctx, hipEventRecord(ctx->b->ev[e][1], ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->b->n_ev = launches < kMaxEvents ? launches : kMaxEvents;
+    float ms = 0.f;
+    for (int i = 0; i < ctx->b->n_ev; i++) {
+        float t = 0.f;
+        HIP_TRY(ctx, hipEventElapsedTime(&t, ctx->b->ev[i][0], ctx->b->ev[i][1]));
+        ms += t;
+    }
+    ctx->last_ms = ms;
+    ctx->last_launches = launches;
+    ctx->last_name = name;
+    return H2Y_OK;
+}
+
+/* h2y_dpx_decode_batch, h2y_tiff_decode_batch, h2y_exr_decode_batch: src's decode of n_frames payloads into their planes */
+template <typename P>
+static int decode_batch(h2y_ctx *ctx, const decode_src &src, int per_launch, int n_frames, const void *const *d_payload, P *const *d_planes)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
+    int rc = src.check(ctx);
+    if (rc) return rc;
+    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
+    if (!d_payload || !d_planes) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
+    const uintptr_t al = src.align();
+    for (int f = 0; f < n_frames; f++) {
+        if (!d_payload[f]) return fail(ctx, H2Y_EINVAL, "frame %d: payload is null", f);
+        if ((uintptr_t)d_payload[f] & (al - 1)) return fail(ctx, H2Y_EINVAL, "frame %d: payload is not %d-byte aligned", f, (int)al);
+        for (int c = 0; c < 3; c++) {
+            const P *p = d_planes[3 * f + c];
+            if (!p) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is null", f, c);
+            if ((uintptr_t)p & (al - 1)) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is not %d-byte aligned", f, c, (int)al);
+        }
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    payload_frame *h;
+    rc = frame_table(ctx, n_frames, h);
+    if (rc) return rc;
+    for (int f = 0; f < n_frames; f++) {
+        h[f].payload = d_payload[f];
+        for (int c = 0; c < 3; c++) h[f].plane[c] = d_planes[3 * f + c];
+    }
+    rc = timed_launches(ctx, h, n_frames, per_launch, src.kernel(),
+                        [&](const payload_frame *frames, int, int nf) { return src.launch(ctx, frames, nf); });
+    if (rc) return rc;
+    ctx->last_variant = src.variant();
+    return H2Y_OK;
+}
+
+} // extern "C++"
+
 int h2y_inverse_batch(h2y_ctx *ctx, int width, int height, int in_chroma_format_idc, int in_bit_depth, int in_full_range,
                       int in_matrix_coeffs, int out_bit_depth, int algorithm, int n_frames, const uint16_t *const *d_in,
                       uint16_t *const *d_out)
@@ -1899,53 +1988,28 @@ int h2y_inverse_batch(h2y_ctx *ctx, int width, int height, int in_chroma_format_
             if (((uintptr_t)i | (uintptr_t)o) & (align - 1)) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is not %d-byte aligned", f, c, (int)align);
         }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    /* the whole table is uploaded once, every launch reads its own part of it */
-    const size_t tb = (size_t)n_frames * sizeof(inv_frame);
-    rc = ensure(ctx, ctx->d_inv_frames, ctx->d_inv_cap, tb);
+    inv_frame *h;
+    rc = frame_table(ctx, n_frames, h);
     if (rc) return rc;
-    if (ctx->h_inv_cap < tb) {
-        if (ctx->h_inv_frames) HIP_TRY(ctx, hipHostFree(ctx->h_inv_frames));
-        ctx->h_inv_frames = nullptr;
-        ctx->h_inv_cap = 0;
-        hipError_t e = hipHostMalloc((void **)&ctx->h_inv_frames, tb, hipHostMallocDefault);
-        if (e != hipSuccess) return fail(ctx, H2Y_ENOMEM, "hipHostMalloc(%zu): %s", tb, hipGetErrorString(e));
-        ctx->h_inv_cap = tb;
-    }
     for (int f = 0; f < n_frames; f++)
         for (int c = 0; c < 3; c++) {
-            ctx->h_inv_frames[f].in[c] = d_in[3 * f + c];
-            ctx->h_inv_frames[f].out[c] = d_out[3 * f + c];
+            h[f].in[c] = d_in[3 * f + c];
+            h[f].out[c] = d_out[3 * f + c];
         }
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_inv_frames, ctx->h_inv_frames, tb, hipMemcpyHostToDevice, ctx->stream));
     inv420_args a;
     inverse420_setup(a, width, height, in_bit_depth, in_full_range, in_matrix_coeffs, out_bit_depth, algorithm);
     /* units of one frame: k_inverse420's tiles, or k_inverse's chunks of 256 quads (+ the npix % 4 single samples) */
     const uint32_t n4 = a.inv.npix >> 2;
     const uint32_t per_frame = sub ? (uint32_t)h2y_inverse420_tiles(width, height) : (n4 + (a.inv.npix & 3u) + 255) / 256;
     const uint32_t max_grid = (uint32_t)ctx->n_cu * (sub ? 8u : 16u); /* as k_inverse420 (eight blocks of 256 per CU) and k_inverse */
-    int launches = 0;
-    for (int f0 = 0; f0 < n_frames; f0 += H2Y_INVERSE_FRAMES_PER_LAUNCH, launches++) {
-        const int nf = n_frames - f0 < H2Y_INVERSE_FRAMES_PER_LAUNCH ? n_frames - f0 : H2Y_INVERSE_FRAMES_PER_LAUNCH;
-        const uint64_t units = (uint64_t)nf * per_frame;
-        const int grid = (int)(units < max_grid ? units : max_grid);
-        /* launches past the last event pair are timed by it: it then spans them all */
-        const int e = launches < kMaxEvents ? launches : kMaxEvents - 1;
-        if (launches < kMaxEvents) HIP_TRY(ctx, hipEventRecord(ctx->b->ev[e][0], ctx->stream));
-        if (sub) HIP_TRY(ctx, h2y_launch_inverse420_batch(grid, ctx->stream, a, ctx->d_inv_frames + f0, nf));
-        else HIP_TRY(ctx, h2y_launch_inverse_batch(grid, ctx->stream, a.inv, ctx->d_inv_frames + f0, nf));
-        HIP_TRY(ctx, hipEventRecord(ctx->b->ev[e][1], ctx->stream));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->b->n_ev = launches < kMaxEvents ? launches : kMaxEvents;
-    float ms = 0.f;
-    for (int i = 0; i < ctx->b->n_ev; i++) {
-        float t = 0.f;
-        HIP_TRY(ctx, hipEventElapsedTime(&t, ctx->b->ev[i][0], ctx->b->ev[i][1]));
-        ms += t;
-    }
-    ctx->last_ms = ms;
-    ctx->last_launches = launches;
-    ctx->last_name = sub ? "k_inverse420_batch" : "k_inverse_batch";
+    rc = timed_launches(ctx, h, n_frames, H2Y_INVERSE_FRAMES_PER_LAUNCH, sub ? "k_inverse420_batch" : "k_inverse_batch",
+                        [&](const inv_frame *frames, int, int nf) {
+                            const uint64_t units = (uint64_t)nf * per_frame;
+                            const int grid = (int)(units < max_grid ? units : max_grid);
+                            return sub ? h2y_launch_inverse420_batch(grid, ctx->stream, a, frames, nf)
+                                       : h2y_launch_inverse_batch(grid, ctx->stream, a.inv, frames, nf);
+                        });
+    if (rc) return rc;
     ctx->last_variant = sub ? (algorithm ? "k_inverse420_batch<FIR>" : "k_inverse420_batch<REPLICATE>") : "k_inverse_batch";
     return H2Y_OK;
 }
@@ -1954,14 +2018,6 @@ int h2y_inverse_batch(h2y_ctx *ctx, int width, int height, int in_chroma_format_
 
 static int dpx_fmt_of(int bit_size) { return bit_size == 10 ? H2Y_DPX_10 : bit_size == 16 ? H2Y_DPX_16 : H2Y_DPX_F32; }
 static uint64_t dpx_pixel_bytes(int bit_size) { return bit_size == 10 ? 4 : bit_size == 16 ? 6 : 12; }
-
-/* k_dpx_decode's grid for n frames: one block per unit of 256 threads, eight blocks of 256 per CU at most */
-static int dpx_grid(const h2y_ctx *ctx, const h2y_dpx_info &di, int n)
-{
-    const uint64_t units = (uint64_t)n * h2y_dpx_chunks(dpx_fmt_of(di.bit_size), (uint32_t)di.width * (uint32_t)di.height);
-    const uint64_t max_grid = (uint64_t)ctx->n_cu * 8u;
-    return (int)(units < max_grid ? (units ? units : 1) : max_grid);
-}
 
 /* what h2y_dpx_parse can return, and nothing else */
 static int dpx_info_check(h2y_ctx *ctx, const h2y_dpx_info *di)
@@ -2012,66 +2068,23 @@ int h2y_dpx_parse(const void *header, size_t n, uint64_t file_bytes, h2y_dpx_inf
     return H2Y_OK;
 }
 
+/* decode_src's DPX launch and variant: k_dpx_decode on n frames of a table */
+static hipError_t dpx_decode(const h2y_ctx *ctx, const h2y_dpx_info &di, const payload_frame *frames, int n)
+{
+    const int fmt = dpx_fmt_of(di.bit_size);
+    const uint32_t npix = (uint32_t)di.width * (uint32_t)di.height;
+    return h2y_launch_dpx_decode(fmt, di.swap != 0, unit_grid(ctx, (uint64_t)n * h2y_dpx_chunks(fmt, npix)), ctx->stream, npix, frames, n);
+}
+
+static std::string dpx_variant(const h2y_dpx_info &di)
+{
+    const int fmt = dpx_fmt_of(di.bit_size);
+    return std::string("k_dpx_decode<") + (fmt == H2Y_DPX_10 ? "10" : fmt == H2Y_DPX_16 ? "16" : "F32") + (di.swap ? ",SWAP>" : ",NOSWAP>");
+}
+
 int h2y_dpx_decode_batch(h2y_ctx *ctx, const h2y_dpx_info *info, int n_frames, const void *const *d_payload, float *const *d_planes)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
-    int rc = dpx_info_check(ctx, info);
-    if (rc) return rc;
-    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
-    if (!d_payload || !d_planes) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
-    for (int f = 0; f < n_frames; f++) {
-        if (!d_payload[f]) return fail(ctx, H2Y_EINVAL, "frame %d: payload is null", f);
-        if ((uintptr_t)d_payload[f] & 3u) return fail(ctx, H2Y_EINVAL, "frame %d: payload is not 4-byte aligned", f);
-        for (int c = 0; c < 3; c++) {
-            const float *p = d_planes[3 * f + c];
-            if (!p) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is null", f, c);
-            if ((uintptr_t)p & 3u) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is not 4-byte aligned", f, c);
-        }
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    /* the whole table is uploaded once, every launch reads its own part of it */
-    const size_t tb = (size_t)n_frames * sizeof(dpx_frame);
-    rc = ensure(ctx, ctx->d_dpx_frames, ctx->d_dpx_cap, tb);
-    if (rc) return rc;
-    if (ctx->h_dpx_cap < tb) {
-        if (ctx->h_dpx_frames) HIP_TRY(ctx, hipHostFree(ctx->h_dpx_frames));
-        ctx->h_dpx_frames = nullptr;
-        ctx->h_dpx_cap = 0;
-        hipError_t e = hipHostMalloc((void **)&ctx->h_dpx_frames, tb, hipHostMallocDefault);
-        if (e != hipSuccess) return fail(ctx, H2Y_ENOMEM, "hipHostMalloc(%zu): %s", tb, hipGetErrorString(e));
-        ctx->h_dpx_cap = tb;
-    }
-    for (int f = 0; f < n_frames; f++) {
-        ctx->h_dpx_frames[f].payload = d_payload[f];
-        for (int c = 0; c < 3; c++) ctx->h_dpx_frames[f].plane[c] = d_planes[3 * f + c];
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_dpx_frames, ctx->h_dpx_frames, tb, hipMemcpyHostToDevice, ctx->stream));
-    const int fmt = dpx_fmt_of(info->bit_size);
-    const uint32_t npix = (uint32_t)info->width * (uint32_t)info->height;
-    int launches = 0;
-    for (int f0 = 0; f0 < n_frames; f0 += H2Y_DPX_FRAMES_PER_LAUNCH, launches++) {
-        const int nf = n_frames - f0 < H2Y_DPX_FRAMES_PER_LAUNCH ? n_frames - f0 : H2Y_DPX_FRAMES_PER_LAUNCH;
-        /* launches past the last event pair are timed by it: it then spans them all */
-        const int e = launches < kMaxEvents ? launches : kMaxEvents - 1;
-        if (launches < kMaxEvents) HIP_TRY(ctx, hipEventRecord(ctx->b->ev[e][0], ctx->stream));
-        HIP_TRY(ctx, h2y_launch_dpx_decode(fmt, info->swap != 0, dpx_grid(ctx, *info, nf), ctx->stream, npix, ctx->d_dpx_frames + f0, nf));
-        HIP_TRY(ctx, hipEventRecord(ctx->b->ev[e][1], ctx->stream));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->b->n_ev = launches < kMaxEvents ? launches : kMaxEvents;
-    float ms = 0.f;
-    for (int i = 0; i < ctx->b->n_ev; i++) {
-        float t = 0.f;
-        HIP_TRY(ctx, hipEventElapsedTime(&t, ctx->b->ev[i][0], ctx->b->ev[i][1]));
-        ms += t;
-    }
-    ctx->last_ms = ms;
-    ctx->last_launches = launches;
-    ctx->last_name = "k_dpx_decode";
-    ctx->last_variant = std::string("k_dpx_decode<") + (fmt == H2Y_DPX_10 ? "10" : fmt == H2Y_DPX_16 ? "16" : "F32") +
-                        (info->swap ? ",SWAP>" : ",NOSWAP>");
-    return H2Y_OK;
+    return decode_batch(ctx, decode_src(info), H2Y_DPX_FRAMES_PER_LAUNCH, n_frames, d_payload, d_planes);
 }
 
 /* ---- streaming pipeline ------------------------------------------------------
@@ -2097,13 +2110,15 @@ static void stream_free(h2y_ctx *ctx)
     if (ctx->s_h2d) (void)hipStreamDestroy(ctx->s_h2d);
     if (ctx->s_d2h) (void)hipStreamDestroy(ctx->s_d2h);
     ctx->s_h2d = ctx->s_d2h = nullptr;
+    if (ctx->s_tab) (void)hipFree(ctx->s_tab);
+    if (ctx->s_cmp_tab) (void)hipFree(ctx->s_cmp_tab);
+    ctx->s_tab = nullptr;
+    ctx->s_cmp_tab = nullptr;
     ctx->streaming = false;
-    ctx->s_inverse = false;
-    ctx->s_dpx = false;
-    ctx->s_tiff = false;
-    ctx->s_exr = false;
-    ctx->s_rgb = false;
-    ctx->s_started = ctx->s_cmp = ctx->s_cmp_only = false;
+    ctx->s_kind = h2y_ctx::RING_FORWARD;
+    ctx->s_src = decode_src();
+    ctx->s_interleave = false;
+    ctx->s_started = ctx->s_cmp = false;
     ctx->s_cmp_keep = true;
     ctx->s_head = ctx->s_tail = 0;
     ctx->s_lent = -1;
@@ -2132,13 +2147,42 @@ static int stream_alloc(h2y_ctx *ctx, int depth, size_t h_in_bytes, size_t d_in_
     return H2Y_OK;
 }
 
-int h2y_stream_open(h2y_ctx *ctx, const h2y_desc *d, int depth)
+extern "C++" {
+
+/* the open ring's s_tab: the decode's or the interleave's entry of every slot, uploaded once (the ring closes if it fails) */
+template <typename T> static int slot_table(h2y_ctx *ctx, const std::vector<T> &tab, const char *what)
+{
+    const size_t tb = tab.size() * sizeof(T);
+    hipError_t e = hipMalloc(&ctx->s_tab, tb);
+    if (e != hipSuccess) {
+        stream_free(ctx);
+        return fail(ctx, H2Y_ENOMEM, "hipMalloc(%zu): %s", tb, hipGetErrorString(e));
+    }
+    e = hipMemcpy(ctx->s_tab, tab.data(), tb, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        stream_free(ctx);
+        return fail(ctx, H2Y_EHIP, "hipMemcpy of the %s slot table: %s", what, hipGetErrorString(e));
+    }
+    return H2Y_OK;
+}
+
+} // extern "C++"
+
+/* The forward ring (h2y_stream_open and the decoding openers).  Without a decode (src null) a slot holds the three planes, each
+ * 256-byte aligned, on the host and on the device.  With one the pinned slot holds the payload, its device twin the three planes
+ * the decode writes and then the payload; each slot's decode table entry is uploaded here once. */
+static int open_forward_ring(h2y_ctx *ctx, const h2y_desc *d, const decode_src *src, int depth)
 {
     if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
     if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is already open");
+    const decode_src &dec = src ? *src : decode_src();
+    int rc = dec.check(ctx);
+    if (rc) return rc;
     const char *why;
-    int rc = h2y_desc_check(d, &why);
+    rc = h2y_desc_check(d, &why);
     if (rc) return fail(ctx, rc, "descriptor: %s", why);
+    rc = dec.planes_check(ctx, d);
+    if (rc) return rc;
     if (depth < 2 || depth > 16) return fail(ctx, H2Y_EINVAL, "depth must be 2..16");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     rc = reserve_batch(ctx, 64);
@@ -2147,77 +2191,77 @@ int h2y_stream_open(h2y_ctx *ctx, const h2y_desc *d, int depth)
     ctx->s_plane_al = (pb + 255) & ~(size_t)255;
     ctx->s_desc = *d;
     for (int c = 0; c < 3; c++) ctx->s_in_off[c] = c * ctx->s_plane_al;
-    return stream_alloc(ctx, depth, 3 * ctx->s_plane_al, 3 * ctx->s_plane_al, ob, ob);
+    ctx->s_pay_off = 3 * ctx->s_plane_al;
+    const bool decode = dec.kind != decode_src::NONE;
+    const size_t h_in = decode ? dec.payload_bytes() : 3 * ctx->s_plane_al;
+    rc = stream_alloc(ctx, depth, h_in, decode ? ctx->s_pay_off + h_in : h_in, ob, ob);
+    if (rc) return rc;
+    if (decode) {
+        std::vector<payload_frame> tab(depth);
+        for (int k = 0; k < depth; k++) {
+            tab[k].payload = ctx->ss[k].d_in + ctx->s_pay_off;
+            for (int c = 0; c < 3; c++) tab[k].plane[c] = ctx->ss[k].d_in + ctx->s_in_off[c];
+        }
+        rc = slot_table(ctx, tab, dec.kind == decode_src::DPX ? "DPX" : dec.kind == decode_src::TIFF ? "TIFF" : "EXR");
+        if (rc) return rc;
+    }
+    ctx->s_kind = h2y_ctx::RING_FORWARD;
+    ctx->s_src = dec;
+    return H2Y_OK;
 }
 
 /* The same ring for the .yuv -> G,B,R flow: a slot's input is Y, Cb/Dz, Cr/Dx one after the other (each 256-byte aligned; one
- * H2D copy), its output G | B | R, width x height each, contiguous on the host (one D2H copy where the device planes are too) */
-int h2y_inverse_stream_open(h2y_ctx *ctx, int width, int height, int in_chroma_format_idc, int in_bit_depth, int in_full_range,
-                            int in_matrix_coeffs, int out_bit_depth, int algorithm, int depth)
+ * H2D copy), its output G | B | R, width x height each, contiguous on the host (one D2H copy where the device planes are too).
+ * With interleave (write_tiff's), the slot's device output holds after the planes, 256-byte aligned, the interleaved samples,
+ * and only those go down; each slot's k_rgb_interleave table entry is uploaded here once. */
+static int open_inverse_ring(h2y_ctx *ctx, const inv_params &p, bool interleave, int depth)
 {
     if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
     if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is already open");
-    const inv_params p{width, height, in_chroma_format_idc, in_bit_depth, in_full_range, in_matrix_coeffs, out_bit_depth, algorithm};
     int rc = inverse_check(ctx, p);
     if (rc) return rc;
     if (depth < 2 || depth > 16) return fail(ctx, H2Y_EINVAL, "depth must be 2..16");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t pb = (size_t)width * height * sizeof(uint16_t), pb_al = (pb + 255) & ~(size_t)255;
-    const size_t cb = in_chroma_format_idc == H2Y_CHROMA_420 ? (size_t)(width >> 1) * (height >> 1) * sizeof(uint16_t) : pb;
+    const size_t pb = (size_t)p.width * p.height * sizeof(uint16_t), pb_al = (pb + 255) & ~(size_t)255;
+    const size_t cb = p.chroma == H2Y_CHROMA_420 ? (size_t)(p.width >> 1) * (p.height >> 1) * sizeof(uint16_t) : pb;
     const size_t cb_al = (cb + 255) & ~(size_t)255;
     ctx->s_in_off[0] = 0;
     ctx->s_in_off[1] = pb_al;
     ctx->s_in_off[2] = pb_al + cb_al;
     ctx->s_in_bytes = pb_al + cb_al + cb;
     ctx->s_out_stride = (pb & 15) ? pb_al : pb; /* 4:2:0 planes are always a multiple of 16 bytes */
+    ctx->s_pay_off = (2 * ctx->s_out_stride + pb + 255) & ~(size_t)255;
     ctx->s_inv = p;
-    rc = stream_alloc(ctx, depth, ctx->s_in_bytes, ctx->s_in_bytes, 3 * pb, 2 * ctx->s_out_stride + pb);
+    rc = stream_alloc(ctx, depth, ctx->s_in_bytes, ctx->s_in_bytes, 3 * pb, interleave ? ctx->s_pay_off + 3 * pb : 2 * ctx->s_out_stride + pb);
     if (rc) return rc;
-    ctx->s_inverse = true;
+    if (interleave) {
+        std::vector<rgb_frame> tab(depth);
+        for (int k = 0; k < depth; k++) {
+            char *o = reinterpret_cast<char *>(ctx->ss[k].d_out);
+            for (int c = 0; c < 3; c++) tab[k].plane[c] = reinterpret_cast<const uint16_t *>(o + c * ctx->s_out_stride);
+            tab[k].rgb = reinterpret_cast<uint16_t *>(o + ctx->s_pay_off);
+        }
+        rc = slot_table(ctx, tab, "TIFF inverse");
+        if (rc) return rc;
+    }
+    ctx->s_kind = h2y_ctx::RING_INVERSE;
+    ctx->s_interleave = interleave;
     return H2Y_OK;
 }
 
-/* The same ring on DPX payloads: the pinned slot holds payload_bytes, its device twin the three float planes (each 256-byte
- * aligned, as h2y_stream_open lays them out) and then the payload; each slot's k_dpx_decode table entry is uploaded here once */
+int h2y_stream_open(h2y_ctx *ctx, const h2y_desc *d, int depth) { return open_forward_ring(ctx, d, nullptr, depth); }
+
+int h2y_inverse_stream_open(h2y_ctx *ctx, int width, int height, int in_chroma_format_idc, int in_bit_depth, int in_full_range,
+                            int in_matrix_coeffs, int out_bit_depth, int algorithm, int depth)
+{
+    const inv_params p{width, height, in_chroma_format_idc, in_bit_depth, in_full_range, in_matrix_coeffs, out_bit_depth, algorithm};
+    return open_inverse_ring(ctx, p, false, depth);
+}
+
 int h2y_dpx_stream_open(h2y_ctx *ctx, const h2y_desc *d, const h2y_dpx_info *info, int depth)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is already open");
-    int rc = dpx_info_check(ctx, info);
-    if (rc) return rc;
-    const char *why;
-    rc = h2y_desc_check(d, &why);
-    if (rc) return fail(ctx, rc, "descriptor: %s", why);
-    if (d->in_sample_type != H2Y_SAMPLE_F32) return fail(ctx, H2Y_EINVAL, "a DPX stream decodes to F32 planes: in_sample_type must be H2Y_SAMPLE_F32");
-    if (d->width != info->width || d->height != info->height)
-        return fail(ctx, H2Y_EINVAL, "DPX picture is %dx%d, the descriptor %dx%d (resizing is not part of convert())", info->width, info->height,
-                    d->width, d->height);
-    if (depth < 2 || depth > 16) return fail(ctx, H2Y_EINVAL, "depth must be 2..16");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    rc = reserve_batch(ctx, 64);
-    if (rc) return rc;
-    rc = ensure(ctx, ctx->d_dpx_frames, ctx->d_dpx_cap, (size_t)depth * sizeof(dpx_frame));
-    if (rc) return rc;
-    const size_t pb = h2y_plane_bytes(d), ob = h2y_frame_bytes(d);
-    ctx->s_plane_al = (pb + 255) & ~(size_t)255;
-    ctx->s_desc = *d;
-    for (int c = 0; c < 3; c++) ctx->s_in_off[c] = c * ctx->s_plane_al;
-    ctx->s_dpx_off = 3 * ctx->s_plane_al;
-    rc = stream_alloc(ctx, depth, info->payload_bytes, ctx->s_dpx_off + info->payload_bytes, ob, ob);
-    if (rc) return rc;
-    std::vector<dpx_frame> tab(depth);
-    for (int k = 0; k < depth; k++) {
-        tab[k].payload = ctx->ss[k].d_in + ctx->s_dpx_off;
-        for (int c = 0; c < 3; c++) tab[k].plane[c] = reinterpret_cast<float *>(ctx->ss[k].d_in + ctx->s_in_off[c]);
-    }
-    hipError_t e = hipMemcpy(ctx->d_dpx_frames, tab.data(), tab.size() * sizeof(dpx_frame), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        stream_free(ctx);
-        return fail(ctx, H2Y_EHIP, "hipMemcpy of the DPX slot table: %s", hipGetErrorString(e));
-    }
-    ctx->s_dpx = true;
-    ctx->s_dpx_info = *info;
-    return H2Y_OK;
+    const decode_src src(info);
+    return open_forward_ring(ctx, d, &src, depth);
 }
 
 /* ---- 16-bit RGB TIFF (read_tiff(), tiff.cpp:54-362; write_tiff(), tiff.cpp:559-652) ------------------------------------- */
@@ -2426,8 +2470,8 @@ int h2y_tiff_layout(int width, int height, uint8_t head[8], uint8_t *tail, size_
     return H2Y_OK;
 }
 
-/* what h2y_tiff_parse can return, and nothing else */
-static int tiff_info_check(h2y_ctx *ctx, const h2y_tiff_info *ti)
+/* what h2y_tiff_parse can return, and nothing else; and the decode's clamp_video_range */
+static int tiff_info_check(h2y_ctx *ctx, const h2y_tiff_info *ti, int clamp)
 {
     if (!ti) return fail(ctx, H2Y_EINVAL, "null h2y_tiff_info");
     if (ti->file_width < 1 || ti->file_width > (1 << 20) || ti->file_height < 1 || ti->file_height > (1 << 20))
@@ -2439,105 +2483,27 @@ static int tiff_info_check(h2y_ctx *ctx, const h2y_tiff_info *ti)
     if (ti->swap != 0 && ti->swap != 1) return fail(ctx, H2Y_EINVAL, "TIFF swap must be 0 or 1");
     if (ti->row_bytes != 6ull * (uint64_t)ti->file_width) return fail(ctx, H2Y_EINVAL, "TIFF row_bytes is not 6 x file_width");
     if (ti->payload_bytes != (uint64_t)ti->height * ti->row_bytes) return fail(ctx, H2Y_EINVAL, "TIFF payload_bytes is not height x row_bytes");
+    if (clamp != 0 && clamp != 1) return fail(ctx, H2Y_EINVAL, "clamp_video_range must be 0 or 1");
     return H2Y_OK;
 }
 
-static tiff_geom tiff_geom_of(const h2y_tiff_info &ti)
+/* decode_src's TIFF launch and variant: k_tiff_decode on n frames of a table */
+static hipError_t tiff_decode(const h2y_ctx *ctx, const h2y_tiff_info &ti, bool clamp, const payload_frame *frames, int n)
 {
-    return tiff_geom{(uint32_t)ti.width, (uint32_t)ti.height, (uint32_t)ti.x0, (uint32_t)ti.row_bytes};
+    const tiff_geom g{(uint32_t)ti.width, (uint32_t)ti.height, (uint32_t)ti.x0, (uint32_t)ti.row_bytes};
+    return h2y_launch_tiff_decode(ti.swap != 0, clamp, unit_grid(ctx, (uint64_t)h2y_tiff_chunks(g.width, g.height) * n), ctx->stream, g,
+                                  frames, n);
 }
 
-/* a grid of one block per unit of 256 threads, eight blocks of 256 per CU at most */
-static int unit_grid(const h2y_ctx *ctx, uint64_t units)
+static std::string tiff_variant(const h2y_tiff_info &ti, bool clamp)
 {
-    const uint64_t max_grid = (uint64_t)ctx->n_cu * 8u;
-    return (int)(units < max_grid ? (units ? units : 1) : max_grid);
+    return std::string("k_tiff_decode<") + (ti.swap ? "SWAP" : "NOSWAP") + (clamp ? ",CLAMP>" : ",NOCLAMP>");
 }
-
-extern "C++" {
-
-/* the pinned host table of n entries and its device copy, grown as needed */
-template <typename T> static int frame_table(h2y_ctx *ctx, T *&d, size_t &dcap, T *&h, size_t &hcap, int n)
-{
-    const size_t tb = (size_t)n * sizeof(T);
-    int rc = ensure(ctx, d, dcap, tb);
-    if (rc) return rc;
-    if (hcap < tb) {
-        if (h) HIP_TRY(ctx, hipHostFree(h));
-        h = nullptr;
-        hcap = 0;
-        hipError_t e = hipHostMalloc((void **)&h, tb, hipHostMallocDefault);
-        if (e != hipSuccess) return fail(ctx, H2Y_ENOMEM, "hipHostMalloc(%zu): %s", tb, hipGetErrorString(e));
-        hcap = tb;
-    }
-    return H2Y_OK;
-}
-
-/* n_frames in launches of H2Y_TIFF_FRAMES_PER_LAUNCH, each timed with an event pair (launches past the last pair are timed by
- * it), then a synchronisation; launch(f0, nf) enqueues one launch */
-template <typename F> static int timed_launches(h2y_ctx *ctx, int n_frames, const char *name, F launch)
-{
-    int launches = 0;
-    for (int f0 = 0; f0 < n_frames; f0 += H2Y_TIFF_FRAMES_PER_LAUNCH, launches++) {
-        const int nf = n_frames - f0 < H2Y_TIFF_FRAMES_PER_LAUNCH ? n_frames - f0 : H2Y_TIFF_FRAMES_PER_LAUNCH;
-        const int e = launches < kMaxEvents ? launches : kMaxEvents - 1;
-        if (launches < kMaxEvents) HIP_TRY(ctx, hipEventRecord(ctx->b->ev[e][0], ctx->stream));
-        HIP_TRY(ctx, launch(f0, nf));
-        HIP_TRY(ctx, hipEventRecord(ctx->b->ev[e][1], ctx->stream));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->b->n_ev = launches < kMaxEvents ? launches : kMaxEvents;
-    float ms = 0.f;
-    for (int i = 0; i < ctx->b->n_ev; i++) {
-        float t = 0.f;
-        HIP_TRY(ctx, hipEventElapsedTime(&t, ctx->b->ev[i][0], ctx->b->ev[i][1]));
-        ms += t;
-    }
-    ctx->last_ms = ms;
-    ctx->last_launches = launches;
-    ctx->last_name = name;
-    return H2Y_OK;
-}
-
-} // extern "C++"
 
 int h2y_tiff_decode_batch(h2y_ctx *ctx, const h2y_tiff_info *info, int clamp_video_range, int n_frames, const void *const *d_payload,
                           uint16_t *const *d_planes)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
-    int rc = tiff_info_check(ctx, info);
-    if (rc) return rc;
-    if (clamp_video_range != 0 && clamp_video_range != 1) return fail(ctx, H2Y_EINVAL, "clamp_video_range must be 0 or 1");
-    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
-    if (!d_payload || !d_planes) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
-    for (int f = 0; f < n_frames; f++) {
-        if (!d_payload[f]) return fail(ctx, H2Y_EINVAL, "frame %d: payload is null", f);
-        if ((uintptr_t)d_payload[f] & 1u) return fail(ctx, H2Y_EINVAL, "frame %d: payload is not 2-byte aligned", f);
-        for (int c = 0; c < 3; c++) {
-            const uint16_t *p = d_planes[3 * f + c];
-            if (!p) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is null", f, c);
-            if ((uintptr_t)p & 1u) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is not 2-byte aligned", f, c);
-        }
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    rc = frame_table(ctx, ctx->d_tiff_frames, ctx->d_tiff_cap, ctx->h_tiff_frames, ctx->h_tiff_cap, n_frames);
-    if (rc) return rc;
-    for (int f = 0; f < n_frames; f++) {
-        ctx->h_tiff_frames[f].payload = d_payload[f];
-        for (int c = 0; c < 3; c++) ctx->h_tiff_frames[f].plane[c] = d_planes[3 * f + c];
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_tiff_frames, ctx->h_tiff_frames, (size_t)n_frames * sizeof(tiff_frame), hipMemcpyHostToDevice,
-                                ctx->stream));
-    const tiff_geom g = tiff_geom_of(*info);
-    const uint64_t per_frame = h2y_tiff_chunks(g.width, g.height);
-    rc = timed_launches(ctx, n_frames, "k_tiff_decode", [&](int f0, int nf) {
-        return h2y_launch_tiff_decode(info->swap != 0, clamp_video_range != 0, unit_grid(ctx, per_frame * nf), ctx->stream, g,
-                                      ctx->d_tiff_frames + f0, nf);
-    });
-    if (rc) return rc;
-    ctx->last_variant = std::string("k_tiff_decode<") + (info->swap ? "SWAP" : "NOSWAP") + (clamp_video_range ? ",CLAMP>" : ",NOCLAMP>");
-    return H2Y_OK;
+    return decode_batch(ctx, decode_src(info, clamp_video_range), H2Y_TIFF_FRAMES_PER_LAUNCH, n_frames, d_payload, d_planes);
 }
 
 static int rgb_size_check(h2y_ctx *ctx, int width, int height)
@@ -2564,111 +2530,34 @@ int h2y_rgb_interleave_batch(h2y_ctx *ctx, int width, int height, int n_frames, 
         }
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    rc = frame_table(ctx, ctx->d_rgb_frames, ctx->d_rgb_cap, ctx->h_rgb_frames, ctx->h_rgb_cap, n_frames);
+    rgb_frame *h;
+    rc = frame_table(ctx, n_frames, h);
     if (rc) return rc;
     for (int f = 0; f < n_frames; f++) {
-        for (int c = 0; c < 3; c++) ctx->h_rgb_frames[f].plane[c] = d_planes[3 * f + c];
-        ctx->h_rgb_frames[f].rgb = d_rgb[f];
+        for (int c = 0; c < 3; c++) h[f].plane[c] = d_planes[3 * f + c];
+        h[f].rgb = d_rgb[f];
     }
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_rgb_frames, ctx->h_rgb_frames, (size_t)n_frames * sizeof(rgb_frame), hipMemcpyHostToDevice,
-                                ctx->stream));
     const uint32_t npix = (uint32_t)width * (uint32_t)height;
     const uint64_t per_frame = h2y_rgb_chunks(npix);
-    rc = timed_launches(ctx, n_frames, "k_rgb_interleave", [&](int f0, int nf) {
-        return h2y_launch_rgb_interleave(unit_grid(ctx, per_frame * nf), ctx->stream, npix, ctx->d_rgb_frames + f0, nf);
+    rc = timed_launches(ctx, h, n_frames, H2Y_TIFF_FRAMES_PER_LAUNCH, "k_rgb_interleave", [&](const rgb_frame *frames, int, int nf) {
+        return h2y_launch_rgb_interleave(unit_grid(ctx, per_frame * nf), ctx->stream, npix, frames, nf);
     });
     if (rc) return rc;
     ctx->last_variant = "k_rgb_interleave";
     return H2Y_OK;
 }
 
-/* The forward ring on TIFF rows: as h2y_dpx_stream_open, with the slot's device twin holding three u16 planes (each 256-byte
- * aligned) and then the packed rows; each slot's k_tiff_decode table entry is uploaded here once */
 int h2y_tiff_stream_open(h2y_ctx *ctx, const h2y_desc *d, const h2y_tiff_info *info, int clamp_video_range, int depth)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is already open");
-    int rc = tiff_info_check(ctx, info);
-    if (rc) return rc;
-    if (clamp_video_range != 0 && clamp_video_range != 1) return fail(ctx, H2Y_EINVAL, "clamp_video_range must be 0 or 1");
-    const char *why;
-    rc = h2y_desc_check(d, &why);
-    if (rc) return fail(ctx, rc, "descriptor: %s", why);
-    if (d->in_sample_type != H2Y_SAMPLE_U16 || d->src_bit_depth != 16)
-        return fail(ctx, H2Y_EINVAL, "a TIFF stream decodes to 16-bit planes: in_sample_type must be H2Y_SAMPLE_U16, src_bit_depth 16");
-    if (d->width != info->width || d->height != info->height)
-        return fail(ctx, H2Y_EINVAL, "TIFF picture is %dx%d, the descriptor %dx%d (resizing is not part of convert())", info->width,
-                    info->height, d->width, d->height);
-    if (depth < 2 || depth > 16) return fail(ctx, H2Y_EINVAL, "depth must be 2..16");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    rc = reserve_batch(ctx, 64);
-    if (rc) return rc;
-    rc = ensure(ctx, ctx->d_tiff_frames, ctx->d_tiff_cap, (size_t)depth * sizeof(tiff_frame));
-    if (rc) return rc;
-    const size_t pb = h2y_plane_bytes(d), ob = h2y_frame_bytes(d);
-    ctx->s_plane_al = (pb + 255) & ~(size_t)255;
-    ctx->s_desc = *d;
-    for (int c = 0; c < 3; c++) ctx->s_in_off[c] = c * ctx->s_plane_al;
-    ctx->s_tiff_off = 3 * ctx->s_plane_al;
-    rc = stream_alloc(ctx, depth, info->payload_bytes, ctx->s_tiff_off + info->payload_bytes, ob, ob);
-    if (rc) return rc;
-    std::vector<tiff_frame> tab(depth);
-    for (int k = 0; k < depth; k++) {
-        tab[k].payload = ctx->ss[k].d_in + ctx->s_tiff_off;
-        for (int c = 0; c < 3; c++) tab[k].plane[c] = reinterpret_cast<uint16_t *>(ctx->ss[k].d_in + ctx->s_in_off[c]);
-    }
-    hipError_t e = hipMemcpy(ctx->d_tiff_frames, tab.data(), tab.size() * sizeof(tiff_frame), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        stream_free(ctx);
-        return fail(ctx, H2Y_EHIP, "hipMemcpy of the TIFF slot table: %s", hipGetErrorString(e));
-    }
-    ctx->s_tiff = true;
-    ctx->s_tiff_clamp = clamp_video_range != 0;
-    ctx->s_tiff_info = *info;
-    return H2Y_OK;
+    const decode_src src(info, clamp_video_range);
+    return open_forward_ring(ctx, d, &src, depth);
 }
 
-/* The inverse ring with write_tiff's interleave: the slot's device output holds the G, B, R planes (as an inverse stream lays
- * them out) and then, 256-byte aligned, the interleaved samples; only those go down.  Each slot's k_rgb_interleave table entry
- * is uploaded here once. */
 int h2y_tiff_inverse_stream_open(h2y_ctx *ctx, int width, int height, int in_chroma_format_idc, int in_bit_depth, int in_full_range,
                                  int in_matrix_coeffs, int out_bit_depth, int algorithm, int depth)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is already open");
     const inv_params p{width, height, in_chroma_format_idc, in_bit_depth, in_full_range, in_matrix_coeffs, out_bit_depth, algorithm};
-    int rc = inverse_check(ctx, p);
-    if (rc) return rc;
-    if (depth < 2 || depth > 16) return fail(ctx, H2Y_EINVAL, "depth must be 2..16");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    rc = ensure(ctx, ctx->d_rgb_frames, ctx->d_rgb_cap, (size_t)depth * sizeof(rgb_frame));
-    if (rc) return rc;
-    const size_t pb = (size_t)width * height * sizeof(uint16_t), pb_al = (pb + 255) & ~(size_t)255;
-    const size_t cb = in_chroma_format_idc == H2Y_CHROMA_420 ? (size_t)(width >> 1) * (height >> 1) * sizeof(uint16_t) : pb;
-    const size_t cb_al = (cb + 255) & ~(size_t)255;
-    ctx->s_in_off[0] = 0;
-    ctx->s_in_off[1] = pb_al;
-    ctx->s_in_off[2] = pb_al + cb_al;
-    ctx->s_in_bytes = pb_al + cb_al + cb;
-    ctx->s_out_stride = (pb & 15) ? pb_al : pb;
-    ctx->s_rgb_off = (2 * ctx->s_out_stride + pb + 255) & ~(size_t)255;
-    ctx->s_inv = p;
-    rc = stream_alloc(ctx, depth, ctx->s_in_bytes, ctx->s_in_bytes, 3 * pb, ctx->s_rgb_off + 3 * pb);
-    if (rc) return rc;
-    std::vector<rgb_frame> tab(depth);
-    for (int k = 0; k < depth; k++) {
-        char *o = reinterpret_cast<char *>(ctx->ss[k].d_out);
-        for (int c = 0; c < 3; c++) tab[k].plane[c] = reinterpret_cast<const uint16_t *>(o + c * ctx->s_out_stride);
-        tab[k].rgb = reinterpret_cast<uint16_t *>(o + ctx->s_rgb_off);
-    }
-    hipError_t e = hipMemcpy(ctx->d_rgb_frames, tab.data(), tab.size() * sizeof(rgb_frame), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        stream_free(ctx);
-        return fail(ctx, H2Y_EHIP, "hipMemcpy of the TIFF inverse slot table: %s", hipGetErrorString(e));
-    }
-    ctx->s_inverse = true;
-    ctx->s_rgb = true;
-    return H2Y_OK;
+    return open_inverse_ring(ctx, p, true, depth);
 }
 
 /* ---- scanline OpenEXR (read_exr(), exr.cpp:138-255) -------------------------------------------------------------------- */
@@ -2960,82 +2849,90 @@ static exr_geom exr_geom_of(const h2y_exr_info &xi)
     return g;
 }
 
+/* decode_src's EXR launch and variant: k_exr_decode on n frames of a table */
+static hipError_t exr_decode(const h2y_ctx *ctx, const h2y_exr_info &xi, const payload_frame *frames, int n)
+{
+    return h2y_launch_exr_decode(unit_grid(ctx, (uint64_t)xi.n_chunks * n), ctx->stream, exr_geom_of(xi), frames, n);
+}
+
+static std::string exr_variant(const h2y_exr_info &xi)
+{
+    static const char *const kComp[] = {"NONE", "RLE", "ZIPS", "ZIP"};
+    return std::string("k_exr_decode<") + kComp[xi.compression] + (xi.all_half ? ",ALL_HALF>" : ",GENERAL>");
+}
+
 int h2y_exr_decode_batch(h2y_ctx *ctx, const h2y_exr_info *info, int n_frames, const void *const *d_payload, uint16_t *const *d_planes)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
-    if (const char *w = exr_info_check(info)) return fail(ctx, H2Y_EINVAL, "%s", w);
-    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
-    if (!d_payload || !d_planes) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
-    for (int f = 0; f < n_frames; f++) {
-        if (!d_payload[f]) return fail(ctx, H2Y_EINVAL, "frame %d: payload is null", f);
-        if ((uintptr_t)d_payload[f] & 1u) return fail(ctx, H2Y_EINVAL, "frame %d: payload is not 2-byte aligned", f);
-        for (int c = 0; c < 3; c++) {
-            const uint16_t *p = d_planes[3 * f + c];
-            if (!p) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is null", f, c);
-            if ((uintptr_t)p & 1u) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is not 2-byte aligned", f, c);
-        }
+    return decode_batch(ctx, decode_src(info), H2Y_EXR_FRAMES_PER_LAUNCH, n_frames, d_payload, d_planes);
+}
+
+int h2y_exr_stream_open(h2y_ctx *ctx, const h2y_desc *d, const h2y_exr_info *info, int depth)
+{
+    const decode_src src(info);
+    return open_forward_ring(ctx, d, &src, depth);
+}
+
+/* ---- decode_src: each format's facts, for the decode batches and the forward rings ------------------------------------- */
+
+int decode_src::check(h2y_ctx *ctx) const
+{
+    switch (kind) {
+    case DPX: return dpx_info_check(ctx, has_info ? &dpx : nullptr);
+    case TIFF: return tiff_info_check(ctx, has_info ? &tiff : nullptr, clamp);
+    case EXR:
+        if (const char *w = exr_info_check(has_info ? &exr : nullptr)) return fail(ctx, H2Y_EINVAL, "%s", w);
+        return H2Y_OK;
+    default: return H2Y_OK;
     }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = frame_table(ctx, ctx->d_exr_frames, ctx->d_exr_cap, ctx->h_exr_frames, ctx->h_exr_cap, n_frames);
-    if (rc) return rc;
-    for (int f = 0; f < n_frames; f++) {
-        ctx->h_exr_frames[f].payload = d_payload[f];
-        for (int c = 0; c < 3; c++) ctx->h_exr_frames[f].plane[c] = d_planes[3 * f + c];
+}
+
+int decode_src::planes_check(h2y_ctx *ctx, const h2y_desc *d) const
+{
+    const char *what;
+    int w, h;
+    switch (kind) {
+    case DPX:
+        if (d->in_sample_type != H2Y_SAMPLE_F32) return fail(ctx, H2Y_EINVAL, "a DPX stream decodes to F32 planes: in_sample_type must be H2Y_SAMPLE_F32");
+        what = "DPX picture", w = dpx.width, h = dpx.height;
+        break;
+    case TIFF:
+        if (d->in_sample_type != H2Y_SAMPLE_U16 || d->src_bit_depth != 16)
+            return fail(ctx, H2Y_EINVAL, "a TIFF stream decodes to 16-bit planes: in_sample_type must be H2Y_SAMPLE_U16, src_bit_depth 16");
+        what = "TIFF picture", w = tiff.width, h = tiff.height;
+        break;
+    case EXR:
+        if (d->in_sample_type != H2Y_SAMPLE_F16) return fail(ctx, H2Y_EINVAL, "an EXR stream decodes to half planes: in_sample_type must be H2Y_SAMPLE_F16");
+        what = "EXR data window", w = exr.width, h = exr.height;
+        break;
+    default: return H2Y_OK;
     }
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_exr_frames, ctx->h_exr_frames, (size_t)n_frames * sizeof(exr_frame), hipMemcpyHostToDevice,
-                                ctx->stream));
-    const exr_geom g = exr_geom_of(*info);
-    static_assert(H2Y_EXR_FRAMES_PER_LAUNCH == H2Y_TIFF_FRAMES_PER_LAUNCH, "timed_launches splits by H2Y_TIFF_FRAMES_PER_LAUNCH");
-    rc = timed_launches(ctx, n_frames, "k_exr_decode", [&](int f0, int nf) {
-        return h2y_launch_exr_decode(unit_grid(ctx, (uint64_t)info->n_chunks * nf), ctx->stream, g, ctx->d_exr_frames + f0, nf);
-    });
-    if (rc) return rc;
-    static const char *const kComp[] = {"NONE", "RLE", "ZIPS", "ZIP"};
-    ctx->last_variant = std::string("k_exr_decode<") + kComp[info->compression] + (info->all_half ? ",ALL_HALF>" : ",GENERAL>");
+    if (d->width != w || d->height != h)
+        return fail(ctx, H2Y_EINVAL, "%s is %dx%d, the descriptor %dx%d (resizing is not part of convert())", what, w, h, d->width, d->height);
     return H2Y_OK;
 }
 
-/* The forward ring on EXR payloads: as h2y_tiff_stream_open, with half planes; each slot's k_exr_decode table entry is uploaded
- * here once */
-int h2y_exr_stream_open(h2y_ctx *ctx, const h2y_desc *d, const h2y_exr_info *info, int depth)
+uint64_t decode_src::payload_bytes() const
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is already open");
-    if (const char *w = exr_info_check(info)) return fail(ctx, H2Y_EINVAL, "%s", w);
-    const char *why;
-    int rc = h2y_desc_check(d, &why);
-    if (rc) return fail(ctx, rc, "descriptor: %s", why);
-    if (d->in_sample_type != H2Y_SAMPLE_F16) return fail(ctx, H2Y_EINVAL, "an EXR stream decodes to half planes: in_sample_type must be H2Y_SAMPLE_F16");
-    if (d->width != info->width || d->height != info->height)
-        return fail(ctx, H2Y_EINVAL, "EXR data window is %dx%d, the descriptor %dx%d (resizing is not part of convert())", info->width,
-                    info->height, d->width, d->height);
-    if (depth < 2 || depth > 16) return fail(ctx, H2Y_EINVAL, "depth must be 2..16");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    rc = reserve_batch(ctx, 64);
-    if (rc) return rc;
-    rc = ensure(ctx, ctx->d_exr_frames, ctx->d_exr_cap, (size_t)depth * sizeof(exr_frame));
-    if (rc) return rc;
-    const size_t pb = h2y_plane_bytes(d), ob = h2y_frame_bytes(d);
-    ctx->s_plane_al = (pb + 255) & ~(size_t)255;
-    ctx->s_desc = *d;
-    for (int c = 0; c < 3; c++) ctx->s_in_off[c] = c * ctx->s_plane_al;
-    ctx->s_exr_off = 3 * ctx->s_plane_al;
-    rc = stream_alloc(ctx, depth, info->payload_bytes, ctx->s_exr_off + info->payload_bytes, ob, ob);
-    if (rc) return rc;
-    std::vector<exr_frame> tab(depth);
-    for (int k = 0; k < depth; k++) {
-        tab[k].payload = ctx->ss[k].d_in + ctx->s_exr_off;
-        for (int c = 0; c < 3; c++) tab[k].plane[c] = reinterpret_cast<uint16_t *>(ctx->ss[k].d_in + ctx->s_in_off[c]);
+    return kind == DPX ? dpx.payload_bytes : kind == TIFF ? tiff.payload_bytes : kind == EXR ? exr.payload_bytes : 0;
+}
+
+uintptr_t decode_src::align() const { return kind == DPX ? 4 : 2; } /* DPX: 32-bit words and float planes; u16 / half elsewhere */
+
+hipError_t decode_src::launch(const h2y_ctx *ctx, const payload_frame *frames, int n) const
+{
+    switch (kind) {
+    case DPX: return dpx_decode(ctx, dpx, frames, n);
+    case TIFF: return tiff_decode(ctx, tiff, clamp != 0, frames, n);
+    case EXR: return exr_decode(ctx, exr, frames, n);
+    default: return hipErrorInvalidValue;
     }
-    hipError_t e = hipMemcpy(ctx->d_exr_frames, tab.data(), tab.size() * sizeof(exr_frame), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        stream_free(ctx);
-        return fail(ctx, H2Y_EHIP, "hipMemcpy of the EXR slot table: %s", hipGetErrorString(e));
-    }
-    ctx->s_exr = true;
-    ctx->s_exr_info = *info;
-    return H2Y_OK;
+}
+
+const char *decode_src::kernel() const { return kind == DPX ? "k_dpx_decode" : kind == TIFF ? "k_tiff_decode" : kind == EXR ? "k_exr_decode" : ""; }
+
+std::string decode_src::variant() const
+{
+    return kind == DPX ? dpx_variant(dpx) : kind == TIFF ? tiff_variant(tiff, clamp != 0) : kind == EXR ? exr_variant(exr) : std::string();
 }
 
 /* ---- comparison with a reference (--ref_filename, hdr2yuv.cpp:91-100, :827-833) ---------------------------------------- */
@@ -3091,7 +2988,6 @@ static int cmp_grid(const h2y_ctx *ctx, const cmp_geom &g, int n_frames)
 int h2y_compare_batch(h2y_ctx *ctx, int width, int height, int chroma_format_idc, int sigma, int n_frames, const uint16_t *const *d_a,
                       const uint16_t *const *d_b, h2y_compare_stats *out)
 {
-    static_assert(H2Y_COMPARE_FRAMES_PER_LAUNCH == H2Y_TIFF_FRAMES_PER_LAUNCH, "timed_launches deals launches of this many frames");
     if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
     if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
     int rc = cmp_check(ctx, width, height, chroma_format_idc, sigma);
@@ -3107,14 +3003,14 @@ int h2y_compare_batch(h2y_ctx *ctx, int width, int height, int chroma_format_idc
     cmp_contiguous(width, height, chroma_format_idc, off);
     const cmp_geom g = cmp_geom_of(width, height, chroma_format_idc, sigma, off, off);
     const int per_launch = std::min(n_frames, H2Y_COMPARE_FRAMES_PER_LAUNCH);
-    rc = frame_table(ctx, ctx->d_cmp_frames, ctx->d_cmp_cap, ctx->h_cmp_frames, ctx->h_cmp_cap, n_frames);
+    cmp_frame *h;
+    rc = frame_table(ctx, n_frames, h);
     if (!rc) rc = cmp_partials(ctx, g, per_launch);
     if (!rc) rc = ensure(ctx, ctx->d_cmp_stats, ctx->cmp_stats_cap, (size_t)n_frames * sizeof(h2y_compare_stats));
     if (rc) return rc;
-    for (int f = 0; f < n_frames; f++) ctx->h_cmp_frames[f] = cmp_frame{d_a[f], d_b[f]};
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_cmp_frames, ctx->h_cmp_frames, (size_t)n_frames * sizeof(cmp_frame), hipMemcpyHostToDevice, ctx->stream));
-    rc = timed_launches(ctx, n_frames, "k_compare", [&](int f0, int nf) {
-        return h2y_launch_compare(cmp_grid(ctx, g, nf), ctx->stream, g, ctx->d_cmp_frames + f0, nf, ctx->d_cmp_part, ctx->d_cmp_stats + f0);
+    for (int f = 0; f < n_frames; f++) h[f] = cmp_frame{d_a[f], d_b[f]};
+    rc = timed_launches(ctx, h, n_frames, H2Y_COMPARE_FRAMES_PER_LAUNCH, "k_compare", [&](const cmp_frame *frames, int f0, int nf) {
+        return h2y_launch_compare(cmp_grid(ctx, g, nf), ctx->stream, g, frames, nf, ctx->d_cmp_part, ctx->d_cmp_stats + f0);
     });
     if (rc) return rc;
     HIP_TRY(ctx, hipMemcpy(out, ctx->d_cmp_stats, (size_t)n_frames * sizeof(h2y_compare_stats), hipMemcpyDeviceToHost));
@@ -3136,20 +3032,19 @@ static int cmp_arm(h2y_ctx *ctx, int width, int height, int chroma, const uint32
     const size_t ref_bytes = ((size_t)g.n[0] + g.n[1] + g.n[2]) * sizeof(uint16_t);
     const size_t dev_al = (((size_t)a_off[2] + g.n[2]) * sizeof(uint16_t) + 255) & ~(size_t)255;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    rc = ensure(ctx, ctx->d_cmp_frames, ctx->d_cmp_cap, (size_t)depth * sizeof(cmp_frame));
-    if (!rc) rc = cmp_partials(ctx, g, 1);
+    rc = cmp_partials(ctx, g, 1);
     if (rc) return rc;
     std::vector<cmp_frame> tab(depth);
-    hipError_t e = hipSuccess;
+    hipError_t e = hipMalloc((void **)&ctx->s_cmp_tab, tab.size() * sizeof(cmp_frame));
     for (int k = 0; k < depth && e == hipSuccess; k++) {
         h2y_ctx::stream_slot &s = ctx->ss[k];
         e = hipHostMalloc((void **)&s.h_ref, ref_bytes, hipHostMallocDefault);
         if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_stats, sizeof(h2y_compare_stats), hipHostMallocDefault);
         if (e == hipSuccess) e = hipMalloc((void **)&s.d_ref, dev_al + sizeof(h2y_compare_stats));
-        tab[k].a = reinterpret_cast<const uint16_t *>(ctx->s_cmp_only ? (char *)s.d_in : (char *)s.d_out);
+        tab[k].a = reinterpret_cast<const uint16_t *>(ctx->s_kind == h2y_ctx::RING_COMPARE ? (char *)s.d_in : (char *)s.d_out);
         tab[k].b = reinterpret_cast<const uint16_t *>(s.d_ref);
     }
-    if (e == hipSuccess) e = hipMemcpy(ctx->d_cmp_frames, tab.data(), tab.size() * sizeof(cmp_frame), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(ctx->s_cmp_tab, tab.data(), tab.size() * sizeof(cmp_frame), hipMemcpyHostToDevice);
     if (e != hipSuccess) { /* the ring stays open, unarmed */
         for (auto &s : ctx->ss) {
             if (s.h_ref) (void)hipHostFree(s.h_ref);
@@ -3158,6 +3053,8 @@ static int cmp_arm(h2y_ctx *ctx, int width, int height, int chroma, const uint32
             s.h_ref = s.d_ref = nullptr;
             s.h_stats = nullptr;
         }
+        if (ctx->s_cmp_tab) (void)hipFree(ctx->s_cmp_tab);
+        ctx->s_cmp_tab = nullptr;
         return fail(ctx, H2Y_ENOMEM, "compare buffers: %s", hipGetErrorString(e));
     }
     ctx->s_cmp_geom = g;
@@ -3176,7 +3073,7 @@ int h2y_stream_compare(h2y_ctx *ctx, int sigma, int keep_output)
     if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
     if (keep_output != 0 && keep_output != 1) return fail(ctx, H2Y_EINVAL, "keep_output must be 0 or 1");
     uint32_t a_off[3];
-    if (ctx->s_inverse) { /* the G, B, R planes the inverse kernel writes, s_out_stride bytes apart */
+    if (ctx->s_kind == h2y_ctx::RING_INVERSE) { /* the G, B, R planes the inverse kernel writes, s_out_stride bytes apart */
         for (int c = 0; c < 3; c++) a_off[c] = (uint32_t)(c * ctx->s_out_stride / sizeof(uint16_t));
         return cmp_arm(ctx, ctx->s_inv.width, ctx->s_inv.height, H2Y_CHROMA_444, a_off, sigma, keep_output);
     }
@@ -3221,7 +3118,7 @@ int h2y_compare_stream_open(h2y_ctx *ctx, int width, int height, int chroma_form
     ctx->s_in_bytes = ((size_t)off[2] + (off[2] - off[1])) * sizeof(uint16_t); /* the last plane is as long as the second */
     rc = stream_alloc(ctx, depth, ctx->s_in_bytes, ctx->s_in_bytes, 16, 16);
     if (rc) return rc;
-    ctx->s_cmp_only = true;
+    ctx->s_kind = h2y_ctx::RING_COMPARE;
     rc = cmp_arm(ctx, width, height, chroma_format_idc, off, sigma, 0);
     if (rc) {
         stream_free(ctx);
@@ -3254,7 +3151,7 @@ static h2y_compare_stats *cmp_dev_stats(const h2y_ctx *ctx, const h2y_ctx::strea
 static int cmp_run(h2y_ctx *ctx, int slot)
 {
     const cmp_geom &g = ctx->s_cmp_geom;
-    HIP_TRY(ctx, h2y_launch_compare(cmp_grid(ctx, g, 1), ctx->stream, g, ctx->d_cmp_frames + slot, 1, ctx->d_cmp_part, cmp_dev_stats(ctx, ctx->ss[slot])));
+    HIP_TRY(ctx, h2y_launch_compare(cmp_grid(ctx, g, 1), ctx->stream, g, ctx->s_cmp_tab + slot, 1, ctx->d_cmp_part, cmp_dev_stats(ctx, ctx->ss[slot])));
     return H2Y_OK;
 }
 
@@ -3316,9 +3213,10 @@ static int inverse_stream_submit(h2y_ctx *ctx, int slot)
         HIP_TRY(ctx, h2y_launch_inverse((int)blocks, ctx->stream, a.inv));
     }
     const bool keep = !ctx->s_cmp || ctx->s_cmp_keep;
-    if (ctx->s_rgb && keep) { /* write_tiff's interleave into the slot's device output behind the planes */
+    if (ctx->s_interleave && keep) { /* write_tiff's interleave into the slot's device output behind the planes */
         const uint32_t npix = (uint32_t)p.width * (uint32_t)p.height;
-        HIP_TRY(ctx, h2y_launch_rgb_interleave(unit_grid(ctx, h2y_rgb_chunks(npix)), ctx->stream, npix, ctx->d_rgb_frames + slot, 1));
+        HIP_TRY(ctx, h2y_launch_rgb_interleave(unit_grid(ctx, h2y_rgb_chunks(npix)), ctx->stream, npix,
+                                               static_cast<const rgb_frame *>(ctx->s_tab) + slot, 1));
     }
     if (ctx->s_cmp) { /* on the G, B, R planes (before the interleave) */
         rc = cmp_run(ctx, slot);
@@ -3327,8 +3225,8 @@ static int inverse_stream_submit(h2y_ctx *ctx, int slot)
     HIP_TRY(ctx, hipEventRecord(s.ev_conv, ctx->stream));
     HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_d2h, s.ev_conv, 0));
     if (!keep) {
-    } else if (ctx->s_rgb)
-        HIP_TRY(ctx, hipMemcpyAsync(s.h_out, reinterpret_cast<char *>(s.d_out) + ctx->s_rgb_off, 3 * pb, hipMemcpyDeviceToHost, ctx->s_d2h));
+    } else if (ctx->s_interleave)
+        HIP_TRY(ctx, hipMemcpyAsync(s.h_out, reinterpret_cast<char *>(s.d_out) + ctx->s_pay_off, 3 * pb, hipMemcpyDeviceToHost, ctx->s_d2h));
     else if (so == pb) HIP_TRY(ctx, hipMemcpyAsync(s.h_out, s.d_out, 3 * pb, hipMemcpyDeviceToHost, ctx->s_d2h));
     else
         for (int c = 0; c < 3; c++)
@@ -3353,7 +3251,7 @@ int h2y_stream_input(h2y_ctx *ctx, void *planes[3])
     } else if (s.state != 0) return fail(ctx, H2Y_EINVAL, "all %d slots are in flight: take an output first", (int)ctx->ss.size());
     s.state = 1;
     ctx->s_started = true;
-    if (ctx->s_dpx || ctx->s_tiff || ctx->s_exr) { /* the payload, as the file holds it (TIFF: the decoded rows, packed; EXR: unpacked) */
+    if (ctx->s_src.kind != decode_src::NONE) { /* the payload, as the file holds it (TIFF: the decoded rows, packed; EXR: unpacked) */
         planes[0] = s.h_in;
         planes[1] = planes[2] = nullptr;
         return H2Y_OK;
@@ -3372,17 +3270,14 @@ int h2y_stream_submit(h2y_ctx *ctx)
     if (ctx->s_cmp && !s.ref_lent) return fail(ctx, H2Y_EINVAL, "the ring is armed: h2y_stream_reference before each submit");
     const h2y_desc *d = &ctx->s_desc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (ctx->s_cmp_only) return compare_stream_submit(ctx, slot);
-    if (ctx->s_inverse) return inverse_stream_submit(ctx, slot);
+    if (ctx->s_kind == h2y_ctx::RING_COMPARE) return compare_stream_submit(ctx, slot);
+    if (ctx->s_kind == h2y_ctx::RING_INVERSE) return inverse_stream_submit(ctx, slot);
+    const decode_src &src = ctx->s_src;
     const size_t pb = h2y_plane_bytes(d), ob = h2y_frame_bytes(d);
     frame_io io;
     for (int c = 0; c < 3; c++) io.in[c] = s.d_in + c * ctx->s_plane_al;
-    if (ctx->s_dpx) /* the payload goes up; k_dpx_decode writes the three planes below */
-        HIP_TRY(ctx, hipMemcpyAsync(s.d_in + ctx->s_dpx_off, s.h_in, ctx->s_dpx_info.payload_bytes, hipMemcpyHostToDevice, ctx->s_h2d));
-    else if (ctx->s_tiff) /* likewise the rows for k_tiff_decode */
-        HIP_TRY(ctx, hipMemcpyAsync(s.d_in + ctx->s_tiff_off, s.h_in, ctx->s_tiff_info.payload_bytes, hipMemcpyHostToDevice, ctx->s_h2d));
-    else if (ctx->s_exr) /* likewise the unpacked chunks for k_exr_decode */
-        HIP_TRY(ctx, hipMemcpyAsync(s.d_in + ctx->s_exr_off, s.h_in, ctx->s_exr_info.payload_bytes, hipMemcpyHostToDevice, ctx->s_h2d));
+    if (src.kind != decode_src::NONE) /* the payload goes up; the decode writes the three planes below it */
+        HIP_TRY(ctx, hipMemcpyAsync(s.d_in + ctx->s_pay_off, s.h_in, src.payload_bytes(), hipMemcpyHostToDevice, ctx->s_h2d));
     else /* the slot's three planes lie one after the other (each padded to 256 bytes): one copy command, not three */
         HIP_TRY(ctx, hipMemcpyAsync(s.d_in, s.h_in, 2 * ctx->s_plane_al + pb, hipMemcpyHostToDevice, ctx->s_h2d));
     if (ctx->s_cmp) {
@@ -3393,21 +3288,7 @@ int h2y_stream_submit(h2y_ctx *ctx)
     io.tmp_cb = io.tmp_cr = nullptr;
     HIP_TRY(ctx, hipEventRecord(s.ev_h2d, ctx->s_h2d));
     HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s.ev_h2d, 0));
-    if (ctx->s_dpx) {
-        const h2y_dpx_info &di = ctx->s_dpx_info;
-        HIP_TRY(ctx, h2y_launch_dpx_decode(dpx_fmt_of(di.bit_size), di.swap != 0, dpx_grid(ctx, di, 1), ctx->stream,
-                                           (uint32_t)di.width * (uint32_t)di.height, ctx->d_dpx_frames + slot, 1));
-    }
-    if (ctx->s_tiff) {
-        const h2y_tiff_info &ti = ctx->s_tiff_info;
-        const tiff_geom g = tiff_geom_of(ti);
-        HIP_TRY(ctx, h2y_launch_tiff_decode(ti.swap != 0, ctx->s_tiff_clamp, unit_grid(ctx, h2y_tiff_chunks(g.width, g.height)), ctx->stream,
-                                            g, ctx->d_tiff_frames + slot, 1));
-    }
-    if (ctx->s_exr) {
-        const h2y_exr_info &xi = ctx->s_exr_info;
-        HIP_TRY(ctx, h2y_launch_exr_decode(unit_grid(ctx, (uint64_t)xi.n_chunks), ctx->stream, exr_geom_of(xi), ctx->d_exr_frames + slot, 1));
-    }
+    if (src.kind != decode_src::NONE) HIP_TRY(ctx, src.launch(ctx, static_cast<const payload_frame *>(ctx->s_tab) + slot, 1));
     const bool needs_stats = d->src_transfer != d->dst_transfer;
     int rc;
     if (needs_stats && !d->stats_override) {

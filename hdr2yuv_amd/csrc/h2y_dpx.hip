@@ -131,14 +131,14 @@ __device__ __forceinline__ void decode_one(gchar_c *__restrict__ pay, gu32 *__re
  * frame is block-uniform: its payload and plane pointers are scalar loads from the table (__restrict__ const: nothing the
  * kernel stores can alias it).  Payload and planes need only be 4-byte aligned; the 16-byte accesses are taken per frame. */
 template <int FMT, bool SWAP>
-__global__ __launch_bounds__(256) void k_dpx_decode(uint32_t npix, const dpx_frame *__restrict__ frames, int n_frames)
+__global__ __launch_bounds__(256) void k_dpx_decode(uint32_t npix, const payload_frame *__restrict__ frames, int n_frames)
 {
     constexpr uint32_t P = dpx_group<FMT>();
     const uint32_t groups = npix / P, tail = npix - groups * P;
     const uint32_t chunks = (groups + tail + 255) / 256, units = (uint32_t)n_frames * chunks;
     for (uint32_t unit = blockIdx.x; unit < units; unit += gridDim.x) {
         const uint32_t f = unit / chunks, i = (unit - f * chunks) * 256 + threadIdx.x;
-        const dpx_frame fr = frames[f];
+        const payload_frame fr = frames[f];
         gchar_c *pay = (gchar_c *)fr.payload;
         gu32 *pg = (gu32 *)fr.plane[0], *pb = (gu32 *)fr.plane[1], *pr = (gu32 *)fr.plane[2];
         const bool vec16 = (((uintptr_t)pay | (uintptr_t)pg | (uintptr_t)pb | (uintptr_t)pr) & 15u) == 0;
@@ -149,7 +149,7 @@ __global__ __launch_bounds__(256) void k_dpx_decode(uint32_t npix, const dpx_fra
 
 namespace {
 
-template <int FMT> void launch_fmt(bool swap, int grid, hipStream_t st, uint32_t npix, const dpx_frame *frames, int n_frames)
+template <int FMT> void launch_fmt(bool swap, int grid, hipStream_t st, uint32_t npix, const payload_frame *frames, int n_frames)
 {
     if (swap) hipLaunchKernelGGL((k_dpx_decode<FMT, true>), dim3(grid), dim3(256), 0, st, npix, frames, n_frames);
     else hipLaunchKernelGGL((k_dpx_decode<FMT, false>), dim3(grid), dim3(256), 0, st, npix, frames, n_frames);
@@ -163,7 +163,7 @@ uint32_t h2y_dpx_chunks(int fmt, uint32_t npix)
     return (groups + (npix - groups * p) + 255) / 256;
 }
 
-hipError_t h2y_launch_dpx_decode(int fmt, bool swap, int grid, hipStream_t st, uint32_t npix, const dpx_frame *frames, int n_frames)
+hipError_t h2y_launch_dpx_decode(int fmt, bool swap, int grid, hipStream_t st, uint32_t npix, const payload_frame *frames, int n_frames)
 {
     switch (fmt) {
     case H2Y_DPX_10: launch_fmt<H2Y_DPX_10>(swap, grid, st, npix, frames, n_frames); break;

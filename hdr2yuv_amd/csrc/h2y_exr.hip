@@ -76,7 +76,7 @@ __device__ __forceinline__ int locate(const exr_geom &g, uint32_t row0, uint32_t
     return -1;
 }
 
-__device__ __forceinline__ void emit(const exr_geom &g, const exr_frame &fr, int c, uint32_t idx, bool hi, uint32_t cur, uint32_t prev)
+__device__ __forceinline__ void emit(const exr_geom &g, const payload_frame &fr, int c, uint32_t idx, bool hi, uint32_t cur, uint32_t prev)
 {
     uint32_t v = cur;
     if (hi) v = g.type[c] == 2 ? float_to_half(prev | cur << 16) : uint_to_half(prev | cur << 16);
@@ -127,7 +127,7 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *part, 
 
 /* 8 half words from word g of an all-half chunk into their plane with one 16-byte store, if their channel is read (the 8
  * lie in one channel's run of a line: g and width are multiples of 8) */
-__device__ __forceinline__ void store8(const exr_geom &g, const exr_frame &fr, uint32_t row0, uint32_t gw, const uint32_t v[4])
+__device__ __forceinline__ void store8(const exr_geom &g, const payload_frame &fr, uint32_t row0, uint32_t gw, const uint32_t v[4])
 {
     const uint32_t seg = gw / g.width, line = seg / g.n_channels, k = seg - line * g.n_channels, x = gw - seg * g.width;
     for (int c = 0; c < 3; c++)
@@ -148,7 +148,7 @@ __device__ __forceinline__ void store8(const exr_geom &g, const exr_frame &fr, u
  *            word is assembled once and goes to its plane (directly on the all-half fast path, else through an LDS tile so
  *            that a 4-byte sample split between two threads is whole)
  * Missing channels: the unit zeroes its lines of that plane. */
-__global__ __launch_bounds__(256) void k_exr_decode(exr_geom g, const exr_frame *__restrict__ frames, int n_frames)
+__global__ __launch_bounds__(256) void k_exr_decode(exr_geom g, const payload_frame *__restrict__ frames, int n_frames)
 {
     __shared__ uint32_t s_part[2][kWaves];
     __shared__ uint16_t s_words[1 + kTile];
@@ -156,7 +156,7 @@ __global__ __launch_bounds__(256) void k_exr_decode(exr_geom g, const exr_frame 
     const uint32_t tid = threadIdx.x;
     for (uint32_t unit = blockIdx.x; unit < units; unit += gridDim.x) {
         const uint32_t f = __builtin_amdgcn_readfirstlane(unit / g.n_chunks), c = unit - f * g.n_chunks;
-        const exr_frame fr = frames[f];
+        const payload_frame fr = frames[f];
         gbyte_c *pay = (gbyte_c *)fr.payload;
         const uint32_t row0 = c * g.lines_per_chunk;
         const uint32_t lines = g.height - row0 < g.lines_per_chunk ? g.height - row0 : g.lines_per_chunk;
@@ -249,7 +249,7 @@ __global__ __launch_bounds__(256) void k_exr_decode(exr_geom g, const exr_frame 
     }
 }
 
-hipError_t h2y_launch_exr_decode(int grid, hipStream_t st, const exr_geom &g, const exr_frame *frames, int n_frames)
+hipError_t h2y_launch_exr_decode(int grid, hipStream_t st, const exr_geom &g, const payload_frame *frames, int n_frames)
 {
     hipLaunchKernelGGL(k_exr_decode, dim3(grid), dim3(256), 0, st, g, frames, n_frames);
     return hipGetLastError();

@@ -235,24 +235,22 @@ hipError_t h2y_launch_yuvp2_420(bool fir, hipStream_t st, const yuvp2_args &a);
 void h2y_yuvp2_lin_table(uint16_t *lin); /* host: the 65 536 entries of yuvp2_args.lin */
 hipError_t h2y_launch_box420(hipStream_t st, const uint16_t *src, uint16_t *dst, int W, int H);
 
-/* k_dpx_decode (h2y_dpx.hip): dpx_read()'s per-pixel loop on the device */
-enum { H2Y_DPX_10 = 0, H2Y_DPX_16 = 1, H2Y_DPX_F32 = 2 };
-/* one frame: its interleaved R,G,B payload in, the planes G, B, R out (muxed_dpx_to_planar_float_buf's order) */
-struct dpx_frame {
+/* one frame of a decode kernel (k_dpx_decode, k_tiff_decode, k_exr_decode): its payload in, the planes G, B, R out, each
+ * plane of the kernel's own element type (DPX float, TIFF u16, EXR half) */
+struct payload_frame {
     const void *payload;
-    float *plane[3];
+    void *plane[3];
 };
+
+/* k_dpx_decode (h2y_dpx.hip): dpx_read()'s per-pixel loop on the device; the payload is interleaved R,G,B, the planes come out in
+ * muxed_dpx_to_planar_float_buf's order */
+enum { H2Y_DPX_10 = 0, H2Y_DPX_16 = 1, H2Y_DPX_F32 = 2 };
 uint32_t h2y_dpx_chunks(int fmt, uint32_t npix); /* k_dpx_decode's units of 256 threads per frame */
-hipError_t h2y_launch_dpx_decode(int fmt, bool swap, int grid, hipStream_t st, uint32_t npix, const dpx_frame *frames, int n_frames);
+hipError_t h2y_launch_dpx_decode(int fmt, bool swap, int grid, hipStream_t st, uint32_t npix, const payload_frame *frames, int n_frames);
 
 /* k_tiff_decode and k_rgb_interleave (h2y_tiff.hip): read_tiff()'s and write_tiff()'s per-pixel work on the device */
 struct tiff_geom { /* the decoded picture within `height` packed rows of row_bytes */
     uint32_t width, height, x0, row_bytes;
-};
-/* one frame: its packed rows of interleaved R,G,B u16 in, the planes G, B, R out */
-struct tiff_frame {
-    const void *payload;
-    uint16_t *plane[3];
 };
 /* one frame: planes G, B, R in, interleaved R,G,B u16 out */
 struct rgb_frame {
@@ -261,7 +259,8 @@ struct rgb_frame {
 };
 uint32_t h2y_tiff_chunks(uint32_t width, uint32_t height); /* k_tiff_decode's units of 256 threads per frame */
 uint32_t h2y_rgb_chunks(uint32_t npix);                    /* k_rgb_interleave's */
-hipError_t h2y_launch_tiff_decode(bool swap, bool clamp, int grid, hipStream_t st, const tiff_geom &g, const tiff_frame *frames, int n_frames);
+/* k_tiff_decode's payload: packed rows of interleaved R,G,B u16 */
+hipError_t h2y_launch_tiff_decode(bool swap, bool clamp, int grid, hipStream_t st, const tiff_geom &g, const payload_frame *frames, int n_frames);
 hipError_t h2y_launch_rgb_interleave(int grid, hipStream_t st, uint32_t npix, const rgb_frame *frames, int n_frames);
 
 /* k_exr_decode (h2y_exr.hip): read_exr()'s scanline decode on the device, from h2y_exr_unpack's payload */
@@ -269,12 +268,7 @@ struct exr_geom { /* what k_exr_decode takes of an h2y_exr_info */
     uint32_t width, height, lines_per_chunk, n_chunks, n_channels, line_bytes, flags_bytes, all_half;
     int32_t type[3], offset[3]; /* planes G, B, R: H2Y_EXR_* pixel type (-1 missing), byte offset within a line */
 };
-/* one frame: its payload in, the half planes G, B, R out */
-struct exr_frame {
-    const void *payload;
-    uint16_t *plane[3];
-};
-hipError_t h2y_launch_exr_decode(int grid, hipStream_t st, const exr_geom &g, const exr_frame *frames, int n_frames);
+hipError_t h2y_launch_exr_decode(int grid, hipStream_t st, const exr_geom &g, const payload_frame *frames, int n_frames);
 
 /* k_compare and k_compare_sum (h2y_compare.hip): two frames of u16 planes reduced per plane to exact integer stats */
 struct cmp_geom {

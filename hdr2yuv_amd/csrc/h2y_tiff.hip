@@ -39,13 +39,13 @@ template <bool SWAP, bool CLAMP> __device__ __forceinline__ uint32_t sample(uint
  * where the frame's payload, row_bytes and 6 x0 are multiples of 16 (every group's 48 bytes then start on a 16-byte boundary),
  * and one 16-byte store per plane where the planes and the plane row (2 x width) are; u16 accesses elsewhere. */
 template <bool SWAP, bool CLAMP>
-__global__ __launch_bounds__(256) void k_tiff_decode(tiff_geom g, const tiff_frame *__restrict__ frames, int n_frames)
+__global__ __launch_bounds__(256) void k_tiff_decode(tiff_geom g, const payload_frame *__restrict__ frames, int n_frames)
 {
     const uint32_t gpr = (g.width + 7u) / 8u, groups = gpr * g.height;
     const uint32_t chunks = (groups + 255u) / 256u, units = (uint32_t)n_frames * chunks;
     for (uint32_t unit = blockIdx.x; unit < units; unit += gridDim.x) {
         const uint32_t f = unit / chunks, i = (unit - f * chunks) * 256u + threadIdx.x;
-        const tiff_frame fr = frames[f];
+        const payload_frame fr = frames[f];
         if (i >= groups) continue;
         const uint32_t row = i / gpr, px = (i - row * gpr) * 8u;
         const uint32_t cnt = g.width - px < 8u ? g.width - px : 8u;
@@ -134,7 +134,7 @@ uint32_t h2y_tiff_chunks(uint32_t width, uint32_t height) { return ((width + 7u)
 
 uint32_t h2y_rgb_chunks(uint32_t npix) { return (npix / 8u + npix % 8u + 255u) / 256u; }
 
-hipError_t h2y_launch_tiff_decode(bool swap, bool clamp, int grid, hipStream_t st, const tiff_geom &g, const tiff_frame *frames, int n_frames)
+hipError_t h2y_launch_tiff_decode(bool swap, bool clamp, int grid, hipStream_t st, const tiff_geom &g, const payload_frame *frames, int n_frames)
 {
     if (swap) {
         if (clamp) hipLaunchKernelGGL((k_tiff_decode<true, true>), dim3(grid), dim3(256), 0, st, g, frames, n_frames);
