@@ -16,6 +16,7 @@ from .api import (  # noqa: F401
     H2YError,
     H2YExrChunk,
     H2YExrInfo,
+    H2YHistogramStats,
     H2YTiffInfo,
     MATRIX_BT2020NC,
     MATRIX_BT709,

@@ -34,9 +34,12 @@ EXPORTS = [
     "h2y_tiff_parse", "h2y_tiff_layout", "h2y_tiff_decode_batch", "h2y_rgb_interleave_batch", "h2y_tiff_stream_open",
     "h2y_tiff_inverse_stream_open", "h2y_exr_parse", "h2y_exr_unpack", "h2y_exr_decode_batch", "h2y_exr_stream_open",
     "h2y_compare_batch", "h2y_stream_compare", "h2y_stream_reference", "h2y_stream_compare_result", "h2y_compare_stream_open",
+    "h2y_histogram_batch", "h2y_stream_histogram", "h2y_stream_histogram_ex", "h2y_stream_histogram_result",
+    "h2y_histogram_stream_open",
 ]
 
 COMPARE_FRAMES_PER_LAUNCH = 64
+HISTOGRAM_FRAMES_PER_LAUNCH = 64
 
 
 class H2YError(RuntimeError):
@@ -140,6 +143,23 @@ class H2YCompareStats(C.Structure):
 
     def __repr__(self):
         return f"H2YCompareStats({self.as_dict()})"
+
+
+class H2YHistogramStats(C.Structure):
+    """h2y_histogram_stats: per plane (0, 1, 2 = Y, Cb, Cr or G, B, R) the samples counted, those below, above and at the limits
+    lo and hi of the legal range, the smallest and largest sample; nbins = 2^bits and shift = bit_depth - bits for every plane."""
+
+    _fields_ = [
+        ("samples", C.c_uint64 * 3), ("below", C.c_uint64 * 3), ("above", C.c_uint64 * 3), ("at_low", C.c_uint64 * 3),
+        ("at_high", C.c_uint64 * 3), ("min", C.c_uint32 * 3), ("max", C.c_uint32 * 3), ("lo", C.c_uint32 * 3),
+        ("hi", C.c_uint32 * 3), ("nbins", C.c_uint32), ("shift", C.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {k: (list(v) if not isinstance(v := getattr(self, k), int) else v) for k, _ in self._fields_}
+
+    def __repr__(self):
+        return f"H2YHistogramStats({self.as_dict()})"
 
 
 def make_desc(width, height, *, sample=SAMPLE_F32, src_depth=32, dst_depth=10, src_transfer=TRANSFER_LINEAR,
@@ -306,6 +326,16 @@ def load_library():
     L.h2y_stream_compare_result.restype = C.c_int
     L.h2y_compare_stream_open.argtypes = [C.c_void_p] + [C.c_int] * 5
     L.h2y_compare_stream_open.restype = C.c_int
+    L.h2y_histogram_batch.argtypes = [C.c_void_p] + [C.c_int] * 8 + [C.POINTER(C.c_void_p), C.POINTER(H2YHistogramStats), C.c_void_p]
+    L.h2y_histogram_batch.restype = C.c_int
+    L.h2y_stream_histogram.argtypes = [C.c_void_p, C.c_int]
+    L.h2y_stream_histogram.restype = C.c_int
+    L.h2y_stream_histogram_ex.argtypes = [C.c_void_p] + [C.c_int] * 4
+    L.h2y_stream_histogram_ex.restype = C.c_int
+    L.h2y_stream_histogram_result.argtypes = [C.c_void_p, C.POINTER(H2YHistogramStats), C.c_void_p]
+    L.h2y_stream_histogram_result.restype = C.c_int
+    L.h2y_histogram_stream_open.argtypes = [C.c_void_p] + [C.c_int] * 8
+    L.h2y_histogram_stream_open.restype = C.c_int
     L.h2y_stream_open.argtypes = [C.c_void_p, C.POINTER(H2YDesc), C.c_int]
     L.h2y_stream_input.restype = C.c_int
     L.h2y_stream_input.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
@@ -634,7 +664,48 @@ class Context:
         self._check(self.lib.h2y_compare_batch(self.h, width, height, chroma, sigma, n, pa, pb, out))
         return list(out[:n])
 
+    def histogram_batch(self, width, height, chroma, bit_depth, full_range, gbr, bits, frames, want_bins=True):
+        """k_histogram on device frames (tensors or pointers, each frame's planes contiguous from a 16-byte aligned base):
+        a list of H2YHistogramStats and, with want_bins, a uint32 array (n_frames, 3, 2^bits) of the bins (else None)."""
+        import numpy as np
+
+        n = len(frames)
+        pf = (C.c_void_p * max(n, 1))(*[self._ptr(x) for x in frames])
+        out = (H2YHistogramStats * max(n, 1))()
+        bins = np.zeros((n, 3, 1 << bits), dtype=np.uint32) if want_bins and 1 <= bits <= 16 else None
+        self._check(self.lib.h2y_histogram_batch(self.h, width, height, chroma, bit_depth, full_range, gbr, bits, n, pf, out,
+                                                 None if bins is None else bins.ctypes.data))
+        return list(out[:n]), bins
+
     # ---- host <-> device pipeline -----------------------------------------------------------
+    def stream_histogram(self, bits=0, bit_depth=None, full_range=None, gbr=None) -> None:
+        """Arm the open ring: every frame is counted on the device (h2y_stream_histogram; with bit_depth, full_range and gbr
+        given, h2y_stream_histogram_ex, as a compare-only ring needs)."""
+        if bit_depth is None and full_range is None and gbr is None:
+            self._check(self.lib.h2y_stream_histogram(self.h, bits))
+        else:
+            f = (lambda v: -1 if v is None else int(v))
+            self._check(self.lib.h2y_stream_histogram_ex(self.h, bits, f(bit_depth), f(full_range), f(gbr)))
+
+    def stream_histogram_result(self):
+        """(H2YHistogramStats, uint32 bins of shape (3, nbins)) of the frame stream_output returned last."""
+        import numpy as np
+
+        st = H2YHistogramStats()
+        self._check(self.lib.h2y_stream_histogram_result(self.h, C.byref(st), None))
+        bins = np.zeros((3, st.nbins), dtype=np.uint32)
+        self._check(self.lib.h2y_stream_histogram_result(self.h, C.byref(st), bins.ctypes.data))
+        return st, bins
+
+    def histogram_stream_open(self, width, height, chroma, bit_depth, full_range, gbr, bits, depth=3) -> None:
+        """A ring that only counts: stream_input lends the frame's three planes, stream_output returns None."""
+        self._check(self.lib.h2y_histogram_stream_open(self.h, width, height, chroma, bit_depth, full_range, gbr, bits, depth))
+        nc = (width >> 1) * (height >> 1) if chroma == CHROMA_420 else width * height
+        self._stream_inverse = None
+        self._stream_dpx = None
+        self._stream_rgb = False
+        self._stream_cmp_planes = (width * height, nc, nc)
+
     def stream_compare(self, sigma, keep_output=1) -> None:
         """Arm the open ring: every frame is compared with the reference stream_reference lends for it."""
         self._check(self.lib.h2y_stream_compare(self.h, sigma, keep_output))

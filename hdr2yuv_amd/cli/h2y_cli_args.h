@@ -33,6 +33,14 @@
  *             may be left out: the run converts and compares and writes nothing, its output type taken from R.
  *             --compare_only 1 (an addition) compares --src_filename (.yuv or .rgb, read with the --src_* size, depth and chroma
  *             format -- 1 or 3 for .yuv, 3 for .rgb --, from --src_start_frame on) with R (same layout, from its frame 0), --n_frames of each; no conversion.
+ * --histogram FILE [--histogram_bits B] [--check_range 1] [--histogram_only 1] (additions: the "hist" and "check video range" the
+ *             reference leaves a TODO at hdr2yuv.cpp:658 and :797): every frame the run produces is counted on the device -- the .yuv
+ *             frames (destination depth and range, Y,Cb,Cr limits), the G,B,R planes of the inverse flow (destination depth, source
+ *             range, G,B,R limits), the source frames of --compare_only -- into 2^B bins (B: 1..depth, the depth by default) and the
+ *             legal range of set_pic_clip() at that depth.  Without --dst_filename nothing is written; without it and without
+ *             --ref_filename the run is the .yuv flow.  --histogram_only 1 counts a .yuv (4:2:0 or 4:4:4) or .rgb (4:4:4) source
+ *             read as --compare_only reads it, without conversion.  --check_range 1: exit status 4 when a counted sample lies
+ *             outside the legal range (refused in full range, which has no such samples to find).
  * Only user_args_t.chroma_resampler_type has no defined default there (never initialised): FIR here, as in
  * make.sh's example.  The reference calls exit(0) on its argument errors; this program returns 1.
  */
@@ -68,6 +76,12 @@ struct cli_args {
     const char *ref = nullptr;
     int sigma = 0, compare_only = 0;
     bool sigma_given = false;
+    /* the histogram: --histogram FILE, --histogram_bits (0: the counted frames' depth), --histogram_only, --check_range; what is
+     * counted, resolved by cli_resolve_histogram: depth, range, G,B,R limits, chroma format */
+    const char *hist = nullptr;
+    int hist_bits = 0, hist_only = 0, check_range = 0;
+    bool hist_bits_given = false;
+    int hist_depth = 0, hist_full = 0, hist_gbr = 0, hist_chroma = 0;
     std::vector<int> devices;
     /* resolved */
     int in_type = CLI_IN_NONE, out_type = CLI_OUT_NONE;
@@ -120,6 +134,8 @@ static inline void cli_help()
            "  additional: [--synthetic SEEDFRAME] [--device D] [--gpus N [--devices d0,d1,..]] [--dry_run 1]\n"
            "  compare: [--ref_filename R.yuv|R.rgb [--sigma_compare S]] (the output against R, frame by frame; without\n"
            "  --dst_filename nothing is written), [--compare_only 1] (--src_filename against R, no conversion)\n"
+           "  histogram: [--histogram FILE [--histogram_bits B] [--check_range 1]] (code values of every frame the run produces,\n"
+           "  totals into FILE; exit status 4 on a sample outside the legal range), [--histogram_only 1] (--src_filename, no conversion)\n"
            "input by extension: .yuv .rgb (16-bit planar), .f32 .f16 (raw planar float / half, plane order G,B,R: what\n"
            "  dpx_read() / read_exr() leave in memory), .dpx (10-bit, 16-bit or float DPX) and .tiff (16-bit R,G,B, uncompressed; centre-cropped\n"
            "  to 3840 wide, [--cutout_hd 1] 1920x1080, [--cutout_qhd 1] 960x540) and .exr (scanline OpenEXR: NONE, RLE, ZIPS or ZIP;\n"
@@ -144,6 +160,10 @@ static inline void cli_parse(cli_args &a, int argc, char **argv)
         else if (is("--ref_filename")) a.ref = val();
         else if (is("--sigma_compare")) { a.sigma = atoi(val()); a.sigma_given = true; }
         else if (is("--compare_only")) a.compare_only = atoi(val());
+        else if (is("--histogram")) a.hist = val();
+        else if (is("--histogram_bits")) { a.hist_bits = atoi(val()); a.hist_bits_given = true; }
+        else if (is("--histogram_only")) a.hist_only = atoi(val());
+        else if (is("--check_range")) a.check_range = atoi(val());
         else if (is("--alpha_channel")) (void)val(); /* (read_tiff ignores alpha too) */
         else if (is("--cutout_hd")) a.cutout = atoi(val()) ? (a.cutout | H2Y_TIFF_CUTOUT_HD) : (a.cutout & ~H2Y_TIFF_CUTOUT_HD);
         else if (is("--cutout_qhd")) a.cutout = atoi(val()) ? (a.cutout | H2Y_TIFF_CUTOUT_QHD) : (a.cutout & ~H2Y_TIFF_CUTOUT_QHD);
@@ -236,10 +256,88 @@ static inline int cli_resolve_compare(cli_args &a)
     return arg_errors;
 }
 
-/* hdr2yuv.cpp:265-572 and the attribute overrides of read_file(); returns the number of argument errors */
+/* --histogram_only 1: one file counted, no conversion; returns the number of argument errors */
+static inline int cli_resolve_histogram_only(cli_args &a)
+{
+    int arg_errors = 0;
+    const char *ext = cli_ext_of(a.src);
+    if (!strcasecmp(ext, "yuv")) a.in_type = CLI_IN_YUV;
+    else if (!strcasecmp(ext, "rgb")) a.in_type = CLI_IN_RGB;
+    else {
+        printf("WARNING: --histogram_only reads .yuv or .rgb; source file (%s) is a .%s\n", a.src ? a.src : "(none)", ext);
+        arg_errors++;
+    }
+    if (a.dst) { printf("WARNING: --histogram_only writes no frames: leave out --dst_filename\n"); arg_errors++; }
+    if (a.ref || a.compare_only) { printf("WARNING: --histogram_only reads one file: leave out --ref_filename and --compare_only\n"); arg_errors++; }
+    printf("histogram_only: 1\nsrc_filename: %s\n", a.src ? a.src : "(none)");
+    printf("src_pic_width: %d\nsrc_pic_height: %d\nsrc_chroma_format_idc: %d\nsrc_bit_depth: %d\nsrc_video_full_range_flag: %d\n"
+           "src_start_frame: %d\nn_frames: %d\n", a.in.width, a.in.height, a.in.chroma_format_idc, a.in.bit_depth,
+           a.in.video_full_range_flag, a.start_frame, a.n_frames);
+    if (a.in.width < 1 || a.in.width > 10000) { printf("WARNING: pic_width(%d) outside range [1,10000]\n", a.in.width); arg_errors++; }
+    if (a.in.height < 1 || a.in.height > 10000) { printf("WARNING: pic_height(%d) outside range [1,10000]\n", a.in.height); arg_errors++; }
+    if (a.in.bit_depth < 8 || a.in.bit_depth > 16) { printf("WARNING: src bit_depth(%d) outside range [8,16]\n", a.in.bit_depth); arg_errors++; }
+    if (a.in.video_full_range_flag != 0 && a.in.video_full_range_flag != 1) {
+        printf("WARNING: video_full_range_flag(%d) not 0 or 1\n", a.in.video_full_range_flag);
+        arg_errors++;
+    }
+    if (a.in.chroma_format_idc != H2Y_CHROMA_420 && a.in.chroma_format_idc != H2Y_CHROMA_444) {
+        printf("WARNING: chroma_format_idc(%d) not %d or %d\n", a.in.chroma_format_idc, H2Y_CHROMA_420, H2Y_CHROMA_444);
+        arg_errors++;
+    } else if (a.in_type == CLI_IN_RGB && a.in.chroma_format_idc != H2Y_CHROMA_444) { /* three full planes R, G, B */
+        printf("WARNING: a .rgb holds three planes of width x height: --histogram_only of a .rgb takes chroma_format_idc %d, not %d\n",
+               H2Y_CHROMA_444, a.in.chroma_format_idc);
+        arg_errors++;
+    }
+    a.out = a.in;
+    return arg_errors;
+}
+
+/* What --histogram counts, printed; returns the number of argument errors */
+static inline int cli_resolve_histogram(cli_args &a)
+{
+    if (!a.hist) {
+        printf("WARNING: --histogram_bits, --histogram_only and --check_range need --histogram FILE\n");
+        return 1;
+    }
+    if (a.compare_only || a.hist_only) { /* the source frames, as read */
+        a.hist_depth = a.in.bit_depth, a.hist_full = a.in.video_full_range_flag;
+        a.hist_gbr = a.in_type == CLI_IN_RGB, a.hist_chroma = a.in.chroma_format_idc;
+    } else if (a.inverse) { /* the G, B, R planes of matrix_inverse(), clamped in the source's range */
+        a.hist_depth = a.out.bit_depth, a.hist_full = a.in.video_full_range_flag, a.hist_gbr = 1, a.hist_chroma = H2Y_CHROMA_444;
+    } else { /* the .yuv frames, clamped by write_yuv() */
+        a.hist_depth = a.out.bit_depth, a.hist_full = a.out.video_full_range_flag, a.hist_gbr = 0, a.hist_chroma = a.out.chroma_format_idc;
+    }
+    if (!a.hist_bits_given) a.hist_bits = a.hist_depth;
+    printf("histogram: %s\nhistogram_bits: %d%s\nhistogram_frames: %s bit_depth %d %s range, planes %s\ncheck_range: %d\n", a.hist,
+           a.hist_bits, a.hist_bits_given ? "" : " (default)", a.compare_only || a.hist_only ? "source" : "output", a.hist_depth,
+           a.hist_full ? "full" : "video", a.hist_gbr ? "G,B,R" : "Y,Cb,Cr", a.check_range);
+    int arg_errors = 0;
+    if (a.hist_depth < 8 || a.hist_depth > 16) {
+        printf("WARNING: --histogram counts frames of bit_depth 8..16, not %d\n", a.hist_depth);
+        arg_errors++;
+    } else if (a.hist_bits < 1 || a.hist_bits > a.hist_depth) {
+        printf("WARNING: histogram_bits(%d) outside range [1,%d]\n", a.hist_bits, a.hist_depth);
+        arg_errors++;
+    }
+    if (a.check_range && a.hist_full) {
+        printf("WARNING: --check_range 1 in full range: every code 0..2^bit_depth-1 is legal, there is no range to check\n");
+        arg_errors++;
+    }
+    return arg_errors;
+}
+
+/* hdr2yuv.cpp:265-572 and the attribute overrides of read_file(), then what --histogram counts; returns the number of argument
+ * errors */
+static inline int cli_resolve_convert(cli_args &a);
 static inline int cli_resolve(cli_args &a)
 {
-    if (a.compare_only) return cli_resolve_compare(a);
+    int arg_errors = a.hist_only ? cli_resolve_histogram_only(a) : a.compare_only ? cli_resolve_compare(a) : cli_resolve_convert(a);
+    if (a.hist || a.hist_bits_given || a.hist_only || a.check_range) arg_errors += cli_resolve_histogram(a);
+    return arg_errors;
+}
+
+static inline int cli_resolve_convert(cli_args &a)
+{
     int arg_errors = 0;
     /* :265-318: unset destination attributes <- the source's, as parsed */
     if (a.out.bit_depth == 0) a.out.bit_depth = a.in.bit_depth;
@@ -275,7 +373,7 @@ static inline int cli_resolve(cli_args &a)
     }
 
     /* :386-440 output type (without a destination: the reference file's) */
-    ext = cli_ext_of(a.dst ? a.dst : a.ref);
+    ext = cli_ext_of(a.dst ? a.dst : a.ref ? a.ref : a.hist ? "(none).yuv" : nullptr); /* only a histogram: the .yuv flow */
     if (!strcasecmp(ext, "yuv")) a.out_type = CLI_OUT_YUV;
     else if (!strcasecmp(ext, "rgb")) a.out_type = CLI_OUT_RGB;
     else if (!strcasecmp(ext, "tiff")) a.out_type = CLI_OUT_TIFF;

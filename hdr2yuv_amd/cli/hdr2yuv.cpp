@@ -42,8 +42,20 @@
  * mean_psnr: the mean over frames of the per-frame value, a frame with sse 0 counting 99.99; global_psnr: from the summed sse
  * and samples; max_abs the largest |a - b|, over the count of |a - b| > S (S 0 by default); first_over the first such sample in
  * frame, plane and raster order, a the output's (the source's) sample, b R's.  Exit status 3 when S was given and over > 0.
+ *
+ * Histogram (--histogram FILE [--histogram_bits B] [--check_range 1], or --histogram_only 1; h2y_cli_args.h): each GPU thread arms
+ * its ring (h2y_stream_histogram; h2y_stream_histogram_ex on a compare-only ring) or opens a histogram-only ring, keeps the stats
+ * of frame k by its index and sums its frames' bins; the report is printed once every thread is done, so it, and FILE, are the
+ * same for any --gpus.  Planes P0 P1 P2 are Y Cb Cr, or G B R for .rgb / .tiff; occupied counts the non-zero bins of 2^B:
+ *   histogram frame <k> <P0> min <m> max <M> below <b> above <a> at_low <l> at_high <h> occupied <o> <P1> ... <P2> ...
+ *   histogram summary frames <N> <P0> min .. occupied <o> <P1> ... <P2> ...   (sums, and bins occupied in the totals)
+ *   histogram legal <P0> <lo>..<hi> <P1> <lo>..<hi> <P2> <lo>..<hi> outside <below + above over all planes and frames>
+ * FILE (text): "bin,code_lo,code_hi,<P0>,<P1>,<P2>", then one line per bin, code_lo = bin << (depth - B), code_hi = code_lo +
+ * 2^(depth - B) - 1, the counts summed over the frames (a code above 2^depth - 1 counts in the last bin).  Exit status 4 under
+ * --check_range 1 when outside > 0 (3 before it, when the comparison's status is 3).
  */
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <cerrno>
 #include <condition_variable>
@@ -418,11 +430,46 @@ struct compare_io {
     }
 };
 
+/* the histogram side of one GPU thread: the stats and occupied bins of frame k kept by its index, the bins summed over its frames */
+struct histogram_io {
+    bool on = false;
+    std::vector<h2y_histogram_stats> *stats = nullptr;
+    std::vector<std::array<uint32_t, 3>> *occupied = nullptr;
+    std::vector<uint32_t> bins;  /* one frame's 3 x nbins */
+    std::vector<uint64_t> total; /* this thread's sums */
+    size_t nbins = 0;
+    void open(const cli_args &a, std::vector<h2y_histogram_stats> *st, std::vector<std::array<uint32_t, 3>> *occ)
+    {
+        on = a.hist != nullptr;
+        if (!on) return;
+        stats = st, occupied = occ;
+        nbins = (size_t)1 << a.hist_bits;
+        bins.assign(3 * nbins, 0u);
+        total.assign(3 * nbins, 0u);
+    }
+    /* after h2y_stream_output: frame k's result */
+    bool take(h2y_ctx *ctx, long k)
+    {
+        if (!on) return true;
+        if (h2y_stream_histogram_result(ctx, &(*stats)[k], bins.data())) return false;
+        for (int p = 0; p < 3; p++) {
+            uint32_t occ = 0;
+            for (size_t i = 0; i < nbins; i++) {
+                const uint32_t c = bins[p * nbins + i];
+                occ += c != 0u;
+                total[p * nbins + i] += c;
+            }
+            (*occupied)[k][p] = occ;
+        }
+        return true;
+    }
+};
+
 /* forward path: frames [first, first+count) through one context's pinned ring (dpx: frame k is file dpx[k], decoded on the
  * device -- the ring of h2y_dpx_stream_open; tiff likewise, file tiff[k] through h2y_tiff_stream_open) */
 static void run_block(const cli_args &a, const h2y_desc &d, const std::vector<dpx_src> &dpx, const h2y_dpx_info &di,
                       const std::vector<tiff_src> &tiff, const h2y_tiff_info &ti, const std::vector<std::string> &exr,
-                      const h2y_exr_info &xi, int fd_out, off_t base, std::vector<h2y_compare_stats> *stats, block *b)
+                      const h2y_exr_info &xi, int fd_out, off_t base, std::vector<h2y_compare_stats> *stats, histogram_io *hist, block *b)
 {
     h2y_ctx *ctx = nullptr;
     FILE *fin = nullptr;
@@ -450,6 +497,7 @@ static void run_block(const cli_args &a, const h2y_desc &d, const std::vector<dp
     compare_io cmp;
     if (!cmp.open(a, b->first, 0, ob, stats)) return fail(std::string("unable to read ") + a.ref);
     if (cmp.ref && h2y_stream_compare(ctx, a.sigma, a.dst ? 1 : 0)) return fail(h2y_last_error(ctx));
+    if (hist->on && h2y_stream_histogram(ctx, a.hist_bits)) return fail(h2y_last_error(ctx));
     std::unique_ptr<unpack_pool> pool;
     std::vector<h2y_exr_chunk> chunks;
     if (a.in_type == CLI_IN_EXR) {
@@ -462,6 +510,7 @@ static void run_block(const cli_args &a, const h2y_desc &d, const std::vector<dp
         if (h2y_stream_output(ctx, &yuv)) { fail(h2y_last_error(ctx)); return false; }
         const long k = b->first + b->done;
         if (cmp.ref && h2y_stream_compare_result(ctx, &(*cmp.stats)[k])) { fail(h2y_last_error(ctx)); return false; }
+        if (!hist->take(ctx, k)) { fail(h2y_last_error(ctx)); return false; }
         if (a.dst && !write_at(fd_out, yuv, ob, base + (off_t)k * (off_t)ob)) { fail(std::string("short write to ") + a.dst); return false; }
         if (a.verbose > 0 && a.dst) printf("frame %ld: %zu bytes written to %s (device %d)\n", k, ob, a.dst, b->device);
         b->done++;
@@ -532,7 +581,8 @@ struct tiff_wrap {
 
 /* .yuv -> RGB (matrix_inverse): frames [first, first+count) through one context's pinned inverse ring, as run_block; .tiff
  * output: the ring with the interleave (h2y_tiff_inverse_stream_open), frame k into its own file, head + samples + tail */
-static void run_block_inverse(const cli_args &a, const tiff_wrap &tw, int fd_out, off_t base, std::vector<h2y_compare_stats> *stats, block *b)
+static void run_block_inverse(const cli_args &a, const tiff_wrap &tw, int fd_out, off_t base, std::vector<h2y_compare_stats> *stats,
+                              histogram_io *hist, block *b)
 {
     h2y_ctx *ctx = nullptr;
     FILE *fin = nullptr;
@@ -558,12 +608,14 @@ static void run_block_inverse(const cli_args &a, const tiff_wrap &tw, int fd_out
     compare_io cmp;
     if (!cmp.open(a, b->first, 2 * n, out_frame, stats)) return fail(std::string("unable to read ") + a.ref);
     if (cmp.ref && h2y_stream_compare(ctx, a.sigma, a.dst ? 1 : 0)) return fail(h2y_last_error(ctx));
+    if (hist->on && h2y_stream_histogram(ctx, a.hist_bits)) return fail(h2y_last_error(ctx));
     long in_flight = 0;
     auto drain_one = [&]() -> bool {
         const uint16_t *gbr = nullptr;
         if (h2y_stream_output(ctx, &gbr)) { fail(h2y_last_error(ctx)); return false; }
         const long k = b->first + b->done;
         if (cmp.ref && h2y_stream_compare_result(ctx, &(*cmp.stats)[k])) { fail(h2y_last_error(ctx)); return false; }
+        if (!hist->take(ctx, k)) { fail(h2y_last_error(ctx)); return false; }
         if (!a.dst) {
             b->done++;
             in_flight--;
@@ -614,7 +666,8 @@ static void run_block_inverse(const cli_args &a, const tiff_wrap &tw, int fd_out
 }
 
 /* --compare_only: frames [first, first+count) of the source against the same frames of R through one compare-only ring */
-static void run_block_compare(const cli_args &a, size_t plane_bytes, size_t frame_bytes, std::vector<h2y_compare_stats> *stats, block *b)
+static void run_block_compare(const cli_args &a, size_t plane_bytes, size_t frame_bytes, std::vector<h2y_compare_stats> *stats,
+                              histogram_io *hist, block *b)
 {
     h2y_ctx *ctx = nullptr;
     FILE *fin = nullptr;
@@ -632,11 +685,15 @@ static void run_block_compare(const cli_args &a, size_t plane_bytes, size_t fram
     if (!cmp.open(a, b->first, plane_bytes, frame_bytes, stats)) return fail(std::string("unable to read ") + a.ref);
     const int depth = 3;
     if (h2y_compare_stream_open(ctx, a.in.width, a.in.height, a.in.chroma_format_idc, a.sigma, depth)) return fail(h2y_last_error(ctx));
+    if (hist->on && h2y_stream_histogram_ex(ctx, a.hist_bits, a.hist_depth, a.hist_full, a.hist_gbr)) return fail(h2y_last_error(ctx));
     long in_flight = 0;
     auto drain_one = [&]() -> bool {
         const uint16_t *none = nullptr;
         const long k = b->first + b->done;
-        if (h2y_stream_output(ctx, &none) || h2y_stream_compare_result(ctx, &(*stats)[k])) { fail(h2y_last_error(ctx)); return false; }
+        if (h2y_stream_output(ctx, &none) || h2y_stream_compare_result(ctx, &(*stats)[k]) || !hist->take(ctx, k)) {
+            fail(h2y_last_error(ctx));
+            return false;
+        }
         b->done++;
         in_flight--;
         return true;
@@ -656,6 +713,102 @@ static void run_block_compare(const cli_args &a, size_t plane_bytes, size_t fram
     h2y_stream_close(ctx);
     fclose(fin);
     h2y_ctx_destroy(ctx);
+}
+
+/* --histogram_only: frames [first, first+count) of the source through one histogram-only ring */
+static void run_block_histogram(const cli_args &a, size_t plane_bytes, size_t frame_bytes, histogram_io *hist, block *b)
+{
+    h2y_ctx *ctx = nullptr;
+    FILE *fin = nullptr;
+    auto fail = [&](const std::string &m) {
+        b->err = m;
+        if (ctx) { h2y_stream_close(ctx); h2y_ctx_destroy(ctx); }
+        if (fin) fclose(fin);
+    };
+    if (b->count < 1) return;
+    if (h2y_ctx_create(b->device, &ctx)) return fail(h2y_last_error(nullptr));
+    fin = fopen(a.src, "rb");
+    if (!fin) return fail(std::string("unable to open file ") + a.src);
+    if (fseeko(fin, (off_t)frame_bytes * (off_t)(a.start_frame + b->first), SEEK_SET)) return fail("seek failed");
+    const int depth = 3;
+    if (h2y_histogram_stream_open(ctx, a.in.width, a.in.height, a.in.chroma_format_idc, a.hist_depth, a.hist_full, a.hist_gbr, a.hist_bits,
+                                  depth))
+        return fail(h2y_last_error(ctx));
+    const bool rgb = a.in_type == CLI_IN_RGB;
+    long in_flight = 0;
+    auto drain_one = [&]() -> bool {
+        const uint16_t *none = nullptr;
+        const long k = b->first + b->done;
+        if (h2y_stream_output(ctx, &none) || !hist->take(ctx, k)) { fail(h2y_last_error(ctx)); return false; }
+        b->done++;
+        in_flight--;
+        return true;
+    };
+    for (long f = 0; f < b->count; f++) {
+        void *planes[3];
+        if (h2y_stream_input(ctx, planes)) return fail(h2y_last_error(ctx));
+        /* the slot's planes lie one after the other: a frame is one read, a .rgb one with its planes put in G, B, R order */
+        if (!read_ref(fin, rgb, plane_bytes, frame_bytes, planes[0])) return fail(std::string("short read from ") + a.src);
+        if (h2y_stream_submit(ctx)) return fail(h2y_last_error(ctx));
+        in_flight++;
+        if (in_flight == depth - 1 && !drain_one()) return;
+    }
+    while (in_flight > 0)
+        if (!drain_one()) return;
+    h2y_stream_close(ctx);
+    fclose(fin);
+    h2y_ctx_destroy(ctx);
+}
+
+/* the histogram report of the header comment and FILE; returns the exit status (4: --check_range 1 and samples outside) */
+static int histogram_report(const cli_args &a, const std::vector<h2y_histogram_stats> &st, const std::vector<std::array<uint32_t, 3>> &occ,
+                            const std::vector<uint64_t> &total)
+{
+    static const char *const kYuv[3] = {"Y", "Cb", "Cr"}, *const kRgb[3] = {"G", "B", "R"};
+    const char *const *name = a.hist_gbr ? kRgb : kYuv;
+    const size_t nbins = (size_t)1 << a.hist_bits;
+    uint64_t below[3] = {0, 0, 0}, above[3] = {0, 0, 0}, at_low[3] = {0, 0, 0}, at_high[3] = {0, 0, 0};
+    uint32_t mn[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, mx[3] = {0, 0, 0};
+    auto plane = [&](int p, uint32_t lo, uint32_t hi, uint64_t b, uint64_t ab, uint64_t l, uint64_t h, uint32_t o) {
+        printf(" %s min %u max %u below %llu above %llu at_low %llu at_high %llu occupied %u", name[p], lo, hi, (unsigned long long)b,
+               (unsigned long long)ab, (unsigned long long)l, (unsigned long long)h, o);
+    };
+    for (size_t k = 0; k < st.size(); k++) {
+        const h2y_histogram_stats &s = st[k];
+        printf("histogram frame %zu", k);
+        for (int p = 0; p < 3; p++) {
+            plane(p, s.min[p], s.max[p], s.below[p], s.above[p], s.at_low[p], s.at_high[p], occ[k][p]);
+            below[p] += s.below[p], above[p] += s.above[p], at_low[p] += s.at_low[p], at_high[p] += s.at_high[p];
+            if (s.samples[p]) mn[p] = std::min(mn[p], s.min[p]), mx[p] = std::max(mx[p], s.max[p]);
+        }
+        printf("\n");
+    }
+    printf("histogram summary frames %zu", st.size());
+    uint64_t outside = 0;
+    for (int p = 0; p < 3; p++) {
+        uint32_t o = 0;
+        for (size_t i = 0; i < nbins; i++) o += total[p * nbins + i] != 0u;
+        plane(p, mn[p] == 0xFFFFFFFFu ? 0u : mn[p], mx[p], below[p], above[p], at_low[p], at_high[p], o);
+        outside += below[p] + above[p];
+    }
+    printf("\nhistogram legal");
+    for (int p = 0; p < 3; p++) printf(" %s %u..%u", name[p], st.empty() ? 0u : st[0].lo[p], st.empty() ? 0u : st[0].hi[p]);
+    printf(" outside %llu\n", (unsigned long long)outside);
+    FILE *f = fopen(a.hist, "w");
+    if (!f) {
+        printf("ERROR: unable to write %s\n", a.hist);
+        return 1;
+    }
+    const uint32_t shift = (uint32_t)(a.hist_depth - a.hist_bits);
+    fprintf(f, "bin,code_lo,code_hi,%s,%s,%s\n", name[0], name[1], name[2]);
+    for (size_t i = 0; i < nbins; i++)
+        fprintf(f, "%zu,%zu,%zu,%llu,%llu,%llu\n", i, i << shift, ((i + 1) << shift) - 1, (unsigned long long)total[i],
+                (unsigned long long)total[nbins + i], (unsigned long long)total[2 * nbins + i]);
+    if (fclose(f)) {
+        printf("ERROR: unable to write %s\n", a.hist);
+        return 1;
+    }
+    return a.check_range && outside ? 4 : 0;
 }
 
 static std::string psnr_str(uint64_t maxv, uint64_t n, uint64_t sse)
@@ -711,7 +864,7 @@ int main(int argc, char **argv)
 {
     cli_args a;
     cli_parse(a, argc, argv);
-    if ((!a.dst && !a.ref) || (!a.src && a.synthetic < 0)) {
+    if ((!a.dst && !a.ref && !a.hist && !a.hist_only) || (!a.src && a.synthetic < 0)) {
         if (!a.help) cli_help();
         return a.help ? 0 : 1;
     }
@@ -738,7 +891,7 @@ int main(int argc, char **argv)
     h2y_desc d;
     cli_make_desc(a, &d);
     size_t in_frame_bytes, out_frame_bytes;
-    if (a.compare_only) { /* two files of one layout */
+    if (a.compare_only || a.hist_only) { /* two files of one layout, or one */
         const size_t n = (size_t)a.in.width * a.in.height;
         const size_t nc = a.in.chroma_format_idc == H2Y_CHROMA_420 ? (size_t)(a.in.width / 2) * (a.in.height / 2) : n;
         in_frame_bytes = out_frame_bytes = (n + 2 * nc) * 2;
@@ -857,10 +1010,16 @@ int main(int argc, char **argv)
         at += blocks[r].count;
     }
     std::vector<h2y_compare_stats> stats(a.ref ? (size_t)frames : 0);
+    std::vector<h2y_histogram_stats> hstats(a.hist ? (size_t)frames : 0);
+    std::vector<std::array<uint32_t, 3>> hocc(a.hist ? (size_t)frames : 0);
+    std::vector<histogram_io> hist(a.gpus);
+    for (auto &x : hist) x.open(a, &hstats, &hocc);
     auto work = [&](block *b) {
-        if (a.compare_only) run_block_compare(a, (size_t)a.in.width * a.in.height * 2, in_frame_bytes, &stats, b);
-        else if (a.inverse) run_block_inverse(a, tw, fd, base, &stats, b);
-        else run_block(a, d, dpx, di, tiff, ti, exr, xi, fd, base, &stats, b);
+        histogram_io *hi = &hist[b - blocks.data()];
+        if (a.hist_only) run_block_histogram(a, (size_t)a.in.width * a.in.height * 2, in_frame_bytes, hi, b);
+        else if (a.compare_only) run_block_compare(a, (size_t)a.in.width * a.in.height * 2, in_frame_bytes, &stats, hi, b);
+        else if (a.inverse) run_block_inverse(a, tw, fd, base, &stats, hi, b);
+        else run_block(a, d, dpx, di, tiff, ti, exr, xi, fd, base, &stats, hi, b);
     };
     if (a.gpus == 1) work(&blocks[0]);
     else {
@@ -876,5 +1035,12 @@ int main(int argc, char **argv)
             rc = 1;
         }
     if (!rc && a.ref) rc = compare_report(a, cmp_yuv, a.out.bit_depth, stats);
+    if ((!rc || rc == 3) && a.hist) { /* the bins of every thread, summed (the same totals for any split) */
+        std::vector<uint64_t> total(hist[0].total.size(), 0u);
+        for (const auto &x : hist)
+            for (size_t i = 0; i < total.size(); i++) total[i] += x.total[i];
+        const int hrc = histogram_report(a, hstats, hocc, total);
+        if (hrc == 1 || !rc) rc = hrc;
+    }
     return rc;
 }

@@ -215,6 +215,9 @@ struct h2y_ctx {
     size_t cmp_part_cap = 0;
     h2y_compare_stats *d_cmp_stats = nullptr;
     size_t cmp_stats_cap = 0;
+    /* h2y_histogram_batch's device workspace: per launch the counts, the bins and the stats (hist_layout) */
+    char *d_hist = nullptr;
+    size_t hist_cap = 0;
 
     /* staging for the host-buffer entry */
     void *d_in = nullptr;
@@ -237,6 +240,10 @@ struct h2y_ctx {
         char *h_ref = nullptr, *d_ref = nullptr;
         h2y_compare_stats *h_stats = nullptr;
         bool ref_lent = false;
+        /* an armed ring (h2y_stream_histogram): the frame's counts, bins and stats on the device (hist_layout), and pinned */
+        char *d_hist = nullptr;
+        h2y_histogram_stats *h_hist_stats = nullptr;
+        uint32_t *h_hist_bins = nullptr;
     };
     std::vector<stream_slot> ss;
     hipStream_t s_h2d = nullptr, s_d2h = nullptr;
@@ -245,8 +252,8 @@ struct h2y_ctx {
     int s_head = 0, s_tail = 0, s_lent = -1;
     bool streaming = false;
     /* what the ring does with a frame: the forward conversion (open_forward_ring), the .yuv -> G,B,R flow (open_inverse_ring),
-     * or a comparison alone (h2y_compare_stream_open) */
-    enum ring_kind { RING_FORWARD, RING_INVERSE, RING_COMPARE } s_kind = RING_FORWARD;
+     * a comparison alone (h2y_compare_stream_open) or a histogram alone (h2y_histogram_stream_open) */
+    enum ring_kind { RING_FORWARD, RING_INVERSE, RING_COMPARE, RING_HISTOGRAM } s_kind = RING_FORWARD;
     /* a forward ring's decode: with one, the pinned slot holds the payload, its device twin the three planes (at s_in_off[0..2])
      * and then the payload at s_pay_off */
     decode_src s_src;
@@ -267,6 +274,10 @@ struct h2y_ctx {
     bool s_started = false; /* an input was handed out: too late to arm */
     bool s_cmp = false, s_cmp_keep = true;
     cmp_geom s_cmp_geom{};
+    /* a ring armed by h2y_stream_histogram (or a histogram-only ring): k_histogram's geometry and each slot's frame */
+    bool s_hist = false;
+    hist_geom s_hist_geom{};
+    hist_frame *s_hist_tab = nullptr;
     size_t s_ref_bytes = 0, s_ref_stats_off = 0; /* the pinned reference's bytes; where the stats lie in its device twin */
     int slot_base = 0; /* run_frames(): first entry of d_frames/h_frames to use (one per stream slot) */
     float last_ms = 0.f;
@@ -1447,6 +1458,7 @@ void h2y_ctx_destroy(h2y_ctx *ctx)
     (void)hipHostFree(ctx->h_tab);
     (void)hipFree(ctx->d_cmp_part);
     (void)hipFree(ctx->d_cmp_stats);
+    (void)hipFree(ctx->d_hist);
     (void)hipFree(ctx->d_in);
     (void)hipFree(ctx->d_out);
     if (ctx->fir_stream) {
@@ -2105,6 +2117,9 @@ static void stream_free(h2y_ctx *ctx)
         if (s.h_ref) (void)hipHostFree(s.h_ref);
         if (s.d_ref) (void)hipFree(s.d_ref);
         if (s.h_stats) (void)hipHostFree(s.h_stats);
+        if (s.d_hist) (void)hipFree(s.d_hist);
+        if (s.h_hist_stats) (void)hipHostFree(s.h_hist_stats);
+        if (s.h_hist_bins) (void)hipHostFree(s.h_hist_bins);
     }
     ctx->ss.clear();
     if (ctx->s_h2d) (void)hipStreamDestroy(ctx->s_h2d);
@@ -2114,6 +2129,9 @@ static void stream_free(h2y_ctx *ctx)
     if (ctx->s_cmp_tab) (void)hipFree(ctx->s_cmp_tab);
     ctx->s_tab = nullptr;
     ctx->s_cmp_tab = nullptr;
+    if (ctx->s_hist_tab) (void)hipFree(ctx->s_hist_tab);
+    ctx->s_hist_tab = nullptr;
+    ctx->s_hist = false;
     ctx->streaming = false;
     ctx->s_kind = h2y_ctx::RING_FORWARD;
     ctx->s_src = decode_src();
@@ -3162,6 +3180,270 @@ static int cmp_download(h2y_ctx *ctx, h2y_ctx::stream_slot &s)
     return H2Y_OK;
 }
 
+/* ---- code-value histograms and the legal-range check (hdr2yuv.cpp:658, :797) ---------------------------------------------- */
+
+/* k_histogram's geometry: planes of the comparison's geometry starting at off samples from the frame's base, the legal range of
+ * set_pic_clip() at bit_depth (planes 1 and 2 of a YCbCr frame: minVRC..maxVRC; plane 0 and every G, B, R plane: minVR..maxVR) */
+static hist_geom hist_geom_of(int width, int height, int chroma, int bit_depth, int full_range, int gbr, int bits, const uint32_t off[3])
+{
+    hist_geom g{};
+    const bool sub = chroma == H2Y_CHROMA_420;
+    const clip_limits c = make_clip(bit_depth, full_range);
+    for (int p = 0; p < 3; p++) {
+        const uint32_t w = p && sub ? (uint32_t)(width >> 1) : (uint32_t)width, h = p && sub ? (uint32_t)(height >> 1) : (uint32_t)height;
+        g.n[p] = w * h;
+        g.off[p] = off[p];
+        g.shift[p] = off[p] & 7u;
+        g.vec |= 1u << p; /* one side: the groups can always follow the plane's start */
+        g.units[p] = h2y_histogram_units(g.n[p], g.shift[p]);
+        const bool luma_like = p == 0 || gbr;
+        g.lo[p] = luma_like ? c.minVR : c.minVRC;
+        g.hi[p] = luma_like ? c.maxVR : c.maxVRC;
+    }
+    g.nbins = 1u << bits;
+    g.down = (uint32_t)(bit_depth - bits);
+    return g;
+}
+
+static int hist_check(h2y_ctx *ctx, int width, int height, int chroma, int bit_depth, int full_range, int gbr, int bits)
+{
+    if (width < 1 || height < 1 || (uint64_t)width * (uint64_t)height >= (1ull << 28)) return fail(ctx, H2Y_EINVAL, "bad picture size");
+    if (chroma == 2) return fail(ctx, H2Y_EUNSUPPORTED, "chroma_format_idc 2 (4:2:2) is not counted on this path");
+    if (chroma != H2Y_CHROMA_420 && chroma != H2Y_CHROMA_444) return fail(ctx, H2Y_EINVAL, "chroma_format_idc must be 1 or 3");
+    if (bit_depth < 8 || bit_depth > 16) return fail(ctx, H2Y_EINVAL, "bit_depth must be 8..16");
+    if (bits < 1 || bits > bit_depth) return fail(ctx, H2Y_EINVAL, "bits must be 1..bit_depth (%d)", bit_depth);
+    if ((full_range != 0 && full_range != 1) || (gbr != 0 && gbr != 1)) return fail(ctx, H2Y_EINVAL, "full_range and gbr must be 0 or 1");
+    return H2Y_OK;
+}
+
+/* A workspace of nf frames: the counts (zeroed), the bins (zeroed), then the stats k_histogram_finish writes */
+struct hist_layout {
+    size_t bins, stats, total;
+};
+static hist_layout hist_layout_of(uint32_t nbins, int nf)
+{
+    hist_layout L;
+    L.bins = ((size_t)nf * 3u * sizeof(hist_acc) + 255) & ~(size_t)255;
+    L.stats = (L.bins + (size_t)nf * 3u * nbins * sizeof(uint32_t) + 255) & ~(size_t)255;
+    L.total = L.stats + (size_t)nf * sizeof(h2y_histogram_stats);
+    return L;
+}
+
+/* the zeroing and both kernels of nf frames on the context's stream, into the workspace ws */
+static int hist_enqueue(h2y_ctx *ctx, const hist_geom &g, const hist_frame *frames, int nf, char *ws)
+{
+    const hist_layout L = hist_layout_of(g.nbins, nf);
+    HIP_TRY(ctx, hipMemsetAsync(ws, 0, L.stats, ctx->stream));
+    HIP_TRY(ctx, h2y_launch_histogram(h2y_histogram_grid(ctx->n_cu, g, nf), ctx->stream, g, frames, nf, reinterpret_cast<hist_acc *>(ws),
+                                      reinterpret_cast<uint32_t *>(ws + L.bins), reinterpret_cast<h2y_histogram_stats *>(ws + L.stats)));
+    return H2Y_OK;
+}
+
+int h2y_histogram_batch(h2y_ctx *ctx, int width, int height, int chroma_format_idc, int bit_depth, int full_range, int gbr, int bits,
+                        int n_frames, const uint16_t *const *d_frames, h2y_histogram_stats *out_stats, uint32_t *out_bins)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
+    int rc = hist_check(ctx, width, height, chroma_format_idc, bit_depth, full_range, gbr, bits);
+    if (rc) return rc;
+    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
+    if (!d_frames || !out_stats) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
+    for (int f = 0; f < n_frames; f++) {
+        if (!d_frames[f]) return fail(ctx, H2Y_EINVAL, "frame %d is null", f);
+        if ((uintptr_t)d_frames[f] & 15u) return fail(ctx, H2Y_EINVAL, "frame %d is not 16-byte aligned", f);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    uint32_t off[3];
+    cmp_contiguous(width, height, chroma_format_idc, off);
+    const hist_geom g = hist_geom_of(width, height, chroma_format_idc, bit_depth, full_range, gbr, bits, off);
+    const int per_launch = std::min(n_frames, H2Y_HISTOGRAM_FRAMES_PER_LAUNCH);
+    const hist_layout L = hist_layout_of(g.nbins, per_launch);
+    hist_frame *h;
+    rc = frame_table(ctx, n_frames, h);
+    if (!rc) rc = ensure(ctx, ctx->d_hist, ctx->hist_cap, L.total);
+    if (rc) return rc;
+    for (int f = 0; f < n_frames; f++) h[f].base = d_frames[f];
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_tab, h, (size_t)n_frames * sizeof(hist_frame), hipMemcpyHostToDevice, ctx->stream));
+    const hist_frame *frames = static_cast<const hist_frame *>(ctx->d_tab);
+    /* one launch at a time: its stats and bins come down before the next one reuses the workspace */
+    float ms = 0.f;
+    int launches = 0;
+    hipEvent_t *ev = ctx->b->ev[0];
+    for (int f0 = 0; f0 < n_frames; f0 += per_launch, launches++) {
+        const int nf = std::min(per_launch, n_frames - f0);
+        const hist_layout Ln = hist_layout_of(g.nbins, nf);
+        HIP_TRY(ctx, hipEventRecord(ev[0], ctx->stream));
+        rc = hist_enqueue(ctx, g, frames + f0, nf, ctx->d_hist);
+        if (rc) return rc;
+        HIP_TRY(ctx, hipEventRecord(ev[1], ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(out_stats + f0, ctx->d_hist + Ln.stats, (size_t)nf * sizeof(h2y_histogram_stats), hipMemcpyDeviceToHost,
+                                    ctx->stream));
+        if (out_bins)
+            HIP_TRY(ctx, hipMemcpyAsync(out_bins + (size_t)f0 * 3u * g.nbins, ctx->d_hist + Ln.bins, (size_t)nf * 3u * g.nbins * sizeof(uint32_t),
+                                        hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        float t = 0.f;
+        HIP_TRY(ctx, hipEventElapsedTime(&t, ev[0], ev[1]));
+        ms += t;
+    }
+    ctx->b->n_ev = 1;
+    ctx->last_ms = ms;
+    ctx->last_launches = launches;
+    ctx->last_name = "k_histogram";
+    ctx->last_variant = std::string("k_histogram<") + (chroma_format_idc == H2Y_CHROMA_420 ? "420" : "444") + "," +
+                        (h2y_histogram_lds(g.nbins) < (size_t)g.nbins * sizeof(uint32_t) ? "U16X2" : "U32") + ",bins=" +
+                        std::to_string(g.nbins) + ">";
+    return H2Y_OK;
+}
+
+/* Arm the open ring for frames whose planes start at off samples from the slot's base (its device output; its input on a
+ * compare-only or histogram-only ring): per slot a device workspace of one frame, pinned stats and bins, and the slot's
+ * k_histogram table entry, uploaded here once */
+static int hist_arm(h2y_ctx *ctx, int width, int height, int chroma, int bit_depth, int full_range, int gbr, int bits, const uint32_t off[3])
+{
+    int rc = hist_check(ctx, width, height, chroma, bit_depth, full_range, gbr, bits);
+    if (rc) return rc;
+    const hist_geom g = hist_geom_of(width, height, chroma, bit_depth, full_range, gbr, bits, off);
+    const hist_layout L = hist_layout_of(g.nbins, 1);
+    const int depth = (int)ctx->ss.size();
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::vector<hist_frame> tab(depth);
+    const bool on_input = ctx->s_kind == h2y_ctx::RING_COMPARE || ctx->s_kind == h2y_ctx::RING_HISTOGRAM;
+    hipError_t e = hipMalloc((void **)&ctx->s_hist_tab, tab.size() * sizeof(hist_frame));
+    for (int k = 0; k < depth && e == hipSuccess; k++) {
+        h2y_ctx::stream_slot &s = ctx->ss[k];
+        e = hipMalloc((void **)&s.d_hist, L.total);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_hist_stats, sizeof(h2y_histogram_stats), hipHostMallocDefault);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_hist_bins, (size_t)3u * g.nbins * sizeof(uint32_t), hipHostMallocDefault);
+        tab[k].base = reinterpret_cast<const uint16_t *>(on_input ? (char *)s.d_in : (char *)s.d_out);
+    }
+    if (e == hipSuccess) e = hipMemcpy(ctx->s_hist_tab, tab.data(), tab.size() * sizeof(hist_frame), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { /* the ring stays open, unarmed */
+        for (auto &s : ctx->ss) {
+            if (s.d_hist) (void)hipFree(s.d_hist);
+            if (s.h_hist_stats) (void)hipHostFree(s.h_hist_stats);
+            if (s.h_hist_bins) (void)hipHostFree(s.h_hist_bins);
+            s.d_hist = nullptr;
+            s.h_hist_stats = nullptr;
+            s.h_hist_bins = nullptr;
+        }
+        if (ctx->s_hist_tab) (void)hipFree(ctx->s_hist_tab);
+        ctx->s_hist_tab = nullptr;
+        return fail(ctx, H2Y_ENOMEM, "histogram buffers: %s", hipGetErrorString(e));
+    }
+    ctx->s_hist_geom = g;
+    ctx->s_hist = true;
+    return H2Y_OK;
+}
+
+int h2y_stream_histogram_ex(h2y_ctx *ctx, int bits, int bit_depth, int full_range, int gbr)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    if (ctx->s_hist) return fail(ctx, H2Y_EINVAL, "the ring counts histograms already");
+    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    uint32_t off[3];
+    int width, height, chroma, depth, full, rgb;
+    if (ctx->s_kind == h2y_ctx::RING_COMPARE) { /* frame A, laid out as k_compare reads it */
+        if (bit_depth < 0 || full_range < 0 || gbr < 0)
+            return fail(ctx, H2Y_EINVAL, "a compare-only ring does not know its frames' bit depth and range: h2y_stream_histogram_ex");
+        const cmp_geom &c = ctx->s_cmp_geom;
+        width = (int)c.width[0], height = (int)(c.n[0] / c.width[0]);
+        chroma = c.n[1] == c.n[0] ? H2Y_CHROMA_444 : H2Y_CHROMA_420;
+        for (int p = 0; p < 3; p++) off[p] = c.a_off[p];
+        depth = full = rgb = 0;
+    } else if (ctx->s_kind == h2y_ctx::RING_INVERSE) { /* the G, B, R planes the inverse kernel writes, s_out_stride bytes apart */
+        const inv_params &p = ctx->s_inv;
+        width = p.width, height = p.height, chroma = H2Y_CHROMA_444;
+        for (int c = 0; c < 3; c++) off[c] = (uint32_t)(c * ctx->s_out_stride / sizeof(uint16_t));
+        depth = p.out_depth, full = p.in_full_range, rgb = 1;
+    } else if (ctx->s_kind == h2y_ctx::RING_FORWARD) { /* the .yuv frame, clamped per plane as write_yuv() does */
+        const h2y_desc &d = ctx->s_desc;
+        width = d.width, height = d.height, chroma = d.dst_chroma_format_idc;
+        cmp_contiguous(width, height, chroma, off);
+        depth = d.dst_bit_depth, full = d.dst_full_range, rgb = 0;
+    } else
+        return fail(ctx, H2Y_EINVAL, "the ring counts histograms already");
+    if (bit_depth >= 0) depth = bit_depth;
+    if (full_range >= 0) full = full_range;
+    if (gbr >= 0) rgb = gbr;
+    if (depth < 8 || depth > 16) return fail(ctx, H2Y_EINVAL, "bit_depth must be 8..16");
+    return hist_arm(ctx, width, height, chroma, depth, full, rgb, bits ? bits : depth, off);
+}
+
+int h2y_stream_histogram(h2y_ctx *ctx, int bits) { return h2y_stream_histogram_ex(ctx, bits, -1, -1, -1); }
+
+int h2y_stream_histogram_result(h2y_ctx *ctx, h2y_histogram_stats *out_stats, uint32_t *out_bins)
+{
+    if (!ctx || !out_stats) return fail(ctx, H2Y_EINVAL, "null argument");
+    if (!ctx->streaming || !ctx->s_hist) return fail(ctx, H2Y_EINVAL, "no stream open that counts histograms");
+    if (ctx->s_lent < 0) return fail(ctx, H2Y_EINVAL, "no output taken yet: h2y_stream_output first");
+    const h2y_ctx::stream_slot &s = ctx->ss[ctx->s_lent];
+    *out_stats = *s.h_hist_stats;
+    if (out_bins) memcpy(out_bins, s.h_hist_bins, (size_t)3u * ctx->s_hist_geom.nbins * sizeof(uint32_t));
+    return H2Y_OK;
+}
+
+/* A ring that only counts: the slot's input is the frame's three planes one after the other (one H2D copy), the device output unused */
+int h2y_histogram_stream_open(h2y_ctx *ctx, int width, int height, int chroma_format_idc, int bit_depth, int full_range, int gbr, int bits,
+                              int depth)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is already open");
+    int rc = hist_check(ctx, width, height, chroma_format_idc, bit_depth, full_range, gbr, bits);
+    if (rc) return rc;
+    if (depth < 2 || depth > 16) return fail(ctx, H2Y_EINVAL, "depth must be 2..16");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    uint32_t off[3];
+    cmp_contiguous(width, height, chroma_format_idc, off);
+    for (int c = 0; c < 3; c++) ctx->s_in_off[c] = off[c] * sizeof(uint16_t);
+    ctx->s_in_bytes = ((size_t)off[2] + (off[2] - off[1])) * sizeof(uint16_t); /* the last plane is as long as the second */
+    rc = stream_alloc(ctx, depth, std::max<size_t>(ctx->s_in_bytes, 16), std::max<size_t>(ctx->s_in_bytes, 16), 16, 16);
+    if (rc) return rc;
+    ctx->s_kind = h2y_ctx::RING_HISTOGRAM;
+    rc = hist_arm(ctx, width, height, chroma_format_idc, bit_depth, full_range, gbr, bits, off);
+    if (rc) {
+        stream_free(ctx);
+        return rc;
+    }
+    return H2Y_OK;
+}
+
+/* k_histogram on the context's stream after the slot's conversion (and comparison) */
+static int hist_run(h2y_ctx *ctx, int slot)
+{
+    return hist_enqueue(ctx, ctx->s_hist_geom, ctx->s_hist_tab + slot, 1, ctx->ss[slot].d_hist);
+}
+
+/* the stats and bins go down on the download stream, after the frame (when it goes down at all) */
+static int hist_download(h2y_ctx *ctx, h2y_ctx::stream_slot &s)
+{
+    const hist_layout L = hist_layout_of(ctx->s_hist_geom.nbins, 1);
+    HIP_TRY(ctx, hipMemcpyAsync(s.h_hist_stats, s.d_hist + L.stats, sizeof(h2y_histogram_stats), hipMemcpyDeviceToHost, ctx->s_d2h));
+    HIP_TRY(ctx, hipMemcpyAsync(s.h_hist_bins, s.d_hist + L.bins, (size_t)3u * ctx->s_hist_geom.nbins * sizeof(uint32_t),
+                                hipMemcpyDeviceToHost, ctx->s_d2h));
+    return H2Y_OK;
+}
+
+/* one frame of a histogram-only ring: H2D of the frame, k_histogram, D2H of the counts */
+static int histogram_stream_submit(h2y_ctx *ctx, int slot)
+{
+    h2y_ctx::stream_slot &s = ctx->ss[slot];
+    if (ctx->s_in_bytes) HIP_TRY(ctx, hipMemcpyAsync(s.d_in, s.h_in, ctx->s_in_bytes, hipMemcpyHostToDevice, ctx->s_h2d));
+    HIP_TRY(ctx, hipEventRecord(s.ev_h2d, ctx->s_h2d));
+    HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s.ev_h2d, 0));
+    int rc = hist_run(ctx, slot);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipEventRecord(s.ev_conv, ctx->stream));
+    HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_d2h, s.ev_conv, 0));
+    rc = hist_download(ctx, s);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipEventRecord(s.ev_done, ctx->s_d2h));
+    s.state = 2;
+    ctx->s_tail = (slot + 1) % (int)ctx->ss.size();
+    return H2Y_OK;
+}
+
 /* one frame of a compare-only ring: H2D of A and B, k_compare, D2H of the stats */
 static int compare_stream_submit(h2y_ctx *ctx, int slot)
 {
@@ -3172,10 +3454,12 @@ static int compare_stream_submit(h2y_ctx *ctx, int slot)
     HIP_TRY(ctx, hipEventRecord(s.ev_h2d, ctx->s_h2d));
     HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s.ev_h2d, 0));
     rc = cmp_run(ctx, slot);
+    if (!rc && ctx->s_hist) rc = hist_run(ctx, slot);
     if (rc) return rc;
     HIP_TRY(ctx, hipEventRecord(s.ev_conv, ctx->stream));
     HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_d2h, s.ev_conv, 0));
     rc = cmp_download(ctx, s);
+    if (!rc && ctx->s_hist) rc = hist_download(ctx, s);
     if (rc) return rc;
     HIP_TRY(ctx, hipEventRecord(s.ev_done, ctx->s_d2h));
     s.state = 2;
@@ -3222,6 +3506,10 @@ static int inverse_stream_submit(h2y_ctx *ctx, int slot)
         rc = cmp_run(ctx, slot);
         if (rc) return rc;
     }
+    if (ctx->s_hist) { /* likewise */
+        rc = hist_run(ctx, slot);
+        if (rc) return rc;
+    }
     HIP_TRY(ctx, hipEventRecord(s.ev_conv, ctx->stream));
     HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_d2h, s.ev_conv, 0));
     if (!keep) {
@@ -3234,6 +3522,10 @@ static int inverse_stream_submit(h2y_ctx *ctx, int slot)
                                         hipMemcpyDeviceToHost, ctx->s_d2h));
     if (ctx->s_cmp) {
         rc = cmp_download(ctx, s);
+        if (rc) return rc;
+    }
+    if (ctx->s_hist) {
+        rc = hist_download(ctx, s);
         if (rc) return rc;
     }
     HIP_TRY(ctx, hipEventRecord(s.ev_done, ctx->s_d2h));
@@ -3271,6 +3563,7 @@ int h2y_stream_submit(h2y_ctx *ctx)
     const h2y_desc *d = &ctx->s_desc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (ctx->s_kind == h2y_ctx::RING_COMPARE) return compare_stream_submit(ctx, slot);
+    if (ctx->s_kind == h2y_ctx::RING_HISTOGRAM) return histogram_stream_submit(ctx, slot);
     if (ctx->s_kind == h2y_ctx::RING_INVERSE) return inverse_stream_submit(ctx, slot);
     const decode_src &src = ctx->s_src;
     const size_t pb = h2y_plane_bytes(d), ob = h2y_frame_bytes(d);
@@ -3315,11 +3608,19 @@ int h2y_stream_submit(h2y_ctx *ctx)
         rc = cmp_run(ctx, slot);
         if (rc) return rc;
     }
+    if (ctx->s_hist) {
+        rc = hist_run(ctx, slot);
+        if (rc) return rc;
+    }
     HIP_TRY(ctx, hipEventRecord(s.ev_conv, ctx->stream));
     HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_d2h, s.ev_conv, 0));
     if (!ctx->s_cmp || ctx->s_cmp_keep) HIP_TRY(ctx, hipMemcpyAsync(s.h_out, s.d_out, ob, hipMemcpyDeviceToHost, ctx->s_d2h));
     if (ctx->s_cmp) {
         rc = cmp_download(ctx, s);
+        if (rc) return rc;
+    }
+    if (ctx->s_hist) {
+        rc = hist_download(ctx, s);
         if (rc) return rc;
     }
     HIP_TRY(ctx, hipEventRecord(s.ev_done, ctx->s_d2h));
@@ -3340,7 +3641,7 @@ int h2y_stream_output(h2y_ctx *ctx, const uint16_t **yuv)
     if (s.state != 2) return fail(ctx, H2Y_EINVAL, "no submitted frame is waiting");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipEventSynchronize(s.ev_done));
-    *yuv = ctx->s_cmp && !ctx->s_cmp_keep ? nullptr : s.h_out;
+    *yuv = (ctx->s_cmp && !ctx->s_cmp_keep) || ctx->s_kind == h2y_ctx::RING_HISTOGRAM ? nullptr : s.h_out;
     s.state = 3;
     ctx->s_lent = ctx->s_head;
     ctx->s_head = (ctx->s_head + 1) % (int)ctx->ss.size();

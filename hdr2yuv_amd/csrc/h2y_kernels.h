@@ -293,4 +293,30 @@ uint32_t h2y_compare_chunks(uint32_t n, uint32_t shift); /* k_compare's units fo
 hipError_t h2y_launch_compare(int grid, hipStream_t st, const cmp_geom &g, const cmp_frame *frames, int n_frames, cmp_partial *partials,
                               h2y_compare_stats *stats);
 
+/* k_histogram and k_histogram_finish (h2y_histogram.hip): code-value bins and legal-range counts of u16 frames, per plane */
+struct hist_geom {
+    uint32_t n[3];      /* samples per plane */
+    uint32_t off[3];    /* plane start in samples from the frame base */
+    uint32_t shift[3];  /* off & 7: the 16-byte groups follow the plane's start */
+    uint32_t vec;       /* bit p: plane p takes 16-byte loads */
+    uint32_t units[3];  /* k_histogram's units per frame and plane */
+    uint32_t lo[3], hi[3]; /* the legal range per plane */
+    uint32_t nbins, down;  /* 2^bits; bin = min(code >> down, nbins - 1) */
+};
+struct hist_frame { /* one frame; base 16-byte aligned */
+    const uint16_t *base;
+};
+struct hist_acc { /* one (frame, plane): zeroed before k_histogram */
+    uint32_t nmin; /* 65535 - min */
+    uint32_t max, below, above, at_low, at_high;
+};
+struct h2y_histogram_stats;
+uint32_t h2y_histogram_units(uint32_t n, uint32_t shift); /* k_histogram's units for a plane of n samples */
+size_t h2y_histogram_lds(uint32_t nbins);                 /* its dynamic LDS bytes */
+int h2y_histogram_grid(int n_cu, const hist_geom &g, int n_frames);
+/* k_histogram over n_frames frames into acc[frame x 3 + plane] and bins[(frame x 3 + plane) x nbins] (both zeroed by the caller),
+ * then k_histogram_finish into stats[frame] */
+hipError_t h2y_launch_histogram(int grid, hipStream_t st, const hist_geom &g, const hist_frame *frames, int n_frames, hist_acc *acc,
+                                uint32_t *bins, h2y_histogram_stats *stats);
+
 #endif

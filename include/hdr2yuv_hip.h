@@ -529,6 +529,52 @@ int h2y_stream_compare_result(h2y_ctx *ctx, h2y_compare_stats *out);
  * h2y_stream_compare_result the stats. */
 int h2y_compare_stream_open(h2y_ctx *ctx, int width, int height, int chroma_format_idc, int sigma, int depth /* 2..16 slots */);
 
+/* ---- code-value histograms and the legal-range check ("hist", "check video range": hdr2yuv.cpp:658, :797 leave them a TODO) --
+ * A frame of u16 samples, three planes in the comparison's geometry (4:2:0 Y, Cb, Cr; 4:4:4 Y, Cb, Cr or G, B, R), counted per
+ * plane on the device (k_histogram, then k_histogram_finish): 2^bits bins, bin = code >> (bit_depth - bits) (a code above
+ * 2^bit_depth - 1 counts in the last bin), and, from the samples themselves, min, max and the samples below, above and at the
+ * limits of the legal range of set_pic_clip() (common.cpp:300-327) at bit_depth: [0, maxCV] in full range; in video range
+ * [minVR, maxVR] for plane 0 and for every plane of a G, B, R frame (gbr 1), [minVRC, maxVRC] for planes 1 and 2 of a YCbCr frame
+ * -- write_yuv()'s per-plane clamp (tiff.cpp:469-478).  Every figure is an exact integer. */
+#define H2Y_HISTOGRAM_FRAMES_PER_LAUNCH 64
+
+typedef struct h2y_histogram_stats {
+    uint64_t samples[3]; /* per plane: samples counted */
+    uint64_t below[3];   /* samples < lo */
+    uint64_t above[3];   /* samples > hi */
+    uint64_t at_low[3];  /* samples == lo */
+    uint64_t at_high[3]; /* samples == hi */
+    uint32_t min[3];     /* smallest and largest sample (0 and 0 for a plane of no samples) */
+    uint32_t max[3];
+    uint32_t lo[3];      /* the legal range the counts are of */
+    uint32_t hi[3];
+    uint32_t nbins;      /* 2^bits: bins per plane */
+    uint32_t shift;      /* bit_depth - bits */
+} h2y_histogram_stats;
+
+/* n_frames device frames (d_frames[f]: the three planes one after the other from a 16-byte aligned base): out_stats[f] (host)
+ * receives frame f's stats and, when out_bins (host) is not NULL, out_bins[(f x 3 + plane) x 2^bits + bin] its bins.
+ * chroma_format_idc 1 or 3 (2: H2Y_EUNSUPPORTED), bit_depth 8..16, bits 1..bit_depth, full_range and gbr 0 or 1.  Launches of up
+ * to H2Y_HISTOGRAM_FRAMES_PER_LAUNCH frames (h2y_last_kernel_ms sums them); synchronous. */
+int h2y_histogram_batch(h2y_ctx *ctx, int width, int height, int chroma_format_idc, int bit_depth, int full_range, int gbr, int bits,
+                        int n_frames, const uint16_t *const *d_frames, h2y_histogram_stats *out_stats, uint32_t *out_bins);
+
+/* Arm an open ring (forward, DPX, TIFF, EXR, inverse, TIFF inverse; with or without h2y_stream_compare) after its *_stream_open
+ * and before its first input: every submitted frame is then counted on the device, after its conversion, on the kernel stream;
+ * the output bytes do not change.  What is counted: on the forward rings the .yuv frame (dst_bit_depth, dst_full_range, YCbCr
+ * limits), on the inverse rings the G, B, R planes before any interleave (out_bit_depth, in_full_range, G/B/R limits).  bits
+ * 1..that bit depth; 0 takes the bit depth itself. */
+int h2y_stream_histogram(h2y_ctx *ctx, int bits);
+/* The same with the frame's bit depth (8..16), range and limits given: required on a compare-only ring (h2y_compare_stream_open),
+ * whose frame A it counts; on the other rings -1 for each takes the ring's own, as h2y_stream_histogram does. */
+int h2y_stream_histogram_ex(h2y_ctx *ctx, int bits, int bit_depth, int full_range, int gbr);
+/* The stats (and, out_bins not NULL, the 3 x 2^bits bins) of the frame that h2y_stream_output returned last. */
+int h2y_stream_histogram_result(h2y_ctx *ctx, h2y_histogram_stats *out_stats, uint32_t *out_bins);
+/* A histogram-only ring: no conversion.  h2y_stream_input lends the frame's three planes one after the other; h2y_stream_output
+ * returns *yuv = NULL and h2y_stream_histogram_result the counts. */
+int h2y_histogram_stream_open(h2y_ctx *ctx, int width, int height, int chroma_format_idc, int bit_depth, int full_range, int gbr,
+                              int bits, int depth /* 2..16 slots */);
+
 /* Timing of the last h2y_convert_batch*() (or h2y_inverse_*, h2y_dpx_decode_batch, h2y_tiff_decode_batch,
  * h2y_rgb_interleave_batch, h2y_exr_decode_batch, h2y_compare_batch) call measured with HIP events on
  * the stream the kernels ran on: total ms over the main kernels and how many

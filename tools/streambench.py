@@ -44,6 +44,15 @@ Prints one line per figure, then one JSON line with all of them.
      armed with keep_output 1 (the reference goes up, the frame comes down) and armed with keep_output 0 (only the stats come
      down), on the same pictures;
   3. frames/s of the compare-only ring (both frames go up, the stats come down).
+Prints one line per figure, then one JSON line with all of them.
+
+`streambench.py histogram`: code-value histograms on 4K frames:
+  1. the kernel time of h2y_histogram_batch (the zeroing, k_histogram and k_histogram_finish) over 64 distinct frames per call
+     (HIP events, median of five), the bytes per frame it reads over that time and their share of the 8 TB/s HBM peak, for
+     10-bit 4:2:0 (24.9 MB) and 16-bit 4:4:4 (49.8 MB) frames at full resolution, on uniform random, constant and
+     one-code-per-row content;
+  2. frames/s from host memory of the forward ring (as `compare`) unarmed and armed with h2y_stream_histogram;
+  3. frames/s of the histogram-only ring on the 10-bit 4:2:0 frames (the frame goes up, the counts come down).
 Prints one line per figure, then one JSON line with all of them."""
 import os
 import sys
@@ -558,6 +567,113 @@ def compare_main():
     print(json.dumps({"streambench_compare": res}), flush=True)
 
 
+def histogram_main():
+    import json
+
+    import torch
+
+    w, hh, nb, reps = 3840, 2160, 64, 5
+    n, nc = w * hh, (w // 2) * (hh // 2)
+    nf = int(os.environ.get("N", "60"))
+    depth = 3
+    rng = np.random.default_rng(19)
+    ctx = h.Context(0)
+    res = {"width": w, "height": hh, "frames_per_call": nb, "reps": reps, "ring_frames": nf, "ring_depth": depth, "hbm_peak_tbs": 8.0}
+
+    # 1. the kernels over 64 distinct frames on the device
+    for chroma, bd in ((h.CHROMA_420, 10), (h.CHROMA_444, 16)):
+        total = n + 2 * (nc if chroma == h.CHROMA_420 else n)
+        for content in ("uniform", "constant", "row"):
+            if content == "uniform":
+                frames = [torch.randint(0, 1 << bd, (total,), dtype=torch.int32, device="cuda").to(torch.int16) for _ in range(nb)]
+            elif content == "constant":
+                frames = [torch.full((total,), (37 * k + 100) % (1 << bd), dtype=torch.int32, device="cuda").to(torch.int16)
+                          for k in range(nb)]
+            else:
+                rows = total // w
+                frames = [(((torch.arange(rows, device="cuda") * 37 + k) % (1 << bd)).to(torch.int16)).repeat_interleave(w)
+                          for k in range(nb)]
+            frames = [f.contiguous() for f in frames]
+            torch.cuda.synchronize()
+            ks = []
+            for rep in range(reps + 1):  # rep 0 warms up
+                ctx.histogram_batch(w, hh, chroma, bd, 0, 0, bd, frames, want_bins=False)
+                if rep:
+                    ks.append(ctx.last_kernel_ms()[0] / nb)
+            k_ms = float(np.median(ks))
+            nbytes = 2 * total
+            tbs = nbytes / (k_ms * 1e-3) / 1e12
+            key = f"k_histogram_{'420' if chroma == h.CHROMA_420 else '444'}_{bd}bit_{content}"
+            res[key] = dict(kernel_us_per_frame=round(k_ms * 1e3, 2), bytes_per_frame=nbytes, kernel_tbs=round(tbs, 2),
+                            hbm_peak_fraction=round(tbs / 8.0, 3), variant=ctx.last_kernel_variant())
+            print(f"{key:34s} {nb} frames per call: {k_ms*1e3:6.2f} us/frame  {nbytes/1e6:6.1f} MB/frame  {tbs:5.2f} TB/s = "
+                  f"{tbs/8.0*100:4.1f} % of 8 TB/s", flush=True)
+            del frames
+            torch.cuda.empty_cache()
+
+    def ring(open_fn, fill, arm=False):
+        open_fn()
+        if arm:
+            ctx.stream_histogram()
+        inflight = 0
+        t0 = time.perf_counter()
+        for _ in range(nf):
+            fill(ctx.stream_input())
+            ctx.stream_submit()
+            inflight += 1
+            if inflight == depth - 1:
+                ctx.stream_output()
+                if arm:
+                    ctx.stream_histogram_result()
+                inflight -= 1
+        while inflight:
+            ctx.stream_output()
+            if arm:
+                ctx.stream_histogram_result()
+            inflight -= 1
+        dt = (time.perf_counter() - t0) / nf
+        ctx.stream_close()
+        return dt
+
+    # 2. the forward ring: 16-bit G,B,R -> BT.2020nc 10-bit 4:2:0 box, unarmed and armed
+    planes = [rng.integers(0, 65536, n, dtype=np.uint16) for _ in range(3)]
+    d = h.make_desc(w, hh, sample=h.SAMPLE_U16, src_depth=16, dst_depth=10, src_transfer=1, dst_transfer=1, src_primaries=1,
+                    dst_primaries=1, dst_matrix=h.MATRIX_BT2020NC, resampler=0)
+    yuv = ctx.convert_frame(d, planes)
+
+    def fill_planes(slot):
+        for c in range(3):
+            slot[c][:] = planes[c]
+
+    def open_fwd():
+        ctx.stream_open(d, depth)
+
+    ring(open_fwd, fill_planes)  # warm-up
+    t_plain = ring(open_fwd, fill_planes)
+    t_armed = ring(open_fwd, fill_planes, True)
+    res["forward_ring"] = dict(unarmed_fps=round(1 / t_plain, 1), armed_fps=round(1 / t_armed, 1), armed_share=round(t_plain / t_armed, 3),
+                               unarmed_ms=round(t_plain * 1e3, 2), armed_ms=round(t_armed * 1e3, 2))
+    print(f"forward ring from host memory: unarmed {1/t_plain:6.1f} frames/s   armed {1/t_armed:6.1f} frames/s "
+          f"({t_plain/t_armed*100:5.1f} %)", flush=True)
+
+    # 3. the histogram-only ring
+    yuv_planes = [yuv[:n], yuv[n:n + nc], yuv[n + nc:]]
+
+    def fill_yuv(slot):
+        for c in range(3):
+            slot[c][:] = yuv_planes[c]
+
+    def open_hist():
+        ctx.histogram_stream_open(w, hh, h.CHROMA_420, 10, 0, 0, 10, depth)
+
+    ring(open_hist, fill_yuv)
+    t_hist = ring(open_hist, fill_yuv)
+    res["histogram_only_ring"] = dict(fps=round(1 / t_hist, 1), ms=round(t_hist * 1e3, 2))
+    print(f"histogram-only ring from host memory: {1/t_hist:6.1f} frames/s ({t_hist*1e3:6.2f} ms/frame)", flush=True)
+    ctx.close()
+    print(json.dumps({"streambench_histogram": res}), flush=True)
+
+
 if __name__ == "__main__":
     if sys.argv[1:] == ["inverse"]:
         inverse_main()
@@ -569,5 +685,7 @@ if __name__ == "__main__":
         exr_main()
     elif sys.argv[1:] == ["compare"]:
         compare_main()
+    elif sys.argv[1:] == ["histogram"]:
+        histogram_main()
     else:
         main()
