@@ -35,11 +35,12 @@ EXPORTS = [
     "h2y_tiff_inverse_stream_open", "h2y_exr_parse", "h2y_exr_unpack", "h2y_exr_decode_batch", "h2y_exr_stream_open",
     "h2y_compare_batch", "h2y_stream_compare", "h2y_stream_reference", "h2y_stream_compare_result", "h2y_compare_stream_open",
     "h2y_histogram_batch", "h2y_stream_histogram", "h2y_stream_histogram_ex", "h2y_stream_histogram_result",
-    "h2y_histogram_stream_open",
+    "h2y_histogram_stream_open", "h2y_ssim_batch", "h2y_stream_ssim", "h2y_stream_ssim_result",
 ]
 
 COMPARE_FRAMES_PER_LAUNCH = 64
 HISTOGRAM_FRAMES_PER_LAUNCH = 64
+SSIM_FRAMES_PER_LAUNCH = 64
 
 
 class H2YError(RuntimeError):
@@ -160,6 +161,19 @@ class H2YHistogramStats(C.Structure):
 
     def __repr__(self):
         return f"H2YHistogramStats({self.as_dict()})"
+
+
+class H2YSsimStats(C.Structure):
+    """h2y_ssim_stats: per plane (0, 1, 2 = Y, Cb, Cr or G, B, R) the 8x8 windows, the sum over them of rint(SSIM x 2^32) and
+    the plane's SSIM; all weights the planes by their sample counts."""
+
+    _fields_ = [("windows", C.c_uint64 * 3), ("sum_q", C.c_int64 * 3), ("ssim", C.c_double * 3), ("all", C.c_double)]
+
+    def as_dict(self):
+        return {k: (list(v) if not isinstance(v := getattr(self, k), (int, float)) else v) for k, _ in self._fields_}
+
+    def __repr__(self):
+        return f"H2YSsimStats({self.as_dict()})"
 
 
 def make_desc(width, height, *, sample=SAMPLE_F32, src_depth=32, dst_depth=10, src_transfer=TRANSFER_LINEAR,
@@ -336,6 +350,12 @@ def load_library():
     L.h2y_stream_histogram_result.restype = C.c_int
     L.h2y_histogram_stream_open.argtypes = [C.c_void_p] + [C.c_int] * 8
     L.h2y_histogram_stream_open.restype = C.c_int
+    L.h2y_ssim_batch.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(H2YSsimStats)]
+    L.h2y_ssim_batch.restype = C.c_int
+    L.h2y_stream_ssim.argtypes = [C.c_void_p, C.c_int]
+    L.h2y_stream_ssim.restype = C.c_int
+    L.h2y_stream_ssim_result.argtypes = [C.c_void_p, C.POINTER(H2YSsimStats)]
+    L.h2y_stream_ssim_result.restype = C.c_int
     L.h2y_stream_open.argtypes = [C.c_void_p, C.POINTER(H2YDesc), C.c_int]
     L.h2y_stream_input.restype = C.c_int
     L.h2y_stream_input.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
@@ -677,6 +697,18 @@ class Context:
                                                  None if bins is None else bins.ctypes.data))
         return list(out[:n]), bins
 
+    def ssim_batch(self, width, height, chroma, bit_depth, frames_a, frames_b):
+        """k_ssim on device frame pairs (tensors or pointers, each frame's planes contiguous from a 16-byte aligned base):
+        a list of H2YSsimStats, one per pair."""
+        n = len(frames_a)
+        if len(frames_b) != n:
+            raise ValueError("frames_a and frames_b differ in length")
+        pa = (C.c_void_p * max(n, 1))(*[self._ptr(x) for x in frames_a])
+        pb = (C.c_void_p * max(n, 1))(*[self._ptr(x) for x in frames_b])
+        out = (H2YSsimStats * max(n, 1))()
+        self._check(self.lib.h2y_ssim_batch(self.h, width, height, chroma, bit_depth, n, pa, pb, out))
+        return list(out[:n])
+
     # ---- host <-> device pipeline -----------------------------------------------------------
     def stream_histogram(self, bits=0, bit_depth=None, full_range=None, gbr=None) -> None:
         """Arm the open ring: every frame is counted on the device (h2y_stream_histogram; with bit_depth, full_range and gbr
@@ -725,6 +757,16 @@ class Context:
     def stream_compare_result(self) -> H2YCompareStats:
         st = H2YCompareStats()
         self._check(self.lib.h2y_stream_compare_result(self.h, C.byref(st)))
+        return st
+
+    def stream_ssim(self, bit_depth=-1) -> None:
+        """Arm a compare-armed ring for SSIM too (bit_depth -1: the ring's own; a compare-only ring needs it given)."""
+        self._check(self.lib.h2y_stream_ssim(self.h, bit_depth))
+
+    def stream_ssim_result(self) -> H2YSsimStats:
+        """The H2YSsimStats of the frame stream_output returned last."""
+        st = H2YSsimStats()
+        self._check(self.lib.h2y_stream_ssim_result(self.h, C.byref(st)))
         return st
 
     def compare_stream_open(self, width, height, chroma, sigma, depth=3) -> None:

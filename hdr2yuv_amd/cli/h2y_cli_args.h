@@ -33,6 +33,9 @@
  *             may be left out: the run converts and compares and writes nothing, its output type taken from R.
  *             --compare_only 1 (an addition) compares --src_filename (.yuv or .rgb, read with the --src_* size, depth and chroma
  *             format -- 1 or 3 for .yuv, 3 for .rgb --, from --src_start_frame on) with R (same layout, from its frame 0), --n_frames of each; no conversion.
+ * --ssim 1 (an addition: the "SNR, etc." hdr2yuv.cpp:826 leaves a TODO): SSIM of every compared frame beside its PSNR, on the
+ *             frames the comparison reads (8x8 windows at a stride of 4 on code values, include/hdr2yuv_hip.h).  Refused (exit 1)
+ *             without a comparison, for 4:2:2 frames and for a plane under 8x8 samples.
  * --histogram FILE [--histogram_bits B] [--check_range 1] [--histogram_only 1] (additions: the "hist" and "check video range" the
  *             reference leaves a TODO at hdr2yuv.cpp:658 and :797): every frame the run produces is counted on the device -- the .yuv
  *             frames (destination depth and range, Y,Cb,Cr limits), the G,B,R planes of the inverse flow (destination depth, source
@@ -76,6 +79,9 @@ struct cli_args {
     const char *ref = nullptr;
     int sigma = 0, compare_only = 0;
     bool sigma_given = false;
+    /* --ssim 1: SSIM beside the comparison */
+    int ssim = 0;
+    bool ssim_given = false;
     /* the histogram: --histogram FILE, --histogram_bits (0: the counted frames' depth), --histogram_only, --check_range; what is
      * counted, resolved by cli_resolve_histogram: depth, range, G,B,R limits, chroma format */
     const char *hist = nullptr;
@@ -133,7 +139,8 @@ static inline void cli_help()
            "  unset source attributes are 0, unset destination attributes take the source's (as the reference resolves them)\n"
            "  additional: [--synthetic SEEDFRAME] [--device D] [--gpus N [--devices d0,d1,..]] [--dry_run 1]\n"
            "  compare: [--ref_filename R.yuv|R.rgb [--sigma_compare S]] (the output against R, frame by frame; without\n"
-           "  --dst_filename nothing is written), [--compare_only 1] (--src_filename against R, no conversion)\n"
+           "  --dst_filename nothing is written), [--compare_only 1] (--src_filename against R, no conversion), [--ssim 1] (SSIM\n"
+           "  beside the PSNR)\n"
            "  histogram: [--histogram FILE [--histogram_bits B] [--check_range 1]] (code values of every frame the run produces,\n"
            "  totals into FILE; exit status 4 on a sample outside the legal range), [--histogram_only 1] (--src_filename, no conversion)\n"
            "input by extension: .yuv .rgb (16-bit planar), .f32 .f16 (raw planar float / half, plane order G,B,R: what\n"
@@ -160,6 +167,7 @@ static inline void cli_parse(cli_args &a, int argc, char **argv)
         else if (is("--ref_filename")) a.ref = val();
         else if (is("--sigma_compare")) { a.sigma = atoi(val()); a.sigma_given = true; }
         else if (is("--compare_only")) a.compare_only = atoi(val());
+        else if (is("--ssim")) { a.ssim = atoi(val()); a.ssim_given = true; }
         else if (is("--histogram")) a.hist = val();
         else if (is("--histogram_bits")) { a.hist_bits = atoi(val()); a.hist_bits_given = true; }
         else if (is("--histogram_only")) a.hist_only = atoi(val());
@@ -329,11 +337,41 @@ static inline int cli_resolve_histogram(cli_args &a)
 /* hdr2yuv.cpp:265-572 and the attribute overrides of read_file(), then what --histogram counts; returns the number of argument
  * errors */
 static inline int cli_resolve_convert(cli_args &a);
+static inline int cli_resolve_ssim(cli_args &a);
 static inline int cli_resolve(cli_args &a)
 {
     int arg_errors = a.hist_only ? cli_resolve_histogram_only(a) : a.compare_only ? cli_resolve_compare(a) : cli_resolve_convert(a);
     if (a.hist || a.hist_bits_given || a.hist_only || a.check_range) arg_errors += cli_resolve_histogram(a);
+    if (a.ssim_given) arg_errors += cli_resolve_ssim(a);
     return arg_errors;
+}
+
+/* --ssim: valid wherever a comparison runs, on frames of 4:2:0 or 4:4:4 whose every plane holds an 8x8 window; returns the number
+ * of argument errors */
+static inline int cli_resolve_ssim(cli_args &a)
+{
+    printf("ssim: %d\n", a.ssim);
+    if (a.ssim != 0 && a.ssim != 1) {
+        printf("WARNING: ssim(%d) not 0 or 1\n", a.ssim);
+        return 1;
+    }
+    if (!a.ssim) return 0;
+    if (!a.ref) {
+        printf("WARNING: --ssim 1 needs a comparison: --ref_filename R (with or without --dst_filename, or with --compare_only 1)\n");
+        return 1;
+    }
+    const bool yuv = a.compare_only ? a.in_type == CLI_IN_YUV : a.out_type == CLI_OUT_YUV;
+    const int chroma = yuv ? a.out.chroma_format_idc : H2Y_CHROMA_444, sub = chroma == H2Y_CHROMA_420;
+    if (chroma != H2Y_CHROMA_420 && chroma != H2Y_CHROMA_444) {
+        printf("WARNING: --ssim 1 compares 4:2:0 or 4:4:4 frames, not chroma_format_idc %d\n", chroma);
+        return 1;
+    }
+    if ((a.out.width >> sub) < 8 || (a.out.height >> sub) < 8) {
+        printf("WARNING: --ssim 1 needs every plane at least 8x8 (one window): %dx%d chroma_format_idc %d is smaller\n", a.out.width,
+               a.out.height, chroma);
+        return 1;
+    }
+    return 0;
 }
 
 static inline int cli_resolve_convert(cli_args &a)

@@ -43,6 +43,13 @@
  * and samples; max_abs the largest |a - b|, over the count of |a - b| > S (S 0 by default); first_over the first such sample in
  * frame, plane and raster order, a the output's (the source's) sample, b R's.  Exit status 3 when S was given and over > 0.
  *
+ * SSIM (--ssim 1 beside a comparison; h2y_cli_args.h): each GPU thread arms its ring for SSIM too (h2y_stream_ssim) and keeps
+ * the figures of frame k by its index; the report follows the compare report, so it is the same for any --gpus.  Planes as there,
+ * values "%.6f", dB = -10 * log10(1 - x) "%.4f" or "inf" for x = 1:
+ *   ssim frame <k> <P0> <v> <P1> <v> <P2> <v> all <v> db <P0> <d> <P1> <d> <P2> <d> all <d>      one line per frame, in order
+ *   ssim summary frames <N> <P0> <m> <P1> <m> <P2> <m> all <m> db ...     the means over frames (summed in frame order), dB of them
+ *   ssim worst frame <k> all <v>                                          the lowest all, the first such frame on ties
+ *
  * Histogram (--histogram FILE [--histogram_bits B] [--check_range 1], or --histogram_only 1; h2y_cli_args.h): each GPU thread arms
  * its ring (h2y_stream_histogram; h2y_stream_histogram_ex on a compare-only ring) or opens a histogram-only ring, keeps the stats
  * of frame k by its index and sums its frames' bins; the report is printed once every thread is done, so it, and FILE, are the
@@ -469,7 +476,8 @@ struct histogram_io {
  * device -- the ring of h2y_dpx_stream_open; tiff likewise, file tiff[k] through h2y_tiff_stream_open) */
 static void run_block(const cli_args &a, const h2y_desc &d, const std::vector<dpx_src> &dpx, const h2y_dpx_info &di,
                       const std::vector<tiff_src> &tiff, const h2y_tiff_info &ti, const std::vector<std::string> &exr,
-                      const h2y_exr_info &xi, int fd_out, off_t base, std::vector<h2y_compare_stats> *stats, histogram_io *hist, block *b)
+                      const h2y_exr_info &xi, int fd_out, off_t base, std::vector<h2y_compare_stats> *stats,
+                      std::vector<h2y_ssim_stats> *ssim, histogram_io *hist, block *b)
 {
     h2y_ctx *ctx = nullptr;
     FILE *fin = nullptr;
@@ -497,6 +505,7 @@ static void run_block(const cli_args &a, const h2y_desc &d, const std::vector<dp
     compare_io cmp;
     if (!cmp.open(a, b->first, 0, ob, stats)) return fail(std::string("unable to read ") + a.ref);
     if (cmp.ref && h2y_stream_compare(ctx, a.sigma, a.dst ? 1 : 0)) return fail(h2y_last_error(ctx));
+    if (a.ssim && h2y_stream_ssim(ctx, -1)) return fail(h2y_last_error(ctx));
     if (hist->on && h2y_stream_histogram(ctx, a.hist_bits)) return fail(h2y_last_error(ctx));
     std::unique_ptr<unpack_pool> pool;
     std::vector<h2y_exr_chunk> chunks;
@@ -510,6 +519,7 @@ static void run_block(const cli_args &a, const h2y_desc &d, const std::vector<dp
         if (h2y_stream_output(ctx, &yuv)) { fail(h2y_last_error(ctx)); return false; }
         const long k = b->first + b->done;
         if (cmp.ref && h2y_stream_compare_result(ctx, &(*cmp.stats)[k])) { fail(h2y_last_error(ctx)); return false; }
+        if (a.ssim && h2y_stream_ssim_result(ctx, &(*ssim)[k])) { fail(h2y_last_error(ctx)); return false; }
         if (!hist->take(ctx, k)) { fail(h2y_last_error(ctx)); return false; }
         if (a.dst && !write_at(fd_out, yuv, ob, base + (off_t)k * (off_t)ob)) { fail(std::string("short write to ") + a.dst); return false; }
         if (a.verbose > 0 && a.dst) printf("frame %ld: %zu bytes written to %s (device %d)\n", k, ob, a.dst, b->device);
@@ -582,7 +592,7 @@ struct tiff_wrap {
 /* .yuv -> RGB (matrix_inverse): frames [first, first+count) through one context's pinned inverse ring, as run_block; .tiff
  * output: the ring with the interleave (h2y_tiff_inverse_stream_open), frame k into its own file, head + samples + tail */
 static void run_block_inverse(const cli_args &a, const tiff_wrap &tw, int fd_out, off_t base, std::vector<h2y_compare_stats> *stats,
-                              histogram_io *hist, block *b)
+                              std::vector<h2y_ssim_stats> *ssim, histogram_io *hist, block *b)
 {
     h2y_ctx *ctx = nullptr;
     FILE *fin = nullptr;
@@ -608,6 +618,7 @@ static void run_block_inverse(const cli_args &a, const tiff_wrap &tw, int fd_out
     compare_io cmp;
     if (!cmp.open(a, b->first, 2 * n, out_frame, stats)) return fail(std::string("unable to read ") + a.ref);
     if (cmp.ref && h2y_stream_compare(ctx, a.sigma, a.dst ? 1 : 0)) return fail(h2y_last_error(ctx));
+    if (a.ssim && h2y_stream_ssim(ctx, -1)) return fail(h2y_last_error(ctx));
     if (hist->on && h2y_stream_histogram(ctx, a.hist_bits)) return fail(h2y_last_error(ctx));
     long in_flight = 0;
     auto drain_one = [&]() -> bool {
@@ -615,6 +626,7 @@ static void run_block_inverse(const cli_args &a, const tiff_wrap &tw, int fd_out
         if (h2y_stream_output(ctx, &gbr)) { fail(h2y_last_error(ctx)); return false; }
         const long k = b->first + b->done;
         if (cmp.ref && h2y_stream_compare_result(ctx, &(*cmp.stats)[k])) { fail(h2y_last_error(ctx)); return false; }
+        if (a.ssim && h2y_stream_ssim_result(ctx, &(*ssim)[k])) { fail(h2y_last_error(ctx)); return false; }
         if (!hist->take(ctx, k)) { fail(h2y_last_error(ctx)); return false; }
         if (!a.dst) {
             b->done++;
@@ -667,7 +679,7 @@ static void run_block_inverse(const cli_args &a, const tiff_wrap &tw, int fd_out
 
 /* --compare_only: frames [first, first+count) of the source against the same frames of R through one compare-only ring */
 static void run_block_compare(const cli_args &a, size_t plane_bytes, size_t frame_bytes, std::vector<h2y_compare_stats> *stats,
-                              histogram_io *hist, block *b)
+                              std::vector<h2y_ssim_stats> *ssim, histogram_io *hist, block *b)
 {
     h2y_ctx *ctx = nullptr;
     FILE *fin = nullptr;
@@ -685,12 +697,14 @@ static void run_block_compare(const cli_args &a, size_t plane_bytes, size_t fram
     if (!cmp.open(a, b->first, plane_bytes, frame_bytes, stats)) return fail(std::string("unable to read ") + a.ref);
     const int depth = 3;
     if (h2y_compare_stream_open(ctx, a.in.width, a.in.height, a.in.chroma_format_idc, a.sigma, depth)) return fail(h2y_last_error(ctx));
+    if (a.ssim && h2y_stream_ssim(ctx, a.in.bit_depth)) return fail(h2y_last_error(ctx));
     if (hist->on && h2y_stream_histogram_ex(ctx, a.hist_bits, a.hist_depth, a.hist_full, a.hist_gbr)) return fail(h2y_last_error(ctx));
     long in_flight = 0;
     auto drain_one = [&]() -> bool {
         const uint16_t *none = nullptr;
         const long k = b->first + b->done;
-        if (h2y_stream_output(ctx, &none) || h2y_stream_compare_result(ctx, &(*stats)[k]) || !hist->take(ctx, k)) {
+        if (h2y_stream_output(ctx, &none) || h2y_stream_compare_result(ctx, &(*stats)[k]) ||
+            (a.ssim && h2y_stream_ssim_result(ctx, &(*ssim)[k])) || !hist->take(ctx, k)) {
             fail(h2y_last_error(ctx));
             return false;
         }
@@ -860,6 +874,41 @@ static int compare_report(const cli_args &a, bool yuv, int bit_depth, const std:
     return a.sigma_given && first_f >= 0 ? 3 : 0;
 }
 
+static std::string ssim_db(double x)
+{
+    if (x >= 1.0) return "inf";
+    char s[32];
+    snprintf(s, sizeof s, "%.4f", -10.0 * log10(1.0 - x));
+    return s;
+}
+
+/* the SSIM report of the header comment */
+static void ssim_report(bool yuv, const std::vector<h2y_ssim_stats> &st)
+{
+    static const char *const kYuv[3] = {"Y", "Cb", "Cr"}, *const kRgb[3] = {"G", "B", "R"};
+    const char *const *name = yuv ? kYuv : kRgb;
+    auto line = [&](const double (&v)[3], double all) {
+        for (int p = 0; p < 3; p++) printf(" %s %.6f", name[p], v[p]);
+        printf(" all %.6f db", all);
+        for (int p = 0; p < 3; p++) printf(" %s %s", name[p], ssim_db(v[p]).c_str());
+        printf(" all %s\n", ssim_db(all).c_str());
+    };
+    double mean[3] = {0, 0, 0}, mean_all = 0;
+    size_t worst = 0;
+    for (size_t k = 0; k < st.size(); k++) {
+        printf("ssim frame %zu", k);
+        line(st[k].ssim, st[k].all);
+        for (int p = 0; p < 3; p++) mean[p] += st[k].ssim[p];
+        mean_all += st[k].all;
+        if (st[k].all < st[worst].all) worst = k;
+    }
+    if (st.empty()) return;
+    for (int p = 0; p < 3; p++) mean[p] /= (double)st.size();
+    printf("ssim summary frames %zu", st.size());
+    line(mean, mean_all / (double)st.size());
+    printf("ssim worst frame %zu all %.6f\n", worst, st[worst].all);
+}
+
 int main(int argc, char **argv)
 {
     cli_args a;
@@ -1010,6 +1059,7 @@ int main(int argc, char **argv)
         at += blocks[r].count;
     }
     std::vector<h2y_compare_stats> stats(a.ref ? (size_t)frames : 0);
+    std::vector<h2y_ssim_stats> sstats(a.ssim ? (size_t)frames : 0);
     std::vector<h2y_histogram_stats> hstats(a.hist ? (size_t)frames : 0);
     std::vector<std::array<uint32_t, 3>> hocc(a.hist ? (size_t)frames : 0);
     std::vector<histogram_io> hist(a.gpus);
@@ -1017,9 +1067,9 @@ int main(int argc, char **argv)
     auto work = [&](block *b) {
         histogram_io *hi = &hist[b - blocks.data()];
         if (a.hist_only) run_block_histogram(a, (size_t)a.in.width * a.in.height * 2, in_frame_bytes, hi, b);
-        else if (a.compare_only) run_block_compare(a, (size_t)a.in.width * a.in.height * 2, in_frame_bytes, &stats, hi, b);
-        else if (a.inverse) run_block_inverse(a, tw, fd, base, &stats, hi, b);
-        else run_block(a, d, dpx, di, tiff, ti, exr, xi, fd, base, &stats, hi, b);
+        else if (a.compare_only) run_block_compare(a, (size_t)a.in.width * a.in.height * 2, in_frame_bytes, &stats, &sstats, hi, b);
+        else if (a.inverse) run_block_inverse(a, tw, fd, base, &stats, &sstats, hi, b);
+        else run_block(a, d, dpx, di, tiff, ti, exr, xi, fd, base, &stats, &sstats, hi, b);
     };
     if (a.gpus == 1) work(&blocks[0]);
     else {
@@ -1034,7 +1084,9 @@ int main(int argc, char **argv)
             printf("ERROR (device %d, frames %ld..%ld): %s\n", blocks[r].device, blocks[r].first, blocks[r].first + blocks[r].count - 1, blocks[r].err.c_str());
             rc = 1;
         }
-    if (!rc && a.ref) rc = compare_report(a, cmp_yuv, a.out.bit_depth, stats);
+    const bool compared = !rc && a.ref;
+    if (compared) rc = compare_report(a, cmp_yuv, a.out.bit_depth, stats);
+    if (compared && a.ssim) ssim_report(cmp_yuv, sstats);
     if ((!rc || rc == 3) && a.hist) { /* the bins of every thread, summed (the same totals for any split) */
         std::vector<uint64_t> total(hist[0].total.size(), 0u);
         for (const auto &x : hist)

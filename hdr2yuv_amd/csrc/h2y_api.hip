@@ -218,6 +218,11 @@ struct h2y_ctx {
     /* h2y_histogram_batch's device workspace: per launch the counts, the bins and the stats (hist_layout) */
     char *d_hist = nullptr;
     size_t hist_cap = 0;
+    /* h2y_ssim_batch's (and an armed ring's) k_ssim partials, and the batch's stats */
+    int64_t *d_ssim_part = nullptr;
+    size_t ssim_part_cap = 0;
+    h2y_ssim_stats *d_ssim_stats = nullptr;
+    size_t ssim_stats_cap = 0;
 
     /* staging for the host-buffer entry */
     void *d_in = nullptr;
@@ -244,6 +249,8 @@ struct h2y_ctx {
         char *d_hist = nullptr;
         h2y_histogram_stats *h_hist_stats = nullptr;
         uint32_t *h_hist_bins = nullptr;
+        /* a ring armed by h2y_stream_ssim: the frame's SSIM on the device and pinned */
+        h2y_ssim_stats *d_ssim = nullptr, *h_ssim = nullptr;
     };
     std::vector<stream_slot> ss;
     hipStream_t s_h2d = nullptr, s_d2h = nullptr;
@@ -278,6 +285,9 @@ struct h2y_ctx {
     bool s_hist = false;
     hist_geom s_hist_geom{};
     hist_frame *s_hist_tab = nullptr;
+    /* a compare-armed ring armed by h2y_stream_ssim too: k_ssim's geometry (its frames are k_compare's, s_cmp_tab) */
+    bool s_ssim = false;
+    ssim_geom s_ssim_geom{};
     size_t s_ref_bytes = 0, s_ref_stats_off = 0; /* the pinned reference's bytes; where the stats lie in its device twin */
     int slot_base = 0; /* run_frames(): first entry of d_frames/h_frames to use (one per stream slot) */
     float last_ms = 0.f;
@@ -1459,6 +1469,8 @@ void h2y_ctx_destroy(h2y_ctx *ctx)
     (void)hipFree(ctx->d_cmp_part);
     (void)hipFree(ctx->d_cmp_stats);
     (void)hipFree(ctx->d_hist);
+    (void)hipFree(ctx->d_ssim_part);
+    (void)hipFree(ctx->d_ssim_stats);
     (void)hipFree(ctx->d_in);
     (void)hipFree(ctx->d_out);
     if (ctx->fir_stream) {
@@ -2120,6 +2132,8 @@ static void stream_free(h2y_ctx *ctx)
         if (s.d_hist) (void)hipFree(s.d_hist);
         if (s.h_hist_stats) (void)hipHostFree(s.h_hist_stats);
         if (s.h_hist_bins) (void)hipHostFree(s.h_hist_bins);
+        if (s.d_ssim) (void)hipFree(s.d_ssim);
+        if (s.h_ssim) (void)hipHostFree(s.h_ssim);
     }
     ctx->ss.clear();
     if (ctx->s_h2d) (void)hipStreamDestroy(ctx->s_h2d);
@@ -2132,6 +2146,7 @@ static void stream_free(h2y_ctx *ctx)
     if (ctx->s_hist_tab) (void)hipFree(ctx->s_hist_tab);
     ctx->s_hist_tab = nullptr;
     ctx->s_hist = false;
+    ctx->s_ssim = false;
     ctx->streaming = false;
     ctx->s_kind = h2y_ctx::RING_FORWARD;
     ctx->s_src = decode_src();
@@ -3180,6 +3195,143 @@ static int cmp_download(h2y_ctx *ctx, h2y_ctx::stream_slot &s)
     return H2Y_OK;
 }
 
+/* ---- SSIM beside the comparison (hdr2yuv.cpp:826) ------------------------------------------------------------------------ */
+
+/* k_ssim's geometry: the comparison's planes (4:2:0: Y, then two chroma planes of (width >> 1) x (height >> 1)) starting at a_off /
+ * b_off samples from the two frames' bases, and the constants of bit_depth, computed once here in binary64, left to right */
+static ssim_geom ssim_geom_of(int width, int height, int chroma, int bit_depth, const uint32_t a_off[3], const uint32_t b_off[3])
+{
+    ssim_geom g{};
+    const bool sub = chroma == H2Y_CHROMA_420;
+    for (int p = 0; p < 3; p++) {
+        g.pw[p] = p && sub ? (uint32_t)(width >> 1) : (uint32_t)width;
+        g.ph[p] = p && sub ? (uint32_t)(height >> 1) : (uint32_t)height;
+        g.a_off[p] = a_off[p];
+        g.b_off[p] = b_off[p];
+        g.strips[p] = h2y_ssim_strips(g.pw[p]);
+        g.units[p] = g.strips[p] * h2y_ssim_segments(g.ph[p]);
+    }
+    g.wide = bit_depth > 12;
+    const double M = (double)((1u << bit_depth) - 1u);
+    g.c1 = ((0.01 * 0.01) * M) * M * 64.0;
+    g.c2 = (((0.03 * 0.03) * M) * M * 64.0) * 63.0;
+    return g;
+}
+
+static int ssim_check(h2y_ctx *ctx, int width, int height, int chroma, int bit_depth)
+{
+    if (width < 1 || height < 1 || (uint64_t)width * (uint64_t)height >= (1ull << 28)) return fail(ctx, H2Y_EINVAL, "bad picture size");
+    if (chroma == 2) return fail(ctx, H2Y_EUNSUPPORTED, "chroma_format_idc 2 (4:2:2) has no SSIM on this path");
+    if (chroma != H2Y_CHROMA_420 && chroma != H2Y_CHROMA_444) return fail(ctx, H2Y_EINVAL, "chroma_format_idc must be 1 or 3");
+    if (bit_depth < 8 || bit_depth > 16) return fail(ctx, H2Y_EINVAL, "bit_depth must be 8..16");
+    const int sub = chroma == H2Y_CHROMA_420;
+    if ((width >> sub) < 8 || (height >> sub) < 8)
+        return fail(ctx, H2Y_EINVAL, "SSIM needs every plane at least 8x8 (one window): %dx%d %s", width, height, sub ? "4:2:0" : "4:4:4");
+    return H2Y_OK;
+}
+
+/* k_ssim's partials for n_frames frames of g */
+static int ssim_partials(h2y_ctx *ctx, const ssim_geom &g, int n_frames)
+{
+    return ensure(ctx, ctx->d_ssim_part, ctx->ssim_part_cap, (size_t)n_frames * (g.units[0] + g.units[1] + g.units[2]) * sizeof(int64_t));
+}
+
+int h2y_ssim_batch(h2y_ctx *ctx, int width, int height, int chroma_format_idc, int bit_depth, int n_frames, const uint16_t *const *d_a,
+                   const uint16_t *const *d_b, h2y_ssim_stats *out)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
+    int rc = ssim_check(ctx, width, height, chroma_format_idc, bit_depth);
+    if (rc) return rc;
+    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
+    if (!d_a || !d_b || !out) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
+    for (int f = 0; f < n_frames; f++) {
+        if (!d_a[f] || !d_b[f]) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is null", f);
+        if (((uintptr_t)d_a[f] | (uintptr_t)d_b[f]) & 15u) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is not 16-byte aligned", f);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    uint32_t off[3];
+    cmp_contiguous(width, height, chroma_format_idc, off);
+    const ssim_geom g = ssim_geom_of(width, height, chroma_format_idc, bit_depth, off, off);
+    const int per_launch = std::min(n_frames, H2Y_SSIM_FRAMES_PER_LAUNCH);
+    cmp_frame *h;
+    rc = frame_table(ctx, n_frames, h);
+    if (!rc) rc = ssim_partials(ctx, g, per_launch);
+    if (!rc) rc = ensure(ctx, ctx->d_ssim_stats, ctx->ssim_stats_cap, (size_t)n_frames * sizeof(h2y_ssim_stats));
+    if (rc) return rc;
+    for (int f = 0; f < n_frames; f++) h[f] = cmp_frame{d_a[f], d_b[f]};
+    rc = timed_launches(ctx, h, n_frames, H2Y_SSIM_FRAMES_PER_LAUNCH, "k_ssim", [&](const cmp_frame *frames, int f0, int nf) {
+        return h2y_launch_ssim(h2y_ssim_grid(ctx->n_cu, g, nf), ctx->stream, g, frames, nf, ctx->d_ssim_part, ctx->d_ssim_stats + f0);
+    });
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpy(out, ctx->d_ssim_stats, (size_t)n_frames * sizeof(h2y_ssim_stats), hipMemcpyDeviceToHost));
+    ctx->last_variant = std::string("k_ssim<") + (chroma_format_idc == H2Y_CHROMA_420 ? "420" : "444") + "," + (g.wide ? "U64" : "U32") + ">";
+    return H2Y_OK;
+}
+
+int h2y_stream_ssim(h2y_ctx *ctx, int bit_depth)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    if (!ctx->s_cmp) return fail(ctx, H2Y_EINVAL, "the ring is not armed for comparison: h2y_stream_compare first");
+    if (ctx->s_ssim) return fail(ctx, H2Y_EINVAL, "the ring computes SSIM already");
+    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    const cmp_geom &c = ctx->s_cmp_geom;
+    const int width = (int)c.width[0], height = (int)(c.n[0] / c.width[0]);
+    const int chroma = c.n[1] == c.n[0] ? H2Y_CHROMA_444 : H2Y_CHROMA_420;
+    if (bit_depth < 0) {
+        if (ctx->s_kind == h2y_ctx::RING_COMPARE)
+            return fail(ctx, H2Y_EINVAL, "a compare-only ring does not know its frames' bit depth: give it to h2y_stream_ssim");
+        bit_depth = ctx->s_kind == h2y_ctx::RING_INVERSE ? ctx->s_inv.out_depth : ctx->s_desc.dst_bit_depth;
+    }
+    int rc = ssim_check(ctx, width, height, chroma, bit_depth);
+    if (rc) return rc;
+    const ssim_geom g = ssim_geom_of(width, height, chroma, bit_depth, c.a_off, c.b_off);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = ssim_partials(ctx, g, 1);
+    if (rc) return rc;
+    hipError_t e = hipSuccess;
+    for (auto &s : ctx->ss) {
+        if (e == hipSuccess) e = hipMalloc((void **)&s.d_ssim, sizeof(h2y_ssim_stats));
+        if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_ssim, sizeof(h2y_ssim_stats), hipHostMallocDefault);
+    }
+    if (e != hipSuccess) { /* the ring stays open, armed for comparison alone */
+        for (auto &s : ctx->ss) {
+            if (s.d_ssim) (void)hipFree(s.d_ssim);
+            if (s.h_ssim) (void)hipHostFree(s.h_ssim);
+            s.d_ssim = s.h_ssim = nullptr;
+        }
+        return fail(ctx, H2Y_ENOMEM, "SSIM buffers: %s", hipGetErrorString(e));
+    }
+    ctx->s_ssim_geom = g;
+    ctx->s_ssim = true;
+    return H2Y_OK;
+}
+
+int h2y_stream_ssim_result(h2y_ctx *ctx, h2y_ssim_stats *out)
+{
+    if (!ctx || !out) return fail(ctx, H2Y_EINVAL, "null argument");
+    if (!ctx->streaming || !ctx->s_ssim) return fail(ctx, H2Y_EINVAL, "no stream open that computes SSIM");
+    if (ctx->s_lent < 0) return fail(ctx, H2Y_EINVAL, "no output taken yet: h2y_stream_output first");
+    *out = *ctx->ss[ctx->s_lent].h_ssim;
+    return H2Y_OK;
+}
+
+/* k_ssim on the context's stream after k_compare, on the slot's pair of k_compare */
+static int ssim_run(h2y_ctx *ctx, int slot)
+{
+    const ssim_geom &g = ctx->s_ssim_geom;
+    HIP_TRY(ctx, h2y_launch_ssim(h2y_ssim_grid(ctx->n_cu, g, 1), ctx->stream, g, ctx->s_cmp_tab + slot, 1, ctx->d_ssim_part, ctx->ss[slot].d_ssim));
+    return H2Y_OK;
+}
+
+/* the SSIM goes down on the download stream, after the compare stats */
+static int ssim_download(h2y_ctx *ctx, h2y_ctx::stream_slot &s)
+{
+    HIP_TRY(ctx, hipMemcpyAsync(s.h_ssim, s.d_ssim, sizeof(h2y_ssim_stats), hipMemcpyDeviceToHost, ctx->s_d2h));
+    return H2Y_OK;
+}
+
 /* ---- code-value histograms and the legal-range check (hdr2yuv.cpp:658, :797) ---------------------------------------------- */
 
 /* k_histogram's geometry: planes of the comparison's geometry starting at off samples from the frame's base, the legal range of
@@ -3454,11 +3606,13 @@ static int compare_stream_submit(h2y_ctx *ctx, int slot)
     HIP_TRY(ctx, hipEventRecord(s.ev_h2d, ctx->s_h2d));
     HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s.ev_h2d, 0));
     rc = cmp_run(ctx, slot);
+    if (!rc && ctx->s_ssim) rc = ssim_run(ctx, slot);
     if (!rc && ctx->s_hist) rc = hist_run(ctx, slot);
     if (rc) return rc;
     HIP_TRY(ctx, hipEventRecord(s.ev_conv, ctx->stream));
     HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_d2h, s.ev_conv, 0));
     rc = cmp_download(ctx, s);
+    if (!rc && ctx->s_ssim) rc = ssim_download(ctx, s);
     if (!rc && ctx->s_hist) rc = hist_download(ctx, s);
     if (rc) return rc;
     HIP_TRY(ctx, hipEventRecord(s.ev_done, ctx->s_d2h));
@@ -3504,6 +3658,7 @@ static int inverse_stream_submit(h2y_ctx *ctx, int slot)
     }
     if (ctx->s_cmp) { /* on the G, B, R planes (before the interleave) */
         rc = cmp_run(ctx, slot);
+        if (!rc && ctx->s_ssim) rc = ssim_run(ctx, slot);
         if (rc) return rc;
     }
     if (ctx->s_hist) { /* likewise */
@@ -3522,6 +3677,7 @@ static int inverse_stream_submit(h2y_ctx *ctx, int slot)
                                         hipMemcpyDeviceToHost, ctx->s_d2h));
     if (ctx->s_cmp) {
         rc = cmp_download(ctx, s);
+        if (!rc && ctx->s_ssim) rc = ssim_download(ctx, s);
         if (rc) return rc;
     }
     if (ctx->s_hist) {
@@ -3606,6 +3762,7 @@ int h2y_stream_submit(h2y_ctx *ctx)
     if (rc) return rc;
     if (ctx->s_cmp) {
         rc = cmp_run(ctx, slot);
+        if (!rc && ctx->s_ssim) rc = ssim_run(ctx, slot);
         if (rc) return rc;
     }
     if (ctx->s_hist) {
@@ -3617,6 +3774,7 @@ int h2y_stream_submit(h2y_ctx *ctx)
     if (!ctx->s_cmp || ctx->s_cmp_keep) HIP_TRY(ctx, hipMemcpyAsync(s.h_out, s.d_out, ob, hipMemcpyDeviceToHost, ctx->s_d2h));
     if (ctx->s_cmp) {
         rc = cmp_download(ctx, s);
+        if (!rc && ctx->s_ssim) rc = ssim_download(ctx, s);
         if (rc) return rc;
     }
     if (ctx->s_hist) {

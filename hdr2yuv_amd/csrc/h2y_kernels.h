@@ -319,4 +319,20 @@ int h2y_histogram_grid(int n_cu, const hist_geom &g, int n_frames);
 hipError_t h2y_launch_histogram(int grid, hipStream_t st, const hist_geom &g, const hist_frame *frames, int n_frames, hist_acc *acc,
                                 uint32_t *bins, h2y_histogram_stats *stats);
 
+/* k_ssim and k_ssim_sum (h2y_ssim.hip): SSIM of two frames of u16 planes, per plane, from exact integer window sums */
+struct ssim_geom {
+    uint32_t pw[3], ph[3];       /* plane width and height (at least 8 x 8) */
+    uint32_t a_off[3], b_off[3]; /* plane start in samples from the frame base, per side */
+    uint32_t strips[3], units[3]; /* k_ssim's strips and units (strips x segments) per frame and plane */
+    uint32_t wide;               /* bit depth above 12: block sums ss and s12 in 64 bits */
+    double c1, c2;               /* the host's constants */
+};
+struct h2y_ssim_stats;
+uint32_t h2y_ssim_strips(uint32_t plane_width);    /* k_ssim's strips of a plane */
+uint32_t h2y_ssim_segments(uint32_t plane_height); /* and its segments */
+int h2y_ssim_grid(int n_cu, const ssim_geom &g, int n_frames);
+/* k_ssim over n_frames pairs into partials[frame x units per frame + unit], then k_ssim_sum into stats[frame] */
+hipError_t h2y_launch_ssim(int grid, hipStream_t st, const ssim_geom &g, const cmp_frame *frames, int n_frames, int64_t *partials,
+                           h2y_ssim_stats *stats);
+
 #endif

@@ -575,8 +575,42 @@ int h2y_stream_histogram_result(h2y_ctx *ctx, h2y_histogram_stats *out_stats, ui
 int h2y_histogram_stream_open(h2y_ctx *ctx, int width, int height, int chroma_format_idc, int bit_depth, int full_range, int gbr,
                               int bits, int depth /* 2..16 slots */);
 
+/* ---- SSIM beside the comparison ("SNR, etc. computation on orig vs. decoded": hdr2yuv.cpp:826 leaves it a TODO) ---------------
+ * SSIM on code values, per plane, of two frames in the comparison's geometry, as x264 and FFmpeg define it: 4x4 blocks at (4i, 4j)
+ * (columns and rows past the last whole block ignored), one window per 2x2 group of neighbouring blocks (8x8 samples at a stride
+ * of 4), with exact integer sums S1 = sum a, S2 = sum b, SS = sum a^2 + sum b^2, S12 = sum ab.  At bit depth d, M = 2^d - 1,
+ * c1 = ((0.01 * 0.01) * M) * M * 64 and c2 = (((0.03 * 0.03) * M) * M * 64) * 63 (binary64, left to right), each window in binary64
+ * with separate roundings:
+ *   vars = ((SS * 64) - S1 * S1) - S2 * S2,  covar = (S12 * 64) - S1 * S2,
+ *   s = (((2 * S1) * S2 + c1) * ((2 * covar) + c2)) / (((S1 * S1 + S2 * S2) + c1) * (vars + c2)),
+ * added to sum_q as rint(s x 2^32) (half to even) in int64, so every figure is independent of the order of the work.
+ * ssim[p] = (sum_q x 2^-32) / windows; all = ((ssim0 n0 + ssim1 n1) + ssim2 n2) / (n0 + n1 + n2), n the planes' sample counts.
+ * Every plane needs at least 8 x 8 samples (4:2:0: width and height of at least 16). */
+#define H2Y_SSIM_FRAMES_PER_LAUNCH 64
+
+typedef struct h2y_ssim_stats {
+    uint64_t windows[3]; /* per plane: ((plane_width >> 2) - 1) x ((plane_height >> 2) - 1) */
+    int64_t sum_q[3];    /* sum over the windows of rint(s x 2^32) */
+    double ssim[3];      /* (sum_q x 2^-32) / windows */
+    double all;          /* the planes' values weighted by their sample counts */
+} h2y_ssim_stats;
+
+/* n_frames pairs of device frames in h2y_compare_batch's layout and alignment: out[f] (host memory) receives the SSIM of d_a[f] against
+ * d_b[f].  chroma_format_idc 1 or 3 (2: H2Y_EUNSUPPORTED), bit_depth 8..16, n_frames >= 1.  Launches of up to
+ * H2Y_SSIM_FRAMES_PER_LAUNCH frames (h2y_last_kernel_ms sums them, h2y_last_kernel_name "k_ssim"); synchronous. */
+int h2y_ssim_batch(h2y_ctx *ctx, int width, int height, int chroma_format_idc, int bit_depth, int n_frames, const uint16_t *const *d_a,
+                   const uint16_t *const *d_b, h2y_ssim_stats *out);
+
+/* Arm a ring that h2y_stream_compare (or h2y_compare_stream_open) has armed, before its first input: k_ssim then runs on the kernel
+ * stream after k_compare, on the same device frame and reference; the output bytes and the compare stats do not change.
+ * bit_depth -1 takes the ring's own (dst_bit_depth on the forward rings, out_bit_depth on the inverse rings); a compare-only ring
+ * needs it given (8..16).  H2Y_EINVAL when the ring is not armed for comparison. */
+int h2y_stream_ssim(h2y_ctx *ctx, int bit_depth);
+/* The SSIM of the frame that h2y_stream_output returned last. */
+int h2y_stream_ssim_result(h2y_ctx *ctx, h2y_ssim_stats *out);
+
 /* Timing of the last h2y_convert_batch*() (or h2y_inverse_*, h2y_dpx_decode_batch, h2y_tiff_decode_batch,
- * h2y_rgb_interleave_batch, h2y_exr_decode_batch, h2y_compare_batch) call measured with HIP events on
+ * h2y_rgb_interleave_batch, h2y_exr_decode_batch, h2y_compare_batch, h2y_ssim_batch) call measured with HIP events on
  * the stream the kernels ran on: total ms over the main kernels and how many
  * launches that covered. */
 int h2y_last_kernel_ms(const h2y_ctx *ctx, float *ms, int *launches);

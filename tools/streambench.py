@@ -53,6 +53,15 @@ Prints one line per figure, then one JSON line with all of them.
      one-code-per-row content;
   2. frames/s from host memory of the forward ring (as `compare`) unarmed and armed with h2y_stream_histogram;
   3. frames/s of the histogram-only ring on the 10-bit 4:2:0 frames (the frame goes up, the counts come down).
+Prints one line per figure, then one JSON line with all of them.
+
+`streambench.py ssim`: SSIM beside the comparison on 4K frames:
+  1. the kernel time of h2y_ssim_batch (k_ssim and k_ssim_sum) over 64 distinct frame pairs per call (HIP events, median of
+     five), the bytes per pair it reads over that time and their share of the 8 TB/s HBM peak, for 10-bit 4:2:0 (49.8 MB) and
+     16-bit 4:4:4 (99.5 MB) pairs;
+  2. frames/s from host memory of the forward ring (as `compare`) armed with h2y_stream_compare alone and with h2y_stream_ssim
+     too, keep_output 1;
+  3. frames/s of the compare-only ring on the 10-bit 4:2:0 frames, without and with SSIM.
 Prints one line per figure, then one JSON line with all of them."""
 import os
 import sys
@@ -674,6 +683,111 @@ def histogram_main():
     print(json.dumps({"streambench_histogram": res}), flush=True)
 
 
+def ssim_main():
+    import json
+
+    import torch
+
+    w, hh, nb, reps = 3840, 2160, 64, 5
+    nf = int(os.environ.get("N", "60"))
+    depth = 3
+    rng = np.random.default_rng(19)
+    ctx = h.Context(0)
+    res = {"width": w, "height": hh, "frames_per_call": nb, "reps": reps, "ring_frames": nf, "ring_depth": depth, "hbm_peak_tbs": 8.0}
+
+    # 1. the kernels over 64 distinct frame pairs on the device
+    for name, chroma, bits in (("10bit_420", h.CHROMA_420, 10), ("16bit_444", h.CHROMA_444, 16)):
+        total = w * hh + 2 * ((w // 2) * (hh // 2) if chroma == h.CHROMA_420 else w * hh)
+        hi = 1 << bits
+        a = [torch.randint(0, hi, (total,), dtype=torch.int32, device="cuda").to(torch.int16) for _ in range(nb)]
+        b = [x + torch.randint(-2, 3, (total,), dtype=torch.int16, device="cuda") for x in a]
+        torch.cuda.synchronize()
+        ks = []
+        for rep in range(reps + 1):  # rep 0 warms up
+            ctx.ssim_batch(w, hh, chroma, bits, a, b)
+            if rep:
+                ks.append(ctx.last_kernel_ms()[0] / nb)
+        k_ms = float(np.median(ks))
+        nbytes = 2 * 2 * total
+        tbs = nbytes / (k_ms * 1e-3) / 1e12
+        res["k_ssim_" + name] = dict(kernel_us_per_frame=round(k_ms * 1e3, 2), bytes_per_frame=nbytes, kernel_tbs=round(tbs, 2),
+                                     hbm_peak_fraction=round(tbs / 8.0, 3), variant=ctx.last_kernel_variant())
+        print(f"k_ssim {name} {nb} pairs per call: {k_ms*1e3:6.2f} us/pair  {nbytes/1e6:6.1f} MB/pair  {tbs:5.2f} TB/s = "
+              f"{tbs/8.0*100:4.1f} % of 8 TB/s", flush=True)
+        del a, b
+        torch.cuda.empty_cache()
+
+    n, nc = w * hh, (w // 2) * (hh // 2)
+
+    def ring(open_fn, fill, ref, ssim, arm=True):
+        open_fn()
+        if arm:
+            ctx.stream_compare(0, 1)
+        if ssim is not None:
+            ctx.stream_ssim(ssim)
+        inflight = 0
+
+        def take():
+            ctx.stream_output()
+            ctx.stream_compare_result()
+            if ssim is not None:
+                ctx.stream_ssim_result()
+
+        t0 = time.perf_counter()
+        for _ in range(nf):
+            fill(ctx.stream_input())
+            ctx.stream_reference()[:] = ref
+            ctx.stream_submit()
+            inflight += 1
+            if inflight == depth - 1:
+                take()
+                inflight -= 1
+        while inflight:
+            take()
+            inflight -= 1
+        dt = (time.perf_counter() - t0) / nf
+        ctx.stream_close()
+        return dt
+
+    # 2. the forward ring: 16-bit G,B,R -> BT.2020nc 10-bit 4:2:0 box, compare alone and compare + SSIM
+    planes = [rng.integers(0, 65536, n, dtype=np.uint16) for _ in range(3)]
+    d = h.make_desc(w, hh, sample=h.SAMPLE_U16, src_depth=16, dst_depth=10, src_transfer=1, dst_transfer=1, src_primaries=1,
+                    dst_primaries=1, dst_matrix=h.MATRIX_BT2020NC, resampler=0)
+    yuv_ref = ctx.convert_frame(d, planes)
+
+    def fill_planes(slot):
+        for c in range(3):
+            slot[c][:] = planes[c]
+
+    def open_fwd():
+        ctx.stream_open(d, depth)
+
+    ring(open_fwd, fill_planes, yuv_ref, None)  # warm-up
+    t_cmp = ring(open_fwd, fill_planes, yuv_ref, None)
+    t_ssim = ring(open_fwd, fill_planes, yuv_ref, -1)
+    res["forward_ring"] = dict(compare_fps=round(1 / t_cmp, 1), compare_ssim_fps=round(1 / t_ssim, 1), compare_ms=round(t_cmp * 1e3, 2),
+                               compare_ssim_ms=round(t_ssim * 1e3, 2))
+    print(f"forward ring from host memory: compare {1/t_cmp:6.1f} frames/s   compare + ssim {1/t_ssim:6.1f} frames/s", flush=True)
+
+    # 3. the compare-only ring, without and with SSIM
+    yuv_a = [yuv_ref[:n], yuv_ref[n:n + nc], yuv_ref[n + nc:]]
+
+    def fill_a(slot):
+        for c in range(3):
+            slot[c][:] = yuv_a[c]
+
+    def open_cmp():
+        ctx.compare_stream_open(w, hh, h.CHROMA_420, 0, depth)
+
+    ring(open_cmp, fill_a, yuv_ref, None, arm=False)
+    t_c = ring(open_cmp, fill_a, yuv_ref, None, arm=False)
+    t_s = ring(open_cmp, fill_a, yuv_ref, 10, arm=False)
+    res["compare_only_ring"] = dict(fps=round(1 / t_c, 1), ssim_fps=round(1 / t_s, 1), ms=round(t_c * 1e3, 2), ssim_ms=round(t_s * 1e3, 2))
+    print(f"compare-only ring from host memory: {1/t_c:6.1f} frames/s, with ssim {1/t_s:6.1f} frames/s", flush=True)
+    ctx.close()
+    print(json.dumps({"streambench_ssim": res}), flush=True)
+
+
 if __name__ == "__main__":
     if sys.argv[1:] == ["inverse"]:
         inverse_main()
@@ -687,5 +801,7 @@ if __name__ == "__main__":
         compare_main()
     elif sys.argv[1:] == ["histogram"]:
         histogram_main()
+    elif sys.argv[1:] == ["ssim"]:
+        ssim_main()
     else:
         main()
