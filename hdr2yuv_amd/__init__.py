@@ -17,6 +17,7 @@ from .api import (  # noqa: F401
     H2YExrChunk,
     H2YExrInfo,
     H2YHistogramStats,
+    H2YLightStats,
     H2YSsimStats,
     H2YTiffInfo,
     MATRIX_BT2020NC,

@@ -36,11 +36,13 @@ EXPORTS = [
     "h2y_compare_batch", "h2y_stream_compare", "h2y_stream_reference", "h2y_stream_compare_result", "h2y_compare_stream_open",
     "h2y_histogram_batch", "h2y_stream_histogram", "h2y_stream_histogram_ex", "h2y_stream_histogram_result",
     "h2y_histogram_stream_open", "h2y_ssim_batch", "h2y_stream_ssim", "h2y_stream_ssim_result",
+    "h2y_light_batch", "h2y_stream_light", "h2y_stream_light_result",
 ]
 
 COMPARE_FRAMES_PER_LAUNCH = 64
 HISTOGRAM_FRAMES_PER_LAUNCH = 64
 SSIM_FRAMES_PER_LAUNCH = 64
+LIGHT_FRAMES_PER_LAUNCH = 64
 
 
 class H2YError(RuntimeError):
@@ -174,6 +176,20 @@ class H2YSsimStats(C.Structure):
 
     def __repr__(self):
         return f"H2YSsimStats({self.as_dict()})"
+
+
+class H2YLightStats(C.Structure):
+    """h2y_light_stats: a frame's content light -- the largest per-pixel max(L_G, L_B, L_R) as binary32 bits and the first pixel
+    (x, y) holding it, the sum over the pixels of rint(m x 2^32), the pixel count, and cll / fall in cd/m2."""
+
+    _fields_ = [("max_bits", C.c_uint32), ("x", C.c_uint32), ("y", C.c_uint32), ("reserved", C.c_uint32), ("sum_q", C.c_uint64),
+                ("pixels", C.c_uint64), ("cll", C.c_double), ("fall", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+    def __repr__(self):
+        return f"H2YLightStats({self.as_dict()})"
 
 
 def make_desc(width, height, *, sample=SAMPLE_F32, src_depth=32, dst_depth=10, src_transfer=TRANSFER_LINEAR,
@@ -356,6 +372,12 @@ def load_library():
     L.h2y_stream_ssim.restype = C.c_int
     L.h2y_stream_ssim_result.argtypes = [C.c_void_p, C.POINTER(H2YSsimStats)]
     L.h2y_stream_ssim_result.restype = C.c_int
+    L.h2y_light_batch.argtypes = [C.c_void_p, C.POINTER(H2YDesc), C.c_int, C.POINTER(C.c_void_p), C.POINTER(H2YLightStats)]
+    L.h2y_light_batch.restype = C.c_int
+    L.h2y_stream_light.argtypes = [C.c_void_p]
+    L.h2y_stream_light.restype = C.c_int
+    L.h2y_stream_light_result.argtypes = [C.c_void_p, C.POINTER(H2YLightStats)]
+    L.h2y_stream_light_result.restype = C.c_int
     L.h2y_stream_open.argtypes = [C.c_void_p, C.POINTER(H2YDesc), C.c_int]
     L.h2y_stream_input.restype = C.c_int
     L.h2y_stream_input.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
@@ -709,6 +731,18 @@ class Context:
         self._check(self.lib.h2y_ssim_batch(self.h, width, height, chroma, bit_depth, n, pa, pb, out))
         return list(out[:n])
 
+    def light_batch(self, d: H2YDesc, frames_in):
+        """k_light on device frames (frames_in[f] = three device planes G, B, R, 16-byte aligned): a list of H2YLightStats, one
+        per frame, with the floor and ceiling the conversion of d takes for each."""
+        n = len(frames_in)
+        ins = (C.c_void_p * max(3 * n, 1))()
+        for f in range(n):
+            for c in range(3):
+                ins[3 * f + c] = self._ptr(frames_in[f][c])
+        out = (H2YLightStats * max(n, 1))()
+        self._check(self.lib.h2y_light_batch(self.h, C.byref(d), n, ins, out))
+        return list(out[:n])
+
     # ---- host <-> device pipeline -----------------------------------------------------------
     def stream_histogram(self, bits=0, bit_depth=None, full_range=None, gbr=None) -> None:
         """Arm the open ring: every frame is counted on the device (h2y_stream_histogram; with bit_depth, full_range and gbr
@@ -762,6 +796,16 @@ class Context:
     def stream_ssim(self, bit_depth=-1) -> None:
         """Arm a compare-armed ring for SSIM too (bit_depth -1: the ring's own; a compare-only ring needs it given)."""
         self._check(self.lib.h2y_stream_ssim(self.h, bit_depth))
+
+    def stream_light(self) -> None:
+        """Arm an open forward ring (plain, DPX, TIFF or EXR) to measure every frame's content light (h2y_stream_light)."""
+        self._check(self.lib.h2y_stream_light(self.h))
+
+    def stream_light_result(self) -> H2YLightStats:
+        """The H2YLightStats of the frame stream_output returned last."""
+        st = H2YLightStats()
+        self._check(self.lib.h2y_stream_light_result(self.h, C.byref(st)))
+        return st
 
     def stream_ssim_result(self) -> H2YSsimStats:
         """The H2YSsimStats of the frame stream_output returned last."""

@@ -44,6 +44,11 @@
  *             --ref_filename the run is the .yuv flow.  --histogram_only 1 counts a .yuv (4:2:0 or 4:4:4) or .rgb (4:4:4) source
  *             read as --compare_only reads it, without conversion.  --check_range 1: exit status 4 when a counted sample lies
  *             outside the legal range (refused in full range, which has no such samples to find).
+ * --content_light 1 (an addition): MaxCLL and MaxFALL (CTA-861.3) of the forward flow, measured on the device from the linear light
+ *             the conversion hands to PQ10000_r (include/hdr2yuv_hip.h states every step), with or without --dst_filename, beside
+ *             --ref_filename and --histogram.  Refused (exit 1, also under --dry_run) unless the destination transfer is PQ (16), the
+ *             source transfer is not PQ and the source matrix is G,B,R (0); refused on the .yuv -> RGB flow, with --compare_only 1
+ *             and with --histogram_only 1.
  * Only user_args_t.chroma_resampler_type has no defined default there (never initialised): FIR here, as in
  * make.sh's example.  The reference calls exit(0) on its argument errors; this program returns 1.
  */
@@ -82,6 +87,9 @@ struct cli_args {
     /* --ssim 1: SSIM beside the comparison */
     int ssim = 0;
     bool ssim_given = false;
+    /* --content_light 1: MaxCLL / MaxFALL of the forward flow */
+    int light = 0;
+    bool light_given = false;
     /* the histogram: --histogram FILE, --histogram_bits (0: the counted frames' depth), --histogram_only, --check_range; what is
      * counted, resolved by cli_resolve_histogram: depth, range, G,B,R limits, chroma format */
     const char *hist = nullptr;
@@ -143,6 +151,8 @@ static inline void cli_help()
            "  beside the PSNR)\n"
            "  histogram: [--histogram FILE [--histogram_bits B] [--check_range 1]] (code values of every frame the run produces,\n"
            "  totals into FILE; exit status 4 on a sample outside the legal range), [--histogram_only 1] (--src_filename, no conversion)\n"
+           "  content light: [--content_light 1] (MaxCLL and MaxFALL of a conversion to PQ, per frame and for the run; without\n"
+           "  --dst_filename nothing is written)\n"
            "input by extension: .yuv .rgb (16-bit planar), .f32 .f16 (raw planar float / half, plane order G,B,R: what\n"
            "  dpx_read() / read_exr() leave in memory), .dpx (10-bit, 16-bit or float DPX) and .tiff (16-bit R,G,B, uncompressed; centre-cropped\n"
            "  to 3840 wide, [--cutout_hd 1] 1920x1080, [--cutout_qhd 1] 960x540) and .exr (scanline OpenEXR: NONE, RLE, ZIPS or ZIP;\n"
@@ -168,6 +178,7 @@ static inline void cli_parse(cli_args &a, int argc, char **argv)
         else if (is("--sigma_compare")) { a.sigma = atoi(val()); a.sigma_given = true; }
         else if (is("--compare_only")) a.compare_only = atoi(val());
         else if (is("--ssim")) { a.ssim = atoi(val()); a.ssim_given = true; }
+        else if (is("--content_light")) { a.light = atoi(val()); a.light_given = true; }
         else if (is("--histogram")) a.hist = val();
         else if (is("--histogram_bits")) { a.hist_bits = atoi(val()); a.hist_bits_given = true; }
         else if (is("--histogram_only")) a.hist_only = atoi(val());
@@ -338,12 +349,50 @@ static inline int cli_resolve_histogram(cli_args &a)
  * errors */
 static inline int cli_resolve_convert(cli_args &a);
 static inline int cli_resolve_ssim(cli_args &a);
+static inline int cli_resolve_light(cli_args &a);
 static inline int cli_resolve(cli_args &a)
 {
     int arg_errors = a.hist_only ? cli_resolve_histogram_only(a) : a.compare_only ? cli_resolve_compare(a) : cli_resolve_convert(a);
     if (a.hist || a.hist_bits_given || a.hist_only || a.check_range) arg_errors += cli_resolve_histogram(a);
     if (a.ssim_given) arg_errors += cli_resolve_ssim(a);
+    if (a.light_given) arg_errors += cli_resolve_light(a);
     return arg_errors;
+}
+
+/* --content_light: the forward flow of a conversion to PQ from another transfer, of a G,B,R source; returns the number of argument
+ * errors */
+static inline int cli_resolve_light(cli_args &a)
+{
+    printf("content_light: %d\n", a.light);
+    if (a.light != 0 && a.light != 1) {
+        printf("WARNING: content_light(%d) not 0 or 1\n", a.light);
+        return 1;
+    }
+    if (!a.light) return 0;
+    if (a.compare_only || a.hist_only) {
+        printf("WARNING: --content_light 1 measures a conversion: not with --%s 1\n", a.compare_only ? "compare_only" : "histogram_only");
+        return 1;
+    }
+    if (a.inverse) {
+        printf("WARNING: --content_light 1 measures the forward flow (to .yuv), not the .yuv -> RGB flow\n");
+        return 1;
+    }
+    if (a.out.transfer_characteristics != 16) {
+        printf("WARNING: --content_light 1 needs a PQ destination: dst_transfer_characteristics(%d) is not 16\n",
+               a.out.transfer_characteristics);
+        return 1;
+    }
+    if (a.in.transfer_characteristics == 16) {
+        printf("WARNING: --content_light 1: a PQ source (src_transfer_characteristics 16) goes to PQ without linear light\n");
+        return 1;
+    }
+    if (a.in.matrix_coeffs != H2Y_MATRIX_GBR) {
+        printf("WARNING: --content_light 1 needs a G,B,R source: src_matrix_coeffs(%d) is not %d\n", a.in.matrix_coeffs, H2Y_MATRIX_GBR);
+        return 1;
+    }
+    printf("content_light_from: src_transfer_characteristics %d -> PQ, G,B,R, floor and ceiling %s\n", a.in.transfer_characteristics,
+           "of each frame's pic_stats");
+    return 0;
 }
 
 /* --ssim: valid wherever a comparison runs, on frames of 4:2:0 or 4:4:4 whose every plane holds an 8x8 window; returns the number
@@ -411,7 +460,7 @@ static inline int cli_resolve_convert(cli_args &a)
     }
 
     /* :386-440 output type (without a destination: the reference file's) */
-    ext = cli_ext_of(a.dst ? a.dst : a.ref ? a.ref : a.hist ? "(none).yuv" : nullptr); /* only a histogram: the .yuv flow */
+    ext = cli_ext_of(a.dst ? a.dst : a.ref ? a.ref : a.hist || a.light ? "(none).yuv" : nullptr); /* only a histogram or the light: the .yuv flow */
     if (!strcasecmp(ext, "yuv")) a.out_type = CLI_OUT_YUV;
     else if (!strcasecmp(ext, "rgb")) a.out_type = CLI_OUT_RGB;
     else if (!strcasecmp(ext, "tiff")) a.out_type = CLI_OUT_TIFF;

@@ -60,6 +60,14 @@
  * FILE (text): "bin,code_lo,code_hi,<P0>,<P1>,<P2>", then one line per bin, code_lo = bin << (depth - B), code_hi = code_lo +
  * 2^(depth - B) - 1, the counts summed over the frames (a code above 2^depth - 1 counts in the last bin).  Exit status 4 under
  * --check_range 1 when outside > 0 (3 before it, when the comparison's status is 3).
+ *
+ * Content light (--content_light 1 on the forward flow; h2y_cli_args.h): each GPU thread arms its ring (h2y_stream_light) and keeps
+ * the figures of frame k by its index; the report is printed once every thread is done, so it is the same for any --gpus.  cd/m2
+ * "%.4f"; MaxCLL and MaxFALL rounded to the nearest integer (halves away from zero):
+ *   light frame <k> peak <cll> at <x> <y> average <fall>              one line per frame, in order (the first pixel holding the peak)
+ *   light summary frames <N> maxcll <CLL> frame <k> maxfall <FALL> frame <k>    the largest of each, the first such frame on ties
+ *   light x265 --max-cll "<CLL>,<FALL>"
+ *   light svt-av1 --content-light <CLL>,<FALL>
  */
 #include <algorithm>
 #include <array>
@@ -477,7 +485,7 @@ struct histogram_io {
 static void run_block(const cli_args &a, const h2y_desc &d, const std::vector<dpx_src> &dpx, const h2y_dpx_info &di,
                       const std::vector<tiff_src> &tiff, const h2y_tiff_info &ti, const std::vector<std::string> &exr,
                       const h2y_exr_info &xi, int fd_out, off_t base, std::vector<h2y_compare_stats> *stats,
-                      std::vector<h2y_ssim_stats> *ssim, histogram_io *hist, block *b)
+                      std::vector<h2y_ssim_stats> *ssim, std::vector<h2y_light_stats> *light, histogram_io *hist, block *b)
 {
     h2y_ctx *ctx = nullptr;
     FILE *fin = nullptr;
@@ -507,6 +515,7 @@ static void run_block(const cli_args &a, const h2y_desc &d, const std::vector<dp
     if (cmp.ref && h2y_stream_compare(ctx, a.sigma, a.dst ? 1 : 0)) return fail(h2y_last_error(ctx));
     if (a.ssim && h2y_stream_ssim(ctx, -1)) return fail(h2y_last_error(ctx));
     if (hist->on && h2y_stream_histogram(ctx, a.hist_bits)) return fail(h2y_last_error(ctx));
+    if (a.light && h2y_stream_light(ctx)) return fail(h2y_last_error(ctx));
     std::unique_ptr<unpack_pool> pool;
     std::vector<h2y_exr_chunk> chunks;
     if (a.in_type == CLI_IN_EXR) {
@@ -521,6 +530,7 @@ static void run_block(const cli_args &a, const h2y_desc &d, const std::vector<dp
         if (cmp.ref && h2y_stream_compare_result(ctx, &(*cmp.stats)[k])) { fail(h2y_last_error(ctx)); return false; }
         if (a.ssim && h2y_stream_ssim_result(ctx, &(*ssim)[k])) { fail(h2y_last_error(ctx)); return false; }
         if (!hist->take(ctx, k)) { fail(h2y_last_error(ctx)); return false; }
+        if (a.light && h2y_stream_light_result(ctx, &(*light)[k])) { fail(h2y_last_error(ctx)); return false; }
         if (a.dst && !write_at(fd_out, yuv, ob, base + (off_t)k * (off_t)ob)) { fail(std::string("short write to ") + a.dst); return false; }
         if (a.verbose > 0 && a.dst) printf("frame %ld: %zu bytes written to %s (device %d)\n", k, ob, a.dst, b->device);
         b->done++;
@@ -909,11 +919,27 @@ static void ssim_report(bool yuv, const std::vector<h2y_ssim_stats> &st)
     printf("ssim worst frame %zu all %.6f\n", worst, st[worst].all);
 }
 
+/* the content light report of the header comment */
+static void light_report(const std::vector<h2y_light_stats> &st)
+{
+    size_t kc = 0, kf = 0;
+    for (size_t k = 0; k < st.size(); k++) {
+        printf("light frame %zu peak %.4f at %u %u average %.4f\n", k, st[k].cll, st[k].x, st[k].y, st[k].fall);
+        if (st[k].cll > st[kc].cll) kc = k;
+        if (st[k].fall > st[kf].fall) kf = k;
+    }
+    if (st.empty()) return;
+    const long long cll = llround(st[kc].cll), fall = llround(st[kf].fall);
+    printf("light summary frames %zu maxcll %lld frame %zu maxfall %lld frame %zu\n", st.size(), cll, kc, fall, kf);
+    printf("light x265 --max-cll \"%lld,%lld\"\n", cll, fall);
+    printf("light svt-av1 --content-light %lld,%lld\n", cll, fall);
+}
+
 int main(int argc, char **argv)
 {
     cli_args a;
     cli_parse(a, argc, argv);
-    if ((!a.dst && !a.ref && !a.hist && !a.hist_only) || (!a.src && a.synthetic < 0)) {
+    if ((!a.dst && !a.ref && !a.hist && !a.hist_only && !a.light) || (!a.src && a.synthetic < 0)) {
         if (!a.help) cli_help();
         return a.help ? 0 : 1;
     }
@@ -1060,6 +1086,7 @@ int main(int argc, char **argv)
     }
     std::vector<h2y_compare_stats> stats(a.ref ? (size_t)frames : 0);
     std::vector<h2y_ssim_stats> sstats(a.ssim ? (size_t)frames : 0);
+    std::vector<h2y_light_stats> lstats(a.light ? (size_t)frames : 0);
     std::vector<h2y_histogram_stats> hstats(a.hist ? (size_t)frames : 0);
     std::vector<std::array<uint32_t, 3>> hocc(a.hist ? (size_t)frames : 0);
     std::vector<histogram_io> hist(a.gpus);
@@ -1069,7 +1096,7 @@ int main(int argc, char **argv)
         if (a.hist_only) run_block_histogram(a, (size_t)a.in.width * a.in.height * 2, in_frame_bytes, hi, b);
         else if (a.compare_only) run_block_compare(a, (size_t)a.in.width * a.in.height * 2, in_frame_bytes, &stats, &sstats, hi, b);
         else if (a.inverse) run_block_inverse(a, tw, fd, base, &stats, &sstats, hi, b);
-        else run_block(a, d, dpx, di, tiff, ti, exr, xi, fd, base, &stats, &sstats, hi, b);
+        else run_block(a, d, dpx, di, tiff, ti, exr, xi, fd, base, &stats, &sstats, &lstats, hi, b);
     };
     if (a.gpus == 1) work(&blocks[0]);
     else {
@@ -1084,6 +1111,7 @@ int main(int argc, char **argv)
             printf("ERROR (device %d, frames %ld..%ld): %s\n", blocks[r].device, blocks[r].first, blocks[r].first + blocks[r].count - 1, blocks[r].err.c_str());
             rc = 1;
         }
+    const bool ran = !rc;
     const bool compared = !rc && a.ref;
     if (compared) rc = compare_report(a, cmp_yuv, a.out.bit_depth, stats);
     if (compared && a.ssim) ssim_report(cmp_yuv, sstats);
@@ -1094,5 +1122,6 @@ int main(int argc, char **argv)
         const int hrc = histogram_report(a, hstats, hocc, total);
         if (hrc == 1 || !rc) rc = hrc;
     }
+    if (ran && a.light) light_report(lstats);
     return rc;
 }

@@ -223,6 +223,11 @@ struct h2y_ctx {
     size_t ssim_part_cap = 0;
     h2y_ssim_stats *d_ssim_stats = nullptr;
     size_t ssim_stats_cap = 0;
+    /* h2y_light_batch's floor / ceiling per frame and k_light's accumulators */
+    assumed_stats *d_light_as = nullptr;
+    size_t light_as_cap = 0;
+    light_acc *d_light_acc = nullptr;
+    size_t light_acc_cap = 0;
 
     /* staging for the host-buffer entry */
     void *d_in = nullptr;
@@ -251,6 +256,8 @@ struct h2y_ctx {
         uint32_t *h_hist_bins = nullptr;
         /* a ring armed by h2y_stream_ssim: the frame's SSIM on the device and pinned */
         h2y_ssim_stats *d_ssim = nullptr, *h_ssim = nullptr;
+        /* a ring armed by h2y_stream_light: the frame's k_light accumulator on the device and pinned */
+        light_acc *d_light = nullptr, *h_light = nullptr;
     };
     std::vector<stream_slot> ss;
     hipStream_t s_h2d = nullptr, s_d2h = nullptr;
@@ -288,6 +295,10 @@ struct h2y_ctx {
     /* a compare-armed ring armed by h2y_stream_ssim too: k_ssim's geometry (its frames are k_compare's, s_cmp_tab) */
     bool s_ssim = false;
     ssim_geom s_ssim_geom{};
+    /* a forward ring armed by h2y_stream_light: k_light's arguments and its table entry per slot (the slot's planes, d_assumed) */
+    bool s_light = false;
+    light_args s_light_args{};
+    light_frame *s_light_tab = nullptr;
     size_t s_ref_bytes = 0, s_ref_stats_off = 0; /* the pinned reference's bytes; where the stats lie in its device twin */
     int slot_base = 0; /* run_frames(): first entry of d_frames/h_frames to use (one per stream slot) */
     float last_ms = 0.f;
@@ -1471,6 +1482,8 @@ void h2y_ctx_destroy(h2y_ctx *ctx)
     (void)hipFree(ctx->d_hist);
     (void)hipFree(ctx->d_ssim_part);
     (void)hipFree(ctx->d_ssim_stats);
+    (void)hipFree(ctx->d_light_as);
+    (void)hipFree(ctx->d_light_acc);
     (void)hipFree(ctx->d_in);
     (void)hipFree(ctx->d_out);
     if (ctx->fir_stream) {
@@ -2134,6 +2147,8 @@ static void stream_free(h2y_ctx *ctx)
         if (s.h_hist_bins) (void)hipHostFree(s.h_hist_bins);
         if (s.d_ssim) (void)hipFree(s.d_ssim);
         if (s.h_ssim) (void)hipHostFree(s.h_ssim);
+        if (s.d_light) (void)hipFree(s.d_light);
+        if (s.h_light) (void)hipHostFree(s.h_light);
     }
     ctx->ss.clear();
     if (ctx->s_h2d) (void)hipStreamDestroy(ctx->s_h2d);
@@ -2147,6 +2162,9 @@ static void stream_free(h2y_ctx *ctx)
     ctx->s_hist_tab = nullptr;
     ctx->s_hist = false;
     ctx->s_ssim = false;
+    if (ctx->s_light_tab) (void)hipFree(ctx->s_light_tab);
+    ctx->s_light_tab = nullptr;
+    ctx->s_light = false;
     ctx->streaming = false;
     ctx->s_kind = h2y_ctx::RING_FORWARD;
     ctx->s_src = decode_src();
@@ -3332,6 +3350,168 @@ static int ssim_download(h2y_ctx *ctx, h2y_ctx::stream_slot &s)
     return H2Y_OK;
 }
 
+/* ---- content light level (MaxCLL / MaxFALL) of a forward conversion to PQ ------------------------------------------------------ */
+
+/* the descriptors whose light is measured: conversions to PQ from another transfer, of a G, B, R source */
+static int light_check(h2y_ctx *ctx, const h2y_desc *d)
+{
+    const char *why;
+    int rc = h2y_desc_check(d, &why);
+    if (rc) return fail(ctx, rc, "descriptor: %s", why);
+    if (d->dst_transfer != 16)
+        return fail(ctx, H2Y_EUNSUPPORTED, "content light is measured on conversions to PQ (dst_transfer 16), not dst_transfer %d", d->dst_transfer);
+    if (d->src_transfer == 16)
+        return fail(ctx, H2Y_EUNSUPPORTED, "a PQ source goes to PQ without linear light: there is no light to measure");
+    if (d->src_matrix != H2Y_MATRIX_GBR)
+        return fail(ctx, H2Y_EUNSUPPORTED, "content light needs a G,B,R source (src_matrix 0), not src_matrix %d", d->src_matrix);
+    return H2Y_OK;
+}
+
+/* k_light's arguments for d: the conversion's parameters and, for a source transfer other than LINEAR, its stage's tables */
+static int light_args_of(h2y_ctx *ctx, const h2y_desc *d, light_args &a)
+{
+    a = light_args{};
+    derive_params(d, &a.pp, false);
+    a.npix = (uint32_t)d->width * (uint32_t)d->height;
+    a.n4 = a.npix / 4u;
+    a.table = nullptr;
+    if (a.pp.src_tf != H2Y_TF_LINEAR) {
+        static const int kSrcFn[4] = {H2Y_TFN_NONE, H2Y_TFN_PQ_F, H2Y_TFN_RHO_H, H2Y_TFN_G24}; /* by H2Y_TF_* class, as run_frames() */
+        const int sf = kSrcFn[a.pp.src_tf];
+        const int rc = ensure_tfn(ctx, sf);
+        if (rc) return rc;
+        a.pp.src_fn = sf;
+        a.table = ctx->d_tfn[sf];
+        a.pp.tf_ext[0] = ctx->d_tfn_ext[sf];
+    }
+    return H2Y_OK;
+}
+
+static std::string light_variant(const h2y_desc *d, const light_args &a)
+{
+    static const char *const kIn[] = {"F32", "F16", "U16"}, *const kTf[] = {"LINEAR", "PQ", "RHO_GAMMA", "BT1886"};
+    return std::string("k_light<") + kIn[in_kind_of(d)] + "," + kTf[a.pp.src_tf] + ">";
+}
+
+/* the stats of one frame of npix pixels, width wide, from its accumulator */
+static void light_finish(const light_acc &acc, uint32_t width, uint32_t npix, h2y_light_stats *o)
+{
+    *o = h2y_light_stats{};
+    o->max_bits = (uint32_t)(acc.key >> 32);
+    const uint32_t i = ~(uint32_t)acc.key;
+    o->x = i % width;
+    o->y = i / width;
+    o->sum_q = acc.sum;
+    o->pixels = npix;
+    o->cll = 10000.0 * (double)bits2f(o->max_bits);
+    o->fall = ((10000.0 * (double)acc.sum) * 0x1p-32) / (double)npix;
+}
+
+int h2y_light_batch(h2y_ctx *ctx, const h2y_desc *d, int n_frames, const void *const *d_planes, h2y_light_stats *out)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
+    int rc = light_check(ctx, d);
+    if (rc) return rc;
+    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
+    if (!d_planes || !out) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
+    for (int f = 0; f < n_frames; f++)
+        for (int c = 0; c < 3; c++)
+            if (!d_planes[3 * f + c] || ((uintptr_t)d_planes[3 * f + c] & 15u))
+                return fail(ctx, H2Y_EINVAL, "input plane %d of frame %d is null or not 16-byte aligned", c, f);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    light_args a;
+    rc = light_args_of(ctx, d, a);
+    light_frame *h;
+    if (!rc) rc = frame_table(ctx, n_frames, h);
+    if (!rc) rc = ensure(ctx, ctx->d_light_as, ctx->light_as_cap, (size_t)n_frames * sizeof(assumed_stats));
+    if (!rc) rc = ensure(ctx, ctx->d_light_acc, ctx->light_acc_cap, (size_t)n_frames * sizeof(light_acc));
+    if (rc) return rc;
+    if (d->stats_override) { /* the same six integers for every frame */
+        std::vector<assumed_stats> as(n_frames);
+        for (auto &x : as)
+            for (int c = 0; c < 3; c++) x.floor_[c] = d->floor[c], x.ceil_[c] = d->ceiling[c];
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_light_as, as.data(), (size_t)n_frames * sizeof(assumed_stats), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    } else /* pic_stats of every frame, as h2y_convert_batch ends up taking it */
+        for (int f = 0; f < n_frames; f++) {
+            rc = run_stats(ctx, d, d_planes + 3 * f, (int)ctx->b->frames_cap, ctx->d_light_as + f);
+            if (rc) return rc;
+        }
+    ctx->b->dev_assumed_ok = false; /* run_stats used the batch state's scratch slot */
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_light_acc, 0, (size_t)n_frames * sizeof(light_acc), ctx->stream));
+    for (int f = 0; f < n_frames; f++)
+        h[f] = light_frame{{d_planes[3 * f], d_planes[3 * f + 1], d_planes[3 * f + 2]}, ctx->d_light_as + f};
+    const int in_kind = in_kind_of(d);
+    rc = timed_launches(ctx, h, n_frames, H2Y_LIGHT_FRAMES_PER_LAUNCH, "k_light", [&](const light_frame *frames, int f0, int nf) {
+        return h2y_launch_light(in_kind, h2y_light_grid(a.npix, nf), ctx->stream, a, frames, nf, ctx->d_light_acc + f0);
+    });
+    if (rc) return rc;
+    std::vector<light_acc> acc(n_frames);
+    HIP_TRY(ctx, hipMemcpy(acc.data(), ctx->d_light_acc, (size_t)n_frames * sizeof(light_acc), hipMemcpyDeviceToHost));
+    for (int f = 0; f < n_frames; f++) light_finish(acc[f], (uint32_t)d->width, a.npix, out + f);
+    ctx->last_variant = light_variant(d, a);
+    return H2Y_OK;
+}
+
+int h2y_stream_light(h2y_ctx *ctx)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    if (ctx->s_kind != h2y_ctx::RING_FORWARD) return fail(ctx, H2Y_EINVAL, "content light is measured on the forward rings only");
+    if (ctx->s_light) return fail(ctx, H2Y_EINVAL, "the ring measures content light already");
+    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    const h2y_desc *d = &ctx->s_desc;
+    int rc = light_check(ctx, d);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    light_args a;
+    rc = light_args_of(ctx, d, a);
+    if (rc) return rc;
+    const int depth = (int)ctx->ss.size();
+    std::vector<light_frame> tab(depth);
+    for (int k = 0; k < depth; k++)
+        for (int c = 0; c < 3; c++) tab[k].in[c] = ctx->ss[k].d_in + c * ctx->s_plane_al, tab[k].assumed = ctx->b->d_assumed;
+    hipError_t e = hipMalloc((void **)&ctx->s_light_tab, (size_t)depth * sizeof(light_frame));
+    if (e == hipSuccess) e = hipMemcpy(ctx->s_light_tab, tab.data(), (size_t)depth * sizeof(light_frame), hipMemcpyHostToDevice);
+    for (auto &s : ctx->ss) {
+        if (e == hipSuccess) e = hipMalloc((void **)&s.d_light, sizeof(light_acc));
+        if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_light, sizeof(light_acc), hipHostMallocDefault);
+    }
+    if (e != hipSuccess) { /* the ring stays open, unarmed */
+        for (auto &s : ctx->ss) {
+            if (s.d_light) (void)hipFree(s.d_light);
+            if (s.h_light) (void)hipHostFree(s.h_light);
+            s.d_light = s.h_light = nullptr;
+        }
+        if (ctx->s_light_tab) (void)hipFree(ctx->s_light_tab);
+        ctx->s_light_tab = nullptr;
+        return fail(ctx, H2Y_ENOMEM, "content light buffers: %s", hipGetErrorString(e));
+    }
+    ctx->s_light_args = a;
+    ctx->s_light = true;
+    return H2Y_OK;
+}
+
+int h2y_stream_light_result(h2y_ctx *ctx, h2y_light_stats *out)
+{
+    if (!ctx || !out) return fail(ctx, H2Y_EINVAL, "null argument");
+    if (!ctx->streaming || !ctx->s_light) return fail(ctx, H2Y_EINVAL, "no stream open that measures content light");
+    if (ctx->s_lent < 0) return fail(ctx, H2Y_EINVAL, "no output taken yet: h2y_stream_output first");
+    light_finish(*ctx->ss[ctx->s_lent].h_light, (uint32_t)ctx->s_desc.width, ctx->s_light_args.npix, out);
+    return H2Y_OK;
+}
+
+/* the zeroing and k_light of the slot's frame on the context's stream */
+static int light_run(h2y_ctx *ctx, int slot)
+{
+    const light_args &a = ctx->s_light_args;
+    HIP_TRY(ctx, hipMemsetAsync(ctx->ss[slot].d_light, 0, sizeof(light_acc), ctx->stream));
+    HIP_TRY(ctx, h2y_launch_light(in_kind_of(&ctx->s_desc), h2y_light_grid(a.npix, 1), ctx->stream, a, ctx->s_light_tab + slot, 1,
+                                  ctx->ss[slot].d_light));
+    return H2Y_OK;
+}
+
 /* ---- code-value histograms and the legal-range check (hdr2yuv.cpp:658, :797) ---------------------------------------------- */
 
 /* k_histogram's geometry: planes of the comparison's geometry starting at off samples from the frame's base, the legal range of
@@ -3760,6 +3940,10 @@ int h2y_stream_submit(h2y_ctx *ctx)
     rc = run_frames(ctx, d, &io, 1, ctx->b->d_assumed, nullptr, false, slot, false);
     ctx->slot_base = 0;
     if (rc) return rc;
+    if (ctx->s_light) { /* on the decoded planes, with the floor and ceiling the conversion just used */
+        rc = light_run(ctx, slot);
+        if (rc) return rc;
+    }
     if (ctx->s_cmp) {
         rc = cmp_run(ctx, slot);
         if (!rc && ctx->s_ssim) rc = ssim_run(ctx, slot);
@@ -3781,6 +3965,7 @@ int h2y_stream_submit(h2y_ctx *ctx)
         rc = hist_download(ctx, s);
         if (rc) return rc;
     }
+    if (ctx->s_light) HIP_TRY(ctx, hipMemcpyAsync(s.h_light, s.d_light, sizeof(light_acc), hipMemcpyDeviceToHost, ctx->s_d2h));
     HIP_TRY(ctx, hipEventRecord(s.ev_done, ctx->s_d2h));
     s.state = 2;
     ctx->s_tail = (slot + 1) % (int)ctx->ss.size();

@@ -335,4 +335,23 @@ int h2y_ssim_grid(int n_cu, const ssim_geom &g, int n_frames);
 hipError_t h2y_launch_ssim(int grid, hipStream_t st, const ssim_geom &g, const cmp_frame *frames, int n_frames, int64_t *partials,
                            h2y_ssim_stats *stats);
 
+/* k_light (h2y_light.hip): the content light of frames of the forward conversion's input (include/hdr2yuv_hip.h, h2y_light_stats) */
+struct light_frame { /* one frame: its G, B, R planes (16-byte aligned) and the floor / ceiling its conversion used */
+    const void *in[3];
+    const assumed_stats *assumed;
+};
+struct light_acc { /* one frame: zeroed before k_light */
+    unsigned long long key; /* max over pixels of (m bits << 32) | ~index: the largest m, the first pixel on ties */
+    unsigned long long sum; /* sum over pixels of rint(m x 2^32) */
+};
+struct light_args {
+    uint32_t npix;           /* pixels per frame (< 2^28) */
+    uint32_t n4;             /* npix / 4: 4-pixel groups read by vector loads; the rest one by one */
+    const void *table;       /* the source transfer's table (tfn_build_table; NULL for a LINEAR source) */
+    h2y::pix_params pp;      /* derive_params() of the descriptor, src_fn / tf_ext[0] of the source stage set; offset / range per frame */
+};
+int h2y_light_grid(uint32_t npix, int n_frames); /* blocks per frame */
+/* k_light over n_frames frames into acc[frame] (zeroed by the caller) */
+hipError_t h2y_launch_light(int in_kind, int grid, hipStream_t st, const light_args &a, const light_frame *frames, int n_frames, light_acc *acc);
+
 #endif

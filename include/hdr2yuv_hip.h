@@ -609,8 +609,48 @@ int h2y_stream_ssim(h2y_ctx *ctx, int bit_depth);
 /* The SSIM of the frame that h2y_stream_output returned last. */
 int h2y_stream_ssim_result(h2y_ctx *ctx, h2y_ssim_stats *out);
 
+/* ---- content light level (MaxCLL / MaxFALL, CTA-861.3) of a forward conversion to PQ ------------------------------------------
+ * Scope: dst_transfer 16 (PQ), src_transfer another transfer the conversion linearises (8 LINEAR, 18 RHO_GAMMA, 1/6/14/15
+ * BT.1886), src_matrix 0 (G, B, R); anything else is H2Y_EUNSUPPORTED.  Light is taken where matrix_convert() defines it
+ * (convert.cpp:930-1040), per frame, with the offset and range the conversion used for that frame (the frame's own pic_stats
+ * floor and ceiling, or the descriptor's stats_override):
+ *   per sample  L_c = the binary32 value matrix_convert() hands to PQ10000_r: v' = (v - offset[c]) / range[c] (binary32 subtract,
+ *               IEEE divide; v itself when every offset is 0 and every range 1), then L_c = tf_to_linear(src transfer, v') (v' itself
+ *               for LINEAR).  A NaN counts as 0; L_c is clamped to [0, 1], what the output can carry.  PQ maps L = 1 to 10000 cd/m2.
+ *   per pixel   m = max(L_G, L_B, L_R)
+ *   per frame   max_bits = the largest m as a binary32 bit pattern, (x, y) the first pixel in raster order that holds it;
+ *               sum_q = sum over the pixels of rint(m x 2^32) (half to even) in uint64 -- exact, whatever the order of the work
+ *               (an 8K frame stays below 2^58); cll = 10000 x m_max and fall = ((10000 x (double)sum_q) x 2^-32) / pixels, binary64,
+ *               in that order.
+ * MaxCLL and MaxFALL of a sequence are the largest cll and fall of its frames (the hdr2yuv CLI rounds them to whole cd/m2). */
+#define H2Y_LIGHT_FRAMES_PER_LAUNCH 64
+
+typedef struct h2y_light_stats {
+    uint32_t max_bits; /* the largest m of the frame, as binary32 bits */
+    uint32_t x, y;     /* the first pixel in raster order that holds it */
+    uint32_t reserved; /* 0 */
+    uint64_t sum_q;    /* sum over the pixels of rint(m x 2^32) */
+    uint64_t pixels;   /* width x height */
+    double cll;        /* 10000 x m_max, cd/m2 */
+    double fall;       /* ((10000 x sum_q) x 2^-32) / pixels, cd/m2 */
+} h2y_light_stats;
+
+/* The light of n_frames device frames of d (d_planes[f x 3 + c]: plane c = G, B, R of frame f, 16-byte aligned, in the layout
+ * h2y_convert_batch reads): out[f] (host memory).  Floor and ceiling as h2y_convert_batch takes them: the descriptor's override,
+ * or pic_stats of each frame (k_stats, run here).  Launches of up to H2Y_LIGHT_FRAMES_PER_LAUNCH frames (h2y_last_kernel_ms sums
+ * them, h2y_last_kernel_name "k_light"); synchronous. */
+int h2y_light_batch(h2y_ctx *ctx, const h2y_desc *d, int n_frames, const void *const *d_planes, h2y_light_stats *out);
+
+/* Arm an open forward ring (h2y_stream_open, h2y_dpx_stream_open, h2y_tiff_stream_open, h2y_exr_stream_open; with or without
+ * h2y_stream_compare and h2y_stream_histogram) before its first input: k_light then runs on every frame's decoded planes, on the
+ * kernel stream after the conversion, with the floor and ceiling the conversion used; the output bytes do not change.
+ * H2Y_EUNSUPPORTED for a descriptor out of the scope above, H2Y_EINVAL on any other ring. */
+int h2y_stream_light(h2y_ctx *ctx);
+/* The light of the frame that h2y_stream_output returned last. */
+int h2y_stream_light_result(h2y_ctx *ctx, h2y_light_stats *out);
+
 /* Timing of the last h2y_convert_batch*() (or h2y_inverse_*, h2y_dpx_decode_batch, h2y_tiff_decode_batch,
- * h2y_rgb_interleave_batch, h2y_exr_decode_batch, h2y_compare_batch, h2y_ssim_batch) call measured with HIP events on
+ * h2y_rgb_interleave_batch, h2y_exr_decode_batch, h2y_compare_batch, h2y_ssim_batch, h2y_light_batch) call measured with HIP events on
  * the stream the kernels ran on: total ms over the main kernels and how many
  * launches that covered. */
 int h2y_last_kernel_ms(const h2y_ctx *ctx, float *ms, int *launches);

@@ -62,6 +62,14 @@ Prints one line per figure, then one JSON line with all of them.
   2. frames/s from host memory of the forward ring (as `compare`) armed with h2y_stream_compare alone and with h2y_stream_ssim
      too, keep_output 1;
   3. frames/s of the compare-only ring on the 10-bit 4:2:0 frames, without and with SSIM.
+Prints one line per figure, then one JSON line with all of them.
+
+`streambench.py light`: the content light level on 4K frames:
+  1. the kernel time of h2y_light_batch (k_light) over 64 distinct frames per call (HIP events, median of five; floor and
+     ceiling given, so no k_stats runs), the bytes per frame it reads over that time and their share of the 8 TB/s HBM peak, for
+     F32 (99.5 MB), F16 and U16 (49.8 MB) LINEAR sources and an F32 BT.1886 source (the transfer's table tier);
+  2. frames/s from host memory of every forward ring -- .f32, float DPX, 16-bit TIFF, half EXR (NONE) -- to PQ BT.2020nc 10-bit
+     4:2:0, unarmed and armed with h2y_stream_light.
 Prints one line per figure, then one JSON line with all of them."""
 import os
 import sys
@@ -788,6 +796,114 @@ def ssim_main():
     print(json.dumps({"streambench_ssim": res}), flush=True)
 
 
+def light_main():
+    import json
+
+    import torch
+
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    from dpx_files import pack_pixels, write_dpx
+    from exr_files import HALF, NONE, smooth_half, write_exr
+    from tiff_files import write_tiff
+
+    w, hh, nb, reps = 3840, 2160, 64, 5
+    n = w * hh
+    nf = int(os.environ.get("N", "60"))
+    depth = 3
+    rng = np.random.default_rng(23)
+    ctx = h.Context(0)
+    res = {"width": w, "height": hh, "frames_per_call": nb, "reps": reps, "ring_frames": nf, "ring_depth": depth, "hbm_peak_tbs": 8.0}
+
+    # 1. k_light over 64 distinct frames on the device (floor and ceiling given: the kernel alone is timed)
+    for name, sample, src_transfer, depth_in in (("f32", h.SAMPLE_F32, 8, 32), ("f16", h.SAMPLE_F16, 8, 32), ("u16", h.SAMPLE_U16, 8, 16),
+                                                 ("f32_bt1886", h.SAMPLE_F32, 1, 32)):
+        d = h.make_desc(w, hh, sample=sample, src_depth=depth_in, dst_depth=10, src_transfer=src_transfer, dst_transfer=16,
+                        dst_matrix=h.MATRIX_BT2020NC, resampler=0, stats=[(0, 1 if sample != h.SAMPLE_U16 else 65535)] * 3)
+        if sample == h.SAMPLE_U16:
+            frames = [[torch.randint(0, 65536, (n,), dtype=torch.int32, device="cuda").to(torch.int16) for _ in range(3)] for _ in range(nb)]
+        else:
+            dt = torch.float32 if sample == h.SAMPLE_F32 else torch.float16
+            frames = [[torch.rand(n, device="cuda").to(dt) for _ in range(3)] for _ in range(nb)]
+        torch.cuda.synchronize()
+        ks = []
+        for rep in range(reps + 1):  # rep 0 warms up
+            ctx.light_batch(d, frames)
+            if rep:
+                ks.append(ctx.last_kernel_ms()[0] / nb)
+        k_ms = float(np.median(ks))
+        nbytes = 3 * n * (4 if sample == h.SAMPLE_F32 else 2)
+        tbs = nbytes / (k_ms * 1e-3) / 1e12
+        res[f"k_light_{name}"] = dict(kernel_us_per_frame=round(k_ms * 1e3, 2), bytes_per_frame=nbytes, kernel_tbs=round(tbs, 2),
+                                      hbm_peak_fraction=round(tbs / 8.0, 3), variant=ctx.last_kernel_variant())
+        print(f"k_light {name:11s} {nb} frames per call: {k_ms*1e3:6.2f} us/frame  {nbytes/1e6:6.1f} MB/frame  {tbs:5.2f} TB/s = "
+              f"{tbs/8.0*100:4.1f} % of 8 TB/s", flush=True)
+        del frames
+        torch.cuda.empty_cache()
+
+    def ring(open_fn, fill, arm):
+        open_fn()
+        if arm:
+            ctx.stream_light()
+        inflight = 0
+        t0 = time.perf_counter()
+        for _ in range(nf):
+            fill(ctx.stream_input())
+            ctx.stream_submit()
+            inflight += 1
+            if inflight == depth - 1:
+                ctx.stream_output()
+                if arm:
+                    ctx.stream_light_result()
+                inflight -= 1
+        while inflight:
+            ctx.stream_output()
+            if arm:
+                ctx.stream_light_result()
+            inflight -= 1
+        dt = (time.perf_counter() - t0) / nf
+        ctx.stream_close()
+        return dt
+
+    def both(key, open_fn, fill):
+        ring(open_fn, fill, False)  # warm-up
+        t_plain, t_armed = ring(open_fn, fill, False), ring(open_fn, fill, True)
+        res[key] = dict(unarmed_fps=round(1 / t_plain, 1), armed_fps=round(1 / t_armed, 1), armed_share=round(t_plain / t_armed, 3))
+        print(f"{key:12s} ring from host memory: unarmed {1/t_plain:6.1f} frames/s   armed {1/t_armed:6.1f} frames/s "
+              f"({t_plain/t_armed*100:5.1f} %)", flush=True)
+
+    # 2. every forward ring, unarmed and armed, linear light -> PQ BT.2020nc 10-bit 4:2:0
+    d32 = h.make_desc(w, hh, dst_depth=10, dst_matrix=h.MATRIX_BT2020NC, resampler=1)
+    rgb = [rng.random(n, dtype=np.float32) for _ in range(3)]
+    planes = [rgb[1], rgb[2], rgb[0]]
+
+    def fill_planes(slot):
+        for c in range(3):
+            slot[c][:] = planes[c]
+
+    both("f32", lambda: ctx.stream_open(d32, depth), fill_planes)
+    data = write_dpx(w, hh, 32, pack_pixels(*(c.view(np.uint32) for c in rgb), 32))
+    info = h.parse_dpx(data[:2048], len(data))
+    payload = np.frombuffer(data, np.uint8, count=info.payload_bytes, offset=info.data_offset)
+
+    def fill_payload(slot, p=payload):
+        slot[0][:] = p
+
+    both("dpx_float", lambda: ctx.dpx_stream_open(d32, info, depth), fill_payload)
+    pic = rng.integers(0, 65536, (hh, w, 3), dtype=np.uint16)
+    tdata = write_tiff(pic)
+    tinfo, rows = h.parse_tiff(tdata)
+    tpay = np.frombuffer(b"".join(tdata[int(o):int(o) + int(tinfo.row_bytes)] for o in rows), np.uint8)
+    d16 = h.make_desc(w, hh, sample=h.SAMPLE_U16, src_depth=16, dst_depth=10, dst_matrix=h.MATRIX_BT2020NC, resampler=1)
+    both("tiff", lambda: ctx.tiff_stream_open(d16, tinfo, 0, depth), lambda slot: fill_payload(slot, tpay))
+    edata, _ = write_exr({name: (HALF, smooth_half(hh, w, 101 * k)) for k, name in enumerate("RGB")}, NONE)
+    ebuf = np.frombuffer(edata, np.uint8)
+    einfo, echunks = h.parse_exr(ebuf)
+    dh = h.make_desc(w, hh, sample=h.SAMPLE_F16, dst_depth=10, dst_matrix=h.MATRIX_BT2020NC, resampler=1)
+    both("exr", lambda: ctx.exr_stream_open(dh, einfo, depth), lambda slot: h.exr_unpack(einfo, echunks, ebuf, slot[0]))
+    ctx.close()
+    print(json.dumps({"streambench_light": res}), flush=True)
+
+
 if __name__ == "__main__":
     if sys.argv[1:] == ["inverse"]:
         inverse_main()
@@ -803,5 +919,7 @@ if __name__ == "__main__":
         histogram_main()
     elif sys.argv[1:] == ["ssim"]:
         ssim_main()
+    elif sys.argv[1:] == ["light"]:
+        light_main()
     else:
         main()
