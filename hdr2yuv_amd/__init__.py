@@ -43,6 +43,8 @@ from .api import (  # noqa: F401
     parse_dpx,
     parse_exr,
     parse_tiff,
+    scale_frame_bytes,
+    scale_taps,
     set_library_path,
     tiff_layout,
 )

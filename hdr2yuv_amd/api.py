@@ -37,12 +37,15 @@ EXPORTS = [
     "h2y_histogram_batch", "h2y_stream_histogram", "h2y_stream_histogram_ex", "h2y_stream_histogram_result",
     "h2y_histogram_stream_open", "h2y_ssim_batch", "h2y_stream_ssim", "h2y_stream_ssim_result",
     "h2y_light_batch", "h2y_stream_light", "h2y_stream_light_result",
+    "h2y_scale_taps", "h2y_scale_frame_bytes", "h2y_scale_batch", "h2y_stream_scale", "h2y_scale_stream_open",
 ]
 
 COMPARE_FRAMES_PER_LAUNCH = 64
 HISTOGRAM_FRAMES_PER_LAUNCH = 64
 SSIM_FRAMES_PER_LAUNCH = 64
 LIGHT_FRAMES_PER_LAUNCH = 64
+SCALE_FRAMES_PER_LAUNCH = 64
+SCALE_TAPS = 32  # coefficients per row of scale_taps' table
 
 
 class H2YError(RuntimeError):
@@ -378,6 +381,16 @@ def load_library():
     L.h2y_stream_light.restype = C.c_int
     L.h2y_stream_light_result.argtypes = [C.c_void_p, C.POINTER(H2YLightStats)]
     L.h2y_stream_light_result.restype = C.c_int
+    L.h2y_scale_taps.argtypes = [C.c_int] * 3 + [C.c_void_p] * 3 + [C.POINTER(C.c_int)]
+    L.h2y_scale_taps.restype = C.c_int
+    L.h2y_scale_frame_bytes.argtypes = [C.c_int] * 3
+    L.h2y_scale_frame_bytes.restype = C.c_size_t
+    L.h2y_scale_batch.argtypes = [C.c_void_p] + [C.c_int] * 10 + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.h2y_scale_batch.restype = C.c_int
+    L.h2y_stream_scale.argtypes = [C.c_void_p] + [C.c_int] * 3
+    L.h2y_stream_scale.restype = C.c_int
+    L.h2y_scale_stream_open.argtypes = [C.c_void_p] + [C.c_int] * 10
+    L.h2y_scale_stream_open.restype = C.c_int
     L.h2y_stream_open.argtypes = [C.c_void_p, C.POINTER(H2YDesc), C.c_int]
     L.h2y_stream_input.restype = C.c_int
     L.h2y_stream_input.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
@@ -498,6 +511,26 @@ def exr_unpack(info, chunks, data, payload=None, first=0, count=None):
 
 def _np_dtype(sample):
     return np.float32 if sample == SAMPLE_F32 else np.uint16
+
+
+def scale_taps(src: int, dst: int, a: int = 3):
+    """h2y_scale_taps: the Lanczos tap table of one axis (host only, no device): (first int32[dst], count int32[dst],
+    coef int16[dst, 32], max_taps)."""
+    lib = load_library()
+    n = max(dst, 1)
+    first = np.zeros(n, dtype=np.int32)
+    count = np.zeros(n, dtype=np.int32)
+    coef = np.zeros((n, SCALE_TAPS), dtype=np.int16)
+    most = C.c_int(0)
+    rc = lib.h2y_scale_taps(src, dst, a, first.ctypes.data, count.ctypes.data, coef.ctypes.data, C.byref(most))
+    if rc != H2Y_OK:
+        raise H2YError(rc, (lib.h2y_last_error(None) or b"").decode())
+    return first, count, coef, most.value
+
+
+def scale_frame_bytes(width: int, height: int, chroma: int) -> int:
+    """h2y_scale_frame_bytes: bytes of a frame of three u16 planes (0 for an unsupported geometry)."""
+    return int(load_library().h2y_scale_frame_bytes(width, height, chroma))
 
 
 class Context:
@@ -743,7 +776,32 @@ class Context:
         self._check(self.lib.h2y_light_batch(self.h, C.byref(d), n, ins, out))
         return list(out[:n])
 
+    def scale_batch(self, src_w, src_h, dst_w, dst_h, chroma, bit_depth, full_range, gbr, a, frames_src, frames_dst) -> None:
+        """k_scale on device frames (tensors or pointers, each frame's planes contiguous from a 16-byte aligned base):
+        frames_dst[f] receives frames_src[f] resampled from src_w x src_h to dst_w x dst_h (Lanczos, a lobes)."""
+        n = len(frames_src)
+        if len(frames_dst) != n:
+            raise ValueError("frames_src and frames_dst differ in length")
+        ps = (C.c_void_p * max(n, 1))(*[self._ptr(x) for x in frames_src])
+        pd = (C.c_void_p * max(n, 1))(*[self._ptr(x) for x in frames_dst])
+        self._check(self.lib.h2y_scale_batch(self.h, src_w, src_h, dst_w, dst_h, chroma, bit_depth, full_range, gbr, a, n, ps, pd))
+
     # ---- host <-> device pipeline -----------------------------------------------------------
+    def stream_scale(self, dst_w, dst_h, a=3) -> None:
+        """Arm an open forward ring (plain, DPX, TIFF or EXR): stream_output then returns the frame scaled to dst_w x dst_h."""
+        self._check(self.lib.h2y_stream_scale(self.h, dst_w, dst_h, a))
+        self._stream_out_words = scale_frame_bytes(dst_w, dst_h, self._stream_desc.dst_chroma_format_idc) // 2
+
+    def scale_stream_open(self, src_w, src_h, chroma, bit_depth, full_range, gbr, dst_w, dst_h, a=3, depth=3) -> None:
+        """A ring that only scales: stream_input lends the frame's three planes, stream_output returns the scaled frame."""
+        self._check(self.lib.h2y_scale_stream_open(self.h, src_w, src_h, chroma, bit_depth, full_range, gbr, dst_w, dst_h, a, depth))
+        nc = (src_w >> 1) * (src_h >> 1) if chroma == CHROMA_420 else src_w * src_h
+        self._stream_inverse = None
+        self._stream_dpx = None
+        self._stream_rgb = False
+        self._stream_cmp_planes = (src_w * src_h, nc, nc)
+        self._stream_out_words = scale_frame_bytes(dst_w, dst_h, chroma) // 2
+
     def stream_histogram(self, bits=0, bit_depth=None, full_range=None, gbr=None) -> None:
         """Arm the open ring: every frame is counted on the device (h2y_stream_histogram; with bit_depth, full_range and gbr
         given, h2y_stream_histogram_ex, as a compare-only ring needs)."""
@@ -907,6 +965,8 @@ class Context:
         self._check(self.lib.h2y_stream_output(self.h, C.byref(p)))
         if not p:  # an armed ring with keep_output 0, or a compare-only ring: the frame stayed on the device
             return None
+        if getattr(self, "_stream_out_words", None):  # a ring that scales
+            return np.ctypeslib.as_array(p, shape=(self._stream_out_words,))
         if getattr(self, "_stream_inverse", None):
             w, h, _ = self._stream_inverse
             if getattr(self, "_stream_rgb", False):
@@ -917,6 +977,7 @@ class Context:
     def stream_close(self) -> None:
         self._check(self.lib.h2y_stream_close(self.h))
         self._stream_cmp_planes = None
+        self._stream_out_words = None
         self._stream_inverse = None
         self._stream_dpx = None
         self._stream_rgb = False

@@ -49,12 +49,24 @@
  *             --ref_filename and --histogram.  Refused (exit 1, also under --dry_run) unless the destination transfer is PQ (16), the
  *             source transfer is not PQ and the source matrix is G,B,R (0); refused on the .yuv -> RGB flow, with --compare_only 1
  *             and with --histogram_only 1.
+ * --scale 1 [--scale_taps 2|3|4] (an addition; the reference parses --dst_pic_width / --dst_pic_height for a Lanczos cv::resize in
+ *             cv.cpp, which is compiled out and does not compile): with it a destination size that differs from the source's is
+ *             legal on the forward flow to .yuv, and every converted frame is resampled on the device by the exact Lanczos
+ *             filter include/hdr2yuv_hip.h defines (3 lobes by default) before it is written.  Without it a size mismatch still
+ *             ends the run.  Refused (exit 1, also under --dry_run): --scale_taps without --scale / --scale_only or outside
+ *             2..4, an axis ratio outside [1/4, 4], odd sizes with 4:2:0, chroma_format_idc 2, --scale beside --ref_filename,
+ *             --histogram, --ssim, --compare_only or --histogram_only, and on the .yuv -> RGB flow.
+ * --scale_only 1 (an addition): a .yuv (4:2:0 or 4:4:4) or .rgb source resampled into a destination of the same extension, no
+ *             conversion; depth, chroma format and range are the source's, read as --histogram_only reads them; the destination
+ *             size is --dst_pic_width / --dst_pic_height.
  * Only user_args_t.chroma_resampler_type has no defined default there (never initialised): FIR here, as in
  * make.sh's example.  The reference calls exit(0) on its argument errors; this program returns 1.
  */
 #ifndef H2Y_CLI_ARGS_H
 #define H2Y_CLI_ARGS_H
 
+#include <algorithm>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -96,6 +108,9 @@ struct cli_args {
     int hist_bits = 0, hist_only = 0, check_range = 0;
     bool hist_bits_given = false;
     int hist_depth = 0, hist_full = 0, hist_gbr = 0, hist_chroma = 0;
+    /* scaling: --scale 1 (the forward flow's frames), --scale_only 1 (a .yuv or .rgb, no conversion), --scale_taps (lobes) */
+    int scale = 0, scale_only = 0, scale_taps = 3;
+    bool scale_given = false, scale_taps_given = false;
     std::vector<int> devices;
     /* resolved */
     int in_type = CLI_IN_NONE, out_type = CLI_OUT_NONE;
@@ -153,6 +168,9 @@ static inline void cli_help()
            "  totals into FILE; exit status 4 on a sample outside the legal range), [--histogram_only 1] (--src_filename, no conversion)\n"
            "  content light: [--content_light 1] (MaxCLL and MaxFALL of a conversion to PQ, per frame and for the run; without\n"
            "  --dst_filename nothing is written)\n"
+           "  scaling: [--scale 1 [--scale_taps A]] (with --dst_pic_width / --dst_pic_height: every .yuv frame resampled on the GPU by\n"
+           "  an exact Lanczos filter of A = 2, 3 or 4 lobes, 3 by default; each axis ratio within 1/4 .. 4), [--scale_only 1] (a .yuv or\n"
+           "  .rgb source into a destination of the same extension, no conversion)\n"
            "input by extension: .yuv .rgb (16-bit planar), .f32 .f16 (raw planar float / half, plane order G,B,R: what\n"
            "  dpx_read() / read_exr() leave in memory), .dpx (10-bit, 16-bit or float DPX) and .tiff (16-bit R,G,B, uncompressed; centre-cropped\n"
            "  to 3840 wide, [--cutout_hd 1] 1920x1080, [--cutout_qhd 1] 960x540) and .exr (scanline OpenEXR: NONE, RLE, ZIPS or ZIP;\n"
@@ -183,6 +201,9 @@ static inline void cli_parse(cli_args &a, int argc, char **argv)
         else if (is("--histogram_bits")) { a.hist_bits = atoi(val()); a.hist_bits_given = true; }
         else if (is("--histogram_only")) a.hist_only = atoi(val());
         else if (is("--check_range")) a.check_range = atoi(val());
+        else if (is("--scale")) { a.scale = atoi(val()); a.scale_given = true; }
+        else if (is("--scale_only")) a.scale_only = atoi(val());
+        else if (is("--scale_taps")) { a.scale_taps = atoi(val()); a.scale_taps_given = true; }
         else if (is("--alpha_channel")) (void)val(); /* (read_tiff ignores alpha too) */
         else if (is("--cutout_hd")) a.cutout = atoi(val()) ? (a.cutout | H2Y_TIFF_CUTOUT_HD) : (a.cutout & ~H2Y_TIFF_CUTOUT_HD);
         else if (is("--cutout_qhd")) a.cutout = atoi(val()) ? (a.cutout | H2Y_TIFF_CUTOUT_QHD) : (a.cutout & ~H2Y_TIFF_CUTOUT_QHD);
@@ -350,13 +371,122 @@ static inline int cli_resolve_histogram(cli_args &a)
 static inline int cli_resolve_convert(cli_args &a);
 static inline int cli_resolve_ssim(cli_args &a);
 static inline int cli_resolve_light(cli_args &a);
+static inline int cli_resolve_scale_only(cli_args &a);
+static inline int cli_resolve_scale(cli_args &a);
 static inline int cli_resolve(cli_args &a)
 {
-    int arg_errors = a.hist_only ? cli_resolve_histogram_only(a) : a.compare_only ? cli_resolve_compare(a) : cli_resolve_convert(a);
+    int arg_errors = a.hist_only    ? cli_resolve_histogram_only(a)
+                     : a.compare_only ? cli_resolve_compare(a)
+                     : a.scale_only   ? cli_resolve_scale_only(a)
+                                      : cli_resolve_convert(a);
     if (a.hist || a.hist_bits_given || a.hist_only || a.check_range) arg_errors += cli_resolve_histogram(a);
     if (a.ssim_given) arg_errors += cli_resolve_ssim(a);
     if (a.light_given) arg_errors += cli_resolve_light(a);
+    if (a.scale_given || a.scale_only || a.scale_taps_given) arg_errors += cli_resolve_scale(a);
     return arg_errors;
+}
+
+/* --scale_only 1: one file resampled into another of the same layout, no conversion; returns the number of argument errors */
+static inline int cli_resolve_scale_only(cli_args &a)
+{
+    int arg_errors = 0;
+    const char *ext = cli_ext_of(a.src);
+    if (!strcasecmp(ext, "yuv")) a.in_type = CLI_IN_YUV;
+    else if (!strcasecmp(ext, "rgb")) a.in_type = CLI_IN_RGB;
+    else {
+        printf("WARNING: --scale_only reads .yuv or .rgb; source file (%s) is a .%s\n", a.src ? a.src : "(none)", ext);
+        arg_errors++;
+    }
+    if (!a.dst) { printf("WARNING: --scale_only needs --dst_filename\n"); arg_errors++; }
+    else if (a.in_type != CLI_IN_NONE && strcasecmp(cli_ext_of(a.dst), ext)) {
+        printf("WARNING: --scale_only writes what it reads: destination file (%s) must be a .%s like the source\n", a.dst, ext);
+        arg_errors++;
+    }
+    if (a.ref || a.hist) { printf("WARNING: --scale_only reads one file and writes one: leave out --ref_filename and --histogram\n"); arg_errors++; }
+    printf("scale_only: 1\nsrc_filename: %s\ndst_filename: %s\n", a.src ? a.src : "(none)", a.dst ? a.dst : "(none)");
+    printf("src_pic_width: %d\nsrc_pic_height: %d\nsrc_chroma_format_idc: %d\nsrc_bit_depth: %d\nsrc_video_full_range_flag: %d\n"
+           "src_start_frame: %d\nn_frames: %d\n", a.in.width, a.in.height, a.in.chroma_format_idc, a.in.bit_depth,
+           a.in.video_full_range_flag, a.start_frame, a.n_frames);
+    if (a.in.bit_depth < 8 || a.in.bit_depth > 16) { printf("WARNING: src bit_depth(%d) outside range [8,16]\n", a.in.bit_depth); arg_errors++; }
+    if (a.in.video_full_range_flag != 0 && a.in.video_full_range_flag != 1) {
+        printf("WARNING: video_full_range_flag(%d) not 0 or 1\n", a.in.video_full_range_flag);
+        arg_errors++;
+    }
+    if (a.in_type == CLI_IN_RGB && a.in.chroma_format_idc != H2Y_CHROMA_444 && a.in.chroma_format_idc != 2) { /* three full planes R, G, B */
+        printf("WARNING: a .rgb holds three planes of width x height: --scale_only of a .rgb takes chroma_format_idc %d, not %d\n",
+               H2Y_CHROMA_444, a.in.chroma_format_idc);
+        arg_errors++;
+    }
+    const int dw = a.out.width ? a.out.width : a.in.width, dh = a.out.height ? a.out.height : a.in.height;
+    a.out = a.in;
+    a.out.width = dw, a.out.height = dh;
+    a.out_type = a.in_type == CLI_IN_RGB ? CLI_OUT_RGB : CLI_OUT_YUV;
+    printf("dst_pic_width: %d\ndst_pic_height: %d\n", dw, dh);
+    return arg_errors;
+}
+
+/* --scale / --scale_only / --scale_taps: what is resampled, printed; returns the number of argument errors */
+static inline int cli_resolve_scale(cli_args &a)
+{
+    int arg_errors = 0;
+    if (a.scale != 0 && a.scale != 1) { printf("WARNING: scale(%d) not 0 or 1\n", a.scale); arg_errors++; }
+    if (a.scale_only != 0 && a.scale_only != 1) { printf("WARNING: scale_only(%d) not 0 or 1\n", a.scale_only); arg_errors++; }
+    if (a.scale_taps_given && !a.scale && !a.scale_only) { printf("WARNING: --scale_taps needs --scale 1 or --scale_only 1\n"); arg_errors++; }
+    if (a.scale_taps < 2 || a.scale_taps > 4) { printf("WARNING: scale_taps(%d) outside range [2,4]\n", a.scale_taps); arg_errors++; }
+    if (a.scale && a.scale_only) { printf("WARNING: --scale 1 scales a conversion, --scale_only 1 a file: give one of them\n"); arg_errors++; }
+    if (a.scale_only && (a.compare_only || a.hist_only)) {
+        printf("WARNING: --scale_only 1: not with --%s 1\n", a.compare_only ? "compare_only" : "histogram_only");
+        arg_errors++;
+    }
+    if (arg_errors || (!a.scale && !a.scale_only)) return arg_errors;
+    if (a.scale) {
+        if (a.compare_only || a.hist_only) {
+            printf("WARNING: --scale 1 scales a conversion: not with --%s 1\n", a.compare_only ? "compare_only" : "histogram_only");
+            return 1;
+        }
+        if (a.ref || a.hist || a.ssim) {
+            printf("WARNING: --scale 1 is not combined with --ref_filename, --histogram or --ssim: compare or count the written file "
+                   "(--compare_only 1, --histogram_only 1)\n");
+            return 1;
+        }
+        if (a.inverse) {
+            printf("WARNING: --scale 1 scales the forward flow (to .yuv), not the .yuv -> RGB flow\n");
+            return 1;
+        }
+        if (a.out_type != CLI_OUT_YUV) return 0; /* refused above with its own message */
+    }
+    const int chroma = a.out.chroma_format_idc, depth = a.out.bit_depth, full = a.out.video_full_range_flag;
+    const bool gbr = a.scale_only && a.in_type == CLI_IN_RGB;
+    if (chroma == 2) { printf("WARNING: --scale%s 1: chroma_format_idc 2 (4:2:2) is not scaled\n", a.scale_only ? "_only" : ""); return 1; }
+    if (chroma != H2Y_CHROMA_420 && chroma != H2Y_CHROMA_444) {
+        printf("WARNING: chroma_format_idc(%d) not %d or %d\n", chroma, H2Y_CHROMA_420, H2Y_CHROMA_444);
+        return 1;
+    }
+    const int sw = a.in.width, sh = a.in.height, dw = a.out.width, dh = a.out.height;
+    if (sw < 2 || sh < 2 || dw < 2 || dh < 2 || sw > 10000 || sh > 10000 || dw > 10000 || dh > 10000) {
+        printf("WARNING: scaling %dx%d -> %dx%d: widths and heights outside range [2,10000]\n", sw, sh, dw, dh);
+        return 1;
+    }
+    if (sw > 4 * dw || dw > 4 * sw || sh > 4 * dh || dh > 4 * sh) {
+        printf("WARNING: scaling %dx%d -> %dx%d: each axis ratio must lie within [1/4, 4]\n", sw, sh, dw, dh);
+        return 1;
+    }
+    if (chroma == H2Y_CHROMA_420 && ((sw | sh | dw | dh) & 1)) {
+        printf("WARNING: scaling %dx%d -> %dx%d: 4:2:0 needs even widths and heights\n", sw, sh, dw, dh);
+        return 1;
+    }
+    if (depth < 8 || depth > 16) { printf("WARNING: scaling takes frames of bit_depth 8..16, not %d\n", depth); return 1; }
+    std::vector<int32_t> first((size_t)std::max(dw, dh)), count(first.size());
+    std::vector<int16_t> coef(first.size() * H2Y_SCALE_TAPS);
+    int th = 0, tv = 0;
+    if (h2y_scale_taps(sw, dw, a.scale_taps, first.data(), count.data(), coef.data(), &th) ||
+        h2y_scale_taps(sh, dh, a.scale_taps, first.data(), count.data(), coef.data(), &tv)) {
+        printf("WARNING: scaling %dx%d -> %dx%d: %s\n", sw, sh, dw, dh, h2y_last_error(nullptr));
+        return 1;
+    }
+    printf("scale: %dx%d -> %dx%d lanczos%d chroma_format_idc %d bit_depth %d %s range, planes %s, taps h %d v %d\n", sw, sh, dw, dh,
+           a.scale_taps, chroma, depth, full ? "full" : "video", gbr ? "G,B,R" : "Y,Cb,Cr", th, tv);
+    return 0;
 }
 
 /* --content_light: the forward flow of a conversion to PQ from another transfer, of a G,B,R source; returns the number of argument

@@ -68,6 +68,11 @@
  *   light summary frames <N> maxcll <CLL> frame <k> maxfall <FALL> frame <k>    the largest of each, the first such frame on ties
  *   light x265 --max-cll "<CLL>,<FALL>"
  *   light svt-av1 --content-light <CLL>,<FALL>
+ *
+ * Scaling (--scale 1 [--scale_taps A] with --dst_pic_width / --dst_pic_height on the forward flow; h2y_cli_args.h): each GPU thread
+ * arms its ring (h2y_stream_scale), so the frame that comes down is the converted frame resampled on the device to the destination
+ * size (include/hdr2yuv_hip.h states the filter); frame k is written at `size of the file at start + k x scaled frame bytes`.
+ * --scale_only 1 resamples a .yuv or .rgb source through a scale-only ring (h2y_scale_stream_open) into a file of the same layout.
  */
 #include <algorithm>
 #include <array>
@@ -516,6 +521,8 @@ static void run_block(const cli_args &a, const h2y_desc &d, const std::vector<dp
     if (a.ssim && h2y_stream_ssim(ctx, -1)) return fail(h2y_last_error(ctx));
     if (hist->on && h2y_stream_histogram(ctx, a.hist_bits)) return fail(h2y_last_error(ctx));
     if (a.light && h2y_stream_light(ctx)) return fail(h2y_last_error(ctx));
+    if (a.scale && h2y_stream_scale(ctx, a.out.width, a.out.height, a.scale_taps)) return fail(h2y_last_error(ctx));
+    const size_t wb = a.scale ? h2y_scale_frame_bytes(a.out.width, a.out.height, a.out.chroma_format_idc) : ob; /* what comes down */
     std::unique_ptr<unpack_pool> pool;
     std::vector<h2y_exr_chunk> chunks;
     if (a.in_type == CLI_IN_EXR) {
@@ -531,8 +538,8 @@ static void run_block(const cli_args &a, const h2y_desc &d, const std::vector<dp
         if (a.ssim && h2y_stream_ssim_result(ctx, &(*ssim)[k])) { fail(h2y_last_error(ctx)); return false; }
         if (!hist->take(ctx, k)) { fail(h2y_last_error(ctx)); return false; }
         if (a.light && h2y_stream_light_result(ctx, &(*light)[k])) { fail(h2y_last_error(ctx)); return false; }
-        if (a.dst && !write_at(fd_out, yuv, ob, base + (off_t)k * (off_t)ob)) { fail(std::string("short write to ") + a.dst); return false; }
-        if (a.verbose > 0 && a.dst) printf("frame %ld: %zu bytes written to %s (device %d)\n", k, ob, a.dst, b->device);
+        if (a.dst && !write_at(fd_out, yuv, wb, base + (off_t)k * (off_t)wb)) { fail(std::string("short write to ") + a.dst); return false; }
+        if (a.verbose > 0 && a.dst) printf("frame %ld: %zu bytes written to %s (device %d)\n", k, wb, a.dst, b->device);
         b->done++;
         in_flight--;
         return true;
@@ -784,6 +791,58 @@ static void run_block_histogram(const cli_args &a, size_t plane_bytes, size_t fr
     h2y_ctx_destroy(ctx);
 }
 
+/* --scale_only: frames [first, first+count) of the source through one scale-only ring into the destination */
+static void run_block_scale(const cli_args &a, size_t plane_bytes, size_t frame_bytes, size_t out_bytes, int fd_out, off_t base, block *b)
+{
+    h2y_ctx *ctx = nullptr;
+    FILE *fin = nullptr;
+    auto fail = [&](const std::string &m) {
+        b->err = m;
+        if (ctx) { h2y_stream_close(ctx); h2y_ctx_destroy(ctx); }
+        if (fin) fclose(fin);
+    };
+    if (b->count < 1) return;
+    if (h2y_ctx_create(b->device, &ctx)) return fail(h2y_last_error(nullptr));
+    fin = fopen(a.src, "rb");
+    if (!fin) return fail(std::string("unable to open file ") + a.src);
+    if (fseeko(fin, (off_t)frame_bytes * (off_t)(a.start_frame + b->first), SEEK_SET)) return fail("seek failed");
+    const int depth = 3;
+    const bool rgb = a.in_type == CLI_IN_RGB;
+    if (h2y_scale_stream_open(ctx, a.in.width, a.in.height, a.in.chroma_format_idc, a.in.bit_depth, a.in.video_full_range_flag, rgb ? 1 : 0,
+                              a.out.width, a.out.height, a.scale_taps, depth))
+        return fail(h2y_last_error(ctx));
+    const size_t on = (size_t)a.out.width * a.out.height * 2; /* bytes of one full output plane */
+    long in_flight = 0;
+    auto drain_one = [&]() -> bool {
+        const uint16_t *out = nullptr;
+        if (h2y_stream_output(ctx, &out)) { fail(h2y_last_error(ctx)); return false; }
+        const long k = b->first + b->done;
+        const off_t at = base + (off_t)k * (off_t)out_bytes;
+        const char *p = reinterpret_cast<const char *>(out);
+        /* a .rgb: planes G, B, R -> file order R, G, B */
+        const bool ok = rgb ? write_at(fd_out, p + 2 * on, on, at) && write_at(fd_out, p, 2 * on, at + (off_t)on) : write_at(fd_out, p, out_bytes, at);
+        if (!ok) { fail(std::string("short write to ") + a.dst); return false; }
+        if (a.verbose > 0) printf("frame %ld: %zu bytes written to %s (device %d)\n", k, out_bytes, a.dst, b->device);
+        b->done++;
+        in_flight--;
+        return true;
+    };
+    for (long f = 0; f < b->count; f++) {
+        void *planes[3];
+        if (h2y_stream_input(ctx, planes)) return fail(h2y_last_error(ctx));
+        /* the slot's planes lie one after the other: a frame is one read, a .rgb one with its planes put in G, B, R order */
+        if (!read_ref(fin, rgb, plane_bytes, frame_bytes, planes[0])) return fail(std::string("short read from ") + a.src);
+        if (h2y_stream_submit(ctx)) return fail(h2y_last_error(ctx));
+        in_flight++;
+        if (in_flight == depth - 1 && !drain_one()) return;
+    }
+    while (in_flight > 0)
+        if (!drain_one()) return;
+    h2y_stream_close(ctx);
+    fclose(fin);
+    h2y_ctx_destroy(ctx);
+}
+
 /* the histogram report of the header comment and FILE; returns the exit status (4: --check_range 1 and samples outside) */
 static int histogram_report(const cli_args &a, const std::vector<h2y_histogram_stats> &st, const std::vector<std::array<uint32_t, 3>> &occ,
                             const std::vector<uint64_t> &total)
@@ -939,7 +998,7 @@ int main(int argc, char **argv)
 {
     cli_args a;
     cli_parse(a, argc, argv);
-    if ((!a.dst && !a.ref && !a.hist && !a.hist_only && !a.light) || (!a.src && a.synthetic < 0)) {
+    if ((!a.dst && !a.ref && !a.hist && !a.hist_only && !a.light && !a.scale_only) || (!a.src && a.synthetic < 0)) {
         if (!a.help) cli_help();
         return a.help ? 0 : 1;
     }
@@ -959,14 +1018,16 @@ int main(int argc, char **argv)
         printf("src_picture: matrix_coeffs %d chroma_format_idc %d bit_depth %d video_full_range_flag %d\n", a.in.matrix_coeffs,
                a.in.chroma_format_idc, a.in.bit_depth, a.in.video_full_range_flag);
     }
-    if (a.out.width != a.in.width || a.out.height != a.in.height) {
-        printf("ERROR: resizing is not part of convert() (cv.cpp is compiled out in the reference)\n");
+    const bool scaling = a.scale == 1 || a.scale_only == 1;
+    if (!scaling && (a.out.width != a.in.width || a.out.height != a.in.height)) {
+        printf("ERROR: resizing is not part of convert() (cv.cpp is compiled out in the reference); --scale 1 resamples the .yuv frames on "
+               "the GPU\n");
         return 1;
     }
     h2y_desc d;
     cli_make_desc(a, &d);
     size_t in_frame_bytes, out_frame_bytes;
-    if (a.compare_only || a.hist_only) { /* two files of one layout, or one */
+    if (a.compare_only || a.hist_only || a.scale_only) { /* two files of one layout, or one */
         const size_t n = (size_t)a.in.width * a.in.height;
         const size_t nc = a.in.chroma_format_idc == H2Y_CHROMA_420 ? (size_t)(a.in.width / 2) * (a.in.height / 2) : n;
         in_frame_bytes = out_frame_bytes = (n + 2 * nc) * 2;
@@ -986,6 +1047,7 @@ int main(int argc, char **argv)
         in_frame_bytes = 3 * h2y_plane_bytes(&d);
         out_frame_bytes = h2y_frame_bytes(&d);
     }
+    if (scaling) out_frame_bytes = h2y_scale_frame_bytes(a.out.width, a.out.height, a.out.chroma_format_idc); /* the scaled frame's */
 
     /* how many frames there are to do: --n_frames, or what the file holds from --src_start_frame on if that is fewer */
     long frames = a.n_frames > 0 ? a.n_frames : 1;
@@ -1094,6 +1156,7 @@ int main(int argc, char **argv)
     auto work = [&](block *b) {
         histogram_io *hi = &hist[b - blocks.data()];
         if (a.hist_only) run_block_histogram(a, (size_t)a.in.width * a.in.height * 2, in_frame_bytes, hi, b);
+        else if (a.scale_only) run_block_scale(a, (size_t)a.in.width * a.in.height * 2, in_frame_bytes, out_frame_bytes, fd, base, b);
         else if (a.compare_only) run_block_compare(a, (size_t)a.in.width * a.in.height * 2, in_frame_bytes, &stats, &sstats, hi, b);
         else if (a.inverse) run_block_inverse(a, tw, fd, base, &stats, &sstats, hi, b);
         else run_block(a, d, dpx, di, tiff, ti, exr, xi, fd, base, &stats, &sstats, &lstats, hi, b);

@@ -8,6 +8,7 @@
  */
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -228,6 +229,9 @@ struct h2y_ctx {
     size_t light_as_cap = 0;
     light_acc *d_light_acc = nullptr;
     size_t light_acc_cap = 0;
+    /* h2y_scale_batch's tap tables on the device */
+    char *d_scale_tabs = nullptr;
+    size_t scale_tabs_cap = 0;
 
     /* staging for the host-buffer entry */
     void *d_in = nullptr;
@@ -258,6 +262,8 @@ struct h2y_ctx {
         h2y_ssim_stats *d_ssim = nullptr, *h_ssim = nullptr;
         /* a ring armed by h2y_stream_light: the frame's k_light accumulator on the device and pinned */
         light_acc *d_light = nullptr, *h_light = nullptr;
+        /* a forward ring armed by h2y_stream_scale: the scaled frame on the device and pinned */
+        uint16_t *d_scaled = nullptr, *h_scaled = nullptr;
     };
     std::vector<stream_slot> ss;
     hipStream_t s_h2d = nullptr, s_d2h = nullptr;
@@ -267,7 +273,7 @@ struct h2y_ctx {
     bool streaming = false;
     /* what the ring does with a frame: the forward conversion (open_forward_ring), the .yuv -> G,B,R flow (open_inverse_ring),
      * a comparison alone (h2y_compare_stream_open) or a histogram alone (h2y_histogram_stream_open) */
-    enum ring_kind { RING_FORWARD, RING_INVERSE, RING_COMPARE, RING_HISTOGRAM } s_kind = RING_FORWARD;
+    enum ring_kind { RING_FORWARD, RING_INVERSE, RING_COMPARE, RING_HISTOGRAM, RING_SCALE } s_kind = RING_FORWARD;
     /* a forward ring's decode: with one, the pinned slot holds the payload, its device twin the three planes (at s_in_off[0..2])
      * and then the payload at s_pay_off */
     decode_src s_src;
@@ -299,6 +305,14 @@ struct h2y_ctx {
     bool s_light = false;
     light_args s_light_args{};
     light_frame *s_light_tab = nullptr;
+    /* a forward ring armed by h2y_stream_scale (source: the slot's device output, target: its d_scaled) or a scale-only ring
+     * (h2y_scale_stream_open; the slot's input and output): k_scale's geometry, its tables on the device, each slot's table
+     * entry and the scaled frame's bytes */
+    bool s_scale = false;
+    scale_geom s_scale_geom{};
+    char *s_scale_tabs = nullptr;
+    scale_frame *s_scale_tab = nullptr;
+    size_t s_scale_bytes = 0;
     size_t s_ref_bytes = 0, s_ref_stats_off = 0; /* the pinned reference's bytes; where the stats lie in its device twin */
     int slot_base = 0; /* run_frames(): first entry of d_frames/h_frames to use (one per stream slot) */
     float last_ms = 0.f;
@@ -1484,6 +1498,7 @@ void h2y_ctx_destroy(h2y_ctx *ctx)
     (void)hipFree(ctx->d_ssim_stats);
     (void)hipFree(ctx->d_light_as);
     (void)hipFree(ctx->d_light_acc);
+    (void)hipFree(ctx->d_scale_tabs);
     (void)hipFree(ctx->d_in);
     (void)hipFree(ctx->d_out);
     if (ctx->fir_stream) {
@@ -2149,6 +2164,8 @@ static void stream_free(h2y_ctx *ctx)
         if (s.h_ssim) (void)hipHostFree(s.h_ssim);
         if (s.d_light) (void)hipFree(s.d_light);
         if (s.h_light) (void)hipHostFree(s.h_light);
+        if (s.d_scaled) (void)hipFree(s.d_scaled);
+        if (s.h_scaled) (void)hipHostFree(s.h_scaled);
     }
     ctx->ss.clear();
     if (ctx->s_h2d) (void)hipStreamDestroy(ctx->s_h2d);
@@ -2165,6 +2182,11 @@ static void stream_free(h2y_ctx *ctx)
     if (ctx->s_light_tab) (void)hipFree(ctx->s_light_tab);
     ctx->s_light_tab = nullptr;
     ctx->s_light = false;
+    if (ctx->s_scale_tabs) (void)hipFree(ctx->s_scale_tabs);
+    if (ctx->s_scale_tab) (void)hipFree(ctx->s_scale_tab);
+    ctx->s_scale_tabs = nullptr;
+    ctx->s_scale_tab = nullptr;
+    ctx->s_scale = false;
     ctx->streaming = false;
     ctx->s_kind = h2y_ctx::RING_FORWARD;
     ctx->s_src = decode_src();
@@ -3121,6 +3143,7 @@ int h2y_stream_compare(h2y_ctx *ctx, int sigma, int keep_output)
     if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
     if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
     if (ctx->s_cmp) return fail(ctx, H2Y_EINVAL, "the ring is armed already");
+    if (ctx->s_scale) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that scales is not compared: compare the written file instead");
     if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
     if (keep_output != 0 && keep_output != 1) return fail(ctx, H2Y_EINVAL, "keep_output must be 0 or 1");
     uint32_t a_off[3];
@@ -3291,6 +3314,7 @@ int h2y_stream_ssim(h2y_ctx *ctx, int bit_depth)
 {
     if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
     if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    if (ctx->s_scale) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that scales computes no SSIM: compare the written file instead");
     if (!ctx->s_cmp) return fail(ctx, H2Y_EINVAL, "the ring is not armed for comparison: h2y_stream_compare first");
     if (ctx->s_ssim) return fail(ctx, H2Y_EINVAL, "the ring computes SSIM already");
     if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
@@ -3673,6 +3697,7 @@ int h2y_stream_histogram_ex(h2y_ctx *ctx, int bits, int bit_depth, int full_rang
     if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
     if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
     if (ctx->s_hist) return fail(ctx, H2Y_EINVAL, "the ring counts histograms already");
+    if (ctx->s_scale) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that scales counts no histograms: count the written file instead");
     if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
     uint32_t off[3];
     int width, height, chroma, depth, full, rgb;
@@ -3754,6 +3779,318 @@ static int hist_download(h2y_ctx *ctx, h2y_ctx::stream_slot &s)
     HIP_TRY(ctx, hipMemcpyAsync(s.h_hist_stats, s.d_hist + L.stats, sizeof(h2y_histogram_stats), hipMemcpyDeviceToHost, ctx->s_d2h));
     HIP_TRY(ctx, hipMemcpyAsync(s.h_hist_bins, s.d_hist + L.bins, (size_t)3u * ctx->s_hist_geom.nbins * sizeof(uint32_t),
                                 hipMemcpyDeviceToHost, ctx->s_d2h));
+    return H2Y_OK;
+}
+
+/* ---- scaling: the Lanczos resampler of include/hdr2yuv_hip.h ----------------------------------------------------------------- */
+
+static double scale_sinc(double x) { return x == 0.0 ? 1.0 : sin(M_PI * x) / (M_PI * x); }
+
+/* one axis' table as the header defines it, in binary64; rc H2Y_EUNSUPPORTED for a row of sum |q| > 32767 */
+static int scale_axis_table(int s, int d, int a, int32_t *first, int32_t *count, int16_t *coef, int *max_taps)
+{
+    const double f = s > d ? (double)s / (double)d : 1.0, r = (double)a * f;
+    int most = 0;
+    for (int o = 0; o < d; o++) {
+        const double c = (((double)o + 0.5) * (double)s) / (double)d - 0.5;
+        int idx[H2Y_SCALE_TAPS + 2];
+        double w[H2Y_SCALE_TAPS + 2], S = 0.0;
+        int n = 0;
+        for (int i = (int)ceil(c - r), hi = (int)floor(c + r); i <= hi; i++) {
+            if (!(fabs((double)i - c) < r)) continue;
+            if (n == H2Y_SCALE_TAPS) return H2Y_EUNSUPPORTED;
+            const double t = ((double)i - c) / f;
+            idx[n] = i;
+            w[n] = scale_sinc(t) * scale_sinc(t / (double)a);
+            S += w[n];
+            n++;
+        }
+        if (n == 0) return H2Y_EUNSUPPORTED;
+        int q[H2Y_SCALE_TAPS], sum = 0, big = 0;
+        for (int k = 0; k < n; k++) {
+            q[k] = (int)rint(w[k] * 16384.0 / S);
+            sum += q[k];
+            if (q[k] > q[big]) big = k;
+        }
+        q[big] += 16384 - sum;
+        const int lo = idx[0] < 0 ? 0 : idx[0] > s - 1 ? s - 1 : idx[0];
+        int folded[H2Y_SCALE_TAPS] = {0}, m = 0, mag = 0;
+        for (int k = 0; k < n; k++) {
+            const int i = idx[k] < 0 ? 0 : idx[k] > s - 1 ? s - 1 : idx[k];
+            folded[i - lo] += q[k];
+            m = i - lo + 1;
+        }
+        for (int k = 0; k < m; k++) mag += folded[k] < 0 ? -folded[k] : folded[k];
+        if (mag > 32767) return H2Y_EUNSUPPORTED;
+        first[o] = lo;
+        count[o] = m;
+        for (int k = 0; k < H2Y_SCALE_TAPS; k++) coef[(size_t)o * H2Y_SCALE_TAPS + k] = (int16_t)(k < m ? folded[k] : 0);
+        most = m > most ? m : most;
+    }
+    if (max_taps) *max_taps = most;
+    return H2Y_OK;
+}
+
+static bool scale_axis_ok(int s, int d) { return s >= 1 && d >= 1 && s <= 10000 && d <= 10000 && s <= 4 * d && d <= 4 * s; }
+
+int h2y_scale_taps(int src, int dst, int a, int32_t *first, int32_t *count, int16_t *coef, int *max_taps)
+{
+    if (!first || !count || !coef) return fail(nullptr, H2Y_EINVAL, "null table");
+    if (a < 2 || a > 4) return fail(nullptr, H2Y_EINVAL, "a (lobes) must be 2, 3 or 4");
+    if (!scale_axis_ok(src, dst)) return fail(nullptr, H2Y_EINVAL, "sizes must be 1..10000 with a ratio in [1/4, 4]");
+    const int rc = scale_axis_table(src, dst, a, first, count, coef, max_taps);
+    if (rc) return fail(nullptr, rc, "a table row's coefficients do not fit (sum |q| > 32767)");
+    return H2Y_OK;
+}
+
+size_t h2y_scale_frame_bytes(int width, int height, int chroma_format_idc)
+{
+    if (width < 1 || height < 1 || width > 10000 || height > 10000) return 0;
+    if (chroma_format_idc == H2Y_CHROMA_444) return (size_t)width * height * 3u * sizeof(uint16_t);
+    if (chroma_format_idc != H2Y_CHROMA_420) return 0;
+    return ((size_t)width * height + 2u * (size_t)(width >> 1) * (height >> 1)) * sizeof(uint16_t);
+}
+
+static int scale_check(h2y_ctx *ctx, int sw, int sh, int dw, int dh, int chroma, int bit_depth, int full_range, int gbr, int a)
+{
+    if (chroma == 2) return fail(ctx, H2Y_EUNSUPPORTED, "chroma_format_idc 2 (4:2:2) is not scaled");
+    if (chroma != H2Y_CHROMA_420 && chroma != H2Y_CHROMA_444) return fail(ctx, H2Y_EINVAL, "chroma_format_idc must be 1 or 3");
+    if (sw < 2 || sh < 2 || dw < 2 || dh < 2 || sw > 10000 || sh > 10000 || dw > 10000 || dh > 10000)
+        return fail(ctx, H2Y_EINVAL, "scaling: widths and heights must be 2..10000");
+    if (chroma == H2Y_CHROMA_420 && ((sw | sh | dw | dh) & 1)) return fail(ctx, H2Y_EINVAL, "scaling 4:2:0: widths and heights must be even");
+    if (!scale_axis_ok(sw, dw) || !scale_axis_ok(sh, dh)) return fail(ctx, H2Y_EINVAL, "scaling: each axis ratio must be in [1/4, 4]");
+    if (bit_depth < 8 || bit_depth > 16) return fail(ctx, H2Y_EINVAL, "bit_depth must be 8..16");
+    if ((full_range != 0 && full_range != 1) || (gbr != 0 && gbr != 1)) return fail(ctx, H2Y_EINVAL, "full_range and gbr must be 0 or 1");
+    if (a < 2 || a > 4) return fail(ctx, H2Y_EINVAL, "a (lobes) must be 2, 3 or 4");
+    return H2Y_OK;
+}
+
+/* k_scale's geometry with its tables still on the host: blob is what goes to the device, at[p][axis][0..2] where plane p's
+ * first, count and coef of that axis lie in it (4:4:4: one pair of tables serves the three planes) */
+struct scale_host {
+    scale_geom g{};
+    std::vector<char> blob;
+    size_t at[3][2][3]{};
+};
+
+static int scale_build(h2y_ctx *ctx, int sw, int sh, int dw, int dh, int chroma, int bit_depth, int full_range, int gbr, int a,
+                       const uint32_t src_off[3], const uint32_t dst_off[3], scale_host &H)
+{
+    const bool sub = chroma == H2Y_CHROMA_420;
+    const clip_limits c = make_clip(bit_depth, full_range);
+    size_t kind_at[2][2][3];
+    for (int kind = 0; kind < (sub ? 2 : 1); kind++)
+        for (int axis = 0; axis < 2; axis++) {
+            const int s = (axis ? sh : sw) >> kind, d = (axis ? dh : dw) >> kind;
+            const size_t ib = ((size_t)d * sizeof(int32_t) + 15) & ~(size_t)15, cb = (size_t)d * H2Y_SCALE_TAPS * sizeof(int16_t);
+            const size_t base = H.blob.size();
+            H.blob.resize(base + 2 * ib + cb);
+            kind_at[kind][axis][0] = base, kind_at[kind][axis][1] = base + ib, kind_at[kind][axis][2] = base + 2 * ib;
+            const int rc = scale_axis_table(s, d, a, reinterpret_cast<int32_t *>(&H.blob[base]), reinterpret_cast<int32_t *>(&H.blob[base + ib]),
+                                            reinterpret_cast<int16_t *>(&H.blob[base + 2 * ib]), nullptr);
+            if (rc) return fail(ctx, rc, "scaling %d -> %d: a table row's coefficients do not fit (sum |q| > 32767)", s, d);
+        }
+    uint32_t h_rows = 1, seg_max = 1;
+    for (int p = 0; p < 3; p++) {
+        const int kind = p && sub ? 1 : 0;
+        scale_plane &P = H.g.p[p];
+        P.sw = (uint32_t)(sw >> kind), P.sh = (uint32_t)(sh >> kind), P.dw = (uint32_t)(dw >> kind), P.dh = (uint32_t)(dh >> kind);
+        P.src_off = src_off[p], P.dst_off = dst_off[p];
+        P.tiles_x = (P.dw + H2Y_SCALE_TILE_W - 1) / H2Y_SCALE_TILE_W;
+        P.tiles = P.tiles_x * ((P.dh + H2Y_SCALE_TILE_H - 1) / H2Y_SCALE_TILE_H);
+        const bool luma_like = p == 0 || gbr;
+        P.lo = (int32_t)(luma_like ? c.minVR : c.minVRC);
+        P.hi = (int32_t)(luma_like ? c.maxVR : c.maxVRC);
+        for (int axis = 0; axis < 2; axis++)
+            for (int k = 0; k < 3; k++) H.at[p][axis][k] = kind_at[kind][axis][k];
+        /* the most source columns and rows one tile reads: what the kernel's LDS must hold */
+        for (int axis = 0; axis < 2; axis++) {
+            const int32_t *first = reinterpret_cast<const int32_t *>(&H.blob[H.at[p][axis][0]]);
+            const int32_t *count = reinterpret_cast<const int32_t *>(&H.blob[H.at[p][axis][1]]);
+            const uint32_t d = axis ? P.dh : P.dw, step = axis ? H2Y_SCALE_TILE_H : H2Y_SCALE_TILE_W;
+            for (uint32_t o0 = 0; o0 < d; o0 += step) {
+                const uint32_t o1 = std::min(d, o0 + step) - 1;
+                const uint32_t span = (uint32_t)(first[o1] + count[o1] - first[o0]);
+                if (axis) h_rows = std::max(h_rows, span);
+                else seg_max = std::max(seg_max, span);
+            }
+        }
+    }
+    H.g.h_rows = h_rows;
+    H.g.src_cols = (seg_max + 7u + 7u) & ~7u;
+    if (h2y_scale_lds(H.g) > 64u * 1024u) return fail(ctx, H2Y_EUNSUPPORTED, "scaling: a tile needs %zu bytes of LDS", h2y_scale_lds(H.g));
+    return H2Y_OK;
+}
+
+/* the tables' addresses once the blob lies at d_base */
+static void scale_bind(scale_host &H, const char *d_base)
+{
+    for (int p = 0; p < 3; p++) {
+        scale_axis *ax[2] = {&H.g.p[p].h, &H.g.p[p].v};
+        for (int axis = 0; axis < 2; axis++) {
+            ax[axis]->first = reinterpret_cast<const int32_t *>(d_base + H.at[p][axis][0]);
+            ax[axis]->count = reinterpret_cast<const int32_t *>(d_base + H.at[p][axis][1]);
+            ax[axis]->coef = reinterpret_cast<const int16_t *>(d_base + H.at[p][axis][2]);
+        }
+    }
+}
+
+static int scale_grid(const h2y_ctx *ctx, const scale_geom &g, int n_frames)
+{
+    return unit_grid(ctx, (uint64_t)n_frames * (g.p[0].tiles + g.p[1].tiles + g.p[2].tiles));
+}
+
+static std::string scale_variant(int chroma, int a)
+{
+    return std::string("k_scale<") + (chroma == H2Y_CHROMA_420 ? "420" : "444") + ",lanczos" + std::to_string(a) + ">";
+}
+
+int h2y_scale_batch(h2y_ctx *ctx, int src_w, int src_h, int dst_w, int dst_h, int chroma_format_idc, int bit_depth, int full_range,
+                    int gbr, int a, int n_frames, const uint16_t *const *d_src, uint16_t *const *d_dst)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
+    int rc = scale_check(ctx, src_w, src_h, dst_w, dst_h, chroma_format_idc, bit_depth, full_range, gbr, a);
+    if (rc) return rc;
+    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
+    if (!d_src || !d_dst) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
+    for (int f = 0; f < n_frames; f++) {
+        if (!d_src[f] || !d_dst[f]) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is null", f);
+        if (((uintptr_t)d_src[f] | (uintptr_t)d_dst[f]) & 15u) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is not 16-byte aligned", f);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    uint32_t src_off[3], dst_off[3];
+    cmp_contiguous(src_w, src_h, chroma_format_idc, src_off);
+    cmp_contiguous(dst_w, dst_h, chroma_format_idc, dst_off);
+    scale_host H;
+    rc = scale_build(ctx, src_w, src_h, dst_w, dst_h, chroma_format_idc, bit_depth, full_range, gbr, a, src_off, dst_off, H);
+    if (rc) return rc;
+    scale_frame *h;
+    rc = frame_table(ctx, n_frames, h);
+    if (!rc) rc = ensure(ctx, ctx->d_scale_tabs, ctx->scale_tabs_cap, H.blob.size());
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpy(ctx->d_scale_tabs, H.blob.data(), H.blob.size(), hipMemcpyHostToDevice));
+    scale_bind(H, ctx->d_scale_tabs);
+    for (int f = 0; f < n_frames; f++) h[f] = scale_frame{d_src[f], d_dst[f]};
+    rc = timed_launches(ctx, h, n_frames, H2Y_SCALE_FRAMES_PER_LAUNCH, "k_scale", [&](const scale_frame *frames, int, int nf) {
+        return h2y_launch_scale(scale_grid(ctx, H.g, nf), ctx->stream, H.g, frames, nf);
+    });
+    if (rc) return rc;
+    ctx->last_variant = scale_variant(chroma_format_idc, a);
+    return H2Y_OK;
+}
+
+/* Arm the open ring: the tables and one k_scale table entry per slot go up once.  on_input: a scale-only ring (the slot's input
+ * into its output); otherwise the slot's device output into a scaled frame of its own, on the device and pinned. */
+static int scale_arm(h2y_ctx *ctx, int sw, int sh, int dw, int dh, int chroma, int bit_depth, int full_range, int gbr, int a, bool on_input)
+{
+    uint32_t src_off[3], dst_off[3];
+    cmp_contiguous(sw, sh, chroma, src_off);
+    cmp_contiguous(dw, dh, chroma, dst_off);
+    scale_host H;
+    int rc = scale_build(ctx, sw, sh, dw, dh, chroma, bit_depth, full_range, gbr, a, src_off, dst_off, H);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t bytes = h2y_scale_frame_bytes(dw, dh, chroma);
+    const int depth = (int)ctx->ss.size();
+    std::vector<scale_frame> tab(depth);
+    hipError_t e = hipMalloc((void **)&ctx->s_scale_tabs, H.blob.size());
+    if (e == hipSuccess) e = hipMalloc((void **)&ctx->s_scale_tab, tab.size() * sizeof(scale_frame));
+    for (int k = 0; k < depth && e == hipSuccess; k++) {
+        h2y_ctx::stream_slot &s = ctx->ss[k];
+        if (!on_input) {
+            e = hipMalloc((void **)&s.d_scaled, bytes);
+            if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_scaled, bytes, hipHostMallocDefault);
+        }
+        tab[k].src = reinterpret_cast<const uint16_t *>(on_input ? (char *)s.d_in : (char *)s.d_out);
+        tab[k].dst = on_input ? s.d_out : s.d_scaled;
+    }
+    if (e == hipSuccess) e = hipMemcpy(ctx->s_scale_tabs, H.blob.data(), H.blob.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(ctx->s_scale_tab, tab.data(), tab.size() * sizeof(scale_frame), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { /* the ring stays open, unarmed */
+        for (auto &s : ctx->ss) {
+            if (s.d_scaled) (void)hipFree(s.d_scaled);
+            if (s.h_scaled) (void)hipHostFree(s.h_scaled);
+            s.d_scaled = nullptr;
+            s.h_scaled = nullptr;
+        }
+        if (ctx->s_scale_tabs) (void)hipFree(ctx->s_scale_tabs);
+        if (ctx->s_scale_tab) (void)hipFree(ctx->s_scale_tab);
+        ctx->s_scale_tabs = nullptr;
+        ctx->s_scale_tab = nullptr;
+        return fail(ctx, H2Y_ENOMEM, "scaling buffers: %s", hipGetErrorString(e));
+    }
+    scale_bind(H, ctx->s_scale_tabs);
+    ctx->s_scale_geom = H.g;
+    ctx->s_scale_bytes = bytes;
+    ctx->s_scale = true;
+    return H2Y_OK;
+}
+
+int h2y_stream_scale(h2y_ctx *ctx, int dst_w, int dst_h, int a)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    if (ctx->s_kind != h2y_ctx::RING_FORWARD) return fail(ctx, H2Y_EINVAL, "only a forward ring is armed for scaling");
+    if (ctx->s_scale) return fail(ctx, H2Y_EINVAL, "the ring scales already");
+    if (ctx->s_cmp || ctx->s_hist || ctx->s_ssim)
+        return fail(ctx, H2Y_EUNSUPPORTED, "a ring armed for comparison, histograms or SSIM is not scaled: compare or count the written file instead");
+    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    const h2y_desc &d = ctx->s_desc;
+    int rc = scale_check(ctx, d.width, d.height, dst_w, dst_h, d.dst_chroma_format_idc, d.dst_bit_depth, d.dst_full_range, 0, a);
+    if (rc) return rc;
+    return scale_arm(ctx, d.width, d.height, dst_w, dst_h, d.dst_chroma_format_idc, d.dst_bit_depth, d.dst_full_range, 0, a, false);
+}
+
+/* A ring that only scales: the slot's input is the frame's three planes one after the other (one H2D copy), its output the
+ * scaled frame */
+int h2y_scale_stream_open(h2y_ctx *ctx, int src_w, int src_h, int chroma_format_idc, int bit_depth, int full_range, int gbr, int dst_w,
+                          int dst_h, int a, int depth)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is already open");
+    int rc = scale_check(ctx, src_w, src_h, dst_w, dst_h, chroma_format_idc, bit_depth, full_range, gbr, a);
+    if (rc) return rc;
+    if (depth < 2 || depth > 16) return fail(ctx, H2Y_EINVAL, "depth must be 2..16");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    uint32_t off[3];
+    cmp_contiguous(src_w, src_h, chroma_format_idc, off);
+    for (int c = 0; c < 3; c++) ctx->s_in_off[c] = off[c] * sizeof(uint16_t);
+    ctx->s_in_bytes = h2y_scale_frame_bytes(src_w, src_h, chroma_format_idc);
+    const size_t ob = h2y_scale_frame_bytes(dst_w, dst_h, chroma_format_idc);
+    rc = stream_alloc(ctx, depth, ctx->s_in_bytes, ctx->s_in_bytes, ob, ob);
+    if (rc) return rc;
+    ctx->s_kind = h2y_ctx::RING_SCALE;
+    rc = scale_arm(ctx, src_w, src_h, dst_w, dst_h, chroma_format_idc, bit_depth, full_range, gbr, a, true);
+    if (rc) {
+        stream_free(ctx);
+        return rc;
+    }
+    return H2Y_OK;
+}
+
+/* k_scale on the context's stream after the slot's conversion (a scale-only ring: after its upload) */
+static int scale_run(h2y_ctx *ctx, int slot)
+{
+    HIP_TRY(ctx, h2y_launch_scale(scale_grid(ctx, ctx->s_scale_geom, 1), ctx->stream, ctx->s_scale_geom, ctx->s_scale_tab + slot, 1));
+    return H2Y_OK;
+}
+
+/* one frame of a scale-only ring: H2D of the frame, k_scale, D2H of the scaled frame */
+static int scale_stream_submit(h2y_ctx *ctx, int slot)
+{
+    h2y_ctx::stream_slot &s = ctx->ss[slot];
+    HIP_TRY(ctx, hipMemcpyAsync(s.d_in, s.h_in, ctx->s_in_bytes, hipMemcpyHostToDevice, ctx->s_h2d));
+    HIP_TRY(ctx, hipEventRecord(s.ev_h2d, ctx->s_h2d));
+    HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s.ev_h2d, 0));
+    const int rc = scale_run(ctx, slot);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipEventRecord(s.ev_conv, ctx->stream));
+    HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_d2h, s.ev_conv, 0));
+    HIP_TRY(ctx, hipMemcpyAsync(s.h_out, s.d_out, ctx->s_scale_bytes, hipMemcpyDeviceToHost, ctx->s_d2h));
+    HIP_TRY(ctx, hipEventRecord(s.ev_done, ctx->s_d2h));
+    s.state = 2;
+    ctx->s_tail = (slot + 1) % (int)ctx->ss.size();
     return H2Y_OK;
 }
 
@@ -3901,6 +4238,7 @@ int h2y_stream_submit(h2y_ctx *ctx)
     if (ctx->s_kind == h2y_ctx::RING_COMPARE) return compare_stream_submit(ctx, slot);
     if (ctx->s_kind == h2y_ctx::RING_HISTOGRAM) return histogram_stream_submit(ctx, slot);
     if (ctx->s_kind == h2y_ctx::RING_INVERSE) return inverse_stream_submit(ctx, slot);
+    if (ctx->s_kind == h2y_ctx::RING_SCALE) return scale_stream_submit(ctx, slot);
     const decode_src &src = ctx->s_src;
     const size_t pb = h2y_plane_bytes(d), ob = h2y_frame_bytes(d);
     frame_io io;
@@ -3953,9 +4291,14 @@ int h2y_stream_submit(h2y_ctx *ctx)
         rc = hist_run(ctx, slot);
         if (rc) return rc;
     }
+    if (ctx->s_scale) { /* the slot's device output into its scaled frame */
+        rc = scale_run(ctx, slot);
+        if (rc) return rc;
+    }
     HIP_TRY(ctx, hipEventRecord(s.ev_conv, ctx->stream));
     HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_d2h, s.ev_conv, 0));
-    if (!ctx->s_cmp || ctx->s_cmp_keep) HIP_TRY(ctx, hipMemcpyAsync(s.h_out, s.d_out, ob, hipMemcpyDeviceToHost, ctx->s_d2h));
+    if (ctx->s_scale) HIP_TRY(ctx, hipMemcpyAsync(s.h_scaled, s.d_scaled, ctx->s_scale_bytes, hipMemcpyDeviceToHost, ctx->s_d2h));
+    else if (!ctx->s_cmp || ctx->s_cmp_keep) HIP_TRY(ctx, hipMemcpyAsync(s.h_out, s.d_out, ob, hipMemcpyDeviceToHost, ctx->s_d2h));
     if (ctx->s_cmp) {
         rc = cmp_download(ctx, s);
         if (!rc && ctx->s_ssim) rc = ssim_download(ctx, s);
@@ -3984,7 +4327,7 @@ int h2y_stream_output(h2y_ctx *ctx, const uint16_t **yuv)
     if (s.state != 2) return fail(ctx, H2Y_EINVAL, "no submitted frame is waiting");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipEventSynchronize(s.ev_done));
-    *yuv = (ctx->s_cmp && !ctx->s_cmp_keep) || ctx->s_kind == h2y_ctx::RING_HISTOGRAM ? nullptr : s.h_out;
+    *yuv = (ctx->s_cmp && !ctx->s_cmp_keep) || ctx->s_kind == h2y_ctx::RING_HISTOGRAM ? nullptr : s.h_scaled ? s.h_scaled : s.h_out;
     s.state = 3;
     ctx->s_lent = ctx->s_head;
     ctx->s_head = (ctx->s_head + 1) % (int)ctx->ss.size();

@@ -354,4 +354,31 @@ int h2y_light_grid(uint32_t npix, int n_frames); /* blocks per frame */
 /* k_light over n_frames frames into acc[frame] (zeroed by the caller) */
 hipError_t h2y_launch_light(int in_kind, int grid, hipStream_t st, const light_args &a, const light_frame *frames, int n_frames, light_acc *acc);
 
+/* k_scale (h2y_scale.hip): the Lanczos resampler of include/hdr2yuv_hip.h on frames of three u16 planes.  One axis' table on the
+ * device: first[d] and count[d] (int32), then d rows of H2Y_SCALE_MAX_TAPS int16 coefficients (zero past count). */
+enum { H2Y_SCALE_MAX_TAPS = 32, H2Y_SCALE_TILE_W = 64, H2Y_SCALE_TILE_H = 32, H2Y_SCALE_STAGE_ROWS = 16 };
+struct scale_axis {
+    const int32_t *first, *count;
+    const int16_t *coef;
+};
+struct scale_plane {
+    uint32_t sw, sh, dw, dh;       /* the plane's source and destination size */
+    uint32_t src_off, dst_off;     /* plane start in samples from the frame base, per side */
+    uint32_t tiles_x, tiles;       /* tiles of H2Y_SCALE_TILE_W x H2Y_SCALE_TILE_H outputs: per row, in all */
+    int32_t lo, hi;                /* the clamp */
+    scale_axis h, v;
+};
+struct scale_geom {
+    scale_plane p[3];
+    uint32_t h_rows;   /* rows of the LDS tile of horizontal sums: the most source rows a tile of the call needs */
+    uint32_t src_cols; /* samples per staged source row (a multiple of 8): the widest segment a tile needs, plus its alignment shift */
+};
+struct scale_frame { /* one frame; bases 16-byte aligned */
+    const uint16_t *src;
+    uint16_t *dst;
+};
+size_t h2y_scale_lds(const scale_geom &g); /* k_scale's dynamic LDS bytes */
+/* k_scale over (frame, plane, tile) units */
+hipError_t h2y_launch_scale(int grid, hipStream_t st, const scale_geom &g, const scale_frame *frames, int n_frames);
+
 #endif

@@ -649,8 +649,63 @@ int h2y_stream_light(h2y_ctx *ctx);
 /* The light of the frame that h2y_stream_output returned last. */
 int h2y_stream_light_result(h2y_ctx *ctx, h2y_light_stats *out);
 
+/* ---- scaling: an exact Lanczos resampler (--dst_pic_width / --dst_pic_height; the reference's cv.cpp is compiled out) ------------
+ * The reference plugs a per-plane Lanczos cv::resize in at hdr2yuv.cpp:892-896, in a file that does not compile; it defines no
+ * bytes.  This is the project's own definition, in integers, so that a restatement checks every output byte.
+ * Frame and target: three u16 planes in the comparison's geometry (4:2:0 Y, Cb, Cr; 4:4:4 Y, Cb, Cr or G, B, R).  Every plane
+ * is resampled on its own from (sw, sh) to (dw, dh); the chroma planes of a 4:2:0 frame from (sw/2, sh/2) to (dw/2, dh/2).  Sample
+ * centres are aligned (the 2x2-centre siting of the box filter is kept; chroma_sample_loc_type is not consulted).
+ * Tap table of one axis, s source samples -> d output samples, a in {2, 3, 4} lobes, all in binary64 on the host:
+ *   f = max(1, s/d), r = a f, and for output o the centre c = ((o + 0.5) x s) / d - 0.5 (the product, exact, then one division);
+ *   taps: the integers i with ceil(c - r) <= i <= floor(c + r) and |i - c| < r;
+ *   w_i = sinc(t) sinc(t/a) with t = (i - c)/f, sinc(x) = sin(pi x)/(pi x), sinc(0) = 1;  S = the w_i added left to right;
+ *   q_i = rint(w_i 16384 / S) (the product first, then the division);  16384 - sum q_i is added to the largest q_i (the first one
+ *   on ties);
+ *   edges replicate: the q_i of a tap outside [0, s-1] is added to the tap at the clamped index; `first` is the lowest clamped
+ *   index; the row is first, the tap count n and n int16 coefficients.
+ *   A row whose stored coefficients have sum |q| > 32767 makes the call fail with H2Y_EUNSUPPORTED (none occurs in the
+ *   tested ratios).
+ * Pixel:  H(y, x) = sum_i qh[x][i] src(y, first_h[x] + i), an exact int32 (sum |q| x 65535 < 2^31);
+ *         V(y, x) = sum_j qv[y][j] H(first_v[y] + j, x) in int64;
+ *         output = clamp((V + 2^27) >> 28, lo, hi), an arithmetic shift: one rounding per sample, none in between, so the answer
+ *         does not depend on tiling or on the order of the passes.
+ *   lo..hi is set_pic_clip()'s range of the plane at the frame's depth -- write_yuv()'s per-plane clamp, the rule
+ *   h2y_histogram_batch documents: [0, maxCV] in full range; in video range [minVR, maxVR] for plane 0 and every plane of a G, B, R
+ *   frame (gbr 1), [minVRC, maxVRC] for planes 1 and 2 of a YCbCr frame.
+ * Limits: each axis ratio s/d in [1/4, 4] (at most 32 taps); widths and heights 2..10000, even for 4:2:0, on both sides;
+ * chroma_format_idc 1 or 3 (2: H2Y_EUNSUPPORTED); bit_depth 8..16; a 2..4. */
+#define H2Y_SCALE_FRAMES_PER_LAUNCH 64
+#define H2Y_SCALE_TAPS 32 /* coefficients per row of h2y_scale_taps' table */
+
+/* The table of one axis.  Host only: no device, no context.  first[o], count[o] (dst entries each) and coef[o x 32 + i] (dst x 32;
+ * zero past count[o]); *max_taps (may be NULL) the largest count.  H2Y_EINVAL for sizes, a ratio or an `a` out of the limits. */
+int h2y_scale_taps(int src, int dst, int a, int32_t *first, int32_t *count, int16_t *coef /* dst x 32 */, int *max_taps);
+
+/* Bytes of one frame of three u16 planes of this geometry (0 for an unsupported one). */
+size_t h2y_scale_frame_bytes(int width, int height, int chroma_format_idc);
+
+/* k_scale on n_frames device frames in h2y_compare_batch's layout (three planes one after the other from a 16-byte aligned base):
+ * d_dst[f] receives d_src[f] resampled from src_w x src_h to dst_w x dst_h.  The tables are built on the host and uploaded once
+ * per call.  Launches of up to H2Y_SCALE_FRAMES_PER_LAUNCH frames (h2y_last_kernel_ms sums them, h2y_last_kernel_name
+ * "k_scale"); synchronous. */
+int h2y_scale_batch(h2y_ctx *ctx, int src_w, int src_h, int dst_w, int dst_h, int chroma_format_idc, int bit_depth, int full_range,
+                    int gbr, int a, int n_frames, const uint16_t *const *d_src, uint16_t *const *d_dst);
+
+/* Arm an open forward ring (h2y_stream_open, h2y_dpx_stream_open, h2y_tiff_stream_open, h2y_exr_stream_open) before its first
+ * input: after the conversion of a slot k_scale runs on the slot's device output, on the kernel stream, and the scaled frame
+ * (dst_w x dst_h, the descriptor's dst_chroma_format_idc, dst_bit_depth and dst_full_range, YCbCr limits) is what goes down and
+ * what h2y_stream_output returns.  h2y_stream_light beside it is unaffected.  H2Y_EINVAL on an inverse, compare-only,
+ * histogram-only or scale-only ring; H2Y_EUNSUPPORTED on a ring armed with h2y_stream_compare / _histogram / _ssim, as is arming any
+ * of those on a scale-armed ring. */
+int h2y_stream_scale(h2y_ctx *ctx, int dst_w, int dst_h, int a);
+
+/* A scale-only ring: no conversion.  h2y_stream_input lends the frame's three planes one after the other, h2y_stream_output
+ * returns the scaled frame. */
+int h2y_scale_stream_open(h2y_ctx *ctx, int src_w, int src_h, int chroma_format_idc, int bit_depth, int full_range, int gbr, int dst_w,
+                          int dst_h, int a, int depth /* 2..16 slots */);
+
 /* Timing of the last h2y_convert_batch*() (or h2y_inverse_*, h2y_dpx_decode_batch, h2y_tiff_decode_batch,
- * h2y_rgb_interleave_batch, h2y_exr_decode_batch, h2y_compare_batch, h2y_ssim_batch, h2y_light_batch) call measured with HIP events on
+ * h2y_rgb_interleave_batch, h2y_exr_decode_batch, h2y_compare_batch, h2y_ssim_batch, h2y_light_batch, h2y_scale_batch) call measured with HIP events on
  * the stream the kernels ran on: total ms over the main kernels and how many
  * launches that covered. */
 int h2y_last_kernel_ms(const h2y_ctx *ctx, float *ms, int *launches);
@@ -658,7 +713,7 @@ int h2y_last_kernel_ms(const h2y_ctx *ctx, float *ms, int *launches);
 /* Name of the kernel those launches ran ("k_fused", "k_fused_t1", "k_fused_lut16",
  * "k_fused_narrow"; of the inverse entries "k_inverse", "k_inverse420", "k_inverse_batch", "k_inverse420_batch"; of
  * h2y_dpx_decode_batch "k_dpx_decode"; of h2y_tiff_decode_batch "k_tiff_decode", of h2y_rgb_interleave_batch
- * "k_rgb_interleave"; of h2y_exr_decode_batch "k_exr_decode"; of h2y_compare_batch "k_compare"): the name to
+ * "k_rgb_interleave"; of h2y_exr_decode_batch "k_exr_decode"; of h2y_compare_batch "k_compare"; of h2y_scale_batch "k_scale"): the name to
  * look for in a rocprofv3 kernel trace. */
 const char *h2y_last_kernel_name(const h2y_ctx *ctx);
 /* The same with its template arguments and launch shape, e.g. "k_fused_t1<F32,420BOX,YCBCR,PQ_IDENT> groups=8 xcd=1";

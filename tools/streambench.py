@@ -70,6 +70,14 @@ Prints one line per figure, then one JSON line with all of them.
      F32 (99.5 MB), F16 and U16 (49.8 MB) LINEAR sources and an F32 BT.1886 source (the transfer's table tier);
   2. frames/s from host memory of every forward ring -- .f32, float DPX, 16-bit TIFF, half EXR (NONE) -- to PQ BT.2020nc 10-bit
      4:2:0, unarmed and armed with h2y_stream_light.
+Prints one line per figure, then one JSON line with all of them.
+
+`streambench.py scale`: the Lanczos resampler:
+  1. the kernel time of h2y_scale_batch (k_scale) over 64 distinct device frames per call (HIP events, median of five after a
+     warm-up call), the bytes per frame -- the source read once plus the output written -- over that time and their share of the
+     8 TB/s HBM peak, for 4K -> 1080p, 4K -> 720p and 1080p -> 4K (10-bit 4:2:0, 3 lobes) and 4K -> 1080p 16-bit 4:4:4 with 4 lobes;
+  2. frames/s from host memory of the forward ring (as `compare`) unarmed and armed with h2y_stream_scale to 1080p;
+  3. frames/s of the scale-only ring, 4K 10-bit 4:2:0 -> 1080p (the frame goes up, the scaled frame comes down).
 Prints one line per figure, then one JSON line with all of them."""
 import os
 import sys
@@ -904,8 +912,107 @@ def light_main():
     print(json.dumps({"streambench_light": res}), flush=True)
 
 
+def scale_main():
+    import json
+
+    import torch
+
+    nb, reps = 64, 5
+    nf = int(os.environ.get("N", "60"))
+    depth = 3
+    rng = np.random.default_rng(23)
+    ctx = h.Context(0)
+    res = {"frames_per_call": nb, "reps": reps, "ring_frames": nf, "ring_depth": depth, "hbm_peak_tbs": 8.0}
+
+    # 1. the kernel over 64 distinct frames on the device
+    cases = [("4k_to_1080p", 3840, 2160, 1920, 1080, h.CHROMA_420, 10, 3), ("4k_to_720p", 3840, 2160, 1280, 720, h.CHROMA_420, 10, 3),
+             ("1080p_to_4k", 1920, 1080, 3840, 2160, h.CHROMA_420, 10, 3), ("4k_to_1080p_444_16bit_a4", 3840, 2160, 1920, 1080, h.CHROMA_444, 16, 4)]
+    for name, sw, sh, dw, dh, chroma, bits, a in cases:
+        sb, db = h.scale_frame_bytes(sw, sh, chroma), h.scale_frame_bytes(dw, dh, chroma)
+        hi = 1 << min(bits, 15)  # int16 storage: codes below 2^15 (the kernel's time does not depend on the values)
+        src = [torch.randint(0, hi, (sb // 2,), dtype=torch.int16, device="cuda") for _ in range(nb)]
+        dst = [torch.empty(db // 2, dtype=torch.int16, device="cuda") for _ in range(nb)]
+        torch.cuda.synchronize()
+        ks = []
+        for rep in range(reps + 1):  # rep 0 warms up
+            ctx.scale_batch(sw, sh, dw, dh, chroma, bits, 0, 0, a, src, dst)
+            if rep:
+                ks.append(ctx.last_kernel_ms()[0] / nb)
+        k_ms = float(np.median(ks))
+        tbs = (sb + db) / (k_ms * 1e-3) / 1e12
+        res[name] = dict(kernel_us_per_frame=round(k_ms * 1e3, 2), min_us=round(min(ks) * 1e3, 2), max_us=round(max(ks) * 1e3, 2),
+                         bytes_per_frame=sb + db, kernel_tbs=round(tbs, 3), hbm_peak_fraction=round(tbs / 8.0, 4),
+                         variant=ctx.last_kernel_variant())
+        print(f"k_scale {name:26s} {nb} frames per call: {k_ms*1e3:7.2f} us/frame ({min(ks)*1e3:.2f}..{max(ks)*1e3:.2f})  "
+              f"{(sb+db)/1e6:6.1f} MB/frame  {tbs:5.3f} TB/s = {tbs/8.0*100:5.2f} % of 8 TB/s", flush=True)
+        del src, dst
+        torch.cuda.empty_cache()
+
+    def ring(open_fn, fill, arm=None):
+        open_fn()
+        if arm:
+            arm()
+        inflight = 0
+        t0 = time.perf_counter()
+        for _ in range(nf):
+            fill(ctx.stream_input())
+            ctx.stream_submit()
+            inflight += 1
+            if inflight == depth - 1:
+                ctx.stream_output()
+                inflight -= 1
+        while inflight:
+            ctx.stream_output()
+            inflight -= 1
+        dt = (time.perf_counter() - t0) / nf
+        ctx.stream_close()
+        return dt
+
+    # 2. the forward ring: 16-bit G,B,R -> BT.2020nc 10-bit 4:2:0 box, unarmed and armed to 1080p
+    w, hh = 3840, 2160
+    n, nc = w * hh, (w // 2) * (hh // 2)
+    planes = [rng.integers(0, 65536, n, dtype=np.uint16) for _ in range(3)]
+    d = h.make_desc(w, hh, sample=h.SAMPLE_U16, src_depth=16, dst_depth=10, src_transfer=1, dst_transfer=1, src_primaries=1,
+                    dst_primaries=1, dst_matrix=h.MATRIX_BT2020NC, resampler=0)
+    yuv = ctx.convert_frame(d, planes)
+
+    def fill_planes(slot):
+        for c in range(3):
+            slot[c][:] = planes[c]
+
+    def open_fwd():
+        ctx.stream_open(d, depth)
+
+    ring(open_fwd, fill_planes)  # warm-up
+    t_plain = ring(open_fwd, fill_planes)
+    t_armed = ring(open_fwd, fill_planes, lambda: ctx.stream_scale(1920, 1080, 3))
+    res["forward_ring"] = dict(unarmed_fps=round(1 / t_plain, 1), armed_fps=round(1 / t_armed, 1), unarmed_ms=round(t_plain * 1e3, 2),
+                               armed_ms=round(t_armed * 1e3, 2))
+    print(f"forward ring from host memory: unarmed {1/t_plain:6.1f} frames/s   armed with h2y_stream_scale to 1080p {1/t_armed:6.1f} frames/s",
+          flush=True)
+
+    # 3. the scale-only ring
+    yuv_planes = [yuv[:n], yuv[n:n + nc], yuv[n + nc:]]
+
+    def fill_yuv(slot):
+        for c in range(3):
+            slot[c][:] = yuv_planes[c]
+
+    def open_scale():
+        ctx.scale_stream_open(w, hh, h.CHROMA_420, 10, 0, 0, 1920, 1080, 3, depth)
+
+    ring(open_scale, fill_yuv)
+    t_only = ring(open_scale, fill_yuv)
+    res["scale_only_ring"] = dict(fps=round(1 / t_only, 1), ms=round(t_only * 1e3, 2))
+    print(f"scale-only ring from host memory: {1/t_only:6.1f} frames/s ({t_only*1e3:6.2f} ms/frame)", flush=True)
+    ctx.close()
+    print(json.dumps({"streambench_scale": res}), flush=True)
+
+
 if __name__ == "__main__":
-    if sys.argv[1:] == ["inverse"]:
+    if sys.argv[1:] == ["scale"]:
+        scale_main()
+    elif sys.argv[1:] == ["inverse"]:
         inverse_main()
     elif sys.argv[1:] == ["dpx"]:
         dpx_main()
