@@ -1,63 +1,22 @@
 /*
- * h2y_api.hip -- the C-ABI shim declared in include/hdr2yuv_hip.h.
+ * h2y_api.hip -- the C-ABI shim declared in include/hdr2yuv_hip.h: the context, the forward conversion and its batches, the
+ * single-step entries, the inverse and decode batch entries and the file parsers.  The streaming ring lies in h2y_ring.hip, the
+ * measurements (comparison, SSIM, content light, histograms, scaling) in h2y_measure.hip; h2y_shim.h is what the three share.
  *
  * Host side of the drop-in boundary: descriptor validation, the scalar setup
  * the reference does in init_pic()/set_pic_clip() (common.cpp:172-327), device
  * buffer ownership, and kernel launches.  No pixel is ever computed on the
  * host: without a HIP device h2y_ctx_create() fails and nothing else works.
  */
-#include <hip/hip_runtime.h>
-
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <algorithm>
-#include <cstring>
-#include <new>
-#include <string>
-#include <vector>
-
-#include "../../include/hdr2yuv_hip.h"
-#include "h2y_kernels.h"
-#include "h2y_math.h"
+#include "h2y_shim.h"
 #include "h2y_walk.h"
 
 #include <zlib.h>
-
-using namespace h2y;
 
 namespace {
 
 thread_local std::string g_err;
 
-struct clip_limits { /* clip_limits_t, hdr.h:345-356 */
-    uint32_t minCV, maxCV, minVR, maxVR, minVRC, maxVRC, Half;
-};
-
-/* set_pic_clip(), common.cpp:300-327 */
-clip_limits make_clip(int bit_depth, int full_range)
-{
-    clip_limits c;
-    c.minCV = 0;
-    c.maxCV = (1u << bit_depth) - 1;
-    c.Half = 1u << (bit_depth - 1);
-    if (!full_range) {
-        uint32_t D = 1u << (bit_depth - 8);
-        c.minVR = 16 * D;
-        c.maxVR = 219 * D + c.minVR; /* = 235*D, kept as the reference has it */
-        c.minVRC = c.minVR;
-        c.maxVRC = 224 * D + c.minVRC;
-    } else {
-        c.minVR = 0;
-        c.maxVR = c.maxCV;
-        c.minVRC = 0;
-        c.maxVRC = c.maxCV;
-    }
-    return c;
-}
-
-const int kMaxEvents = 64;
 const size_t kRangeWords = 1025; /* a table of slice ranges: up to 1024 blocks of a group + 1 */
 /* Share of a batch's pixels (counted in tiles of eight) the first tier passed on, above which the next batches go to the binary64
  * tier's kernels.  Both first-tier kernels now take that tier inside their loops, a wave at a time: with 0.1-0.2 % of the pixels
@@ -76,254 +35,6 @@ const int kFirSubBatch = 32; /* frames per fused launch on the FIR path: every l
 
 } // namespace
 
-/* The parameters of one .yuv -> G,B,R flow (h2y_inverse_batch, h2y_inverse_stream_open) */
-struct inv_params {
-    int width, height, chroma, in_depth, in_full_range, matrix, out_depth, algorithm;
-};
-
-/* What a decode batch entry or a forward ring decodes: nothing (a ring's caller fills the planes), or one format's payload
- * described by the info its parser returned.  Each format's launch and variant lie beside its parser. */
-struct decode_src {
-    enum kind_t { NONE, DPX, TIFF, EXR } kind = NONE;
-    bool has_info = true; /* false: the caller passed a null info, which check() refuses */
-    int clamp = 0;        /* TIFF: clamp_video_range */
-    h2y_dpx_info dpx{};
-    h2y_tiff_info tiff{};
-    h2y_exr_info exr{};
-    decode_src() = default;
-    explicit decode_src(const h2y_dpx_info *i) : kind(DPX), has_info(i != nullptr) { if (i) dpx = *i; }
-    decode_src(const h2y_tiff_info *i, int clamp_video_range) : kind(TIFF), has_info(i != nullptr), clamp(clamp_video_range) { if (i) tiff = *i; }
-    explicit decode_src(const h2y_exr_info *i) : kind(EXR), has_info(i != nullptr) { if (i) exr = *i; }
-    int check(h2y_ctx *ctx) const;                           /* the info is one the parser can return (TIFF: and clamp is 0 or 1) */
-    int planes_check(h2y_ctx *ctx, const h2y_desc *d) const; /* d's input planes are the decode's: its sample type, the picture's size */
-    uint64_t payload_bytes() const;
-    uintptr_t align() const; /* what the payload and the planes must be aligned to, in bytes */
-    hipError_t launch(const h2y_ctx *ctx, const payload_frame *frames, int n) const; /* the decode of n frames of a table */
-    const char *kernel() const;
-    std::string variant() const;
-};
-
-/* Everything one batch in flight owns: two of them let h2y_convert_batch_enqueue() queue batch k+1 behind batch k
- * before h2y_batch_finish() has looked at k (the 35 us between two launches -- the statistics kernel, one copy, the
- * host's turn-around -- disappear behind the running kernel). */
-struct batch_state {
-    /* per-batch device arrays */
-    frame_io *d_frames = nullptr, *h_frames = nullptr;
-    size_t frames_cap = 0;
-    std::vector<frame_io> dev_frames; /* what d_frames holds (size frames_cap once anything was copied; cleared when d_frames is reallocated) */
-    float *d_partial = nullptr;
-    size_t partial_cap = 0;
-    uint32_t *d_redo = nullptr; /* k_fused_t1: per-wave counts of redone tiles */
-    size_t redo_cap = 0;
-    uint32_t *d_low = nullptr;  /* k_fused_t1: per-frame flag "a sample <= -1 was seen" (zero between launches) */
-    size_t low_cap = 0;
-    bool approx_min = false;    /* the batch's statistics hold a subsampled minimum (exact only where they match) */
-    unsigned long long *d_clock = nullptr;
-    size_t clock_cap = 0;
-    int bal_slot = 0;                         /* the eight run times travel in the frame_stats entry after the batch's last */
-    bool bal_pending = false;                 /* h_fstats[bal_slot] will hold the times of a launch dealt with bal_work */
-    double bal_work[8] = {1, 1, 1, 1, 1, 1, 1, 1}; /* relative work a block of XCD x had in that launch */
-    /* fused_args.slice_ranges ([blocks of a group + 1]): two tables in pinned host memory that the kernels read in place (a
-     * block reads two words of it, once) -- no copy command between two launches.  Two, because the launches of one batch may
-     * need different tables (the last one, when it holds fewer frames) while the earlier ones have not run yet. */
-    uint32_t *h_ranges = nullptr, *hd_ranges = nullptr; /* host and device address of the same 2 x kRangeWords words */
-    uint32_t *d_tail = nullptr; /* the dynamic last frame's counters: [16 groups][H2Y_TAIL_WORDS]: counters and exhausted bits, zero between launches (k_stats_final) */
-    float *h_btime = nullptr, *hd_btime = nullptr; /* every block's run time of a timed launch (pinned, written by k_stats_final) */
-    int bal_grid = 0, bal_groups = 0;              /* the launch those times (and bal_bwork) belong to; 0: none */
-    std::vector<double> bal_bwork;                 /* relative work each block of the grid had in that launch */
-    std::vector<uint32_t> range_slot[2];      /* what the two tables hold */
-    bool slot_busy[2] = {false, false};       /* a launch of the batch being queued reads it */
-    /* k_fir_fused: the rows of every unit (frame, segment, strip), cut by XCD speed */
-    uint32_t *d_unit_rows = nullptr, *h_unit_rows = nullptr;
-    size_t unit_rows_cap = 0;                 /* in units */
-    std::vector<uint32_t> dev_unit_rows;      /* what d_unit_rows holds */
-    bool ffb_pending = false;                 /* h_fstats[bal_slot] will hold the XCD run times of a k_fir_fused launch ... */
-    double ffb_work[8] = {0, 0, 0, 0, 0, 0, 0, 0}; /* ... in which a block of XCD x had this much work (steps, mean) */
-    frame_stats *d_fstats = nullptr, *h_fstats = nullptr;
-    frame_stats *m_fstats = nullptr; /* h_fstats as the device sees it (pinned host memory): k_stats_final of a batch writes there, no copy command */
-    frame_stats *fs_out = nullptr;   /* where run_frames() has the statistics written: d_fstats, or m_fstats for an enqueued batch */
-    assumed_stats *d_assumed = nullptr, *h_assumed = nullptr; /* [2]: [0] batch, [1] redo */
-    assumed_stats dev_assumed;       /* what d_assumed[0] holds when dev_assumed_ok (one small copy command less per batch) */
-    bool dev_assumed_ok = false;
-    /* the batch itself, between enqueue and finish */
-    h2y_desc p_desc;
-    int p_n = 0;
-    bool p_check = false;
-    bool was_t1 = false;
-    std::vector<frame_io> p_frames;
-    hipEvent_t ev_done = nullptr; /* after the batch's last operation on the stream (the copy of its statistics) */
-    /* timing of the main kernels */
-    hipEvent_t ev[kMaxEvents][2];
-    int n_ev = 0;
-};
-
-struct h2y_ctx {
-    int device = 0;
-    batch_state bs[2];
-    batch_state *b = &bs[0]; /* the batch the shim is working on (enqueue: the newest; finish: the oldest) */
-    int q_head = 0, q_count = 0; /* batches in flight: bs[q_head] is the oldest */
-    int n_cu = 0;
-    hipStream_t own_stream = nullptr, stream = nullptr;
-    /* FIR pass runs on its own stream so that it overlaps the next sub-batch's fused kernel */
-    hipStream_t fir_stream = nullptr;
-    hipEvent_t ev_fused[2] = {nullptr, nullptr}, ev_fir[2] = {nullptr, nullptr};
-    bool fir_used[2] = {false, false};
-    void *d_table = nullptr;
-    void *d_table1 = nullptr; /* binary32 first-tier records */
-    void *d_table_ext = nullptr; /* pq_build_table_ext(): the binary64 table below 2^-24, read from global memory by pq_slow() */
-    void *d_tfn[H2Y_TFN_COUNT] = {}; /* the other transfer functions' tables (tfn_build_table), built when first needed */
-    void *d_tfn_ext[H2Y_TFN_COUNT] = {}; /* and their full-range tables in global memory (tfn_build_ext; PQ10000_r's is d_table_ext) */
-    float *d_lut16 = nullptr; /* PQ10000_r of every half in [0,2), built on the device at creation */
-    /* The first tier is slow on pictures with many exactly-zero samples (black bars: every such tile is done twice).
-     * The kernel counts the tiles it had to redo; when their share in a batch exceeds kT1DenseShare the next
-     * kT1SkipBatches batches go to k_fused2 (the binary64 tier answers zero by itself), then the first tier is
-     * tried again. */
-    /* Balancing across XCDs (frame_walk in h2y_kernels.hip): the loop-form kernels leave the mean run time of the blocks
-     * of each XCD; the shares of the next launch follow the speeds seen (balance_update()). */
-    bool bal_have = false;
-    double bal_speed[8] = {1, 1, 1, 1, 1, 1, 1, 1};
-    std::vector<double> bal_bspeed; /* per block of the grid (round 3): what is left between blocks once their XCDs are level */
-    int bal_bgrid = 0, bal_bgroups = 0; /* the grid shape bal_bspeed is for */
-    bool ffb_have = false;                    /* k_fir_fused has its own speeds: it is vector-issue bound, the XCDs differ more on it */
-    double ffb_speed[8] = {1, 1, 1, 1, 1, 1, 1, 1};
-    int t1_skip = 0, t1_skip_len = 0;
-    bool cur_skip_t1 = false;
-    /* h2y_ctx_set_option(): tuning / test knobs, per context (nothing is read from the environment) */
-    bool opt_t1 = true;        /* "t1": binary32 first tier on */
-    bool opt_t1_steer = true;  /* ... and left for the binary64 tier's kernels while the pictures keep it busy passing pixels on */
-    int opt_groups = 0;        /* "groups": at most this many frame groups (power of two; 1 = off); 0 = by the frame's size (groups_cap()) */
-    bool opt_cols8 = true;     /* "cols8": 8-column tiles for half input where the planes allow */
-    int opt_bal_mode = 0;      /* "balance": 0 adaptive, 1 off, 2 fixed */
-    int opt_tail = 2;           /* "tail": 0 auto (groups of at least kTailMinFrames frames), 1 on (two frames suffice), 2 off (the default: measured
-                                   neutral on 64 x 4K -- the blocks' finish times close up from +-30 us to +-15 us of a 1.5 ms launch, and the
-                                   frame's own dealing costs what that saves) */
-    bool opt_bal_blocks = true; /* adaptive: by the speed of every block ("adaptive"), or of the XCDs only ("xcd") */
-    uint32_t opt_bal_mask = 0xFFu;
-    double opt_bal_rho = 1.0;
-    int opt_fir = 0;           /* "fir": 0 auto, 1 two-pass (4:4:4 scratch + k_fir420), 2 fused single pass where it applies */
-    int opt_fir_sync = -1;     /* "firsync": k_fir_fused's blocks meet at a barrier every so many steps (power of two; 0 = never);
-                                  -1 = by the pictures: every step, never while the first tier passes many pixels on */
-    double fir_flag_share = 0.0; /* share of the last k_fir_fused batch's pixels (in tiles of eight) the first tier could not settle */
-    uint16_t *d_tmp = nullptr;
-    size_t tmp_cap = 0;
-    uint16_t *d_lin = nullptr; /* k_yuvp2_420: lin(Y') of every u16 code (h2y_yuvp2_lin_table), built when first needed */
-    /* the frame table of whichever synchronous batch entry runs (h2y_inverse_batch, the decode and compare batches; none runs
-     * beside another batch or a stream): pinned on the host, and its device copy the kernels read (frame_table) */
-    void *d_tab = nullptr, *h_tab = nullptr;
-    size_t d_tab_cap = 0, h_tab_cap = 0; /* bytes */
-    /* k_compare's partials (h2y_compare_batch and an armed ring), and h2y_compare_batch's device stats */
-    cmp_partial *d_cmp_part = nullptr;
-    size_t cmp_part_cap = 0;
-    h2y_compare_stats *d_cmp_stats = nullptr;
-    size_t cmp_stats_cap = 0;
-    /* h2y_histogram_batch's device workspace: per launch the counts, the bins and the stats (hist_layout) */
-    char *d_hist = nullptr;
-    size_t hist_cap = 0;
-    /* h2y_ssim_batch's (and an armed ring's) k_ssim partials, and the batch's stats */
-    int64_t *d_ssim_part = nullptr;
-    size_t ssim_part_cap = 0;
-    h2y_ssim_stats *d_ssim_stats = nullptr;
-    size_t ssim_stats_cap = 0;
-    /* h2y_light_batch's floor / ceiling per frame and k_light's accumulators */
-    assumed_stats *d_light_as = nullptr;
-    size_t light_as_cap = 0;
-    light_acc *d_light_acc = nullptr;
-    size_t light_acc_cap = 0;
-    /* h2y_scale_batch's tap tables on the device */
-    char *d_scale_tabs = nullptr;
-    size_t scale_tabs_cap = 0;
-
-    /* staging for the host-buffer entry */
-    void *d_in = nullptr;
-    size_t in_cap = 0;
-    uint16_t *d_out = nullptr;
-    size_t out_cap = 0;
-    /* floor/ceiling of the last frame seen: the assumption for the next batch */
-    bool have_hint = false;
-    int hint_kind = -1;
-    int32_t hint_floor[3] = {0, 0, 0}, hint_ceil[3] = {0, 0, 0};
-    /* streaming pipeline (h2y_stream_*): a ring of pinned host slots with device twins */
-    struct stream_slot {
-        char *h_in = nullptr;      /* pinned: three planes, at s_in_off[0..2] */
-        uint16_t *h_out = nullptr; /* pinned: one .yuv frame (an inverse stream: G | B | R) */
-        char *d_in = nullptr;
-        uint16_t *d_out = nullptr;
-        hipEvent_t ev_h2d = nullptr, ev_conv = nullptr, ev_done = nullptr;
-        int state = 0; /* 0 free, 1 handed out for filling, 2 submitted, 3 output lent to the caller */
-        /* an armed ring (h2y_stream_compare): the reference frame (pinned, and its device twin followed by the frame's stats) */
-        char *h_ref = nullptr, *d_ref = nullptr;
-        h2y_compare_stats *h_stats = nullptr;
-        bool ref_lent = false;
-        /* an armed ring (h2y_stream_histogram): the frame's counts, bins and stats on the device (hist_layout), and pinned */
-        char *d_hist = nullptr;
-        h2y_histogram_stats *h_hist_stats = nullptr;
-        uint32_t *h_hist_bins = nullptr;
-        /* a ring armed by h2y_stream_ssim: the frame's SSIM on the device and pinned */
-        h2y_ssim_stats *d_ssim = nullptr, *h_ssim = nullptr;
-        /* a ring armed by h2y_stream_light: the frame's k_light accumulator on the device and pinned */
-        light_acc *d_light = nullptr, *h_light = nullptr;
-        /* a forward ring armed by h2y_stream_scale: the scaled frame on the device and pinned */
-        uint16_t *d_scaled = nullptr, *h_scaled = nullptr;
-    };
-    std::vector<stream_slot> ss;
-    hipStream_t s_h2d = nullptr, s_d2h = nullptr;
-    h2y_desc s_desc;
-    size_t s_plane_al = 0;
-    int s_head = 0, s_tail = 0, s_lent = -1;
-    bool streaming = false;
-    /* what the ring does with a frame: the forward conversion (open_forward_ring), the .yuv -> G,B,R flow (open_inverse_ring),
-     * a comparison alone (h2y_compare_stream_open) or a histogram alone (h2y_histogram_stream_open) */
-    enum ring_kind { RING_FORWARD, RING_INVERSE, RING_COMPARE, RING_HISTOGRAM, RING_SCALE } s_kind = RING_FORWARD;
-    /* a forward ring's decode: with one, the pinned slot holds the payload, its device twin the three planes (at s_in_off[0..2])
-     * and then the payload at s_pay_off */
-    decode_src s_src;
-    /* an inverse ring: the flow's parameters, where the slot's input planes lie, the bytes of one H2D copy, and the distance
-     * between the G, B, R planes in the slot's device output (one plane's bytes, or 256-byte aligned when that would leave a plane
-     * misaligned for the kernel); with s_interleave (h2y_tiff_inverse_stream_open) the device output holds, at s_pay_off after
-     * the planes, write_tiff's interleaved R,G,B samples, and only they go down */
-    inv_params s_inv{};
-    bool s_interleave = false;
-    size_t s_pay_off = 0;
-    size_t s_in_off[3] = {0, 0, 0}, s_in_bytes = 0, s_out_stride = 0;
-    /* one entry per slot, uploaded when the ring is opened or armed: the decode's or the interleave's (payload_frame, rgb_frame),
-     * and k_compare's of an armed ring; stream_free releases them */
-    void *s_tab = nullptr;
-    cmp_frame *s_cmp_tab = nullptr;
-    /* an armed ring (h2y_stream_compare) or a compare-only ring (h2y_compare_stream_open): k_compare's geometry (A the slot's
-     * device output, or its input on a compare-only ring; B its reference), the reference's bytes, whether the frame goes down */
-    bool s_started = false; /* an input was handed out: too late to arm */
-    bool s_cmp = false, s_cmp_keep = true;
-    cmp_geom s_cmp_geom{};
-    /* a ring armed by h2y_stream_histogram (or a histogram-only ring): k_histogram's geometry and each slot's frame */
-    bool s_hist = false;
-    hist_geom s_hist_geom{};
-    hist_frame *s_hist_tab = nullptr;
-    /* a compare-armed ring armed by h2y_stream_ssim too: k_ssim's geometry (its frames are k_compare's, s_cmp_tab) */
-    bool s_ssim = false;
-    ssim_geom s_ssim_geom{};
-    /* a forward ring armed by h2y_stream_light: k_light's arguments and its table entry per slot (the slot's planes, d_assumed) */
-    bool s_light = false;
-    light_args s_light_args{};
-    light_frame *s_light_tab = nullptr;
-    /* a forward ring armed by h2y_stream_scale (source: the slot's device output, target: its d_scaled) or a scale-only ring
-     * (h2y_scale_stream_open; the slot's input and output): k_scale's geometry, its tables on the device, each slot's table
-     * entry and the scaled frame's bytes */
-    bool s_scale = false;
-    scale_geom s_scale_geom{};
-    char *s_scale_tabs = nullptr;
-    scale_frame *s_scale_tab = nullptr;
-    size_t s_scale_bytes = 0;
-    size_t s_ref_bytes = 0, s_ref_stats_off = 0; /* the pinned reference's bytes; where the stats lie in its device twin */
-    int slot_base = 0; /* run_frames(): first entry of d_frames/h_frames to use (one per stream slot) */
-    float last_ms = 0.f;
-    const char *last_name = "";
-    std::string last_variant; /* last_name with its template arguments and launch shape, e.g. "k_fused_t1<F32,420BOX,YCBCR,PQ_IDENT> groups=8 xcd=1" */
-    int last_launches = 0;
-    std::string err;
-};
-
-namespace {
-
 int fail(h2y_ctx *ctx, int code, const char *fmt, ...)
 {
     char buf[512];
@@ -336,25 +47,7 @@ int fail(h2y_ctx *ctx, int code, const char *fmt, ...)
     return code;
 }
 
-#define HIP_TRY(ctx, call)                                                                                  \
-    do {                                                                                                    \
-        hipError_t e_ = (call);                                                                             \
-        if (e_ != hipSuccess) return fail(ctx, H2Y_EHIP, "%s: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
-template <typename T> int ensure(h2y_ctx *ctx, T *&p, size_t &cap, size_t need_bytes)
-{
-    if (cap >= need_bytes) return 0;
-    if (p) HIP_TRY(ctx, hipFree(p));
-    p = nullptr;
-    cap = 0;
-    void *q = nullptr;
-    hipError_t e = hipMalloc(&q, need_bytes);
-    if (e != hipSuccess) return fail(ctx, H2Y_ENOMEM, "hipMalloc(%zu): %s", need_bytes, hipGetErrorString(e));
-    p = static_cast<T *>(q);
-    cap = need_bytes;
-    return 0;
-}
+namespace {
 
 /* transfer_characteristics code -> what matrix_convert() does with it (convert.cpp:1024-1109);
  * -1: the reference only prints a warning for every pixel */
@@ -369,15 +62,13 @@ int tf_class(int t)
     }
 }
 
-int in_kind_of(const h2y_desc *d)
-{
-    return d->in_sample_type == H2Y_SAMPLE_F32 ? H2Y_IN_F32 : d->in_sample_type == H2Y_SAMPLE_F16 ? H2Y_IN_F16 : H2Y_IN_U16;
-}
 size_t sample_bytes(const h2y_desc *d) { return d->in_sample_type == H2Y_SAMPLE_F32 ? 4 : 2; }
 
 /* hdr2yuv.cpp:803-808: the matrix_convert() target takes the input's depth
  * when both pictures are U16, else the output's */
 int tmp_depth_of(const h2y_desc *d) { return d->in_sample_type == H2Y_SAMPLE_U16 ? d->src_bit_depth : d->dst_bit_depth; }
+
+} // namespace
 
 /* Scalar setup for the kernels: everything matrix_convert()/convert()/
  * write_yuv() derive from the picture attributes before their pixel loops. */
@@ -442,6 +133,8 @@ void derive_params(const h2y_desc *d, pix_params *pp, bool stage_matrix_only)
     }
     pix_limits_finish(pp);
 }
+
+namespace {
 
 struct geom {
     bool narrow;
@@ -600,6 +293,8 @@ void balance_update(h2y_ctx *ctx)
     }
 }
 
+} // namespace
+
 /* the table of transfer function fn on the device (built on the host the first time it is asked for) */
 int ensure_tfn(h2y_ctx *ctx, int fn)
 {
@@ -623,6 +318,8 @@ int ensure_tfn(h2y_ctx *ctx, int fn)
     }
     return 0;
 }
+
+namespace {
 
 /* k_yuvp2_420's table, once per context */
 int ensure_lin(h2y_ctx *ctx)
@@ -657,6 +354,8 @@ void ffb_update(h2y_ctx *ctx)
     }
     ctx->ffb_have = true;
 }
+
+} // namespace
 
 /* launch fused (+FIR) over frames [0,n) whose frame_io entries are in h_frames */
 int run_frames(h2y_ctx *ctx, const h2y_desc *d, const frame_io *frames, int n, const assumed_stats *d_assumed,
@@ -1241,10 +940,6 @@ int run_stats(h2y_ctx *ctx, const h2y_desc *d, const void *const in[3], int slot
     return 0;
 }
 
-} // namespace
-
-extern "C" {
-
 int h2y_abi_version(void)
 {
 #ifdef H2Y_EXPERIMENT
@@ -1758,7 +1453,7 @@ static void inverse_setup(inverse_args &a, int width, int height, int in_bit_dep
 }
 
 /* ... and those of the 4:2:0 flow (yuv2tiff.cpp:92-93,142-154: minCV 0, maxCV 2^depth - 1 for the upsampling) */
-static void inverse420_setup(inv420_args &a, int width, int height, int in_bit_depth, int in_full_range, int in_matrix_coeffs,
+void inverse420_setup(inv420_args &a, int width, int height, int in_bit_depth, int in_full_range, int in_matrix_coeffs,
                              int out_bit_depth, int algorithm)
 {
     a.up.src0 = a.up.src1 = nullptr;
@@ -1911,7 +1606,7 @@ int h2y_inverse_frame(h2y_ctx *ctx, int width, int height, int in_chroma_format_
 }
 
 /* What h2y_inverse_batch and h2y_inverse_stream_open accept: the checks of h2y_inverse_420 (4:2:0) or h2y_matrix_inverse (4:4:4) */
-static int inverse_check(h2y_ctx *ctx, const inv_params &p)
+int inverse_check(h2y_ctx *ctx, const inv_params &p)
 {
     if (p.chroma != H2Y_CHROMA_444 && p.chroma != H2Y_CHROMA_420)
         return fail(ctx, H2Y_EUNSUPPORTED, "inverse flow: input chroma_format_idc must be 3 (4:4:4) or 1 (4:2:0)");
@@ -1922,64 +1617,6 @@ static int inverse_check(h2y_ctx *ctx, const inv_params &p)
         return fail(ctx, H2Y_EINVAL, "bad picture size");
     if (p.in_depth < 8 || p.in_depth > 16 || p.out_depth < 8 || p.out_depth > 16) return fail(ctx, H2Y_EINVAL, "bit depths must be 8..16");
     if (p.matrix == H2Y_MATRIX_GBR) return fail(ctx, H2Y_EUNSUPPORTED, "matrix_coeffs 0 (GBR) has no inverse in the reference (it exits)");
-    return H2Y_OK;
-}
-
-/* a grid of one block per unit of 256 threads, eight blocks of 256 per CU at most */
-static int unit_grid(const h2y_ctx *ctx, uint64_t units)
-{
-    const uint64_t max_grid = (uint64_t)ctx->n_cu * 8u;
-    return (int)(units < max_grid ? (units ? units : 1) : max_grid);
-}
-
-extern "C++" {
-
-/* A synchronous batch entry's frame table of n entries of T: the context's pinned host table h, and its device copy, grown as
- * needed.  One pair serves every entry: none runs beside another batch or a stream. */
-template <typename T> static int frame_table(h2y_ctx *ctx, int n, T *&h)
-{
-    const size_t tb = (size_t)n * sizeof(T);
-    int rc = ensure(ctx, ctx->d_tab, ctx->d_tab_cap, tb);
-    if (rc) return rc;
-    if (ctx->h_tab_cap < tb) {
-        if (ctx->h_tab) HIP_TRY(ctx, hipHostFree(ctx->h_tab));
-        ctx->h_tab = nullptr;
-        ctx->h_tab_cap = 0;
-        hipError_t e = hipHostMalloc(&ctx->h_tab, tb, hipHostMallocDefault);
-        if (e != hipSuccess) return fail(ctx, H2Y_ENOMEM, "hipHostMalloc(%zu): %s", tb, hipGetErrorString(e));
-        ctx->h_tab_cap = tb;
-    }
-    h = static_cast<T *>(ctx->h_tab);
-    return H2Y_OK;
-}
-
-/* The table h of n_frames entries (frame_table's) goes up once, then launch(frames, f0, nf) enqueues one launch on the device
- * entries [f0, f0 + nf), in launches of up to per_launch frames, each timed with an event pair (launches past the last pair are
- * timed by it); then a synchronisation, and last_ms, last_launches and last_name are the batch's */
-template <typename T, typename F>
-static int timed_launches(h2y_ctx *ctx, const T *h, int n_frames, int per_launch, const char *name, F launch)
-{
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_tab, h, (size_t)n_frames * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-    const T *frames = static_cast<const T *>(ctx->d_tab);
-    int launches = 0;
-    for (int f0 = 0; f0 < n_frames; f0 += per_launch, launches++) {
-        const int nf = n_frames - f0 < per_launch ? n_frames - f0 : per_launch;
-        const int e = launches < kMaxEvents ? launches : kMaxEvents - 1;
-        if (launches < kMaxEvents) HIP_TRY(ctx, hipEventRecord(ctx->b->ev[e][0], ctx->stream));
-        HIP_TRY(ctx, launch(frames + f0, f0, nf));
-        HIP_TRY(ctx, hipEventRecord(ctx->b->ev[e][1], ctx->stream));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->b->n_ev = launches < kMaxEvents ? launches : kMaxEvents;
-    float ms = 0.f;
-    for (int i = 0; i < ctx->b->n_ev; i++) {
-        float t = 0.f;
-        HIP_TRY(ctx, hipEventElapsedTime(&t, ctx->b->ev[i][0], ctx->b->ev[i][1]));
-        ms += t;
-    }
-    ctx->last_ms = ms;
-    ctx->last_launches = launches;
-    ctx->last_name = name;
     return H2Y_OK;
 }
 
@@ -2017,8 +1654,6 @@ static int decode_batch(h2y_ctx *ctx, const decode_src &src, int per_launch, int
     ctx->last_variant = src.variant();
     return H2Y_OK;
 }
-
-} // extern "C++"
 
 int h2y_inverse_batch(h2y_ctx *ctx, int width, int height, int in_chroma_format_idc, int in_bit_depth, int in_full_range,
                       int in_matrix_coeffs, int out_bit_depth, int algorithm, int n_frames, const uint16_t *const *d_in,
@@ -2137,204 +1772,6 @@ static std::string dpx_variant(const h2y_dpx_info &di)
 int h2y_dpx_decode_batch(h2y_ctx *ctx, const h2y_dpx_info *info, int n_frames, const void *const *d_payload, float *const *d_planes)
 {
     return decode_batch(ctx, decode_src(info), H2Y_DPX_FRAMES_PER_LAUNCH, n_frames, d_payload, d_planes);
-}
-
-/* ---- streaming pipeline ------------------------------------------------------
- * H2D of frame k+1, conversion of frame k and D2H of frame k-1 overlap: three streams, a ring of
- * pinned host slots the caller fills and drains in place.  Every frame is converted in the
- * reference's order (pic_stats pre-pass on the device, then the pixel kernel with its result in
- * device memory): no speculation, nothing to redo, no host round trip between the stages. */
-static void stream_free(h2y_ctx *ctx)
-{
-    for (auto &s : ctx->ss) {
-        if (s.h_in) (void)hipHostFree(s.h_in);
-        if (s.h_out) (void)hipHostFree(s.h_out);
-        if (s.d_in) (void)hipFree(s.d_in);
-        if (s.d_out) (void)hipFree(s.d_out);
-        if (s.ev_h2d) (void)hipEventDestroy(s.ev_h2d);
-        if (s.ev_conv) (void)hipEventDestroy(s.ev_conv);
-        if (s.ev_done) (void)hipEventDestroy(s.ev_done);
-        if (s.h_ref) (void)hipHostFree(s.h_ref);
-        if (s.d_ref) (void)hipFree(s.d_ref);
-        if (s.h_stats) (void)hipHostFree(s.h_stats);
-        if (s.d_hist) (void)hipFree(s.d_hist);
-        if (s.h_hist_stats) (void)hipHostFree(s.h_hist_stats);
-        if (s.h_hist_bins) (void)hipHostFree(s.h_hist_bins);
-        if (s.d_ssim) (void)hipFree(s.d_ssim);
-        if (s.h_ssim) (void)hipHostFree(s.h_ssim);
-        if (s.d_light) (void)hipFree(s.d_light);
-        if (s.h_light) (void)hipHostFree(s.h_light);
-        if (s.d_scaled) (void)hipFree(s.d_scaled);
-        if (s.h_scaled) (void)hipHostFree(s.h_scaled);
-    }
-    ctx->ss.clear();
-    if (ctx->s_h2d) (void)hipStreamDestroy(ctx->s_h2d);
-    if (ctx->s_d2h) (void)hipStreamDestroy(ctx->s_d2h);
-    ctx->s_h2d = ctx->s_d2h = nullptr;
-    if (ctx->s_tab) (void)hipFree(ctx->s_tab);
-    if (ctx->s_cmp_tab) (void)hipFree(ctx->s_cmp_tab);
-    ctx->s_tab = nullptr;
-    ctx->s_cmp_tab = nullptr;
-    if (ctx->s_hist_tab) (void)hipFree(ctx->s_hist_tab);
-    ctx->s_hist_tab = nullptr;
-    ctx->s_hist = false;
-    ctx->s_ssim = false;
-    if (ctx->s_light_tab) (void)hipFree(ctx->s_light_tab);
-    ctx->s_light_tab = nullptr;
-    ctx->s_light = false;
-    if (ctx->s_scale_tabs) (void)hipFree(ctx->s_scale_tabs);
-    if (ctx->s_scale_tab) (void)hipFree(ctx->s_scale_tab);
-    ctx->s_scale_tabs = nullptr;
-    ctx->s_scale_tab = nullptr;
-    ctx->s_scale = false;
-    ctx->streaming = false;
-    ctx->s_kind = h2y_ctx::RING_FORWARD;
-    ctx->s_src = decode_src();
-    ctx->s_interleave = false;
-    ctx->s_started = ctx->s_cmp = false;
-    ctx->s_cmp_keep = true;
-    ctx->s_head = ctx->s_tail = 0;
-    ctx->s_lent = -1;
-}
-
-/* the ring's streams and `depth` slots: pinned input / output and their device twins */
-static int stream_alloc(h2y_ctx *ctx, int depth, size_t h_in_bytes, size_t d_in_bytes, size_t h_out_bytes, size_t d_out_bytes)
-{
-    ctx->ss.assign(depth, h2y_ctx::stream_slot());
-    ctx->streaming = true;
-    hipError_t e = hipStreamCreateWithFlags(&ctx->s_h2d, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->s_d2h, hipStreamNonBlocking);
-    for (auto &s : ctx->ss) {
-        if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_in, h_in_bytes, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_out, h_out_bytes, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipMalloc((void **)&s.d_in, d_in_bytes);
-        if (e == hipSuccess) e = hipMalloc((void **)&s.d_out, d_out_bytes);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&s.ev_h2d, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&s.ev_conv, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&s.ev_done, hipEventDisableTiming);
-    }
-    if (e != hipSuccess) {
-        stream_free(ctx);
-        return fail(ctx, H2Y_ENOMEM, "stream buffers: %s", hipGetErrorString(e));
-    }
-    return H2Y_OK;
-}
-
-extern "C++" {
-
-/* the open ring's s_tab: the decode's or the interleave's entry of every slot, uploaded once (the ring closes if it fails) */
-template <typename T> static int slot_table(h2y_ctx *ctx, const std::vector<T> &tab, const char *what)
-{
-    const size_t tb = tab.size() * sizeof(T);
-    hipError_t e = hipMalloc(&ctx->s_tab, tb);
-    if (e != hipSuccess) {
-        stream_free(ctx);
-        return fail(ctx, H2Y_ENOMEM, "hipMalloc(%zu): %s", tb, hipGetErrorString(e));
-    }
-    e = hipMemcpy(ctx->s_tab, tab.data(), tb, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        stream_free(ctx);
-        return fail(ctx, H2Y_EHIP, "hipMemcpy of the %s slot table: %s", what, hipGetErrorString(e));
-    }
-    return H2Y_OK;
-}
-
-} // extern "C++"
-
-/* The forward ring (h2y_stream_open and the decoding openers).  Without a decode (src null) a slot holds the three planes, each
- * 256-byte aligned, on the host and on the device.  With one the pinned slot holds the payload, its device twin the three planes
- * the decode writes and then the payload; each slot's decode table entry is uploaded here once. */
-static int open_forward_ring(h2y_ctx *ctx, const h2y_desc *d, const decode_src *src, int depth)
-{
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is already open");
-    const decode_src &dec = src ? *src : decode_src();
-    int rc = dec.check(ctx);
-    if (rc) return rc;
-    const char *why;
-    rc = h2y_desc_check(d, &why);
-    if (rc) return fail(ctx, rc, "descriptor: %s", why);
-    rc = dec.planes_check(ctx, d);
-    if (rc) return rc;
-    if (depth < 2 || depth > 16) return fail(ctx, H2Y_EINVAL, "depth must be 2..16");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    rc = reserve_batch(ctx, 64);
-    if (rc) return rc;
-    const size_t pb = h2y_plane_bytes(d), ob = h2y_frame_bytes(d);
-    ctx->s_plane_al = (pb + 255) & ~(size_t)255;
-    ctx->s_desc = *d;
-    for (int c = 0; c < 3; c++) ctx->s_in_off[c] = c * ctx->s_plane_al;
-    ctx->s_pay_off = 3 * ctx->s_plane_al;
-    const bool decode = dec.kind != decode_src::NONE;
-    const size_t h_in = decode ? dec.payload_bytes() : 3 * ctx->s_plane_al;
-    rc = stream_alloc(ctx, depth, h_in, decode ? ctx->s_pay_off + h_in : h_in, ob, ob);
-    if (rc) return rc;
-    if (decode) {
-        std::vector<payload_frame> tab(depth);
-        for (int k = 0; k < depth; k++) {
-            tab[k].payload = ctx->ss[k].d_in + ctx->s_pay_off;
-            for (int c = 0; c < 3; c++) tab[k].plane[c] = ctx->ss[k].d_in + ctx->s_in_off[c];
-        }
-        rc = slot_table(ctx, tab, dec.kind == decode_src::DPX ? "DPX" : dec.kind == decode_src::TIFF ? "TIFF" : "EXR");
-        if (rc) return rc;
-    }
-    ctx->s_kind = h2y_ctx::RING_FORWARD;
-    ctx->s_src = dec;
-    return H2Y_OK;
-}
-
-/* The same ring for the .yuv -> G,B,R flow: a slot's input is Y, Cb/Dz, Cr/Dx one after the other (each 256-byte aligned; one
- * H2D copy), its output G | B | R, width x height each, contiguous on the host (one D2H copy where the device planes are too).
- * With interleave (write_tiff's), the slot's device output holds after the planes, 256-byte aligned, the interleaved samples,
- * and only those go down; each slot's k_rgb_interleave table entry is uploaded here once. */
-static int open_inverse_ring(h2y_ctx *ctx, const inv_params &p, bool interleave, int depth)
-{
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is already open");
-    int rc = inverse_check(ctx, p);
-    if (rc) return rc;
-    if (depth < 2 || depth > 16) return fail(ctx, H2Y_EINVAL, "depth must be 2..16");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t pb = (size_t)p.width * p.height * sizeof(uint16_t), pb_al = (pb + 255) & ~(size_t)255;
-    const size_t cb = p.chroma == H2Y_CHROMA_420 ? (size_t)(p.width >> 1) * (p.height >> 1) * sizeof(uint16_t) : pb;
-    const size_t cb_al = (cb + 255) & ~(size_t)255;
-    ctx->s_in_off[0] = 0;
-    ctx->s_in_off[1] = pb_al;
-    ctx->s_in_off[2] = pb_al + cb_al;
-    ctx->s_in_bytes = pb_al + cb_al + cb;
-    ctx->s_out_stride = (pb & 15) ? pb_al : pb; /* 4:2:0 planes are always a multiple of 16 bytes */
-    ctx->s_pay_off = (2 * ctx->s_out_stride + pb + 255) & ~(size_t)255;
-    ctx->s_inv = p;
-    rc = stream_alloc(ctx, depth, ctx->s_in_bytes, ctx->s_in_bytes, 3 * pb, interleave ? ctx->s_pay_off + 3 * pb : 2 * ctx->s_out_stride + pb);
-    if (rc) return rc;
-    if (interleave) {
-        std::vector<rgb_frame> tab(depth);
-        for (int k = 0; k < depth; k++) {
-            char *o = reinterpret_cast<char *>(ctx->ss[k].d_out);
-            for (int c = 0; c < 3; c++) tab[k].plane[c] = reinterpret_cast<const uint16_t *>(o + c * ctx->s_out_stride);
-            tab[k].rgb = reinterpret_cast<uint16_t *>(o + ctx->s_pay_off);
-        }
-        rc = slot_table(ctx, tab, "TIFF inverse");
-        if (rc) return rc;
-    }
-    ctx->s_kind = h2y_ctx::RING_INVERSE;
-    ctx->s_interleave = interleave;
-    return H2Y_OK;
-}
-
-int h2y_stream_open(h2y_ctx *ctx, const h2y_desc *d, int depth) { return open_forward_ring(ctx, d, nullptr, depth); }
-
-int h2y_inverse_stream_open(h2y_ctx *ctx, int width, int height, int in_chroma_format_idc, int in_bit_depth, int in_full_range,
-                            int in_matrix_coeffs, int out_bit_depth, int algorithm, int depth)
-{
-    const inv_params p{width, height, in_chroma_format_idc, in_bit_depth, in_full_range, in_matrix_coeffs, out_bit_depth, algorithm};
-    return open_inverse_ring(ctx, p, false, depth);
-}
-
-int h2y_dpx_stream_open(h2y_ctx *ctx, const h2y_desc *d, const h2y_dpx_info *info, int depth)
-{
-    const decode_src src(info);
-    return open_forward_ring(ctx, d, &src, depth);
 }
 
 /* ---- 16-bit RGB TIFF (read_tiff(), tiff.cpp:54-362; write_tiff(), tiff.cpp:559-652) ------------------------------------- */
@@ -2618,19 +2055,6 @@ int h2y_rgb_interleave_batch(h2y_ctx *ctx, int width, int height, int n_frames, 
     if (rc) return rc;
     ctx->last_variant = "k_rgb_interleave";
     return H2Y_OK;
-}
-
-int h2y_tiff_stream_open(h2y_ctx *ctx, const h2y_desc *d, const h2y_tiff_info *info, int clamp_video_range, int depth)
-{
-    const decode_src src(info, clamp_video_range);
-    return open_forward_ring(ctx, d, &src, depth);
-}
-
-int h2y_tiff_inverse_stream_open(h2y_ctx *ctx, int width, int height, int in_chroma_format_idc, int in_bit_depth, int in_full_range,
-                                 int in_matrix_coeffs, int out_bit_depth, int algorithm, int depth)
-{
-    const inv_params p{width, height, in_chroma_format_idc, in_bit_depth, in_full_range, in_matrix_coeffs, out_bit_depth, algorithm};
-    return open_inverse_ring(ctx, p, true, depth);
 }
 
 /* ---- scanline OpenEXR (read_exr(), exr.cpp:138-255) -------------------------------------------------------------------- */
@@ -2939,12 +2363,6 @@ int h2y_exr_decode_batch(h2y_ctx *ctx, const h2y_exr_info *info, int n_frames, c
     return decode_batch(ctx, decode_src(info), H2Y_EXR_FRAMES_PER_LAUNCH, n_frames, d_payload, d_planes);
 }
 
-int h2y_exr_stream_open(h2y_ctx *ctx, const h2y_desc *d, const h2y_exr_info *info, int depth)
-{
-    const decode_src src(info);
-    return open_forward_ring(ctx, d, &src, depth);
-}
-
 /* ---- decode_src: each format's facts, for the decode batches and the forward rings ------------------------------------- */
 
 int decode_src::check(h2y_ctx *ctx) const
@@ -3007,1345 +2425,6 @@ std::string decode_src::variant() const
 {
     return kind == DPX ? dpx_variant(dpx) : kind == TIFF ? tiff_variant(tiff, clamp != 0) : kind == EXR ? exr_variant(exr) : std::string();
 }
-
-/* ---- comparison with a reference (--ref_filename, hdr2yuv.cpp:91-100, :827-833) ---------------------------------------- */
-
-/* k_compare's geometry: planes of n[p] samples (4:2:0: Y, then two chroma planes of (width >> 1) x (height >> 1)) starting at
- * a_off / b_off samples from the two frames' bases */
-static cmp_geom cmp_geom_of(int width, int height, int chroma, int sigma, const uint32_t a_off[3], const uint32_t b_off[3])
-{
-    cmp_geom g{};
-    const bool sub = chroma == H2Y_CHROMA_420;
-    for (int p = 0; p < 3; p++) {
-        const uint32_t w = p && sub ? (uint32_t)(width >> 1) : (uint32_t)width, h = p && sub ? (uint32_t)(height >> 1) : (uint32_t)height;
-        g.n[p] = w * h;
-        g.width[p] = w;
-        g.a_off[p] = a_off[p];
-        g.b_off[p] = b_off[p];
-        const bool vec = (a_off[p] & 7u) == (b_off[p] & 7u);
-        g.shift[p] = vec ? a_off[p] & 7u : 0u;
-        g.vec |= vec ? 1u << p : 0u;
-        g.chunks[p] = h2y_compare_chunks(g.n[p], g.shift[p]);
-    }
-    g.sigma = (uint32_t)sigma;
-    return g;
-}
-
-/* the offsets of three planes one after the other */
-static void cmp_contiguous(int width, int height, int chroma, uint32_t off[3])
-{
-    const uint32_t n = (uint32_t)width * (uint32_t)height, nc = chroma == H2Y_CHROMA_420 ? (uint32_t)(width >> 1) * (uint32_t)(height >> 1) : n;
-    off[0] = 0, off[1] = n, off[2] = n + nc;
-}
-
-static int cmp_check(h2y_ctx *ctx, int width, int height, int chroma, int sigma)
-{
-    if (width < 1 || height < 1 || (uint64_t)width * (uint64_t)height >= (1ull << 28)) return fail(ctx, H2Y_EINVAL, "bad picture size");
-    if (chroma != H2Y_CHROMA_420 && chroma != H2Y_CHROMA_444) return fail(ctx, H2Y_EINVAL, "chroma_format_idc must be 1 or 3");
-    if (sigma < 0) return fail(ctx, H2Y_EINVAL, "sigma must be >= 0");
-    return H2Y_OK;
-}
-
-/* k_compare's partials for n_frames frames of g */
-static int cmp_partials(h2y_ctx *ctx, const cmp_geom &g, int n_frames)
-{
-    return ensure(ctx, ctx->d_cmp_part, ctx->cmp_part_cap,
-                  std::max<size_t>(1, (size_t)n_frames * (g.chunks[0] + g.chunks[1] + g.chunks[2])) * sizeof(cmp_partial));
-}
-
-static int cmp_grid(const h2y_ctx *ctx, const cmp_geom &g, int n_frames)
-{
-    return unit_grid(ctx, (uint64_t)n_frames * (g.chunks[0] + g.chunks[1] + g.chunks[2]));
-}
-
-int h2y_compare_batch(h2y_ctx *ctx, int width, int height, int chroma_format_idc, int sigma, int n_frames, const uint16_t *const *d_a,
-                      const uint16_t *const *d_b, h2y_compare_stats *out)
-{
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
-    int rc = cmp_check(ctx, width, height, chroma_format_idc, sigma);
-    if (rc) return rc;
-    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
-    if (!d_a || !d_b || !out) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
-    for (int f = 0; f < n_frames; f++) {
-        if (!d_a[f] || !d_b[f]) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is null", f);
-        if (((uintptr_t)d_a[f] | (uintptr_t)d_b[f]) & 15u) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is not 16-byte aligned", f);
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    uint32_t off[3];
-    cmp_contiguous(width, height, chroma_format_idc, off);
-    const cmp_geom g = cmp_geom_of(width, height, chroma_format_idc, sigma, off, off);
-    const int per_launch = std::min(n_frames, H2Y_COMPARE_FRAMES_PER_LAUNCH);
-    cmp_frame *h;
-    rc = frame_table(ctx, n_frames, h);
-    if (!rc) rc = cmp_partials(ctx, g, per_launch);
-    if (!rc) rc = ensure(ctx, ctx->d_cmp_stats, ctx->cmp_stats_cap, (size_t)n_frames * sizeof(h2y_compare_stats));
-    if (rc) return rc;
-    for (int f = 0; f < n_frames; f++) h[f] = cmp_frame{d_a[f], d_b[f]};
-    rc = timed_launches(ctx, h, n_frames, H2Y_COMPARE_FRAMES_PER_LAUNCH, "k_compare", [&](const cmp_frame *frames, int f0, int nf) {
-        return h2y_launch_compare(cmp_grid(ctx, g, nf), ctx->stream, g, frames, nf, ctx->d_cmp_part, ctx->d_cmp_stats + f0);
-    });
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpy(out, ctx->d_cmp_stats, (size_t)n_frames * sizeof(h2y_compare_stats), hipMemcpyDeviceToHost));
-    ctx->last_variant = std::string("k_compare<") + (chroma_format_idc == H2Y_CHROMA_420 ? "420" : "444") + ">";
-    return H2Y_OK;
-}
-
-/* Arm the open ring for frames of width x height and `chroma` whose A planes start at a_off samples from the slot's A base:
- * per slot a pinned reference (the planes one after the other), its device twin laid out as A (so both sides share each
- * plane's alignment and k_compare keeps its 16-byte loads) with the frame's stats behind it (256-byte aligned), pinned stats,
- * and the slot's k_compare table entry (A: the slot's device output -- its input on a compare-only ring --, B: the device
- * reference), uploaded here once */
-static int cmp_arm(h2y_ctx *ctx, int width, int height, int chroma, const uint32_t a_off[3], int sigma, int keep_output)
-{
-    int rc = cmp_check(ctx, width, height, chroma, sigma);
-    if (rc) return rc;
-    const cmp_geom g = cmp_geom_of(width, height, chroma, sigma, a_off, a_off);
-    const int depth = (int)ctx->ss.size();
-    const size_t ref_bytes = ((size_t)g.n[0] + g.n[1] + g.n[2]) * sizeof(uint16_t);
-    const size_t dev_al = (((size_t)a_off[2] + g.n[2]) * sizeof(uint16_t) + 255) & ~(size_t)255;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    rc = cmp_partials(ctx, g, 1);
-    if (rc) return rc;
-    std::vector<cmp_frame> tab(depth);
-    hipError_t e = hipMalloc((void **)&ctx->s_cmp_tab, tab.size() * sizeof(cmp_frame));
-    for (int k = 0; k < depth && e == hipSuccess; k++) {
-        h2y_ctx::stream_slot &s = ctx->ss[k];
-        e = hipHostMalloc((void **)&s.h_ref, ref_bytes, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_stats, sizeof(h2y_compare_stats), hipHostMallocDefault);
-        if (e == hipSuccess) e = hipMalloc((void **)&s.d_ref, dev_al + sizeof(h2y_compare_stats));
-        tab[k].a = reinterpret_cast<const uint16_t *>(ctx->s_kind == h2y_ctx::RING_COMPARE ? (char *)s.d_in : (char *)s.d_out);
-        tab[k].b = reinterpret_cast<const uint16_t *>(s.d_ref);
-    }
-    if (e == hipSuccess) e = hipMemcpy(ctx->s_cmp_tab, tab.data(), tab.size() * sizeof(cmp_frame), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { /* the ring stays open, unarmed */
-        for (auto &s : ctx->ss) {
-            if (s.h_ref) (void)hipHostFree(s.h_ref);
-            if (s.h_stats) (void)hipHostFree(s.h_stats);
-            if (s.d_ref) (void)hipFree(s.d_ref);
-            s.h_ref = s.d_ref = nullptr;
-            s.h_stats = nullptr;
-        }
-        if (ctx->s_cmp_tab) (void)hipFree(ctx->s_cmp_tab);
-        ctx->s_cmp_tab = nullptr;
-        return fail(ctx, H2Y_ENOMEM, "compare buffers: %s", hipGetErrorString(e));
-    }
-    ctx->s_cmp_geom = g;
-    ctx->s_ref_bytes = ref_bytes;
-    ctx->s_ref_stats_off = dev_al;
-    ctx->s_cmp = true;
-    ctx->s_cmp_keep = keep_output != 0;
-    return H2Y_OK;
-}
-
-int h2y_stream_compare(h2y_ctx *ctx, int sigma, int keep_output)
-{
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
-    if (ctx->s_cmp) return fail(ctx, H2Y_EINVAL, "the ring is armed already");
-    if (ctx->s_scale) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that scales is not compared: compare the written file instead");
-    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
-    if (keep_output != 0 && keep_output != 1) return fail(ctx, H2Y_EINVAL, "keep_output must be 0 or 1");
-    uint32_t a_off[3];
-    if (ctx->s_kind == h2y_ctx::RING_INVERSE) { /* the G, B, R planes the inverse kernel writes, s_out_stride bytes apart */
-        for (int c = 0; c < 3; c++) a_off[c] = (uint32_t)(c * ctx->s_out_stride / sizeof(uint16_t));
-        return cmp_arm(ctx, ctx->s_inv.width, ctx->s_inv.height, H2Y_CHROMA_444, a_off, sigma, keep_output);
-    }
-    const h2y_desc &d = ctx->s_desc; /* the .yuv frame of a forward ring */
-    cmp_contiguous(d.width, d.height, d.dst_chroma_format_idc, a_off);
-    return cmp_arm(ctx, d.width, d.height, d.dst_chroma_format_idc, a_off, sigma, keep_output);
-}
-
-int h2y_stream_reference(h2y_ctx *ctx, void **ref)
-{
-    if (!ctx || !ref) return fail(ctx, H2Y_EINVAL, "null argument");
-    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
-    if (!ctx->s_cmp) return fail(ctx, H2Y_EINVAL, "the ring is not armed: h2y_stream_compare first");
-    h2y_ctx::stream_slot &s = ctx->ss[ctx->s_tail];
-    if (s.state != 0 && s.state != 1) return fail(ctx, H2Y_EINVAL, "all %d slots are in flight: take an output first", (int)ctx->ss.size());
-    s.ref_lent = true;
-    *ref = s.h_ref;
-    return H2Y_OK;
-}
-
-int h2y_stream_compare_result(h2y_ctx *ctx, h2y_compare_stats *out)
-{
-    if (!ctx || !out) return fail(ctx, H2Y_EINVAL, "null argument");
-    if (!ctx->streaming || !ctx->s_cmp) return fail(ctx, H2Y_EINVAL, "no armed stream open");
-    if (ctx->s_lent < 0) return fail(ctx, H2Y_EINVAL, "no output taken yet: h2y_stream_output first");
-    *out = *ctx->ss[ctx->s_lent].h_stats;
-    return H2Y_OK;
-}
-
-/* A ring that only compares: the slot's input is A's three planes one after the other (one H2D copy), the device output unused */
-int h2y_compare_stream_open(h2y_ctx *ctx, int width, int height, int chroma_format_idc, int sigma, int depth)
-{
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is already open");
-    int rc = cmp_check(ctx, width, height, chroma_format_idc, sigma);
-    if (rc) return rc;
-    if (depth < 2 || depth > 16) return fail(ctx, H2Y_EINVAL, "depth must be 2..16");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    uint32_t off[3];
-    cmp_contiguous(width, height, chroma_format_idc, off);
-    for (int c = 0; c < 3; c++) ctx->s_in_off[c] = off[c] * sizeof(uint16_t);
-    ctx->s_in_bytes = ((size_t)off[2] + (off[2] - off[1])) * sizeof(uint16_t); /* the last plane is as long as the second */
-    rc = stream_alloc(ctx, depth, ctx->s_in_bytes, ctx->s_in_bytes, 16, 16);
-    if (rc) return rc;
-    ctx->s_kind = h2y_ctx::RING_COMPARE;
-    rc = cmp_arm(ctx, width, height, chroma_format_idc, off, sigma, 0);
-    if (rc) {
-        stream_free(ctx);
-        return rc;
-    }
-    return H2Y_OK;
-}
-
-/* an armed slot's reference goes up on the upload stream (before the slot's ev_h2d is recorded) */
-static int cmp_upload(h2y_ctx *ctx, h2y_ctx::stream_slot &s)
-{
-    if (!s.ref_lent) return fail(ctx, H2Y_EINVAL, "the ring is armed: h2y_stream_reference before each submit");
-    const cmp_geom &g = ctx->s_cmp_geom;
-    if (g.b_off[1] == g.n[0] && g.b_off[2] == g.n[0] + g.n[1]) /* the device twin is contiguous too: one copy */
-        HIP_TRY(ctx, hipMemcpyAsync(s.d_ref, s.h_ref, ctx->s_ref_bytes, hipMemcpyHostToDevice, ctx->s_h2d));
-    else /* padded apart as the inverse ring's output planes */
-        for (size_t c = 0, h_off = 0; c < 3; h_off += g.n[c] * sizeof(uint16_t), c++)
-            HIP_TRY(ctx, hipMemcpyAsync(s.d_ref + g.b_off[c] * sizeof(uint16_t), s.h_ref + h_off, g.n[c] * sizeof(uint16_t),
-                                        hipMemcpyHostToDevice, ctx->s_h2d));
-    s.ref_lent = false;
-    return H2Y_OK;
-}
-
-/* k_compare on the context's stream after the slot's conversion; the stats land behind the slot's device reference */
-static h2y_compare_stats *cmp_dev_stats(const h2y_ctx *ctx, const h2y_ctx::stream_slot &s)
-{
-    return reinterpret_cast<h2y_compare_stats *>(s.d_ref + ctx->s_ref_stats_off);
-}
-
-static int cmp_run(h2y_ctx *ctx, int slot)
-{
-    const cmp_geom &g = ctx->s_cmp_geom;
-    HIP_TRY(ctx, h2y_launch_compare(cmp_grid(ctx, g, 1), ctx->stream, g, ctx->s_cmp_tab + slot, 1, ctx->d_cmp_part, cmp_dev_stats(ctx, ctx->ss[slot])));
-    return H2Y_OK;
-}
-
-/* the stats go down on the download stream, after the frame (when it goes down at all) */
-static int cmp_download(h2y_ctx *ctx, h2y_ctx::stream_slot &s)
-{
-    HIP_TRY(ctx, hipMemcpyAsync(s.h_stats, cmp_dev_stats(ctx, s), sizeof(h2y_compare_stats), hipMemcpyDeviceToHost, ctx->s_d2h));
-    return H2Y_OK;
-}
-
-/* ---- SSIM beside the comparison (hdr2yuv.cpp:826) ------------------------------------------------------------------------ */
-
-/* k_ssim's geometry: the comparison's planes (4:2:0: Y, then two chroma planes of (width >> 1) x (height >> 1)) starting at a_off /
- * b_off samples from the two frames' bases, and the constants of bit_depth, computed once here in binary64, left to right */
-static ssim_geom ssim_geom_of(int width, int height, int chroma, int bit_depth, const uint32_t a_off[3], const uint32_t b_off[3])
-{
-    ssim_geom g{};
-    const bool sub = chroma == H2Y_CHROMA_420;
-    for (int p = 0; p < 3; p++) {
-        g.pw[p] = p && sub ? (uint32_t)(width >> 1) : (uint32_t)width;
-        g.ph[p] = p && sub ? (uint32_t)(height >> 1) : (uint32_t)height;
-        g.a_off[p] = a_off[p];
-        g.b_off[p] = b_off[p];
-        g.strips[p] = h2y_ssim_strips(g.pw[p]);
-        g.units[p] = g.strips[p] * h2y_ssim_segments(g.ph[p]);
-    }
-    g.wide = bit_depth > 12;
-    const double M = (double)((1u << bit_depth) - 1u);
-    g.c1 = ((0.01 * 0.01) * M) * M * 64.0;
-    g.c2 = (((0.03 * 0.03) * M) * M * 64.0) * 63.0;
-    return g;
-}
-
-static int ssim_check(h2y_ctx *ctx, int width, int height, int chroma, int bit_depth)
-{
-    if (width < 1 || height < 1 || (uint64_t)width * (uint64_t)height >= (1ull << 28)) return fail(ctx, H2Y_EINVAL, "bad picture size");
-    if (chroma == 2) return fail(ctx, H2Y_EUNSUPPORTED, "chroma_format_idc 2 (4:2:2) has no SSIM on this path");
-    if (chroma != H2Y_CHROMA_420 && chroma != H2Y_CHROMA_444) return fail(ctx, H2Y_EINVAL, "chroma_format_idc must be 1 or 3");
-    if (bit_depth < 8 || bit_depth > 16) return fail(ctx, H2Y_EINVAL, "bit_depth must be 8..16");
-    const int sub = chroma == H2Y_CHROMA_420;
-    if ((width >> sub) < 8 || (height >> sub) < 8)
-        return fail(ctx, H2Y_EINVAL, "SSIM needs every plane at least 8x8 (one window): %dx%d %s", width, height, sub ? "4:2:0" : "4:4:4");
-    return H2Y_OK;
-}
-
-/* k_ssim's partials for n_frames frames of g */
-static int ssim_partials(h2y_ctx *ctx, const ssim_geom &g, int n_frames)
-{
-    return ensure(ctx, ctx->d_ssim_part, ctx->ssim_part_cap, (size_t)n_frames * (g.units[0] + g.units[1] + g.units[2]) * sizeof(int64_t));
-}
-
-int h2y_ssim_batch(h2y_ctx *ctx, int width, int height, int chroma_format_idc, int bit_depth, int n_frames, const uint16_t *const *d_a,
-                   const uint16_t *const *d_b, h2y_ssim_stats *out)
-{
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
-    int rc = ssim_check(ctx, width, height, chroma_format_idc, bit_depth);
-    if (rc) return rc;
-    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
-    if (!d_a || !d_b || !out) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
-    for (int f = 0; f < n_frames; f++) {
-        if (!d_a[f] || !d_b[f]) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is null", f);
-        if (((uintptr_t)d_a[f] | (uintptr_t)d_b[f]) & 15u) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is not 16-byte aligned", f);
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    uint32_t off[3];
-    cmp_contiguous(width, height, chroma_format_idc, off);
-    const ssim_geom g = ssim_geom_of(width, height, chroma_format_idc, bit_depth, off, off);
-    const int per_launch = std::min(n_frames, H2Y_SSIM_FRAMES_PER_LAUNCH);
-    cmp_frame *h;
-    rc = frame_table(ctx, n_frames, h);
-    if (!rc) rc = ssim_partials(ctx, g, per_launch);
-    if (!rc) rc = ensure(ctx, ctx->d_ssim_stats, ctx->ssim_stats_cap, (size_t)n_frames * sizeof(h2y_ssim_stats));
-    if (rc) return rc;
-    for (int f = 0; f < n_frames; f++) h[f] = cmp_frame{d_a[f], d_b[f]};
-    rc = timed_launches(ctx, h, n_frames, H2Y_SSIM_FRAMES_PER_LAUNCH, "k_ssim", [&](const cmp_frame *frames, int f0, int nf) {
-        return h2y_launch_ssim(h2y_ssim_grid(ctx->n_cu, g, nf), ctx->stream, g, frames, nf, ctx->d_ssim_part, ctx->d_ssim_stats + f0);
-    });
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpy(out, ctx->d_ssim_stats, (size_t)n_frames * sizeof(h2y_ssim_stats), hipMemcpyDeviceToHost));
-    ctx->last_variant = std::string("k_ssim<") + (chroma_format_idc == H2Y_CHROMA_420 ? "420" : "444") + "," + (g.wide ? "U64" : "U32") + ">";
-    return H2Y_OK;
-}
-
-int h2y_stream_ssim(h2y_ctx *ctx, int bit_depth)
-{
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
-    if (ctx->s_scale) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that scales computes no SSIM: compare the written file instead");
-    if (!ctx->s_cmp) return fail(ctx, H2Y_EINVAL, "the ring is not armed for comparison: h2y_stream_compare first");
-    if (ctx->s_ssim) return fail(ctx, H2Y_EINVAL, "the ring computes SSIM already");
-    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
-    const cmp_geom &c = ctx->s_cmp_geom;
-    const int width = (int)c.width[0], height = (int)(c.n[0] / c.width[0]);
-    const int chroma = c.n[1] == c.n[0] ? H2Y_CHROMA_444 : H2Y_CHROMA_420;
-    if (bit_depth < 0) {
-        if (ctx->s_kind == h2y_ctx::RING_COMPARE)
-            return fail(ctx, H2Y_EINVAL, "a compare-only ring does not know its frames' bit depth: give it to h2y_stream_ssim");
-        bit_depth = ctx->s_kind == h2y_ctx::RING_INVERSE ? ctx->s_inv.out_depth : ctx->s_desc.dst_bit_depth;
-    }
-    int rc = ssim_check(ctx, width, height, chroma, bit_depth);
-    if (rc) return rc;
-    const ssim_geom g = ssim_geom_of(width, height, chroma, bit_depth, c.a_off, c.b_off);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    rc = ssim_partials(ctx, g, 1);
-    if (rc) return rc;
-    hipError_t e = hipSuccess;
-    for (auto &s : ctx->ss) {
-        if (e == hipSuccess) e = hipMalloc((void **)&s.d_ssim, sizeof(h2y_ssim_stats));
-        if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_ssim, sizeof(h2y_ssim_stats), hipHostMallocDefault);
-    }
-    if (e != hipSuccess) { /* the ring stays open, armed for comparison alone */
-        for (auto &s : ctx->ss) {
-            if (s.d_ssim) (void)hipFree(s.d_ssim);
-            if (s.h_ssim) (void)hipHostFree(s.h_ssim);
-            s.d_ssim = s.h_ssim = nullptr;
-        }
-        return fail(ctx, H2Y_ENOMEM, "SSIM buffers: %s", hipGetErrorString(e));
-    }
-    ctx->s_ssim_geom = g;
-    ctx->s_ssim = true;
-    return H2Y_OK;
-}
-
-int h2y_stream_ssim_result(h2y_ctx *ctx, h2y_ssim_stats *out)
-{
-    if (!ctx || !out) return fail(ctx, H2Y_EINVAL, "null argument");
-    if (!ctx->streaming || !ctx->s_ssim) return fail(ctx, H2Y_EINVAL, "no stream open that computes SSIM");
-    if (ctx->s_lent < 0) return fail(ctx, H2Y_EINVAL, "no output taken yet: h2y_stream_output first");
-    *out = *ctx->ss[ctx->s_lent].h_ssim;
-    return H2Y_OK;
-}
-
-/* k_ssim on the context's stream after k_compare, on the slot's pair of k_compare */
-static int ssim_run(h2y_ctx *ctx, int slot)
-{
-    const ssim_geom &g = ctx->s_ssim_geom;
-    HIP_TRY(ctx, h2y_launch_ssim(h2y_ssim_grid(ctx->n_cu, g, 1), ctx->stream, g, ctx->s_cmp_tab + slot, 1, ctx->d_ssim_part, ctx->ss[slot].d_ssim));
-    return H2Y_OK;
-}
-
-/* the SSIM goes down on the download stream, after the compare stats */
-static int ssim_download(h2y_ctx *ctx, h2y_ctx::stream_slot &s)
-{
-    HIP_TRY(ctx, hipMemcpyAsync(s.h_ssim, s.d_ssim, sizeof(h2y_ssim_stats), hipMemcpyDeviceToHost, ctx->s_d2h));
-    return H2Y_OK;
-}
-
-/* ---- content light level (MaxCLL / MaxFALL) of a forward conversion to PQ ------------------------------------------------------ */
-
-/* the descriptors whose light is measured: conversions to PQ from another transfer, of a G, B, R source */
-static int light_check(h2y_ctx *ctx, const h2y_desc *d)
-{
-    const char *why;
-    int rc = h2y_desc_check(d, &why);
-    if (rc) return fail(ctx, rc, "descriptor: %s", why);
-    if (d->dst_transfer != 16)
-        return fail(ctx, H2Y_EUNSUPPORTED, "content light is measured on conversions to PQ (dst_transfer 16), not dst_transfer %d", d->dst_transfer);
-    if (d->src_transfer == 16)
-        return fail(ctx, H2Y_EUNSUPPORTED, "a PQ source goes to PQ without linear light: there is no light to measure");
-    if (d->src_matrix != H2Y_MATRIX_GBR)
-        return fail(ctx, H2Y_EUNSUPPORTED, "content light needs a G,B,R source (src_matrix 0), not src_matrix %d", d->src_matrix);
-    return H2Y_OK;
-}
-
-/* k_light's arguments for d: the conversion's parameters and, for a source transfer other than LINEAR, its stage's tables */
-static int light_args_of(h2y_ctx *ctx, const h2y_desc *d, light_args &a)
-{
-    a = light_args{};
-    derive_params(d, &a.pp, false);
-    a.npix = (uint32_t)d->width * (uint32_t)d->height;
-    a.n4 = a.npix / 4u;
-    a.table = nullptr;
-    if (a.pp.src_tf != H2Y_TF_LINEAR) {
-        static const int kSrcFn[4] = {H2Y_TFN_NONE, H2Y_TFN_PQ_F, H2Y_TFN_RHO_H, H2Y_TFN_G24}; /* by H2Y_TF_* class, as run_frames() */
-        const int sf = kSrcFn[a.pp.src_tf];
-        const int rc = ensure_tfn(ctx, sf);
-        if (rc) return rc;
-        a.pp.src_fn = sf;
-        a.table = ctx->d_tfn[sf];
-        a.pp.tf_ext[0] = ctx->d_tfn_ext[sf];
-    }
-    return H2Y_OK;
-}
-
-static std::string light_variant(const h2y_desc *d, const light_args &a)
-{
-    static const char *const kIn[] = {"F32", "F16", "U16"}, *const kTf[] = {"LINEAR", "PQ", "RHO_GAMMA", "BT1886"};
-    return std::string("k_light<") + kIn[in_kind_of(d)] + "," + kTf[a.pp.src_tf] + ">";
-}
-
-/* the stats of one frame of npix pixels, width wide, from its accumulator */
-static void light_finish(const light_acc &acc, uint32_t width, uint32_t npix, h2y_light_stats *o)
-{
-    *o = h2y_light_stats{};
-    o->max_bits = (uint32_t)(acc.key >> 32);
-    const uint32_t i = ~(uint32_t)acc.key;
-    o->x = i % width;
-    o->y = i / width;
-    o->sum_q = acc.sum;
-    o->pixels = npix;
-    o->cll = 10000.0 * (double)bits2f(o->max_bits);
-    o->fall = ((10000.0 * (double)acc.sum) * 0x1p-32) / (double)npix;
-}
-
-int h2y_light_batch(h2y_ctx *ctx, const h2y_desc *d, int n_frames, const void *const *d_planes, h2y_light_stats *out)
-{
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
-    int rc = light_check(ctx, d);
-    if (rc) return rc;
-    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
-    if (!d_planes || !out) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
-    for (int f = 0; f < n_frames; f++)
-        for (int c = 0; c < 3; c++)
-            if (!d_planes[3 * f + c] || ((uintptr_t)d_planes[3 * f + c] & 15u))
-                return fail(ctx, H2Y_EINVAL, "input plane %d of frame %d is null or not 16-byte aligned", c, f);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    light_args a;
-    rc = light_args_of(ctx, d, a);
-    light_frame *h;
-    if (!rc) rc = frame_table(ctx, n_frames, h);
-    if (!rc) rc = ensure(ctx, ctx->d_light_as, ctx->light_as_cap, (size_t)n_frames * sizeof(assumed_stats));
-    if (!rc) rc = ensure(ctx, ctx->d_light_acc, ctx->light_acc_cap, (size_t)n_frames * sizeof(light_acc));
-    if (rc) return rc;
-    if (d->stats_override) { /* the same six integers for every frame */
-        std::vector<assumed_stats> as(n_frames);
-        for (auto &x : as)
-            for (int c = 0; c < 3; c++) x.floor_[c] = d->floor[c], x.ceil_[c] = d->ceiling[c];
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_light_as, as.data(), (size_t)n_frames * sizeof(assumed_stats), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    } else /* pic_stats of every frame, as h2y_convert_batch ends up taking it */
-        for (int f = 0; f < n_frames; f++) {
-            rc = run_stats(ctx, d, d_planes + 3 * f, (int)ctx->b->frames_cap, ctx->d_light_as + f);
-            if (rc) return rc;
-        }
-    ctx->b->dev_assumed_ok = false; /* run_stats used the batch state's scratch slot */
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_light_acc, 0, (size_t)n_frames * sizeof(light_acc), ctx->stream));
-    for (int f = 0; f < n_frames; f++)
-        h[f] = light_frame{{d_planes[3 * f], d_planes[3 * f + 1], d_planes[3 * f + 2]}, ctx->d_light_as + f};
-    const int in_kind = in_kind_of(d);
-    rc = timed_launches(ctx, h, n_frames, H2Y_LIGHT_FRAMES_PER_LAUNCH, "k_light", [&](const light_frame *frames, int f0, int nf) {
-        return h2y_launch_light(in_kind, h2y_light_grid(a.npix, nf), ctx->stream, a, frames, nf, ctx->d_light_acc + f0);
-    });
-    if (rc) return rc;
-    std::vector<light_acc> acc(n_frames);
-    HIP_TRY(ctx, hipMemcpy(acc.data(), ctx->d_light_acc, (size_t)n_frames * sizeof(light_acc), hipMemcpyDeviceToHost));
-    for (int f = 0; f < n_frames; f++) light_finish(acc[f], (uint32_t)d->width, a.npix, out + f);
-    ctx->last_variant = light_variant(d, a);
-    return H2Y_OK;
-}
-
-int h2y_stream_light(h2y_ctx *ctx)
-{
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
-    if (ctx->s_kind != h2y_ctx::RING_FORWARD) return fail(ctx, H2Y_EINVAL, "content light is measured on the forward rings only");
-    if (ctx->s_light) return fail(ctx, H2Y_EINVAL, "the ring measures content light already");
-    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
-    const h2y_desc *d = &ctx->s_desc;
-    int rc = light_check(ctx, d);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    light_args a;
-    rc = light_args_of(ctx, d, a);
-    if (rc) return rc;
-    const int depth = (int)ctx->ss.size();
-    std::vector<light_frame> tab(depth);
-    for (int k = 0; k < depth; k++)
-        for (int c = 0; c < 3; c++) tab[k].in[c] = ctx->ss[k].d_in + c * ctx->s_plane_al, tab[k].assumed = ctx->b->d_assumed;
-    hipError_t e = hipMalloc((void **)&ctx->s_light_tab, (size_t)depth * sizeof(light_frame));
-    if (e == hipSuccess) e = hipMemcpy(ctx->s_light_tab, tab.data(), (size_t)depth * sizeof(light_frame), hipMemcpyHostToDevice);
-    for (auto &s : ctx->ss) {
-        if (e == hipSuccess) e = hipMalloc((void **)&s.d_light, sizeof(light_acc));
-        if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_light, sizeof(light_acc), hipHostMallocDefault);
-    }
-    if (e != hipSuccess) { /* the ring stays open, unarmed */
-        for (auto &s : ctx->ss) {
-            if (s.d_light) (void)hipFree(s.d_light);
-            if (s.h_light) (void)hipHostFree(s.h_light);
-            s.d_light = s.h_light = nullptr;
-        }
-        if (ctx->s_light_tab) (void)hipFree(ctx->s_light_tab);
-        ctx->s_light_tab = nullptr;
-        return fail(ctx, H2Y_ENOMEM, "content light buffers: %s", hipGetErrorString(e));
-    }
-    ctx->s_light_args = a;
-    ctx->s_light = true;
-    return H2Y_OK;
-}
-
-int h2y_stream_light_result(h2y_ctx *ctx, h2y_light_stats *out)
-{
-    if (!ctx || !out) return fail(ctx, H2Y_EINVAL, "null argument");
-    if (!ctx->streaming || !ctx->s_light) return fail(ctx, H2Y_EINVAL, "no stream open that measures content light");
-    if (ctx->s_lent < 0) return fail(ctx, H2Y_EINVAL, "no output taken yet: h2y_stream_output first");
-    light_finish(*ctx->ss[ctx->s_lent].h_light, (uint32_t)ctx->s_desc.width, ctx->s_light_args.npix, out);
-    return H2Y_OK;
-}
-
-/* the zeroing and k_light of the slot's frame on the context's stream */
-static int light_run(h2y_ctx *ctx, int slot)
-{
-    const light_args &a = ctx->s_light_args;
-    HIP_TRY(ctx, hipMemsetAsync(ctx->ss[slot].d_light, 0, sizeof(light_acc), ctx->stream));
-    HIP_TRY(ctx, h2y_launch_light(in_kind_of(&ctx->s_desc), h2y_light_grid(a.npix, 1), ctx->stream, a, ctx->s_light_tab + slot, 1,
-                                  ctx->ss[slot].d_light));
-    return H2Y_OK;
-}
-
-/* ---- code-value histograms and the legal-range check (hdr2yuv.cpp:658, :797) ---------------------------------------------- */
-
-/* k_histogram's geometry: planes of the comparison's geometry starting at off samples from the frame's base, the legal range of
- * set_pic_clip() at bit_depth (planes 1 and 2 of a YCbCr frame: minVRC..maxVRC; plane 0 and every G, B, R plane: minVR..maxVR) */
-static hist_geom hist_geom_of(int width, int height, int chroma, int bit_depth, int full_range, int gbr, int bits, const uint32_t off[3])
-{
-    hist_geom g{};
-    const bool sub = chroma == H2Y_CHROMA_420;
-    const clip_limits c = make_clip(bit_depth, full_range);
-    for (int p = 0; p < 3; p++) {
-        const uint32_t w = p && sub ? (uint32_t)(width >> 1) : (uint32_t)width, h = p && sub ? (uint32_t)(height >> 1) : (uint32_t)height;
-        g.n[p] = w * h;
-        g.off[p] = off[p];
-        g.shift[p] = off[p] & 7u;
-        g.vec |= 1u << p; /* one side: the groups can always follow the plane's start */
-        g.units[p] = h2y_histogram_units(g.n[p], g.shift[p]);
-        const bool luma_like = p == 0 || gbr;
-        g.lo[p] = luma_like ? c.minVR : c.minVRC;
-        g.hi[p] = luma_like ? c.maxVR : c.maxVRC;
-    }
-    g.nbins = 1u << bits;
-    g.down = (uint32_t)(bit_depth - bits);
-    return g;
-}
-
-static int hist_check(h2y_ctx *ctx, int width, int height, int chroma, int bit_depth, int full_range, int gbr, int bits)
-{
-    if (width < 1 || height < 1 || (uint64_t)width * (uint64_t)height >= (1ull << 28)) return fail(ctx, H2Y_EINVAL, "bad picture size");
-    if (chroma == 2) return fail(ctx, H2Y_EUNSUPPORTED, "chroma_format_idc 2 (4:2:2) is not counted on this path");
-    if (chroma != H2Y_CHROMA_420 && chroma != H2Y_CHROMA_444) return fail(ctx, H2Y_EINVAL, "chroma_format_idc must be 1 or 3");
-    if (bit_depth < 8 || bit_depth > 16) return fail(ctx, H2Y_EINVAL, "bit_depth must be 8..16");
-    if (bits < 1 || bits > bit_depth) return fail(ctx, H2Y_EINVAL, "bits must be 1..bit_depth (%d)", bit_depth);
-    if ((full_range != 0 && full_range != 1) || (gbr != 0 && gbr != 1)) return fail(ctx, H2Y_EINVAL, "full_range and gbr must be 0 or 1");
-    return H2Y_OK;
-}
-
-/* A workspace of nf frames: the counts (zeroed), the bins (zeroed), then the stats k_histogram_finish writes */
-struct hist_layout {
-    size_t bins, stats, total;
-};
-static hist_layout hist_layout_of(uint32_t nbins, int nf)
-{
-    hist_layout L;
-    L.bins = ((size_t)nf * 3u * sizeof(hist_acc) + 255) & ~(size_t)255;
-    L.stats = (L.bins + (size_t)nf * 3u * nbins * sizeof(uint32_t) + 255) & ~(size_t)255;
-    L.total = L.stats + (size_t)nf * sizeof(h2y_histogram_stats);
-    return L;
-}
-
-/* the zeroing and both kernels of nf frames on the context's stream, into the workspace ws */
-static int hist_enqueue(h2y_ctx *ctx, const hist_geom &g, const hist_frame *frames, int nf, char *ws)
-{
-    const hist_layout L = hist_layout_of(g.nbins, nf);
-    HIP_TRY(ctx, hipMemsetAsync(ws, 0, L.stats, ctx->stream));
-    HIP_TRY(ctx, h2y_launch_histogram(h2y_histogram_grid(ctx->n_cu, g, nf), ctx->stream, g, frames, nf, reinterpret_cast<hist_acc *>(ws),
-                                      reinterpret_cast<uint32_t *>(ws + L.bins), reinterpret_cast<h2y_histogram_stats *>(ws + L.stats)));
-    return H2Y_OK;
-}
-
-int h2y_histogram_batch(h2y_ctx *ctx, int width, int height, int chroma_format_idc, int bit_depth, int full_range, int gbr, int bits,
-                        int n_frames, const uint16_t *const *d_frames, h2y_histogram_stats *out_stats, uint32_t *out_bins)
-{
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
-    int rc = hist_check(ctx, width, height, chroma_format_idc, bit_depth, full_range, gbr, bits);
-    if (rc) return rc;
-    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
-    if (!d_frames || !out_stats) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
-    for (int f = 0; f < n_frames; f++) {
-        if (!d_frames[f]) return fail(ctx, H2Y_EINVAL, "frame %d is null", f);
-        if ((uintptr_t)d_frames[f] & 15u) return fail(ctx, H2Y_EINVAL, "frame %d is not 16-byte aligned", f);
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    uint32_t off[3];
-    cmp_contiguous(width, height, chroma_format_idc, off);
-    const hist_geom g = hist_geom_of(width, height, chroma_format_idc, bit_depth, full_range, gbr, bits, off);
-    const int per_launch = std::min(n_frames, H2Y_HISTOGRAM_FRAMES_PER_LAUNCH);
-    const hist_layout L = hist_layout_of(g.nbins, per_launch);
-    hist_frame *h;
-    rc = frame_table(ctx, n_frames, h);
-    if (!rc) rc = ensure(ctx, ctx->d_hist, ctx->hist_cap, L.total);
-    if (rc) return rc;
-    for (int f = 0; f < n_frames; f++) h[f].base = d_frames[f];
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_tab, h, (size_t)n_frames * sizeof(hist_frame), hipMemcpyHostToDevice, ctx->stream));
-    const hist_frame *frames = static_cast<const hist_frame *>(ctx->d_tab);
-    /* one launch at a time: its stats and bins come down before the next one reuses the workspace */
-    float ms = 0.f;
-    int launches = 0;
-    hipEvent_t *ev = ctx->b->ev[0];
-    for (int f0 = 0; f0 < n_frames; f0 += per_launch, launches++) {
-        const int nf = std::min(per_launch, n_frames - f0);
-        const hist_layout Ln = hist_layout_of(g.nbins, nf);
-        HIP_TRY(ctx, hipEventRecord(ev[0], ctx->stream));
-        rc = hist_enqueue(ctx, g, frames + f0, nf, ctx->d_hist);
-        if (rc) return rc;
-        HIP_TRY(ctx, hipEventRecord(ev[1], ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(out_stats + f0, ctx->d_hist + Ln.stats, (size_t)nf * sizeof(h2y_histogram_stats), hipMemcpyDeviceToHost,
-                                    ctx->stream));
-        if (out_bins)
-            HIP_TRY(ctx, hipMemcpyAsync(out_bins + (size_t)f0 * 3u * g.nbins, ctx->d_hist + Ln.bins, (size_t)nf * 3u * g.nbins * sizeof(uint32_t),
-                                        hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        float t = 0.f;
-        HIP_TRY(ctx, hipEventElapsedTime(&t, ev[0], ev[1]));
-        ms += t;
-    }
-    ctx->b->n_ev = 1;
-    ctx->last_ms = ms;
-    ctx->last_launches = launches;
-    ctx->last_name = "k_histogram";
-    ctx->last_variant = std::string("k_histogram<") + (chroma_format_idc == H2Y_CHROMA_420 ? "420" : "444") + "," +
-                        (h2y_histogram_lds(g.nbins) < (size_t)g.nbins * sizeof(uint32_t) ? "U16X2" : "U32") + ",bins=" +
-                        std::to_string(g.nbins) + ">";
-    return H2Y_OK;
-}
-
-/* Arm the open ring for frames whose planes start at off samples from the slot's base (its device output; its input on a
- * compare-only or histogram-only ring): per slot a device workspace of one frame, pinned stats and bins, and the slot's
- * k_histogram table entry, uploaded here once */
-static int hist_arm(h2y_ctx *ctx, int width, int height, int chroma, int bit_depth, int full_range, int gbr, int bits, const uint32_t off[3])
-{
-    int rc = hist_check(ctx, width, height, chroma, bit_depth, full_range, gbr, bits);
-    if (rc) return rc;
-    const hist_geom g = hist_geom_of(width, height, chroma, bit_depth, full_range, gbr, bits, off);
-    const hist_layout L = hist_layout_of(g.nbins, 1);
-    const int depth = (int)ctx->ss.size();
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    std::vector<hist_frame> tab(depth);
-    const bool on_input = ctx->s_kind == h2y_ctx::RING_COMPARE || ctx->s_kind == h2y_ctx::RING_HISTOGRAM;
-    hipError_t e = hipMalloc((void **)&ctx->s_hist_tab, tab.size() * sizeof(hist_frame));
-    for (int k = 0; k < depth && e == hipSuccess; k++) {
-        h2y_ctx::stream_slot &s = ctx->ss[k];
-        e = hipMalloc((void **)&s.d_hist, L.total);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_hist_stats, sizeof(h2y_histogram_stats), hipHostMallocDefault);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_hist_bins, (size_t)3u * g.nbins * sizeof(uint32_t), hipHostMallocDefault);
-        tab[k].base = reinterpret_cast<const uint16_t *>(on_input ? (char *)s.d_in : (char *)s.d_out);
-    }
-    if (e == hipSuccess) e = hipMemcpy(ctx->s_hist_tab, tab.data(), tab.size() * sizeof(hist_frame), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { /* the ring stays open, unarmed */
-        for (auto &s : ctx->ss) {
-            if (s.d_hist) (void)hipFree(s.d_hist);
-            if (s.h_hist_stats) (void)hipHostFree(s.h_hist_stats);
-            if (s.h_hist_bins) (void)hipHostFree(s.h_hist_bins);
-            s.d_hist = nullptr;
-            s.h_hist_stats = nullptr;
-            s.h_hist_bins = nullptr;
-        }
-        if (ctx->s_hist_tab) (void)hipFree(ctx->s_hist_tab);
-        ctx->s_hist_tab = nullptr;
-        return fail(ctx, H2Y_ENOMEM, "histogram buffers: %s", hipGetErrorString(e));
-    }
-    ctx->s_hist_geom = g;
-    ctx->s_hist = true;
-    return H2Y_OK;
-}
-
-int h2y_stream_histogram_ex(h2y_ctx *ctx, int bits, int bit_depth, int full_range, int gbr)
-{
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
-    if (ctx->s_hist) return fail(ctx, H2Y_EINVAL, "the ring counts histograms already");
-    if (ctx->s_scale) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that scales counts no histograms: count the written file instead");
-    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
-    uint32_t off[3];
-    int width, height, chroma, depth, full, rgb;
-    if (ctx->s_kind == h2y_ctx::RING_COMPARE) { /* frame A, laid out as k_compare reads it */
-        if (bit_depth < 0 || full_range < 0 || gbr < 0)
-            return fail(ctx, H2Y_EINVAL, "a compare-only ring does not know its frames' bit depth and range: h2y_stream_histogram_ex");
-        const cmp_geom &c = ctx->s_cmp_geom;
-        width = (int)c.width[0], height = (int)(c.n[0] / c.width[0]);
-        chroma = c.n[1] == c.n[0] ? H2Y_CHROMA_444 : H2Y_CHROMA_420;
-        for (int p = 0; p < 3; p++) off[p] = c.a_off[p];
-        depth = full = rgb = 0;
-    } else if (ctx->s_kind == h2y_ctx::RING_INVERSE) { /* the G, B, R planes the inverse kernel writes, s_out_stride bytes apart */
-        const inv_params &p = ctx->s_inv;
-        width = p.width, height = p.height, chroma = H2Y_CHROMA_444;
-        for (int c = 0; c < 3; c++) off[c] = (uint32_t)(c * ctx->s_out_stride / sizeof(uint16_t));
-        depth = p.out_depth, full = p.in_full_range, rgb = 1;
-    } else if (ctx->s_kind == h2y_ctx::RING_FORWARD) { /* the .yuv frame, clamped per plane as write_yuv() does */
-        const h2y_desc &d = ctx->s_desc;
-        width = d.width, height = d.height, chroma = d.dst_chroma_format_idc;
-        cmp_contiguous(width, height, chroma, off);
-        depth = d.dst_bit_depth, full = d.dst_full_range, rgb = 0;
-    } else
-        return fail(ctx, H2Y_EINVAL, "the ring counts histograms already");
-    if (bit_depth >= 0) depth = bit_depth;
-    if (full_range >= 0) full = full_range;
-    if (gbr >= 0) rgb = gbr;
-    if (depth < 8 || depth > 16) return fail(ctx, H2Y_EINVAL, "bit_depth must be 8..16");
-    return hist_arm(ctx, width, height, chroma, depth, full, rgb, bits ? bits : depth, off);
-}
-
-int h2y_stream_histogram(h2y_ctx *ctx, int bits) { return h2y_stream_histogram_ex(ctx, bits, -1, -1, -1); }
-
-int h2y_stream_histogram_result(h2y_ctx *ctx, h2y_histogram_stats *out_stats, uint32_t *out_bins)
-{
-    if (!ctx || !out_stats) return fail(ctx, H2Y_EINVAL, "null argument");
-    if (!ctx->streaming || !ctx->s_hist) return fail(ctx, H2Y_EINVAL, "no stream open that counts histograms");
-    if (ctx->s_lent < 0) return fail(ctx, H2Y_EINVAL, "no output taken yet: h2y_stream_output first");
-    const h2y_ctx::stream_slot &s = ctx->ss[ctx->s_lent];
-    *out_stats = *s.h_hist_stats;
-    if (out_bins) memcpy(out_bins, s.h_hist_bins, (size_t)3u * ctx->s_hist_geom.nbins * sizeof(uint32_t));
-    return H2Y_OK;
-}
-
-/* A ring that only counts: the slot's input is the frame's three planes one after the other (one H2D copy), the device output unused */
-int h2y_histogram_stream_open(h2y_ctx *ctx, int width, int height, int chroma_format_idc, int bit_depth, int full_range, int gbr, int bits,
-                              int depth)
-{
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is already open");
-    int rc = hist_check(ctx, width, height, chroma_format_idc, bit_depth, full_range, gbr, bits);
-    if (rc) return rc;
-    if (depth < 2 || depth > 16) return fail(ctx, H2Y_EINVAL, "depth must be 2..16");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    uint32_t off[3];
-    cmp_contiguous(width, height, chroma_format_idc, off);
-    for (int c = 0; c < 3; c++) ctx->s_in_off[c] = off[c] * sizeof(uint16_t);
-    ctx->s_in_bytes = ((size_t)off[2] + (off[2] - off[1])) * sizeof(uint16_t); /* the last plane is as long as the second */
-    rc = stream_alloc(ctx, depth, std::max<size_t>(ctx->s_in_bytes, 16), std::max<size_t>(ctx->s_in_bytes, 16), 16, 16);
-    if (rc) return rc;
-    ctx->s_kind = h2y_ctx::RING_HISTOGRAM;
-    rc = hist_arm(ctx, width, height, chroma_format_idc, bit_depth, full_range, gbr, bits, off);
-    if (rc) {
-        stream_free(ctx);
-        return rc;
-    }
-    return H2Y_OK;
-}
-
-/* k_histogram on the context's stream after the slot's conversion (and comparison) */
-static int hist_run(h2y_ctx *ctx, int slot)
-{
-    return hist_enqueue(ctx, ctx->s_hist_geom, ctx->s_hist_tab + slot, 1, ctx->ss[slot].d_hist);
-}
-
-/* the stats and bins go down on the download stream, after the frame (when it goes down at all) */
-static int hist_download(h2y_ctx *ctx, h2y_ctx::stream_slot &s)
-{
-    const hist_layout L = hist_layout_of(ctx->s_hist_geom.nbins, 1);
-    HIP_TRY(ctx, hipMemcpyAsync(s.h_hist_stats, s.d_hist + L.stats, sizeof(h2y_histogram_stats), hipMemcpyDeviceToHost, ctx->s_d2h));
-    HIP_TRY(ctx, hipMemcpyAsync(s.h_hist_bins, s.d_hist + L.bins, (size_t)3u * ctx->s_hist_geom.nbins * sizeof(uint32_t),
-                                hipMemcpyDeviceToHost, ctx->s_d2h));
-    return H2Y_OK;
-}
-
-/* ---- scaling: the Lanczos resampler of include/hdr2yuv_hip.h ----------------------------------------------------------------- */
-
-static double scale_sinc(double x) { return x == 0.0 ? 1.0 : sin(M_PI * x) / (M_PI * x); }
-
-/* one axis' table as the header defines it, in binary64; rc H2Y_EUNSUPPORTED for a row of sum |q| > 32767 */
-static int scale_axis_table(int s, int d, int a, int32_t *first, int32_t *count, int16_t *coef, int *max_taps)
-{
-    const double f = s > d ? (double)s / (double)d : 1.0, r = (double)a * f;
-    int most = 0;
-    for (int o = 0; o < d; o++) {
-        const double c = (((double)o + 0.5) * (double)s) / (double)d - 0.5;
-        int idx[H2Y_SCALE_TAPS + 2];
-        double w[H2Y_SCALE_TAPS + 2], S = 0.0;
-        int n = 0;
-        for (int i = (int)ceil(c - r), hi = (int)floor(c + r); i <= hi; i++) {
-            if (!(fabs((double)i - c) < r)) continue;
-            if (n == H2Y_SCALE_TAPS) return H2Y_EUNSUPPORTED;
-            const double t = ((double)i - c) / f;
-            idx[n] = i;
-            w[n] = scale_sinc(t) * scale_sinc(t / (double)a);
-            S += w[n];
-            n++;
-        }
-        if (n == 0) return H2Y_EUNSUPPORTED;
-        int q[H2Y_SCALE_TAPS], sum = 0, big = 0;
-        for (int k = 0; k < n; k++) {
-            q[k] = (int)rint(w[k] * 16384.0 / S);
-            sum += q[k];
-            if (q[k] > q[big]) big = k;
-        }
-        q[big] += 16384 - sum;
-        const int lo = idx[0] < 0 ? 0 : idx[0] > s - 1 ? s - 1 : idx[0];
-        int folded[H2Y_SCALE_TAPS] = {0}, m = 0, mag = 0;
-        for (int k = 0; k < n; k++) {
-            const int i = idx[k] < 0 ? 0 : idx[k] > s - 1 ? s - 1 : idx[k];
-            folded[i - lo] += q[k];
-            m = i - lo + 1;
-        }
-        for (int k = 0; k < m; k++) mag += folded[k] < 0 ? -folded[k] : folded[k];
-        if (mag > 32767) return H2Y_EUNSUPPORTED;
-        first[o] = lo;
-        count[o] = m;
-        for (int k = 0; k < H2Y_SCALE_TAPS; k++) coef[(size_t)o * H2Y_SCALE_TAPS + k] = (int16_t)(k < m ? folded[k] : 0);
-        most = m > most ? m : most;
-    }
-    if (max_taps) *max_taps = most;
-    return H2Y_OK;
-}
-
-static bool scale_axis_ok(int s, int d) { return s >= 1 && d >= 1 && s <= 10000 && d <= 10000 && s <= 4 * d && d <= 4 * s; }
-
-int h2y_scale_taps(int src, int dst, int a, int32_t *first, int32_t *count, int16_t *coef, int *max_taps)
-{
-    if (!first || !count || !coef) return fail(nullptr, H2Y_EINVAL, "null table");
-    if (a < 2 || a > 4) return fail(nullptr, H2Y_EINVAL, "a (lobes) must be 2, 3 or 4");
-    if (!scale_axis_ok(src, dst)) return fail(nullptr, H2Y_EINVAL, "sizes must be 1..10000 with a ratio in [1/4, 4]");
-    const int rc = scale_axis_table(src, dst, a, first, count, coef, max_taps);
-    if (rc) return fail(nullptr, rc, "a table row's coefficients do not fit (sum |q| > 32767)");
-    return H2Y_OK;
-}
-
-size_t h2y_scale_frame_bytes(int width, int height, int chroma_format_idc)
-{
-    if (width < 1 || height < 1 || width > 10000 || height > 10000) return 0;
-    if (chroma_format_idc == H2Y_CHROMA_444) return (size_t)width * height * 3u * sizeof(uint16_t);
-    if (chroma_format_idc != H2Y_CHROMA_420) return 0;
-    return ((size_t)width * height + 2u * (size_t)(width >> 1) * (height >> 1)) * sizeof(uint16_t);
-}
-
-static int scale_check(h2y_ctx *ctx, int sw, int sh, int dw, int dh, int chroma, int bit_depth, int full_range, int gbr, int a)
-{
-    if (chroma == 2) return fail(ctx, H2Y_EUNSUPPORTED, "chroma_format_idc 2 (4:2:2) is not scaled");
-    if (chroma != H2Y_CHROMA_420 && chroma != H2Y_CHROMA_444) return fail(ctx, H2Y_EINVAL, "chroma_format_idc must be 1 or 3");
-    if (sw < 2 || sh < 2 || dw < 2 || dh < 2 || sw > 10000 || sh > 10000 || dw > 10000 || dh > 10000)
-        return fail(ctx, H2Y_EINVAL, "scaling: widths and heights must be 2..10000");
-    if (chroma == H2Y_CHROMA_420 && ((sw | sh | dw | dh) & 1)) return fail(ctx, H2Y_EINVAL, "scaling 4:2:0: widths and heights must be even");
-    if (!scale_axis_ok(sw, dw) || !scale_axis_ok(sh, dh)) return fail(ctx, H2Y_EINVAL, "scaling: each axis ratio must be in [1/4, 4]");
-    if (bit_depth < 8 || bit_depth > 16) return fail(ctx, H2Y_EINVAL, "bit_depth must be 8..16");
-    if ((full_range != 0 && full_range != 1) || (gbr != 0 && gbr != 1)) return fail(ctx, H2Y_EINVAL, "full_range and gbr must be 0 or 1");
-    if (a < 2 || a > 4) return fail(ctx, H2Y_EINVAL, "a (lobes) must be 2, 3 or 4");
-    return H2Y_OK;
-}
-
-/* k_scale's geometry with its tables still on the host: blob is what goes to the device, at[p][axis][0..2] where plane p's
- * first, count and coef of that axis lie in it (4:4:4: one pair of tables serves the three planes) */
-struct scale_host {
-    scale_geom g{};
-    std::vector<char> blob;
-    size_t at[3][2][3]{};
-};
-
-static int scale_build(h2y_ctx *ctx, int sw, int sh, int dw, int dh, int chroma, int bit_depth, int full_range, int gbr, int a,
-                       const uint32_t src_off[3], const uint32_t dst_off[3], scale_host &H)
-{
-    const bool sub = chroma == H2Y_CHROMA_420;
-    const clip_limits c = make_clip(bit_depth, full_range);
-    size_t kind_at[2][2][3];
-    for (int kind = 0; kind < (sub ? 2 : 1); kind++)
-        for (int axis = 0; axis < 2; axis++) {
-            const int s = (axis ? sh : sw) >> kind, d = (axis ? dh : dw) >> kind;
-            const size_t ib = ((size_t)d * sizeof(int32_t) + 15) & ~(size_t)15, cb = (size_t)d * H2Y_SCALE_TAPS * sizeof(int16_t);
-            const size_t base = H.blob.size();
-            H.blob.resize(base + 2 * ib + cb);
-            kind_at[kind][axis][0] = base, kind_at[kind][axis][1] = base + ib, kind_at[kind][axis][2] = base + 2 * ib;
-            const int rc = scale_axis_table(s, d, a, reinterpret_cast<int32_t *>(&H.blob[base]), reinterpret_cast<int32_t *>(&H.blob[base + ib]),
-                                            reinterpret_cast<int16_t *>(&H.blob[base + 2 * ib]), nullptr);
-            if (rc) return fail(ctx, rc, "scaling %d -> %d: a table row's coefficients do not fit (sum |q| > 32767)", s, d);
-        }
-    uint32_t h_rows = 1, seg_max = 1;
-    for (int p = 0; p < 3; p++) {
-        const int kind = p && sub ? 1 : 0;
-        scale_plane &P = H.g.p[p];
-        P.sw = (uint32_t)(sw >> kind), P.sh = (uint32_t)(sh >> kind), P.dw = (uint32_t)(dw >> kind), P.dh = (uint32_t)(dh >> kind);
-        P.src_off = src_off[p], P.dst_off = dst_off[p];
-        P.tiles_x = (P.dw + H2Y_SCALE_TILE_W - 1) / H2Y_SCALE_TILE_W;
-        P.tiles = P.tiles_x * ((P.dh + H2Y_SCALE_TILE_H - 1) / H2Y_SCALE_TILE_H);
-        const bool luma_like = p == 0 || gbr;
-        P.lo = (int32_t)(luma_like ? c.minVR : c.minVRC);
-        P.hi = (int32_t)(luma_like ? c.maxVR : c.maxVRC);
-        for (int axis = 0; axis < 2; axis++)
-            for (int k = 0; k < 3; k++) H.at[p][axis][k] = kind_at[kind][axis][k];
-        /* the most source columns and rows one tile reads: what the kernel's LDS must hold */
-        for (int axis = 0; axis < 2; axis++) {
-            const int32_t *first = reinterpret_cast<const int32_t *>(&H.blob[H.at[p][axis][0]]);
-            const int32_t *count = reinterpret_cast<const int32_t *>(&H.blob[H.at[p][axis][1]]);
-            const uint32_t d = axis ? P.dh : P.dw, step = axis ? H2Y_SCALE_TILE_H : H2Y_SCALE_TILE_W;
-            for (uint32_t o0 = 0; o0 < d; o0 += step) {
-                const uint32_t o1 = std::min(d, o0 + step) - 1;
-                const uint32_t span = (uint32_t)(first[o1] + count[o1] - first[o0]);
-                if (axis) h_rows = std::max(h_rows, span);
-                else seg_max = std::max(seg_max, span);
-            }
-        }
-    }
-    H.g.h_rows = h_rows;
-    H.g.src_cols = (seg_max + 7u + 7u) & ~7u;
-    if (h2y_scale_lds(H.g) > 64u * 1024u) return fail(ctx, H2Y_EUNSUPPORTED, "scaling: a tile needs %zu bytes of LDS", h2y_scale_lds(H.g));
-    return H2Y_OK;
-}
-
-/* the tables' addresses once the blob lies at d_base */
-static void scale_bind(scale_host &H, const char *d_base)
-{
-    for (int p = 0; p < 3; p++) {
-        scale_axis *ax[2] = {&H.g.p[p].h, &H.g.p[p].v};
-        for (int axis = 0; axis < 2; axis++) {
-            ax[axis]->first = reinterpret_cast<const int32_t *>(d_base + H.at[p][axis][0]);
-            ax[axis]->count = reinterpret_cast<const int32_t *>(d_base + H.at[p][axis][1]);
-            ax[axis]->coef = reinterpret_cast<const int16_t *>(d_base + H.at[p][axis][2]);
-        }
-    }
-}
-
-static int scale_grid(const h2y_ctx *ctx, const scale_geom &g, int n_frames)
-{
-    return unit_grid(ctx, (uint64_t)n_frames * (g.p[0].tiles + g.p[1].tiles + g.p[2].tiles));
-}
-
-static std::string scale_variant(int chroma, int a)
-{
-    return std::string("k_scale<") + (chroma == H2Y_CHROMA_420 ? "420" : "444") + ",lanczos" + std::to_string(a) + ">";
-}
-
-int h2y_scale_batch(h2y_ctx *ctx, int src_w, int src_h, int dst_w, int dst_h, int chroma_format_idc, int bit_depth, int full_range,
-                    int gbr, int a, int n_frames, const uint16_t *const *d_src, uint16_t *const *d_dst)
-{
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
-    int rc = scale_check(ctx, src_w, src_h, dst_w, dst_h, chroma_format_idc, bit_depth, full_range, gbr, a);
-    if (rc) return rc;
-    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
-    if (!d_src || !d_dst) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
-    for (int f = 0; f < n_frames; f++) {
-        if (!d_src[f] || !d_dst[f]) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is null", f);
-        if (((uintptr_t)d_src[f] | (uintptr_t)d_dst[f]) & 15u) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is not 16-byte aligned", f);
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    uint32_t src_off[3], dst_off[3];
-    cmp_contiguous(src_w, src_h, chroma_format_idc, src_off);
-    cmp_contiguous(dst_w, dst_h, chroma_format_idc, dst_off);
-    scale_host H;
-    rc = scale_build(ctx, src_w, src_h, dst_w, dst_h, chroma_format_idc, bit_depth, full_range, gbr, a, src_off, dst_off, H);
-    if (rc) return rc;
-    scale_frame *h;
-    rc = frame_table(ctx, n_frames, h);
-    if (!rc) rc = ensure(ctx, ctx->d_scale_tabs, ctx->scale_tabs_cap, H.blob.size());
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpy(ctx->d_scale_tabs, H.blob.data(), H.blob.size(), hipMemcpyHostToDevice));
-    scale_bind(H, ctx->d_scale_tabs);
-    for (int f = 0; f < n_frames; f++) h[f] = scale_frame{d_src[f], d_dst[f]};
-    rc = timed_launches(ctx, h, n_frames, H2Y_SCALE_FRAMES_PER_LAUNCH, "k_scale", [&](const scale_frame *frames, int, int nf) {
-        return h2y_launch_scale(scale_grid(ctx, H.g, nf), ctx->stream, H.g, frames, nf);
-    });
-    if (rc) return rc;
-    ctx->last_variant = scale_variant(chroma_format_idc, a);
-    return H2Y_OK;
-}
-
-/* Arm the open ring: the tables and one k_scale table entry per slot go up once.  on_input: a scale-only ring (the slot's input
- * into its output); otherwise the slot's device output into a scaled frame of its own, on the device and pinned. */
-static int scale_arm(h2y_ctx *ctx, int sw, int sh, int dw, int dh, int chroma, int bit_depth, int full_range, int gbr, int a, bool on_input)
-{
-    uint32_t src_off[3], dst_off[3];
-    cmp_contiguous(sw, sh, chroma, src_off);
-    cmp_contiguous(dw, dh, chroma, dst_off);
-    scale_host H;
-    int rc = scale_build(ctx, sw, sh, dw, dh, chroma, bit_depth, full_range, gbr, a, src_off, dst_off, H);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t bytes = h2y_scale_frame_bytes(dw, dh, chroma);
-    const int depth = (int)ctx->ss.size();
-    std::vector<scale_frame> tab(depth);
-    hipError_t e = hipMalloc((void **)&ctx->s_scale_tabs, H.blob.size());
-    if (e == hipSuccess) e = hipMalloc((void **)&ctx->s_scale_tab, tab.size() * sizeof(scale_frame));
-    for (int k = 0; k < depth && e == hipSuccess; k++) {
-        h2y_ctx::stream_slot &s = ctx->ss[k];
-        if (!on_input) {
-            e = hipMalloc((void **)&s.d_scaled, bytes);
-            if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_scaled, bytes, hipHostMallocDefault);
-        }
-        tab[k].src = reinterpret_cast<const uint16_t *>(on_input ? (char *)s.d_in : (char *)s.d_out);
-        tab[k].dst = on_input ? s.d_out : s.d_scaled;
-    }
-    if (e == hipSuccess) e = hipMemcpy(ctx->s_scale_tabs, H.blob.data(), H.blob.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(ctx->s_scale_tab, tab.data(), tab.size() * sizeof(scale_frame), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { /* the ring stays open, unarmed */
-        for (auto &s : ctx->ss) {
-            if (s.d_scaled) (void)hipFree(s.d_scaled);
-            if (s.h_scaled) (void)hipHostFree(s.h_scaled);
-            s.d_scaled = nullptr;
-            s.h_scaled = nullptr;
-        }
-        if (ctx->s_scale_tabs) (void)hipFree(ctx->s_scale_tabs);
-        if (ctx->s_scale_tab) (void)hipFree(ctx->s_scale_tab);
-        ctx->s_scale_tabs = nullptr;
-        ctx->s_scale_tab = nullptr;
-        return fail(ctx, H2Y_ENOMEM, "scaling buffers: %s", hipGetErrorString(e));
-    }
-    scale_bind(H, ctx->s_scale_tabs);
-    ctx->s_scale_geom = H.g;
-    ctx->s_scale_bytes = bytes;
-    ctx->s_scale = true;
-    return H2Y_OK;
-}
-
-int h2y_stream_scale(h2y_ctx *ctx, int dst_w, int dst_h, int a)
-{
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
-    if (ctx->s_kind != h2y_ctx::RING_FORWARD) return fail(ctx, H2Y_EINVAL, "only a forward ring is armed for scaling");
-    if (ctx->s_scale) return fail(ctx, H2Y_EINVAL, "the ring scales already");
-    if (ctx->s_cmp || ctx->s_hist || ctx->s_ssim)
-        return fail(ctx, H2Y_EUNSUPPORTED, "a ring armed for comparison, histograms or SSIM is not scaled: compare or count the written file instead");
-    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
-    const h2y_desc &d = ctx->s_desc;
-    int rc = scale_check(ctx, d.width, d.height, dst_w, dst_h, d.dst_chroma_format_idc, d.dst_bit_depth, d.dst_full_range, 0, a);
-    if (rc) return rc;
-    return scale_arm(ctx, d.width, d.height, dst_w, dst_h, d.dst_chroma_format_idc, d.dst_bit_depth, d.dst_full_range, 0, a, false);
-}
-
-/* A ring that only scales: the slot's input is the frame's three planes one after the other (one H2D copy), its output the
- * scaled frame */
-int h2y_scale_stream_open(h2y_ctx *ctx, int src_w, int src_h, int chroma_format_idc, int bit_depth, int full_range, int gbr, int dst_w,
-                          int dst_h, int a, int depth)
-{
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is already open");
-    int rc = scale_check(ctx, src_w, src_h, dst_w, dst_h, chroma_format_idc, bit_depth, full_range, gbr, a);
-    if (rc) return rc;
-    if (depth < 2 || depth > 16) return fail(ctx, H2Y_EINVAL, "depth must be 2..16");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    uint32_t off[3];
-    cmp_contiguous(src_w, src_h, chroma_format_idc, off);
-    for (int c = 0; c < 3; c++) ctx->s_in_off[c] = off[c] * sizeof(uint16_t);
-    ctx->s_in_bytes = h2y_scale_frame_bytes(src_w, src_h, chroma_format_idc);
-    const size_t ob = h2y_scale_frame_bytes(dst_w, dst_h, chroma_format_idc);
-    rc = stream_alloc(ctx, depth, ctx->s_in_bytes, ctx->s_in_bytes, ob, ob);
-    if (rc) return rc;
-    ctx->s_kind = h2y_ctx::RING_SCALE;
-    rc = scale_arm(ctx, src_w, src_h, dst_w, dst_h, chroma_format_idc, bit_depth, full_range, gbr, a, true);
-    if (rc) {
-        stream_free(ctx);
-        return rc;
-    }
-    return H2Y_OK;
-}
-
-/* k_scale on the context's stream after the slot's conversion (a scale-only ring: after its upload) */
-static int scale_run(h2y_ctx *ctx, int slot)
-{
-    HIP_TRY(ctx, h2y_launch_scale(scale_grid(ctx, ctx->s_scale_geom, 1), ctx->stream, ctx->s_scale_geom, ctx->s_scale_tab + slot, 1));
-    return H2Y_OK;
-}
-
-/* one frame of a scale-only ring: H2D of the frame, k_scale, D2H of the scaled frame */
-static int scale_stream_submit(h2y_ctx *ctx, int slot)
-{
-    h2y_ctx::stream_slot &s = ctx->ss[slot];
-    HIP_TRY(ctx, hipMemcpyAsync(s.d_in, s.h_in, ctx->s_in_bytes, hipMemcpyHostToDevice, ctx->s_h2d));
-    HIP_TRY(ctx, hipEventRecord(s.ev_h2d, ctx->s_h2d));
-    HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s.ev_h2d, 0));
-    const int rc = scale_run(ctx, slot);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipEventRecord(s.ev_conv, ctx->stream));
-    HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_d2h, s.ev_conv, 0));
-    HIP_TRY(ctx, hipMemcpyAsync(s.h_out, s.d_out, ctx->s_scale_bytes, hipMemcpyDeviceToHost, ctx->s_d2h));
-    HIP_TRY(ctx, hipEventRecord(s.ev_done, ctx->s_d2h));
-    s.state = 2;
-    ctx->s_tail = (slot + 1) % (int)ctx->ss.size();
-    return H2Y_OK;
-}
-
-/* one frame of a histogram-only ring: H2D of the frame, k_histogram, D2H of the counts */
-static int histogram_stream_submit(h2y_ctx *ctx, int slot)
-{
-    h2y_ctx::stream_slot &s = ctx->ss[slot];
-    if (ctx->s_in_bytes) HIP_TRY(ctx, hipMemcpyAsync(s.d_in, s.h_in, ctx->s_in_bytes, hipMemcpyHostToDevice, ctx->s_h2d));
-    HIP_TRY(ctx, hipEventRecord(s.ev_h2d, ctx->s_h2d));
-    HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s.ev_h2d, 0));
-    int rc = hist_run(ctx, slot);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipEventRecord(s.ev_conv, ctx->stream));
-    HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_d2h, s.ev_conv, 0));
-    rc = hist_download(ctx, s);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipEventRecord(s.ev_done, ctx->s_d2h));
-    s.state = 2;
-    ctx->s_tail = (slot + 1) % (int)ctx->ss.size();
-    return H2Y_OK;
-}
-
-/* one frame of a compare-only ring: H2D of A and B, k_compare, D2H of the stats */
-static int compare_stream_submit(h2y_ctx *ctx, int slot)
-{
-    h2y_ctx::stream_slot &s = ctx->ss[slot];
-    HIP_TRY(ctx, hipMemcpyAsync(s.d_in, s.h_in, ctx->s_in_bytes, hipMemcpyHostToDevice, ctx->s_h2d));
-    int rc = cmp_upload(ctx, s);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipEventRecord(s.ev_h2d, ctx->s_h2d));
-    HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s.ev_h2d, 0));
-    rc = cmp_run(ctx, slot);
-    if (!rc && ctx->s_ssim) rc = ssim_run(ctx, slot);
-    if (!rc && ctx->s_hist) rc = hist_run(ctx, slot);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipEventRecord(s.ev_conv, ctx->stream));
-    HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_d2h, s.ev_conv, 0));
-    rc = cmp_download(ctx, s);
-    if (!rc && ctx->s_ssim) rc = ssim_download(ctx, s);
-    if (!rc && ctx->s_hist) rc = hist_download(ctx, s);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipEventRecord(s.ev_done, ctx->s_d2h));
-    s.state = 2;
-    ctx->s_tail = (slot + 1) % (int)ctx->ss.size();
-    return H2Y_OK;
-}
-
-/* one frame of an inverse stream: H2D of its planes, k_inverse420 / k_inverse on the context's stream, D2H of G, B, R */
-static int inverse_stream_submit(h2y_ctx *ctx, int slot)
-{
-    h2y_ctx::stream_slot &s = ctx->ss[slot];
-    const inv_params &p = ctx->s_inv;
-    const size_t pb = (size_t)p.width * p.height * sizeof(uint16_t), so = ctx->s_out_stride;
-    HIP_TRY(ctx, hipMemcpyAsync(s.d_in, s.h_in, ctx->s_in_bytes, hipMemcpyHostToDevice, ctx->s_h2d));
-    int rc = ctx->s_cmp ? cmp_upload(ctx, s) : H2Y_OK;
-    if (rc) return rc;
-    HIP_TRY(ctx, hipEventRecord(s.ev_h2d, ctx->s_h2d));
-    HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s.ev_h2d, 0));
-    /* every plane starts on a 16-byte boundary here: the single-frame kernels' wide accesses are safe */
-    inv420_args a;
-    inverse420_setup(a, p.width, p.height, p.in_depth, p.in_full_range, p.matrix, p.out_depth, p.algorithm);
-    for (int c = 0; c < 3; c++) {
-        a.inv.in[c] = s.d_in + ctx->s_in_off[c];
-        a.inv.out[c] = reinterpret_cast<char *>(s.d_out) + c * so;
-    }
-    if (p.chroma == H2Y_CHROMA_420) {
-        a.up.src0 = static_cast<const uint16_t *>(a.inv.in[1]);
-        a.up.src1 = static_cast<const uint16_t *>(a.inv.in[2]);
-        a.inv.in[1] = a.inv.in[2] = nullptr;
-        HIP_TRY(ctx, h2y_launch_inverse420(ctx->stream, a));
-    } else {
-        uint32_t blocks = (a.inv.npix / 4 + 255) / 256; /* as h2y_matrix_inverse */
-        if (blocks > (uint32_t)ctx->n_cu * 16u) blocks = (uint32_t)ctx->n_cu * 16u;
-        if (blocks < 1) blocks = 1;
-        HIP_TRY(ctx, h2y_launch_inverse((int)blocks, ctx->stream, a.inv));
-    }
-    const bool keep = !ctx->s_cmp || ctx->s_cmp_keep;
-    if (ctx->s_interleave && keep) { /* write_tiff's interleave into the slot's device output behind the planes */
-        const uint32_t npix = (uint32_t)p.width * (uint32_t)p.height;
-        HIP_TRY(ctx, h2y_launch_rgb_interleave(unit_grid(ctx, h2y_rgb_chunks(npix)), ctx->stream, npix,
-                                               static_cast<const rgb_frame *>(ctx->s_tab) + slot, 1));
-    }
-    if (ctx->s_cmp) { /* on the G, B, R planes (before the interleave) */
-        rc = cmp_run(ctx, slot);
-        if (!rc && ctx->s_ssim) rc = ssim_run(ctx, slot);
-        if (rc) return rc;
-    }
-    if (ctx->s_hist) { /* likewise */
-        rc = hist_run(ctx, slot);
-        if (rc) return rc;
-    }
-    HIP_TRY(ctx, hipEventRecord(s.ev_conv, ctx->stream));
-    HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_d2h, s.ev_conv, 0));
-    if (!keep) {
-    } else if (ctx->s_interleave)
-        HIP_TRY(ctx, hipMemcpyAsync(s.h_out, reinterpret_cast<char *>(s.d_out) + ctx->s_pay_off, 3 * pb, hipMemcpyDeviceToHost, ctx->s_d2h));
-    else if (so == pb) HIP_TRY(ctx, hipMemcpyAsync(s.h_out, s.d_out, 3 * pb, hipMemcpyDeviceToHost, ctx->s_d2h));
-    else
-        for (int c = 0; c < 3; c++)
-            HIP_TRY(ctx, hipMemcpyAsync(reinterpret_cast<char *>(s.h_out) + c * pb, reinterpret_cast<char *>(s.d_out) + c * so, pb,
-                                        hipMemcpyDeviceToHost, ctx->s_d2h));
-    if (ctx->s_cmp) {
-        rc = cmp_download(ctx, s);
-        if (!rc && ctx->s_ssim) rc = ssim_download(ctx, s);
-        if (rc) return rc;
-    }
-    if (ctx->s_hist) {
-        rc = hist_download(ctx, s);
-        if (rc) return rc;
-    }
-    HIP_TRY(ctx, hipEventRecord(s.ev_done, ctx->s_d2h));
-    s.state = 2;
-    ctx->s_tail = (slot + 1) % (int)ctx->ss.size();
-    return H2Y_OK;
-}
-
-int h2y_stream_input(h2y_ctx *ctx, void *planes[3])
-{
-    if (!ctx || !planes) return fail(ctx, H2Y_EINVAL, "null argument");
-    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
-    h2y_ctx::stream_slot &s = ctx->ss[ctx->s_tail];
-    if (s.state == 1) { /* asked twice without a submit: same buffers again */
-    } else if (s.state != 0) return fail(ctx, H2Y_EINVAL, "all %d slots are in flight: take an output first", (int)ctx->ss.size());
-    s.state = 1;
-    ctx->s_started = true;
-    if (ctx->s_src.kind != decode_src::NONE) { /* the payload, as the file holds it (TIFF: the decoded rows, packed; EXR: unpacked) */
-        planes[0] = s.h_in;
-        planes[1] = planes[2] = nullptr;
-        return H2Y_OK;
-    }
-    for (int c = 0; c < 3; c++) planes[c] = s.h_in + ctx->s_in_off[c];
-    return H2Y_OK;
-}
-
-int h2y_stream_submit(h2y_ctx *ctx)
-{
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
-    const int slot = ctx->s_tail;
-    h2y_ctx::stream_slot &s = ctx->ss[slot];
-    if (s.state != 1) return fail(ctx, H2Y_EINVAL, "nothing to submit: call h2y_stream_input first");
-    if (ctx->s_cmp && !s.ref_lent) return fail(ctx, H2Y_EINVAL, "the ring is armed: h2y_stream_reference before each submit");
-    const h2y_desc *d = &ctx->s_desc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (ctx->s_kind == h2y_ctx::RING_COMPARE) return compare_stream_submit(ctx, slot);
-    if (ctx->s_kind == h2y_ctx::RING_HISTOGRAM) return histogram_stream_submit(ctx, slot);
-    if (ctx->s_kind == h2y_ctx::RING_INVERSE) return inverse_stream_submit(ctx, slot);
-    if (ctx->s_kind == h2y_ctx::RING_SCALE) return scale_stream_submit(ctx, slot);
-    const decode_src &src = ctx->s_src;
-    const size_t pb = h2y_plane_bytes(d), ob = h2y_frame_bytes(d);
-    frame_io io;
-    for (int c = 0; c < 3; c++) io.in[c] = s.d_in + c * ctx->s_plane_al;
-    if (src.kind != decode_src::NONE) /* the payload goes up; the decode writes the three planes below it */
-        HIP_TRY(ctx, hipMemcpyAsync(s.d_in + ctx->s_pay_off, s.h_in, src.payload_bytes(), hipMemcpyHostToDevice, ctx->s_h2d));
-    else /* the slot's three planes lie one after the other (each padded to 256 bytes): one copy command, not three */
-        HIP_TRY(ctx, hipMemcpyAsync(s.d_in, s.h_in, 2 * ctx->s_plane_al + pb, hipMemcpyHostToDevice, ctx->s_h2d));
-    if (ctx->s_cmp) {
-        const int rc = cmp_upload(ctx, s);
-        if (rc) return rc;
-    }
-    io.out = s.d_out;
-    io.tmp_cb = io.tmp_cr = nullptr;
-    HIP_TRY(ctx, hipEventRecord(s.ev_h2d, ctx->s_h2d));
-    HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s.ev_h2d, 0));
-    if (src.kind != decode_src::NONE) HIP_TRY(ctx, src.launch(ctx, static_cast<const payload_frame *>(ctx->s_tab) + slot, 1));
-    const bool needs_stats = d->src_transfer != d->dst_transfer;
-    int rc;
-    if (needs_stats && !d->stats_override) {
-        rc = run_stats(ctx, d, io.in, (int)ctx->b->frames_cap, ctx->b->d_assumed); /* published in device memory, read by the next kernel */
-        ctx->b->dev_assumed_ok = false; /* d_assumed[0] no longer holds what the last enqueued batch left there */
-        if (rc) return rc;
-    } else {
-        /* the same six integers for every frame of the stream: staged once per slot, so an earlier copy still in flight reads its own */
-        assumed_stats *as = reinterpret_cast<assumed_stats *>(s.h_out); /* the slot's pinned output is idle until its D2H */
-        for (int c = 0; c < 3; c++) {
-            as->floor_[c] = d->stats_override ? d->floor[c] : 0;
-            as->ceil_[c] = d->stats_override ? d->ceiling[c] : 1;
-        }
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->b->d_assumed, as, sizeof *as, hipMemcpyHostToDevice, ctx->stream));
-        ctx->b->dev_assumed_ok = false; /* d_assumed[0] no longer holds what the last enqueued batch left there */
-    }
-    ctx->slot_base = slot;
-    ctx->b->n_ev = 0;
-    ctx->cur_skip_t1 = false; /* PCIe-bound here: no steering between the tiers */
-    rc = run_frames(ctx, d, &io, 1, ctx->b->d_assumed, nullptr, false, slot, false);
-    ctx->slot_base = 0;
-    if (rc) return rc;
-    if (ctx->s_light) { /* on the decoded planes, with the floor and ceiling the conversion just used */
-        rc = light_run(ctx, slot);
-        if (rc) return rc;
-    }
-    if (ctx->s_cmp) {
-        rc = cmp_run(ctx, slot);
-        if (!rc && ctx->s_ssim) rc = ssim_run(ctx, slot);
-        if (rc) return rc;
-    }
-    if (ctx->s_hist) {
-        rc = hist_run(ctx, slot);
-        if (rc) return rc;
-    }
-    if (ctx->s_scale) { /* the slot's device output into its scaled frame */
-        rc = scale_run(ctx, slot);
-        if (rc) return rc;
-    }
-    HIP_TRY(ctx, hipEventRecord(s.ev_conv, ctx->stream));
-    HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_d2h, s.ev_conv, 0));
-    if (ctx->s_scale) HIP_TRY(ctx, hipMemcpyAsync(s.h_scaled, s.d_scaled, ctx->s_scale_bytes, hipMemcpyDeviceToHost, ctx->s_d2h));
-    else if (!ctx->s_cmp || ctx->s_cmp_keep) HIP_TRY(ctx, hipMemcpyAsync(s.h_out, s.d_out, ob, hipMemcpyDeviceToHost, ctx->s_d2h));
-    if (ctx->s_cmp) {
-        rc = cmp_download(ctx, s);
-        if (!rc && ctx->s_ssim) rc = ssim_download(ctx, s);
-        if (rc) return rc;
-    }
-    if (ctx->s_hist) {
-        rc = hist_download(ctx, s);
-        if (rc) return rc;
-    }
-    if (ctx->s_light) HIP_TRY(ctx, hipMemcpyAsync(s.h_light, s.d_light, sizeof(light_acc), hipMemcpyDeviceToHost, ctx->s_d2h));
-    HIP_TRY(ctx, hipEventRecord(s.ev_done, ctx->s_d2h));
-    s.state = 2;
-    ctx->s_tail = (slot + 1) % (int)ctx->ss.size();
-    return H2Y_OK;
-}
-
-int h2y_stream_output(h2y_ctx *ctx, const uint16_t **yuv)
-{
-    if (!ctx || !yuv) return fail(ctx, H2Y_EINVAL, "null argument");
-    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
-    if (ctx->s_lent >= 0) { /* the frame handed out last time goes back into the ring */
-        ctx->ss[ctx->s_lent].state = 0;
-        ctx->s_lent = -1;
-    }
-    h2y_ctx::stream_slot &s = ctx->ss[ctx->s_head];
-    if (s.state != 2) return fail(ctx, H2Y_EINVAL, "no submitted frame is waiting");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipEventSynchronize(s.ev_done));
-    *yuv = (ctx->s_cmp && !ctx->s_cmp_keep) || ctx->s_kind == h2y_ctx::RING_HISTOGRAM ? nullptr : s.h_scaled ? s.h_scaled : s.h_out;
-    s.state = 3;
-    ctx->s_lent = ctx->s_head;
-    ctx->s_head = (ctx->s_head + 1) % (int)ctx->ss.size();
-    return H2Y_OK;
-}
-
-int h2y_stream_close(h2y_ctx *ctx)
-{
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if (!ctx->streaming) return H2Y_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    (void)hipStreamSynchronize(ctx->s_h2d);
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipStreamSynchronize(ctx->s_d2h);
-    stream_free(ctx);
-    return H2Y_OK;
-}
-
 
 int h2y_pic_stats(h2y_ctx *ctx, const h2y_desc *d, const void *const d_in[3], float fminmax[6], int32_t floor_ceiling[6])
 {
@@ -4486,5 +2565,3 @@ int h2y_last_kernel_ms(const h2y_ctx *ctx, float *ms, int *launches)
     if (launches) *launches = ctx->last_launches;
     return H2Y_OK;
 }
-
-} // extern "C"

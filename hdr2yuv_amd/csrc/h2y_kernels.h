@@ -1,5 +1,5 @@
 /* h2y_kernels.h -- argument blocks and launch entry points shared by
- * h2y_kernels.hip (device code) and h2y_api.hip (the C-ABI shim). */
+ * h2y_kernels.hip (device code) and the C-ABI shim (h2y_api.hip, h2y_ring.hip, h2y_measure.hip). */
 #ifndef H2Y_KERNELS_H
 #define H2Y_KERNELS_H
 

@@ -1,0 +1,987 @@
+/*
+ * h2y_measure.hip -- the measurements of the C-ABI shim: the comparison with a reference, SSIM, content light, histograms and the
+ * scaler.  Each has its checks and geometry, its batch entry, its ring stage (ring_stage, h2y_shim.h), and its arm, result and
+ * *_stream_open entries.
+ */
+#include "h2y_shim.h"
+
+/* ---- comparison with a reference (--ref_filename, hdr2yuv.cpp:91-100, :827-833) ---------------------------------------- */
+
+/* k_compare's geometry: planes of n[p] samples (4:2:0: Y, then two chroma planes of (width >> 1) x (height >> 1)) starting at
+ * a_off / b_off samples from the two frames' bases */
+static cmp_geom cmp_geom_of(int width, int height, int chroma, int sigma, const uint32_t a_off[3], const uint32_t b_off[3])
+{
+    cmp_geom g{};
+    const bool sub = chroma == H2Y_CHROMA_420;
+    for (int p = 0; p < 3; p++) {
+        const uint32_t w = p && sub ? (uint32_t)(width >> 1) : (uint32_t)width, h = p && sub ? (uint32_t)(height >> 1) : (uint32_t)height;
+        g.n[p] = w * h;
+        g.width[p] = w;
+        g.a_off[p] = a_off[p];
+        g.b_off[p] = b_off[p];
+        const bool vec = (a_off[p] & 7u) == (b_off[p] & 7u);
+        g.shift[p] = vec ? a_off[p] & 7u : 0u;
+        g.vec |= vec ? 1u << p : 0u;
+        g.chunks[p] = h2y_compare_chunks(g.n[p], g.shift[p]);
+    }
+    g.sigma = (uint32_t)sigma;
+    return g;
+}
+
+static int cmp_check(h2y_ctx *ctx, int width, int height, int chroma, int sigma)
+{
+    if (width < 1 || height < 1 || (uint64_t)width * (uint64_t)height >= (1ull << 28)) return fail(ctx, H2Y_EINVAL, "bad picture size");
+    if (chroma != H2Y_CHROMA_420 && chroma != H2Y_CHROMA_444) return fail(ctx, H2Y_EINVAL, "chroma_format_idc must be 1 or 3");
+    if (sigma < 0) return fail(ctx, H2Y_EINVAL, "sigma must be >= 0");
+    return H2Y_OK;
+}
+
+/* k_compare's partials for n_frames frames of g */
+static int cmp_partials(h2y_ctx *ctx, const cmp_geom &g, int n_frames)
+{
+    return ensure(ctx, ctx->d_cmp_part, ctx->cmp_part_cap,
+                  std::max<size_t>(1, (size_t)n_frames * (g.chunks[0] + g.chunks[1] + g.chunks[2])) * sizeof(cmp_partial));
+}
+
+static int cmp_grid(const h2y_ctx *ctx, const cmp_geom &g, int n_frames)
+{
+    return unit_grid(ctx, (uint64_t)n_frames * (g.chunks[0] + g.chunks[1] + g.chunks[2]));
+}
+
+int h2y_compare_batch(h2y_ctx *ctx, int width, int height, int chroma_format_idc, int sigma, int n_frames, const uint16_t *const *d_a,
+                      const uint16_t *const *d_b, h2y_compare_stats *out)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
+    int rc = cmp_check(ctx, width, height, chroma_format_idc, sigma);
+    if (rc) return rc;
+    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
+    if (!d_a || !d_b || !out) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
+    for (int f = 0; f < n_frames; f++) {
+        if (!d_a[f] || !d_b[f]) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is null", f);
+        if (((uintptr_t)d_a[f] | (uintptr_t)d_b[f]) & 15u) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is not 16-byte aligned", f);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    uint32_t off[3];
+    contiguous_planes(width, height, chroma_format_idc, off);
+    const cmp_geom g = cmp_geom_of(width, height, chroma_format_idc, sigma, off, off);
+    const int per_launch = std::min(n_frames, H2Y_COMPARE_FRAMES_PER_LAUNCH);
+    cmp_frame *h;
+    rc = frame_table(ctx, n_frames, h);
+    if (!rc) rc = cmp_partials(ctx, g, per_launch);
+    if (!rc) rc = ensure(ctx, ctx->d_cmp_stats, ctx->cmp_stats_cap, (size_t)n_frames * sizeof(h2y_compare_stats));
+    if (rc) return rc;
+    for (int f = 0; f < n_frames; f++) h[f] = cmp_frame{d_a[f], d_b[f]};
+    rc = timed_launches(ctx, h, n_frames, H2Y_COMPARE_FRAMES_PER_LAUNCH, "k_compare", [&](const cmp_frame *frames, int f0, int nf) {
+        return h2y_launch_compare(cmp_grid(ctx, g, nf), ctx->stream, g, frames, nf, ctx->d_cmp_part, ctx->d_cmp_stats + f0);
+    });
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpy(out, ctx->d_cmp_stats, (size_t)n_frames * sizeof(h2y_compare_stats), hipMemcpyDeviceToHost));
+    ctx->last_variant = std::string("k_compare<") + (chroma_format_idc == H2Y_CHROMA_420 ? "420" : "444") + ">";
+    return H2Y_OK;
+}
+
+/* The comparison's ring stage.  Per slot a pinned reference (the planes one after the other), its device twin laid out as the
+ * ring's frame (so both sides share each plane's alignment and k_compare keeps its 16-byte loads) with the frame's stats behind
+ * it (256-byte aligned), pinned stats, and the slot's k_compare table entry (A: the ring's frame, B: the device reference) */
+struct cmp_stage : ring_stage {
+    struct slot {
+        char *h_ref = nullptr, *d_ref = nullptr;
+        h2y_compare_stats *h_stats = nullptr;
+        bool ref_lent = false;
+    };
+    std::vector<slot> ss;
+    cmp_geom g{};
+    cmp_frame *tab = nullptr;
+    size_t ref_bytes = 0, stats_off = 0; /* the pinned reference's bytes; where the stats lie in its device twin */
+    h2y_compare_stats *dev_stats(int k) const { return reinterpret_cast<h2y_compare_stats *>(ss[k].d_ref + stats_off); }
+    int ready(h2y_ctx *ctx, int k) override
+    {
+        if (!ss[k].ref_lent) return fail(ctx, H2Y_EINVAL, "the ring is armed: h2y_stream_reference before each submit");
+        return H2Y_OK;
+    }
+    int upload(h2y_ctx *ctx, int k) override
+    {
+        slot &s = ss[k];
+        if (g.b_off[1] == g.n[0] && g.b_off[2] == g.n[0] + g.n[1]) /* the device twin is contiguous too: one copy */
+            HIP_TRY(ctx, hipMemcpyAsync(s.d_ref, s.h_ref, ref_bytes, hipMemcpyHostToDevice, ctx->s_h2d));
+        else /* padded apart as the inverse ring's output planes */
+            for (size_t c = 0, h_off = 0; c < 3; h_off += g.n[c] * sizeof(uint16_t), c++)
+                HIP_TRY(ctx, hipMemcpyAsync(s.d_ref + g.b_off[c] * sizeof(uint16_t), s.h_ref + h_off, g.n[c] * sizeof(uint16_t),
+                                            hipMemcpyHostToDevice, ctx->s_h2d));
+        s.ref_lent = false;
+        return H2Y_OK;
+    }
+    int run(h2y_ctx *ctx, int k) override
+    {
+        HIP_TRY(ctx, h2y_launch_compare(cmp_grid(ctx, g, 1), ctx->stream, g, tab + k, 1, ctx->d_cmp_part, dev_stats(k)));
+        return H2Y_OK;
+    }
+    int download(h2y_ctx *ctx, int k) override
+    {
+        HIP_TRY(ctx, hipMemcpyAsync(ss[k].h_stats, dev_stats(k), sizeof(h2y_compare_stats), hipMemcpyDeviceToHost, ctx->s_d2h));
+        return H2Y_OK;
+    }
+};
+
+/* arm the open ring's frame; keep_output 0: the frame stays on the device */
+static int cmp_arm(h2y_ctx *ctx, int sigma, int keep_output)
+{
+    const ring_frame &f = ctx->s_frame;
+    int rc = cmp_check(ctx, f.width, f.height, f.chroma, sigma);
+    if (rc) return rc;
+    auto st = std::make_unique<cmp_stage>();
+    const cmp_geom &g = st->g = cmp_geom_of(f.width, f.height, f.chroma, sigma, f.off, f.off);
+    const int depth = (int)ctx->ss.size();
+    st->ref_bytes = ((size_t)g.n[0] + g.n[1] + g.n[2]) * sizeof(uint16_t);
+    st->stats_off = (((size_t)f.off[2] + g.n[2]) * sizeof(uint16_t) + 255) & ~(size_t)255;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = cmp_partials(ctx, g, 1);
+    if (rc) return rc;
+    std::vector<cmp_frame> tab(depth);
+    st->ss.resize(depth);
+    for (int k = 0; k < depth; k++) {
+        cmp_stage::slot &s = st->ss[k];
+        st->pin_alloc(s.h_ref, st->ref_bytes);
+        st->pin_alloc(s.h_stats, sizeof(h2y_compare_stats));
+        st->dev_alloc(s.d_ref, st->stats_off + sizeof(h2y_compare_stats));
+        tab[k] = cmp_frame{frame_base(ctx, k), reinterpret_cast<const uint16_t *>(s.d_ref)};
+    }
+    st->table(st->tab, tab);
+    rc = stage_arm(ctx, STAGE_COMPARE, std::move(st), "compare");
+    if (!rc && !keep_output) ring_frame_stays(ctx);
+    return rc;
+}
+
+int h2y_stream_compare(h2y_ctx *ctx, int sigma, int keep_output)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    if (ctx->s_stage[STAGE_COMPARE]) return fail(ctx, H2Y_EINVAL, "the ring is armed already");
+    if (ctx->s_stage[STAGE_SCALE]) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that scales is not compared: compare the written file instead");
+    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    if (keep_output != 0 && keep_output != 1) return fail(ctx, H2Y_EINVAL, "keep_output must be 0 or 1");
+    return cmp_arm(ctx, sigma, keep_output);
+}
+
+int h2y_stream_reference(h2y_ctx *ctx, void **ref)
+{
+    if (!ctx || !ref) return fail(ctx, H2Y_EINVAL, "null argument");
+    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    cmp_stage *st = stage_of<cmp_stage>(ctx, STAGE_COMPARE);
+    if (!st) return fail(ctx, H2Y_EINVAL, "the ring is not armed: h2y_stream_compare first");
+    const int state = ctx->ss[ctx->s_tail].state;
+    if (state != 0 && state != 1) return fail(ctx, H2Y_EINVAL, "all %d slots are in flight: take an output first", (int)ctx->ss.size());
+    st->ss[ctx->s_tail].ref_lent = true;
+    *ref = st->ss[ctx->s_tail].h_ref;
+    return H2Y_OK;
+}
+
+int h2y_stream_compare_result(h2y_ctx *ctx, h2y_compare_stats *out)
+{
+    if (!ctx || !out) return fail(ctx, H2Y_EINVAL, "null argument");
+    const cmp_stage *st = ctx->streaming ? stage_of<cmp_stage>(ctx, STAGE_COMPARE) : nullptr;
+    if (!st) return fail(ctx, H2Y_EINVAL, "no armed stream open");
+    if (ctx->s_lent < 0) return fail(ctx, H2Y_EINVAL, "no output taken yet: h2y_stream_output first");
+    *out = *st->ss[ctx->s_lent].h_stats;
+    return H2Y_OK;
+}
+
+/* A ring that only compares: the slot's input is A's three planes, the device output unused */
+int h2y_compare_stream_open(h2y_ctx *ctx, int width, int height, int chroma_format_idc, int sigma, int depth)
+{
+    int rc = ring_may_open(ctx);
+    if (!rc) rc = cmp_check(ctx, width, height, chroma_format_idc, sigma);
+    if (!rc) rc = open_planes_ring(ctx, width, height, chroma_format_idc, 0, 0, 0, 0, depth);
+    if (rc) return rc;
+    rc = cmp_arm(ctx, sigma, 0);
+    if (rc) stream_free(ctx);
+    return rc;
+}
+
+/* ---- SSIM beside the comparison (hdr2yuv.cpp:826) ------------------------------------------------------------------------ */
+
+/* k_ssim's geometry: the comparison's planes (4:2:0: Y, then two chroma planes of (width >> 1) x (height >> 1)) starting at a_off /
+ * b_off samples from the two frames' bases, and the constants of bit_depth, computed once here in binary64, left to right */
+static ssim_geom ssim_geom_of(int width, int height, int chroma, int bit_depth, const uint32_t a_off[3], const uint32_t b_off[3])
+{
+    ssim_geom g{};
+    const bool sub = chroma == H2Y_CHROMA_420;
+    for (int p = 0; p < 3; p++) {
+        g.pw[p] = p && sub ? (uint32_t)(width >> 1) : (uint32_t)width;
+        g.ph[p] = p && sub ? (uint32_t)(height >> 1) : (uint32_t)height;
+        g.a_off[p] = a_off[p];
+        g.b_off[p] = b_off[p];
+        g.strips[p] = h2y_ssim_strips(g.pw[p]);
+        g.units[p] = g.strips[p] * h2y_ssim_segments(g.ph[p]);
+    }
+    g.wide = bit_depth > 12;
+    const double M = (double)((1u << bit_depth) - 1u);
+    g.c1 = ((0.01 * 0.01) * M) * M * 64.0;
+    g.c2 = (((0.03 * 0.03) * M) * M * 64.0) * 63.0;
+    return g;
+}
+
+static int ssim_check(h2y_ctx *ctx, int width, int height, int chroma, int bit_depth)
+{
+    if (width < 1 || height < 1 || (uint64_t)width * (uint64_t)height >= (1ull << 28)) return fail(ctx, H2Y_EINVAL, "bad picture size");
+    if (chroma == 2) return fail(ctx, H2Y_EUNSUPPORTED, "chroma_format_idc 2 (4:2:2) has no SSIM on this path");
+    if (chroma != H2Y_CHROMA_420 && chroma != H2Y_CHROMA_444) return fail(ctx, H2Y_EINVAL, "chroma_format_idc must be 1 or 3");
+    if (bit_depth < 8 || bit_depth > 16) return fail(ctx, H2Y_EINVAL, "bit_depth must be 8..16");
+    const int sub = chroma == H2Y_CHROMA_420;
+    if ((width >> sub) < 8 || (height >> sub) < 8)
+        return fail(ctx, H2Y_EINVAL, "SSIM needs every plane at least 8x8 (one window): %dx%d %s", width, height, sub ? "4:2:0" : "4:4:4");
+    return H2Y_OK;
+}
+
+/* k_ssim's partials for n_frames frames of g */
+static int ssim_partials(h2y_ctx *ctx, const ssim_geom &g, int n_frames)
+{
+    return ensure(ctx, ctx->d_ssim_part, ctx->ssim_part_cap, (size_t)n_frames * (g.units[0] + g.units[1] + g.units[2]) * sizeof(int64_t));
+}
+
+int h2y_ssim_batch(h2y_ctx *ctx, int width, int height, int chroma_format_idc, int bit_depth, int n_frames, const uint16_t *const *d_a,
+                   const uint16_t *const *d_b, h2y_ssim_stats *out)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
+    int rc = ssim_check(ctx, width, height, chroma_format_idc, bit_depth);
+    if (rc) return rc;
+    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
+    if (!d_a || !d_b || !out) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
+    for (int f = 0; f < n_frames; f++) {
+        if (!d_a[f] || !d_b[f]) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is null", f);
+        if (((uintptr_t)d_a[f] | (uintptr_t)d_b[f]) & 15u) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is not 16-byte aligned", f);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    uint32_t off[3];
+    contiguous_planes(width, height, chroma_format_idc, off);
+    const ssim_geom g = ssim_geom_of(width, height, chroma_format_idc, bit_depth, off, off);
+    const int per_launch = std::min(n_frames, H2Y_SSIM_FRAMES_PER_LAUNCH);
+    cmp_frame *h;
+    rc = frame_table(ctx, n_frames, h);
+    if (!rc) rc = ssim_partials(ctx, g, per_launch);
+    if (!rc) rc = ensure(ctx, ctx->d_ssim_stats, ctx->ssim_stats_cap, (size_t)n_frames * sizeof(h2y_ssim_stats));
+    if (rc) return rc;
+    for (int f = 0; f < n_frames; f++) h[f] = cmp_frame{d_a[f], d_b[f]};
+    rc = timed_launches(ctx, h, n_frames, H2Y_SSIM_FRAMES_PER_LAUNCH, "k_ssim", [&](const cmp_frame *frames, int f0, int nf) {
+        return h2y_launch_ssim(h2y_ssim_grid(ctx->n_cu, g, nf), ctx->stream, g, frames, nf, ctx->d_ssim_part, ctx->d_ssim_stats + f0);
+    });
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpy(out, ctx->d_ssim_stats, (size_t)n_frames * sizeof(h2y_ssim_stats), hipMemcpyDeviceToHost));
+    ctx->last_variant = std::string("k_ssim<") + (chroma_format_idc == H2Y_CHROMA_420 ? "420" : "444") + "," + (g.wide ? "U64" : "U32") + ">";
+    return H2Y_OK;
+}
+
+/* SSIM's ring stage: k_ssim after k_compare, on the comparison's table entry of the slot, the frame's SSIM on the device and
+ * pinned */
+struct ssim_stage : ring_stage {
+    struct slot {
+        h2y_ssim_stats *d = nullptr, *h = nullptr;
+    };
+    std::vector<slot> ss;
+    ssim_geom g{};
+    const cmp_frame *tab = nullptr; /* the comparison's stage's */
+    int run(h2y_ctx *ctx, int k) override
+    {
+        HIP_TRY(ctx, h2y_launch_ssim(h2y_ssim_grid(ctx->n_cu, g, 1), ctx->stream, g, tab + k, 1, ctx->d_ssim_part, ss[k].d));
+        return H2Y_OK;
+    }
+    int download(h2y_ctx *ctx, int k) override
+    {
+        HIP_TRY(ctx, hipMemcpyAsync(ss[k].h, ss[k].d, sizeof(h2y_ssim_stats), hipMemcpyDeviceToHost, ctx->s_d2h));
+        return H2Y_OK;
+    }
+};
+
+int h2y_stream_ssim(h2y_ctx *ctx, int bit_depth)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    if (ctx->s_stage[STAGE_SCALE]) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that scales computes no SSIM: compare the written file instead");
+    const cmp_stage *cmp = stage_of<cmp_stage>(ctx, STAGE_COMPARE);
+    if (!cmp) return fail(ctx, H2Y_EINVAL, "the ring is not armed for comparison: h2y_stream_compare first");
+    if (ctx->s_stage[STAGE_SSIM]) return fail(ctx, H2Y_EINVAL, "the ring computes SSIM already");
+    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    const ring_frame &f = ctx->s_frame;
+    if (bit_depth < 0) {
+        if (!f.depth) return fail(ctx, H2Y_EINVAL, "a compare-only ring does not know its frames' bit depth: give it to h2y_stream_ssim");
+        bit_depth = f.depth;
+    }
+    int rc = ssim_check(ctx, f.width, f.height, f.chroma, bit_depth);
+    if (rc) return rc;
+    auto st = std::make_unique<ssim_stage>();
+    st->g = ssim_geom_of(f.width, f.height, f.chroma, bit_depth, f.off, f.off);
+    st->tab = cmp->tab;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = ssim_partials(ctx, st->g, 1);
+    if (rc) return rc;
+    st->ss.resize(ctx->ss.size());
+    for (auto &s : st->ss) {
+        st->dev_alloc(s.d, sizeof(h2y_ssim_stats));
+        st->pin_alloc(s.h, sizeof(h2y_ssim_stats));
+    }
+    return stage_arm(ctx, STAGE_SSIM, std::move(st), "SSIM");
+}
+
+int h2y_stream_ssim_result(h2y_ctx *ctx, h2y_ssim_stats *out)
+{
+    if (!ctx || !out) return fail(ctx, H2Y_EINVAL, "null argument");
+    const ssim_stage *st = ctx->streaming ? stage_of<ssim_stage>(ctx, STAGE_SSIM) : nullptr;
+    if (!st) return fail(ctx, H2Y_EINVAL, "no stream open that computes SSIM");
+    if (ctx->s_lent < 0) return fail(ctx, H2Y_EINVAL, "no output taken yet: h2y_stream_output first");
+    *out = *st->ss[ctx->s_lent].h;
+    return H2Y_OK;
+}
+
+/* ---- content light level (MaxCLL / MaxFALL) of a forward conversion to PQ ------------------------------------------------------ */
+
+/* the descriptors whose light is measured: conversions to PQ from another transfer, of a G, B, R source */
+static int light_check(h2y_ctx *ctx, const h2y_desc *d)
+{
+    const char *why;
+    int rc = h2y_desc_check(d, &why);
+    if (rc) return fail(ctx, rc, "descriptor: %s", why);
+    if (d->dst_transfer != 16)
+        return fail(ctx, H2Y_EUNSUPPORTED, "content light is measured on conversions to PQ (dst_transfer 16), not dst_transfer %d", d->dst_transfer);
+    if (d->src_transfer == 16)
+        return fail(ctx, H2Y_EUNSUPPORTED, "a PQ source goes to PQ without linear light: there is no light to measure");
+    if (d->src_matrix != H2Y_MATRIX_GBR)
+        return fail(ctx, H2Y_EUNSUPPORTED, "content light needs a G,B,R source (src_matrix 0), not src_matrix %d", d->src_matrix);
+    return H2Y_OK;
+}
+
+/* k_light's arguments for d: the conversion's parameters and, for a source transfer other than LINEAR, its stage's tables */
+static int light_args_of(h2y_ctx *ctx, const h2y_desc *d, light_args &a)
+{
+    a = light_args{};
+    derive_params(d, &a.pp, false);
+    a.npix = (uint32_t)d->width * (uint32_t)d->height;
+    a.n4 = a.npix / 4u;
+    a.table = nullptr;
+    if (a.pp.src_tf != H2Y_TF_LINEAR) {
+        static const int kSrcFn[4] = {H2Y_TFN_NONE, H2Y_TFN_PQ_F, H2Y_TFN_RHO_H, H2Y_TFN_G24}; /* by H2Y_TF_* class, as run_frames() */
+        const int sf = kSrcFn[a.pp.src_tf];
+        const int rc = ensure_tfn(ctx, sf);
+        if (rc) return rc;
+        a.pp.src_fn = sf;
+        a.table = ctx->d_tfn[sf];
+        a.pp.tf_ext[0] = ctx->d_tfn_ext[sf];
+    }
+    return H2Y_OK;
+}
+
+static std::string light_variant(const h2y_desc *d, const light_args &a)
+{
+    static const char *const kIn[] = {"F32", "F16", "U16"}, *const kTf[] = {"LINEAR", "PQ", "RHO_GAMMA", "BT1886"};
+    return std::string("k_light<") + kIn[in_kind_of(d)] + "," + kTf[a.pp.src_tf] + ">";
+}
+
+/* the stats of one frame of npix pixels, width wide, from its accumulator */
+static void light_finish(const light_acc &acc, uint32_t width, uint32_t npix, h2y_light_stats *o)
+{
+    *o = h2y_light_stats{};
+    o->max_bits = (uint32_t)(acc.key >> 32);
+    const uint32_t i = ~(uint32_t)acc.key;
+    o->x = i % width;
+    o->y = i / width;
+    o->sum_q = acc.sum;
+    o->pixels = npix;
+    o->cll = 10000.0 * (double)bits2f(o->max_bits);
+    o->fall = ((10000.0 * (double)acc.sum) * 0x1p-32) / (double)npix;
+}
+
+int h2y_light_batch(h2y_ctx *ctx, const h2y_desc *d, int n_frames, const void *const *d_planes, h2y_light_stats *out)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
+    int rc = light_check(ctx, d);
+    if (rc) return rc;
+    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
+    if (!d_planes || !out) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
+    for (int f = 0; f < n_frames; f++)
+        for (int c = 0; c < 3; c++)
+            if (!d_planes[3 * f + c] || ((uintptr_t)d_planes[3 * f + c] & 15u))
+                return fail(ctx, H2Y_EINVAL, "input plane %d of frame %d is null or not 16-byte aligned", c, f);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    light_args a;
+    rc = light_args_of(ctx, d, a);
+    light_frame *h;
+    if (!rc) rc = frame_table(ctx, n_frames, h);
+    if (!rc) rc = ensure(ctx, ctx->d_light_as, ctx->light_as_cap, (size_t)n_frames * sizeof(assumed_stats));
+    if (!rc) rc = ensure(ctx, ctx->d_light_acc, ctx->light_acc_cap, (size_t)n_frames * sizeof(light_acc));
+    if (rc) return rc;
+    if (d->stats_override) { /* the same six integers for every frame */
+        std::vector<assumed_stats> as(n_frames);
+        for (auto &x : as)
+            for (int c = 0; c < 3; c++) x.floor_[c] = d->floor[c], x.ceil_[c] = d->ceiling[c];
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_light_as, as.data(), (size_t)n_frames * sizeof(assumed_stats), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    } else /* pic_stats of every frame, as h2y_convert_batch ends up taking it */
+        for (int f = 0; f < n_frames; f++) {
+            rc = run_stats(ctx, d, d_planes + 3 * f, (int)ctx->b->frames_cap, ctx->d_light_as + f);
+            if (rc) return rc;
+        }
+    ctx->b->dev_assumed_ok = false; /* run_stats used the batch state's scratch slot */
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_light_acc, 0, (size_t)n_frames * sizeof(light_acc), ctx->stream));
+    for (int f = 0; f < n_frames; f++)
+        h[f] = light_frame{{d_planes[3 * f], d_planes[3 * f + 1], d_planes[3 * f + 2]}, ctx->d_light_as + f};
+    const int in_kind = in_kind_of(d);
+    rc = timed_launches(ctx, h, n_frames, H2Y_LIGHT_FRAMES_PER_LAUNCH, "k_light", [&](const light_frame *frames, int f0, int nf) {
+        return h2y_launch_light(in_kind, h2y_light_grid(a.npix, nf), ctx->stream, a, frames, nf, ctx->d_light_acc + f0);
+    });
+    if (rc) return rc;
+    std::vector<light_acc> acc(n_frames);
+    HIP_TRY(ctx, hipMemcpy(acc.data(), ctx->d_light_acc, (size_t)n_frames * sizeof(light_acc), hipMemcpyDeviceToHost));
+    for (int f = 0; f < n_frames; f++) light_finish(acc[f], (uint32_t)d->width, a.npix, out + f);
+    ctx->last_variant = light_variant(d, a);
+    return H2Y_OK;
+}
+
+/* Content light's ring stage, on the forward ring's decoded planes with the floor and ceiling the conversion just used
+ * (d_assumed): k_light's arguments, its table entry per slot, and the frame's accumulator on the device and pinned */
+struct light_stage : ring_stage {
+    struct slot {
+        light_acc *d = nullptr, *h = nullptr;
+    };
+    std::vector<slot> ss;
+    light_args a{};
+    light_frame *tab = nullptr;
+    int run(h2y_ctx *ctx, int k) override
+    {
+        HIP_TRY(ctx, hipMemsetAsync(ss[k].d, 0, sizeof(light_acc), ctx->stream));
+        HIP_TRY(ctx, h2y_launch_light(in_kind_of(&ctx->s_desc), h2y_light_grid(a.npix, 1), ctx->stream, a, tab + k, 1, ss[k].d));
+        return H2Y_OK;
+    }
+    int download(h2y_ctx *ctx, int k) override
+    {
+        HIP_TRY(ctx, hipMemcpyAsync(ss[k].h, ss[k].d, sizeof(light_acc), hipMemcpyDeviceToHost, ctx->s_d2h));
+        return H2Y_OK;
+    }
+};
+
+int h2y_stream_light(h2y_ctx *ctx)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    if (ctx->s_kind != h2y_ctx::RING_FORWARD) return fail(ctx, H2Y_EINVAL, "content light is measured on the forward rings only");
+    if (ctx->s_stage[STAGE_LIGHT]) return fail(ctx, H2Y_EINVAL, "the ring measures content light already");
+    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    const h2y_desc *d = &ctx->s_desc;
+    int rc = light_check(ctx, d);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    auto st = std::make_unique<light_stage>();
+    rc = light_args_of(ctx, d, st->a);
+    if (rc) return rc;
+    const int depth = (int)ctx->ss.size();
+    std::vector<light_frame> tab(depth);
+    st->ss.resize(depth);
+    for (int k = 0; k < depth; k++) {
+        for (int c = 0; c < 3; c++) tab[k].in[c] = ctx->ss[k].d_in + c * ctx->s_plane_al;
+        tab[k].assumed = ctx->b->d_assumed;
+        st->dev_alloc(st->ss[k].d, sizeof(light_acc));
+        st->pin_alloc(st->ss[k].h, sizeof(light_acc));
+    }
+    st->table(st->tab, tab);
+    return stage_arm(ctx, STAGE_LIGHT, std::move(st), "content light");
+}
+
+int h2y_stream_light_result(h2y_ctx *ctx, h2y_light_stats *out)
+{
+    if (!ctx || !out) return fail(ctx, H2Y_EINVAL, "null argument");
+    const light_stage *st = ctx->streaming ? stage_of<light_stage>(ctx, STAGE_LIGHT) : nullptr;
+    if (!st) return fail(ctx, H2Y_EINVAL, "no stream open that measures content light");
+    if (ctx->s_lent < 0) return fail(ctx, H2Y_EINVAL, "no output taken yet: h2y_stream_output first");
+    light_finish(*st->ss[ctx->s_lent].h, (uint32_t)ctx->s_desc.width, st->a.npix, out);
+    return H2Y_OK;
+}
+
+/* ---- code-value histograms and the legal-range check (hdr2yuv.cpp:658, :797) ---------------------------------------------- */
+
+/* k_histogram's geometry: planes of the comparison's geometry starting at off samples from the frame's base, the legal range of
+ * set_pic_clip() at bit_depth (planes 1 and 2 of a YCbCr frame: minVRC..maxVRC; plane 0 and every G, B, R plane: minVR..maxVR) */
+static hist_geom hist_geom_of(int width, int height, int chroma, int bit_depth, int full_range, int gbr, int bits, const uint32_t off[3])
+{
+    hist_geom g{};
+    const bool sub = chroma == H2Y_CHROMA_420;
+    const clip_limits c = make_clip(bit_depth, full_range);
+    for (int p = 0; p < 3; p++) {
+        const uint32_t w = p && sub ? (uint32_t)(width >> 1) : (uint32_t)width, h = p && sub ? (uint32_t)(height >> 1) : (uint32_t)height;
+        g.n[p] = w * h;
+        g.off[p] = off[p];
+        g.shift[p] = off[p] & 7u;
+        g.vec |= 1u << p; /* one side: the groups can always follow the plane's start */
+        g.units[p] = h2y_histogram_units(g.n[p], g.shift[p]);
+        const bool luma_like = p == 0 || gbr;
+        g.lo[p] = luma_like ? c.minVR : c.minVRC;
+        g.hi[p] = luma_like ? c.maxVR : c.maxVRC;
+    }
+    g.nbins = 1u << bits;
+    g.down = (uint32_t)(bit_depth - bits);
+    return g;
+}
+
+static int hist_check(h2y_ctx *ctx, int width, int height, int chroma, int bit_depth, int full_range, int gbr, int bits)
+{
+    if (width < 1 || height < 1 || (uint64_t)width * (uint64_t)height >= (1ull << 28)) return fail(ctx, H2Y_EINVAL, "bad picture size");
+    if (chroma == 2) return fail(ctx, H2Y_EUNSUPPORTED, "chroma_format_idc 2 (4:2:2) is not counted on this path");
+    if (chroma != H2Y_CHROMA_420 && chroma != H2Y_CHROMA_444) return fail(ctx, H2Y_EINVAL, "chroma_format_idc must be 1 or 3");
+    if (bit_depth < 8 || bit_depth > 16) return fail(ctx, H2Y_EINVAL, "bit_depth must be 8..16");
+    if (bits < 1 || bits > bit_depth) return fail(ctx, H2Y_EINVAL, "bits must be 1..bit_depth (%d)", bit_depth);
+    if ((full_range != 0 && full_range != 1) || (gbr != 0 && gbr != 1)) return fail(ctx, H2Y_EINVAL, "full_range and gbr must be 0 or 1");
+    return H2Y_OK;
+}
+
+/* A workspace of nf frames: the counts (zeroed), the bins (zeroed), then the stats k_histogram_finish writes */
+struct hist_layout {
+    size_t bins, stats, total;
+};
+static hist_layout hist_layout_of(uint32_t nbins, int nf)
+{
+    hist_layout L;
+    L.bins = ((size_t)nf * 3u * sizeof(hist_acc) + 255) & ~(size_t)255;
+    L.stats = (L.bins + (size_t)nf * 3u * nbins * sizeof(uint32_t) + 255) & ~(size_t)255;
+    L.total = L.stats + (size_t)nf * sizeof(h2y_histogram_stats);
+    return L;
+}
+
+/* the zeroing and both kernels of nf frames on the context's stream, into the workspace ws */
+static int hist_enqueue(h2y_ctx *ctx, const hist_geom &g, const hist_frame *frames, int nf, char *ws)
+{
+    const hist_layout L = hist_layout_of(g.nbins, nf);
+    HIP_TRY(ctx, hipMemsetAsync(ws, 0, L.stats, ctx->stream));
+    HIP_TRY(ctx, h2y_launch_histogram(h2y_histogram_grid(ctx->n_cu, g, nf), ctx->stream, g, frames, nf, reinterpret_cast<hist_acc *>(ws),
+                                      reinterpret_cast<uint32_t *>(ws + L.bins), reinterpret_cast<h2y_histogram_stats *>(ws + L.stats)));
+    return H2Y_OK;
+}
+
+int h2y_histogram_batch(h2y_ctx *ctx, int width, int height, int chroma_format_idc, int bit_depth, int full_range, int gbr, int bits,
+                        int n_frames, const uint16_t *const *d_frames, h2y_histogram_stats *out_stats, uint32_t *out_bins)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
+    int rc = hist_check(ctx, width, height, chroma_format_idc, bit_depth, full_range, gbr, bits);
+    if (rc) return rc;
+    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
+    if (!d_frames || !out_stats) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
+    for (int f = 0; f < n_frames; f++) {
+        if (!d_frames[f]) return fail(ctx, H2Y_EINVAL, "frame %d is null", f);
+        if ((uintptr_t)d_frames[f] & 15u) return fail(ctx, H2Y_EINVAL, "frame %d is not 16-byte aligned", f);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    uint32_t off[3];
+    contiguous_planes(width, height, chroma_format_idc, off);
+    const hist_geom g = hist_geom_of(width, height, chroma_format_idc, bit_depth, full_range, gbr, bits, off);
+    const int per_launch = std::min(n_frames, H2Y_HISTOGRAM_FRAMES_PER_LAUNCH);
+    const hist_layout L = hist_layout_of(g.nbins, per_launch);
+    hist_frame *h;
+    rc = frame_table(ctx, n_frames, h);
+    if (!rc) rc = ensure(ctx, ctx->d_hist, ctx->hist_cap, L.total);
+    if (rc) return rc;
+    for (int f = 0; f < n_frames; f++) h[f].base = d_frames[f];
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_tab, h, (size_t)n_frames * sizeof(hist_frame), hipMemcpyHostToDevice, ctx->stream));
+    const hist_frame *frames = static_cast<const hist_frame *>(ctx->d_tab);
+    /* one launch at a time: its stats and bins come down before the next one reuses the workspace */
+    float ms = 0.f;
+    int launches = 0;
+    hipEvent_t *ev = ctx->b->ev[0];
+    for (int f0 = 0; f0 < n_frames; f0 += per_launch, launches++) {
+        const int nf = std::min(per_launch, n_frames - f0);
+        const hist_layout Ln = hist_layout_of(g.nbins, nf);
+        HIP_TRY(ctx, hipEventRecord(ev[0], ctx->stream));
+        rc = hist_enqueue(ctx, g, frames + f0, nf, ctx->d_hist);
+        if (rc) return rc;
+        HIP_TRY(ctx, hipEventRecord(ev[1], ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(out_stats + f0, ctx->d_hist + Ln.stats, (size_t)nf * sizeof(h2y_histogram_stats), hipMemcpyDeviceToHost,
+                                    ctx->stream));
+        if (out_bins)
+            HIP_TRY(ctx, hipMemcpyAsync(out_bins + (size_t)f0 * 3u * g.nbins, ctx->d_hist + Ln.bins, (size_t)nf * 3u * g.nbins * sizeof(uint32_t),
+                                        hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        float t = 0.f;
+        HIP_TRY(ctx, hipEventElapsedTime(&t, ev[0], ev[1]));
+        ms += t;
+    }
+    ctx->b->n_ev = 1;
+    ctx->last_ms = ms;
+    ctx->last_launches = launches;
+    ctx->last_name = "k_histogram";
+    ctx->last_variant = std::string("k_histogram<") + (chroma_format_idc == H2Y_CHROMA_420 ? "420" : "444") + "," +
+                        (h2y_histogram_lds(g.nbins) < (size_t)g.nbins * sizeof(uint32_t) ? "U16X2" : "U32") + ",bins=" +
+                        std::to_string(g.nbins) + ">";
+    return H2Y_OK;
+}
+
+/* The histogram's ring stage: per slot a device workspace of one frame (hist_layout), pinned stats and bins, and the slot's
+ * k_histogram table entry (the ring's frame) */
+struct hist_stage : ring_stage {
+    struct slot {
+        char *d = nullptr;
+        h2y_histogram_stats *h_stats = nullptr;
+        uint32_t *h_bins = nullptr;
+    };
+    std::vector<slot> ss;
+    hist_geom g{};
+    hist_frame *tab = nullptr;
+    int run(h2y_ctx *ctx, int k) override { return hist_enqueue(ctx, g, tab + k, 1, ss[k].d); }
+    int download(h2y_ctx *ctx, int k) override
+    {
+        const hist_layout L = hist_layout_of(g.nbins, 1);
+        HIP_TRY(ctx, hipMemcpyAsync(ss[k].h_stats, ss[k].d + L.stats, sizeof(h2y_histogram_stats), hipMemcpyDeviceToHost, ctx->s_d2h));
+        HIP_TRY(ctx, hipMemcpyAsync(ss[k].h_bins, ss[k].d + L.bins, (size_t)3u * g.nbins * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->s_d2h));
+        return H2Y_OK;
+    }
+};
+
+/* arm the open ring's frame, counted as bit_depth, full_range and gbr say */
+static int hist_arm(h2y_ctx *ctx, int bit_depth, int full_range, int gbr, int bits)
+{
+    const ring_frame &f = ctx->s_frame;
+    int rc = hist_check(ctx, f.width, f.height, f.chroma, bit_depth, full_range, gbr, bits);
+    if (rc) return rc;
+    auto st = std::make_unique<hist_stage>();
+    st->g = hist_geom_of(f.width, f.height, f.chroma, bit_depth, full_range, gbr, bits, f.off);
+    const hist_layout L = hist_layout_of(st->g.nbins, 1);
+    const int depth = (int)ctx->ss.size();
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::vector<hist_frame> tab(depth);
+    st->ss.resize(depth);
+    for (int k = 0; k < depth; k++) {
+        hist_stage::slot &s = st->ss[k];
+        st->dev_alloc(s.d, L.total);
+        st->pin_alloc(s.h_stats, sizeof(h2y_histogram_stats));
+        st->pin_alloc(s.h_bins, (size_t)3u * st->g.nbins * sizeof(uint32_t));
+        tab[k].base = frame_base(ctx, k);
+    }
+    st->table(st->tab, tab);
+    return stage_arm(ctx, STAGE_HISTOGRAM, std::move(st), "histogram");
+}
+
+int h2y_stream_histogram_ex(h2y_ctx *ctx, int bits, int bit_depth, int full_range, int gbr)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    if (ctx->s_stage[STAGE_HISTOGRAM]) return fail(ctx, H2Y_EINVAL, "the ring counts histograms already");
+    if (ctx->s_stage[STAGE_SCALE]) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that scales counts no histograms: count the written file instead");
+    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    const ring_frame &f = ctx->s_frame;
+    if (!f.depth && (bit_depth < 0 || full_range < 0 || gbr < 0))
+        return fail(ctx, H2Y_EINVAL, "a compare-only ring does not know its frames' bit depth and range: h2y_stream_histogram_ex");
+    const int depth = bit_depth >= 0 ? bit_depth : f.depth;
+    if (depth < 8 || depth > 16) return fail(ctx, H2Y_EINVAL, "bit_depth must be 8..16");
+    return hist_arm(ctx, depth, full_range >= 0 ? full_range : f.full_range, gbr >= 0 ? gbr : (int)f.gbr, bits ? bits : depth);
+}
+
+int h2y_stream_histogram(h2y_ctx *ctx, int bits) { return h2y_stream_histogram_ex(ctx, bits, -1, -1, -1); }
+
+int h2y_stream_histogram_result(h2y_ctx *ctx, h2y_histogram_stats *out_stats, uint32_t *out_bins)
+{
+    if (!ctx || !out_stats) return fail(ctx, H2Y_EINVAL, "null argument");
+    const hist_stage *st = ctx->streaming ? stage_of<hist_stage>(ctx, STAGE_HISTOGRAM) : nullptr;
+    if (!st) return fail(ctx, H2Y_EINVAL, "no stream open that counts histograms");
+    if (ctx->s_lent < 0) return fail(ctx, H2Y_EINVAL, "no output taken yet: h2y_stream_output first");
+    const hist_stage::slot &s = st->ss[ctx->s_lent];
+    *out_stats = *s.h_stats;
+    if (out_bins) memcpy(out_bins, s.h_bins, (size_t)3u * st->g.nbins * sizeof(uint32_t));
+    return H2Y_OK;
+}
+
+/* A ring that only counts: the slot's input is the frame's three planes, the device output unused */
+int h2y_histogram_stream_open(h2y_ctx *ctx, int width, int height, int chroma_format_idc, int bit_depth, int full_range, int gbr, int bits,
+                              int depth)
+{
+    int rc = ring_may_open(ctx);
+    if (!rc) rc = hist_check(ctx, width, height, chroma_format_idc, bit_depth, full_range, gbr, bits);
+    if (!rc) rc = open_planes_ring(ctx, width, height, chroma_format_idc, bit_depth, full_range, gbr, 0, depth);
+    if (rc) return rc;
+    rc = hist_arm(ctx, bit_depth, full_range, gbr, bits);
+    if (rc) stream_free(ctx);
+    return rc;
+}
+
+/* ---- scaling: the Lanczos resampler of include/hdr2yuv_hip.h ----------------------------------------------------------------- */
+
+static double scale_sinc(double x) { return x == 0.0 ? 1.0 : sin(M_PI * x) / (M_PI * x); }
+
+/* one axis' table as the header defines it, in binary64; rc H2Y_EUNSUPPORTED for a row of sum |q| > 32767 */
+static int scale_axis_table(int s, int d, int a, int32_t *first, int32_t *count, int16_t *coef, int *max_taps)
+{
+    const double f = s > d ? (double)s / (double)d : 1.0, r = (double)a * f;
+    int most = 0;
+    for (int o = 0; o < d; o++) {
+        const double c = (((double)o + 0.5) * (double)s) / (double)d - 0.5;
+        int idx[H2Y_SCALE_TAPS + 2];
+        double w[H2Y_SCALE_TAPS + 2], S = 0.0;
+        int n = 0;
+        for (int i = (int)ceil(c - r), hi = (int)floor(c + r); i <= hi; i++) {
+            if (!(fabs((double)i - c) < r)) continue;
+            if (n == H2Y_SCALE_TAPS) return H2Y_EUNSUPPORTED;
+            const double t = ((double)i - c) / f;
+            idx[n] = i;
+            w[n] = scale_sinc(t) * scale_sinc(t / (double)a);
+            S += w[n];
+            n++;
+        }
+        if (n == 0) return H2Y_EUNSUPPORTED;
+        int q[H2Y_SCALE_TAPS], sum = 0, big = 0;
+        for (int k = 0; k < n; k++) {
+            q[k] = (int)rint(w[k] * 16384.0 / S);
+            sum += q[k];
+            if (q[k] > q[big]) big = k;
+        }
+        q[big] += 16384 - sum;
+        const int lo = idx[0] < 0 ? 0 : idx[0] > s - 1 ? s - 1 : idx[0];
+        int folded[H2Y_SCALE_TAPS] = {0}, m = 0, mag = 0;
+        for (int k = 0; k < n; k++) {
+            const int i = idx[k] < 0 ? 0 : idx[k] > s - 1 ? s - 1 : idx[k];
+            folded[i - lo] += q[k];
+            m = i - lo + 1;
+        }
+        for (int k = 0; k < m; k++) mag += folded[k] < 0 ? -folded[k] : folded[k];
+        if (mag > 32767) return H2Y_EUNSUPPORTED;
+        first[o] = lo;
+        count[o] = m;
+        for (int k = 0; k < H2Y_SCALE_TAPS; k++) coef[(size_t)o * H2Y_SCALE_TAPS + k] = (int16_t)(k < m ? folded[k] : 0);
+        most = m > most ? m : most;
+    }
+    if (max_taps) *max_taps = most;
+    return H2Y_OK;
+}
+
+static bool scale_axis_ok(int s, int d) { return s >= 1 && d >= 1 && s <= 10000 && d <= 10000 && s <= 4 * d && d <= 4 * s; }
+
+int h2y_scale_taps(int src, int dst, int a, int32_t *first, int32_t *count, int16_t *coef, int *max_taps)
+{
+    if (!first || !count || !coef) return fail(nullptr, H2Y_EINVAL, "null table");
+    if (a < 2 || a > 4) return fail(nullptr, H2Y_EINVAL, "a (lobes) must be 2, 3 or 4");
+    if (!scale_axis_ok(src, dst)) return fail(nullptr, H2Y_EINVAL, "sizes must be 1..10000 with a ratio in [1/4, 4]");
+    const int rc = scale_axis_table(src, dst, a, first, count, coef, max_taps);
+    if (rc) return fail(nullptr, rc, "a table row's coefficients do not fit (sum |q| > 32767)");
+    return H2Y_OK;
+}
+
+size_t h2y_scale_frame_bytes(int width, int height, int chroma_format_idc)
+{
+    if (width < 1 || height < 1 || width > 10000 || height > 10000) return 0;
+    if (chroma_format_idc == H2Y_CHROMA_444) return (size_t)width * height * 3u * sizeof(uint16_t);
+    if (chroma_format_idc != H2Y_CHROMA_420) return 0;
+    return ((size_t)width * height + 2u * (size_t)(width >> 1) * (height >> 1)) * sizeof(uint16_t);
+}
+
+static int scale_check(h2y_ctx *ctx, int sw, int sh, int dw, int dh, int chroma, int bit_depth, int full_range, int gbr, int a)
+{
+    if (chroma == 2) return fail(ctx, H2Y_EUNSUPPORTED, "chroma_format_idc 2 (4:2:2) is not scaled");
+    if (chroma != H2Y_CHROMA_420 && chroma != H2Y_CHROMA_444) return fail(ctx, H2Y_EINVAL, "chroma_format_idc must be 1 or 3");
+    if (sw < 2 || sh < 2 || dw < 2 || dh < 2 || sw > 10000 || sh > 10000 || dw > 10000 || dh > 10000)
+        return fail(ctx, H2Y_EINVAL, "scaling: widths and heights must be 2..10000");
+    if (chroma == H2Y_CHROMA_420 && ((sw | sh | dw | dh) & 1)) return fail(ctx, H2Y_EINVAL, "scaling 4:2:0: widths and heights must be even");
+    if (!scale_axis_ok(sw, dw) || !scale_axis_ok(sh, dh)) return fail(ctx, H2Y_EINVAL, "scaling: each axis ratio must be in [1/4, 4]");
+    if (bit_depth < 8 || bit_depth > 16) return fail(ctx, H2Y_EINVAL, "bit_depth must be 8..16");
+    if ((full_range != 0 && full_range != 1) || (gbr != 0 && gbr != 1)) return fail(ctx, H2Y_EINVAL, "full_range and gbr must be 0 or 1");
+    if (a < 2 || a > 4) return fail(ctx, H2Y_EINVAL, "a (lobes) must be 2, 3 or 4");
+    return H2Y_OK;
+}
+
+/* k_scale's geometry with its tables still on the host: blob is what goes to the device, at[p][axis][0..2] where plane p's
+ * first, count and coef of that axis lie in it (4:4:4: one pair of tables serves the three planes) */
+struct scale_host {
+    scale_geom g{};
+    std::vector<char> blob;
+    size_t at[3][2][3]{};
+};
+
+static int scale_build(h2y_ctx *ctx, int sw, int sh, int dw, int dh, int chroma, int bit_depth, int full_range, int gbr, int a,
+                       const uint32_t src_off[3], const uint32_t dst_off[3], scale_host &H)
+{
+    const bool sub = chroma == H2Y_CHROMA_420;
+    const clip_limits c = make_clip(bit_depth, full_range);
+    size_t kind_at[2][2][3];
+    for (int kind = 0; kind < (sub ? 2 : 1); kind++)
+        for (int axis = 0; axis < 2; axis++) {
+            const int s = (axis ? sh : sw) >> kind, d = (axis ? dh : dw) >> kind;
+            const size_t ib = ((size_t)d * sizeof(int32_t) + 15) & ~(size_t)15, cb = (size_t)d * H2Y_SCALE_TAPS * sizeof(int16_t);
+            const size_t base = H.blob.size();
+            H.blob.resize(base + 2 * ib + cb);
+            kind_at[kind][axis][0] = base, kind_at[kind][axis][1] = base + ib, kind_at[kind][axis][2] = base + 2 * ib;
+            const int rc = scale_axis_table(s, d, a, reinterpret_cast<int32_t *>(&H.blob[base]), reinterpret_cast<int32_t *>(&H.blob[base + ib]),
+                                            reinterpret_cast<int16_t *>(&H.blob[base + 2 * ib]), nullptr);
+            if (rc) return fail(ctx, rc, "scaling %d -> %d: a table row's coefficients do not fit (sum |q| > 32767)", s, d);
+        }
+    uint32_t h_rows = 1, seg_max = 1;
+    for (int p = 0; p < 3; p++) {
+        const int kind = p && sub ? 1 : 0;
+        scale_plane &P = H.g.p[p];
+        P.sw = (uint32_t)(sw >> kind), P.sh = (uint32_t)(sh >> kind), P.dw = (uint32_t)(dw >> kind), P.dh = (uint32_t)(dh >> kind);
+        P.src_off = src_off[p], P.dst_off = dst_off[p];
+        P.tiles_x = (P.dw + H2Y_SCALE_TILE_W - 1) / H2Y_SCALE_TILE_W;
+        P.tiles = P.tiles_x * ((P.dh + H2Y_SCALE_TILE_H - 1) / H2Y_SCALE_TILE_H);
+        const bool luma_like = p == 0 || gbr;
+        P.lo = (int32_t)(luma_like ? c.minVR : c.minVRC);
+        P.hi = (int32_t)(luma_like ? c.maxVR : c.maxVRC);
+        for (int axis = 0; axis < 2; axis++)
+            for (int k = 0; k < 3; k++) H.at[p][axis][k] = kind_at[kind][axis][k];
+        /* the most source columns and rows one tile reads: what the kernel's LDS must hold */
+        for (int axis = 0; axis < 2; axis++) {
+            const int32_t *first = reinterpret_cast<const int32_t *>(&H.blob[H.at[p][axis][0]]);
+            const int32_t *count = reinterpret_cast<const int32_t *>(&H.blob[H.at[p][axis][1]]);
+            const uint32_t d = axis ? P.dh : P.dw, step = axis ? H2Y_SCALE_TILE_H : H2Y_SCALE_TILE_W;
+            for (uint32_t o0 = 0; o0 < d; o0 += step) {
+                const uint32_t o1 = std::min(d, o0 + step) - 1;
+                const uint32_t span = (uint32_t)(first[o1] + count[o1] - first[o0]);
+                if (axis) h_rows = std::max(h_rows, span);
+                else seg_max = std::max(seg_max, span);
+            }
+        }
+    }
+    H.g.h_rows = h_rows;
+    H.g.src_cols = (seg_max + 7u + 7u) & ~7u;
+    if (h2y_scale_lds(H.g) > 64u * 1024u) return fail(ctx, H2Y_EUNSUPPORTED, "scaling: a tile needs %zu bytes of LDS", h2y_scale_lds(H.g));
+    return H2Y_OK;
+}
+
+/* the tables' addresses once the blob lies at d_base */
+static void scale_bind(scale_host &H, const char *d_base)
+{
+    for (int p = 0; p < 3; p++) {
+        scale_axis *ax[2] = {&H.g.p[p].h, &H.g.p[p].v};
+        for (int axis = 0; axis < 2; axis++) {
+            ax[axis]->first = reinterpret_cast<const int32_t *>(d_base + H.at[p][axis][0]);
+            ax[axis]->count = reinterpret_cast<const int32_t *>(d_base + H.at[p][axis][1]);
+            ax[axis]->coef = reinterpret_cast<const int16_t *>(d_base + H.at[p][axis][2]);
+        }
+    }
+}
+
+static int scale_grid(const h2y_ctx *ctx, const scale_geom &g, int n_frames)
+{
+    return unit_grid(ctx, (uint64_t)n_frames * (g.p[0].tiles + g.p[1].tiles + g.p[2].tiles));
+}
+
+static std::string scale_variant(int chroma, int a)
+{
+    return std::string("k_scale<") + (chroma == H2Y_CHROMA_420 ? "420" : "444") + ",lanczos" + std::to_string(a) + ">";
+}
+
+int h2y_scale_batch(h2y_ctx *ctx, int src_w, int src_h, int dst_w, int dst_h, int chroma_format_idc, int bit_depth, int full_range,
+                    int gbr, int a, int n_frames, const uint16_t *const *d_src, uint16_t *const *d_dst)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
+    int rc = scale_check(ctx, src_w, src_h, dst_w, dst_h, chroma_format_idc, bit_depth, full_range, gbr, a);
+    if (rc) return rc;
+    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
+    if (!d_src || !d_dst) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
+    for (int f = 0; f < n_frames; f++) {
+        if (!d_src[f] || !d_dst[f]) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is null", f);
+        if (((uintptr_t)d_src[f] | (uintptr_t)d_dst[f]) & 15u) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is not 16-byte aligned", f);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    uint32_t src_off[3], dst_off[3];
+    contiguous_planes(src_w, src_h, chroma_format_idc, src_off);
+    contiguous_planes(dst_w, dst_h, chroma_format_idc, dst_off);
+    scale_host H;
+    rc = scale_build(ctx, src_w, src_h, dst_w, dst_h, chroma_format_idc, bit_depth, full_range, gbr, a, src_off, dst_off, H);
+    if (rc) return rc;
+    scale_frame *h;
+    rc = frame_table(ctx, n_frames, h);
+    if (!rc) rc = ensure(ctx, ctx->d_scale_tabs, ctx->scale_tabs_cap, H.blob.size());
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpy(ctx->d_scale_tabs, H.blob.data(), H.blob.size(), hipMemcpyHostToDevice));
+    scale_bind(H, ctx->d_scale_tabs);
+    for (int f = 0; f < n_frames; f++) h[f] = scale_frame{d_src[f], d_dst[f]};
+    rc = timed_launches(ctx, h, n_frames, H2Y_SCALE_FRAMES_PER_LAUNCH, "k_scale", [&](const scale_frame *frames, int, int nf) {
+        return h2y_launch_scale(scale_grid(ctx, H.g, nf), ctx->stream, H.g, frames, nf);
+    });
+    if (rc) return rc;
+    ctx->last_variant = scale_variant(chroma_format_idc, a);
+    return H2Y_OK;
+}
+
+/* Scaling's ring stage: k_scale's geometry, its tables on the device and each slot's table entry.  On a ring that produces its
+ * frame the stage scales it into a frame of its own, on the device and pinned, which goes down and is handed out in the
+ * produced frame's place; on a ring without a producer it scales the slot's input into its output. */
+struct scale_stage : ring_stage {
+    struct slot {
+        uint16_t *d = nullptr, *h = nullptr;
+    };
+    std::vector<slot> ss;
+    scale_geom g{};
+    char *tabs = nullptr;
+    scale_frame *tab = nullptr;
+    size_t bytes = 0; /* of the scaled frame */
+    int run(h2y_ctx *ctx, int k) override
+    {
+        HIP_TRY(ctx, h2y_launch_scale(scale_grid(ctx, g, 1), ctx->stream, g, tab + k, 1));
+        return H2Y_OK;
+    }
+    int download(h2y_ctx *ctx, int k) override
+    {
+        if (ss[k].d) HIP_TRY(ctx, hipMemcpyAsync(ss[k].h, ss[k].d, bytes, hipMemcpyDeviceToHost, ctx->s_d2h));
+        return H2Y_OK;
+    }
+};
+
+/* arm the open ring's frame, scaled to dw x dh */
+static int scale_arm(h2y_ctx *ctx, int dw, int dh, int a)
+{
+    const ring_frame &f = ctx->s_frame;
+    uint32_t dst_off[3];
+    contiguous_planes(dw, dh, f.chroma, dst_off);
+    scale_host H;
+    int rc = scale_build(ctx, f.width, f.height, dw, dh, f.chroma, f.depth, f.full_range, f.gbr, a, f.off, dst_off, H);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    auto st = std::make_unique<scale_stage>();
+    scale_stage *sc = st.get();
+    sc->bytes = h2y_scale_frame_bytes(dw, dh, f.chroma);
+    const int depth = (int)ctx->ss.size();
+    std::vector<scale_frame> tab(depth);
+    sc->ss.resize(depth);
+    sc->dev_alloc(sc->tabs, H.blob.size());
+    for (int k = 0; k < depth; k++) {
+        if (!f.in_input) {
+            sc->dev_alloc(sc->ss[k].d, sc->bytes);
+            sc->pin_alloc(sc->ss[k].h, sc->bytes);
+        }
+        tab[k] = scale_frame{frame_base(ctx, k), f.in_input ? ctx->ss[k].d_out : sc->ss[k].d};
+    }
+    if (sc->err == hipSuccess) sc->err = hipMemcpy(sc->tabs, H.blob.data(), H.blob.size(), hipMemcpyHostToDevice);
+    sc->table(sc->tab, tab);
+    scale_bind(H, sc->tabs);
+    sc->g = H.g;
+    rc = stage_arm(ctx, STAGE_SCALE, std::move(st), "scaling");
+    if (rc || f.in_input) return rc;
+    ring_frame_stays(ctx);
+    for (int k = 0; k < depth; k++) ctx->ss[k].result = sc->ss[k].h;
+    return H2Y_OK;
+}
+
+int h2y_stream_scale(h2y_ctx *ctx, int dst_w, int dst_h, int a)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    if (ctx->s_kind != h2y_ctx::RING_FORWARD) return fail(ctx, H2Y_EINVAL, "only a forward ring is armed for scaling");
+    if (ctx->s_stage[STAGE_SCALE]) return fail(ctx, H2Y_EINVAL, "the ring scales already");
+    if (ctx->s_stage[STAGE_COMPARE] || ctx->s_stage[STAGE_HISTOGRAM] || ctx->s_stage[STAGE_SSIM])
+        return fail(ctx, H2Y_EUNSUPPORTED, "a ring armed for comparison, histograms or SSIM is not scaled: compare or count the written file instead");
+    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    const ring_frame &f = ctx->s_frame;
+    int rc = scale_check(ctx, f.width, f.height, dst_w, dst_h, f.chroma, f.depth, f.full_range, f.gbr, a);
+    if (rc) return rc;
+    return scale_arm(ctx, dst_w, dst_h, a);
+}
+
+/* A ring that only scales: the slot's input is the frame's three planes, its output the scaled frame */
+int h2y_scale_stream_open(h2y_ctx *ctx, int src_w, int src_h, int chroma_format_idc, int bit_depth, int full_range, int gbr, int dst_w,
+                          int dst_h, int a, int depth)
+{
+    int rc = ring_may_open(ctx);
+    if (!rc) rc = scale_check(ctx, src_w, src_h, dst_w, dst_h, chroma_format_idc, bit_depth, full_range, gbr, a);
+    if (!rc) rc = open_planes_ring(ctx, src_w, src_h, chroma_format_idc, bit_depth, full_range, gbr,
+                                   h2y_scale_frame_bytes(dst_w, dst_h, chroma_format_idc), depth);
+    if (rc) return rc;
+    rc = scale_arm(ctx, dst_w, dst_h, a);
+    if (rc) stream_free(ctx);
+    return rc;
+}
