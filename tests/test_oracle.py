@@ -181,3 +181,42 @@ def test_upsampler_restatement_equals_reference(oracle, ref):
                     a = oracle.up444(src, w, h, alg, lo, hi)
                     b = ref.up444(src, w, h, alg, lo, hi)
                     assert _same(a, b), (w, h, depth, alg, lo, hi, _differing(a, b))
+
+
+def test_saturated_pictures_equal_reference(oracle, ref):
+    """The pictures of tests/chroma_pictures.py (corners of the RGB cube changing every one to three pixels: both stages' sums of
+    the FIR leave their clamps' ranges, the box average sits on its rounding ties): convert_frame, the two subsamplers on the
+    oracle's own 4:4:4 planes, and the upsampler on two-level chroma planes, against the reference's object code.  The other
+    tests here pin the oracle on narrow-chroma content only; tests/test_chroma_extremes.py relies on this one."""
+    import sys
+
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import chroma_pictures as cp
+
+    w, h = 64, 32
+    configs = ((ob.MATRIX_BT2020NC, 10, 0), (ob.MATRIX_BT709, 12, 0), (ob.MATRIX_YDZDX, 14, 0), (ob.MATRIX_BT2020NC, 16, 0), (ob.MATRIX_BT709, 16, 1))
+    for name in ("corners2", "checker3_by", "steps_by", "steps_rc"):
+        planes = cp.planes_f32(name, w, h)
+        _, fl, ce = oracle.stats_f32(planes)
+        for (m, dep, fr) in configs:
+            for res in (1, 0):
+                d = ob.make_desc(w, h, dst_depth=dep, dst_matrix=m, resampler=res, full_range=fr)
+                assert _same(oracle.convert_frame(d, planes), ref.convert_frame(d, planes)), (name, m, dep, fr, res)
+            t = oracle.matrix_convert(d, planes, fl, ce, dep).reshape(3, h, w)
+            for c in (1, 2):
+                for fir in (True, False):
+                    a, b = oracle.sub420(t[c], dep, fir), ref.sub420(t[c], dep, fir)
+                    assert _same(a, b), (name, m, dep, fr, c, fir, _differing(a, b))
+        # 16-bit integer input, the FIR at 16 bits, then write_yuv's shift
+        u16 = cp.planes_u16(name, w, h)
+        for dep in (10, 16):
+            d = ob.make_desc(w, h, sample=ob.SAMPLE_U16, src_depth=16, dst_depth=dep, src_transfer=16, dst_transfer=16, dst_matrix=ob.MATRIX_BT2020NC, resampler=1)
+            assert _same(oracle.convert_frame(d, u16), ref.convert_frame(d, u16)), (name, dep)
+        for depth in (10, 12, 16):
+            maxcv = (1 << depth) - 1
+            for (lo, hi) in ((0, maxcv), (16 << (depth - 8), 240 << (depth - 8))):
+                for levels in (cp.inside_levels(lo, hi), (0, maxcv)):
+                    for src in cp.chroma_planes(name, w // 2, h // 2, *levels):
+                        for alg in (0, 1):
+                            a, b = oracle.up444(src, w, h, alg, lo, hi), ref.up444(src, w, h, alg, lo, hi)
+                            assert _same(a, b), (name, depth, lo, hi, levels, alg, _differing(a, b))
