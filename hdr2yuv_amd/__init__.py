@@ -37,6 +37,7 @@ from .api import (  # noqa: F401
     desc_check,
     exr_unpack,
     frame_bytes,
+    gamut_matrix,
     library_path,
     load_library,
     make_desc,

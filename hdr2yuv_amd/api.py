@@ -38,6 +38,7 @@ EXPORTS = [
     "h2y_histogram_stream_open", "h2y_ssim_batch", "h2y_stream_ssim", "h2y_stream_ssim_result",
     "h2y_light_batch", "h2y_stream_light", "h2y_stream_light_result",
     "h2y_scale_taps", "h2y_scale_frame_bytes", "h2y_scale_batch", "h2y_stream_scale", "h2y_scale_stream_open",
+    "h2y_gamut_matrix", "h2y_gamut_batch", "h2y_stream_gamut",
 ]
 
 COMPARE_FRAMES_PER_LAUNCH = 64
@@ -45,6 +46,7 @@ HISTOGRAM_FRAMES_PER_LAUNCH = 64
 SSIM_FRAMES_PER_LAUNCH = 64
 LIGHT_FRAMES_PER_LAUNCH = 64
 SCALE_FRAMES_PER_LAUNCH = 64
+GAMUT_FRAMES_PER_LAUNCH = 64
 SCALE_TAPS = 32  # coefficients per row of scale_taps' table
 
 
@@ -391,6 +393,12 @@ def load_library():
     L.h2y_stream_scale.restype = C.c_int
     L.h2y_scale_stream_open.argtypes = [C.c_void_p] + [C.c_int] * 10
     L.h2y_scale_stream_open.restype = C.c_int
+    L.h2y_gamut_matrix.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_char_p)]
+    L.h2y_gamut_matrix.restype = C.c_int
+    L.h2y_gamut_batch.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.h2y_gamut_batch.restype = C.c_int
+    L.h2y_stream_gamut.argtypes = [C.c_void_p] + [C.c_int] * 3
+    L.h2y_stream_gamut.restype = C.c_int
     L.h2y_stream_open.argtypes = [C.c_void_p, C.POINTER(H2YDesc), C.c_int]
     L.h2y_stream_input.restype = C.c_int
     L.h2y_stream_input.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
@@ -526,6 +534,17 @@ def scale_taps(src: int, dst: int, a: int = 3):
     if rc != H2Y_OK:
         raise H2YError(rc, (lib.h2y_last_error(None) or b"").decode())
     return first, count, coef, most.value
+
+
+def gamut_matrix(src_primaries: int, dst_primaries: int) -> np.ndarray:
+    """h2y_gamut_matrix (host only, no device): the float32 (3, 3) matrix NPM(dst)^-1 NPM(src) on (R, G, B) columns, every entry
+    the exact value rounded to nearest.  Raises H2YError (EUNSUPPORTED: primaries it does not know; EINVAL: equal chromaticities)."""
+    m = np.zeros(9, dtype=np.float32)
+    why = C.c_char_p()
+    rc = load_library().h2y_gamut_matrix(int(src_primaries), int(dst_primaries), m.ctypes.data_as(C.POINTER(C.c_float)), C.byref(why))
+    if rc != H2Y_OK:
+        raise H2YError(rc, (why.value or b"").decode())
+    return m.reshape(3, 3)
 
 
 def scale_frame_bytes(width: int, height: int, chroma: int) -> int:
@@ -786,7 +805,27 @@ class Context:
         pd = (C.c_void_p * max(n, 1))(*[self._ptr(x) for x in frames_dst])
         self._check(self.lib.h2y_scale_batch(self.h, src_w, src_h, dst_w, dst_h, chroma, bit_depth, full_range, gbr, a, n, ps, pd))
 
+    def gamut_batch(self, width, height, sample, src_primaries, dst_primaries, clip, frames_src, frames_dst=None) -> None:
+        """k_gamut on device frames (frames_src[f] = three device planes G, B, R of float or half samples, 16-byte aligned):
+        frames_dst[f] receives them converted from src_primaries to dst_primaries; frames_dst None: in place."""
+        frames_dst = frames_src if frames_dst is None else frames_dst
+        n = len(frames_src)
+        if len(frames_dst) != n:
+            raise ValueError("frames_src and frames_dst differ in length")
+        ins = (C.c_void_p * max(3 * n, 1))()
+        outs = (C.c_void_p * max(3 * n, 1))()
+        for f in range(n):
+            for c in range(3):
+                ins[3 * f + c] = self._ptr(frames_src[f][c])
+                outs[3 * f + c] = self._ptr(frames_dst[f][c])
+        self._check(self.lib.h2y_gamut_batch(self.h, width, height, sample, src_primaries, dst_primaries, clip, n, ins, outs))
+
     # ---- host <-> device pipeline -----------------------------------------------------------
+    def stream_gamut(self, src_primaries, dst_primaries, clip=1) -> None:
+        """Arm an open forward ring of float or half planes (plain, DPX or EXR): every slot's decoded planes are converted in
+        place from src_primaries to dst_primaries before pic_stats and the conversion (h2y_stream_gamut)."""
+        self._check(self.lib.h2y_stream_gamut(self.h, src_primaries, dst_primaries, clip))
+
     def stream_scale(self, dst_w, dst_h, a=3) -> None:
         """Arm an open forward ring (plain, DPX, TIFF or EXR): stream_output then returns the frame scaled to dst_w x dst_h."""
         self._check(self.lib.h2y_stream_scale(self.h, dst_w, dst_h, a))

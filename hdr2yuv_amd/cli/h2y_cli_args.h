@@ -59,6 +59,15 @@
  * --scale_only 1 (an addition): a .yuv (4:2:0 or 4:4:4) or .rgb source resampled into a destination of the same extension, no
  *             conversion; depth, chroma format and range are the source's, read as --histogram_only reads them; the destination
  *             size is --dst_pic_width / --dst_pic_height.
+ * --gamut_convert 1 [--gamut_clip 0|1] (an addition; the reference's matrix_to_primaries() is empty, convert.cpp:1991, and the two
+ *             colour_primaries values only pick a branch of matrix_convert()): the decoded source planes are converted on the device
+ *             from --src_colour_primaries to --dst_colour_primaries, in linear light, before the unchanged forward conversion
+ *             (include/hdr2yuv_hip.h states the matrix and every rounding); results that are not above 0 are clipped to +0.0 unless
+ *             --gamut_clip 0.  On the forward flow from .f32, .f16, .exr and .dpx to .yuv, with or without --dst_filename, beside
+ *             --content_light, --ref_filename, --histogram, --ssim and --scale; neither primaries flag changes what it did.  Refused
+ *             (exit 1, also under --dry_run): a value other than 0 or 1, --gamut_clip without --gamut_convert 1, a source transfer
+ *             other than 8 (LINEAR), a source matrix other than 0 (G,B,R), primaries other than 1, 8, 9, 10 and 12 or a pair of equal
+ *             chromaticities, .rgb, .tiff and .yuv input, the .yuv -> RGB flow, --compare_only, --histogram_only and --scale_only.
  * Only user_args_t.chroma_resampler_type has no defined default there (never initialised): FIR here, as in
  * make.sh's example.  The reference calls exit(0) on its argument errors; this program returns 1.
  */
@@ -102,6 +111,9 @@ struct cli_args {
     /* --content_light 1: MaxCLL / MaxFALL of the forward flow */
     int light = 0;
     bool light_given = false;
+    /* --gamut_convert 1: the source planes go from the source's to the destination's primaries; --gamut_clip (1 by default) */
+    int gamut = 0, gamut_clip = 1;
+    bool gamut_given = false, gamut_clip_given = false;
     /* the histogram: --histogram FILE, --histogram_bits (0: the counted frames' depth), --histogram_only, --check_range; what is
      * counted, resolved by cli_resolve_histogram: depth, range, G,B,R limits, chroma format */
     const char *hist = nullptr;
@@ -168,6 +180,9 @@ static inline void cli_help()
            "  totals into FILE; exit status 4 on a sample outside the legal range), [--histogram_only 1] (--src_filename, no conversion)\n"
            "  content light: [--content_light 1] (MaxCLL and MaxFALL of a conversion to PQ, per frame and for the run; without\n"
            "  --dst_filename nothing is written)\n"
+           "  primaries: [--gamut_convert 1 [--gamut_clip 0|1]] (float or half G,B,R source planes in linear light converted from\n"
+           "  --src_colour_primaries to --dst_colour_primaries on the GPU before the conversion; 1 BT.709, 8 / 9 BT.2020, 12 P3-D65,\n"
+           "  10 XYZ; what is not above 0 is clipped to 0 unless --gamut_clip 0)\n"
            "  scaling: [--scale 1 [--scale_taps A]] (with --dst_pic_width / --dst_pic_height: every .yuv frame resampled on the GPU by\n"
            "  an exact Lanczos filter of A = 2, 3 or 4 lobes, 3 by default; each axis ratio within 1/4 .. 4), [--scale_only 1] (a .yuv or\n"
            "  .rgb source into a destination of the same extension, no conversion)\n"
@@ -197,6 +212,8 @@ static inline void cli_parse(cli_args &a, int argc, char **argv)
         else if (is("--compare_only")) a.compare_only = atoi(val());
         else if (is("--ssim")) { a.ssim = atoi(val()); a.ssim_given = true; }
         else if (is("--content_light")) { a.light = atoi(val()); a.light_given = true; }
+        else if (is("--gamut_convert")) { a.gamut = atoi(val()); a.gamut_given = true; }
+        else if (is("--gamut_clip")) { a.gamut_clip = atoi(val()); a.gamut_clip_given = true; }
         else if (is("--histogram")) a.hist = val();
         else if (is("--histogram_bits")) { a.hist_bits = atoi(val()); a.hist_bits_given = true; }
         else if (is("--histogram_only")) a.hist_only = atoi(val());
@@ -373,8 +390,10 @@ static inline int cli_resolve_ssim(cli_args &a);
 static inline int cli_resolve_light(cli_args &a);
 static inline int cli_resolve_scale_only(cli_args &a);
 static inline int cli_resolve_scale(cli_args &a);
+static inline int cli_resolve_gamut(cli_args &a, int src_matrix_arg);
 static inline int cli_resolve(cli_args &a)
 {
+    const int src_matrix_arg = a.in.matrix_coeffs; /* as given: the float readers force G,B,R on the input picture below */
     int arg_errors = a.hist_only    ? cli_resolve_histogram_only(a)
                      : a.compare_only ? cli_resolve_compare(a)
                      : a.scale_only   ? cli_resolve_scale_only(a)
@@ -383,6 +402,7 @@ static inline int cli_resolve(cli_args &a)
     if (a.ssim_given) arg_errors += cli_resolve_ssim(a);
     if (a.light_given) arg_errors += cli_resolve_light(a);
     if (a.scale_given || a.scale_only || a.scale_taps_given) arg_errors += cli_resolve_scale(a);
+    if (a.gamut_given || a.gamut_clip_given) arg_errors += cli_resolve_gamut(a, src_matrix_arg);
     return arg_errors;
 }
 
@@ -522,6 +542,59 @@ static inline int cli_resolve_light(cli_args &a)
     }
     printf("content_light_from: src_transfer_characteristics %d -> PQ, G,B,R, floor and ceiling %s\n", a.in.transfer_characteristics,
            "of each frame's pic_stats");
+    return 0;
+}
+
+/* --gamut_convert / --gamut_clip: the forward flow's float or half G,B,R planes in linear light, between two sets of primaries the
+ * library converts (src_matrix_arg: --src_matrix_coeffs as given); prints the matrix; returns the number of argument errors */
+static inline int cli_resolve_gamut(cli_args &a, int src_matrix_arg)
+{
+    printf("gamut_convert: %d\ngamut_clip: %d%s\n", a.gamut, a.gamut_clip, a.gamut_clip_given ? "" : " (default)");
+    if (a.gamut != 0 && a.gamut != 1) {
+        printf("WARNING: gamut_convert(%d) not 0 or 1\n", a.gamut);
+        return 1;
+    }
+    if (a.gamut_clip != 0 && a.gamut_clip != 1) {
+        printf("WARNING: gamut_clip(%d) not 0 or 1\n", a.gamut_clip);
+        return 1;
+    }
+    if (!a.gamut) {
+        if (a.gamut_clip_given) { printf("WARNING: --gamut_clip needs --gamut_convert 1\n"); return 1; }
+        return 0;
+    }
+    if (a.compare_only || a.hist_only || a.scale_only) {
+        printf("WARNING: --gamut_convert 1 converts a conversion's source: not with --%s 1\n",
+               a.compare_only ? "compare_only" : a.hist_only ? "histogram_only" : "scale_only");
+        return 1;
+    }
+    if (a.inverse) {
+        printf("WARNING: --gamut_convert 1 converts the forward flow's source (to .yuv), not the .yuv -> RGB flow\n");
+        return 1;
+    }
+    if (a.in_type != CLI_IN_F32 && a.in_type != CLI_IN_F16 && a.in_type != CLI_IN_EXR && a.in_type != CLI_IN_DPX) {
+        printf("WARNING: --gamut_convert 1 converts float or half planes (.f32, .f16, .exr, .dpx input), not .%s input\n",
+               a.in_type == CLI_IN_SYNTH ? "(synthetic)" : cli_ext_of(a.src));
+        return 1;
+    }
+    if (a.in.transfer_characteristics != H2Y_TRANSFER_LINEAR) {
+        printf("WARNING: --gamut_convert 1 converts linear light: src_transfer_characteristics(%d) is not %d\n",
+               a.in.transfer_characteristics, H2Y_TRANSFER_LINEAR);
+        return 1;
+    }
+    if (src_matrix_arg != H2Y_MATRIX_GBR) { /* the readers would override it: a source called Y'CbCr is not one to convert as R, G, B */
+        printf("WARNING: --gamut_convert 1 needs a G,B,R source: src_matrix_coeffs(%d) is not %d\n", src_matrix_arg, H2Y_MATRIX_GBR);
+        return 1;
+    }
+    float m[9];
+    const char *why = nullptr;
+    if (h2y_gamut_matrix(a.in.colour_primaries, a.out.colour_primaries, m, &why)) {
+        printf("WARNING: --gamut_convert 1: src_colour_primaries(%d) -> dst_colour_primaries(%d): %s\n", a.in.colour_primaries,
+               a.out.colour_primaries, why);
+        return 1;
+    }
+    printf("gamut_matrix:");
+    for (int i = 0; i < 9; i++) printf(" %.9g", m[i]);
+    printf("\n");
     return 0;
 }
 

@@ -73,6 +73,12 @@
  * arms its ring (h2y_stream_scale), so the frame that comes down is the converted frame resampled on the device to the destination
  * size (include/hdr2yuv_hip.h states the filter); frame k is written at `size of the file at start + k x scaled frame bytes`.
  * --scale_only 1 resamples a .yuv or .rgb source through a scale-only ring (h2y_scale_stream_open) into a file of the same layout.
+ *
+ * Primaries (--gamut_convert 1 [--gamut_clip 0|1] on the forward flow from .f32, .f16, .exr and .dpx; h2y_cli_args.h): each GPU thread
+ * arms its ring (h2y_stream_gamut) with --src_colour_primaries and --dst_colour_primaries, so every slot's decoded planes are
+ * converted in place on the device before pic_stats and the conversion: the run writes the bytes it would write had the source
+ * held the converted planes, and --content_light beside it measures the converted light.  The banner carries gamut_convert:,
+ * gamut_clip: and the nine entries of gamut_matrix: as "%.9g".
  */
 #include <algorithm>
 #include <array>
@@ -521,6 +527,7 @@ static void run_block(const cli_args &a, const h2y_desc &d, const std::vector<dp
     if (a.ssim && h2y_stream_ssim(ctx, -1)) return fail(h2y_last_error(ctx));
     if (hist->on && h2y_stream_histogram(ctx, a.hist_bits)) return fail(h2y_last_error(ctx));
     if (a.light && h2y_stream_light(ctx)) return fail(h2y_last_error(ctx));
+    if (a.gamut && h2y_stream_gamut(ctx, a.in.colour_primaries, a.out.colour_primaries, a.gamut_clip)) return fail(h2y_last_error(ctx));
     if (a.scale && h2y_stream_scale(ctx, a.out.width, a.out.height, a.scale_taps)) return fail(h2y_last_error(ctx));
     const size_t wb = a.scale ? h2y_scale_frame_bytes(a.out.width, a.out.height, a.out.chroma_format_idc) : ob; /* what comes down */
     std::unique_ptr<unpack_pool> pool;

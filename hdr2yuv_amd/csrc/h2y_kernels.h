@@ -354,6 +354,20 @@ int h2y_light_grid(uint32_t npix, int n_frames); /* blocks per frame */
 /* k_light over n_frames frames into acc[frame] (zeroed by the caller) */
 hipError_t h2y_launch_light(int in_kind, int grid, hipStream_t st, const light_args &a, const light_frame *frames, int n_frames, light_acc *acc);
 
+/* k_gamut (h2y_gamut.hip): the conversion between colour primaries of include/hdr2yuv_hip.h on frames of three float or half
+ * planes G, B, R; dst may be src (in place) */
+struct gamut_frame {
+    const void *src[3];
+    void *dst[3];
+};
+struct gamut_args {
+    uint32_t npix; /* pixels per frame (< 2^28) */
+    uint32_t clip; /* 1: results that are not above 0 become +0.0 */
+    float m[9];    /* row-major, on (R, G, B) columns */
+};
+uint32_t h2y_gamut_chunks(int in_kind, uint32_t npix); /* k_gamut's units of 256 threads per frame */
+hipError_t h2y_launch_gamut(int in_kind, int grid, hipStream_t st, const gamut_args &a, const gamut_frame *frames, int n_frames);
+
 /* k_scale (h2y_scale.hip): the Lanczos resampler of include/hdr2yuv_hip.h on frames of three u16 planes.  One axis' table on the
  * device: first[d] and count[d] (int32), then d rows of H2Y_SCALE_MAX_TAPS int16 coefficients (zero past count). */
 enum { H2Y_SCALE_MAX_TAPS = 32, H2Y_SCALE_TILE_W = 64, H2Y_SCALE_TILE_H = 32, H2Y_SCALE_STAGE_ROWS = 16 };

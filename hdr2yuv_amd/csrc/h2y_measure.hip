@@ -1,6 +1,6 @@
 /*
- * h2y_measure.hip -- the measurements of the C-ABI shim: the comparison with a reference, SSIM, content light, histograms and the
- * scaler.  Each has its checks and geometry, its batch entry, its ring stage (ring_stage, h2y_shim.h), and its arm, result and
+ * h2y_measure.hip -- the measurements of the C-ABI shim: the comparison with a reference, SSIM, content light, histograms, the
+ * scaler and the conversion between colour primaries.  Each has its checks and geometry, its batch entry, its ring stage (ring_stage, h2y_shim.h), and its arm, result and
  * *_stream_open entries.
  */
 #include "h2y_shim.h"
@@ -984,4 +984,207 @@ int h2y_scale_stream_open(h2y_ctx *ctx, int src_w, int src_h, int chroma_format_
     rc = scale_arm(ctx, dst_w, dst_h, a);
     if (rc) stream_free(ctx);
     return rc;
+}
+
+/* ---- conversion between colour primaries (--gamut_convert; the reference's matrix_to_primaries() is empty, convert.cpp:1991) ------ */
+
+namespace {
+
+typedef __int128 i128;
+
+/* One set of primaries in exact integers: its normalised primary matrix is A diag(u) / (det k).  RGB: A's columns are the primaries'
+ * (x, y, z) in units of 1e-4, u = adj(A) (xw, yw, zw), det = |A|, k = yw; XYZ: the identity. */
+struct gamut_set {
+    i128 A[3][3], u[3], det, k;
+};
+
+void gamut_adj(const i128 A[3][3], i128 adj[3][3])
+{
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) { /* adj[i][j] = the cofactor of A[j][i] */
+            const int r0 = (j + 1) % 3, r1 = (j + 2) % 3, c0 = (i + 1) % 3, c1 = (i + 2) % 3;
+            adj[i][j] = A[r0][c0] * A[r1][c1] - A[r0][c1] * A[r1][c0];
+        }
+}
+
+/* 0: not a set this conversion knows; otherwise a number that is equal for equal chromaticities */
+int gamut_set_of(int code, gamut_set &s)
+{
+    static const int kXy[3][6] = {{6400, 3300, 3000, 6000, 1500, 600},   /* BT.709 */
+                                  {7080, 2920, 1700, 7970, 1310, 460},   /* BT.2020 */
+                                  {6800, 3200, 2650, 6900, 1500, 600}};  /* P3-D65 */
+    static const int kWhite[3] = {3127, 3290, 10000 - 3127 - 3290};      /* D65 */
+    const int which = code == 1 ? 0 : code == 8 || code == 9 ? 1 : code == 12 ? 2 : code == 10 ? 3 : -1;
+    if (which < 0) return 0;
+    if (which == 3) {
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) s.A[i][j] = i == j;
+        s.u[0] = s.u[1] = s.u[2] = s.det = s.k = 1;
+        return 4;
+    }
+    for (int j = 0; j < 3; j++) {
+        s.A[0][j] = kXy[which][2 * j];
+        s.A[1][j] = kXy[which][2 * j + 1];
+        s.A[2][j] = 10000 - kXy[which][2 * j] - kXy[which][2 * j + 1];
+    }
+    i128 adj[3][3];
+    gamut_adj(s.A, adj);
+    s.det = 0;
+    for (int j = 0; j < 3; j++) s.det += s.A[0][j] * adj[j][0];
+    for (int i = 0; i < 3; i++) s.u[i] = adj[i][0] * kWhite[0] + adj[i][1] * kWhite[1] + adj[i][2] * kWhite[2];
+    s.k = kWhite[1];
+    return which + 1;
+}
+
+/* num / den (den != 0, both below 2^100) rounded to nearest binary32, ties to even; false where the result is no normal number */
+bool gamut_round(i128 num, i128 den, float *out)
+{
+    if (num == 0) { *out = 0.0f; return true; }
+    const bool neg = (num < 0) != (den < 0);
+    i128 n = num < 0 ? -num : num, d = den < 0 ? -den : den;
+    int e = 0;
+    const i128 lim = (i128)1 << 124;
+    while (n >= 2 * d) {
+        if (d >= lim) return false;
+        d <<= 1, e++;
+    }
+    while (n < d) {
+        if (n >= lim) return false;
+        n <<= 1, e--;
+    }
+    uint32_t q = 1; /* d <= n < 2 d */
+    i128 r = n - d;
+    for (int b = 0; b < 23; b++) {
+        r <<= 1;
+        q <<= 1;
+        if (r >= d) r -= d, q |= 1u;
+    }
+    r <<= 1;
+    if (r > d || (r == d && (q & 1u))) q++;
+    if (q == (1u << 24)) q >>= 1, e++;
+    if (e < -126 || e > 127) return false;
+    const float v = ldexpf((float)q, e - 23);
+    *out = neg ? -v : v;
+    return true;
+}
+
+} // namespace
+
+int h2y_gamut_matrix(int src_primaries, int dst_primaries, float m[9], const char **why)
+{
+    const char *dummy;
+    if (!why) why = &dummy;
+    *why = "";
+    if (!m) { *why = "null matrix"; return H2Y_EINVAL; }
+    gamut_set s, d;
+    const int ks = gamut_set_of(src_primaries, s), kd = gamut_set_of(dst_primaries, d);
+    if (!ks || !kd) {
+        *why = "colour primaries other than 1 (BT.709), 8 / 9 (BT.2020), 12 (P3-D65) and 10 (XYZ) are not converted";
+        return H2Y_EUNSUPPORTED;
+    }
+    if (ks == kd) { *why = "source and destination primaries have the same chromaticities: there is nothing to convert"; return H2Y_EINVAL; }
+    /* M = NPM(d)^-1 NPM(s) = k_d diag(1 / u_d) adj(A_d) A_s diag(u_s) / (det_s k_s)   (det_d cancels) */
+    i128 adj[3][3];
+    gamut_adj(d.A, adj);
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) {
+            i128 p = 0;
+            for (int t = 0; t < 3; t++) p += adj[i][t] * s.A[t][j];
+            if (!gamut_round(d.k * p * s.u[j], d.u[i] * s.det * s.k, &m[3 * i + j])) { *why = "matrix entry out of range"; return H2Y_EINVAL; }
+        }
+    return H2Y_OK;
+}
+
+/* k_gamut's arguments for frames of width x height and a pair of primaries; the checks of both entries */
+static int gamut_args_of(h2y_ctx *ctx, int width, int height, int sample_type, int src_primaries, int dst_primaries, int clip, gamut_args &a)
+{
+    if (sample_type == H2Y_SAMPLE_U16)
+        return fail(ctx, H2Y_EUNSUPPORTED, "primaries are converted in linear light on float or half planes, not on U16 samples");
+    if (sample_type != H2Y_SAMPLE_F32 && sample_type != H2Y_SAMPLE_F16) return fail(ctx, H2Y_EINVAL, "bad sample type %d", sample_type);
+    if (width < 1 || height < 1 || (uint64_t)width * (uint64_t)height >= (1ull << 28)) return fail(ctx, H2Y_EINVAL, "bad picture size");
+    if (clip != 0 && clip != 1) return fail(ctx, H2Y_EINVAL, "clip must be 0 or 1");
+    const char *why;
+    const int rc = h2y_gamut_matrix(src_primaries, dst_primaries, a.m, &why);
+    if (rc) return fail(ctx, rc, "primaries %d -> %d: %s", src_primaries, dst_primaries, why);
+    a.npix = (uint32_t)width * (uint32_t)height;
+    a.clip = (uint32_t)clip;
+    return H2Y_OK;
+}
+
+static std::string gamut_variant(int in_kind, const gamut_args &a)
+{
+    return std::string("k_gamut<") + (in_kind == H2Y_IN_F16 ? "F16" : "F32") + (a.clip ? ",CLIP>" : ",NOCLIP>");
+}
+
+int h2y_gamut_batch(h2y_ctx *ctx, int width, int height, int sample_type, int src_primaries, int dst_primaries, int clip, int n_frames,
+                    const void *const *d_src, void *const *d_dst)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
+    gamut_args a{};
+    int rc = gamut_args_of(ctx, width, height, sample_type, src_primaries, dst_primaries, clip, a);
+    if (rc) return rc;
+    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
+    if (!d_src || !d_dst) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
+    for (int f = 0; f < n_frames; f++)
+        for (int c = 0; c < 3; c++) {
+            const void *i = d_src[3 * f + c], *o = d_dst[3 * f + c];
+            if (!i || !o) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is null", f, c);
+            if (((uintptr_t)i | (uintptr_t)o) & 15u) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is not 16-byte aligned", f, c);
+        }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    gamut_frame *h;
+    rc = frame_table(ctx, n_frames, h);
+    if (rc) return rc;
+    for (int f = 0; f < n_frames; f++)
+        for (int c = 0; c < 3; c++) h[f].src[c] = d_src[3 * f + c], h[f].dst[c] = d_dst[3 * f + c];
+    const int in_kind = sample_type == H2Y_SAMPLE_F16 ? H2Y_IN_F16 : H2Y_IN_F32;
+    const uint64_t per_frame = h2y_gamut_chunks(in_kind, a.npix);
+    rc = timed_launches(ctx, h, n_frames, H2Y_GAMUT_FRAMES_PER_LAUNCH, "k_gamut", [&](const gamut_frame *frames, int, int nf) {
+        return h2y_launch_gamut(in_kind, unit_grid(ctx, per_frame * nf), ctx->stream, a, frames, nf);
+    });
+    if (rc) return rc;
+    ctx->last_variant = gamut_variant(in_kind, a);
+    return H2Y_OK;
+}
+
+/* The conversion's ring stage, in place on a forward ring's decoded planes before pic_stats: k_gamut's arguments and its table entry
+ * per slot.  It leaves nothing of its own behind: what follows reads the converted planes. */
+struct gamut_stage : ring_stage {
+    gamut_args a{};
+    gamut_frame *tab = nullptr;
+    int in_kind = H2Y_IN_F32;
+    int grid = 1;
+    int decoded(h2y_ctx *ctx, int k) override
+    {
+        HIP_TRY(ctx, h2y_launch_gamut(in_kind, grid, ctx->stream, a, tab + k, 1));
+        return H2Y_OK;
+    }
+    int run(h2y_ctx *, int) override { return H2Y_OK; }
+};
+
+int h2y_stream_gamut(h2y_ctx *ctx, int src_primaries, int dst_primaries, int clip)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    if (ctx->s_kind != h2y_ctx::RING_FORWARD) return fail(ctx, H2Y_EINVAL, "primaries are converted on the forward rings only");
+    if (ctx->s_stage[STAGE_GAMUT]) return fail(ctx, H2Y_EINVAL, "the ring converts primaries already");
+    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    const h2y_desc *d = &ctx->s_desc;
+    auto st = std::make_unique<gamut_stage>();
+    int rc = gamut_args_of(ctx, d->width, d->height, d->in_sample_type, src_primaries, dst_primaries, clip, st->a);
+    if (rc) return rc;
+    if (d->src_transfer != H2Y_TRANSFER_LINEAR)
+        return fail(ctx, H2Y_EUNSUPPORTED, "primaries are converted in linear light (src_transfer 8), not src_transfer %d", d->src_transfer);
+    if (d->src_matrix != H2Y_MATRIX_GBR)
+        return fail(ctx, H2Y_EUNSUPPORTED, "converting primaries needs a G,B,R source (src_matrix 0), not src_matrix %d", d->src_matrix);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    st->in_kind = in_kind_of(d);
+    st->grid = unit_grid(ctx, h2y_gamut_chunks(st->in_kind, st->a.npix));
+    const int depth = (int)ctx->ss.size();
+    std::vector<gamut_frame> tab(depth);
+    for (int k = 0; k < depth; k++)
+        for (int c = 0; c < 3; c++) tab[k].src[c] = tab[k].dst[c] = ctx->ss[k].d_in + c * ctx->s_plane_al;
+    st->table(st->tab, tab);
+    return stage_arm(ctx, STAGE_GAMUT, std::move(st), "gamut");
 }

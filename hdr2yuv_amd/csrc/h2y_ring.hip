@@ -279,8 +279,11 @@ static int forward_produce(h2y_ctx *ctx, int slot)
     io.out = s.d_out;
     io.tmp_cb = io.tmp_cr = nullptr;
     if (src.kind != decode_src::NONE) HIP_TRY(ctx, src.launch(ctx, static_cast<const payload_frame *>(ctx->s_tab) + slot, 1));
+    int rc = H2Y_OK;
+    for (auto &st : ctx->s_stage) /* what works on the decoded planes: pic_stats and all that follows see its result */
+        if (!rc && st) rc = st->decoded(ctx, slot);
+    if (rc) return rc;
     const bool needs_stats = d->src_transfer != d->dst_transfer;
-    int rc;
     if (needs_stats && !d->stats_override) {
         rc = run_stats(ctx, d, io.in, (int)ctx->b->frames_cap, ctx->b->d_assumed); /* published in device memory, read by the next kernel */
         ctx->b->dev_assumed_ok = false; /* d_assumed[0] no longer holds what the last enqueued batch left there */

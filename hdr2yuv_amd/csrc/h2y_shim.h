@@ -176,10 +176,12 @@ struct ring_stage {
     }
     virtual int ready(h2y_ctx *, int) { return H2Y_OK; }  /* may the slot be submitted? */
     virtual int upload(h2y_ctx *, int) { return H2Y_OK; } /* on s_h2d, before the slot's ev_h2d */
+    /* on the context's stream, on a forward ring's decoded planes: after the decode, before pic_stats and the conversion */
+    virtual int decoded(h2y_ctx *, int) { return H2Y_OK; }
     virtual int run(h2y_ctx *ctx, int slot) = 0;          /* on the context's stream, after the frame was produced */
     virtual int download(h2y_ctx *, int) { return H2Y_OK; } /* the result, on s_d2h after the slot's ev_conv */
 };
-enum stage_id { STAGE_LIGHT, STAGE_COMPARE, STAGE_SSIM, STAGE_HISTOGRAM, STAGE_SCALE, STAGE_COUNT };
+enum stage_id { STAGE_GAMUT, STAGE_LIGHT, STAGE_COMPARE, STAGE_SSIM, STAGE_HISTOGRAM, STAGE_SCALE, STAGE_COUNT };
 
 struct h2y_ctx {
     int device = 0;

@@ -704,8 +704,53 @@ int h2y_stream_scale(h2y_ctx *ctx, int dst_w, int dst_h, int a);
 int h2y_scale_stream_open(h2y_ctx *ctx, int src_w, int src_h, int chroma_format_idc, int bit_depth, int full_range, int gbr, int dst_w,
                           int dst_h, int a, int depth /* 2..16 slots */);
 
+/* ---- conversion between colour primaries, in linear light, before the forward conversion (--gamut_convert 1) ---------------------
+ * The reference parses --src_colour_primaries / --dst_colour_primaries and never converts between them: matrix_to_primaries() is an
+ * empty function (convert.cpp:1991), and the two values only choose between the identity and the colour-difference branch of
+ * matrix_convert() (convert.cpp:1159-1160).  That behaviour is kept, bit for bit, by everything above.  This is the project's own
+ * definition of the missing step: a pass over the decoded source planes, after which the unchanged forward conversion writes the
+ * bytes it would write had the source file held the converted planes.
+ * Primaries (colour_primaries codes, hdr.h:95-105, and H.273's 12), CIE 1931 x/y:
+ *    1        BT.709   R .640/.330  G .300/.600  B .150/.060
+ *    8 and 9  BT.2020  R .708/.292  G .170/.797  B .131/.046
+ *   12        P3-D65   R .680/.320  G .265/.690  B .150/.060
+ *   10        XYZ      the planes hold X, Y, Z: the normalised primary matrix is the identity
+ *   The RGB sets share the D65 white .3127/.3290; there is no chromatic adaptation.  Any other code is H2Y_EUNSUPPORTED (11, P3 with
+ *   the DCI white, included); a pair of equal chromaticities (s == d, or 8 and 9) is H2Y_EINVAL: there is nothing to convert.
+ * Matrix: M = NPM(dst)^-1 NPM(src), row-major, on column vectors (R, G, B) -- (X, Y, Z) for code 10.  NPM is the normalised primary
+ *   matrix of SMPTE RP 177: its columns are the XYZ of the primaries, scaled so that R = G = B = 1 gives the white with Y = 1.
+ *   Each of the nine entries is the exact rational value rounded to nearest binary32; an entry whose exact value is 0 is +0.0 (709 and
+ *   P3 share the blue primary).  So the matrix does not depend on how it is computed.
+ * Pixel: planes 0 = G (Y), 1 = B (Z), 2 = R (X), so v = (p2, p0, p1).  A half is widened to binary32 (exact).
+ *   o_i = ((m[i][0] v0) + (m[i][1] v1)) + (m[i][2] v2): every multiply and add its own binary32 round-to-nearest operation, in that
+ *   order, no fused multiply-add; subnormal inputs and results are kept.
+ *   clip 1: o_i = o_i > 0 ? o_i : +0.0 (negatives, -0.0 and NaN become +0.0; +inf stays).  clip 0: the sums as they are; a NaN result
+ *   is some NaN.
+ *   p0' = o_1, p1' = o_2, p2' = o_0.  F32 is stored as is; F16 is rounded to nearest even (overflow gives inf).  The sample type
+ *   does not change. */
+#define H2Y_GAMUT_FRAMES_PER_LAUNCH 64
+
+/* The matrix of a pair of primaries.  Host only: no device, no context.  `why` (may be NULL) receives a static string. */
+int h2y_gamut_matrix(int src_primaries, int dst_primaries, float m[9], const char **why);
+
+/* k_gamut on n_frames device frames of width x height: d_src[f*3 + c] / d_dst[f*3 + c] are plane c = G, B, R of frame f, 16-byte
+ * aligned; a d_dst entry may equal its d_src entry (in place; no other overlap).  sample_type H2Y_SAMPLE_F32 or H2Y_SAMPLE_F16
+ * (H2Y_SAMPLE_U16: H2Y_EUNSUPPORTED), clip 0 or 1.  Launches of up to H2Y_GAMUT_FRAMES_PER_LAUNCH frames (h2y_last_kernel_ms sums
+ * them, h2y_last_kernel_name "k_gamut"); synchronous. */
+int h2y_gamut_batch(h2y_ctx *ctx, int width, int height, int sample_type, int src_primaries, int dst_primaries, int clip, int n_frames,
+                    const void *const *d_src, void *const *d_dst);
+
+/* Arm an open forward ring whose decoded planes are float or half (h2y_stream_open with F32 or F16 planes, h2y_dpx_stream_open,
+ * h2y_exr_stream_open) before its first input: k_gamut then runs in place on every slot's decoded device planes, on the context's
+ * stream, after the decode and before pic_stats, so the floor, the ceiling, the conversion and h2y_stream_light beside it see the
+ * converted planes.  The primaries are the arguments, not the descriptor's: no field of h2y_desc changes meaning.
+ * H2Y_EUNSUPPORTED where the planes are U16 (the TIFF ring, a U16 plain ring), where src_transfer is not 8 (LINEAR) or src_matrix not
+ * 0 (G, B, R), and for unsupported primaries; H2Y_EINVAL on an inverse, compare-only, histogram-only or scale-only ring, after the
+ * first input, on a ring armed already, for equal chromaticities and a clip other than 0 or 1. */
+int h2y_stream_gamut(h2y_ctx *ctx, int src_primaries, int dst_primaries, int clip);
+
 /* Timing of the last h2y_convert_batch*() (or h2y_inverse_*, h2y_dpx_decode_batch, h2y_tiff_decode_batch,
- * h2y_rgb_interleave_batch, h2y_exr_decode_batch, h2y_compare_batch, h2y_ssim_batch, h2y_light_batch, h2y_scale_batch) call measured with HIP events on
+ * h2y_rgb_interleave_batch, h2y_exr_decode_batch, h2y_compare_batch, h2y_ssim_batch, h2y_light_batch, h2y_scale_batch, h2y_gamut_batch) call measured with HIP events on
  * the stream the kernels ran on: total ms over the main kernels and how many
  * launches that covered. */
 int h2y_last_kernel_ms(const h2y_ctx *ctx, float *ms, int *launches);
@@ -713,7 +758,7 @@ int h2y_last_kernel_ms(const h2y_ctx *ctx, float *ms, int *launches);
 /* Name of the kernel those launches ran ("k_fused", "k_fused_t1", "k_fused_lut16",
  * "k_fused_narrow"; of the inverse entries "k_inverse", "k_inverse420", "k_inverse_batch", "k_inverse420_batch"; of
  * h2y_dpx_decode_batch "k_dpx_decode"; of h2y_tiff_decode_batch "k_tiff_decode", of h2y_rgb_interleave_batch
- * "k_rgb_interleave"; of h2y_exr_decode_batch "k_exr_decode"; of h2y_compare_batch "k_compare"; of h2y_scale_batch "k_scale"): the name to
+ * "k_rgb_interleave"; of h2y_exr_decode_batch "k_exr_decode"; of h2y_compare_batch "k_compare"; of h2y_scale_batch "k_scale"; of h2y_gamut_batch "k_gamut"): the name to
  * look for in a rocprofv3 kernel trace. */
 const char *h2y_last_kernel_name(const h2y_ctx *ctx);
 /* The same with its template arguments and launch shape, e.g. "k_fused_t1<F32,420BOX,YCBCR,PQ_IDENT> groups=8 xcd=1";

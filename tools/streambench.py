@@ -78,6 +78,16 @@ Prints one line per figure, then one JSON line with all of them.
      8 TB/s HBM peak, for 4K -> 1080p, 4K -> 720p and 1080p -> 4K (10-bit 4:2:0, 3 lobes) and 4K -> 1080p 16-bit 4:4:4 with 4 lobes;
   2. frames/s from host memory of the forward ring (as `compare`) unarmed and armed with h2y_stream_scale to 1080p;
   3. frames/s of the scale-only ring, 4K 10-bit 4:2:0 -> 1080p (the frame goes up, the scaled frame comes down).
+Prints one line per figure, then one JSON line with all of them.
+
+`streambench.py gamut`: the conversion between colour primaries on 4K frames:
+  1. the kernel time of h2y_gamut_batch (k_gamut, BT.709 -> BT.2020, clip on) over 64 distinct device frames per call (HIP events,
+     median of five after a warm-up call), F32 and F16, out of place and in place, the algorithmic bytes per frame -- every plane
+     read once and written once: 24 and 12 B/pixel -- over that time and their share of the 8 TB/s HBM peak;
+  2. the yardstick, in the same job: h2y_tiff_decode_batch (12 B/pixel) and h2y_dpx_decode_batch (10-bit: 16 B/pixel, float:
+     24 B/pixel) timed the same way -- streaming kernels of the same shape that this change does not touch;
+  3. frames/s from host memory of the .f32 ring and the half EXR ring (NONE) to PQ BT.2020nc 10-bit 4:2:0, unarmed and armed with
+     h2y_stream_gamut.
 Prints one line per figure, then one JSON line with all of them."""
 import os
 import sys
@@ -1009,8 +1019,121 @@ def scale_main():
     print(json.dumps({"streambench_scale": res}), flush=True)
 
 
+def gamut_main():
+    import json
+
+    import torch
+
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    from dpx_files import pack_pixels, write_dpx
+    from exr_files import HALF, NONE, smooth_half, write_exr
+    from tiff_files import write_tiff
+
+    w, hh, nb, reps = 3840, 2160, 64, 5
+    n = w * hh
+    nf = int(os.environ.get("N", "60"))
+    depth = 3
+    rng = np.random.default_rng(29)
+    ctx = h.Context(0)
+    res = {"width": w, "height": hh, "frames_per_call": nb, "reps": reps, "ring_frames": nf, "ring_depth": depth, "hbm_peak_tbs": 8.0}
+
+    def timed(key, label, nbytes, call):
+        ks = []
+        for r in range(reps + 1):  # the first call warms up
+            call()
+            if r:
+                ks.append(ctx.last_kernel_ms()[0] / nb)
+        k_ms = float(np.median(ks))
+        tbs = nbytes / (k_ms * 1e-3) / 1e12
+        res[key] = dict(kernel_us_per_frame=round(k_ms * 1e3, 2), min_us=round(min(ks) * 1e3, 2), max_us=round(max(ks) * 1e3, 2),
+                        bytes_per_frame=nbytes, kernel_tbs=round(tbs, 2), hbm_peak_fraction=round(tbs / 8.0, 3), variant=ctx.last_kernel_variant())
+        print(f"{label:32s} {nb} frames per call: {k_ms*1e3:7.2f} us/frame ({min(ks)*1e3:.2f}..{max(ks)*1e3:.2f})  {nbytes/1e6:6.1f} MB/frame  "
+              f"{tbs:5.2f} TB/s = {tbs/8.0*100:4.1f} % of 8 TB/s", flush=True)
+
+    # 1. k_gamut over 64 distinct frames on the device
+    for name, sample, dt in (("f32", h.SAMPLE_F32, torch.float32), ("f16", h.SAMPLE_F16, torch.float16)):
+        src = [[torch.rand(n, device="cuda").to(dt) for _ in range(3)] for _ in range(nb)]
+        dst = [[torch.empty(n, dtype=dt, device="cuda") for _ in range(3)] for _ in range(nb)]
+        torch.cuda.synchronize()
+        nbytes = 2 * 3 * n * (4 if sample == h.SAMPLE_F32 else 2)
+        timed(f"k_gamut_{name}_out_of_place", f"k_gamut {name} out of place", nbytes, lambda: ctx.gamut_batch(w, hh, sample, 1, 9, 1, src, dst))
+        del dst
+        timed(f"k_gamut_{name}_in_place", f"k_gamut {name} in place", nbytes, lambda: ctx.gamut_batch(w, hh, sample, 1, 9, 1, src))
+        del src
+        torch.cuda.empty_cache()
+
+    # 2. the yardstick: the decode kernels of the TIFF and DPX rings, on 64 payloads
+    tdata = write_tiff(rng.integers(0, 65536, (hh, w, 3), dtype=np.uint16))
+    tinfo, rows = h.parse_tiff(tdata)
+    tpay = np.frombuffer(b"".join(tdata[int(o):int(o) + int(tinfo.row_bytes)] for o in rows), np.uint8)
+    pays = [torch.from_numpy(tpay.copy()).cuda() for _ in range(nb)]
+    outs = [[torch.empty(n, dtype=torch.int16, device="cuda") for _ in range(3)] for _ in range(nb)]
+    torch.cuda.synchronize()
+    timed("k_tiff_decode", "k_tiff_decode", 12 * n, lambda: ctx.tiff_decode_batch(tinfo, 0, pays, outs))
+    del pays, outs
+    torch.cuda.empty_cache()
+    rgb = [rng.random(n, dtype=np.float32) for _ in range(3)]
+    for name, bits in (("10", 10), ("float", 32)):
+        vals = [c.view(np.uint32) for c in rgb] if bits == 32 else [rng.integers(0, 1024, n, dtype=np.uint32) for _ in range(3)]
+        data = write_dpx(w, hh, bits, pack_pixels(*vals, bits))
+        info = h.parse_dpx(data[:2048], len(data))
+        pay = np.frombuffer(data, np.uint8, count=info.payload_bytes, offset=info.data_offset)
+        pays = [torch.from_numpy(pay.copy()).cuda() for _ in range(nb)]
+        outs = [[torch.empty(n, dtype=torch.float32, device="cuda") for _ in range(3)] for _ in range(nb)]
+        torch.cuda.synchronize()
+        timed(f"k_dpx_decode_{name}", f"k_dpx_decode {name}", int(info.payload_bytes) + 12 * n, lambda: ctx.dpx_decode_batch(info, pays, outs))
+        del pays, outs
+        torch.cuda.empty_cache()
+
+    # 3. the .f32 ring and the EXR ring from host memory, unarmed and armed
+    def ring(open_fn, fill, arm):
+        open_fn()
+        if arm:
+            ctx.stream_gamut(1, 9, 1)
+        inflight = 0
+        t0 = time.perf_counter()
+        for _ in range(nf):
+            fill(ctx.stream_input())
+            ctx.stream_submit()
+            inflight += 1
+            if inflight == depth - 1:
+                ctx.stream_output()
+                inflight -= 1
+        while inflight:
+            ctx.stream_output()
+            inflight -= 1
+        dt = (time.perf_counter() - t0) / nf
+        ctx.stream_close()
+        return dt
+
+    def both(key, open_fn, fill):
+        ring(open_fn, fill, False)  # warm-up
+        t_plain, t_armed = ring(open_fn, fill, False), ring(open_fn, fill, True)
+        res[key] = dict(unarmed_fps=round(1 / t_plain, 1), armed_fps=round(1 / t_armed, 1), armed_share=round(t_plain / t_armed, 3))
+        print(f"{key:12s} ring from host memory: unarmed {1/t_plain:6.1f} frames/s   armed {1/t_armed:6.1f} frames/s "
+              f"({t_plain/t_armed*100:5.1f} %)", flush=True)
+
+    d32 = h.make_desc(w, hh, dst_depth=10, dst_matrix=h.MATRIX_BT2020NC, src_primaries=1, dst_primaries=9, resampler=1)
+    planes = [rgb[1], rgb[2], rgb[0]]
+
+    def fill_planes(slot):
+        for c in range(3):
+            slot[c][:] = planes[c]
+
+    both("f32", lambda: ctx.stream_open(d32, depth), fill_planes)
+    edata, _ = write_exr({name: (HALF, smooth_half(hh, w, 101 * k)) for k, name in enumerate("RGB")}, NONE)
+    ebuf = np.frombuffer(edata, np.uint8)
+    einfo, echunks = h.parse_exr(ebuf)
+    dh = h.make_desc(w, hh, sample=h.SAMPLE_F16, dst_depth=10, dst_matrix=h.MATRIX_BT2020NC, src_primaries=1, dst_primaries=9, resampler=1)
+    both("exr", lambda: ctx.exr_stream_open(dh, einfo, depth), lambda slot: h.exr_unpack(einfo, echunks, ebuf, slot[0]))
+    ctx.close()
+    print(json.dumps({"streambench_gamut": res}), flush=True)
+
+
 if __name__ == "__main__":
-    if sys.argv[1:] == ["scale"]:
+    if sys.argv[1:] == ["gamut"]:
+        gamut_main()
+    elif sys.argv[1:] == ["scale"]:
         scale_main()
     elif sys.argv[1:] == ["inverse"]:
         inverse_main()
