@@ -43,7 +43,7 @@
 #ifndef FF_BUFFER_STORE
 #define FF_BUFFER_STORE 1 /* 1: chroma through range-checked buffer stores (lanes without a column are dropped by the hardware) */
 #endif
-#define FF_OWN_LANES H2Y_FF_OWN_LANES /* lanes 2 .. 61 own chroma: 240 picture columns per strip (h2y_kernels.h) */
+#define FF_OWN_LANES H2Y_FF_OWN_LANES /* lanes 2 .. 61 own chroma: 240 picture columns per strip (h2y_walk.h) */
 #define FF_HALO ((64 - FF_OWN_LANES) / 2) /* lanes on either side that only feed the horizontal taps */
 
 /* one row pair of the lane's four columns, three planes: as floats, or -- FF_TIER_LUT16, whose table is indexed by the
@@ -211,7 +211,7 @@ __global__ __launch_bounds__(FF_THREADS) void k_fir_fused(firf_args a)
 
     const uint32_t lane = threadIdx.x & (WAVE - 1);
     const uint32_t GW = gridDim.x * (FF_THREADS / WAVE);
-    const uint32_t vblock = a.mix_xcds ? ((blockIdx.x & ~6u) | ((blockIdx.x & 2u) << 1) | ((blockIdx.x & 4u) >> 1)) : blockIdx.x; /* h2y_firf_vblock() */
+    const uint32_t vblock = a.mix_xcds ? ((blockIdx.x & ~6u) | ((blockIdx.x & 2u) << 1) | ((blockIdx.x & 4u) >> 1)) : blockIdx.x; /* h2y_firf_vblock(), h2y_walk.h */
     const uint32_t gw = __builtin_amdgcn_readfirstlane(vblock * (FF_THREADS / WAVE) + threadIdx.x / WAVE); /* uniform, and known to be */
     const uint32_t W = a.width, H = a.height, WQ = a.wq, H2 = H >> 1;
     const uint32_t npix = W * H, ncb = (W >> 1) * (H >> 1);

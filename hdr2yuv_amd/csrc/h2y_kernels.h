@@ -1,5 +1,5 @@
 /* h2y_kernels.h -- argument blocks and launch entry points shared by
- * h2y_kernels.hip (device code) and the C-ABI shim (h2y_api.hip, h2y_ring.hip, h2y_measure.hip). */
+ * h2y_kernels.hip (device code) and the C-ABI shim (h2y_api.hip, h2y_forward.hip, h2y_ring.hip, h2y_measure.hip). */
 #ifndef H2Y_KERNELS_H
 #define H2Y_KERNELS_H
 
@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "h2y_math.h"
+#include "h2y_walk.h" /* H2Y_FF_OWN_LANES, h2y_firf_vblock */
 
 #ifndef H2Y_FUSED_THREADS
 #define H2Y_FUSED_THREADS 512
@@ -202,11 +203,6 @@ struct inv_frame {
     uint16_t *out[3];
 };
 
-/* k_fir_fused: lanes of a wave that own chroma columns (the others, half on either side, only feed the horizontal taps):
- * a strip is 4 x this many picture columns */
-#ifndef H2Y_FF_OWN_LANES
-#define H2Y_FF_OWN_LANES 60
-#endif
 #ifdef H2Y_BLOCK_TIMES
 void h2y_dump_block_times(const char *path); /* timing experiments only */
 void h2y_dump_ff_block_times(const char *path);
@@ -221,9 +217,6 @@ hipError_t h2y_launch_stats(int in_kind, int grid, hipStream_t st, const stats_a
 hipError_t h2y_launch_stats_final(int n_frames, hipStream_t st, const final_args &a);
 hipError_t h2y_launch_fir420(hipStream_t st, const fir_args &a);
 hipError_t h2y_launch_inverse(int grid, hipStream_t st, const inverse_args &a);
-/* k_fir_fused: bits 1 and 2 of the block number exchanged (an involution on [0, 8k)).  Block b runs on XCD b % 8; with four
- * segments per column, b = 4 f + segment would give a column the XCDs {0..3} or {4..7} -- after the exchange {0,1,4,5} or {2,3,6,7} */
-static inline uint32_t h2y_firf_vblock(uint32_t b) { return (b & ~6u) | ((b & 2u) << 1) | ((b & 4u) >> 1); }
 hipError_t h2y_launch_fir_fused(int in_kind, int mode, bool ident, bool lut16, int grid, hipStream_t st, const firf_args &a);
 hipError_t h2y_launch_up444(hipStream_t st, const up_args &a);
 hipError_t h2y_launch_inverse420(hipStream_t st, const inv420_args &a);

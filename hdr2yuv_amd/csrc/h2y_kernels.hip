@@ -849,7 +849,7 @@ __global__ __launch_bounds__(H2Y_T1_THREADS) void k_fused_t1(fused_args a)
     /* ticket tk of the dynamic frame -> its slice's first tile; false: the frame is dealt out */
     auto dyn_tile0 = [&](uint32_t tk, uint32_t &tile0) -> bool {
         const uint32_t c = tk / H2Y_TAIL_CHUNK, idx = tk % H2Y_TAIL_CHUNK;
-        if (c >= H2Y_TAIL_QLEN) return false; /* (the host sees to it that a block never gets this far: run_frames()) */
+        if (c >= H2Y_TAIL_QLEN) return false; /* (the host sees to it that a block never gets this far: tail_queue_fits(), h2y_plan.h) */
         if (tk == 0u) draw_chunk(0u);          /* the first wave of the block to get here */
         uint32_t e;
         while ((e = tq[c]) == kTqNone) __builtin_amdgcn_s_sleep(1);
@@ -1760,7 +1760,7 @@ __global__ __launch_bounds__(256) void k_inverse_batch(inverse_args base, const 
     }
 }
 
-/* ---- launch helpers (called from h2y_api.hip) --------------------------- */
+/* ---- launch helpers (called from h2y_forward.hip, h2y_api.hip) --------------------------- */
 typedef void (*fused_fn)(fused_args);
 
 template <int IN_KIND, int OUT_KIND, int MODE> static fused_fn pick_pipe(int pipe, bool even_h)

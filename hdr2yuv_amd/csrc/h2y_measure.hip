@@ -360,8 +360,7 @@ static int light_args_of(h2y_ctx *ctx, const h2y_desc *d, light_args &a)
     a.n4 = a.npix / 4u;
     a.table = nullptr;
     if (a.pp.src_tf != H2Y_TF_LINEAR) {
-        static const int kSrcFn[4] = {H2Y_TFN_NONE, H2Y_TFN_PQ_F, H2Y_TFN_RHO_H, H2Y_TFN_G24}; /* by H2Y_TF_* class, as run_frames() */
-        const int sf = kSrcFn[a.pp.src_tf];
+        const int sf = kSrcFn[a.pp.src_tf]; /* h2y_shim.h */
         const int rc = ensure_tfn(ctx, sf);
         if (rc) return rc;
         a.pp.src_fn = sf;

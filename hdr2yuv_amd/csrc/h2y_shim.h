@@ -1,6 +1,6 @@
 /*
- * h2y_shim.h -- what the shim's translation units share (h2y_api.hip, h2y_ring.hip, h2y_measure.hip): the context, the streaming
- * ring's stage interface, and the helpers every entry uses.  Internal: not installed, no part of the ABI.
+ * h2y_shim.h -- what the shim's translation units share (h2y_api.hip, h2y_forward.hip, h2y_ring.hip, h2y_measure.hip): the context,
+ * the streaming ring's stage interface, and the helpers every entry uses.  Internal: not installed, no part of the ABI.
  */
 #pragma once
 
@@ -103,7 +103,7 @@ struct batch_state {
     /* fused_args.slice_ranges ([blocks of a group + 1]): two tables in pinned host memory that the kernels read in place (a
      * block reads two words of it, once) -- no copy command between two launches.  Two, because the launches of one batch may
      * need different tables (the last one, when it holds fewer frames) while the earlier ones have not run yet. */
-    uint32_t *h_ranges = nullptr, *hd_ranges = nullptr; /* host and device address of the same 2 x kRangeWords words */
+    uint32_t *h_ranges = nullptr, *hd_ranges = nullptr; /* host and device address of the same 2 x kRangeWords words (h2y_plan.h) */
     uint32_t *d_tail = nullptr; /* the dynamic last frame's counters: [16 groups][H2Y_TAIL_WORDS]: counters and exhausted bits, zero between launches (k_stats_final) */
     float *h_btime = nullptr, *hd_btime = nullptr; /* every block's run time of a timed launch (pinned, written by k_stats_final) */
     int bal_grid = 0, bal_groups = 0;              /* the launch those times (and bal_bwork) belong to; 0: none */
@@ -351,6 +351,24 @@ inline const uint16_t *frame_base(const h2y_ctx *ctx, int k)
     return ctx->s_frame.in_input ? reinterpret_cast<const uint16_t *>(ctx->ss[k].d_in) : ctx->ss[k].d_out;
 }
 
+/* transfer_characteristics code -> what matrix_convert() does with it (convert.cpp:1024-1109);
+ * -1: the reference only prints a warning for every pixel */
+inline int tf_class(int t)
+{
+    switch (t) {
+    case 8: return H2Y_TF_LINEAR;
+    case 16: return H2Y_TF_PQ;
+    case 18: return H2Y_TF_RHO_GAMMA;
+    case 1: case 6: case 14: case 15: return H2Y_TF_BT1886; /* BT709, BT601, BT2020_10bit, BT2020_12bit */
+    default: return -1;
+    }
+}
+/* a generic transfer pair through the table tier: the source stage's and the destination stage's function, by H2Y_TF_* class */
+const int kSrcFn[4] = {H2Y_TFN_NONE, H2Y_TFN_PQ_F, H2Y_TFN_RHO_H, H2Y_TFN_G24};
+const int kDstFn[4] = {H2Y_TFN_NONE, H2Y_TFN_PQ_R, H2Y_TFN_RHO_R, H2Y_TFN_G24INV};
+
+inline size_t sample_bytes(const h2y_desc *d) { return d->in_sample_type == H2Y_SAMPLE_F32 ? 4 : 2; }
+
 inline int in_kind_of(const h2y_desc *d)
 {
     return d->in_sample_type == H2Y_SAMPLE_F32 ? H2Y_IN_F32 : d->in_sample_type == H2Y_SAMPLE_F16 ? H2Y_IN_F16 : H2Y_IN_U16;
@@ -382,6 +400,19 @@ template <typename T> int frame_table(h2y_ctx *ctx, int n, T *&h)
     return H2Y_OK;
 }
 
+/* the time between the two events of each of the batch's n_ev pairs, summed, in milliseconds */
+inline hipError_t event_ms(const batch_state *b, float *ms)
+{
+    *ms = 0.f;
+    for (int i = 0; i < b->n_ev; i++) {
+        float t = 0.f;
+        const hipError_t e = hipEventElapsedTime(&t, b->ev[i][0], b->ev[i][1]);
+        if (e != hipSuccess) return e;
+        *ms += t;
+    }
+    return hipSuccess;
+}
+
 /* The table h of n_frames entries (frame_table's) goes up once, then launch(frames, f0, nf) enqueues one launch on the device
  * entries [f0, f0 + nf), in launches of up to per_launch frames, each timed with an event pair (launches past the last pair are
  * timed by it); then a synchronisation, and last_ms, last_launches and last_name are the batch's */
@@ -400,19 +431,13 @@ int timed_launches(h2y_ctx *ctx, const T *h, int n_frames, int per_launch, const
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->b->n_ev = launches < kMaxEvents ? launches : kMaxEvents;
-    float ms = 0.f;
-    for (int i = 0; i < ctx->b->n_ev; i++) {
-        float t = 0.f;
-        HIP_TRY(ctx, hipEventElapsedTime(&t, ctx->b->ev[i][0], ctx->b->ev[i][1]));
-        ms += t;
-    }
-    ctx->last_ms = ms;
+    HIP_TRY(ctx, event_ms(ctx->b, &ctx->last_ms));
     ctx->last_launches = launches;
     ctx->last_name = name;
     return H2Y_OK;
 }
 
-/* ---- h2y_api.hip: the forward path and the inverse set-up, as the ring and the measurements use them ---------------------------- */
+/* ---- h2y_forward.hip: the forward path, as the ring and the measurements use it ---------------------------------------------------- */
 
 void derive_params(const h2y_desc *d, pix_params *pp, bool stage_matrix_only);
 int ensure_tfn(h2y_ctx *ctx, int fn);
@@ -420,6 +445,9 @@ int run_frames(h2y_ctx *ctx, const h2y_desc *d, const frame_io *frames, int n, c
                bool check, int fstats_offset, bool time_it);
 int reserve_batch(h2y_ctx *ctx, int n);
 int run_stats(h2y_ctx *ctx, const h2y_desc *d, const void *const in[3], int slot, assumed_stats *publish);
+
+/* ---- h2y_api.hip: the inverse set-up ------------------------------------------------------------------------------------------------ */
+
 int inverse_check(h2y_ctx *ctx, const inv_params &p);
 void inverse420_setup(inv420_args &a, int width, int height, int in_bit_depth, int in_full_range, int in_matrix_coeffs, int out_bit_depth,
                       int algorithm);

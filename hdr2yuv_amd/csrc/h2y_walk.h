@@ -1,6 +1,7 @@
 /* h2y_walk.h -- which frames and which parts of them a block of the loop-form kernels (k_fused2, k_fused_t1,
  * k_fused_lut16) works on.  Host and device: tools/walk_check.cpp (run by tests/test_walk.py) checks on the CPU that
- * every chunk / slice of every frame is dealt to exactly one block, for the same code the kernels and the shim run. */
+ * every chunk / slice of every frame is dealt to exactly one block, for the same code the kernels and the shim run.  Also
+ * which block of k_fir_fused works as which (h2y_firf_vblock). */
 #ifndef H2Y_WALK_H
 #define H2Y_WALK_H
 #include "h2y_math.h" /* H2Y_FN */
@@ -107,6 +108,15 @@ inline void slice_ranges(const double speed[8], uint32_t G, uint32_t n_slices, u
 }
 /* the block of the grid that is block i of group g under the XCD layout (the inverse of frame_walk::init) */
 H2Y_FN uint32_t walk_block_of(uint32_t g, uint32_t i, uint32_t NG) { return (((i >> 3) * NG + g) << 3) | (i & 7u); }
+
+/* k_fir_fused: lanes of a wave that own chroma columns (the others, half on either side, only feed the horizontal taps):
+ * a strip is 4 x this many picture columns */
+#ifndef H2Y_FF_OWN_LANES
+#define H2Y_FF_OWN_LANES 60
+#endif
+/* k_fir_fused: bits 1 and 2 of the block number exchanged (an involution on [0, 8k)).  Block b runs on XCD b % 8; with four
+ * segments per column, b = 4 f + segment would give a column the XCDs {0..3} or {4..7} -- after the exchange {0,1,4,5} or {2,3,6,7} */
+H2Y_FN uint32_t h2y_firf_vblock(uint32_t b) { return (b & ~6u) | ((b & 2u) << 1) | ((b & 4u) >> 1); }
 
 /*
  * The dynamic last frame (round 3).  With every frame dealt in fixed shares a launch ends when its slowest block ends, and

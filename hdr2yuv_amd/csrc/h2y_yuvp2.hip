@@ -5,7 +5,7 @@
  *   k_yuvp2_420<BOX|FIR>  tmp_pic (U16 4:4:4: Y', Z = Cb, X = Cr) -> the .yuv frame (Y, u', v')
  *
  * The fused kernel has written tmp_pic -- matrix_convert()'s output, neither shifted nor range-clamped -- into scratch first
- * (run_frames() in h2y_api.hip).  What the reference then does, per picture:
+ * (run_frames() in h2y_forward.hip).  What the reference then does, per picture:
  *   - Y: tmp Y' copied (convert.cpp:857-859).
  *   - four planes, each subsampled by Subsample444to420_box or _FIR with tmp_pic's clip (convert.cpp:520: in_pic->clip, the
  *     temporary picture's maxCV, whatever the planes hold): lin(Y'), Z, X and Y'.  lin(c) is
