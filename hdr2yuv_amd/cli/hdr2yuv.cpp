@@ -4,6 +4,12 @@
  * planes to the C-ABI (include/hdr2yuv_hip.h) and writes the .yuv frames where write_yuv() would append them
  * (tiff.cpp:440: the file is opened in append mode; planes Y, Cb, Cr, little-endian 16-bit).
  *
+ * How the file is laid out: main resolves the command line, scans the source (h2y_cli_sources.h) and checks every file's size,
+ * then chooses one of five flows -- forward, .yuv -> RGB, --compare_only, --histogram_only, --scale_only.  A flow is a `flow`: how
+ * to open its ring and arm its stages, how frame k gets into a slot's planes, the layout of the reference frame, how frame k is
+ * written.  run_block drives every flow the same way (context, source, ring, reference, stages, the fill / submit / drain loop
+ * three slots deep, the tail) and tears down through one guard; what the blocks measure is kept in one `results`.
+ *
  * Input formats:
  *   .yuv / .rgb  16-bit planar integer (hdr2yuv.cpp:582-656; .rgb is R,G,B in the file, planes 2,0,1 in memory)
  *   .f32 / .f16  raw planar float / half in G,B,R plane order -- what dpx_read() or read_exr() (exr.cpp:233-235) leave in
@@ -80,65 +86,11 @@
  * held the converted planes, and --content_light beside it measures the converted light.  The banner carries gamut_convert:,
  * gamut_clip: and the nine entries of gamut_matrix: as "%.9g".
  */
-#include <algorithm>
 #include <array>
-#include <atomic>
-#include <cerrno>
-#include <condition_variable>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <cmath>
-#include <fcntl.h>
 #include <memory>
-#include <mutex>
-#include <string>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <thread>
-#include <unistd.h>
-#include <vector>
 
-#include "h2y_cli_args.h"
-
-static uint16_t f32_to_f16(float f)
-{
-    uint32_t x;
-    memcpy(&x, &f, 4);
-    uint32_t sign = (x >> 16) & 0x8000u;
-    int32_t e = (int32_t)((x >> 23) & 0xFF) - 127 + 15;
-    uint32_t m = x & 0x7FFFFFu;
-    if (e >= 31) return (uint16_t)(sign | 0x7C00u);
-    if (e <= 0) {
-        if (e < -10) return (uint16_t)sign;
-        m |= 0x800000u;
-        int shift = 14 - e;
-        uint32_t r = m >> shift, rem = m & ((1u << shift) - 1), half = 1u << (shift - 1);
-        if (rem > half || (rem == half && (r & 1))) r++;
-        return (uint16_t)(sign | r);
-    }
-    uint32_t r = ((uint32_t)e << 10) | (m >> 13), rem = m & 0x1FFFu;
-    if (rem > 0x1000u || (rem == 0x1000u && (r & 1))) r++;
-    return (uint16_t)(sign | r);
-}
-
-/* the seeded frame of SURVEY 8c: frame k of a run uses seed 12345 + k */
-static void synth_fill(const h2y_desc &d, void *const planes[3], uint32_t seed)
-{
-    const size_t n = (size_t)d.width * d.height;
-    uint32_t s = seed;
-    for (int c = 0; c < 3; c++) {
-        for (size_t i = 0; i < n; i++) {
-            s = s * 1664525u + 1013904223u;
-            float v = (float)(s >> 8) * (1.0f / 16777216.0f);
-            if (i == 0) v = 0.0f;
-            if (i == 1) v = 1.0f;
-            if (d.in_sample_type == H2Y_SAMPLE_F16) ((uint16_t *)planes[c])[i] = f32_to_f16(v);
-            else ((float *)planes[c])[i] = v;
-        }
-    }
-}
+#include "h2y_cli_sources.h"
 
 static bool write_at(int fd, const void *buf, size_t n, off_t at)
 {
@@ -156,266 +108,11 @@ static bool write_at(int fd, const void *buf, size_t n, off_t at)
     return true;
 }
 
-/* one .dpx file of the run: its name and where its payload starts */
-struct dpx_src {
-    std::string path;
-    uint64_t offset;
-};
-
-/* The .dpx files of the run -- --src_filename itself, or the files numbered --src_start_frame .. + want - 1 of a sequence (as
- * many of them as exist in a row) -- parsed, checked against the command line's size and against the first file's geometry
- * and format.  Returns 0 and fills info and files, or prints the first problem and returns 1. */
-static int dpx_scan(const cli_args &a, long want, h2y_dpx_info &info, std::vector<dpx_src> &files)
+/* the bytes of one 16-bit planar frame, 4:2:0 or 4:4:4: h2y_scale_frame_bytes states them for every size and chroma format
+ * cli_resolve lets through to a flow that reads or writes such frames (1..10000 a side, chroma_format_idc 1 or 3; it is 0 beyond) */
+static size_t planar16_bytes(const cli_pic &p)
 {
-    const bool seq = cli_frame_pattern(a.src) == 1;
-    for (long k = 0; k < (seq ? want : 1); k++) {
-        const std::string path = cli_frame_name(a.src, a.start_frame + k);
-        struct stat st;
-        if (stat(path.c_str(), &st)) {
-            if (k) break; /* the sequence ends here */
-            printf("ERROR: unable to open file %s\n", path.c_str());
-            return 1;
-        }
-        unsigned char hdr[2048];
-        FILE *f = fopen(path.c_str(), "rb");
-        if (!f) { printf("ERROR: unable to open file %s\n", path.c_str()); return 1; }
-        const size_t got = fread(hdr, 1, sizeof hdr, f);
-        fclose(f);
-        h2y_dpx_info di;
-        const char *why = nullptr;
-        if (h2y_dpx_parse(hdr, got, (uint64_t)st.st_size, &di, &why)) { printf("ERROR: %s: %s\n", path.c_str(), why); return 1; }
-        if (di.width != a.in.width || di.height != a.in.height) {
-            printf("ERROR: %s is %dx%d, --src_pic_width/--src_pic_height say %dx%d: resizing is not part of convert() (cv.cpp is "
-                   "compiled out in the reference)\n", path.c_str(), di.width, di.height, a.in.width, a.in.height);
-            return 1;
-        }
-        if (k && (di.width != info.width || di.height != info.height || di.bit_size != info.bit_size || di.swap != info.swap)) {
-            printf("ERROR: %s is %dx%d %d-bit %s-endian, %s %dx%d %d-bit %s-endian: every file of a sequence must have the same\n",
-                   path.c_str(), di.width, di.height, di.bit_size, di.swap ? "big" : "little", files[0].path.c_str(), info.width,
-                   info.height, info.bit_size, info.swap ? "big" : "little");
-            return 1;
-        }
-        /* fields dpx_read() ignores: the image element's descriptor (byte 800) and packing (u16 at 804) */
-        const unsigned descriptor = hdr[800], packing = di.swap ? (unsigned)hdr[804] << 8 | hdr[805] : (unsigned)hdr[805] << 8 | hdr[804];
-        if (descriptor != 50) printf("WARNING: %s: descriptor %u is not 50 (RGB); decoded as R,G,B, as dpx_read() does\n", path.c_str(), descriptor);
-        if (di.bit_size == 10 && packing != 1)
-            printf("WARNING: %s: 10-bit packing %u is not 1 (filled to 32-bit words, method A); decoded as packing 1, as dpx_read() does\n",
-                   path.c_str(), packing);
-        if (!k) info = di;
-        files.push_back({path, di.data_offset});
-    }
-    return 0;
-}
-
-/* one .tiff file of the run: its name and where its decoded rows lie */
-struct tiff_src {
-    std::string path;
-    std::vector<uint64_t> rows; /* file offset of each decoded row */
-    bool contiguous;
-};
-
-/* The .tiff files of the run, as dpx_scan: each mapped, its IFD parsed for read_tiff's geometry with the command line's
- * cutouts, checked against the command line's size and against the first file's geometry and byte order. */
-static int tiff_scan(const cli_args &a, long want, h2y_tiff_info &info, std::vector<tiff_src> &files)
-{
-    const bool seq = cli_frame_pattern(a.src) == 1;
-    for (long k = 0; k < (seq ? want : 1); k++) {
-        const std::string path = cli_frame_name(a.src, a.start_frame + k);
-        const int fd = open(path.c_str(), O_RDONLY);
-        if (fd < 0) {
-            if (k) break; /* the sequence ends here */
-            printf("ERROR: unable to open file %s\n", path.c_str());
-            return 1;
-        }
-        struct stat st;
-        void *map = MAP_FAILED;
-        if (!fstat(fd, &st) && st.st_size > 0) map = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
-        close(fd);
-        if (map == MAP_FAILED) { printf("ERROR: unable to map file %s\n", path.c_str()); return 1; }
-        h2y_tiff_info ti;
-        const char *why = nullptr;
-        int rc = h2y_tiff_parse(map, (size_t)st.st_size, a.cutout, &ti, nullptr, 0, &why);
-        tiff_src src{path, {}, false};
-        if (!rc) {
-            src.rows.resize((size_t)ti.height);
-            rc = h2y_tiff_parse(map, (size_t)st.st_size, a.cutout, &ti, src.rows.data(), ti.height, &why);
-        }
-        munmap(map, (size_t)st.st_size);
-        if (rc) { printf("ERROR: %s: %s\n", path.c_str(), why); return 1; }
-        if (ti.width != a.in.width || ti.height != a.in.height) {
-            printf("ERROR: %s decodes to %dx%d, --src_pic_width/--src_pic_height say %dx%d: resizing is not part of convert() (cv.cpp "
-                   "is compiled out in the reference)\n", path.c_str(), ti.width, ti.height, a.in.width, a.in.height);
-            return 1;
-        }
-        if (k && (ti.file_width != info.file_width || ti.file_height != info.file_height || ti.swap != info.swap)) {
-            printf("ERROR: %s is %dx%d %s-endian, %s %dx%d %s-endian: every file of a sequence must have the same\n", path.c_str(),
-                   ti.file_width, ti.file_height, ti.swap ? "big" : "little", files[0].path.c_str(), info.file_width, info.file_height,
-                   info.swap ? "big" : "little");
-            return 1;
-        }
-        if (!k && ti.swap)
-            printf("WARNING: %s is big-endian (MM): decoded with the bytes of each sample exchanged; the reference reads them unswapped\n",
-                   path.c_str());
-        src.contiguous = ti.contiguous != 0;
-        if (!k) info = ti;
-        files.push_back(std::move(src));
-    }
-    return 0;
-}
-
-/* a whole file mapped read-only */
-struct mapped_file {
-    void *p = MAP_FAILED;
-    size_t n = 0;
-    bool open(const std::string &path)
-    {
-        const int fd = ::open(path.c_str(), O_RDONLY);
-        if (fd < 0) return false;
-        struct stat st;
-        if (!fstat(fd, &st) && st.st_size > 0) {
-            n = (size_t)st.st_size;
-            p = mmap(nullptr, n, PROT_READ, MAP_PRIVATE, fd, 0);
-        }
-        close(fd);
-        return p != MAP_FAILED;
-    }
-    ~mapped_file()
-    {
-        if (p != MAP_FAILED) munmap(p, n);
-    }
-};
-
-/* The .exr files of the run, as dpx_scan: each mapped and parsed, its data window checked against the command line and its
- * header against the first file's (every file of a sequence has one h2y_exr_info).  Messages cite read_exr(). */
-static int exr_scan(const cli_args &a, long want, h2y_exr_info &info, std::vector<std::string> &files)
-{
-    const bool seq = cli_frame_pattern(a.src) == 1;
-    for (long k = 0; k < (seq ? want : 1); k++) {
-        const std::string path = cli_frame_name(a.src, a.start_frame + k);
-        mapped_file m;
-        if (!m.open(path)) {
-            if (k) break; /* the sequence ends here */
-            printf("ERROR: read_exr() (exr.cpp:146): unable to open or read file %s\n", path.c_str());
-            return 1;
-        }
-        h2y_exr_info xi;
-        const char *why = nullptr;
-        if (h2y_exr_parse(m.p, m.n, &xi, nullptr, 0, &why)) {
-            printf("ERROR: read_exr() (exr.cpp): %s: %s\n", path.c_str(), why);
-            return 1;
-        }
-        if (xi.width != a.in.width || xi.height != a.in.height) {
-            printf("ERROR: read_exr() (exr.cpp:149-153): %s has a %dx%d data window, --src_pic_width/--src_pic_height say %dx%d: "
-                   "resizing is not part of convert() (cv.cpp is compiled out in the reference)\n", path.c_str(), xi.width, xi.height,
-                   a.in.width, a.in.height);
-            return 1;
-        }
-        if (k && memcmp(&xi, &info, sizeof xi)) {
-            printf("ERROR: read_exr() (exr.cpp): %s differs from %s in its data window, compression or channels: every file of a "
-                   "sequence must have the same\n", path.c_str(), files[0].c_str());
-            return 1;
-        }
-        if (!k) info = xi;
-        files.push_back(path);
-    }
-    return 0;
-}
-
-/* The unpack threads of one GPU thread: h2y_exr_unpack of one frame's chunks, in ranges taken by the pool's threads and the
- * caller alike.  n counts the caller. */
-class unpack_pool {
-  public:
-    explicit unpack_pool(int n)
-    {
-        for (int i = 1; i < n; i++) th_.emplace_back([this] { work(); });
-    }
-    ~unpack_pool()
-    {
-        {
-            std::lock_guard<std::mutex> lk(m_);
-            quit_ = true;
-        }
-        cv_.notify_all();
-        for (auto &t : th_) t.join();
-    }
-    int threads() const { return (int)th_.size() + 1; }
-    /* the whole frame into payload: "" or the first error */
-    std::string run(const h2y_exr_info &xi, const h2y_exr_chunk *chunks, const void *file, void *payload)
-    {
-        {
-            std::lock_guard<std::mutex> lk(m_);
-            xi_ = &xi, chunks_ = chunks, file_ = file, payload_ = payload;
-            step_ = std::max(1, xi.n_chunks / (4 * threads()));
-            next_ = 0;
-            err_.clear();
-            busy_ = (int)th_.size();
-            gen_++;
-        }
-        cv_.notify_all();
-        take();
-        std::unique_lock<std::mutex> lk(m_);
-        done_.wait(lk, [&] { return busy_ == 0; });
-        return err_;
-    }
-
-  private:
-    void take()
-    {
-        for (;;) {
-            const int c0 = next_.fetch_add(step_);
-            if (c0 >= xi_->n_chunks) return;
-            const char *why = nullptr;
-            if (h2y_exr_unpack(xi_, chunks_, file_, c0, std::min(step_, xi_->n_chunks - c0), payload_, &why)) {
-                std::lock_guard<std::mutex> lk(m_);
-                if (err_.empty()) err_ = why;
-            }
-        }
-    }
-    void work()
-    {
-        uint64_t seen = 0;
-        for (;;) {
-            {
-                std::unique_lock<std::mutex> lk(m_);
-                cv_.wait(lk, [&] { return quit_ || gen_ != seen; });
-                if (quit_) return;
-                seen = gen_;
-            }
-            take();
-            std::lock_guard<std::mutex> lk(m_);
-            if (--busy_ == 0) done_.notify_one();
-        }
-    }
-    std::vector<std::thread> th_;
-    std::mutex m_;
-    std::condition_variable cv_, done_;
-    bool quit_ = false;
-    uint64_t gen_ = 0;
-    int busy_ = 0, step_ = 1;
-    std::atomic<int> next_{0};
-    const h2y_exr_info *xi_ = nullptr;
-    const h2y_exr_chunk *chunks_ = nullptr;
-    const void *file_ = nullptr;
-    void *payload_ = nullptr;
-    std::string err_;
-};
-
-/* at most this many unpack threads in the whole process, the GPU threads that unpack included */
-static constexpr int kUnpackThreads = 16;
-
-/* n bytes at `at` of the open file fd into buf */
-static bool read_at(int fd, void *buf, size_t n, off_t at)
-{
-    char *p = (char *)buf;
-    while (n) {
-        ssize_t r = pread(fd, p, n, at);
-        if (r < 0 && errno == EINTR) continue;
-        if (r <= 0) return false;
-        p += r;
-        at += r;
-        n -= (size_t)r;
-    }
-    return true;
+    return h2y_scale_frame_bytes(p.width, p.height, p.chroma_format_idc);
 }
 
 struct block { /* one thread's share: frames [first, first + count) of the run, on `device` */
@@ -435,177 +132,56 @@ static bool read_ref(FILE *f, bool rgb, size_t plane_bytes, size_t frame_bytes, 
     return fread(p + 2 * plane_bytes, 1, plane_bytes, f) == plane_bytes && fread(p, 1, 2 * plane_bytes, f) == 2 * plane_bytes;
 }
 
-/* the comparison side of one GPU thread: R opened at its frame `first`, the stats kept by frame index */
-struct compare_io {
-    std::vector<h2y_compare_stats> *stats = nullptr;
-    FILE *ref = nullptr;
-    bool rgb = false;
-    size_t plane_bytes = 0, frame_bytes = 0;
-    bool open(const cli_args &a, long first, size_t plane_b, size_t frame_b, std::vector<h2y_compare_stats> *st)
-    {
-        stats = st;
-        if (!a.ref) return true;
-        rgb = !strcasecmp(cli_ext_of(a.ref), "rgb");
-        plane_bytes = plane_b, frame_bytes = frame_b;
-        ref = fopen(a.ref, "rb");
-        return ref && !fseeko(ref, (off_t)frame_b * (off_t)first, SEEK_SET);
-    }
-    ~compare_io()
-    {
-        if (ref) fclose(ref);
-    }
-};
-
-/* the histogram side of one GPU thread: the stats and occupied bins of frame k kept by its index, the bins summed over its frames */
-struct histogram_io {
-    bool on = false;
-    std::vector<h2y_histogram_stats> *stats = nullptr;
-    std::vector<std::array<uint32_t, 3>> *occupied = nullptr;
-    std::vector<uint32_t> bins;  /* one frame's 3 x nbins */
-    std::vector<uint64_t> total; /* this thread's sums */
+/* What a run measures: the stats of frame k kept by its index, whichever GPU thread took them, so that every report is the same
+ * for any --gpus; the histogram's bins summed per GPU thread and added up at the end. */
+struct results {
+    std::vector<h2y_compare_stats> compare;
+    std::vector<h2y_ssim_stats> ssim;
+    std::vector<h2y_light_stats> light;
+    std::vector<h2y_histogram_stats> hist;
+    std::vector<std::array<uint32_t, 3>> occupied; /* the non-zero bins of frame k's planes */
+    std::vector<uint32_t> bins;                    /* per GPU thread: one frame's 3 x nbins */
+    std::vector<uint64_t> total;                   /* per GPU thread: its sums */
     size_t nbins = 0;
-    void open(const cli_args &a, std::vector<h2y_histogram_stats> *st, std::vector<std::array<uint32_t, 3>> *occ)
+    results(const cli_args &a, long frames)
+        : compare(a.ref ? (size_t)frames : 0), ssim(a.ssim ? (size_t)frames : 0), light(a.light ? (size_t)frames : 0),
+          hist(a.hist ? (size_t)frames : 0), occupied(hist.size())
     {
-        on = a.hist != nullptr;
-        if (!on) return;
-        stats = st, occupied = occ;
+        if (!a.hist) return;
         nbins = (size_t)1 << a.hist_bits;
-        bins.assign(3 * nbins, 0u);
-        total.assign(3 * nbins, 0u);
+        bins.assign((size_t)a.gpus * 3 * nbins, 0u);
+        total.assign((size_t)a.gpus * 3 * nbins, 0u);
     }
-    /* after h2y_stream_output: frame k's result */
-    bool take(h2y_ctx *ctx, long k)
+    /* after h2y_stream_output on GPU thread r: frame k's results; false when the library refused one */
+    bool take(const cli_args &a, h2y_ctx *ctx, long k, int r)
     {
-        if (!on) return true;
-        if (h2y_stream_histogram_result(ctx, &(*stats)[k], bins.data())) return false;
-        for (int p = 0; p < 3; p++) {
-            uint32_t occ = 0;
-            for (size_t i = 0; i < nbins; i++) {
-                const uint32_t c = bins[p * nbins + i];
-                occ += c != 0u;
-                total[p * nbins + i] += c;
+        if (a.ref && h2y_stream_compare_result(ctx, &compare[k])) return false;
+        if (a.ssim && h2y_stream_ssim_result(ctx, &ssim[k])) return false;
+        if (a.hist) {
+            uint32_t *b = &bins[(size_t)r * 3 * nbins];
+            uint64_t *t = &total[(size_t)r * 3 * nbins];
+            if (h2y_stream_histogram_result(ctx, &hist[k], b)) return false;
+            for (int p = 0; p < 3; p++) {
+                uint32_t occ = 0;
+                for (size_t i = 0; i < nbins; i++) {
+                    const uint32_t c = b[p * nbins + i];
+                    occ += c != 0u;
+                    t[p * nbins + i] += c;
+                }
+                occupied[k][p] = occ;
             }
-            (*occupied)[k][p] = occ;
         }
+        if (a.light && h2y_stream_light_result(ctx, &light[k])) return false;
         return true;
+    }
+    /* the bins of every thread, summed (the same totals for any split) */
+    std::vector<uint64_t> histogram_total() const
+    {
+        std::vector<uint64_t> sum(3 * nbins, 0u);
+        for (size_t i = 0; i < total.size(); i++) sum[i % sum.size()] += total[i];
+        return sum;
     }
 };
-
-/* forward path: frames [first, first+count) through one context's pinned ring (dpx: frame k is file dpx[k], decoded on the
- * device -- the ring of h2y_dpx_stream_open; tiff likewise, file tiff[k] through h2y_tiff_stream_open) */
-static void run_block(const cli_args &a, const h2y_desc &d, const std::vector<dpx_src> &dpx, const h2y_dpx_info &di,
-                      const std::vector<tiff_src> &tiff, const h2y_tiff_info &ti, const std::vector<std::string> &exr,
-                      const h2y_exr_info &xi, int fd_out, off_t base, std::vector<h2y_compare_stats> *stats,
-                      std::vector<h2y_ssim_stats> *ssim, std::vector<h2y_light_stats> *light, histogram_io *hist, block *b)
-{
-    h2y_ctx *ctx = nullptr;
-    FILE *fin = nullptr;
-    auto fail = [&](const std::string &m) {
-        b->err = m;
-        if (ctx) { h2y_stream_close(ctx); h2y_ctx_destroy(ctx); }
-        if (fin) fclose(fin);
-    };
-    if (b->count < 1) return;
-    if (h2y_ctx_create(b->device, &ctx)) return fail(h2y_last_error(nullptr));
-    const size_t pb = h2y_plane_bytes(&d), ob = h2y_frame_bytes(&d);
-    if (a.in_type != CLI_IN_SYNTH && a.in_type != CLI_IN_DPX && a.in_type != CLI_IN_TIFF && a.in_type != CLI_IN_EXR) {
-        fin = fopen(a.src, "rb");
-        if (!fin) return fail(std::string("unable to open file ") + a.src);
-        if (fseeko(fin, (off_t)(3 * pb) * (off_t)(a.start_frame + b->first), SEEK_SET)) return fail("seek failed"); /* hdr2yuv.cpp:624 */
-    }
-    /* The reader fills the pinned slot of the pipeline directly, the writer drains what comes out of it two frames
-     * later: upload, conversion and download of neighbouring frames overlap. */
-    const int depth = 3;
-    const int open_rc = a.in_type == CLI_IN_DPX    ? h2y_dpx_stream_open(ctx, &d, &di, depth)
-                        : a.in_type == CLI_IN_TIFF ? h2y_tiff_stream_open(ctx, &d, &ti, a.in.video_full_range_flag == 0, depth)
-                        : a.in_type == CLI_IN_EXR  ? h2y_exr_stream_open(ctx, &d, &xi, depth)
-                                                   : h2y_stream_open(ctx, &d, depth);
-    if (open_rc) return fail(h2y_last_error(ctx));
-    compare_io cmp;
-    if (!cmp.open(a, b->first, 0, ob, stats)) return fail(std::string("unable to read ") + a.ref);
-    if (cmp.ref && h2y_stream_compare(ctx, a.sigma, a.dst ? 1 : 0)) return fail(h2y_last_error(ctx));
-    if (a.ssim && h2y_stream_ssim(ctx, -1)) return fail(h2y_last_error(ctx));
-    if (hist->on && h2y_stream_histogram(ctx, a.hist_bits)) return fail(h2y_last_error(ctx));
-    if (a.light && h2y_stream_light(ctx)) return fail(h2y_last_error(ctx));
-    if (a.gamut && h2y_stream_gamut(ctx, a.in.colour_primaries, a.out.colour_primaries, a.gamut_clip)) return fail(h2y_last_error(ctx));
-    if (a.scale && h2y_stream_scale(ctx, a.out.width, a.out.height, a.scale_taps)) return fail(h2y_last_error(ctx));
-    const size_t wb = a.scale ? h2y_scale_frame_bytes(a.out.width, a.out.height, a.out.chroma_format_idc) : ob; /* what comes down */
-    std::unique_ptr<unpack_pool> pool;
-    std::vector<h2y_exr_chunk> chunks;
-    if (a.in_type == CLI_IN_EXR) {
-        pool.reset(new unpack_pool(std::max(1, kUnpackThreads / std::max(1, a.gpus))));
-        chunks.resize((size_t)xi.n_chunks);
-    }
-    long in_flight = 0;
-    auto drain_one = [&]() -> bool {
-        const uint16_t *yuv = nullptr;
-        if (h2y_stream_output(ctx, &yuv)) { fail(h2y_last_error(ctx)); return false; }
-        const long k = b->first + b->done;
-        if (cmp.ref && h2y_stream_compare_result(ctx, &(*cmp.stats)[k])) { fail(h2y_last_error(ctx)); return false; }
-        if (a.ssim && h2y_stream_ssim_result(ctx, &(*ssim)[k])) { fail(h2y_last_error(ctx)); return false; }
-        if (!hist->take(ctx, k)) { fail(h2y_last_error(ctx)); return false; }
-        if (a.light && h2y_stream_light_result(ctx, &(*light)[k])) { fail(h2y_last_error(ctx)); return false; }
-        if (a.dst && !write_at(fd_out, yuv, wb, base + (off_t)k * (off_t)wb)) { fail(std::string("short write to ") + a.dst); return false; }
-        if (a.verbose > 0 && a.dst) printf("frame %ld: %zu bytes written to %s (device %d)\n", k, wb, a.dst, b->device);
-        b->done++;
-        in_flight--;
-        return true;
-    };
-    for (long f = 0; f < b->count; f++) {
-        void *planes[3];
-        if (h2y_stream_input(ctx, planes)) return fail(h2y_last_error(ctx));
-        if (a.in_type == CLI_IN_DPX) { /* the payload as the file holds it, straight into the pinned slot */
-            const dpx_src &src = dpx[b->first + f];
-            FILE *fd = fopen(src.path.c_str(), "rb");
-            if (!fd) return fail("unable to open file " + src.path);
-            size_t got = 0;
-            if (!fseeko(fd, (off_t)src.offset, SEEK_SET)) got = fread(planes[0], 1, di.payload_bytes, fd);
-            fclose(fd);
-            if (got != di.payload_bytes) return fail("only " + std::to_string(got) + " payload bytes read from " + src.path);
-        } else if (a.in_type == CLI_IN_TIFF) { /* the decoded rows, whole: one read when they lie back to back, else one per row */
-            const tiff_src &src = tiff[b->first + f];
-            const int fd = open(src.path.c_str(), O_RDONLY);
-            if (fd < 0) return fail("unable to open file " + src.path);
-            bool ok = true;
-            char *dst = static_cast<char *>(planes[0]);
-            if (src.contiguous) ok = read_at(fd, dst, ti.payload_bytes, (off_t)src.rows[0]);
-            else
-                for (size_t r = 0; ok && r < src.rows.size(); r++) ok = read_at(fd, dst + r * ti.row_bytes, ti.row_bytes, (off_t)src.rows[r]);
-            close(fd);
-            if (!ok) return fail("short read from " + src.path);
-        } else if (a.in_type == CLI_IN_EXR) { /* parsed again (the file may have changed since the scan), unpacked into the slot */
-            const std::string &path = exr[b->first + f];
-            mapped_file m;
-            if (!m.open(path)) return fail("read_exr() (exr.cpp:146): unable to open or read file " + path);
-            h2y_exr_info x2;
-            const char *why = nullptr;
-            if (h2y_exr_parse(m.p, m.n, &x2, chunks.data(), xi.n_chunks, &why)) return fail("read_exr() (exr.cpp): " + path + ": " + why);
-            if (memcmp(&x2, &xi, sizeof xi)) return fail("read_exr() (exr.cpp): " + path + " no longer has the header the run started with");
-            const std::string err = pool->run(xi, chunks.data(), m.p, planes[0]);
-            if (!err.empty()) return fail("read_exr() (exr.cpp): " + path + ": " + err);
-        } else if (fin) {
-            /* file plane order -> memory planes (0=G/Y, 1=B/Cb, 2=R/Cr); .rgb holds R,G,B (hdr2yuv.cpp:635-637) */
-            const int order_rgb[3] = {2, 0, 1}, order_nat[3] = {0, 1, 2};
-            const int *ord = a.in_type == CLI_IN_RGB ? order_rgb : order_nat;
-            size_t got = 0;
-            for (int k = 0; k < 3; k++) got += fread(planes[ord[k]], 1, pb, fin);
-            if (got != 3 * pb) return fail("only " + std::to_string(got) + " bytes read from " + a.src + ", expecting " + std::to_string(3 * pb));
-        } else synth_fill(d, planes, 12345u + (uint32_t)(a.synthetic + a.start_frame + b->first + f));
-        if (cmp.ref) {
-            void *ref = nullptr;
-            if (h2y_stream_reference(ctx, &ref)) return fail(h2y_last_error(ctx));
-            if (!read_ref(cmp.ref, false, 0, ob, ref)) return fail(std::string("short read from ") + a.ref);
-        }
-        if (h2y_stream_submit(ctx)) return fail(h2y_last_error(ctx));
-        in_flight++;
-        if (in_flight == depth - 1 && !drain_one()) return;
-    }
-    while (in_flight > 0)
-        if (!drain_one()) return;
-    h2y_stream_close(ctx);
-    if (fin) fclose(fin);
-    h2y_ctx_destroy(ctx);
-}
 
 /* the bytes libtiff writes around write_tiff()'s samples (h2y_tiff_layout) */
 struct tiff_wrap {
@@ -613,241 +189,294 @@ struct tiff_wrap {
     std::vector<uint8_t> tail;
 };
 
-/* .yuv -> RGB (matrix_inverse): frames [first, first+count) through one context's pinned inverse ring, as run_block; .tiff
- * output: the ring with the interleave (h2y_tiff_inverse_stream_open), frame k into its own file, head + samples + tail */
-static void run_block_inverse(const cli_args &a, const tiff_wrap &tw, int fd_out, off_t base, std::vector<h2y_compare_stats> *stats,
-                              std::vector<h2y_ssim_stats> *ssim, histogram_io *hist, block *b)
+/* what main resolved and every block of the run shares */
+struct job {
+    cli_args a;
+    h2y_desc d{};
+    scanned src;
+    tiff_wrap tw;
+    size_t in_frame_bytes = 0, out_frame_bytes = 0;
+    int fd_out = -1; /* the one destination file (not .tiff output), frames going in from `base` on */
+    off_t base = 0;
+};
+
+/* The reader fills the pinned slot of the pipeline directly, the writer drains what comes out of it two frames later: upload,
+ * conversion and download of neighbouring frames overlap. */
+static constexpr int kRingDepth = 3;
+
+/* What one of the five flows hands to run_block.  open and arm return the library's status; fill and write return "" or the
+ * block's error message. */
+struct flow {
+    std::function<int(h2y_ctx *)> open; /* the flow's ring, kRingDepth deep */
+    std::function<int(h2y_ctx *)> arm;  /* its stages, once the reference file is open (empty: none) */
+    size_t src_frame_bytes = 0;         /* of the one raw source file run_block opens and seeks; 0: the flow has none */
+    std::function<std::string(long, FILE *, void *const *)> fill; /* frame k (of that file, where there is one) into the slot's planes */
+    bool ref_rgb = false;               /* frame k of --ref_filename, where given, as read_ref takes it */
+    size_t ref_plane_bytes = 0, ref_frame_bytes = 0;
+    std::function<std::string(long, const uint16_t *)> write; /* frame k as it came down (empty: nothing is written) */
+    size_t out_bytes = 0;               /* what write writes */
+    bool says_written = false;          /* a written frame prints the --verbose_level line */
+};
+
+/* Frames [first, first + count) of the run through one context's pinned ring, the same way for every flow: frame k filled into a
+ * slot (and frame k of the reference beside it), submitted, and with two frames in flight the oldest taken out, measured and
+ * written.  Returns "" or the block's error; the guard tears down on every way out. */
+static std::string run_block(const cli_args &a, const flow &fl, results &res, int r, block *b)
 {
-    h2y_ctx *ctx = nullptr;
-    FILE *fin = nullptr;
-    auto fail = [&](const std::string &m) {
-        b->err = m;
-        if (ctx) { h2y_stream_close(ctx); h2y_ctx_destroy(ctx); }
-        if (fin) fclose(fin);
-    };
-    if (b->count < 1) return;
-    if (h2y_ctx_create(b->device, &ctx)) return fail(h2y_last_error(nullptr));
-    const size_t n = (size_t)a.in.width * a.in.height;
-    const bool sub = a.in.chroma_format_idc == H2Y_CHROMA_420;
-    const size_t nc = sub ? (size_t)(a.in.width / 2) * (a.in.height / 2) : n, in_frame = (n + 2 * nc) * 2, out_frame = 3 * n * 2;
-    fin = fopen(a.src, "rb");
-    if (!fin) return fail(std::string("unable to open file ") + a.src);
-    if (fseeko(fin, (off_t)in_frame * (off_t)(a.start_frame + b->first), SEEK_SET)) return fail("seek failed");
-    const int depth = 3;
-    const bool tiff = a.out_type == CLI_OUT_TIFF;
-    if ((tiff ? h2y_tiff_inverse_stream_open : h2y_inverse_stream_open)(ctx, a.in.width, a.in.height, a.in.chroma_format_idc,
-                                                                       a.in.bit_depth, a.in.video_full_range_flag, a.in.matrix_coeffs,
-                                                                       a.out.bit_depth, a.resampler, depth))
-        return fail(h2y_last_error(ctx));
-    compare_io cmp;
-    if (!cmp.open(a, b->first, 2 * n, out_frame, stats)) return fail(std::string("unable to read ") + a.ref);
-    if (cmp.ref && h2y_stream_compare(ctx, a.sigma, a.dst ? 1 : 0)) return fail(h2y_last_error(ctx));
-    if (a.ssim && h2y_stream_ssim(ctx, -1)) return fail(h2y_last_error(ctx));
-    if (hist->on && h2y_stream_histogram(ctx, a.hist_bits)) return fail(h2y_last_error(ctx));
-    long in_flight = 0;
-    auto drain_one = [&]() -> bool {
-        const uint16_t *gbr = nullptr;
-        if (h2y_stream_output(ctx, &gbr)) { fail(h2y_last_error(ctx)); return false; }
-        const long k = b->first + b->done;
-        if (cmp.ref && h2y_stream_compare_result(ctx, &(*cmp.stats)[k])) { fail(h2y_last_error(ctx)); return false; }
-        if (a.ssim && h2y_stream_ssim_result(ctx, &(*ssim)[k])) { fail(h2y_last_error(ctx)); return false; }
-        if (!hist->take(ctx, k)) { fail(h2y_last_error(ctx)); return false; }
-        if (!a.dst) {
-            b->done++;
-            in_flight--;
-            return true;
+    struct guard {
+        h2y_ctx *ctx = nullptr;
+        FILE *src = nullptr, *ref = nullptr;
+        ~guard()
+        {
+            if (ctx) { h2y_stream_close(ctx); h2y_ctx_destroy(ctx); } /* (closing is a no-op when no ring was opened) */
+            if (src) fclose(src);
+            if (ref) fclose(ref);
         }
-        if (tiff) { /* TIFFOpen(filename, "w"): a new file */
+    } g;
+    if (h2y_ctx_create(b->device, &g.ctx)) return h2y_last_error(nullptr);
+    auto library = [&] { return std::string(h2y_last_error(g.ctx)); };
+    if (fl.src_frame_bytes) {
+        g.src = fopen(a.src, "rb");
+        if (!g.src) return std::string("unable to open file ") + a.src;
+        if (fseeko(g.src, (off_t)fl.src_frame_bytes * (off_t)(a.start_frame + b->first), SEEK_SET)) return "seek failed"; /* hdr2yuv.cpp:624 */
+    }
+    if (fl.open(g.ctx)) return library();
+    if (a.ref) { /* R from its frame 0 on: this block's frames start at `first` */
+        g.ref = fopen(a.ref, "rb");
+        if (!g.ref || fseeko(g.ref, (off_t)fl.ref_frame_bytes * (off_t)b->first, SEEK_SET)) return std::string("unable to read ") + a.ref;
+    }
+    if (fl.arm && fl.arm(g.ctx)) return library();
+    long in_flight = 0;
+    auto drain_one = [&]() -> std::string {
+        const uint16_t *out = nullptr;
+        if (h2y_stream_output(g.ctx, &out)) return library();
+        const long k = b->first + b->done;
+        if (!res.take(a, g.ctx, k, r)) return library();
+        if (fl.write) {
+            const std::string err = fl.write(k, out);
+            if (!err.empty()) return err;
+            if (fl.says_written) printf("frame %ld: %zu bytes written to %s (device %d)\n", k, fl.out_bytes, a.dst, b->device);
+        }
+        b->done++;
+        in_flight--;
+        return "";
+    };
+    for (long f = 0; f < b->count; f++) {
+        void *planes[3];
+        if (h2y_stream_input(g.ctx, planes)) return library();
+        std::string err = fl.fill(b->first + f, g.src, planes);
+        if (!err.empty()) return err;
+        if (g.ref) {
+            void *ref = nullptr;
+            if (h2y_stream_reference(g.ctx, &ref)) return library();
+            if (!read_ref(g.ref, fl.ref_rgb, fl.ref_plane_bytes, fl.ref_frame_bytes, ref)) return std::string("short read from ") + a.ref;
+        }
+        if (h2y_stream_submit(g.ctx)) return library();
+        in_flight++;
+        if (in_flight == kRingDepth - 1 && !(err = drain_one()).empty()) return err;
+    }
+    while (in_flight > 0) {
+        const std::string err = drain_one();
+        if (!err.empty()) return err;
+    }
+    return "";
+}
+
+/* frame k at `base + k x bytes` of the one destination file */
+static std::function<std::string(long, const uint16_t *)> write_plain(const job &j, size_t bytes)
+{
+    return [&j, bytes](long k, const uint16_t *out) {
+        return write_at(j.fd_out, out, bytes, j.base + (off_t)k * (off_t)bytes) ? "" : std::string("short write to ") + j.a.dst;
+    };
+}
+
+/* the same for a .rgb: planes G, B, R of plane_bytes each -> file order R, G, B (write_tiff: R, G, B per pixel) */
+static std::function<std::string(long, const uint16_t *)> write_rgb(const job &j, size_t plane_bytes)
+{
+    return [&j, plane_bytes](long k, const uint16_t *out) {
+        const char *p = reinterpret_cast<const char *>(out);
+        const off_t at = j.base + (off_t)k * (off_t)(3 * plane_bytes);
+        return write_at(j.fd_out, p + 2 * plane_bytes, plane_bytes, at) && write_at(j.fd_out, p, 2 * plane_bytes, at + (off_t)plane_bytes)
+                   ? "" : std::string("short write to ") + j.a.dst;
+    };
+}
+
+/* forward path: the ring of h2y_stream_open, or for .dpx, .tiff and .exr the ring that decodes on the device what the file holds
+ * (frame k is file k of the scan) */
+static flow forward_flow(const job &j)
+{
+    const cli_args &a = j.a;
+    const scanned &s = j.src;
+    const size_t pb = h2y_plane_bytes(&j.d);
+    flow f;
+    f.open = [&j, &a, &s](h2y_ctx *ctx) {
+        return a.in_type == CLI_IN_DPX    ? h2y_dpx_stream_open(ctx, &j.d, &s.di, kRingDepth)
+               : a.in_type == CLI_IN_TIFF ? h2y_tiff_stream_open(ctx, &j.d, &s.ti, a.in.video_full_range_flag == 0, kRingDepth)
+               : a.in_type == CLI_IN_EXR  ? h2y_exr_stream_open(ctx, &j.d, &s.xi, kRingDepth)
+                                          : h2y_stream_open(ctx, &j.d, kRingDepth);
+    };
+    f.arm = [&a](h2y_ctx *ctx) {
+        return (a.ref && h2y_stream_compare(ctx, a.sigma, a.dst ? 1 : 0)) || (a.ssim && h2y_stream_ssim(ctx, -1)) ||
+               (a.hist && h2y_stream_histogram(ctx, a.hist_bits)) || (a.light && h2y_stream_light(ctx)) ||
+               (a.gamut && h2y_stream_gamut(ctx, a.in.colour_primaries, a.out.colour_primaries, a.gamut_clip)) ||
+               (a.scale && h2y_stream_scale(ctx, a.out.width, a.out.height, a.scale_taps));
+    };
+    if (a.in_type == CLI_IN_DPX) { /* the payload as the file holds it, straight into the pinned slot */
+        f.fill = [&s](long k, FILE *, void *const *planes) -> std::string {
+            const dpx_src &src = s.dpx[k];
+            FILE *fd = fopen(src.path.c_str(), "rb");
+            if (!fd) return "unable to open file " + src.path;
+            size_t got = 0;
+            if (!fseeko(fd, (off_t)src.offset, SEEK_SET)) got = fread(planes[0], 1, s.di.payload_bytes, fd);
+            fclose(fd);
+            return got == s.di.payload_bytes ? "" : "only " + std::to_string(got) + " payload bytes read from " + src.path;
+        };
+    } else if (a.in_type == CLI_IN_TIFF) { /* the decoded rows, whole: one read when they lie back to back, else one per row */
+        f.fill = [&s](long k, FILE *, void *const *planes) -> std::string {
+            const tiff_src &src = s.tiff[k];
+            const int fd = open(src.path.c_str(), O_RDONLY);
+            if (fd < 0) return "unable to open file " + src.path;
+            bool ok = true;
+            char *dst = static_cast<char *>(planes[0]);
+            if (src.contiguous) ok = read_at(fd, dst, s.ti.payload_bytes, (off_t)src.rows[0]);
+            else
+                for (size_t r = 0; ok && r < src.rows.size(); r++) ok = read_at(fd, dst + r * s.ti.row_bytes, s.ti.row_bytes, (off_t)src.rows[r]);
+            close(fd);
+            return ok ? "" : "short read from " + src.path;
+        };
+    } else if (a.in_type == CLI_IN_EXR) { /* parsed again (the file may have changed since the scan), unpacked into the slot */
+        struct unpacker { /* this block's own (a flow is made per block) */
+            unpack_pool pool;
+            std::vector<h2y_exr_chunk> chunks;
+            unpacker(int threads, int n_chunks) : pool(threads), chunks((size_t)n_chunks) {}
+        };
+        auto u = std::make_shared<unpacker>(std::max(1, kUnpackThreads / std::max(1, a.gpus)), s.xi.n_chunks);
+        f.fill = [&s, u](long k, FILE *, void *const *planes) -> std::string {
+            const std::string &path = s.exr[k];
+            mapped_file m;
+            if (!m.open(path)) return "read_exr() (exr.cpp:146): unable to open or read file " + path;
+            h2y_exr_info x2;
+            const char *why = nullptr;
+            if (h2y_exr_parse(m.p, m.n, &x2, u->chunks.data(), s.xi.n_chunks, &why)) return "read_exr() (exr.cpp): " + path + ": " + why;
+            if (memcmp(&x2, &s.xi, sizeof s.xi)) return "read_exr() (exr.cpp): " + path + " no longer has the header the run started with";
+            const std::string err = u->pool.run(s.xi, u->chunks.data(), m.p, planes[0]);
+            return err.empty() ? err : "read_exr() (exr.cpp): " + path + ": " + err;
+        };
+    } else if (a.in_type == CLI_IN_SYNTH) {
+        f.fill = [&j, &a](long k, FILE *, void *const *planes) {
+            synth_fill(j.d, planes, 12345u + (uint32_t)(a.synthetic + a.start_frame + k));
+            return std::string();
+        };
+    } else { /* .yuv, .rgb, .f32, .f16: three planes of the one source file */
+        f.src_frame_bytes = 3 * pb;
+        f.fill = [&a, pb](long, FILE *src, void *const *planes) -> std::string {
+            /* file plane order -> memory planes (0=G/Y, 1=B/Cb, 2=R/Cr); .rgb holds R,G,B (hdr2yuv.cpp:635-637) */
+            const int order_rgb[3] = {2, 0, 1}, order_nat[3] = {0, 1, 2};
+            const int *ord = a.in_type == CLI_IN_RGB ? order_rgb : order_nat;
+            size_t got = 0;
+            for (int p = 0; p < 3; p++) got += fread(planes[ord[p]], 1, pb, src);
+            return got == 3 * pb ? "" : "only " + std::to_string(got) + " bytes read from " + a.src + ", expecting " + std::to_string(3 * pb);
+        };
+    }
+    f.ref_frame_bytes = h2y_frame_bytes(&j.d);
+    f.out_bytes = j.out_frame_bytes; /* what comes down: the converted frame, or under --scale the scaled one */
+    if (a.dst) f.write = write_plain(j, f.out_bytes);
+    f.says_written = a.verbose > 0;
+    return f;
+}
+
+/* .yuv -> RGB (matrix_inverse): the inverse ring; .tiff output: the ring with the interleave (h2y_tiff_inverse_stream_open), frame
+ * k into its own file, head + samples + tail */
+static flow inverse_flow(const job &j)
+{
+    const cli_args &a = j.a;
+    const bool tiff = a.out_type == CLI_OUT_TIFF;
+    const size_t luma = (size_t)a.in.width * a.in.height * 2, chroma = (j.in_frame_bytes - luma) / 2, out_frame = j.out_frame_bytes;
+    flow f;
+    f.open = [&a, tiff](h2y_ctx *ctx) {
+        return (tiff ? h2y_tiff_inverse_stream_open : h2y_inverse_stream_open)(ctx, a.in.width, a.in.height, a.in.chroma_format_idc,
+                                                                              a.in.bit_depth, a.in.video_full_range_flag, a.in.matrix_coeffs,
+                                                                              a.out.bit_depth, a.resampler, kRingDepth);
+    };
+    f.arm = [&a](h2y_ctx *ctx) {
+        return (a.ref && h2y_stream_compare(ctx, a.sigma, a.dst ? 1 : 0)) || (a.ssim && h2y_stream_ssim(ctx, -1)) ||
+               (a.hist && h2y_stream_histogram(ctx, a.hist_bits));
+    };
+    f.src_frame_bytes = j.in_frame_bytes;
+    f.fill = [&a, luma, chroma](long, FILE *src, void *const *planes) {
+        const size_t got = fread(planes[0], 1, luma, src) + fread(planes[1], 1, chroma, src) + fread(planes[2], 1, chroma, src);
+        return got == luma + 2 * chroma ? "" : std::string("short read from ") + a.src;
+    };
+    f.ref_rgb = true, f.ref_plane_bytes = luma, f.ref_frame_bytes = out_frame;
+    f.out_bytes = out_frame;
+    if (a.dst && tiff)
+        f.write = [&j, &a, out_frame](long k, const uint16_t *gbr) { /* TIFFOpen(filename, "w"): a new file */
             const std::string path = cli_frame_name(a.dst, a.start_frame + k);
             const int fd = open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
-            const bool ok = fd >= 0 && write_at(fd, tw.head, sizeof tw.head, 0) && write_at(fd, gbr, out_frame, sizeof tw.head) &&
-                            write_at(fd, tw.tail.data(), tw.tail.size(), (off_t)(sizeof tw.head + out_frame));
+            const bool ok = fd >= 0 && write_at(fd, j.tw.head, sizeof j.tw.head, 0) && write_at(fd, gbr, out_frame, sizeof j.tw.head) &&
+                            write_at(fd, j.tw.tail.data(), j.tw.tail.size(), (off_t)(sizeof j.tw.head + out_frame));
             if (fd >= 0) close(fd);
-            if (!ok) { fail("unable to write " + path); return false; }
-            b->done++;
-            in_flight--;
-            return true;
-        }
-        const off_t at = base + (off_t)k * (off_t)out_frame;
-        /* planes G, B, R -> file order R, G, B (write_tiff: R, G, B per pixel) */
-        if (!write_at(fd_out, gbr + 2 * n, 2 * n, at) || !write_at(fd_out, gbr, 4 * n, at + (off_t)(2 * n))) {
-            fail(std::string("short write to ") + a.dst);
-            return false;
-        }
-        b->done++;
-        in_flight--;
-        return true;
-    };
-    for (long f = 0; f < b->count; f++) {
-        void *planes[3];
-        if (h2y_stream_input(ctx, planes)) return fail(h2y_last_error(ctx));
-        size_t got = fread(planes[0], 1, 2 * n, fin);
-        got += fread(planes[1], 1, 2 * nc, fin);
-        got += fread(planes[2], 1, 2 * nc, fin);
-        if (got != in_frame) return fail(std::string("short read from ") + a.src);
-        if (cmp.ref) {
-            void *ref = nullptr;
-            if (h2y_stream_reference(ctx, &ref)) return fail(h2y_last_error(ctx));
-            if (!read_ref(cmp.ref, true, 2 * n, out_frame, ref)) return fail(std::string("short read from ") + a.ref);
-        }
-        if (h2y_stream_submit(ctx)) return fail(h2y_last_error(ctx));
-        in_flight++;
-        if (in_flight == depth - 1 && !drain_one()) return;
-    }
-    while (in_flight > 0)
-        if (!drain_one()) return;
-    h2y_stream_close(ctx);
-    fclose(fin);
-    h2y_ctx_destroy(ctx);
+            return ok ? "" : "unable to write " + path;
+        };
+    else if (a.dst) f.write = write_rgb(j, luma);
+    return f;
 }
 
-/* --compare_only: frames [first, first+count) of the source against the same frames of R through one compare-only ring */
-static void run_block_compare(const cli_args &a, size_t plane_bytes, size_t frame_bytes, std::vector<h2y_compare_stats> *stats,
-                              std::vector<h2y_ssim_stats> *ssim, histogram_io *hist, block *b)
+/* the source of the three flows that convert nothing, .yuv or .rgb: the slot's planes lie one after the other, so a frame is
+ * one read, a .rgb one with its planes put in G, B, R order */
+static flow whole_frame_flow(const job &j)
 {
-    h2y_ctx *ctx = nullptr;
-    FILE *fin = nullptr;
-    auto fail = [&](const std::string &m) {
-        b->err = m;
-        if (ctx) { h2y_stream_close(ctx); h2y_ctx_destroy(ctx); }
-        if (fin) fclose(fin);
-    };
-    if (b->count < 1) return;
-    if (h2y_ctx_create(b->device, &ctx)) return fail(h2y_last_error(nullptr));
-    fin = fopen(a.src, "rb");
-    if (!fin) return fail(std::string("unable to open file ") + a.src);
-    if (fseeko(fin, (off_t)frame_bytes * (off_t)(a.start_frame + b->first), SEEK_SET)) return fail("seek failed");
-    compare_io cmp;
-    if (!cmp.open(a, b->first, plane_bytes, frame_bytes, stats)) return fail(std::string("unable to read ") + a.ref);
-    const int depth = 3;
-    if (h2y_compare_stream_open(ctx, a.in.width, a.in.height, a.in.chroma_format_idc, a.sigma, depth)) return fail(h2y_last_error(ctx));
-    if (a.ssim && h2y_stream_ssim(ctx, a.in.bit_depth)) return fail(h2y_last_error(ctx));
-    if (hist->on && h2y_stream_histogram_ex(ctx, a.hist_bits, a.hist_depth, a.hist_full, a.hist_gbr)) return fail(h2y_last_error(ctx));
-    long in_flight = 0;
-    auto drain_one = [&]() -> bool {
-        const uint16_t *none = nullptr;
-        const long k = b->first + b->done;
-        if (h2y_stream_output(ctx, &none) || h2y_stream_compare_result(ctx, &(*stats)[k]) ||
-            (a.ssim && h2y_stream_ssim_result(ctx, &(*ssim)[k])) || !hist->take(ctx, k)) {
-            fail(h2y_last_error(ctx));
-            return false;
-        }
-        b->done++;
-        in_flight--;
-        return true;
-    };
-    for (long f = 0; f < b->count; f++) {
-        void *planes[3], *ref = nullptr;
-        if (h2y_stream_input(ctx, planes) || h2y_stream_reference(ctx, &ref)) return fail(h2y_last_error(ctx));
-        /* the slot's planes lie one after the other: a frame is one read, a .rgb one with its planes put in G, B, R order */
-        if (!read_ref(fin, cmp.rgb, plane_bytes, frame_bytes, planes[0])) return fail(std::string("short read from ") + a.src);
-        if (!read_ref(cmp.ref, cmp.rgb, plane_bytes, frame_bytes, ref)) return fail(std::string("short read from ") + a.ref);
-        if (h2y_stream_submit(ctx)) return fail(h2y_last_error(ctx));
-        in_flight++;
-        if (in_flight == depth - 1 && !drain_one()) return;
-    }
-    while (in_flight > 0)
-        if (!drain_one()) return;
-    h2y_stream_close(ctx);
-    fclose(fin);
-    h2y_ctx_destroy(ctx);
-}
-
-/* --histogram_only: frames [first, first+count) of the source through one histogram-only ring */
-static void run_block_histogram(const cli_args &a, size_t plane_bytes, size_t frame_bytes, histogram_io *hist, block *b)
-{
-    h2y_ctx *ctx = nullptr;
-    FILE *fin = nullptr;
-    auto fail = [&](const std::string &m) {
-        b->err = m;
-        if (ctx) { h2y_stream_close(ctx); h2y_ctx_destroy(ctx); }
-        if (fin) fclose(fin);
-    };
-    if (b->count < 1) return;
-    if (h2y_ctx_create(b->device, &ctx)) return fail(h2y_last_error(nullptr));
-    fin = fopen(a.src, "rb");
-    if (!fin) return fail(std::string("unable to open file ") + a.src);
-    if (fseeko(fin, (off_t)frame_bytes * (off_t)(a.start_frame + b->first), SEEK_SET)) return fail("seek failed");
-    const int depth = 3;
-    if (h2y_histogram_stream_open(ctx, a.in.width, a.in.height, a.in.chroma_format_idc, a.hist_depth, a.hist_full, a.hist_gbr, a.hist_bits,
-                                  depth))
-        return fail(h2y_last_error(ctx));
+    const cli_args &a = j.a;
     const bool rgb = a.in_type == CLI_IN_RGB;
-    long in_flight = 0;
-    auto drain_one = [&]() -> bool {
-        const uint16_t *none = nullptr;
-        const long k = b->first + b->done;
-        if (h2y_stream_output(ctx, &none) || !hist->take(ctx, k)) { fail(h2y_last_error(ctx)); return false; }
-        b->done++;
-        in_flight--;
-        return true;
+    const size_t plane = (size_t)a.in.width * a.in.height * 2, frame = j.in_frame_bytes;
+    flow f;
+    f.src_frame_bytes = frame;
+    f.fill = [&a, rgb, plane, frame](long, FILE *src, void *const *planes) {
+        return read_ref(src, rgb, plane, frame, planes[0]) ? "" : std::string("short read from ") + a.src;
     };
-    for (long f = 0; f < b->count; f++) {
-        void *planes[3];
-        if (h2y_stream_input(ctx, planes)) return fail(h2y_last_error(ctx));
-        /* the slot's planes lie one after the other: a frame is one read, a .rgb one with its planes put in G, B, R order */
-        if (!read_ref(fin, rgb, plane_bytes, frame_bytes, planes[0])) return fail(std::string("short read from ") + a.src);
-        if (h2y_stream_submit(ctx)) return fail(h2y_last_error(ctx));
-        in_flight++;
-        if (in_flight == depth - 1 && !drain_one()) return;
-    }
-    while (in_flight > 0)
-        if (!drain_one()) return;
-    h2y_stream_close(ctx);
-    fclose(fin);
-    h2y_ctx_destroy(ctx);
+    f.ref_rgb = rgb, f.ref_plane_bytes = plane, f.ref_frame_bytes = frame; /* --compare_only: R has the source's layout */
+    return f;
 }
 
-/* --scale_only: frames [first, first+count) of the source through one scale-only ring into the destination */
-static void run_block_scale(const cli_args &a, size_t plane_bytes, size_t frame_bytes, size_t out_bytes, int fd_out, off_t base, block *b)
+/* --compare_only: the source against the same frames of R through one compare-only ring */
+static flow compare_flow(const job &j)
 {
-    h2y_ctx *ctx = nullptr;
-    FILE *fin = nullptr;
-    auto fail = [&](const std::string &m) {
-        b->err = m;
-        if (ctx) { h2y_stream_close(ctx); h2y_ctx_destroy(ctx); }
-        if (fin) fclose(fin);
+    const cli_args &a = j.a;
+    flow f = whole_frame_flow(j);
+    f.open = [&a](h2y_ctx *ctx) { return h2y_compare_stream_open(ctx, a.in.width, a.in.height, a.in.chroma_format_idc, a.sigma, kRingDepth); };
+    f.arm = [&a](h2y_ctx *ctx) {
+        return (a.ssim && h2y_stream_ssim(ctx, a.in.bit_depth)) ||
+               (a.hist && h2y_stream_histogram_ex(ctx, a.hist_bits, a.hist_depth, a.hist_full, a.hist_gbr));
     };
-    if (b->count < 1) return;
-    if (h2y_ctx_create(b->device, &ctx)) return fail(h2y_last_error(nullptr));
-    fin = fopen(a.src, "rb");
-    if (!fin) return fail(std::string("unable to open file ") + a.src);
-    if (fseeko(fin, (off_t)frame_bytes * (off_t)(a.start_frame + b->first), SEEK_SET)) return fail("seek failed");
-    const int depth = 3;
+    return f;
+}
+
+/* --histogram_only: the source through one histogram-only ring */
+static flow histogram_flow(const job &j)
+{
+    const cli_args &a = j.a;
+    flow f = whole_frame_flow(j);
+    f.open = [&a](h2y_ctx *ctx) {
+        return h2y_histogram_stream_open(ctx, a.in.width, a.in.height, a.in.chroma_format_idc, a.hist_depth, a.hist_full, a.hist_gbr, a.hist_bits,
+                                         kRingDepth);
+    };
+    return f;
+}
+
+/* --scale_only: the source through one scale-only ring into the destination */
+static flow scale_flow(const job &j)
+{
+    const cli_args &a = j.a;
     const bool rgb = a.in_type == CLI_IN_RGB;
-    if (h2y_scale_stream_open(ctx, a.in.width, a.in.height, a.in.chroma_format_idc, a.in.bit_depth, a.in.video_full_range_flag, rgb ? 1 : 0,
-                              a.out.width, a.out.height, a.scale_taps, depth))
-        return fail(h2y_last_error(ctx));
-    const size_t on = (size_t)a.out.width * a.out.height * 2; /* bytes of one full output plane */
-    long in_flight = 0;
-    auto drain_one = [&]() -> bool {
-        const uint16_t *out = nullptr;
-        if (h2y_stream_output(ctx, &out)) { fail(h2y_last_error(ctx)); return false; }
-        const long k = b->first + b->done;
-        const off_t at = base + (off_t)k * (off_t)out_bytes;
-        const char *p = reinterpret_cast<const char *>(out);
-        /* a .rgb: planes G, B, R -> file order R, G, B */
-        const bool ok = rgb ? write_at(fd_out, p + 2 * on, on, at) && write_at(fd_out, p, 2 * on, at + (off_t)on) : write_at(fd_out, p, out_bytes, at);
-        if (!ok) { fail(std::string("short write to ") + a.dst); return false; }
-        if (a.verbose > 0) printf("frame %ld: %zu bytes written to %s (device %d)\n", k, out_bytes, a.dst, b->device);
-        b->done++;
-        in_flight--;
-        return true;
+    flow f = whole_frame_flow(j);
+    f.open = [&a, rgb](h2y_ctx *ctx) {
+        return h2y_scale_stream_open(ctx, a.in.width, a.in.height, a.in.chroma_format_idc, a.in.bit_depth, a.in.video_full_range_flag, rgb ? 1 : 0,
+                                     a.out.width, a.out.height, a.scale_taps, kRingDepth);
     };
-    for (long f = 0; f < b->count; f++) {
-        void *planes[3];
-        if (h2y_stream_input(ctx, planes)) return fail(h2y_last_error(ctx));
-        /* the slot's planes lie one after the other: a frame is one read, a .rgb one with its planes put in G, B, R order */
-        if (!read_ref(fin, rgb, plane_bytes, frame_bytes, planes[0])) return fail(std::string("short read from ") + a.src);
-        if (h2y_stream_submit(ctx)) return fail(h2y_last_error(ctx));
-        in_flight++;
-        if (in_flight == depth - 1 && !drain_one()) return;
-    }
-    while (in_flight > 0)
-        if (!drain_one()) return;
-    h2y_stream_close(ctx);
-    fclose(fin);
-    h2y_ctx_destroy(ctx);
+    f.out_bytes = j.out_frame_bytes;
+    f.write = rgb ? write_rgb(j, (size_t)a.out.width * a.out.height * 2) : write_plain(j, f.out_bytes);
+    f.says_written = a.verbose > 0;
+    return f;
 }
 
 /* the histogram report of the header comment and FILE; returns the exit status (4: --check_range 1 and samples outside) */
@@ -1003,7 +632,9 @@ static void light_report(const std::vector<h2y_light_stats> &st)
 
 int main(int argc, char **argv)
 {
-    cli_args a;
+    job j;
+    cli_args &a = j.a;
+    scanned &s = j.src;
     cli_parse(a, argc, argv);
     if ((!a.dst && !a.ref && !a.hist && !a.hist_only && !a.light && !a.scale_only) || (!a.src && a.synthetic < 0)) {
         if (!a.help) cli_help();
@@ -1014,13 +645,11 @@ int main(int argc, char **argv)
         return 1;
     }
     /* read_exr() runs before anything else is checked and takes the size from the file: a dry run reads the .exr too */
-    std::vector<std::string> exr;
-    h2y_exr_info xi{};
     if (a.in_type == CLI_IN_EXR) {
-        if (exr_scan(a, a.n_frames > 0 ? a.n_frames : 1, xi, exr)) return 1;
+        if (exr_scan(a, a.n_frames > 0 ? a.n_frames : 1, s.xi, s.exr)) return 1;
         static const char *const kComp[] = {"NONE", "RLE", "ZIPS", "ZIP"};
-        printf("exr: %dx%d data window at (%d, %d), %s, %s y, %d channels, %d unpack threads per GPU\n", xi.width, xi.height, xi.x_min,
-               xi.y_min, kComp[xi.compression], xi.line_order ? "decreasing" : "increasing", xi.n_channels,
+        printf("exr: %dx%d data window at (%d, %d), %s, %s y, %d channels, %d unpack threads per GPU\n", s.xi.width, s.xi.height, s.xi.x_min,
+               s.xi.y_min, kComp[s.xi.compression], s.xi.line_order ? "decreasing" : "increasing", s.xi.n_channels,
                std::max(1, kUnpackThreads / std::max(1, a.gpus)));
         printf("src_picture: matrix_coeffs %d chroma_format_idc %d bit_depth %d video_full_range_flag %d\n", a.in.matrix_coeffs,
                a.in.chroma_format_idc, a.in.bit_depth, a.in.video_full_range_flag);
@@ -1031,55 +660,51 @@ int main(int argc, char **argv)
                "the GPU\n");
         return 1;
     }
-    h2y_desc d;
-    cli_make_desc(a, &d);
-    size_t in_frame_bytes, out_frame_bytes;
+    cli_make_desc(a, &j.d);
+    /* the flow, and the bytes of one frame as it reads and as it writes them */
+    flow (*make_flow)(const job &);
+    size_t &in_frame_bytes = j.in_frame_bytes, &out_frame_bytes = j.out_frame_bytes;
     if (a.compare_only || a.hist_only || a.scale_only) { /* two files of one layout, or one */
-        const size_t n = (size_t)a.in.width * a.in.height;
-        const size_t nc = a.in.chroma_format_idc == H2Y_CHROMA_420 ? (size_t)(a.in.width / 2) * (a.in.height / 2) : n;
-        in_frame_bytes = out_frame_bytes = (n + 2 * nc) * 2;
+        make_flow = a.hist_only ? histogram_flow : a.scale_only ? scale_flow : compare_flow;
+        in_frame_bytes = out_frame_bytes = planar16_bytes(a.in);
     } else if (a.inverse) {
         if (a.out.bit_depth > 16 || a.in.bit_depth > 16) { printf("ERROR: bit depths must be 8..16 on the inverse flow\n"); return 1; }
         if (a.out.bit_depth < a.in.bit_depth) { /* tiff.cpp:564: SR = dst - src depth, then `R << SR` */
             printf("ERROR: dst bit_depth(%d) < src bit_depth(%d): write_tiff() would shift by a negative count (undefined in the reference)\n", a.out.bit_depth, a.in.bit_depth);
             return 1;
         }
-        const size_t n = (size_t)a.in.width * a.in.height;
-        const size_t nc = a.in.chroma_format_idc == H2Y_CHROMA_420 ? (size_t)(a.in.width / 2) * (a.in.height / 2) : n;
-        in_frame_bytes = (n + 2 * nc) * 2;
-        out_frame_bytes = 3 * n * 2;
+        make_flow = inverse_flow;
+        in_frame_bytes = planar16_bytes(a.in);
+        out_frame_bytes = 3 * (size_t)a.in.width * a.in.height * 2;
     } else {
         const char *why = nullptr;
-        if (h2y_desc_check(&d, &why)) { printf("ERROR: %s\n", why); return 1; }
-        in_frame_bytes = 3 * h2y_plane_bytes(&d);
-        out_frame_bytes = h2y_frame_bytes(&d);
+        if (h2y_desc_check(&j.d, &why)) { printf("ERROR: %s\n", why); return 1; }
+        make_flow = forward_flow;
+        in_frame_bytes = 3 * h2y_plane_bytes(&j.d);
+        out_frame_bytes = h2y_frame_bytes(&j.d);
     }
     if (scaling) out_frame_bytes = h2y_scale_frame_bytes(a.out.width, a.out.height, a.out.chroma_format_idc); /* the scaled frame's */
 
     /* how many frames there are to do: --n_frames, or what the file holds from --src_start_frame on if that is fewer */
     long frames = a.n_frames > 0 ? a.n_frames : 1;
     struct stat st;
-    std::vector<dpx_src> dpx;
-    h2y_dpx_info di{};
-    std::vector<tiff_src> tiff;
-    h2y_tiff_info ti{};
-    if (a.in_type == CLI_IN_EXR) frames = (long)exr.size();
+    if (a.in_type == CLI_IN_EXR) frames = (long)s.exr.size();
     else if (a.in_type == CLI_IN_TIFF) { /* as .dpx */
         if (!(a.dry_run && stat(cli_frame_name(a.src, a.start_frame).c_str(), &st))) {
-            if (tiff_scan(a, frames, ti, tiff)) return 1;
-            frames = (long)tiff.size();
-            printf("tiff: %dx%d %s-endian, %d rows per strip, decoded %dx%d from (%d, %d), rows %s\n", ti.file_width, ti.file_height,
-                   ti.swap ? "big" : "little", ti.rows_per_strip, ti.width, ti.height, ti.x0, ti.y0,
-                   ti.contiguous ? "contiguous" : "scattered");
+            if (tiff_scan(a, frames, s.ti, s.tiff)) return 1;
+            frames = (long)s.tiff.size();
+            printf("tiff: %dx%d %s-endian, %d rows per strip, decoded %dx%d from (%d, %d), rows %s\n", s.ti.file_width, s.ti.file_height,
+                   s.ti.swap ? "big" : "little", s.ti.rows_per_strip, s.ti.width, s.ti.height, s.ti.x0, s.ti.y0,
+                   s.ti.contiguous ? "contiguous" : "scattered");
         }
         printf("src_picture: matrix_coeffs %d chroma_format_idc %d bit_depth %d video_full_range_flag %d\n", a.in.matrix_coeffs,
                a.in.chroma_format_idc, a.in.bit_depth, a.in.video_full_range_flag);
     } else if (a.in_type == CLI_IN_DPX) { /* one file per frame; a dry run may name a file that is not there */
         if (!(a.dry_run && stat(cli_frame_name(a.src, a.start_frame).c_str(), &st))) {
-            if (dpx_scan(a, frames, di, dpx)) return 1;
-            frames = (long)dpx.size();
-            printf("dpx: %dx%d %d-bit %s-endian, payload %llu bytes\n", di.width, di.height, di.bit_size, di.swap ? "big" : "little",
-                   (unsigned long long)di.payload_bytes);
+            if (dpx_scan(a, frames, s.di, s.dpx)) return 1;
+            frames = (long)s.dpx.size();
+            printf("dpx: %dx%d %d-bit %s-endian, payload %llu bytes\n", s.di.width, s.di.height, s.di.bit_size, s.di.swap ? "big" : "little",
+                   (unsigned long long)s.di.payload_bytes);
         }
         printf("src_picture: matrix_coeffs %d chroma_format_idc %d bit_depth %d video_full_range_flag %d\n", a.in.matrix_coeffs,
                a.in.chroma_format_idc, a.in.bit_depth, a.in.video_full_range_flag);
@@ -1120,7 +745,7 @@ int main(int argc, char **argv)
                cmp_yuv ? "yuv" : "rgb", a.out.width, a.out.height, cmp_yuv ? a.out.chroma_format_idc : H2Y_CHROMA_444, a.out.bit_depth,
                cmp_yuv ? "Y,Cb,Cr" : "G,B,R", frames, a.ref, a.sigma, a.compare_only ? "none (compare only)" : a.dst ? "kept" : "none (not written)");
     }
-    tiff_wrap tw;
+    tiff_wrap &tw = j.tw;
     if (a.out_type == CLI_OUT_TIFF) {
         if (frames > 1 && cli_frame_pattern(a.dst) != 1) {
             printf("ERROR: %ld frames into one .tiff: a .tiff holds one frame; name them with one integer conversion (shot.%%06d.tiff)\n",
@@ -1135,13 +760,11 @@ int main(int argc, char **argv)
     }
     if (a.dry_run) return 0;
 
-    /* tiff.cpp:440 opens ios::ate | ios::app: what is in the file stays, frames go behind it (.tiff: one file per frame, below) */
-    int fd = -1;
-    off_t base = 0;
+    /* tiff.cpp:440 opens ios::ate | ios::app: what is in the file stays, frames go behind it (.tiff: one file per frame) */
     if (a.dst && a.out_type != CLI_OUT_TIFF) {
-        fd = open(a.dst, O_WRONLY | O_CREAT, 0644);
-        if (fd < 0) { printf("ERROR: unable to open %s\n", a.dst); return 1; }
-        base = lseek(fd, 0, SEEK_END);
+        j.fd_out = open(a.dst, O_WRONLY | O_CREAT, 0644);
+        if (j.fd_out < 0) { printf("ERROR: unable to open %s\n", a.dst); return 1; }
+        j.base = lseek(j.fd_out, 0, SEEK_END);
     }
 
     /* contiguous blocks of frame indices, the first `frames % gpus` one longer (hdr2yuv_amd/shard.py) */
@@ -1153,28 +776,17 @@ int main(int argc, char **argv)
         blocks[r].count = frames / a.gpus + (r < frames % a.gpus ? 1 : 0);
         at += blocks[r].count;
     }
-    std::vector<h2y_compare_stats> stats(a.ref ? (size_t)frames : 0);
-    std::vector<h2y_ssim_stats> sstats(a.ssim ? (size_t)frames : 0);
-    std::vector<h2y_light_stats> lstats(a.light ? (size_t)frames : 0);
-    std::vector<h2y_histogram_stats> hstats(a.hist ? (size_t)frames : 0);
-    std::vector<std::array<uint32_t, 3>> hocc(a.hist ? (size_t)frames : 0);
-    std::vector<histogram_io> hist(a.gpus);
-    for (auto &x : hist) x.open(a, &hstats, &hocc);
-    auto work = [&](block *b) {
-        histogram_io *hi = &hist[b - blocks.data()];
-        if (a.hist_only) run_block_histogram(a, (size_t)a.in.width * a.in.height * 2, in_frame_bytes, hi, b);
-        else if (a.scale_only) run_block_scale(a, (size_t)a.in.width * a.in.height * 2, in_frame_bytes, out_frame_bytes, fd, base, b);
-        else if (a.compare_only) run_block_compare(a, (size_t)a.in.width * a.in.height * 2, in_frame_bytes, &stats, &sstats, hi, b);
-        else if (a.inverse) run_block_inverse(a, tw, fd, base, &stats, &sstats, hi, b);
-        else run_block(a, d, dpx, di, tiff, ti, exr, xi, fd, base, &stats, &sstats, &lstats, hi, b);
+    results res(a, frames);
+    auto work = [&](int r) { /* one GPU thread: its own flow (an .exr source keeps its unpack threads there), context and ring */
+        if (blocks[r].count > 0) blocks[r].err = run_block(a, make_flow(j), res, r, &blocks[r]);
     };
-    if (a.gpus == 1) work(&blocks[0]);
+    if (a.gpus == 1) work(0);
     else {
         std::vector<std::thread> th;
-        for (int r = 0; r < a.gpus; r++) th.emplace_back(work, &blocks[r]);
+        for (int r = 0; r < a.gpus; r++) th.emplace_back(work, r);
         for (auto &t : th) t.join();
     }
-    if (fd >= 0) close(fd);
+    if (j.fd_out >= 0) close(j.fd_out);
     int rc = 0;
     for (int r = 0; r < a.gpus; r++)
         if (!blocks[r].err.empty()) {
@@ -1183,15 +795,12 @@ int main(int argc, char **argv)
         }
     const bool ran = !rc;
     const bool compared = !rc && a.ref;
-    if (compared) rc = compare_report(a, cmp_yuv, a.out.bit_depth, stats);
-    if (compared && a.ssim) ssim_report(cmp_yuv, sstats);
-    if ((!rc || rc == 3) && a.hist) { /* the bins of every thread, summed (the same totals for any split) */
-        std::vector<uint64_t> total(hist[0].total.size(), 0u);
-        for (const auto &x : hist)
-            for (size_t i = 0; i < total.size(); i++) total[i] += x.total[i];
-        const int hrc = histogram_report(a, hstats, hocc, total);
+    if (compared) rc = compare_report(a, cmp_yuv, a.out.bit_depth, res.compare);
+    if (compared && a.ssim) ssim_report(cmp_yuv, res.ssim);
+    if ((!rc || rc == 3) && a.hist) {
+        const int hrc = histogram_report(a, res.hist, res.occupied, res.histogram_total());
         if (hrc == 1 || !rc) rc = hrc;
     }
-    if (ran && a.light) light_report(lstats);
+    if (ran && a.light) light_report(res.light);
     return rc;
 }

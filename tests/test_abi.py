@@ -92,6 +92,36 @@ def test_cli_built_and_fails_loudly_without_gpu(tmp_path):
                             str(tmp_path / "never.yuv"), "--src_bit_depth", "32", "--dst_bit_depth", "10", "--src_transfer_characteristics", "8", "--dst_transfer_characteristics", "16", "--dst_matrix_coeffs", "9",
                             "--dst_chroma_format_idc", "1", "--dst_video_full_range_flag", "0"], capture_output=True, text=True)
         assert r.returncode == 1 and "no CPU path" in r.stdout
+        # every flow, on one context and on two: each block that has frames fails on its own context and says so once; an
+        # empty block says nothing; the destination is created and stays empty
+        import numpy as np
+
+        w, hh, n420 = 32, 18, 32 * 18 + 2 * 16 * 9
+        np.zeros(5 * 3 * w * hh, np.float32).tofile(tmp_path / "in.f32")
+        np.zeros(5 * n420, np.uint16).tofile(tmp_path / "in.yuv")
+        size = ["--src_pic_width", w, "--src_pic_height", hh]
+        source = ["--src_filename", tmp_path / "in.yuv", "--src_bit_depth", 10, "--src_chroma_format_idc", 1] + size
+        flows = {
+            "forward": ["--src_filename", tmp_path / "in.f32", "--dst_filename", tmp_path / "forward.yuv", "--src_bit_depth", 32,
+                        "--dst_bit_depth", 10, "--src_transfer_characteristics", 8, "--dst_transfer_characteristics", 16,
+                        "--dst_matrix_coeffs", 9, "--dst_chroma_format_idc", 1] + size,
+            "inverse": source + ["--dst_filename", tmp_path / "inverse.rgb", "--src_matrix_coeffs", 9, "--dst_bit_depth", 12],
+            "compare": source + ["--compare_only", 1, "--ref_filename", tmp_path / "in.yuv"],
+            "histogram": source + ["--histogram_only", 1, "--histogram", tmp_path / "h.csv"],
+            "scale": source + ["--scale_only", 1, "--dst_filename", tmp_path / "scale.yuv", "--dst_pic_width", 16, "--dst_pic_height", 10],
+        }
+        for name, args in flows.items():
+            for frames, extra, ranges in ((5, [], ["0..4"]), (5, ["--gpus", 2, "--devices", "0,0"], ["0..2", "3..4"]),
+                                          (1, ["--gpus", 2, "--devices", "0,0"], ["0..0"])):
+                r = subprocess.run([exe] + [str(x) for x in args + ["--n_frames", frames] + extra], capture_output=True, text=True)
+                errors = [x for x in r.stdout.splitlines() if x.startswith("ERROR")]
+                assert r.returncode == 1, (name, r.stdout)
+                assert len(errors) == len(ranges), (name, r.stdout)
+                for line, rng in zip(errors, ranges):
+                    assert re.fullmatch(r"ERROR \(device 0, frames %s\): no HIP device \(.*\): this library has no CPU path" % re.escape(rng), line), line
+        for dst in ("forward.yuv", "inverse.rgb", "scale.yuv"):
+            assert os.path.getsize(tmp_path / dst) == 0
+        assert not os.path.exists(tmp_path / "h.csv")
 
 
 def test_experiment_variants_need_the_experiment_flag():
