@@ -39,6 +39,7 @@ EXPORTS = [
     "h2y_light_batch", "h2y_stream_light", "h2y_stream_light_result",
     "h2y_scale_taps", "h2y_scale_frame_bytes", "h2y_scale_batch", "h2y_stream_scale", "h2y_scale_stream_open",
     "h2y_gamut_matrix", "h2y_gamut_batch", "h2y_stream_gamut",
+    "h2y_ctx_set_chroma_siting", "h2y_subsample_420_sited",
 ]
 
 COMPARE_FRAMES_PER_LAUNCH = 64
@@ -308,6 +309,10 @@ def load_library():
     L.h2y_matrix_convert.argtypes = [C.c_void_p, C.POINTER(H2YDesc), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.h2y_subsample_420.restype = C.c_int
     L.h2y_subsample_420.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.h2y_subsample_420_sited.restype = C.c_int
+    L.h2y_subsample_420_sited.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.h2y_ctx_set_chroma_siting.restype = C.c_int
+    L.h2y_ctx_set_chroma_siting.argtypes = [C.c_void_p, C.c_int]
     L.h2y_matrix_inverse.restype = C.c_int
     L.h2y_matrix_inverse.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.h2y_upsample_444.restype = C.c_int
@@ -583,6 +588,10 @@ class Context:
         """h2y_ctx_set_option: "t1", "groups", "cols8", "balance", "fir" (tuning / test knobs; output bytes never change)."""
         self._check(self.lib.h2y_ctx_set_option(self.h, name.encode(), str(value).encode()))
 
+    def set_chroma_siting(self, chroma_sample_loc_type: int) -> None:
+        """h2y_ctx_set_chroma_siting: 0 as the resampler sites the 4:2:0 chroma (the default), 2 top-left (HDR10); before a ring is opened."""
+        self._check(self.lib.h2y_ctx_set_chroma_siting(self.h, chroma_sample_loc_type))
+
     def set_stream(self, hip_stream_ptr: int | None):
         self._check(self.lib.h2y_ctx_set_stream(self.h, C.c_void_p(hip_stream_ptr or 0)))
 
@@ -647,6 +656,10 @@ class Context:
 
     def subsample_420(self, width, height, bit_depth, resampler, src, dst) -> None:
         self._check(self.lib.h2y_subsample_420(self.h, width, height, bit_depth, resampler, self._ptr(src), self._ptr(dst)))
+
+    def subsample_420_sited(self, width, height, bit_depth, loc_type, src, dst) -> None:
+        """One u16 plane through the FIR, sited as chroma_sample_loc_type says: 0 the reference's, 2 top-left."""
+        self._check(self.lib.h2y_subsample_420_sited(self.h, width, height, bit_depth, loc_type, self._ptr(src), self._ptr(dst)))
 
     def last_kernel_ms(self):
         ms = C.c_float()

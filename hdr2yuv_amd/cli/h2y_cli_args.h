@@ -68,6 +68,14 @@
  *             (exit 1, also under --dry_run): a value other than 0 or 1, --gamut_clip without --gamut_convert 1, a source transfer
  *             other than 8 (LINEAR), a source matrix other than 0 (G,B,R), primaries other than 1, 8, 9, 10 and 12 or a pair of equal
  *             chromaticities, .rgb, .tiff and .yuv input, the .yuv -> RGB flow, --compare_only, --histogram_only and --scale_only.
+ * --dst_chroma_sample_loc_type 0|2 (an addition; the reference carries chroma_sample_loc_type through pic_t and prints it,
+ *             hdr2yuv.cpp:490 and :505, parses no flag for it and never acts on it): 2 writes the 4:2:0 chroma co-sited with the
+ *             top-left luma sample of every 2x2 block, as HDR10 and UHD Blu-ray assume (include/hdr2yuv_hip.h states every step); 0
+ *             is the FIR resampler's own siting, the bytes written without the flag.  On the forward flow to .yuv from every
+ *             input type, with any --gpus, with or without --dst_filename, beside --ref_filename, --ssim, --histogram,
+ *             --content_light and --gamut_convert.  Refused (exit 1, also under --dry_run): any other value (1 is the box
+ *             resampler's siting), 2 with --chroma_resampler_type 0, with --dst_chroma_format_idc 3, with --dst_matrix_coeffs 15,
+ *             with --scale 1 or --scale_only 1, on the .yuv -> RGB flow, with --compare_only 1 and with --histogram_only 1.
  * Only user_args_t.chroma_resampler_type has no defined default there (never initialised): FIR here, as in
  * make.sh's example.  The reference calls exit(0) on its argument errors; this program returns 1.
  */
@@ -114,6 +122,9 @@ struct cli_args {
     /* --gamut_convert 1: the source planes go from the source's to the destination's primaries; --gamut_clip (1 by default) */
     int gamut = 0, gamut_clip = 1;
     bool gamut_given = false, gamut_clip_given = false;
+    /* --dst_chroma_sample_loc_type: 0 as the resampler sites the 4:2:0 chroma, 2 top-left */
+    int siting = 0;
+    bool siting_given = false;
     /* the histogram: --histogram FILE, --histogram_bits (0: the counted frames' depth), --histogram_only, --check_range; what is
      * counted, resolved by cli_resolve_histogram: depth, range, G,B,R limits, chroma format */
     const char *hist = nullptr;
@@ -183,6 +194,8 @@ static inline void cli_help()
            "  primaries: [--gamut_convert 1 [--gamut_clip 0|1]] (float or half G,B,R source planes in linear light converted from\n"
            "  --src_colour_primaries to --dst_colour_primaries on the GPU before the conversion; 1 BT.709, 8 / 9 BT.2020, 12 P3-D65,\n"
            "  10 XYZ; what is not above 0 is clipped to 0 unless --gamut_clip 0)\n"
+           "  chroma siting: [--dst_chroma_sample_loc_type 0|2] (2: 4:2:0 chroma co-sited with the top-left luma sample, as HDR10\n"
+           "  assumes -- x265 --chromaloc 2, SVT-AV1 --chroma-sample-position topleft; needs the FIR resampler; 0: as without the flag)\n"
            "  scaling: [--scale 1 [--scale_taps A]] (with --dst_pic_width / --dst_pic_height: every .yuv frame resampled on the GPU by\n"
            "  an exact Lanczos filter of A = 2, 3 or 4 lobes, 3 by default; each axis ratio within 1/4 .. 4), [--scale_only 1] (a .yuv or\n"
            "  .rgb source into a destination of the same extension, no conversion)\n"
@@ -214,6 +227,7 @@ static inline void cli_parse(cli_args &a, int argc, char **argv)
         else if (is("--content_light")) { a.light = atoi(val()); a.light_given = true; }
         else if (is("--gamut_convert")) { a.gamut = atoi(val()); a.gamut_given = true; }
         else if (is("--gamut_clip")) { a.gamut_clip = atoi(val()); a.gamut_clip_given = true; }
+        else if (is("--dst_chroma_sample_loc_type")) { a.siting = atoi(val()); a.siting_given = true; }
         else if (is("--histogram")) a.hist = val();
         else if (is("--histogram_bits")) { a.hist_bits = atoi(val()); a.hist_bits_given = true; }
         else if (is("--histogram_only")) a.hist_only = atoi(val());
@@ -391,6 +405,7 @@ static inline int cli_resolve_light(cli_args &a);
 static inline int cli_resolve_scale_only(cli_args &a);
 static inline int cli_resolve_scale(cli_args &a);
 static inline int cli_resolve_gamut(cli_args &a, int src_matrix_arg);
+static inline int cli_resolve_siting(cli_args &a);
 static inline int cli_resolve(cli_args &a)
 {
     const int src_matrix_arg = a.in.matrix_coeffs; /* as given: the float readers force G,B,R on the input picture below */
@@ -403,6 +418,7 @@ static inline int cli_resolve(cli_args &a)
     if (a.light_given) arg_errors += cli_resolve_light(a);
     if (a.scale_given || a.scale_only || a.scale_taps_given) arg_errors += cli_resolve_scale(a);
     if (a.gamut_given || a.gamut_clip_given) arg_errors += cli_resolve_gamut(a, src_matrix_arg);
+    if (a.siting_given) arg_errors += cli_resolve_siting(a);
     return arg_errors;
 }
 
@@ -595,6 +611,52 @@ static inline int cli_resolve_gamut(cli_args &a, int src_matrix_arg)
     printf("gamut_matrix:");
     for (int i = 0; i < 9; i++) printf(" %.9g", m[i]);
     printf("\n");
+    return 0;
+}
+
+/* --dst_chroma_sample_loc_type: the siting of the forward flow's 4:2:0 chroma, 0 (the FIR resampler's own) or 2 (top-left); returns
+ * the number of argument errors */
+static inline int cli_resolve_siting(cli_args &a)
+{
+    printf("dst_chroma_sample_loc_type: %d\n", a.siting);
+    if (a.siting == 1) {
+        printf("WARNING: dst_chroma_sample_loc_type(1) is the box resampler's siting, --chroma_resampler_type 0: not selected by this flag\n");
+        return 1;
+    }
+    if (a.siting != 0 && a.siting != 2) {
+        printf("WARNING: dst_chroma_sample_loc_type(%d) not 0 or 2\n", a.siting);
+        return 1;
+    }
+    if (a.compare_only || a.hist_only) {
+        printf("WARNING: --dst_chroma_sample_loc_type sites a conversion's chroma: not with --%s 1\n",
+               a.compare_only ? "compare_only" : "histogram_only");
+        return 1;
+    }
+    if (a.inverse) {
+        printf("WARNING: --dst_chroma_sample_loc_type sites the forward flow's chroma (to .yuv): the .yuv -> RGB flow does not honour it\n");
+        return 1;
+    }
+    if (!a.siting) return 0;
+    if (a.scale_only) {
+        printf("WARNING: --dst_chroma_sample_loc_type 2 sites a conversion's chroma: not with --scale_only 1\n");
+        return 1;
+    }
+    if (a.out.chroma_format_idc != H2Y_CHROMA_420) {
+        printf("WARNING: --dst_chroma_sample_loc_type 2 sites 4:2:0 chroma: dst_chroma_format_idc(%d) has none to site\n", a.out.chroma_format_idc);
+        return 1;
+    }
+    if (a.resampler == 0) {
+        printf("WARNING: --dst_chroma_sample_loc_type 2 needs the FIR resampler: the box (--chroma_resampler_type 0) is centre sited by construction\n");
+        return 1;
+    }
+    if (a.out.matrix_coeffs == H2Y_MATRIX_YUVPRIME2) {
+        printf("WARNING: --dst_chroma_sample_loc_type 2 is not defined for dst_matrix_coeffs(%d)\n", a.out.matrix_coeffs);
+        return 1;
+    }
+    if (a.scale) {
+        printf("WARNING: --dst_chroma_sample_loc_type 2 is not combined with --scale 1: the scaler aligns sample centres and would move the siting\n");
+        return 1;
+    }
     return 0;
 }
 

@@ -85,6 +85,13 @@
  * converted in place on the device before pic_stats and the conversion: the run writes the bytes it would write had the source
  * held the converted planes, and --content_light beside it measures the converted light.  The banner carries gamut_convert:,
  * gamut_clip: and the nine entries of gamut_matrix: as "%.9g".
+ *
+ * Chroma siting (--dst_chroma_sample_loc_type 0|2 on the forward flow to .yuv; h2y_cli_args.h): each GPU thread sets its context's
+ * siting (h2y_ctx_set_chroma_siting) before it opens its ring, so every frame, and whatever is armed on the ring, has its 4:2:0
+ * chroma where the flag says.  The banner carries dst_chroma_sample_loc_type: only when the flag is given, and with 2 it ends with
+ * the settings that signal the siting to an encoder:
+ *   chroma_siting x265 --chromaloc 2
+ *   chroma_siting svt-av1 --chroma-sample-position topleft
  */
 #include <array>
 #include <cmath>
@@ -310,6 +317,7 @@ static flow forward_flow(const job &j)
     const size_t pb = h2y_plane_bytes(&j.d);
     flow f;
     f.open = [&j, &a, &s](h2y_ctx *ctx) {
+        if (a.siting && h2y_ctx_set_chroma_siting(ctx, a.siting)) return (int)H2Y_EINVAL; /* before the ring is opened */
         return a.in_type == CLI_IN_DPX    ? h2y_dpx_stream_open(ctx, &j.d, &s.di, kRingDepth)
                : a.in_type == CLI_IN_TIFF ? h2y_tiff_stream_open(ctx, &j.d, &s.ti, a.in.video_full_range_flag == 0, kRingDepth)
                : a.in_type == CLI_IN_EXR  ? h2y_exr_stream_open(ctx, &j.d, &s.xi, kRingDepth)
@@ -758,6 +766,7 @@ int main(int argc, char **argv)
         if (h2y_tiff_layout(a.in.width, a.in.height, tw.head, tw.tail.data(), &tb)) { printf("ERROR: %s\n", h2y_last_error(nullptr)); return 1; }
         printf("tiff_file_bytes: %zu\n", sizeof tw.head + out_frame_bytes + tb);
     }
+    if (a.siting == 2) printf("chroma_siting x265 --chromaloc 2\nchroma_siting svt-av1 --chroma-sample-position topleft\n");
     if (a.dry_run) return 0;
 
     /* tiff.cpp:440 opens ios::ate | ios::app: what is in the file stays, frames go behind it (.tiff: one file per frame) */

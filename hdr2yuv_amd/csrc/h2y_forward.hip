@@ -251,6 +251,7 @@ struct frames_run {
     pix_params pp;
     t1_sens sn;
     fused_variant var;
+    bool top_left = false; /* the context's chroma siting 2 applies: the second pass is k_fir420_tl */
 };
 
 balance balance_of(const h2y_ctx *ctx) { return balance{ctx->opt_bal_mode, ctx->opt_bal_mask, ctx->opt_bal_rho}; }
@@ -570,7 +571,7 @@ int launch_fused(h2y_ctx *ctx, const frames_run &r, const geom &g, const launch_
                          : var.mode == H2Y_MODE_YUVP2 ? "YUVP2" : "YPQRS";
         char buf[192];
         snprintf(buf, sizeof buf, "%s<%s,%s,%s,%s%s>%s groups=%d xcd=%d%s", h2y_fused_name(var), kIn[var.in_kind], kOut[var.out_kind], mode,
-                 kPipe[var.pipe], var.cols8 ? ",COLS8" : "", var.out_kind == H2Y_OUT_444TMP ? "+k_fir420" : yuvp2 ? (d->chroma_resampler_type ? "+k_yuvp2_420<FIR>" : "+k_yuvp2_420<BOX>") : "", groups, l.xcd_layout ? 1 : 0,
+                 kPipe[var.pipe], var.cols8 ? ",COLS8" : "", var.out_kind == H2Y_OUT_444TMP ? (r.top_left ? "+k_fir420_tl" : "+k_fir420") : yuvp2 ? (d->chroma_resampler_type ? "+k_yuvp2_420<FIR>" : "+k_yuvp2_420<BOX>") : "", groups, l.xcd_layout ? 1 : 0,
                  a.tail_ctr ? " tail=1" : "");
         if ((rc = timer_start(ctx, h2y_fused_name(var), buf))) return rc;
     }
@@ -592,8 +593,8 @@ int launch_fused(h2y_ctx *ctx, const frames_run &r, const geom &g, const launch_
     return 0;
 }
 
-/* The second pass of the staged frames [f0, f0 + nf), whose fused launch wrote scratch half `half`: k_yuvp2_420 or k_fir420 on
- * fir_stream behind that launch, so that it overlaps the next launch on the main stream */
+/* The second pass of the staged frames [f0, f0 + nf), whose fused launch wrote scratch half `half`: k_yuvp2_420, k_fir420 or
+ * (chroma siting 2) k_fir420_tl on fir_stream behind that launch, so that it overlaps the next launch on the main stream */
 int second_pass(h2y_ctx *ctx, const frames_run &r, bool yuvp2, int f0, int nf, int half)
 {
     const h2y_desc *d = r.d;
@@ -620,7 +621,7 @@ int second_pass(h2y_ctx *ctx, const frames_run &r, bool yuvp2, int f0, int nf, i
         fr.fir_max = r.pp.fir_max;
         fr.apply_yuv_clamp = 1;
         fr.pp = r.pp;
-        HIP_TRY(ctx, h2y_launch_fir420(ctx->fir_stream, fr));
+        HIP_TRY(ctx, r.top_left ? h2y_launch_fir420_tl(ctx->fir_stream, fr) : h2y_launch_fir420(ctx->fir_stream, fr));
     }
     HIP_TRY(ctx, hipEventRecord(ctx->ev_fir[half], ctx->fir_stream));
     ctx->fir_used[half] = true;
@@ -681,6 +682,21 @@ int launch_loop_form(h2y_ctx *ctx, const frames_run &r, bool yuvp2)
 
 } // namespace
 
+/* What the context's chroma siting (h2y_ctx_set_chroma_siting) makes of descriptor d: *top_left says whether the top-left form
+ * applies (not with siting 0, nor with 4:4:4 output, which has no siting); the status is the refusal of what siting 2 cannot site:
+ * the box is centre sited by construction, and Y'u'v' 4:2:0 has its own resamplers (k_yuvp2_420). */
+int siting_of(h2y_ctx *ctx, const h2y_desc *d, bool *top_left)
+{
+    *top_left = false;
+    if (ctx->opt_siting != 2 || d->dst_chroma_format_idc != H2Y_CHROMA_420) return H2Y_OK;
+    if (d->dst_matrix == H2Y_MATRIX_YUVPRIME2)
+        return fail(ctx, H2Y_EUNSUPPORTED, "chroma siting 2 (top-left) is not defined for dst_matrix_coeffs 15 with 4:2:0 output");
+    if (d->chroma_resampler_type == 0)
+        return fail(ctx, H2Y_EUNSUPPORTED, "chroma siting 2 (top-left) needs the FIR resampler: the 2x2 box (chroma_resampler_type 0) is centre sited by construction");
+    *top_left = true;
+    return H2Y_OK;
+}
+
 /* launch fused (+FIR) over frames [0,n) whose frame_io entries are in `frames`: derive the parameters, pick the variant, ask the
  * plan, and queue either one k_fir_fused launch or the loop-form launches of the batch */
 int run_frames(h2y_ctx *ctx, const h2y_desc *d, const frame_io *frames, int n, const assumed_stats *d_assumed,
@@ -690,13 +706,12 @@ int run_frames(h2y_ctx *ctx, const h2y_desc *d, const frame_io *frames, int n, c
      * output's range -- into scratch, and k_yuvp2_420 makes the .yuv frame of it (h2y_yuvp2.hip) */
     const bool yuvp2 = d->dst_matrix == H2Y_MATRIX_YUVPRIME2 && d->dst_chroma_format_idc == H2Y_CHROMA_420;
     frames_run r{d, frames, n, d_assumed, check, fstats_offset, time_it};
+    int rc = siting_of(ctx, d, &r.top_left); /* read once per call: the whole batch takes one path */
+    if (rc) return rc;
     derive_params(d, &r.pp, yuvp2);
     r.pp.pq_ext = ctx->d_table_ext;
     const int out_kind = yuvp2 ? H2Y_OUT_444 : out_kind_of(d);
-    if (yuvp2) {
-        const int rc = ensure_lin(ctx);
-        if (rc) return rc;
-    }
+    if (yuvp2 && (rc = ensure_lin(ctx))) return rc;
     fused_variant &var = r.var;
     var = pick_variant(ctx, d, r.pp, out_kind, known, &r.sn);
     /* k_fused_t1's redo list numbers tiles as frame * tiles + tile in 32 bits */
@@ -711,7 +726,8 @@ int run_frames(h2y_ctx *ctx, const h2y_desc *d, const frame_io *frames, int n, c
         }
         var.cols8 = ok;
     }
-    if (out_kind == H2Y_OUT_444TMP && ctx->opt_fir != 1 && var.t1_ok && !ctx->cur_skip_t1 && tmp_depth_of(d) <= H2Y_FIR_INT_MAX_DEPTH) {
+    /* (top-left siting has no one-pass form: decided here, before the plan is asked) */
+    if (out_kind == H2Y_OUT_444TMP && !r.top_left && ctx->opt_fir != 1 && var.t1_ok && !ctx->cur_skip_t1 && tmp_depth_of(d) <= H2Y_FIR_INT_MAX_DEPTH) {
         const fir_plan p = make_fir_plan(n, d->width, d->height, ctx->n_cu, ctx->opt_fir);
         if (p.take) return launch_fir_fused(ctx, r, p); /* the FIR resampler in one pass */
     }
@@ -1068,6 +1084,23 @@ int h2y_matrix_convert(h2y_ctx *ctx, const h2y_desc *d, const void *const d_in[3
     return H2Y_OK;
 }
 
+/* the stage entries' FIR: one u16 plane, no write_yuv clamp */
+static hipError_t launch_plane_fir(h2y_ctx *ctx, bool top_left, int width, int height, int bit_depth, const uint16_t *d_src, uint16_t *d_dst)
+{
+    fir_args fr;
+    memset(&fr, 0, sizeof fr);
+    fr.frames = nullptr;
+    fr.src_cb = d_src;
+    fr.src_cr = nullptr;
+    fr.dst_cb = d_dst;
+    fr.dst_cr = nullptr;
+    fr.width = width;
+    fr.height = height;
+    fr.fir_max = (float)((1u << bit_depth) - 1);
+    fr.apply_yuv_clamp = 0;
+    return top_left ? h2y_launch_fir420_tl(ctx->stream, fr) : h2y_launch_fir420(ctx->stream, fr);
+}
+
 int h2y_subsample_420(h2y_ctx *ctx, int width, int height, int bit_depth, int chroma_resampler_type, const uint16_t *d_src,
                       uint16_t *d_dst)
 {
@@ -1079,20 +1112,41 @@ int h2y_subsample_420(h2y_ctx *ctx, int width, int height, int bit_depth, int ch
     if (chroma_resampler_type == 0 && ((width & 3) || (height & 3))) return fail(ctx, H2Y_EINVAL, "box needs multiples of 4");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (chroma_resampler_type == 0) HIP_TRY(ctx, h2y_launch_box420(ctx->stream, d_src, d_dst, width, height));
-    else {
-        fir_args fr;
-        memset(&fr, 0, sizeof fr);
-        fr.frames = nullptr;
-        fr.src_cb = d_src;
-        fr.src_cr = nullptr;
-        fr.dst_cb = d_dst;
-        fr.dst_cr = nullptr;
-        fr.width = width;
-        fr.height = height;
-        fr.fir_max = (float)((1u << bit_depth) - 1);
-        fr.apply_yuv_clamp = 0;
-        HIP_TRY(ctx, h2y_launch_fir420(ctx->stream, fr));
-    }
+    else HIP_TRY(ctx, launch_plane_fir(ctx, false, width, height, bit_depth, d_src, d_dst));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return H2Y_OK;
+}
+
+int h2y_subsample_420_sited(h2y_ctx *ctx, int width, int height, int bit_depth, int chroma_sample_loc_type, const uint16_t *d_src,
+                            uint16_t *d_dst)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0)) return fail(ctx, H2Y_EINVAL, "a batch is pending");
+    if (ctx->streaming) return fail(ctx, H2Y_EINVAL, "a stream is open: close it first");
+    if (width < 2 || height < 2 || (width & 1) || (height & 1) || bit_depth < 8 || bit_depth > 16 || !d_src || !d_dst)
+        return fail(ctx, H2Y_EINVAL, "bad subsample arguments");
+    if (chroma_sample_loc_type != 0 && chroma_sample_loc_type != 2)
+        return fail(ctx, H2Y_EINVAL, "chroma_sample_loc_type %d: want 0 (the reference's FIR) or 2 (top-left)", chroma_sample_loc_type);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    /* timed like a batch entry's launch (h2y_last_kernel_ms / _name): tools/streambench.py holds the two kernels side by side */
+    HIP_TRY(ctx, hipEventRecord(ctx->b->ev[0][0], ctx->stream));
+    HIP_TRY(ctx, launch_plane_fir(ctx, chroma_sample_loc_type == 2, width, height, bit_depth, d_src, d_dst));
+    HIP_TRY(ctx, hipEventRecord(ctx->b->ev[0][1], ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->b->n_ev = 1;
+    HIP_TRY(ctx, event_ms(ctx->b, &ctx->last_ms));
+    ctx->last_launches = 1;
+    ctx->last_name = chroma_sample_loc_type == 2 ? "k_fir420_tl" : "k_fir420";
+    ctx->last_variant = ctx->last_name;
+    return H2Y_OK;
+}
+
+int h2y_ctx_set_chroma_siting(h2y_ctx *ctx, int chroma_sample_loc_type)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open: set the chroma siting before");
+    if (chroma_sample_loc_type != 0 && chroma_sample_loc_type != 2)
+        return fail(ctx, H2Y_EINVAL, "chroma_sample_loc_type %d: want 0 (as the resampler sites it) or 2 (top-left)", chroma_sample_loc_type);
+    ctx->opt_siting = chroma_sample_loc_type;
     return H2Y_OK;
 }

@@ -216,6 +216,7 @@ hipError_t h2y_launch_build_lut16(hipStream_t st, const void *table, float *lut)
 hipError_t h2y_launch_stats(int in_kind, int grid, hipStream_t st, const stats_args &a);
 hipError_t h2y_launch_stats_final(int n_frames, hipStream_t st, const final_args &a);
 hipError_t h2y_launch_fir420(hipStream_t st, const fir_args &a);
+hipError_t h2y_launch_fir420_tl(hipStream_t st, const fir_args &a); /* k_fir420_tl (h2y_siting.hip): the same arguments, top-left sited */
 hipError_t h2y_launch_inverse(int grid, hipStream_t st, const inverse_args &a);
 hipError_t h2y_launch_fir_fused(int in_kind, int mode, bool ident, bool lut16, int grid, hipStream_t st, const firf_args &a);
 hipError_t h2y_launch_up444(hipStream_t st, const up_args &a);

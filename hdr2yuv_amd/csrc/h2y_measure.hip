@@ -966,6 +966,9 @@ int h2y_stream_scale(h2y_ctx *ctx, int dst_w, int dst_h, int a)
         return fail(ctx, H2Y_EUNSUPPORTED, "a ring armed for comparison, histograms or SSIM is not scaled: compare or count the written file instead");
     if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
     const ring_frame &f = ctx->s_frame;
+    /* k_scale aligns sample centres: it would move a top-left sited chroma plane again (the setting cannot change while the ring is open) */
+    if (ctx->opt_siting == 2 && f.chroma == H2Y_CHROMA_420)
+        return fail(ctx, H2Y_EUNSUPPORTED, "a ring with chroma siting 2 (top-left) is not scaled: the resampler aligns sample centres");
     int rc = scale_check(ctx, f.width, f.height, dst_w, dst_h, f.chroma, f.depth, f.full_range, f.gbr, a);
     if (rc) return rc;
     return scale_arm(ctx, dst_w, dst_h, a);

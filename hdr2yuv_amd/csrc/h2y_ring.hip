@@ -119,6 +119,9 @@ static int open_forward_ring(h2y_ctx *ctx, const h2y_desc *d, const decode_src *
     const char *why;
     rc = h2y_desc_check(d, &why);
     if (rc) return fail(ctx, rc, "descriptor: %s", why);
+    bool top_left;
+    rc = siting_of(ctx, d, &top_left); /* what run_frames() would refuse for every frame */
+    if (rc) return rc;
     rc = dec.planes_check(ctx, d);
     if (rc) return rc;
     if (depth < 2 || depth > 16) return fail(ctx, H2Y_EINVAL, "depth must be 2..16");

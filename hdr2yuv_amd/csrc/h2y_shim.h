@@ -227,6 +227,7 @@ struct h2y_ctx {
     uint32_t opt_bal_mask = 0xFFu;
     double opt_bal_rho = 1.0;
     int opt_fir = 0;           /* "fir": 0 auto, 1 two-pass (4:4:4 scratch + k_fir420), 2 fused single pass where it applies */
+    int opt_siting = 0;        /* h2y_ctx_set_chroma_siting(): 0 as the resampler sites the chroma, 2 top-left (k_fir420_tl as the second pass) */
     int opt_fir_sync = -1;     /* "firsync": k_fir_fused's blocks meet at a barrier every so many steps (power of two; 0 = never);
                                   -1 = by the pictures: every step, never while the first tier passes many pixels on */
     double fir_flag_share = 0.0; /* share of the last k_fir_fused batch's pixels (in tiles of eight) the first tier could not settle */
@@ -443,6 +444,7 @@ void derive_params(const h2y_desc *d, pix_params *pp, bool stage_matrix_only);
 int ensure_tfn(h2y_ctx *ctx, int fn);
 int run_frames(h2y_ctx *ctx, const h2y_desc *d, const frame_io *frames, int n, const assumed_stats *d_assumed, const assumed_stats *known,
                bool check, int fstats_offset, bool time_it);
+int siting_of(h2y_ctx *ctx, const h2y_desc *d, bool *top_left); /* the context's chroma siting on d: applies, does not, or the refusal */
 int reserve_batch(h2y_ctx *ctx, int n);
 int run_stats(h2y_ctx *ctx, const h2y_desc *d, const void *const in[3], int slot, assumed_stats *publish);
 

@@ -749,6 +749,47 @@ int h2y_gamut_batch(h2y_ctx *ctx, int width, int height, int sample_type, int sr
  * first input, on a ring armed already, for equal chromaticities and a clip other than 0 or 1. */
 int h2y_stream_gamut(h2y_ctx *ctx, int src_primaries, int dst_primaries, int clip);
 
+/* ---- chroma siting: 4:2:0 chroma co-sited with the top-left luma sample (chroma_sample_loc_type 2; HDR10, UHD Blu-ray) -----------
+ * The reference carries chroma_sample_loc_type through pic_t and prints it (hdr2yuv.cpp:490, :505); it parses no flag for it and
+ * never acts on it.  Its two resamplers site the chroma as they happen to: the 2x2 box in the centre of the block both ways (loc
+ * type 1), Subsample444to420_FIR co-sited horizontally (an odd 7-tap filter at the even columns) and centred vertically (an even
+ * 12-tap filter, "0.5 sample interval phase shift", convert.cpp:364): loc type 0.  That is kept, bit for bit, by everything above.
+ * This is the project's own definition of loc type 2, built from the reference's filter.
+ * Input: a chroma plane T of W x H codes (W, H even): matrix_convert's output, not shifted and not yet clamped to the output's
+ *   range -- what the two-pass FIR form holds in scratch.  maxCV is the FIR's clip (fir_max; 2^bit_depth - 1 in the stage entry).
+ *   1. Horizontal, the reference's stage 1 unchanged: at every row j and every even column i
+ *        M[j][i/2] = fir_h(T[j][i-5], T[j][i-3], T[j][i-1], T[j][i], T[j][i+1], T[j][i+3], T[j][i+5]),  columns clamped into 0..W-1;
+ *      fir_h in binary32, every product and sum rounded by itself, in this order (convert.cpp:305-317):
+ *        acc = (21/512)(m5 + p5) - (52/512)(m3 + p3);  acc = acc + (159/512)(m1 + p1);  acc = acc + (256/512) c;  acc = acc + 0.5
+ *      then clamped to [0, maxCV] and truncated to u16.  The 4:2:2 intermediate M is the reference's, bit for bit.
+ *   2. Vertical, in exact integers: at every even row j = 2r, the same seven taps down the column,
+ *        S = 21 (M[j-5] + M[j+5]) - 52 (M[j-3] + M[j+3]) + 159 (M[j-1] + M[j+1]) + 256 M[j],  rows clamped into 0..H-1,
+ *        V = (S + 256) >> 9 (an arithmetic shift: the floor), clamped to [0, maxCV].  |S| < 2^26: int32 holds it.
+ *      An integer sum depends on no order of summation at 16-bit codes, where the binary32 form does; up to 14-bit codes it
+ *      equals fir_h down the column.
+ *   3. write_yuv's shift and per-plane range clamp, as after the reference's FIR (not in the stage entry).
+ *   4. Y is untouched.
+ * Not honoured by the .yuv -> RGB direction, whose upsampler assumes the reference's siting. */
+
+/* The siting of the 4:2:0 chroma this context's forward conversions write: 0 (the default) as the resampler sites it -- every byte
+ * as without this call -- or 2, top-left.  Any other value: H2Y_EINVAL.  H2Y_EINVAL too while a batch is in flight or a ring is
+ * open: set it before a ring is opened on the context.  It is read once per batch.  With 2:
+ *   - a descriptor with 4:2:0 output and chroma_resampler_type != 0 always runs the two-pass form, k_fir420_tl as its second pass
+ *     ("+k_fir420_tl" in h2y_last_kernel_variant); the "fir" option changes nothing then.  4:4:4 output is unaffected;
+ *   - h2y_convert_frame, h2y_convert_batch[_enqueue] and every forward ring (plain, DPX, TIFF, EXR) follow it, and what is armed on
+ *     a ring (compare, SSIM, histogram, light, gamut) sees the sited frame;
+ *   - H2Y_EUNSUPPORTED for 4:2:0 output with chroma_resampler_type 0 (the box is centre sited by construction) or with
+ *     dst_matrix_coeffs 15, and for h2y_stream_scale on a 4:2:0 ring of such a context (k_scale aligns sample centres: it would
+ *     move the siting again). */
+int h2y_ctx_set_chroma_siting(h2y_ctx *ctx, int chroma_sample_loc_type);
+
+/* The stage entry beside h2y_subsample_420: one U16 plane 4:4:4 -> 4:2:0 by the FIR, sited as chroma_sample_loc_type says: 0 the
+ * reference's FIR (h2y_subsample_420 with chroma_resampler_type 1), 2 the top-left form above.  maxCV = 2^bit_depth - 1; no
+ * write_yuv clamp.  d_src, d_dst: device pointers, 2-byte aligned.  Synchronous; h2y_last_kernel_ms gives the launch's time and
+ * h2y_last_kernel_name "k_fir420" or "k_fir420_tl". */
+int h2y_subsample_420_sited(h2y_ctx *ctx, int width, int height, int bit_depth, int chroma_sample_loc_type, const uint16_t *d_src,
+                            uint16_t *d_dst);
+
 /* Timing of the last h2y_convert_batch*() (or h2y_inverse_*, h2y_dpx_decode_batch, h2y_tiff_decode_batch,
  * h2y_rgb_interleave_batch, h2y_exr_decode_batch, h2y_compare_batch, h2y_ssim_batch, h2y_light_batch, h2y_scale_batch, h2y_gamut_batch) call measured with HIP events on
  * the stream the kernels ran on: total ms over the main kernels and how many
@@ -762,7 +803,7 @@ int h2y_last_kernel_ms(const h2y_ctx *ctx, float *ms, int *launches);
  * look for in a rocprofv3 kernel trace. */
 const char *h2y_last_kernel_name(const h2y_ctx *ctx);
 /* The same with its template arguments and launch shape, e.g. "k_fused_t1<F32,420BOX,YCBCR,PQ_IDENT> groups=8 xcd=1";
- * "+k_fir420" after the '>' when the chroma went through the two-pass FIR form.  Tests assert on it: which
+ * "+k_fir420" after the '>' when the chroma went through the two-pass FIR form ("+k_fir420_tl" with chroma siting 2).  Tests assert on it: which
  * variant a call took must not depend on what ran before. */
 const char *h2y_last_kernel_variant(const h2y_ctx *ctx);
 

@@ -88,6 +88,18 @@ Prints one line per figure, then one JSON line with all of them.
      24 B/pixel) timed the same way -- streaming kernels of the same shape that this change does not touch;
   3. frames/s from host memory of the .f32 ring and the half EXR ring (NONE) to PQ BT.2020nc 10-bit 4:2:0, unarmed and armed with
      h2y_stream_gamut.
+Prints one line per figure, then one JSON line with all of them.
+
+`streambench.py siting`: top-left co-sited 4:2:0 chroma (chroma siting 2) on 4K frames, in one job:
+  1. k_fir420 and k_fir420_tl through h2y_subsample_420_sited (loc 0 / loc 2) over the 128 distinct chroma planes of 64 frames, one
+     launch per plane (HIP events; the two planes of a frame added up), five passes: median and spread in us per frame, and the
+     5 B/pixel a frame's second pass moves (two 4:4:4 planes read, two 4:2:0 planes written) over that time as a share of the
+     8 TB/s HBM peak.  k_fir420 is the yardstick;
+  2. h2y_convert_batch of 64 C2 frames (fp32 -> PQ -> 12-bit BT.2020nc 4:2:0) with "fir" "twopass", siting 0 against siting 2:
+     wall time of a call (two kernels on two streams: there is no single kernel time), median and spread of five calls after a
+     warm-up, us per frame, and the two-pass form's 23 B/pixel over that time as a share of the peak;
+  3. the two sitings alternating, five calls each (ABAB...: drift of the card shows in both alike), the same figures; and the
+     default one-pass form (k_fir_fused, siting 0, "fir" "auto") in the same job: what a user gives up by choosing siting 2.
 Prints one line per figure, then one JSON line with all of them."""
 import os
 import sys
@@ -1130,8 +1142,94 @@ def gamut_main():
     print(json.dumps({"streambench_gamut": res}), flush=True)
 
 
+def siting_main():
+    import json
+
+    import torch
+
+    w, hh, nb, reps = 3840, 2160, 64, 5
+    n = w * hh
+    res = {"width": w, "height": hh, "frames_per_call": nb, "reps": reps, "hbm_peak_tbs": 8.0}
+
+    def figures(key, label, us, nbytes, extra=""):
+        """us: per-frame times of the passes"""
+        med = float(np.median(us))
+        tbs = nbytes / (med * 1e-6) / 1e12
+        res[key] = dict(us_per_frame=round(med, 2), min_us=round(min(us), 2), max_us=round(max(us), 2), bytes_per_frame=nbytes,
+                        tbs=round(tbs, 2), hbm_peak_fraction=round(tbs / 8.0, 3))
+        print(f"{label:44s} {med:8.2f} us/frame ({min(us):.2f}..{max(us):.2f})  {nbytes/1e6:6.1f} MB/frame  {tbs:5.2f} TB/s = "
+              f"{tbs/8.0*100:4.1f} % of 8 TB/s{extra}", flush=True)
+        return med
+
+    # 1. the two second-pass kernels alone, plane by plane, on 128 distinct 12-bit planes
+    ctx = h.Context(0)
+    planes = [torch.randint(0, 4096, (n,), dtype=torch.int16, device="cuda") for _ in range(2 * nb)]
+    outs = [torch.empty(n // 4, dtype=torch.int16, device="cuda") for _ in range(2 * nb)]
+    torch.cuda.synchronize()
+    per = {0: [], 2: []}
+    for r in range(reps + 1):  # the first pass warms up; the kernels alternate pass by pass
+        for loc in (0, 2):
+            ms = 0.0
+            for p, o in zip(planes, outs):
+                ctx.subsample_420_sited(w, hh, 12, loc, p, o)
+                ms += ctx.last_kernel_ms()[0]
+            if r:
+                per[loc].append(ms * 1e3 / nb)
+    ref = figures("k_fir420", "k_fir420 (loc 0), one launch per plane", per[0], 5 * n)
+    tl = figures("k_fir420_tl", "k_fir420_tl (loc 2), one launch per plane", per[2], 5 * n)
+    res["k_fir420_tl"]["of_k_fir420"] = round(tl / ref, 3)
+    res["k_fir420_tl"]["outside_yardstick_spread_on_the_slow_side"] = bool(tl > max(per[0]))
+    print(f"k_fir420_tl / k_fir420 = {tl/ref:.3f}; slower than the yardstick's slowest pass: {tl > max(per[0])}", flush=True)
+    del planes, outs
+    ctx.close()
+    torch.cuda.empty_cache()
+
+    # 2. and 3. the batch entry on C2
+    d = h.make_desc(w, hh, dst_depth=12, dst_matrix=h.MATRIX_BT2020NC, resampler=1)
+    frames = [[torch.rand(n, device="cuda") for _ in range(3)] for _ in range(nb)]
+    for fr in frames:
+        for p in fr:
+            p[0], p[1] = 0.0, 1.0  # floor 0, ceiling 1
+    outs = [torch.empty(h.frame_bytes(d) // 2, dtype=torch.int16, device="cuda") for _ in range(nb)]
+    torch.cuda.synchronize()
+    ctxs = {}
+    for key, fir, loc in (("twopass_siting0", "twopass", 0), ("twopass_siting2", "twopass", 2), ("fused_siting0", "auto", 0)):
+        c = h.Context(0)
+        c.set_option("fir", fir)
+        c.set_chroma_siting(loc)
+        ctxs[key] = c
+
+    def call(key):
+        t0 = time.perf_counter()
+        ctxs[key].convert_batch(d, frames, outs)  # synchronous: every frame final on return
+        return (time.perf_counter() - t0) * 1e6 / nb
+
+    for key in ctxs:  # warm-up: allocations, the statistics hint, the tier steering
+        call(key)
+        call(key)
+        res[key + "_variant"] = ctxs[key].last_kernel_variant()
+    back = {k: [call(k) for _ in range(reps)] for k in ("twopass_siting0", "twopass_siting2")}
+    t0 = figures("batch_twopass_siting0", 'h2y_convert_batch C2 "fir" "twopass", siting 0', back["twopass_siting0"], 23 * n)
+    t2 = figures("batch_twopass_siting2", 'h2y_convert_batch C2 "fir" "twopass", siting 2', back["twopass_siting2"], 23 * n, f"  ({res['twopass_siting2_variant']})")
+    alt = {k: [] for k in ctxs}
+    for _ in range(reps):
+        for k in ctxs:
+            alt[k].append(call(k))
+    a0 = figures("alternating_twopass_siting0", "alternating: two-pass, siting 0", alt["twopass_siting0"], 23 * n)
+    a2 = figures("alternating_twopass_siting2", "alternating: two-pass, siting 2", alt["twopass_siting2"], 23 * n)
+    af = figures("alternating_fused_siting0", 'alternating: "fir" "auto" (one pass), siting 0', alt["fused_siting0"], 15 * n, f"  ({res['fused_siting0_variant']})")
+    res["siting2_of_siting0_twopass"] = round(a2 / a0, 3)
+    res["siting2_of_default_one_pass"] = round(a2 / af, 3)
+    print(f"siting 2 / siting 0, both two-pass: back to back {t2/t0:.3f}, alternating {a2/a0:.3f}; siting 2 / the default one-pass form: {a2/af:.3f}", flush=True)
+    for c in ctxs.values():
+        c.close()
+    print(json.dumps({"streambench_siting": res}), flush=True)
+
+
 if __name__ == "__main__":
-    if sys.argv[1:] == ["gamut"]:
+    if sys.argv[1:] == ["siting"]:
+        siting_main()
+    elif sys.argv[1:] == ["gamut"]:
         gamut_main()
     elif sys.argv[1:] == ["scale"]:
         scale_main()
