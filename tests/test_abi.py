@@ -7,6 +7,7 @@ import subprocess
 
 import pytest
 
+import h2y_testing as ht
 import hdr2yuv_amd as h
 from hdr2yuv_amd import api
 
@@ -82,15 +83,12 @@ def test_context_fails_loudly_without_gpu():
 def test_cli_built_and_fails_loudly_without_gpu(tmp_path):
     import torch
 
-    exe = os.path.join(ROOT, "hdr2yuv_amd", "hdr2yuv")
-    if not os.path.exists(exe):
-        subprocess.run(["make", "-C", os.path.join(ROOT, "hdr2yuv_amd", "cli"), "--no-print-directory"], check=True)
-    r = subprocess.run([exe, "--help"], capture_output=True, text=True)
+    r = ht.run_cli(["--help"], timeout=None)
     assert r.returncode == 0 and "--dst_matrix_coeffs" in r.stdout and "--chroma_resampler_type" in r.stdout
     if not torch.cuda.is_available():
-        r = subprocess.run([exe, "--synthetic", "0", "--src_pic_width", "64", "--src_pic_height", "32", "--dst_filename",
-                            str(tmp_path / "never.yuv"), "--src_bit_depth", "32", "--dst_bit_depth", "10", "--src_transfer_characteristics", "8", "--dst_transfer_characteristics", "16", "--dst_matrix_coeffs", "9",
-                            "--dst_chroma_format_idc", "1", "--dst_video_full_range_flag", "0"], capture_output=True, text=True)
+        r = ht.run_cli(["--synthetic", "0", "--src_pic_width", "64", "--src_pic_height", "32", "--dst_filename",
+                        str(tmp_path / "never.yuv"), "--src_bit_depth", "32", "--dst_bit_depth", "10", "--src_transfer_characteristics", "8", "--dst_transfer_characteristics", "16", "--dst_matrix_coeffs", "9",
+                        "--dst_chroma_format_idc", "1", "--dst_video_full_range_flag", "0"], timeout=None)
         assert r.returncode == 1 and "no CPU path" in r.stdout
         # every flow, on one context and on two: each block that has frames fails on its own context and says so once; an
         # empty block says nothing; the destination is created and stays empty
@@ -113,7 +111,7 @@ def test_cli_built_and_fails_loudly_without_gpu(tmp_path):
         for name, args in flows.items():
             for frames, extra, ranges in ((5, [], ["0..4"]), (5, ["--gpus", 2, "--devices", "0,0"], ["0..2", "3..4"]),
                                           (1, ["--gpus", 2, "--devices", "0,0"], ["0..0"])):
-                r = subprocess.run([exe] + [str(x) for x in args + ["--n_frames", frames] + extra], capture_output=True, text=True)
+                r = ht.run_cli(args + ["--n_frames", frames] + extra, timeout=None)
                 errors = [x for x in r.stdout.splitlines() if x.startswith("ERROR")]
                 assert r.returncode == 1, (name, r.stdout)
                 assert len(errors) == len(ranges), (name, r.stdout)

@@ -22,6 +22,7 @@ from oracle import binding as ob
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import chroma_pictures as cp  # noqa: E402
+import h2y_testing as ht  # noqa: E402
 import yuvp2_files as yf  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -46,12 +47,6 @@ def _want(oracle, kw, kind):
     if key not in _wanted:
         _wanted[key] = [oracle.convert_frame(od, planes) for planes in _pictures(kind)]
     return _wanted[key]
-
-
-def _upload(planes):
-    import torch
-
-    return [torch.from_numpy(np.ascontiguousarray(p) if p.dtype == np.float32 else np.ascontiguousarray(p).view(np.int16)).cuda() for p in planes]
 
 
 def _where(i):
@@ -88,7 +83,7 @@ def run_batch(oracle, kw, kind, options, name, parts, want=None):
     try:
         for k, v in options.items():
             c.set_option(k, v)
-        dev_in = [_upload(planes) for planes in host]
+        dev_in = [[ht.dev(p) for p in planes] for planes in host]
         dev_out = [torch.zeros(h.frame_bytes(d) // 2, dtype=torch.int16, device="cuda") for _ in host]
         torch.cuda.synchronize()
         c.convert_batch(d, dev_in, dev_out)
@@ -195,22 +190,6 @@ IW, IH = 264, 40  # chroma 132 x 20: k_inverse420's 64 x 8 tiles and k_up444's 6
 INVERSE_DEPTHS = [(12, 16), (10, 10), (16, 10)]  # (in depth, out depth)
 
 
-def _dev(p):
-    import torch
-
-    return torch.from_numpy(np.ascontiguousarray(p).reshape(-1).view(np.int16)).cuda()
-
-
-def _zeros(n):
-    import torch
-
-    return torch.zeros(n, dtype=torch.int16, device="cuda")
-
-
-def _host(t):
-    return t.cpu().numpy().view(np.uint16)
-
-
 def _inverse_frames(depth, lo, hi):
     """(label, Cb, Cr) of every picture at the inside levels of [lo, hi] and at 0 / maxCV"""
     maxcv = (1 << depth) - 1
@@ -236,11 +215,11 @@ def test_upsample_444_clamps(ctx, oracle, depth):
         inside = []
         for k, (label, cb, cr) in enumerate(_inverse_frames(depth, lo, hi)):
             for src in (cb, cr):
-                dsrc, ddst = _dev(src), _zeros(IW * IH)
+                dsrc, ddst = ht.dev(src), ht.dev_zeros(IW * IH, np.uint16)
                 torch.cuda.synchronize()  # the context's stream does not wait for torch's
                 ctx.upsample_444(IW, IH, 1, lo, hi, dsrc, ddst)
                 want = oracle.up444(src, IW, IH, 1, lo, hi)
-                got = _host(ddst).reshape(IH, IW)
+                got = ht.host(ddst, np.uint16).reshape(IH, IW)
                 assert np.array_equal(got, want), (label, depth, lo, hi, int(np.count_nonzero(got != want)), np.argwhere(got != want)[:4].tolist())
                 if k < len(cp.PICTURES):
                     inside.append(want)
@@ -272,9 +251,9 @@ def test_inverse_420_and_batch(ctx, oracle, mat, alg):
         frames, want, inside = _inverse_case(oracle, ind, outd, mat, alg)
         if alg == 1:
             _reaches_both_ends(inside, 0, (1 << ind) - 1, f"inverse {ind} bits")
-        din = [[_dev(p) for p in planes] for _, planes in frames]
-        single = [[_zeros(IW * IH) for _ in range(3)] for _ in frames]
-        batch = [[_zeros(IW * IH) for _ in range(3)] for _ in frames]
+        din = [[ht.dev(p) for p in planes] for _, planes in frames]
+        single = [[ht.dev_zeros(IW * IH, np.uint16) for _ in range(3)] for _ in frames]
+        batch = [[ht.dev_zeros(IW * IH, np.uint16) for _ in range(3)] for _ in frames]
         torch.cuda.synchronize()
         for f in range(len(frames)):
             ctx.inverse_420(IW, IH, ind, 0, mat, outd, alg, din[f], single[f])
@@ -284,5 +263,5 @@ def test_inverse_420_and_batch(ctx, oracle, mat, alg):
         for f, (label, _) in enumerate(frames):
             for c in range(3):
                 for entry, outs in (("inverse_420", single), ("inverse_batch", batch)):
-                    got = _host(outs[f][c])
+                    got = ht.host(outs[f][c], np.uint16)
                     assert np.array_equal(got, want[f][c]), (entry, label, mat, ind, outd, alg, "GBR"[c], int(np.count_nonzero(got != want[f][c])))

@@ -4,7 +4,6 @@ program's --dst_chroma_sample_loc_type.  Everything is compared bit for bit with
 the oracle by tests/test_chroma_siting_host.py, which also holds the census of the two-level pictures: both clamps of the vertical
 stage act on about a tenth of their samples)."""
 import os
-import subprocess
 import sys
 import warnings
 
@@ -12,34 +11,19 @@ import numpy as np
 import pytest
 
 import hdr2yuv_amd as h
-from oracle import binding as ob
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import chroma_pictures as cp  # noqa: E402
+import h2y_testing as ht  # noqa: E402
 import siting_ref as sr  # noqa: E402
 from tiff_files import read_tiff, write_tiff  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GUARD = 0x7E57
 TL = "+k_fir420_tl"
 _SAMPLE = {"f32": h.SAMPLE_F32, "f16": h.SAMPLE_F16, "u16": h.SAMPLE_U16}
 _INPUT = {"f32": cp.planes_f32, "f16": cp.planes_f16, "u16": cp.planes_u16}
-
-
-def _descs(w, hh, **kw):
-    """the library's descriptor and the oracle's: the same bytes"""
-    d, od = h.make_desc(w, hh, **kw), ob.make_desc(w, hh, **kw)
-    assert bytes(d) == bytes(od)
-    return d, od
-
-
-def _dev(a):
-    import torch
-
-    a = np.ascontiguousarray(a)
-    return torch.from_numpy(a if a.dtype == np.float32 else a.view(np.int16)).cuda()
 
 
 # ---- the stage entry --------------------------------------------------------------------------------------------------------
@@ -52,9 +36,9 @@ def _stage(ctx, src, depth, loc, offset=0):
     hh, w = src.shape
     buf = np.full(offset + src.size, GUARD, np.uint16)
     buf[offset:] = src.reshape(-1)
-    d_src = _dev(buf)
+    d_src = ht.dev(buf)
     nc = (w >> 1) * (hh >> 1)
-    d_dst = _dev(np.full(nc + 16, GUARD, np.uint16))
+    d_dst = ht.dev(np.full(nc + 16, GUARD, np.uint16))
     ctx.subsample_420_sited(w, hh, depth, loc, d_src.data_ptr() + 2 * offset, d_dst.data_ptr() + 16)
     torch.cuda.synchronize()
     out = d_dst.cpu().numpy().view(np.uint16)
@@ -95,7 +79,7 @@ def test_stage_entry_loc_0_is_the_reference_fir(ctx, oracle, w, hh, depth):
     import torch
 
     src = _random_plane(w, hh, depth)
-    d_src, d_dst = _dev(src), _dev(np.zeros((hh >> 1) * (w >> 1), np.uint16))
+    d_src, d_dst = ht.dev(src), ht.dev(np.zeros((hh >> 1) * (w >> 1), np.uint16))
     ctx.subsample_420(w, hh, depth, 1, d_src, d_dst)
     torch.cuda.synchronize()
     old = d_dst.cpu().numpy().view(np.uint16).reshape(hh >> 1, w >> 1)
@@ -103,7 +87,7 @@ def test_stage_entry_loc_0_is_the_reference_fir(ctx, oracle, w, hh, depth):
 
 
 def test_stage_entry_refusals(ctx):
-    d_src, d_dst = _dev(np.zeros(64, np.uint16)), _dev(np.zeros(16, np.uint16))
+    d_src, d_dst = ht.dev(np.zeros(64, np.uint16)), ht.dev(np.zeros(16, np.uint16))
     for loc in (1, 3, 4, 5, -1):
         with pytest.raises(h.H2YError) as e:
             ctx.subsample_420_sited(8, 8, 10, loc, d_src, d_dst)
@@ -136,7 +120,7 @@ def test_whole_frame(oracle, kind, matrix):
             detail, columns = _INPUT[kind]("corners2", w, hh), _INPUT[kind]("cols3_by", w, hh)
             for depth in (10, 12, 16):
                 for full in (0, 1):
-                    d, od = _descs(w, hh, **_frame_kw(kind, matrix, depth, full))
+                    d, od = ht.descs(w, hh, **_frame_kw(kind, matrix, depth, full))
                     base, got = c0.convert_frame(d, detail), c2.convert_frame(d, detail)
                     want = sr.frame_top_left(oracle, od, detail)
                     where = (kind, matrix, w, hh, depth, full)
@@ -153,7 +137,7 @@ def test_whole_frame(oracle, kind, matrix):
 def test_444_output_is_unaffected(oracle):
     w, hh = 130, 66
     planes = cp.planes_f32("corners2", w, hh)
-    d, od = _descs(w, hh, dst_depth=10, chroma=h.CHROMA_444, resampler=1)
+    d, od = ht.descs(w, hh, dst_depth=10, chroma=h.CHROMA_444, resampler=1)
     c = h.Context(0)
     try:
         c.set_chroma_siting(2)
@@ -174,7 +158,7 @@ _batch = {}
 def _batch_frames(oracle):
     """70 frames of 64 x 32 and the restatement's .yuv frames, computed once"""
     if not _batch:
-        d, od = _descs(BW, BH, dst_depth=10, dst_matrix=h.MATRIX_BT2020NC, chroma=1, resampler=1)
+        d, od = ht.descs(BW, BH, dst_depth=10, dst_matrix=h.MATRIX_BT2020NC, chroma=1, resampler=1)
         frames = [oracle.synth_frame(BW, BH, 300 + k) for k in range(BN)]
         _batch.update(d=d, od=od, frames=frames, want=[sr.frame_top_left(oracle, od, fr) for fr in frames])
     return _batch["d"], _batch["od"], _batch["frames"], _batch["want"]
@@ -187,8 +171,8 @@ def _run_batch(c, d, frames):
     words = h.frame_bytes(d) // 2
     stride = words + 16
     order = np.random.default_rng(len(frames)).permutation(len(frames))
-    out = _dev(np.full(stride * len(frames), GUARD, np.uint16))
-    dev_in = [[_dev(p) for p in fr] for fr in frames]
+    out = ht.dev(np.full(stride * len(frames), GUARD, np.uint16))
+    dev_in = [[ht.dev(p) for p in fr] for fr in frames]
     torch.cuda.synchronize()
     c.convert_batch(d, dev_in, [out.data_ptr() + 2 * int(order[f]) * stride for f in range(len(frames))])
     res = out.cpu().numpy().view(np.uint16)
@@ -249,7 +233,7 @@ def test_setter_rules(ctx, oracle):
         assert e.value.code == h.api.H2Y_EINVAL
     import torch
 
-    dev_in = [[_dev(p) for p in fr] for fr in frames[:4]]
+    dev_in = [[ht.dev(p) for p in fr] for fr in frames[:4]]
     outs = [torch.zeros(h.frame_bytes(d) // 2, dtype=torch.int16, device="cuda") for _ in range(4)]
     torch.cuda.synchronize()
     ctx.convert_batch_enqueue(d, dev_in, outs)
@@ -271,34 +255,6 @@ def test_setter_rules(ctx, oracle):
 
 # ---- rings ------------------------------------------------------------------------------------------------------------------------
 
-def _ring(ctx, fill, n, refs=None, hist=None, depth=3):
-    """n frames through the open ring: fill(k, slots); the compared and counted figures of every frame where armed"""
-    got, cs, hs, inflight = [], [], [], 0
-
-    def take():
-        got.append(ctx.stream_output().copy())
-        if refs is not None:
-            cs.append(ctx.stream_compare_result())
-        if hist is not None:
-            st, bins = ctx.stream_histogram_result()
-            hs.append((st, bins.copy()))
-
-    for k in range(n):
-        fill(k, ctx.stream_input())
-        if refs is not None:
-            ctx.stream_reference()[:] = refs[k]
-        ctx.stream_submit()
-        inflight += 1
-        if inflight == depth - 1:
-            take()
-            inflight -= 1
-    while inflight:
-        take()
-        inflight -= 1
-    ctx.stream_close()
-    return got, cs, hs
-
-
 def test_plain_ring_with_compare_and_histogram(ctx, oracle):
     """the F32 ring with siting 2 writes the batch's frames, and what is armed on it sees the sited frame: compared with the
     siting-0 frame the luma's figures are zero and the chroma's are numpy's on the restatement's bytes"""
@@ -309,12 +265,8 @@ def test_plain_ring_with_compare_and_histogram(ctx, oracle):
     ctx.stream_open(d, 3)
     ctx.stream_compare(0, 1)
     ctx.stream_histogram(bits)
-
-    def fill(k, slots):
-        for dst, src in zip(slots, frames[k]):
-            dst[:] = src
-
-    got, cs, hs = _ring(ctx, fill, n, refs=refs, hist=True)
+    recs = ht.drive_ring(ctx, frames[:n], 3, refs=refs, results=("compare", "histogram"))
+    got, cs, hs = ([r[key] for r in recs] for key in ("out", "compare", "histogram"))
     planes = ((0, npix), (npix, npix + npix // 4), (npix + npix // 4, npix + npix // 2))
     for k in range(n):
         assert np.array_equal(got[k], want[k]), k
@@ -335,7 +287,7 @@ def test_tiff_ring(ctx, oracle):
     datas = [write_tiff(f) for f in rgbs]
     kw = dict(sample=h.SAMPLE_U16, src_depth=16, dst_depth=10, src_transfer=1, dst_transfer=1, src_primaries=1, dst_primaries=1,
               dst_matrix=h.MATRIX_BT709, chroma=1, resampler=1, full_range=0)
-    d, od = _descs(w, hh, **kw)
+    d, od = ht.descs(w, hh, **kw)
     planes = [read_tiff(f, full_range=0)[0] for f in rgbs]
     want = [sr.frame_top_left(oracle, od, p) for p in planes]
     with warnings.catch_warnings():
@@ -343,17 +295,14 @@ def test_tiff_ring(ctx, oracle):
         parsed = [h.parse_tiff(x, 0) for x in datas]
     info = parsed[0][0]
     rb = int(info.row_bytes)
-
-    def fill(k, slots):
-        slots[0][:] = np.frombuffer(b"".join(datas[k][int(o):int(o) + rb] for o in parsed[k][1]), np.uint8)
-
+    pays = [[np.frombuffer(b"".join(x[int(o):int(o) + rb] for o in rows), np.uint8)] for x, (_, rows) in zip(datas, parsed)]
     ctx.set_chroma_siting(2)
     ctx.tiff_stream_open(d, info, 1, 3)
-    got, _, _ = _ring(ctx, fill, 4)
+    got = [r["out"] for r in ht.drive_ring(ctx, pays, 3)]
     import torch
 
     outs = [torch.zeros(h.frame_bytes(d) // 2, dtype=torch.int16, device="cuda") for _ in planes]
-    ctx.convert_batch(d, [[_dev(p) for p in fr] for fr in planes], outs)
+    ctx.convert_batch(d, [[ht.dev(p) for p in fr] for fr in planes], outs)
     assert TL in ctx.last_kernel_variant()
     for k in range(4):
         assert np.array_equal(got[k], want[k]), k
@@ -380,7 +329,7 @@ def test_refusals(ctx, oracle):
     yuvp2 = h.make_desc(w, hh, sample=h.SAMPLE_U16, src_depth=16, dst_depth=16, src_transfer=16, dst_transfer=16, dst_matrix=15, chroma=1, resampler=1)
     for d, host in ((box, planes), (yuvp2, codes)):
         out = [torch.zeros(h.frame_bytes(d) // 2, dtype=torch.int16, device="cuda")]
-        frames = [[_dev(p) for p in host]]
+        frames = [[ht.dev(p) for p in host]]
         _refused(lambda: ctx.convert_frame(d, host))
         _refused(lambda: ctx.convert_batch(d, frames, out))
         _refused(lambda: ctx.convert_batch_enqueue(d, frames, out))
@@ -405,19 +354,6 @@ def test_refusals(ctx, oracle):
 
 # ---- the command line ----------------------------------------------------------------------------------------------------------------
 
-def _exe():
-    exe = os.path.join(ROOT, "hdr2yuv_amd", "hdr2yuv")
-    if not os.path.exists(exe):
-        subprocess.run(["make", "-C", os.path.join(ROOT, "hdr2yuv_amd", "cli"), "--no-print-directory"], check=True)
-    return exe
-
-
-def _run(args):
-    r = subprocess.run([_exe()] + [str(a) for a in args], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return r.stdout
-
-
 def test_cli(tmp_path, oracle):
     """.f32 -> .yuv: with the flag the restatement's bytes, from one GPU thread and from two; without it the bytes of today"""
     d, od, frames, want = _batch_frames(oracle)
@@ -426,18 +362,18 @@ def test_cli(tmp_path, oracle):
     args = ["--src_filename", tmp_path / "in.f32", "--src_pic_width", BW, "--src_pic_height", BH, "--src_bit_depth", 32, "--dst_bit_depth", 10,
             "--dst_chroma_format_idc", 1, "--src_matrix_coeffs", 0, "--dst_matrix_coeffs", 9, "--src_transfer_characteristics", 8,
             "--dst_transfer_characteristics", 16, "--src_colour_primaries", 9, "--dst_colour_primaries", 9, "--n_frames", n]
-    out = _run(args + ["--dst_filename", tmp_path / "tl.yuv", "--dst_chroma_sample_loc_type", 2])
+    out = ht.cli_ok(args + ["--dst_filename", tmp_path / "tl.yuv", "--dst_chroma_sample_loc_type", 2], timeout=120).stdout
     assert "dst_chroma_sample_loc_type: 2" in out.splitlines() and "chroma_siting x265 --chromaloc 2" in out.splitlines()
     sited = b"".join(w.tobytes() for w in want[:n])
     assert (tmp_path / "tl.yuv").read_bytes() == sited
-    _run(args + ["--dst_filename", tmp_path / "tl2.yuv", "--dst_chroma_sample_loc_type", 2, "--gpus", 2, "--devices", "0,0"])
+    ht.cli_ok(args + ["--dst_filename", tmp_path / "tl2.yuv", "--dst_chroma_sample_loc_type", 2, "--gpus", 2, "--devices", "0,0"], timeout=120)
     assert (tmp_path / "tl2.yuv").read_bytes() == sited
     plain = b"".join(oracle.convert_frame(od, fr).tobytes() for fr in frames[:n])
-    out = _run(args + ["--dst_filename", tmp_path / "plain.yuv"])
+    out = ht.cli_ok(args + ["--dst_filename", tmp_path / "plain.yuv"], timeout=120).stdout
     assert "chroma_sample_loc_type" not in out and "chroma_siting" not in out
     assert (tmp_path / "plain.yuv").read_bytes() == plain and plain != sited
-    _run(args + ["--dst_filename", tmp_path / "zero.yuv", "--dst_chroma_sample_loc_type", 0])
+    ht.cli_ok(args + ["--dst_filename", tmp_path / "zero.yuv", "--dst_chroma_sample_loc_type", 0], timeout=120)
     assert (tmp_path / "zero.yuv").read_bytes() == plain
     # beside the comparison: the ring's compare stage sees the sited frame (a sample off would end the run with status 3)
-    out = _run(args + ["--ref_filename", tmp_path / "tl.yuv", "--sigma_compare", 0, "--dst_chroma_sample_loc_type", 2])
+    out = ht.cli_ok(args + ["--ref_filename", tmp_path / "tl.yuv", "--sigma_compare", 0, "--dst_chroma_sample_loc_type", 2], timeout=120).stdout
     assert "chroma_siting svt-av1 --chroma-sample-position topleft" in out.splitlines()

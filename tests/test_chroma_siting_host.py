@@ -1,7 +1,6 @@
 """Top-left co-sited 4:2:0 chroma (chroma_sample_loc_type 2), the parts that need no GPU: tests/siting_ref.py's restatement against
 the oracle and by hand, the census of the test pictures under the new vertical stage, and the host program's flag."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -11,9 +10,8 @@ from oracle import binding as ob
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import chroma_pictures as cp  # noqa: E402
+import h2y_testing as ht  # noqa: E402
 import siting_ref as sr  # noqa: E402
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZES = ((2, 2), (6, 4), (130, 66), (496, 260))
 DEPTHS = (10, 12, 16)
 
@@ -138,23 +136,6 @@ FLAG = "--dst_chroma_sample_loc_type"
 ENCODER = ["chroma_siting x265 --chromaloc 2", "chroma_siting svt-av1 --chroma-sample-position topleft"]
 
 
-def _exe():
-    exe = os.path.join(ROOT, "hdr2yuv_amd", "hdr2yuv")
-    if not os.path.exists(exe):
-        subprocess.run(["make", "-C", os.path.join(ROOT, "hdr2yuv_amd", "cli"), "--no-print-directory"], check=True)
-    return exe
-
-
-def _run(args):
-    r = subprocess.run([_exe()] + [str(a) for a in args], capture_output=True, text=True, timeout=60)
-    return r.returncode, r.stdout
-
-
-def _file(path, nbytes):
-    np.zeros(nbytes, np.uint8).tofile(path)
-    return path
-
-
 def _forward(src, depth=32, chroma=1, matrix=9, extra=()):
     return ["--src_filename", src, "--src_pic_width", W, "--src_pic_height", HH, "--src_bit_depth", depth, "--dst_bit_depth", 10,
             "--dst_chroma_format_idc", chroma, "--src_matrix_coeffs", 0, "--dst_matrix_coeffs", matrix, "--src_transfer_characteristics", 8,
@@ -163,22 +144,22 @@ def _forward(src, depth=32, chroma=1, matrix=9, extra=()):
 
 
 def test_dry_run_prints_the_setting(tmp_path):
-    src = _file(tmp_path / "in.f32", 2 * 3 * W * HH * 4)
-    ref = _file(tmp_path / "ref.yuv", 2 * (W * HH * 3 // 2) * 2)
+    src = ht.zero_file(tmp_path / "in.f32", 2 * 3 * W * HH * 4)
+    ref = ht.zero_file(tmp_path / "ref.yuv", 2 * (W * HH * 3 // 2) * 2)
     dst = ["--dst_filename", tmp_path / "o.yuv"]
     for extra in (dst, ["--content_light", 1], dst + ["--histogram", tmp_path / "h.csv"], dst + ["--ref_filename", ref, "--ssim", 1],
                   dst + ["--gamut_convert", 1], dst + ["--gpus", 2], dst + ["--chroma_resampler_type", 1]):
-        rc0, out0 = _run(_forward(src, extra=extra))
-        assert rc0 == 0, out0
-        assert "chroma_sample_loc_type" not in out0 and "chroma_siting" not in out0  # without the flag: the lines as they were
-        rc, out = _run(_forward(src, extra=extra + [FLAG, 2]))
-        assert rc == 0, out
-        lines = out.splitlines()
+        r0 = ht.run_cli(_forward(src, extra=extra), timeout=60)
+        assert r0.returncode == 0, r0.stdout
+        assert "chroma_sample_loc_type" not in r0.stdout and "chroma_siting" not in r0.stdout  # without the flag: the lines as they were
+        r = ht.run_cli(_forward(src, extra=extra + [FLAG, 2]), timeout=60)
+        assert r.returncode == 0, r.stdout
+        lines = r.stdout.splitlines()
         assert "dst_chroma_sample_loc_type: 2" in lines and lines[-2:] == ENCODER
-        assert [x for x in lines if x != "dst_chroma_sample_loc_type: 2" and x not in ENCODER] == out0.splitlines()
-        rc, out = _run(_forward(src, extra=extra + [FLAG, 0]))  # 0: printed, nothing else
-        assert rc == 0 and [x for x in out.splitlines() if x != "dst_chroma_sample_loc_type: 0"] == out0.splitlines()
-        assert "dst_chroma_sample_loc_type: 0" in out.splitlines()
+        assert [x for x in lines if x != "dst_chroma_sample_loc_type: 2" and x not in ENCODER] == r0.stdout.splitlines()
+        r = ht.run_cli(_forward(src, extra=extra + [FLAG, 0]), timeout=60)  # 0: printed, nothing else
+        assert r.returncode == 0 and [x for x in r.stdout.splitlines() if x != "dst_chroma_sample_loc_type: 0"] == r0.stdout.splitlines()
+        assert "dst_chroma_sample_loc_type: 0" in r.stdout.splitlines()
     assert not (tmp_path / "o.yuv").exists()
 
 
@@ -193,26 +174,26 @@ def test_dry_run_every_input_type(tmp_path, ext, depth):
         src = tmp_path / "in.exr"
         src.write_bytes(xf.write_exr({"R": (xf.HALF, g), "G": (xf.HALF, g), "B": (xf.HALF, g)})[0])
     elif ext in ("f16", "rgb"):
-        src = _file(tmp_path / f"in.{ext}", 2 * 3 * W * HH * 2)
+        src = ht.zero_file(tmp_path / f"in.{ext}", 2 * 3 * W * HH * 2)
     args = _forward(src, depth=depth, extra=["--dst_filename", tmp_path / "o.yuv", FLAG, 2])
     if ext in ("rgb", "tiff"):  # integer sources: 4:4:4 planes, no transfer conversion here
         args[args.index("--src_transfer_characteristics") + 1] = 16
         args += ["--src_chroma_format_idc", 3]
-    rc, out = _run(args)
-    assert rc == 0, out
-    assert "dst_chroma_sample_loc_type: 2" in out.splitlines() and out.splitlines()[-2:] == ENCODER
+    r = ht.run_cli(args, timeout=60)
+    assert r.returncode == 0, r.stdout
+    assert "dst_chroma_sample_loc_type: 2" in r.stdout.splitlines() and r.stdout.splitlines()[-2:] == ENCODER
 
 
 def _refused(args, why):
-    rc, out = _run(args)
-    assert rc == 1, out
-    assert why in out, out
-    assert "WARNING: " in out and "TOO MANY ARGUMENT ERRORS" in out
-    assert "chroma_siting" not in out
+    r = ht.run_cli(args, timeout=60)
+    assert r.returncode == 1, r.stdout
+    assert why in r.stdout, r.stdout
+    assert "WARNING: " in r.stdout and "TOO MANY ARGUMENT ERRORS" in r.stdout
+    assert "chroma_siting" not in r.stdout
 
 
 def test_refused_values(tmp_path):
-    src = _file(tmp_path / "in.f32", 2 * 3 * W * HH * 4)
+    src = ht.zero_file(tmp_path / "in.f32", 2 * 3 * W * HH * 4)
     dst = ["--dst_filename", tmp_path / "o.yuv"]
     _refused(_forward(src, extra=dst + [FLAG, 1]), "the box resampler's siting, --chroma_resampler_type 0")
     for v in (3, 4, 5, -1):
@@ -220,7 +201,7 @@ def test_refused_values(tmp_path):
 
 
 def test_refused_combinations(tmp_path):
-    src = _file(tmp_path / "in.f32", 2 * 3 * W * HH * 4)
+    src = ht.zero_file(tmp_path / "in.f32", 2 * 3 * W * HH * 4)
     dst = ["--dst_filename", tmp_path / "o.yuv", FLAG, 2]
     _refused(_forward(src, extra=dst + ["--chroma_resampler_type", 0]), "needs the FIR resampler: the box (--chroma_resampler_type 0) is centre sited")
     _refused(_forward(src, chroma=3, extra=dst), "sites 4:2:0 chroma: dst_chroma_format_idc(3) has none to site")
@@ -229,7 +210,7 @@ def test_refused_combinations(tmp_path):
 
 
 def test_refused_inverse_flow(tmp_path):
-    src = _file(tmp_path / "in.yuv", 2 * (W * HH * 3 // 2) * 2)
+    src = ht.zero_file(tmp_path / "in.yuv", 2 * (W * HH * 3 // 2) * 2)
     for v in (0, 2):
         args = ["--src_filename", src, "--dst_filename", tmp_path / "o.rgb", "--src_pic_width", W, "--src_pic_height", HH,
                 "--src_bit_depth", 10, "--src_chroma_format_idc", 1, "--dst_bit_depth", 12, "--src_matrix_coeffs", 9, "--dst_matrix_coeffs", 0,
@@ -239,7 +220,7 @@ def test_refused_inverse_flow(tmp_path):
 
 def test_refused_file_only_modes(tmp_path):
     n = (W * HH * 3 // 2) * 2
-    a, b = _file(tmp_path / "a.yuv", 2 * n), _file(tmp_path / "b.yuv", 2 * n)
+    a, b = ht.zero_file(tmp_path / "a.yuv", 2 * n), ht.zero_file(tmp_path / "b.yuv", 2 * n)
     common = ["--src_filename", a, "--src_pic_width", W, "--src_pic_height", HH, "--src_bit_depth", 10, "--src_chroma_format_idc", 1,
               "--n_frames", 2, FLAG, 2, "--dry_run", 1]
     _refused(common + ["--compare_only", 1, "--ref_filename", b], "sites a conversion's chroma: not with --compare_only 1")

@@ -5,9 +5,10 @@ hdr2yuv_amd/cli/hdr2yuv.cpp) has to do the same."""
 import importlib.util
 import json
 import os
-import subprocess
 
 import pytest
+
+import h2y_testing as ht
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _spec = importlib.util.spec_from_file_location("make_cli_flows", os.path.join(ROOT, "tests", "golden", "make_cli_flows.py"))
@@ -25,10 +26,7 @@ def test_every_case_is_recorded():
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", sorted(flows.CASES))
 def test_cli_flow(name):
-    exe = os.path.join(ROOT, "hdr2yuv_amd", "hdr2yuv")
-    if not os.path.exists(exe):
-        subprocess.run(["make", "-C", os.path.join(ROOT, "hdr2yuv_amd", "cli"), "--no-print-directory"], check=True)
-    got, want = flows.record(exe, name), GOLDEN[name]
+    got, want = flows.record(ht.exe(), name), GOLDEN[name]
     assert len(got) == len(want)
     for k, (g, w) in enumerate(zip(got, want)):
         assert g["stdout"] == w["stdout"], (name, k)

@@ -3,28 +3,21 @@ compare-only ring, and the command line's --ref_filename / --sigma_compare / --c
 with numpy int64 on the same arrays."""
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import h2y_testing as ht
 import hdr2yuv_amd as h
 from dpx_files import pack_pixels, write_dpx
 from exr_files import HALF, smooth_half, write_exr
 from oracle import binding as ob
 from tiff_files import write_tiff
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _planes(w, hh, chroma):
-    nc = (w >> 1) * (hh >> 1) if chroma == h.CHROMA_420 else w * hh
-    return [w * hh, nc, nc], [w, w >> 1 if chroma == h.CHROMA_420 else w, w >> 1 if chroma == h.CHROMA_420 else w]
-
 
 def _want(a, b, w, hh, chroma, sigma):
     """the stats of two frames (flat u16 arrays, planes one after the other) in numpy int64"""
-    sizes, _ = _planes(w, hh, chroma)
+    sizes = ht.plane_sizes(w, hh, chroma)
     out, o = [], 0
     for n in sizes:
         pa, pb = a[o:o + n].astype(np.int64), b[o:o + n].astype(np.int64)
@@ -45,12 +38,6 @@ def _check(st, want):
             assert got[k][p] == v, (p, k, got[k][p], v)
 
 
-def _dev(x):
-    import torch
-
-    return torch.from_numpy(x.view(np.int16)).cuda()
-
-
 # ---- h2y_compare_batch ------------------------------------------------------------------------------------------------
 
 @pytest.mark.gpu
@@ -59,13 +46,13 @@ def _dev(x):
 @pytest.mark.parametrize("sigma", [0, 1, 65534, 65535])
 def test_batch_sizes_and_sigmas(ctx, w, hh, chroma, sigma):
     rng = np.random.default_rng(w * 31 + hh + sigma)
-    total = sum(_planes(w, hh, chroma)[0])
+    total = sum(ht.plane_sizes(w, hh, chroma))
     a = [rng.integers(0, 65536, total, dtype=np.uint16) for _ in range(2)]
     b = [x.copy() for x in a]
     b[0][rng.integers(0, total, max(1, total // 100))] ^= 0x1234  # a few differences
     b[1] = rng.integers(0, 65536, total, dtype=np.uint16)  # differences from 0 to 65535, the largest at the last sample
     a[1][-1], b[1][-1] = 0, 65535
-    got = ctx.compare_batch(w, hh, chroma, sigma, [_dev(x) for x in a], [_dev(x) for x in b])
+    got = ctx.compare_batch(w, hh, chroma, sigma, [ht.dev(x) for x in a], [ht.dev(x) for x in b])
     assert ctx.last_kernel_name() == "k_compare"
     for k in range(2):
         _check(got[k], _want(a[k], b[k], w, hh, chroma, sigma))
@@ -75,12 +62,12 @@ def test_batch_sizes_and_sigmas(ctx, w, hh, chroma, sigma):
 def test_batch_extremes_4k(ctx):
     """a whole 4K plane of 65535 against 0: sse 65535^2 x 8294400 does not fit 32 bits, nor do the sums of one wave"""
     w, hh = 3840, 2160
-    sizes, _ = _planes(w, hh, 1)
+    sizes = ht.plane_sizes(w, hh, 1)
     a = np.full(sum(sizes), 65535, np.uint16)
     b = np.zeros_like(a)
     b[sizes[0]:] = a[sizes[0]:]
     b[sizes[0] + 5] = 0
-    got = ctx.compare_batch(w, hh, 1, 0, [_dev(a)], [_dev(b)])[0]
+    got = ctx.compare_batch(w, hh, 1, 0, [ht.dev(a)], [ht.dev(b)])[0]
     assert got.sse[0] == 65535 ** 2 * w * hh and got.sad[0] == 65535 * w * hh and got.over[0] == w * hh
     assert got.max_abs[0] == 65535 and got.first_over[0] == 0 and got.over[1] == 1 and got.first_over[1] == 5
     _check(got, _want(a, b, w, hh, 1, 0))
@@ -91,12 +78,12 @@ def test_batch_extremes_4k(ctx):
 def test_batch_70_frames_two_launches(ctx):
     rng = np.random.default_rng(70)
     w, hh = 64, 18
-    total = sum(_planes(w, hh, 1)[0])
+    total = sum(ht.plane_sizes(w, hh, 1))
     a = [rng.integers(0, 1024, total, dtype=np.uint16) for _ in range(70)]
     b = [x.copy() for x in a]
     for k in range(0, 70, 3):
         b[k][(k * 37) % total] += 1 + k
-    got = ctx.compare_batch(w, hh, 1, 2, [_dev(x) for x in a], [_dev(x) for x in b])
+    got = ctx.compare_batch(w, hh, 1, 2, [ht.dev(x) for x in a], [ht.dev(x) for x in b])
     assert ctx.last_kernel_ms()[1] == 2
     for k in range(70):
         _check(got[k], _want(a[k], b[k], w, hh, 1, 2))
@@ -108,10 +95,10 @@ def test_batch_identical_and_errors(ctx):
 
     rng = np.random.default_rng(1)
     a = rng.integers(0, 65536, 3 * 40 * 8 + 8, dtype=np.uint16)
-    got = ctx.compare_batch(40, 8, 3, 0, [_dev(a[:960])], [_dev(a[:960].copy())])[0]
+    got = ctx.compare_batch(40, 8, 3, 0, [ht.dev(a[:960])], [ht.dev(a[:960].copy())])[0]
     assert list(got.sse) == [0, 0, 0] and list(got.over) == [0, 0, 0] and list(got.first_over) == [-1, -1, -1]
     assert list(got.samples) == [320, 320, 320]
-    buf = _dev(a)
+    buf = ht.dev(a)
     with pytest.raises(h.H2YError) as e:  # 2 bytes past a 16-byte boundary
         ctx.compare_batch(40, 8, 3, 0, [buf.data_ptr() + 2], [buf.data_ptr()])
     assert e.value.code == h.api.H2Y_EINVAL
@@ -129,32 +116,8 @@ def _ring(ctx, opener, inputs, refs=None, sigma=0, keep=1, depth=3, arm=True):
     opener()
     if refs is not None and arm:
         ctx.stream_compare(sigma, keep)
-    got, stats, inflight = [], [], 0
-
-    def take():
-        o = ctx.stream_output()
-        got.append(None if o is None else o.copy())
-        if refs is not None:
-            stats.append(ctx.stream_compare_result())
-
-    for k, inp in enumerate(inputs):
-        for dst, src in zip(ctx.stream_input(), inp):
-            if callable(src):
-                src(dst)
-            else:
-                dst[:] = src
-        if refs is not None:
-            ctx.stream_reference()[:] = refs[k]
-        ctx.stream_submit()
-        inflight += 1
-        if inflight == depth - 1:
-            take()
-            inflight -= 1
-    while inflight:
-        take()
-        inflight -= 1
-    ctx.stream_close()
-    return got, stats
+    recs = ht.drive_ring(ctx, inputs, depth, refs=refs, results=("compare",) if refs is not None else ())
+    return [r["out"] for r in recs], [r["compare"] for r in recs if refs is not None]
 
 
 PLANTED = [(0, 0, 5), (1, 77, 1), (2, 3, 900)]  # (plane, index, added)
@@ -162,7 +125,7 @@ PLANTED = [(0, 0, 5), (1, 77, 1), (2, 3, 900)]  # (plane, index, added)
 
 def _planted(frames, w, hh, chroma):
     """the frames with samples changed at known positions: frame k gets PLANTED[k % 3] (and frame 1 nothing)"""
-    sizes, _ = _planes(w, hh, chroma)
+    sizes = ht.plane_sizes(w, hh, chroma)
     offs = np.cumsum([0] + sizes)
     out = []
     for k, f in enumerate(frames):
@@ -246,7 +209,7 @@ def test_inverse_rings(ctx, oracle, tiff, chroma, w, hh):
     """the inverse ring (G | B | R planes, padded apart on the device when a plane is not a multiple of 16 bytes) and the TIFF
     inverse ring (compared before the interleave)"""
     rng = np.random.default_rng(chroma + w)
-    sizes, _ = _planes(w, hh, chroma)
+    sizes = ht.plane_sizes(w, hh, chroma)
     frames = [[rng.integers(0, 1024, m).astype(np.uint16) for m in sizes] for _ in range(4)]
     args = (w, hh, chroma, 10, 0, h.MATRIX_BT2020NC, 16, 1)
     opener = (lambda: ctx.tiff_inverse_stream_open(*args)) if tiff else (lambda: ctx.inverse_stream_open(*args))
@@ -270,7 +233,7 @@ def test_inverse_rings(ctx, oracle, tiff, chroma, w, hh):
 @pytest.mark.parametrize("w,hh,chroma", [(35, 19, 1), (64, 32, 3)])
 def test_compare_only_ring(ctx, w, hh, chroma):
     rng = np.random.default_rng(w)
-    sizes, _ = _planes(w, hh, chroma)
+    sizes = ht.plane_sizes(w, hh, chroma)
     a = [rng.integers(0, 4096, sum(sizes), dtype=np.uint16) for _ in range(5)]
     b = _planted(a, w, hh, chroma)
     offs = np.cumsum([0] + sizes)
@@ -301,23 +264,7 @@ def test_ring_arming_rules(ctx):
 
 # ---- the command line -------------------------------------------------------------------------------------------------
 
-def _exe():
-    exe = os.path.join(ROOT, "hdr2yuv_amd", "hdr2yuv")
-    if not os.path.exists(exe):
-        subprocess.run(["make", "-C", os.path.join(ROOT, "hdr2yuv_amd", "cli"), "--no-print-directory"], check=True)
-    return exe
-
-
-def _run(args, rc=0):
-    r = subprocess.run([_exe()] + [str(a) for a in args], capture_output=True, text=True, timeout=600)
-    assert r.returncode == rc, r.stdout + r.stderr
-    return r.stdout
-
-
-def _report(out):
-    return [ln for ln in out.splitlines() if ln.startswith(("frame ", "summary ", "first_over "))]
-
-
+REPORT = ("frame ", "summary ", "first_over ")
 W, HH = 64, 16
 
 
@@ -344,8 +291,8 @@ def test_cli_forward_exact_then_planted(tmp_path, oracle):
     src, want = _fwd_files(tmp_path, oracle)
     ref = tmp_path / "ref.yuv"
     np.concatenate(want).tofile(ref)
-    out = _run(_fwd_args(src, 5) + ["--dst_filename", tmp_path / "o.yuv", "--ref_filename", ref, "--sigma_compare", 0])
-    rep = _report(out)
+    out = ht.cli_ok(_fwd_args(src, 5) + ["--dst_filename", tmp_path / "o.yuv", "--ref_filename", ref, "--sigma_compare", 0]).stdout
+    rep = ht.lines_with(out, REPORT)
     assert len(rep) == 7 and rep[-1] == "first_over none" and rep[5].endswith("over 0 0 0"), out
     assert all(" inf " in ln for ln in rep[:5]), out
     assert np.array_equal(np.fromfile(tmp_path / "o.yuv", np.uint16), np.concatenate(want))
@@ -354,12 +301,12 @@ def test_cli_forward_exact_then_planted(tmp_path, oracle):
     bad[4][5] ^= 1
     np.concatenate(bad).tofile(ref)
     a_val, b_val = int(want[2][W * HH + 3 * (W // 2) + 7]), int(bad[2][W * HH + 3 * (W // 2) + 7])
-    out = _run(_fwd_args(src, 5) + ["--ref_filename", ref, "--sigma_compare", 0, "--verbose_level", 1], rc=3)  # no destination
+    out = ht.cli_ok(_fwd_args(src, 5) + ["--ref_filename", ref, "--sigma_compare", 0, "--verbose_level", 1], rc=3).stdout  # no destination
     assert "bytes written" not in out, out  # nothing written, nothing said to be
-    assert _report(out)[-1] == f"first_over frame 2 plane Cb x 7 y 3 a {a_val} b {b_val}", out
-    assert "over 1 0 0" in _report(out)[4]
-    out = _run(_fwd_args(src, 5) + ["--ref_filename", ref])  # sigma not given: reported, exit 0
-    assert _report(out)[-1].startswith("first_over frame 2 plane Cb")
+    assert ht.lines_with(out, REPORT)[-1] == f"first_over frame 2 plane Cb x 7 y 3 a {a_val} b {b_val}", out
+    assert "over 1 0 0" in ht.lines_with(out, REPORT)[4]
+    out = ht.cli_ok(_fwd_args(src, 5) + ["--ref_filename", ref]).stdout  # sigma not given: reported, exit 0
+    assert ht.lines_with(out, REPORT)[-1].startswith("first_over frame 2 plane Cb")
     assert sorted(os.listdir(tmp_path)) == ["in.yuv", "o.yuv", "ref.yuv"]
 
 
@@ -371,8 +318,8 @@ def test_cli_gpus_2_same_report(tmp_path, oracle):
         bad[k][(k * 131) % bad[k].size] ^= k + 1
     ref = tmp_path / "ref.yuv"
     np.concatenate(bad).tofile(ref)
-    one = _report(_run(_fwd_args(src, 7) + ["--ref_filename", ref]))
-    two = _report(_run(_fwd_args(src, 7) + ["--ref_filename", ref, "--gpus", 2, "--devices", "0,0"]))
+    one = ht.lines_with(ht.cli_ok(_fwd_args(src, 7) + ["--ref_filename", ref]).stdout, REPORT)
+    two = ht.lines_with(ht.cli_ok(_fwd_args(src, 7) + ["--ref_filename", ref, "--gpus", 2, "--devices", "0,0"]).stdout, REPORT)
     assert len(one) == 9 and one == two
 
 
@@ -388,9 +335,9 @@ def test_cli_compare_only_psnr(tmp_path):
     b[total:] = np.clip(b[total:].astype(np.int64) + noise[total:], 0, (1 << depth) - 1).astype(np.uint16)
     a.tofile(tmp_path / "a.yuv")
     b.tofile(tmp_path / "b.yuv")
-    out = _run(["--compare_only", 1, "--src_filename", tmp_path / "a.yuv", "--ref_filename", tmp_path / "b.yuv", "--src_pic_width", w,
-                "--src_pic_height", hh, "--src_bit_depth", depth, "--src_chroma_format_idc", 1, "--src_start_frame", 1, "--n_frames", n])
-    rep = _report(out)
+    out = ht.cli_ok(["--compare_only", 1, "--src_filename", tmp_path / "a.yuv", "--ref_filename", tmp_path / "b.yuv", "--src_pic_width", w,
+                     "--src_pic_height", hh, "--src_bit_depth", depth, "--src_chroma_format_idc", 1, "--src_start_frame", 1, "--n_frames", n]).stdout
+    rep = ht.lines_with(out, REPORT)
     maxv = (1 << depth) - 1
     sizes = [w * hh, (w // 2) * (hh // 2), (w // 2) * (hh // 2)]
 
@@ -427,7 +374,7 @@ def test_cli_tiff_output_against_rgb(tmp_path, oracle):
     args = ["--src_filename", tmp_path / "in.yuv", "--dst_filename", tmp_path / "o.tiff", "--src_pic_width", w, "--src_pic_height", hh,
             "--src_bit_depth", 10, "--src_chroma_format_idc", 1, "--src_matrix_coeffs", 9, "--dst_bit_depth", 16,
             "--ref_filename", tmp_path / "ref.rgb", "--sigma_compare", 7]
-    rep = _report(_run(args, rc=3))
+    rep = ht.lines_with(ht.cli_ok(args, rc=3).stdout, REPORT)
     assert rep[0].startswith("frame 0 psnr G ") and rep[0].endswith("max_abs 8 0 0 over 1 0 0")
     assert rep[-1] == f"first_over frame 0 plane G x 9 y 0 a {int(g[9])} b {int(g[9]) ^ 8}"
     assert os.path.getsize(tmp_path / "o.tiff") > 6 * w * hh

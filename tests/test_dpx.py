@@ -2,17 +2,14 @@
 .dpx path.  Every decoded plane is compared bit for bit with tests/dpx_files.read_dpx, a numpy restatement of dpx_read()
 (dpx.cpp:412-520) and muxed_dpx_to_planar_float_buf() (common.cpp:14-27): np.float32(codes / 1023.0) is the C code's binary64
 divide and round to float.  The .yuv bytes are oracle.convert_frame's on the restated planes."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+import h2y_testing as ht
 import hdr2yuv_amd as h
 from dpx_files import pack_pixels, read_dpx, write_dpx
 from oracle import binding as ob
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GUARD = 0x7E57C0DE
 
 
@@ -208,21 +205,15 @@ def test_decode_then_convert_batch(ctx, oracle, bits, big, depth, mat, chroma, r
 def _ring(ctx, d, info, datas, depth=3):
     """Every file through the DPX ring: the payload written into the pinned slot, the .yuv frames in submission order."""
     ctx.dpx_stream_open(d, info, depth)
-    got, inflight = [], 0
-    for data in datas:
-        (slot,) = ctx.stream_input()
-        assert slot.dtype == np.uint8 and slot.size == info.payload_bytes
-        slot[:] = np.frombuffer(data, np.uint8, count=info.payload_bytes, offset=info.data_offset)
-        ctx.stream_submit()
-        inflight += 1
-        if inflight == depth - 1:
-            got.append(ctx.stream_output().copy())
-            inflight -= 1
-    while inflight:
-        got.append(ctx.stream_output().copy())
-        inflight -= 1
-    ctx.stream_close()
-    return got
+
+    def fill(data):
+        def into(slots):
+            (slot,) = slots
+            assert slot.dtype == np.uint8 and slot.size == info.payload_bytes
+            slot[:] = np.frombuffer(data, np.uint8, count=info.payload_bytes, offset=info.data_offset)
+        return into
+
+    return [r["out"] for r in ht.drive_ring(ctx, [fill(x) for x in datas], depth)]
 
 
 @pytest.mark.gpu
@@ -313,15 +304,11 @@ def test_cli_dpx_sequence(tmp_path, oracle):
             "--dst_bit_depth", 10, "--src_matrix_coeffs", 0, "--dst_matrix_coeffs", 9, "--src_transfer_characteristics", 8,
             "--dst_transfer_characteristics", 16, "--src_colour_primaries", 9, "--dst_colour_primaries", 9,
             "--dst_chroma_format_idc", 1, "--chroma_resampler_type", 1, "--src_start_frame", 2, "--n_frames", 3]
-    exe = os.path.join(ROOT, "hdr2yuv_amd", "hdr2yuv")
-    if not os.path.exists(exe):
-        subprocess.run(["make", "-C", os.path.join(ROOT, "hdr2yuv_amd", "cli"), "--no-print-directory"], check=True)
     od = ob.make_desc(w, hh, dst_depth=10, dst_matrix=9, resampler=1)
     want = b"\x07" * 10 + b"".join(oracle.convert_frame(od, read_dpx(datas[k])[1]).tobytes() for k in (2, 3, 4))
     for name, extra in (("one.yuv", []), ("two.yuv", ["--gpus", 2, "--devices", "0,0"])):
         dst = tmp_path / name
         dst.write_bytes(b"\x07" * 10)
-        r = subprocess.run([exe] + [str(a) for a in args + ["--dst_filename", dst] + extra], capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stdout + r.stderr
+        r = ht.cli_ok(args + ["--dst_filename", dst] + extra, timeout=300)
         assert "frames: 3" in r.stdout
         assert dst.read_bytes() == want, name

@@ -2,16 +2,12 @@
 and refuses what the reference aborts on or would read uninitialised memory for; the command line takes .dpx sources and
 resolves their attributes as the reference's read_file() does (hdr2yuv.cpp:700-735).  No GPU: --dry_run stops before any
 device is touched."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+import h2y_testing as ht
 import hdr2yuv_amd as h
 from dpx_files import BPP, pack_pixels, write_dpx
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _file(w, hh, bits, big, **kw):
@@ -87,19 +83,6 @@ def test_dpx_entries_refuse_null_context():
 
 # ---- the command line ----------------------------------------------------------------------------------------------------
 
-def _cli(args):
-    exe = os.path.join(ROOT, "hdr2yuv_amd", "hdr2yuv")
-    if not os.path.exists(exe):
-        subprocess.run(["make", "-C", os.path.join(ROOT, "hdr2yuv_amd", "cli"), "--no-print-directory"], check=True)
-    r = subprocess.run([exe] + [str(a) for a in args] + ["--dry_run", "1"], capture_output=True, text=True, timeout=60)
-    kv = {}
-    for ln in r.stdout.splitlines():
-        if ": " in ln and not ln.startswith(("WARNING", "ERROR")):
-            k, v = ln.split(": ", 1)
-            kv[k] = v
-    return r, kv
-
-
 def _line(src, dst, w, hh, *extra):
     return ["--src_filename", src, "--dst_filename", dst, "--src_pic_width", w, "--src_pic_height", hh, "--src_bit_depth", 10,
             "--dst_bit_depth", 10, "--src_matrix_coeffs", 9, "--dst_matrix_coeffs", 9, "--src_transfer_characteristics", 8,
@@ -113,7 +96,8 @@ def test_cli_dpx_resolves_like_read_file(tmp_path, full):
     w, hh = 24, 6
     src = tmp_path / "a.dpx"
     src.write_bytes(_file(w, hh, 16, True))
-    r, kv = _cli(_line(src, tmp_path / "o.yuv", w, hh, "--src_video_full_range_flag", full))
+    r = ht.run_cli(_line(src, tmp_path / "o.yuv", w, hh, "--src_video_full_range_flag", full), timeout=60, dry=True)
+    kv = ht.banner(r.stdout)
     assert r.returncode == 0, r.stdout
     assert kv["src_picture"] == f"matrix_coeffs 0 chroma_format_idc 3 bit_depth 32 video_full_range_flag {full}"
     assert kv["dpx"] == f"{w}x{hh} 16-bit big-endian, payload {w * hh * 6} bytes"
@@ -127,18 +111,20 @@ def test_cli_dpx_counts_a_numbered_sequence(tmp_path):
     for k in range(3, 7):
         (tmp_path / f"shot.{k:04d}.dpx").write_bytes(_file(w, hh, 10, True))
     pat = tmp_path / "shot.%04d.dpx"
-    r, kv = _cli(_line(pat, tmp_path / "o.yuv", w, hh, "--src_start_frame", 4, "--n_frames", 2))
+    r = ht.run_cli(_line(pat, tmp_path / "o.yuv", w, hh, "--src_start_frame", 4, "--n_frames", 2), timeout=60, dry=True)
+    kv = ht.banner(r.stdout)
     assert r.returncode == 0, r.stdout
     assert kv["frames"] == "2"
-    r, kv = _cli(_line(pat, tmp_path / "o.yuv", w, hh, "--src_start_frame", 4, "--n_frames", 9))
+    r = ht.run_cli(_line(pat, tmp_path / "o.yuv", w, hh, "--src_start_frame", 4, "--n_frames", 9), timeout=60, dry=True)
+    kv = ht.banner(r.stdout)
     assert r.returncode == 0, r.stdout
     assert kv["frames"] == "3"  # 4, 5, 6
     # a file whose format differs from the first one is named
     (tmp_path / "shot.0005.dpx").write_bytes(_file(w, hh, 16, True))
-    r, kv = _cli(_line(pat, tmp_path / "o.yuv", w, hh, "--src_start_frame", 3, "--n_frames", 4))
+    r = ht.run_cli(_line(pat, tmp_path / "o.yuv", w, hh, "--src_start_frame", 3, "--n_frames", 4), timeout=60, dry=True)
     assert r.returncode != 0 and "shot.0005.dpx" in r.stdout and "ERROR" in r.stdout
     # '%' that is not one integer conversion
-    r, kv = _cli(_line(tmp_path / "shot.%s.dpx", tmp_path / "o.yuv", w, hh))
+    r = ht.run_cli(_line(tmp_path / "shot.%s.dpx", tmp_path / "o.yuv", w, hh), timeout=60, dry=True)
     assert r.returncode != 0 and "TOO MANY ARGUMENT ERRORS" in r.stdout
 
 
@@ -147,22 +133,22 @@ def test_cli_dpx_refusals(tmp_path):
     src = tmp_path / "a.dpx"
     src.write_bytes(_file(w, hh, 10, False))
     # the header's size must be the command line's: the reference would hand convert() two different sizes
-    r, kv = _cli(_line(src, tmp_path / "o.yuv", w + 2, hh))
+    r = ht.run_cli(_line(src, tmp_path / "o.yuv", w + 2, hh), timeout=60, dry=True)
     assert r.returncode != 0 and "resizing is not part of convert()" in r.stdout
     # dpx.cpp:232-236
-    r, kv = _cli(_line(src, tmp_path / "o.yuv", w, hh, "--src_half_float_flag", 1))
+    r = ht.run_cli(_line(src, tmp_path / "o.yuv", w, hh, "--src_half_float_flag", 1), timeout=60, dry=True)
     assert r.returncode != 0 and "half-float reading not supported for dpx files" in r.stdout
     # a header the parser refuses
     bad = tmp_path / "b.dpx"
     bad.write_bytes(_file(w, hh, 10, False)[:-1])
-    r, kv = _cli(_line(bad, tmp_path / "o.yuv", w, hh))
+    r = ht.run_cli(_line(bad, tmp_path / "o.yuv", w, hh), timeout=60, dry=True)
     assert r.returncode != 0 and "past the end" in r.stdout
     # descriptor and packing are ignored, with a warning
     odd = tmp_path / "c.dpx"
     odd.write_bytes(_file(w, hh, 10, True, descriptor=51, packing=0))
-    r, kv = _cli(_line(odd, tmp_path / "o.yuv", w, hh))
+    r = ht.run_cli(_line(odd, tmp_path / "o.yuv", w, hh), timeout=60, dry=True)
     assert r.returncode == 0, r.stdout
     assert "descriptor 51 is not 50" in r.stdout and "packing 0 is not 1" in r.stdout
     # DPX output stays refused
-    r, kv = _cli(_line(src, tmp_path / "o.dpx", w, hh))
+    r = ht.run_cli(_line(src, tmp_path / "o.dpx", w, hh), timeout=60, dry=True)
     assert r.returncode != 0 and "TOO MANY ARGUMENT ERRORS" in r.stdout

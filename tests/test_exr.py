@@ -2,16 +2,15 @@
 every compression, pixel type, line order and a range of sizes; the EXR ring and the command line against the oracle on the
 restated half planes, and against the same planes given as .f16."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import h2y_testing as ht
 import hdr2yuv_amd as h
 from exr_files import FLOAT, HALF, NONE, RLE, UINT, ZIP, ZIPS, random_half, read_exr, smooth_half, write_exr
 from oracle import binding as ob
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GUARD = 0x7E57
 COMPS = [NONE, RLE, ZIPS, ZIP]
 
@@ -182,27 +181,21 @@ E2E = [  # (dst depth, dst matrix, chroma, resampler, src transfer, dst transfer
 def _descs(w, hh, depth, mat, chroma, res, st, dt):
     kw = dict(sample=h.SAMPLE_F16, dst_depth=depth, src_transfer=st, dst_transfer=dt, src_primaries=1, dst_primaries=1,
               dst_matrix=mat, chroma=chroma, resampler=res, full_range=0)
-    return h.make_desc(w, hh, **kw), ob.make_desc(w, hh, **kw)
+    return ht.descs(w, hh, **kw)
 
 
 def _ring(ctx, d, info, datas, depth=3):
     ctx.exr_stream_open(d, info, depth)
-    got, inflight = [], 0
-    for data in datas:
-        i, chunks = h.parse_exr(data)
-        (slot,) = ctx.stream_input()
-        assert slot.dtype == np.uint8 and slot.size == info.payload_bytes
-        h.exr_unpack(i, chunks, data, slot)
-        ctx.stream_submit()
-        inflight += 1
-        if inflight == depth - 1:
-            got.append(ctx.stream_output().copy())
-            inflight -= 1
-    while inflight:
-        got.append(ctx.stream_output().copy())
-        inflight -= 1
-    ctx.stream_close()
-    return got
+
+    def fill(data):
+        def into(slots):
+            (slot,) = slots
+            assert slot.dtype == np.uint8 and slot.size == info.payload_bytes
+            i, chunks = h.parse_exr(data)
+            h.exr_unpack(i, chunks, data, slot)
+        return into
+
+    return [r["out"] for r in ht.drive_ring(ctx, [fill(x) for x in datas], depth)]
 
 
 @pytest.mark.gpu
@@ -222,14 +215,7 @@ def test_ring_against_oracle(ctx, oracle, depth, mat, chroma, res, st, dt, comp)
     info, _ = h.parse_exr(datas[0])
     got = _ring(ctx, d, info, datas)
     ctx.stream_open(d, 3)
-    f16 = []
-    for p in planes:
-        slot = ctx.stream_input()
-        for c in range(3):
-            slot[c][:] = p[c]
-        ctx.stream_submit()
-        f16.append(ctx.stream_output().copy())
-    ctx.stream_close()
+    f16 = [r["out"] for r in ht.drive_ring(ctx, planes, 2)]  # one frame in flight, in a ring of three slots
     for f in range(5):
         assert np.array_equal(got[f], f16[f]), f
         assert np.array_equal(got[f], wants[f]), f
@@ -254,19 +240,6 @@ def test_ring_4k(ctx, oracle):
 
 # ---- the command line ------------------------------------------------------------------------------------------------------
 
-def _exe():
-    exe = os.path.join(ROOT, "hdr2yuv_amd", "hdr2yuv")
-    if not os.path.exists(exe):
-        subprocess.run(["make", "-C", os.path.join(ROOT, "hdr2yuv_amd", "cli"), "--no-print-directory"], check=True)
-    return exe
-
-
-def _run(args):
-    r = subprocess.run([_exe()] + [str(a) for a in args], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return r
-
-
 def _line(src, dst, w, hh):
     from test_exr_host import exr_line
 
@@ -284,8 +257,8 @@ def test_cli_test_sh_exr_line(tmp_path, oracle):
     (tmp_path / "a.exr").write_bytes(data)
     planes = read_exr(data)
     (tmp_path / "a.f16").write_bytes(b"".join(p.tobytes() for p in planes))
-    _run(_line(tmp_path / "a.exr", tmp_path / "e.yuv", w, hh))
-    _run(_line(tmp_path / "a.f16", tmp_path / "f.yuv", w, hh))
+    ht.cli_ok(_line(tmp_path / "a.exr", tmp_path / "e.yuv", w, hh))
+    ht.cli_ok(_line(tmp_path / "a.f16", tmp_path / "f.yuv", w, hh))
     got = (tmp_path / "e.yuv").read_bytes()
     assert got == (tmp_path / "f.yuv").read_bytes()
     od = ob.make_desc(w, hh, sample=ob.SAMPLE_F16, dst_depth=10, src_transfer=8, dst_transfer=1, src_matrix=0, dst_matrix=1,
@@ -306,9 +279,9 @@ def test_cli_sequence(tmp_path, gpus):
         (tmp_path / f"s.{10 + k:06d}.exr").write_bytes(data)
         f16 += b"".join(p.tobytes() for p in read_exr(data))
     (tmp_path / "s.f16").write_bytes(f16)
-    _run(_line(tmp_path / "s.%06d.exr", tmp_path / "e.yuv", w, hh) + ["--src_start_frame", 10, "--n_frames", n, "--gpus", gpus]
-         + (["--devices", "0,0"] if gpus == 2 else []))
-    _run(_line(tmp_path / "s.f16", tmp_path / "f.yuv", w, hh) + ["--n_frames", n])
+    ht.cli_ok(_line(tmp_path / "s.%06d.exr", tmp_path / "e.yuv", w, hh) + ["--src_start_frame", 10, "--n_frames", n, "--gpus", gpus]
+              + (["--devices", "0,0"] if gpus == 2 else []))
+    ht.cli_ok(_line(tmp_path / "s.f16", tmp_path / "f.yuv", w, hh) + ["--n_frames", n])
     assert (tmp_path / "e.yuv").read_bytes() == (tmp_path / "f.yuv").read_bytes()
     assert os.path.getsize(tmp_path / "e.yuv") > 0
 
@@ -320,6 +293,6 @@ def test_cli_single_file_zips(tmp_path):
     data, _ = write_exr(ch, ZIPS, x_min=-7, y_min=-3)
     (tmp_path / "a.exr").write_bytes(data)
     (tmp_path / "a.f16").write_bytes(b"".join(p.tobytes() for p in read_exr(data)))
-    _run(_line(tmp_path / "a.exr", tmp_path / "e.yuv", w, hh))
-    _run(_line(tmp_path / "a.f16", tmp_path / "f.yuv", w, hh))
+    ht.cli_ok(_line(tmp_path / "a.exr", tmp_path / "e.yuv", w, hh))
+    ht.cli_ok(_line(tmp_path / "a.f16", tmp_path / "f.yuv", w, hh))
     assert (tmp_path / "e.yuv").read_bytes() == (tmp_path / "f.yuv").read_bytes()

@@ -1,19 +1,16 @@
 """OpenEXR on the host: h2y_exr_parse (through hdr2yuv_amd.parse_exr) and h2y_exr_unpack against the writer and the read_exr()
 restatement of tests/exr_files.py, one file spelled out byte by byte from the format's layout, every refusal, and the command
 line's .exr resolution.  No GPU: --dry_run stops before any device is touched."""
-import os
 import struct
-import subprocess
 import zlib
 
 import numpy as np
 import pytest
 
+import h2y_testing as ht
 import hdr2yuv_amd as h
 from cli_lines import TEST_SH
 from exr_files import FLOAT, HALF, NONE, RLE, UINT, ZIP, ZIPS, predict_reorder, read_exr, smooth_half, write_exr
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # A 3x2 NONE file with channels B, G, R (HALF), written down from the OpenEXR layout, not by the writer.
 _TINY_PIXELS = {  # name: rows of half bits
@@ -243,20 +240,6 @@ def test_zip_chunks_hold_sixteen_lines():
 
 # ---- the command line ----------------------------------------------------------------------------------------------------
 
-def _cli(args, dry=True):
-    exe = os.path.join(ROOT, "hdr2yuv_amd", "hdr2yuv")
-    if not os.path.exists(exe):
-        subprocess.run(["make", "-C", os.path.join(ROOT, "hdr2yuv_amd", "cli"), "--no-print-directory"], check=True)
-    r = subprocess.run([exe] + [str(a) for a in args] + (["--dry_run", "1"] if dry else []), capture_output=True, text=True,
-                       timeout=120)
-    kv = {}
-    for ln in r.stdout.splitlines():
-        if ": " in ln and not ln.startswith(("WARNING", "ERROR")):
-            k, v = ln.split(": ", 1)
-            kv[k] = v
-    return r, kv
-
-
 def exr_line(src, dst, w, hh):
     """test.sh's .exr line (test.sh:66-74) with the file names and the size of the test"""
     line = TEST_SH["exr_to_420_10b"].replace("{src}.f16", str(src)).replace("{dst}.yuv", str(dst)).split()
@@ -270,27 +253,29 @@ def test_cli_dry_run(tmp_path):
     data, _ = write_exr(ch, ZIP, x_min=-2, y_min=-3)
     src = tmp_path / "a.exr"
     src.write_bytes(data)
-    r, kv = _cli(exr_line(src, tmp_path / "o.yuv", 64, 8))
+    r = ht.run_cli(exr_line(src, tmp_path / "o.yuv", 64, 8), timeout=120, dry=True)
+    kv = ht.banner(r.stdout)
     assert r.returncode == 0, r.stdout
     # read_exr forces 4:4:4, 32 bits, GBR and full range on the input picture (exr.cpp:172-183)
     assert kv["src_picture"] == "matrix_coeffs 0 chroma_format_idc 3 bit_depth 32 video_full_range_flag 1"
     assert kv["exr"].startswith("64x8 data window at (-2, -3), ZIP, increasing y, 3 channels") and kv["frames"] == "1"
     assert int(kv["exr"].split(", ")[-1].split()[0]) <= 16
     # the data window must be the command line's size
-    r, kv = _cli(exr_line(src, tmp_path / "o.yuv", 66, 8))
+    r = ht.run_cli(exr_line(src, tmp_path / "o.yuv", 66, 8), timeout=120, dry=True)
     assert r.returncode != 0 and "data window" in r.stdout and "exr.cpp" in r.stdout
     # a missing file and a refused one: non-zero, citing read_exr(), also under --dry_run
-    r, kv = _cli(exr_line(tmp_path / "none.exr", tmp_path / "o.yuv", 64, 8))
+    r = ht.run_cli(exr_line(tmp_path / "none.exr", tmp_path / "o.yuv", 64, 8), timeout=120, dry=True)
     assert r.returncode != 0 and "read_exr()" in r.stdout and "exr.cpp" in r.stdout
     tiled = tmp_path / "t.exr"
     tiled.write_bytes(write_exr(ch, version=2 | 0x200)[0])
-    r, kv = _cli(exr_line(tiled, tmp_path / "o.yuv", 64, 8))
+    r = ht.run_cli(exr_line(tiled, tmp_path / "o.yuv", 64, 8), timeout=120, dry=True)
     assert r.returncode != 0 and "tiled" in r.stdout and "exr.cpp" in r.stdout
     # .exr output stays refused
-    r, kv = _cli(exr_line(src, tmp_path / "o.exr", 64, 8))
+    r = ht.run_cli(exr_line(src, tmp_path / "o.exr", 64, 8), timeout=120, dry=True)
     assert r.returncode != 0 and "writers stay with the reference" in r.stdout
     # --gpus: the unpack threads are shared out, 16 at most in all
-    r, kv = _cli(exr_line(src, tmp_path / "o.yuv", 64, 8) + ["--gpus", 4])
+    r = ht.run_cli(exr_line(src, tmp_path / "o.yuv", 64, 8) + ["--gpus", 4], timeout=120, dry=True)
+    kv = ht.banner(r.stdout)
     assert r.returncode == 0 and kv["exr"].endswith("4 unpack threads per GPU")
 
 
@@ -299,13 +284,15 @@ def test_cli_sequences(tmp_path):
         ch = {n: (HALF, smooth_half(8, 64, k + j)) for j, n in enumerate("RGB")}
         (tmp_path / f"s.{k:04d}.exr").write_bytes(write_exr(ch, ZIPS)[0])
     line = exr_line(tmp_path / "s.%04d.exr", tmp_path / "o.yuv", 64, 8)
-    r, kv = _cli(line + ["--n_frames", 4, "--src_start_frame", 4])
+    r = ht.run_cli(line + ["--n_frames", 4, "--src_start_frame", 4], timeout=120, dry=True)
+    kv = ht.banner(r.stdout)
     assert r.returncode == 0 and kv["frames"] == "4", r.stdout
-    r, kv = _cli(line + ["--n_frames", 10, "--src_start_frame", 3])
+    r = ht.run_cli(line + ["--n_frames", 10, "--src_start_frame", 3], timeout=120, dry=True)
+    kv = ht.banner(r.stdout)
     assert r.returncode == 0 and kv["frames"] == "5"  # as many as exist in a row
     # a file of the sequence whose header differs from the first's
     (tmp_path / "s.0006.exr").write_bytes(write_exr({n: (HALF, smooth_half(8, 64)) for n in "RGB"}, ZIP)[0])
-    r, kv = _cli(line + ["--n_frames", 5, "--src_start_frame", 3])
+    r = ht.run_cli(line + ["--n_frames", 5, "--src_start_frame", 3], timeout=120, dry=True)
     assert r.returncode != 0 and "every file of a sequence must have the same" in r.stdout
-    r, kv = _cli(exr_line(tmp_path / "s.%d%d.exr", tmp_path / "o.yuv", 64, 8))
+    r = ht.run_cli(exr_line(tmp_path / "s.%d%d.exr", tmp_path / "o.yuv", 64, 8), timeout=120, dry=True)
     assert r.returncode != 0 and "'%'" in r.stdout

@@ -2,36 +2,21 @@
 h2y_stream_gamut, and the command line's --gamut_convert.  Every converted sample is the numpy restatement's (gamut_ref.py), bit for
 bit (with clip 0 a NaN is a NaN where the restatement has one); every output frame is the oracle's convert_frame on the
 restatement's planes: the bytes the same run writes when the source holds the converted planes."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import gamut_ref as gr
+import h2y_testing as ht
 import hdr2yuv_amd as h
 import light_ref as lr
 from dpx_files import pack_pixels, write_dpx
 from exr_files import HALF, write_exr
-from oracle import binding as ob
 from tiff_files import write_tiff
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F32, F16, U16 = h.SAMPLE_F32, h.SAMPLE_F16, h.SAMPLE_U16
 NP = {F32: np.float32, F16: np.float16}
 BITS = {F32: np.uint32, F16: np.uint16}
 PAIRS = [(1, 9), (12, 9), (9, 1), (1, 10)]
-
-
-def _dev(x):
-    import torch
-
-    x = np.array(x).reshape(-1)  # a writable copy
-    return torch.from_numpy(x.view({2: np.int16, 4: np.int32, 1: np.uint8}[x.dtype.itemsize])).cuda()
-
-
-def _host(t, sample):
-    return t.cpu().numpy().view(NP[sample])
 
 
 def _same(got, want, clip, where):
@@ -68,20 +53,20 @@ def _frame(rng, n, sample, specials=True):
 
 def _batch(ctx, frames, w, hh, sample, s, d, clip, in_place):
     m = gr.matrix(s, d)
-    dev = [[_dev(p) for p in f] for f in frames]
+    dev = [[ht.dev(p) for p in f] for f in frames]
     if in_place:
         ctx.gamut_batch(w, hh, sample, s, d, clip, dev)
         res = dev
     else:
-        res = [[_dev(np.full(w * hh, 7, NP[sample])) for _ in range(3)] for _ in frames]
+        res = [[ht.dev(np.full(w * hh, 7, NP[sample])) for _ in range(3)] for _ in frames]
         ctx.gamut_batch(w, hh, sample, s, d, clip, dev, res)
     assert ctx.last_kernel_name() == "k_gamut"
     for k, f in enumerate(frames):
         want = gr.convert(f, m, clip)
         for c in range(3):
-            _same(_host(res[k][c], sample), want[c], clip, (k, c, s, d, clip, in_place))
+            _same(ht.host(res[k][c], NP[sample]), want[c], clip, (k, c, s, d, clip, in_place))
             if not in_place:  # the source is left as it was
-                assert np.array_equal(_host(dev[k][c], sample).view(BITS[sample]), f[c].view(BITS[sample]))
+                assert np.array_equal(ht.host(dev[k][c], NP[sample]).view(BITS[sample]), f[c].view(BITS[sample]))
     return res
 
 
@@ -121,7 +106,7 @@ def test_batch_specials(ctx, sample):
             res = _batch(ctx, [planes], w, hh, sample, s, d, clip, False)
             if clip:
                 for c in range(3):
-                    got = _host(res[0][c], sample)
+                    got = ht.host(res[0][c], NP[sample])
                     assert not np.isnan(got).any() and not np.signbit(got).any()  # nothing below +0.0 is left
 
 
@@ -134,14 +119,14 @@ def test_saturated_green_leaves_bt709(ctx, sample):
     g, b, r = np.ones(n, NP[sample]), np.zeros(n, NP[sample]), np.zeros(n, NP[sample])
     g[8:] = 65504
     m = gr.matrix(9, 1)
-    og, ob_, orr = [_host(t, sample) for t in _batch(ctx, [[g, b, r]], n, 1, sample, 9, 1, 0, False)[0]]
+    og, ob_, orr = [ht.host(t, NP[sample]) for t in _batch(ctx, [[g, b, r]], n, 1, sample, 9, 1, 0, False)[0]]
     assert (orr < 0).all() and (ob_ < 0).all() and og[0] == NP[sample](m[1][1])
     assert orr[0] == NP[sample](m[0][1]) and ob_[0] == NP[sample](m[2][1])
     if sample == F16:
         assert np.isposinf(og[8:]).all() and np.isfinite(orr[8:]).all()
     else:
         assert og[8] == np.float32(m[1][1]) * np.float32(65504)
-    og, ob_, orr = [_host(t, sample) for t in _batch(ctx, [[g, b, r]], n, 1, sample, 9, 1, 1, True)[0]]
+    og, ob_, orr = [ht.host(t, NP[sample]) for t in _batch(ctx, [[g, b, r]], n, 1, sample, 9, 1, 1, True)[0]]
     for x in (orr, ob_):
         assert (x == 0).all() and not np.signbit(x).any()
     assert og[0] == NP[sample](m[1][1])
@@ -166,7 +151,7 @@ def test_batch_70_frames_two_launches_grid_wraps(ctx):
 
 @pytest.mark.gpu
 def test_batch_refusals(ctx):
-    f = [[_dev(np.zeros(64, np.float32)) for _ in range(3)]]
+    f = [[ht.dev(np.zeros(64, np.float32)) for _ in range(3)]]
 
     def refused(code, why, *args, src=f, dst=None):
         with pytest.raises(h.H2YError, match=why) as e:
@@ -208,35 +193,14 @@ def _ring(ctx, opener, inputs, gamut=None, light=False, depth=3):
         ctx.stream_light()
     if gamut:
         ctx.stream_gamut(*gamut)
-    got, ls, inflight = [], [], 0
-
-    def take():
-        got.append(ctx.stream_output().copy())
-        if light:
-            ls.append(ctx.stream_light_result().as_dict())
-
-    for inp in inputs:
-        for dst, src in zip(ctx.stream_input(), inp):
-            if callable(src):
-                src(dst)
-            else:
-                dst[:] = src
-        ctx.stream_submit()
-        inflight += 1
-        if inflight == depth - 1:
-            take()
-            inflight -= 1
-    while inflight:
-        take()
-        inflight -= 1
-    ctx.stream_close()
-    return got, ls
+    recs = ht.drive_ring(ctx, inputs, depth, results=("light",) if light else ())
+    return [r["out"] for r in recs], [r["light"].as_dict() for r in recs if light]
 
 
 def _descs(w, hh, sample, s, d, **kw):
     kw = dict(dict(sample=sample, dst_depth=10, src_transfer=8, dst_transfer=16, src_matrix=0, dst_matrix=h.MATRIX_BT2020NC,
                    src_primaries=s, dst_primaries=d, chroma=1, resampler=1), **kw)
-    return h.make_desc(w, hh, **kw), ob.make_desc(w, hh, **kw)
+    return ht.descs(w, hh, **kw)
 
 
 def _as_uploaded(p):
@@ -293,7 +257,7 @@ def test_dpx_ring(ctx, oracle):
     info = h.parse_dpx(datas[0][:2048], len(datas[0]))
     pays = [np.frombuffer(x, np.uint8, count=info.payload_bytes, offset=info.data_offset) for x in datas]
     dev = [[torch.zeros(w * hh, dtype=torch.float32, device="cuda") for _ in range(3)] for _ in pays]
-    ctx.dpx_decode_batch(info, [_dev(p) for p in pays], dev)  # the planes the ring decodes
+    ctx.dpx_decode_batch(info, [ht.dev(p) for p in pays], dev)  # the planes the ring decodes
     planes = [[t.cpu().numpy() for t in f] for f in dev]
     d, od = _descs(w, hh, F32, 1, 9, dst_matrix=h.MATRIX_BT709, resampler=0)
     _armed(ctx, oracle, lambda: ctx.dpx_stream_open(d, info, 3), [[p] for p in pays], planes, w, F32, d, od, 1, 9, 1)
@@ -310,7 +274,7 @@ def test_exr_ring(ctx, oracle):
     info, _ = h.parse_exr(datas[0])
     pays = [h.exr_unpack(info, h.parse_exr(x)[1], x) for x in datas]
     dev = [[torch.zeros(w * hh, dtype=torch.int16, device="cuda") for _ in range(3)] for _ in pays]
-    ctx.exr_decode_batch(info, [_dev(p) for p in pays], dev)  # the planes the ring decodes
+    ctx.exr_decode_batch(info, [ht.dev(p) for p in pays], dev)  # the planes the ring decodes
     planes = [[t.cpu().numpy().view(np.float16) for t in f] for f in dev]
     d, od = _descs(w, hh, F16, 12, 9, dst_depth=12, chroma=3, resampler=0)
     inputs = [[(lambda x: (lambda slot: h.exr_unpack(info, h.parse_exr(x)[1], x, slot)))(x)] for x in datas]
@@ -359,19 +323,6 @@ def test_ring_arming_rules(ctx):
 
 # ---- the command line ---------------------------------------------------------------------------------------------------
 
-def _exe():
-    exe = os.path.join(ROOT, "hdr2yuv_amd", "hdr2yuv")
-    if not os.path.exists(exe):
-        subprocess.run(["make", "-C", os.path.join(ROOT, "hdr2yuv_amd", "cli"), "--no-print-directory"], check=True)
-    return exe
-
-
-def _run(args):
-    r = subprocess.run([_exe()] + [str(a) for a in args], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return r.stdout
-
-
 W, HH, N = 64, 32, 3
 
 
@@ -393,19 +344,19 @@ def _cli_cases(tmp_path, oracle, src, planes, sample, s, dp):
         return conv, np.concatenate([oracle.convert_frame(od, [_as_uploaded(x) for x in c]) for c in conv]).tobytes()
 
     conv1, yuv1 = want(1)
-    out = _run(_args(src, s, dp, ["--dst_filename", tmp_path / "a.yuv", "--gamut_convert", 1]))
+    out = ht.cli_ok(_args(src, s, dp, ["--dst_filename", tmp_path / "a.yuv", "--gamut_convert", 1])).stdout
     assert "gamut_matrix: " + " ".join("%.9g" % float(x) for x in m.reshape(-1)) in out.splitlines()
     assert (tmp_path / "a.yuv").read_bytes() == yuv1
-    _run(_args(src, s, dp, ["--dst_filename", tmp_path / "b.yuv", "--gamut_convert", 1, "--gpus", 2, "--devices", "0,0"]))
+    ht.cli_ok(_args(src, s, dp, ["--dst_filename", tmp_path / "b.yuv", "--gamut_convert", 1, "--gpus", 2, "--devices", "0,0"]))
     assert (tmp_path / "b.yuv").read_bytes() == yuv1
-    _run(_args(src, s, dp, ["--dst_filename", tmp_path / "c.yuv", "--gamut_convert", 1, "--gamut_clip", 0]))
+    ht.cli_ok(_args(src, s, dp, ["--dst_filename", tmp_path / "c.yuv", "--gamut_convert", 1, "--gamut_clip", 0]))
     assert (tmp_path / "c.yuv").read_bytes() == want(0)[1]
     lines = lr.report_lines([lr.light_stats(c, W, sample, 8) for c in conv1])
     for extra in (["--dst_filename", tmp_path / "d.yuv"], []):  # beside the light, with and without a destination
-        out = _run(_args(src, s, dp, extra + ["--gamut_convert", 1, "--content_light", 1]))
+        out = ht.cli_ok(_args(src, s, dp, extra + ["--gamut_convert", 1, "--content_light", 1])).stdout
         assert [x for x in out.splitlines() if x.startswith("light ")] == lines, out
     assert (tmp_path / "d.yuv").read_bytes() == yuv1
-    out = _run(_args(src, s, dp, ["--dst_filename", tmp_path / "e.yuv"]))  # unchanged behaviour without the flag
+    out = ht.cli_ok(_args(src, s, dp, ["--dst_filename", tmp_path / "e.yuv"])).stdout  # unchanged behaviour without the flag
     assert not any(x.startswith("gamut_") for x in out.splitlines())
     plain = np.concatenate([oracle.convert_frame(od, [_as_uploaded(x) for x in p]) for p in planes]).tobytes()
     assert (tmp_path / "e.yuv").read_bytes() == plain and plain != yuv1

@@ -2,16 +2,14 @@
 the matrices BT.2087 and BT.2407 publish, the restatement's per-pixel arithmetic on pixels worked by hand, and the command line's
 --gamut_convert / --gamut_clip as --dry_run resolves them, with every refusal, before any device is touched."""
 import itertools
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import gamut_ref as gr
+import h2y_testing as ht
 import hdr2yuv_amd as h
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W, HH = 16, 8
 F32 = np.float32
 
@@ -112,23 +110,6 @@ def test_restatement_specials_and_half():
 
 # ---- the command line ----------------------------------------------------------------------------------------------------
 
-def _exe():
-    exe = os.path.join(ROOT, "hdr2yuv_amd", "hdr2yuv")
-    if not os.path.exists(exe):
-        subprocess.run(["make", "-C", os.path.join(ROOT, "hdr2yuv_amd", "cli"), "--no-print-directory"], check=True)
-    return exe
-
-
-def _run(args):
-    r = subprocess.run([_exe()] + [str(a) for a in args], capture_output=True, text=True, timeout=60)
-    return r.returncode, r.stdout
-
-
-def _file(path, nbytes):
-    np.zeros(nbytes, np.uint8).tofile(path)
-    return path
-
-
 def _forward(src, sp=1, dp=9, src_tf=8, src_matrix=0, extra=()):
     return ["--src_filename", src, "--src_pic_width", W, "--src_pic_height", HH, "--src_bit_depth", 32, "--dst_bit_depth", 10,
             "--dst_chroma_format_idc", 1, "--src_matrix_coeffs", src_matrix, "--dst_matrix_coeffs", 9, "--src_transfer_characteristics",
@@ -142,40 +123,40 @@ def _matrix_line(s, d):
 
 @pytest.mark.parametrize("ext,bytes_per", [("f32", 4), ("f16", 2)])
 def test_dry_run_prints_the_setting(tmp_path, ext, bytes_per):
-    src = _file(tmp_path / f"in.{ext}", 2 * 3 * W * HH * bytes_per)
+    src = ht.zero_file(tmp_path / f"in.{ext}", 2 * 3 * W * HH * bytes_per)
     dst = ["--dst_filename", tmp_path / "o.yuv"]
     for extra in (dst, ["--content_light", 1], dst + ["--histogram", tmp_path / "h.csv"], dst + ["--scale", 1, "--dst_pic_width", 32]):
-        rc, out = _run(_forward(src, extra=extra + ["--gamut_convert", 1]))
-        assert rc == 0, out
-        lines = out.splitlines()
+        r = ht.run_cli(_forward(src, extra=extra + ["--gamut_convert", 1]), timeout=60)
+        assert r.returncode == 0, r.stdout
+        lines = r.stdout.splitlines()
         assert "gamut_convert: 1" in lines and "gamut_clip: 1 (default)" in lines and _matrix_line(1, 9) in lines
-        rc0, out0 = _run(_forward(src, extra=extra))  # without the flag nothing else changes
-        assert rc0 == 0 and [x for x in lines if not x.startswith("gamut_")] == out0.splitlines()
-    rc, out = _run(_forward(src, 12, 1, extra=dst + ["--gamut_convert", 1, "--gamut_clip", 0]))
-    assert rc == 0 and "gamut_clip: 0" in out.splitlines() and _matrix_line(12, 1) in out.splitlines()
-    rc, out = _run(_forward(src, 10, 8, extra=dst + ["--gamut_convert", 1, "--gamut_clip", 1]))
-    assert rc == 0 and "gamut_clip: 1" in out.splitlines() and _matrix_line(10, 9) in out.splitlines()
-    rc, out = _run(_forward(src, extra=dst + ["--gamut_convert", 0]))  # off: printed, nothing refused
-    assert rc == 0 and "gamut_convert: 0" in out.splitlines() and "gamut_matrix" not in out
+        r0 = ht.run_cli(_forward(src, extra=extra), timeout=60)  # without the flag nothing else changes
+        assert r0.returncode == 0 and [x for x in lines if not x.startswith("gamut_")] == r0.stdout.splitlines()
+    r = ht.run_cli(_forward(src, 12, 1, extra=dst + ["--gamut_convert", 1, "--gamut_clip", 0]), timeout=60)
+    assert r.returncode == 0 and "gamut_clip: 0" in r.stdout.splitlines() and _matrix_line(12, 1) in r.stdout.splitlines()
+    r = ht.run_cli(_forward(src, 10, 8, extra=dst + ["--gamut_convert", 1, "--gamut_clip", 1]), timeout=60)
+    assert r.returncode == 0 and "gamut_clip: 1" in r.stdout.splitlines() and _matrix_line(10, 9) in r.stdout.splitlines()
+    r = ht.run_cli(_forward(src, extra=dst + ["--gamut_convert", 0]), timeout=60)  # off: printed, nothing refused
+    assert r.returncode == 0 and "gamut_convert: 0" in r.stdout.splitlines() and "gamut_matrix" not in r.stdout
     assert not (tmp_path / "o.yuv").exists()
 
 
 def test_dry_run_dpx_and_exr_names(tmp_path):
     """a dry run may name a .dpx that is not there; the flag resolves all the same"""
-    rc, out = _run(_forward(tmp_path / "none.dpx", extra=["--dst_filename", tmp_path / "o.yuv", "--gamut_convert", 1]))
-    assert rc == 0 and _matrix_line(1, 9) in out.splitlines(), out
+    r = ht.run_cli(_forward(tmp_path / "none.dpx", extra=["--dst_filename", tmp_path / "o.yuv", "--gamut_convert", 1]), timeout=60)
+    assert r.returncode == 0 and _matrix_line(1, 9) in r.stdout.splitlines(), r.stdout
 
 
 def _refused(args, why):
-    rc, out = _run(args)
-    assert rc == 1, out
-    assert why in out, out
-    assert "WARNING: " in out and "TOO MANY ARGUMENT ERRORS" in out
-    assert "gamut_matrix" not in out
+    r = ht.run_cli(args, timeout=60)
+    assert r.returncode == 1, r.stdout
+    assert why in r.stdout, r.stdout
+    assert "WARNING: " in r.stdout and "TOO MANY ARGUMENT ERRORS" in r.stdout
+    assert "gamut_matrix" not in r.stdout
 
 
 def test_refused_values(tmp_path):
-    src = _file(tmp_path / "in.f32", 2 * 3 * W * HH * 4)
+    src = ht.zero_file(tmp_path / "in.f32", 2 * 3 * W * HH * 4)
     dst = ["--dst_filename", tmp_path / "o.yuv"]
     _refused(_forward(src, extra=dst + ["--gamut_convert", 2]), "gamut_convert(2) not 0 or 1")
     _refused(_forward(src, extra=dst + ["--gamut_convert", -1]), "gamut_convert(-1) not 0 or 1")
@@ -185,7 +166,7 @@ def test_refused_values(tmp_path):
 
 
 def test_refused_transfer_and_matrix(tmp_path):
-    src = _file(tmp_path / "in.f32", 2 * 3 * W * HH * 4)
+    src = ht.zero_file(tmp_path / "in.f32", 2 * 3 * W * HH * 4)
     dst = ["--dst_filename", tmp_path / "o.yuv", "--gamut_convert", 1]
     _refused(_forward(src, src_tf=1, extra=dst), "converts linear light: src_transfer_characteristics(1) is not 8")
     _refused(_forward(src, src_tf=16, extra=dst), "converts linear light: src_transfer_characteristics(16) is not 8")
@@ -193,7 +174,7 @@ def test_refused_transfer_and_matrix(tmp_path):
 
 
 def test_refused_primaries(tmp_path):
-    src = _file(tmp_path / "in.f32", 2 * 3 * W * HH * 4)
+    src = ht.zero_file(tmp_path / "in.f32", 2 * 3 * W * HH * 4)
     dst = ["--dst_filename", tmp_path / "o.yuv", "--gamut_convert", 1]
     _refused(_forward(src, 11, 9, extra=dst), "src_colour_primaries(11) -> dst_colour_primaries(9): colour primaries other than")
     _refused(_forward(src, 1, 2, extra=dst), "src_colour_primaries(1) -> dst_colour_primaries(2): colour primaries other than")
@@ -212,13 +193,13 @@ def test_refused_inputs(tmp_path):
               "--dst_matrix_coeffs", 9, "--src_transfer_characteristics", 8, "--dst_transfer_characteristics", 16, "--src_colour_primaries",
               1, "--dst_colour_primaries", 9, "--src_chroma_format_idc", 3, "--dry_run", 1]
     for ext, depth in (("rgb", 16), ("yuv", 16), ("tiff", 16)):
-        src = _file(tmp_path / f"in.{ext}", 3 * n * 2)
+        src = ht.zero_file(tmp_path / f"in.{ext}", 3 * n * 2)
         _refused(["--src_filename", src, "--src_bit_depth", depth] + common + dst, f"not .{ext} input")
     _refused(["--synthetic", 0, "--src_bit_depth", 32] + common + dst, "not .(synthetic) input")
 
 
 def test_refused_inverse_flow(tmp_path):
-    src = _file(tmp_path / "in.yuv", 2 * (W * HH * 3 // 2) * 2)
+    src = ht.zero_file(tmp_path / "in.yuv", 2 * (W * HH * 3 // 2) * 2)
     args = ["--src_filename", src, "--dst_filename", tmp_path / "o.rgb", "--src_pic_width", W, "--src_pic_height", HH,
             "--src_bit_depth", 10, "--src_chroma_format_idc", 1, "--dst_bit_depth", 12, "--src_matrix_coeffs", 9, "--dst_matrix_coeffs", 0,
             "--src_transfer_characteristics", 16, "--dst_transfer_characteristics", 16, "--src_colour_primaries", 9,
@@ -228,7 +209,7 @@ def test_refused_inverse_flow(tmp_path):
 
 def test_refused_file_only_modes(tmp_path):
     n = (W * HH * 3 // 2) * 2
-    a, b = _file(tmp_path / "a.yuv", 2 * n), _file(tmp_path / "b.yuv", 2 * n)
+    a, b = ht.zero_file(tmp_path / "a.yuv", 2 * n), ht.zero_file(tmp_path / "b.yuv", 2 * n)
     common = ["--src_filename", a, "--src_pic_width", W, "--src_pic_height", HH, "--src_bit_depth", 10, "--src_chroma_format_idc", 1,
               "--n_frames", 2, "--src_colour_primaries", 1, "--dst_colour_primaries", 9, "--gamut_convert", 1, "--dry_run", 1]
     _refused(common + ["--compare_only", 1, "--ref_filename", b], "converts a conversion's source: not with --compare_only 1")

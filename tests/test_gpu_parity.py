@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import h2y_testing as ht
 import hdr2yuv_amd as h
 from oracle import binding as ob
 
@@ -151,10 +152,6 @@ def test_golden_fixtures(ctx):
         assert np.array_equal(got, z["yuv"]), case["file"]
 
 
-def _md5(a):
-    return hashlib.md5(np.ascontiguousarray(a).tobytes()).hexdigest()
-
-
 KNOWN = json.load(open(os.path.join(GOLD, "known_md5.json")))
 
 
@@ -167,7 +164,7 @@ def test_full_size_known_md5(ctx, oracle, name):
     planes = oracle.synth_frame(d.width, d.height, 0, f16=(d.in_sample_type == h.SAMPLE_F16))
     got = ctx.convert_frame(d, planes)
     assert got.nbytes == case["bytes"]
-    assert _md5(got) == case["md5"]
+    assert ht.md5(got) == case["md5"]
 
 
 def test_batch_device_path_and_stats_redo(ctx, oracle):
@@ -334,20 +331,13 @@ def test_cli_writes_reference_bytes(tmp_path):
     """The C++ host program with the reference's flags: 64x32 synthetic frame, 10-bit
     BT.2020nc 4:2:0 FIR -> the md5 SURVEY 8c recorded from the reference binary; a second
     invocation appends (tiff.cpp:440)."""
-    import subprocess
-
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = os.path.join(root, "hdr2yuv_amd", "hdr2yuv")
-    if not os.path.exists(exe):
-        subprocess.run(["make", "-C", os.path.join(root, "hdr2yuv_amd", "cli"), "--no-print-directory"], check=True)
     out = str(tmp_path / "o.yuv")
-    cmd = [exe, "--synthetic", "0", "--src_pic_width", "64", "--src_pic_height", "32", "--dst_filename", out,
+    cmd = ["--synthetic", "0", "--src_pic_width", "64", "--src_pic_height", "32", "--dst_filename", out,
            "--src_bit_depth", "32", "--dst_bit_depth", "10", "--src_transfer_characteristics", "8", "--dst_transfer_characteristics", "16",
            "--dst_matrix_coeffs", "9", "--dst_colour_primaries", "9", "--dst_chroma_format_idc", "1",
            "--dst_video_full_range_flag", "0", "--chroma_resampler_type", "1"]
     for n in (1, 2):
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        assert r.returncode == 0, r.stdout + r.stderr
+        ht.cli_ok(cmd, timeout=None)
         data = open(out, "rb").read()
         assert len(data) == 6144 * n
         assert hashlib.md5(data[-6144:]).hexdigest() == KNOWN["cases"]["tiny_64x32_2020_10b_fir"]["md5"]
@@ -418,7 +408,7 @@ def test_c4_known_md5_through_batch_table_path(ctx, oracle):
             dev_out = [torch.zeros(h.frame_bytes(d) // 2, dtype=torch.int16, device="cuda")]
             torch.cuda.synchronize()
             fresh.convert_batch(d, dev_in, dev_out)
-            assert _md5(dev_out[0].cpu().numpy().view(np.uint16)) == case["md5"]
+            assert ht.md5(dev_out[0].cpu().numpy().view(np.uint16)) == case["md5"]
     finally:
         fresh.close()
 
@@ -604,20 +594,7 @@ def test_stream_pipeline(oracle, res, depth_out):
     c = h.Context(0)
     try:
         c.stream_open(d, 3)
-        got, inflight = [], 0
-        for fr in frames:
-            dst = c.stream_input()
-            for k in range(3):
-                dst[k][:] = fr[k]
-            c.stream_submit()
-            inflight += 1
-            if inflight == 2:
-                got.append(c.stream_output().copy())
-                inflight -= 1
-        while inflight:
-            got.append(c.stream_output().copy())
-            inflight -= 1
-        c.stream_close()
+        got = [r["out"] for r in ht.drive_ring(c, frames, 3)]
         assert len(got) == len(frames)
         for k, fr in enumerate(frames):
             assert np.array_equal(got[k], oracle.convert_frame(od, fr)), f"frame {k}"
@@ -667,7 +644,7 @@ def test_full_size_batch_of_frames(ctx, oracle, name):
     torch.cuda.synchronize()
     ctx.convert_batch(d, dev_in, dev_out)
     got0 = dev_out[0].cpu().numpy().view(np.uint16)
-    assert _md5(got0) == case["md5"]
+    assert ht.md5(got0) == case["md5"]
     od = _to_oracle_desc(d)
     for f in (1, 2):
         got = dev_out[f].cpu().numpy().view(np.uint16)
@@ -1260,18 +1237,6 @@ def test_two_batches_in_flight(oracle, res):
         c.close()
 
 
-def _cli(args):
-    import subprocess
-
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = os.path.join(root, "hdr2yuv_amd", "hdr2yuv")
-    if not os.path.exists(exe):
-        subprocess.run(["make", "-C", os.path.join(root, "hdr2yuv_amd", "cli"), "--no-print-directory"], check=True)
-    r = subprocess.run([exe] + [str(a) for a in args], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return r
-
-
 def test_cli_reads_raw_files(tmp_path, oracle):
     """The host program on real input files, every raw format it takes (hdr2yuv.cpp:582-656 for the integer ones):
     .f32 planar float (two frames, default resampler = FIR), .f16, .rgb 16-bit in R,G,B file order -> planes 2,0,1,
@@ -1284,9 +1249,9 @@ def test_cli_reads_raw_files(tmp_path, oracle):
     frames = [_rand_planes(rng, w, hh, h.SAMPLE_F32) for _ in range(2)]
     src, dst = tmp_path / "in.f32", tmp_path / "f32.yuv"
     src.write_bytes(b"".join(p.tobytes() for fr in frames for p in fr))
-    _cli(["--src_filename", src, "--dst_filename", dst, "--src_pic_width", w, "--src_pic_height", hh, "--n_frames", 2, "--src_bit_depth", 32, "--dst_bit_depth", 10,
-          "--src_transfer_characteristics", 8, "--dst_transfer_characteristics", 16, "--dst_matrix_coeffs", 1, "--dst_chroma_format_idc", 1,
-          "--dst_video_full_range_flag", 0])
+    ht.cli_ok(["--src_filename", src, "--dst_filename", dst, "--src_pic_width", w, "--src_pic_height", hh, "--n_frames", 2, "--src_bit_depth", 32, "--dst_bit_depth", 10,
+               "--src_transfer_characteristics", 8, "--dst_transfer_characteristics", 16, "--dst_matrix_coeffs", 1, "--dst_chroma_format_idc", 1,
+               "--dst_video_full_range_flag", 0], timeout=None)
     od = ob.make_desc(w, hh, dst_depth=10, dst_matrix=1, resampler=1)
     want = np.concatenate([oracle.convert_frame(od, fr) for fr in frames])
     assert np.array_equal(np.fromfile(dst, np.uint16), want)
@@ -1295,9 +1260,9 @@ def test_cli_reads_raw_files(tmp_path, oracle):
     hframes = [[p.astype(np.float16).view(np.uint16) for p in frames[0]]]
     src, dst = tmp_path / "in.f16", tmp_path / "f16.yuv"
     src.write_bytes(b"".join(p.tobytes() for fr in hframes for p in fr))
-    _cli(["--src_filename", src, "--dst_filename", dst, "--src_pic_width", w, "--src_pic_height", hh, "--src_bit_depth", 16, "--dst_bit_depth", 12,
-          "--src_transfer_characteristics", 8, "--dst_transfer_characteristics", 16, "--dst_matrix_coeffs", 9, "--dst_chroma_format_idc", 1,
-          "--dst_video_full_range_flag", 1, "--chroma_resampler_type", 0])
+    ht.cli_ok(["--src_filename", src, "--dst_filename", dst, "--src_pic_width", w, "--src_pic_height", hh, "--src_bit_depth", 16, "--dst_bit_depth", 12,
+               "--src_transfer_characteristics", 8, "--dst_transfer_characteristics", 16, "--dst_matrix_coeffs", 9, "--dst_chroma_format_idc", 1,
+               "--dst_video_full_range_flag", 1, "--chroma_resampler_type", 0], timeout=None)
     od = ob.make_desc(w, hh, sample=ob.SAMPLE_F16, dst_depth=12, dst_matrix=9, resampler=0, full_range=1)
     assert np.array_equal(np.fromfile(dst, np.uint16), oracle.convert_frame(od, hframes[0]))
 
@@ -1305,9 +1270,9 @@ def test_cli_reads_raw_files(tmp_path, oracle):
     r, g, b = [rng.integers(0, 65536, n).astype(np.uint16) for _ in range(3)]
     src, dst = tmp_path / "in.rgb", tmp_path / "rgb.yuv"
     src.write_bytes(r.tobytes() + g.tobytes() + b.tobytes())
-    _cli(["--src_filename", src, "--dst_filename", dst, "--src_pic_width", w, "--src_pic_height", hh, "--src_bit_depth", 16, "--dst_bit_depth", 10,
-          "--src_transfer_characteristics", 16, "--dst_transfer_characteristics", 16, "--dst_matrix_coeffs", 9, "--src_chroma_format_idc", 3,
-          "--dst_chroma_format_idc", 1, "--src_video_full_range_flag", 0, "--chroma_resampler_type", 1])
+    ht.cli_ok(["--src_filename", src, "--dst_filename", dst, "--src_pic_width", w, "--src_pic_height", hh, "--src_bit_depth", 16, "--dst_bit_depth", 10,
+               "--src_transfer_characteristics", 16, "--dst_transfer_characteristics", 16, "--dst_matrix_coeffs", 9, "--src_chroma_format_idc", 3,
+               "--dst_chroma_format_idc", 1, "--src_video_full_range_flag", 0, "--chroma_resampler_type", 1], timeout=None)
     od = ob.make_desc(w, hh, sample=ob.SAMPLE_U16, src_depth=16, dst_depth=10, src_transfer=16, dst_transfer=16, dst_matrix=9, resampler=1)
     assert np.array_equal(np.fromfile(dst, np.uint16), oracle.convert_frame(od, [g, b, r]))
 
@@ -1316,9 +1281,9 @@ def test_cli_reads_raw_files(tmp_path, oracle):
     src, dst = tmp_path / "in.yuv", tmp_path / "yuv.yuv"
     src.write_bytes(b"".join(p.tobytes() for fr in yframes for p in fr))
     dst.write_bytes(b"\x01\x02" * 8)  # what is already there stays
-    _cli(["--src_filename", src, "--dst_filename", dst, "--src_pic_width", w, "--src_pic_height", hh, "--src_bit_depth", 16, "--dst_bit_depth", 12,
-          "--src_start_frame", 1, "--n_frames", 3, "--src_transfer_characteristics", 16, "--dst_transfer_characteristics", 16,
-          "--dst_matrix_coeffs", 11, "--src_chroma_format_idc", 3, "--dst_chroma_format_idc", 3, "--src_video_full_range_flag", 0])
+    ht.cli_ok(["--src_filename", src, "--dst_filename", dst, "--src_pic_width", w, "--src_pic_height", hh, "--src_bit_depth", 16, "--dst_bit_depth", 12,
+               "--src_start_frame", 1, "--n_frames", 3, "--src_transfer_characteristics", 16, "--dst_transfer_characteristics", 16,
+               "--dst_matrix_coeffs", 11, "--src_chroma_format_idc", 3, "--dst_chroma_format_idc", 3, "--src_video_full_range_flag", 0], timeout=None)
     od = ob.make_desc(w, hh, sample=ob.SAMPLE_U16, src_depth=16, dst_depth=12, src_transfer=16, dst_transfer=16, dst_matrix=11, chroma=3)
     got = dst.read_bytes()
     assert got[:16] == b"\x01\x02" * 8
@@ -1460,13 +1425,13 @@ def test_cli_runs_the_reference_test_sh_lines(tmp_path, oracle):
                       src_primaries=1, dst_primaries=1, full_range=0, chroma=1, resampler=1)),
     ):
         dst = tmp_path / (name + ".yuv")
-        _cli(TEST_SH[name].format(src=tmp_path / "in", dst=tmp_path / name).split())
+        ht.cli_ok(TEST_SH[name].format(src=tmp_path / "in", dst=tmp_path / name).split(), timeout=None)
         assert np.array_equal(np.fromfile(dst, np.uint16), oracle.convert_frame(od, mem)), name
     # the .exr line: half planes as read_exr() leaves them; LINEAR -> BT.709 (bt1886_r), 10-bit BT.709 4:2:0, video range
     w, hh = 1920, 1080
     half = [p.astype(np.float16).view(np.uint16) for p in _rand_planes(rng, w, hh, h.SAMPLE_F32)]
     (tmp_path / "in.f16").write_bytes(b"".join(p.tobytes() for p in half))
-    _cli(TEST_SH["exr_to_420_10b"].format(src=tmp_path / "in", dst=tmp_path / "exr").split())
+    ht.cli_ok(TEST_SH["exr_to_420_10b"].format(src=tmp_path / "in", dst=tmp_path / "exr").split(), timeout=None)
     od = ob.make_desc(w, hh, sample=ob.SAMPLE_F16, dst_depth=10, src_transfer=8, dst_transfer=1, src_matrix=0, dst_matrix=1,
                       src_primaries=1, dst_primaries=1, full_range=0, chroma=1, resampler=1)
     assert np.array_equal(np.fromfile(tmp_path / "exr.yuv", np.uint16), oracle.convert_frame(od, half))
@@ -1485,7 +1450,7 @@ def test_cli_default_range_is_the_reference_s(tmp_path, oracle):
               "--src_transfer_characteristics", 8, "--dst_transfer_characteristics", 16, "--dst_matrix_coeffs", 9, "--dst_chroma_format_idc", 1]
     for extra, full in (([], 0), (["--src_video_full_range_flag", 1], 1), (["--src_video_full_range_flag", 1, "--dst_video_full_range_flag", 0], 0)):
         dst = tmp_path / f"o{len(extra)}.yuv"
-        _cli(common + ["--dst_filename", dst] + extra)
+        ht.cli_ok(common + ["--dst_filename", dst] + extra, timeout=None)
         od = ob.make_desc(w, hh, dst_depth=10, dst_matrix=9, src_primaries=0, dst_primaries=0, resampler=1, full_range=full)
         assert np.array_equal(np.fromfile(dst, np.uint16), oracle.convert_frame(od, frame)), extra
 
@@ -1505,8 +1470,8 @@ def test_cli_frame_blocks_on_two_contexts(tmp_path, oracle):
     one, two = tmp_path / "one.yuv", tmp_path / "two.yuv"
     for path in (one, two):
         path.write_bytes(b"\x07" * 10)  # what is already in the file stays in front
-    _cli(args + ["--dst_filename", one])
-    r = _cli(args + ["--dst_filename", two, "--gpus", 2, "--devices", "0,0", "--verbose_level", 1])
+    ht.cli_ok(args + ["--dst_filename", one], timeout=None)
+    r = ht.cli_ok(args + ["--dst_filename", two, "--gpus", 2, "--devices", "0,0", "--verbose_level", 1], timeout=None)
     assert "frame 3:" in r.stdout and "frame 6:" in r.stdout
     od = ob.make_desc(w, hh, dst_depth=12, dst_matrix=9, src_primaries=0, dst_primaries=0, resampler=1, full_range=0)
     want = b"\x07" * 10 + np.concatenate([oracle.convert_frame(od, frames[k]) for k in range(1, 8)]).tobytes()
@@ -1524,10 +1489,10 @@ def test_cli_inverse_flow_writes_planar_rgb(tmp_path, oracle, ctx):
     y, cb, cr = [rng.integers(0, 4096, n).astype(np.uint16) for _ in range(3)]
     src, dst = tmp_path / "in.yuv", tmp_path / "out.rgb"
     src.write_bytes(y.tobytes() + cb.tobytes() + cr.tobytes())
-    _cli(("--src_matrix_coeffs 1 --dst_matrix_coeffs 0 --src_transfer_characteristics 1 --dst_transfer_characteristics 1 "
-          f"--src_colour_primaries 1 --dst_colour_primaries 1 --src_filename {src} --dst_filename {dst} "
-          f"--src_pic_width {w} --src_pic_height {hh} --src_bit_depth 12 --dst_bit_depth 16 "
-          "--src_chroma_format_idc 3 --dst_chroma_format_idc 3 --verbose_level 4 --src_start_frame 0").split())
+    ht.cli_ok(("--src_matrix_coeffs 1 --dst_matrix_coeffs 0 --src_transfer_characteristics 1 --dst_transfer_characteristics 1 "
+               f"--src_colour_primaries 1 --dst_colour_primaries 1 --src_filename {src} --dst_filename {dst} "
+               f"--src_pic_width {w} --src_pic_height {hh} --src_bit_depth 12 --dst_bit_depth 16 "
+               "--src_chroma_format_idc 3 --dst_chroma_format_idc 3 --verbose_level 4 --src_start_frame 0").split(), timeout=None)
     g, b, r = oracle.matrix_inverse(w, hh, 12, 0, 1, 16, [y, cb, cr])
     assert np.array_equal(np.fromfile(dst, np.uint16), np.concatenate([r, g, b]))
     got = ctx.inverse_frame(w, hh, 3, 12, 0, 1, 16, 0, [y, cb, cr])
@@ -1536,8 +1501,8 @@ def test_cli_inverse_flow_writes_planar_rgb(tmp_path, oracle, ctx):
     cb2, cr2 = cb[: n // 4], cr[: n // 4]
     src.write_bytes(y.tobytes() + cb2.tobytes() + cr2.tobytes())
     dst = tmp_path / "out2.rgb"
-    _cli(["--src_filename", src, "--dst_filename", dst, "--src_pic_width", w, "--src_pic_height", hh, "--src_bit_depth", 12, "--dst_bit_depth", 16,
-          "--src_matrix_coeffs", 11, "--src_chroma_format_idc", 1, "--dst_chroma_format_idc", 3, "--chroma_resampler_type", 1])
+    ht.cli_ok(["--src_filename", src, "--dst_filename", dst, "--src_pic_width", w, "--src_pic_height", hh, "--src_bit_depth", 12, "--dst_bit_depth", 16,
+               "--src_matrix_coeffs", 11, "--src_chroma_format_idc", 1, "--dst_chroma_format_idc", 3, "--chroma_resampler_type", 1], timeout=None)
     full = [y, oracle.up444(cb2, w, hh, 1, 0, 4095).reshape(-1), oracle.up444(cr2, w, hh, 1, 0, 4095).reshape(-1)]
     g, b, r = oracle.matrix_inverse(w, hh, 12, 0, 11, 16, full)
     assert np.array_equal(np.fromfile(dst, np.uint16), np.concatenate([r, g, b]))
@@ -1842,7 +1807,7 @@ def test_fir_fused_rows_by_xcd_speed(oracle, balance):
             torch.cuda.synchronize()
             c.convert_batch(d, dev_in, dev_out)
             assert c.last_kernel_name() == "k_fir_fused", c.last_kernel_variant()
-            assert _md5(dev_out[0].cpu().numpy().view(np.uint16)) == case["md5"]
+            assert ht.md5(dev_out[0].cpu().numpy().view(np.uint16)) == case["md5"]
             od = _to_oracle_desc(d)
             for k in (5, 11):
                 got = dev_out[k].cpu().numpy().view(np.uint16)

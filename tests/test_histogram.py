@@ -2,23 +2,16 @@
 h2y_stream_histogram (alone and beside the comparison), the histogram-only ring, and the command line's --histogram,
 --histogram_only and --check_range.  Every expected figure is np.bincount or plain numpy on the same arrays."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import h2y_testing as ht
 import hdr2yuv_amd as h
 from dpx_files import pack_pixels, write_dpx
 from exr_files import HALF, smooth_half, write_exr
 from oracle import binding as ob
 from tiff_files import write_tiff
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _sizes(w, hh, chroma):
-    nc = (w >> 1) * (hh >> 1) if chroma == h.CHROMA_420 else w * hh
-    return [w * hh, nc, nc]
 
 
 def _limits(depth, full, gbr):
@@ -32,7 +25,7 @@ def _limits(depth, full, gbr):
 
 def _want(frame, w, hh, chroma, depth, full, gbr, bits):
     """(per plane stats, bins (3, 2^bits)) of one frame (flat u16, planes one after the other)"""
-    sizes, lim = _sizes(w, hh, chroma), _limits(depth, full, gbr)
+    sizes, lim = ht.plane_sizes(w, hh, chroma), _limits(depth, full, gbr)
     nb, out, bins, o = 1 << bits, [], np.zeros((3, 1 << bits), np.uint32), 0
     for p, n in enumerate(sizes):
         x = frame[o:o + n].astype(np.int64)
@@ -53,14 +46,8 @@ def _check(st, want, bits=None, depth=None):
         assert st.nbins == 1 << bits and st.shift == depth - bits
 
 
-def _dev(x):
-    import torch
-
-    return torch.from_numpy(x.view(np.int16)).cuda()
-
-
 def _batch_check(ctx, frames, w, hh, chroma, depth, full, gbr, bits):
-    st, bins = ctx.histogram_batch(w, hh, chroma, depth, full, gbr, bits, [_dev(f) for f in frames])
+    st, bins = ctx.histogram_batch(w, hh, chroma, depth, full, gbr, bits, [ht.dev(f) for f in frames])
     assert ctx.last_kernel_name() == "k_histogram"
     for k, f in enumerate(frames):
         want, wb = _want(f, w, hh, chroma, depth, full, gbr, bits)
@@ -76,7 +63,7 @@ def _batch_check(ctx, frames, w, hh, chroma, depth, full, gbr, bits):
 @pytest.mark.parametrize("depth", [8, 10, 12, 16])
 def test_batch_sizes_depths(ctx, w, hh, chroma, depth):
     rng = np.random.default_rng(w * 7 + hh + depth)
-    total = sum(_sizes(w, hh, chroma))
+    total = sum(ht.plane_sizes(w, hh, chroma))
     frames = [rng.integers(0, 1 << depth, total, dtype=np.uint16) for _ in range(2)]
     frames[1][:: max(1, total // 50)] = rng.integers(0, 65536, len(frames[1][:: max(1, total // 50)]), dtype=np.uint16)  # codes past maxCV
     for bits in sorted({1, 8, depth}):
@@ -121,11 +108,11 @@ def test_batch_row_codes_and_planted(ctx):
 def test_batch_70_frames_two_launches(ctx):
     rng = np.random.default_rng(70)
     w, hh = 64, 18
-    total = sum(_sizes(w, hh, 1))
+    total = sum(ht.plane_sizes(w, hh, 1))
     frames = [rng.integers(0, 1024, total, dtype=np.uint16) for _ in range(70)]
     _batch_check(ctx, frames, w, hh, 1, 10, 0, 0, 10)
     assert ctx.last_kernel_ms()[1] == 2
-    st, bins = ctx.histogram_batch(w, hh, 1, 10, 0, 0, 10, [_dev(f) for f in frames], want_bins=False)
+    st, bins = ctx.histogram_batch(w, hh, 1, 10, 0, 0, 10, [ht.dev(f) for f in frames], want_bins=False)
     assert bins is None and st[69].samples[0] == w * hh
 
 
@@ -133,7 +120,7 @@ def test_batch_70_frames_two_launches(ctx):
 def test_batch_refusals(ctx):
     import torch
 
-    buf = _dev(np.zeros(3 * 40 * 8 + 8, np.uint16))
+    buf = ht.dev(np.zeros(3 * 40 * 8 + 8, np.uint16))
     with pytest.raises(h.H2YError) as e:  # 2 bytes past a 16-byte boundary
         ctx.histogram_batch(40, 8, 3, 10, 0, 0, 10, [buf.data_ptr() + 2])
     assert e.value.code == h.api.H2Y_EINVAL
@@ -160,35 +147,9 @@ def _ring(ctx, opener, inputs, hist=None, refs=None, depth=3):
         ctx.stream_compare(0, 1)
     if hist is not None and hist != "opened":
         ctx.stream_histogram(**hist)
-    got, hs, cs, inflight = [], [], [], 0
-
-    def take():
-        o = ctx.stream_output()
-        got.append(None if o is None else o.copy())
-        if hist is not None:
-            st, b = ctx.stream_histogram_result()
-            hs.append((st, b.copy()))
-        if refs is not None:
-            cs.append(ctx.stream_compare_result())
-
-    for k, inp in enumerate(inputs):
-        for dst, src in zip(ctx.stream_input(), inp):
-            if callable(src):
-                src(dst)
-            else:
-                dst[:] = src
-        if refs is not None:
-            ctx.stream_reference()[:] = refs[k]
-        ctx.stream_submit()
-        inflight += 1
-        if inflight == depth - 1:
-            take()
-            inflight -= 1
-    while inflight:
-        take()
-        inflight -= 1
-    ctx.stream_close()
-    return got, hs, cs
+    results = (("histogram",) if hist is not None else ()) + (("compare",) if refs is not None else ())
+    recs = ht.drive_ring(ctx, inputs, depth, refs=refs, results=results)
+    return [r["out"] for r in recs], [r["histogram"] for r in recs if hist is not None], [r["compare"] for r in recs if refs is not None]
 
 
 def _armed(ctx, opener, inputs, w, hh, chroma, depth, full, gbr, bits=0, clamped=True):
@@ -265,7 +226,7 @@ def test_exr_ring(ctx):
 def test_inverse_rings(ctx, tiff, chroma, w, hh):
     """the G, B, R planes before any interleave (padded apart on the device when a plane is not a multiple of 16 bytes)"""
     rng = np.random.default_rng(chroma + w)
-    sizes = _sizes(w, hh, chroma)
+    sizes = ht.plane_sizes(w, hh, chroma)
     frames = [[rng.integers(0, 1024, m).astype(np.uint16) for m in sizes] for _ in range(4)]
     args = (w, hh, chroma, 10, 0, h.MATRIX_BT2020NC, 12, 1)
     plain_open = lambda: ctx.inverse_stream_open(*args)  # noqa: E731
@@ -289,7 +250,7 @@ def test_inverse_rings(ctx, tiff, chroma, w, hh):
 @pytest.mark.parametrize("w,hh,chroma", [(35, 19, 1), (64, 32, 3)])
 def test_compare_only_ring(ctx, w, hh, chroma):
     rng = np.random.default_rng(w)
-    sizes = _sizes(w, hh, chroma)
+    sizes = ht.plane_sizes(w, hh, chroma)
     a = [rng.integers(0, 4096, sum(sizes), dtype=np.uint16) for _ in range(5)]
     offs = np.cumsum([0] + sizes)
     inputs = [[x[offs[p]:offs[p + 1]] for p in range(3)] for x in a]
@@ -317,7 +278,7 @@ def test_compare_only_ring(ctx, w, hh, chroma):
 @pytest.mark.parametrize("w,hh,chroma,depth,full,gbr,bits", [(35, 19, 1, 10, 0, 0, 10), (64, 32, 3, 16, 1, 1, 16), (1, 1, 1, 8, 0, 0, 3)])
 def test_histogram_only_ring(ctx, w, hh, chroma, depth, full, gbr, bits):
     rng = np.random.default_rng(w + depth)
-    sizes = _sizes(w, hh, chroma)
+    sizes = ht.plane_sizes(w, hh, chroma)
     a = [rng.integers(0, 1 << depth, sum(sizes), dtype=np.uint16) for _ in range(5)]
     offs = np.cumsum([0] + sizes)
     inputs = [[x[offs[p]:offs[p + 1]] for p in range(3)] for x in a]
@@ -355,23 +316,6 @@ def test_ring_arming_rules(ctx):
 
 
 # ---- the command line -------------------------------------------------------------------------------------------------
-
-def _exe():
-    exe = os.path.join(ROOT, "hdr2yuv_amd", "hdr2yuv")
-    if not os.path.exists(exe):
-        subprocess.run(["make", "-C", os.path.join(ROOT, "hdr2yuv_amd", "cli"), "--no-print-directory"], check=True)
-    return exe
-
-
-def _run(args, rc=0):
-    r = subprocess.run([_exe()] + [str(a) for a in args], capture_output=True, text=True, timeout=600)
-    assert r.returncode == rc, r.stdout + r.stderr
-    return r.stdout
-
-
-def _report(out):
-    return [ln for ln in out.splitlines() if ln.startswith("histogram ")]
-
 
 def _cli_want(frames, w, hh, chroma, depth, full, gbr, bits, names):
     """the report's lines and FILE's text for frames (flat u16 each, planes in the counted order)"""
@@ -427,14 +371,14 @@ def test_cli_forward_file_and_lines(tmp_path, bits):
     n = 5
     src = _fwd_src(tmp_path, n)
     extra = [] if bits is None else ["--histogram_bits", bits]
-    out = _run(_fwd_args(src, n) + ["--dst_filename", tmp_path / "o.yuv", "--histogram", tmp_path / "h.csv", "--check_range", 1] + extra)
+    out = ht.cli_ok(_fwd_args(src, n) + ["--dst_filename", tmp_path / "o.yuv", "--histogram", tmp_path / "h.csv", "--check_range", 1] + extra).stdout
     yuv = np.fromfile(tmp_path / "o.yuv", np.uint16).reshape(n, -1)
     lines, text = _cli_want(list(yuv), W, HH, 1, 10, 0, 0, bits or 10, ["Y", "Cb", "Cr"])
-    assert _report(out) == lines, out
+    assert ht.lines_with(out, "histogram ") == lines, out
     assert (tmp_path / "h.csv").read_text() == text
     assert lines[-1].endswith("outside 0")  # write_yuv() clamps: nothing to find
-    out2 = _run(_fwd_args(src, n) + ["--histogram", tmp_path / "h2.csv"] + extra)  # no destination: nothing written
-    assert _report(out2) == lines and (tmp_path / "h2.csv").read_text() == text
+    out2 = ht.cli_ok(_fwd_args(src, n) + ["--histogram", tmp_path / "h2.csv"] + extra).stdout  # no destination: nothing written
+    assert ht.lines_with(out2, "histogram ") == lines and (tmp_path / "h2.csv").read_text() == text
     assert sorted(os.listdir(tmp_path)) == ["h.csv", "h2.csv", "in.yuv", "o.yuv"]
 
 
@@ -442,8 +386,8 @@ def test_cli_forward_file_and_lines(tmp_path, bits):
 def test_cli_gpus_2_same_output(tmp_path):
     n = 7
     src = _fwd_src(tmp_path, n)
-    one = _report(_run(_fwd_args(src, n) + ["--histogram", tmp_path / "h1.csv"]))
-    two = _report(_run(_fwd_args(src, n) + ["--histogram", tmp_path / "h2.csv", "--gpus", 2, "--devices", "0,0"]))
+    one = ht.lines_with(ht.cli_ok(_fwd_args(src, n) + ["--histogram", tmp_path / "h1.csv"]).stdout, "histogram ")
+    two = ht.lines_with(ht.cli_ok(_fwd_args(src, n) + ["--histogram", tmp_path / "h2.csv", "--gpus", 2, "--devices", "0,0"]).stdout, "histogram ")
     assert len(one) == n + 2 and one == two
     assert (tmp_path / "h1.csv").read_bytes() == (tmp_path / "h2.csv").read_bytes()
 
@@ -457,11 +401,11 @@ def test_cli_inverse_rgb(tmp_path):
     args = ["--src_filename", tmp_path / "in.yuv", "--src_pic_width", w, "--src_pic_height", hh, "--src_bit_depth", 10,
             "--src_chroma_format_idc", 1, "--src_matrix_coeffs", 9, "--dst_bit_depth", 12, "--n_frames", n, "--histogram",
             tmp_path / "h.csv", "--check_range", 1]
-    out = _run(args + ["--dst_filename", tmp_path / "o.rgb"])
+    out = ht.cli_ok(args + ["--dst_filename", tmp_path / "o.rgb"]).stdout
     rgb = np.fromfile(tmp_path / "o.rgb", np.uint16).reshape(n, 3, w * hh)  # planes R, G, B in the file
     gbr = [np.concatenate([f[1], f[2], f[0]]) for f in rgb]
     lines, text = _cli_want(gbr, w, hh, 3, 12, 0, 1, 12, ["G", "B", "R"])
-    assert _report(out) == lines, out
+    assert ht.lines_with(out, "histogram ") == lines, out
     assert (tmp_path / "h.csv").read_text() == text
 
 
@@ -470,12 +414,12 @@ def test_cli_inverse_rgb(tmp_path):
 def test_cli_histogram_only(tmp_path, ext, chroma, depth, full):
     w, hh, n = 35, 19, 4
     rng = np.random.default_rng(depth + chroma)
-    sizes = _sizes(w, hh, chroma)
+    sizes = ht.plane_sizes(w, hh, chroma)
     frames = [rng.integers(0, 1 << depth, sum(sizes), dtype=np.uint16) for _ in range(n + 1)]
     np.concatenate(frames).tofile(tmp_path / f"in.{ext}")
-    out = _run(["--histogram_only", 1, "--src_filename", tmp_path / f"in.{ext}", "--src_pic_width", w, "--src_pic_height", hh,
-                "--src_bit_depth", depth, "--src_chroma_format_idc", chroma, "--src_video_full_range_flag", full, "--src_start_frame", 1,
-                "--n_frames", n, "--histogram", tmp_path / "h.csv"])
+    out = ht.cli_ok(["--histogram_only", 1, "--src_filename", tmp_path / f"in.{ext}", "--src_pic_width", w, "--src_pic_height", hh,
+                     "--src_bit_depth", depth, "--src_chroma_format_idc", chroma, "--src_video_full_range_flag", full, "--src_start_frame", 1,
+                     "--n_frames", n, "--histogram", tmp_path / "h.csv"]).stdout
     counted = frames[1:]
     names = ["Y", "Cb", "Cr"]
     if ext == "rgb":  # planes R, G, B in the file; counted as G, B, R
@@ -483,44 +427,44 @@ def test_cli_histogram_only(tmp_path, ext, chroma, depth, full):
         counted = [np.concatenate([f[m:2 * m], f[2 * m:], f[:m]]) for f in counted]
         names = ["G", "B", "R"]
     lines, text = _cli_want(counted, w, hh, chroma, depth, full, int(ext == "rgb"), depth, names)
-    assert _report(out) == lines, out
+    assert ht.lines_with(out, "histogram ") == lines, out
     assert (tmp_path / "h.csv").read_text() == text
 
 
 @pytest.mark.gpu
 def test_cli_check_range(tmp_path):
     w, hh = 40, 10
-    sizes = _sizes(w, hh, 1)
+    sizes = ht.plane_sizes(w, hh, 1)
     rng = np.random.default_rng(5)
     legal = np.concatenate([rng.integers(64, 941, sizes[0]), rng.integers(64, 961, 2 * sizes[1])]).astype(np.uint16)
     legal[[0, 1, sizes[0], sizes[0] + 1]] = [64, 940, 64, 960]  # at the limits: legal
     np.concatenate([legal, legal]).tofile(tmp_path / "ok.yuv")
     base = ["--histogram_only", 1, "--src_pic_width", w, "--src_pic_height", hh, "--src_bit_depth", 10, "--src_chroma_format_idc", 1,
             "--n_frames", 2, "--histogram", tmp_path / "h.csv", "--check_range", 1]
-    out = _run(base + ["--src_filename", tmp_path / "ok.yuv"])
-    assert _report(out)[-1] == "histogram legal Y 64..940 Cb 64..960 Cr 64..960 outside 0", out
+    out = ht.cli_ok(base + ["--src_filename", tmp_path / "ok.yuv"]).stdout
+    assert ht.lines_with(out, "histogram ")[-1] == "histogram legal Y 64..940 Cb 64..960 Cr 64..960 outside 0", out
     bad = legal.copy()
     bad[sizes[0] + sizes[1] + 3] = 961  # one Cr sample above 960, in the second frame
     np.concatenate([legal, bad]).tofile(tmp_path / "bad.yuv")
-    out = _run(base + ["--src_filename", tmp_path / "bad.yuv"], rc=4)
+    out = ht.cli_ok(base + ["--src_filename", tmp_path / "bad.yuv"], rc=4).stdout
     lines, _ = _cli_want([legal, bad], w, hh, 1, 10, 0, 0, 10, ["Y", "Cb", "Cr"])
-    assert _report(out) == lines and lines[-1].endswith("outside 1") and " max 961 below 0 above 1 " in lines[1].split(" Cr ")[1], out
-    out = _run(base[:-2] + ["--src_filename", tmp_path / "bad.yuv"])  # without --check_range: reported, exit 0
-    assert _report(out)[-1].endswith("outside 1")
+    assert ht.lines_with(out, "histogram ") == lines and lines[-1].endswith("outside 1") and " max 961 below 0 above 1 " in lines[1].split(" Cr ")[1], out
+    out = ht.cli_ok(base[:-2] + ["--src_filename", tmp_path / "bad.yuv"]).stdout  # without --check_range: reported, exit 0
+    assert ht.lines_with(out, "histogram ")[-1].endswith("outside 1")
 
 
 @pytest.mark.gpu
 def test_cli_compare_only_with_histogram(tmp_path):
     w, hh, n = 34, 10, 3
     rng = np.random.default_rng(4)
-    total = sum(_sizes(w, hh, 1))
+    total = sum(ht.plane_sizes(w, hh, 1))
     a = rng.integers(0, 1024, n * total, dtype=np.uint16)
     a.tofile(tmp_path / "a.yuv")
     a.tofile(tmp_path / "b.yuv")
-    out = _run(["--compare_only", 1, "--src_filename", tmp_path / "a.yuv", "--ref_filename", tmp_path / "b.yuv", "--src_pic_width", w,
-                "--src_pic_height", hh, "--src_bit_depth", 10, "--src_chroma_format_idc", 1, "--n_frames", n, "--histogram",
-                tmp_path / "h.csv", "--histogram_bits", 5])
+    out = ht.cli_ok(["--compare_only", 1, "--src_filename", tmp_path / "a.yuv", "--ref_filename", tmp_path / "b.yuv", "--src_pic_width", w,
+                     "--src_pic_height", hh, "--src_bit_depth", 10, "--src_chroma_format_idc", 1, "--n_frames", n, "--histogram",
+                     tmp_path / "h.csv", "--histogram_bits", 5]).stdout
     lines, text = _cli_want(list(a.reshape(n, total)), w, hh, 1, 10, 0, 0, 5, ["Y", "Cb", "Cr"])
-    assert _report(out) == lines, out
+    assert ht.lines_with(out, "histogram ") == lines, out
     assert (tmp_path / "h.csv").read_text() == text
     assert "first_over none" in out

@@ -2,12 +2,14 @@
 (h2y_inverse_stream_open: the pinned h2y_stream_* ring for that flow) and the CLI's .yuv -> .rgb path on it.  The answers are the
 oracle's up444 + matrix_inverse (tests/test_oracle.py pins both to the reference's compiled functions), byte for byte."""
 import ctypes as C
+import functools
 import os
 import re
 
 import numpy as np
 import pytest
 
+import h2y_testing as ht
 import hdr2yuv_amd as h
 from hdr2yuv_amd import api
 from oracle import binding as ob
@@ -65,22 +67,6 @@ def _want(oracle, w, hh, chroma, alg, ind, full, mat, outd, planes):
     return oracle.matrix_inverse(w, hh, ind, full, mat, outd, planes)
 
 
-def _dev(p):
-    import torch
-
-    return torch.from_numpy(p.view(np.int16)).cuda()
-
-
-def _host(t):
-    return t.cpu().numpy().view(np.uint16)
-
-
-def _zeros(n):
-    import torch
-
-    return torch.zeros(n, dtype=torch.int16, device="cuda")
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("chroma,alg", FORMATS)
 def test_inverse_batch_parity(ctx, oracle, chroma, alg):
@@ -94,15 +80,15 @@ def test_inverse_batch_parity(ctx, oracle, chroma, alg):
     cases += [(1920, 1080, mat, DEPTHS[0], 2) for mat in (1, 11)] + [(1920, 1080, 9, DEPTHS[3], 2)]
     for (w, hh, mat, (ind, outd, full), nf) in cases:
         host = [_frame(rng, w, hh, chroma, ind) for _ in range(nf)]
-        din = [[_dev(p) for p in fr] for fr in host]
-        dout = [[_zeros(w * hh) for _ in range(3)] for _ in range(nf)]
+        din = [[ht.dev(p) for p in fr] for fr in host]
+        dout = [[ht.dev_zeros(w * hh, np.uint16) for _ in range(3)] for _ in range(nf)]
         torch.cuda.synchronize()  # the context's stream does not wait for torch's
         ctx.inverse_batch(w, hh, chroma, ind, full, mat, outd, alg, din, dout)
         assert ctx.last_kernel_name() == ("k_inverse420_batch" if chroma == 1 else "k_inverse_batch")
         for f in range(nf):
             want = _want(oracle, w, hh, chroma, alg, ind, full, mat, outd, host[f])
             for c in range(3):
-                got = _host(dout[f][c])
+                got = ht.host(dout[f][c], np.uint16)
                 assert np.array_equal(got, want[c]), (w, hh, mat, ind, outd, full, f, c, int(np.count_nonzero(got != want[c])))
     want_variant = {(1, 1): "k_inverse420_batch<FIR>", (1, 0): "k_inverse420_batch<REPLICATE>", (3, 0): "k_inverse_batch"}
     assert ctx.last_kernel_variant() == want_variant[(chroma, alg)]
@@ -126,7 +112,7 @@ def test_inverse_batch_pointer_tables(ctx, oracle, chroma, alg):
         ins = []
         for p in host[f]:
             b = torch.zeros(p.size + 8, dtype=torch.int16, device="cuda")
-            b[sh:sh + p.size] = _dev(p)
+            b[sh:sh + p.size] = ht.dev(p)
             bufs_in.append(b)
             ins.append(b[sh:sh + p.size])
         outs = []
@@ -144,9 +130,9 @@ def test_inverse_batch_pointer_tables(ctx, oracle, chroma, alg):
     for f in range(nf):
         want = _want(oracle, w, hh, chroma, alg, ind, full, mat, outd, host[f])
         for c in range(3):
-            assert np.array_equal(_host(dout[f][c]), want[c]), (f, c)
+            assert np.array_equal(ht.host(dout[f][c], np.uint16), want[c]), (f, c)
     for b, sh in bufs_out:
-        a = _host(b)
+        a = ht.host(b, np.uint16)
         assert np.all(a[:g + sh] == 0x5A5A) and np.all(a[g + sh + w * hh:] == 0x5A5A)
 
 
@@ -160,9 +146,9 @@ def test_inverse_batch_equals_single_frame_entries(ctx, chroma, alg):
     w, hh, nf = 320, 40, 4
     for (mat, (ind, outd, full)) in ((1, DEPTHS[0]), (11, DEPTHS[2])):
         host = [_frame(rng, w, hh, chroma, ind) for _ in range(nf)]
-        din = [[_dev(p) for p in fr] for fr in host]
-        batch = [[_zeros(w * hh) for _ in range(3)] for _ in range(nf)]
-        single = [[_zeros(w * hh) for _ in range(3)] for _ in range(nf)]
+        din = [[ht.dev(p) for p in fr] for fr in host]
+        batch = [[ht.dev_zeros(w * hh, np.uint16) for _ in range(3)] for _ in range(nf)]
+        single = [[ht.dev_zeros(w * hh, np.uint16) for _ in range(3)] for _ in range(nf)]
         torch.cuda.synchronize()
         ctx.inverse_batch(w, hh, chroma, ind, full, mat, outd, alg, din, batch)
         for f in range(nf):
@@ -184,8 +170,8 @@ def test_inverse_batch_splits_long_batches(ctx, oracle):
     rng = np.random.default_rng(64)
     w, hh, nf = 64, 8, fpl + 3
     host = [_frame(rng, w, hh, 1, 10) for _ in range(nf)]
-    din = [[_dev(p) for p in fr] for fr in host]
-    dout = [[_zeros(w * hh) for _ in range(3)] for _ in range(nf)]
+    din = [[ht.dev(p) for p in fr] for fr in host]
+    dout = [[ht.dev_zeros(w * hh, np.uint16) for _ in range(3)] for _ in range(nf)]
     torch.cuda.synchronize()
     ctx.inverse_batch(w, hh, 1, 10, 0, 9, 16, 1, din, dout)
     ms, launches = ctx.last_kernel_ms()
@@ -193,7 +179,7 @@ def test_inverse_batch_splits_long_batches(ctx, oracle):
     for f in range(nf):
         want = _want(oracle, w, hh, 1, 1, 10, 0, 9, 16, host[f])
         for c in range(3):
-            assert np.array_equal(_host(dout[f][c]), want[c]), (f, c)
+            assert np.array_equal(ht.host(dout[f][c], np.uint16), want[c]), (f, c)
 
 
 @pytest.mark.gpu
@@ -205,9 +191,9 @@ def test_inverse_batch_argument_errors(ctx, oracle):
     w, hh = 64, 16
     rng = np.random.default_rng(3)
     host = _frame(rng, w, hh, 1, 12)
-    din = [_dev(p) for p in host]
-    dout = [_zeros(w * hh) for _ in range(3)]
-    big = _zeros(w * hh + 8)
+    din = [ht.dev(p) for p in host]
+    dout = [ht.dev_zeros(w * hh, np.uint16) for _ in range(3)]
+    big = ht.dev_zeros(w * hh + 8, np.uint16)
     torch.cuda.synchronize()
 
     def code(*args, chroma=1, frames_in=None, frames_out=None, width=w):
@@ -221,7 +207,7 @@ def test_inverse_batch_argument_errors(ctx, oracle):
     assert code(frames_out=[[dout[0], dout[1], 0]]) == api.H2Y_EINVAL
     assert code(0) == api.H2Y_EUNSUPPORTED
     assert code(frames_out=[[dout[0], big[1:], dout[2]]]) == api.H2Y_EINVAL  # 2-byte aligned, 4:2:0 needs 4
-    full = [_zeros(w * hh) for _ in range(3)]
+    full = [ht.dev_zeros(w * hh, np.uint16) for _ in range(3)]
     assert code(chroma=3, frames_in=[[full[0], big[2:], full[2]]]) == api.H2Y_EINVAL  # 4-byte aligned, 4:4:4 needs 8
     assert code(width=66) == api.H2Y_EINVAL
     ctx.inverse_stream_open(w, hh, 1, 12, 0, 9, 16, 1, 3)
@@ -230,26 +216,14 @@ def test_inverse_batch_argument_errors(ctx, oracle):
     ctx.inverse_batch(w, hh, 1, 12, 0, 9, 16, 1, [din], [dout])
     want = _want(oracle, w, hh, 1, 1, 12, 0, 9, 16, host)
     for c in range(3):
-        assert np.array_equal(_host(dout[c]), want[c])
+        assert np.array_equal(ht.host(dout[c], np.uint16), want[c])
 
 
-def _run_inverse_stream(ctx, frames, depth):
-    """Push frames through the open stream the way the CLI does; the outputs in the order they come out."""
-    outs, in_flight = [], 0
-    for fr in frames:
-        planes = ctx.stream_input()
-        for dst, src in zip(planes, fr):
-            assert dst.shape == src.shape
-            dst[:] = src
-        ctx.stream_submit()
-        in_flight += 1
-        if in_flight == depth - 1:
-            outs.append(ctx.stream_output().copy())
-            in_flight -= 1
-    while in_flight:
-        outs.append(ctx.stream_output().copy())
-        in_flight -= 1
-    return outs
+def _fill(fr, slots):
+    """the frame's planes into the slot's, which have their shapes"""
+    for dst, src in zip(slots, fr):
+        assert dst.shape == src.shape
+        dst[:] = src
 
 
 @pytest.mark.gpu
@@ -265,8 +239,7 @@ def test_inverse_stream(ctx, oracle, depth, chroma, alg, w, hh):
     d = h.make_desc(64, 32, dst_depth=12, dst_matrix=h.MATRIX_BT2020NC, resampler=0)
     with pytest.raises(h.H2YError):
         ctx.stream_open(d, 3)
-    outs = _run_inverse_stream(ctx, frames, depth)
-    ctx.stream_close()
+    outs = [r["out"] for r in ht.drive_ring(ctx, [functools.partial(_fill, fr) for fr in frames], depth)]
     assert len(outs) == 9
     for f, got in enumerate(outs):
         assert got.shape == (3, w * hh)
@@ -290,8 +263,6 @@ def test_inverse_stream(ctx, oracle, depth, chroma, alg, w, hh):
 def test_cli_inverse_flow_over_several_frames(tmp_path, oracle):
     """.yuv 4:2:0 (FIR) in, .rgb out over frames 1..5 of seven, appended behind what the file holds: R, G, B planes of every
     frame at `old size + k x frame bytes`; two contexts (--gpus 2 --devices 0,0) write the same bytes."""
-    import subprocess
-
     rng = np.random.default_rng(7)
     w, hh, ind = 132, 18, 12
     frames = [_frame(rng, w, hh, 1, ind) for _ in range(7)]
@@ -300,9 +271,6 @@ def test_cli_inverse_flow_over_several_frames(tmp_path, oracle):
     args = ["--src_filename", src, "--src_pic_width", w, "--src_pic_height", hh, "--src_bit_depth", ind, "--dst_bit_depth", 16,
             "--src_matrix_coeffs", 11, "--src_chroma_format_idc", 1, "--dst_chroma_format_idc", 3, "--chroma_resampler_type", 1,
             "--src_start_frame", 1, "--n_frames", 5]
-    exe = os.path.join(ROOT, "hdr2yuv_amd", "hdr2yuv")
-    if not os.path.exists(exe):
-        subprocess.run(["make", "-C", os.path.join(ROOT, "hdr2yuv_amd", "cli"), "--no-print-directory"], check=True)
     want = [b"\x07" * 10]
     for k in range(1, 6):
         g, b, r = _want(oracle, w, hh, 1, 1, ind, 0, 11, 16, frames[k])
@@ -311,7 +279,6 @@ def test_cli_inverse_flow_over_several_frames(tmp_path, oracle):
     for name, extra in (("one.rgb", []), ("two.rgb", ["--gpus", 2, "--devices", "0,0"])):
         dst = tmp_path / name
         dst.write_bytes(b"\x07" * 10)
-        r = subprocess.run([exe] + [str(a) for a in args + ["--dst_filename", dst] + extra], capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stdout + r.stderr
+        r = ht.cli_ok(args + ["--dst_filename", dst] + extra, timeout=300)
         assert "frames: 5" in r.stdout
         assert dst.read_bytes() == want, name

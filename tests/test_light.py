@@ -1,28 +1,18 @@
 """Content light (MaxCLL / MaxFALL) on the GPU: k_light through h2y_light_batch, every forward ring armed with h2y_stream_light,
 and the command line's --content_light.  Every expected figure is the numpy restatement (light_ref.py) on the same samples, bit
 for bit: max_bits, the position of the peak and sum_q."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+import h2y_testing as ht
 import hdr2yuv_amd as h
 import light_ref as lr
 from dpx_files import pack_pixels, write_dpx
 from exr_files import HALF, read_exr, smooth_half, write_exr
 from tiff_files import write_tiff
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F32, F16, U16 = h.SAMPLE_F32, h.SAMPLE_F16, h.SAMPLE_U16
 NP = {F32: np.float32, F16: np.float16, U16: np.uint16}
-
-
-def _dev(x):
-    import torch
-
-    x = np.ascontiguousarray(x).reshape(-1)
-    return torch.from_numpy(x.view(np.int16) if x.dtype == np.uint16 else x).cuda()
 
 
 def _want(planes, w, sample, src_transfer, src_depth=32, override=None):
@@ -40,7 +30,7 @@ def _batch(ctx, frames, w, hh, sample, src_transfer=8, src_depth=32, stats=None)
     """h2y_light_batch on frames (lists of three host planes), checked against the restatement; the stats"""
     d = h.make_desc(w, hh, sample=sample, src_depth=src_depth, dst_depth=10 if sample != U16 else min(10, src_depth),
                     src_transfer=src_transfer, dst_transfer=16, dst_matrix=h.MATRIX_BT2020NC, chroma=3, resampler=0, stats=stats)
-    dev = [[_dev(p) for p in f] for f in frames]
+    dev = [[ht.dev(p) for p in f] for f in frames]
     st = ctx.light_batch(d, dev)
     assert ctx.last_kernel_name() == "k_light"
     ov = None if stats is None else ([s[0] for s in stats], [s[1] for s in stats])
@@ -165,7 +155,7 @@ def test_batch_70_frames_two_launches(ctx):
 
 @pytest.mark.gpu
 def test_batch_refusals(ctx):
-    f = [_dev(np.zeros(64, np.float32)) for _ in range(3)]
+    f = [ht.dev(np.zeros(64, np.float32)) for _ in range(3)]
     for kw, why in ((dict(dst_transfer=1), "dst_transfer"), (dict(src_transfer=16), "PQ source"),
                     (dict(src_matrix=h.MATRIX_BT709, dst_matrix=h.MATRIX_BT2020NC), "G,B,R source")):
         d = h.make_desc(8, 8, **dict(dict(chroma=3, resampler=0), **kw))
@@ -183,31 +173,8 @@ def _ring(ctx, opener, inputs, light, depth=3, refs=None, hist=False):
         ctx.stream_histogram()
     if light:
         ctx.stream_light()
-    got, ls, inflight = [], [], 0
-
-    def take():
-        got.append(ctx.stream_output().copy())
-        if light:
-            ls.append(ctx.stream_light_result())
-
-    for k, inp in enumerate(inputs):
-        for dst, src in zip(ctx.stream_input(), inp):
-            if callable(src):
-                src(dst)
-            else:
-                dst[:] = src
-        if refs is not None:
-            ctx.stream_reference()[:] = refs[k]
-        ctx.stream_submit()
-        inflight += 1
-        if inflight == depth - 1:
-            take()
-            inflight -= 1
-    while inflight:
-        take()
-        inflight -= 1
-    ctx.stream_close()
-    return got, ls
+    recs = ht.drive_ring(ctx, inputs, depth, refs=refs, results=("light",) if light else ())
+    return [r["out"] for r in recs], [r["light"] for r in recs if light]
 
 
 def _armed(ctx, opener, inputs, wants):
@@ -236,7 +203,7 @@ def test_forward_ring(ctx, sample, src_transfer):
                     chroma=1, resampler=1)
     wants = [_want(f, w, sample, src_transfer, depth) for f in frames]
     _armed(ctx, lambda: ctx.stream_open(d, 3), frames, wants)
-    st = ctx.light_batch(d, [[_dev(p) for p in f] for f in frames])  # the batch's figures
+    st = ctx.light_batch(d, [[ht.dev(p) for p in f] for f in frames])  # the batch's figures
     for k in range(4):
         _check(st[k], wants[k], k)
 
@@ -300,23 +267,6 @@ def test_ring_arming_rules(ctx):
 
 # ---- the command line ---------------------------------------------------------------------------------------------------
 
-def _exe():
-    exe = os.path.join(ROOT, "hdr2yuv_amd", "hdr2yuv")
-    if not os.path.exists(exe):
-        subprocess.run(["make", "-C", os.path.join(ROOT, "hdr2yuv_amd", "cli"), "--no-print-directory"], check=True)
-    return exe
-
-
-def _run(args):
-    r = subprocess.run([_exe()] + [str(a) for a in args], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return r.stdout
-
-
-def _lines(out):
-    return [ln for ln in out.splitlines() if ln.startswith("light ")]
-
-
 W, HH, N = 64, 24, 5
 
 
@@ -330,14 +280,14 @@ def _args(src, extra=(), light=True):
 def _cli_cases(tmp_path, src, want):
     """with and without a destination, beside --histogram and --ref_filename, and with --gpus 2: the same light lines"""
     lines = lr.report_lines(want)
-    out = _run(_args(src, ["--dst_filename", tmp_path / "o.yuv"]))
-    assert _lines(out) == lines, out
-    assert _lines(_run(_args(src))) == lines
-    both = _run(_args(src, ["--ref_filename", tmp_path / "o.yuv", "--histogram", tmp_path / "h.csv"]))
-    assert _lines(both) == lines and any(x.startswith("summary frames") for x in both.splitlines())
-    assert _lines(_run(_args(src, ["--gpus", 2, "--devices", "0,0"]))) == lines
-    out0 = _run(_args(src, ["--dst_filename", tmp_path / "p.yuv"], light=False))  # without the flag: the same bytes, no light lines
-    assert not _lines(out0) and (tmp_path / "o.yuv").read_bytes() == (tmp_path / "p.yuv").read_bytes()
+    out = ht.cli_ok(_args(src, ["--dst_filename", tmp_path / "o.yuv"])).stdout
+    assert ht.lines_with(out, "light ") == lines, out
+    assert ht.lines_with(ht.cli_ok(_args(src)).stdout, "light ") == lines
+    both = ht.cli_ok(_args(src, ["--ref_filename", tmp_path / "o.yuv", "--histogram", tmp_path / "h.csv"])).stdout
+    assert ht.lines_with(both, "light ") == lines and any(x.startswith("summary frames") for x in both.splitlines())
+    assert ht.lines_with(ht.cli_ok(_args(src, ["--gpus", 2, "--devices", "0,0"])).stdout, "light ") == lines
+    out0 = ht.cli_ok(_args(src, ["--dst_filename", tmp_path / "p.yuv"], light=False)).stdout  # without the flag: the same bytes, no light lines
+    assert not ht.lines_with(out0, "light ") and (tmp_path / "o.yuv").read_bytes() == (tmp_path / "p.yuv").read_bytes()
 
 
 @pytest.mark.gpu

@@ -1,13 +1,10 @@
 """Content light (MaxCLL / MaxFALL) on the host: the numpy restatement (light_ref.py) on cases that can be checked by hand, and the
 command line's --content_light as --dry_run resolves it, with every refusal, before any device is touched."""
-import os
-import subprocess
-
 import numpy as np
 
+import h2y_testing as ht
 import light_ref as lr
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W, HH = 16, 8
 F32 = np.float32
 
@@ -86,23 +83,6 @@ def test_report_lines():
 
 # ---- the command line ----------------------------------------------------------------------------------------------------
 
-def _exe():
-    exe = os.path.join(ROOT, "hdr2yuv_amd", "hdr2yuv")
-    if not os.path.exists(exe):
-        subprocess.run(["make", "-C", os.path.join(ROOT, "hdr2yuv_amd", "cli"), "--no-print-directory"], check=True)
-    return exe
-
-
-def _run(args):
-    r = subprocess.run([_exe()] + [str(a) for a in args], capture_output=True, text=True, timeout=60)
-    return r.returncode, r.stdout
-
-
-def _file(path, nbytes):
-    np.zeros(nbytes, np.uint8).tofile(path)
-    return path
-
-
 def _forward(src, src_tf=8, dst_tf=16, extra=()):
     return ["--src_filename", src, "--src_pic_width", W, "--src_pic_height", HH, "--src_bit_depth", 32, "--dst_bit_depth", 10,
             "--dst_chroma_format_idc", 1, "--dst_matrix_coeffs", 9, "--src_transfer_characteristics", src_tf,
@@ -110,48 +90,48 @@ def _forward(src, src_tf=8, dst_tf=16, extra=()):
 
 
 def test_dry_run_prints_the_setting(tmp_path):
-    src = _file(tmp_path / "in.f32", 2 * 3 * W * HH * 4)
+    src = ht.zero_file(tmp_path / "in.f32", 2 * 3 * W * HH * 4)
     for extra in ([], ["--dst_filename", tmp_path / "o.yuv"], ["--histogram", tmp_path / "h.csv"]):
-        rc, out = _run(_forward(src, extra=extra + ["--content_light", 1]))
-        assert rc == 0, out
-        lines = out.splitlines()
+        r = ht.run_cli(_forward(src, extra=extra + ["--content_light", 1]), timeout=60)
+        assert r.returncode == 0, r.stdout
+        lines = r.stdout.splitlines()
         assert "content_light: 1" in lines
         assert "content_light_from: src_transfer_characteristics 8 -> PQ, G,B,R, floor and ceiling of each frame's pic_stats" in lines
-        rc0, out0 = _run(_forward(src, extra=extra))
+        r0 = ht.run_cli(_forward(src, extra=extra), timeout=60)
         if extra:  # without --content_light nothing changes
-            assert rc0 == 0 and [x for x in lines if not x.startswith("content_light")] == out0.splitlines()
-    rc, out = _run(_forward(src, src_tf=1, extra=["--content_light", 1]))
-    assert rc == 0 and "content_light_from: src_transfer_characteristics 1 -> PQ" in out
+            assert r0.returncode == 0 and [x for x in lines if not x.startswith("content_light")] == r0.stdout.splitlines()
+    r = ht.run_cli(_forward(src, src_tf=1, extra=["--content_light", 1]), timeout=60)
+    assert r.returncode == 0 and "content_light_from: src_transfer_characteristics 1 -> PQ" in r.stdout
     assert not (tmp_path / "o.yuv").exists()
 
 
 def test_dry_run_beside_reference(tmp_path):
-    src = _file(tmp_path / "in.f32", 2 * 3 * W * HH * 4)
-    ref = _file(tmp_path / "r.yuv", 2 * (W * HH * 3 // 2) * 2)
-    rc, out = _run(_forward(src, extra=["--ref_filename", ref, "--content_light", 1]))
-    assert rc == 0, out
-    assert "content_light: 1" in out.splitlines() and any(x.startswith("compare: ") for x in out.splitlines())
+    src = ht.zero_file(tmp_path / "in.f32", 2 * 3 * W * HH * 4)
+    ref = ht.zero_file(tmp_path / "r.yuv", 2 * (W * HH * 3 // 2) * 2)
+    r = ht.run_cli(_forward(src, extra=["--ref_filename", ref, "--content_light", 1]), timeout=60)
+    assert r.returncode == 0, r.stdout
+    assert "content_light: 1" in r.stdout.splitlines() and any(x.startswith("compare: ") for x in r.stdout.splitlines())
 
 
 def _refused(args, why):
-    rc, out = _run(args)
-    assert rc == 1, out
-    assert why in out, out
-    assert "TOO MANY ARGUMENT ERRORS" in out
+    r = ht.run_cli(args, timeout=60)
+    assert r.returncode == 1, r.stdout
+    assert why in r.stdout, r.stdout
+    assert "TOO MANY ARGUMENT ERRORS" in r.stdout
 
 
 def test_refused_destination_not_pq(tmp_path):
-    src = _file(tmp_path / "in.f32", 2 * 3 * W * HH * 4)
+    src = ht.zero_file(tmp_path / "in.f32", 2 * 3 * W * HH * 4)
     _refused(_forward(src, dst_tf=1, extra=["--content_light", 1]), "needs a PQ destination: dst_transfer_characteristics(1) is not 16")
 
 
 def test_refused_pq_source(tmp_path):
-    src = _file(tmp_path / "in.f32", 2 * 3 * W * HH * 4)
+    src = ht.zero_file(tmp_path / "in.f32", 2 * 3 * W * HH * 4)
     _refused(_forward(src, src_tf=16, extra=["--content_light", 1]), "a PQ source (src_transfer_characteristics 16)")
 
 
 def test_refused_matrix_not_gbr(tmp_path):
-    src = _file(tmp_path / "in.yuv", 2 * 3 * W * HH * 2)
+    src = ht.zero_file(tmp_path / "in.yuv", 2 * 3 * W * HH * 2)
     args = ["--src_filename", src, "--src_pic_width", W, "--src_pic_height", HH, "--src_bit_depth", 16, "--src_chroma_format_idc", 3,
             "--src_matrix_coeffs", 9, "--dst_bit_depth", 10, "--dst_chroma_format_idc", 1, "--src_transfer_characteristics", 8,
             "--dst_transfer_characteristics", 16, "--dst_filename", tmp_path / "o.yuv", "--content_light", 1, "--dry_run", 1]
@@ -159,7 +139,7 @@ def test_refused_matrix_not_gbr(tmp_path):
 
 
 def test_refused_inverse_flow(tmp_path):
-    src = _file(tmp_path / "in.yuv", 2 * (W * HH * 3 // 2) * 2)
+    src = ht.zero_file(tmp_path / "in.yuv", 2 * (W * HH * 3 // 2) * 2)
     args = ["--src_filename", src, "--dst_filename", tmp_path / "o.rgb", "--src_pic_width", W, "--src_pic_height", HH,
             "--src_bit_depth", 10, "--src_chroma_format_idc", 1, "--dst_bit_depth", 12, "--src_matrix_coeffs", 9, "--dst_matrix_coeffs", 0,
             "--src_transfer_characteristics", 16, "--dst_transfer_characteristics", 16, "--content_light", 1, "--dry_run", 1]
@@ -168,7 +148,7 @@ def test_refused_inverse_flow(tmp_path):
 
 def test_refused_compare_only_and_histogram_only(tmp_path):
     n = (W * HH * 3 // 2) * 2
-    a, b = _file(tmp_path / "a.yuv", 2 * n), _file(tmp_path / "b.yuv", 2 * n)
+    a, b = ht.zero_file(tmp_path / "a.yuv", 2 * n), ht.zero_file(tmp_path / "b.yuv", 2 * n)
     common = ["--src_filename", a, "--src_pic_width", W, "--src_pic_height", HH, "--src_bit_depth", 10, "--src_chroma_format_idc", 1,
               "--n_frames", 2, "--content_light", 1, "--dry_run", 1]
     _refused(common + ["--compare_only", 1, "--ref_filename", b], "measures a conversion: not with --compare_only 1")
@@ -176,5 +156,5 @@ def test_refused_compare_only_and_histogram_only(tmp_path):
 
 
 def test_refused_value_2(tmp_path):
-    src = _file(tmp_path / "in.f32", 2 * 3 * W * HH * 4)
+    src = ht.zero_file(tmp_path / "in.f32", 2 * 3 * W * HH * 4)
     _refused(_forward(src, extra=["--content_light", 2]), "content_light(2) not 0 or 1")

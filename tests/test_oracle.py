@@ -1,20 +1,16 @@
 """CPU tests of the oracle (oracle/h2y_oracle.c): against the committed golden
 vectors, and against the reference's own object code -- its answers recorded in
 tests/golden/ref_answers.npz, and run live as well where oracle/_ref exists."""
-import hashlib
 import json
 import os
 
 import numpy as np
 import pytest
 
+import h2y_testing as ht
 from oracle import binding as ob
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
-
-
-def _md5(a):
-    return hashlib.md5(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
 def _same(ours, theirs):
@@ -28,7 +24,7 @@ def _same(ours, theirs):
 def _differing(ours, theirs):
     """For a failure message: how many samples differ (against a RecordedArray only the two md5s can be shown)."""
     if isinstance(theirs, ob.RecordedArray):
-        return f"md5 {_md5(np.asarray(ours, dtype=theirs.dtype))} against {theirs.md5}"
+        return f"md5 {ht.md5(np.asarray(ours, dtype=theirs.dtype))} against {theirs.md5}"
     return int(np.count_nonzero(ours != theirs))
 
 
@@ -40,7 +36,7 @@ def test_golden_vectors(oracle):
         d = ob.make_desc(**case["desc"])
         got = oracle.convert_frame(d, [z["in0"], z["in1"], z["in2"]])
         assert np.array_equal(got, z["yuv"]), case["file"]
-        assert _md5(got) == case["md5"]
+        assert ht.md5(got) == case["md5"]
 
 
 def test_known_md5_small_and_1080p(oracle):
@@ -53,7 +49,7 @@ def test_known_md5_small_and_1080p(oracle):
         planes = oracle.synth_frame(d.width, d.height, 0)
         got = oracle.convert_frame(d, planes)
         assert got.nbytes == case["bytes"]
-        assert _md5(got) == case["md5"], name
+        assert ht.md5(got) == case["md5"], name
 
 
 def test_pq_known_points(oracle):

@@ -4,14 +4,10 @@ Depth 2 and five frames, so every slot is reused at least twice.  No tolerance: 
 import numpy as np
 import pytest
 
+import h2y_testing as ht
 import hdr2yuv_amd.api as h
 
 DEPTH, FRAMES = 2, 5
-
-
-def _noisy(x, depth, rng, amp=3):
-    """x with a few codes changed, so that no PSNR is infinite"""
-    return np.clip(x.astype(np.int64) + rng.integers(-amp, amp + 1, x.size), 0, (1 << depth) - 1).astype(np.uint16)
 
 
 def _ring(ctx, opener, inputs, refs=None, keep=None, ssim=None, hist=None, light=False):
@@ -27,41 +23,23 @@ def _ring(ctx, opener, inputs, refs=None, keep=None, ssim=None, hist=None, light
         ctx.stream_histogram(**hist)
     if light:
         ctx.stream_light()
-    res = []
-    try:
-        for k, inp in enumerate(inputs):
-            for dst, src in zip(ctx.stream_input(), inp):
-                dst[:] = src
-            if refs is not None:
-                ctx.stream_reference()[:] = refs[k]
-            ctx.stream_submit()
-            o = ctx.stream_output()  # depth 2: one frame in flight
-            r = {"out": None if o is None else o.copy()}
-            if refs is not None:
-                r["cmp"] = ctx.stream_compare_result().as_dict()
-            if ssim is not None:
-                r["ssim"] = ctx.stream_ssim_result()
-            if hist is not None:
-                r["hist"] = ctx.stream_histogram_result()
-            if light:
-                r["light"] = ctx.stream_light_result()
-            res.append(r)
-    finally:
-        ctx.stream_close()
+    armed = [("compare", refs is not None), ("ssim", ssim is not None), ("histogram", hist is not None), ("light", light)]
+    res = ht.drive_ring(ctx, inputs, DEPTH, refs=refs, results=[name for name, on in armed if on])
     assert len(res) == FRAMES
     return res
 
 
 def _same(full, alone, stage, k):
     a, b = full[stage], alone[stage]
-    if stage == "cmp":
+    if stage == "compare":
+        a, b = a.as_dict(), b.as_dict()
         assert a == b, (stage, k, a, b)
         assert all(s > 0 for s in a["sse"]), (k, a)  # the references differ from the frames: a finite PSNR
     elif stage == "ssim":
         assert list(a.windows) == list(b.windows) and list(a.sum_q) == list(b.sum_q), (stage, k, a, b)
         assert [float(x).hex() for x in a.ssim] == [float(x).hex() for x in b.ssim], (stage, k, a, b)
         assert float(a.all).hex() == float(b.all).hex(), (stage, k, a, b)
-    elif stage == "hist":
+    elif stage == "histogram":
         assert np.array_equal(np.frombuffer(a[0], np.uint8), np.frombuffer(b[0], np.uint8)), (stage, k, a[0], b[0])
         assert np.array_equal(a[1], b[1]), (stage, k)
     else:
@@ -94,12 +72,12 @@ def test_forward_ring_all_stages(ctx):
                     resampler=1)
     opener = lambda: ctx.stream_open(d, DEPTH)  # noqa: E731
     plain = _ring(ctx, opener, frames)
-    refs = [_noisy(p["out"], 10, rng) for p in plain]
+    refs = [ht.noisy(p["out"], 10, rng) for p in plain]
     full = _ring(ctx, opener, frames, refs, keep=1, ssim=-1, hist={}, light=True)
     alone = {
-        "cmp": _ring(ctx, opener, frames, refs, keep=1),
+        "compare": _ring(ctx, opener, frames, refs, keep=1),
         "ssim": _ring(ctx, opener, frames, refs, keep=1, ssim=-1),
-        "hist": _ring(ctx, opener, frames, hist={}),
+        "histogram": _ring(ctx, opener, frames, hist={}),
         "light": _ring(ctx, opener, frames, light=True),
     }
     _check(full, alone, plain, True)
@@ -113,16 +91,16 @@ def test_inverse_ring_all_stages(ctx):
     frames = [[rng.integers(0, 1024, m).astype(np.uint16) for m in sizes] for _ in range(FRAMES)]
     opener = lambda: ctx.inverse_stream_open(w, hh, 1, 10, 0, h.MATRIX_BT2020NC, 12, 1, DEPTH)  # noqa: E731
     plain = _ring(ctx, opener, frames)
-    refs = [_noisy(p["out"].reshape(-1), 12, rng) for p in plain]
+    refs = [ht.noisy(p["out"].reshape(-1), 12, rng) for p in plain]
     full = _ring(ctx, opener, frames, refs, keep=0, ssim=-1, hist={})
     alone = {
-        "cmp": _ring(ctx, opener, frames, refs, keep=0),
+        "compare": _ring(ctx, opener, frames, refs, keep=0),
         "ssim": _ring(ctx, opener, frames, refs, keep=0, ssim=-1),
     }
     _check(full, alone, plain, False)
     hist = _ring(ctx, opener, frames, hist={})  # the histogram alone keeps the frame
     for k in range(FRAMES):
-        _same(full[k], hist[k], "hist", k)
+        _same(full[k], hist[k], "histogram", k)
         assert np.array_equal(hist[k]["out"], plain[k]["out"]), k
 
 
@@ -134,13 +112,13 @@ def test_compare_only_ring_all_stages(ctx):
     a = [rng.integers(0, 1024, sum(sizes), dtype=np.uint16) for _ in range(FRAMES)]
     offs = np.cumsum([0] + sizes)
     frames = [[x[offs[p]:offs[p + 1]] for p in range(3)] for x in a]
-    refs = [_noisy(x, 10, rng) for x in a]
+    refs = [ht.noisy(x, 10, rng) for x in a]
     opener = lambda: ctx.compare_stream_open(w, hh, chroma, 0, DEPTH)  # noqa: E731
     hist = dict(bits=10, bit_depth=10, full_range=0, gbr=0)
     full = _ring(ctx, opener, frames, refs, ssim=10, hist=hist)
     alone = {
-        "cmp": _ring(ctx, opener, frames, refs),
+        "compare": _ring(ctx, opener, frames, refs),
         "ssim": _ring(ctx, opener, frames, refs, ssim=10),
-        "hist": _ring(ctx, opener, frames, refs, hist=hist),
+        "histogram": _ring(ctx, opener, frames, refs, hist=hist),
     }
     _check(full, alone, None, False)

@@ -1,12 +1,10 @@
 """Scaling on the GPU: k_scale through h2y_scale_batch, the armed forward rings and the scale-only ring, bit for bit against the
 numpy restatement (scale_ref.py), and the command line's --scale and --scale_only.  The restatement's pixels are computed with the tables h2y_scale_taps returned (which
 test_scale_host.py holds equal to the restatement's own), so a table fault and a kernel fault cannot hide each other."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+import h2y_testing as ht
 import hdr2yuv_amd as h
 import scale_ref as sr
 from dpx_files import pack_pixels, write_dpx
@@ -25,19 +23,13 @@ def _want(frame, sw, sh, dw, dh, chroma, depth, full, gbr, a):
     return sr.scale_frame(frame, sw, sh, dw, dh, chroma, depth, full, gbr, a, taps_fn=_lib_taps)
 
 
-def _dev(x):
-    import torch
-
-    return torch.from_numpy(np.ascontiguousarray(x).reshape(-1).view(np.int16)).cuda()
-
-
 def _batch(ctx, frames, sw, sh, dw, dh, chroma, depth=10, full=0, gbr=0, a=3, wants=None):
     """h2y_scale_batch on frames (flat u16 host frames), each output checked against the restatement"""
     import torch
 
     words = sr.frame_words(dw, dh, chroma)
     assert h.scale_frame_bytes(dw, dh, chroma) == 2 * words
-    src = [_dev(f) for f in frames]
+    src = [ht.dev(f) for f in frames]
     dst = [torch.full((words + GUARD,), 0x5A5A, dtype=torch.int16, device="cuda") for _ in frames]
     ctx.scale_batch(sw, sh, dw, dh, chroma, depth, full, gbr, a, src, dst)
     assert ctx.last_kernel_name() == "k_scale"
@@ -191,41 +183,20 @@ def _ring(ctx, opener, inputs, scale=None, light=False, depth=3):
         ctx.stream_light()
     if scale:
         ctx.stream_scale(*scale)
-    got, ls, inflight = [], [], 0
-
-    def take():
-        got.append(ctx.stream_output().copy())
-        if light:
-            ls.append(ctx.stream_light_result().as_dict())
-
-    for inp in inputs:
-        for dst, src in zip(ctx.stream_input(), inp):
-            if callable(src):
-                src(dst)
-            else:
-                dst[:] = src
-        ctx.stream_submit()
-        inflight += 1
-        if inflight == depth - 1:
-            take()
-            inflight -= 1
-    while inflight:
-        take()
-        inflight -= 1
-    ctx.stream_close()
-    return got, ls
+    recs = ht.drive_ring(ctx, inputs, depth, results=("light",) if light else ())
+    return [r["out"] for r in recs], [r["light"].as_dict() for r in recs if light]
 
 
-def _armed(ctx, opener, inputs, d, dw, dh, a=3, light=False):
+def _armed(ctx, opener, inputs, d, dw, dh, a=3, light=False, depth=3):
     """the armed ring's frames are the restatement of the unarmed ring's; the light beside it is the unarmed ring's"""
-    plain, ls0 = _ring(ctx, opener, inputs, None, light)
-    armed, ls1 = _ring(ctx, opener, inputs, (dw, dh, a), light)
+    plain, ls0 = _ring(ctx, opener, inputs, None, light, depth)
+    armed, ls1 = _ring(ctx, opener, inputs, (dw, dh, a), light, depth)
     assert len(plain) == len(armed) == len(inputs)
     for k in range(len(inputs)):
         want = _want(plain[k].reshape(-1), d.width, d.height, dw, dh, d.dst_chroma_format_idc, d.dst_bit_depth, d.dst_full_range, 0, a)
         assert armed[k].shape == want.shape and np.array_equal(armed[k], want), k
     assert ls0 == ls1 and len(ls0) == (len(inputs) if light else 0)
-    again, _ = _ring(ctx, opener, inputs, None)  # a ring opened after an armed one is unarmed
+    again, _ = _ring(ctx, opener, inputs, None, depth=depth)  # a ring opened after an armed one is unarmed
     assert all(np.array_equal(x, y) for x, y in zip(again, plain))
 
 
@@ -245,7 +216,7 @@ def test_forward_ring(ctx, sample):
     _armed(ctx, lambda: ctx.stream_open(d, 3), frames, d, 100, 12, 3, light=True)
     d3 = h.make_desc(w, hh, sample=sample, src_depth=depth, dst_depth=min(depth, 16), dst_matrix=h.MATRIX_BT709, chroma=3, resampler=0,
                      full_range=1)
-    _armed(ctx, lambda: ctx.stream_open(d3, 4), frames, d3, 17, 80, 4)  # a scaled frame larger than the source's
+    _armed(ctx, lambda: ctx.stream_open(d3, 4), frames, d3, 17, 80, 4, depth=3)  # a scaled frame larger than the source's; two frames in flight in a ring of four slots
 
 
 @pytest.mark.gpu
@@ -339,21 +310,7 @@ def test_ring_arming_rules(ctx):
 
 # ---- the command line ---------------------------------------------------------------------------------------------------
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W, HH, N = 64, 24, 5
-
-
-def _exe():
-    exe = os.path.join(ROOT, "hdr2yuv_amd", "hdr2yuv")
-    if not os.path.exists(exe):
-        subprocess.run(["make", "-C", os.path.join(ROOT, "hdr2yuv_amd", "cli"), "--no-print-directory"], check=True)
-    return exe
-
-
-def _run(args):
-    r = subprocess.run([_exe()] + [str(a) for a in args], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return r.stdout
 
 
 def _args(src, dst, extra=(), chroma=1):
@@ -374,22 +331,22 @@ def _scaled_file(path, dw, dh, chroma, depth, full, gbr, a, sw=W, sh=HH):
 def _cli_cases(tmp_path, src, chroma=1):
     """the scaled run's file is the restatement of the unscaled run's; appending, --gpus 2 and the light lines beside it"""
     plain, dw, dh = tmp_path / "plain.yuv", 40, 36
-    out0 = _run(_args(src, plain, ["--content_light", 1], chroma))
+    out0 = ht.cli_ok(_args(src, plain, ["--content_light", 1], chroma)).stdout
     to = ["--dst_pic_width", dw, "--dst_pic_height", dh, "--scale", 1]
     want = _scaled_file(plain, dw, dh, chroma, 10, 0, 0, 3)
-    out1 = _run(_args(src, tmp_path / "s.yuv", to + ["--content_light", 1], chroma))
+    out1 = ht.cli_ok(_args(src, tmp_path / "s.yuv", to + ["--content_light", 1], chroma)).stdout
     got = np.fromfile(tmp_path / "s.yuv", np.uint16)
     assert got.size == N * sr.frame_words(dw, dh, chroma) and np.array_equal(got, want)
     light = lambda out: [x for x in out.splitlines() if x.startswith("light ")]  # noqa: E731
     assert light(out0) and light(out1) == light(out0)  # --content_light reads the source planes: unchanged by --scale
-    _run(_args(src, tmp_path / "s.yuv", to, chroma))  # appending: what is in the file stays
+    ht.cli_ok(_args(src, tmp_path / "s.yuv", to, chroma))  # appending: what is in the file stays
     assert np.array_equal(np.fromfile(tmp_path / "s.yuv", np.uint16), np.concatenate([want, want]))
-    _run(_args(src, tmp_path / "g.yuv", to + ["--gpus", 2, "--devices", "0,0"], chroma))
+    ht.cli_ok(_args(src, tmp_path / "g.yuv", to + ["--gpus", 2, "--devices", "0,0"], chroma))
     assert (tmp_path / "g.yuv").read_bytes() == want.tobytes()
     want4 = _scaled_file(plain, 100, 12, chroma, 10, 0, 0, 4)
-    _run(_args(src, tmp_path / "t.yuv", ["--dst_pic_width", 100, "--dst_pic_height", 12, "--scale", 1, "--scale_taps", 4], chroma))
+    ht.cli_ok(_args(src, tmp_path / "t.yuv", ["--dst_pic_width", 100, "--dst_pic_height", 12, "--scale", 1, "--scale_taps", 4], chroma))
     assert (tmp_path / "t.yuv").read_bytes() == want4.tobytes()
-    out = _run(_args(src, tmp_path / "p.yuv", (), chroma))  # without the flags: the unscaled bytes, no line about scaling
+    out = ht.cli_ok(_args(src, tmp_path / "p.yuv", (), chroma)).stdout  # without the flags: the unscaled bytes, no line about scaling
     assert "scale" not in out and (tmp_path / "p.yuv").read_bytes() == plain.read_bytes()
 
 
@@ -423,9 +380,9 @@ def test_cli_scale_only(tmp_path, ext, chroma, depth, full):
     args = ["--src_filename", src, "--dst_filename", dst, "--scale_only", 1, "--src_pic_width", W, "--src_pic_height", HH,
             "--src_bit_depth", depth, "--src_chroma_format_idc", chroma, "--src_video_full_range_flag", full, "--dst_pic_width", dw,
             "--dst_pic_height", dh, "--scale_taps", a, "--src_start_frame", 1, "--n_frames", N]
-    _run(args)
+    ht.cli_ok(args)
     # a .rgb holds planes R, G, B, each scaled on its own with the G, B, R limits: the order in the file does not matter
     want = np.concatenate([_want(f, W, HH, dw, dh, chroma, depth, full, 1 if ext == "rgb" else 0, a) for f in frames[1:]])
     assert np.array_equal(np.fromfile(dst, np.uint16), want)
-    _run(args + ["--gpus", 2, "--devices", "0,0"])  # appended behind the first run's frames, the same bytes from two threads
+    ht.cli_ok(args + ["--gpus", 2, "--devices", "0,0"])  # appended behind the first run's frames, the same bytes from two threads
     assert np.array_equal(np.fromfile(dst, np.uint16), np.concatenate([want, want]))

@@ -2,12 +2,11 @@
 cases that can be checked by hand, the library's device entries failing loudly without a device, and the command line's --scale and
 --scale_only as --dry_run resolves them, with every refusal, before any device is touched."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import h2y_testing as ht
 import hdr2yuv_amd as h
 import scale_ref as sr
 
@@ -149,29 +148,11 @@ def test_device_entries_fail_loudly_without_a_context():
 
 # ---- the command line ------------------------------------------------------------------------------------------------------
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W, HH = 64, 24
 
 
-def _exe():
-    exe = os.path.join(ROOT, "hdr2yuv_amd", "hdr2yuv")
-    if not os.path.exists(exe):
-        subprocess.run(["make", "-C", os.path.join(ROOT, "hdr2yuv_amd", "cli"), "--no-print-directory"], check=True)
-    return exe
-
-
-def _run(args):
-    r = subprocess.run([_exe()] + [str(a) for a in args], capture_output=True, text=True, timeout=60)
-    return r.returncode, r.stdout
-
-
-def _file(path, nbytes):
-    np.zeros(nbytes, np.uint8).tofile(path)
-    return path
-
-
 def _forward(tmp_path, extra=(), dst="o.yuv", chroma=1, src=None):
-    src = src or _file(tmp_path / "in.f32", 2 * 3 * W * HH * 4)
+    src = src or ht.zero_file(tmp_path / "in.f32", 2 * 3 * W * HH * 4)
     return ["--src_filename", src, "--src_pic_width", W, "--src_pic_height", HH, "--src_bit_depth", 32, "--dst_bit_depth", 10,
             "--dst_chroma_format_idc", chroma, "--dst_matrix_coeffs", 9, "--src_transfer_characteristics", 8,
             "--dst_transfer_characteristics", 16, "--n_frames", 2, "--dry_run", 1] + (["--dst_filename", tmp_path / dst] if dst else []) + \
@@ -180,7 +161,7 @@ def _forward(tmp_path, extra=(), dst="o.yuv", chroma=1, src=None):
 
 def _only(tmp_path, extra=(), ext="yuv", chroma=1, dst=True, depth=10):
     nbytes = 2 * sr.frame_words(W, HH, 3 if ext == "rgb" else chroma) * 2
-    src = _file(tmp_path / f"a.{ext}", nbytes)
+    src = ht.zero_file(tmp_path / f"a.{ext}", nbytes)
     return ["--src_filename", src, "--scale_only", 1, "--src_pic_width", W, "--src_pic_height", HH, "--src_bit_depth", depth,
             "--src_chroma_format_idc", chroma, "--n_frames", 2, "--dry_run", 1] + (["--dst_filename", tmp_path / f"b.{ext}"] if dst else []) + \
         list(extra)
@@ -191,52 +172,52 @@ def _to(w, hh):
 
 
 def test_dry_run_scale(tmp_path):
-    rc, out = _run(_forward(tmp_path, _to(32, 12) + ["--scale", 1]))
-    assert rc == 0, out
-    lines = out.splitlines()
+    r = ht.run_cli(_forward(tmp_path, _to(32, 12) + ["--scale", 1]), timeout=60)
+    assert r.returncode == 0, r.stdout
+    lines = r.stdout.splitlines()
     assert "scale: 64x24 -> 32x12 lanczos3 chroma_format_idc 1 bit_depth 10 video range, planes Y,Cb,Cr, taps h 12 v 12" in lines
     assert f"frame_bytes: {32 * 12 * 3}" in lines and "dst_pic_width: 32" in lines
-    rc, out = _run(_forward(tmp_path, _to(96, 36) + ["--scale", 1, "--scale_taps", 4, "--dst_video_full_range_flag", 1], chroma=3))
-    assert rc == 0, out
-    assert "scale: 64x24 -> 96x36 lanczos4 chroma_format_idc 3 bit_depth 10 full range, planes Y,Cb,Cr, taps h 8 v 8" in out.splitlines()
-    assert f"frame_bytes: {96 * 36 * 6}" in out.splitlines()
-    rc, out = _run(_forward(tmp_path, _to(32, 12) + ["--scale", 1, "--content_light", 1], dst=None))  # beside the light, nothing written
-    assert rc == 0 and "content_light: 1" in out.splitlines() and any(x.startswith("scale: ") for x in out.splitlines())
+    r = ht.run_cli(_forward(tmp_path, _to(96, 36) + ["--scale", 1, "--scale_taps", 4, "--dst_video_full_range_flag", 1], chroma=3), timeout=60)
+    assert r.returncode == 0, r.stdout
+    assert "scale: 64x24 -> 96x36 lanczos4 chroma_format_idc 3 bit_depth 10 full range, planes Y,Cb,Cr, taps h 8 v 8" in r.stdout.splitlines()
+    assert f"frame_bytes: {96 * 36 * 6}" in r.stdout.splitlines()
+    r = ht.run_cli(_forward(tmp_path, _to(32, 12) + ["--scale", 1, "--content_light", 1], dst=None), timeout=60)  # beside the light, nothing written
+    assert r.returncode == 0 and "content_light: 1" in r.stdout.splitlines() and any(x.startswith("scale: ") for x in r.stdout.splitlines())
     assert not (tmp_path / "o.yuv").exists()
 
 
 def test_dry_run_scale_only(tmp_path):
-    rc, out = _run(_only(tmp_path, _to(32, 16)))
-    assert rc == 0, out
-    lines = out.splitlines()
+    r = ht.run_cli(_only(tmp_path, _to(32, 16)), timeout=60)
+    assert r.returncode == 0, r.stdout
+    lines = r.stdout.splitlines()
     assert "scale_only: 1" in lines
     assert "scale: 64x24 -> 32x16 lanczos3 chroma_format_idc 1 bit_depth 10 video range, planes Y,Cb,Cr, taps h 12 v 9" in lines
     assert f"frame_bytes: {32 * 16 * 3}" in lines and "frames: 2" in lines
-    rc, out = _run(_only(tmp_path, _to(128, 24) + ["--scale_taps", 2, "--src_video_full_range_flag", 1], ext="rgb", chroma=3, depth=16))
-    assert rc == 0, out
-    assert "scale: 64x24 -> 128x24 lanczos2 chroma_format_idc 3 bit_depth 16 full range, planes G,B,R, taps h 4 v 3" in out.splitlines()
-    assert f"frame_bytes: {128 * 24 * 6}" in out.splitlines()
+    r = ht.run_cli(_only(tmp_path, _to(128, 24) + ["--scale_taps", 2, "--src_video_full_range_flag", 1], ext="rgb", chroma=3, depth=16), timeout=60)
+    assert r.returncode == 0, r.stdout
+    assert "scale: 64x24 -> 128x24 lanczos2 chroma_format_idc 3 bit_depth 16 full range, planes G,B,R, taps h 4 v 3" in r.stdout.splitlines()
+    assert f"frame_bytes: {128 * 24 * 6}" in r.stdout.splitlines()
 
 
 def test_without_the_flags_nothing_changes(tmp_path):
-    rc, out = _run(_forward(tmp_path))
-    assert rc == 0 and "scale" not in out, out
-    rc, out = _run(_forward(tmp_path, _to(32, 12)))  # a size mismatch without --scale 1: the old message
-    assert rc == 1 and "resizing is not part of convert()" in out
-    rc, out = _run(_forward(tmp_path, _to(32, 12) + ["--scale", 0]))
-    assert rc == 1 and "resizing is not part of convert()" in out
+    r = ht.run_cli(_forward(tmp_path), timeout=60)
+    assert r.returncode == 0 and "scale" not in r.stdout, r.stdout
+    r = ht.run_cli(_forward(tmp_path, _to(32, 12)), timeout=60)  # a size mismatch without --scale 1: the old message
+    assert r.returncode == 1 and "resizing is not part of convert()" in r.stdout
+    r = ht.run_cli(_forward(tmp_path, _to(32, 12) + ["--scale", 0]), timeout=60)
+    assert r.returncode == 1 and "resizing is not part of convert()" in r.stdout
 
 
 def test_help_names_the_flags():
-    rc, out = _run(["--help"])
-    assert rc == 0 and "[--scale 1 [--scale_taps A]]" in out and "[--scale_only 1]" in out
+    r = ht.run_cli(["--help"], timeout=60)
+    assert r.returncode == 0 and "[--scale 1 [--scale_taps A]]" in r.stdout and "[--scale_only 1]" in r.stdout
 
 
 def _refused(args, why):
-    rc, out = _run(args)
-    assert rc == 1, out
-    assert "WARNING:" in out and why in out, out
-    assert "TOO MANY ARGUMENT ERRORS" in out
+    r = ht.run_cli(args, timeout=60)
+    assert r.returncode == 1, r.stdout
+    assert "WARNING:" in r.stdout and why in r.stdout, r.stdout
+    assert "TOO MANY ARGUMENT ERRORS" in r.stdout
 
 
 def test_refused_taps(tmp_path):
@@ -253,8 +234,8 @@ def test_refused_ratio_and_sizes(tmp_path):
     _refused(_only(tmp_path, _to(258, 24)), "each axis ratio must lie within [1/4, 4]")
     _refused(_forward(tmp_path, _to(33, 12) + ["--scale", 1]), "4:2:0 needs even widths and heights")
     _refused(_only(tmp_path, _to(32, 13)), "4:2:0 needs even widths and heights")
-    rc, out = _run(_forward(tmp_path, _to(33, 13) + ["--scale", 1], chroma=3))  # 4:4:4 takes odd sizes
-    assert rc == 0, out
+    r = ht.run_cli(_forward(tmp_path, _to(33, 13) + ["--scale", 1], chroma=3), timeout=60)  # 4:4:4 takes odd sizes
+    assert r.returncode == 0, r.stdout
 
 
 def test_refused_chroma_422(tmp_path):
@@ -263,13 +244,13 @@ def test_refused_chroma_422(tmp_path):
 
 
 def test_refused_beside_the_instruments(tmp_path):
-    ref = _file(tmp_path / "r.yuv", 2 * 32 * 12 * 3)
+    ref = ht.zero_file(tmp_path / "r.yuv", 2 * 32 * 12 * 3)
     why = "--scale 1 is not combined with --ref_filename, --histogram or --ssim"
     _refused(_forward(tmp_path, _to(32, 12) + ["--scale", 1, "--ref_filename", ref]), why)
     _refused(_forward(tmp_path, _to(32, 12) + ["--scale", 1, "--histogram", tmp_path / "h.csv"]), why)
     _refused(_forward(tmp_path, _to(32, 12) + ["--scale", 1, "--ref_filename", ref, "--ssim", 1]), why)
     n = sr.frame_words(W, HH, 1) * 2
-    a, b = _file(tmp_path / "a.yuv", 2 * n), _file(tmp_path / "b.yuv", 2 * n)
+    a, b = ht.zero_file(tmp_path / "a.yuv", 2 * n), ht.zero_file(tmp_path / "b.yuv", 2 * n)
     common = ["--src_filename", a, "--src_pic_width", W, "--src_pic_height", HH, "--src_bit_depth", 10, "--src_chroma_format_idc", 1,
               "--n_frames", 2, "--scale", 1, "--dry_run", 1]
     _refused(common + ["--compare_only", 1, "--ref_filename", b], "--scale 1 scales a conversion: not with --compare_only 1")
@@ -277,7 +258,7 @@ def test_refused_beside_the_instruments(tmp_path):
 
 
 def test_refused_inverse_flow(tmp_path):
-    src = _file(tmp_path / "in.yuv", 2 * sr.frame_words(W, HH, 1) * 2)
+    src = ht.zero_file(tmp_path / "in.yuv", 2 * sr.frame_words(W, HH, 1) * 2)
     for dst in ("o.rgb", "o.tiff"):
         args = ["--src_filename", src, "--dst_filename", tmp_path / dst, "--src_pic_width", W, "--src_pic_height", HH,
                 "--src_bit_depth", 10, "--src_chroma_format_idc", 1, "--dst_bit_depth", 12, "--src_matrix_coeffs", 9, "--dst_matrix_coeffs", 0,
@@ -290,7 +271,7 @@ def test_refused_scale_only(tmp_path):
     _refused(_only(tmp_path, _to(32, 12) + ["--dst_filename", tmp_path / "b.rgb"], dst=False), "must be a .yuv like the source")
     _refused(_only(tmp_path, _to(32, 12) + ["--scale", 1]), "--scale 1 scales a conversion, --scale_only 1 a file: give one of them")
     for ext in ("tiff", "dpx", "exr", "f32", "f16"):
-        src = _file(tmp_path / f"s.{ext}", 64)
+        src = ht.zero_file(tmp_path / f"s.{ext}", 64)
         args = ["--src_filename", src, "--dst_filename", tmp_path / f"d.{ext}", "--scale_only", 1, "--src_pic_width", W, "--src_pic_height", HH,
                 "--src_bit_depth", 16, "--src_chroma_format_idc", 3, "--dry_run", 1] + _to(32, 12)
         _refused(args, f"--scale_only reads .yuv or .rgb; source file ({src}) is a .{ext}")

@@ -1,29 +1,16 @@
 """SSIM on the GPU: k_ssim through h2y_ssim_batch, every compare-armed ring armed for SSIM too, and the command line's --ssim.
 Every expected figure comes from ssim_ref.py: windows and sum_q compared with ==, the doubles bit for bit."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import h2y_testing as ht
 import hdr2yuv_amd as h
 import ssim_ref
 from dpx_files import pack_pixels, write_dpx
 from exr_files import HALF, smooth_half, write_exr
 from tiff_files import write_tiff
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _sizes(w, hh, chroma):
-    nc = (w >> 1) * (hh >> 1) if chroma == 1 else w * hh
-    return [w * hh, nc, nc]
-
-
-def _dev(x):
-    import torch
-
-    return torch.from_numpy(np.ascontiguousarray(x).view(np.int16)).cuda()
 
 
 def _same(st, want, what=""):
@@ -33,13 +20,8 @@ def _same(st, want, what=""):
     assert float(st.all).hex() == want["all"].hex(), what
 
 
-def _noisy(x, depth, rng, amp):
-    m = (1 << depth) - 1
-    return np.clip(x.astype(np.int64) + rng.integers(-amp, amp + 1, x.size), 0, m).astype(np.uint16)
-
-
 def _batch_check(ctx, a, b, w, hh, chroma, depth):
-    st = ctx.ssim_batch(w, hh, chroma, depth, [_dev(x) for x in a], [_dev(x) for x in b])
+    st = ctx.ssim_batch(w, hh, chroma, depth, [ht.dev(x) for x in a], [ht.dev(x) for x in b])
     assert ctx.last_kernel_name() == "k_ssim"
     for k in range(len(a)):
         _same(st[k], ssim_ref.frame(a[k], b[k], w, hh, chroma, depth), k)
@@ -54,12 +36,12 @@ def _batch_check(ctx, a, b, w, hh, chroma, depth):
 @pytest.mark.parametrize("depth", [8, 10, 12, 16])
 def test_batch_sizes_depths(ctx, w, hh, chroma, depth):
     rng = np.random.default_rng(w + hh + 7 * depth + chroma)
-    total = sum(_sizes(w, hh, chroma))
+    total = sum(ht.plane_sizes(w, hh, chroma))
     m = 1 << depth
     a0 = rng.integers(0, m, total, dtype=np.uint16)
     b0 = rng.integers(0, m, total, dtype=np.uint16)  # a random pair
     a1 = rng.integers(0, m, total, dtype=np.uint16)
-    b1 = _noisy(a1, depth, rng, 1 << max(depth - 6, 1))  # a noisy copy
+    b1 = ht.noisy(a1, depth, rng, 1 << max(depth - 6, 1))  # a noisy copy
     _batch_check(ctx, [a0, a1], [b0, b1], w, hh, chroma, depth)
 
 
@@ -67,7 +49,7 @@ def test_batch_sizes_depths(ctx, w, hh, chroma, depth):
 def test_batch_identical_and_constant(ctx):
     rng = np.random.default_rng(5)
     w, hh = 1922, 1082
-    total = sum(_sizes(w, hh, 1))
+    total = sum(ht.plane_sizes(w, hh, 1))
     a = rng.integers(0, 1024, total, dtype=np.uint16)
     c0, c1 = np.full(total, 512, np.uint16), np.full(total, 100, np.uint16)
     st = _batch_check(ctx, [a, c0, c0, a], [a.copy(), c0.copy(), c1, c0], w, hh, 1, 10)
@@ -92,15 +74,15 @@ def test_batch_70_frames_two_launches_shuffled(ctx):
 
     rng = np.random.default_rng(70)
     w, hh = 64, 48
-    total = sum(_sizes(w, hh, 1))
+    total = sum(ht.plane_sizes(w, hh, 1))
     a = [rng.integers(0, 1024, total, dtype=np.uint16) for _ in range(70)]
-    b = [_noisy(x, 10, rng, 20) for x in a]
+    b = [ht.noisy(x, 10, rng, 20) for x in a]
     stride = (total + 7) // 8 * 8  # frames 16-byte aligned within one buffer
     da, db = torch.zeros(70 * stride, dtype=torch.int16, device="cuda"), torch.zeros(70 * stride, dtype=torch.int16, device="cuda")
     order = rng.permutation(70)
     for k in range(70):
-        da[order[k] * stride:order[k] * stride + total] = _dev(a[k])
-        db[order[k] * stride:order[k] * stride + total] = _dev(b[k])
+        da[order[k] * stride:order[k] * stride + total] = ht.dev(a[k])
+        db[order[k] * stride:order[k] * stride + total] = ht.dev(b[k])
     pa = [da.data_ptr() + 2 * int(order[k]) * stride for k in range(70)]
     pb = [db.data_ptr() + 2 * int(order[k]) * stride for k in range(70)]
     st = ctx.ssim_batch(w, hh, 1, 10, pa, pb)
@@ -114,7 +96,7 @@ def test_batch_70_frames_two_launches_shuffled(ctx):
 def test_batch_refusals(ctx):
     import torch
 
-    buf = _dev(np.zeros(3 * 40 * 16 + 8, np.uint16))
+    buf = ht.dev(np.zeros(3 * 40 * 16 + 8, np.uint16))
     with pytest.raises(h.H2YError) as e:  # 2 bytes past a 16-byte boundary
         ctx.ssim_batch(40, 16, 3, 10, [buf.data_ptr() + 2], [buf])
     assert e.value.code == h.api.H2Y_EINVAL
@@ -142,32 +124,8 @@ def _ring(ctx, opener, inputs, refs, keep, ssim=None, arm_compare=True, depth=3)
         ctx.stream_compare(0, keep)
     if ssim is not None:
         ctx.stream_ssim(ssim)
-    got, cs, ss, inflight = [], [], [], 0
-
-    def take():
-        o = ctx.stream_output()
-        got.append(None if o is None else o.copy())
-        cs.append(ctx.stream_compare_result().as_dict())
-        if ssim is not None:
-            ss.append(ctx.stream_ssim_result())
-
-    for k, inp in enumerate(inputs):
-        for dst, src in zip(ctx.stream_input(), inp):
-            if callable(src):
-                src(dst)
-            else:
-                dst[:] = src
-        ctx.stream_reference()[:] = refs[k]
-        ctx.stream_submit()
-        inflight += 1
-        if inflight == depth - 1:
-            take()
-            inflight -= 1
-    while inflight:
-        take()
-        inflight -= 1
-    ctx.stream_close()
-    return got, cs, ss
+    recs = ht.drive_ring(ctx, inputs, depth, refs=refs, results=("compare", "ssim") if ssim is not None else ("compare",))
+    return [r["out"] for r in recs], [r["compare"].as_dict() for r in recs], [r["ssim"] for r in recs if ssim is not None]
 
 
 def _armed(ctx, opener, inputs, w, hh, chroma, depth, planes=lambda o: o.reshape(-1)):
@@ -175,14 +133,14 @@ def _armed(ctx, opener, inputs, w, hh, chroma, depth, planes=lambda o: o.reshape
     and to the restatement on the frames; planes(o) turns an output into the compared planes"""
     rng = np.random.default_rng(w * hh + depth)
     first, _, _ = _ring(ctx, opener, inputs, [0] * len(inputs), 1)
-    refs = [_noisy(planes(o), depth, rng, 3) for o in first]
+    refs = [ht.noisy(planes(o), depth, rng, 3) for o in first]
     outs, cmp_alone, _ = _ring(ctx, opener, inputs, refs, 1)
     for keep in (1, 0):
         got, cs, ss = _ring(ctx, opener, inputs, refs, keep, -1)
         _, cs0, _ = _ring(ctx, opener, inputs, refs, keep)
         assert cs == cmp_alone and cs0 == cmp_alone
         frames = [planes(o) for o in outs]
-        batch = ctx.ssim_batch(w, hh, chroma, depth, [_dev(x) for x in frames], [_dev(r) for r in refs])
+        batch = ctx.ssim_batch(w, hh, chroma, depth, [ht.dev(x) for x in frames], [ht.dev(r) for r in refs])
         for k in range(len(inputs)):
             if keep:
                 assert np.array_equal(got[k], outs[k]), k
@@ -244,7 +202,7 @@ def test_exr_ring(ctx):
 def test_inverse_rings(ctx, tiff, chroma, w, hh):
     """the G, B, R planes before any interleave (padded apart on the device when a plane is not a multiple of 16 bytes)"""
     rng = np.random.default_rng(chroma + w)
-    sizes = _sizes(w, hh, chroma)
+    sizes = ht.plane_sizes(w, hh, chroma)
     frames = [[rng.integers(0, 1024, m).astype(np.uint16) for m in sizes] for _ in range(4)]
     args = (w, hh, chroma, 10, 0, h.MATRIX_BT2020NC, 12, 1)
     if tiff:  # interleaved R, G, B per pixel -> planes G, B, R
@@ -258,9 +216,9 @@ def test_inverse_rings(ctx, tiff, chroma, w, hh):
 @pytest.mark.parametrize("w,hh,chroma,depth", [(35, 19, 1, 12), (64, 32, 3, 16), (37, 16, 1, 8)])
 def test_compare_only_ring(ctx, w, hh, chroma, depth):
     rng = np.random.default_rng(w + depth)
-    sizes = _sizes(w, hh, chroma)
+    sizes = ht.plane_sizes(w, hh, chroma)
     a = [rng.integers(0, 1 << depth, sum(sizes), dtype=np.uint16) for _ in range(5)]
-    b = [_noisy(x, depth, rng, 5) for x in a]
+    b = [ht.noisy(x, depth, rng, 5) for x in a]
     offs = np.cumsum([0] + sizes)
     inputs = [[x[offs[p]:offs[p + 1]] for p in range(3)] for x in a]
     with pytest.raises(h.H2YError):  # the ring does not know the frames' depth
@@ -305,23 +263,6 @@ def test_ring_arming_rules(ctx):
 
 # ---- the command line -------------------------------------------------------------------------------------------------
 
-def _exe():
-    exe = os.path.join(ROOT, "hdr2yuv_amd", "hdr2yuv")
-    if not os.path.exists(exe):
-        subprocess.run(["make", "-C", os.path.join(ROOT, "hdr2yuv_amd", "cli"), "--no-print-directory"], check=True)
-    return exe
-
-
-def _run(args, rc=0):
-    r = subprocess.run([_exe()] + [str(a) for a in args], capture_output=True, text=True, timeout=600)
-    assert r.returncode == rc, r.stdout + r.stderr
-    return r.stdout
-
-
-def _report(out):
-    return [ln for ln in out.splitlines() if ln.startswith("ssim ")]
-
-
 W, HH = 64, 32
 
 
@@ -337,9 +278,9 @@ def _fwd(tmp_path, n):
     rng = np.random.default_rng(9)
     src = tmp_path / "in.yuv"
     rng.integers(0, 65536, 3 * W * HH * n, dtype=np.uint16).tofile(src)
-    _run(_fwd_args(src, n) + ["--dst_filename", tmp_path / "first.yuv"])
+    ht.cli_ok(_fwd_args(src, n) + ["--dst_filename", tmp_path / "first.yuv"])
     out = np.fromfile(tmp_path / "first.yuv", np.uint16).reshape(n, -1)
-    ref = np.stack([_noisy(f, 10, rng, 2 + 3 * k) for k, f in enumerate(out)])
+    ref = np.stack([ht.noisy(f, 10, rng, 2 + 3 * k) for k, f in enumerate(out)])
     ref[2] = out[2]  # one identical frame: inf dB
     ref.tofile(tmp_path / "ref.yuv")
     os.remove(tmp_path / "first.yuv")
@@ -352,13 +293,13 @@ def test_cli_forward_with_and_without_destination(tmp_path):
     src, out, ref = _fwd(tmp_path, n)
     want = ssim_ref.report([ssim_ref.frame(out[k], ref[k], W, HH, 1, 10) for k in range(n)], ["Y", "Cb", "Cr"])
     base = _fwd_args(src, n) + ["--ref_filename", tmp_path / "ref.yuv"]
-    got = _run(base + ["--dst_filename", tmp_path / "o.yuv", "--ssim", 1])
+    got = ht.cli_ok(base + ["--dst_filename", tmp_path / "o.yuv", "--ssim", 1]).stdout
     assert np.array_equal(np.fromfile(tmp_path / "o.yuv", np.uint16).reshape(n, -1), out)
-    assert _report(got) == want, got
+    assert ht.lines_with(got, "ssim ") == want, got
     assert "inf" in want[2] and len(want) == n + 2
-    got2 = _run(base + ["--ssim", 1])
-    assert _report(got2) == want
-    plain = _run(base)  # without --ssim every line is as before
+    got2 = ht.cli_ok(base + ["--ssim", 1]).stdout
+    assert ht.lines_with(got2, "ssim ") == want
+    plain = ht.cli_ok(base).stdout  # without --ssim every line is as before
     assert [ln for ln in got2.splitlines() if not ln.startswith("ssim")] == plain.splitlines()
 
 
@@ -367,8 +308,8 @@ def test_cli_gpus_2_same_output(tmp_path):
     n = 7
     src, _, _ = _fwd(tmp_path, n)
     base = _fwd_args(src, n) + ["--ref_filename", tmp_path / "ref.yuv", "--ssim", 1]
-    one = _report(_run(base))
-    two = _report(_run(base + ["--gpus", 2, "--devices", "0,0"]))
+    one = ht.lines_with(ht.cli_ok(base).stdout, "ssim ")
+    two = ht.lines_with(ht.cli_ok(base + ["--gpus", 2, "--devices", "0,0"]).stdout, "ssim ")
     assert len(one) == n + 2 and one == two
 
 
@@ -377,14 +318,14 @@ def test_cli_gpus_2_same_output(tmp_path):
 def test_cli_compare_only(tmp_path, ext, chroma, depth):
     w, hh, n = 35, 19, 4
     rng = np.random.default_rng(depth + chroma)
-    sizes = _sizes(w, hh, chroma)
+    sizes = ht.plane_sizes(w, hh, chroma)
     a = [rng.integers(0, 1 << depth, sum(sizes), dtype=np.uint16) for _ in range(n + 1)]
-    b = [_noisy(x, depth, rng, 9) for x in a[1:]]
+    b = [ht.noisy(x, depth, rng, 9) for x in a[1:]]
     np.concatenate(a).tofile(tmp_path / f"a.{ext}")
     np.concatenate(b).tofile(tmp_path / f"b.{ext}")
-    out = _run(["--compare_only", 1, "--src_filename", tmp_path / f"a.{ext}", "--ref_filename", tmp_path / f"b.{ext}",
-                "--src_pic_width", w, "--src_pic_height", hh, "--src_bit_depth", depth, "--src_chroma_format_idc", chroma,
-                "--src_start_frame", 1, "--n_frames", n, "--ssim", 1])
+    out = ht.cli_ok(["--compare_only", 1, "--src_filename", tmp_path / f"a.{ext}", "--ref_filename", tmp_path / f"b.{ext}",
+                     "--src_pic_width", w, "--src_pic_height", hh, "--src_bit_depth", depth, "--src_chroma_format_idc", chroma,
+                     "--src_start_frame", 1, "--n_frames", n, "--ssim", 1]).stdout
     pa, pb, names = a[1:], b, ["Y", "Cb", "Cr"]
     if ext == "rgb":  # planes R, G, B in the file; compared as G, B, R
         m = w * hh
@@ -392,23 +333,23 @@ def test_cli_compare_only(tmp_path, ext, chroma, depth):
         pb = [np.concatenate([f[m:2 * m], f[2 * m:], f[:m]]) for f in pb]
         names = ["G", "B", "R"]
     want = ssim_ref.report([ssim_ref.frame(pa[k], pb[k], w, hh, chroma, depth) for k in range(n)], names)
-    assert _report(out) == want, out
+    assert ht.lines_with(out, "ssim ") == want, out
 
 
 @pytest.mark.gpu
 def test_cli_compare_only_beside_histogram(tmp_path):
     w, hh, n = 34, 18, 3
     rng = np.random.default_rng(4)
-    total = sum(_sizes(w, hh, 1))
+    total = sum(ht.plane_sizes(w, hh, 1))
     a = rng.integers(0, 1024, n * total, dtype=np.uint16)
-    b = _noisy(a, 10, rng, 4)
+    b = ht.noisy(a, 10, rng, 4)
     a.tofile(tmp_path / "a.yuv")
     b.tofile(tmp_path / "b.yuv")
     args = ["--compare_only", 1, "--src_filename", tmp_path / "a.yuv", "--ref_filename", tmp_path / "b.yuv", "--src_pic_width", w,
             "--src_pic_height", hh, "--src_bit_depth", 10, "--src_chroma_format_idc", 1, "--n_frames", n, "--histogram", tmp_path / "h.csv"]
-    out = _run(args + ["--ssim", 1])
+    out = ht.cli_ok(args + ["--ssim", 1]).stdout
     want = ssim_ref.report([ssim_ref.frame(a[k * total:(k + 1) * total], b[k * total:(k + 1) * total], w, hh, 1, 10) for k in range(n)],
                            ["Y", "Cb", "Cr"])
-    assert _report(out) == want, out
-    plain = _run(args)
+    assert ht.lines_with(out, "ssim ") == want, out
+    plain = ht.cli_ok(args).stdout
     assert [ln for ln in out.splitlines() if not ln.startswith("ssim")] == plain.splitlines()

@@ -1,13 +1,10 @@
 """SSIM on the host: the numpy restatement (ssim_ref.py) on cases that can be checked by hand, and the command line's --ssim as
 --dry_run resolves it, with every refusal, before any device is touched."""
-import os
-import subprocess
-
 import numpy as np
 
+import h2y_testing as ht
 import ssim_ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W, HH = 16, 16
 YUV420 = (W * HH + 2 * (W // 2) * (HH // 2)) * 2  # bytes of one 4:2:0 frame
 
@@ -68,23 +65,6 @@ def test_frame_weights_and_db():
 
 # ---- the command line ----------------------------------------------------------------------------------------------------
 
-def _exe():
-    exe = os.path.join(ROOT, "hdr2yuv_amd", "hdr2yuv")
-    if not os.path.exists(exe):
-        subprocess.run(["make", "-C", os.path.join(ROOT, "hdr2yuv_amd", "cli"), "--no-print-directory"], check=True)
-    return exe
-
-
-def _run(args):
-    r = subprocess.run([_exe()] + [str(a) for a in args], capture_output=True, text=True, timeout=60)
-    return r.returncode, r.stdout
-
-
-def _file(path, nbytes):
-    np.zeros(nbytes, np.uint8).tofile(path)
-    return path
-
-
 def _compare_only(src, ref, w=W, hh=HH, chroma=1):
     return ["--compare_only", 1, "--src_filename", src, "--ref_filename", ref, "--src_pic_width", w, "--src_pic_height", hh,
             "--src_bit_depth", 10, "--src_chroma_format_idc", chroma, "--n_frames", 2, "--dry_run", 1]
@@ -96,60 +76,60 @@ def _forward(src, n=2):
 
 
 def test_dry_run_compare_only(tmp_path):
-    src, ref = _file(tmp_path / "a.yuv", 2 * YUV420), _file(tmp_path / "b.yuv", 2 * YUV420)
-    rc, out = _run(_compare_only(src, ref) + ["--ssim", 1])
-    assert rc == 0, out
-    assert "ssim: 1" in out.splitlines()
-    rc, out0 = _run(_compare_only(src, ref))
-    assert rc == 0 and "ssim" not in out0  # without --ssim nothing changes
-    assert [x for x in out.splitlines() if x != "ssim: 1"] == out0.splitlines()
+    src, ref = ht.zero_file(tmp_path / "a.yuv", 2 * YUV420), ht.zero_file(tmp_path / "b.yuv", 2 * YUV420)
+    r = ht.run_cli(_compare_only(src, ref) + ["--ssim", 1], timeout=60)
+    assert r.returncode == 0, r.stdout
+    assert "ssim: 1" in r.stdout.splitlines()
+    r0 = ht.run_cli(_compare_only(src, ref), timeout=60)
+    assert r0.returncode == 0 and "ssim" not in r0.stdout  # without --ssim nothing changes
+    assert [x for x in r.stdout.splitlines() if x != "ssim: 1"] == r0.stdout.splitlines()
 
 
 def test_dry_run_forward_with_and_without_destination(tmp_path):
-    src = _file(tmp_path / "in.rgb", 2 * 3 * W * HH * 2)
-    ref = _file(tmp_path / "r.yuv", 2 * YUV420)
+    src = ht.zero_file(tmp_path / "in.rgb", 2 * 3 * W * HH * 2)
+    ref = ht.zero_file(tmp_path / "r.yuv", 2 * YUV420)
     for extra in ([], ["--dst_filename", tmp_path / "out.yuv"]):
-        rc, out = _run(_forward(src) + ["--ref_filename", ref, "--ssim", 1] + extra)
-        assert rc == 0, out
-        assert "ssim: 1" in out.splitlines()
+        r = ht.run_cli(_forward(src) + ["--ref_filename", ref, "--ssim", 1] + extra, timeout=60)
+        assert r.returncode == 0, r.stdout
+        assert "ssim: 1" in r.stdout.splitlines()
 
 
 def test_dry_run_beside_histogram(tmp_path):
-    src, ref = _file(tmp_path / "a.yuv", 2 * YUV420), _file(tmp_path / "b.yuv", 2 * YUV420)
-    rc, out = _run(_compare_only(src, ref) + ["--ssim", 1, "--histogram", tmp_path / "h.csv"])
-    assert rc == 0, out
-    assert "ssim: 1" in out.splitlines() and any(x.startswith("histogram:") for x in out.splitlines())
+    src, ref = ht.zero_file(tmp_path / "a.yuv", 2 * YUV420), ht.zero_file(tmp_path / "b.yuv", 2 * YUV420)
+    r = ht.run_cli(_compare_only(src, ref) + ["--ssim", 1, "--histogram", tmp_path / "h.csv"], timeout=60)
+    assert r.returncode == 0, r.stdout
+    assert "ssim: 1" in r.stdout.splitlines() and any(x.startswith("histogram:") for x in r.stdout.splitlines())
 
 
 def test_refused_without_reference(tmp_path):
-    src = _file(tmp_path / "in.rgb", 2 * 3 * W * HH * 2)
-    rc, out = _run(_forward(src) + ["--dst_filename", tmp_path / "out.yuv", "--ssim", 1])
-    assert rc == 1 and "WARNING: --ssim 1 needs a comparison" in out, out
-    rc, out = _run(["--histogram_only", 1, "--src_filename", _file(tmp_path / "a.yuv", YUV420), "--src_pic_width", W,
-                    "--src_pic_height", HH, "--src_bit_depth", 10, "--src_chroma_format_idc", 1, "--ssim", 1, "--dry_run", 1])
-    assert rc == 1 and "WARNING: --ssim 1 needs a comparison" in out, out
+    src = ht.zero_file(tmp_path / "in.rgb", 2 * 3 * W * HH * 2)
+    r = ht.run_cli(_forward(src) + ["--dst_filename", tmp_path / "out.yuv", "--ssim", 1], timeout=60)
+    assert r.returncode == 1 and "WARNING: --ssim 1 needs a comparison" in r.stdout, r.stdout
+    r = ht.run_cli(["--histogram_only", 1, "--src_filename", ht.zero_file(tmp_path / "a.yuv", YUV420), "--src_pic_width", W,
+                          "--src_pic_height", HH, "--src_bit_depth", 10, "--src_chroma_format_idc", 1, "--ssim", 1, "--dry_run", 1], timeout=60)
+    assert r.returncode == 1 and "WARNING: --ssim 1 needs a comparison" in r.stdout, r.stdout
 
 
 def test_refused_under_8x8(tmp_path):
     for w, hh, chroma in ((15, 16, 1), (16, 15, 1), (7, 40, 3), (40, 7, 3)):
         nbytes = (w * hh + 2 * ((w >> 1) * (hh >> 1) if chroma == 1 else w * hh)) * 2
-        src, ref = _file(tmp_path / "a.yuv", 2 * nbytes), _file(tmp_path / "b.yuv", 2 * nbytes)
-        rc, out = _run(_compare_only(src, ref, w, hh, chroma) + ["--ssim", 1])
-        assert rc == 1 and "at least 8x8" in out, (w, hh, chroma, out)
+        src, ref = ht.zero_file(tmp_path / "a.yuv", 2 * nbytes), ht.zero_file(tmp_path / "b.yuv", 2 * nbytes)
+        r = ht.run_cli(_compare_only(src, ref, w, hh, chroma) + ["--ssim", 1], timeout=60)
+        assert r.returncode == 1 and "at least 8x8" in r.stdout, (w, hh, chroma, r.stdout)
     nbytes = (8 * 8 * 3) * 2  # 8x8 4:4:4 is the smallest frame with a window
-    src, ref = _file(tmp_path / "a.yuv", 2 * nbytes), _file(tmp_path / "b.yuv", 2 * nbytes)
-    rc, out = _run(_compare_only(src, ref, 8, 8, 3) + ["--ssim", 1])
-    assert rc == 0, out
+    src, ref = ht.zero_file(tmp_path / "a.yuv", 2 * nbytes), ht.zero_file(tmp_path / "b.yuv", 2 * nbytes)
+    r = ht.run_cli(_compare_only(src, ref, 8, 8, 3) + ["--ssim", 1], timeout=60)
+    assert r.returncode == 0, r.stdout
 
 
 def test_refused_ssim_2(tmp_path):
-    src, ref = _file(tmp_path / "a.yuv", 2 * YUV420), _file(tmp_path / "b.yuv", 2 * YUV420)
-    rc, out = _run(_compare_only(src, ref) + ["--ssim", 2])
-    assert rc == 1 and "WARNING: ssim(2) not 0 or 1" in out, out
+    src, ref = ht.zero_file(tmp_path / "a.yuv", 2 * YUV420), ht.zero_file(tmp_path / "b.yuv", 2 * YUV420)
+    r = ht.run_cli(_compare_only(src, ref) + ["--ssim", 2], timeout=60)
+    assert r.returncode == 1 and "WARNING: ssim(2) not 0 or 1" in r.stdout, r.stdout
 
 
 def test_refused_422_compare_only(tmp_path):
     nbytes = (W * HH + 2 * (W // 2) * HH) * 2
-    src, ref = _file(tmp_path / "a.yuv", 2 * nbytes), _file(tmp_path / "b.yuv", 2 * nbytes)
-    rc, out = _run(_compare_only(src, ref, chroma=2) + ["--ssim", 1])
-    assert rc == 1 and "WARNING: --ssim 1 compares 4:2:0 or 4:4:4 frames, not chroma_format_idc 2" in out, out
+    src, ref = ht.zero_file(tmp_path / "a.yuv", 2 * nbytes), ht.zero_file(tmp_path / "b.yuv", 2 * nbytes)
+    r = ht.run_cli(_compare_only(src, ref, chroma=2) + ["--ssim", 1], timeout=60)
+    assert r.returncode == 1 and "WARNING: --ssim 1 compares 4:2:0 or 4:4:4 frames, not chroma_format_idc 2" in r.stdout, r.stdout

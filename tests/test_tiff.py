@@ -3,18 +3,16 @@ through h2y_rgb_interleave_batch and the TIFF inverse ring, and the command line
 with tests/tiff_files.read_tiff, a numpy restatement of read_tiff() (tiff.cpp:54-362); the .yuv bytes are oracle.convert_frame's
 on the restated planes, the .tiff bytes h2y_tiff_layout's head and tail around the interleaved oracle.matrix_inverse planes (and
 libtiff's own file for those samples where libtiff loads)."""
-import os
-import subprocess
 import warnings
 
 import numpy as np
 import pytest
 
+import h2y_testing as ht
 import hdr2yuv_amd as h
 from oracle import binding as ob
 from tiff_files import CUTOUT_HD, CUTOUT_QHD, LIBTIFF, interleave, libtiff_write, read_tiff, write_tiff
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GUARD = 0x7E57
 
 
@@ -41,19 +39,6 @@ def _decode(ctx, datas, clamp, cutout=0):
     ctx.tiff_decode_batch(info, clamp, pays, outs)
     assert ctx.last_kernel_name() == "k_tiff_decode"
     return [[p.cpu().numpy().view(np.uint16) for p in fr] for fr in outs]
-
-
-def _exe():
-    exe = os.path.join(ROOT, "hdr2yuv_amd", "hdr2yuv")
-    if not os.path.exists(exe):
-        subprocess.run(["make", "-C", os.path.join(ROOT, "hdr2yuv_amd", "cli"), "--no-print-directory"], check=True)
-    return exe
-
-
-def _run(args):
-    r = subprocess.run([_exe()] + [str(a) for a in args], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return r
 
 
 # ---- every code, both byte orders, with and without the clamp ----------------------------------------------------------
@@ -188,27 +173,20 @@ E2E = [  # (dst depth, dst matrix, chroma, resampler, full range)
 def _descs(w, hh, depth, mat, chroma, res, full):
     kw = dict(sample=h.SAMPLE_U16, src_depth=16, dst_depth=depth, src_transfer=1, dst_transfer=1, src_primaries=1, dst_primaries=1,
               dst_matrix=mat, chroma=chroma, resampler=res, full_range=full)
-    return h.make_desc(w, hh, **kw), ob.make_desc(w, hh, **kw)
+    return ht.descs(w, hh, **kw)
 
 
 def _ring(ctx, d, info, clamp, datas, depth=3):
     ctx.tiff_stream_open(d, info, clamp, depth)
-    got, inflight = [], 0
-    for data in datas:
-        i, rows = _parse(data)
-        (slot,) = ctx.stream_input()
-        assert slot.dtype == np.uint8 and slot.size == info.payload_bytes
-        slot[:] = _payload(data, i, rows)
-        ctx.stream_submit()
-        inflight += 1
-        if inflight == depth - 1:
-            got.append(ctx.stream_output().copy())
-            inflight -= 1
-    while inflight:
-        got.append(ctx.stream_output().copy())
-        inflight -= 1
-    ctx.stream_close()
-    return got
+
+    def fill(data):
+        def into(slots):
+            (slot,) = slots
+            assert slot.dtype == np.uint8 and slot.size == info.payload_bytes
+            slot[:] = _payload(data, *_parse(data))
+        return into
+
+    return [r["out"] for r in ht.drive_ring(ctx, [fill(x) for x in datas], depth)]
 
 
 @pytest.mark.gpu
@@ -269,11 +247,11 @@ def test_cli_test_sh_tiff_to_yuv(tmp_path, oracle):
     rng = np.random.default_rng(715)
     rgb = rng.integers(0, 65536, (1080, 1920, 3), dtype=np.uint16)
     (tmp_path / "b.tiff").write_bytes(write_tiff(rgb))
-    _run(_tiff_line(tmp_path / "b.tiff", tmp_path / "b.yuv", 1920, 1080))
+    ht.cli_ok(_tiff_line(tmp_path / "b.tiff", tmp_path / "b.yuv", 1920, 1080))
     assert (tmp_path / "b.yuv").read_bytes() == _tiff_line_want(oracle, rgb)
     uhd = rng.integers(0, 65536, (2160, 3840, 3), dtype=np.uint16)
     (tmp_path / "u.tiff").write_bytes(write_tiff(uhd))
-    _run(_tiff_line(tmp_path / "u.tiff", tmp_path / "u.yuv", 1920, 1080, "--cutout_hd", 1))
+    ht.cli_ok(_tiff_line(tmp_path / "u.tiff", tmp_path / "u.yuv", 1920, 1080, "--cutout_hd", 1))
     assert (tmp_path / "u.yuv").read_bytes() == _tiff_line_want(oracle, uhd, CUTOUT_HD)
 
 
@@ -282,7 +260,7 @@ def test_cli_scattered_strips(tmp_path, oracle):
     """RowsPerStrip 3, strips in descending order with gaps, big-endian: one read per row into the slot"""
     rgb = np.random.default_rng(3).integers(0, 65536, (20, 72, 3), dtype=np.uint16)
     (tmp_path / "s.tiff").write_bytes(write_tiff(rgb, rps=3, order="descending", gap=10, big_endian=True))
-    r = _run(_tiff_line(tmp_path / "s.tiff", tmp_path / "s.yuv", 72, 20))
+    r = ht.cli_ok(_tiff_line(tmp_path / "s.tiff", tmp_path / "s.yuv", 72, 20))
     assert "rows scattered" in r.stdout and "big-endian" in r.stdout
     assert (tmp_path / "s.yuv").read_bytes() == _tiff_line_want(oracle, rgb)
 
@@ -314,7 +292,7 @@ def test_cli_test_sh_yuv_to_tiff(tmp_path, oracle):
     (tmp_path / "t.yuv").write_bytes(b"".join(p.tobytes() for p in planes))
     dst = tmp_path / "t.tiff"
     dst.write_bytes(b"\x07" * (60 << 20))  # longer than the frame: "w" truncates
-    _run(_yuv_line(tmp_path / "t.yuv", dst, w, hh))
+    ht.cli_ok(_yuv_line(tmp_path / "t.yuv", dst, w, hh))
     want, rgb = _tiff_want(oracle, planes, w, hh)
     got = dst.read_bytes()
     assert got == want
@@ -333,19 +311,7 @@ def test_tiff_inverse_ring(ctx, oracle):
         nc = (w // 2) * (hh // 2) if chroma == 1 else w * hh
         frames = [[rng.integers(0, 1024, m).astype(np.uint16) for m in (w * hh, nc, nc)] for _ in range(4)]
         ctx.tiff_inverse_stream_open(w, hh, chroma, 10, 0, h.MATRIX_BT2020NC, 16, 1)
-        got, inflight = [], 0
-        for fr in frames:
-            for dst, src in zip(ctx.stream_input(), fr):
-                dst[:] = src
-            ctx.stream_submit()
-            inflight += 1
-            if inflight == 2:
-                got.append(ctx.stream_output().copy())
-                inflight -= 1
-        while inflight:
-            got.append(ctx.stream_output().copy())
-            inflight -= 1
-        ctx.stream_close()
+        got = [r["out"] for r in ht.drive_ring(ctx, frames, 3)]
         for k, fr in enumerate(frames):
             pl = fr
             if chroma == 1:
@@ -367,13 +333,13 @@ def test_cli_tiff_sequences(tmp_path, oracle):
     for name, extra in (("one.yuv", []), ("two.yuv", ["--gpus", 2, "--devices", "0,0"])):
         dst = tmp_path / name
         dst.write_bytes(b"\x07" * 10)
-        r = _run(_tiff_line(tmp_path / "shot.%03d.tiff", dst, w, hh, "--src_start_frame", 2, "--n_frames", 3, *extra))
+        r = ht.cli_ok(_tiff_line(tmp_path / "shot.%03d.tiff", dst, w, hh, "--src_start_frame", 2, "--n_frames", 3, *extra))
         assert "frames: 3" in r.stdout
         assert dst.read_bytes() == want, name
     yuv = [_yuv_frame(rng, w, hh) for _ in range(5)]
     (tmp_path / "in.yuv").write_bytes(b"".join(p.tobytes() for fr in yuv for p in fr))
-    _run(_yuv_line(tmp_path / "in.yuv", tmp_path / "out.%04d.tiff", w, hh, "--src_start_frame", 1, "--n_frames", 3,
-                   "--gpus", 2, "--devices", "0,0"))
+    ht.cli_ok(_yuv_line(tmp_path / "in.yuv", tmp_path / "out.%04d.tiff", w, hh, "--src_start_frame", 1, "--n_frames", 3,
+                        "--gpus", 2, "--devices", "0,0"))
     for k in (1, 2, 3):
         assert (tmp_path / f"out.{k:04d}.tiff").read_bytes() == _tiff_want(oracle, yuv[k], w, hh)[0], k
     assert not (tmp_path / "out.0000.tiff").exists() and not (tmp_path / "out.0004.tiff").exists()

@@ -1,17 +1,14 @@
 """TIFF on the host: h2y_tiff_parse (through hdr2yuv_amd.parse_tiff) against the restatement of read_tiff()'s geometry
 (tests/tiff_files.py), its refusals, h2y_tiff_layout against the file libtiff itself writes for write_tiff()'s call sequence,
 and the command line's .tiff resolution.  No GPU: --dry_run stops before any device is touched."""
-import os
-import subprocess
 import warnings
 
 import numpy as np
 import pytest
 
+import h2y_testing as ht
 import hdr2yuv_amd as h
 from tiff_files import CUTOUT_HD, CUTOUT_QHD, LIBTIFF, geometry, libtiff_write, write_tiff
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _samples(w, hh, seed=0):
@@ -168,20 +165,6 @@ def test_tiff_entries_refuse_null_context():
 
 # ---- the command line ---------------------------------------------------------------------------------------------------
 
-def _cli(args, dry=True):
-    exe = os.path.join(ROOT, "hdr2yuv_amd", "hdr2yuv")
-    if not os.path.exists(exe):
-        subprocess.run(["make", "-C", os.path.join(ROOT, "hdr2yuv_amd", "cli"), "--no-print-directory"], check=True)
-    r = subprocess.run([exe] + [str(a) for a in args] + (["--dry_run", "1"] if dry else []), capture_output=True, text=True,
-                       timeout=120)
-    kv = {}
-    for ln in r.stdout.splitlines():
-        if ": " in ln and not ln.startswith(("WARNING", "ERROR")):
-            k, v = ln.split(": ", 1)
-            kv[k] = v
-    return r, kv
-
-
 def test_sh_tiff_line(src, dst, w=1920, hh=1080):
     """test.sh:7-15, flag for flag"""
     return ["--src_matrix_coeffs", 0, "--dst_matrix_coeffs", 1, "--src_transfer_characteristics", 1, "--dst_transfer_characteristics", 1,
@@ -197,7 +180,8 @@ def test_cli_tiff_resolves_like_read_tiff(tmp_path):
     """the test.sh:7-15 line on a .tiff: 16-bit (with read_tiff's warning: the line says 12), GBR, 4:4:4, video range"""
     src = tmp_path / "balloon.tiff"
     src.write_bytes(write_tiff(_samples(1920, 1080)))
-    r, kv = _cli(test_sh_tiff_line(src, tmp_path / "o.yuv"))
+    r = ht.run_cli(test_sh_tiff_line(src, tmp_path / "o.yuv"), timeout=120, dry=True)
+    kv = ht.banner(r.stdout)
     assert r.returncode == 0, r.stdout
     assert "bit_depth(12) != 16-bit precision assumed for tiff input samples" in r.stdout
     assert kv["src_picture"] == "matrix_coeffs 0 chroma_format_idc 3 bit_depth 16 video_full_range_flag 0"
@@ -205,17 +189,19 @@ def test_cli_tiff_resolves_like_read_tiff(tmp_path):
     assert kv["frames"] == "1" and kv["dst_bit_depth"] == "10"
     assert "tiff.cpp" not in r.stdout and "not recongized" not in r.stdout
     # .tif is not one of the reference's input types
-    r, kv = _cli(test_sh_tiff_line(tmp_path / "balloon.tif", tmp_path / "o.yuv"))
+    r = ht.run_cli(test_sh_tiff_line(tmp_path / "balloon.tif", tmp_path / "o.yuv"), timeout=120, dry=True)
     assert r.returncode != 0 and "not recongized or not supported" in r.stdout
 
 
 def test_cli_tiff_cutouts(tmp_path):
     src = tmp_path / "uhd.tiff"
     src.write_bytes(write_tiff(_samples(3840, 2160)))
-    r, kv = _cli(test_sh_tiff_line(src, tmp_path / "o.yuv") + ["--cutout_hd", 1])
+    r = ht.run_cli(test_sh_tiff_line(src, tmp_path / "o.yuv") + ["--cutout_hd", 1], timeout=120, dry=True)
+    kv = ht.banner(r.stdout)
     assert r.returncode == 0, r.stdout
     assert kv["tiff"].endswith("decoded 1920x1080 from (960, 540), rows contiguous")
-    r, kv = _cli(test_sh_tiff_line(src, tmp_path / "o.yuv", 960, 540) + ["--cutout_hd", 1, "--cutout_qhd", 1])
+    r = ht.run_cli(test_sh_tiff_line(src, tmp_path / "o.yuv", 960, 540) + ["--cutout_hd", 1, "--cutout_qhd", 1], timeout=120, dry=True)
+    kv = ht.banner(r.stdout)
     assert r.returncode == 0, r.stdout
     assert kv["tiff"].endswith("decoded 960x540 from (1440, 810), rows contiguous")
 
@@ -223,28 +209,29 @@ def test_cli_tiff_cutouts(tmp_path):
 def test_cli_tiff_refusals(tmp_path):
     odd = tmp_path / "odd.tiff"
     odd.write_bytes(write_tiff(_samples(3841, 4)))
-    r, kv = _cli(test_sh_tiff_line(odd, tmp_path / "o.yuv", 3840, 4))
+    r = ht.run_cli(test_sh_tiff_line(odd, tmp_path / "o.yuv", 3840, 4), timeout=120, dry=True)
     assert r.returncode != 0 and "inside a pixel" in r.stdout
     src = tmp_path / "a.tiff"
     src.write_bytes(write_tiff(_samples(64, 8)))
-    r, kv = _cli(test_sh_tiff_line(src, tmp_path / "o.yuv", 66, 8))
+    r = ht.run_cli(test_sh_tiff_line(src, tmp_path / "o.yuv", 66, 8), timeout=120, dry=True)
     assert r.returncode != 0 and "resizing is not part of convert()" in r.stdout
     # .tiff output from anything but .yuv input
     rgb = tmp_path / "a.rgb"
     rgb.write_bytes(b"\0" * 64 * 8 * 6)
-    r, kv = _cli(["--src_filename", rgb, "--dst_filename", tmp_path / "o.tiff", "--src_pic_width", 64, "--src_pic_height", 8,
-                  "--src_bit_depth", 12, "--src_chroma_format_idc", 3, "--dst_matrix_coeffs", 0])
+    r = ht.run_cli(["--src_filename", rgb, "--dst_filename", tmp_path / "o.tiff", "--src_pic_width", 64, "--src_pic_height", 8,
+                    "--src_bit_depth", 12, "--src_chroma_format_idc", 3, "--dst_matrix_coeffs", 0], timeout=120, dry=True)
     assert r.returncode != 0 and ".tiff output is the .yuv -> RGB flow's" in r.stdout
     # several frames into one .tiff
     yuv = tmp_path / "a.yuv"
     yuv.write_bytes(b"\0" * 64 * 8 * 6 * 3)
     inv = ["--src_filename", yuv, "--src_pic_width", 64, "--src_pic_height", 8, "--src_bit_depth", 12, "--dst_bit_depth", 16,
            "--src_chroma_format_idc", 3, "--dst_chroma_format_idc", 3, "--src_matrix_coeffs", 1, "--dst_matrix_coeffs", 0]
-    r, kv = _cli(inv + ["--dst_filename", tmp_path / "o.tiff", "--n_frames", 3])
+    r = ht.run_cli(inv + ["--dst_filename", tmp_path / "o.tiff", "--n_frames", 3], timeout=120, dry=True)
     assert r.returncode != 0 and "frames into one .tiff" in r.stdout
-    r, kv = _cli(inv + ["--dst_filename", tmp_path / "o.%03d.tiff", "--n_frames", 3])
+    r = ht.run_cli(inv + ["--dst_filename", tmp_path / "o.%03d.tiff", "--n_frames", 3], timeout=120, dry=True)
+    kv = ht.banner(r.stdout)
     assert r.returncode == 0 and kv["frames"] == "3", r.stdout
     assert kv["tiff_file_bytes"] == str(len(b"".join(h.tiff_layout(64, 8))) + 64 * 8 * 6)
     # .exr input keeps its message
-    r, kv = _cli(test_sh_tiff_line(tmp_path / "a.exr", tmp_path / "o.yuv"))
+    r = ht.run_cli(test_sh_tiff_line(tmp_path / "a.exr", tmp_path / "o.yuv"), timeout=120, dry=True)
     assert r.returncode != 0 and "exr.cpp" in r.stdout

@@ -23,9 +23,9 @@ import numpy as np
 import pytest
 
 import hdr2yuv_amd as h
-from oracle import binding as ob
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import h2y_testing as ht  # noqa: E402
 import sweep_values as sv  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -39,18 +39,10 @@ def pool():
         yield p
 
 
-def _descs(kw, w, hh):
-    return h.make_desc(w, hh, **kw), ob.make_desc(w, hh, **kw)
-
-
-def _upload(planes):
-    import torch
-
-    view = np.int32 if planes[0].dtype == np.uint32 else np.int16
+def _planes_dev(planes):
     if planes[0] is planes[1] is planes[2]:  # grey: one device buffer, passed three times
-        t = torch.from_numpy(planes[0].view(view)).cuda()
-        return [t, t, t]
-    return [torch.from_numpy(p.view(view)).cuda() for p in planes]
+        return [ht.dev(planes[0])] * 3
+    return [ht.dev(p) for p in planes]
 
 
 def _probe(kw, options, name, sample_f32=True):
@@ -59,7 +51,7 @@ def _probe(kw, options, name, sample_f32=True):
     import torch
 
     w, hh = 256, 64
-    d, _ = _descs(kw, w, hh)
+    d, _ = ht.descs(w, hh, **kw)
     rng = np.random.default_rng(5)
     planes = [rng.uniform(0.0, 1.0, w * hh).astype(np.float32).view(np.uint32) for _ in range(3)]
     c = h.Context(0)
@@ -67,7 +59,7 @@ def _probe(kw, options, name, sample_f32=True):
         for k, v in options.items():
             c.set_option(k, v)
         out = [torch.zeros(h.frame_bytes(d) // 2, dtype=torch.int16, device="cuda")]
-        dev = [_upload(planes)]
+        dev = [_planes_dev(planes)]
         torch.cuda.synchronize()
         c.convert_batch(d, dev, out)
         return c.last_kernel_name() == name
@@ -92,7 +84,7 @@ def run_sweep(oracle, pool, tag, sweep, kw, forms, conditions=True, codes=True, 
     import torch
 
     f32 = sweep.values.dtype == np.uint32
-    d, od = _descs(kw, sweep.width, sweep.height)
+    d, od = ht.descs(sweep.width, sweep.height, **kw)
     c420 = d.dst_chroma_format_idc == h.CHROMA_420
     cond = sv.Conditions(sweep, d.dst_bit_depth, d.dst_full_range, d.dst_matrix, c420, codes=codes, label=tag, max_low=max_low) if conditions else None
     ctxs = []
@@ -115,7 +107,7 @@ def run_sweep(oracle, pool, tag, sweep, kw, forms, conditions=True, codes=True, 
             ks = list(range(k0, min(k0 + batch, sweep.n_frames)))
             host = [sweep.planes(k) for k in ks]
             futures = [pool.submit(one, planes) for planes in host]  # the oracle works while the GPU does
-            dev_in = [_upload(planes) for planes in host]
+            dev_in = [_planes_dev(planes) for planes in host]
             got = []
             for i, (options, name, parts) in enumerate(forms):
                 for rnd in range(rounds):
@@ -268,7 +260,7 @@ def test_cast_undefined_halves_saturate(ctx, name):
     values = sv.all_halves()[sv.cast_undefined_halves()]
     sweep = sv.Sweep(values, "grey", 64, 8)
     assert values.size == 260 and sweep.n_frames == 1
-    d, _ = _descs(dict(H_DESCS[name], sample=h.SAMPLE_F16, stats=sv.IDENT, src_transfer=16, dst_transfer=8), 64, 8)
+    d, _ = ht.descs(64, 8, **dict(H_DESCS[name], sample=h.SAMPLE_F16, stats=sv.IDENT, src_transfer=16, dst_transfer=8))
     got = ctx.convert_frame(d, sweep.planes(0))
     top = sv.luma_limits(d.dst_bit_depth, d.dst_full_range)[1]
     assert np.all(got[:64 * 8] == top), (name, top, np.unique(got[:64 * 8]).tolist())
@@ -360,13 +352,13 @@ def test_guard_edge_pixels(oracle, name, mode, t1):
     shape, options = GUARD_MODES[mode]
     kw = dict(GUARD_CONFIGS[name], stats=sv.IDENT, **shape)
     planes, w, hh, at = guard_frame(pixels, 99)
-    d, od = _descs(kw, w, hh)
+    d, od = ht.descs(w, hh, **kw)
     c = h.Context(0)
     try:
         for k, v in dict(options, t1=t1).items():
             c.set_option(k, v)
         out = [torch.zeros(h.frame_bytes(d) // 2, dtype=torch.int16, device="cuda")]
-        dev = [_upload(planes)]
+        dev = [_planes_dev(planes)]
         torch.cuda.synchronize()
         c.convert_batch(d, dev, out)
         variant = c.last_kernel_variant()

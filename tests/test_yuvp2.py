@@ -3,11 +3,11 @@ the batch -- h2y_convert_frame, h2y_convert_batch, the pinned ring and the comma
 (md5) with the reference's, recorded in tests/golden/ref_answers_yuvp2.npz from its own object code (and rerun against that
 code where oracle/_ref is present); a mismatch is reported sample by sample against the numpy restatement (yuvp2_files)."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import h2y_testing as ht
 import hdr2yuv_amd as h
 import yuvp2_files as yf
 from oracle import binding as ob
@@ -82,20 +82,7 @@ def test_ring(oracle, yref):
     c = h.Context(0)
     try:
         c.stream_open(_hd(d), 3)
-        got, inflight = [], 0
-        for fr in frames:
-            dst = c.stream_input()
-            for k in range(3):
-                dst[k][:] = fr[k]
-            c.stream_submit()
-            inflight += 1
-            if inflight == 2:
-                got.append(c.stream_output().copy())
-                inflight -= 1
-        while inflight:
-            got.append(c.stream_output().copy())
-            inflight -= 1
-        c.stream_close()
+        got = [r["out"] for r in ht.drive_ring(c, frames, 3)]
     finally:
         c.close()
     assert len(got) == len(frames)
@@ -110,28 +97,15 @@ def test_uhd_frame(ctx, oracle, yref, res):
     _expect(oracle, yref, d, planes, got, "3840x2160")
 
 
-def _exe():
-    exe = os.path.join(ROOT, "hdr2yuv_amd", "hdr2yuv")
-    if not os.path.exists(exe):
-        subprocess.run(["make", "-C", os.path.join(ROOT, "hdr2yuv_amd", "cli"), "--no-print-directory"], check=True)
-    return exe
-
-
-def _run(args):
-    r = subprocess.run([_exe()] + [str(a) for a in args], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return r
-
-
 def test_cli_yuv_444_to_420(tmp_path, oracle, yref):
     d, frames = yf.cli_yuv_case()
     src, dst = tmp_path / "yzx.yuv", tmp_path / "out.yuv"
     src.write_bytes(b"".join(np.concatenate(fr).astype("<u2").tobytes() for fr in frames))
-    _run(["--src_filename", src, "--dst_filename", dst, "--src_pic_width", d.width, "--src_pic_height", d.height,
-          "--src_bit_depth", 16, "--dst_bit_depth", 10, "--src_chroma_format_idc", 3, "--dst_chroma_format_idc", 1,
-          "--src_matrix_coeffs", 15, "--dst_matrix_coeffs", 15, "--src_colour_primaries", 1, "--dst_colour_primaries", 1,
-          "--src_transfer_characteristics", 1, "--dst_transfer_characteristics", 1, "--chroma_resampler_type", 1,
-          "--dst_video_full_range_flag", 0, "--n_frames", 2])
+    ht.cli_ok(["--src_filename", src, "--dst_filename", dst, "--src_pic_width", d.width, "--src_pic_height", d.height,
+               "--src_bit_depth", 16, "--dst_bit_depth", 10, "--src_chroma_format_idc", 3, "--dst_chroma_format_idc", 1,
+               "--src_matrix_coeffs", 15, "--dst_matrix_coeffs", 15, "--src_colour_primaries", 1, "--dst_colour_primaries", 1,
+               "--src_transfer_characteristics", 1, "--dst_transfer_characteristics", 1, "--chroma_resampler_type", 1,
+               "--dst_video_full_range_flag", 0, "--n_frames", 2])
     out = np.frombuffer(dst.read_bytes(), "<u2")
     fb = h.frame_bytes(_hd(d)) // 2
     assert out.size == 2 * fb
@@ -144,10 +118,10 @@ def test_cli_tiff_to_420(tmp_path, oracle, yref):
     d = yf.cli_tiff_desc()
     src, dst = tmp_path / "in.tiff", tmp_path / "out.yuv"
     src.write_bytes(write_tiff(rgb))
-    _run(["--src_filename", src, "--dst_filename", dst, "--src_pic_width", d.width, "--src_pic_height", d.height,
-          "--src_bit_depth", 16, "--dst_bit_depth", 16, "--src_chroma_format_idc", 3, "--dst_chroma_format_idc", 1,
-          "--src_matrix_coeffs", 0, "--dst_matrix_coeffs", 15, "--src_colour_primaries", 1, "--dst_colour_primaries", 1,
-          "--src_transfer_characteristics", 1, "--dst_transfer_characteristics", 1, "--chroma_resampler_type", 0,
-          "--src_video_full_range_flag", 1, "--dst_video_full_range_flag", 1])
+    ht.cli_ok(["--src_filename", src, "--dst_filename", dst, "--src_pic_width", d.width, "--src_pic_height", d.height,
+               "--src_bit_depth", 16, "--dst_bit_depth", 16, "--src_chroma_format_idc", 3, "--dst_chroma_format_idc", 1,
+               "--src_matrix_coeffs", 0, "--dst_matrix_coeffs", 15, "--src_colour_primaries", 1, "--dst_colour_primaries", 1,
+               "--src_transfer_characteristics", 1, "--dst_transfer_characteristics", 1, "--chroma_resampler_type", 0,
+               "--src_video_full_range_flag", 1, "--dst_video_full_range_flag", 1])
     planes, _ = read_tiff(rgb, full_range=1)
     _expect(oracle, yref, d, planes, np.frombuffer(dst.read_bytes(), "<u2"), ".tiff")

@@ -2,11 +2,11 @@
 answers (tests/golden/ref_answers_yuvp2.npz, checked against oracle/_ref's object code where that is built), what
 h2y_desc_check takes and refuses, and the command line's --dry_run.  No GPU."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import h2y_testing as ht
 import hdr2yuv_amd as h
 import yuvp2_files as yf
 from oracle import binding as ob
@@ -67,15 +67,11 @@ def test_desc_check_refuses_other_resamplers():
 
 
 def test_dry_run_takes_15(tmp_path):
-    exe = os.path.join(ROOT, "hdr2yuv_amd", "hdr2yuv")
-    if not os.path.exists(exe):
-        subprocess.run(["make", "-C", os.path.join(ROOT, "hdr2yuv_amd", "cli"), "--no-print-directory"], check=True)
     args = ["--src_filename", tmp_path / "in.yuv", "--dst_filename", tmp_path / "out.yuv", "--src_pic_width", 64, "--src_pic_height", 32,
             "--src_bit_depth", 16, "--dst_bit_depth", 12, "--src_chroma_format_idc", 3, "--dst_chroma_format_idc", 1,
             "--src_matrix_coeffs", 0, "--dst_matrix_coeffs", 15, "--chroma_resampler_type", 1, "--dry_run", 1]
-    r = subprocess.run([exe] + [str(a) for a in args], capture_output=True, text=True, timeout=120)
+    r = ht.run_cli(args, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "dst_matrix_coeffs: 15" in r.stdout
-    r = subprocess.run([exe] + [str(a) for a in args[:-4]] + ["--chroma_resampler_type", "2", "--dry_run", "1"], capture_output=True,
-                       text=True, timeout=120)
+    r = ht.run_cli(args[:-4] + ["--chroma_resampler_type", "2"], timeout=120, dry=True)
     assert r.returncode != 0 and "chroma_resampler_type" in r.stdout
