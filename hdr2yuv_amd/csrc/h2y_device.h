@@ -479,8 +479,15 @@ template <int THREADS> __device__ __forceinline__ void stage_lut16_scaled(const 
 
 /* ---- matrix_inverse (convert.cpp:1320-1867), one pixel: see k_inverse (h2y_kernels.hip) for the behaviour kept ----
  * BT.709 green: the reference divides by 0.7152 in binary64.  Here: one fused multiply-add with the reciprocal, and the IEEE
- * division only when the result's rounding to float could differ (its low 29 bits within 4096 ulp(double) of the tie:
- * the reciprocal form is off by an ulp or two; 1.5e-5 of the pixels). */
+ * division only when the result's rounding to float could differ (its low 29 bits within 4096 ulp(double) of the tie; 1.5e-5
+ * of the pixels by chance, 6.7e-5 measured over the 2^36 triples of 12-bit input: many quotients are nearly exact).
+ * How far off the reciprocal form is (host restatement, libm fma, every 12-bit triple): at most 2 ulp(double) where |q| >= 1
+ * and at most 2^-40 in absolute terms anywhere -- an ulp of num / 0.7152 before the add.  Counted in ulps of the SUM it has no
+ * bound: where num / 0.7152 is close to -0.5 the sum cancels and the two forms are 6.6e12 ulp apart (13 046 on the planes of
+ * the inverse sweeps), far outside the window.  That is harmless because such a q is tiny and (int)(float)q is 0 either way:
+ * a code can change only where the tie lies ON an integer (1 801 triples of the 2^36, tests/golden/inverse_guard_triples.npz
+ * holds them all), there |q| >= 1, and there the window is 2000 times the error.  The unguarded form changes the float at
+ * 635 820 triples and the code at 16 of them ("Inverse sweeps"). */
 __device__ __forceinline__ void inverse_pixel(const inverse_args &a, uint32_t y, uint32_t cb, uint32_t cr, uint32_t &G, uint32_t &B, uint32_t &R)
 {
     float Yav = (float)y;
