@@ -127,6 +127,25 @@ class Oracle:
         self._inverse_fn = L.h2y_oracle_matrix_inverse
         L.h2y_oracle_up444.restype = None
         L.h2y_oracle_up444.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_uint]
+        L.h2y_oracle_powf25.restype = None
+        L.h2y_oracle_powf25.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.h2y_oracle_to_linear.restype = None
+        L.h2y_oracle_to_linear.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
+
+    def powf25(self, v: np.ndarray) -> np.ndarray:
+        """powf(25, v) of every binary32 of `v`: the float RHO_GAMMA_f's outer pow starts from."""
+        v = np.ascontiguousarray(v, dtype=np.float32)
+        out = np.empty_like(v)
+        self.lib.h2y_oracle_powf25(v.ctypes.data, out.ctypes.data, v.size)
+        return out
+
+    def to_linear(self, v: np.ndarray, src_transfer: int) -> np.ndarray:
+        """Source transfer -> linear light of every binary32 of `v` (what the transfer chain computes before the destination
+        function): binary32, the shape of `v`.  One C call: it releases the GIL, so a thread pool splits a long list."""
+        v = np.ascontiguousarray(v, dtype=np.float32)
+        out = np.empty_like(v)
+        self.lib.h2y_oracle_to_linear(int(src_transfer), v.ctypes.data, out.ctypes.data, v.size)
+        return out
 
     def pq(self, x: float) -> float:
         return float(self.lib.h2y_oracle_pq10000_r(float(x)))

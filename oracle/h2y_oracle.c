@@ -99,6 +99,16 @@ static float o_transfer_chain(int src, int dst, float x)
     return x;
 }
 float h2y_oracle_transfer_chain(int src, int dst, float x) { return o_transfer_chain(src, dst, x); }
+/* RHO_GAMMA_f's inner powf(rho, V) over n samples: the binary32 its outer pow starts from */
+void h2y_oracle_powf25(const float *in, float *out, size_t n)
+{
+    for (size_t i = 0; i < n; i++) out[i] = powf(25.0f, in[i]);
+}
+/* the source half of the chain over n samples: source transfer -> linear light (dst 8 adds nothing) */
+void h2y_oracle_to_linear(int src_transfer, const float *in, float *out, size_t n)
+{
+    for (size_t i = 0; i < n; i++) out[i] = o_transfer_chain(src_transfer, 8, in[i]);
+}
 
 /* ---- pic_stats(), common.cpp:66-168 ------------------------------------ */
 void h2y_oracle_stats_f32(const float *const planes[3], size_t n, float mm[6],

@@ -43,6 +43,10 @@ float h2y_oracle_pq10000_r(float L);
 
 /* source transfer -> linear -> destination transfer for one sample, convert.cpp:1024-1109 */
 float h2y_oracle_transfer_chain(int src_transfer, int dst_transfer, float x);
+/* h2y_oracle_transfer_chain(src_transfer, 8, .) over n samples: source transfer -> linear light; in and out may be the same array */
+void h2y_oracle_to_linear(int src_transfer, const float *in, float *out, size_t n);
+/* powf(25.0f, .) over n samples: the inner pow of RHO_GAMMA_f, convert.cpp:12-27 */
+void h2y_oracle_powf25(const float *in, float *out, size_t n);
 
 /* pic_stats F32 branch, common.cpp:116-136. mm = {min0,max0,min1,max1,min2,max2} */
 void h2y_oracle_stats_f32(const float *const planes[3], size_t n, float mm[6],

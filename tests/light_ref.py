@@ -49,8 +49,12 @@ def powf25(v):
     return out[inv.reshape(-1)].reshape(v.shape)
 
 
-def to_linear(v, src_transfer):
-    """tf_to_linear(class of src_transfer, v) on binary32 v: a binary32 result"""
+def to_linear(v, src_transfer, to_linear_fn=None):
+    """tf_to_linear(class of src_transfer, v) on binary32 v: a binary32 result.  to_linear_fn(v, src_transfer), when given,
+    computes it instead (the oracle's vector export, for lists too long for powf25's loop; test_light_sweeps.py pins it to the
+    numpy + libm form below)"""
+    if to_linear_fn is not None and src_transfer != LINEAR:
+        return to_linear_fn(v, src_transfer)
     with np.errstate(all="ignore"):
         if src_transfer == LINEAR:
             return v
@@ -66,23 +70,27 @@ def to_linear(v, src_transfer):
     raise ValueError(f"no linear light for src_transfer {src_transfer}")
 
 
-def light_m(planes, floor, ceiling, src_transfer):
+def light_m(planes, floor, ceiling, src_transfer, to_linear_fn=None):
     """m per pixel (binary32, flat): max over G, B, R of the normalised, linearised sample, NaN as 0, clamped to [0, 1]"""
     out = None
     for c, p in enumerate(planes):
         v = p.astype(np.float32).reshape(-1)
         with np.errstate(all="ignore"):
             x = (v - np.float32(floor[c])) / np.float32(_wrap32(ceiling[c] - floor[c]))
-        x = to_linear(x.astype(np.float32), src_transfer)
+        x = to_linear(x.astype(np.float32), src_transfer, to_linear_fn)
         x = np.where(x > 0, np.minimum(x, np.float32(1.0)), np.float32(0.0)).astype(np.float32)
         out = x if out is None else np.maximum(out, x)
     return out
 
 
-def light_stats(planes, width, sample, src_transfer, src_depth=16, override=None):
+def light_stats(planes, width, sample, src_transfer, src_depth=16, override=None, to_linear_fn=None):
     """the figures of h2y_light_stats for one frame (planes: G, B, R arrays as uploaded); override: (floor, ceiling) lists"""
     fl, ce = override if override is not None else pic_stats(planes, sample, src_depth)
-    m = light_m(planes, fl, ce, src_transfer)
+    return stats_of_m(light_m(planes, fl, ce, src_transfer, to_linear_fn), width)
+
+
+def stats_of_m(m, width):
+    """the figures of one frame from its pixels' m (flat binary32)"""
     i = int(np.argmax(m))  # the first index of the maximum
     mx = m[i]
     sum_q = int(np.rint(m.astype(np.float64) * 2.0 ** 32).astype(np.uint64).sum(dtype=np.uint64))

@@ -140,3 +140,27 @@ def test_other_transfer_tables_equal_libm(pq_check, fn, lo, hi, stride):
     assert rc == 0 and " mismatches 0," in out, out
     m = re.search(r"slow tier (\d+) \(([\d.]+)%\)", out)
     assert float(m.group(2)) < 0.01, out
+
+
+def test_slow_samples_whose_table_float_is_not_the_references(pq_check):
+    """What a table tier that never said "slow" would get wrong on the dense light sweeps' lists (tests/light_sweeps.py, rows L1
+    and L2), counted on the host: x^2.4 over every float of [2^-14, 1] flags 1 883 samples and the table's float differs from
+    libm's at 6 of them; H(P) over every P of [1, 25] at 12 -- the seven floats above 1.0 that lie below the table's foot and five
+    others.  light_sweeps.TIE_VALUES holds the six and the V of the five, so that the one-value row L3 compares each float for
+    float."""
+    import numpy as np
+
+    import light_ref as lr
+    import light_sweeps as ls
+
+    rc, out = _run(pq_check, "tfx", "3", hex(ls.DENSE["L1"]["lo"]), hex(ls.DENSE["L1"]["hi"] + 1), "8", "1", "list")
+    assert rc == 0 and "117440513 floats, mismatches 0, slow tier 1883 " in out and "samples 6 have a table float" in out, out
+    rows = [ln.split() for ln in out.splitlines() if ln.startswith("0x")]
+    assert [int(r[0], 16) for r in rows] == ls.TIE_VALUES[:6].tolist()
+    want = lr.to_linear(ls.TIE_VALUES[:6].view(np.float32), 1).view(np.uint32).astype(np.int64)
+    assert np.all(np.abs(np.array([int(r[1], 16) for r in rows]) - want) == 1)  # one ulp off, each of them
+    rc, out = _run(pq_check, "tfx", "6", "0x3f800000", "0x41c80001", "8", "1", "list")
+    assert rc == 0 and " mismatches 0," in out and "samples 12 have a table float" in out, out
+    p_bits = [int(ln.split()[0], 16) for ln in out.splitlines() if ln.startswith("0x")]
+    assert p_bits[:7] == [0x3F800001 + k for k in range(7)]
+    assert lr.powf25(ls.TIE_VALUES[6:].view(np.float32)).view(np.uint32).tolist() == p_bits[7:]

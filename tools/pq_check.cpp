@@ -135,19 +135,23 @@ int main(int argc, char **argv)
         /* The table tier of the other transfer functions (tfn_build_table / tfn_fast, h2y_math.h) against this machine's
          * libm, function by function, over every float x in [LO, HI) (bit patterns; default: the whole table domain
          * [2^-24, 2) plus what lies around it).  A sample the tier flags "slow" is not compared (it goes to the careful
-         * tier); one it answers must be the reference's float.  pq_check tfx FN LO HI THREADS [STRIDE] */
+         * tier); one it answers must be the reference's float.  Of the flagged samples, those whose table float is NOT the
+         * reference's are counted too -- what a tier that never said "slow" would get wrong -- and with a last argument
+         * "list" printed, a line each: the input's bit pattern, the table float's.  pq_check tfx FN LO HI THREADS [STRIDE [list]] */
         const int fn = atoi(argv[2]);
         uint32_t lo = argc > 3 ? (uint32_t)strtoul(argv[3], 0, 0) : 0x33000000u, hi = argc > 4 ? (uint32_t)strtoul(argv[4], 0, 0) : 0x40800000u;
         int T = argc > 5 ? atoi(argv[5]) : 8;
         uint64_t stride = argc > 6 ? strtoull(argv[6], 0, 0) : 1;
         std::vector<pq_recA> A(2 * H2Y_PQ_NREC);
         const int nbad = tfn_build_table(fn, A.data(), reinterpret_cast<pq_recB *>(A.data() + H2Y_PQ_NREC));
-        std::atomic<uint64_t> mism{0}, nslow{0}, total{0};
+        const bool list = argc > 7 && !strcmp(argv[7], "list");
+        std::atomic<uint64_t> mism{0}, nslow{0}, total{0}, changed{0};
+        std::vector<std::vector<uint32_t>> lists(T);
         std::vector<std::thread> th;
         uint64_t span = (uint64_t)hi - lo;
         for (int t = 0; t < T; t++)
             th.emplace_back([&, t]() {
-                uint64_t a = lo + span * t / T, b = lo + span * (t + 1) / T, mm = 0, ns = 0, n = 0;
+                uint64_t a = lo + span * t / T, b = lo + span * (t + 1) / T, mm = 0, ns = 0, n = 0, ch = 0;
                 for (uint64_t u = a; u < b; u += stride) {
                     float x = bits2f((uint32_t)u);
                     float want;
@@ -168,17 +172,28 @@ int main(int argc, char **argv)
                     bool slow;
                     const float got = tfn_fast(x, A.data(), tfn_cut_of(fn), tfn_zero_bits(fn), tfn_one_bits(fn), &slow);
                     n++;
-                    if (slow) { ns++; continue; }
-                    if (f2bits(got) != f2bits(want) && !(got != got && want != want)) {
+                    const bool differs = f2bits(got) != f2bits(want) && !(got != got && want != want);
+                    if (slow) {
+                        ns++;
+                        if (differs) {
+                            ch++;
+                            if (list) { lists[t].push_back((uint32_t)u); lists[t].push_back(f2bits(got)); }
+                        }
+                        continue;
+                    }
+                    if (differs) {
                         if (mm++ < 3) fprintf(stderr, "tfx fn %d MISMATCH x=%a (0x%08x) got %a want %a\n", fn, x, (uint32_t)u, got, want);
                     }
                 }
-                mism += mm; nslow += ns; total += n;
+                mism += mm; nslow += ns; total += n; changed += ch;
             });
         for (auto &x : th) x.join();
         printf("tfx fn %d over [0x%08x,0x%08x) step %llu: %llu floats, mismatches %llu, slow tier %llu (%.4f%%), sentinel segments %d of %d\n", fn, lo, hi,
                (unsigned long long)stride, (unsigned long long)total.load(), (unsigned long long)mism.load(), (unsigned long long)nslow.load(),
                100.0 * nslow.load() / (double)total.load(), nbad, tfn_nseg(tfn_cut_of(fn)));
+        printf("tfx fn %d: of the slow tier's samples %llu have a table float that is not the reference's\n", fn, (unsigned long long)changed.load());
+        for (const auto &l : lists) /* the threads' ranges ascend */
+            for (size_t i = 0; i + 1 < l.size(); i += 2) printf("0x%08x 0x%08x\n", l[i], l[i + 1]);
         return mism ? 1 : 0;
     }
     if (!strcmp(argv[1], "powf")) {
