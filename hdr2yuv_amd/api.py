@@ -40,6 +40,7 @@ EXPORTS = [
     "h2y_scale_taps", "h2y_scale_frame_bytes", "h2y_scale_batch", "h2y_stream_scale", "h2y_scale_stream_open",
     "h2y_gamut_matrix", "h2y_gamut_batch", "h2y_stream_gamut",
     "h2y_ctx_set_chroma_siting", "h2y_subsample_420_sited",
+    "h2y_ctx_set_inverse_chroma_siting", "h2y_upsample_444_sited",
 ]
 
 COMPARE_FRAMES_PER_LAUNCH = 64
@@ -313,6 +314,10 @@ def load_library():
     L.h2y_subsample_420_sited.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.h2y_ctx_set_chroma_siting.restype = C.c_int
     L.h2y_ctx_set_chroma_siting.argtypes = [C.c_void_p, C.c_int]
+    L.h2y_ctx_set_inverse_chroma_siting.restype = C.c_int
+    L.h2y_ctx_set_inverse_chroma_siting.argtypes = [C.c_void_p, C.c_int]
+    L.h2y_upsample_444_sited.restype = C.c_int
+    L.h2y_upsample_444_sited.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p]
     L.h2y_matrix_inverse.restype = C.c_int
     L.h2y_matrix_inverse.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.h2y_upsample_444.restype = C.c_int
@@ -592,6 +597,11 @@ class Context:
         """h2y_ctx_set_chroma_siting: 0 as the resampler sites the 4:2:0 chroma (the default), 2 top-left (HDR10); before a ring is opened."""
         self._check(self.lib.h2y_ctx_set_chroma_siting(self.h, chroma_sample_loc_type))
 
+    def set_inverse_chroma_siting(self, chroma_sample_loc_type: int) -> None:
+        """h2y_ctx_set_inverse_chroma_siting: how the .yuv -> RGB entries take 4:2:0 chroma: 0 as the reference's upsampler does (the
+        default), 2 top-left (HDR10); before a ring is opened."""
+        self._check(self.lib.h2y_ctx_set_inverse_chroma_siting(self.h, chroma_sample_loc_type))
+
     def set_stream(self, hip_stream_ptr: int | None):
         self._check(self.lib.h2y_ctx_set_stream(self.h, C.c_void_p(hip_stream_ptr or 0)))
 
@@ -676,6 +686,10 @@ class Context:
     def upsample_444(self, width, height, algorithm, min_cv, max_cv, src, dst) -> None:
         """Subsample420to444: device U16 (height/2 x width/2) plane -> device U16 (height x width) plane."""
         self._check(self.lib.h2y_upsample_444(self.h, width, height, algorithm, min_cv, max_cv, self._ptr(src), self._ptr(dst)))
+
+    def upsample_444_sited(self, width, height, loc_type, min_cv, max_cv, src, dst) -> None:
+        """One u16 chroma plane 4:2:0 -> 4:4:4 by the FIR, its source sited as chroma_sample_loc_type says: 0 the reference's, 2 top-left."""
+        self._check(self.lib.h2y_upsample_444_sited(self.h, width, height, loc_type, min_cv, max_cv, self._ptr(src), self._ptr(dst)))
 
     def inverse_420(self, width, height, in_depth, in_full_range, in_matrix, out_depth, algorithm, in_planes, out_planes) -> None:
         """Device U16 4:2:0 planes (Y, Cb/Dz, Cr/Dx) -> device U16 planes (G, B, R): upsample, then matrix_inverse."""

@@ -76,6 +76,13 @@
  *             --content_light and --gamut_convert.  Refused (exit 1, also under --dry_run): any other value (1 is the box
  *             resampler's siting), 2 with --chroma_resampler_type 0, with --dst_chroma_format_idc 3, with --dst_matrix_coeffs 15,
  *             with --scale 1 or --scale_only 1, on the .yuv -> RGB flow, with --compare_only 1 and with --histogram_only 1.
+ * --src_chroma_sample_loc_type 0|2 (an addition, the way back of the flag above): 2 reads the 4:2:0 chroma of a .yuv as co-sited with
+ *             the top-left luma sample (HDR10, UHD Blu-ray; what --dst_chroma_sample_loc_type 2 writes) and upsamples it accordingly
+ *             (include/hdr2yuv_hip.h, "inverse chroma siting", states every step); 0 is the reference's upsampler, the bytes written
+ *             without the flag.  On the .yuv -> .rgb / .tiff flow with --src_chroma_format_idc 1, with any --gpus, with or without
+ *             --dst_filename, beside --ref_filename, --ssim and --histogram.  Refused (exit 1, also under --dry_run): any other
+ *             value (1 is replication's siting), 2 with --chroma_resampler_type 0, 2 with --src_chroma_format_idc 3, every forward
+ *             flow, --compare_only 1, --histogram_only 1 and --scale_only 1.
  * Only user_args_t.chroma_resampler_type has no defined default there (never initialised): FIR here, as in
  * make.sh's example.  The reference calls exit(0) on its argument errors; this program returns 1.
  */
@@ -125,6 +132,9 @@ struct cli_args {
     /* --dst_chroma_sample_loc_type: 0 as the resampler sites the 4:2:0 chroma, 2 top-left */
     int siting = 0;
     bool siting_given = false;
+    /* --src_chroma_sample_loc_type: how the .yuv -> RGB flow takes the 4:2:0 chroma, 0 as the reference's upsampler, 2 top-left */
+    int src_siting = 0;
+    bool src_siting_given = false;
     /* the histogram: --histogram FILE, --histogram_bits (0: the counted frames' depth), --histogram_only, --check_range; what is
      * counted, resolved by cli_resolve_histogram: depth, range, G,B,R limits, chroma format */
     const char *hist = nullptr;
@@ -196,6 +206,8 @@ static inline void cli_help()
            "  10 XYZ; what is not above 0 is clipped to 0 unless --gamut_clip 0)\n"
            "  chroma siting: [--dst_chroma_sample_loc_type 0|2] (2: 4:2:0 chroma co-sited with the top-left luma sample, as HDR10\n"
            "  assumes -- x265 --chromaloc 2, SVT-AV1 --chroma-sample-position topleft; needs the FIR resampler; 0: as without the flag)\n"
+           "  [--src_chroma_sample_loc_type 0|2] (.yuv -> .rgb / .tiff with --src_chroma_format_idc 1; 2: the 4:2:0 chroma is co-sited\n"
+           "  with the top-left luma sample and is upsampled so; needs the FIR resampler; 0: as without the flag)\n"
            "  scaling: [--scale 1 [--scale_taps A]] (with --dst_pic_width / --dst_pic_height: every .yuv frame resampled on the GPU by\n"
            "  an exact Lanczos filter of A = 2, 3 or 4 lobes, 3 by default; each axis ratio within 1/4 .. 4), [--scale_only 1] (a .yuv or\n"
            "  .rgb source into a destination of the same extension, no conversion)\n"
@@ -228,6 +240,7 @@ static inline void cli_parse(cli_args &a, int argc, char **argv)
         else if (is("--gamut_convert")) { a.gamut = atoi(val()); a.gamut_given = true; }
         else if (is("--gamut_clip")) { a.gamut_clip = atoi(val()); a.gamut_clip_given = true; }
         else if (is("--dst_chroma_sample_loc_type")) { a.siting = atoi(val()); a.siting_given = true; }
+        else if (is("--src_chroma_sample_loc_type")) { a.src_siting = atoi(val()); a.src_siting_given = true; }
         else if (is("--histogram")) a.hist = val();
         else if (is("--histogram_bits")) { a.hist_bits = atoi(val()); a.hist_bits_given = true; }
         else if (is("--histogram_only")) a.hist_only = atoi(val());
@@ -406,6 +419,7 @@ static inline int cli_resolve_scale_only(cli_args &a);
 static inline int cli_resolve_scale(cli_args &a);
 static inline int cli_resolve_gamut(cli_args &a, int src_matrix_arg);
 static inline int cli_resolve_siting(cli_args &a);
+static inline int cli_resolve_src_siting(cli_args &a);
 static inline int cli_resolve(cli_args &a)
 {
     const int src_matrix_arg = a.in.matrix_coeffs; /* as given: the float readers force G,B,R on the input picture below */
@@ -419,6 +433,7 @@ static inline int cli_resolve(cli_args &a)
     if (a.scale_given || a.scale_only || a.scale_taps_given) arg_errors += cli_resolve_scale(a);
     if (a.gamut_given || a.gamut_clip_given) arg_errors += cli_resolve_gamut(a, src_matrix_arg);
     if (a.siting_given) arg_errors += cli_resolve_siting(a);
+    if (a.src_siting_given) arg_errors += cli_resolve_src_siting(a);
     return arg_errors;
 }
 
@@ -655,6 +670,42 @@ static inline int cli_resolve_siting(cli_args &a)
     }
     if (a.scale) {
         printf("WARNING: --dst_chroma_sample_loc_type 2 is not combined with --scale 1: the scaler aligns sample centres and would move the siting\n");
+        return 1;
+    }
+    return 0;
+}
+
+/* --src_chroma_sample_loc_type: how the .yuv -> RGB flow takes its 4:2:0 chroma, 0 (as the reference's upsampler) or 2 (top-left);
+ * returns the number of argument errors */
+static inline int cli_resolve_src_siting(cli_args &a)
+{
+    printf("src_chroma_sample_loc_type: %d\n", a.src_siting);
+    if (a.src_siting == 1) {
+        printf("WARNING: src_chroma_sample_loc_type(1) is replication's siting, --chroma_resampler_type 0: not selected by this flag\n");
+        return 1;
+    }
+    if (a.src_siting != 0 && a.src_siting != 2) {
+        printf("WARNING: src_chroma_sample_loc_type(%d) not 0 or 2\n", a.src_siting);
+        return 1;
+    }
+    if (a.compare_only || a.hist_only || a.scale_only) {
+        printf("WARNING: --src_chroma_sample_loc_type sites the chroma a conversion reads: not with --%s 1\n",
+               a.compare_only ? "compare_only" : a.hist_only ? "histogram_only" : "scale_only");
+        return 1;
+    }
+    if (!a.inverse) {
+        printf("WARNING: --src_chroma_sample_loc_type sites the chroma of the .yuv -> RGB flow (.yuv to .rgb or .tiff): the forward flow "
+               "reads no subsampled chroma\n");
+        return 1;
+    }
+    if (!a.src_siting) return 0;
+    if (a.in.chroma_format_idc != H2Y_CHROMA_420) {
+        printf("WARNING: --src_chroma_sample_loc_type 2 sites 4:2:0 chroma: src_chroma_format_idc(%d) has none to site\n", a.in.chroma_format_idc);
+        return 1;
+    }
+    if (a.resampler == 0) {
+        printf("WARNING: --src_chroma_sample_loc_type 2 needs the FIR resampler: replication (--chroma_resampler_type 0) is centre sited by "
+               "construction\n");
         return 1;
     }
     return 0;

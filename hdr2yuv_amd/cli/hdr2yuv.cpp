@@ -92,6 +92,10 @@
  * the settings that signal the siting to an encoder:
  *   chroma_siting x265 --chromaloc 2
  *   chroma_siting svt-av1 --chroma-sample-position topleft
+ * The way back (--src_chroma_sample_loc_type 0|2 on the .yuv -> .rgb / .tiff flow with 4:2:0 input): each GPU thread sets its
+ * context's inverse chroma siting (h2y_ctx_set_inverse_chroma_siting) before it opens its inverse ring, so every frame, and what is
+ * armed on the ring, is upsampled from where the flag says the chroma lies.  The banner carries src_chroma_sample_loc_type: only
+ * when the flag is given.
  */
 #include <array>
 #include <cmath>
@@ -402,6 +406,7 @@ static flow inverse_flow(const job &j)
     const size_t luma = (size_t)a.in.width * a.in.height * 2, chroma = (j.in_frame_bytes - luma) / 2, out_frame = j.out_frame_bytes;
     flow f;
     f.open = [&a, tiff](h2y_ctx *ctx) {
+        if (a.src_siting && h2y_ctx_set_inverse_chroma_siting(ctx, a.src_siting)) return (int)H2Y_EINVAL; /* before the ring is opened */
         return (tiff ? h2y_tiff_inverse_stream_open : h2y_inverse_stream_open)(ctx, a.in.width, a.in.height, a.in.chroma_format_idc,
                                                                               a.in.bit_depth, a.in.video_full_range_flag, a.in.matrix_coeffs,
                                                                               a.out.bit_depth, a.resampler, kRingDepth);

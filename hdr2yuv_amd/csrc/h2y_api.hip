@@ -316,12 +316,12 @@ static void inverse_setup(inverse_args &a, int width, int height, int in_bit_dep
 
 /* ... and those of the 4:2:0 flow (yuv2tiff.cpp:92-93,142-154: minCV 0, maxCV 2^depth - 1 for the upsampling) */
 void inverse420_setup(inv420_args &a, int width, int height, int in_bit_depth, int in_full_range, int in_matrix_coeffs,
-                             int out_bit_depth, int algorithm)
+                             int out_bit_depth, int form)
 {
     a.up.src0 = a.up.src1 = nullptr;
     a.up.dst0 = a.up.dst1 = nullptr;
     a.up.width = width; a.up.height = height;
-    a.up.algorithm = algorithm;
+    a.up.algorithm = form;
     a.up.fmin = 0.0f; a.up.fmax = (float)((1u << in_bit_depth) - 1u);
     for (int c = 0; c < 3; c++) {
         a.inv.in[c] = nullptr;
@@ -379,8 +379,8 @@ static int upsample_launch(h2y_ctx *ctx, int width, int height, int algorithm, u
     return H2Y_OK;
 }
 
-int h2y_upsample_444(h2y_ctx *ctx, int width, int height, int algorithm, unsigned min_cv, unsigned max_cv, const uint16_t *d_src,
-                     uint16_t *d_dst)
+static int upsample_444(h2y_ctx *ctx, int width, int height, int algorithm /* UP_* */, unsigned min_cv, unsigned max_cv,
+                        const uint16_t *d_src, uint16_t *d_dst)
 {
     if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
     if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
@@ -394,6 +394,44 @@ int h2y_upsample_444(h2y_ctx *ctx, int width, int height, int algorithm, unsigne
     int rc = upsample_launch(ctx, width, height, algorithm, min_cv, max_cv, d_src, nullptr, d_dst, nullptr);
     if (rc) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return H2Y_OK;
+}
+
+int h2y_upsample_444(h2y_ctx *ctx, int width, int height, int algorithm, unsigned min_cv, unsigned max_cv, const uint16_t *d_src,
+                     uint16_t *d_dst)
+{
+    return upsample_444(ctx, width, height, algorithm ? UP_FIR : UP_REPLICATE, min_cv, max_cv, d_src, d_dst);
+}
+
+int h2y_upsample_444_sited(h2y_ctx *ctx, int width, int height, int chroma_sample_loc_type, unsigned min_cv, unsigned max_cv,
+                           const uint16_t *d_src, uint16_t *d_dst)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if (chroma_sample_loc_type != 0 && chroma_sample_loc_type != 2)
+        return fail(ctx, H2Y_EINVAL, "chroma_sample_loc_type %d: want 0 (the reference's upsampler) or 2 (top-left)", chroma_sample_loc_type);
+    return upsample_444(ctx, width, height, chroma_sample_loc_type == 2 ? UP_FIR_TL : UP_FIR, min_cv, max_cv, d_src, d_dst);
+}
+
+int h2y_ctx_set_inverse_chroma_siting(h2y_ctx *ctx, int chroma_sample_loc_type)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0) || ctx->streaming)
+        return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open: set the inverse chroma siting before");
+    if (chroma_sample_loc_type != 0 && chroma_sample_loc_type != 2)
+        return fail(ctx, H2Y_EINVAL, "chroma_sample_loc_type %d: want 0 (as the reference's upsampler sites it) or 2 (top-left)", chroma_sample_loc_type);
+    ctx->opt_inv_siting = chroma_sample_loc_type;
+    return H2Y_OK;
+}
+
+/* What `algorithm` means on this context: replication, the reference's FIR pair, or under inverse chroma siting 2 the top-left
+ * form.  4:4:4 input has nothing to upsample; replication is centre sited by construction and is refused under siting 2. */
+int inverse_form(h2y_ctx *ctx, int chroma, int algorithm, int *form)
+{
+    *form = algorithm ? UP_FIR : UP_REPLICATE;
+    if (ctx->opt_inv_siting != 2 || chroma != H2Y_CHROMA_420) return H2Y_OK;
+    if (!algorithm)
+        return fail(ctx, H2Y_EUNSUPPORTED, "inverse chroma siting 2 (top-left) with algorithm 0: replication is centre sited by construction");
+    *form = UP_FIR_TL;
     return H2Y_OK;
 }
 
@@ -411,11 +449,14 @@ int h2y_inverse_420(h2y_ctx *ctx, int width, int height, int in_bit_depth, int i
     if (!d_out || !d_out[0] || !d_out[1] || !d_out[2]) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
     for (int c = 0; c < 3; c++)
         if (((uintptr_t)d_in[c] & 3) || ((uintptr_t)d_out[c] & 3)) return fail(ctx, H2Y_EINVAL, "plane %d is not 4-byte aligned", c);
+    int form;
+    const int frc = inverse_form(ctx, H2Y_CHROMA_420, algorithm, &form);
+    if (frc) return frc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     /* one pass: both chroma planes upsampled inside the blocks (yuv2tiff.cpp:92-93,142-154: minCV 0, maxCV 2^depth - 1), then
      * matrix_inverse's pixel; the 4:4:4 chroma never reaches memory (k_inverse420, h2y_resample.hip) */
     inv420_args a;
-    inverse420_setup(a, width, height, in_bit_depth, in_full_range, in_matrix_coeffs, out_bit_depth, algorithm);
+    inverse420_setup(a, width, height, in_bit_depth, in_full_range, in_matrix_coeffs, out_bit_depth, form);
     a.up.src0 = d_in[1]; a.up.src1 = d_in[2];
     a.inv.in[0] = d_in[0];
     for (int c = 0; c < 3; c++) a.inv.out[c] = d_out[c];
@@ -429,7 +470,7 @@ int h2y_inverse_420(h2y_ctx *ctx, int width, int height, int in_bit_depth, int i
     ctx->last_ms = ms;
     ctx->last_launches = 1;
     ctx->last_name = "k_inverse420";
-    ctx->last_variant = algorithm ? "k_inverse420<FIR>" : "k_inverse420<REPLICATE>";
+    ctx->last_variant = form == UP_FIR_TL ? "k_inverse420<FIR_TL>" : form == UP_FIR ? "k_inverse420<FIR>" : "k_inverse420<REPLICATE>";
     return H2Y_OK;
 }
 
@@ -444,6 +485,10 @@ int h2y_inverse_frame(h2y_ctx *ctx, int width, int height, int in_chroma_format_
     if (!in_planes || !out_planes) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
     for (int c = 0; c < 3; c++)
         if (!in_planes[c] || !out_planes[c]) return fail(ctx, H2Y_EINVAL, "plane %d is null", c);
+    int form;
+    const int frc = inverse_form(ctx, in_chroma_format_idc, algorithm, &form); /* the refusal, before anything is copied or launched */
+    if (frc) return frc;
+    (void)form; /* h2y_inverse_420 below takes it again */
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const bool sub = in_chroma_format_idc == H2Y_CHROMA_420;
     const size_t pb = (size_t)width * height * sizeof(uint16_t), pb_al = (pb + 255) & ~(size_t)255;
@@ -526,6 +571,9 @@ int h2y_inverse_batch(h2y_ctx *ctx, int width, int height, int in_chroma_format_
     const inv_params p{width, height, in_chroma_format_idc, in_bit_depth, in_full_range, in_matrix_coeffs, out_bit_depth, algorithm};
     int rc = inverse_check(ctx, p);
     if (rc) return rc;
+    int form;
+    rc = inverse_form(ctx, in_chroma_format_idc, algorithm, &form);
+    if (rc) return rc;
     if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
     if (!d_in || !d_out) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
     const bool sub = in_chroma_format_idc == H2Y_CHROMA_420;
@@ -546,7 +594,7 @@ int h2y_inverse_batch(h2y_ctx *ctx, int width, int height, int in_chroma_format_
             h[f].out[c] = d_out[3 * f + c];
         }
     inv420_args a;
-    inverse420_setup(a, width, height, in_bit_depth, in_full_range, in_matrix_coeffs, out_bit_depth, algorithm);
+    inverse420_setup(a, width, height, in_bit_depth, in_full_range, in_matrix_coeffs, out_bit_depth, form);
     /* units of one frame: k_inverse420's tiles, or k_inverse's chunks of 256 quads (+ the npix % 4 single samples) */
     const uint32_t n4 = a.inv.npix >> 2;
     const uint32_t per_frame = sub ? (uint32_t)h2y_inverse420_tiles(width, height) : (n4 + (a.inv.npix & 3u) + 255) / 256;
@@ -559,7 +607,8 @@ int h2y_inverse_batch(h2y_ctx *ctx, int width, int height, int in_chroma_format_
                                        : h2y_launch_inverse_batch(grid, ctx->stream, a.inv, frames, nf);
                         });
     if (rc) return rc;
-    ctx->last_variant = sub ? (algorithm ? "k_inverse420_batch<FIR>" : "k_inverse420_batch<REPLICATE>") : "k_inverse_batch";
+    ctx->last_variant = !sub ? "k_inverse_batch"
+                        : form == UP_FIR_TL ? "k_inverse420_batch<FIR_TL>" : form == UP_FIR ? "k_inverse420_batch<FIR>" : "k_inverse420_batch<REPLICATE>";
     return H2Y_OK;
 }
 

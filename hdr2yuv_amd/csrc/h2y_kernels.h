@@ -184,11 +184,14 @@ struct firf_args {
     h2y::pix_params pp;
 };
 
+/* the upsampling forms of k_up444 / k_inverse420(_batch): up_args.algorithm.  The entries map the public `algorithm` (0, or any other
+ * value for the FIR) and the context's inverse chroma siting onto these */
+enum { UP_REPLICATE = 0, UP_FIR = 1, UP_FIR_TL = 2 };
 struct up_args { /* k_up444: one or two chroma planes, (width/2 x height/2) -> (width x height) */
     const uint16_t *src0, *src1; /* src1 may be NULL (one plane) */
     uint16_t *dst0, *dst1;
     int width, height;           /* of the 4:4:4 result; both even */
-    int algorithm;               /* 0 replication, else the FIR pair */
+    int algorithm;               /* UP_REPLICATE, UP_FIR_TL, else the reference's FIR pair */
     float fmin, fmax;            /* (float) of minCV / maxCV, convert.cpp:1932-1934 */
 };
 

@@ -1534,6 +1534,14 @@ H2Y_FN uint32_t up_fir_odd(float m0, float m1, float m2, float m3, float m4, flo
     acc = acc + c159 * (m2 + m3);
     return up_clamp_trunc(acc + 0.5f, lo, hi);
 }
+/* vertical stage of the top-left sited form (the project's own, include/hdr2yuv_hip.h "inverse chroma siting"), odd output rows:
+ * the half-phase taps of up_fir_odd down the column, m0..m5 = source rows r-2 .. r+3, in exact integers (159 (a + b) passes 2^24 at
+ * 16-bit codes, so binary32 would depend on the order of summation; |S| < 2^25).  The even rows are imed3(C[r], lo, hi). */
+H2Y_FN uint32_t up_fir_tl(int32_t m0, int32_t m1, int32_t m2, int32_t m3, int32_t m4, int32_t m5, int32_t lo, int32_t hi)
+{
+    const int32_t S = 21 * (m0 + m5) - 52 * (m1 + m4) + 159 * (m2 + m3) + 128;
+    return (uint32_t)imed3(S >> 8, lo, hi);
+}
 
 } // namespace h2y
 #endif /* H2Y_MATH_H */

@@ -6,6 +6,9 @@
  *             (3 -16 67 227 -32 7)/256 per output-row parity into a U16 4:2:2 intermediate, then
  *             horizontal: even samples copied, odd samples (21 -52 159 159 -52 21)/256; edges replicated
  *             by index clamping; every stage clamps to [minCV, maxCV] and truncates to unsigned short.
+ *             A third form, UP_FIR_TL, is the project's own for chroma co-sited with the top-left luma sample
+ *             (chroma_sample_loc_type 2; include/hdr2yuv_hip.h, "inverse chroma siting"): its vertical stage copies the
+ *             even rows and takes the odd rows by the half-phase six-tap in integers (up_fir_tl); the rest is shared.
  *
  *   k_inverse420  the .yuv 4:2:0 -> RGB flow in ONE pass (yuv2tiff.cpp:341-342 then its pixel loop = matrix_inverse,
  *             convert.cpp:1320-1867): both chroma planes upsampled as above inside the block (source tiles and the U16
@@ -28,9 +31,10 @@
 #define UP_SW (UP_TW + 5) /* staged source / intermediate columns: 2 left, 3 right of the tile */
 #define UP_SH (UP_TH + 6) /* staged source rows: 3 above, 3 below */
 
-template <bool FIR>
+template <int FORM> /* UP_REPLICATE, UP_FIR or UP_FIR_TL (h2y_kernels.h) */
 __global__ __launch_bounds__(256) void k_up444(up_args a)
 {
+    constexpr bool FIR = FORM != UP_REPLICATE;
     const int W = a.width, w2 = W >> 1, h2 = a.height >> 1;
     const uint16_t *src = blockIdx.z ? a.src1 : a.src0;
     uint16_t *dst = blockIdx.z ? a.dst1 : a.dst0;
@@ -63,6 +67,15 @@ __global__ __launch_bounds__(256) void k_up444(up_args a)
     /* vertical stage, :1911-1946: intermediate rows 2j (taps j-3..j+2) and 2j+1 (taps j+3..j-2, mirrored) */
     for (int i = threadIdx.x; i < UP_TH * UP_SW; i += 256) {
         const int r = i / UP_SW, c = i - r * UP_SW;
+        if (FORM == UP_FIR_TL) { /* top-left sited: row 2j is source row j, row 2j+1 the half-phase taps of rows j-2 .. j+3 */
+            int32_t t[6];
+#pragma unroll
+            for (int k = 0; k < 6; k++) t[k] = s_src[r + 1 + k][c];
+            const int32_t lo = (int32_t)a.fmin, hi = (int32_t)a.fmax;
+            s_mid[2 * r][c] = (uint16_t)imed3(t[2], lo, hi);
+            s_mid[2 * r + 1][c] = (uint16_t)up_fir_tl(t[0], t[1], t[2], t[3], t[4], t[5], lo, hi);
+            continue;
+        }
         float s[7];
 #pragma unroll
         for (int k = 0; k < 7; k++) s[k] = (float)s_src[r + k][c]; /* source rows j-3 .. j+3 */
@@ -96,10 +109,12 @@ typedef uint32_t iv_u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t iv_u32x4 __attribute__((ext_vector_type(4)));
 /* One tile of k_inverse420 / k_inverse420_batch.  vec16: the luma and the G, B, R planes all start on a 16-byte boundary (the
  * 16-byte loads and stores of the last stage are taken only then; otherwise 4-byte ones) */
-template <bool FIR>
+template <int FORM>
 __device__ __forceinline__ void inverse420_tile(const inv420_args &a, int tile, int tiles_x, bool vec16,
-                                                float (&s_src)[2][FIR ? IV_SH : 1][IV_LW], float (&s_mid)[2][FIR ? 2 * IV_TH : 1][IV_LW])
+                                                float (&s_src)[2][FORM != UP_REPLICATE ? IV_SH : 1][IV_LW],
+                                                float (&s_mid)[2][FORM != UP_REPLICATE ? 2 * IV_TH : 1][IV_LW])
 {
+    constexpr bool FIR = FORM != UP_REPLICATE;
     const up_args &u = a.up;
     const int W = u.width, w2 = W >> 1, h2 = u.height >> 1;
     const int ty = tile / tiles_x, c0 = (tile - ty * tiles_x) * UP_TW, r0 = ty * IV_TH;
@@ -128,6 +143,24 @@ __device__ __forceinline__ void inverse420_tile(const inv420_args &a, int tile, 
         for (int i = threadIdx.x; i < 2 * IV_TH * (IV_LW / 4); i += 256) { /* 288 items: one or two per thread */
             const int p = i >= IV_TH * (IV_LW / 4), j = i - p * (IV_TH * (IV_LW / 4));
             const int r = j / (IV_LW / 4), c = (j - r * (IV_LW / 4)) * 4;
+            if (FORM == UP_FIR_TL) { /* top-left sited: row 2r is source row r, row 2r+1 up_fir_tl of rows r-2 .. r+3, in integers */
+                int32_t t[6][4];
+#pragma unroll
+                for (int k = 0; k < 6; k++) {
+                    const float4 v = *reinterpret_cast<const float4 *>(&s_src[p][r + 1 + k][c]);
+                    t[k][0] = (int32_t)v.x; t[k][1] = (int32_t)v.y; t[k][2] = (int32_t)v.z; t[k][3] = (int32_t)v.w;
+                }
+                const int32_t lo = (int32_t)u.fmin, hi = (int32_t)u.fmax;
+                float ev[4], od[4];
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    ev[q] = (float)imed3(t[2][q], lo, hi);
+                    od[q] = (float)up_fir_tl(t[0][q], t[1][q], t[2][q], t[3][q], t[4][q], t[5][q], lo, hi);
+                }
+                *reinterpret_cast<float4 *>(&s_mid[p][2 * r][c]) = float4{ev[0], ev[1], ev[2], ev[3]};
+                *reinterpret_cast<float4 *>(&s_mid[p][2 * r + 1][c]) = float4{od[0], od[1], od[2], od[3]};
+                continue;
+            }
             float4 s[7];
 #pragma unroll
             for (int k = 0; k < 7; k++) s[k] = *reinterpret_cast<const float4 *>(&s_src[p][r + k][c]);
@@ -208,25 +241,27 @@ __device__ __forceinline__ void inverse420_tile(const inv420_args &a, int tile, 
     }
 }
 
-template <bool FIR>
+template <int FORM>
 __global__ __launch_bounds__(256) void k_inverse420(inv420_args a)
 {
+    constexpr bool FIR = FORM != UP_REPLICATE;
     const int w2 = a.up.width >> 1, h2 = a.up.height >> 1;
     const int tiles_x = (w2 + UP_TW - 1) / UP_TW, tiles = tiles_x * ((h2 + IV_TH - 1) / IV_TH);
     /* both stages' samples are kept as floats in LDS (every one of them is an integer below 2^16: exact), converted once where
      * they are produced instead of at each of their seven (vertical) or six (horizontal) uses */
     __shared__ __attribute__((aligned(16))) float s_src[2][FIR ? IV_SH : 1][IV_LW];
     __shared__ __attribute__((aligned(16))) float s_mid[2][FIR ? 2 * IV_TH : 1][IV_LW];
-    for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) inverse420_tile<FIR>(a, tile, tiles_x, true, s_src, s_mid);
+    for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) inverse420_tile<FORM>(a, tile, tiles_x, true, s_src, s_mid);
 }
 
 /* k_inverse420 over n_frames frames of one size in one launch: a persistent grid deals (frame, tile) units over all of them, so
  * that no frame boundary leaves CUs idle.  The frame of a unit is block-uniform: its six plane pointers are scalar loads from
  * the table (__restrict__ const: nothing the kernel stores can alias it).  Unlike k_inverse420 the planes need only be 4-byte
  * aligned: the 16-byte accesses are taken per frame, where its four full-size planes allow them. */
-template <bool FIR>
+template <int FORM>
 __global__ __launch_bounds__(256) void k_inverse420_batch(inv420_args base, const inv_frame *__restrict__ frames, int n_frames)
 {
+    constexpr bool FIR = FORM != UP_REPLICATE;
     const int w2 = base.up.width >> 1, h2 = base.up.height >> 1;
     const int tiles_x = (w2 + UP_TW - 1) / UP_TW, tiles = tiles_x * ((h2 + IV_TH - 1) / IV_TH);
     __shared__ __attribute__((aligned(16))) float s_src[2][FIR ? IV_SH : 1][IV_LW];
@@ -241,7 +276,7 @@ __global__ __launch_bounds__(256) void k_inverse420_batch(inv420_args base, cons
         a.inv.in[0] = fr.in[0];
         for (int c = 0; c < 3; c++) a.inv.out[c] = fr.out[c];
         const bool vec16 = (((uintptr_t)fr.in[0] | (uintptr_t)fr.out[0] | (uintptr_t)fr.out[1] | (uintptr_t)fr.out[2]) & 15u) == 0;
-        inverse420_tile<FIR>(a, tile, tiles_x, vec16, s_src, s_mid);
+        inverse420_tile<FORM>(a, tile, tiles_x, vec16, s_src, s_mid);
     }
 }
 
@@ -250,15 +285,17 @@ hipError_t h2y_launch_inverse420(hipStream_t st, const inv420_args &a)
     const int w2 = a.up.width >> 1, h2 = a.up.height >> 1;
     const int tiles = ((w2 + UP_TW - 1) / UP_TW) * ((h2 + IV_TH - 1) / IV_TH);
     dim3 grid(tiles < 2048 ? tiles : 2048, 1, 1); /* eight blocks of 256 per CU at most: the rest of the tiles by the same blocks */
-    if (a.up.algorithm == 0) hipLaunchKernelGGL(k_inverse420<false>, grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(k_inverse420<true>, grid, dim3(256), 0, st, a);
+    if (a.up.algorithm == UP_REPLICATE) hipLaunchKernelGGL(k_inverse420<UP_REPLICATE>, grid, dim3(256), 0, st, a);
+    else if (a.up.algorithm == UP_FIR_TL) hipLaunchKernelGGL(k_inverse420<UP_FIR_TL>, grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_inverse420<UP_FIR>, grid, dim3(256), 0, st, a);
     return hipGetLastError();
 }
 
 hipError_t h2y_launch_inverse420_batch(int grid, hipStream_t st, const inv420_args &base, const inv_frame *frames, int n_frames)
 {
-    if (base.up.algorithm == 0) hipLaunchKernelGGL(k_inverse420_batch<false>, dim3(grid), dim3(256), 0, st, base, frames, n_frames);
-    else hipLaunchKernelGGL(k_inverse420_batch<true>, dim3(grid), dim3(256), 0, st, base, frames, n_frames);
+    if (base.up.algorithm == UP_REPLICATE) hipLaunchKernelGGL(k_inverse420_batch<UP_REPLICATE>, dim3(grid), dim3(256), 0, st, base, frames, n_frames);
+    else if (base.up.algorithm == UP_FIR_TL) hipLaunchKernelGGL(k_inverse420_batch<UP_FIR_TL>, dim3(grid), dim3(256), 0, st, base, frames, n_frames);
+    else hipLaunchKernelGGL(k_inverse420_batch<UP_FIR>, dim3(grid), dim3(256), 0, st, base, frames, n_frames);
     return hipGetLastError();
 }
 
@@ -272,7 +309,8 @@ hipError_t h2y_launch_up444(hipStream_t st, const up_args &a)
 {
     const int w2 = a.width >> 1, h2 = a.height >> 1;
     dim3 grid((w2 + UP_TW - 1) / UP_TW, (h2 + UP_TH - 1) / UP_TH, a.src1 ? 2 : 1);
-    if (a.algorithm == 0) hipLaunchKernelGGL(k_up444<false>, grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(k_up444<true>, grid, dim3(256), 0, st, a);
+    if (a.algorithm == UP_REPLICATE) hipLaunchKernelGGL(k_up444<UP_REPLICATE>, grid, dim3(256), 0, st, a);
+    else if (a.algorithm == UP_FIR_TL) hipLaunchKernelGGL(k_up444<UP_FIR_TL>, grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_up444<UP_FIR>, grid, dim3(256), 0, st, a);
     return hipGetLastError();
 }

@@ -165,6 +165,8 @@ static int open_inverse_ring(h2y_ctx *ctx, const inv_params &p, bool interleave,
 {
     int rc = ring_may_open(ctx);
     if (!rc) rc = inverse_check(ctx, p);
+    int form = 0;
+    if (!rc) rc = inverse_form(ctx, p.chroma, p.algorithm, &form); /* the context's inverse chroma siting, read as the ring opens */
     if (rc) return rc;
     if (depth < 2 || depth > 16) return fail(ctx, H2Y_EINVAL, "depth must be 2..16");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -178,6 +180,7 @@ static int open_inverse_ring(h2y_ctx *ctx, const inv_params &p, bool interleave,
     ctx->s_out_stride = (pb & 15) ? pb_al : pb; /* 4:2:0 planes are always a multiple of 16 bytes */
     ctx->s_pay_off = (2 * ctx->s_out_stride + pb + 255) & ~(size_t)255;
     ctx->s_inv = p;
+    ctx->s_inv.algorithm = form; /* inverse_produce's UP_* form */
     rc = stream_alloc(ctx, depth, ctx->s_in_bytes, ctx->s_in_bytes, 3 * pb, interleave ? ctx->s_pay_off + 3 * pb : 2 * ctx->s_out_stride + pb);
     if (rc) return rc;
     if (interleave) {

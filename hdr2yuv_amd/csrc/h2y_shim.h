@@ -228,6 +228,8 @@ struct h2y_ctx {
     double opt_bal_rho = 1.0;
     int opt_fir = 0;           /* "fir": 0 auto, 1 two-pass (4:4:4 scratch + k_fir420), 2 fused single pass where it applies */
     int opt_siting = 0;        /* h2y_ctx_set_chroma_siting(): 0 as the resampler sites the chroma, 2 top-left (k_fir420_tl as the second pass) */
+    int opt_inv_siting = 0;    /* h2y_ctx_set_inverse_chroma_siting(): 0 the 4:2:0 chroma sited as the reference's upsampler takes it, 2 top-left
+                                  (k_up444 / k_inverse420(_batch) in their UP_FIR_TL form) */
     int opt_fir_sync = -1;     /* "firsync": k_fir_fused's blocks meet at a barrier every so many steps (power of two; 0 = never);
                                   -1 = by the pictures: every step, never while the first tier passes many pixels on */
     double fir_flag_share = 0.0; /* share of the last k_fir_fused batch's pixels (in tiles of eight) the first tier could not settle */
@@ -451,8 +453,9 @@ int run_stats(h2y_ctx *ctx, const h2y_desc *d, const void *const in[3], int slot
 /* ---- h2y_api.hip: the inverse set-up ------------------------------------------------------------------------------------------------ */
 
 int inverse_check(h2y_ctx *ctx, const inv_params &p);
+int inverse_form(h2y_ctx *ctx, int chroma, int algorithm, int *form); /* the UP_* form of `algorithm` under the context's inverse chroma siting, or the refusal */
 void inverse420_setup(inv420_args &a, int width, int height, int in_bit_depth, int in_full_range, int in_matrix_coeffs, int out_bit_depth,
-                      int algorithm);
+                      int form);
 
 /* ---- h2y_ring.hip: what a measurement's arm and *_stream_open entries use ----------------------------------------------------------- */
 

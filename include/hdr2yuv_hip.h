@@ -769,7 +769,7 @@ int h2y_stream_gamut(h2y_ctx *ctx, int src_primaries, int dst_primaries, int cli
  *      equals fir_h down the column.
  *   3. write_yuv's shift and per-plane range clamp, as after the reference's FIR (not in the stage entry).
  *   4. Y is untouched.
- * Not honoured by the .yuv -> RGB direction, whose upsampler assumes the reference's siting. */
+ * The .yuv -> RGB direction honours it through h2y_ctx_set_inverse_chroma_siting, below ("inverse chroma siting"). */
 
 /* The siting of the 4:2:0 chroma this context's forward conversions write: 0 (the default) as the resampler sites it -- every byte
  * as without this call -- or 2, top-left.  Any other value: H2Y_EINVAL.  H2Y_EINVAL too while a batch is in flight or a ring is
@@ -789,6 +789,40 @@ int h2y_ctx_set_chroma_siting(h2y_ctx *ctx, int chroma_sample_loc_type);
  * h2y_last_kernel_name "k_fir420" or "k_fir420_tl". */
 int h2y_subsample_420_sited(h2y_ctx *ctx, int width, int height, int bit_depth, int chroma_sample_loc_type, const uint16_t *d_src,
                             uint16_t *d_dst);
+
+/* ---- inverse chroma siting: upsampling 4:2:0 chroma that is co-sited with the top-left luma sample (chroma_sample_loc_type 2) -----
+ * The reference's Subsample420to444 (h2y_upsample_444) takes the chroma as its own FIR wrote it: co-sited horizontally, centred
+ * between two luma rows vertically (loc type 0) -- its vertical stage is the quarter-phase pair (3 -16 67 227 -32 7)/256.  On
+ * HDR10-style 4:2:0 (what h2y_ctx_set_chroma_siting(2) writes, or any decoded HDR10 stream) that leaves the chroma half a luma row
+ * low.  This is the project's own definition of the top-left upsampler; the reference has none, so there are no bytes to match.
+ * Input: a chroma plane C of w2 x h2 codes (w2 = width/2, h2 = height/2), sample (r, c) co-sited with luma (2r, 2c); the clip
+ *   [minCV, maxCV] (0 and 2^in_bit_depth - 1 in the flow, yuv2tiff.cpp:92-93,142-154).
+ *   1. Vertical, in exact integers, into a U16 intermediate M of w2 x height; rows clamped into 0..h2-1:
+ *        M[2r][c]   = med3(C[r][c], minCV, maxCV)                                           (a copy)
+ *        S          = 21 (C[r-2] + C[r+3]) - 52 (C[r-1] + C[r+2]) + 159 (C[r] + C[r+1])     (the half-phase six-tap, down the column)
+ *        M[2r+1][c] = med3((S + 128) >> 8, minCV, maxCV)
+ *      The shift is arithmetic (the floor); |S| < 2^25: int32 holds it.  The taps read the unclamped source codes, as the
+ *      reference's vertical stage does.  Integers, not binary32: 159 (a + b) passes 2^24 at 16-bit codes.
+ *   2. Horizontal, the reference's stage unchanged (convert.cpp:1956-1979): out[y][2c] = M[y][c]; out[y][2c+1] the binary32
+ *      (21 -52 159 159 -52 21)/256 of M[y][c-2..c+3], columns clamped, every product and sum rounded by itself, + 0.5, the clamp,
+ *      truncation.  Horizontally the reference is co-sited already.
+ *   3. matrix_inverse's pixel, unchanged. */
+
+/* The siting of the 4:2:0 chroma this context's .yuv -> RGB entries read: 0 (the default) as the reference's upsampler takes it --
+ * every byte as without this call -- or 2, top-left.  Any other value: H2Y_EINVAL.  H2Y_EINVAL too while a batch is pending or a
+ * ring is open.  Independent of h2y_ctx_set_chroma_siting.  It is read at each call of h2y_inverse_420, h2y_inverse_frame and
+ * h2y_inverse_batch, and when h2y_inverse_stream_open or h2y_tiff_inverse_stream_open opens; what is armed on those rings (compare,
+ * SSIM, histogram) sees the G, B, R of the sited upsampling.  With 2:
+ *   - 4:2:0 input with `algorithm` != 0 runs the form above ("k_inverse420<FIR_TL>" / "k_inverse420_batch<FIR_TL>" in
+ *     h2y_last_kernel_variant; h2y_last_kernel_name stays "k_inverse420" / "k_inverse420_batch").  4:4:4 input is unaffected;
+ *   - H2Y_EUNSUPPORTED for 4:2:0 input with `algorithm` 0 (replication is centre sited by construction); nothing is launched. */
+int h2y_ctx_set_inverse_chroma_siting(h2y_ctx *ctx, int chroma_sample_loc_type);
+
+/* The stage entry beside h2y_upsample_444: one U16 chroma plane 4:2:0 -> 4:4:4 by the FIR, the source sited as
+ * chroma_sample_loc_type says: 0 the reference's FIR pair (h2y_upsample_444 with algorithm 1), 2 the top-left form above.  Any
+ * other value: H2Y_EINVAL.  Sizes, the clip and alignment as h2y_upsample_444.  Synchronous. */
+int h2y_upsample_444_sited(h2y_ctx *ctx, int width, int height, int chroma_sample_loc_type, unsigned min_cv, unsigned max_cv,
+                           const uint16_t *d_src, uint16_t *d_dst);
 
 /* Timing of the last h2y_convert_batch*() (or h2y_inverse_*, h2y_dpx_decode_batch, h2y_tiff_decode_batch,
  * h2y_rgb_interleave_batch, h2y_exr_decode_batch, h2y_compare_batch, h2y_ssim_batch, h2y_light_batch, h2y_scale_batch, h2y_gamut_batch) call measured with HIP events on

@@ -8,7 +8,10 @@ pinned ring of h2y_stream_* (the three overlapped).
   1. kernel us per frame (HIP events, h2y_last_kernel_ms) and wall time per frame (host clock, every call synchronous) of
      h2y_inverse_batch at 64 frames per call, next to the single-frame entries (h2y_inverse_420 / h2y_matrix_inverse) called
      64 times, in the same process: 4:2:0 FIR, 4:2:0 replication, 4:4:4;
-  2. frames/s from host memory, 4:2:0 FIR: h2y_inverse_frame (pageable, serial) against the inverse stream (depth 3).
+  2. the top-left sited form beside the FIR form (h2y_ctx_set_inverse_chroma_siting 2 and 0): k_inverse420_batch<FIR_TL> and
+     k_inverse420_batch<FIR> on the same 64 frames, five calls each, taken in turn: the median kernel us per frame and the
+     lowest and highest call of each;
+  3. frames/s from host memory, 4:2:0 FIR: h2y_inverse_frame (pageable, serial) against the inverse stream (depth 3).
 Prints one line per figure, then one JSON line with all of them.
 
 `streambench.py dpx`: DPX input on 4K pictures, for each of 10-bit, 16-bit and float DPX:
@@ -152,6 +155,23 @@ def inverse_main():
         res[name] = r
         print(f"{name:14s} us/frame  single: kernel {r['single_kernel_us']:7.1f} wall {r['single_wall_us']:7.1f}   "
               f"batch of {nb}: kernel {r['batch_kernel_us']:7.1f} wall {r['batch_wall_us']:7.1f}", flush=True)
+        if name == "420_fir":  # the sited form beside it, on the same buffers: one warm-up call each, then five each in turn
+            calls = {0: [], 2: []}
+            variant = {}
+            for rep in range(6):
+                for loc in (0, 2):
+                    ctx.set_inverse_chroma_siting(loc)
+                    ctx.inverse_batch(w, hh, 1, 12, 0, 1, 16, 1, frames_in, frames_out)
+                    variant[loc] = ctx.last_kernel_variant()
+                    if rep:
+                        calls[loc].append(ctx.last_kernel_ms()[0] / nb * 1e3)
+            ctx.set_inverse_chroma_siting(0)
+            for loc, key in ((0, "sited_0"), (2, "sited_2")):
+                v = calls[loc]
+                res[key] = {"variant": variant[loc], "calls": len(v), "median_us": round(float(np.median(v)), 1),
+                            "min_us": round(min(v), 1), "max_us": round(max(v), 1)}
+                print(f"{variant[loc]:28s} us/frame over {len(v)} calls of {nb}: median {np.median(v):7.1f}  min {min(v):7.1f}  max {max(v):7.1f}",
+                      flush=True)
         del srcs, frames_in, frames_out
         torch.cuda.empty_cache()
 
