@@ -18,6 +18,10 @@ from .api import (  # noqa: F401
     H2YExrInfo,
     H2YHistogramStats,
     H2YLightStats,
+    H2YLightdistStats,
+    LIGHTDIST_BINS,
+    LIGHTDIST_FIRST_BITS,
+    LIGHTDIST_PCT,
     H2YSsimStats,
     H2YTiffInfo,
     MATRIX_BT2020NC,
@@ -39,6 +43,7 @@ from .api import (  # noqa: F401
     frame_bytes,
     gamut_matrix,
     library_path,
+    lightdist_json,
     load_library,
     make_desc,
     parse_dpx,

@@ -37,6 +37,7 @@ EXPORTS = [
     "h2y_histogram_batch", "h2y_stream_histogram", "h2y_stream_histogram_ex", "h2y_stream_histogram_result",
     "h2y_histogram_stream_open", "h2y_ssim_batch", "h2y_stream_ssim", "h2y_stream_ssim_result",
     "h2y_light_batch", "h2y_stream_light", "h2y_stream_light_result",
+    "h2y_lightdist_batch", "h2y_stream_lightdist", "h2y_stream_lightdist_result", "h2y_lightdist_json",
     "h2y_scale_taps", "h2y_scale_frame_bytes", "h2y_scale_batch", "h2y_stream_scale", "h2y_scale_stream_open",
     "h2y_gamut_matrix", "h2y_gamut_batch", "h2y_stream_gamut",
     "h2y_ctx_set_chroma_siting", "h2y_subsample_420_sited",
@@ -47,6 +48,10 @@ COMPARE_FRAMES_PER_LAUNCH = 64
 HISTOGRAM_FRAMES_PER_LAUNCH = 64
 SSIM_FRAMES_PER_LAUNCH = 64
 LIGHT_FRAMES_PER_LAUNCH = 64
+LIGHTDIST_FRAMES_PER_LAUNCH = 64
+LIGHTDIST_BINS = 8706  # bins of max(L_G, L_B, L_R) by its binary32 bits: below 2^-17, 512 per binade up to 1, and 1 itself
+LIGHTDIST_FIRST_BITS = 0x37000000  # 2^-17: the lower edge of bin 1
+LIGHTDIST_PCT = (100, 500, 1000, 2500, 5000, 7500, 9000, 9500, 9900, 9998)  # the percentiles, in hundredths of a percent
 SCALE_FRAMES_PER_LAUNCH = 64
 GAMUT_FRAMES_PER_LAUNCH = 64
 SCALE_TAPS = 32  # coefficients per row of scale_taps' table
@@ -197,6 +202,22 @@ class H2YLightStats(C.Structure):
 
     def __repr__(self):
         return f"H2YLightStats({self.as_dict()})"
+
+
+class H2YLightdistStats(C.Structure):
+    """h2y_lightdist_stats: a frame's light distribution -- the largest L of planes G, B, R and the largest m = max(L_G, L_B, L_R)
+    as binary32 bits, the sum over the pixels of rint(m x 2^32), the pixel count, the pixels with m <= 0.01f, and the lower bin edges
+    of the LIGHTDIST_PCT percentiles of m as binary32 bits."""
+
+    _fields_ = [("maxscl_bits", C.c_uint32 * 3), ("max_bits", C.c_uint32), ("sum_q", C.c_uint64), ("pixels", C.c_uint64),
+                ("below_100", C.c_uint64), ("pct_bits", C.c_uint32 * len(LIGHTDIST_PCT))]
+
+    def as_dict(self):
+        return dict(maxscl_bits=list(self.maxscl_bits), max_bits=self.max_bits, sum_q=self.sum_q, pixels=self.pixels,
+                    below_100=self.below_100, pct_bits=list(self.pct_bits))
+
+    def __repr__(self):
+        return f"H2YLightdistStats({self.as_dict()})"
 
 
 def make_desc(width, height, *, sample=SAMPLE_F32, src_depth=32, dst_depth=10, src_transfer=TRANSFER_LINEAR,
@@ -393,6 +414,14 @@ def load_library():
     L.h2y_stream_light.restype = C.c_int
     L.h2y_stream_light_result.argtypes = [C.c_void_p, C.POINTER(H2YLightStats)]
     L.h2y_stream_light_result.restype = C.c_int
+    L.h2y_lightdist_batch.argtypes = [C.c_void_p, C.POINTER(H2YDesc), C.c_int, C.POINTER(C.c_void_p), C.POINTER(H2YLightdistStats), C.c_void_p]
+    L.h2y_lightdist_batch.restype = C.c_int
+    L.h2y_stream_lightdist.argtypes = [C.c_void_p]
+    L.h2y_stream_lightdist.restype = C.c_int
+    L.h2y_stream_lightdist_result.argtypes = [C.c_void_p, C.POINTER(H2YLightdistStats)]
+    L.h2y_stream_lightdist_result.restype = C.c_int
+    L.h2y_lightdist_json.argtypes = [C.POINTER(H2YLightdistStats), C.c_int, C.c_long, C.c_char_p, C.c_size_t]
+    L.h2y_lightdist_json.restype = C.c_size_t
     L.h2y_scale_taps.argtypes = [C.c_int] * 3 + [C.c_void_p] * 3 + [C.POINTER(C.c_int)]
     L.h2y_scale_taps.restype = C.c_int
     L.h2y_scale_frame_bytes.argtypes = [C.c_int] * 3
@@ -544,6 +573,19 @@ def scale_taps(src: int, dst: int, a: int = 3):
     if rc != H2Y_OK:
         raise H2YError(rc, (lib.h2y_last_error(None) or b"").decode())
     return first, count, coef, most.value
+
+
+def lightdist_json(stats, first_frame_index: int = 0) -> str:
+    """h2y_lightdist_json (host only, no device): the HDR10+ JSON of the frames of stats (H2YLightdistStats), one scene."""
+    lib = load_library()
+    n = len(stats)
+    arr = (H2YLightdistStats * max(n, 1))(*stats)
+    need = lib.h2y_lightdist_json(arr, n, first_frame_index, None, 0)
+    if not need:
+        raise H2YError(H2Y_EINVAL, "h2y_lightdist_json: no frames, a negative first frame index or a frame without pixels")
+    buf = C.create_string_buffer(need + 1)
+    lib.h2y_lightdist_json(arr, n, first_frame_index, buf, need + 1)
+    return buf.value.decode()
 
 
 def gamut_matrix(src_primaries: int, dst_primaries: int) -> np.ndarray:
@@ -822,6 +864,19 @@ class Context:
         self._check(self.lib.h2y_light_batch(self.h, C.byref(d), n, ins, out))
         return list(out[:n])
 
+    def lightdist_batch(self, d: H2YDesc, frames_in, bins: bool = False):
+        """k_lightdist on device frames (as light_batch takes them): a list of H2YLightdistStats, one per frame; with bins also the
+        uint32 (n, LIGHTDIST_BINS) histograms."""
+        n = len(frames_in)
+        ins = (C.c_void_p * max(3 * n, 1))()
+        for f in range(n):
+            for c in range(3):
+                ins[3 * f + c] = self._ptr(frames_in[f][c])
+        out = (H2YLightdistStats * max(n, 1))()
+        b = np.zeros((max(n, 1), LIGHTDIST_BINS), dtype=np.uint32) if bins else None
+        self._check(self.lib.h2y_lightdist_batch(self.h, C.byref(d), n, ins, out, b.ctypes.data if bins else None))
+        return (list(out[:n]), b[:n]) if bins else list(out[:n])
+
     def scale_batch(self, src_w, src_h, dst_w, dst_h, chroma, bit_depth, full_range, gbr, a, frames_src, frames_dst) -> None:
         """k_scale on device frames (tensors or pointers, each frame's planes contiguous from a 16-byte aligned base):
         frames_dst[f] receives frames_src[f] resampled from src_w x src_h to dst_w x dst_h (Lanczos, a lobes)."""
@@ -924,6 +979,16 @@ class Context:
     def stream_light(self) -> None:
         """Arm an open forward ring (plain, DPX, TIFF or EXR) to measure every frame's content light (h2y_stream_light)."""
         self._check(self.lib.h2y_stream_light(self.h))
+
+    def stream_lightdist(self) -> None:
+        """Arm an open forward ring to measure every frame's light distribution (h2y_stream_lightdist)."""
+        self._check(self.lib.h2y_stream_lightdist(self.h))
+
+    def stream_lightdist_result(self) -> H2YLightdistStats:
+        """The light distribution of the frame stream_output returned last."""
+        st = H2YLightdistStats()
+        self._check(self.lib.h2y_stream_lightdist_result(self.h, C.byref(st)))
+        return st
 
     def stream_light_result(self) -> H2YLightStats:
         """The H2YLightStats of the frame stream_output returned last."""

@@ -49,6 +49,12 @@
  *             --ref_filename and --histogram.  Refused (exit 1, also under --dry_run) unless the destination transfer is PQ (16), the
  *             source transfer is not PQ and the source matrix is G,B,R (0); refused on the .yuv -> RGB flow, with --compare_only 1
  *             and with --histogram_only 1.
+ * --dynamic_metadata FILE (an addition): the HDR10+ (SMPTE ST 2094-40) dynamic metadata of the forward flow, measured on the device on
+ *             the samples --content_light 1 measures (include/hdr2yuv_hip.h, "light distribution", states every step): per frame the
+ *             largest R, G and B, the average and ten percentiles of max(R, G, B) and the share of pixels at or below 100 cd/m2,
+ *             printed per frame and written to FILE as the JSON x265 takes as --dhdr10-info (all frames in one scene).  Accepted
+ *             wherever --content_light 1 is, beside it, for any --gpus; refused (exit 1, also under --dry_run) wherever that flag
+ *             is, and for a FILE that cannot be created.
  * --scale 1 [--scale_taps 2|3|4] (an addition; the reference parses --dst_pic_width / --dst_pic_height for a Lanczos cv::resize in
  *             cv.cpp, which is compiled out and does not compile): with it a destination size that differs from the source's is
  *             legal on the forward flow to .yuv, and every converted frame is resampled on the device by the exact Lanczos
@@ -95,6 +101,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <strings.h>
+#include <sys/stat.h>
+#include <unistd.h>
 #include <string>
 #include <vector>
 
@@ -126,6 +134,8 @@ struct cli_args {
     /* --content_light 1: MaxCLL / MaxFALL of the forward flow */
     int light = 0;
     bool light_given = false;
+    /* --dynamic_metadata FILE: the HDR10+ JSON of the forward flow */
+    const char *dynmeta = nullptr;
     /* --gamut_convert 1: the source planes go from the source's to the destination's primaries; --gamut_clip (1 by default) */
     int gamut = 0, gamut_clip = 1;
     bool gamut_given = false, gamut_clip_given = false;
@@ -201,6 +211,8 @@ static inline void cli_help()
            "  totals into FILE; exit status 4 on a sample outside the legal range), [--histogram_only 1] (--src_filename, no conversion)\n"
            "  content light: [--content_light 1] (MaxCLL and MaxFALL of a conversion to PQ, per frame and for the run; without\n"
            "  --dst_filename nothing is written)\n"
+           "  dynamic metadata: [--dynamic_metadata FILE] (HDR10+, SMPTE ST 2094-40: per frame maxSCL, the average and percentiles of\n"
+           "  max(R,G,B) of a conversion to PQ, written to FILE as the JSON of x265 --dhdr10-info)\n"
            "  primaries: [--gamut_convert 1 [--gamut_clip 0|1]] (float or half G,B,R source planes in linear light converted from\n"
            "  --src_colour_primaries to --dst_colour_primaries on the GPU before the conversion; 1 BT.709, 8 / 9 BT.2020, 12 P3-D65,\n"
            "  10 XYZ; what is not above 0 is clipped to 0 unless --gamut_clip 0)\n"
@@ -237,6 +249,7 @@ static inline void cli_parse(cli_args &a, int argc, char **argv)
         else if (is("--compare_only")) a.compare_only = atoi(val());
         else if (is("--ssim")) { a.ssim = atoi(val()); a.ssim_given = true; }
         else if (is("--content_light")) { a.light = atoi(val()); a.light_given = true; }
+        else if (is("--dynamic_metadata")) a.dynmeta = val();
         else if (is("--gamut_convert")) { a.gamut = atoi(val()); a.gamut_given = true; }
         else if (is("--gamut_clip")) { a.gamut_clip = atoi(val()); a.gamut_clip_given = true; }
         else if (is("--dst_chroma_sample_loc_type")) { a.siting = atoi(val()); a.siting_given = true; }
@@ -415,6 +428,7 @@ static inline int cli_resolve_histogram(cli_args &a)
 static inline int cli_resolve_convert(cli_args &a);
 static inline int cli_resolve_ssim(cli_args &a);
 static inline int cli_resolve_light(cli_args &a);
+static inline int cli_resolve_dynmeta(cli_args &a);
 static inline int cli_resolve_scale_only(cli_args &a);
 static inline int cli_resolve_scale(cli_args &a);
 static inline int cli_resolve_gamut(cli_args &a, int src_matrix_arg);
@@ -430,6 +444,7 @@ static inline int cli_resolve(cli_args &a)
     if (a.hist || a.hist_bits_given || a.hist_only || a.check_range) arg_errors += cli_resolve_histogram(a);
     if (a.ssim_given) arg_errors += cli_resolve_ssim(a);
     if (a.light_given) arg_errors += cli_resolve_light(a);
+    if (a.dynmeta) arg_errors += cli_resolve_dynmeta(a);
     if (a.scale_given || a.scale_only || a.scale_taps_given) arg_errors += cli_resolve_scale(a);
     if (a.gamut_given || a.gamut_clip_given) arg_errors += cli_resolve_gamut(a, src_matrix_arg);
     if (a.siting_given) arg_errors += cli_resolve_siting(a);
@@ -540,8 +555,34 @@ static inline int cli_resolve_scale(cli_args &a)
     return 0;
 }
 
-/* --content_light: the forward flow of a conversion to PQ from another transfer, of a G,B,R source; returns the number of argument
- * errors */
+/* what measures light (`flag`: --content_light 1, --dynamic_metadata FILE) takes: the forward flow of a conversion to PQ from another
+ * transfer, of a G,B,R source; returns the number of argument errors */
+static inline int cli_light_scope(const cli_args &a, const char *flag)
+{
+    if (a.compare_only || a.hist_only) {
+        printf("WARNING: %s measures a conversion: not with --%s 1\n", flag, a.compare_only ? "compare_only" : "histogram_only");
+        return 1;
+    }
+    if (a.inverse) {
+        printf("WARNING: %s measures the forward flow (to .yuv), not the .yuv -> RGB flow\n", flag);
+        return 1;
+    }
+    if (a.out.transfer_characteristics != 16) {
+        printf("WARNING: %s needs a PQ destination: dst_transfer_characteristics(%d) is not 16\n", flag, a.out.transfer_characteristics);
+        return 1;
+    }
+    if (a.in.transfer_characteristics == 16) {
+        printf("WARNING: %s: a PQ source (src_transfer_characteristics 16) goes to PQ without linear light\n", flag);
+        return 1;
+    }
+    if (a.in.matrix_coeffs != H2Y_MATRIX_GBR) {
+        printf("WARNING: %s needs a G,B,R source: src_matrix_coeffs(%d) is not %d\n", flag, a.in.matrix_coeffs, H2Y_MATRIX_GBR);
+        return 1;
+    }
+    return 0;
+}
+
+/* --content_light; returns the number of argument errors */
 static inline int cli_resolve_light(cli_args &a)
 {
     printf("content_light: %d\n", a.light);
@@ -550,29 +591,32 @@ static inline int cli_resolve_light(cli_args &a)
         return 1;
     }
     if (!a.light) return 0;
-    if (a.compare_only || a.hist_only) {
-        printf("WARNING: --content_light 1 measures a conversion: not with --%s 1\n", a.compare_only ? "compare_only" : "histogram_only");
-        return 1;
-    }
-    if (a.inverse) {
-        printf("WARNING: --content_light 1 measures the forward flow (to .yuv), not the .yuv -> RGB flow\n");
-        return 1;
-    }
-    if (a.out.transfer_characteristics != 16) {
-        printf("WARNING: --content_light 1 needs a PQ destination: dst_transfer_characteristics(%d) is not 16\n",
-               a.out.transfer_characteristics);
-        return 1;
-    }
-    if (a.in.transfer_characteristics == 16) {
-        printf("WARNING: --content_light 1: a PQ source (src_transfer_characteristics 16) goes to PQ without linear light\n");
-        return 1;
-    }
-    if (a.in.matrix_coeffs != H2Y_MATRIX_GBR) {
-        printf("WARNING: --content_light 1 needs a G,B,R source: src_matrix_coeffs(%d) is not %d\n", a.in.matrix_coeffs, H2Y_MATRIX_GBR);
-        return 1;
-    }
+    if (cli_light_scope(a, "--content_light 1")) return 1;
     printf("content_light_from: src_transfer_characteristics %d -> PQ, G,B,R, floor and ceiling %s\n", a.in.transfer_characteristics,
            "of each frame's pic_stats");
+    return 0;
+}
+
+/* --dynamic_metadata FILE: content light's scope, and a FILE that can be created (an existing regular file that can be written, or
+ * a name in a directory that can be written to; nothing is created here); returns the number of argument errors */
+static inline int cli_resolve_dynmeta(cli_args &a)
+{
+    printf("dynamic_metadata_file: %s\n", a.dynmeta);
+    if (cli_light_scope(a, "--dynamic_metadata FILE")) return 1;
+    struct stat st;
+    bool ok;
+    if (!stat(a.dynmeta, &st)) ok = S_ISREG(st.st_mode) && !access(a.dynmeta, W_OK);
+    else {
+        const char *slash = strrchr(a.dynmeta, '/');
+        const std::string dir = !slash ? "." : slash == a.dynmeta ? "/" : std::string(a.dynmeta, slash);
+        ok = *a.dynmeta && !stat(dir.c_str(), &st) && S_ISDIR(st.st_mode) && !access(dir.c_str(), W_OK | X_OK);
+    }
+    if (!ok) {
+        printf("WARNING: --dynamic_metadata: file (%s) cannot be created\n", a.dynmeta);
+        return 1;
+    }
+    printf("dynamic_metadata_from: src_transfer_characteristics %d -> PQ, G,B,R, floor and ceiling %s; HDR10+ profile A, one scene, "
+           "percentiles of max(R,G,B) in %d bins\n", a.in.transfer_characteristics, "of each frame's pic_stats", H2Y_LIGHTDIST_BINS);
     return 0;
 }
 
@@ -776,7 +820,7 @@ static inline int cli_resolve_convert(cli_args &a)
     }
 
     /* :386-440 output type (without a destination: the reference file's) */
-    ext = cli_ext_of(a.dst ? a.dst : a.ref ? a.ref : a.hist || a.light ? "(none).yuv" : nullptr); /* only a histogram or the light: the .yuv flow */
+    ext = cli_ext_of(a.dst ? a.dst : a.ref ? a.ref : a.hist || a.light || a.dynmeta ? "(none).yuv" : nullptr); /* only a histogram or the light: the .yuv flow */
     if (!strcasecmp(ext, "yuv")) a.out_type = CLI_OUT_YUV;
     else if (!strcasecmp(ext, "rgb")) a.out_type = CLI_OUT_RGB;
     else if (!strcasecmp(ext, "tiff")) a.out_type = CLI_OUT_TIFF;

@@ -75,6 +75,13 @@
  *   light x265 --max-cll "<CLL>,<FALL>"
  *   light svt-av1 --content-light <CLL>,<FALL>
  *
+ * Dynamic metadata (--dynamic_metadata FILE on the forward flow; h2y_cli_args.h): each GPU thread arms its ring (h2y_stream_lightdist)
+ * and keeps the figures of frame k by its index; the report is printed and FILE written (h2y_lightdist_json: HDR10+ JSON, every frame
+ * in scene 0) once every thread is done, so both are the same for any --gpus.  cd/m2 "%.4f" (10000 x L; the percentiles are the lower
+ * edges of their bins), the percentiles 1, 5, 10, 25, 50, 75, 90, 95, 99 and 99.98 %, the share in percent:
+ *   dynamic_metadata: frame <k> maxscl <R> <G> <B> average <A> percentiles <p1> ... <p99.98> below_100 <share>
+ *   dynamic_metadata_written: <N> frames to FILE
+ *
  * Scaling (--scale 1 [--scale_taps A] with --dst_pic_width / --dst_pic_height on the forward flow; h2y_cli_args.h): each GPU thread
  * arms its ring (h2y_stream_scale), so the frame that comes down is the converted frame resampled on the device to the destination
  * size (include/hdr2yuv_hip.h states the filter); frame k is written at `size of the file at start + k x scaled frame bytes`.
@@ -149,6 +156,7 @@ struct results {
     std::vector<h2y_compare_stats> compare;
     std::vector<h2y_ssim_stats> ssim;
     std::vector<h2y_light_stats> light;
+    std::vector<h2y_lightdist_stats> lightdist;
     std::vector<h2y_histogram_stats> hist;
     std::vector<std::array<uint32_t, 3>> occupied; /* the non-zero bins of frame k's planes */
     std::vector<uint32_t> bins;                    /* per GPU thread: one frame's 3 x nbins */
@@ -156,7 +164,7 @@ struct results {
     size_t nbins = 0;
     results(const cli_args &a, long frames)
         : compare(a.ref ? (size_t)frames : 0), ssim(a.ssim ? (size_t)frames : 0), light(a.light ? (size_t)frames : 0),
-          hist(a.hist ? (size_t)frames : 0), occupied(hist.size())
+          lightdist(a.dynmeta ? (size_t)frames : 0), hist(a.hist ? (size_t)frames : 0), occupied(hist.size())
     {
         if (!a.hist) return;
         nbins = (size_t)1 << a.hist_bits;
@@ -183,6 +191,7 @@ struct results {
             }
         }
         if (a.light && h2y_stream_light_result(ctx, &light[k])) return false;
+        if (a.dynmeta && h2y_stream_lightdist_result(ctx, &lightdist[k])) return false;
         return true;
     }
     /* the bins of every thread, summed (the same totals for any split) */
@@ -330,6 +339,7 @@ static flow forward_flow(const job &j)
     f.arm = [&a](h2y_ctx *ctx) {
         return (a.ref && h2y_stream_compare(ctx, a.sigma, a.dst ? 1 : 0)) || (a.ssim && h2y_stream_ssim(ctx, -1)) ||
                (a.hist && h2y_stream_histogram(ctx, a.hist_bits)) || (a.light && h2y_stream_light(ctx)) ||
+               (a.dynmeta && h2y_stream_lightdist(ctx)) ||
                (a.gamut && h2y_stream_gamut(ctx, a.in.colour_primaries, a.out.colour_primaries, a.gamut_clip)) ||
                (a.scale && h2y_stream_scale(ctx, a.out.width, a.out.height, a.scale_taps));
     };
@@ -643,13 +653,46 @@ static void light_report(const std::vector<h2y_light_stats> &st)
     printf("light svt-av1 --content-light %lld,%lld\n", cll, fall);
 }
 
+/* the dynamic metadata report of the header comment, and FILE; 0, or 1 when FILE could not be written */
+static int lightdist_report(const cli_args &a, const std::vector<h2y_lightdist_stats> &st)
+{
+    auto nits = [](uint32_t bits) {
+        float l;
+        memcpy(&l, &bits, sizeof l);
+        return 10000.0 * (double)l;
+    };
+    for (size_t k = 0; k < st.size(); k++) {
+        const h2y_lightdist_stats &t = st[k];
+        printf("dynamic_metadata: frame %zu maxscl %.4f %.4f %.4f average %.4f percentiles", k, nits(t.maxscl_bits[2]), nits(t.maxscl_bits[0]),
+               nits(t.maxscl_bits[1]), ((10000.0 * (double)t.sum_q) * 0x1p-32) / (double)t.pixels);
+        for (int i = 0; i < H2Y_LIGHTDIST_PERCENTILES; i++) printf(" %.4f", nits(t.pct_bits[i]));
+        printf(" below_100 %.4f\n", 100.0 * (double)t.below_100 / (double)t.pixels);
+    }
+    std::string text(h2y_lightdist_json(st.data(), (int)st.size(), 0, nullptr, 0), '\0');
+    bool ok = !text.empty();
+    if (ok) {
+        text.resize(text.size() + 1);
+        h2y_lightdist_json(st.data(), (int)st.size(), 0, &text[0], text.size());
+        text.pop_back();
+        FILE *f = fopen(a.dynmeta, "w");
+        ok = f && fwrite(text.data(), 1, text.size(), f) == text.size();
+        if (f && fclose(f)) ok = false;
+    }
+    if (!ok) {
+        printf("ERROR: unable to write %s\n", a.dynmeta);
+        return 1;
+    }
+    printf("dynamic_metadata_written: %zu frames to %s\n", st.size(), a.dynmeta);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     job j;
     cli_args &a = j.a;
     scanned &s = j.src;
     cli_parse(a, argc, argv);
-    if ((!a.dst && !a.ref && !a.hist && !a.hist_only && !a.light && !a.scale_only) || (!a.src && a.synthetic < 0)) {
+    if ((!a.dst && !a.ref && !a.hist && !a.hist_only && !a.light && !a.dynmeta && !a.scale_only) || (!a.src && a.synthetic < 0)) {
         if (!a.help) cli_help();
         return a.help ? 0 : 1;
     }
@@ -816,5 +859,6 @@ int main(int argc, char **argv)
         if (hrc == 1 || !rc) rc = hrc;
     }
     if (ran && a.light) light_report(res.light);
+    if (ran && a.dynmeta && lightdist_report(a, res.lightdist)) rc = 1;
     return rc;
 }

@@ -351,6 +351,18 @@ int h2y_light_grid(uint32_t npix, int n_frames); /* blocks per frame */
 /* k_light over n_frames frames into acc[frame] (zeroed by the caller) */
 hipError_t h2y_launch_light(int in_kind, int grid, hipStream_t st, const light_args &a, const light_frame *frames, int n_frames, light_acc *acc);
 
+/* k_lightdist (h2y_lightdist.hip): the light distribution of the same frames (include/hdr2yuv_hip.h, h2y_lightdist_stats), with
+ * k_light's frame table and arguments */
+struct lightdist_acc { /* one frame: zeroed before k_lightdist */
+    unsigned long long sum; /* sum over pixels of rint(m x 2^32) */
+    uint32_t maxscl[3];     /* the largest L of planes G, B, R, as bits */
+    uint32_t below;         /* pixels with m <= 0.01f */
+};
+int h2y_lightdist_grid(uint32_t npix, int n_frames); /* blocks per frame */
+/* k_lightdist over n_frames frames into acc[frame] and bins[frame x H2Y_LIGHTDIST_BINS] (both zeroed by the caller) */
+hipError_t h2y_launch_lightdist(int in_kind, int grid, hipStream_t st, const light_args &a, const light_frame *frames, int n_frames,
+                                lightdist_acc *acc, uint32_t *bins);
+
 /* k_gamut (h2y_gamut.hip): the conversion between colour primaries of include/hdr2yuv_hip.h on frames of three float or half
  * planes G, B, R; dst may be src (in place) */
 struct gamut_frame {

@@ -1,5 +1,5 @@
 /*
- * h2y_measure.hip -- the measurements of the C-ABI shim: the comparison with a reference, SSIM, content light, histograms, the
+ * h2y_measure.hip -- the measurements of the C-ABI shim: the comparison with a reference, SSIM, content light, the light distribution, histograms, the
  * scaler and the conversion between colour primaries.  Each has its checks and geometry, its batch entry, its ring stage (ring_stage, h2y_shim.h), and its arm, result and
  * *_stream_open entries.
  */
@@ -390,7 +390,10 @@ static void light_finish(const light_acc &acc, uint32_t width, uint32_t npix, h2
     o->fall = ((10000.0 * (double)acc.sum) * 0x1p-32) / (double)npix;
 }
 
-int h2y_light_batch(h2y_ctx *ctx, const h2y_desc *d, int n_frames, const void *const *d_planes, h2y_light_stats *out)
+/* What h2y_light_batch and h2y_lightdist_batch share: the checks, k_light's arguments, every frame's floor and ceiling on the device
+ * (d_light_as: the descriptor's override, or pic_stats of each frame) and the frame table h */
+static int light_batch_prepare(h2y_ctx *ctx, const h2y_desc *d, int n_frames, const void *const *d_planes, const void *out, light_args &a,
+                               light_frame *&h)
 {
     if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
     if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
@@ -403,12 +406,9 @@ int h2y_light_batch(h2y_ctx *ctx, const h2y_desc *d, int n_frames, const void *c
             if (!d_planes[3 * f + c] || ((uintptr_t)d_planes[3 * f + c] & 15u))
                 return fail(ctx, H2Y_EINVAL, "input plane %d of frame %d is null or not 16-byte aligned", c, f);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    light_args a;
     rc = light_args_of(ctx, d, a);
-    light_frame *h;
     if (!rc) rc = frame_table(ctx, n_frames, h);
     if (!rc) rc = ensure(ctx, ctx->d_light_as, ctx->light_as_cap, (size_t)n_frames * sizeof(assumed_stats));
-    if (!rc) rc = ensure(ctx, ctx->d_light_acc, ctx->light_acc_cap, (size_t)n_frames * sizeof(light_acc));
     if (rc) return rc;
     if (d->stats_override) { /* the same six integers for every frame */
         std::vector<assumed_stats> as(n_frames);
@@ -422,9 +422,19 @@ int h2y_light_batch(h2y_ctx *ctx, const h2y_desc *d, int n_frames, const void *c
             if (rc) return rc;
         }
     ctx->b->dev_assumed_ok = false; /* run_stats used the batch state's scratch slot */
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_light_acc, 0, (size_t)n_frames * sizeof(light_acc), ctx->stream));
     for (int f = 0; f < n_frames; f++)
         h[f] = light_frame{{d_planes[3 * f], d_planes[3 * f + 1], d_planes[3 * f + 2]}, ctx->d_light_as + f};
+    return H2Y_OK;
+}
+
+int h2y_light_batch(h2y_ctx *ctx, const h2y_desc *d, int n_frames, const void *const *d_planes, h2y_light_stats *out)
+{
+    light_args a;
+    light_frame *h;
+    int rc = light_batch_prepare(ctx, d, n_frames, d_planes, out, a, h);
+    if (!rc) rc = ensure(ctx, ctx->d_light_acc, ctx->light_acc_cap, (size_t)n_frames * sizeof(light_acc));
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_light_acc, 0, (size_t)n_frames * sizeof(light_acc), ctx->stream));
     const int in_kind = in_kind_of(d);
     rc = timed_launches(ctx, h, n_frames, H2Y_LIGHT_FRAMES_PER_LAUNCH, "k_light", [&](const light_frame *frames, int f0, int nf) {
         return h2y_launch_light(in_kind, h2y_light_grid(a.npix, nf), ctx->stream, a, frames, nf, ctx->d_light_acc + f0);
@@ -494,6 +504,171 @@ int h2y_stream_light_result(h2y_ctx *ctx, h2y_light_stats *out)
     if (ctx->s_lent < 0) return fail(ctx, H2Y_EINVAL, "no output taken yet: h2y_stream_output first");
     light_finish(*st->ss[ctx->s_lent].h, (uint32_t)ctx->s_desc.width, st->a.npix, out);
     return H2Y_OK;
+}
+
+/* ---- light distribution (ST 2094-40 dynamic metadata) of a forward conversion to PQ ------------------------------------------- */
+
+/* A workspace of nf frames: k_lightdist's accumulators, then the bins (both zeroed before a launch) */
+struct lightdist_layout {
+    size_t bins, total;
+};
+static lightdist_layout lightdist_layout_of(int nf)
+{
+    lightdist_layout L;
+    L.bins = ((size_t)nf * sizeof(lightdist_acc) + 255) & ~(size_t)255;
+    L.total = L.bins + (size_t)nf * H2Y_LIGHTDIST_BINS * sizeof(uint32_t);
+    return L;
+}
+
+/* the stats of one frame of npix pixels from its accumulator and its bins: the finishing step runs here, on the host */
+static void lightdist_finish(const lightdist_acc &acc, const uint32_t *bins, uint32_t npix, h2y_lightdist_stats *o)
+{
+    static const uint32_t kPct[H2Y_LIGHTDIST_PERCENTILES] = H2Y_LIGHTDIST_PCT;
+    *o = h2y_lightdist_stats{};
+    for (int c = 0; c < 3; c++) o->maxscl_bits[c] = acc.maxscl[c];
+    o->max_bits = std::max(acc.maxscl[0], std::max(acc.maxscl[1], acc.maxscl[2]));
+    o->sum_q = acc.sum;
+    o->pixels = npix;
+    o->below_100 = acc.below;
+    uint64_t cum = 0;
+    int i = 0;
+    for (uint32_t k = 0; k < H2Y_LIGHTDIST_BINS && i < H2Y_LIGHTDIST_PERCENTILES; k++) {
+        cum += bins[k];
+        for (; i < H2Y_LIGHTDIST_PERCENTILES && cum * 10000u >= (uint64_t)kPct[i] * npix; i++)
+            o->pct_bits[i] = k ? H2Y_LIGHTDIST_FIRST_BITS + ((k - 1u) << 14) : 0u;
+    }
+}
+
+static std::string lightdist_variant(const h2y_desc *d, const light_args &a)
+{
+    return "k_lightdist" + light_variant(d, a).substr(strlen("k_light"));
+}
+
+int h2y_lightdist_batch(h2y_ctx *ctx, const h2y_desc *d, int n_frames, const void *const *d_planes, h2y_lightdist_stats *out,
+                        uint32_t *bins_out)
+{
+    light_args a;
+    light_frame *h;
+    int rc = light_batch_prepare(ctx, d, n_frames, d_planes, out, a, h);
+    const lightdist_layout L = lightdist_layout_of(n_frames > 0 ? n_frames : 1);
+    if (!rc) rc = ensure(ctx, ctx->d_lightdist, ctx->lightdist_cap, L.total);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_lightdist, 0, L.total, ctx->stream));
+    lightdist_acc *d_acc = reinterpret_cast<lightdist_acc *>(ctx->d_lightdist);
+    uint32_t *d_bins = reinterpret_cast<uint32_t *>(ctx->d_lightdist + L.bins);
+    const int in_kind = in_kind_of(d);
+    rc = timed_launches(ctx, h, n_frames, H2Y_LIGHTDIST_FRAMES_PER_LAUNCH, "k_lightdist", [&](const light_frame *frames, int f0, int nf) {
+        return h2y_launch_lightdist(in_kind, h2y_lightdist_grid(a.npix, nf), ctx->stream, a, frames, nf, d_acc + f0,
+                                    d_bins + (size_t)f0 * H2Y_LIGHTDIST_BINS);
+    });
+    if (rc) return rc;
+    std::vector<lightdist_acc> acc(n_frames);
+    std::vector<uint32_t> own(bins_out ? 0 : (size_t)n_frames * H2Y_LIGHTDIST_BINS);
+    uint32_t *bins = bins_out ? bins_out : own.data();
+    HIP_TRY(ctx, hipMemcpy(acc.data(), d_acc, (size_t)n_frames * sizeof(lightdist_acc), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(bins, d_bins, (size_t)n_frames * H2Y_LIGHTDIST_BINS * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (int f = 0; f < n_frames; f++) lightdist_finish(acc[f], bins + (size_t)f * H2Y_LIGHTDIST_BINS, a.npix, out + f);
+    ctx->last_variant = lightdist_variant(d, a);
+    return H2Y_OK;
+}
+
+/* The light distribution's ring stage, on what content light's stage sees: k_light's arguments and table entry per slot, and the
+ * frame's workspace (lightdist_layout of one frame) on the device and pinned */
+struct lightdist_stage : ring_stage {
+    struct slot {
+        char *d = nullptr, *h = nullptr;
+    };
+    std::vector<slot> ss;
+    light_args a{};
+    light_frame *tab = nullptr;
+    int run(h2y_ctx *ctx, int k) override
+    {
+        const lightdist_layout L = lightdist_layout_of(1);
+        HIP_TRY(ctx, hipMemsetAsync(ss[k].d, 0, L.total, ctx->stream));
+        HIP_TRY(ctx, h2y_launch_lightdist(in_kind_of(&ctx->s_desc), h2y_lightdist_grid(a.npix, 1), ctx->stream, a, tab + k, 1,
+                                          reinterpret_cast<lightdist_acc *>(ss[k].d), reinterpret_cast<uint32_t *>(ss[k].d + L.bins)));
+        return H2Y_OK;
+    }
+    int download(h2y_ctx *ctx, int k) override
+    {
+        HIP_TRY(ctx, hipMemcpyAsync(ss[k].h, ss[k].d, lightdist_layout_of(1).total, hipMemcpyDeviceToHost, ctx->s_d2h));
+        return H2Y_OK;
+    }
+};
+
+int h2y_stream_lightdist(h2y_ctx *ctx)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    if (ctx->s_kind != h2y_ctx::RING_FORWARD) return fail(ctx, H2Y_EINVAL, "the light distribution is measured on the forward rings only");
+    if (ctx->s_stage[STAGE_LIGHTDIST]) return fail(ctx, H2Y_EINVAL, "the ring measures the light distribution already");
+    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    const h2y_desc *d = &ctx->s_desc;
+    int rc = light_check(ctx, d);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    auto st = std::make_unique<lightdist_stage>();
+    rc = light_args_of(ctx, d, st->a);
+    if (rc) return rc;
+    const int depth = (int)ctx->ss.size();
+    const lightdist_layout L = lightdist_layout_of(1);
+    std::vector<light_frame> tab(depth);
+    st->ss.resize(depth);
+    for (int k = 0; k < depth; k++) {
+        for (int c = 0; c < 3; c++) tab[k].in[c] = ctx->ss[k].d_in + c * ctx->s_plane_al;
+        tab[k].assumed = ctx->b->d_assumed;
+        st->dev_alloc(st->ss[k].d, L.total);
+        st->pin_alloc(st->ss[k].h, L.total);
+    }
+    st->table(st->tab, tab);
+    return stage_arm(ctx, STAGE_LIGHTDIST, std::move(st), "light distribution");
+}
+
+int h2y_stream_lightdist_result(h2y_ctx *ctx, h2y_lightdist_stats *out)
+{
+    if (!ctx || !out) return fail(ctx, H2Y_EINVAL, "null argument");
+    const lightdist_stage *st = ctx->streaming ? stage_of<lightdist_stage>(ctx, STAGE_LIGHTDIST) : nullptr;
+    if (!st) return fail(ctx, H2Y_EINVAL, "no stream open that measures the light distribution");
+    if (ctx->s_lent < 0) return fail(ctx, H2Y_EINVAL, "no output taken yet: h2y_stream_output first");
+    const char *h = st->ss[ctx->s_lent].h;
+    lightdist_finish(*reinterpret_cast<const lightdist_acc *>(h), reinterpret_cast<const uint32_t *>(h + lightdist_layout_of(1).bins), st->a.npix, out);
+    return H2Y_OK;
+}
+
+/* 0.1 cd/m2 of a light L in [0, 1] given as bits: rint(100000 x (double)L), half to even */
+static long lightdist_units(uint32_t bits) { return lrint(100000.0 * (double)bits2f(bits)); }
+
+size_t h2y_lightdist_json(const h2y_lightdist_stats *stats, int n_frames, long first_frame_index, char *buf, size_t cap)
+{
+    if (!stats || n_frames < 1 || first_frame_index < 0) return 0;
+    for (int k = 0; k < n_frames; k++)
+        if (!stats[k].pixels) return 0;
+    std::string s = "{\"JSONInfo\": {\"HDR10plusProfile\": \"A\", \"Version\": \"1.0\"},\n\"SceneInfo\": [\n";
+    char line[1024];
+    for (int k = 0; k < n_frames; k++) {
+        const h2y_lightdist_stats &t = stats[k];
+        const long avg = lrint(((100000.0 * (double)t.sum_q) * 0x1p-32) / (double)t.pixels);
+        const long share = (long)(100u * t.below_100 / t.pixels);
+        const uint32_t *p = t.pct_bits; /* 1, 5, 10, 25, 50, 75, 90, 95, 99, 99.98 % */
+        snprintf(line, sizeof line,
+                 "{\"LuminanceParameters\": {\"AverageRGB\": %ld, \"LuminanceDistributions\": {\"DistributionIndex\": [1, 5, 10, 25, 50, 75, 90, "
+                 "95, 99], \"DistributionValues\": [%ld, %ld, %ld, %ld, %ld, %ld, %ld, %ld, %ld]}, \"MaxScl\": [%ld, %ld, %ld]}, "
+                 "\"NumberOfWindows\": 1, \"TargetedSystemDisplayMaximumLuminance\": 400, \"SceneFrameIndex\": %d, \"SceneId\": 0, "
+                 "\"SequenceFrameIndex\": %ld}%s\n",
+                 avg, lightdist_units(p[0]), lightdist_units(p[9]), share, lightdist_units(p[3]), lightdist_units(p[4]), lightdist_units(p[5]),
+                 lightdist_units(p[6]), lightdist_units(p[7]), lightdist_units(p[8]), lightdist_units(t.maxscl_bits[2]),
+                 lightdist_units(t.maxscl_bits[0]), lightdist_units(t.maxscl_bits[1]), k, first_frame_index + k, k + 1 < n_frames ? "," : "");
+        s += line;
+    }
+    snprintf(line, sizeof line, "],\n\"SceneInfoSummary\": {\"SceneFirstFrameIndex\": [%ld], \"SceneFrameNumbers\": [%d]},\n"
+             "\"ToolInfo\": {\"Tool\": \"hdr2yuv\", \"Version\": \"1.0\"}}\n", first_frame_index, n_frames);
+    s += line;
+    if (buf && cap) {
+        const size_t n = std::min(s.size(), cap - 1);
+        memcpy(buf, s.data(), n);
+        buf[n] = 0;
+    }
+    return s.size();
 }
 
 /* ---- code-value histograms and the legal-range check (hdr2yuv.cpp:658, :797) ---------------------------------------------- */

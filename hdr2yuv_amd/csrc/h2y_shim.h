@@ -181,7 +181,7 @@ struct ring_stage {
     virtual int run(h2y_ctx *ctx, int slot) = 0;          /* on the context's stream, after the frame was produced */
     virtual int download(h2y_ctx *, int) { return H2Y_OK; } /* the result, on s_d2h after the slot's ev_conv */
 };
-enum stage_id { STAGE_GAMUT, STAGE_LIGHT, STAGE_COMPARE, STAGE_SSIM, STAGE_HISTOGRAM, STAGE_SCALE, STAGE_COUNT };
+enum stage_id { STAGE_GAMUT, STAGE_LIGHT, STAGE_LIGHTDIST, STAGE_COMPARE, STAGE_SSIM, STAGE_HISTOGRAM, STAGE_SCALE, STAGE_COUNT };
 
 struct h2y_ctx {
     int device = 0;
@@ -258,6 +258,9 @@ struct h2y_ctx {
     size_t light_as_cap = 0;
     light_acc *d_light_acc = nullptr;
     size_t light_acc_cap = 0;
+    /* h2y_lightdist_batch's device workspace: per launch k_lightdist's accumulators, then the bins (lightdist_layout) */
+    char *d_lightdist = nullptr;
+    size_t lightdist_cap = 0;
     /* h2y_scale_batch's tap tables on the device */
     char *d_scale_tabs = nullptr;
     size_t scale_tabs_cap = 0;

@@ -649,6 +649,71 @@ int h2y_stream_light(h2y_ctx *ctx);
 /* The light of the frame that h2y_stream_output returned last. */
 int h2y_stream_light_result(h2y_ctx *ctx, h2y_light_stats *out);
 
+/* ---- light distribution (SMPTE ST 2094-40, "HDR10+" dynamic metadata) of a forward conversion to PQ ------------------------------
+ * A second measurement on the samples of the content-light section above, in its scope, word for word: dst_transfer 16, a source
+ * transfer the conversion linearises (8, 18, 1/6/14/15), src_matrix 0; anything else is H2Y_EUNSUPPORTED.
+ *   per sample  L_c as above: normalised with the frame's floor and ceiling, through the source transfer by the conversion's own
+ *               tiers, a NaN as 0, clamped to [+0, 1].
+ *   per pixel   m = max(L_G, L_B, L_R)
+ *   per frame, all exact integers, independent of the order of the work:
+ *     maxscl_bits[c]  the largest L_c of plane c (0 G, 1 B, 2 R) as a binary32 bit pattern (L >= +0 orders as its bits)
+ *     max_bits        the largest m = the largest of the three maxscl_bits; sum_q = sum over the pixels of rint(m x 2^32) (half to
+ *                     even) in uint64; pixels = width x height: h2y_light_stats' figures, equal to h2y_light_batch's on the same frame
+ *     below_100       the pixels with m <= 0.01f (bits 0x3C23D70A: 100 cd/m2)
+ *     the histogram   H2Y_LIGHTDIST_BINS = 8706 uint32 bins of m by its bit pattern e: bin 0 when e < 0x37000000 (m < 2^-17, below
+ *                     0.08 cd/m2), otherwise bin = ((e - 0x37000000) >> 14) + 1: 512 bins per binade (0.2 % wide) over the 17
+ *                     binades [2^-17, 1), bins 1..8704; m = 1 alone lands in bin 8705
+ *     pct_bits[i]     for p = H2Y_LIGHTDIST_PCT[i] hundredths of a percent (1, 5, 10, 25, 50, 75, 90, 95, 99 and 99.98 %): the
+ *                     percentile's bin is the smallest k with cum(k) x 10000 >= p x pixels (uint64; cum(k) the count in bins 0..k),
+ *                     and pct_bits[i] that bin's lower edge as binary32 bits: 0 for bin 0, 0x37000000 + ((k - 1) << 14) otherwise.
+ *                     A percentile never exceeds max_bits; a 1 x 1 frame returns its own bin's edge for every p.
+ * k_lightdist counts the bins on the device; the percentiles are found on the host from the downloaded bins.
+ * Units of the HDR10+ file are 0.1 cd/m2 as integers: u(L) = rint(100000 x (double)L), half to even, 0..100000; the average is
+ * rint(((100000 x (double)sum_q) x 2^-32) / pixels), in fall's order of operations. */
+#define H2Y_LIGHTDIST_BINS 8706
+#define H2Y_LIGHTDIST_FIRST_BITS 0x37000000u /* 2^-17: the lower edge of bin 1 */
+#define H2Y_LIGHTDIST_PERCENTILES 10
+#define H2Y_LIGHTDIST_PCT {100, 500, 1000, 2500, 5000, 7500, 9000, 9500, 9900, 9998}
+#define H2Y_LIGHTDIST_FRAMES_PER_LAUNCH 64
+
+typedef struct h2y_lightdist_stats {
+    uint32_t maxscl_bits[3]; /* the largest L of planes G, B, R, as binary32 bits */
+    uint32_t max_bits;       /* the largest m of the frame */
+    uint64_t sum_q;          /* sum over the pixels of rint(m x 2^32) */
+    uint64_t pixels;         /* width x height */
+    uint64_t below_100;      /* pixels with m <= 0.01f */
+    uint32_t pct_bits[H2Y_LIGHTDIST_PERCENTILES]; /* the percentiles' bin edges, as binary32 bits */
+} h2y_lightdist_stats;
+
+/* The light distribution of n_frames device frames of d: planes, alignment and floor / ceiling (stats_override, or k_stats run
+ * here) exactly as h2y_light_batch takes them.  out[f] (host memory); bins_out may be NULL, otherwise it receives n_frames x
+ * H2Y_LIGHTDIST_BINS uint32.  Launches of up to H2Y_LIGHTDIST_FRAMES_PER_LAUNCH frames (h2y_last_kernel_ms sums them,
+ * h2y_last_kernel_name "k_lightdist"); synchronous. */
+int h2y_lightdist_batch(h2y_ctx *ctx, const h2y_desc *d, int n_frames, const void *const *d_planes, h2y_lightdist_stats *out,
+                        uint32_t *bins_out);
+
+/* Arm an open forward ring before its first input, beside any other stage (after h2y_stream_gamut it sees the converted planes):
+ * k_lightdist then runs on every frame's decoded planes, on the kernel stream after the conversion, with the floor and ceiling the
+ * conversion used; the output bytes and every other stage's results do not change.  H2Y_EUNSUPPORTED / H2Y_EINVAL exactly where
+ * h2y_stream_light returns them. */
+int h2y_stream_lightdist(h2y_ctx *ctx);
+/* The light distribution of the frame that h2y_stream_output returned last. */
+int h2y_stream_lightdist_result(h2y_ctx *ctx, h2y_lightdist_stats *out);
+
+/* The HDR10+ JSON (the file x265 takes as --dhdr10-info) of n_frames frames in one scene, SceneId 0, the first of them frame
+ * first_frame_index of the sequence.  Host only: no device, no context.  Writes at most cap - 1 bytes and a terminating 0 into buf
+ * (buf may be NULL when cap is 0) and returns the bytes the whole text needs, the terminator not counted; 0 for a null stats, n_frames
+ * < 1, a negative first_frame_index or a frame without pixels.  Layout, one SceneInfo entry per frame and line:
+ *   {"JSONInfo": {"HDR10plusProfile": "A", "Version": "1.0"}, "SceneInfo": [ENTRY, ...],
+ *    "SceneInfoSummary": {"SceneFirstFrameIndex": [first], "SceneFrameNumbers": [n]}, "ToolInfo": {"Tool": "hdr2yuv", "Version": "1.0"}}
+ *   ENTRY = {"LuminanceParameters": {"AverageRGB": A, "LuminanceDistributions": {"DistributionIndex": [1, 5, 10, 25, 50, 75, 90, 95, 99],
+ *            "DistributionValues": [9 integers]}, "MaxScl": [R, G, B]}, "NumberOfWindows": 1,
+ *            "TargetedSystemDisplayMaximumLuminance": 400, "SceneFrameIndex": k, "SceneId": 0, "SequenceFrameIndex": first + k}
+ * in 0.1 cd/m2 (u(L) above).  The DistributionValues slots follow the HDR10+ convention: slot "1" and slots "25".."99" carry those
+ * percentiles, slot "5" the 99.98th percentile, slot "10" the whole percentage of pixels at or below 100 cd/m2,
+ * floor(100 x below_100 / pixels).  The layout is written from x265's documentation; no encoder's parser has checked it. */
+size_t h2y_lightdist_json(const h2y_lightdist_stats *stats, int n_frames, long first_frame_index, char *buf, size_t cap);
+
 /* ---- scaling: an exact Lanczos resampler (--dst_pic_width / --dst_pic_height; the reference's cv.cpp is compiled out) ------------
  * The reference plugs a per-plane Lanczos cv::resize in at hdr2yuv.cpp:892-896, in a file that does not compile; it defines no
  * bytes.  This is the project's own definition, in integers, so that a restatement checks every output byte.
@@ -825,7 +890,7 @@ int h2y_upsample_444_sited(h2y_ctx *ctx, int width, int height, int chroma_sampl
                            const uint16_t *d_src, uint16_t *d_dst);
 
 /* Timing of the last h2y_convert_batch*() (or h2y_inverse_*, h2y_dpx_decode_batch, h2y_tiff_decode_batch,
- * h2y_rgb_interleave_batch, h2y_exr_decode_batch, h2y_compare_batch, h2y_ssim_batch, h2y_light_batch, h2y_scale_batch, h2y_gamut_batch) call measured with HIP events on
+ * h2y_rgb_interleave_batch, h2y_exr_decode_batch, h2y_compare_batch, h2y_ssim_batch, h2y_light_batch, h2y_lightdist_batch, h2y_scale_batch, h2y_gamut_batch) call measured with HIP events on
  * the stream the kernels ran on: total ms over the main kernels and how many
  * launches that covered. */
 int h2y_last_kernel_ms(const h2y_ctx *ctx, float *ms, int *launches);

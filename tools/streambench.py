@@ -75,6 +75,16 @@ Prints one line per figure, then one JSON line with all of them.
      4:2:0, unarmed and armed with h2y_stream_light.
 Prints one line per figure, then one JSON line with all of them.
 
+`streambench.py lightdist`: the light distribution (HDR10+ dynamic metadata) on 4K frames, in one job:
+  1. h2y_lightdist_batch (k_lightdist) beside h2y_light_batch (k_light, the yardstick: it reads the same bytes) over the same 64
+     distinct device frames per call, five calls each taken in turn after a warm-up (HIP events round the launch; floor and ceiling
+     given, so no k_stats runs; the one memset that zeroes a call's accumulators -- 2.2 MB of bins for k_lightdist, 1 KB for k_light
+     -- lies before the first event): the median and spread in us per frame, the ratio to k_light, and the bytes per frame over
+     that time as a share of the 8 TB/s HBM peak, for F32, F16 and U16 LINEAR sources and an F32 BT.1886 source, on noise;
+  2. the same on a constant and on a letterboxed F32 picture (the flat-run path: whole waves in one bin);
+  3. frames/s from host memory of the .f32 ring to PQ BT.2020nc 10-bit 4:2:0, unarmed and armed with h2y_stream_lightdist.
+Prints one line per figure, then one JSON line with all of them.
+
 `streambench.py scale`: the Lanczos resampler:
   1. the kernel time of h2y_scale_batch (k_scale) over 64 distinct device frames per call (HIP events, median of five after a
      warm-up call), the bytes per frame -- the source read once plus the output written -- over that time and their share of the
@@ -954,6 +964,106 @@ def light_main():
     print(json.dumps({"streambench_light": res}), flush=True)
 
 
+def lightdist_main():
+    import json
+
+    import torch
+
+    w, hh, nb, reps = 3840, 2160, 64, 5
+    n = w * hh
+    nf = int(os.environ.get("N", "60"))
+    depth = 3
+    rng = np.random.default_rng(29)
+    ctx = h.Context(0)
+    res = {"width": w, "height": hh, "frames_per_call": nb, "reps": reps, "ring_frames": nf, "ring_depth": depth, "hbm_peak_tbs": 8.0}
+
+    def noise(dt):
+        return lambda: [torch.rand(n, device="cuda").to(dt) for _ in range(3)]
+
+    def codes():
+        return [torch.randint(0, 65536, (n,), dtype=torch.int32, device="cuda").to(torch.int16) for _ in range(3)]
+
+    def constant():
+        return [torch.full((n,), 0.25, dtype=torch.float32, device="cuda") for _ in range(3)]
+
+    def letterbox():  # a 2.39:1 picture in a 16:9 frame: black bars above and below
+        bar = (hh - int(w / 2.39)) // 2 * w
+        planes = noise(torch.float32)()
+        for p in planes:
+            p[:bar] = 0.0
+            p[n - bar:] = 0.0
+        return planes
+
+    # 1. and 2.: k_lightdist beside k_light on the same 64 device frames, the calls taken in turn
+    F32, F16, U16 = h.SAMPLE_F32, h.SAMPLE_F16, h.SAMPLE_U16
+    for name, sample, src_transfer, depth_in, make in (("f32", F32, 8, 32, noise(torch.float32)), ("f16", F16, 8, 32, noise(torch.float16)),
+                                                       ("u16", U16, 8, 16, codes), ("f32_bt1886", F32, 1, 32, noise(torch.float32)),
+                                                       ("f32_constant", F32, 8, 32, constant), ("f32_letterbox", F32, 8, 32, letterbox)):
+        d = h.make_desc(w, hh, sample=sample, src_depth=depth_in, dst_depth=10, src_transfer=src_transfer, dst_transfer=16,
+                        dst_matrix=h.MATRIX_BT2020NC, resampler=0, stats=[(0, 1 if sample != U16 else 65535)] * 3)
+        frames = [make() for _ in range(nb)]
+        torch.cuda.synchronize()
+        light, dist = [], []
+        for rep in range(reps + 1):  # rep 0 warms up
+            ctx.light_batch(d, frames)
+            if rep:
+                light.append(ctx.last_kernel_ms()[0] / nb)
+            ctx.lightdist_batch(d, frames)
+            if rep:
+                dist.append(ctx.last_kernel_ms()[0] / nb)
+        variant = ctx.last_kernel_variant()
+        l_ms, d_ms = float(np.median(light)), float(np.median(dist))
+        nbytes = 3 * n * (4 if sample == F32 else 2)
+        tbs = nbytes / (d_ms * 1e-3) / 1e12
+        res[f"k_lightdist_{name}"] = dict(kernel_us_per_frame=round(d_ms * 1e3, 2), min_us=round(min(dist) * 1e3, 2), max_us=round(max(dist) * 1e3, 2),
+                                          k_light_us_per_frame=round(l_ms * 1e3, 2), k_light_min_us=round(min(light) * 1e3, 2),
+                                          k_light_max_us=round(max(light) * 1e3, 2), ratio_to_k_light=round(d_ms / l_ms, 3),
+                                          bytes_per_frame=nbytes, kernel_tbs=round(tbs, 2), hbm_peak_fraction=round(tbs / 8.0, 3), variant=variant)
+        print(f"k_lightdist {name:13s} {nb} frames per call: {d_ms*1e3:6.2f} us/frame ({min(dist)*1e3:.2f}..{max(dist)*1e3:.2f})  k_light "
+              f"{l_ms*1e3:6.2f} us/frame ({min(light)*1e3:.2f}..{max(light)*1e3:.2f})  ratio {d_ms/l_ms:5.3f}  {tbs:5.2f} TB/s = "
+              f"{tbs/8.0*100:4.1f} % of 8 TB/s", flush=True)
+        del frames
+        torch.cuda.empty_cache()
+
+    # 3. the .f32 ring, unarmed and armed
+    def ring(arm):
+        ctx.stream_open(d32, depth)
+        if arm:
+            ctx.stream_lightdist()
+        inflight = 0
+        t0 = time.perf_counter()
+
+        def take():
+            ctx.stream_output()
+            if arm:
+                ctx.stream_lightdist_result()
+
+        for _ in range(nf):
+            slot = ctx.stream_input()
+            for c in range(3):
+                slot[c][:] = planes[c]
+            ctx.stream_submit()
+            inflight += 1
+            if inflight == depth - 1:
+                take()
+                inflight -= 1
+        while inflight:
+            take()
+            inflight -= 1
+        dt = (time.perf_counter() - t0) / nf
+        ctx.stream_close()
+        return dt
+
+    d32 = h.make_desc(w, hh, dst_depth=10, dst_matrix=h.MATRIX_BT2020NC, resampler=1)
+    planes = [rng.random(n, dtype=np.float32) for _ in range(3)]
+    ring(False)  # warm-up
+    t_plain, t_armed = ring(False), ring(True)
+    res["f32_ring"] = dict(unarmed_fps=round(1 / t_plain, 1), armed_fps=round(1 / t_armed, 1), armed_share=round(t_plain / t_armed, 3))
+    print(f"f32 ring from host memory: unarmed {1/t_plain:6.1f} frames/s   armed {1/t_armed:6.1f} frames/s ({t_plain/t_armed*100:5.1f} %)", flush=True)
+    ctx.close()
+    print(json.dumps({"streambench_lightdist": res}), flush=True)
+
+
 def scale_main():
     import json
 
@@ -1269,5 +1379,7 @@ if __name__ == "__main__":
         ssim_main()
     elif sys.argv[1:] == ["light"]:
         light_main()
+    elif sys.argv[1:] == ["lightdist"]:
+        lightdist_main()
     else:
         main()
