@@ -10,6 +10,8 @@ a :class:`Context` needs a HIP device and the built library.
 from .api import (  # noqa: F401
     CHROMA_420,
     CHROMA_444,
+    CODELIGHT_FRAMES_PER_LAUNCH,
+    H2YCodelightDesc,
     H2YCompareStats,
     H2YDesc,
     H2YDpxInfo,
@@ -45,6 +47,7 @@ from .api import (  # noqa: F401
     library_path,
     lightdist_json,
     load_library,
+    make_codelight_desc,
     make_desc,
     parse_dpx,
     parse_exr,

@@ -38,6 +38,7 @@ EXPORTS = [
     "h2y_histogram_stream_open", "h2y_ssim_batch", "h2y_stream_ssim", "h2y_stream_ssim_result",
     "h2y_light_batch", "h2y_stream_light", "h2y_stream_light_result",
     "h2y_lightdist_batch", "h2y_stream_lightdist", "h2y_stream_lightdist_result", "h2y_lightdist_json",
+    "h2y_codelight_batch", "h2y_codelight_stream_open",
     "h2y_scale_taps", "h2y_scale_frame_bytes", "h2y_scale_batch", "h2y_stream_scale", "h2y_scale_stream_open",
     "h2y_gamut_matrix", "h2y_gamut_batch", "h2y_stream_gamut",
     "h2y_ctx_set_chroma_siting", "h2y_subsample_420_sited",
@@ -52,6 +53,7 @@ LIGHTDIST_FRAMES_PER_LAUNCH = 64
 LIGHTDIST_BINS = 8706  # bins of max(L_G, L_B, L_R) by its binary32 bits: below 2^-17, 512 per binade up to 1, and 1 itself
 LIGHTDIST_FIRST_BITS = 0x37000000  # 2^-17: the lower edge of bin 1
 LIGHTDIST_PCT = (100, 500, 1000, 2500, 5000, 7500, 9000, 9500, 9900, 9998)  # the percentiles, in hundredths of a percent
+CODELIGHT_FRAMES_PER_LAUNCH = 8  # a launch's 4:2:0 scratch stays at 253 MiB for 3840 x 2160
 SCALE_FRAMES_PER_LAUNCH = 64
 GAMUT_FRAMES_PER_LAUNCH = 64
 SCALE_TAPS = 32  # coefficients per row of scale_taps' table
@@ -218,6 +220,18 @@ class H2YLightdistStats(C.Structure):
 
     def __repr__(self):
         return f"H2YLightdistStats({self.as_dict()})"
+
+
+class H2YCodelightDesc(C.Structure):
+    """h2y_codelight_desc: frames of three u16 PQ code planes whose light codelight_batch and codelight_stream_open measure --
+    matrix_coeffs 0 (G, B, R), 1 (BT.709) or 9 (BT.2020nc); chroma_format_idc 3, or 1 with even sizes; algorithm: the 4:2:0
+    upsampler (0 replication, otherwise the FIR the context's inverse chroma siting selects)."""
+
+    _fields_ = [(n, C.c_int) for n in ("width", "height", "chroma_format_idc", "bit_depth", "full_range", "matrix_coeffs", "algorithm")]
+
+
+def make_codelight_desc(width, height, chroma=3, bit_depth=10, full_range=0, matrix=9, algorithm=1) -> H2YCodelightDesc:
+    return H2YCodelightDesc(width, height, chroma, bit_depth, full_range, matrix, algorithm)
 
 
 def make_desc(width, height, *, sample=SAMPLE_F32, src_depth=32, dst_depth=10, src_transfer=TRANSFER_LINEAR,
@@ -420,6 +434,11 @@ def load_library():
     L.h2y_stream_lightdist.restype = C.c_int
     L.h2y_stream_lightdist_result.argtypes = [C.c_void_p, C.POINTER(H2YLightdistStats)]
     L.h2y_stream_lightdist_result.restype = C.c_int
+    L.h2y_codelight_batch.argtypes = [C.c_void_p, C.POINTER(H2YCodelightDesc), C.c_int, C.POINTER(C.c_void_p), C.POINTER(H2YLightStats),
+                                      C.POINTER(H2YLightdistStats), C.c_void_p]
+    L.h2y_codelight_batch.restype = C.c_int
+    L.h2y_codelight_stream_open.argtypes = [C.c_void_p, C.POINTER(H2YCodelightDesc), C.c_int, C.c_int]
+    L.h2y_codelight_stream_open.restype = C.c_int
     L.h2y_lightdist_json.argtypes = [C.POINTER(H2YLightdistStats), C.c_int, C.c_long, C.c_char_p, C.c_size_t]
     L.h2y_lightdist_json.restype = C.c_size_t
     L.h2y_scale_taps.argtypes = [C.c_int] * 3 + [C.c_void_p] * 3 + [C.POINTER(C.c_int)]
@@ -876,6 +895,30 @@ class Context:
         b = np.zeros((max(n, 1), LIGHTDIST_BINS), dtype=np.uint32) if bins else None
         self._check(self.lib.h2y_lightdist_batch(self.h, C.byref(d), n, ins, out, b.ctypes.data if bins else None))
         return (list(out[:n]), b[:n]) if bins else list(out[:n])
+
+    def codelight_batch(self, d: H2YCodelightDesc, frames, dist: bool = False, bins: bool = False):
+        """k_codelight on device frames of PQ codes (tensors or pointers, each frame's planes contiguous from a 16-byte aligned
+        base): a list of H2YLightStats; with dist also a list of H2YLightdistStats, with bins also the uint32 (n, LIGHTDIST_BINS)
+        histograms -- (light, dist or None, bins or None) when either is asked for."""
+        n = len(frames)
+        pf = (C.c_void_p * max(n, 1))(*[self._ptr(x) for x in frames])
+        out = (H2YLightStats * max(n, 1))()
+        dout = (H2YLightdistStats * max(n, 1))() if dist else None
+        b = np.zeros((max(n, 1), LIGHTDIST_BINS), dtype=np.uint32) if bins else None
+        self._check(self.lib.h2y_codelight_batch(self.h, C.byref(d), n, pf, out, dout, b.ctypes.data if bins else None))
+        if not dist and not bins:
+            return list(out[:n])
+        return list(out[:n]), (list(dout[:n]) if dist else None), (b[:n] if bins else None)
+
+    def codelight_stream_open(self, d: H2YCodelightDesc, want_dist=0, depth=3) -> None:
+        """A ring that only measures light: stream_input lends the frame's three planes, stream_output returns None,
+        stream_light_result (and with want_dist stream_lightdist_result) the frame's figures."""
+        self._check(self.lib.h2y_codelight_stream_open(self.h, C.byref(d), int(want_dist), depth))
+        nc = (d.width >> 1) * (d.height >> 1) if d.chroma_format_idc == CHROMA_420 else d.width * d.height
+        self._stream_inverse = None
+        self._stream_dpx = None
+        self._stream_rgb = False
+        self._stream_cmp_planes = (d.width * d.height, nc, nc)
 
     def scale_batch(self, src_w, src_h, dst_w, dst_h, chroma, bit_depth, full_range, gbr, a, frames_src, frames_dst) -> None:
         """k_scale on device frames (tensors or pointers, each frame's planes contiguous from a 16-byte aligned base):

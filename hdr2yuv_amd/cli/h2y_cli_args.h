@@ -89,6 +89,16 @@
  *             --dst_filename, beside --ref_filename, --ssim and --histogram.  Refused (exit 1, also under --dry_run): any other
  *             value (1 is replication's siting), 2 with --chroma_resampler_type 0, 2 with --src_chroma_format_idc 3, every forward
  *             flow, --compare_only 1, --histogram_only 1 and --scale_only 1.
+ * --light_only 1 (an addition): the light of a finished PQ master, from its codes, without a conversion (include/hdr2yuv_hip.h, "light
+ *             of PQ code planes", states every step): MaxCLL / MaxFALL of a .yuv (--src_chroma_format_idc 1 or 3, --src_matrix_coeffs
+ *             0, 1 or 9) or a .rgb (4:4:4, matrix 0) read as --histogram_only reads it, with --src_bit_depth 8..16, the source range
+ *             flag and --src_transfer_characteristics 16; it prints the lines --content_light 1 prints and, with --dynamic_metadata
+ *             FILE, the dynamic_metadata: lines and the HDR10+ JSON.  4:2:0 chroma is upsampled as the .yuv -> RGB flow does it:
+ *             --chroma_resampler_type 0 replication, otherwise the FIR, with --src_chroma_sample_loc_type 2 its top-left form.  Any
+ *             --gpus gives the same lines and FILE.  Refused (exit 1, also under --dry_run): a value other than 0 or 1, a transfer
+ *             other than 16, any other matrix, matrix 0 with 4:2:0, 4:2:2, a source that is not .yuv / .rgb, --dst_filename,
+ *             --ref_filename, --histogram, --ssim, --scale, --gamut_convert, --content_light or another *_only flag beside it, and
+ *             --src_chroma_sample_loc_type 2 with --chroma_resampler_type 0 or with 4:4:4.
  * Only user_args_t.chroma_resampler_type has no defined default there (never initialised): FIR here, as in
  * make.sh's example.  The reference calls exit(0) on its argument errors; this program returns 1.
  */
@@ -154,6 +164,9 @@ struct cli_args {
     /* scaling: --scale 1 (the forward flow's frames), --scale_only 1 (a .yuv or .rgb, no conversion), --scale_taps (lobes) */
     int scale = 0, scale_only = 0, scale_taps = 3;
     bool scale_given = false, scale_taps_given = false;
+    /* --light_only 1: the light of a PQ .yuv or .rgb from its codes, no conversion */
+    int light_only = 0;
+    bool light_only_given = false;
     std::vector<int> devices;
     /* resolved */
     int in_type = CLI_IN_NONE, out_type = CLI_OUT_NONE;
@@ -213,6 +226,9 @@ static inline void cli_help()
            "  --dst_filename nothing is written)\n"
            "  dynamic metadata: [--dynamic_metadata FILE] (HDR10+, SMPTE ST 2094-40: per frame maxSCL, the average and percentiles of\n"
            "  max(R,G,B) of a conversion to PQ, written to FILE as the JSON of x265 --dhdr10-info)\n"
+           "  light of a PQ master: [--light_only 1] (--src_filename, a PQ .yuv -- 4:2:0 or 4:4:4, --src_matrix_coeffs 1 or 9 -- or .rgb,\n"
+           "  --src_transfer_characteristics 16: MaxCLL / MaxFALL from its codes, no conversion; with --dynamic_metadata FILE the HDR10+\n"
+           "  JSON too; --src_chroma_sample_loc_type 2 for top-left sited 4:2:0 chroma)\n"
            "  primaries: [--gamut_convert 1 [--gamut_clip 0|1]] (float or half G,B,R source planes in linear light converted from\n"
            "  --src_colour_primaries to --dst_colour_primaries on the GPU before the conversion; 1 BT.709, 8 / 9 BT.2020, 12 P3-D65,\n"
            "  10 XYZ; what is not above 0 is clipped to 0 unless --gamut_clip 0)\n"
@@ -249,6 +265,7 @@ static inline void cli_parse(cli_args &a, int argc, char **argv)
         else if (is("--compare_only")) a.compare_only = atoi(val());
         else if (is("--ssim")) { a.ssim = atoi(val()); a.ssim_given = true; }
         else if (is("--content_light")) { a.light = atoi(val()); a.light_given = true; }
+        else if (is("--light_only")) { a.light_only = atoi(val()); a.light_only_given = true; }
         else if (is("--dynamic_metadata")) a.dynmeta = val();
         else if (is("--gamut_convert")) { a.gamut = atoi(val()); a.gamut_given = true; }
         else if (is("--gamut_clip")) { a.gamut_clip = atoi(val()); a.gamut_clip_given = true; }
@@ -434,8 +451,17 @@ static inline int cli_resolve_scale(cli_args &a);
 static inline int cli_resolve_gamut(cli_args &a, int src_matrix_arg);
 static inline int cli_resolve_siting(cli_args &a);
 static inline int cli_resolve_src_siting(cli_args &a);
+static inline int cli_resolve_light_only(cli_args &a);
 static inline int cli_resolve(cli_args &a)
 {
+    if (a.light_only_given) { /* its own flow: it resolves everything it takes and refuses the rest */
+        printf("light_only: %d\n", a.light_only);
+        if (a.light_only != 0 && a.light_only != 1) {
+            printf("WARNING: light_only(%d) not 0 or 1\n", a.light_only);
+            return 1;
+        }
+        if (a.light_only) return cli_resolve_light_only(a);
+    }
     const int src_matrix_arg = a.in.matrix_coeffs; /* as given: the float readers force G,B,R on the input picture below */
     int arg_errors = a.hist_only    ? cli_resolve_histogram_only(a)
                      : a.compare_only ? cli_resolve_compare(a)
@@ -597,21 +623,119 @@ static inline int cli_resolve_light(cli_args &a)
     return 0;
 }
 
+/* can `path` be created: an existing regular file that can be written, or a name in a directory that can be written to */
+static inline bool cli_can_create(const char *path)
+{
+    struct stat st;
+    if (!stat(path, &st)) return S_ISREG(st.st_mode) && !access(path, W_OK);
+    const char *slash = strrchr(path, '/');
+    const std::string dir = !slash ? "." : slash == path ? "/" : std::string(path, slash);
+    return *path && !stat(dir.c_str(), &st) && S_ISDIR(st.st_mode) && !access(dir.c_str(), W_OK | X_OK);
+}
+
+/* --light_only 1: the light of a PQ .yuv or .rgb from its codes, one file read, no conversion; with --dynamic_metadata FILE the
+ * light distribution too.  Sets a.light (and keeps a.dynmeta) so that the run keeps and reports those figures; returns the number
+ * of argument errors */
+static inline int cli_resolve_light_only(cli_args &a)
+{
+    int arg_errors = 0;
+    const char *ext = cli_ext_of(a.src);
+    if (!strcasecmp(ext, "yuv")) a.in_type = CLI_IN_YUV;
+    else if (!strcasecmp(ext, "rgb")) a.in_type = CLI_IN_RGB;
+    else {
+        printf("WARNING: --light_only reads .yuv or .rgb; source file (%s) is a .%s\n", a.src ? a.src : "(none)", ext);
+        arg_errors++;
+    }
+    if (a.dst) { printf("WARNING: --light_only writes no frames: leave out --dst_filename\n"); arg_errors++; }
+    if (a.ref || a.hist || a.hist_bits_given || a.check_range || a.ssim_given || a.scale_given || a.scale_taps_given || a.gamut_given ||
+        a.gamut_clip_given || a.light_given || a.siting_given) {
+        printf("WARNING: --light_only measures one file's light: leave out --ref_filename, --histogram, --ssim, --scale, --gamut_convert, "
+               "--content_light and --dst_chroma_sample_loc_type\n");
+        arg_errors++;
+    }
+    if (a.compare_only || a.hist_only || a.scale_only) {
+        printf("WARNING: --light_only 1: not with --%s 1\n", a.compare_only ? "compare_only" : a.hist_only ? "histogram_only" : "scale_only");
+        arg_errors++;
+    }
+    printf("src_filename: %s\n", a.src ? a.src : "(none)");
+    printf("src_pic_width: %d\nsrc_pic_height: %d\nsrc_chroma_format_idc: %d\nsrc_bit_depth: %d\nsrc_video_full_range_flag: %d\n"
+           "src_matrix_coeffs: %d\nsrc_transfer_characteristics: %d\nsrc_start_frame: %d\nn_frames: %d\n", a.in.width, a.in.height,
+           a.in.chroma_format_idc, a.in.bit_depth, a.in.video_full_range_flag, a.in.matrix_coeffs, a.in.transfer_characteristics,
+           a.start_frame, a.n_frames);
+    if (a.src_siting_given) printf("src_chroma_sample_loc_type: %d\n", a.src_siting);
+    if (a.dynmeta) printf("dynamic_metadata_file: %s\n", a.dynmeta);
+    if (a.in.width < 1 || a.in.width > 10000) { printf("WARNING: pic_width(%d) outside range [1,10000]\n", a.in.width); arg_errors++; }
+    if (a.in.height < 1 || a.in.height > 10000) { printf("WARNING: pic_height(%d) outside range [1,10000]\n", a.in.height); arg_errors++; }
+    if (a.in.bit_depth < 8 || a.in.bit_depth > 16) { printf("WARNING: src bit_depth(%d) outside range [8,16]\n", a.in.bit_depth); arg_errors++; }
+    if (a.in.video_full_range_flag != 0 && a.in.video_full_range_flag != 1) {
+        printf("WARNING: video_full_range_flag(%d) not 0 or 1\n", a.in.video_full_range_flag);
+        arg_errors++;
+    }
+    if (a.in.transfer_characteristics != 16) {
+        printf("WARNING: --light_only 1 measures PQ codes: src_transfer_characteristics(%d) is not 16\n", a.in.transfer_characteristics);
+        arg_errors++;
+    }
+    const int m = a.in.matrix_coeffs, chroma = a.in.chroma_format_idc;
+    if (m != H2Y_MATRIX_GBR && m != H2Y_MATRIX_BT709 && m != H2Y_MATRIX_BT2020NC) {
+        printf("WARNING: --light_only 1: src_matrix_coeffs(%d) not %d (G,B,R), %d (BT.709) or %d (BT.2020nc)\n", m, H2Y_MATRIX_GBR,
+               H2Y_MATRIX_BT709, H2Y_MATRIX_BT2020NC);
+        arg_errors++;
+    } else if (a.in_type == CLI_IN_RGB && m != H2Y_MATRIX_GBR) {
+        printf("WARNING: a .rgb holds planes R, G, B: --light_only of a .rgb takes src_matrix_coeffs %d, not %d\n", H2Y_MATRIX_GBR, m);
+        arg_errors++;
+    }
+    if (chroma == 2) { printf("WARNING: --light_only 1: chroma_format_idc 2 (4:2:2) is not measured\n"); arg_errors++; }
+    else if (chroma != H2Y_CHROMA_420 && chroma != H2Y_CHROMA_444) {
+        printf("WARNING: chroma_format_idc(%d) not %d or %d\n", chroma, H2Y_CHROMA_420, H2Y_CHROMA_444);
+        arg_errors++;
+    } else if (a.in_type == CLI_IN_RGB && chroma != H2Y_CHROMA_444) { /* three full planes R, G, B */
+        printf("WARNING: a .rgb holds three planes of width x height: --light_only of a .rgb takes chroma_format_idc %d, not %d\n",
+               H2Y_CHROMA_444, chroma);
+        arg_errors++;
+    } else if (chroma == H2Y_CHROMA_420 && m == H2Y_MATRIX_GBR) {
+        printf("WARNING: --light_only 1: G,B,R planes (src_matrix_coeffs %d) are 4:4:4, not chroma_format_idc %d\n", H2Y_MATRIX_GBR, chroma);
+        arg_errors++;
+    } else if (chroma == H2Y_CHROMA_420 && ((a.in.width | a.in.height) & 1)) {
+        printf("WARNING: --light_only 1: 4:2:0 needs an even width and height, not %dx%d\n", a.in.width, a.in.height);
+        arg_errors++;
+    }
+    if (a.src_siting == 1) {
+        printf("WARNING: src_chroma_sample_loc_type(1) is replication's siting, --chroma_resampler_type 0: not selected by this flag\n");
+        arg_errors++;
+    } else if (a.src_siting != 0 && a.src_siting != 2) {
+        printf("WARNING: src_chroma_sample_loc_type(%d) not 0 or 2\n", a.src_siting);
+        arg_errors++;
+    } else if (a.src_siting == 2 && chroma != H2Y_CHROMA_420) {
+        printf("WARNING: --src_chroma_sample_loc_type 2 sites 4:2:0 chroma: src_chroma_format_idc(%d) has none to site\n", chroma);
+        arg_errors++;
+    } else if (a.src_siting == 2 && a.resampler == 0) {
+        printf("WARNING: --src_chroma_sample_loc_type 2 needs the FIR resampler: replication (--chroma_resampler_type 0) is centre sited by "
+               "construction\n");
+        arg_errors++;
+    }
+    if (a.dynmeta && !cli_can_create(a.dynmeta)) {
+        printf("WARNING: --dynamic_metadata: file (%s) cannot be created\n", a.dynmeta);
+        arg_errors++;
+    }
+    a.out = a.in;
+    if (arg_errors) return arg_errors;
+    a.light = 1; /* the run keeps and reports content light's figures */
+    static const char *const kMatrix[10] = {"G,B,R", "BT.709", "", "", "", "", "", "", "", "BT.2020nc"};
+    printf("light_only_from: PQ codes, bit_depth %d %s range, matrix_coeffs %d (%s), chroma_format_idc %d, upsampler %s\n", a.in.bit_depth,
+           a.in.video_full_range_flag ? "full" : "video", m, kMatrix[m], chroma,
+           chroma == H2Y_CHROMA_444 ? "none" : !a.resampler ? "replicate" : a.src_siting == 2 ? "fir_top_left" : "fir");
+    if (a.dynmeta)
+        printf("dynamic_metadata_from: PQ codes; HDR10+ profile A, one scene, percentiles of max(R,G,B) in %d bins\n", H2Y_LIGHTDIST_BINS);
+    return 0;
+}
+
 /* --dynamic_metadata FILE: content light's scope, and a FILE that can be created (an existing regular file that can be written, or
  * a name in a directory that can be written to; nothing is created here); returns the number of argument errors */
 static inline int cli_resolve_dynmeta(cli_args &a)
 {
     printf("dynamic_metadata_file: %s\n", a.dynmeta);
     if (cli_light_scope(a, "--dynamic_metadata FILE")) return 1;
-    struct stat st;
-    bool ok;
-    if (!stat(a.dynmeta, &st)) ok = S_ISREG(st.st_mode) && !access(a.dynmeta, W_OK);
-    else {
-        const char *slash = strrchr(a.dynmeta, '/');
-        const std::string dir = !slash ? "." : slash == a.dynmeta ? "/" : std::string(a.dynmeta, slash);
-        ok = *a.dynmeta && !stat(dir.c_str(), &st) && S_ISDIR(st.st_mode) && !access(dir.c_str(), W_OK | X_OK);
-    }
-    if (!ok) {
+    if (!cli_can_create(a.dynmeta)) {
         printf("WARNING: --dynamic_metadata: file (%s) cannot be created\n", a.dynmeta);
         return 1;
     }

@@ -5,7 +5,7 @@
  * (tiff.cpp:440: the file is opened in append mode; planes Y, Cb, Cr, little-endian 16-bit).
  *
  * How the file is laid out: main resolves the command line, scans the source (h2y_cli_sources.h) and checks every file's size,
- * then chooses one of five flows -- forward, .yuv -> RGB, --compare_only, --histogram_only, --scale_only.  A flow is a `flow`: how
+ * then chooses one of six flows -- forward, .yuv -> RGB, --compare_only, --histogram_only, --scale_only, --light_only.  A flow is a `flow`: how
  * to open its ring and arm its stages, how frame k gets into a slot's planes, the layout of the reference frame, how frame k is
  * written.  run_block drives every flow the same way (context, source, ring, reference, stages, the fill / submit / drain loop
  * three slots deep, the tail) and tears down through one guard; what the blocks measure is kept in one `results`.
@@ -81,6 +81,11 @@
  * edges of their bins), the percentiles 1, 5, 10, 25, 50, 75, 90, 95, 99 and 99.98 %, the share in percent:
  *   dynamic_metadata: frame <k> maxscl <R> <G> <B> average <A> percentiles <p1> ... <p99.98> below_100 <share>
  *   dynamic_metadata_written: <N> frames to FILE
+ *
+ * Light of a PQ master (--light_only 1 [--dynamic_metadata FILE]; h2y_cli_args.h): each GPU thread sets its context's inverse chroma
+ * siting where --src_chroma_sample_loc_type 2 says so and opens a light-only ring (h2y_codelight_stream_open) on the source's code
+ * planes; the figures of frame k are kept by its index and reported by the two reports above, word for word, so the lines and FILE
+ * are the same for any --gpus.  The banner carries light_only: and light_only_from:.
  *
  * Scaling (--scale 1 [--scale_taps A] with --dst_pic_width / --dst_pic_height on the forward flow; h2y_cli_args.h): each GPU thread
  * arms its ring (h2y_stream_scale), so the frame that comes down is the converted frame resampled on the device to the destination
@@ -224,7 +229,7 @@ struct job {
  * conversion and download of neighbouring frames overlap. */
 static constexpr int kRingDepth = 3;
 
-/* What one of the five flows hands to run_block.  open and arm return the library's status; fill and write return "" or the
+/* What one of the six flows hands to run_block.  open and arm return the library's status; fill and write return "" or the
  * block's error message. */
 struct flow {
     std::function<int(h2y_ctx *)> open; /* the flow's ring, kRingDepth deep */
@@ -445,7 +450,7 @@ static flow inverse_flow(const job &j)
     return f;
 }
 
-/* the source of the three flows that convert nothing, .yuv or .rgb: the slot's planes lie one after the other, so a frame is
+/* the source of the four flows that convert nothing, .yuv or .rgb: the slot's planes lie one after the other, so a frame is
  * one read, a .rgb one with its planes put in G, B, R order */
 static flow whole_frame_flow(const job &j)
 {
@@ -482,6 +487,20 @@ static flow histogram_flow(const job &j)
     f.open = [&a](h2y_ctx *ctx) {
         return h2y_histogram_stream_open(ctx, a.in.width, a.in.height, a.in.chroma_format_idc, a.hist_depth, a.hist_full, a.hist_gbr, a.hist_bits,
                                          kRingDepth);
+    };
+    return f;
+}
+
+/* --light_only: the source's PQ code planes through one light-only ring */
+static flow light_flow(const job &j)
+{
+    const cli_args &a = j.a;
+    flow f = whole_frame_flow(j);
+    f.open = [&a](h2y_ctx *ctx) {
+        if (a.src_siting && h2y_ctx_set_inverse_chroma_siting(ctx, a.src_siting)) return (int)H2Y_EINVAL; /* before the ring is opened */
+        const h2y_codelight_desc d{a.in.width, a.in.height, a.in.chroma_format_idc, a.in.bit_depth, a.in.video_full_range_flag,
+                                   a.in.matrix_coeffs, a.resampler};
+        return h2y_codelight_stream_open(ctx, &d, a.dynmeta ? 1 : 0, kRingDepth);
     };
     return f;
 }
@@ -692,7 +711,7 @@ int main(int argc, char **argv)
     cli_args &a = j.a;
     scanned &s = j.src;
     cli_parse(a, argc, argv);
-    if ((!a.dst && !a.ref && !a.hist && !a.hist_only && !a.light && !a.dynmeta && !a.scale_only) || (!a.src && a.synthetic < 0)) {
+    if ((!a.dst && !a.ref && !a.hist && !a.hist_only && !a.light && !a.dynmeta && !a.scale_only && !a.light_only) || (!a.src && a.synthetic < 0)) {
         if (!a.help) cli_help();
         return a.help ? 0 : 1;
     }
@@ -720,8 +739,8 @@ int main(int argc, char **argv)
     /* the flow, and the bytes of one frame as it reads and as it writes them */
     flow (*make_flow)(const job &);
     size_t &in_frame_bytes = j.in_frame_bytes, &out_frame_bytes = j.out_frame_bytes;
-    if (a.compare_only || a.hist_only || a.scale_only) { /* two files of one layout, or one */
-        make_flow = a.hist_only ? histogram_flow : a.scale_only ? scale_flow : compare_flow;
+    if (a.compare_only || a.hist_only || a.scale_only || a.light_only) { /* two files of one layout, or one */
+        make_flow = a.light_only ? light_flow : a.hist_only ? histogram_flow : a.scale_only ? scale_flow : compare_flow;
         in_frame_bytes = out_frame_bytes = planar16_bytes(a.in);
     } else if (a.inverse) {
         if (a.out.bit_depth > 16 || a.in.bit_depth > 16) { printf("ERROR: bit depths must be 8..16 on the inverse flow\n"); return 1; }

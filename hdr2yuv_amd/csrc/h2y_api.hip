@@ -279,6 +279,8 @@ void h2y_ctx_destroy(h2y_ctx *ctx)
     (void)hipFree(ctx->d_light_as);
     (void)hipFree(ctx->d_light_acc);
     (void)hipFree(ctx->d_lightdist);
+    (void)hipFree(ctx->d_codelight);
+    (void)hipFree(ctx->d_codelight_up);
     (void)hipFree(ctx->d_scale_tabs);
     (void)hipFree(ctx->d_in);
     (void)hipFree(ctx->d_out);

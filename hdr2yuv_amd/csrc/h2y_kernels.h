@@ -363,6 +363,25 @@ int h2y_lightdist_grid(uint32_t npix, int n_frames); /* blocks per frame */
 hipError_t h2y_launch_lightdist(int in_kind, int grid, hipStream_t st, const light_args &a, const light_frame *frames, int n_frames,
                                 lightdist_acc *acc, uint32_t *bins);
 
+/* k_codelight (h2y_codelight.hip): content light and the light distribution of frames of three u16 PQ code planes, 4:4:4
+ * (include/hdr2yuv_hip.h, "light of PQ code planes") */
+struct codelight_frame { /* one frame: Y, Cb, Cr (or G, B, R), width x height codes each */
+    const uint16_t *p[3];
+};
+struct codelight_args {
+    uint32_t npix;           /* pixels per frame (< 2^28) */
+    uint32_t n8;             /* npix / 8: 8-pixel groups; the rest one by one */
+    uint32_t vec;            /* bit p: plane p of every frame starts 16-byte aligned and takes 16-byte loads */
+    float sub[2], div[2];    /* the normalisation of [0] Y (and of G, B, R planes), [1] Cb and Cr: (code - sub) / div */
+    const void *table;       /* PQ10000_f's table (tfn_build_table of H2Y_TFN_PQ_F) */
+    h2y::pix_params pp;      /* what light1<true> reads: src_tf PQ, src_fn H2Y_TFN_PQ_F, tf_ext[0], norm_identity 1 */
+};
+int h2y_codelight_grid(uint32_t npix, int n_frames); /* blocks per frame */
+/* k_codelight over n_frames frames into acc[frame] and, where dacc is not NULL, dacc[frame] and bins[frame x H2Y_LIGHTDIST_BINS]
+ * (all zeroed by the caller); matrix: H2Y_MATRIX_GBR, _BT709 or _BT2020NC */
+hipError_t h2y_launch_codelight(int matrix, int grid, hipStream_t st, const codelight_args &a, const codelight_frame *frames, int n_frames,
+                                light_acc *acc, lightdist_acc *dacc, uint32_t *bins);
+
 /* k_gamut (h2y_gamut.hip): the conversion between colour primaries of include/hdr2yuv_hip.h on frames of three float or half
  * planes G, B, R; dst may be src (in place) */
 struct gamut_frame {

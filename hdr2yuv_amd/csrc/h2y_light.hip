@@ -35,9 +35,7 @@ __device__ __forceinline__ void light_pixel(const pix_params &pp, const pq_recA 
                                             unsigned long long &key, unsigned long long &sum)
 {
     const float m = fmaxf(fmaxf(light1<TFN>(pp, tab, 0, g), light1<TFN>(pp, tab, 1, b)), light1<TFN>(pp, tab, 2, r));
-    const unsigned long long k = ((unsigned long long)f2bits(m) << 32) | (unsigned long long)~i;
-    key = k > key ? k : key;
-    sum += (unsigned long long)__builtin_rintf(m * 0x1p32f); /* m x 2^32 is exact; at most 2^32 */
+    light_keep(m, i, key, sum);
 }
 
 template <int IN_KIND, bool TFN>

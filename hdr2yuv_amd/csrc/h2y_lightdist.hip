@@ -32,31 +32,12 @@ constexpr uint32_t kMaxBlocks = 1024u;     /* blocks of a launch: four per CU, w
 constexpr uint32_t kBins = H2Y_LIGHTDIST_BINS;
 constexpr uint32_t kNone = 0xFFFFFFFFu;
 
-/* what a thread keeps of its pixels */
-struct dist_regs {
-    uint32_t mx[3]; /* the largest L of each plane, as bits */
-    uint32_t below; /* pixels with m <= 0.01f */
-    unsigned long long sum;
-};
-
-/* the bin of m (in [+0, 1]) by its bit pattern */
-__device__ __forceinline__ uint32_t bin_of(uint32_t e)
-{
-    const uint32_t b = e < H2Y_LIGHTDIST_FIRST_BITS ? 0u : ((e - H2Y_LIGHTDIST_FIRST_BITS) >> 14) + 1u;
-    return b < kBins ? b : kBins - 1u; /* m <= 1 never gets there: no index leaves the LDS bins whatever light1 returns */
-}
-
 /* one pixel into the thread's registers; returns its bin */
 template <bool TFN>
 __device__ __forceinline__ uint32_t dist_pixel(const pix_params &pp, const pq_recA *tab, float g, float b, float r, dist_regs &t)
 {
     const float lg = light1<TFN>(pp, tab, 0, g), lb = light1<TFN>(pp, tab, 1, b), lr = light1<TFN>(pp, tab, 2, r);
-    t.mx[0] = max(t.mx[0], f2bits(lg));
-    t.mx[1] = max(t.mx[1], f2bits(lb));
-    t.mx[2] = max(t.mx[2], f2bits(lr));
-    const float m = fmaxf(fmaxf(lg, lb), lr);
-    t.sum += (unsigned long long)__builtin_rintf(m * 0x1p32f); /* m x 2^32 is exact; at most 2^32 */
-    t.below += m <= 0.01f;
+    const float m = dist_keep(lg, lb, lr, t);
     return bin_of(f2bits(m));
 }
 

@@ -1,5 +1,5 @@
 /*
- * h2y_measure.hip -- the measurements of the C-ABI shim: the comparison with a reference, SSIM, content light, the light distribution, histograms, the
+ * h2y_measure.hip -- the measurements of the C-ABI shim: the comparison with a reference, SSIM, content light, the light distribution, the light of PQ code planes, histograms, the
  * scaler and the conversion between colour primaries.  Each has its checks and geometry, its batch entry, its ring stage (ring_stage, h2y_shim.h), and its arm, result and
  * *_stream_open entries.
  */
@@ -158,6 +158,7 @@ int h2y_stream_compare(h2y_ctx *ctx, int sigma, int keep_output)
     if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
     if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
     if (ctx->s_stage[STAGE_COMPARE]) return fail(ctx, H2Y_EINVAL, "the ring is armed already");
+    if (ctx->s_stage[STAGE_CODELIGHT]) return fail(ctx, H2Y_EINVAL, "a light-only ring takes no other stage");
     if (ctx->s_stage[STAGE_SCALE]) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that scales is not compared: compare the written file instead");
     if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
     if (keep_output != 0 && keep_output != 1) return fail(ctx, H2Y_EINVAL, "keep_output must be 0 or 1");
@@ -377,6 +378,11 @@ static std::string light_variant(const h2y_desc *d, const light_args &a)
 }
 
 /* the stats of one frame of npix pixels, width wide, from its accumulator */
+static void light_finish(const light_acc &acc, uint32_t width, uint32_t npix, h2y_light_stats *o);
+/* a light-only ring (h2y_codelight_stream_open, below): its lent frame's figures; false on any other ring */
+static bool codelight_light_result(const h2y_ctx *ctx, h2y_light_stats *out);
+static int codelight_dist_result(h2y_ctx *ctx, h2y_lightdist_stats *out, bool *mine);
+
 static void light_finish(const light_acc &acc, uint32_t width, uint32_t npix, h2y_light_stats *o)
 {
     *o = h2y_light_stats{};
@@ -500,8 +506,9 @@ int h2y_stream_light_result(h2y_ctx *ctx, h2y_light_stats *out)
 {
     if (!ctx || !out) return fail(ctx, H2Y_EINVAL, "null argument");
     const light_stage *st = ctx->streaming ? stage_of<light_stage>(ctx, STAGE_LIGHT) : nullptr;
-    if (!st) return fail(ctx, H2Y_EINVAL, "no stream open that measures content light");
+    if (!st && !(ctx->streaming && ctx->s_stage[STAGE_CODELIGHT])) return fail(ctx, H2Y_EINVAL, "no stream open that measures content light");
     if (ctx->s_lent < 0) return fail(ctx, H2Y_EINVAL, "no output taken yet: h2y_stream_output first");
+    if (codelight_light_result(ctx, out)) return H2Y_OK;
     light_finish(*st->ss[ctx->s_lent].h, (uint32_t)ctx->s_desc.width, st->a.npix, out);
     return H2Y_OK;
 }
@@ -627,6 +634,9 @@ int h2y_stream_lightdist(h2y_ctx *ctx)
 int h2y_stream_lightdist_result(h2y_ctx *ctx, h2y_lightdist_stats *out)
 {
     if (!ctx || !out) return fail(ctx, H2Y_EINVAL, "null argument");
+    bool mine = false;
+    const int crc = codelight_dist_result(ctx, out, &mine);
+    if (mine) return crc;
     const lightdist_stage *st = ctx->streaming ? stage_of<lightdist_stage>(ctx, STAGE_LIGHTDIST) : nullptr;
     if (!st) return fail(ctx, H2Y_EINVAL, "no stream open that measures the light distribution");
     if (ctx->s_lent < 0) return fail(ctx, H2Y_EINVAL, "no output taken yet: h2y_stream_output first");
@@ -669,6 +679,236 @@ size_t h2y_lightdist_json(const h2y_lightdist_stats *stats, int n_frames, long f
         buf[n] = 0;
     }
     return s.size();
+}
+
+/* ---- light of PQ code planes (h2y_codelight_batch, h2y_codelight_stream_open): include/hdr2yuv_hip.h states the definition ------ */
+
+/* what a checked h2y_codelight_desc comes to */
+struct codelight_plan {
+    codelight_args a{};
+    int matrix = 0, form = UP_REPLICATE;
+    bool sub = false;      /* 4:2:0: planes 1 and 2 come from the scratch */
+    size_t plane_al = 0;   /* 4:2:0: the bytes from one upsampled plane to the next (256-byte aligned) */
+    up_args up{};          /* 4:2:0: k_up444's arguments but the planes */
+    uint32_t off[3] = {0, 0, 0}; /* the planes' starts in the frame, in samples */
+};
+
+static int codelight_check(h2y_ctx *ctx, const h2y_codelight_desc *d, codelight_plan &p)
+{
+    if (!d) return fail(ctx, H2Y_EINVAL, "null h2y_codelight_desc");
+    if (d->chroma_format_idc == 2) return fail(ctx, H2Y_EUNSUPPORTED, "chroma_format_idc 2 (4:2:2) has no light on this path");
+    if (d->chroma_format_idc != H2Y_CHROMA_420 && d->chroma_format_idc != H2Y_CHROMA_444)
+        return fail(ctx, H2Y_EINVAL, "chroma_format_idc must be 1 or 3");
+    if (d->matrix_coeffs != H2Y_MATRIX_GBR && d->matrix_coeffs != H2Y_MATRIX_BT709 && d->matrix_coeffs != H2Y_MATRIX_BT2020NC)
+        return fail(ctx, H2Y_EUNSUPPORTED, "light of code planes: matrix_coeffs must be 0 (G,B,R), 1 (BT.709) or 9 (BT.2020nc), not %d", d->matrix_coeffs);
+    if (d->width < 1 || d->height < 1 || (uint64_t)d->width * (uint64_t)d->height >= (1ull << 28)) return fail(ctx, H2Y_EINVAL, "bad picture size");
+    if (d->bit_depth < 8 || d->bit_depth > 16) return fail(ctx, H2Y_EINVAL, "bit_depth must be 8..16");
+    if (d->full_range != 0 && d->full_range != 1) return fail(ctx, H2Y_EINVAL, "full_range must be 0 or 1");
+    p.sub = d->chroma_format_idc == H2Y_CHROMA_420;
+    if (p.sub) {
+        if (d->matrix_coeffs == H2Y_MATRIX_GBR) return fail(ctx, H2Y_EINVAL, "G,B,R planes (matrix_coeffs 0) are 4:4:4");
+        if ((d->width & 1) || (d->height & 1) || d->width > 32766 || d->height > 32766)
+            return fail(ctx, H2Y_EINVAL, "4:2:0: width and height must be even, up to 32766");
+    }
+    const int rc = inverse_form(ctx, d->chroma_format_idc, d->algorithm, &p.form); /* siting 2 with replication: the inverse entries' refusal */
+    if (rc) return rc;
+    p.matrix = d->matrix_coeffs;
+    codelight_args &a = p.a;
+    a.npix = (uint32_t)d->width * (uint32_t)d->height;
+    a.n8 = a.npix / 8u;
+    const float s = (float)(1u << (d->bit_depth - 8)), top = (float)((1u << d->bit_depth) - 1u);
+    a.sub[0] = d->full_range ? 0.0f : 16.0f * s;
+    a.div[0] = d->full_range ? top : 219.0f * s;
+    a.sub[1] = d->full_range ? (float)(1u << (d->bit_depth - 1)) : 128.0f * s;
+    a.div[1] = d->full_range ? top : 224.0f * s;
+    contiguous_planes(d->width, d->height, d->chroma_format_idc, p.off);
+    /* the frames' bases are 16-byte aligned, and so is the scratch: a plane takes 16-byte loads where its start is */
+    a.vec = 1u;
+    for (int c = 1; c < 3; c++) a.vec |= (p.sub || ((size_t)p.off[c] * sizeof(uint16_t) & 15u) == 0) ? 1u << c : 0u;
+    if (p.sub) {
+        inv420_args ia;
+        inverse420_setup(ia, d->width, d->height, d->bit_depth, d->full_range, d->matrix_coeffs, d->bit_depth, p.form);
+        p.up = ia.up;
+        p.plane_al = ((size_t)a.npix * sizeof(uint16_t) + 255) & ~(size_t)255;
+    }
+    return H2Y_OK;
+}
+
+/* PQ10000_f's tables into the plan: what light1<true> reads of pix_params */
+static int codelight_tables(h2y_ctx *ctx, codelight_plan &p)
+{
+    const int rc = ensure_tfn(ctx, H2Y_TFN_PQ_F);
+    if (rc) return rc;
+    pix_params &pp = p.a.pp;
+    pp = pix_params{};
+    pp.convert_transfer = 2;
+    pp.src_tf = H2Y_TF_PQ;
+    pp.src_fn = H2Y_TFN_PQ_F;
+    pp.norm_identity = 1; /* the kernel normalises the codes itself */
+    for (int c = 0; c < 3; c++) pp.range[c] = 1.0f;
+    pp.tf_ext[0] = ctx->d_tfn_ext[H2Y_TFN_PQ_F];
+    p.a.table = ctx->d_tfn[H2Y_TFN_PQ_F];
+    return H2Y_OK;
+}
+
+static std::string codelight_variant(const codelight_plan &p, bool dist)
+{
+    return std::string("k_codelight<") + (p.matrix == H2Y_MATRIX_GBR ? "GBR" : p.matrix == H2Y_MATRIX_BT709 ? "BT709" : "BT2020NC") +
+           (dist ? ",DIST," : ",LIGHT,") + (!p.sub ? "444" : p.form == UP_FIR_TL ? "FIR_TL" : p.form == UP_FIR ? "FIR" : "REPLICATE") + ">";
+}
+
+/* one 4:2:0 frame's chroma (planes at p.off[1], p.off[2] of base) upsampled into the two planes at up */
+static hipError_t codelight_upsample(const h2y_ctx *ctx, const codelight_plan &p, const uint16_t *base, char *up)
+{
+    up_args u = p.up;
+    u.src0 = base + p.off[1];
+    u.src1 = base + p.off[2];
+    u.dst0 = reinterpret_cast<uint16_t *>(up);
+    u.dst1 = reinterpret_cast<uint16_t *>(up + p.plane_al);
+    return h2y_launch_up444(ctx->stream, u);
+}
+
+/* the frame's table entry: its own planes, or its luma and the upsampled chroma at up */
+static codelight_frame codelight_entry(const codelight_plan &p, const uint16_t *base, const char *up)
+{
+    if (!p.sub) return codelight_frame{{base, base + p.off[1], base + p.off[2]}};
+    return codelight_frame{{base, reinterpret_cast<const uint16_t *>(up), reinterpret_cast<const uint16_t *>(up + p.plane_al)}};
+}
+
+/* A workspace of nf frames: light_acc, then lightdist_layout (all zeroed before a launch) */
+static size_t codelight_dist_off(int nf) { return ((size_t)nf * sizeof(light_acc) + 255) & ~(size_t)255; }
+
+int h2y_codelight_batch(h2y_ctx *ctx, const h2y_codelight_desc *d, int n_frames, const uint16_t *const *d_frames, h2y_light_stats *out,
+                        h2y_lightdist_stats *dist_out, uint32_t *bins_out)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
+    codelight_plan p;
+    int rc = codelight_check(ctx, d, p);
+    if (rc) return rc;
+    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
+    if (!d_frames || !out) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
+    for (int f = 0; f < n_frames; f++) {
+        if (!d_frames[f]) return fail(ctx, H2Y_EINVAL, "frame %d is null", f);
+        if ((uintptr_t)d_frames[f] & 15u) return fail(ctx, H2Y_EINVAL, "frame %d is not 16-byte aligned", f);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const bool dist = dist_out || bins_out;
+    const int per_launch = std::min(n_frames, H2Y_CODELIGHT_FRAMES_PER_LAUNCH);
+    const lightdist_layout L = lightdist_layout_of(n_frames);
+    const size_t dist_off = codelight_dist_off(n_frames), ws = dist_off + (dist ? L.total : 0);
+    codelight_frame *h;
+    rc = codelight_tables(ctx, p);
+    if (!rc) rc = frame_table(ctx, n_frames, h);
+    if (!rc) rc = ensure(ctx, ctx->d_codelight, ctx->codelight_cap, ws);
+    if (!rc && p.sub) rc = ensure(ctx, ctx->d_codelight_up, ctx->codelight_up_cap, (size_t)per_launch * 2u * p.plane_al);
+    if (rc) return rc;
+    /* frame f's upsampled chroma lies in the scratch of its place in its launch; the launches follow one another on one stream */
+    for (int f = 0; f < n_frames; f++)
+        h[f] = codelight_entry(p, d_frames[f], p.sub ? ctx->d_codelight_up + (size_t)(f % per_launch) * 2u * p.plane_al : nullptr);
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_codelight, 0, ws, ctx->stream));
+    light_acc *d_acc = reinterpret_cast<light_acc *>(ctx->d_codelight);
+    lightdist_acc *d_dacc = dist ? reinterpret_cast<lightdist_acc *>(ctx->d_codelight + dist_off) : nullptr;
+    uint32_t *d_bins = dist ? reinterpret_cast<uint32_t *>(ctx->d_codelight + dist_off + L.bins) : nullptr;
+    rc = timed_launches(ctx, h, n_frames, H2Y_CODELIGHT_FRAMES_PER_LAUNCH, "k_codelight", [&](const codelight_frame *frames, int f0, int nf) {
+        for (int f = 0; p.sub && f < nf; f++) {
+            const hipError_t e = codelight_upsample(ctx, p, d_frames[f0 + f], ctx->d_codelight_up + (size_t)f * 2u * p.plane_al);
+            if (e != hipSuccess) return e;
+        }
+        return h2y_launch_codelight(p.matrix, h2y_codelight_grid(p.a.npix, nf), ctx->stream, p.a, frames, nf, d_acc + f0,
+                                    dist ? d_dacc + f0 : nullptr, dist ? d_bins + (size_t)f0 * H2Y_LIGHTDIST_BINS : nullptr);
+    });
+    if (rc) return rc;
+    std::vector<light_acc> acc(n_frames);
+    HIP_TRY(ctx, hipMemcpy(acc.data(), d_acc, (size_t)n_frames * sizeof(light_acc), hipMemcpyDeviceToHost));
+    for (int f = 0; f < n_frames; f++) light_finish(acc[f], (uint32_t)d->width, p.a.npix, out + f);
+    if (dist) {
+        std::vector<lightdist_acc> dacc(n_frames);
+        std::vector<uint32_t> own(bins_out ? 0 : (size_t)n_frames * H2Y_LIGHTDIST_BINS);
+        uint32_t *bins = bins_out ? bins_out : own.data();
+        HIP_TRY(ctx, hipMemcpy(dacc.data(), d_dacc, (size_t)n_frames * sizeof(lightdist_acc), hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(bins, d_bins, (size_t)n_frames * H2Y_LIGHTDIST_BINS * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (int f = 0; dist_out && f < n_frames; f++) lightdist_finish(dacc[f], bins + (size_t)f * H2Y_LIGHTDIST_BINS, p.a.npix, dist_out + f);
+    }
+    ctx->last_variant = codelight_variant(p, dist);
+    return H2Y_OK;
+}
+
+/* The light-only ring's stage, on the planes the ring's input holds: per slot the upsampled chroma (4:2:0), the workspace of one
+ * frame on the device and pinned, and the slot's k_codelight table entry */
+struct codelight_stage : ring_stage {
+    struct slot {
+        char *up = nullptr, *d = nullptr, *h = nullptr;
+    };
+    std::vector<slot> ss;
+    codelight_plan p;
+    bool dist = false;
+    size_t ws = 0;
+    codelight_frame *tab = nullptr;
+    int run(h2y_ctx *ctx, int k) override
+    {
+        HIP_TRY(ctx, hipMemsetAsync(ss[k].d, 0, ws, ctx->stream));
+        if (p.sub) HIP_TRY(ctx, codelight_upsample(ctx, p, frame_base(ctx, k), ss[k].up));
+        const size_t off = codelight_dist_off(1);
+        HIP_TRY(ctx, h2y_launch_codelight(p.matrix, h2y_codelight_grid(p.a.npix, 1), ctx->stream, p.a, tab + k, 1,
+                                          reinterpret_cast<light_acc *>(ss[k].d), dist ? reinterpret_cast<lightdist_acc *>(ss[k].d + off) : nullptr,
+                                          dist ? reinterpret_cast<uint32_t *>(ss[k].d + off + lightdist_layout_of(1).bins) : nullptr));
+        return H2Y_OK;
+    }
+    int download(h2y_ctx *ctx, int k) override
+    {
+        HIP_TRY(ctx, hipMemcpyAsync(ss[k].h, ss[k].d, ws, hipMemcpyDeviceToHost, ctx->s_d2h));
+        return H2Y_OK;
+    }
+};
+
+static bool codelight_light_result(const h2y_ctx *ctx, h2y_light_stats *out)
+{
+    const codelight_stage *st = ctx->streaming ? stage_of<codelight_stage>(ctx, STAGE_CODELIGHT) : nullptr;
+    if (!st || ctx->s_lent < 0) return false;
+    light_finish(*reinterpret_cast<const light_acc *>(st->ss[ctx->s_lent].h), (uint32_t)ctx->s_frame.width, st->p.a.npix, out);
+    return true;
+}
+
+static int codelight_dist_result(h2y_ctx *ctx, h2y_lightdist_stats *out, bool *mine)
+{
+    const codelight_stage *st = ctx->streaming ? stage_of<codelight_stage>(ctx, STAGE_CODELIGHT) : nullptr;
+    *mine = st != nullptr;
+    if (!st) return H2Y_OK;
+    if (!st->dist) return fail(ctx, H2Y_EINVAL, "the light-only ring was opened without want_dist");
+    if (ctx->s_lent < 0) return fail(ctx, H2Y_EINVAL, "no output taken yet: h2y_stream_output first");
+    const char *h = st->ss[ctx->s_lent].h + codelight_dist_off(1);
+    lightdist_finish(*reinterpret_cast<const lightdist_acc *>(h), reinterpret_cast<const uint32_t *>(h + lightdist_layout_of(1).bins), st->p.a.npix, out);
+    return H2Y_OK;
+}
+
+int h2y_codelight_stream_open(h2y_ctx *ctx, const h2y_codelight_desc *d, int want_dist, int depth)
+{
+    int rc = ring_may_open(ctx);
+    if (rc) return rc;
+    auto st = std::make_unique<codelight_stage>();
+    rc = codelight_check(ctx, d, st->p); /* the inverse chroma siting is read here */
+    if (rc) return rc;
+    if (want_dist != 0 && want_dist != 1) return fail(ctx, H2Y_EINVAL, "want_dist must be 0 or 1");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = codelight_tables(ctx, st->p);
+    if (!rc) rc = open_planes_ring(ctx, d->width, d->height, d->chroma_format_idc, d->bit_depth, d->full_range, d->matrix_coeffs == H2Y_MATRIX_GBR, 0, depth);
+    if (rc) return rc;
+    st->dist = want_dist != 0;
+    st->ws = codelight_dist_off(1) + (st->dist ? lightdist_layout_of(1).total : 0);
+    std::vector<codelight_frame> tab(depth);
+    st->ss.resize(depth);
+    for (int k = 0; k < depth; k++) {
+        codelight_stage::slot &s = st->ss[k];
+        if (st->p.sub) st->dev_alloc(s.up, 2u * st->p.plane_al);
+        st->dev_alloc(s.d, st->ws);
+        st->pin_alloc(s.h, st->ws);
+        tab[k] = codelight_entry(st->p, frame_base(ctx, k), s.up);
+    }
+    st->table(st->tab, tab);
+    rc = stage_arm(ctx, STAGE_CODELIGHT, std::move(st), "code light");
+    if (rc) stream_free(ctx);
+    return rc;
 }
 
 /* ---- code-value histograms and the legal-range check (hdr2yuv.cpp:658, :797) ---------------------------------------------- */
@@ -837,6 +1077,7 @@ int h2y_stream_histogram_ex(h2y_ctx *ctx, int bits, int bit_depth, int full_rang
     if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
     if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
     if (ctx->s_stage[STAGE_HISTOGRAM]) return fail(ctx, H2Y_EINVAL, "the ring counts histograms already");
+    if (ctx->s_stage[STAGE_CODELIGHT]) return fail(ctx, H2Y_EINVAL, "a light-only ring takes no other stage");
     if (ctx->s_stage[STAGE_SCALE]) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that scales counts no histograms: count the written file instead");
     if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
     const ring_frame &f = ctx->s_frame;

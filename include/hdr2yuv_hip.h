@@ -714,6 +714,58 @@ int h2y_stream_lightdist_result(h2y_ctx *ctx, h2y_lightdist_stats *out);
  * floor(100 x below_100 / pixels).  The layout is written from x265's documentation; no encoder's parser has checked it. */
 size_t h2y_lightdist_json(const h2y_lightdist_stats *stats, int n_frames, long first_frame_index, char *buf, size_t cap);
 
+/* ---- light of PQ code planes: MaxCLL / MaxFALL and the HDR10+ figures of a finished PQ master, from its codes (--light_only 1) ---
+ * The two sections above see the light of a conversion.  This one measures a picture that is PQ already: a PQ Y'CbCr .yuv, a
+ * decoded stream, a 16-bit PQ .rgb.  It is the project's own definition, as gamut and siting are: the reference's matrix_inverse
+ * treats BT.2020 as Y'DzDx and hard-codes 12-bit constants, so it defines no bytes here.
+ * Frame: three u16 code planes at bit_depth n (8..16), video or full range; matrix_coeffs 0 (G, B, R planes), 1 (BT.709) or 9
+ *   (BT.2020nc); chroma_format_idc 3, or 1 with even sizes (not with matrix 0).  The transfer is PQ, always.
+ *   1. Chroma at every pixel.  4:4:4 planes are used as they are.  4:2:0 planes are first upsampled by what the .yuv -> RGB flow
+ *      uses: k_up444 with the clip [0, 2^n - 1], in the form `algorithm` and the context's inverse chroma siting select (algorithm
+ *      0 replication; otherwise the reference's FIR pair, or under h2y_ctx_set_inverse_chroma_siting(2) the top-left form; siting 2
+ *      with algorithm 0 is H2Y_EUNSUPPORTED), into a scratch area the context owns.  Two passes.
+ *   2. Normalise, in binary32: the codes are integers and so exact; each step is one subtraction and one IEEE division.  With
+ *      s = 2^(n-8):  video range  y = (Y - 16 s) / (219 s),  cb = (Cb - 128 s) / (224 s),  cr likewise;
+ *                    full range   y = Y / (2^n - 1),         cb = (Cb - 2^(n-1)) / (2^n - 1),  cr likewise.
+ *      Matrix 0: all three planes are normalised as Y is.
+ *   3. Matrix, every product and sum rounded by itself to binary32 (no fused multiply-add), the constants being these decimal
+ *      values rounded once to binary32:
+ *        matrix 9:  R' = y + 1.4746 cr;  B' = y + 1.8814 cb;  G' = (y - 0.16455313 cb) - 0.57135313 cr
+ *        matrix 1:  R' = y + 1.5748 cr;  B' = y + 1.8556 cb;  G' = (y - 0.18732427 cb) - 0.46812427 cr
+ *        matrix 0:  none.
+ *      No subnormal arises: the smallest non-zero |v'| over all 10-bit (Y, Cb) pairs is 1.16e-6.
+ *   4. Clamp before the transfer: v' = v > 0 ? min(v, 1) : +0; L_c = PQ10000_f(v') by the conversion's tiers (the table, the
+ *      full-range table, the careful tier), then the clamp to [+0, 1] of the sections above.  The clamp in front is part of the
+ *      definition: PQ10000_f of a negative argument is a NaN, and every near-black pixel with a little chroma would otherwise
+ *      take the careful tier.
+ *   5. From here on nothing is new: m = max(L_G, L_B, L_R), and per frame h2y_light_stats and h2y_lightdist_stats word for word.
+ * Anchors (10-bit video range, Cb = Cr = 512): Y 64 -> 0; Y 940 and 1023 -> 1.0 (10000 cd/m2); Y 509 -> 99.9128 cd/m2; Y 723 ->
+ * 1004.19 cd/m2. */
+#define H2Y_CODELIGHT_FRAMES_PER_LAUNCH 8 /* a launch's 4:2:0 scratch: 2 planes x 2 bytes x width x height x 8 frames -- 253 MiB at 3840 x 2160 */
+
+typedef struct h2y_codelight_desc {
+    int width, height, chroma_format_idc, bit_depth, full_range, matrix_coeffs, algorithm;
+} h2y_codelight_desc;
+
+/* The light of n_frames device frames of d.  d_frames[f] holds the frame's three planes one after the other from a 16-byte
+ * aligned base, as h2y_histogram_batch takes them (4:2:0: Y, then two chroma planes of (width / 2) x (height / 2)).  out[f]
+ * (host memory) always; dist_out (n_frames entries) and bins_out (n_frames x H2Y_LIGHTDIST_BINS uint32) may each be NULL: with
+ * either given, the one pass yields both structs, and their max_bits and sum_q agree.  Launches of up to
+ * H2Y_CODELIGHT_FRAMES_PER_LAUNCH frames, each k_up444 per 4:2:0 frame and then one k_codelight (h2y_last_kernel_ms sums them,
+ * upsampling included; h2y_last_kernel_name "k_codelight"; the variant names the matrix, DIST and the upsampling form, e.g.
+ * "k_codelight<BT2020NC,DIST,FIR>"); synchronous.
+ * H2Y_EUNSUPPORTED: chroma_format_idc 2, a matrix other than 0, 1, 9, siting 2 with replication.  H2Y_EINVAL: a bad size (4:2:0:
+ * odd, or above 32766), depth or alignment, full_range not 0 or 1, matrix 0 with 4:2:0. */
+int h2y_codelight_batch(h2y_ctx *ctx, const h2y_codelight_desc *d, int n_frames, const uint16_t *const *d_frames, h2y_light_stats *out,
+                        h2y_lightdist_stats *dist_out, uint32_t *bins_out);
+
+/* A ring that only measures light: h2y_stream_input lends the frame's three planes (contiguous, as above), h2y_stream_output
+ * returns *yuv = NULL, h2y_stream_light_result the frame's light and, when want_dist is 1, h2y_stream_lightdist_result its
+ * distribution.  The inverse chroma siting is read when the ring opens.  Every arming entry (h2y_stream_compare, _ssim, _histogram,
+ * _histogram_ex, _light, _lightdist, _scale, _gamut) is H2Y_EINVAL on this ring.  Refusals as h2y_codelight_batch; want_dist other
+ * than 0 or 1 and depth outside 2..16 are H2Y_EINVAL. */
+int h2y_codelight_stream_open(h2y_ctx *ctx, const h2y_codelight_desc *d, int want_dist, int depth);
+
 /* ---- scaling: an exact Lanczos resampler (--dst_pic_width / --dst_pic_height; the reference's cv.cpp is compiled out) ------------
  * The reference plugs a per-plane Lanczos cv::resize in at hdr2yuv.cpp:892-896, in a file that does not compile; it defines no
  * bytes.  This is the project's own definition, in integers, so that a restatement checks every output byte.
@@ -890,7 +942,7 @@ int h2y_upsample_444_sited(h2y_ctx *ctx, int width, int height, int chroma_sampl
                            const uint16_t *d_src, uint16_t *d_dst);
 
 /* Timing of the last h2y_convert_batch*() (or h2y_inverse_*, h2y_dpx_decode_batch, h2y_tiff_decode_batch,
- * h2y_rgb_interleave_batch, h2y_exr_decode_batch, h2y_compare_batch, h2y_ssim_batch, h2y_light_batch, h2y_lightdist_batch, h2y_scale_batch, h2y_gamut_batch) call measured with HIP events on
+ * h2y_rgb_interleave_batch, h2y_exr_decode_batch, h2y_compare_batch, h2y_ssim_batch, h2y_light_batch, h2y_lightdist_batch, h2y_codelight_batch, h2y_scale_batch, h2y_gamut_batch) call measured with HIP events on
  * the stream the kernels ran on: total ms over the main kernels and how many
  * launches that covered. */
 int h2y_last_kernel_ms(const h2y_ctx *ctx, float *ms, int *launches);
@@ -898,7 +950,7 @@ int h2y_last_kernel_ms(const h2y_ctx *ctx, float *ms, int *launches);
 /* Name of the kernel those launches ran ("k_fused", "k_fused_t1", "k_fused_lut16",
  * "k_fused_narrow"; of the inverse entries "k_inverse", "k_inverse420", "k_inverse_batch", "k_inverse420_batch"; of
  * h2y_dpx_decode_batch "k_dpx_decode"; of h2y_tiff_decode_batch "k_tiff_decode", of h2y_rgb_interleave_batch
- * "k_rgb_interleave"; of h2y_exr_decode_batch "k_exr_decode"; of h2y_compare_batch "k_compare"; of h2y_scale_batch "k_scale"; of h2y_gamut_batch "k_gamut"): the name to
+ * "k_rgb_interleave"; of h2y_exr_decode_batch "k_exr_decode"; of h2y_compare_batch "k_compare"; of h2y_scale_batch "k_scale"; of h2y_gamut_batch "k_gamut"; of h2y_codelight_batch "k_codelight"): the name to
  * look for in a rocprofv3 kernel trace. */
 const char *h2y_last_kernel_name(const h2y_ctx *ctx);
 /* The same with its template arguments and launch shape, e.g. "k_fused_t1<F32,420BOX,YCBCR,PQ_IDENT> groups=8 xcd=1";

@@ -85,6 +85,18 @@ Prints one line per figure, then one JSON line with all of them.
   3. frames/s from host memory of the .f32 ring to PQ BT.2020nc 10-bit 4:2:0, unarmed and armed with h2y_stream_lightdist.
 Prints one line per figure, then one JSON line with all of them.
 
+`streambench.py codelight`: the light of PQ code planes (k_codelight) on 4K frames, in one job:
+  1. h2y_codelight_batch over 64 distinct device frames per call, DIST off and on, five calls each taken in turn after a warm-up (HIP
+     events round each launch of up to 8 frames, k_up444 included; the memset of the accumulators lies before the first event): the
+     median and spread in us per frame for 10-bit 4:2:0 BT.2020nc frames (noise, constant, letterboxed), the same noise as 10-bit
+     4:4:4 (no upsampling: the k_up444 share of the 4:2:0 time is what is left), and 16-bit 4:4:4 noise; the algorithmic bytes per
+     frame -- 4:2:0: 3 B/pixel read by k_up444 and k_codelight, 4 B/pixel of scratch written and 4 read back, 11 in all; 4:4:4:
+     6 B/pixel -- over that time as a share of the 8 TB/s HBM peak;
+  2. the yardsticks, in the same job, on the 16-bit 4:4:4 frames' planes read as a U16 LINEAR source: h2y_light_batch (k_light) and
+     h2y_lightdist_batch (k_lightdist), timed the same way: the same 6 B/pixel, no matrix and no transfer;
+  3. frames/s of the light-only ring from host memory, 10-bit 4:2:0, without and with want_dist.
+Prints one line per figure, then one JSON line with all of them.
+
 `streambench.py scale`: the Lanczos resampler:
   1. the kernel time of h2y_scale_batch (k_scale) over 64 distinct device frames per call (HIP events, median of five after a
      warm-up call), the bytes per frame -- the source read once plus the output written -- over that time and their share of the
@@ -1064,6 +1076,141 @@ def lightdist_main():
     print(json.dumps({"streambench_lightdist": res}), flush=True)
 
 
+def codelight_main():
+    import json
+
+    import torch
+
+    w, hh, nb, reps = 3840, 2160, 64, 5
+    n = w * hh
+    nf = int(os.environ.get("N", "60"))
+    depth = 3
+    ctx = h.Context(0)
+    res = {"width": w, "height": hh, "frames_per_call": nb, "frames_per_launch": h.CODELIGHT_FRAMES_PER_LAUNCH, "reps": reps,
+           "ring_frames": nf, "ring_depth": depth, "hbm_peak_tbs": 8.0}
+
+    def codes(count, lo, hi):
+        return torch.randint(lo, hi + 1, (count,), dtype=torch.int32, device="cuda").to(torch.int16)
+
+    def noise(chroma, bits):
+        s = 1 << (bits - 8)
+        nc = n // 4 if chroma == 1 else n
+        return lambda: torch.cat([codes(n, 16 * s, 235 * s), codes(nc, 16 * s, 240 * s), codes(nc, 16 * s, 240 * s)])
+
+    def constant():
+        return torch.cat([torch.full((n,), 600, dtype=torch.int16, device="cuda"), torch.full((n // 2,), 512, dtype=torch.int16, device="cuda")])
+
+    def letterbox():  # a 2.39:1 picture in a 16:9 frame: black bars above and below
+        bar = (hh - int(w / 2.39)) // 2 // 2 * 2
+        f = noise(1, 10)()
+        f[:bar * w] = 64
+        f[n - bar * w:n] = 64
+        for c in range(2):
+            plane = f[n + c * (n // 4):n + (c + 1) * (n // 4)]
+            plane[:bar // 2 * (w // 2)] = 512
+            plane[n // 4 - bar // 2 * (w // 2):] = 512
+        return f
+
+    def timed(calls):
+        """every call of calls in turn, reps times after a warm-up: per call its kernel times in ms per frame"""
+        out = [[] for _ in calls]
+        for rep in range(reps + 1):
+            for k, call in enumerate(calls):
+                call()
+                if rep:
+                    out[k].append(ctx.last_kernel_ms()[0] / nb)
+        return out
+
+    def report(key, label, t, nbytes, variant, **more):
+        med = float(np.median(t))
+        tbs = nbytes / (med * 1e-3) / 1e12
+        res[key] = dict(kernel_us_per_frame=round(med * 1e3, 2), min_us=round(min(t) * 1e3, 2), max_us=round(max(t) * 1e3, 2),
+                        bytes_per_frame=nbytes, kernel_tbs=round(tbs, 2), hbm_peak_fraction=round(tbs / 8.0, 3), variant=variant, **more)
+        print(f"{label:34s} {nb} frames per call: {med*1e3:7.2f} us/frame ({min(t)*1e3:.2f}..{max(t)*1e3:.2f})  {tbs:5.2f} TB/s = "
+              f"{tbs/8.0*100:4.1f} % of 8 TB/s  {variant}", flush=True)
+        return med
+
+    # 1. k_codelight, DIST off and on
+    med = {}
+    for name, chroma, bits, make in (("420_10_noise", 1, 10, noise(1, 10)), ("420_10_constant", 1, 10, constant),
+                                     ("420_10_letterbox", 1, 10, letterbox), ("444_10_noise", 3, 10, noise(3, 10))):
+        d = h.make_codelight_desc(w, hh, chroma, bits, 0, h.MATRIX_BT2020NC, 1)
+        frames = [make() for _ in range(nb)]
+        torch.cuda.synchronize()
+        variants = []
+        off, on = timed([lambda: (ctx.codelight_batch(d, frames), variants.append(ctx.last_kernel_variant())),
+                         lambda: (ctx.codelight_batch(d, frames, dist=True), variants.append(ctx.last_kernel_variant()))])
+        nbytes = n * (11 if chroma == 1 else 6)
+        med[name, 0] = report(f"k_codelight_{name}", f"k_codelight {name}", off, nbytes, variants[0])
+        med[name, 1] = report(f"k_codelight_{name}_dist", f"k_codelight {name} DIST", on, nbytes, variants[1])
+        del frames
+        torch.cuda.empty_cache()
+    for dist in (0, 1):
+        share = 1.0 - med["444_10_noise", dist] / med["420_10_noise", dist]
+        res[f"k_up444_share{'_dist' if dist else ''}"] = round(share, 3)
+        print(f"k_up444 share of the 4:2:0 time ({'DIST' if dist else 'LIGHT'}): {share*100:4.1f} %", flush=True)
+
+    # 16-bit 4:4:4, and 2. the yardsticks on the same planes
+    d = h.make_codelight_desc(w, hh, 3, 16, 0, h.MATRIX_BT2020NC, 1)
+    dl = h.make_desc(w, hh, sample=h.SAMPLE_U16, src_depth=16, dst_depth=10, src_transfer=8, dst_transfer=16, dst_matrix=h.MATRIX_BT2020NC,
+                     resampler=0, stats=[(0, 65535)] * 3)
+    frames = [noise(3, 16)() for _ in range(nb)]
+    planes = [[f[c * n:(c + 1) * n] for c in range(3)] for f in frames]
+    torch.cuda.synchronize()
+    variants = []
+    note = lambda: variants.append(ctx.last_kernel_variant())
+    off, on, light, ldist = timed([lambda: (ctx.codelight_batch(d, frames), note()), lambda: (ctx.codelight_batch(d, frames, dist=True), note()),
+                                   lambda: (ctx.light_batch(dl, planes), note()), lambda: (ctx.lightdist_batch(dl, planes), note())])
+    m_off = report("k_codelight_444_16_noise", "k_codelight 444_16_noise", off, 6 * n, variants[0])
+    m_on = report("k_codelight_444_16_noise_dist", "k_codelight 444_16_noise DIST", on, 6 * n, variants[1])
+    m_l = report("k_light_u16", "k_light U16 LINEAR (yardstick)", light, 6 * n, variants[2])
+    m_ld = report("k_lightdist_u16", "k_lightdist U16 LINEAR (yardstick)", ldist, 6 * n, variants[3])
+    res["ratio_to_k_light"] = round(m_off / m_l, 3)
+    res["ratio_to_k_lightdist"] = round(m_on / m_ld, 3)
+    print(f"k_codelight / k_light {m_off/m_l:5.3f}   k_codelight DIST / k_lightdist {m_on/m_ld:5.3f}", flush=True)
+    del frames, planes
+    torch.cuda.empty_cache()
+
+    # 3. the light-only ring from host memory
+    d = h.make_codelight_desc(w, hh, 1, 10, 0, h.MATRIX_BT2020NC, 1)
+    host = noise(1, 10)().cpu().numpy().view(np.uint16)
+    parts = [host[:n], host[n:n + n // 4], host[n + n // 4:]]
+
+    def ring(want_dist):
+        ctx.codelight_stream_open(d, want_dist, depth)
+        inflight = 0
+        t0 = time.perf_counter()
+
+        def take():
+            ctx.stream_output()
+            ctx.stream_light_result()
+            if want_dist:
+                ctx.stream_lightdist_result()
+
+        for _ in range(nf):
+            slot = ctx.stream_input()
+            for c in range(3):
+                slot[c][:] = parts[c]
+            ctx.stream_submit()
+            inflight += 1
+            if inflight == depth - 1:
+                take()
+                inflight -= 1
+        while inflight:
+            take()
+            inflight -= 1
+        dt = (time.perf_counter() - t0) / nf
+        ctx.stream_close()
+        return dt
+
+    ring(0)  # warm-up
+    t_light, t_dist = ring(0), ring(1)
+    res["light_only_ring"] = dict(light_fps=round(1 / t_light, 1), dist_fps=round(1 / t_dist, 1), bytes_per_frame=3 * n)
+    print(f"light-only ring from host memory, 10-bit 4:2:0: {1/t_light:6.1f} frames/s   with want_dist {1/t_dist:6.1f} frames/s", flush=True)
+    ctx.close()
+    print(json.dumps({"streambench_codelight": res}), flush=True)
+
+
 def scale_main():
     import json
 
@@ -1381,5 +1528,7 @@ if __name__ == "__main__":
         light_main()
     elif sys.argv[1:] == ["lightdist"]:
         lightdist_main()
+    elif sys.argv[1:] == ["codelight"]:
+        codelight_main()
     else:
         main()
