@@ -41,6 +41,7 @@ EXPORTS = [
     "h2y_codelight_batch", "h2y_codelight_stream_open",
     "h2y_scale_taps", "h2y_scale_frame_bytes", "h2y_scale_batch", "h2y_stream_scale", "h2y_scale_stream_open",
     "h2y_gamut_matrix", "h2y_gamut_batch", "h2y_stream_gamut",
+    "h2y_tonemap_curve", "h2y_tonemap_batch", "h2y_stream_tonemap",
     "h2y_ctx_set_chroma_siting", "h2y_subsample_420_sited",
     "h2y_ctx_set_inverse_chroma_siting", "h2y_upsample_444_sited",
 ]
@@ -56,6 +57,7 @@ LIGHTDIST_PCT = (100, 500, 1000, 2500, 5000, 7500, 9000, 9500, 9900, 9998)  # th
 CODELIGHT_FRAMES_PER_LAUNCH = 8  # a launch's 4:2:0 scratch stays at 253 MiB for 3840 x 2160
 SCALE_FRAMES_PER_LAUNCH = 64
 GAMUT_FRAMES_PER_LAUNCH = 64
+TONEMAP_FRAMES_PER_LAUNCH = 64
 SCALE_TAPS = 32  # coefficients per row of scale_taps' table
 
 
@@ -457,6 +459,12 @@ def load_library():
     L.h2y_gamut_batch.restype = C.c_int
     L.h2y_stream_gamut.argtypes = [C.c_void_p] + [C.c_int] * 3
     L.h2y_stream_gamut.restype = C.c_int
+    L.h2y_tonemap_curve.argtypes = [C.c_int] * 3 + [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_char_p)]
+    L.h2y_tonemap_curve.restype = C.c_int
+    L.h2y_tonemap_batch.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.h2y_tonemap_batch.restype = C.c_int
+    L.h2y_stream_tonemap.argtypes = [C.c_void_p] + [C.c_int] * 3
+    L.h2y_stream_tonemap.restype = C.c_int
     L.h2y_stream_open.argtypes = [C.c_void_p, C.POINTER(H2YDesc), C.c_int]
     L.h2y_stream_input.restype = C.c_int
     L.h2y_stream_input.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
@@ -616,6 +624,19 @@ def gamut_matrix(src_primaries: int, dst_primaries: int) -> np.ndarray:
     if rc != H2Y_OK:
         raise H2YError(rc, (why.value or b"").decode())
     return m.reshape(3, 3)
+
+
+def tonemap_curve(src_peak: int, dst_peak: int, relative: int):
+    """h2y_tonemap_curve (host only, no device): (the LIGHTDIST_BINS float32 gains of the BT.2390 curve from src_peak to dst_peak
+    cd/m2 on the light distribution's nodes, the cap as a float32).  Raises H2YError (EINVAL: peaks or relative out of range)."""
+    gain = np.zeros(LIGHTDIST_BINS, dtype=np.float32)
+    cap = C.c_float()
+    why = C.c_char_p()
+    rc = load_library().h2y_tonemap_curve(int(src_peak), int(dst_peak), int(relative), gain.ctypes.data_as(C.POINTER(C.c_float)),
+                                          C.byref(cap), C.byref(why))
+    if rc != H2Y_OK:
+        raise H2YError(rc, (why.value or b"").decode())
+    return gain, np.float32(cap.value)
 
 
 def scale_frame_bytes(width: int, height: int, chroma: int) -> int:
@@ -945,7 +966,27 @@ class Context:
                 outs[3 * f + c] = self._ptr(frames_dst[f][c])
         self._check(self.lib.h2y_gamut_batch(self.h, width, height, sample, src_primaries, dst_primaries, clip, n, ins, outs))
 
+    def tonemap_batch(self, width, height, sample, src_peak, dst_peak, relative, frames_src, frames_dst=None) -> None:
+        """k_tonemap on device frames (frames_src[f] = three device planes G, B, R of float or half samples in linear light, 16-byte
+        aligned): frames_dst[f] receives them mapped from src_peak to dst_peak cd/m2; frames_dst None: in place."""
+        frames_dst = frames_src if frames_dst is None else frames_dst
+        n = len(frames_src)
+        if len(frames_dst) != n:
+            raise ValueError("frames_src and frames_dst differ in length")
+        ins = (C.c_void_p * max(3 * n, 1))()
+        outs = (C.c_void_p * max(3 * n, 1))()
+        for f in range(n):
+            for c in range(3):
+                ins[3 * f + c] = self._ptr(frames_src[f][c])
+                outs[3 * f + c] = self._ptr(frames_dst[f][c])
+        self._check(self.lib.h2y_tonemap_batch(self.h, width, height, sample, src_peak, dst_peak, relative, n, ins, outs))
+
     # ---- host <-> device pipeline -----------------------------------------------------------
+    def stream_tonemap(self, src_peak, dst_peak, relative) -> None:
+        """Arm an open forward ring of float or half planes (plain, DPX or EXR) that was opened with the 0 / 1 statistics override:
+        every slot's decoded planes are tone-mapped in place, after stream_gamut's pass, before the conversion (h2y_stream_tonemap)."""
+        self._check(self.lib.h2y_stream_tonemap(self.h, src_peak, dst_peak, relative))
+
     def stream_gamut(self, src_primaries, dst_primaries, clip=1) -> None:
         """Arm an open forward ring of float or half planes (plain, DPX or EXR): every slot's decoded planes are converted in
         place from src_primaries to dst_primaries before pic_stats and the conversion (h2y_stream_gamut)."""

@@ -74,6 +74,19 @@
  *             (exit 1, also under --dry_run): a value other than 0 or 1, --gamut_clip without --gamut_convert 1, a source transfer
  *             other than 8 (LINEAR), a source matrix other than 0 (G,B,R), primaries other than 1, 8, 9, 10 and 12 or a pair of equal
  *             chromaticities, .rgb, .tiff and .yuv input, the .yuv -> RGB flow, --compare_only, --histogram_only and --scale_only.
+ * --tone_map 1 [--tone_map_src_peak S] [--tone_map_dst_peak D] (an addition; the reference has no tone mapper, its README sends the
+ *             user to ctlrender): the decoded source planes, after --gamut_convert's pass where that is given, are brought from a
+ *             mastering peak of S cd/m2 (1000 by default) down to a target peak of D cd/m2 (100 by default) on the device by the
+ *             BT.2390 curve on max(R, G, B), one gain per pixel (include/hdr2yuv_hip.h, "tone mapping", states every step), before
+ *             the unchanged forward conversion.  For --dst_transfer_characteristics 16 the output stays in units of 10000 cd/m2
+ *             (absolute); for every other destination transfer it is display-referred, 1.0 = D (relative).  With the flag the run
+ *             takes floor 0 and ceiling 1 for every frame instead of its pic_stats: mapped planes are referred to their target.
+ *             On the forward flow from .f32, .f16, .exr and .dpx to .yuv, with or without --dst_filename, with any --gpus, beside
+ *             --gamut_convert, --scale, --dst_chroma_sample_loc_type, --ref_filename, --ssim and --histogram, and for a PQ
+ *             destination beside --content_light and --dynamic_metadata, which then measure the mapped light.  Refused (exit 1,
+ *             also under --dry_run): a value other than 0 or 1, a peak flag without --tone_map 1, peaks outside 100 <= D < S <=
+ *             10000, a source transfer other than 8 (LINEAR), a source matrix other than 0 (G,B,R), a destination transfer of 8,
+ *             .rgb, .tiff and .yuv input, the .yuv -> RGB flow and every *_only flow.
  * --dst_chroma_sample_loc_type 0|2 (an addition; the reference carries chroma_sample_loc_type through pic_t and prints it,
  *             hdr2yuv.cpp:490 and :505, parses no flag for it and never acts on it): 2 writes the 4:2:0 chroma co-sited with the
  *             top-left luma sample of every 2x2 block, as HDR10 and UHD Blu-ray assume (include/hdr2yuv_hip.h states every step); 0
@@ -106,6 +119,7 @@
 #define H2Y_CLI_ARGS_H
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -149,6 +163,10 @@ struct cli_args {
     /* --gamut_convert 1: the source planes go from the source's to the destination's primaries; --gamut_clip (1 by default) */
     int gamut = 0, gamut_clip = 1;
     bool gamut_given = false, gamut_clip_given = false;
+    /* --tone_map 1: the source planes go from a mastering peak of tone_src_peak cd/m2 down to tone_dst_peak; tone_relative, resolved:
+     * the output is display-referred (1.0 = tone_dst_peak) for every destination transfer but PQ */
+    int tone_map = 0, tone_src_peak = 1000, tone_dst_peak = 100, tone_relative = 1;
+    bool tone_map_given = false, tone_src_peak_given = false, tone_dst_peak_given = false;
     /* --dst_chroma_sample_loc_type: 0 as the resampler sites the 4:2:0 chroma, 2 top-left */
     int siting = 0;
     bool siting_given = false;
@@ -232,6 +250,9 @@ static inline void cli_help()
            "  primaries: [--gamut_convert 1 [--gamut_clip 0|1]] (float or half G,B,R source planes in linear light converted from\n"
            "  --src_colour_primaries to --dst_colour_primaries on the GPU before the conversion; 1 BT.709, 8 / 9 BT.2020, 12 P3-D65,\n"
            "  10 XYZ; what is not above 0 is clipped to 0 unless --gamut_clip 0)\n"
+           "  tone mapping: [--tone_map 1 [--tone_map_src_peak S] [--tone_map_dst_peak D]] (float or half G,B,R source planes in linear\n"
+           "  light brought from a mastering peak of S cd/m2, 1000 by default, down to D, 100 by default, on the GPU by the BT.2390\n"
+           "  curve on max(R,G,B) before the conversion: the SDR rung of an HDR master, or a 1000 cd/m2 PQ rung of a 4000 cd/m2 one)\n"
            "  chroma siting: [--dst_chroma_sample_loc_type 0|2] (2: 4:2:0 chroma co-sited with the top-left luma sample, as HDR10\n"
            "  assumes -- x265 --chromaloc 2, SVT-AV1 --chroma-sample-position topleft; needs the FIR resampler; 0: as without the flag)\n"
            "  [--src_chroma_sample_loc_type 0|2] (.yuv -> .rgb / .tiff with --src_chroma_format_idc 1; 2: the 4:2:0 chroma is co-sited\n"
@@ -269,6 +290,9 @@ static inline void cli_parse(cli_args &a, int argc, char **argv)
         else if (is("--dynamic_metadata")) a.dynmeta = val();
         else if (is("--gamut_convert")) { a.gamut = atoi(val()); a.gamut_given = true; }
         else if (is("--gamut_clip")) { a.gamut_clip = atoi(val()); a.gamut_clip_given = true; }
+        else if (is("--tone_map")) { a.tone_map = atoi(val()); a.tone_map_given = true; }
+        else if (is("--tone_map_src_peak")) { a.tone_src_peak = atoi(val()); a.tone_src_peak_given = true; }
+        else if (is("--tone_map_dst_peak")) { a.tone_dst_peak = atoi(val()); a.tone_dst_peak_given = true; }
         else if (is("--dst_chroma_sample_loc_type")) { a.siting = atoi(val()); a.siting_given = true; }
         else if (is("--src_chroma_sample_loc_type")) { a.src_siting = atoi(val()); a.src_siting_given = true; }
         else if (is("--histogram")) a.hist = val();
@@ -449,6 +473,7 @@ static inline int cli_resolve_dynmeta(cli_args &a);
 static inline int cli_resolve_scale_only(cli_args &a);
 static inline int cli_resolve_scale(cli_args &a);
 static inline int cli_resolve_gamut(cli_args &a, int src_matrix_arg);
+static inline int cli_resolve_tone_map(cli_args &a, int src_matrix_arg);
 static inline int cli_resolve_siting(cli_args &a);
 static inline int cli_resolve_src_siting(cli_args &a);
 static inline int cli_resolve_light_only(cli_args &a);
@@ -473,6 +498,7 @@ static inline int cli_resolve(cli_args &a)
     if (a.dynmeta) arg_errors += cli_resolve_dynmeta(a);
     if (a.scale_given || a.scale_only || a.scale_taps_given) arg_errors += cli_resolve_scale(a);
     if (a.gamut_given || a.gamut_clip_given) arg_errors += cli_resolve_gamut(a, src_matrix_arg);
+    if (a.tone_map_given || a.tone_src_peak_given || a.tone_dst_peak_given) arg_errors += cli_resolve_tone_map(a, src_matrix_arg);
     if (a.siting_given) arg_errors += cli_resolve_siting(a);
     if (a.src_siting_given) arg_errors += cli_resolve_src_siting(a);
     return arg_errors;
@@ -619,7 +645,7 @@ static inline int cli_resolve_light(cli_args &a)
     if (!a.light) return 0;
     if (cli_light_scope(a, "--content_light 1")) return 1;
     printf("content_light_from: src_transfer_characteristics %d -> PQ, G,B,R, floor and ceiling %s\n", a.in.transfer_characteristics,
-           "of each frame's pic_stats");
+           a.tone_map == 1 ? "0 and 1 (--tone_map 1)" : "of each frame's pic_stats");
     return 0;
 }
 
@@ -655,6 +681,10 @@ static inline int cli_resolve_light_only(cli_args &a)
     }
     if (a.compare_only || a.hist_only || a.scale_only) {
         printf("WARNING: --light_only 1: not with --%s 1\n", a.compare_only ? "compare_only" : a.hist_only ? "histogram_only" : "scale_only");
+        arg_errors++;
+    }
+    if (a.tone_map_given || a.tone_src_peak_given || a.tone_dst_peak_given) {
+        printf("WARNING: --tone_map maps a conversion's source: not with --light_only 1\n");
         arg_errors++;
     }
     printf("src_filename: %s\n", a.src ? a.src : "(none)");
@@ -740,7 +770,8 @@ static inline int cli_resolve_dynmeta(cli_args &a)
         return 1;
     }
     printf("dynamic_metadata_from: src_transfer_characteristics %d -> PQ, G,B,R, floor and ceiling %s; HDR10+ profile A, one scene, "
-           "percentiles of max(R,G,B) in %d bins\n", a.in.transfer_characteristics, "of each frame's pic_stats", H2Y_LIGHTDIST_BINS);
+           "percentiles of max(R,G,B) in %d bins\n", a.in.transfer_characteristics,
+           a.tone_map == 1 ? "0 and 1 (--tone_map 1)" : "of each frame's pic_stats", H2Y_LIGHTDIST_BINS);
     return 0;
 }
 
@@ -794,6 +825,78 @@ static inline int cli_resolve_gamut(cli_args &a, int src_matrix_arg)
     printf("gamut_matrix:");
     for (int i = 0; i < 9; i++) printf(" %.9g", m[i]);
     printf("\n");
+    return 0;
+}
+
+/* ST 2084's inverse EOTF and its inverse in binary64, as include/hdr2yuv_hip.h states them: for the knee the banner prints */
+static inline double cli_pq_n(double l)
+{
+    const double p = pow(l, 2610.0 / 16384.0);
+    return pow((3424.0 / 4096.0 + 2413.0 / 4096.0 * 32.0 * p) / (1.0 + 2392.0 / 4096.0 * 32.0 * p), 2523.0 / 4096.0 * 128.0);
+}
+static inline double cli_pq_n_inv(double v)
+{
+    const double p = pow(v, 1.0 / (2523.0 / 4096.0 * 128.0)), num = p - 3424.0 / 4096.0;
+    return pow((num > 0.0 ? num : 0.0) / (2413.0 / 4096.0 * 32.0 - 2392.0 / 4096.0 * 32.0 * p), 1.0 / (2610.0 / 16384.0));
+}
+
+/* --tone_map / --tone_map_src_peak / --tone_map_dst_peak: the forward flow's float or half G,B,R planes in linear light, between
+ * two peaks the library's curve takes (src_matrix_arg: --src_matrix_coeffs as given); prints the peaks, the output's reference and
+ * the knee; returns the number of argument errors */
+static inline int cli_resolve_tone_map(cli_args &a, int src_matrix_arg)
+{
+    printf("tone_map: %d\n", a.tone_map);
+    if (a.tone_map != 0 && a.tone_map != 1) {
+        printf("WARNING: tone_map(%d) not 0 or 1\n", a.tone_map);
+        return 1;
+    }
+    if (!a.tone_map) {
+        if (a.tone_src_peak_given || a.tone_dst_peak_given) {
+            printf("WARNING: --tone_map_src_peak and --tone_map_dst_peak need --tone_map 1\n");
+            return 1;
+        }
+        return 0;
+    }
+    printf("tone_map_src_peak: %d%s\ntone_map_dst_peak: %d%s\n", a.tone_src_peak, a.tone_src_peak_given ? "" : " (default)",
+           a.tone_dst_peak, a.tone_dst_peak_given ? "" : " (default)");
+    if (a.compare_only || a.hist_only || a.scale_only) {
+        printf("WARNING: --tone_map 1 maps a conversion's source: not with --%s 1\n",
+               a.compare_only ? "compare_only" : a.hist_only ? "histogram_only" : "scale_only");
+        return 1;
+    }
+    if (a.inverse) {
+        printf("WARNING: --tone_map 1 maps the forward flow's source (to .yuv), not the .yuv -> RGB flow\n");
+        return 1;
+    }
+    if (a.in_type != CLI_IN_F32 && a.in_type != CLI_IN_F16 && a.in_type != CLI_IN_EXR && a.in_type != CLI_IN_DPX) {
+        printf("WARNING: --tone_map 1 maps float or half planes (.f32, .f16, .exr, .dpx input), not .%s input\n",
+               a.in_type == CLI_IN_SYNTH ? "(synthetic)" : cli_ext_of(a.src));
+        return 1;
+    }
+    if (a.in.transfer_characteristics != H2Y_TRANSFER_LINEAR) {
+        printf("WARNING: --tone_map 1 maps linear light: src_transfer_characteristics(%d) is not %d\n", a.in.transfer_characteristics,
+               H2Y_TRANSFER_LINEAR);
+        return 1;
+    }
+    if (src_matrix_arg != H2Y_MATRIX_GBR) { /* the readers would override it: a source called Y'CbCr is not one to map as R, G, B */
+        printf("WARNING: --tone_map 1 needs a G,B,R source: src_matrix_coeffs(%d) is not %d\n", src_matrix_arg, H2Y_MATRIX_GBR);
+        return 1;
+    }
+    if (a.out.transfer_characteristics == H2Y_TRANSFER_LINEAR) {
+        printf("WARNING: --tone_map 1 maps light for a display: dst_transfer_characteristics(%d) keeps linear light\n",
+               a.out.transfer_characteristics);
+        return 1;
+    }
+    a.tone_relative = a.out.transfer_characteristics != 16;
+    std::vector<float> gain(H2Y_LIGHTDIST_BINS);
+    float cap = 0.0f;
+    const char *why = nullptr;
+    if (h2y_tonemap_curve(a.tone_src_peak, a.tone_dst_peak, a.tone_relative, gain.data(), &cap, &why)) {
+        printf("WARNING: --tone_map 1: tone_map_src_peak(%d) -> tone_map_dst_peak(%d): %s\n", a.tone_src_peak, a.tone_dst_peak, why);
+        return 1;
+    }
+    const double W = cli_pq_n(a.tone_src_peak / 10000.0), ks = 1.5 * (cli_pq_n(a.tone_dst_peak / 10000.0) / W) - 0.5;
+    printf("tone_map_output: %s\ntone_map_knee: %.9g\n", a.tone_relative ? "relative" : "absolute", 10000.0 * cli_pq_n_inv(ks * W));
     return 0;
 }
 
@@ -1076,6 +1179,10 @@ static inline void cli_make_desc(const cli_args &a, h2y_desc *d)
     d->dst_full_range = a.out.video_full_range_flag;
     d->dst_chroma_format_idc = a.out.chroma_format_idc;
     d->chroma_resampler_type = a.resampler;
+    if (a.tone_map) { /* mapped planes are referred to their target: floor 0 and ceiling 1, not each frame's pic_stats */
+        d->stats_override = 1;
+        for (int c = 0; c < 3; c++) d->floor[c] = 0, d->ceiling[c] = 1;
+    }
 }
 
 #endif /* H2Y_CLI_ARGS_H */

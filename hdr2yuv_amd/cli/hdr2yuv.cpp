@@ -98,6 +98,13 @@
  * held the converted planes, and --content_light beside it measures the converted light.  The banner carries gamut_convert:,
  * gamut_clip: and the nine entries of gamut_matrix: as "%.9g".
  *
+ * Tone mapping (--tone_map 1 [--tone_map_src_peak S] [--tone_map_dst_peak D] on the forward flow from .f32, .f16, .exr and .dpx;
+ * h2y_cli_args.h): each GPU thread opens its ring with floor 0 and ceiling 1 for every frame and arms it (h2y_stream_tonemap), so
+ * every slot's decoded planes are mapped in place on the device, after --gamut_convert's pass, before the conversion: the run
+ * writes the bytes it would write had the source held the mapped planes, and --content_light and --dynamic_metadata beside it
+ * measure the mapped light.  The banner carries tone_map:, tone_map_src_peak:, tone_map_dst_peak: ("(default)" where not given),
+ * tone_map_output: relative|absolute and the knee in cd/m2 as tone_map_knee: "%.9g".
+ *
  * Chroma siting (--dst_chroma_sample_loc_type 0|2 on the forward flow to .yuv; h2y_cli_args.h): each GPU thread sets its context's
  * siting (h2y_ctx_set_chroma_siting) before it opens its ring, so every frame, and whatever is armed on the ring, has its 4:2:0
  * chroma where the flag says.  The banner carries dst_chroma_sample_loc_type: only when the flag is given, and with 2 it ends with
@@ -346,6 +353,7 @@ static flow forward_flow(const job &j)
                (a.hist && h2y_stream_histogram(ctx, a.hist_bits)) || (a.light && h2y_stream_light(ctx)) ||
                (a.dynmeta && h2y_stream_lightdist(ctx)) ||
                (a.gamut && h2y_stream_gamut(ctx, a.in.colour_primaries, a.out.colour_primaries, a.gamut_clip)) ||
+               (a.tone_map && h2y_stream_tonemap(ctx, a.tone_src_peak, a.tone_dst_peak, a.tone_relative)) ||
                (a.scale && h2y_stream_scale(ctx, a.out.width, a.out.height, a.scale_taps));
     };
     if (a.in_type == CLI_IN_DPX) { /* the payload as the file holds it, straight into the pinned slot */

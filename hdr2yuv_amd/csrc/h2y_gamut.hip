@@ -13,11 +13,9 @@
 #include <hip/hip_runtime.h>
 
 #include "h2y_kernels.h"
+#include "h2y_planes.h"
 
 namespace {
-
-#define H2Y_GLOBAL __attribute__((address_space(1)))
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4))); /* one 16-byte access */
 
 /* (r, g, b) -> o = M (r, g, b), clipped at 0 where asked: o[0] = R', o[1] = G', o[2] = B' */
 __device__ __forceinline__ void gamut_pixel(const gamut_args &a, float r, float g, float b, float o[3])
@@ -27,36 +25,6 @@ __device__ __forceinline__ void gamut_pixel(const gamut_args &a, float r, float 
         o[i] = a.clip ? (s > 0.0f ? s : 0.0f) : s; /* a NaN, -0.0 and every negative: +0.0 */
     }
 }
-
-template <int IN> struct gamut_sample;
-template <> struct gamut_sample<H2Y_IN_F32> {
-    typedef uint32_t bits;
-    static constexpr uint32_t per_group = 4; /* pixels of one 16-byte access */
-    static __device__ __forceinline__ float widen(uint32_t u) { return __builtin_bit_cast(float, u); }
-    static __device__ __forceinline__ uint32_t narrow(float f) { return __builtin_bit_cast(uint32_t, f); }
-    static __device__ __forceinline__ void unpack(const u32x4 v, float f[4])
-    {
-        f[0] = widen(v.x), f[1] = widen(v.y), f[2] = widen(v.z), f[3] = widen(v.w);
-    }
-    static __device__ __forceinline__ u32x4 pack(const float f[4]) { return u32x4{narrow(f[0]), narrow(f[1]), narrow(f[2]), narrow(f[3])}; }
-};
-template <> struct gamut_sample<H2Y_IN_F16> {
-    typedef uint16_t bits;
-    static constexpr uint32_t per_group = 8;
-    static __device__ __forceinline__ float widen(uint32_t u) { return (float)__builtin_bit_cast(_Float16, (uint16_t)u); } /* exact */
-    static __device__ __forceinline__ uint32_t narrow(float f) { return __builtin_bit_cast(uint16_t, (_Float16)f); } /* to nearest even; inf past 65504 */
-    static __device__ __forceinline__ void unpack(const u32x4 v, float f[8])
-    {
-        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-        for (int k = 0; k < 4; k++) f[2 * k] = widen(w[k] & 0xFFFFu), f[2 * k + 1] = widen(w[k] >> 16);
-    }
-    static __device__ __forceinline__ u32x4 pack(const float f[8])
-    {
-        uint32_t w[4];
-        for (int k = 0; k < 4; k++) w[k] = narrow(f[2 * k]) | narrow(f[2 * k + 1]) << 16;
-        return u32x4{w[0], w[1], w[2], w[3]};
-    }
-};
 
 } // namespace
 
@@ -68,7 +36,7 @@ template <> struct gamut_sample<H2Y_IN_F16> {
 template <int IN>
 __global__ __launch_bounds__(256) void k_gamut(gamut_args a, const gamut_frame *frames, int n_frames)
 {
-    typedef gamut_sample<IN> S;
+    typedef plane_sample<IN> S;
     typedef typename S::bits bits;
     constexpr uint32_t G = S::per_group;
     const uint32_t groups = a.npix / G, tail = a.npix - groups * G;

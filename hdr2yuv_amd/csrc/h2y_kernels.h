@@ -396,6 +396,16 @@ struct gamut_args {
 uint32_t h2y_gamut_chunks(int in_kind, uint32_t npix); /* k_gamut's units of 256 threads per frame */
 hipError_t h2y_launch_gamut(int in_kind, int grid, hipStream_t st, const gamut_args &a, const gamut_frame *frames, int n_frames);
 
+/* k_tonemap (h2y_tonemap.hip): the tone curve of include/hdr2yuv_hip.h on frames of three float or half planes G, B, R in linear
+ * light, k_gamut's frame table (dst may be src: in place) */
+struct tonemap_args {
+    uint32_t npix;     /* pixels per frame (< 2^28) */
+    float cap;         /* no sample leaves the pass above it */
+    const float *gain; /* device: H2Y_LIGHTDIST_BINS gains, h2y_tonemap_curve's */
+};
+int h2y_tonemap_grid(int n_cu, uint64_t units); /* blocks for so many of k_gamut's units (h2y_gamut_chunks per frame) */
+hipError_t h2y_launch_tonemap(int in_kind, int grid, hipStream_t st, const tonemap_args &a, const gamut_frame *frames, int n_frames);
+
 /* k_scale (h2y_scale.hip): the Lanczos resampler of include/hdr2yuv_hip.h on frames of three u16 planes.  One axis' table on the
  * device: first[d] and count[d] (int32), then d rows of H2Y_SCALE_MAX_TAPS int16 coefficients (zero past count). */
 enum { H2Y_SCALE_MAX_TAPS = 32, H2Y_SCALE_TILE_W = 64, H2Y_SCALE_TILE_H = 32, H2Y_SCALE_STAGE_ROWS = 16 };

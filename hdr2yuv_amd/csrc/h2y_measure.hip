@@ -1606,3 +1606,156 @@ int h2y_stream_gamut(h2y_ctx *ctx, int src_primaries, int dst_primaries, int cli
     st->table(st->tab, tab);
     return stage_arm(ctx, STAGE_GAMUT, std::move(st), "gamut");
 }
+
+/* ---- tone mapping (--tone_map; the reference has no tone mapper) ------------------------------------------------------------------ */
+
+namespace {
+
+/* ST 2084's inverse EOTF and its inverse, in binary64 */
+const double kPqM1 = 2610.0 / 16384.0, kPqM2 = 2523.0 / 4096.0 * 128.0, kPqC1 = 3424.0 / 4096.0, kPqC2 = 2413.0 / 4096.0 * 32.0,
+             kPqC3 = 2392.0 / 4096.0 * 32.0;
+double pq_n(double l)
+{
+    const double p = pow(l, kPqM1);
+    return pow((kPqC1 + kPqC2 * p) / (1.0 + kPqC3 * p), kPqM2);
+}
+double pq_n_inv(double v)
+{
+    const double p = pow(v, 1.0 / kPqM2), num = p - kPqC1;
+    return pow((num > 0.0 ? num : 0.0) / (kPqC2 - kPqC3 * p), 1.0 / kPqM1);
+}
+
+const char *tonemap_params_why(int src_peak, int dst_peak, int relative)
+{
+    if (dst_peak < 100 || dst_peak >= src_peak || src_peak > 10000) return "peaks outside 100 <= dst_peak < src_peak <= 10000 cd/m2";
+    if (relative != 0 && relative != 1) return "relative must be 0 or 1";
+    return nullptr;
+}
+
+} // namespace
+
+int h2y_tonemap_curve(int src_peak, int dst_peak, int relative, float gain[H2Y_LIGHTDIST_BINS], float *cap, const char **why)
+{
+    const char *dummy;
+    if (!why) why = &dummy;
+    *why = "";
+    if (!gain || !cap) { *why = "null gain table or cap"; return H2Y_EINVAL; }
+    if (const char *w = tonemap_params_why(src_peak, dst_peak, relative)) { *why = w; return H2Y_EINVAL; }
+    const double W = pq_n(src_peak / 10000.0), max_lum = pq_n(dst_peak / 10000.0) / W, ks = 1.5 * max_lum - 0.5;
+    const double u = relative ? dst_peak / 10000.0 : 1.0, inv_u = relative ? 10000.0 / dst_peak : 1.0;
+    gain[0] = (float)inv_u;
+    for (uint32_t k = 1; k < H2Y_LIGHTDIST_BINS; k++) {
+        const uint32_t bits = H2Y_LIGHTDIST_FIRST_BITS + ((k - 1u) << 14);
+        float ef;
+        memcpy(&ef, &bits, sizeof ef);
+        const double e = ef, n = pq_n(e) / W, e1 = n < 1.0 ? n : 1.0;
+        if (e1 < ks) { gain[k] = (float)inv_u; continue; }
+        const double t = (e1 - ks) / (1.0 - ks), t2 = t * t, t3 = t2 * t;
+        const double e2 = (2.0 * t3 - 3.0 * t2 + 1.0) * ks + (t3 - 2.0 * t2 + t) * (1.0 - ks) + (-2.0 * t3 + 3.0 * t2) * max_lum;
+        gain[k] = (float)(pq_n_inv(e2 * W) / (e * u));
+    }
+    *cap = relative ? 1.0f : (float)(dst_peak / 10000.0);
+    return H2Y_OK;
+}
+
+/* k_tonemap's arguments for frames of width x height and a pair of peaks, but for the device table; the checks of both entries */
+static int tonemap_args_of(h2y_ctx *ctx, int width, int height, int sample_type, int src_peak, int dst_peak, int relative,
+                           tonemap_args &a, std::vector<float> &gain)
+{
+    if (sample_type == H2Y_SAMPLE_U16)
+        return fail(ctx, H2Y_EUNSUPPORTED, "tone mapping works in linear light on float or half planes, not on U16 samples");
+    if (sample_type != H2Y_SAMPLE_F32 && sample_type != H2Y_SAMPLE_F16) return fail(ctx, H2Y_EINVAL, "bad sample type %d", sample_type);
+    if (width < 1 || height < 1 || (uint64_t)width * (uint64_t)height >= (1ull << 28)) return fail(ctx, H2Y_EINVAL, "bad picture size");
+    gain.resize(H2Y_LIGHTDIST_BINS);
+    const char *why;
+    const int rc = h2y_tonemap_curve(src_peak, dst_peak, relative, gain.data(), &a.cap, &why);
+    if (rc) return fail(ctx, rc, "tone map %d -> %d cd/m2, relative %d: %s", src_peak, dst_peak, relative, why);
+    a.npix = (uint32_t)width * (uint32_t)height;
+    return H2Y_OK;
+}
+
+int h2y_tonemap_batch(h2y_ctx *ctx, int width, int height, int sample_type, int src_peak, int dst_peak, int relative, int n_frames,
+                      const void *const *d_src, void *const *d_dst)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
+    tonemap_args a{};
+    std::vector<float> gain;
+    int rc = tonemap_args_of(ctx, width, height, sample_type, src_peak, dst_peak, relative, a, gain);
+    if (rc) return rc;
+    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
+    if (!d_src || !d_dst) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
+    for (int f = 0; f < n_frames; f++)
+        for (int c = 0; c < 3; c++) {
+            const void *i = d_src[3 * f + c], *o = d_dst[3 * f + c];
+            if (!i || !o) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is null", f, c);
+            if (((uintptr_t)i | (uintptr_t)o) & 15u) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is not 16-byte aligned", f, c);
+        }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    gamut_frame *h;
+    rc = frame_table(ctx, n_frames, h);
+    if (!rc) rc = ensure(ctx, ctx->d_tonemap_gain, ctx->tonemap_gain_cap, gain.size() * sizeof(float));
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpy(ctx->d_tonemap_gain, gain.data(), gain.size() * sizeof(float), hipMemcpyHostToDevice));
+    a.gain = ctx->d_tonemap_gain;
+    for (int f = 0; f < n_frames; f++)
+        for (int c = 0; c < 3; c++) h[f].src[c] = d_src[3 * f + c], h[f].dst[c] = d_dst[3 * f + c];
+    const int in_kind = sample_type == H2Y_SAMPLE_F16 ? H2Y_IN_F16 : H2Y_IN_F32;
+    const uint64_t per_frame = h2y_gamut_chunks(in_kind, a.npix);
+    rc = timed_launches(ctx, h, n_frames, H2Y_TONEMAP_FRAMES_PER_LAUNCH, "k_tonemap", [&](const gamut_frame *frames, int, int nf) {
+        return h2y_launch_tonemap(in_kind, h2y_tonemap_grid(ctx->n_cu, per_frame * nf), ctx->stream, a, frames, nf);
+    });
+    if (rc) return rc;
+    ctx->last_variant = std::string("k_tonemap<") + (in_kind == H2Y_IN_F16 ? "F16" : "F32") + (relative ? ",RELATIVE>" : ",ABSOLUTE>");
+    return H2Y_OK;
+}
+
+/* The curve's ring stage, in place on a forward ring's decoded planes after the gamut stage's pass and before the conversion:
+ * k_tonemap's arguments, the gain table and its frame table entry per slot.  It leaves nothing of its own behind. */
+struct tonemap_stage : ring_stage {
+    tonemap_args a{};
+    gamut_frame *tab = nullptr;
+    int in_kind = H2Y_IN_F32;
+    int grid = 1;
+    int decoded(h2y_ctx *ctx, int k) override
+    {
+        HIP_TRY(ctx, h2y_launch_tonemap(in_kind, grid, ctx->stream, a, tab + k, 1));
+        return H2Y_OK;
+    }
+    int run(h2y_ctx *, int) override { return H2Y_OK; }
+};
+
+int h2y_stream_tonemap(h2y_ctx *ctx, int src_peak, int dst_peak, int relative)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    if (ctx->s_kind != h2y_ctx::RING_FORWARD) return fail(ctx, H2Y_EINVAL, "tone mapping works on the forward rings only");
+    if (ctx->s_stage[STAGE_TONEMAP]) return fail(ctx, H2Y_EINVAL, "the ring maps tones already");
+    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    const h2y_desc *d = &ctx->s_desc;
+    auto st = std::make_unique<tonemap_stage>();
+    std::vector<float> gain;
+    int rc = tonemap_args_of(ctx, d->width, d->height, d->in_sample_type, src_peak, dst_peak, relative, st->a, gain);
+    if (rc) return rc;
+    if (d->src_transfer != H2Y_TRANSFER_LINEAR)
+        return fail(ctx, H2Y_EUNSUPPORTED, "tone mapping works in linear light (src_transfer 8), not src_transfer %d", d->src_transfer);
+    if (d->src_matrix != H2Y_MATRIX_GBR)
+        return fail(ctx, H2Y_EUNSUPPORTED, "tone mapping needs a G,B,R source (src_matrix 0), not src_matrix %d", d->src_matrix);
+    bool unit = d->stats_override == 1;
+    for (int c = 0; c < 3; c++) unit = unit && d->floor[c] == 0 && d->ceiling[c] == 1;
+    if (!unit)
+        return fail(ctx, H2Y_EINVAL, "tone-mapped planes are referred to their target: open the ring with stats_override 1, floor 0 and "
+                                     "ceiling 1 on all three planes");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    st->in_kind = in_kind_of(d);
+    st->grid = h2y_tonemap_grid(ctx->n_cu, h2y_gamut_chunks(st->in_kind, st->a.npix));
+    float *d_gain = nullptr;
+    st->table(d_gain, gain);
+    st->a.gain = d_gain;
+    const int depth = (int)ctx->ss.size();
+    std::vector<gamut_frame> tab(depth);
+    for (int k = 0; k < depth; k++)
+        for (int c = 0; c < 3; c++) tab[k].src[c] = tab[k].dst[c] = ctx->ss[k].d_in + c * ctx->s_plane_al;
+    st->table(st->tab, tab);
+    return stage_arm(ctx, STAGE_TONEMAP, std::move(st), "tone map");
+}

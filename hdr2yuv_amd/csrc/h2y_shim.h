@@ -181,7 +181,7 @@ struct ring_stage {
     virtual int run(h2y_ctx *ctx, int slot) = 0;          /* on the context's stream, after the frame was produced */
     virtual int download(h2y_ctx *, int) { return H2Y_OK; } /* the result, on s_d2h after the slot's ev_conv */
 };
-enum stage_id { STAGE_GAMUT, STAGE_LIGHT, STAGE_LIGHTDIST, STAGE_CODELIGHT, STAGE_COMPARE, STAGE_SSIM, STAGE_HISTOGRAM, STAGE_SCALE, STAGE_COUNT };
+enum stage_id { STAGE_GAMUT, STAGE_TONEMAP, STAGE_LIGHT, STAGE_LIGHTDIST, STAGE_CODELIGHT, STAGE_COMPARE, STAGE_SSIM, STAGE_HISTOGRAM, STAGE_SCALE, STAGE_COUNT };
 
 struct h2y_ctx {
     int device = 0;
@@ -267,6 +267,9 @@ struct h2y_ctx {
     /* h2y_scale_batch's tap tables on the device */
     char *d_scale_tabs = nullptr;
     size_t scale_tabs_cap = 0;
+    /* h2y_tonemap_batch's gain table on the device */
+    float *d_tonemap_gain = nullptr;
+    size_t tonemap_gain_cap = 0;
 
     /* staging for the host-buffer entry */
     void *d_in = nullptr;

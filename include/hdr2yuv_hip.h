@@ -866,6 +866,67 @@ int h2y_gamut_batch(h2y_ctx *ctx, int width, int height, int sample_type, int sr
  * first input, on a ring armed already, for equal chromaticities and a clip other than 0 or 1. */
 int h2y_stream_gamut(h2y_ctx *ctx, int src_primaries, int dst_primaries, int clip);
 
+/* ---- tone mapping: the light of an HDR master brought down to a target peak, in linear light (--tone_map 1) ----------------------
+ * The reference has no tone mapper (its README sends the user to ctlrender), so there are no bytes to match: this is the project's
+ * own definition, as scaling, primaries, siting and the light figures are.  A pass over the decoded source planes, after
+ * h2y_stream_gamut where both are armed, after which the unchanged forward conversion writes the bytes it would write had the
+ * source file held the mapped planes.
+ * The curve is the EETF of Rep. ITU-R BT.2390 with both black levels at 0, applied to m = max(R, G, B); the three samples of a
+ * pixel are scaled by one gain, so their ratios (the hue) are kept.  A source sample of 1.0 is 10000 cd/m2, as the PQ path assumes.
+ * Parameters: integers S (the source's mastering peak) and D (the target's peak) in cd/m2, 100 <= D < S <= 10000, and `relative`:
+ *   1: the output is display-referred, 1.0 = D (for BT.1886 / rho-gamma destinations); 0: it stays in units of 10000 cd/m2 (PQ).
+ * The curve, in binary64 on the host.  N is the ST 2084 inverse EOTF,
+ *     N(L) = ((c1 + c2 L^m1) / (1 + c3 L^m1))^m2,   N^-1(V) = (max(V^(1/m2) - c1, 0) / (c2 - c3 V^(1/m2)))^(1/m1),
+ *     m1 = 2610/16384, m2 = 2523/4096 x 128, c1 = 3424/4096, c2 = 2413/4096 x 32, c3 = 2392/4096 x 32.
+ *   W = N(S/10000), maxLum = N(D/10000) / W, KS = 1.5 maxLum - 0.5.  For a light e:
+ *     E1 = min(N(e) / W, 1);
+ *     E2 = E1 where E1 < KS; otherwise, with t = (E1 - KS) / (1 - KS), the Hermite spline
+ *          E2 = (2t^3 - 3t^2 + 1) KS + (t^3 - 2t^2 + t) (1 - KS) + (-2t^3 + 3t^2) maxLum;
+ *     T(e) = N^-1(E2 W);   u = D/10000 if relative, else 1;   1/u is computed as 10000.0 / D (relative) or is 1;
+ *     the gain g(e) = 1/u where E1 < KS -- exactly the identity below the knee, no round trip through pow -- and
+ *     g(e) = T(e) / (e u) elsewhere.
+ * The table: H2Y_LIGHTDIST_BINS = 8706 binary32 gains on the nodes of the light distribution's bins (above): entry 0 is 1/u
+ *   (everything below 2^-17 is far below any knee: the lowest, S = 10000 and D = 100, lies near 6 cd/m2); entry k, 1 <= k <= 8705,
+ *   is g at the float whose bits are H2Y_LIGHTDIST_FIRST_BITS + ((k - 1) << 14), so entry 8705 is g(1.0); each is rounded once to
+ *   binary32.  cap = 1.0f if relative, else D/10000 rounded once.
+ * Pixel, in binary32; a half is widened first (exact).  Every product, difference and sum is one round-to-nearest operation, no
+ *   fused multiply-add:
+ *   1. for each of G, B, R: c' = c > 0 ? min(c, 1) : +0.0 (NaN, -0.0 and negatives become +0.0, +inf becomes 1);
+ *   2. m = max(max(G', B'), R'), its bits e, k = the bin of e: 0 when e < 0x37000000, else min(((e - 0x37000000) >> 14) + 1, 8705);
+ *   3. gain = table[0] for k = 0, table[8705] for k = 8705; otherwise, with t = float(e & 0x3FFF) x 2^-14 (exact),
+ *      gain = table[k] + (table[k + 1] - table[k]) t;
+ *   4. out_c = min(c' gain, cap).  In binary64 m g(m) reaches 1 + 1e-9 at the peak: the min is part of the definition.
+ *   F32 is stored as is; F16 is rounded to nearest even.  The sample type does not change.
+ * On (S, D) = (1000, 100), (4000, 1000), (10000, 100), (1000, 600) T is monotone, the gains do not increase with e, and the
+ * interpolation between nodes stays within 1e-6 (relative) of the exact curve; the binary32 pixel arithmetic adds its roundings. */
+#define H2Y_TONEMAP_FRAMES_PER_LAUNCH 64
+
+/* The table and the cap of a pair of peaks.  Host only: no device, no context.  gain receives H2Y_LIGHTDIST_BINS floats; `why` (may
+ * be NULL) receives a static string.  H2Y_EINVAL for a null gain or cap, peaks outside 100 <= dst_peak < src_peak <= 10000 and a
+ * `relative` other than 0 or 1. */
+int h2y_tonemap_curve(int src_peak, int dst_peak, int relative, float gain[H2Y_LIGHTDIST_BINS], float *cap, const char **why);
+
+/* k_tonemap on n_frames device frames of width x height: d_src[f*3 + c] / d_dst[f*3 + c] are plane c = G, B, R of frame f, 16-byte
+ * aligned; a d_dst entry may equal its d_src entry (in place; no other overlap).  sample_type H2Y_SAMPLE_F32 or H2Y_SAMPLE_F16
+ * (H2Y_SAMPLE_U16: H2Y_EUNSUPPORTED); a bad size, null or unaligned planes, peaks or `relative` out of range, a pending batch or an
+ * open stream: H2Y_EINVAL.  Launches of up to H2Y_TONEMAP_FRAMES_PER_LAUNCH frames (h2y_last_kernel_ms sums them,
+ * h2y_last_kernel_name "k_tonemap", the variant "k_tonemap<F32,RELATIVE>" .. "k_tonemap<F16,ABSOLUTE>"); synchronous. */
+int h2y_tonemap_batch(h2y_ctx *ctx, int width, int height, int sample_type, int src_peak, int dst_peak, int relative, int n_frames,
+                      const void *const *d_src, void *const *d_dst);
+
+/* Arm an open forward ring whose decoded planes are float or half (h2y_stream_open with F32 or F16 planes, h2y_dpx_stream_open,
+ * h2y_exr_stream_open) before its first input, once: k_tonemap then runs in place on every slot's decoded device planes, on the
+ * context's stream, after the decode and after h2y_stream_gamut's pass where that is armed (whichever was armed first) -- so it
+ * sees the converted, clipped planes, and no channel leaves [0, cap] in the destination's primaries -- and before the conversion;
+ * h2y_stream_light and h2y_stream_lightdist beside it measure the mapped light.
+ * The ring must have been opened with stats_override 1, floor 0 and ceiling 1 on all three planes (H2Y_EINVAL otherwise): mapped
+ * planes are referred to their target by definition, and the measured pic_stats of such a frame -- (int)max, 0 below 1.0 -- would
+ * normalise them by a zero range.
+ * H2Y_EUNSUPPORTED where the planes are U16 (the TIFF ring, a U16 plain ring) and where src_transfer is not 8 (LINEAR) or src_matrix
+ * not 0 (G, B, R); H2Y_EINVAL on an inverse, compare-only, histogram-only, scale-only or light-only ring, after the first input, on
+ * a ring armed already, and for peaks or a `relative` out of range. */
+int h2y_stream_tonemap(h2y_ctx *ctx, int src_peak, int dst_peak, int relative);
+
 /* ---- chroma siting: 4:2:0 chroma co-sited with the top-left luma sample (chroma_sample_loc_type 2; HDR10, UHD Blu-ray) -----------
  * The reference carries chroma_sample_loc_type through pic_t and prints it (hdr2yuv.cpp:490, :505); it parses no flag for it and
  * never acts on it.  Its two resamplers site the chroma as they happen to: the 2x2 box in the centre of the block both ways (loc

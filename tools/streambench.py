@@ -115,6 +115,15 @@ Prints one line per figure, then one JSON line with all of them.
      h2y_stream_gamut.
 Prints one line per figure, then one JSON line with all of them.
 
+`streambench.py tonemap`: the tone curve on 4K frames, beside k_gamut in the same job:
+  1. the kernel time of h2y_tonemap_batch (k_tonemap, 1000 -> 100 cd/m2, relative) and of h2y_gamut_batch (k_gamut, BT.2020 ->
+     BT.709, clip on) on the same 64 distinct device frames per call (HIP events, median of five after a warm-up call), F32 and
+     F16, out of place and in place, the algorithmic bytes per frame -- every plane read once and written once: 24 and 12 B/pixel
+     -- over that time and their share of the 8 TB/s HBM peak.  The frames hold light up to 5000 cd/m2, most of it dark;
+  2. frames/s from host memory of the .f32 ring to BT.709 10-bit 4:2:0 with the 0 / 1 statistics override, unarmed and armed with
+     h2y_stream_tonemap, three times in turn.
+Prints one line per figure, then one JSON line with all of them.
+
 `streambench.py siting`: top-left co-sited 4:2:0 chroma (chroma siting 2) on 4K frames, in one job:
   1. k_fir420 and k_fir420_tl through h2y_subsample_420_sited (loc 0 / loc 2) over the 128 distinct chroma planes of 64 frames, one
      launch per plane (HIP events; the two planes of a frame added up), five passes: median and spread in us per frame, and the
@@ -1419,6 +1428,84 @@ def gamut_main():
     print(json.dumps({"streambench_gamut": res}), flush=True)
 
 
+def tonemap_main():
+    import json
+
+    import torch
+
+    w, hh, nb, reps = 3840, 2160, 64, 5
+    n = w * hh
+    nf = int(os.environ.get("N", "60"))
+    depth = 3
+    ctx = h.Context(0)
+    res = {"width": w, "height": hh, "frames_per_call": nb, "reps": reps, "ring_frames": nf, "ring_depth": depth, "hbm_peak_tbs": 8.0}
+
+    def timed(key, label, nbytes, call):
+        ks = []
+        for r in range(reps + 1):  # the first call warms up
+            call()
+            if r:
+                ks.append(ctx.last_kernel_ms()[0] / nb)
+        k_ms = float(np.median(ks))
+        tbs = nbytes / (k_ms * 1e-3) / 1e12
+        res[key] = dict(kernel_us_per_frame=round(k_ms * 1e3, 2), min_us=round(min(ks) * 1e3, 2), max_us=round(max(ks) * 1e3, 2),
+                        bytes_per_frame=nbytes, kernel_tbs=round(tbs, 2), hbm_peak_fraction=round(tbs / 8.0, 3), variant=ctx.last_kernel_variant())
+        print(f"{label:32s} {nb} frames per call: {k_ms*1e3:7.2f} us/frame ({min(ks)*1e3:.2f}..{max(ks)*1e3:.2f})  {nbytes/1e6:6.1f} MB/frame  "
+              f"{tbs:5.2f} TB/s = {tbs/8.0*100:4.1f} % of 8 TB/s", flush=True)
+
+    # 1. k_tonemap and k_gamut over the same 64 distinct frames on the device; out of place first, so that both kernels read the
+    # light as it was made, then in place (k_gamut last: what the curve left is light all the same)
+    for name, sample, dt in (("f32", h.SAMPLE_F32, torch.float32), ("f16", h.SAMPLE_F16, torch.float16)):
+        src = [[(torch.rand(n, device="cuda") ** 3 * 0.5).to(dt) for _ in range(3)] for _ in range(nb)]
+        dst = [[torch.empty(n, dtype=dt, device="cuda") for _ in range(3)] for _ in range(nb)]
+        torch.cuda.synchronize()
+        nbytes = 2 * 3 * n * (4 if sample == h.SAMPLE_F32 else 2)
+        timed(f"k_tonemap_{name}_out_of_place", f"k_tonemap {name} out of place", nbytes, lambda: ctx.tonemap_batch(w, hh, sample, 1000, 100, 1, src, dst))
+        timed(f"k_gamut_{name}_out_of_place", f"k_gamut {name} out of place", nbytes, lambda: ctx.gamut_batch(w, hh, sample, 9, 1, 1, src, dst))
+        del dst
+        timed(f"k_tonemap_{name}_in_place", f"k_tonemap {name} in place", nbytes, lambda: ctx.tonemap_batch(w, hh, sample, 1000, 100, 1, src))
+        timed(f"k_gamut_{name}_in_place", f"k_gamut {name} in place", nbytes, lambda: ctx.gamut_batch(w, hh, sample, 9, 1, 1, src))
+        del src
+        torch.cuda.empty_cache()
+
+    # 2. the .f32 ring from host memory, unarmed and armed
+    planes = [(np.random.default_rng(31 + c).random(n, dtype=np.float32) ** 3 * np.float32(0.5)) for c in range(3)]
+    d32 = h.make_desc(w, hh, dst_depth=10, dst_transfer=1, dst_matrix=h.MATRIX_BT709, src_primaries=9, dst_primaries=1, resampler=1,
+                      stats=[(0, 1)] * 3)
+
+    def ring(arm):
+        ctx.stream_open(d32, depth)
+        if arm:
+            ctx.stream_tonemap(1000, 100, 1)
+        inflight = 0
+        t0 = time.perf_counter()
+        for _ in range(nf):
+            slot = ctx.stream_input()
+            for c in range(3):
+                slot[c][:] = planes[c]
+            ctx.stream_submit()
+            inflight += 1
+            if inflight == depth - 1:
+                ctx.stream_output()
+                inflight -= 1
+        while inflight:
+            ctx.stream_output()
+            inflight -= 1
+        dt = (time.perf_counter() - t0) / nf
+        ctx.stream_close()
+        return dt
+
+    ring(False)  # warm-up
+    res["f32"] = []
+    for _ in range(3):  # unarmed and armed in turn: what the card drifts by shows in both alike
+        t_plain, t_armed = ring(False), ring(True)
+        res["f32"].append(dict(unarmed_fps=round(1 / t_plain, 1), armed_fps=round(1 / t_armed, 1), armed_share=round(t_plain / t_armed, 3)))
+        print(f"f32          ring from host memory: unarmed {1/t_plain:6.1f} frames/s   armed {1/t_armed:6.1f} frames/s "
+              f"({t_plain/t_armed*100:5.1f} %)", flush=True)
+    ctx.close()
+    print(json.dumps({"streambench_tonemap": res}), flush=True)
+
+
 def siting_main():
     import json
 
@@ -1508,6 +1595,8 @@ if __name__ == "__main__":
         siting_main()
     elif sys.argv[1:] == ["gamut"]:
         gamut_main()
+    elif sys.argv[1:] == ["tonemap"]:
+        tonemap_main()
     elif sys.argv[1:] == ["scale"]:
         scale_main()
     elif sys.argv[1:] == ["inverse"]:
