@@ -39,6 +39,7 @@ EXPORTS = [
     "h2y_light_batch", "h2y_stream_light", "h2y_stream_light_result",
     "h2y_lightdist_batch", "h2y_stream_lightdist", "h2y_stream_lightdist_result", "h2y_lightdist_json",
     "h2y_codelight_batch", "h2y_codelight_stream_open",
+    "h2y_linearize_batch", "h2y_pqcode_stream_open",
     "h2y_scale_taps", "h2y_scale_frame_bytes", "h2y_scale_batch", "h2y_stream_scale", "h2y_scale_stream_open",
     "h2y_gamut_matrix", "h2y_gamut_batch", "h2y_stream_gamut",
     "h2y_tonemap_curve", "h2y_tonemap_batch", "h2y_stream_tonemap",
@@ -55,6 +56,7 @@ LIGHTDIST_BINS = 8706  # bins of max(L_G, L_B, L_R) by its binary32 bits: below 
 LIGHTDIST_FIRST_BITS = 0x37000000  # 2^-17: the lower edge of bin 1
 LIGHTDIST_PCT = (100, 500, 1000, 2500, 5000, 7500, 9000, 9500, 9900, 9998)  # the percentiles, in hundredths of a percent
 CODELIGHT_FRAMES_PER_LAUNCH = 8  # a launch's 4:2:0 scratch stays at 253 MiB for 3840 x 2160
+LINEARIZE_FRAMES_PER_LAUNCH = 8  # the same rule, the same scratch
 SCALE_FRAMES_PER_LAUNCH = 64
 GAMUT_FRAMES_PER_LAUNCH = 64
 TONEMAP_FRAMES_PER_LAUNCH = 64
@@ -441,6 +443,10 @@ def load_library():
     L.h2y_codelight_batch.restype = C.c_int
     L.h2y_codelight_stream_open.argtypes = [C.c_void_p, C.POINTER(H2YCodelightDesc), C.c_int, C.c_int]
     L.h2y_codelight_stream_open.restype = C.c_int
+    L.h2y_linearize_batch.argtypes = [C.c_void_p, C.POINTER(H2YCodelightDesc), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.h2y_linearize_batch.restype = C.c_int
+    L.h2y_pqcode_stream_open.argtypes = [C.c_void_p, C.POINTER(H2YDesc), C.POINTER(H2YCodelightDesc), C.c_int]
+    L.h2y_pqcode_stream_open.restype = C.c_int
     L.h2y_lightdist_json.argtypes = [C.POINTER(H2YLightdistStats), C.c_int, C.c_long, C.c_char_p, C.c_size_t]
     L.h2y_lightdist_json.restype = C.c_size_t
     L.h2y_scale_taps.argtypes = [C.c_int] * 3 + [C.c_void_p] * 3 + [C.POINTER(C.c_int)]
@@ -940,6 +946,30 @@ class Context:
         self._stream_dpx = None
         self._stream_rgb = False
         self._stream_cmp_planes = (d.width * d.height, nc, nc)
+
+    def linearize_batch(self, d: H2YCodelightDesc, frames, planes_out) -> None:
+        """k_linearize on device frames of PQ codes (as codelight_batch takes them): planes_out[f] = three device planes G, B, R of
+        float32, 16-byte aligned, receive the frame's linear light (1.0 = 10000 cd/m2)."""
+        n = len(frames)
+        if len(planes_out) != n:
+            raise ValueError("frames and planes_out differ in length")
+        pf = (C.c_void_p * max(n, 1))(*[self._ptr(x) for x in frames])
+        outs = (C.c_void_p * max(3 * n, 1))()
+        for f in range(n):
+            for c in range(3):
+                outs[3 * f + c] = self._ptr(planes_out[f][c])
+        self._check(self.lib.h2y_linearize_batch(self.h, C.byref(d), n, pf, outs))
+
+    def pqcode_stream_open(self, d, src: H2YCodelightDesc, depth=3) -> None:
+        """The forward ring on PQ code frames: stream_input gives one uint8 view of the pinned slot to fill with the frame's three
+        u16 planes one after the other; the device linearises them (k_up444, k_linearize) into the F32 G,B,R planes d describes
+        (src_transfer 8, src_matrix 0, stats_override 1 with floor 0, ceiling 1); stream_output gives the .yuv frame."""
+        self._check(self.lib.h2y_pqcode_stream_open(self.h, C.byref(d), C.byref(src), depth))
+        nc = (src.width >> 1) * (src.height >> 1) if src.chroma_format_idc == CHROMA_420 else src.width * src.height
+        self._stream_desc = d
+        self._stream_inverse = None
+        self._stream_dpx = 2 * (src.width * src.height + 2 * nc)
+        self._stream_rgb = False
 
     def scale_batch(self, src_w, src_h, dst_w, dst_h, chroma, bit_depth, full_range, gbr, a, frames_src, frames_dst) -> None:
         """k_scale on device frames (tensors or pointers, each frame's planes contiguous from a 16-byte aligned base):

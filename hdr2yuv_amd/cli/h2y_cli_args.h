@@ -112,6 +112,20 @@
  *             other than 16, any other matrix, matrix 0 with 4:2:0, 4:2:2, a source that is not .yuv / .rgb, --dst_filename,
  *             --ref_filename, --histogram, --ssim, --scale, --gamut_convert, --content_light or another *_only flag beside it, and
  *             --src_chroma_sample_loc_type 2 with --chroma_resampler_type 0 or with 4:4:4.
+ * --linearize 1 (an addition): a finished PQ master as the source of the forward flow to .yuv (include/hdr2yuv_hip.h, "linearised PQ code
+ *             planes", states every step): a .yuv (--src_chroma_format_idc 1 or 3, --src_matrix_coeffs 1 or 9) or a .rgb (4:4:4, matrix
+ *             0, its planes assigned to G, B, R as the .rgb forward reader assigns them) with --src_bit_depth 8..16, the source range flag
+ *             and --src_transfer_characteristics 16 is read as --light_only reads it and linearised on the device into F32 G,B,R planes
+ *             in units of 10000 cd/m2.  4:2:0 chroma is upsampled as --light_only does it (--chroma_resampler_type, which also selects
+ *             the destination's subsampler as always; --src_chroma_sample_loc_type 0|2).  Destination attributes that are not given
+ *             take the source's as parsed, as always; from there on the run is a run from a .f32 LINEAR (8) G,B,R (0) 4:4:4 source with
+ *             floor 0 and ceiling 1 for every frame: --gamut_convert, --tone_map and its peaks, --content_light, --dynamic_metadata,
+ *             --scale, --dst_chroma_sample_loc_type, --ref_filename, --ssim and --histogram are accepted and refused exactly as for
+ *             .f32, for any --gpus, with or without --dst_filename.  The banner carries linearize: and linearize_from:.  Refused (exit
+ *             1, also under --dry_run): a value other than 0 or 1, a source that is not .yuv / .rgb, a transfer other than 16, another
+ *             matrix, 4:2:2, matrix 0 with 4:2:0 or with a .yuv, a .rgb with another matrix, odd 4:2:0 sizes, a .rgb / .tiff destination
+ *             (the .yuv -> RGB flow), every *_only flag, --src_chroma_sample_loc_type 2 with --chroma_resampler_type 0 or with 4:4:4.
+ *             Without the flag nothing changes: .yuv 4:4:4 -> .yuv stays the reference's integer flow.
  * Only user_args_t.chroma_resampler_type has no defined default there (never initialised): FIR here, as in
  * make.sh's example.  The reference calls exit(0) on its argument errors; this program returns 1.
  */
@@ -185,6 +199,12 @@ struct cli_args {
     /* --light_only 1: the light of a PQ .yuv or .rgb from its codes, no conversion */
     int light_only = 0;
     bool light_only_given = false;
+    /* --linearize 1: a PQ .yuv or .rgb linearised on the device as the forward flow's source; resolved: `lin` and lin_type keep the
+     * file's own attributes and type, while `in` and in_type become those of the F32 LINEAR G,B,R planes the ring decodes */
+    int linearize = 0;
+    bool linearize_given = false;
+    cli_pic lin{};
+    int lin_type = CLI_IN_NONE;
     std::vector<int> devices;
     /* resolved */
     int in_type = CLI_IN_NONE, out_type = CLI_OUT_NONE;
@@ -247,6 +267,9 @@ static inline void cli_help()
            "  light of a PQ master: [--light_only 1] (--src_filename, a PQ .yuv -- 4:2:0 or 4:4:4, --src_matrix_coeffs 1 or 9 -- or .rgb,\n"
            "  --src_transfer_characteristics 16: MaxCLL / MaxFALL from its codes, no conversion; with --dynamic_metadata FILE the HDR10+\n"
            "  JSON too; --src_chroma_sample_loc_type 2 for top-left sited 4:2:0 chroma)\n"
+           "  a PQ master as the source: [--linearize 1] (--src_filename, a PQ .yuv or .rgb as --light_only takes it, linearised on the\n"
+           "  GPU into float G,B,R planes in linear light; from there the run is one from a .f32: --tone_map, --gamut_convert, --scale,\n"
+           "  --content_light, --dynamic_metadata, --dst_chroma_sample_loc_type, --ref_filename, --ssim and --histogram apply)\n"
            "  primaries: [--gamut_convert 1 [--gamut_clip 0|1]] (float or half G,B,R source planes in linear light converted from\n"
            "  --src_colour_primaries to --dst_colour_primaries on the GPU before the conversion; 1 BT.709, 8 / 9 BT.2020, 12 P3-D65,\n"
            "  10 XYZ; what is not above 0 is clipped to 0 unless --gamut_clip 0)\n"
@@ -287,6 +310,7 @@ static inline void cli_parse(cli_args &a, int argc, char **argv)
         else if (is("--ssim")) { a.ssim = atoi(val()); a.ssim_given = true; }
         else if (is("--content_light")) { a.light = atoi(val()); a.light_given = true; }
         else if (is("--light_only")) { a.light_only = atoi(val()); a.light_only_given = true; }
+        else if (is("--linearize")) { a.linearize = atoi(val()); a.linearize_given = true; }
         else if (is("--dynamic_metadata")) a.dynmeta = val();
         else if (is("--gamut_convert")) { a.gamut = atoi(val()); a.gamut_given = true; }
         else if (is("--gamut_clip")) { a.gamut_clip = atoi(val()); a.gamut_clip_given = true; }
@@ -477,8 +501,17 @@ static inline int cli_resolve_tone_map(cli_args &a, int src_matrix_arg);
 static inline int cli_resolve_siting(cli_args &a);
 static inline int cli_resolve_src_siting(cli_args &a);
 static inline int cli_resolve_light_only(cli_args &a);
+static inline int cli_resolve_linearize(cli_args &a);
 static inline int cli_resolve(cli_args &a)
 {
+    if (a.linearize_given) { /* first: what follows resolves the linearised source */
+        printf("linearize: %d\n", a.linearize);
+        if (a.linearize != 0 && a.linearize != 1) {
+            printf("WARNING: linearize(%d) not 0 or 1\n", a.linearize);
+            return 1;
+        }
+        if (a.linearize && cli_resolve_linearize(a)) return 1;
+    }
     if (a.light_only_given) { /* its own flow: it resolves everything it takes and refuses the rest */
         printf("light_only: %d\n", a.light_only);
         if (a.light_only != 0 && a.light_only != 1) {
@@ -500,7 +533,7 @@ static inline int cli_resolve(cli_args &a)
     if (a.gamut_given || a.gamut_clip_given) arg_errors += cli_resolve_gamut(a, src_matrix_arg);
     if (a.tone_map_given || a.tone_src_peak_given || a.tone_dst_peak_given) arg_errors += cli_resolve_tone_map(a, src_matrix_arg);
     if (a.siting_given) arg_errors += cli_resolve_siting(a);
-    if (a.src_siting_given) arg_errors += cli_resolve_src_siting(a);
+    if (a.src_siting_given && !a.linearize) arg_errors += cli_resolve_src_siting(a); /* (--linearize 1 resolved its own) */
     return arg_errors;
 }
 
@@ -645,7 +678,7 @@ static inline int cli_resolve_light(cli_args &a)
     if (!a.light) return 0;
     if (cli_light_scope(a, "--content_light 1")) return 1;
     printf("content_light_from: src_transfer_characteristics %d -> PQ, G,B,R, floor and ceiling %s\n", a.in.transfer_characteristics,
-           a.tone_map == 1 ? "0 and 1 (--tone_map 1)" : "of each frame's pic_stats");
+           a.linearize == 1 ? "0 and 1 (--linearize 1)" : a.tone_map == 1 ? "0 and 1 (--tone_map 1)" : "of each frame's pic_stats");
     return 0;
 }
 
@@ -759,6 +792,103 @@ static inline int cli_resolve_light_only(cli_args &a)
     return 0;
 }
 
+/* --linearize 1: a PQ .yuv or .rgb as the forward flow's source.  Checks the file's attributes as --light_only checks them, gives the
+ * destination what it leaves unset from the source as parsed (hdr2yuv.cpp:265-318), keeps the file's attributes in a.lin and
+ * rewrites a.in to the planes the ring decodes -- F32, LINEAR, G,B,R, 4:4:4 -- so that every resolver after this one sees a .f32
+ * source; returns the number of argument errors */
+static inline int cli_resolve_linearize(cli_args &a)
+{
+    int arg_errors = 0;
+    const char *ext = cli_ext_of(a.src);
+    if (a.synthetic < 0 && !strcasecmp(ext, "yuv")) a.lin_type = CLI_IN_YUV;
+    else if (a.synthetic < 0 && !strcasecmp(ext, "rgb")) a.lin_type = CLI_IN_RGB;
+    else {
+        printf("WARNING: --linearize 1 reads .yuv or .rgb; source file (%s) is a .%s\n", a.src ? a.src : "(none)", ext);
+        arg_errors++;
+    }
+    if (a.light_only || a.compare_only || a.hist_only || a.scale_only) {
+        printf("WARNING: --linearize 1 is the source of a conversion: not with --%s 1\n",
+               a.light_only ? "light_only" : a.compare_only ? "compare_only" : a.hist_only ? "histogram_only" : "scale_only");
+        arg_errors++;
+    }
+    const char *dext = cli_ext_of(a.dst ? a.dst : a.ref);
+    if (!strcasecmp(dext, "rgb") || !strcasecmp(dext, "tiff")) {
+        printf("WARNING: --linearize 1 is the forward flow's source (to .yuv): a .%s %s is the .yuv -> RGB flow's\n", dext,
+               a.dst ? "destination" : "reference");
+        arg_errors++;
+    }
+    if (a.in.width < 1 || a.in.width > 10000) { printf("WARNING: pic_width(%d) outside range [1,10000]\n", a.in.width); arg_errors++; }
+    if (a.in.height < 1 || a.in.height > 10000) { printf("WARNING: pic_height(%d) outside range [1,10000]\n", a.in.height); arg_errors++; }
+    if (a.in.bit_depth < 8 || a.in.bit_depth > 16) { printf("WARNING: src bit_depth(%d) outside range [8,16]\n", a.in.bit_depth); arg_errors++; }
+    if (a.in.video_full_range_flag != 0 && a.in.video_full_range_flag != 1) {
+        printf("WARNING: video_full_range_flag(%d) not 0 or 1\n", a.in.video_full_range_flag);
+        arg_errors++;
+    }
+    if (a.in.transfer_characteristics != 16) {
+        printf("WARNING: --linearize 1 linearises PQ codes: src_transfer_characteristics(%d) is not 16\n", a.in.transfer_characteristics);
+        arg_errors++;
+    }
+    const int m = a.in.matrix_coeffs, chroma = a.in.chroma_format_idc;
+    if (m != H2Y_MATRIX_GBR && m != H2Y_MATRIX_BT709 && m != H2Y_MATRIX_BT2020NC) {
+        printf("WARNING: --linearize 1: src_matrix_coeffs(%d) not %d (G,B,R), %d (BT.709) or %d (BT.2020nc)\n", m, H2Y_MATRIX_GBR,
+               H2Y_MATRIX_BT709, H2Y_MATRIX_BT2020NC);
+        arg_errors++;
+    } else if (a.lin_type == CLI_IN_RGB && m != H2Y_MATRIX_GBR) {
+        printf("WARNING: a .rgb holds planes R, G, B: --linearize of a .rgb takes src_matrix_coeffs %d, not %d\n", H2Y_MATRIX_GBR, m);
+        arg_errors++;
+    } else if (a.lin_type == CLI_IN_YUV && m == H2Y_MATRIX_GBR) {
+        printf("WARNING: a .yuv holds planes Y, Cb, Cr: --linearize of a .yuv takes src_matrix_coeffs %d or %d, not %d\n", H2Y_MATRIX_BT709,
+               H2Y_MATRIX_BT2020NC, m);
+        arg_errors++;
+    }
+    if (chroma == 2) { printf("WARNING: --linearize 1: chroma_format_idc 2 (4:2:2) is not linearised\n"); arg_errors++; }
+    else if (chroma != H2Y_CHROMA_420 && chroma != H2Y_CHROMA_444) {
+        printf("WARNING: chroma_format_idc(%d) not %d or %d\n", chroma, H2Y_CHROMA_420, H2Y_CHROMA_444);
+        arg_errors++;
+    } else if (chroma == H2Y_CHROMA_420 && (a.lin_type == CLI_IN_RGB || m == H2Y_MATRIX_GBR)) {
+        printf("WARNING: --linearize 1: G,B,R planes (a .rgb, src_matrix_coeffs %d) are 4:4:4, not chroma_format_idc %d\n", H2Y_MATRIX_GBR, chroma);
+        arg_errors++;
+    } else if (chroma == H2Y_CHROMA_420 && ((a.in.width | a.in.height) & 1)) {
+        printf("WARNING: --linearize 1: 4:2:0 needs an even width and height, not %dx%d\n", a.in.width, a.in.height);
+        arg_errors++;
+    }
+    if (a.src_siting_given) printf("src_chroma_sample_loc_type: %d\n", a.src_siting);
+    if (a.src_siting == 1) {
+        printf("WARNING: src_chroma_sample_loc_type(1) is replication's siting, --chroma_resampler_type 0: not selected by this flag\n");
+        arg_errors++;
+    } else if (a.src_siting != 0 && a.src_siting != 2) {
+        printf("WARNING: src_chroma_sample_loc_type(%d) not 0 or 2\n", a.src_siting);
+        arg_errors++;
+    } else if (a.src_siting == 2 && chroma != H2Y_CHROMA_420) {
+        printf("WARNING: --src_chroma_sample_loc_type 2 sites 4:2:0 chroma: src_chroma_format_idc(%d) has none to site\n", chroma);
+        arg_errors++;
+    } else if (a.src_siting == 2 && a.resampler == 0) {
+        printf("WARNING: --src_chroma_sample_loc_type 2 needs the FIR resampler: replication (--chroma_resampler_type 0) is centre sited by "
+               "construction\n");
+        arg_errors++;
+    }
+    if (arg_errors) return arg_errors;
+    static const char *const kMatrix[10] = {"G,B,R", "BT.709", "", "", "", "", "", "", "", "BT.2020nc"};
+    printf("linearize_from: PQ codes, bit_depth %d %s range, matrix_coeffs %d (%s), chroma_format_idc %d, upsampler %s\n", a.in.bit_depth,
+           a.in.video_full_range_flag ? "full" : "video", m, kMatrix[m], chroma,
+           chroma == H2Y_CHROMA_444 ? "none" : !a.resampler ? "replicate" : a.src_siting == 2 ? "fir_top_left" : "fir");
+    /* hdr2yuv.cpp:265-318: unset destination attributes <- the source's, as parsed */
+    if (a.out.bit_depth == 0) a.out.bit_depth = a.in.bit_depth;
+    if (a.out.chroma_format_idc == -1) a.out.chroma_format_idc = a.in.chroma_format_idc;
+    if (a.out.video_full_range_flag == -1) a.out.video_full_range_flag = a.in.video_full_range_flag;
+    if (a.out.colour_primaries == -1) a.out.colour_primaries = a.in.colour_primaries;
+    if (a.out.transfer_characteristics == -1) a.out.transfer_characteristics = a.in.transfer_characteristics;
+    if (a.out.matrix_coeffs == -1) a.out.matrix_coeffs = a.in.matrix_coeffs;
+    /* the planes the ring decodes: what a .f32 of the same picture would be given as */
+    a.lin = a.in;
+    a.in.bit_depth = 32;
+    a.in.half_float_flag = 0;
+    a.in.chroma_format_idc = H2Y_CHROMA_444;
+    a.in.transfer_characteristics = H2Y_TRANSFER_LINEAR;
+    a.in.matrix_coeffs = H2Y_MATRIX_GBR;
+    return 0;
+}
+
 /* --dynamic_metadata FILE: content light's scope, and a FILE that can be created (an existing regular file that can be written, or
  * a name in a directory that can be written to; nothing is created here); returns the number of argument errors */
 static inline int cli_resolve_dynmeta(cli_args &a)
@@ -771,7 +901,8 @@ static inline int cli_resolve_dynmeta(cli_args &a)
     }
     printf("dynamic_metadata_from: src_transfer_characteristics %d -> PQ, G,B,R, floor and ceiling %s; HDR10+ profile A, one scene, "
            "percentiles of max(R,G,B) in %d bins\n", a.in.transfer_characteristics,
-           a.tone_map == 1 ? "0 and 1 (--tone_map 1)" : "of each frame's pic_stats", H2Y_LIGHTDIST_BINS);
+           a.linearize == 1 ? "0 and 1 (--linearize 1)" : a.tone_map == 1 ? "0 and 1 (--tone_map 1)" : "of each frame's pic_stats",
+           H2Y_LIGHTDIST_BINS);
     return 0;
 }
 
@@ -1025,7 +1156,8 @@ static inline int cli_resolve_convert(cli_args &a)
 
     /* :321-372 input type */
     const char *ext = cli_ext_of(a.src);
-    if (a.synthetic >= 0) a.in_type = CLI_IN_SYNTH;
+    if (a.linearize == 1) a.in_type = CLI_IN_F32; /* cli_resolve_linearize: the F32 planes the ring decodes from the file's codes */
+    else if (a.synthetic >= 0) a.in_type = CLI_IN_SYNTH;
     else if (!strcasecmp(ext, "yuv")) a.in_type = CLI_IN_YUV;
     else if (!strcasecmp(ext, "rgb")) a.in_type = CLI_IN_RGB;
     else if (!strcasecmp(ext, "f32")) a.in_type = CLI_IN_F32;
@@ -1179,7 +1311,8 @@ static inline void cli_make_desc(const cli_args &a, h2y_desc *d)
     d->dst_full_range = a.out.video_full_range_flag;
     d->dst_chroma_format_idc = a.out.chroma_format_idc;
     d->chroma_resampler_type = a.resampler;
-    if (a.tone_map) { /* mapped planes are referred to their target: floor 0 and ceiling 1, not each frame's pic_stats */
+    if (a.tone_map || a.linearize == 1) { /* mapped planes are referred to their target, linearised ones lie in [0, 1] by definition: floor
+                                           * 0 and ceiling 1, not each frame's pic_stats */
         d->stats_override = 1;
         for (int c = 0; c < 3; c++) d->floor[c] = 0, d->ceiling[c] = 1;
     }

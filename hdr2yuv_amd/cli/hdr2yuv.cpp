@@ -105,6 +105,12 @@
  * measure the mapped light.  The banner carries tone_map:, tone_map_src_peak:, tone_map_dst_peak: ("(default)" where not given),
  * tone_map_output: relative|absolute and the knee in cd/m2 as tone_map_knee: "%.9g".
  *
+ * A PQ master as the source (--linearize 1 on the forward flow from a PQ .yuv or .rgb; h2y_cli_args.h): each GPU thread sets its
+ * context's inverse chroma siting where --src_chroma_sample_loc_type 2 says so and opens the forward ring that decodes PQ code frames
+ * (h2y_pqcode_stream_open): a frame is read whole into the pinned slot, as --light_only reads it, and linearised on the device into
+ * the slot's F32 G,B,R planes; everything armed on the ring sees those planes.  One more source kind of the forward flow, not a flow
+ * of its own.  The banner carries linearize: and linearize_from:.
+ *
  * Chroma siting (--dst_chroma_sample_loc_type 0|2 on the forward flow to .yuv; h2y_cli_args.h): each GPU thread sets its context's
  * siting (h2y_ctx_set_chroma_siting) before it opens its ring, so every frame, and whatever is armed on the ring, has its 4:2:0
  * chroma where the flag says.  The banner carries dst_chroma_sample_loc_type: only when the flag is given, and with 2 it ends with
@@ -343,6 +349,12 @@ static flow forward_flow(const job &j)
     flow f;
     f.open = [&j, &a, &s](h2y_ctx *ctx) {
         if (a.siting && h2y_ctx_set_chroma_siting(ctx, a.siting)) return (int)H2Y_EINVAL; /* before the ring is opened */
+        if (a.linearize) { /* the file's PQ codes, linearised on the device into the planes j.d describes */
+            if (a.src_siting && h2y_ctx_set_inverse_chroma_siting(ctx, a.src_siting)) return (int)H2Y_EINVAL;
+            const h2y_codelight_desc code{a.lin.width, a.lin.height, a.lin.chroma_format_idc, a.lin.bit_depth, a.lin.video_full_range_flag,
+                                          a.lin.matrix_coeffs, a.resampler};
+            return h2y_pqcode_stream_open(ctx, &j.d, &code, kRingDepth);
+        }
         return a.in_type == CLI_IN_DPX    ? h2y_dpx_stream_open(ctx, &j.d, &s.di, kRingDepth)
                : a.in_type == CLI_IN_TIFF ? h2y_tiff_stream_open(ctx, &j.d, &s.ti, a.in.video_full_range_flag == 0, kRingDepth)
                : a.in_type == CLI_IN_EXR  ? h2y_exr_stream_open(ctx, &j.d, &s.xi, kRingDepth)
@@ -356,7 +368,14 @@ static flow forward_flow(const job &j)
                (a.tone_map && h2y_stream_tonemap(ctx, a.tone_src_peak, a.tone_dst_peak, a.tone_relative)) ||
                (a.scale && h2y_stream_scale(ctx, a.out.width, a.out.height, a.scale_taps));
     };
-    if (a.in_type == CLI_IN_DPX) { /* the payload as the file holds it, straight into the pinned slot */
+    if (a.linearize) { /* the code frame whole, as whole_frame_flow reads it: one read, a .rgb with its planes put in G, B, R order */
+        const bool rgb = a.lin_type == CLI_IN_RGB;
+        const size_t plane = (size_t)a.lin.width * a.lin.height * 2, frame = j.in_frame_bytes;
+        f.src_frame_bytes = frame;
+        f.fill = [&a, rgb, plane, frame](long, FILE *src, void *const *planes) {
+            return read_ref(src, rgb, plane, frame, planes[0]) ? "" : std::string("short read from ") + a.src;
+        };
+    } else if (a.in_type == CLI_IN_DPX) { /* the payload as the file holds it, straight into the pinned slot */
         f.fill = [&s](long k, FILE *, void *const *planes) -> std::string {
             const dpx_src &src = s.dpx[k];
             FILE *fd = fopen(src.path.c_str(), "rb");
@@ -763,7 +782,7 @@ int main(int argc, char **argv)
         const char *why = nullptr;
         if (h2y_desc_check(&j.d, &why)) { printf("ERROR: %s\n", why); return 1; }
         make_flow = forward_flow;
-        in_frame_bytes = 3 * h2y_plane_bytes(&j.d);
+        in_frame_bytes = a.linearize ? planar16_bytes(a.lin) : 3 * h2y_plane_bytes(&j.d);
         out_frame_bytes = h2y_frame_bytes(&j.d);
     }
     if (scaling) out_frame_bytes = h2y_scale_frame_bytes(a.out.width, a.out.height, a.out.chroma_format_idc); /* the scaled frame's */

@@ -1310,6 +1310,14 @@ int decode_src::planes_check(h2y_ctx *ctx, const h2y_desc *d) const
         if (d->in_sample_type != H2Y_SAMPLE_F16) return fail(ctx, H2Y_EINVAL, "an EXR stream decodes to half planes: in_sample_type must be H2Y_SAMPLE_F16");
         what = "EXR data window", w = exr.width, h = exr.height;
         break;
+    case PQCODE: /* the linearised planes: F32 LINEAR G,B,R in [+0, 1], floor 0 and ceiling 1 whatever the frame holds */
+        if (d->in_sample_type != H2Y_SAMPLE_F32 || d->src_transfer != 8 || d->src_matrix != H2Y_MATRIX_GBR)
+            return fail(ctx, H2Y_EINVAL, "a PQ code stream linearises to F32 G,B,R planes: in_sample_type H2Y_SAMPLE_F32, src_transfer 8, src_matrix 0");
+        if (d->stats_override != 1) return fail(ctx, H2Y_EINVAL, "a PQ code stream needs stats_override 1 with floor 0 and ceiling 1");
+        for (int c = 0; c < 3; c++)
+            if (d->floor[c] != 0 || d->ceiling[c] != 1) return fail(ctx, H2Y_EINVAL, "a PQ code stream needs stats_override 1 with floor 0 and ceiling 1");
+        what = "PQ code frame", w = code.width, h = code.height;
+        break;
     default: return H2Y_OK;
     }
     if (d->width != w || d->height != h)
@@ -1319,6 +1327,7 @@ int decode_src::planes_check(h2y_ctx *ctx, const h2y_desc *d) const
 
 uint64_t decode_src::payload_bytes() const
 {
+    if (kind == PQCODE) return (uint64_t)code.samples * sizeof(uint16_t);
     return kind == DPX ? dpx.payload_bytes : kind == TIFF ? tiff.payload_bytes : kind == EXR ? exr.payload_bytes : 0;
 }
 

@@ -3,7 +3,8 @@
  * distribution (ST 2094-40) of frames of three u16 code planes, 4:4:4 (4:2:0 chroma arrives upsampled by k_up444, h2y_resample.hip).
  * include/hdr2yuv_hip.h, "light of PQ code planes", states every step: the codes normalised by one subtraction and one IEEE
  * division, Y'CbCr -> R'G'B' with every product and sum rounded by itself (this file is built -ffp-contract=off), the clamp to
- * [+0, 1], PQ10000_f through light1<true>'s tiers, and from there k_light's and k_lightdist's own statement (h2y_light1.h).
+ * [+0, 1], PQ10000_f through light1<true>'s tiers (these steps in h2y_codepixel.h, shared with k_linearize), and from there k_light's
+ * and k_lightdist's own statement (h2y_light1.h).
  *
  *   k_codelight<MATRIX, DIST>  (block column, frame) blocks: a block takes a contiguous share of its frame's 8-pixel groups; a
  *                              thread reads a group with one 16-byte load per plane whose start is 16-byte aligned (u16 loads
@@ -21,6 +22,7 @@
 #include "h2y_math.h"
 #include "h2y_device.h"
 #include "h2y_light1.h"
+#include "h2y_codepixel.h"
 
 namespace {
 
@@ -29,37 +31,6 @@ constexpr uint32_t kGroupsPerThread = 4u; /* 8-pixel groups per thread a one-fra
 constexpr uint32_t kMaxBlocks = 1024u;    /* blocks of a launch: four per CU, what the LDS bins leave room for */
 constexpr uint32_t kBins = H2Y_LIGHTDIST_BINS;
 constexpr uint32_t kNone = 0xFFFFFFFFu;
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-/* the matrix's constants: the decimal values of the header, rounded once to binary32 */
-template <int MATRIX> struct ycc_coef;
-template <> struct ycc_coef<H2Y_MATRIX_BT2020NC> {
-    static constexpr float rv = 1.4746f, bu = 1.8814f, gu = 0.16455313f, gv = 0.57135313f;
-};
-template <> struct ycc_coef<H2Y_MATRIX_BT709> {
-    static constexpr float rv = 1.5748f, bu = 1.8556f, gu = 0.18732427f, gv = 0.46812427f;
-};
-template <> struct ycc_coef<H2Y_MATRIX_GBR> {
-    static constexpr float rv = 0.f, bu = 0.f, gu = 0.f, gv = 0.f;
-};
-
-/* eight codes of a plane: group q of a plane that starts 16-byte aligned, else one by one */
-__device__ __forceinline__ void load8(const uint16_t *p, bool vec, uint32_t q, uint32_t c[8])
-{
-    if (vec) {
-        const u32x4 v = gload_nt<u32x4>(p, q);
-        c[0] = v.x & 0xFFFFu; c[1] = v.x >> 16;
-        c[2] = v.y & 0xFFFFu; c[3] = v.y >> 16;
-        c[4] = v.z & 0xFFFFu; c[5] = v.z >> 16;
-        c[6] = v.w & 0xFFFFu; c[7] = v.w >> 16;
-    } else {
-#pragma unroll
-        for (uint32_t j = 0; j < 8u; j++) c[j] = gload<uint16_t>(p, 8u * q + j);
-    }
-}
-
-__device__ __forceinline__ float clamp01(float v) { return v > 0.0f ? fminf(v, 1.0f) : 0.0f; }
 
 /* what a thread keeps of its pixels */
 struct code_regs {
@@ -72,20 +43,8 @@ template <int MATRIX, bool DIST>
 __device__ __forceinline__ uint32_t code_pixel(const codelight_args &a, const pq_recA *tab, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t i,
                                                code_regs &k)
 {
-    typedef ycc_coef<MATRIX> K;
-    const float y = ((float)c0 - a.sub[0]) / a.div[0];
-    float g, b, r;
-    if (MATRIX == H2Y_MATRIX_GBR) {
-        g = y;
-        b = ((float)c1 - a.sub[0]) / a.div[0];
-        r = ((float)c2 - a.sub[0]) / a.div[0];
-    } else {
-        const float cb = ((float)c1 - a.sub[1]) / a.div[1], cr = ((float)c2 - a.sub[1]) / a.div[1];
-        r = y + K::rv * cr;
-        b = y + K::bu * cb;
-        g = (y - K::gu * cb) - K::gv * cr;
-    }
-    const float lg = light1<true>(a.pp, tab, 0, clamp01(g)), lb = light1<true>(a.pp, tab, 1, clamp01(b)), lr = light1<true>(a.pp, tab, 2, clamp01(r));
+    float lg, lb, lr;
+    code_lights<MATRIX>(a, tab, c0, c1, c2, lg, lb, lr);
     if (DIST) {
         const float m = dist_keep(lg, lb, lr, k.t);
         const unsigned long long key = ((unsigned long long)f2bits(m) << 32) | (unsigned long long)~i;

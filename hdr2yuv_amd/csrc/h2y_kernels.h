@@ -382,6 +382,15 @@ int h2y_codelight_grid(uint32_t npix, int n_frames); /* blocks per frame */
 hipError_t h2y_launch_codelight(int matrix, int grid, hipStream_t st, const codelight_args &a, const codelight_frame *frames, int n_frames,
                                 light_acc *acc, lightdist_acc *dacc, uint32_t *bins);
 
+/* k_linearize (h2y_linearize.hip): the three lights of every pixel of such frames as binary32 planes G, B, R
+ * (include/hdr2yuv_hip.h, "linearised PQ code planes"); k_codelight's arguments */
+struct linearize_frame { /* one frame: its code planes as codelight_frame has them, and the three output planes (16-byte aligned) */
+    const uint16_t *p[3];
+    float *out[3];
+};
+int h2y_linearize_grid(uint32_t npix, int n_frames); /* blocks per frame */
+hipError_t h2y_launch_linearize(int matrix, int grid, hipStream_t st, const codelight_args &a, const linearize_frame *frames, int n_frames);
+
 /* k_gamut (h2y_gamut.hip): the conversion between colour primaries of include/hdr2yuv_hip.h on frames of three float or half
  * planes G, B, R; dst may be src (in place) */
 struct gamut_frame {

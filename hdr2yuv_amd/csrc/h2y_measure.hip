@@ -683,17 +683,7 @@ size_t h2y_lightdist_json(const h2y_lightdist_stats *stats, int n_frames, long f
 
 /* ---- light of PQ code planes (h2y_codelight_batch, h2y_codelight_stream_open): include/hdr2yuv_hip.h states the definition ------ */
 
-/* what a checked h2y_codelight_desc comes to */
-struct codelight_plan {
-    codelight_args a{};
-    int matrix = 0, form = UP_REPLICATE;
-    bool sub = false;      /* 4:2:0: planes 1 and 2 come from the scratch */
-    size_t plane_al = 0;   /* 4:2:0: the bytes from one upsampled plane to the next (256-byte aligned) */
-    up_args up{};          /* 4:2:0: k_up444's arguments but the planes */
-    uint32_t off[3] = {0, 0, 0}; /* the planes' starts in the frame, in samples */
-};
-
-static int codelight_check(h2y_ctx *ctx, const h2y_codelight_desc *d, codelight_plan &p)
+int codelight_check(h2y_ctx *ctx, const h2y_codelight_desc *d, codelight_plan &p)
 {
     if (!d) return fail(ctx, H2Y_EINVAL, "null h2y_codelight_desc");
     if (d->chroma_format_idc == 2) return fail(ctx, H2Y_EUNSUPPORTED, "chroma_format_idc 2 (4:2:2) has no light on this path");
@@ -722,6 +712,8 @@ static int codelight_check(h2y_ctx *ctx, const h2y_codelight_desc *d, codelight_
     a.sub[1] = d->full_range ? (float)(1u << (d->bit_depth - 1)) : 128.0f * s;
     a.div[1] = d->full_range ? top : 224.0f * s;
     contiguous_planes(d->width, d->height, d->chroma_format_idc, p.off);
+    p.width = d->width, p.height = d->height;
+    p.samples = p.off[2] + (p.off[2] - p.off[1]); /* the last plane is as long as the second */
     /* the frames' bases are 16-byte aligned, and so is the scratch: a plane takes 16-byte loads where its start is */
     a.vec = 1u;
     for (int c = 1; c < 3; c++) a.vec |= (p.sub || ((size_t)p.off[c] * sizeof(uint16_t) & 15u) == 0) ? 1u << c : 0u;
@@ -735,7 +727,7 @@ static int codelight_check(h2y_ctx *ctx, const h2y_codelight_desc *d, codelight_
 }
 
 /* PQ10000_f's tables into the plan: what light1<true> reads of pix_params */
-static int codelight_tables(h2y_ctx *ctx, codelight_plan &p)
+int codelight_tables(h2y_ctx *ctx, codelight_plan &p)
 {
     const int rc = ensure_tfn(ctx, H2Y_TFN_PQ_F);
     if (rc) return rc;
@@ -909,6 +901,81 @@ int h2y_codelight_stream_open(h2y_ctx *ctx, const h2y_codelight_desc *d, int wan
     rc = stage_arm(ctx, STAGE_CODELIGHT, std::move(st), "code light");
     if (rc) stream_free(ctx);
     return rc;
+}
+
+/* ---- linearised PQ code planes (h2y_linearize_batch, h2y_pqcode_stream_open): include/hdr2yuv_hip.h states the definition ------ */
+
+static std::string linearize_variant(const codelight_plan &p)
+{
+    return std::string("k_linearize<") + (p.matrix == H2Y_MATRIX_GBR ? "GBR" : p.matrix == H2Y_MATRIX_BT709 ? "BT709" : "BT2020NC") + "," +
+           (!p.sub ? "444" : p.form == UP_FIR_TL ? "FIR_TL" : p.form == UP_FIR ? "FIR" : "REPLICATE") + ">";
+}
+
+/* the frame's table entry: codelight_entry's planes, and the three output planes */
+static linearize_frame linearize_entry(const codelight_plan &p, const uint16_t *base, const char *up, void *const out[3])
+{
+    const codelight_frame c = codelight_entry(p, base, up);
+    return linearize_frame{{c.p[0], c.p[1], c.p[2]}, {static_cast<float *>(out[0]), static_cast<float *>(out[1]), static_cast<float *>(out[2])}};
+}
+
+int h2y_linearize_batch(h2y_ctx *ctx, const h2y_codelight_desc *d, int n_frames, const uint16_t *const *d_frames, void *const *d_planes_out)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
+    codelight_plan p;
+    int rc = codelight_check(ctx, d, p);
+    if (rc) return rc;
+    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
+    if (!d_frames || !d_planes_out) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
+    for (int f = 0; f < n_frames; f++) {
+        if (!d_frames[f]) return fail(ctx, H2Y_EINVAL, "frame %d is null", f);
+        if ((uintptr_t)d_frames[f] & 15u) return fail(ctx, H2Y_EINVAL, "frame %d is not 16-byte aligned", f);
+        for (int c = 0; c < 3; c++) {
+            if (!d_planes_out[3 * f + c]) return fail(ctx, H2Y_EINVAL, "frame %d: output plane %d is null", f, c);
+            if ((uintptr_t)d_planes_out[3 * f + c] & 15u) return fail(ctx, H2Y_EINVAL, "frame %d: output plane %d is not 16-byte aligned", f, c);
+        }
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int per_launch = std::min(n_frames, H2Y_LINEARIZE_FRAMES_PER_LAUNCH);
+    linearize_frame *h;
+    rc = codelight_tables(ctx, p);
+    if (!rc) rc = frame_table(ctx, n_frames, h);
+    if (!rc && p.sub) rc = ensure(ctx, ctx->d_codelight_up, ctx->codelight_up_cap, (size_t)per_launch * 2u * p.plane_al);
+    if (rc) return rc;
+    /* frame f's upsampled chroma lies in the scratch of its place in its launch; the launches follow one another on one stream */
+    for (int f = 0; f < n_frames; f++)
+        h[f] = linearize_entry(p, d_frames[f], p.sub ? ctx->d_codelight_up + (size_t)(f % per_launch) * 2u * p.plane_al : nullptr, d_planes_out + 3 * f);
+    rc = timed_launches(ctx, h, n_frames, H2Y_LINEARIZE_FRAMES_PER_LAUNCH, "k_linearize", [&](const linearize_frame *frames, int f0, int nf) {
+        for (int f = 0; p.sub && f < nf; f++) {
+            const hipError_t e = codelight_upsample(ctx, p, d_frames[f0 + f], ctx->d_codelight_up + (size_t)f * 2u * p.plane_al);
+            if (e != hipSuccess) return e;
+        }
+        return h2y_launch_linearize(p.matrix, h2y_linearize_grid(p.a.npix, nf), ctx->stream, p.a, frames, nf);
+    });
+    if (rc) return rc;
+    ctx->last_variant = linearize_variant(p);
+    return H2Y_OK;
+}
+
+/* The forward ring's PQCODE decode.  One scratch of the context serves every slot: the frames follow one another on its stream. */
+int pqcode_scratch(h2y_ctx *ctx, const codelight_plan &p)
+{
+    return p.sub ? ensure(ctx, ctx->d_codelight_up, ctx->codelight_up_cap, 2u * p.plane_al) : H2Y_OK;
+}
+
+linearize_frame pqcode_entry(const h2y_ctx *ctx, const codelight_plan &p, const char *payload, char *const planes[3])
+{
+    void *const out[3] = {planes[0], planes[1], planes[2]};
+    return linearize_entry(p, reinterpret_cast<const uint16_t *>(payload), ctx->d_codelight_up, out);
+}
+
+int pqcode_decode(h2y_ctx *ctx, int slot)
+{
+    const codelight_plan &p = ctx->s_src.code;
+    if (p.sub)
+        HIP_TRY(ctx, codelight_upsample(ctx, p, reinterpret_cast<const uint16_t *>(ctx->ss[slot].d_in + ctx->s_pay_off), ctx->d_codelight_up));
+    HIP_TRY(ctx, h2y_launch_linearize(p.matrix, h2y_linearize_grid(p.a.npix, 1), ctx->stream, p.a, static_cast<const linearize_frame *>(ctx->s_tab) + slot, 1));
+    return H2Y_OK;
 }
 
 /* ---- code-value histograms and the legal-range check (hdr2yuv.cpp:658, :797) ---------------------------------------------- */

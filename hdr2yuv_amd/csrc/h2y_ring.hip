@@ -137,7 +137,15 @@ static int open_forward_ring(h2y_ctx *ctx, const h2y_desc *d, const decode_src *
     const size_t h_in = decode ? dec.payload_bytes() : 3 * ctx->s_plane_al;
     rc = stream_alloc(ctx, depth, h_in, decode ? ctx->s_pay_off + h_in : h_in, ob, ob);
     if (rc) return rc;
-    if (decode) {
+    if (dec.kind == decode_src::PQCODE) { /* the linearisation's entries: the code planes in the payload, the slot's three planes */
+        std::vector<linearize_frame> tab(depth);
+        for (int k = 0; k < depth; k++) {
+            char *const planes[3] = {ctx->ss[k].d_in + ctx->s_in_off[0], ctx->ss[k].d_in + ctx->s_in_off[1], ctx->ss[k].d_in + ctx->s_in_off[2]};
+            tab[k] = pqcode_entry(ctx, dec.code, ctx->ss[k].d_in + ctx->s_pay_off, planes);
+        }
+        rc = slot_table(ctx, tab, "PQ code");
+        if (rc) return rc;
+    } else if (decode) {
         std::vector<payload_frame> tab(depth);
         for (int k = 0; k < depth; k++) {
             tab[k].payload = ctx->ss[k].d_in + ctx->s_pay_off;
@@ -260,6 +268,22 @@ int h2y_exr_stream_open(h2y_ctx *ctx, const h2y_desc *d, const h2y_exr_info *inf
     return open_forward_ring(ctx, d, &src, depth);
 }
 
+int h2y_pqcode_stream_open(h2y_ctx *ctx, const h2y_desc *d, const h2y_codelight_desc *code, int depth)
+{
+    int rc = ring_may_open(ctx);
+    if (rc) return rc;
+    codelight_plan p;
+    rc = codelight_check(ctx, code, p); /* the inverse chroma siting is read here */
+    if (rc) return rc;
+    if (!d) return fail(ctx, H2Y_EINVAL, "null h2y_desc");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = codelight_tables(ctx, p);
+    if (!rc) rc = pqcode_scratch(ctx, p);
+    if (rc) return rc;
+    const decode_src src(p);
+    return open_forward_ring(ctx, d, &src, depth);
+}
+
 /* ---- the ring's frame by frame entries ------------------------------------------------------------------------------------------ */
 
 /* the slot's input goes up on s_h2d */
@@ -284,8 +308,10 @@ static int forward_produce(h2y_ctx *ctx, int slot)
     for (int c = 0; c < 3; c++) io.in[c] = s.d_in + c * ctx->s_plane_al;
     io.out = s.d_out;
     io.tmp_cb = io.tmp_cr = nullptr;
-    if (src.kind != decode_src::NONE) HIP_TRY(ctx, src.launch(ctx, static_cast<const payload_frame *>(ctx->s_tab) + slot, 1));
     int rc = H2Y_OK;
+    if (src.kind == decode_src::PQCODE) rc = pqcode_decode(ctx, slot);
+    else if (src.kind != decode_src::NONE) HIP_TRY(ctx, src.launch(ctx, static_cast<const payload_frame *>(ctx->s_tab) + slot, 1));
+    if (rc) return rc;
     for (auto &st : ctx->s_stage) /* what works on the decoded planes: pic_stats and all that follows see its result */
         if (!rc && st) rc = st->decoded(ctx, slot);
     if (rc) return rc;

@@ -58,16 +58,31 @@ struct inv_params {
     int width, height, chroma, in_depth, in_full_range, matrix, out_depth, algorithm;
 };
 
+/* what a checked h2y_codelight_desc comes to (codelight_check, h2y_measure.hip) */
+struct codelight_plan {
+    codelight_args a{};
+    int width = 0, height = 0;
+    int matrix = 0, form = UP_REPLICATE;
+    bool sub = false;      /* 4:2:0: planes 1 and 2 come from the scratch */
+    size_t plane_al = 0;   /* 4:2:0: the bytes from one upsampled plane to the next (256-byte aligned) */
+    up_args up{};          /* 4:2:0: k_up444's arguments but the planes */
+    uint32_t off[3] = {0, 0, 0}; /* the planes' starts in the frame, in samples */
+    uint32_t samples = 0;  /* the frame's samples, all three planes */
+};
+
 /* What a decode batch entry or a forward ring decodes: nothing (a ring's caller fills the planes), or one format's payload
- * described by the info its parser returned.  Each format's launch and variant lie beside its parser. */
+ * described by the info its parser returned.  Each format's launch and variant lie beside its parser.  PQCODE (h2y_pqcode_stream_open):
+ * the payload is a PQ code frame, the decode its linearisation (pqcode_decode, h2y_measure.hip) by the plan checked at the opening. */
 struct decode_src {
-    enum kind_t { NONE, DPX, TIFF, EXR } kind = NONE;
+    enum kind_t { NONE, DPX, TIFF, EXR, PQCODE } kind = NONE;
     bool has_info = true; /* false: the caller passed a null info, which check() refuses */
     int clamp = 0;        /* TIFF: clamp_video_range */
     h2y_dpx_info dpx{};
     h2y_tiff_info tiff{};
     h2y_exr_info exr{};
+    codelight_plan code{};
     decode_src() = default;
+    explicit decode_src(const codelight_plan &p) : kind(PQCODE), code(p) {}
     explicit decode_src(const h2y_dpx_info *i) : kind(DPX), has_info(i != nullptr) { if (i) dpx = *i; }
     decode_src(const h2y_tiff_info *i, int clamp_video_range) : kind(TIFF), has_info(i != nullptr), clamp(clamp_video_range) { if (i) tiff = *i; }
     explicit decode_src(const h2y_exr_info *i) : kind(EXR), has_info(i != nullptr) { if (i) exr = *i; }
@@ -465,6 +480,14 @@ int inverse_check(h2y_ctx *ctx, const inv_params &p);
 int inverse_form(h2y_ctx *ctx, int chroma, int algorithm, int *form); /* the UP_* form of `algorithm` under the context's inverse chroma siting, or the refusal */
 void inverse420_setup(inv420_args &a, int width, int height, int in_bit_depth, int in_full_range, int in_matrix_coeffs, int out_bit_depth,
                       int form);
+
+/* ---- h2y_measure.hip: PQ code planes, for h2y_pqcode_stream_open and the forward ring's PQCODE decode ------------------------------ */
+
+int codelight_check(h2y_ctx *ctx, const h2y_codelight_desc *d, codelight_plan &p); /* reads the context's inverse chroma siting */
+int codelight_tables(h2y_ctx *ctx, codelight_plan &p);
+int pqcode_scratch(h2y_ctx *ctx, const codelight_plan &p);                    /* the context's scratch for one frame's upsampled chroma */
+linearize_frame pqcode_entry(const h2y_ctx *ctx, const codelight_plan &p, const char *payload, char *const planes[3]);
+int pqcode_decode(h2y_ctx *ctx, int slot);                                    /* k_up444 (4:2:0) and k_linearize on the slot's payload */
 
 /* ---- h2y_ring.hip: what a measurement's arm and *_stream_open entries use ----------------------------------------------------------- */
 

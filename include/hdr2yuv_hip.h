@@ -641,7 +641,7 @@ typedef struct h2y_light_stats {
  * them, h2y_last_kernel_name "k_light"); synchronous. */
 int h2y_light_batch(h2y_ctx *ctx, const h2y_desc *d, int n_frames, const void *const *d_planes, h2y_light_stats *out);
 
-/* Arm an open forward ring (h2y_stream_open, h2y_dpx_stream_open, h2y_tiff_stream_open, h2y_exr_stream_open; with or without
+/* Arm an open forward ring (h2y_stream_open, h2y_dpx_stream_open, h2y_tiff_stream_open, h2y_exr_stream_open, h2y_pqcode_stream_open; with or without
  * h2y_stream_compare and h2y_stream_histogram) before its first input: k_light then runs on every frame's decoded planes, on the
  * kernel stream after the conversion, with the floor and ceiling the conversion used; the output bytes do not change.
  * H2Y_EUNSUPPORTED for a descriptor out of the scope above, H2Y_EINVAL on any other ring. */
@@ -765,6 +765,33 @@ int h2y_codelight_batch(h2y_ctx *ctx, const h2y_codelight_desc *d, int n_frames,
  * _histogram_ex, _light, _lightdist, _scale, _gamut) is H2Y_EINVAL on this ring.  Refusals as h2y_codelight_batch; want_dist other
  * than 0 or 1 and depth outside 2..16 are H2Y_EINVAL. */
 int h2y_codelight_stream_open(h2y_ctx *ctx, const h2y_codelight_desc *d, int want_dist, int depth);
+
+/* ---- linearised PQ code planes: a finished PQ master as a LINEAR G,B,R F32 source of the forward flow (--linearize 1) ------------
+ * Nothing in the arithmetic is new.  The output is three binary32 planes G, B, R of width x height that hold L_G, L_B, L_R exactly as
+ * steps 1-4 of "light of PQ code planes" above define them, in that order: 4:2:0 chroma upsampled by k_up444 in the form `algorithm`
+ * and the context's inverse chroma siting select; the normalisation; the matrix, every operation rounded by itself; the clamp to
+ * [+0, 1]; PQ10000_f through light1<true>'s tiers; the clamp again.  Where k_codelight keeps m = max(L_G, L_B, L_R) of a pixel,
+ * k_linearize writes the three lights (both call the one function of h2y_codepixel.h).  The values lie in [+0, 1], 1.0 = 10000
+ * cd/m2: what k_gamut, k_tonemap, k_light and the forward kernels take as a LINEAR (transfer 8) G,B,R (matrix 0) F32 source.  Their
+ * floor and ceiling are 0 and 1 by stats_override: measured pic_stats of such planes are 0 / 0 whenever no sample reaches 1.0. */
+#define H2Y_LINEARIZE_FRAMES_PER_LAUNCH 8 /* h2y_codelight_batch's rule: the launch's 4:2:0 scratch is the same one */
+
+/* n_frames device frames of d, taken as h2y_codelight_batch takes them, into d_planes_out[f x 3 + c]: plane c = G, B, R of frame
+ * f, width x height binary32 each, 16-byte aligned, the layout h2y_light_batch, h2y_gamut_batch and h2y_convert_batch read.
+ * Launches of up to H2Y_LINEARIZE_FRAMES_PER_LAUNCH frames, each k_up444 per 4:2:0 frame and then one k_linearize
+ * (h2y_last_kernel_ms sums them, upsampling included; h2y_last_kernel_name "k_linearize"; the variant names the matrix and the
+ * upsampling form, e.g. "k_linearize<BT2020NC,FIR>"); synchronous.  Refusals word for word h2y_codelight_batch's, and H2Y_EINVAL
+ * for an output plane that is null or not 16-byte aligned. */
+int h2y_linearize_batch(h2y_ctx *ctx, const h2y_codelight_desc *d, int n_frames, const uint16_t *const *d_frames, void *const *d_planes_out);
+
+/* A forward ring whose decode is the linearisation, beside h2y_dpx_stream_open, h2y_tiff_stream_open and h2y_exr_stream_open:
+ * h2y_stream_input lends planes[0] for the code frame of src (its three planes one after the other, as above), the device runs
+ * k_up444 (4:2:0; one scratch of the context serves every slot) and k_linearize into the slot's three planes, and from there the
+ * ring is h2y_stream_open's on an F32 source: every arming entry works on it as on the DPX ring.  The inverse chroma siting is read
+ * when the ring opens.  Refusals: src as h2y_codelight_batch; H2Y_EINVAL unless d describes that source -- in_sample_type
+ * H2Y_SAMPLE_F32, src_transfer 8, src_matrix 0, width and height of src, stats_override 1 with floor 0 and ceiling 1 -- and for a
+ * depth outside 2..16. */
+int h2y_pqcode_stream_open(h2y_ctx *ctx, const h2y_desc *d, const h2y_codelight_desc *src, int depth);
 
 /* ---- scaling: an exact Lanczos resampler (--dst_pic_width / --dst_pic_height; the reference's cv.cpp is compiled out) ------------
  * The reference plugs a per-plane Lanczos cv::resize in at hdr2yuv.cpp:892-896, in a file that does not compile; it defines no
@@ -1003,7 +1030,7 @@ int h2y_upsample_444_sited(h2y_ctx *ctx, int width, int height, int chroma_sampl
                            const uint16_t *d_src, uint16_t *d_dst);
 
 /* Timing of the last h2y_convert_batch*() (or h2y_inverse_*, h2y_dpx_decode_batch, h2y_tiff_decode_batch,
- * h2y_rgb_interleave_batch, h2y_exr_decode_batch, h2y_compare_batch, h2y_ssim_batch, h2y_light_batch, h2y_lightdist_batch, h2y_codelight_batch, h2y_scale_batch, h2y_gamut_batch) call measured with HIP events on
+ * h2y_rgb_interleave_batch, h2y_exr_decode_batch, h2y_compare_batch, h2y_ssim_batch, h2y_light_batch, h2y_lightdist_batch, h2y_codelight_batch, h2y_linearize_batch, h2y_scale_batch, h2y_gamut_batch) call measured with HIP events on
  * the stream the kernels ran on: total ms over the main kernels and how many
  * launches that covered. */
 int h2y_last_kernel_ms(const h2y_ctx *ctx, float *ms, int *launches);
@@ -1011,7 +1038,7 @@ int h2y_last_kernel_ms(const h2y_ctx *ctx, float *ms, int *launches);
 /* Name of the kernel those launches ran ("k_fused", "k_fused_t1", "k_fused_lut16",
  * "k_fused_narrow"; of the inverse entries "k_inverse", "k_inverse420", "k_inverse_batch", "k_inverse420_batch"; of
  * h2y_dpx_decode_batch "k_dpx_decode"; of h2y_tiff_decode_batch "k_tiff_decode", of h2y_rgb_interleave_batch
- * "k_rgb_interleave"; of h2y_exr_decode_batch "k_exr_decode"; of h2y_compare_batch "k_compare"; of h2y_scale_batch "k_scale"; of h2y_gamut_batch "k_gamut"; of h2y_codelight_batch "k_codelight"): the name to
+ * "k_rgb_interleave"; of h2y_exr_decode_batch "k_exr_decode"; of h2y_compare_batch "k_compare"; of h2y_scale_batch "k_scale"; of h2y_gamut_batch "k_gamut"; of h2y_codelight_batch "k_codelight"; of h2y_linearize_batch "k_linearize"): the name to
  * look for in a rocprofv3 kernel trace. */
 const char *h2y_last_kernel_name(const h2y_ctx *ctx);
 /* The same with its template arguments and launch shape, e.g. "k_fused_t1<F32,420BOX,YCBCR,PQ_IDENT> groups=8 xcd=1";

@@ -134,6 +134,19 @@ Prints one line per figure, then one JSON line with all of them.
      warm-up, us per frame, and the two-pass form's 23 B/pixel over that time as a share of the peak;
   3. the two sitings alternating, five calls each (ABAB...: drift of the card shows in both alike), the same figures; and the
      default one-pass form (k_fir_fused, siting 0, "fir" "auto") in the same job: what a user gives up by choosing siting 2.
+Prints one line per figure, then one JSON line with all of them.
+
+`streambench.py linearize`: the linearisation of PQ code planes (k_linearize) on 4K frames, beside its yardsticks in the same job:
+  1. h2y_linearize_batch over 64 distinct device frames per call (HIP events round each launch of up to 8 frames, k_up444 included),
+     h2y_codelight_batch (LIGHT) on the same frames and h2y_gamut_batch (k_gamut, F32, in place, BT.2020 -> BT.709, clip on) on the
+     planes just written, the three taken in turn five times after a warm-up: median and spread in us per frame for 10-bit 4:2:0
+     BT.2020nc FIR noise, the same as 10-bit 4:4:4, and 16-bit 4:4:4 matrix 0; the algorithmic bytes per frame -- the 18 B/pixel
+     of k_linearize itself (6 read, 12 written), and for 4:2:0 k_up444's 3 read, 4 written and 4 read back less the 4 of chroma
+     k_linearize no longer reads from the frame: 23 -- over that time as a share of the 8 TB/s HBM peak.  The yardstick printed
+     beside each: with no overlap at all the kernel would cost k_codelight's time plus a plain 18 B/pixel streaming pass at
+     k_gamut's rate (18 / 24 of k_gamut's time);
+  2. frames/s from host memory to PQ BT.2020nc 10-bit 4:2:0 of the PQ code ring (h2y_pqcode_stream_open, 10-bit 4:2:0 frames of
+     24.9 MB) beside the .f32 ring fed the linearised planes (99.5 MB a frame), both with the 0 / 1 override, three times in turn.
 Prints one line per figure, then one JSON line with all of them."""
 import os
 import sys
@@ -1220,6 +1233,113 @@ def codelight_main():
     print(json.dumps({"streambench_codelight": res}), flush=True)
 
 
+def linearize_main():
+    import json
+
+    import torch
+
+    w, hh, nb, reps = 3840, 2160, 64, 5
+    n = w * hh
+    nf = int(os.environ.get("N", "60"))
+    depth = 3
+    ctx = h.Context(0)
+    res = {"width": w, "height": hh, "frames_per_call": nb, "frames_per_launch": h.api.LINEARIZE_FRAMES_PER_LAUNCH, "reps": reps,
+           "ring_frames": nf, "ring_depth": depth, "hbm_peak_tbs": 8.0}
+
+    def codes(count, lo, hi):
+        return torch.randint(lo, hi + 1, (count,), dtype=torch.int32, device="cuda").to(torch.int16)
+
+    def noise(chroma, bits):
+        s = 1 << (bits - 8)
+        nc = n // 4 if chroma == 1 else n
+        return torch.cat([codes(n, 16 * s, 235 * s), codes(nc, 16 * s, 240 * s), codes(nc, 16 * s, 240 * s)])
+
+    def report(key, label, t, nbytes, variant):
+        med = float(np.median(t))
+        tbs = nbytes / (med * 1e-3) / 1e12
+        res[key] = dict(kernel_us_per_frame=round(med * 1e3, 2), min_us=round(min(t) * 1e3, 2), max_us=round(max(t) * 1e3, 2),
+                        bytes_per_frame=nbytes, kernel_tbs=round(tbs, 2), hbm_peak_fraction=round(tbs / 8.0, 3), variant=variant)
+        print(f"{label:34s} {nb} frames per call: {med*1e3:7.2f} us/frame ({min(t)*1e3:.2f}..{max(t)*1e3:.2f})  {tbs:5.2f} TB/s = "
+              f"{tbs/8.0*100:4.1f} % of 8 TB/s  {variant}", flush=True)
+        return med
+
+    # 1. k_linearize, k_codelight on the same frames, k_gamut on the planes just written, in turn
+    outs = [[torch.empty(n, dtype=torch.float32, device="cuda") for _ in range(3)] for _ in range(nb)]
+    for name, chroma, bits, matrix in (("420_10_noise", 1, 10, h.MATRIX_BT2020NC), ("444_10_noise", 3, 10, h.MATRIX_BT2020NC),
+                                       ("444_16_gbr_noise", 3, 16, h.MATRIX_GBR)):
+        d = h.make_codelight_desc(w, hh, chroma, bits, 0, matrix, 1)
+        frames = [noise(chroma, bits) for _ in range(nb)]
+        torch.cuda.synchronize()
+        t = {"lin": [], "light": [], "gamut": []}
+        variants = {}
+        for rep in range(reps + 1):  # the first round warms up
+            for key, call in (("lin", lambda: ctx.linearize_batch(d, frames, outs)), ("light", lambda: ctx.codelight_batch(d, frames)),
+                              ("gamut", lambda: ctx.gamut_batch(w, hh, h.SAMPLE_F32, 9, 1, 1, outs))):
+                call()
+                variants[key] = ctx.last_kernel_variant()
+                if rep:
+                    t[key].append(ctx.last_kernel_ms()[0] / nb)
+        m_lin = report(f"k_linearize_{name}", f"k_linearize {name}", t["lin"], n * (23 if chroma == 1 else 18), variants["lin"])
+        m_light = report(f"k_codelight_{name}", f"k_codelight {name} (yardstick)", t["light"], n * (11 if chroma == 1 else 6), variants["light"])
+        m_gamut = report(f"k_gamut_f32_{name}", f"k_gamut F32 in place (yardstick)", t["gamut"], 24 * n, variants["gamut"])
+        yard = m_light + m_gamut * 18.0 / 24.0
+        res[f"yardstick_{name}"] = dict(no_overlap_us_per_frame=round(yard * 1e3, 2), measured_over_yardstick=round(m_lin / yard, 3))
+        print(f"k_linearize {name}: {m_lin*1e3:7.2f} us/frame against k_codelight + 18 B/pixel at k_gamut's rate = {yard*1e3:7.2f} us/frame "
+              f"({m_lin/yard:5.3f} of it)", flush=True)
+        del frames
+        torch.cuda.empty_cache()
+
+    # 2. the PQ code ring beside the .f32 ring fed the linearised planes
+    cd = h.make_codelight_desc(w, hh, 1, 10, 0, h.MATRIX_BT2020NC, 1)
+    code = noise(1, 10)
+    ctx.linearize_batch(cd, [code], outs[:1])
+    planes = [t.cpu().numpy() for t in outs[0]]
+    payload = code.cpu().numpy().view(np.uint8)
+    del outs, code
+    torch.cuda.empty_cache()
+    d32 = h.make_desc(w, hh, dst_depth=10, dst_matrix=h.MATRIX_BT2020NC, resampler=1, stats=[(0, 1)] * 3)
+
+    def ring(open_fn, fill):
+        open_fn()
+        inflight = 0
+        t0 = time.perf_counter()
+        for _ in range(nf):
+            fill(ctx.stream_input())
+            ctx.stream_submit()
+            inflight += 1
+            if inflight == depth - 1:
+                ctx.stream_output()
+                inflight -= 1
+        while inflight:
+            ctx.stream_output()
+            inflight -= 1
+        dt = (time.perf_counter() - t0) / nf
+        ctx.stream_close()
+        return dt
+
+    def fill_code(slot):
+        slot[0][:] = payload
+
+    def fill_planes(slot):
+        for c in range(3):
+            slot[c][:] = planes[c]
+
+    rings = (("pqcode", lambda: ctx.pqcode_stream_open(d32, cd, depth), fill_code), ("f32", lambda: ctx.stream_open(d32, depth), fill_planes))
+    fps = {key: [] for key, _, _ in rings}
+    for rep in range(4):  # the first round warms up
+        for key, open_fn, fill in rings:
+            dt = ring(open_fn, fill)
+            if rep:
+                fps[key].append(1 / dt)
+    for key, bytes_up in (("pqcode", 3 * n), ("f32", 12 * n)):
+        res[f"{key}_ring"] = dict(fps=round(float(np.median(fps[key])), 1), min_fps=round(min(fps[key]), 1), max_fps=round(max(fps[key]), 1),
+                                  upload_bytes_per_frame=bytes_up)
+        print(f"{key:7s} ring from host memory to PQ BT.2020nc 10-bit 4:2:0: {np.median(fps[key]):6.1f} frames/s "
+              f"({min(fps[key]):.1f}..{max(fps[key]):.1f}), {bytes_up/1e6:5.1f} MB up per frame", flush=True)
+    ctx.close()
+    print(json.dumps({"streambench_linearize": res}), flush=True)
+
+
 def scale_main():
     import json
 
@@ -1619,5 +1739,7 @@ if __name__ == "__main__":
         lightdist_main()
     elif sys.argv[1:] == ["codelight"]:
         codelight_main()
+    elif sys.argv[1:] == ["linearize"]:
+        linearize_main()
     else:
         main()
