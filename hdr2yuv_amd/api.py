@@ -40,6 +40,7 @@ EXPORTS = [
     "h2y_lightdist_batch", "h2y_stream_lightdist", "h2y_stream_lightdist_result", "h2y_lightdist_json",
     "h2y_codelight_batch", "h2y_codelight_stream_open",
     "h2y_linearize_batch", "h2y_pqcode_stream_open",
+    "h2y_deltae_batch", "h2y_stream_deltae", "h2y_stream_deltae_result",
     "h2y_scale_taps", "h2y_scale_frame_bytes", "h2y_scale_batch", "h2y_stream_scale", "h2y_scale_stream_open",
     "h2y_gamut_matrix", "h2y_gamut_batch", "h2y_stream_gamut",
     "h2y_tonemap_curve", "h2y_tonemap_batch", "h2y_stream_tonemap",
@@ -57,6 +58,7 @@ LIGHTDIST_FIRST_BITS = 0x37000000  # 2^-17: the lower edge of bin 1
 LIGHTDIST_PCT = (100, 500, 1000, 2500, 5000, 7500, 9000, 9500, 9900, 9998)  # the percentiles, in hundredths of a percent
 CODELIGHT_FRAMES_PER_LAUNCH = 8  # a launch's 4:2:0 scratch stays at 253 MiB for 3840 x 2160
 LINEARIZE_FRAMES_PER_LAUNCH = 8  # the same rule, the same scratch
+DELTAE_FRAMES_PER_LAUNCH = 4  # the same scratch again: four upsampled chroma planes a pair
 SCALE_FRAMES_PER_LAUNCH = 64
 GAMUT_FRAMES_PER_LAUNCH = 64
 TONEMAP_FRAMES_PER_LAUNCH = 64
@@ -224,6 +226,21 @@ class H2YLightdistStats(C.Structure):
 
     def __repr__(self):
         return f"H2YLightdistStats({self.as_dict()})"
+
+
+class H2YDeltaeStats(C.Structure):
+    """h2y_deltae_stats: a frame's Delta E ITP against its reference -- the largest per-pixel d as binary32 bits and the first pixel
+    (max_x, max_y) holding it, the caller's threshold, the sum over the pixels of rint(d x 2^20), the pixel count, the pixels with
+    d > threshold, and mean / max as doubles."""
+
+    _fields_ = [("max_bits", C.c_uint32), ("max_x", C.c_uint32), ("max_y", C.c_uint32), ("threshold", C.c_float), ("sum_q", C.c_uint64),
+                ("pixels", C.c_uint64), ("over", C.c_uint64), ("mean", C.c_double), ("max", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+    def __repr__(self):
+        return f"H2YDeltaeStats({self.as_dict()})"
 
 
 class H2YCodelightDesc(C.Structure):
@@ -447,6 +464,13 @@ def load_library():
     L.h2y_linearize_batch.restype = C.c_int
     L.h2y_pqcode_stream_open.argtypes = [C.c_void_p, C.POINTER(H2YDesc), C.POINTER(H2YCodelightDesc), C.c_int]
     L.h2y_pqcode_stream_open.restype = C.c_int
+    L.h2y_deltae_batch.argtypes = [C.c_void_p, C.POINTER(H2YCodelightDesc), C.c_float, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                   C.POINTER(H2YDeltaeStats)]
+    L.h2y_deltae_batch.restype = C.c_int
+    L.h2y_stream_deltae.argtypes = [C.c_void_p, C.POINTER(H2YCodelightDesc), C.c_float]
+    L.h2y_stream_deltae.restype = C.c_int
+    L.h2y_stream_deltae_result.argtypes = [C.c_void_p, C.POINTER(H2YDeltaeStats)]
+    L.h2y_stream_deltae_result.restype = C.c_int
     L.h2y_lightdist_json.argtypes = [C.POINTER(H2YLightdistStats), C.c_int, C.c_long, C.c_char_p, C.c_size_t]
     L.h2y_lightdist_json.restype = C.c_size_t
     L.h2y_scale_taps.argtypes = [C.c_int] * 3 + [C.c_void_p] * 3 + [C.POINTER(C.c_int)]
@@ -947,6 +971,18 @@ class Context:
         self._stream_rgb = False
         self._stream_cmp_planes = (d.width * d.height, nc, nc)
 
+    def deltae_batch(self, d: H2YCodelightDesc, frames_a, frames_b, threshold=1.0):
+        """k_deltae on device frame pairs of PQ codes (as codelight_batch takes each frame): a list of H2YDeltaeStats, one per
+        pair."""
+        n = len(frames_a)
+        if len(frames_b) != n:
+            raise ValueError("frames_a and frames_b differ in length")
+        pa = (C.c_void_p * max(n, 1))(*[self._ptr(x) for x in frames_a])
+        pb = (C.c_void_p * max(n, 1))(*[self._ptr(x) for x in frames_b])
+        out = (H2YDeltaeStats * max(n, 1))()
+        self._check(self.lib.h2y_deltae_batch(self.h, C.byref(d), float(threshold), n, pa, pb, out))
+        return list(out[:n])
+
     def linearize_batch(self, d: H2YCodelightDesc, frames, planes_out) -> None:
         """k_linearize on device frames of PQ codes (as codelight_batch takes them): planes_out[f] = three device planes G, B, R of
         float32, 16-byte aligned, receive the frame's linear light (1.0 = 10000 cd/m2)."""
@@ -1089,6 +1125,16 @@ class Context:
     def stream_ssim(self, bit_depth=-1) -> None:
         """Arm a compare-armed ring for SSIM too (bit_depth -1: the ring's own; a compare-only ring needs it given)."""
         self._check(self.lib.h2y_stream_ssim(self.h, bit_depth))
+
+    def stream_deltae(self, d: H2YCodelightDesc, threshold=1.0) -> None:
+        """Arm a compare-armed ring for Delta E ITP too: d describes the ring's frames as PQ code planes."""
+        self._check(self.lib.h2y_stream_deltae(self.h, C.byref(d), float(threshold)))
+
+    def stream_deltae_result(self) -> H2YDeltaeStats:
+        """The H2YDeltaeStats of the frame stream_output returned last."""
+        st = H2YDeltaeStats()
+        self._check(self.lib.h2y_stream_deltae_result(self.h, C.byref(st)))
+        return st
 
     def stream_light(self) -> None:
         """Arm an open forward ring (plain, DPX, TIFF or EXR) to measure every frame's content light (h2y_stream_light)."""

@@ -126,6 +126,22 @@
  *             matrix, 4:2:2, matrix 0 with 4:2:0 or with a .yuv, a .rgb with another matrix, odd 4:2:0 sizes, a .rgb / .tiff destination
  *             (the .yuv -> RGB flow), every *_only flag, --src_chroma_sample_loc_type 2 with --chroma_resampler_type 0 or with 4:4:4.
  *             Without the flag nothing changes: .yuv 4:4:4 -> .yuv stays the reference's integer flow.
+ * --delta_e 1 [--delta_e_threshold X] [--delta_e_limit Y] (an addition): Delta E ITP (Rec. ITU-R BT.2124; include/hdr2yuv_hip.h, "Delta E
+ *             ITP of PQ code planes", states every step) of every compared frame against the reference's, beside the PSNR, wherever a
+ *             comparison runs on PQ code frames of BT.2020 primaries: with --compare_only 1 on two .yuv files (--src_chroma_format_idc
+ *             1 or 3, --src_matrix_coeffs 1 or 9) or two .rgb files (matrix 0), --src_transfer_characteristics 16,
+ *             --src_colour_primaries 8 or 9, --src_bit_depth 8..16 and the source range flag, --chroma_resampler_type and
+ *             --src_chroma_sample_loc_type 0|2 choosing the 4:2:0 upsampler as for --light_only; or with --ref_filename on a forward run
+ *             to a PQ .yuv (--dst_transfer_characteristics 16, --dst_colour_primaries 8 or 9, --dst_matrix_coeffs 0, 1 or 9, 4:2:0 with
+ *             1 or 9 only), with or without --dst_filename, --linearize, --tone_map and --gamut_convert runs included, where
+ *             --dst_chroma_sample_loc_type 2 selects the top-left upsampler.  Beside --ssim and --histogram, same lines for any --gpus.
+ *             X (1 by default) is the threshold of the per-frame count `over` (d > X, strictly); --delta_e_limit Y makes the exit
+ *             status 5 when a frame's mean exceeds Y (status 3 and 4 keep precedence).  Refused (exit 1, also under --dry_run): a value
+ *             other than 0 or 1, the threshold or limit flag without --delta_e 1 or negative, no comparison in the run, a transfer other
+ *             than 16, primaries other than 8 / 9 (BT.709-primaries PQ would need --gamut_convert's pass first), matrix 11-15 or any
+ *             other, 4:2:2, matrix 0 with 4:2:0, the .yuv -> RGB flow, --histogram_only, --scale_only and --light_only, siting 2 with
+ *             --chroma_resampler_type 0, and with --linearize 1 a 4:2:0 source and destination whose sitings differ (one context siting
+ *             serves both upsamplers).  Without the flag not a line changes.
  * Only user_args_t.chroma_resampler_type has no defined default there (never initialised): FIR here, as in
  * make.sh's example.  The reference calls exit(0) on its argument errors; this program returns 1.
  */
@@ -205,6 +221,14 @@ struct cli_args {
     bool linearize_given = false;
     cli_pic lin{};
     int lin_type = CLI_IN_NONE;
+    /* --delta_e 1: Delta E ITP beside the comparison; --delta_e_threshold (the `over` count), --delta_e_limit (exit status 5);
+     * resolved by cli_resolve_delta_e: the compared frames as PQ code planes, and the inverse chroma siting their upsampler takes */
+    int delta_e = 0;
+    bool delta_e_given = false, delta_e_threshold_given = false, delta_e_limit_given = false;
+    float delta_e_threshold = 1.0f;
+    double delta_e_limit = 0.0;
+    h2y_codelight_desc de{};
+    int de_siting = 0;
     std::vector<int> devices;
     /* resolved */
     int in_type = CLI_IN_NONE, out_type = CLI_OUT_NONE;
@@ -257,7 +281,8 @@ static inline void cli_help()
            "  additional: [--synthetic SEEDFRAME] [--device D] [--gpus N [--devices d0,d1,..]] [--dry_run 1]\n"
            "  compare: [--ref_filename R.yuv|R.rgb [--sigma_compare S]] (the output against R, frame by frame; without\n"
            "  --dst_filename nothing is written), [--compare_only 1] (--src_filename against R, no conversion), [--ssim 1] (SSIM\n"
-           "  beside the PSNR)\n"
+           "  beside the PSNR), [--delta_e 1 [--delta_e_threshold X] [--delta_e_limit Y]] (Delta E ITP, BT.2124, of compared PQ BT.2020\n"
+           "  frames: per frame the mean, the max and the pixels above X, 1 by default; exit status 5 when a frame's mean exceeds Y)\n"
            "  histogram: [--histogram FILE [--histogram_bits B] [--check_range 1]] (code values of every frame the run produces,\n"
            "  totals into FILE; exit status 4 on a sample outside the legal range), [--histogram_only 1] (--src_filename, no conversion)\n"
            "  content light: [--content_light 1] (MaxCLL and MaxFALL of a conversion to PQ, per frame and for the run; without\n"
@@ -308,6 +333,9 @@ static inline void cli_parse(cli_args &a, int argc, char **argv)
         else if (is("--sigma_compare")) { a.sigma = atoi(val()); a.sigma_given = true; }
         else if (is("--compare_only")) a.compare_only = atoi(val());
         else if (is("--ssim")) { a.ssim = atoi(val()); a.ssim_given = true; }
+        else if (is("--delta_e")) { a.delta_e = atoi(val()); a.delta_e_given = true; }
+        else if (is("--delta_e_threshold")) { a.delta_e_threshold = strtof(val(), nullptr); a.delta_e_threshold_given = true; }
+        else if (is("--delta_e_limit")) { a.delta_e_limit = strtod(val(), nullptr); a.delta_e_limit_given = true; }
         else if (is("--content_light")) { a.light = atoi(val()); a.light_given = true; }
         else if (is("--light_only")) { a.light_only = atoi(val()); a.light_only_given = true; }
         else if (is("--linearize")) { a.linearize = atoi(val()); a.linearize_given = true; }
@@ -502,6 +530,7 @@ static inline int cli_resolve_siting(cli_args &a);
 static inline int cli_resolve_src_siting(cli_args &a);
 static inline int cli_resolve_light_only(cli_args &a);
 static inline int cli_resolve_linearize(cli_args &a);
+static inline int cli_resolve_delta_e(cli_args &a);
 static inline int cli_resolve(cli_args &a)
 {
     if (a.linearize_given) { /* first: what follows resolves the linearised source */
@@ -518,7 +547,10 @@ static inline int cli_resolve(cli_args &a)
             printf("WARNING: light_only(%d) not 0 or 1\n", a.light_only);
             return 1;
         }
-        if (a.light_only) return cli_resolve_light_only(a);
+        if (a.light_only) {
+            const int arg_errors = cli_resolve_light_only(a);
+            return arg_errors + (a.delta_e_given || a.delta_e_threshold_given || a.delta_e_limit_given ? cli_resolve_delta_e(a) : 0);
+        }
     }
     const int src_matrix_arg = a.in.matrix_coeffs; /* as given: the float readers force G,B,R on the input picture below */
     int arg_errors = a.hist_only    ? cli_resolve_histogram_only(a)
@@ -533,7 +565,10 @@ static inline int cli_resolve(cli_args &a)
     if (a.gamut_given || a.gamut_clip_given) arg_errors += cli_resolve_gamut(a, src_matrix_arg);
     if (a.tone_map_given || a.tone_src_peak_given || a.tone_dst_peak_given) arg_errors += cli_resolve_tone_map(a, src_matrix_arg);
     if (a.siting_given) arg_errors += cli_resolve_siting(a);
-    if (a.src_siting_given && !a.linearize) arg_errors += cli_resolve_src_siting(a); /* (--linearize 1 resolved its own) */
+    const bool de_flags = a.delta_e_given || a.delta_e_threshold_given || a.delta_e_limit_given;
+    /* (--linearize 1 resolved its own; under --compare_only 1 --delta_e 1 the flag chooses Delta E's upsampler, checked there) */
+    if (a.src_siting_given && !a.linearize && !(a.compare_only && a.delta_e == 1)) arg_errors += cli_resolve_src_siting(a);
+    if (de_flags) arg_errors += cli_resolve_delta_e(a);
     return arg_errors;
 }
 
@@ -1138,6 +1173,112 @@ static inline int cli_resolve_ssim(cli_args &a)
                a.out.height, chroma);
         return 1;
     }
+    return 0;
+}
+
+/* --delta_e: valid wherever a comparison runs on PQ code frames of BT.2020 primaries -- the source and R of --compare_only, or the
+ * .yuv a forward run produces -- with the attribute checks of --light_only on those frames; fills a.de and a.de_siting; returns the
+ * number of argument errors */
+static inline int cli_resolve_delta_e(cli_args &a)
+{
+    printf("delta_e: %d\n", a.delta_e);
+    if (a.delta_e != 0 && a.delta_e != 1) {
+        printf("WARNING: delta_e(%d) not 0 or 1\n", a.delta_e);
+        return 1;
+    }
+    if (!a.delta_e) {
+        if (a.delta_e_threshold_given || a.delta_e_limit_given) {
+            printf("WARNING: --delta_e_threshold and --delta_e_limit need --delta_e 1\n");
+            return 1;
+        }
+        return 0;
+    }
+    int arg_errors = 0;
+    if (!(a.delta_e_threshold >= 0.0f)) { printf("WARNING: delta_e_threshold(%g) is not a number >= 0\n", a.delta_e_threshold); arg_errors++; }
+    if (!(a.delta_e_limit >= 0.0)) { printf("WARNING: delta_e_limit(%g) is not a number >= 0\n", a.delta_e_limit); arg_errors++; }
+    if (a.hist_only || a.scale_only || a.light_only) {
+        printf("WARNING: --delta_e 1 judges a comparison: not with --%s 1\n", a.hist_only ? "histogram_only" : a.scale_only ? "scale_only" : "light_only");
+        return arg_errors + 1;
+    }
+    if (!a.ref) {
+        printf("WARNING: --delta_e 1 needs a comparison: --ref_filename R (with or without --dst_filename, or with --compare_only 1)\n");
+        return arg_errors + 1;
+    }
+    if (a.inverse) {
+        printf("WARNING: --delta_e 1 judges PQ code frames: the .yuv -> RGB flow's output is compared by --compare_only 1 on the written .rgb\n");
+        return arg_errors + 1;
+    }
+    if (!a.compare_only && a.out_type != CLI_OUT_YUV) return arg_errors; /* refused elsewhere with its own message */
+    const bool src = a.compare_only != 0, rgb = src && a.in_type == CLI_IN_RGB;
+    const cli_pic &p = src ? a.in : a.out;
+    const char *side = src ? "src" : "dst";
+    const int m = p.matrix_coeffs, chroma = p.chroma_format_idc, siting = src ? a.src_siting : a.siting;
+    if (src && a.src_siting_given) printf("src_chroma_sample_loc_type: %d\n", a.src_siting);
+    if (p.bit_depth < 8 || p.bit_depth > 16) { printf("WARNING: --delta_e 1 takes frames of bit_depth 8..16, not %d\n", p.bit_depth); arg_errors++; }
+    if (p.video_full_range_flag != 0 && p.video_full_range_flag != 1) {
+        printf("WARNING: video_full_range_flag(%d) not 0 or 1\n", p.video_full_range_flag);
+        arg_errors++;
+    }
+    if (p.transfer_characteristics != 16) {
+        printf("WARNING: --delta_e 1 judges PQ codes: %s_transfer_characteristics(%d) is not 16\n", side, p.transfer_characteristics);
+        arg_errors++;
+    }
+    if (p.colour_primaries != 8 && p.colour_primaries != 9) {
+        printf("WARNING: --delta_e 1 takes BT.2020 primaries: %s_colour_primaries(%d) is not 8 or 9 (other primaries need --gamut_convert's pass "
+               "first)\n", side, p.colour_primaries);
+        arg_errors++;
+    }
+    if (m != H2Y_MATRIX_GBR && m != H2Y_MATRIX_BT709 && m != H2Y_MATRIX_BT2020NC) {
+        printf("WARNING: --delta_e 1: %s_matrix_coeffs(%d) not %d (G,B,R), %d (BT.709) or %d (BT.2020nc)\n", side, m, H2Y_MATRIX_GBR, H2Y_MATRIX_BT709,
+               H2Y_MATRIX_BT2020NC);
+        arg_errors++;
+    } else if (rgb && m != H2Y_MATRIX_GBR) {
+        printf("WARNING: a .rgb holds planes R, G, B: --delta_e of .rgb files takes src_matrix_coeffs %d, not %d\n", H2Y_MATRIX_GBR, m);
+        arg_errors++;
+    } else if (src && !rgb && a.in_type == CLI_IN_YUV && m == H2Y_MATRIX_GBR) {
+        printf("WARNING: --delta_e of .yuv files takes src_matrix_coeffs %d or %d, not %d: G,B,R planes come as .rgb\n", H2Y_MATRIX_BT709,
+               H2Y_MATRIX_BT2020NC, m);
+        arg_errors++;
+    }
+    if (chroma == 2) { printf("WARNING: --delta_e 1: chroma_format_idc 2 (4:2:2) is not judged\n"); arg_errors++; }
+    else if (chroma != H2Y_CHROMA_420 && chroma != H2Y_CHROMA_444) { /* (--compare_only has said so already) */
+        if (!src) { printf("WARNING: chroma_format_idc(%d) not %d or %d\n", chroma, H2Y_CHROMA_420, H2Y_CHROMA_444); arg_errors++; }
+    } else if (chroma == H2Y_CHROMA_420 && m == H2Y_MATRIX_GBR) {
+        printf("WARNING: --delta_e 1: G,B,R planes (%s_matrix_coeffs %d) are 4:4:4, not chroma_format_idc %d\n", side, H2Y_MATRIX_GBR, chroma);
+        arg_errors++;
+    } else if (chroma == H2Y_CHROMA_420 && ((p.width | p.height) & 1)) {
+        printf("WARNING: --delta_e 1: 4:2:0 needs an even width and height, not %dx%d\n", p.width, p.height);
+        arg_errors++;
+    }
+    if (src) { /* the forward flow's --dst_chroma_sample_loc_type has its own checks (cli_resolve_siting) */
+        if (siting == 1) {
+            printf("WARNING: src_chroma_sample_loc_type(1) is replication's siting, --chroma_resampler_type 0: not selected by this flag\n");
+            arg_errors++;
+        } else if (siting != 0 && siting != 2) {
+            printf("WARNING: src_chroma_sample_loc_type(%d) not 0 or 2\n", siting);
+            arg_errors++;
+        } else if (siting == 2 && chroma != H2Y_CHROMA_420) {
+            printf("WARNING: --src_chroma_sample_loc_type 2 sites 4:2:0 chroma: src_chroma_format_idc(%d) has none to site\n", chroma);
+            arg_errors++;
+        } else if (siting == 2 && a.resampler == 0) {
+            printf("WARNING: --src_chroma_sample_loc_type 2 needs the FIR resampler: replication (--chroma_resampler_type 0) is centre sited by "
+                   "construction\n");
+            arg_errors++;
+        }
+    } else if (a.linearize && a.lin.chroma_format_idc == H2Y_CHROMA_420 && chroma == H2Y_CHROMA_420 && a.src_siting != a.siting) {
+        printf("WARNING: --delta_e 1 with --linearize 1: --src_chroma_sample_loc_type (%d) and --dst_chroma_sample_loc_type (%d) must agree, one "
+               "inverse chroma siting serves both upsamplers\n", a.src_siting, a.siting);
+        arg_errors++;
+    }
+    if (arg_errors) return arg_errors;
+    a.de = h2y_codelight_desc{p.width, p.height, chroma, p.bit_depth, p.video_full_range_flag, m, a.resampler};
+    a.de_siting = siting == 2 ? 2 : 0;
+    static const char *const kMatrix[10] = {"G,B,R", "BT.709", "", "", "", "", "", "", "", "BT.2020nc"};
+    printf("delta_e_from: %s PQ codes, bit_depth %d %s range, matrix_coeffs %d (%s), chroma_format_idc %d, upsampler %s, threshold %g%s\n",
+           src ? "source" : "output", p.bit_depth, p.video_full_range_flag ? "full" : "video", m, kMatrix[m], chroma,
+           chroma == H2Y_CHROMA_444 ? "none" : !a.resampler ? "replicate" : siting == 2 ? "fir_top_left" : "fir", (double)a.delta_e_threshold,
+           a.delta_e_threshold_given ? "" : " (default)");
+    if (a.delta_e_limit_given) printf("delta_e_limit: %g\n", a.delta_e_limit);
     return 0;
 }
 

@@ -56,6 +56,16 @@
  *   ssim summary frames <N> <P0> <m> <P1> <m> <P2> <m> all <m> db ...     the means over frames (summed in frame order), dB of them
  *   ssim worst frame <k> all <v>                                          the lowest all, the first such frame on ties
  *
+ * Delta E ITP (--delta_e 1 [--delta_e_threshold X] [--delta_e_limit Y] beside a comparison of PQ code frames; h2y_cli_args.h): each GPU
+ * thread sets its context's inverse chroma siting where the frames' siting flag says 2 and arms its ring for Delta E too
+ * (h2y_stream_deltae) and keeps the figures of frame k by its index; the report follows the SSIM report, so it is the same for any
+ * --gpus.  Values "%.6f", the share of the frame's pixels above the threshold in percent "%.4f":
+ *   delta_e: frame <k> mean <m> max <d> at <x> <y> over <n> share <s>        one line per frame, in order
+ *   delta_e: summary frames <N> mean <m> worst frame <k> mean <m> max <d> frame <k> at <x> <y> over <n> share <s>
+ * the summary's mean is the mean of the frames' means (summed in frame order), worst the frame with the largest mean and max the largest
+ * max (the first such frame on ties), over and share over all frames.  Exit status 5 when --delta_e_limit Y was given and a frame's mean
+ * exceeds Y (3 and 4 before it).
+ *
  * Histogram (--histogram FILE [--histogram_bits B] [--check_range 1], or --histogram_only 1; h2y_cli_args.h): each GPU thread arms
  * its ring (h2y_stream_histogram; h2y_stream_histogram_ex on a compare-only ring) or opens a histogram-only ring, keeps the stats
  * of frame k by its index and sums its frames' bins; the report is printed once every thread is done, so it, and FILE, are the
@@ -173,6 +183,7 @@ static bool read_ref(FILE *f, bool rgb, size_t plane_bytes, size_t frame_bytes, 
 struct results {
     std::vector<h2y_compare_stats> compare;
     std::vector<h2y_ssim_stats> ssim;
+    std::vector<h2y_deltae_stats> deltae;
     std::vector<h2y_light_stats> light;
     std::vector<h2y_lightdist_stats> lightdist;
     std::vector<h2y_histogram_stats> hist;
@@ -181,7 +192,7 @@ struct results {
     std::vector<uint64_t> total;                   /* per GPU thread: its sums */
     size_t nbins = 0;
     results(const cli_args &a, long frames)
-        : compare(a.ref ? (size_t)frames : 0), ssim(a.ssim ? (size_t)frames : 0), light(a.light ? (size_t)frames : 0),
+        : compare(a.ref ? (size_t)frames : 0), ssim(a.ssim ? (size_t)frames : 0), deltae(a.delta_e ? (size_t)frames : 0), light(a.light ? (size_t)frames : 0),
           lightdist(a.dynmeta ? (size_t)frames : 0), hist(a.hist ? (size_t)frames : 0), occupied(hist.size())
     {
         if (!a.hist) return;
@@ -194,6 +205,7 @@ struct results {
     {
         if (a.ref && h2y_stream_compare_result(ctx, &compare[k])) return false;
         if (a.ssim && h2y_stream_ssim_result(ctx, &ssim[k])) return false;
+        if (a.delta_e && h2y_stream_deltae_result(ctx, &deltae[k])) return false;
         if (a.hist) {
             uint32_t *b = &bins[(size_t)r * 3 * nbins];
             uint64_t *t = &total[(size_t)r * 3 * nbins];
@@ -349,8 +361,10 @@ static flow forward_flow(const job &j)
     flow f;
     f.open = [&j, &a, &s](h2y_ctx *ctx) {
         if (a.siting && h2y_ctx_set_chroma_siting(ctx, a.siting)) return (int)H2Y_EINVAL; /* before the ring is opened */
+        /* the inverse siting serves --linearize's upsampler and --delta_e's (cli_resolve_delta_e has them agree where both upsample) */
+        const int inv_siting = a.linearize && a.src_siting ? a.src_siting : a.delta_e ? a.de_siting : 0;
+        if (inv_siting && h2y_ctx_set_inverse_chroma_siting(ctx, inv_siting)) return (int)H2Y_EINVAL;
         if (a.linearize) { /* the file's PQ codes, linearised on the device into the planes j.d describes */
-            if (a.src_siting && h2y_ctx_set_inverse_chroma_siting(ctx, a.src_siting)) return (int)H2Y_EINVAL;
             const h2y_codelight_desc code{a.lin.width, a.lin.height, a.lin.chroma_format_idc, a.lin.bit_depth, a.lin.video_full_range_flag,
                                           a.lin.matrix_coeffs, a.resampler};
             return h2y_pqcode_stream_open(ctx, &j.d, &code, kRingDepth);
@@ -362,6 +376,7 @@ static flow forward_flow(const job &j)
     };
     f.arm = [&a](h2y_ctx *ctx) {
         return (a.ref && h2y_stream_compare(ctx, a.sigma, a.dst ? 1 : 0)) || (a.ssim && h2y_stream_ssim(ctx, -1)) ||
+               (a.delta_e && h2y_stream_deltae(ctx, &a.de, a.delta_e_threshold)) ||
                (a.hist && h2y_stream_histogram(ctx, a.hist_bits)) || (a.light && h2y_stream_light(ctx)) ||
                (a.dynmeta && h2y_stream_lightdist(ctx)) ||
                (a.gamut && h2y_stream_gamut(ctx, a.in.colour_primaries, a.out.colour_primaries, a.gamut_clip)) ||
@@ -498,9 +513,12 @@ static flow compare_flow(const job &j)
 {
     const cli_args &a = j.a;
     flow f = whole_frame_flow(j);
-    f.open = [&a](h2y_ctx *ctx) { return h2y_compare_stream_open(ctx, a.in.width, a.in.height, a.in.chroma_format_idc, a.sigma, kRingDepth); };
+    f.open = [&a](h2y_ctx *ctx) {
+        if (a.delta_e && a.de_siting && h2y_ctx_set_inverse_chroma_siting(ctx, a.de_siting)) return (int)H2Y_EINVAL; /* before the ring is opened */
+        return h2y_compare_stream_open(ctx, a.in.width, a.in.height, a.in.chroma_format_idc, a.sigma, kRingDepth);
+    };
     f.arm = [&a](h2y_ctx *ctx) {
-        return (a.ssim && h2y_stream_ssim(ctx, a.in.bit_depth)) ||
+        return (a.ssim && h2y_stream_ssim(ctx, a.in.bit_depth)) || (a.delta_e && h2y_stream_deltae(ctx, &a.de, a.delta_e_threshold)) ||
                (a.hist && h2y_stream_histogram_ex(ctx, a.hist_bits, a.hist_depth, a.hist_full, a.hist_gbr));
     };
     return f;
@@ -681,6 +699,31 @@ static void ssim_report(bool yuv, const std::vector<h2y_ssim_stats> &st)
     printf("ssim summary frames %zu", st.size());
     line(mean, mean_all / (double)st.size());
     printf("ssim worst frame %zu all %.6f\n", worst, st[worst].all);
+}
+
+/* the Delta E report of the header comment; returns the exit status (5: --delta_e_limit given and a frame's mean above it) */
+static int deltae_report(const cli_args &a, const std::vector<h2y_deltae_stats> &st)
+{
+    auto share = [](uint64_t over, uint64_t pixels) { return pixels ? 100.0 * (double)over / (double)pixels : 0.0; };
+    double mean = 0;
+    size_t worst = 0, top = 0;
+    uint64_t over = 0, pixels = 0;
+    bool beyond = false;
+    for (size_t k = 0; k < st.size(); k++) {
+        const h2y_deltae_stats &t = st[k];
+        printf("delta_e: frame %zu mean %.6f max %.6f at %u %u over %llu share %.4f\n", k, t.mean, t.max, t.max_x, t.max_y,
+               (unsigned long long)t.over, share(t.over, t.pixels));
+        mean += t.mean;
+        over += t.over, pixels += t.pixels;
+        if (t.mean > st[worst].mean) worst = k;
+        if (t.max > st[top].max) top = k;
+        beyond = beyond || t.mean > a.delta_e_limit;
+    }
+    if (st.empty()) return 0;
+    printf("delta_e: summary frames %zu mean %.6f worst frame %zu mean %.6f max %.6f frame %zu at %u %u over %llu share %.4f\n", st.size(),
+           mean / (double)st.size(), worst, st[worst].mean, st[top].max, top, st[top].max_x, st[top].max_y, (unsigned long long)over,
+           share(over, pixels));
+    return a.delta_e_limit_given && beyond ? 5 : 0;
 }
 
 /* the content light report of the header comment */
@@ -903,6 +946,10 @@ int main(int argc, char **argv)
     if ((!rc || rc == 3) && a.hist) {
         const int hrc = histogram_report(a, res.hist, res.occupied, res.histogram_total());
         if (hrc == 1 || !rc) rc = hrc;
+    }
+    if (ran && a.delta_e) {
+        const int drc = deltae_report(a, res.deltae);
+        if (!rc) rc = drc;
     }
     if (ran && a.light) light_report(res.light);
     if (ran && a.dynmeta && lightdist_report(a, res.lightdist)) rc = 1;

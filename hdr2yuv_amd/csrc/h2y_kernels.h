@@ -391,6 +391,25 @@ struct linearize_frame { /* one frame: its code planes as codelight_frame has th
 int h2y_linearize_grid(uint32_t npix, int n_frames); /* blocks per frame */
 hipError_t h2y_launch_linearize(int matrix, int grid, hipStream_t st, const codelight_args &a, const linearize_frame *frames, int n_frames);
 
+/* k_deltae (h2y_deltae.hip): Delta E ITP of pairs of such frames (include/hdr2yuv_hip.h, "Delta E ITP of PQ code planes") */
+struct deltae_frame { /* one pair: the planes of A and of B as codelight_frame has them */
+    const uint16_t *a[3], *b[3];
+};
+struct deltae_acc { /* one pair: zeroed before k_deltae */
+    unsigned long long key;  /* max over pixels of (d bits << 32) | ~index: the largest d, the first pixel on ties */
+    unsigned long long sum;  /* sum over pixels of rint(d x 2^20) */
+    unsigned long long over; /* pixels with d > threshold */
+};
+struct deltae_args {
+    codelight_args c;        /* k_codelight's, for both sides (vec: plane p of A and of B alike); pp also carries what code1 reads:
+                                dst_tf PQ, dst_fn H2Y_TFN_PQ_R, tf_ext[1] */
+    const void *table_r;     /* PQ10000_r's table (tfn_build_table of H2Y_TFN_PQ_R) */
+    float threshold;
+};
+int h2y_deltae_grid(uint32_t npix, int n_frames); /* blocks per pair */
+/* k_deltae over n_frames pairs into acc[pair] (zeroed by the caller); matrix: H2Y_MATRIX_GBR, _BT709 or _BT2020NC */
+hipError_t h2y_launch_deltae(int matrix, int grid, hipStream_t st, const deltae_args &a, const deltae_frame *frames, int n_frames, deltae_acc *acc);
+
 /* k_gamut (h2y_gamut.hip): the conversion between colour primaries of include/hdr2yuv_hip.h on frames of three float or half
  * planes G, B, R; dst may be src (in place) */
 struct gamut_frame {

@@ -1,7 +1,8 @@
 /*
  * h2y_light1.h -- what the kernels that measure light share (k_light in h2y_light.hip, k_lightdist in h2y_lightdist.hip, k_codelight
- * in h2y_codelight.hip): one sample's light as include/hdr2yuv_hip.h defines it, what a thread keeps of a pixel once its three
- * lights exist, and a 64-bit wave shuffle.  Device code only; include after h2y_device.h.
+ * in h2y_codelight.hip, k_deltae in h2y_deltae.hip): one sample's light as include/hdr2yuv_hip.h defines it and its way back to a
+ * code value, what a thread keeps of a pixel once its three lights exist, and a 64-bit wave shuffle.  Device code only; include
+ * after h2y_device.h.
  */
 #pragma once
 
@@ -23,6 +24,20 @@ __device__ __forceinline__ float light1(const pix_params &pp, const pq_recA *tab
         }
     }
     return x > 0.0f ? fminf(x, 1.0f) : 0.0f;
+}
+
+/* light1<true>'s twin for a destination stage: one light (in [+0, 1]) through the destination transfer pp.dst_fn by the conversion's
+ * tiers, pixel_fast()'s second stage word for word -- the function's table (tab), its full-range table, the careful tier */
+__device__ __forceinline__ float code1(const pix_params &pp, const pq_recA *tab, float x)
+{
+    const float x1 = x;
+    bool slow;
+    x = tfn_fast(x, tab, tfn_cut_of(pp.dst_fn), tfn_zero_bits(pp.dst_fn), tfn_one_bits(pp.dst_fn), &slow);
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(slow) != 0, 0)) {
+        x = pq_ext_gather(x1, x, slow, pp.tf_ext[1], tfn_lo_bits(pp.dst_fn));
+        if (slow) x = tf_from_linear_careful(pp.dst_tf, x1);
+    }
+    return x;
 }
 
 __device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int o)

@@ -1,5 +1,5 @@
 /*
- * h2y_measure.hip -- the measurements of the C-ABI shim: the comparison with a reference, SSIM, content light, the light distribution, the light of PQ code planes, histograms, the
+ * h2y_measure.hip -- the measurements of the C-ABI shim: the comparison with a reference, SSIM, content light, the light distribution, the light of PQ code planes, Delta E ITP, histograms, the
  * scaler and the conversion between colour primaries.  Each has its checks and geometry, its batch entry, its ring stage (ring_stage, h2y_shim.h), and its arm, result and
  * *_stream_open entries.
  */
@@ -901,6 +901,200 @@ int h2y_codelight_stream_open(h2y_ctx *ctx, const h2y_codelight_desc *d, int wan
     rc = stage_arm(ctx, STAGE_CODELIGHT, std::move(st), "code light");
     if (rc) stream_free(ctx);
     return rc;
+}
+
+/* ---- Delta E ITP of PQ code planes (h2y_deltae_batch, h2y_stream_deltae): include/hdr2yuv_hip.h states the definition ------------- */
+
+/* k_deltae's arguments from a checked plan: k_codelight's, and PQ10000_r's tables, what code1 reads of pix_params */
+static int deltae_args_of(h2y_ctx *ctx, codelight_plan &p, float threshold, deltae_args &a)
+{
+    if (!(threshold >= 0.0f)) return fail(ctx, H2Y_EINVAL, "the Delta E threshold must be a number >= 0");
+    int rc = codelight_tables(ctx, p);
+    if (!rc) rc = ensure_tfn(ctx, H2Y_TFN_PQ_R);
+    if (rc) return rc;
+    a.c = p.a;
+    a.c.pp.dst_tf = H2Y_TF_PQ;
+    a.c.pp.dst_fn = H2Y_TFN_PQ_R;
+    a.c.pp.tf_ext[1] = ctx->d_tfn_ext[H2Y_TFN_PQ_R];
+    a.table_r = ctx->d_tfn[H2Y_TFN_PQ_R];
+    a.threshold = threshold;
+    return H2Y_OK;
+}
+
+static std::string deltae_variant(const codelight_plan &p)
+{
+    return std::string("k_deltae<") + (p.matrix == H2Y_MATRIX_GBR ? "GBR" : p.matrix == H2Y_MATRIX_BT709 ? "BT709" : "BT2020NC") + "," +
+           (!p.sub ? "444" : p.form == UP_FIR_TL ? "FIR_TL" : p.form == UP_FIR ? "FIR" : "REPLICATE") + ">";
+}
+
+/* one 4:2:0 pair's chroma (A's planes a1, a2, B's b1, b2) upsampled into the four planes at up */
+static hipError_t deltae_upsample(const h2y_ctx *ctx, const codelight_plan &p, const uint16_t *a1, const uint16_t *a2, const uint16_t *b1,
+                                  const uint16_t *b2, char *up)
+{
+    up_args u = p.up;
+    u.src0 = a1, u.src1 = a2;
+    u.dst0 = reinterpret_cast<uint16_t *>(up);
+    u.dst1 = reinterpret_cast<uint16_t *>(up + p.plane_al);
+    const hipError_t e = h2y_launch_up444(ctx->stream, u);
+    if (e != hipSuccess) return e;
+    u.src0 = b1, u.src1 = b2;
+    u.dst0 = reinterpret_cast<uint16_t *>(up + 2u * p.plane_al);
+    u.dst1 = reinterpret_cast<uint16_t *>(up + 3u * p.plane_al);
+    return h2y_launch_up444(ctx->stream, u);
+}
+
+/* the pair's table entry: the two frames' own planes (off[] samples from their bases), or their lumas and the upsampled chroma at up */
+static deltae_frame deltae_entry(const codelight_plan &p, const uint32_t off[3], const uint16_t *a, const uint16_t *b, const char *up)
+{
+    if (!p.sub) return deltae_frame{{a, a + off[1], a + off[2]}, {b, b + off[1], b + off[2]}};
+    const uint16_t *u = reinterpret_cast<const uint16_t *>(up);
+    const size_t n = p.plane_al / sizeof(uint16_t);
+    return deltae_frame{{a, u, u + n}, {b, u + 2u * n, u + 3u * n}};
+}
+
+/* the stats of one frame of npix pixels, width wide, from its accumulator */
+static void deltae_finish(const deltae_acc &acc, uint32_t width, uint32_t npix, float threshold, h2y_deltae_stats *o)
+{
+    *o = h2y_deltae_stats{};
+    o->max_bits = (uint32_t)(acc.key >> 32);
+    const uint32_t i = ~(uint32_t)acc.key;
+    o->max_x = i % width;
+    o->max_y = i / width;
+    o->threshold = threshold;
+    o->sum_q = acc.sum;
+    o->pixels = npix;
+    o->over = acc.over;
+    o->mean = ((double)acc.sum * 0x1p-20) / (double)npix;
+    o->max = (double)bits2f(o->max_bits);
+}
+
+int h2y_deltae_batch(h2y_ctx *ctx, const h2y_codelight_desc *d, float threshold, int n_frames, const uint16_t *const *d_a,
+                     const uint16_t *const *d_b, h2y_deltae_stats *out)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
+    codelight_plan p;
+    int rc = codelight_check(ctx, d, p);
+    if (rc) return rc;
+    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
+    if (!d_a || !d_b || !out) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
+    for (int f = 0; f < n_frames; f++) {
+        if (!d_a[f] || !d_b[f]) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is null", f);
+        if (((uintptr_t)d_a[f] | (uintptr_t)d_b[f]) & 15u) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is not 16-byte aligned", f);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int per_launch = std::min(n_frames, H2Y_DELTAE_FRAMES_PER_LAUNCH);
+    deltae_args a;
+    deltae_frame *h;
+    rc = deltae_args_of(ctx, p, threshold, a);
+    if (!rc) rc = frame_table(ctx, n_frames, h);
+    if (!rc) rc = ensure(ctx, ctx->d_deltae, ctx->deltae_cap, (size_t)n_frames * sizeof(deltae_acc));
+    if (!rc && p.sub) rc = ensure(ctx, ctx->d_codelight_up, ctx->codelight_up_cap, (size_t)per_launch * 4u * p.plane_al);
+    if (rc) return rc;
+    /* pair f's upsampled chroma lies in the scratch of its place in its launch; the launches follow one another on one stream */
+    for (int f = 0; f < n_frames; f++)
+        h[f] = deltae_entry(p, p.off, d_a[f], d_b[f], p.sub ? ctx->d_codelight_up + (size_t)(f % per_launch) * 4u * p.plane_al : nullptr);
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_deltae, 0, (size_t)n_frames * sizeof(deltae_acc), ctx->stream));
+    rc = timed_launches(ctx, h, n_frames, H2Y_DELTAE_FRAMES_PER_LAUNCH, "k_deltae", [&](const deltae_frame *frames, int f0, int nf) {
+        for (int f = 0; p.sub && f < nf; f++) {
+            const uint16_t *xa = d_a[f0 + f], *xb = d_b[f0 + f];
+            const hipError_t e = deltae_upsample(ctx, p, xa + p.off[1], xa + p.off[2], xb + p.off[1], xb + p.off[2],
+                                                 ctx->d_codelight_up + (size_t)f * 4u * p.plane_al);
+            if (e != hipSuccess) return e;
+        }
+        return h2y_launch_deltae(p.matrix, h2y_deltae_grid(a.c.npix, nf), ctx->stream, a, frames, nf, ctx->d_deltae + f0);
+    });
+    if (rc) return rc;
+    std::vector<deltae_acc> acc(n_frames);
+    HIP_TRY(ctx, hipMemcpy(acc.data(), ctx->d_deltae, (size_t)n_frames * sizeof(deltae_acc), hipMemcpyDeviceToHost));
+    for (int f = 0; f < n_frames; f++) deltae_finish(acc[f], (uint32_t)d->width, a.c.npix, threshold, out + f);
+    ctx->last_variant = deltae_variant(p);
+    return H2Y_OK;
+}
+
+/* Delta E's ring stage: k_deltae after k_compare and k_ssim, on the slot's frame and its reference twin (the comparison's table
+ * entry).  One scratch serves every slot's four upsampled planes: the frames follow one another on the context's stream.  Per slot
+ * the pair's accumulator on the device and pinned, and its k_deltae table entry */
+struct deltae_stage : ring_stage {
+    struct slot {
+        deltae_acc *d = nullptr, *h = nullptr;
+        const uint16_t *a = nullptr, *b = nullptr;
+    };
+    std::vector<slot> ss;
+    codelight_plan p;
+    deltae_args a{};
+    uint32_t off[3] = {0, 0, 0}; /* the ring frame's planes */
+    char *up = nullptr;
+    deltae_frame *tab = nullptr;
+    int run(h2y_ctx *ctx, int k) override
+    {
+        const slot &s = ss[k];
+        HIP_TRY(ctx, hipMemsetAsync(s.d, 0, sizeof(deltae_acc), ctx->stream));
+        if (p.sub) HIP_TRY(ctx, deltae_upsample(ctx, p, s.a + off[1], s.a + off[2], s.b + off[1], s.b + off[2], up));
+        HIP_TRY(ctx, h2y_launch_deltae(p.matrix, h2y_deltae_grid(a.c.npix, 1), ctx->stream, a, tab + k, 1, s.d));
+        return H2Y_OK;
+    }
+    int download(h2y_ctx *ctx, int k) override
+    {
+        HIP_TRY(ctx, hipMemcpyAsync(ss[k].h, ss[k].d, sizeof(deltae_acc), hipMemcpyDeviceToHost, ctx->s_d2h));
+        return H2Y_OK;
+    }
+};
+
+int h2y_stream_deltae(h2y_ctx *ctx, const h2y_codelight_desc *d, float threshold)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    if (ctx->s_stage[STAGE_CODELIGHT]) return fail(ctx, H2Y_EINVAL, "a light-only ring takes no other stage");
+    const cmp_stage *cmp = stage_of<cmp_stage>(ctx, STAGE_COMPARE);
+    if (!cmp) return fail(ctx, H2Y_EINVAL, "the ring is not armed for comparison: h2y_stream_compare first");
+    if (ctx->s_stage[STAGE_DELTAE]) return fail(ctx, H2Y_EINVAL, "the ring computes Delta E already");
+    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    auto st = std::make_unique<deltae_stage>();
+    int rc = codelight_check(ctx, d, st->p); /* the inverse chroma siting is read here */
+    if (rc) return rc;
+    const ring_frame &f = ctx->s_frame;
+    if (d->width != f.width || d->height != f.height || d->chroma_format_idc != f.chroma)
+        return fail(ctx, H2Y_EINVAL, "Delta E: the descriptor is %dx%d chroma_format_idc %d, the ring's frame %dx%d chroma_format_idc %d", d->width,
+                    d->height, d->chroma_format_idc, f.width, f.height, f.chroma);
+    /* a forward ring's planes are G, B, R where its conversion's matrix is the identity */
+    const bool gbr = ctx->s_kind == h2y_ctx::RING_FORWARD ? ctx->s_desc.dst_matrix == H2Y_MATRIX_GBR : f.gbr;
+    if (f.depth && (d->bit_depth != f.depth || d->full_range != f.full_range || (d->matrix_coeffs == H2Y_MATRIX_GBR) != gbr))
+        return fail(ctx, H2Y_EINVAL, "Delta E: the descriptor (bit_depth %d, full_range %d, matrix_coeffs %d) is not the ring's frame (bit_depth %d, full_range %d, %s)",
+                    d->bit_depth, d->full_range, d->matrix_coeffs, f.depth, f.full_range, gbr ? "G,B,R" : "Y,Cb,Cr");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = deltae_args_of(ctx, st->p, threshold, st->a);
+    if (rc) return rc;
+    /* the ring's planes, not the contiguous ones of the plan: a plane takes 16-byte loads where it starts 16-byte aligned in both frames */
+    st->a.c.vec = 1u;
+    for (int c = 0; c < 3; c++) {
+        st->off[c] = f.off[c];
+        if (c) st->a.c.vec |= (st->p.sub || (((size_t)f.off[c] * sizeof(uint16_t)) & 15u) == 0) ? 1u << c : 0u;
+    }
+    const int depth = (int)ctx->ss.size();
+    if (st->p.sub) st->dev_alloc(st->up, 4u * st->p.plane_al);
+    std::vector<deltae_frame> tab(depth);
+    st->ss.resize(depth);
+    for (int k = 0; k < depth; k++) {
+        deltae_stage::slot &s = st->ss[k];
+        st->dev_alloc(s.d, sizeof(deltae_acc));
+        st->pin_alloc(s.h, sizeof(deltae_acc));
+        s.a = frame_base(ctx, k);
+        s.b = reinterpret_cast<const uint16_t *>(cmp->ss[k].d_ref);
+        tab[k] = deltae_entry(st->p, st->off, s.a, s.b, st->up);
+    }
+    st->table(st->tab, tab);
+    return stage_arm(ctx, STAGE_DELTAE, std::move(st), "Delta E");
+}
+
+int h2y_stream_deltae_result(h2y_ctx *ctx, h2y_deltae_stats *out)
+{
+    if (!ctx || !out) return fail(ctx, H2Y_EINVAL, "null argument");
+    const deltae_stage *st = ctx->streaming ? stage_of<deltae_stage>(ctx, STAGE_DELTAE) : nullptr;
+    if (!st) return fail(ctx, H2Y_EINVAL, "no stream open that computes Delta E");
+    if (ctx->s_lent < 0) return fail(ctx, H2Y_EINVAL, "no output taken yet: h2y_stream_output first");
+    deltae_finish(*st->ss[ctx->s_lent].h, (uint32_t)ctx->s_frame.width, st->a.c.npix, st->a.threshold, out);
+    return H2Y_OK;
 }
 
 /* ---- linearised PQ code planes (h2y_linearize_batch, h2y_pqcode_stream_open): include/hdr2yuv_hip.h states the definition ------ */

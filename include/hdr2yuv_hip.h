@@ -793,6 +793,70 @@ int h2y_linearize_batch(h2y_ctx *ctx, const h2y_codelight_desc *d, int n_frames,
  * depth outside 2..16. */
 int h2y_pqcode_stream_open(h2y_ctx *ctx, const h2y_desc *d, const h2y_codelight_desc *src, int depth);
 
+/* ---- Delta E ITP of PQ code planes: the visible difference (Rec. ITU-R BT.2124) of a PQ picture from a reference (--delta_e 1) -----
+ * PSNR and SSIM judge code values; this judges what is seen: 720 x the Euclidean distance in ICtCp with T = Ct / 2, where 1.0 is about
+ * one just-noticeable difference.  The reference has nothing here: it is the project's own definition, every step in binary32.
+ * Two frames A and B of one geometry, each exactly what h2y_codelight_desc describes: three u16 code planes at bit depth 8..16, video or
+ * full range, matrix_coeffs 0, 1 or 9, chroma_format_idc 3, or 1 with even sizes, `algorithm` for the 4:2:0 upsampler.  The transfer is
+ * PQ; the planes are taken as BT.2020 primaries (the entries take no primaries: the caller checks them).
+ * Per pixel, for A and for B alike:
+ *   1. Steps 1-4 of "light of PQ code planes" give L_G, L_B, L_R in [+0, 1] (code_lights<MATRIX>, h2y_codepixel.h), 4:2:0 chroma first
+ *      upsampled by k_up444 in the form `algorithm` and the context's inverse chroma siting select.
+ *   2. LMS (BT.2100), every product and every sum rounded by itself to binary32, left to right, no fused multiply-add; the constants
+ *      are k / 4096, exact in binary32; with R = L_R, G = L_G, B = L_B:
+ *        l = ((1688/4096) R + (2146/4096) G) + (262/4096) B
+ *        m = ((683/4096) R + (2951/4096) G) + (462/4096) B
+ *        s = ((99/4096) R + (309/4096) G) + (3688/4096) B
+ *      each then v > 0 ? min(v, 1) : +0.  Every row adds up to 4096/4096 and the inputs are <= 1, so by monotone rounding no value exceeds
+ *      1; the clamp is kept so that the table tiers never see anything else.
+ *   3. l' = PQ10000_r(l), m' and s' likewise: the binary32 value the forward conversion's own tiers give for that argument (the
+ *      H2Y_TFN_PQ_R table, the full-range table, the careful tier: pixel_fast()'s destination stage).  PQ10000_r(+0) = 7.3e-7, not 0.
+ *   4. ITP, every constant exact in binary32, every product and sum rounded by itself, left to right:
+ *        I = 0.5 l' + 0.5 m'
+ *        T = ((6610/8192) l' - (13613/8192) m') + (7003/8192) s'      (= Ct / 2)
+ *        P = ((17933/4096) l' - (17390/4096) m') - (543/4096) s'      (= Cp)
+ *   5. dI = I_A - I_B, dT and dP likewise;  d = 720 x sqrt((dI dI + dT dT) + dP dP), every operation rounded by itself, the square
+ *      root the correctly rounded IEEE one.  d is finite, never negative, and below 2^13.
+ * Per frame, all exact integers, independent of the order of the work and of the GPU count:
+ *   pixels = width x height;  sum_q = the sum over the pixels of rint(d x 2^20) (the product is exact; a term is at most 2^33, a 2^28-
+ *   pixel frame stays below 2^61) in uint64;  max_bits = the largest d as a binary32 bit pattern and (max_x, max_y) the first pixel in
+ *   raster order that holds it;  over = the pixels with d > threshold, strictly, threshold a binary32 of the caller's.
+ *   mean = ((double)sum_q x 2^-20) / pixels and max = (double)d_max are conveniences computed on the host in binary64.
+ * Anchors (10-bit video range, Cb = Cr = 512): Y against Y + 1 gives d = 0.822 (720 / 876) anywhere on the scale; Y 64 against Y 940
+ * gives 720. */
+#define H2Y_DELTAE_FRAMES_PER_LAUNCH 4 /* a launch's 4:2:0 scratch: 4 planes x 2 bytes x width x height x 4 pairs -- 253 MiB at 3840 x 2160 */
+
+typedef struct h2y_deltae_stats {
+    uint32_t max_bits;     /* the largest d of the frame, as binary32 bits */
+    uint32_t max_x, max_y; /* the first pixel in raster order that holds it */
+    float threshold;       /* the caller's */
+    uint64_t sum_q;        /* sum over the pixels of rint(d x 2^20) */
+    uint64_t pixels;       /* width x height */
+    uint64_t over;         /* pixels with d > threshold */
+    double mean;           /* (sum_q x 2^-20) / pixels */
+    double max;            /* the largest d */
+} h2y_deltae_stats;
+
+/* Delta E ITP of n_frames pairs of device frames of d: d_a[f] and d_b[f] each hold a frame's three planes one after the other from a
+ * 16-byte aligned base, as h2y_codelight_batch takes them; out[f] (host memory).  Launches of up to H2Y_DELTAE_FRAMES_PER_LAUNCH
+ * pairs, each k_up444 twice per 4:2:0 pair (four upsampled chroma planes a pair, in a scratch area the context owns) and then one
+ * k_deltae (h2y_last_kernel_ms sums them, upsampling included; h2y_last_kernel_name "k_deltae"; the variant names the matrix and the
+ * upsampling form, e.g. "k_deltae<BT2020NC,FIR>"); synchronous.  Refusals word for word h2y_codelight_batch's, and H2Y_EINVAL for a
+ * threshold that is NaN or negative. */
+int h2y_deltae_batch(h2y_ctx *ctx, const h2y_codelight_desc *d, float threshold, int n_frames, const uint16_t *const *d_a,
+                     const uint16_t *const *d_b, h2y_deltae_stats *out);
+
+/* Arm a ring that h2y_stream_compare or h2y_compare_stream_open has armed, before its first input, beside h2y_stream_ssim and the
+ * histogram: k_deltae then runs on every slot's device frame (A) and its reference twin (B), on the kernel stream after k_compare and
+ * k_ssim; the output bytes and every other stage's results do not change.  d must agree with the ring's frame -- size and chroma
+ * format, and where the ring knows them bit depth, range and matrix_coeffs 0 exactly where its planes are G, B, R -- otherwise
+ * H2Y_EINVAL.  The stage owns one scratch for the four upsampled planes (stream order makes one enough); the inverse chroma siting is
+ * read here.  H2Y_EINVAL on a ring not armed for comparison (the histogram-only and scale-only rings among them) and on the light-only
+ * ring; d's and the threshold's refusals as h2y_deltae_batch. */
+int h2y_stream_deltae(h2y_ctx *ctx, const h2y_codelight_desc *d, float threshold);
+/* Delta E ITP of the frame that h2y_stream_output returned last. */
+int h2y_stream_deltae_result(h2y_ctx *ctx, h2y_deltae_stats *out);
+
 /* ---- scaling: an exact Lanczos resampler (--dst_pic_width / --dst_pic_height; the reference's cv.cpp is compiled out) ------------
  * The reference plugs a per-plane Lanczos cv::resize in at hdr2yuv.cpp:892-896, in a file that does not compile; it defines no
  * bytes.  This is the project's own definition, in integers, so that a restatement checks every output byte.

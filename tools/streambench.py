@@ -85,6 +85,12 @@ Prints one line per figure, then one JSON line with all of them.
   3. frames/s from host memory of the .f32 ring to PQ BT.2020nc 10-bit 4:2:0, unarmed and armed with h2y_stream_lightdist.
 Prints one line per figure, then one JSON line with all of them.
 
+`streambench.py deltae`: Delta E ITP of PQ code planes (k_deltae) on 4K frames, in one job:
+  1. h2y_deltae_batch over 64 distinct device frame pairs per call, 10-bit 4:2:0 and 4:4:4, beside h2y_codelight_batch (on A),
+     h2y_compare_batch and h2y_ssim_batch on the same pairs, five calls each taken in turn after a warm-up, the median per frame; the
+     k_up444 share of the 4:2:0 time from the 4:4:4 figure.
+  2. the compare-only ring from host memory, unarmed and armed with h2y_stream_deltae, three runs of each in turn.
+
 `streambench.py codelight`: the light of PQ code planes (k_codelight) on 4K frames, in one job:
   1. h2y_codelight_batch over 64 distinct device frames per call, DIST off and on, five calls each taken in turn after a warm-up (HIP
      events round each launch of up to 8 frames, k_up444 included; the memset of the accumulators lies before the first event): the
@@ -1233,6 +1239,117 @@ def codelight_main():
     print(json.dumps({"streambench_codelight": res}), flush=True)
 
 
+def deltae_main():
+    import json
+
+    import torch
+
+    w, hh, nb, reps = 3840, 2160, 64, 5
+    n = w * hh
+    nf = int(os.environ.get("N", "60"))
+    depth = 3
+    ctx = h.Context(0)
+    res = {"width": w, "height": hh, "frames_per_call": nb, "frames_per_launch": h.DELTAE_FRAMES_PER_LAUNCH, "reps": reps, "ring_frames": nf,
+           "ring_depth": depth, "hbm_peak_tbs": 8.0}
+
+    def codes(count, lo, hi):
+        return torch.randint(lo, hi + 1, (count,), dtype=torch.int32, device="cuda").to(torch.int16)
+
+    def noise(chroma):
+        nc = n // 4 if chroma == 1 else n
+        return torch.cat([codes(n, 64, 940), codes(nc, 64, 960), codes(nc, 64, 960)])
+
+    def timed(calls):
+        """every call of calls in turn, reps times after a warm-up: per call its kernel times in ms per frame"""
+        out = [[] for _ in calls]
+        for rep in range(reps + 1):
+            for k, call in enumerate(calls):
+                call()
+                if rep:
+                    out[k].append(ctx.last_kernel_ms()[0] / nb)
+        return out
+
+    def report(key, label, t, nbytes, variant):
+        med = float(np.median(t))
+        tbs = nbytes / (med * 1e-3) / 1e12
+        res[key] = dict(kernel_us_per_frame=round(med * 1e3, 2), min_us=round(min(t) * 1e3, 2), max_us=round(max(t) * 1e3, 2),
+                        bytes_per_frame=nbytes, kernel_tbs=round(tbs, 2), hbm_peak_fraction=round(tbs / 8.0, 3), variant=variant)
+        print(f"{label:30s} {nb} pairs per call: {med*1e3:7.2f} us/frame ({min(t)*1e3:.2f}..{max(t)*1e3:.2f})  {tbs:5.2f} TB/s = "
+              f"{tbs/8.0*100:4.1f} % of 8 TB/s  {variant}", flush=True)
+        return med
+
+    # 1. k_deltae beside k_codelight (on A), k_compare and k_ssim on the same 64 pairs, in turn.  Bytes: 4:2:0 -- 6 B/pixel read by
+    # k_up444 and k_deltae's lumas, 8 B/pixel of scratch written and 8 read back, 22 in all; 4:4:4 -- 12 read.
+    med = {}
+    for name, chroma in (("420_10", 1), ("444_10", 3)):
+        d = h.make_codelight_desc(w, hh, chroma, 10, 0, h.MATRIX_BT2020NC, 1)
+        a = [noise(chroma) for _ in range(nb)]
+        b = [torch.clamp(x + torch.randint(-2, 3, x.shape, dtype=torch.int16, device="cuda"), 0, 1023) for x in a]
+        torch.cuda.synchronize()
+        variants = {}
+        note = lambda key: variants.setdefault(key, ctx.last_kernel_variant())
+        t = timed([lambda: (ctx.deltae_batch(d, a, b), note("de")), lambda: (ctx.codelight_batch(d, a), note("cl")),
+                   lambda: (ctx.compare_batch(w, hh, chroma, 0, a, b), note("cmp")), lambda: (ctx.ssim_batch(w, hh, chroma, 10, a, b), note("ssim"))])
+        frame = n * (3 if chroma == 1 else 6)
+        med[name] = report(f"k_deltae_{name}", f"k_deltae {name}", t[0], n * (22 if chroma == 1 else 12), variants["de"])
+        m_cl = report(f"k_codelight_{name}", f"k_codelight {name} (A alone)", t[1], n * (11 if chroma == 1 else 6), variants["cl"])
+        report(f"k_compare_{name}", f"k_compare {name}", t[2], 2 * frame, variants["cmp"])
+        report(f"k_ssim_{name}", f"k_ssim {name}", t[3], 2 * frame, variants["ssim"])
+        res[f"ratio_to_k_codelight_{name}"] = round(med[name] / m_cl, 3)
+        print(f"k_deltae / k_codelight {name}: {med[name]/m_cl:5.3f} (four times the table transfers, twice the bytes)", flush=True)
+        del a, b
+        torch.cuda.empty_cache()
+    share = 1.0 - med["444_10"] / med["420_10"]
+    res["k_up444_share"] = round(share, 3)
+    print(f"k_up444 share of the 4:2:0 time: {share*100:4.1f} %", flush=True)
+
+    # 2. the compare-only ring from host memory, 10-bit 4:2:0, unarmed and armed for Delta E
+    d = h.make_codelight_desc(w, hh, 1, 10, 0, h.MATRIX_BT2020NC, 1)
+    host = noise(1).cpu().numpy().view(np.uint16)
+    parts = [host[:n], host[n:n + n // 4], host[n + n // 4:]]
+    ref = np.clip(host.astype(np.int32) + 1, 0, 1023).astype(np.uint16)
+
+    def ring(armed):
+        ctx.compare_stream_open(w, hh, h.CHROMA_420, 0, depth)
+        if armed:
+            ctx.stream_deltae(d, 1.0)
+        inflight = 0
+        t0 = time.perf_counter()
+
+        def take():
+            ctx.stream_output()
+            ctx.stream_compare_result()
+            if armed:
+                ctx.stream_deltae_result()
+
+        for _ in range(nf):
+            slot = ctx.stream_input()
+            for c in range(3):
+                slot[c][:] = parts[c]
+            ctx.stream_reference()[:] = ref
+            ctx.stream_submit()
+            inflight += 1
+            if inflight == depth - 1:
+                take()
+                inflight -= 1
+        while inflight:
+            take()
+            inflight -= 1
+        dt = (time.perf_counter() - t0) / nf
+        ctx.stream_close()
+        return dt
+
+    ring(False)  # warm-up
+    ts = [(ring(False), ring(True)) for _ in range(3)]
+    t_plain, t_armed = float(np.median([x[0] for x in ts])), float(np.median([x[1] for x in ts]))
+    res["compare_only_ring"] = dict(unarmed_fps=round(1 / t_plain, 1), armed_fps=round(1 / t_armed, 1), unarmed_ms=round(t_plain * 1e3, 2),
+                                    armed_ms=round(t_armed * 1e3, 2))
+    print(f"compare-only ring from host memory, 10-bit 4:2:0: unarmed {1/t_plain:6.1f} frames/s   armed for Delta E {1/t_armed:6.1f} frames/s",
+          flush=True)
+    ctx.close()
+    print(json.dumps({"streambench_deltae": res}), flush=True)
+
+
 def linearize_main():
     import json
 
@@ -1741,5 +1858,7 @@ if __name__ == "__main__":
         codelight_main()
     elif sys.argv[1:] == ["linearize"]:
         linearize_main()
+    elif sys.argv[1:] == ["deltae"]:
+        deltae_main()
     else:
         main()
