@@ -39,6 +39,8 @@ EXPORTS = [
     "h2y_light_batch", "h2y_stream_light", "h2y_stream_light_result",
     "h2y_lightdist_batch", "h2y_stream_lightdist", "h2y_stream_lightdist_result", "h2y_lightdist_json",
     "h2y_codelight_batch", "h2y_codelight_stream_open",
+    "h2y_scenesig_batch", "h2y_codescenesig_batch", "h2y_stream_scenesig", "h2y_stream_scenesig_result", "h2y_stream_lightdist_bins",
+    "h2y_scene_distance", "h2y_scene_cuts", "h2y_scene_merge", "h2y_lightdist_json_scenes",
     "h2y_linearize_batch", "h2y_pqcode_stream_open",
     "h2y_deltae_batch", "h2y_stream_deltae", "h2y_stream_deltae_result",
     "h2y_scale_taps", "h2y_scale_frame_bytes", "h2y_scale_batch", "h2y_stream_scale", "h2y_scale_stream_open",
@@ -56,6 +58,8 @@ LIGHTDIST_FRAMES_PER_LAUNCH = 64
 LIGHTDIST_BINS = 8706  # bins of max(L_G, L_B, L_R) by its binary32 bits: below 2^-17, 512 per binade up to 1, and 1 itself
 LIGHTDIST_FIRST_BITS = 0x37000000  # 2^-17: the lower edge of bin 1
 LIGHTDIST_PCT = (100, 500, 1000, 2500, 5000, 7500, 9000, 9500, 9900, 9998)  # the percentiles, in hundredths of a percent
+SCENESIG_COLS, SCENESIG_ROWS = 16, 9  # the scene signature's grid of cells
+SCENESIG_FRAMES_PER_LAUNCH = 64
 CODELIGHT_FRAMES_PER_LAUNCH = 8  # a launch's 4:2:0 scratch stays at 253 MiB for 3840 x 2160
 LINEARIZE_FRAMES_PER_LAUNCH = 8  # the same rule, the same scratch
 DELTAE_FRAMES_PER_LAUNCH = 4  # the same scratch again: four upsampled chroma planes a pair
@@ -226,6 +230,36 @@ class H2YLightdistStats(C.Structure):
 
     def __repr__(self):
         return f"H2YLightdistStats({self.as_dict()})"
+
+
+class H2YScenesig(C.Structure):
+    """h2y_scenesig: a frame's scene signature -- per cell of the 16 x 9 grid (row-major, cy * 16 + cx) the sum over its pixels of
+    the logarithmic bin of m = max(L_G, L_B, L_R), and the pixel count."""
+
+    _fields_ = [("cell", C.c_uint64 * (SCENESIG_COLS * SCENESIG_ROWS)), ("pixels", C.c_uint64)]
+
+    def as_dict(self):
+        return dict(cell=list(self.cell), pixels=self.pixels)
+
+    def __repr__(self):
+        return f"H2YScenesig({self.as_dict()})"
+
+
+class H2YSceneStats(C.Structure):
+    """h2y_scene_stats: a scene's figures -- its first frame and frame count, the maxima over its frames, the 128-bit sum of their
+    sum_q, the sums of their pixels and below_100, and the percentiles of their summed bins."""
+
+    _fields_ = [("first_frame", C.c_int64), ("n_frames", C.c_int64), ("maxscl_bits", C.c_uint32 * 3), ("max_bits", C.c_uint32),
+                ("sum_q_hi", C.c_uint64), ("sum_q_lo", C.c_uint64), ("pixels", C.c_uint64), ("below_100", C.c_uint64),
+                ("pct_bits", C.c_uint32 * len(LIGHTDIST_PCT))]
+
+    def as_dict(self):
+        return dict(first_frame=self.first_frame, n_frames=self.n_frames, maxscl_bits=list(self.maxscl_bits), max_bits=self.max_bits,
+                    sum_q=(self.sum_q_hi << 64) | self.sum_q_lo, pixels=self.pixels, below_100=self.below_100,
+                    pct_bits=list(self.pct_bits))
+
+    def __repr__(self):
+        return f"H2YSceneStats({self.as_dict()})"
 
 
 class H2YDeltaeStats(C.Structure):
@@ -473,6 +507,24 @@ def load_library():
     L.h2y_stream_deltae_result.restype = C.c_int
     L.h2y_lightdist_json.argtypes = [C.POINTER(H2YLightdistStats), C.c_int, C.c_long, C.c_char_p, C.c_size_t]
     L.h2y_lightdist_json.restype = C.c_size_t
+    L.h2y_scenesig_batch.argtypes = [C.c_void_p, C.POINTER(H2YDesc), C.c_int, C.POINTER(C.c_void_p), C.POINTER(H2YScenesig)]
+    L.h2y_scenesig_batch.restype = C.c_int
+    L.h2y_codescenesig_batch.argtypes = [C.c_void_p, C.POINTER(H2YCodelightDesc), C.c_int, C.POINTER(C.c_void_p), C.POINTER(H2YScenesig)]
+    L.h2y_codescenesig_batch.restype = C.c_int
+    L.h2y_stream_scenesig.argtypes = [C.c_void_p]
+    L.h2y_stream_scenesig.restype = C.c_int
+    L.h2y_stream_scenesig_result.argtypes = [C.c_void_p, C.POINTER(H2YScenesig)]
+    L.h2y_stream_scenesig_result.restype = C.c_int
+    L.h2y_stream_lightdist_bins.argtypes = [C.c_void_p, C.c_void_p]
+    L.h2y_stream_lightdist_bins.restype = C.c_int
+    L.h2y_scene_distance.argtypes = [C.POINTER(H2YScenesig), C.POINTER(H2YScenesig)]
+    L.h2y_scene_distance.restype = C.c_double
+    L.h2y_scene_cuts.argtypes = [C.POINTER(H2YScenesig), C.c_int, C.c_double, C.POINTER(C.c_int32)]
+    L.h2y_scene_cuts.restype = C.c_int
+    L.h2y_scene_merge.argtypes = [C.POINTER(H2YLightdistStats), C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.POINTER(H2YSceneStats), C.c_int]
+    L.h2y_scene_merge.restype = C.c_int
+    L.h2y_lightdist_json_scenes.argtypes = [C.POINTER(H2YSceneStats), C.c_int, C.c_long, C.c_char_p, C.c_size_t]
+    L.h2y_lightdist_json_scenes.restype = C.c_size_t
     L.h2y_scale_taps.argtypes = [C.c_int] * 3 + [C.c_void_p] * 3 + [C.POINTER(C.c_int)]
     L.h2y_scale_taps.restype = C.c_int
     L.h2y_scale_frame_bytes.argtypes = [C.c_int] * 3
@@ -642,6 +694,56 @@ def lightdist_json(stats, first_frame_index: int = 0) -> str:
         raise H2YError(H2Y_EINVAL, "h2y_lightdist_json: no frames, a negative first frame index or a frame without pixels")
     buf = C.create_string_buffer(need + 1)
     lib.h2y_lightdist_json(arr, n, first_frame_index, buf, need + 1)
+    return buf.value.decode()
+
+
+def scene_distance(a: H2YScenesig, b: H2YScenesig) -> float:
+    """h2y_scene_distance (host only): the mean absolute change of the cells' mean log light between two signatures, in stops; -1
+    for zero or differing pixel counts."""
+    return load_library().h2y_scene_distance(C.byref(a), C.byref(b))
+
+
+def scene_cuts(sigs, threshold: float):
+    """h2y_scene_cuts (host only): the scene id of every frame from the frames' signatures -- a list of ints, frame 0 in scene 0."""
+    n = len(sigs)
+    arr = (H2YScenesig * max(n, 1))(*sigs)
+    ids = (C.c_int32 * max(n, 1))()
+    scenes = load_library().h2y_scene_cuts(arr, n, threshold, ids)
+    if not scenes:
+        raise H2YError(H2Y_EINVAL, "h2y_scene_cuts: no frames, or a threshold that is negative or not finite")
+    return list(ids[:n])
+
+
+def scene_merge(stats, bins, scene_id):
+    """h2y_scene_merge (host only): a list of H2YSceneStats, the figures of the scenes of the frames of stats (H2YLightdistStats)
+    with their bins (uint32, (n, LIGHTDIST_BINS)) and scene ids."""
+    lib = load_library()
+    n = len(stats)
+    arr = (H2YLightdistStats * max(n, 1))(*stats)
+    b = np.ascontiguousarray(bins, dtype=np.uint32)
+    ids = (C.c_int32 * max(n, 1))(*scene_id)
+    if len(scene_id) != n or b.size != n * LIGHTDIST_BINS:
+        raise ValueError("stats, bins and scene_id differ in length")
+    scenes = lib.h2y_scene_merge(arr, b.ctypes.data, ids, n, None, 0)
+    if not scenes:
+        raise H2YError(H2Y_EINVAL, "h2y_scene_merge: no frames, a frame without pixels, or scene ids that do not run 0, 0.., 1, ..")
+    out = (H2YSceneStats * scenes)()
+    lib.h2y_scene_merge(arr, b.ctypes.data, ids, n, out, scenes)
+    return list(out)
+
+
+def lightdist_json_scenes(scenes, first_frame_index: int = 0) -> str:
+    """h2y_lightdist_json_scenes (host only): the HDR10+ JSON of the frames of scenes (H2YSceneStats), every frame carrying its
+    scene's figures."""
+    lib = load_library()
+    n = len(scenes)
+    arr = (H2YSceneStats * max(n, 1))(*scenes)
+    need = lib.h2y_lightdist_json_scenes(arr, n, first_frame_index, None, 0)
+    if not need:
+        raise H2YError(H2Y_EINVAL, "h2y_lightdist_json_scenes: no scenes, a negative first frame index, a scene without pixels or frames, "
+                                   "or scenes that do not tile the frames in order")
+    buf = C.create_string_buffer(need + 1)
+    lib.h2y_lightdist_json_scenes(arr, n, first_frame_index, buf, need + 1)
     return buf.value.decode()
 
 
@@ -961,6 +1063,25 @@ class Context:
             return list(out[:n])
         return list(out[:n]), (list(dout[:n]) if dist else None), (b[:n] if bins else None)
 
+    def scenesig_batch(self, d: H2YDesc, frames_in):
+        """k_scenesig on device frames (as lightdist_batch takes them): a list of H2YScenesig, one per frame."""
+        n = len(frames_in)
+        ins = (C.c_void_p * max(3 * n, 1))()
+        for f in range(n):
+            for c in range(3):
+                ins[3 * f + c] = self._ptr(frames_in[f][c])
+        out = (H2YScenesig * max(n, 1))()
+        self._check(self.lib.h2y_scenesig_batch(self.h, C.byref(d), n, ins, out))
+        return list(out[:n])
+
+    def codescenesig_batch(self, d: H2YCodelightDesc, frames):
+        """k_codescenesig on device frames of PQ codes (as codelight_batch takes them): a list of H2YScenesig, one per frame."""
+        n = len(frames)
+        pf = (C.c_void_p * max(n, 1))(*[self._ptr(x) for x in frames])
+        out = (H2YScenesig * max(n, 1))()
+        self._check(self.lib.h2y_codescenesig_batch(self.h, C.byref(d), n, pf, out))
+        return list(out[:n])
+
     def codelight_stream_open(self, d: H2YCodelightDesc, want_dist=0, depth=3) -> None:
         """A ring that only measures light: stream_input lends the frame's three planes, stream_output returns None,
         stream_light_result (and with want_dist stream_lightdist_result) the frame's figures."""
@@ -1143,6 +1264,22 @@ class Context:
     def stream_lightdist(self) -> None:
         """Arm an open forward ring to measure every frame's light distribution (h2y_stream_lightdist)."""
         self._check(self.lib.h2y_stream_lightdist(self.h))
+
+    def stream_scenesig(self) -> None:
+        """Arm an open forward ring or light-only ring to measure every frame's scene signature (h2y_stream_scenesig)."""
+        self._check(self.lib.h2y_stream_scenesig(self.h))
+
+    def stream_scenesig_result(self) -> H2YScenesig:
+        """The scene signature of the frame stream_output() returned last."""
+        st = H2YScenesig()
+        self._check(self.lib.h2y_stream_scenesig_result(self.h, C.byref(st)))
+        return st
+
+    def stream_lightdist_bins(self) -> np.ndarray:
+        """The LIGHTDIST_BINS bins (uint32) of the frame stream_output() returned last, on a ring that measures the distribution."""
+        b = np.zeros(LIGHTDIST_BINS, dtype=np.uint32)
+        self._check(self.lib.h2y_stream_lightdist_bins(self.h, b.ctypes.data))
+        return b
 
     def stream_lightdist_result(self) -> H2YLightdistStats:
         """The light distribution of the frame stream_output returned last."""

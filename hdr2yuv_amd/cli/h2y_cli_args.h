@@ -55,6 +55,19 @@
  *             printed per frame and written to FILE as the JSON x265 takes as --dhdr10-info (all frames in one scene).  Accepted
  *             wherever --content_light 1 is, beside it, for any --gpus; refused (exit 1, also under --dry_run) wherever that flag
  *             is, and for a FILE that cannot be created.
+ * --scene_detect 1 [--scene_threshold T] | --scene_cuts FILE, [--scene_qpfile OUT] (additions): HDR10+ metadata is scene-based, and with
+ *             one of the two scene flags the JSON of --dynamic_metadata FILE is: every frame's entry carries its scene's figures,
+ *             merged exactly from the frames' figures and bins (include/hdr2yuv_hip.h, "scene signature and scene cuts", states every
+ *             step).  --scene_detect 1 measures a 16 x 9 grid signature of every frame's light on the device and opens a scene where
+ *             the distance between two frames' signatures exceeds T stops (0.5 by default: a choice, not tuned on real programmes;
+ *             every distance is printed); --scene_cuts FILE names the scenes' first frames instead (decimal indices relative to the
+ *             run's first frame, one a line, strictly ascending, 0 optional, '#' comments and blank lines ignored) and runs no
+ *             signature kernel.  --scene_qpfile OUT writes one line "<frame> I" per scene start, the form x265's --qpfile is
+ *             documented to take.  Accepted wherever --dynamic_metadata FILE is (the forward flow and --light_only 1), and only
+ *             beside it, for any --gpus.  Refused (exit 1, also under --dry_run): a --scene_detect value other than 0 or 1, either
+ *             scene flag without --dynamic_metadata, both together, --scene_threshold without --scene_detect 1 or negative or not
+ *             finite, --scene_qpfile without a scene flag, a cuts file that is unreadable, malformed, not ascending or names a frame
+ *             >= --n_frames, and an OUT that cannot be created.  Without the flags not a line or byte changes.
  * --scale 1 [--scale_taps 2|3|4] (an addition; the reference parses --dst_pic_width / --dst_pic_height for a Lanczos cv::resize in
  *             cv.cpp, which is compiled out and does not compile): with it a destination size that differs from the source's is
  *             legal on the forward flow to .yuv, and every converted frame is resampled on the device by the exact Lanczos
@@ -190,6 +203,14 @@ struct cli_args {
     bool light_given = false;
     /* --dynamic_metadata FILE: the HDR10+ JSON of the forward flow */
     const char *dynmeta = nullptr;
+    /* scenes of the dynamic metadata: --scene_detect 1 [--scene_threshold T] or --scene_cuts FILE, and --scene_qpfile OUT; resolved by
+     * cli_resolve_scenes: scene_firsts, the first frames --scene_cuts names (0 among them) */
+    int scene_detect = 0;
+    bool scene_detect_given = false, scene_threshold_given = false;
+    double scene_threshold = 0.5;
+    const char *scene_cuts = nullptr, *scene_qpfile = nullptr;
+    std::vector<long> scene_firsts;
+    bool scenes() const { return scene_detect == 1 || scene_cuts; }
     /* --gamut_convert 1: the source planes go from the source's to the destination's primaries; --gamut_clip (1 by default) */
     int gamut = 0, gamut_clip = 1;
     bool gamut_given = false, gamut_clip_given = false;
@@ -289,6 +310,10 @@ static inline void cli_help()
            "  --dst_filename nothing is written)\n"
            "  dynamic metadata: [--dynamic_metadata FILE] (HDR10+, SMPTE ST 2094-40: per frame maxSCL, the average and percentiles of\n"
            "  max(R,G,B) of a conversion to PQ, written to FILE as the JSON of x265 --dhdr10-info)\n"
+           "  scenes: beside --dynamic_metadata, [--scene_detect 1 [--scene_threshold T]] (scene cuts from a 16x9 signature of every frame's\n"
+           "  light, measured on the GPU: a cut where the mean change of the cells' log light exceeds T stops, 0.5 by default; FILE then\n"
+           "  carries per-scene figures) or [--scene_cuts FILE] (the scenes' first frames, one a line), [--scene_qpfile OUT] (one line\n"
+           "  \"<frame> I\" per scene start, for x265 --qpfile)\n"
            "  light of a PQ master: [--light_only 1] (--src_filename, a PQ .yuv -- 4:2:0 or 4:4:4, --src_matrix_coeffs 1 or 9 -- or .rgb,\n"
            "  --src_transfer_characteristics 16: MaxCLL / MaxFALL from its codes, no conversion; with --dynamic_metadata FILE the HDR10+\n"
            "  JSON too; --src_chroma_sample_loc_type 2 for top-left sited 4:2:0 chroma)\n"
@@ -340,6 +365,10 @@ static inline void cli_parse(cli_args &a, int argc, char **argv)
         else if (is("--light_only")) { a.light_only = atoi(val()); a.light_only_given = true; }
         else if (is("--linearize")) { a.linearize = atoi(val()); a.linearize_given = true; }
         else if (is("--dynamic_metadata")) a.dynmeta = val();
+        else if (is("--scene_detect")) { a.scene_detect = atoi(val()); a.scene_detect_given = true; }
+        else if (is("--scene_threshold")) { a.scene_threshold = strtod(val(), nullptr); a.scene_threshold_given = true; }
+        else if (is("--scene_cuts")) a.scene_cuts = val();
+        else if (is("--scene_qpfile")) a.scene_qpfile = val();
         else if (is("--gamut_convert")) { a.gamut = atoi(val()); a.gamut_given = true; }
         else if (is("--gamut_clip")) { a.gamut_clip = atoi(val()); a.gamut_clip_given = true; }
         else if (is("--tone_map")) { a.tone_map = atoi(val()); a.tone_map_given = true; }
@@ -529,6 +558,7 @@ static inline int cli_resolve_tone_map(cli_args &a, int src_matrix_arg);
 static inline int cli_resolve_siting(cli_args &a);
 static inline int cli_resolve_src_siting(cli_args &a);
 static inline int cli_resolve_light_only(cli_args &a);
+static inline int cli_resolve_scenes(cli_args &a);
 static inline int cli_resolve_linearize(cli_args &a);
 static inline int cli_resolve_delta_e(cli_args &a);
 static inline int cli_resolve(cli_args &a)
@@ -548,7 +578,8 @@ static inline int cli_resolve(cli_args &a)
             return 1;
         }
         if (a.light_only) {
-            const int arg_errors = cli_resolve_light_only(a);
+            int arg_errors = cli_resolve_light_only(a);
+            if (a.scene_detect_given || a.scene_threshold_given || a.scene_cuts || a.scene_qpfile) arg_errors += cli_resolve_scenes(a);
             return arg_errors + (a.delta_e_given || a.delta_e_threshold_given || a.delta_e_limit_given ? cli_resolve_delta_e(a) : 0);
         }
     }
@@ -561,6 +592,7 @@ static inline int cli_resolve(cli_args &a)
     if (a.ssim_given) arg_errors += cli_resolve_ssim(a);
     if (a.light_given) arg_errors += cli_resolve_light(a);
     if (a.dynmeta) arg_errors += cli_resolve_dynmeta(a);
+    if (a.scene_detect_given || a.scene_threshold_given || a.scene_cuts || a.scene_qpfile) arg_errors += cli_resolve_scenes(a);
     if (a.scale_given || a.scale_only || a.scale_taps_given) arg_errors += cli_resolve_scale(a);
     if (a.gamut_given || a.gamut_clip_given) arg_errors += cli_resolve_gamut(a, src_matrix_arg);
     if (a.tone_map_given || a.tone_src_peak_given || a.tone_dst_peak_given) arg_errors += cli_resolve_tone_map(a, src_matrix_arg);
@@ -939,6 +971,82 @@ static inline int cli_resolve_dynmeta(cli_args &a)
            a.linearize == 1 ? "0 and 1 (--linearize 1)" : a.tone_map == 1 ? "0 and 1 (--tone_map 1)" : "of each frame's pic_stats",
            H2Y_LIGHTDIST_BINS);
     return 0;
+}
+
+/* The first frames a --scene_cuts FILE names into `firsts`, 0 put in front where the file leaves it out: decimal indices one a line,
+ * strictly ascending, below n_frames; '#' comments and blank lines ignored.  Returns "" or what is wrong with the file. */
+static inline std::string cli_read_scene_cuts(const char *path, long n_frames, std::vector<long> &firsts)
+{
+    FILE *f = fopen(path, "r");
+    if (!f) return "cannot be read";
+    firsts.assign(1, 0);
+    std::string err;
+    char line[256];
+    long prev = -1;
+    for (long no = 1; err.empty() && fgets(line, sizeof line, f); no++) {
+        char *p = line;
+        while (*p == ' ' || *p == '\t') p++;
+        if (*p == '#' || *p == '\n' || *p == '\r' || !*p) continue;
+        char *end = nullptr;
+        const long v = (*p >= '0' && *p <= '9') ? strtol(p, &end, 10) : -1;
+        while (end && (*end == ' ' || *end == '\t' || *end == '\r' || *end == '\n')) end++;
+        if (v < 0 || !end || *end) err = "line " + std::to_string(no) + " is not a decimal frame index";
+        else if (v <= prev) err = "line " + std::to_string(no) + " is not above the line before it";
+        else if (v >= n_frames) err = "line " + std::to_string(no) + " names frame " + std::to_string(v) + ", the run has --n_frames " + std::to_string(n_frames);
+        else if (v > 0) firsts.push_back(v);
+        prev = v;
+    }
+    fclose(f);
+    return err;
+}
+
+/* --scene_detect / --scene_threshold / --scene_cuts / --scene_qpfile: beside a --dynamic_metadata FILE that resolved; returns the
+ * number of argument errors */
+static inline int cli_resolve_scenes(cli_args &a)
+{
+    int arg_errors = 0;
+    if (a.scene_detect_given) printf("scene_detect: %d\n", a.scene_detect);
+    if (a.scene_detect != 0 && a.scene_detect != 1) {
+        printf("WARNING: scene_detect(%d) not 0 or 1\n", a.scene_detect);
+        return 1;
+    }
+    if (a.scene_detect == 1 && a.scene_cuts) {
+        printf("WARNING: --scene_detect 1 finds the cuts, --scene_cuts FILE gives them: not both\n");
+        return 1;
+    }
+    if (a.scenes() && !a.dynmeta) {
+        printf("WARNING: %s makes the scenes of --dynamic_metadata FILE: it needs that flag\n", a.scene_cuts ? "--scene_cuts FILE" : "--scene_detect 1");
+        return 1;
+    }
+    if (a.scene_threshold_given && a.scene_detect != 1) {
+        printf("WARNING: --scene_threshold needs --scene_detect 1\n");
+        arg_errors++;
+    } else if (a.scene_detect == 1) {
+        printf("scene_threshold: %.4f%s\nscene_grid: %dx%d\n", a.scene_threshold, a.scene_threshold_given ? "" : " (default)",
+               H2Y_SCENESIG_COLS, H2Y_SCENESIG_ROWS);
+        if (!(a.scene_threshold >= 0.0) || !std::isfinite(a.scene_threshold)) {
+            printf("WARNING: scene_threshold(%g) is negative or not finite\n", a.scene_threshold);
+            arg_errors++;
+        }
+    }
+    if (a.scene_cuts) {
+        const std::string err = cli_read_scene_cuts(a.scene_cuts, a.n_frames > 0 ? a.n_frames : 1, a.scene_firsts);
+        if (!err.empty()) {
+            printf("WARNING: --scene_cuts: file (%s) %s\n", a.scene_cuts, err.c_str());
+            arg_errors++;
+        } else printf("scene_cuts: %s %zu scenes\n", a.scene_cuts, a.scene_firsts.size());
+    }
+    if (a.scene_qpfile) {
+        printf("scene_qpfile: %s\n", a.scene_qpfile);
+        if (!a.scenes()) {
+            printf("WARNING: --scene_qpfile OUT lists the scene starts: it needs --scene_detect 1 or --scene_cuts FILE\n");
+            arg_errors++;
+        } else if (!cli_can_create(a.scene_qpfile)) {
+            printf("WARNING: --scene_qpfile: file (%s) cannot be created\n", a.scene_qpfile);
+            arg_errors++;
+        }
+    }
+    return arg_errors;
 }
 
 /* --gamut_convert / --gamut_clip: the forward flow's float or half G,B,R planes in linear light, between two sets of primaries the

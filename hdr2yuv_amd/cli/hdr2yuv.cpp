@@ -91,6 +91,15 @@
  * edges of their bins), the percentiles 1, 5, 10, 25, 50, 75, 90, 95, 99 and 99.98 %, the share in percent:
  *   dynamic_metadata: frame <k> maxscl <R> <G> <B> average <A> percentiles <p1> ... <p99.98> below_100 <share>
  *   dynamic_metadata_written: <N> frames to FILE
+ * Scenes (--scene_detect 1 [--scene_threshold T] or --scene_cuts FILE, [--scene_qpfile OUT], beside --dynamic_metadata; h2y_cli_args.h):
+ * each GPU thread also arms its ring with h2y_stream_scenesig (the detected case) and keeps frame k's signature and its bins
+ * (h2y_stream_lightdist_bins: 34 KB a frame of host memory) by its index; after every thread is done the cuts are decided
+ * (h2y_scene_cuts) or taken from FILE, the scenes merged (h2y_scene_merge) and FILE written by h2y_lightdist_json_scenes, the same for
+ * any --gpus.  Between the dynamic_metadata: frame lines and dynamic_metadata_written:
+ *   scene: frame <k> distance <D>[ cut]                      (the detected case, k from 1)
+ *   scene: <s> first <f> frames <n> maxscl <R> <G> <B> average <A> percentiles <p1> ... <p99.98> below_100 <share>
+ *   scene: summary scenes <S> frames <N>
+ *   scene_qpfile_written: <S> scenes to OUT                  (--scene_qpfile: one line "<frame> I" per scene start)
  *
  * Light of a PQ master (--light_only 1 [--dynamic_metadata FILE]; h2y_cli_args.h): each GPU thread sets its context's inverse chroma
  * siting where --src_chroma_sample_loc_type 2 says so and opens a light-only ring (h2y_codelight_stream_open) on the source's code
@@ -186,6 +195,8 @@ struct results {
     std::vector<h2y_deltae_stats> deltae;
     std::vector<h2y_light_stats> light;
     std::vector<h2y_lightdist_stats> lightdist;
+    std::vector<h2y_scenesig> scenesig; /* --scene_detect 1: frame k's signature */
+    std::vector<uint32_t> dist_bins;    /* a scene flag: frame k's H2Y_LIGHTDIST_BINS bins, for the scenes' percentiles */
     std::vector<h2y_histogram_stats> hist;
     std::vector<std::array<uint32_t, 3>> occupied; /* the non-zero bins of frame k's planes */
     std::vector<uint32_t> bins;                    /* per GPU thread: one frame's 3 x nbins */
@@ -193,7 +204,8 @@ struct results {
     size_t nbins = 0;
     results(const cli_args &a, long frames)
         : compare(a.ref ? (size_t)frames : 0), ssim(a.ssim ? (size_t)frames : 0), deltae(a.delta_e ? (size_t)frames : 0), light(a.light ? (size_t)frames : 0),
-          lightdist(a.dynmeta ? (size_t)frames : 0), hist(a.hist ? (size_t)frames : 0), occupied(hist.size())
+          lightdist(a.dynmeta ? (size_t)frames : 0), scenesig(a.scene_detect == 1 ? (size_t)frames : 0),
+          dist_bins(a.scenes() ? (size_t)frames * H2Y_LIGHTDIST_BINS : 0), hist(a.hist ? (size_t)frames : 0), occupied(hist.size())
     {
         if (!a.hist) return;
         nbins = (size_t)1 << a.hist_bits;
@@ -222,6 +234,8 @@ struct results {
         }
         if (a.light && h2y_stream_light_result(ctx, &light[k])) return false;
         if (a.dynmeta && h2y_stream_lightdist_result(ctx, &lightdist[k])) return false;
+        if (a.scene_detect == 1 && h2y_stream_scenesig_result(ctx, &scenesig[k])) return false;
+        if (a.scenes() && h2y_stream_lightdist_bins(ctx, &dist_bins[(size_t)k * H2Y_LIGHTDIST_BINS])) return false;
         return true;
     }
     /* the bins of every thread, summed (the same totals for any split) */
@@ -378,7 +392,7 @@ static flow forward_flow(const job &j)
         return (a.ref && h2y_stream_compare(ctx, a.sigma, a.dst ? 1 : 0)) || (a.ssim && h2y_stream_ssim(ctx, -1)) ||
                (a.delta_e && h2y_stream_deltae(ctx, &a.de, a.delta_e_threshold)) ||
                (a.hist && h2y_stream_histogram(ctx, a.hist_bits)) || (a.light && h2y_stream_light(ctx)) ||
-               (a.dynmeta && h2y_stream_lightdist(ctx)) ||
+               (a.dynmeta && h2y_stream_lightdist(ctx)) || (a.scene_detect == 1 && h2y_stream_scenesig(ctx)) ||
                (a.gamut && h2y_stream_gamut(ctx, a.in.colour_primaries, a.out.colour_primaries, a.gamut_clip)) ||
                (a.tone_map && h2y_stream_tonemap(ctx, a.tone_src_peak, a.tone_dst_peak, a.tone_relative)) ||
                (a.scale && h2y_stream_scale(ctx, a.out.width, a.out.height, a.scale_taps));
@@ -547,6 +561,7 @@ static flow light_flow(const job &j)
                                    a.in.matrix_coeffs, a.resampler};
         return h2y_codelight_stream_open(ctx, &d, a.dynmeta ? 1 : 0, kRingDepth);
     };
+    if (a.scene_detect == 1) f.arm = [](h2y_ctx *ctx) { return h2y_stream_scenesig(ctx); };
     return f;
 }
 
@@ -742,9 +757,82 @@ static void light_report(const std::vector<h2y_light_stats> &st)
     printf("light svt-av1 --content-light %lld,%lld\n", cll, fall);
 }
 
-/* the dynamic metadata report of the header comment, and FILE; 0, or 1 when FILE could not be written */
-static int lightdist_report(const cli_args &a, const std::vector<h2y_lightdist_stats> &st)
+/* `text` into the file `path`; false when it could not be written */
+static bool write_text(const char *path, const std::string &text)
 {
+    FILE *f = fopen(path, "w");
+    bool ok = f && fwrite(text.data(), 1, text.size(), f) == text.size();
+    if (f && fclose(f)) ok = false;
+    return ok;
+}
+
+/* The scenes of the run's frames: detected from the signatures (with a line per distance) or as --scene_cuts names them; their
+ * figures merged from the frames' and printed; `text` becomes the scene-based JSON, and --scene_qpfile's OUT is written.  0, or 1 */
+static int scene_report(const cli_args &a, const results &res, std::string &text)
+{
+    const std::vector<h2y_lightdist_stats> &st = res.lightdist;
+    const int n = (int)st.size();
+    std::vector<int32_t> id((size_t)n, 0);
+    if (a.scene_detect == 1) {
+        if (!h2y_scene_cuts(res.scenesig.data(), n, a.scene_threshold, id.data())) {
+            printf("ERROR: the scene cuts could not be found\n");
+            return 1;
+        }
+        for (int k = 1; k < n; k++)
+            printf("scene: frame %d distance %.6f%s\n", k, h2y_scene_distance(&res.scenesig[k - 1], &res.scenesig[k]), id[k] != id[k - 1] ? " cut" : "");
+    } else {
+        if (a.scene_firsts.back() >= n) {
+            printf("ERROR: --scene_cuts names frame %ld, the run had %d frames\n", a.scene_firsts.back(), n);
+            return 1;
+        }
+        size_t s = 0;
+        for (int k = 0; k < n; k++) {
+            if (s + 1 < a.scene_firsts.size() && a.scene_firsts[s + 1] == k) s++;
+            id[k] = (int32_t)s;
+        }
+    }
+    std::vector<h2y_scene_stats> sc((size_t)id[n - 1] + 1);
+    if (h2y_scene_merge(st.data(), res.dist_bins.data(), id.data(), n, sc.data(), (int)sc.size()) != (int)sc.size()) {
+        printf("ERROR: the scenes' figures could not be merged\n");
+        return 1;
+    }
+    auto nits = [](uint32_t bits) {
+        float l;
+        memcpy(&l, &bits, sizeof l);
+        return 10000.0 * (double)l;
+    };
+    for (size_t s = 0; s < sc.size(); s++) {
+        const h2y_scene_stats &t = sc[s];
+        const unsigned __int128 q = ((unsigned __int128)t.sum_q_hi << 64) | t.sum_q_lo;
+        printf("scene: %zu first %lld frames %lld maxscl %.4f %.4f %.4f average %.4f percentiles", s, (long long)t.first_frame, (long long)t.n_frames,
+               nits(t.maxscl_bits[2]), nits(t.maxscl_bits[0]), nits(t.maxscl_bits[1]), ((10000.0 * (double)q) * 0x1p-32) / (double)t.pixels);
+        for (int i = 0; i < H2Y_LIGHTDIST_PERCENTILES; i++) printf(" %.4f", nits(t.pct_bits[i]));
+        printf(" below_100 %.4f\n", 100.0 * (double)t.below_100 / (double)t.pixels);
+    }
+    printf("scene: summary scenes %zu frames %d\n", sc.size(), n);
+    text.assign(h2y_lightdist_json_scenes(sc.data(), (int)sc.size(), 0, nullptr, 0), '\0');
+    if (!text.empty()) {
+        text.resize(text.size() + 1);
+        h2y_lightdist_json_scenes(sc.data(), (int)sc.size(), 0, &text[0], text.size());
+        text.pop_back();
+    }
+    if (a.scene_qpfile) {
+        std::string qp;
+        for (const h2y_scene_stats &t : sc) qp += std::to_string(t.first_frame) + " I\n";
+        if (!write_text(a.scene_qpfile, qp)) {
+            printf("ERROR: unable to write %s\n", a.scene_qpfile);
+            return 1;
+        }
+        printf("scene_qpfile_written: %zu scenes to %s\n", sc.size(), a.scene_qpfile);
+    }
+    return 0;
+}
+
+/* the dynamic metadata report of the header comment, and FILE (with a scene flag the scene report and the scene-based text); 0, or 1
+ * when a file could not be written */
+static int lightdist_report(const cli_args &a, const results &res)
+{
+    const std::vector<h2y_lightdist_stats> &st = res.lightdist;
     auto nits = [](uint32_t bits) {
         float l;
         memcpy(&l, &bits, sizeof l);
@@ -757,17 +845,18 @@ static int lightdist_report(const cli_args &a, const std::vector<h2y_lightdist_s
         for (int i = 0; i < H2Y_LIGHTDIST_PERCENTILES; i++) printf(" %.4f", nits(t.pct_bits[i]));
         printf(" below_100 %.4f\n", 100.0 * (double)t.below_100 / (double)t.pixels);
     }
-    std::string text(h2y_lightdist_json(st.data(), (int)st.size(), 0, nullptr, 0), '\0');
-    bool ok = !text.empty();
-    if (ok) {
-        text.resize(text.size() + 1);
-        h2y_lightdist_json(st.data(), (int)st.size(), 0, &text[0], text.size());
-        text.pop_back();
-        FILE *f = fopen(a.dynmeta, "w");
-        ok = f && fwrite(text.data(), 1, text.size(), f) == text.size();
-        if (f && fclose(f)) ok = false;
+    std::string text;
+    if (a.scenes()) {
+        if (st.empty() || scene_report(a, res, text)) return 1;
+    } else {
+        text.assign(h2y_lightdist_json(st.data(), (int)st.size(), 0, nullptr, 0), '\0');
+        if (!text.empty()) {
+            text.resize(text.size() + 1);
+            h2y_lightdist_json(st.data(), (int)st.size(), 0, &text[0], text.size());
+            text.pop_back();
+        }
     }
-    if (!ok) {
+    if (text.empty() || !write_text(a.dynmeta, text)) {
         printf("ERROR: unable to write %s\n", a.dynmeta);
         return 1;
     }
@@ -952,6 +1041,6 @@ int main(int argc, char **argv)
         if (!rc) rc = drc;
     }
     if (ran && a.light) light_report(res.light);
-    if (ran && a.dynmeta && lightdist_report(a, res.lightdist)) rc = 1;
+    if (ran && a.dynmeta && lightdist_report(a, res)) rc = 1;
     return rc;
 }

@@ -281,6 +281,7 @@ void h2y_ctx_destroy(h2y_ctx *ctx)
     (void)hipFree(ctx->d_lightdist);
     (void)hipFree(ctx->d_codelight);
     (void)hipFree(ctx->d_codelight_up);
+    (void)hipFree(ctx->d_scenesig);
     (void)hipFree(ctx->d_deltae);
     (void)hipFree(ctx->d_scale_tabs);
     (void)hipFree(ctx->d_tonemap_gain);

@@ -382,6 +382,20 @@ int h2y_codelight_grid(uint32_t npix, int n_frames); /* blocks per frame */
 hipError_t h2y_launch_codelight(int matrix, int grid, hipStream_t st, const codelight_args &a, const codelight_frame *frames, int n_frames,
                                 light_acc *acc, lightdist_acc *dacc, uint32_t *bins);
 
+/* k_scenesig and k_codescenesig (h2y_scenesig.hip): the scene signature (include/hdr2yuv_hip.h, h2y_scenesig) of the frames k_lightdist
+ * and k_codelight measure, with their frame tables and arguments */
+struct scenesig_geom {
+    uint32_t width, height;
+    uint32_t rows; /* rows of a block's band */
+};
+/* the geometry of a launch of n_frames frames read in groups of `group` pixels (4: k_scenesig, 8: k_codescenesig) */
+scenesig_geom h2y_scenesig_geom(uint32_t width, uint32_t height, uint32_t group, int n_frames);
+/* over n_frames frames into sig[frame x 144] (zeroed by the caller): cell cy x 16 + cx */
+hipError_t h2y_launch_scenesig(int in_kind, hipStream_t st, const light_args &a, const scenesig_geom &g, const light_frame *frames, int n_frames,
+                               unsigned long long *sig);
+hipError_t h2y_launch_codescenesig(int matrix, hipStream_t st, const codelight_args &a, const scenesig_geom &g, const codelight_frame *frames,
+                                   int n_frames, unsigned long long *sig);
+
 /* k_linearize (h2y_linearize.hip): the three lights of every pixel of such frames as binary32 planes G, B, R
  * (include/hdr2yuv_hip.h, "linearised PQ code planes"); k_codelight's arguments */
 struct linearize_frame { /* one frame: its code planes as codelight_frame has them, and the three output planes (16-byte aligned) */

@@ -903,6 +903,276 @@ int h2y_codelight_stream_open(h2y_ctx *ctx, const h2y_codelight_desc *d, int wan
     return rc;
 }
 
+/* ---- scene signature and scene cuts (h2y_scenesig_batch, h2y_codescenesig_batch, h2y_stream_scenesig, and the host-only merge and
+ * JSON): include/hdr2yuv_hip.h states the definition ---------------------------------------------------------------------------- */
+
+constexpr size_t kSigCells = H2Y_SCENESIG_COLS * H2Y_SCENESIG_ROWS, kSigBytes = kSigCells * sizeof(unsigned long long);
+
+/* n_frames frames' cells from the device into out, each with its pixel count */
+static int scenesig_finish(h2y_ctx *ctx, const unsigned long long *d_sig, int n_frames, uint32_t npix, h2y_scenesig *out)
+{
+    std::vector<unsigned long long> cells((size_t)n_frames * kSigCells);
+    HIP_TRY(ctx, hipMemcpy(cells.data(), d_sig, cells.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (int f = 0; f < n_frames; f++) {
+        for (size_t c = 0; c < kSigCells; c++) out[f].cell[c] = cells[(size_t)f * kSigCells + c];
+        out[f].pixels = npix;
+    }
+    return H2Y_OK;
+}
+
+int h2y_scenesig_batch(h2y_ctx *ctx, const h2y_desc *d, int n_frames, const void *const *d_planes, h2y_scenesig *out)
+{
+    light_args a;
+    light_frame *h;
+    int rc = light_batch_prepare(ctx, d, n_frames, d_planes, out, a, h);
+    if (!rc) rc = ensure(ctx, ctx->d_scenesig, ctx->scenesig_cap, (size_t)n_frames * kSigBytes);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_scenesig, 0, (size_t)n_frames * kSigBytes, ctx->stream));
+    const int in_kind = in_kind_of(d);
+    rc = timed_launches(ctx, h, n_frames, H2Y_SCENESIG_FRAMES_PER_LAUNCH, "k_scenesig", [&](const light_frame *frames, int f0, int nf) {
+        return h2y_launch_scenesig(in_kind, ctx->stream, a, h2y_scenesig_geom((uint32_t)d->width, (uint32_t)d->height, 4u, nf), frames, nf,
+                                   ctx->d_scenesig + (size_t)f0 * kSigCells);
+    });
+    if (!rc) rc = scenesig_finish(ctx, ctx->d_scenesig, n_frames, a.npix, out);
+    if (rc) return rc;
+    ctx->last_variant = "k_scenesig" + light_variant(d, a).substr(strlen("k_light"));
+    return H2Y_OK;
+}
+
+int h2y_codescenesig_batch(h2y_ctx *ctx, const h2y_codelight_desc *d, int n_frames, const uint16_t *const *d_frames, h2y_scenesig *out)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
+    codelight_plan p;
+    int rc = codelight_check(ctx, d, p);
+    if (rc) return rc;
+    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
+    if (!d_frames || !out) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
+    for (int f = 0; f < n_frames; f++) {
+        if (!d_frames[f]) return fail(ctx, H2Y_EINVAL, "frame %d is null", f);
+        if ((uintptr_t)d_frames[f] & 15u) return fail(ctx, H2Y_EINVAL, "frame %d is not 16-byte aligned", f);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int per_launch = std::min(n_frames, H2Y_CODELIGHT_FRAMES_PER_LAUNCH);
+    codelight_frame *h;
+    rc = codelight_tables(ctx, p);
+    if (!rc) rc = frame_table(ctx, n_frames, h);
+    if (!rc) rc = ensure(ctx, ctx->d_scenesig, ctx->scenesig_cap, (size_t)n_frames * kSigBytes);
+    if (!rc && p.sub) rc = ensure(ctx, ctx->d_codelight_up, ctx->codelight_up_cap, (size_t)per_launch * 2u * p.plane_al);
+    if (rc) return rc;
+    for (int f = 0; f < n_frames; f++) /* as h2y_codelight_batch: the upsampled chroma in the scratch of the frame's place in its launch */
+        h[f] = codelight_entry(p, d_frames[f], p.sub ? ctx->d_codelight_up + (size_t)(f % per_launch) * 2u * p.plane_al : nullptr);
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_scenesig, 0, (size_t)n_frames * kSigBytes, ctx->stream));
+    rc = timed_launches(ctx, h, n_frames, H2Y_CODELIGHT_FRAMES_PER_LAUNCH, "k_codescenesig", [&](const codelight_frame *frames, int f0, int nf) {
+        for (int f = 0; p.sub && f < nf; f++) {
+            const hipError_t e = codelight_upsample(ctx, p, d_frames[f0 + f], ctx->d_codelight_up + (size_t)f * 2u * p.plane_al);
+            if (e != hipSuccess) return e;
+        }
+        return h2y_launch_codescenesig(p.matrix, ctx->stream, p.a, h2y_scenesig_geom((uint32_t)p.width, (uint32_t)p.height, 8u, nf), frames, nf,
+                                       ctx->d_scenesig + (size_t)f0 * kSigCells);
+    });
+    if (!rc) rc = scenesig_finish(ctx, ctx->d_scenesig, n_frames, p.a.npix, out);
+    if (rc) return rc;
+    ctx->last_variant = std::string("k_codescenesig<") + (p.matrix == H2Y_MATRIX_GBR ? "GBR" : p.matrix == H2Y_MATRIX_BT709 ? "BT709" : "BT2020NC") + "," +
+                        (!p.sub ? "444" : p.form == UP_FIR_TL ? "FIR_TL" : p.form == UP_FIR ? "FIR" : "REPLICATE") + ">";
+    return H2Y_OK;
+}
+
+/* The signature's ring stage.  On a forward ring: k_scenesig on what the light distribution's stage sees, with k_light's arguments
+ * and table entry per slot.  On the light-only ring: k_codescenesig on the planes of the ring's codelight_stage, which ran before it
+ * (stage_id order) and left the slot's upsampled chroma where its table entry points.  Per slot the frame's cells on the device and
+ * pinned. */
+struct scenesig_stage : ring_stage {
+    struct slot {
+        unsigned long long *d = nullptr, *h = nullptr;
+    };
+    std::vector<slot> ss;
+    bool code = false;
+    uint32_t npix = 0;
+    scenesig_geom g{};
+    light_args a{};
+    light_frame *tab = nullptr;
+    int run(h2y_ctx *ctx, int k) override
+    {
+        HIP_TRY(ctx, hipMemsetAsync(ss[k].d, 0, kSigBytes, ctx->stream));
+        if (code) {
+            const codelight_stage *cl = stage_of<codelight_stage>(ctx, STAGE_CODELIGHT);
+            HIP_TRY(ctx, h2y_launch_codescenesig(cl->p.matrix, ctx->stream, cl->p.a, g, cl->tab + k, 1, ss[k].d));
+        } else HIP_TRY(ctx, h2y_launch_scenesig(in_kind_of(&ctx->s_desc), ctx->stream, a, g, tab + k, 1, ss[k].d));
+        return H2Y_OK;
+    }
+    int download(h2y_ctx *ctx, int k) override
+    {
+        HIP_TRY(ctx, hipMemcpyAsync(ss[k].h, ss[k].d, kSigBytes, hipMemcpyDeviceToHost, ctx->s_d2h));
+        return H2Y_OK;
+    }
+};
+
+int h2y_stream_scenesig(h2y_ctx *ctx)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    const codelight_stage *cl = stage_of<codelight_stage>(ctx, STAGE_CODELIGHT);
+    if (!cl && ctx->s_kind != h2y_ctx::RING_FORWARD)
+        return fail(ctx, H2Y_EINVAL, "the scene signature is measured on the forward rings and the light-only ring only");
+    if (ctx->s_stage[STAGE_SCENESIG]) return fail(ctx, H2Y_EINVAL, "the ring measures the scene signature already");
+    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    auto st = std::make_unique<scenesig_stage>();
+    const int depth = (int)ctx->ss.size();
+    std::vector<light_frame> tab(depth);
+    if (cl) {
+        st->code = true;
+        st->npix = cl->p.a.npix;
+        st->g = h2y_scenesig_geom((uint32_t)cl->p.width, (uint32_t)cl->p.height, 8u, 1);
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+    } else {
+        const h2y_desc *d = &ctx->s_desc;
+        int rc = light_check(ctx, d);
+        if (rc) return rc;
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        rc = light_args_of(ctx, d, st->a);
+        if (rc) return rc;
+        st->npix = st->a.npix;
+        st->g = h2y_scenesig_geom((uint32_t)d->width, (uint32_t)d->height, 4u, 1);
+        for (int k = 0; k < depth; k++) {
+            for (int c = 0; c < 3; c++) tab[k].in[c] = ctx->ss[k].d_in + c * ctx->s_plane_al;
+            tab[k].assumed = ctx->b->d_assumed;
+        }
+    }
+    st->ss.resize(depth);
+    for (int k = 0; k < depth; k++) {
+        st->dev_alloc(st->ss[k].d, kSigBytes);
+        st->pin_alloc(st->ss[k].h, kSigBytes);
+    }
+    if (!cl) st->table(st->tab, tab);
+    return stage_arm(ctx, STAGE_SCENESIG, std::move(st), "scene signature");
+}
+
+int h2y_stream_scenesig_result(h2y_ctx *ctx, h2y_scenesig *out)
+{
+    if (!ctx || !out) return fail(ctx, H2Y_EINVAL, "null argument");
+    const scenesig_stage *st = ctx->streaming ? stage_of<scenesig_stage>(ctx, STAGE_SCENESIG) : nullptr;
+    if (!st) return fail(ctx, H2Y_EINVAL, "no stream open that measures the scene signature");
+    if (ctx->s_lent < 0) return fail(ctx, H2Y_EINVAL, "no output taken yet: h2y_stream_output first");
+    for (size_t c = 0; c < kSigCells; c++) out->cell[c] = st->ss[ctx->s_lent].h[c];
+    out->pixels = st->npix;
+    return H2Y_OK;
+}
+
+int h2y_stream_lightdist_bins(h2y_ctx *ctx, uint32_t *bins)
+{
+    if (!ctx || !bins) return fail(ctx, H2Y_EINVAL, "null argument");
+    const codelight_stage *cl = ctx->streaming ? stage_of<codelight_stage>(ctx, STAGE_CODELIGHT) : nullptr;
+    const lightdist_stage *st = ctx->streaming ? stage_of<lightdist_stage>(ctx, STAGE_LIGHTDIST) : nullptr;
+    if (!(cl && cl->dist) && !st) return fail(ctx, H2Y_EINVAL, "no stream open that measures the light distribution");
+    if (ctx->s_lent < 0) return fail(ctx, H2Y_EINVAL, "no output taken yet: h2y_stream_output first");
+    const char *h = cl ? cl->ss[ctx->s_lent].h + codelight_dist_off(1) : st->ss[ctx->s_lent].h;
+    memcpy(bins, h + lightdist_layout_of(1).bins, H2Y_LIGHTDIST_BINS * sizeof(uint32_t));
+    return H2Y_OK;
+}
+
+double h2y_scene_distance(const h2y_scenesig *a, const h2y_scenesig *b)
+{
+    if (!a || !b || !a->pixels || a->pixels != b->pixels) return -1.0;
+    uint64_t s = 0;
+    for (size_t c = 0; c < kSigCells; c++) s += a->cell[c] > b->cell[c] ? a->cell[c] - b->cell[c] : b->cell[c] - a->cell[c];
+    return (double)s / (512.0 * (double)a->pixels);
+}
+
+int h2y_scene_cuts(const h2y_scenesig *sig, int n, double threshold, int32_t *scene_id)
+{
+    if (!sig || !scene_id || n < 1 || !(threshold >= 0.0) || !std::isfinite(threshold)) return 0;
+    int32_t s = 0;
+    scene_id[0] = 0;
+    for (int f = 1; f < n; f++) {
+        if (h2y_scene_distance(&sig[f - 1], &sig[f]) > threshold) s++;
+        scene_id[f] = s;
+    }
+    return s + 1;
+}
+
+int h2y_scene_merge(const h2y_lightdist_stats *stats, const uint32_t *bins, const int32_t *scene_id, int n_frames, h2y_scene_stats *out, int cap)
+{
+    static const uint32_t kPct[H2Y_LIGHTDIST_PERCENTILES] = H2Y_LIGHTDIST_PCT;
+    if (!stats || !bins || !scene_id || n_frames < 1 || cap < 0 || (cap > 0 && !out) || scene_id[0] != 0) return 0;
+    for (int f = 0; f < n_frames; f++)
+        if (!stats[f].pixels || (f > 0 && scene_id[f] != scene_id[f - 1] && scene_id[f] != scene_id[f - 1] + 1)) return 0;
+    std::vector<uint64_t> sum(H2Y_LIGHTDIST_BINS);
+    int scenes = 0;
+    for (int f0 = 0; f0 < n_frames; scenes++) {
+        int f1 = f0 + 1;
+        while (f1 < n_frames && scene_id[f1] == scene_id[f0]) f1++;
+        if (scenes < cap) {
+            h2y_scene_stats &o = out[scenes];
+            o = h2y_scene_stats{};
+            o.first_frame = f0, o.n_frames = f1 - f0;
+            unsigned __int128 q = 0;
+            std::fill(sum.begin(), sum.end(), 0u);
+            for (int f = f0; f < f1; f++) {
+                for (int c = 0; c < 3; c++) o.maxscl_bits[c] = std::max(o.maxscl_bits[c], stats[f].maxscl_bits[c]);
+                o.max_bits = std::max(o.max_bits, stats[f].max_bits);
+                q += stats[f].sum_q;
+                o.pixels += stats[f].pixels, o.below_100 += stats[f].below_100;
+                const uint32_t *b = bins + (size_t)f * H2Y_LIGHTDIST_BINS;
+                for (uint32_t k = 0; k < H2Y_LIGHTDIST_BINS; k++) sum[k] += b[k];
+            }
+            o.sum_q_hi = (uint64_t)(q >> 64), o.sum_q_lo = (uint64_t)q;
+            uint64_t cum = 0;
+            int i = 0;
+            for (uint32_t k = 0; k < H2Y_LIGHTDIST_BINS && i < H2Y_LIGHTDIST_PERCENTILES; k++) { /* lightdist_finish's rule */
+                cum += sum[k];
+                for (; i < H2Y_LIGHTDIST_PERCENTILES && cum * 10000u >= (uint64_t)kPct[i] * o.pixels; i++)
+                    o.pct_bits[i] = k ? H2Y_LIGHTDIST_FIRST_BITS + ((k - 1u) << 14) : 0u;
+            }
+        }
+        f0 = f1;
+    }
+    return scenes;
+}
+
+size_t h2y_lightdist_json_scenes(const h2y_scene_stats *scenes, int n_scenes, long first_frame_index, char *buf, size_t cap)
+{
+    if (!scenes || n_scenes < 1 || first_frame_index < 0) return 0;
+    int64_t at = 0;
+    for (int s = 0; s < n_scenes; s++) {
+        if (!scenes[s].pixels || scenes[s].n_frames < 1 || scenes[s].first_frame != at) return 0;
+        at += scenes[s].n_frames;
+    }
+    std::string text = "{\"JSONInfo\": {\"HDR10plusProfile\": \"A\", \"Version\": \"1.0\"},\n\"SceneInfo\": [\n";
+    std::string firsts, counts;
+    char line[1024];
+    for (int s = 0; s < n_scenes; s++) {
+        const h2y_scene_stats &t = scenes[s];
+        const unsigned __int128 q = ((unsigned __int128)t.sum_q_hi << 64) | t.sum_q_lo;
+        const long avg = lrint(((100000.0 * (double)q) * 0x1p-32) / (double)t.pixels); /* h2y_lightdist_json's order of operations */
+        const long share = (long)((unsigned __int128)100u * t.below_100 / t.pixels);
+        const uint32_t *p = t.pct_bits;
+        for (int64_t k = 0; k < t.n_frames; k++) {
+            const bool last = s + 1 == n_scenes && k + 1 == t.n_frames;
+            snprintf(line, sizeof line,
+                     "{\"LuminanceParameters\": {\"AverageRGB\": %ld, \"LuminanceDistributions\": {\"DistributionIndex\": [1, 5, 10, 25, 50, 75, 90, "
+                     "95, 99], \"DistributionValues\": [%ld, %ld, %ld, %ld, %ld, %ld, %ld, %ld, %ld]}, \"MaxScl\": [%ld, %ld, %ld]}, "
+                     "\"NumberOfWindows\": 1, \"TargetedSystemDisplayMaximumLuminance\": 400, \"SceneFrameIndex\": %lld, \"SceneId\": %d, "
+                     "\"SequenceFrameIndex\": %lld}%s\n",
+                     avg, lightdist_units(p[0]), lightdist_units(p[9]), share, lightdist_units(p[3]), lightdist_units(p[4]), lightdist_units(p[5]),
+                     lightdist_units(p[6]), lightdist_units(p[7]), lightdist_units(p[8]), lightdist_units(t.maxscl_bits[2]),
+                     lightdist_units(t.maxscl_bits[0]), lightdist_units(t.maxscl_bits[1]), (long long)k, s,
+                     (long long)(first_frame_index + t.first_frame + k), last ? "" : ",");
+            text += line;
+        }
+        firsts += (s ? ", " : "") + std::to_string(first_frame_index + t.first_frame);
+        counts += (s ? ", " : "") + std::to_string(t.n_frames);
+    }
+    text += "],\n\"SceneInfoSummary\": {\"SceneFirstFrameIndex\": [" + firsts + "], \"SceneFrameNumbers\": [" + counts +
+            "]},\n\"ToolInfo\": {\"Tool\": \"hdr2yuv\", \"Version\": \"1.0\"}}\n";
+    if (buf && cap) {
+        const size_t n = std::min(text.size(), cap - 1);
+        memcpy(buf, text.data(), n);
+        buf[n] = 0;
+    }
+    return text.size();
+}
+
 /* ---- Delta E ITP of PQ code planes (h2y_deltae_batch, h2y_stream_deltae): include/hdr2yuv_hip.h states the definition ------------- */
 
 /* k_deltae's arguments from a checked plan: k_codelight's, and PQ10000_r's tables, what code1 reads of pix_params */

@@ -196,7 +196,7 @@ struct ring_stage {
     virtual int run(h2y_ctx *ctx, int slot) = 0;          /* on the context's stream, after the frame was produced */
     virtual int download(h2y_ctx *, int) { return H2Y_OK; } /* the result, on s_d2h after the slot's ev_conv */
 };
-enum stage_id { STAGE_GAMUT, STAGE_TONEMAP, STAGE_LIGHT, STAGE_LIGHTDIST, STAGE_CODELIGHT, STAGE_COMPARE, STAGE_SSIM, STAGE_DELTAE, STAGE_HISTOGRAM, STAGE_SCALE, STAGE_COUNT };
+enum stage_id { STAGE_GAMUT, STAGE_TONEMAP, STAGE_LIGHT, STAGE_LIGHTDIST, STAGE_CODELIGHT, STAGE_SCENESIG, STAGE_COMPARE, STAGE_SSIM, STAGE_DELTAE, STAGE_HISTOGRAM, STAGE_SCALE, STAGE_COUNT };
 
 struct h2y_ctx {
     int device = 0;
@@ -279,6 +279,9 @@ struct h2y_ctx {
     /* h2y_codelight_batch's device workspace (light_acc, then lightdist_layout) and its launches' upsampled 4:2:0 chroma */
     char *d_codelight = nullptr, *d_codelight_up = nullptr;
     size_t codelight_cap = 0, codelight_up_cap = 0;
+    /* h2y_scenesig_batch's and h2y_codescenesig_batch's cells on the device: 144 uint64 a frame */
+    unsigned long long *d_scenesig = nullptr;
+    size_t scenesig_cap = 0;
     /* h2y_deltae_batch's accumulators (its launches' upsampled 4:2:0 chroma lies in d_codelight_up) */
     deltae_acc *d_deltae = nullptr;
     size_t deltae_cap = 0;

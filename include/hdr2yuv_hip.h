@@ -762,9 +762,91 @@ int h2y_codelight_batch(h2y_ctx *ctx, const h2y_codelight_desc *d, int n_frames,
 /* A ring that only measures light: h2y_stream_input lends the frame's three planes (contiguous, as above), h2y_stream_output
  * returns *yuv = NULL, h2y_stream_light_result the frame's light and, when want_dist is 1, h2y_stream_lightdist_result its
  * distribution.  The inverse chroma siting is read when the ring opens.  Every arming entry (h2y_stream_compare, _ssim, _histogram,
- * _histogram_ex, _light, _lightdist, _scale, _gamut) is H2Y_EINVAL on this ring.  Refusals as h2y_codelight_batch; want_dist other
+ * _histogram_ex, _light, _lightdist, _scale, _gamut) but h2y_stream_scenesig is H2Y_EINVAL on this ring.  Refusals as h2y_codelight_batch; want_dist other
  * than 0 or 1 and depth outside 2..16 are H2Y_EINVAL. */
 int h2y_codelight_stream_open(h2y_ctx *ctx, const h2y_codelight_desc *d, int want_dist, int depth);
+
+/* ---- scene signature and scene cuts: per-scene HDR10+ metadata of a conversion or of a PQ master (--scene_detect 1, --scene_cuts) ----
+ * HDR10+ metadata is scene-based: a display adapts its tone curve per scene.  This section is the project's own definition (the
+ * reference has none): a spatial signature of a frame's light, counted on the device; a distance between two signatures and the
+ * cuts it gives; the figures of a scene, merged exactly from its frames' figures and bins; and the scene-based JSON.
+ *
+ * Signature of a frame.  m = max(L_G, L_B, L_R) of a pixel exactly as the light sections above define it: on the forward flow
+ *   light1 with the frame's floor and ceiling, a NaN as 0, the clamp ("light distribution"); on PQ code frames steps 1-4 of "light of
+ *   PQ code planes".  Its log-light value is the bin index of the light distribution, b = bin_of(bits(m)), 0..8705, 512 to a stop.
+ *   The frame is divided into a fixed grid of H2Y_SCENESIG_COLS x H2Y_SCENESIG_ROWS cells: pixel (x, y) of a W x H frame belongs to
+ *   cell (cy, cx) = ((y x 9) / H, (x x 16) / W), by integer division.  Every pixel has exactly one cell; a frame narrower than 16 or
+ *   lower than 9 leaves some cells empty.  cell[cy x 16 + cx] is the sum of b over the cell's pixels, pixels = W x H.  All figures
+ *   are integer sums: exact whatever the order of the work and the number of GPUs.
+ * Distance.  S = the sum over the cells of |a.cell - b.cell|, an exact uint64; D = (double)S / (512.0 x (double)a.pixels): the mean
+ *   absolute change of the cells' mean log light, in stops (weighted by the cells' sizes).
+ * Cuts.  Frame 0 opens scene 0; frame f opens a new scene when the distance between frames f - 1 and f exceeds the threshold.
+ * Figures of a scene.  maxscl_bits and max_bits: the maxima over the scene's frames; the 128-bit sum of the frames' sum_q; pixels
+ *   and below_100: sums; pct_bits from the frames' bins summed in uint64, by the rule of "light distribution": the smallest k with
+ *   cum(k) x 10000 >= p x pixels, all in uint64.  The scene's average in 0.1 cd/m2 is rint(((100000 x (double)S128) x 2^-32) /
+ *   (double)pixels), half to even, in that order, (double)S128 being the correctly rounded conversion of the 128-bit sum: it is
+ *   h2y_lightdist_json's order of operations.
+ *   Invariant: a scene of one frame carries exactly that frame's figures, and its entry in h2y_lightdist_json_scenes' text has the
+ *   LuminanceParameters of that frame's entry in h2y_lightdist_json's.
+ * The threshold the hdr2yuv CLI takes by default (0.5 stops) is a choice, not a measurement. */
+#define H2Y_SCENESIG_COLS 16
+#define H2Y_SCENESIG_ROWS 9
+#define H2Y_SCENESIG_FRAMES_PER_LAUNCH 64
+
+typedef struct h2y_scenesig {
+    uint64_t cell[H2Y_SCENESIG_COLS * H2Y_SCENESIG_ROWS]; /* row-major, cy*16+cx: sum of b over the cell's pixels */
+    uint64_t pixels;                                      /* W x H */
+} h2y_scenesig;
+
+typedef struct h2y_scene_stats {
+    int64_t  first_frame, n_frames;
+    uint32_t maxscl_bits[3], max_bits;              /* maxima over the scene's frames */
+    uint64_t sum_q_hi, sum_q_lo;                    /* the 128-bit sum of the frames' sum_q */
+    uint64_t pixels, below_100;                     /* sums */
+    uint32_t pct_bits[H2Y_LIGHTDIST_PERCENTILES];   /* from the summed bins, by the header's own rule */
+} h2y_scene_stats;
+
+/* The signatures of n_frames device frames of d: scope, planes, alignment and floor / ceiling exactly as h2y_lightdist_batch takes
+ * them; out[f] (host memory).  Launches of up to H2Y_SCENESIG_FRAMES_PER_LAUNCH frames (h2y_last_kernel_ms sums them,
+ * h2y_last_kernel_name "k_scenesig"); synchronous. */
+int h2y_scenesig_batch(h2y_ctx *ctx, const h2y_desc *d, int n_frames, const void *const *d_planes, h2y_scenesig *out);
+
+/* The signatures of n_frames device frames of PQ codes: scope, layout and refusals exactly as h2y_codelight_batch takes them (4:2:0
+ * chroma upsampled by k_up444 into the same scratch); out[f] (host memory).  Launches of up to H2Y_CODELIGHT_FRAMES_PER_LAUNCH
+ * frames (h2y_last_kernel_name "k_codescenesig"); synchronous. */
+int h2y_codescenesig_batch(h2y_ctx *ctx, const h2y_codelight_desc *d, int n_frames, const uint16_t *const *d_frames, h2y_scenesig *out);
+
+/* Arm an open ring before its first input: a forward ring wherever h2y_stream_lightdist is accepted, with its return values
+ * (k_scenesig then runs after k_lightdist on the same decoded planes: behind h2y_stream_gamut / _tonemap the converted ones), or the
+ * ring of h2y_codelight_stream_open (k_codescenesig on the planes k_codelight read).  Any other ring is H2Y_EINVAL.  The output
+ * bytes and every other stage's results do not change. */
+int h2y_stream_scenesig(h2y_ctx *ctx);
+/* The signature of the frame that h2y_stream_output returned last. */
+int h2y_stream_scenesig_result(h2y_ctx *ctx, h2y_scenesig *out);
+/* The H2Y_LIGHTDIST_BINS bins of the frame that h2y_stream_output returned last, on a ring armed with h2y_stream_lightdist or opened
+ * by h2y_codelight_stream_open with want_dist (they come down with the frame for its percentiles); H2Y_EINVAL on a ring that does
+ * not measure the distribution. */
+int h2y_stream_lightdist_bins(h2y_ctx *ctx, uint32_t *bins);
+
+/* The four functions below are host only: no device, no context. */
+
+/* D of two signatures; -1 for a null argument, zero pixels or differing pixels. */
+double h2y_scene_distance(const h2y_scenesig *a, const h2y_scenesig *b);
+/* scene_id[f] of n frames from their signatures; returns the number of scenes, 0 for n < 1, a null pointer, or a threshold that is
+ * negative or not finite (a pair whose distance is -1 opens no scene). */
+int h2y_scene_cuts(const h2y_scenesig *sig, int n, double threshold, int32_t *scene_id);
+/* The figures of the scenes of n_frames frames: stats[f] and bins[f x H2Y_LIGHTDIST_BINS] as h2y_lightdist_batch returns them,
+ * scene_id[f] as h2y_scene_cuts does (0 first, then equal to the frame before or one more).  Returns the number of scenes and writes
+ * the first min(that, cap) of them to out (out may be NULL when cap is 0); 0 for a null stats, bins or scene_id, n_frames < 1, a
+ * negative cap, scene ids of any other form, or a frame without pixels. */
+int h2y_scene_merge(const h2y_lightdist_stats *stats, const uint32_t *bins, const int32_t *scene_id, int n_frames, h2y_scene_stats *out,
+                    int cap);
+/* h2y_lightdist_json's text for scenes: its layout and slot convention, one SceneInfo entry per frame and line, every entry of scene
+ * s carrying the scene's figures with "SceneId": s, "SceneFrameIndex" counting from 0 inside the scene, "SequenceFrameIndex" running
+ * on from first_frame_index, and "SceneFirstFrameIndex" / "SceneFrameNumbers" listing every scene.  Sizing and refusals as
+ * h2y_lightdist_json (0 for null scenes, n_scenes < 1, a negative first_frame_index, a scene without pixels or frames); scenes that do
+ * not tile [0, N) in order return 0.  As there, no encoder's parser has checked the layout. */
+size_t h2y_lightdist_json_scenes(const h2y_scene_stats *scenes, int n_scenes, long first_frame_index, char *buf, size_t cap);
 
 /* ---- linearised PQ code planes: a finished PQ master as a LINEAR G,B,R F32 source of the forward flow (--linearize 1) ------------
  * Nothing in the arithmetic is new.  The output is three binary32 planes G, B, R of width x height that hold L_G, L_B, L_R exactly as
@@ -1094,7 +1176,7 @@ int h2y_upsample_444_sited(h2y_ctx *ctx, int width, int height, int chroma_sampl
                            const uint16_t *d_src, uint16_t *d_dst);
 
 /* Timing of the last h2y_convert_batch*() (or h2y_inverse_*, h2y_dpx_decode_batch, h2y_tiff_decode_batch,
- * h2y_rgb_interleave_batch, h2y_exr_decode_batch, h2y_compare_batch, h2y_ssim_batch, h2y_light_batch, h2y_lightdist_batch, h2y_codelight_batch, h2y_linearize_batch, h2y_scale_batch, h2y_gamut_batch) call measured with HIP events on
+ * h2y_rgb_interleave_batch, h2y_exr_decode_batch, h2y_compare_batch, h2y_ssim_batch, h2y_light_batch, h2y_lightdist_batch, h2y_codelight_batch, h2y_scenesig_batch, h2y_codescenesig_batch, h2y_linearize_batch, h2y_scale_batch, h2y_gamut_batch) call measured with HIP events on
  * the stream the kernels ran on: total ms over the main kernels and how many
  * launches that covered. */
 int h2y_last_kernel_ms(const h2y_ctx *ctx, float *ms, int *launches);
@@ -1102,7 +1184,7 @@ int h2y_last_kernel_ms(const h2y_ctx *ctx, float *ms, int *launches);
 /* Name of the kernel those launches ran ("k_fused", "k_fused_t1", "k_fused_lut16",
  * "k_fused_narrow"; of the inverse entries "k_inverse", "k_inverse420", "k_inverse_batch", "k_inverse420_batch"; of
  * h2y_dpx_decode_batch "k_dpx_decode"; of h2y_tiff_decode_batch "k_tiff_decode", of h2y_rgb_interleave_batch
- * "k_rgb_interleave"; of h2y_exr_decode_batch "k_exr_decode"; of h2y_compare_batch "k_compare"; of h2y_scale_batch "k_scale"; of h2y_gamut_batch "k_gamut"; of h2y_codelight_batch "k_codelight"; of h2y_linearize_batch "k_linearize"): the name to
+ * "k_rgb_interleave"; of h2y_exr_decode_batch "k_exr_decode"; of h2y_compare_batch "k_compare"; of h2y_scale_batch "k_scale"; of h2y_gamut_batch "k_gamut"; of h2y_codelight_batch "k_codelight"; of h2y_scenesig_batch "k_scenesig"; of h2y_codescenesig_batch "k_codescenesig"; of h2y_linearize_batch "k_linearize"): the name to
  * look for in a rocprofv3 kernel trace. */
 const char *h2y_last_kernel_name(const h2y_ctx *ctx);
 /* The same with its template arguments and launch shape, e.g. "k_fused_t1<F32,420BOX,YCBCR,PQ_IDENT> groups=8 xcd=1";

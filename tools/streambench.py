@@ -85,6 +85,19 @@ Prints one line per figure, then one JSON line with all of them.
   3. frames/s from host memory of the .f32 ring to PQ BT.2020nc 10-bit 4:2:0, unarmed and armed with h2y_stream_lightdist.
 Prints one line per figure, then one JSON line with all of them.
 
+`streambench.py scenes`: the scene signature (k_scenesig, k_codescenesig) on 4K frames, in one job:
+  1. h2y_scenesig_batch beside h2y_lightdist_batch (k_lightdist) and h2y_light_batch (k_light, the yardstick: the same bytes and the
+     same transfer arithmetic) over the same 64 distinct device frames per call, five calls each taken in turn after a warm-up (HIP
+     events round the launch; floor and ceiling given, so no k_stats runs; the memset that zeroes a call's accumulators lies before
+     the first event): the median and spread in us per frame, the ratios to k_light and k_lightdist, and the bytes per frame over
+     that time as a share of the 8 TB/s HBM peak at 12 (F32) and 6 (F16, U16) B/pixel, on noise, and for F32 on a constant and on a
+     letterboxed picture;
+  2. h2y_codescenesig_batch beside h2y_codelight_batch with DIST on 10-bit 4:2:0 BT.2020nc noise, timed the same way (launches of
+     up to 8 frames, k_up444 included in both; 11 B/pixel as `codelight` counts them);
+  3. frames/s from host memory of the .f32 ring to PQ BT.2020nc 10-bit 4:2:0, armed with h2y_stream_lightdist alone and with
+     h2y_stream_scenesig as well (the bins taken with every output), three runs of each in turn after a warm-up.
+Prints one line per figure, then one JSON line with all of them.
+
 `streambench.py deltae`: Delta E ITP of PQ code planes (k_deltae) on 4K frames, in one job:
   1. h2y_deltae_batch over 64 distinct device frame pairs per call, 10-bit 4:2:0 and 4:4:4, beside h2y_codelight_batch (on A),
      h2y_compare_batch and h2y_ssim_batch on the same pairs, five calls each taken in turn after a warm-up, the median per frame; the
@@ -1104,6 +1117,142 @@ def lightdist_main():
     print(json.dumps({"streambench_lightdist": res}), flush=True)
 
 
+def scenes_main():
+    import json
+
+    import torch
+
+    w, hh, nb, reps = 3840, 2160, 64, 5
+    n = w * hh
+    nf = int(os.environ.get("N", "60"))
+    depth = 3
+    rng = np.random.default_rng(31)
+    ctx = h.Context(0)
+    res = {"width": w, "height": hh, "frames_per_call": nb, "reps": reps, "ring_frames": nf, "ring_depth": depth, "hbm_peak_tbs": 8.0}
+
+    def noise(dt):
+        return lambda: [torch.rand(n, device="cuda").to(dt) for _ in range(3)]
+
+    def codes16():
+        return [torch.randint(0, 65536, (n,), dtype=torch.int32, device="cuda").to(torch.int16) for _ in range(3)]
+
+    def constant():
+        return [torch.full((n,), 0.25, dtype=torch.float32, device="cuda") for _ in range(3)]
+
+    def letterbox():  # a 2.39:1 picture in a 16:9 frame: black bars above and below
+        bar = (hh - int(w / 2.39)) // 2 * w
+        planes = noise(torch.float32)()
+        for p in planes:
+            p[:bar] = 0.0
+            p[n - bar:] = 0.0
+        return planes
+
+    def timed(calls):
+        """every call of calls in turn, reps times after a warm-up: per call its kernel times in ms per frame, and its variant"""
+        out, variants = [[] for _ in calls], [None] * len(calls)
+        for rep in range(reps + 1):
+            for k, call in enumerate(calls):
+                call()
+                variants[k] = ctx.last_kernel_variant()
+                if rep:
+                    out[k].append(ctx.last_kernel_ms()[0] / nb)
+        return out, variants
+
+    def figures(t, nbytes, variant):
+        med = float(np.median(t))
+        tbs = nbytes / (med * 1e-3) / 1e12
+        return dict(kernel_us_per_frame=round(med * 1e3, 2), min_us=round(min(t) * 1e3, 2), max_us=round(max(t) * 1e3, 2), bytes_per_frame=nbytes,
+                    kernel_tbs=round(tbs, 2), hbm_peak_fraction=round(tbs / 8.0, 3), variant=variant)
+
+    def line(label, f):
+        print(f"{label:34s} {nb} frames per call: {f['kernel_us_per_frame']:7.2f} us/frame ({f['min_us']:.2f}..{f['max_us']:.2f})  "
+              f"{f['kernel_tbs']:5.2f} TB/s = {f['hbm_peak_fraction']*100:4.1f} % of 8 TB/s  {f['variant']}", flush=True)
+
+    # 1. k_scenesig beside k_lightdist and k_light on the same 64 device frames
+    F32, F16, U16 = h.SAMPLE_F32, h.SAMPLE_F16, h.SAMPLE_U16
+    for name, sample, depth_in, make in (("f32", F32, 32, noise(torch.float32)), ("f16", F16, 32, noise(torch.float16)), ("u16", U16, 16, codes16),
+                                         ("f32_constant", F32, 32, constant), ("f32_letterbox", F32, 32, letterbox)):
+        d = h.make_desc(w, hh, sample=sample, src_depth=depth_in, dst_depth=10, src_transfer=8, dst_transfer=16,
+                        dst_matrix=h.MATRIX_BT2020NC, resampler=0, stats=[(0, 1 if sample != U16 else 65535)] * 3)
+        frames = [make() for _ in range(nb)]
+        torch.cuda.synchronize()
+        (light, dist, sig), variants = timed([lambda: ctx.light_batch(d, frames), lambda: ctx.lightdist_batch(d, frames),
+                                              lambda: ctx.scenesig_batch(d, frames)])
+        nbytes = 3 * n * (4 if sample == F32 else 2)
+        fl, fd, fs = figures(light, nbytes, variants[0]), figures(dist, nbytes, variants[1]), figures(sig, nbytes, variants[2])
+        fs["ratio_to_k_light"] = round(fs["kernel_us_per_frame"] / fl["kernel_us_per_frame"], 3)
+        fs["ratio_to_k_lightdist"] = round(fs["kernel_us_per_frame"] / fd["kernel_us_per_frame"], 3)
+        res[f"k_scenesig_{name}"], res[f"k_lightdist_{name}"], res[f"k_light_{name}"] = fs, fd, fl
+        line(f"k_scenesig {name}", fs)
+        line(f"k_lightdist {name}", fd)
+        line(f"k_light {name} (yardstick)", fl)
+        print(f"k_scenesig / k_light {fs['ratio_to_k_light']:5.3f}   k_scenesig / k_lightdist {fs['ratio_to_k_lightdist']:5.3f}", flush=True)
+        del frames
+        torch.cuda.empty_cache()
+
+    # 2. k_codescenesig beside k_codelight DIST on 10-bit 4:2:0
+    def code_frame():
+        part = lambda count, lo, hi: torch.randint(lo, hi + 1, (count,), dtype=torch.int32, device="cuda").to(torch.int16)
+        return torch.cat([part(n, 64, 940), part(n // 4, 64, 960), part(n // 4, 64, 960)])
+
+    dc = h.make_codelight_desc(w, hh, 1, 10, 0, h.MATRIX_BT2020NC, 1)
+    frames = [code_frame() for _ in range(nb)]
+    torch.cuda.synchronize()
+    (cl, cs), variants = timed([lambda: ctx.codelight_batch(dc, frames, dist=True), lambda: ctx.codescenesig_batch(dc, frames)])
+    fcl, fcs = figures(cl, 11 * n, variants[0]), figures(cs, 11 * n, variants[1])
+    fcs["ratio_to_k_codelight_dist"] = round(fcs["kernel_us_per_frame"] / fcl["kernel_us_per_frame"], 3)
+    res["k_codescenesig_420_10_noise"], res["k_codelight_420_10_noise_dist"] = fcs, fcl
+    line("k_codescenesig 420_10_noise", fcs)
+    line("k_codelight 420_10_noise DIST", fcl)
+    print(f"k_codescenesig / k_codelight DIST {fcs['ratio_to_k_codelight_dist']:5.3f}", flush=True)
+    del frames
+    torch.cuda.empty_cache()
+
+    # 3. the .f32 ring from host memory: the distribution alone, and the signature as well
+    def ring(sig):
+        ctx.stream_open(d32, depth)
+        ctx.stream_lightdist()
+        if sig:
+            ctx.stream_scenesig()
+        inflight = 0
+        t0 = time.perf_counter()
+
+        def take():
+            ctx.stream_output()
+            ctx.stream_lightdist_result()
+            if sig:
+                ctx.stream_scenesig_result()
+                ctx.stream_lightdist_bins()
+
+        for _ in range(nf):
+            slot = ctx.stream_input()
+            for c in range(3):
+                slot[c][:] = planes[c]
+            ctx.stream_submit()
+            inflight += 1
+            if inflight == depth - 1:
+                take()
+                inflight -= 1
+        while inflight:
+            take()
+            inflight -= 1
+        dt = (time.perf_counter() - t0) / nf
+        ctx.stream_close()
+        return dt
+
+    d32 = h.make_desc(w, hh, dst_depth=10, dst_matrix=h.MATRIX_BT2020NC, resampler=1)
+    planes = [rng.random(n, dtype=np.float32) for _ in range(3)]
+    ring(False)  # warm-up
+    runs = [(ring(False), ring(True)) for _ in range(3)]
+    t_dist, t_sig = float(np.median([r[0] for r in runs])), float(np.median([r[1] for r in runs]))
+    res["f32_ring"] = dict(lightdist_fps=round(1 / t_dist, 1), lightdist_scenesig_fps=round(1 / t_sig, 1), share=round(t_dist / t_sig, 3),
+                           runs_fps=[[round(1 / a, 1), round(1 / b, 1)] for a, b in runs])
+    print(f"f32 ring from host memory: h2y_stream_lightdist {1/t_dist:6.1f} frames/s   with h2y_stream_scenesig {1/t_sig:6.1f} frames/s "
+          f"({t_dist/t_sig*100:5.1f} %)", flush=True)
+    ctx.close()
+    print(json.dumps({"streambench_scenes": res}), flush=True)
+
+
 def codelight_main():
     import json
 
@@ -1856,6 +2005,8 @@ if __name__ == "__main__":
         lightdist_main()
     elif sys.argv[1:] == ["codelight"]:
         codelight_main()
+    elif sys.argv[1:] == ["scenes"]:
+        scenes_main()
     elif sys.argv[1:] == ["linearize"]:
         linearize_main()
     elif sys.argv[1:] == ["deltae"]:
