@@ -44,6 +44,7 @@ EXPORTS = [
     "h2y_linearize_batch", "h2y_pqcode_stream_open",
     "h2y_deltae_batch", "h2y_stream_deltae", "h2y_stream_deltae_result",
     "h2y_scale_taps", "h2y_scale_frame_bytes", "h2y_scale_batch", "h2y_stream_scale", "h2y_scale_stream_open",
+    "h2y_dither_offsets", "h2y_dither_batch", "h2y_stream_dither", "h2y_dither_stream_open",
     "h2y_gamut_matrix", "h2y_gamut_batch", "h2y_stream_gamut",
     "h2y_tonemap_curve", "h2y_tonemap_batch", "h2y_stream_tonemap",
     "h2y_ctx_set_chroma_siting", "h2y_subsample_420_sited",
@@ -67,6 +68,8 @@ SCALE_FRAMES_PER_LAUNCH = 64
 GAMUT_FRAMES_PER_LAUNCH = 64
 TONEMAP_FRAMES_PER_LAUNCH = 64
 SCALE_TAPS = 32  # coefficients per row of scale_taps' table
+DITHER_FRAMES_PER_LAUNCH = 64
+DITHER_CUT, DITHER_ORDERED, DITHER_NOISE = 0, 1, 2
 
 
 class H2YError(RuntimeError):
@@ -535,6 +538,15 @@ def load_library():
     L.h2y_stream_scale.restype = C.c_int
     L.h2y_scale_stream_open.argtypes = [C.c_void_p] + [C.c_int] * 10
     L.h2y_scale_stream_open.restype = C.c_int
+    L.h2y_dither_offsets.argtypes = [C.c_int] * 3 + [C.c_uint32] * 2 + [C.c_int] * 3 + [C.c_void_p]
+    L.h2y_dither_offsets.restype = C.c_int
+    L.h2y_dither_batch.argtypes = ([C.c_void_p] + [C.c_int] * 9 + [C.c_uint32] * 2 + [C.c_int]
+                                   + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)])
+    L.h2y_dither_batch.restype = C.c_int
+    L.h2y_stream_dither.argtypes = [C.c_void_p] + [C.c_int] * 3 + [C.c_uint32] * 2
+    L.h2y_stream_dither.restype = C.c_int
+    L.h2y_dither_stream_open.argtypes = [C.c_void_p] + [C.c_int] * 9 + [C.c_uint32] * 2 + [C.c_int]
+    L.h2y_dither_stream_open.restype = C.c_int
     L.h2y_gamut_matrix.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_char_p)]
     L.h2y_gamut_matrix.restype = C.c_int
     L.h2y_gamut_batch.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
@@ -682,6 +694,16 @@ def scale_taps(src: int, dst: int, a: int = 3):
     if rc != H2Y_OK:
         raise H2YError(rc, (lib.h2y_last_error(None) or b"").decode())
     return first, count, coef, most.value
+
+
+def dither_offsets(mode: int, shift: int, temporal: int, seed: int, frame: int, plane: int, width: int, height: int):
+    """h2y_dither_offsets: t of every sample of one plane (host only, no device): uint16[height, width]."""
+    lib = load_library()
+    t = np.zeros((max(height, 1), max(width, 1)), dtype=np.uint16)
+    rc = lib.h2y_dither_offsets(mode, shift, temporal, seed & 0xFFFFFFFF, frame & 0xFFFFFFFF, plane, width, height, t.ctypes.data)
+    if rc != H2Y_OK:
+        raise H2YError(rc, (lib.h2y_last_error(None) or b"").decode())
+    return t
 
 
 def lightdist_json(stats, first_frame_index: int = 0) -> str:
@@ -1138,6 +1160,20 @@ class Context:
         pd = (C.c_void_p * max(n, 1))(*[self._ptr(x) for x in frames_dst])
         self._check(self.lib.h2y_scale_batch(self.h, src_w, src_h, dst_w, dst_h, chroma, bit_depth, full_range, gbr, a, n, ps, pd))
 
+    def dither_batch(self, width, height, chroma, src_depth, dst_depth, full_range, gbr, mode, temporal, seed, first_frame,
+                     frames_src, frames_dst=None) -> None:
+        """k_dither on device frames (tensors or pointers, each frame's planes contiguous from a 16-byte aligned base):
+        frames_dst[f] receives frames_src[f] reduced from src_depth to dst_depth as frame number first_frame + f; frames_dst
+        None: in place."""
+        frames_dst = frames_src if frames_dst is None else frames_dst
+        n = len(frames_src)
+        if len(frames_dst) != n:
+            raise ValueError("frames_src and frames_dst differ in length")
+        ps = (C.c_void_p * max(n, 1))(*[self._ptr(x) for x in frames_src])
+        pd = (C.c_void_p * max(n, 1))(*[self._ptr(x) for x in frames_dst])
+        self._check(self.lib.h2y_dither_batch(self.h, width, height, chroma, src_depth, dst_depth, full_range, gbr, mode, temporal,
+                                              seed & 0xFFFFFFFF, first_frame & 0xFFFFFFFF, n, ps, pd))
+
     def gamut_batch(self, width, height, sample, src_primaries, dst_primaries, clip, frames_src, frames_dst=None) -> None:
         """k_gamut on device frames (frames_src[f] = three device planes G, B, R of float or half samples, 16-byte aligned):
         frames_dst[f] receives them converted from src_primaries to dst_primaries; frames_dst None: in place."""
@@ -1193,6 +1229,23 @@ class Context:
         self._stream_rgb = False
         self._stream_cmp_planes = (src_w * src_h, nc, nc)
         self._stream_out_words = scale_frame_bytes(dst_w, dst_h, chroma) // 2
+
+    def stream_dither(self, dst_depth, mode, temporal=0, seed=0, first_frame=0) -> None:
+        """Arm an open forward ring (plain, DPX, TIFF, EXR or PQ code), after stream_scale where the ring scales: stream_output
+        then returns the frame reduced from the descriptor's dst_bit_depth to dst_depth (h2y_stream_dither)."""
+        self._check(self.lib.h2y_stream_dither(self.h, dst_depth, mode, temporal, seed & 0xFFFFFFFF, first_frame & 0xFFFFFFFF))
+
+    def dither_stream_open(self, width, height, chroma, src_depth, dst_depth, full_range, gbr, mode, temporal=0, seed=0,
+                           first_frame=0, depth=3) -> None:
+        """A ring that only dithers: stream_input lends the frame's three planes, stream_output returns the reduced frame."""
+        self._check(self.lib.h2y_dither_stream_open(self.h, width, height, chroma, src_depth, dst_depth, full_range, gbr, mode,
+                                                    temporal, seed & 0xFFFFFFFF, first_frame & 0xFFFFFFFF, depth))
+        nc = (width >> 1) * (height >> 1) if chroma == CHROMA_420 else width * height
+        self._stream_inverse = None
+        self._stream_dpx = None
+        self._stream_rgb = False
+        self._stream_cmp_planes = (width * height, nc, nc)
+        self._stream_out_words = width * height + 2 * nc
 
     def stream_histogram(self, bits=0, bit_depth=None, full_range=None, gbr=None) -> None:
         """Arm the open ring: every frame is counted on the device (h2y_stream_histogram; with bit_depth, full_range and gbr

@@ -78,6 +78,27 @@
  * --scale_only 1 (an addition): a .yuv (4:2:0 or 4:4:4) or .rgb source resampled into a destination of the same extension, no
  *             conversion; depth, chroma format and range are the source's, read as --histogram_only reads them; the destination
  *             size is --dst_pic_width / --dst_pic_height.
+ * --dither 1|2 [--dither_temporal 0|1] [--dither_seed N] (an addition; the reference's to-do list names "TEMPORAL DITHERING -- dither",
+ *             and the reference itself only cuts: (unsigned int) in matrix_convert(), a plain >> in write_yuv()): on the forward flow
+ *             to .yuv the run converts at a working depth W -- 16 bits from float and half planes, --src_bit_depth from .tiff, .rgb
+ *             and .yuv sources -- and every frame that would be written is reduced to --dst_bit_depth D on the device, 1 by a 16 x 16
+ *             ordered pattern, 2 by uniform noise (include/hdr2yuv_hip.h, "dither", states every step in integers), with the plane's
+ *             legal-range clamp at D.  0 is the run without the flag.  The pattern is the same in every frame unless
+ *             --dither_temporal 1 (0 by default: a still pattern costs an encoder nothing); --dither_seed (0 by default) moves it.
+ *             cli_resolve_dither runs first: it keeps D and rewrites the run's destination depth to W, so every later resolver and
+ *             the ring's descriptor see a W-bit conversion (--scale then resamples at W bits).  Each GPU thread arms its ring with its
+ *             block's first frame counted from the run's first, so any --gpus writes the same file.  From every input type, beside
+ *             --linearize, --tone_map, --gamut_convert, --scale, --dst_chroma_sample_loc_type, --content_light, --dynamic_metadata
+ *             and the scene flags, appending included.  The banner ends with dither: <1 (ordered)|2 (noise)>, dither_depth: W -> D,
+ *             dither_temporal: and dither_seed:.  Refused (exit 1, also under --dry_run): a value outside 0..2, --dither_temporal or
+ *             --dither_seed without --dither 1|2, a --dither_temporal other than 0 / 1, D >= W or W - D > 8 or D < 8, no
+ *             --dst_filename, a .rgb / .tiff destination and the .yuv -> RGB flow, --dst_matrix_coeffs 15, chroma_format_idc 2,
+ *             --ref_filename, --histogram, --ssim, --delta_e (compare or count the written file) and every other *_only flag.
+ * --dither_only 1 (an addition): a .yuv (4:2:0 or 4:4:4) or planar .rgb source at --src_bit_depth W reduced into a destination of the
+ *             same extension at --dst_bit_depth D, no conversion, with --dither 1|2 required; it honours the source range flag, takes
+ *             the G,B,R limits for a .rgb, numbers the frames from --src_start_frame on as 0, 1, ... and works for any --gpus.  It
+ *             prints dither_only: 1 and the four lines above.  Refused as above, and for a source that is not .yuv / .rgb, differing
+ *             extensions, and a destination size other than the source's.
  * --gamut_convert 1 [--gamut_clip 0|1] (an addition; the reference's matrix_to_primaries() is empty, convert.cpp:1991, and the two
  *             colour_primaries values only pick a branch of matrix_convert()): the decoded source planes are converted on the device
  *             from --src_colour_primaries to --dst_colour_primaries, in linear light, before the unchanged forward conversion
@@ -250,6 +271,14 @@ struct cli_args {
     double delta_e_limit = 0.0;
     h2y_codelight_desc de{};
     int de_siting = 0;
+    /* --dither 1|2 (ordered, noise) [--dither_temporal 0|1] [--dither_seed N]: the frames that go into the .yuv are reduced from a
+     * working depth to --dst_bit_depth on the device; --dither_only 1: a .yuv or .rgb reduced into a file of the same layout.
+     * Resolved by cli_resolve_dither: dither_from (W) and dither_to (D); the run's destination depth becomes W */
+    int dither = 0, dither_temporal = 0, dither_only = 0;
+    uint32_t dither_seed = 0;
+    bool dither_given = false, dither_temporal_given = false, dither_seed_given = false, dither_only_given = false;
+    int dither_from = 0, dither_to = 0;
+    bool dithers() const { return dither == 1 || dither == 2; }
     std::vector<int> devices;
     /* resolved */
     int in_type = CLI_IN_NONE, out_type = CLI_OUT_NONE;
@@ -333,6 +362,11 @@ static inline void cli_help()
            "  scaling: [--scale 1 [--scale_taps A]] (with --dst_pic_width / --dst_pic_height: every .yuv frame resampled on the GPU by\n"
            "  an exact Lanczos filter of A = 2, 3 or 4 lobes, 3 by default; each axis ratio within 1/4 .. 4), [--scale_only 1] (a .yuv or\n"
            "  .rgb source into a destination of the same extension, no conversion)\n"
+           "  dither: [--dither 1|2 [--dither_temporal 0|1] [--dither_seed N]] (the .yuv frames are converted at a working depth -- 16 bits\n"
+           "  from float and half sources, --src_bit_depth from 16-bit ones -- and reduced to --dst_bit_depth on the GPU, 1 by a 16x16\n"
+           "  ordered pattern, 2 by uniform noise, where the program otherwise cuts the low bits; at most 8 bits; the pattern is the same\n"
+           "  in every frame unless --dither_temporal 1), [--dither_only 1] (a .yuv or .rgb source at --src_bit_depth into a destination\n"
+           "  of the same extension at --dst_bit_depth, no conversion)\n"
            "input by extension: .yuv .rgb (16-bit planar), .f32 .f16 (raw planar float / half, plane order G,B,R: what\n"
            "  dpx_read() / read_exr() leave in memory), .dpx (10-bit, 16-bit or float DPX) and .tiff (16-bit R,G,B, uncompressed; centre-cropped\n"
            "  to 3840 wide, [--cutout_hd 1] 1920x1080, [--cutout_qhd 1] 960x540) and .exr (scanline OpenEXR: NONE, RLE, ZIPS or ZIP;\n"
@@ -383,6 +417,10 @@ static inline void cli_parse(cli_args &a, int argc, char **argv)
         else if (is("--scale")) { a.scale = atoi(val()); a.scale_given = true; }
         else if (is("--scale_only")) a.scale_only = atoi(val());
         else if (is("--scale_taps")) { a.scale_taps = atoi(val()); a.scale_taps_given = true; }
+        else if (is("--dither")) { a.dither = atoi(val()); a.dither_given = true; }
+        else if (is("--dither_temporal")) { a.dither_temporal = atoi(val()); a.dither_temporal_given = true; }
+        else if (is("--dither_seed")) { a.dither_seed = (uint32_t)strtoul(val(), nullptr, 0); a.dither_seed_given = true; }
+        else if (is("--dither_only")) { a.dither_only = atoi(val()); a.dither_only_given = true; }
         else if (is("--alpha_channel")) (void)val(); /* (read_tiff ignores alpha too) */
         else if (is("--cutout_hd")) a.cutout = atoi(val()) ? (a.cutout | H2Y_TIFF_CUTOUT_HD) : (a.cutout & ~H2Y_TIFF_CUTOUT_HD);
         else if (is("--cutout_qhd")) a.cutout = atoi(val()) ? (a.cutout | H2Y_TIFF_CUTOUT_QHD) : (a.cutout & ~H2Y_TIFF_CUTOUT_QHD);
@@ -561,7 +599,22 @@ static inline int cli_resolve_light_only(cli_args &a);
 static inline int cli_resolve_scenes(cli_args &a);
 static inline int cli_resolve_linearize(cli_args &a);
 static inline int cli_resolve_delta_e(cli_args &a);
+static inline int cli_resolve_dither(cli_args &a);
+static inline int cli_resolve_dither_only(cli_args &a);
+static inline int cli_resolve_all(cli_args &a);
 static inline int cli_resolve(cli_args &a)
+{
+    const bool dither_flags = a.dither_given || a.dither_temporal_given || a.dither_seed_given || a.dither_only_given;
+    /* first, and without a line of its own yet: every later resolver sees a conversion at the working depth */
+    if (dither_flags && cli_resolve_dither(a)) return 1;
+    const int arg_errors = a.dither_only == 1 ? cli_resolve_dither_only(a) : cli_resolve_all(a);
+    if (arg_errors || !a.dithers()) return arg_errors;
+    printf("dither: %d (%s)\ndither_depth: %d -> %d\ndither_temporal: %d\ndither_seed: %u\n", a.dither, a.dither == 1 ? "ordered" : "noise",
+           a.dither_from, a.dither_to, a.dither_temporal, a.dither_seed);
+    return 0;
+}
+
+static inline int cli_resolve_all(cli_args &a)
 {
     if (a.linearize_given) { /* first: what follows resolves the linearised source */
         printf("linearize: %d\n", a.linearize);
@@ -601,6 +654,107 @@ static inline int cli_resolve(cli_args &a)
     /* (--linearize 1 resolved its own; under --compare_only 1 --delta_e 1 the flag chooses Delta E's upsampler, checked there) */
     if (a.src_siting_given && !a.linearize && !(a.compare_only && a.delta_e == 1)) arg_errors += cli_resolve_src_siting(a);
     if (de_flags) arg_errors += cli_resolve_delta_e(a);
+    return arg_errors;
+}
+
+/* --dither / --dither_temporal / --dither_seed / --dither_only: the refusals, W (dither_from) and D (dither_to); on the forward
+ * flow the run's destination depth becomes W.  Prints warnings only; returns the number of argument errors */
+static inline int cli_resolve_dither(cli_args &a)
+{
+    int arg_errors = 0;
+    if (a.dither < 0 || a.dither > 2) { printf("WARNING: dither(%d) outside range [0,2]\n", a.dither); arg_errors++; }
+    if (a.dither_only != 0 && a.dither_only != 1) { printf("WARNING: dither_only(%d) not 0 or 1\n", a.dither_only); arg_errors++; }
+    if (a.dither_temporal != 0 && a.dither_temporal != 1) { printf("WARNING: dither_temporal(%d) not 0 or 1\n", a.dither_temporal); arg_errors++; }
+    if (arg_errors) return arg_errors;
+    if ((a.dither_temporal_given || a.dither_seed_given) && !a.dithers()) {
+        printf("WARNING: --dither_temporal and --dither_seed need --dither 1 or 2\n");
+        arg_errors++;
+    }
+    if (a.dither_only && !a.dithers()) { printf("WARNING: --dither_only 1 needs --dither 1 or 2\n"); arg_errors++; }
+    if (arg_errors || !a.dithers()) return arg_errors;
+    const char *flag = a.dither_only ? "--dither_only 1" : "--dither";
+    const char *other = a.compare_only ? "compare_only" : a.hist_only ? "histogram_only" : a.scale_only ? "scale_only" : a.light_only ? "light_only" : nullptr;
+    if (other) { printf("WARNING: %s: not with --%s 1\n", flag, other); return 1; }
+    if (a.dither_only && a.linearize) { printf("WARNING: --linearize 1 is the source of a conversion: not with --dither_only 1\n"); return 1; }
+    if (a.ref || a.hist || a.ssim || a.delta_e) {
+        printf("WARNING: %s is not combined with --ref_filename, --histogram, --ssim or --delta_e: compare or count the written file "
+               "(--compare_only 1, --histogram_only 1)\n", flag);
+        return 1;
+    }
+    if (!a.dst) { printf("WARNING: %s needs --dst_filename\n", flag); return 1; }
+    const char *sext = cli_ext_of(a.src), *dext = cli_ext_of(a.dst);
+    int W, chroma;
+    if (a.dither_only) {
+        if (strcasecmp(sext, "yuv") && strcasecmp(sext, "rgb")) {
+            printf("WARNING: --dither_only reads .yuv or .rgb; source file (%s) is a .%s\n", a.src ? a.src : "(none)", sext);
+            return 1;
+        }
+        if (strcasecmp(dext, sext)) {
+            printf("WARNING: --dither_only writes what it reads: destination file (%s) must be a .%s like the source\n", a.dst, sext);
+            return 1;
+        }
+        W = a.in.bit_depth;
+        chroma = a.in.chroma_format_idc;
+    } else {
+        if (strcasecmp(dext, "yuv")) {
+            printf("WARNING: --dither dithers the forward flow's .yuv frames: destination file (%s) is a .%s\n", a.dst, dext);
+            return 1;
+        }
+        if ((a.out.matrix_coeffs == -1 ? a.in.matrix_coeffs : a.out.matrix_coeffs) == H2Y_MATRIX_YUVPRIME2) {
+            printf("WARNING: --dither: dst_matrix_coeffs %d (Y'u'v') is not dithered\n", H2Y_MATRIX_YUVPRIME2);
+            return 1;
+        }
+        /* the working depth: a U16 source's own (the reference converts there and shifts), 16 bits for float and half planes */
+        const bool u16 = a.linearize != 1 && a.synthetic < 0 && (!strcasecmp(sext, "yuv") || !strcasecmp(sext, "rgb") || !strcasecmp(sext, "tiff"));
+        W = !u16 ? 16 : !strcasecmp(sext, "tiff") ? 16 : a.in.bit_depth;
+        chroma = a.out.chroma_format_idc == -1 ? (u16 && strcasecmp(sext, "tiff") ? a.in.chroma_format_idc : H2Y_CHROMA_444) : a.out.chroma_format_idc;
+    }
+    if (chroma == 2) { printf("WARNING: %s: chroma_format_idc 2 (4:2:2) is not dithered\n", flag); return 1; }
+    const int D = a.out.bit_depth ? a.out.bit_depth : a.in.bit_depth;
+    if (W < 9 || W > 16 || D < 8 || D >= W || W - D > 8) {
+        printf("WARNING: %s reduces the working depth (%d) to dst_bit_depth (%d): it needs 8 <= dst_bit_depth < %d <= 16, at most 8 bits apart\n",
+               flag, W, D, W);
+        return 1;
+    }
+    a.dither_from = W, a.dither_to = D;
+    if (!a.dither_only) a.out.bit_depth = W;
+    return 0;
+}
+
+/* --dither_only 1: one file reduced into another of the same layout, no conversion (cli_resolve_dither made the checks); returns
+ * the number of argument errors */
+static inline int cli_resolve_dither_only(cli_args &a)
+{
+    int arg_errors = 0;
+    a.in_type = !strcasecmp(cli_ext_of(a.src), "rgb") ? CLI_IN_RGB : CLI_IN_YUV;
+    printf("dither_only: 1\nsrc_filename: %s\ndst_filename: %s\n", a.src, a.dst);
+    printf("src_pic_width: %d\nsrc_pic_height: %d\nsrc_chroma_format_idc: %d\nsrc_bit_depth: %d\nsrc_video_full_range_flag: %d\n"
+           "dst_bit_depth: %d\nsrc_start_frame: %d\nn_frames: %d\n", a.in.width, a.in.height, a.in.chroma_format_idc, a.in.bit_depth,
+           a.in.video_full_range_flag, a.dither_to, a.start_frame, a.n_frames);
+    if (a.in.width < 1 || a.in.width > 10000) { printf("WARNING: pic_width(%d) outside range [1,10000]\n", a.in.width); arg_errors++; }
+    if (a.in.height < 1 || a.in.height > 10000) { printf("WARNING: pic_height(%d) outside range [1,10000]\n", a.in.height); arg_errors++; }
+    if (a.in.video_full_range_flag != 0 && a.in.video_full_range_flag != 1) {
+        printf("WARNING: video_full_range_flag(%d) not 0 or 1\n", a.in.video_full_range_flag);
+        arg_errors++;
+    }
+    if (a.in_type == CLI_IN_RGB && a.in.chroma_format_idc != H2Y_CHROMA_444) { /* three full planes R, G, B */
+        printf("WARNING: a .rgb holds three planes of width x height: --dither_only of a .rgb takes chroma_format_idc %d, not %d\n",
+               H2Y_CHROMA_444, a.in.chroma_format_idc);
+        arg_errors++;
+    } else if (a.in.chroma_format_idc != H2Y_CHROMA_420 && a.in.chroma_format_idc != H2Y_CHROMA_444) {
+        printf("WARNING: chroma_format_idc(%d) not %d or %d\n", a.in.chroma_format_idc, H2Y_CHROMA_420, H2Y_CHROMA_444);
+        arg_errors++;
+    } else if (a.in.chroma_format_idc == H2Y_CHROMA_420 && ((a.in.width | a.in.height) & 1)) {
+        printf("WARNING: --dither_only 1: 4:2:0 needs an even width and height, not %dx%d\n", a.in.width, a.in.height);
+        arg_errors++;
+    }
+    if ((a.out.width && a.out.width != a.in.width) || (a.out.height && a.out.height != a.in.height)) {
+        printf("WARNING: --dither_only 1 keeps the picture's size: leave out --dst_pic_width and --dst_pic_height\n");
+        arg_errors++;
+    }
+    a.out = a.in;
+    a.out.bit_depth = a.dither_to;
+    a.out_type = a.in_type == CLI_IN_RGB ? CLI_OUT_RGB : CLI_OUT_YUV;
     return arg_errors;
 }
 

@@ -5,7 +5,7 @@
  * (tiff.cpp:440: the file is opened in append mode; planes Y, Cb, Cr, little-endian 16-bit).
  *
  * How the file is laid out: main resolves the command line, scans the source (h2y_cli_sources.h) and checks every file's size,
- * then chooses one of six flows -- forward, .yuv -> RGB, --compare_only, --histogram_only, --scale_only, --light_only.  A flow is a `flow`: how
+ * then chooses one of seven flows -- forward, .yuv -> RGB, --compare_only, --histogram_only, --scale_only, --light_only, --dither_only.  A flow is a `flow`: how
  * to open its ring and arm its stages, how frame k gets into a slot's planes, the layout of the reference frame, how frame k is
  * written.  run_block drives every flow the same way (context, source, ring, reference, stages, the fill / submit / drain loop
  * three slots deep, the tail) and tears down through one guard; what the blocks measure is kept in one `results`.
@@ -110,6 +110,13 @@
  * arms its ring (h2y_stream_scale), so the frame that comes down is the converted frame resampled on the device to the destination
  * size (include/hdr2yuv_hip.h states the filter); frame k is written at `size of the file at start + k x scaled frame bytes`.
  * --scale_only 1 resamples a .yuv or .rgb source through a scale-only ring (h2y_scale_stream_open) into a file of the same layout.
+ *
+ * Dither (--dither 1|2 [--dither_temporal 0|1] [--dither_seed N] on the forward flow to .yuv; h2y_cli_args.h): the run's descriptor
+ * converts at the working depth (cli_resolve_dither), and each GPU thread arms its ring last (h2y_stream_dither, after
+ * h2y_stream_scale) with the destination depth and its block's first frame counted from the run's first, so the frame that comes
+ * down is the converted (and scaled) frame reduced on the device, numbered as one thread would number it: any --gpus writes the
+ * same file.  --dither_only 1 reduces a .yuv or .rgb source through a dither-only ring (h2y_dither_stream_open) into a file of the
+ * same layout.
  *
  * Primaries (--gamut_convert 1 [--gamut_clip 0|1] on the forward flow from .f32, .f16, .exr and .dpx; h2y_cli_args.h): each GPU thread
  * arms its ring (h2y_stream_gamut) with --src_colour_primaries and --dst_colour_primaries, so every slot's decoded planes are
@@ -271,8 +278,9 @@ static constexpr int kRingDepth = 3;
 /* What one of the six flows hands to run_block.  open and arm return the library's status; fill and write return "" or the
  * block's error message. */
 struct flow {
-    std::function<int(h2y_ctx *)> open; /* the flow's ring, kRingDepth deep */
-    std::function<int(h2y_ctx *)> arm;  /* its stages, once the reference file is open (empty: none) */
+    /* `first` is the block's first frame, counted from the run's first: the number of the ring's first frame where frames are numbered */
+    std::function<int(h2y_ctx *, long first)> open; /* the flow's ring, kRingDepth deep */
+    std::function<int(h2y_ctx *, long first)> arm;  /* its stages, once the reference file is open (empty: none) */
     size_t src_frame_bytes = 0;         /* of the one raw source file run_block opens and seeks; 0: the flow has none */
     std::function<std::string(long, FILE *, void *const *)> fill; /* frame k (of that file, where there is one) into the slot's planes */
     bool ref_rgb = false;               /* frame k of --ref_filename, where given, as read_ref takes it */
@@ -304,12 +312,12 @@ static std::string run_block(const cli_args &a, const flow &fl, results &res, in
         if (!g.src) return std::string("unable to open file ") + a.src;
         if (fseeko(g.src, (off_t)fl.src_frame_bytes * (off_t)(a.start_frame + b->first), SEEK_SET)) return "seek failed"; /* hdr2yuv.cpp:624 */
     }
-    if (fl.open(g.ctx)) return library();
+    if (fl.open(g.ctx, b->first)) return library();
     if (a.ref) { /* R from its frame 0 on: this block's frames start at `first` */
         g.ref = fopen(a.ref, "rb");
         if (!g.ref || fseeko(g.ref, (off_t)fl.ref_frame_bytes * (off_t)b->first, SEEK_SET)) return std::string("unable to read ") + a.ref;
     }
-    if (fl.arm && fl.arm(g.ctx)) return library();
+    if (fl.arm && fl.arm(g.ctx, b->first)) return library();
     long in_flight = 0;
     auto drain_one = [&]() -> std::string {
         const uint16_t *out = nullptr;
@@ -373,7 +381,7 @@ static flow forward_flow(const job &j)
     const scanned &s = j.src;
     const size_t pb = h2y_plane_bytes(&j.d);
     flow f;
-    f.open = [&j, &a, &s](h2y_ctx *ctx) {
+    f.open = [&j, &a, &s](h2y_ctx *ctx, long) {
         if (a.siting && h2y_ctx_set_chroma_siting(ctx, a.siting)) return (int)H2Y_EINVAL; /* before the ring is opened */
         /* the inverse siting serves --linearize's upsampler and --delta_e's (cli_resolve_delta_e has them agree where both upsample) */
         const int inv_siting = a.linearize && a.src_siting ? a.src_siting : a.delta_e ? a.de_siting : 0;
@@ -388,14 +396,15 @@ static flow forward_flow(const job &j)
                : a.in_type == CLI_IN_EXR  ? h2y_exr_stream_open(ctx, &j.d, &s.xi, kRingDepth)
                                           : h2y_stream_open(ctx, &j.d, kRingDepth);
     };
-    f.arm = [&a](h2y_ctx *ctx) {
+    f.arm = [&a](h2y_ctx *ctx, long first) {
         return (a.ref && h2y_stream_compare(ctx, a.sigma, a.dst ? 1 : 0)) || (a.ssim && h2y_stream_ssim(ctx, -1)) ||
                (a.delta_e && h2y_stream_deltae(ctx, &a.de, a.delta_e_threshold)) ||
                (a.hist && h2y_stream_histogram(ctx, a.hist_bits)) || (a.light && h2y_stream_light(ctx)) ||
                (a.dynmeta && h2y_stream_lightdist(ctx)) || (a.scene_detect == 1 && h2y_stream_scenesig(ctx)) ||
                (a.gamut && h2y_stream_gamut(ctx, a.in.colour_primaries, a.out.colour_primaries, a.gamut_clip)) ||
                (a.tone_map && h2y_stream_tonemap(ctx, a.tone_src_peak, a.tone_dst_peak, a.tone_relative)) ||
-               (a.scale && h2y_stream_scale(ctx, a.out.width, a.out.height, a.scale_taps));
+               (a.scale && h2y_stream_scale(ctx, a.out.width, a.out.height, a.scale_taps)) ||
+               (a.dithers() && h2y_stream_dither(ctx, a.dither_to, a.dither, a.dither_temporal, a.dither_seed, (uint32_t)first)); /* after scale */
     };
     if (a.linearize) { /* the code frame whole, as whole_frame_flow reads it: one read, a .rgb with its planes put in G, B, R order */
         const bool rgb = a.lin_type == CLI_IN_RGB;
@@ -476,13 +485,13 @@ static flow inverse_flow(const job &j)
     const bool tiff = a.out_type == CLI_OUT_TIFF;
     const size_t luma = (size_t)a.in.width * a.in.height * 2, chroma = (j.in_frame_bytes - luma) / 2, out_frame = j.out_frame_bytes;
     flow f;
-    f.open = [&a, tiff](h2y_ctx *ctx) {
+    f.open = [&a, tiff](h2y_ctx *ctx, long) {
         if (a.src_siting && h2y_ctx_set_inverse_chroma_siting(ctx, a.src_siting)) return (int)H2Y_EINVAL; /* before the ring is opened */
         return (tiff ? h2y_tiff_inverse_stream_open : h2y_inverse_stream_open)(ctx, a.in.width, a.in.height, a.in.chroma_format_idc,
                                                                               a.in.bit_depth, a.in.video_full_range_flag, a.in.matrix_coeffs,
                                                                               a.out.bit_depth, a.resampler, kRingDepth);
     };
-    f.arm = [&a](h2y_ctx *ctx) {
+    f.arm = [&a](h2y_ctx *ctx, long) {
         return (a.ref && h2y_stream_compare(ctx, a.sigma, a.dst ? 1 : 0)) || (a.ssim && h2y_stream_ssim(ctx, -1)) ||
                (a.hist && h2y_stream_histogram(ctx, a.hist_bits));
     };
@@ -527,11 +536,11 @@ static flow compare_flow(const job &j)
 {
     const cli_args &a = j.a;
     flow f = whole_frame_flow(j);
-    f.open = [&a](h2y_ctx *ctx) {
+    f.open = [&a](h2y_ctx *ctx, long) {
         if (a.delta_e && a.de_siting && h2y_ctx_set_inverse_chroma_siting(ctx, a.de_siting)) return (int)H2Y_EINVAL; /* before the ring is opened */
         return h2y_compare_stream_open(ctx, a.in.width, a.in.height, a.in.chroma_format_idc, a.sigma, kRingDepth);
     };
-    f.arm = [&a](h2y_ctx *ctx) {
+    f.arm = [&a](h2y_ctx *ctx, long) {
         return (a.ssim && h2y_stream_ssim(ctx, a.in.bit_depth)) || (a.delta_e && h2y_stream_deltae(ctx, &a.de, a.delta_e_threshold)) ||
                (a.hist && h2y_stream_histogram_ex(ctx, a.hist_bits, a.hist_depth, a.hist_full, a.hist_gbr));
     };
@@ -543,7 +552,7 @@ static flow histogram_flow(const job &j)
 {
     const cli_args &a = j.a;
     flow f = whole_frame_flow(j);
-    f.open = [&a](h2y_ctx *ctx) {
+    f.open = [&a](h2y_ctx *ctx, long) {
         return h2y_histogram_stream_open(ctx, a.in.width, a.in.height, a.in.chroma_format_idc, a.hist_depth, a.hist_full, a.hist_gbr, a.hist_bits,
                                          kRingDepth);
     };
@@ -555,13 +564,13 @@ static flow light_flow(const job &j)
 {
     const cli_args &a = j.a;
     flow f = whole_frame_flow(j);
-    f.open = [&a](h2y_ctx *ctx) {
+    f.open = [&a](h2y_ctx *ctx, long) {
         if (a.src_siting && h2y_ctx_set_inverse_chroma_siting(ctx, a.src_siting)) return (int)H2Y_EINVAL; /* before the ring is opened */
         const h2y_codelight_desc d{a.in.width, a.in.height, a.in.chroma_format_idc, a.in.bit_depth, a.in.video_full_range_flag,
                                    a.in.matrix_coeffs, a.resampler};
         return h2y_codelight_stream_open(ctx, &d, a.dynmeta ? 1 : 0, kRingDepth);
     };
-    if (a.scene_detect == 1) f.arm = [](h2y_ctx *ctx) { return h2y_stream_scenesig(ctx); };
+    if (a.scene_detect == 1) f.arm = [](h2y_ctx *ctx, long) { return h2y_stream_scenesig(ctx); };
     return f;
 }
 
@@ -571,12 +580,28 @@ static flow scale_flow(const job &j)
     const cli_args &a = j.a;
     const bool rgb = a.in_type == CLI_IN_RGB;
     flow f = whole_frame_flow(j);
-    f.open = [&a, rgb](h2y_ctx *ctx) {
+    f.open = [&a, rgb](h2y_ctx *ctx, long) {
         return h2y_scale_stream_open(ctx, a.in.width, a.in.height, a.in.chroma_format_idc, a.in.bit_depth, a.in.video_full_range_flag, rgb ? 1 : 0,
                                      a.out.width, a.out.height, a.scale_taps, kRingDepth);
     };
     f.out_bytes = j.out_frame_bytes;
     f.write = rgb ? write_rgb(j, (size_t)a.out.width * a.out.height * 2) : write_plain(j, f.out_bytes);
+    f.says_written = a.verbose > 0;
+    return f;
+}
+
+/* --dither_only: the source through one dither-only ring into the destination, the block's frames numbered from its first */
+static flow dither_flow(const job &j)
+{
+    const cli_args &a = j.a;
+    const bool rgb = a.in_type == CLI_IN_RGB;
+    flow f = whole_frame_flow(j);
+    f.open = [&a, rgb](h2y_ctx *ctx, long first) {
+        return h2y_dither_stream_open(ctx, a.in.width, a.in.height, a.in.chroma_format_idc, a.dither_from, a.dither_to, a.in.video_full_range_flag,
+                                      rgb ? 1 : 0, a.dither, a.dither_temporal, a.dither_seed, (uint32_t)first, kRingDepth);
+    };
+    f.out_bytes = j.out_frame_bytes;
+    f.write = rgb ? write_rgb(j, (size_t)a.in.width * a.in.height * 2) : write_plain(j, f.out_bytes);
     f.says_written = a.verbose > 0;
     return f;
 }
@@ -870,7 +895,8 @@ int main(int argc, char **argv)
     cli_args &a = j.a;
     scanned &s = j.src;
     cli_parse(a, argc, argv);
-    if ((!a.dst && !a.ref && !a.hist && !a.hist_only && !a.light && !a.dynmeta && !a.scale_only && !a.light_only) || (!a.src && a.synthetic < 0)) {
+    if ((!a.dst && !a.ref && !a.hist && !a.hist_only && !a.light && !a.dynmeta && !a.scale_only && !a.light_only && !a.dither_given && !a.dither_only_given) ||
+        (!a.src && a.synthetic < 0)) {
         if (!a.help) cli_help();
         return a.help ? 0 : 1;
     }
@@ -898,8 +924,8 @@ int main(int argc, char **argv)
     /* the flow, and the bytes of one frame as it reads and as it writes them */
     flow (*make_flow)(const job &);
     size_t &in_frame_bytes = j.in_frame_bytes, &out_frame_bytes = j.out_frame_bytes;
-    if (a.compare_only || a.hist_only || a.scale_only || a.light_only) { /* two files of one layout, or one */
-        make_flow = a.light_only ? light_flow : a.hist_only ? histogram_flow : a.scale_only ? scale_flow : compare_flow;
+    if (a.compare_only || a.hist_only || a.scale_only || a.light_only || a.dither_only) { /* two files of one layout, or one */
+        make_flow = a.light_only ? light_flow : a.hist_only ? histogram_flow : a.scale_only ? scale_flow : a.dither_only ? dither_flow : compare_flow;
         in_frame_bytes = out_frame_bytes = planar16_bytes(a.in);
     } else if (a.inverse) {
         if (a.out.bit_depth > 16 || a.in.bit_depth > 16) { printf("ERROR: bit depths must be 8..16 on the inverse flow\n"); return 1; }

@@ -475,4 +475,28 @@ size_t h2y_scale_lds(const scale_geom &g); /* k_scale's dynamic LDS bytes */
 /* k_scale over (frame, plane, tile) units */
 hipError_t h2y_launch_scale(int grid, hipStream_t st, const scale_geom &g, const scale_frame *frames, int n_frames);
 
+/* k_dither (h2y_dither.hip): the reduction to the output bit depth of include/hdr2yuv_hip.h ("dither") on frames of three u16
+ * planes; a frame's dst may be its src (in place).  Plane p holds n samples in rows of w, off samples from both bases. */
+struct dither_plane {
+    uint32_t w, n, off;
+    uint32_t chunks; /* k_dither's units of the plane */
+    uint32_t lo, hi; /* the clamp at the destination depth */
+    uint32_t div_m, div_k; /* (i x div_m) >> div_k = i / w for a plane index i < 2^28 */
+};
+struct dither_args {
+    dither_plane p[3];
+    uint32_t shift;    /* s = W - D, 1..8 */
+    uint32_t key;      /* seed ^ 0x9E3779B9 */
+    uint32_t temporal; /* 1: the frame number enters the keys */
+    uint32_t first;    /* the number of the launch's first frame */
+};
+struct dither_frame { /* one frame; bases 16-byte aligned for 16-byte accesses */
+    const uint16_t *src;
+    uint16_t *dst;
+};
+/* plane of `rows` rows of w samples (w x rows < 2^28), off samples from the frame bases, clamped to lo..hi: its units and reciprocal */
+dither_plane h2y_dither_plane(uint32_t w, uint32_t rows, uint32_t off, uint32_t lo, uint32_t hi);
+/* k_dither<mode> over (frame, plane, chunk) units; mode: H2Y_DITHER_CUT, _ORDERED or _NOISE (h2y_dither1.h) */
+hipError_t h2y_launch_dither(int mode, int grid, hipStream_t st, const dither_args &a, const dither_frame *frames, int n_frames);
+
 #endif

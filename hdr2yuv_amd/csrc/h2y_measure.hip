@@ -160,6 +160,7 @@ int h2y_stream_compare(h2y_ctx *ctx, int sigma, int keep_output)
     if (ctx->s_stage[STAGE_COMPARE]) return fail(ctx, H2Y_EINVAL, "the ring is armed already");
     if (ctx->s_stage[STAGE_CODELIGHT]) return fail(ctx, H2Y_EINVAL, "a light-only ring takes no other stage");
     if (ctx->s_stage[STAGE_SCALE]) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that scales is not compared: compare the written file instead");
+    if (ctx->s_stage[STAGE_DITHER]) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that dithers is not compared: compare the written file instead");
     if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
     if (keep_output != 0 && keep_output != 1) return fail(ctx, H2Y_EINVAL, "keep_output must be 0 or 1");
     return cmp_arm(ctx, sigma, keep_output);
@@ -300,6 +301,7 @@ int h2y_stream_ssim(h2y_ctx *ctx, int bit_depth)
     if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
     if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
     if (ctx->s_stage[STAGE_SCALE]) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that scales computes no SSIM: compare the written file instead");
+    if (ctx->s_stage[STAGE_DITHER]) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that dithers computes no SSIM: compare the written file instead");
     const cmp_stage *cmp = stage_of<cmp_stage>(ctx, STAGE_COMPARE);
     if (!cmp) return fail(ctx, H2Y_EINVAL, "the ring is not armed for comparison: h2y_stream_compare first");
     if (ctx->s_stage[STAGE_SSIM]) return fail(ctx, H2Y_EINVAL, "the ring computes SSIM already");
@@ -1316,6 +1318,7 @@ int h2y_stream_deltae(h2y_ctx *ctx, const h2y_codelight_desc *d, float threshold
     if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
     if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
     if (ctx->s_stage[STAGE_CODELIGHT]) return fail(ctx, H2Y_EINVAL, "a light-only ring takes no other stage");
+    if (ctx->s_stage[STAGE_DITHER]) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that dithers computes no Delta E: compare the written file instead");
     const cmp_stage *cmp = stage_of<cmp_stage>(ctx, STAGE_COMPARE);
     if (!cmp) return fail(ctx, H2Y_EINVAL, "the ring is not armed for comparison: h2y_stream_compare first");
     if (ctx->s_stage[STAGE_DELTAE]) return fail(ctx, H2Y_EINVAL, "the ring computes Delta E already");
@@ -1610,6 +1613,7 @@ int h2y_stream_histogram_ex(h2y_ctx *ctx, int bits, int bit_depth, int full_rang
     if (ctx->s_stage[STAGE_HISTOGRAM]) return fail(ctx, H2Y_EINVAL, "the ring counts histograms already");
     if (ctx->s_stage[STAGE_CODELIGHT]) return fail(ctx, H2Y_EINVAL, "a light-only ring takes no other stage");
     if (ctx->s_stage[STAGE_SCALE]) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that scales counts no histograms: count the written file instead");
+    if (ctx->s_stage[STAGE_DITHER]) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that dithers counts no histograms: count the written file instead");
     if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
     const ring_frame &f = ctx->s_frame;
     if (!f.depth && (bit_depth < 0 || full_range < 0 || gbr < 0))
@@ -1856,6 +1860,7 @@ struct scale_stage : ring_stage {
     char *tabs = nullptr;
     scale_frame *tab = nullptr;
     size_t bytes = 0; /* of the scaled frame */
+    bool down = true; /* false: a dither stage armed behind this one sends its own frame down instead */
     int run(h2y_ctx *ctx, int k) override
     {
         HIP_TRY(ctx, h2y_launch_scale(scale_grid(ctx, g, 1), ctx->stream, g, tab + k, 1));
@@ -1863,7 +1868,7 @@ struct scale_stage : ring_stage {
     }
     int download(h2y_ctx *ctx, int k) override
     {
-        if (ss[k].d) HIP_TRY(ctx, hipMemcpyAsync(ss[k].h, ss[k].d, bytes, hipMemcpyDeviceToHost, ctx->s_d2h));
+        if (ss[k].d && down) HIP_TRY(ctx, hipMemcpyAsync(ss[k].h, ss[k].d, bytes, hipMemcpyDeviceToHost, ctx->s_d2h));
         return H2Y_OK;
     }
 };
@@ -1909,6 +1914,7 @@ int h2y_stream_scale(h2y_ctx *ctx, int dst_w, int dst_h, int a)
     if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
     if (ctx->s_kind != h2y_ctx::RING_FORWARD) return fail(ctx, H2Y_EINVAL, "only a forward ring is armed for scaling");
     if (ctx->s_stage[STAGE_SCALE]) return fail(ctx, H2Y_EINVAL, "the ring scales already");
+    if (ctx->s_stage[STAGE_DITHER]) return fail(ctx, H2Y_EINVAL, "the ring dithers already: arm scaling before dither");
     if (ctx->s_stage[STAGE_COMPARE] || ctx->s_stage[STAGE_HISTOGRAM] || ctx->s_stage[STAGE_SSIM])
         return fail(ctx, H2Y_EUNSUPPORTED, "a ring armed for comparison, histograms or SSIM is not scaled: compare or count the written file instead");
     if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
@@ -2289,4 +2295,198 @@ int h2y_stream_tonemap(h2y_ctx *ctx, int src_peak, int dst_peak, int relative)
         for (int c = 0; c < 3; c++) tab[k].src[c] = tab[k].dst[c] = ctx->ss[k].d_in + c * ctx->s_plane_al;
     st->table(st->tab, tab);
     return stage_arm(ctx, STAGE_TONEMAP, std::move(st), "tone map");
+}
+
+/* ---- dither: the reduction to the output bit depth (--dither; the reference's to-do list names it): include/hdr2yuv_hip.h states
+ * the definition ------------------------------------------------------------------------------------------------------------------ */
+
+#include "h2y_dither1.h"
+
+static const char *const kDitherMode[3] = {"cut", "ordered", "noise"};
+
+template <int MODE>
+static void dither_offsets_of(uint32_t kp, uint32_t s, int width, int height, uint16_t *t)
+{
+    for (int y = 0; y < height; y++) {
+        const uint32_t row = dither_row<MODE>(kp, (uint32_t)y);
+        for (int x = 0; x < width; x++) t[(size_t)y * width + x] = (uint16_t)dither_t<MODE>(kp, row, (uint32_t)x, s);
+    }
+}
+
+int h2y_dither_offsets(int mode, int shift, int temporal, uint32_t seed, uint32_t frame, int plane, int width, int height, uint16_t *t)
+{
+    if (!t) return fail(nullptr, H2Y_EINVAL, "null table");
+    if (mode < 0 || mode > 2) return fail(nullptr, H2Y_EINVAL, "mode must be 0 (cut), 1 (ordered) or 2 (noise)");
+    if (shift < 1 || shift > 8) return fail(nullptr, H2Y_EINVAL, "shift must be 1..8");
+    if (temporal != 0 && temporal != 1) return fail(nullptr, H2Y_EINVAL, "temporal must be 0 or 1");
+    if (plane < 0 || plane > 2) return fail(nullptr, H2Y_EINVAL, "plane must be 0..2");
+    if (width < 1 || height < 1) return fail(nullptr, H2Y_EINVAL, "width and height must be >= 1");
+    const uint32_t kp = dither_plane_key(seed ^ 0x9E3779B9u, (uint32_t)temporal, frame, (uint32_t)plane);
+    if (mode == H2Y_DITHER_ORDERED) dither_offsets_of<H2Y_DITHER_ORDERED>(kp, (uint32_t)shift, width, height, t);
+    else if (mode == H2Y_DITHER_NOISE) dither_offsets_of<H2Y_DITHER_NOISE>(kp, (uint32_t)shift, width, height, t);
+    else dither_offsets_of<H2Y_DITHER_CUT>(kp, (uint32_t)shift, width, height, t);
+    return H2Y_OK;
+}
+
+static int dither_check(h2y_ctx *ctx, int width, int height, int chroma, int src_depth, int dst_depth, int full_range, int gbr, int mode,
+                        int temporal)
+{
+    if (chroma == 2) return fail(ctx, H2Y_EUNSUPPORTED, "chroma_format_idc 2 (4:2:2) is not dithered");
+    if (chroma != H2Y_CHROMA_420 && chroma != H2Y_CHROMA_444) return fail(ctx, H2Y_EINVAL, "chroma_format_idc must be 1 or 3");
+    if (width < 1 || height < 1 || (uint64_t)width * (uint64_t)height >= (1ull << 28)) return fail(ctx, H2Y_EINVAL, "dither: bad picture size");
+    if (chroma == H2Y_CHROMA_420 && ((width | height) & 1)) return fail(ctx, H2Y_EINVAL, "dither 4:2:0: width and height must be even");
+    if (dst_depth < 8 || src_depth > 16 || dst_depth >= src_depth || src_depth - dst_depth > 8)
+        return fail(ctx, H2Y_EINVAL, "dither: depths must be 8 <= dst < src <= 16, at most 8 bits apart (src %d, dst %d)", src_depth, dst_depth);
+    if ((full_range != 0 && full_range != 1) || (gbr != 0 && gbr != 1)) return fail(ctx, H2Y_EINVAL, "full_range and gbr must be 0 or 1");
+    if (mode < 0 || mode > 2) return fail(ctx, H2Y_EINVAL, "dither mode must be 0 (cut), 1 (ordered) or 2 (noise)");
+    if (temporal != 0 && temporal != 1) return fail(ctx, H2Y_EINVAL, "dither: temporal must be 0 or 1");
+    return H2Y_OK;
+}
+
+/* k_dither's arguments for checked parameters: planes one after the other, the clamp write_yuv's at the destination depth */
+static dither_args dither_args_of(int width, int height, int chroma, int src_depth, int dst_depth, int full_range, int gbr, int temporal,
+                                  uint32_t seed)
+{
+    dither_args a{};
+    uint32_t off[3];
+    contiguous_planes(width, height, chroma, off);
+    const clip_limits c = make_clip(dst_depth, full_range);
+    const bool sub = chroma == H2Y_CHROMA_420;
+    for (int p = 0; p < 3; p++) {
+        const bool luma_like = p == 0 || gbr;
+        a.p[p] = h2y_dither_plane((uint32_t)(p && sub ? width >> 1 : width), (uint32_t)(p && sub ? height >> 1 : height), off[p],
+                                  luma_like ? c.minVR : c.minVRC, luma_like ? c.maxVR : c.maxVRC);
+    }
+    a.shift = (uint32_t)(src_depth - dst_depth);
+    a.key = seed ^ 0x9E3779B9u;
+    a.temporal = (uint32_t)temporal;
+    return a;
+}
+
+static size_t dither_frame_bytes(const dither_args &a) { return ((size_t)a.p[2].off + a.p[2].n) * sizeof(uint16_t); }
+
+static int dither_grid(const h2y_ctx *ctx, const dither_args &a, int n_frames)
+{
+    return unit_grid(ctx, (uint64_t)n_frames * (a.p[0].chunks + a.p[1].chunks + a.p[2].chunks));
+}
+
+int h2y_dither_batch(h2y_ctx *ctx, int width, int height, int chroma_format_idc, int src_depth, int dst_depth, int full_range, int gbr,
+                     int mode, int temporal, uint32_t seed, uint32_t first_frame, int n_frames, const uint16_t *const *d_src,
+                     uint16_t *const *d_dst)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
+    int rc = dither_check(ctx, width, height, chroma_format_idc, src_depth, dst_depth, full_range, gbr, mode, temporal);
+    if (rc) return rc;
+    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
+    if (!d_src || !d_dst) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
+    for (int f = 0; f < n_frames; f++) {
+        if (!d_src[f] || !d_dst[f]) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is null", f);
+        if (((uintptr_t)d_src[f] | (uintptr_t)d_dst[f]) & 15u) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is not 16-byte aligned", f);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const dither_args a = dither_args_of(width, height, chroma_format_idc, src_depth, dst_depth, full_range, gbr, temporal, seed);
+    dither_frame *h;
+    rc = frame_table(ctx, n_frames, h);
+    if (rc) return rc;
+    for (int f = 0; f < n_frames; f++) h[f] = dither_frame{d_src[f], d_dst[f]};
+    rc = timed_launches(ctx, h, n_frames, H2Y_DITHER_FRAMES_PER_LAUNCH, "k_dither", [&](const dither_frame *frames, int f0, int nf) {
+        dither_args b = a;
+        b.first = first_frame + (uint32_t)f0;
+        return h2y_launch_dither(mode, dither_grid(ctx, b, nf), ctx->stream, b, frames, nf);
+    });
+    if (rc) return rc;
+    ctx->last_variant = std::string("k_dither<") + kDitherMode[mode] + ">";
+    return H2Y_OK;
+}
+
+/* Dither's ring stage, the last of a slot's: on a ring that produces its frame it reduces the frame that would go down -- the
+ * conversion's, or the scale stage's -- into a frame of its own, on the device and pinned, which goes down and is handed out in
+ * that frame's place; on a ring without a producer it reduces the slot's input into its output.  The k-th submitted frame has
+ * number first + k. */
+struct dither_stage : ring_stage {
+    struct slot {
+        uint16_t *d = nullptr, *h = nullptr;
+    };
+    std::vector<slot> ss;
+    dither_args a{};
+    dither_frame *tab = nullptr;
+    size_t bytes = 0; /* of the frame */
+    int mode = 0;
+    uint32_t submitted = 0;
+    int run(h2y_ctx *ctx, int k) override
+    {
+        dither_args b = a;
+        b.first = a.first + submitted++;
+        HIP_TRY(ctx, h2y_launch_dither(mode, dither_grid(ctx, b, 1), ctx->stream, b, tab + k, 1));
+        return H2Y_OK;
+    }
+    int download(h2y_ctx *ctx, int k) override
+    {
+        if (ss[k].d) HIP_TRY(ctx, hipMemcpyAsync(ss[k].h, ss[k].d, bytes, hipMemcpyDeviceToHost, ctx->s_d2h));
+        return H2Y_OK;
+    }
+};
+
+/* arm the open ring's frame (a scale stage's where one is armed), reduced to dst_depth */
+static int dither_arm(h2y_ctx *ctx, int dst_depth, int gbr, int mode, int temporal, uint32_t seed, uint32_t first_frame)
+{
+    const ring_frame &f = ctx->s_frame;
+    scale_stage *sc = stage_of<scale_stage>(ctx, STAGE_SCALE);
+    const int width = sc ? (int)sc->g.p[0].dw : f.width, height = sc ? (int)sc->g.p[0].dh : f.height;
+    int rc = dither_check(ctx, width, height, f.chroma, f.depth, dst_depth, f.full_range, gbr, mode, temporal);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    auto st = std::make_unique<dither_stage>();
+    dither_stage *di = st.get();
+    di->a = dither_args_of(width, height, f.chroma, f.depth, dst_depth, f.full_range, gbr, temporal, seed);
+    di->a.first = first_frame;
+    di->mode = mode;
+    di->bytes = dither_frame_bytes(di->a);
+    const int depth = (int)ctx->ss.size();
+    std::vector<dither_frame> tab(depth);
+    di->ss.resize(depth);
+    for (int k = 0; k < depth; k++) {
+        if (!f.in_input) {
+            di->dev_alloc(di->ss[k].d, std::max<size_t>(di->bytes, 16));
+            di->pin_alloc(di->ss[k].h, std::max<size_t>(di->bytes, 16));
+        }
+        const uint16_t *src = sc && !f.in_input ? sc->ss[k].d : frame_base(ctx, k);
+        tab[k] = dither_frame{src, f.in_input ? ctx->ss[k].d_out : di->ss[k].d};
+    }
+    di->table(di->tab, tab);
+    rc = stage_arm(ctx, STAGE_DITHER, std::move(st), "dither");
+    if (rc || f.in_input) return rc;
+    if (sc) sc->down = false; /* the scaled frame stays on the device: its reduction goes down */
+    ring_frame_stays(ctx);
+    for (int k = 0; k < depth; k++) ctx->ss[k].result = di->ss[k].h;
+    return H2Y_OK;
+}
+
+int h2y_stream_dither(h2y_ctx *ctx, int dst_depth, int mode, int temporal, uint32_t seed, uint32_t first_frame)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    if (ctx->s_kind != h2y_ctx::RING_FORWARD) return fail(ctx, H2Y_EINVAL, "only a forward ring is armed for dither");
+    if (ctx->s_stage[STAGE_DITHER]) return fail(ctx, H2Y_EINVAL, "the ring dithers already");
+    if (ctx->s_stage[STAGE_COMPARE] || ctx->s_stage[STAGE_HISTOGRAM] || ctx->s_stage[STAGE_SSIM] || ctx->s_stage[STAGE_DELTAE])
+        return fail(ctx, H2Y_EUNSUPPORTED, "a ring armed for comparison, histograms, SSIM or Delta E is not dithered: compare or count the written file instead");
+    if (ctx->s_desc.dst_matrix == H2Y_MATRIX_YUVPRIME2) return fail(ctx, H2Y_EUNSUPPORTED, "a Y'u'v' ring (dst_matrix_coeffs 15) is not dithered");
+    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    return dither_arm(ctx, dst_depth, 0, mode, temporal, seed, first_frame);
+}
+
+/* A ring that only dithers: the slot's input is the frame's three planes, its output the reduced frame */
+int h2y_dither_stream_open(h2y_ctx *ctx, int width, int height, int chroma_format_idc, int src_depth, int dst_depth, int full_range, int gbr,
+                           int mode, int temporal, uint32_t seed, uint32_t first_frame, int depth)
+{
+    int rc = ring_may_open(ctx);
+    if (!rc) rc = dither_check(ctx, width, height, chroma_format_idc, src_depth, dst_depth, full_range, gbr, mode, temporal);
+    if (!rc) rc = open_planes_ring(ctx, width, height, chroma_format_idc, src_depth, full_range, gbr,
+                                   dither_frame_bytes(dither_args_of(width, height, chroma_format_idc, src_depth, dst_depth, full_range, gbr, temporal, seed)),
+                                   depth);
+    if (rc) return rc;
+    rc = dither_arm(ctx, dst_depth, gbr, mode, temporal, seed, first_frame);
+    if (rc) stream_free(ctx);
+    return rc;
 }

@@ -994,6 +994,65 @@ int h2y_stream_scale(h2y_ctx *ctx, int dst_w, int dst_h, int a);
 int h2y_scale_stream_open(h2y_ctx *ctx, int src_w, int src_h, int chroma_format_idc, int bit_depth, int full_range, int gbr, int dst_w,
                           int dst_h, int a, int depth /* 2..16 slots */);
 
+/* ---- dither: the reduction to the output bit depth (--dither; "TEMPORAL DITHERING -- dither" is an open entry of the reference's
+ * to-do list, and the reference itself only cuts: (unsigned int) in matrix_convert(), a plain >> in write_yuv()) --------------------
+ * There are no bytes of the reference to match: this is the project's own definition, in integers, so that a restatement checks
+ * every output bit.
+ * A frame of three u16 planes at a working depth W is reduced to depth D; the geometry is h2y_scale_batch's (4:2:0 or 4:4:4,
+ * planes one after the other).  The shift is s = W - D with 1 <= s <= 8 and 8 <= D < W <= 16.  All arithmetic is uint32 with
+ * wrap-around.  For sample v at (x, y) of plane p (coordinates within that plane) of frame number n:
+ *   mix(a):  a ^= a >> 16;  a *= 0x7FEB352D;  a ^= a >> 15;  a *= 0x846CA68B;  a ^= a >> 16
+ *   fi = temporal ? n : 0
+ *   kf = mix((seed ^ 0x9E3779B9) + fi)
+ *   kp = mix(kf + p)
+ *   mode 0 (library only, "cut"):  t = 0
+ *   mode 1 (ordered):  ox = kp & 15,  oy = (kp >> 4) & 15
+ *                      t = B((x + ox) & 15, (y + oy) & 15) >> (8 - s)
+ *   mode 2 (noise):    t = mix(mix(kp + y) + x) & (2^s - 1)
+ *   out = min(max((uint32(v) + t) >> s, lo), hi)
+ * B is the 16 x 16 ordered matrix, defined without a table: with a = x ^ y, bit i (0..3) of a goes to bit 2 (3 - i) + 1 of B and
+ * bit i of y to bit 2 (3 - i).  Anchors: mix(0) = 0, mix(1) = 0x688990C0; rows y = 0..3, columns x = 0..3 of B are
+ * 0 128 32 160 / 192 64 224 96 / 48 176 16 144 / 240 112 208 80.
+ * lo..hi is write_yuv()'s per-plane clamp at depth D, the rule h2y_scale_batch documents: [0, 2^D - 1] in full range; in video
+ * range [16 << (D-8), 235 << (D-8)] for plane 0 and every plane of a G, B, R frame (gbr 1), [16 << (D-8), 240 << (D-8)] for planes
+ * 1 and 2 otherwise.
+ * Ordered mode: every aligned 16 x 16 tile of B holds 0..255 once, and B >> (8 - s) each of the 2^s levels 256 / 2^s times, so on a
+ * constant plane v the outputs of any 16 x 16 tile add up to exactly 256 v / 2^s: the mean is kept exactly.  Noise mode is uniform
+ * and keeps the mean in expectation.  The value of a W-bit code is taken as v / 2^s: in full range 65535 >> 6 is 1023, and 2^16
+ * does not map onto 2^10 - 1 exactly; that is the definition, not a defect.
+ * For a U16 source the reference converts at the source's depth and shifts: the conversion with dst_bit_depth = W followed by
+ * mode 0 to D (gbr 0) is byte for byte the conversion with dst_bit_depth = D.  For float and half sources no such identity holds
+ * (at 16 bits the matrix's +0.5 rounds before the floor): there the definition is "the frame converted at 16 bits, then reduced". */
+#define H2Y_DITHER_FRAMES_PER_LAUNCH 64
+
+/* t of every sample of one plane, t[y x width + x].  Host only: no device, no context; the CPU-testable twin of k_dither.
+ * H2Y_EINVAL for a mode outside 0..2, a shift outside 1..8, temporal not 0 / 1, a plane outside 0..2, sizes below 1, a null t. */
+int h2y_dither_offsets(int mode, int shift, int temporal, uint32_t seed, uint32_t frame, int plane, int width, int height, uint16_t *t);
+
+/* k_dither on n_frames device frames in h2y_scale_batch's layout (three planes one after the other from a 16-byte aligned base):
+ * d_dst[f] receives d_src[f] reduced from src_depth to dst_depth as frame number first_frame + f; d_dst[f] may be d_src[f] (in
+ * place; no other overlap).  Launches of up to H2Y_DITHER_FRAMES_PER_LAUNCH frames (h2y_last_kernel_ms sums them,
+ * h2y_last_kernel_name "k_dither", the variant "k_dither<ordered>", "<noise>" or "<cut>"); synchronous.  H2Y_EUNSUPPORTED for
+ * 4:2:2; H2Y_EINVAL for depths outside 8 <= dst < src <= 16 or more than 8 bits apart, odd 4:2:0 sizes, sizes below 1 or of 2^28
+ * pixels and more, null or misaligned frames, while a batch is pending or a stream open. */
+int h2y_dither_batch(h2y_ctx *ctx, int width, int height, int chroma_format_idc, int src_depth, int dst_depth, int full_range, int gbr,
+                     int mode, int temporal, uint32_t seed, uint32_t first_frame, int n_frames, const uint16_t *const *d_src,
+                     uint16_t *const *d_dst);
+
+/* Arm an open forward ring (plain, DPX, TIFF, EXR, PQ code) before its first input: after a slot's conversion -- and after
+ * k_scale on a ring armed with h2y_stream_scale before this call, at the scaled size -- k_dither reduces the frame that would go
+ * down, from the descriptor's dst_bit_depth to dst_depth with the YCbCr limits (gbr 0), into a frame of its own, which goes down
+ * and is what h2y_stream_output returns.  The k-th submitted frame has number first_frame + k.  H2Y_EUNSUPPORTED on a ring armed
+ * with h2y_stream_compare / _histogram / _ssim / _deltae, as is arming any of those afterwards (they would see the undithered
+ * frame), and on dst_matrix_coeffs 15; H2Y_EINVAL on every other kind of ring, after the first input, on a ring armed already, and
+ * for h2y_stream_scale after this call. */
+int h2y_stream_dither(h2y_ctx *ctx, int dst_depth, int mode, int temporal, uint32_t seed, uint32_t first_frame);
+
+/* A dither-only ring: no conversion.  h2y_stream_input lends the frame's three planes one after the other, h2y_stream_output
+ * returns the reduced frame. */
+int h2y_dither_stream_open(h2y_ctx *ctx, int width, int height, int chroma_format_idc, int src_depth, int dst_depth, int full_range, int gbr,
+                           int mode, int temporal, uint32_t seed, uint32_t first_frame, int depth /* 2..16 slots */);
+
 /* ---- conversion between colour primaries, in linear light, before the forward conversion (--gamut_convert 1) ---------------------
  * The reference parses --src_colour_primaries / --dst_colour_primaries and never converts between them: matrix_to_primaries() is an
  * empty function (convert.cpp:1991), and the two values only choose between the identity and the colour-difference branch of
@@ -1176,7 +1235,7 @@ int h2y_upsample_444_sited(h2y_ctx *ctx, int width, int height, int chroma_sampl
                            const uint16_t *d_src, uint16_t *d_dst);
 
 /* Timing of the last h2y_convert_batch*() (or h2y_inverse_*, h2y_dpx_decode_batch, h2y_tiff_decode_batch,
- * h2y_rgb_interleave_batch, h2y_exr_decode_batch, h2y_compare_batch, h2y_ssim_batch, h2y_light_batch, h2y_lightdist_batch, h2y_codelight_batch, h2y_scenesig_batch, h2y_codescenesig_batch, h2y_linearize_batch, h2y_scale_batch, h2y_gamut_batch) call measured with HIP events on
+ * h2y_rgb_interleave_batch, h2y_exr_decode_batch, h2y_compare_batch, h2y_ssim_batch, h2y_light_batch, h2y_lightdist_batch, h2y_codelight_batch, h2y_scenesig_batch, h2y_codescenesig_batch, h2y_linearize_batch, h2y_scale_batch, h2y_gamut_batch, h2y_dither_batch) call measured with HIP events on
  * the stream the kernels ran on: total ms over the main kernels and how many
  * launches that covered. */
 int h2y_last_kernel_ms(const h2y_ctx *ctx, float *ms, int *launches);
@@ -1184,7 +1243,7 @@ int h2y_last_kernel_ms(const h2y_ctx *ctx, float *ms, int *launches);
 /* Name of the kernel those launches ran ("k_fused", "k_fused_t1", "k_fused_lut16",
  * "k_fused_narrow"; of the inverse entries "k_inverse", "k_inverse420", "k_inverse_batch", "k_inverse420_batch"; of
  * h2y_dpx_decode_batch "k_dpx_decode"; of h2y_tiff_decode_batch "k_tiff_decode", of h2y_rgb_interleave_batch
- * "k_rgb_interleave"; of h2y_exr_decode_batch "k_exr_decode"; of h2y_compare_batch "k_compare"; of h2y_scale_batch "k_scale"; of h2y_gamut_batch "k_gamut"; of h2y_codelight_batch "k_codelight"; of h2y_scenesig_batch "k_scenesig"; of h2y_codescenesig_batch "k_codescenesig"; of h2y_linearize_batch "k_linearize"): the name to
+ * "k_rgb_interleave"; of h2y_exr_decode_batch "k_exr_decode"; of h2y_compare_batch "k_compare"; of h2y_scale_batch "k_scale"; of h2y_dither_batch "k_dither"; of h2y_gamut_batch "k_gamut"; of h2y_codelight_batch "k_codelight"; of h2y_scenesig_batch "k_scenesig"; of h2y_codescenesig_batch "k_codescenesig"; of h2y_linearize_batch "k_linearize"): the name to
  * look for in a rocprofv3 kernel trace. */
 const char *h2y_last_kernel_name(const h2y_ctx *ctx);
 /* The same with its template arguments and launch shape, e.g. "k_fused_t1<F32,420BOX,YCBCR,PQ_IDENT> groups=8 xcd=1";

@@ -166,6 +166,19 @@ Prints one line per figure, then one JSON line with all of them.
      k_gamut's rate (18 / 24 of k_gamut's time);
   2. frames/s from host memory to PQ BT.2020nc 10-bit 4:2:0 of the PQ code ring (h2y_pqcode_stream_open, 10-bit 4:2:0 frames of
      24.9 MB) beside the .f32 ring fed the linearised planes (99.5 MB a frame), both with the 0 / 1 override, three times in turn.
+Prints one line per figure, then one JSON line with all of them.
+
+`streambench.py dither`: the reduction to the output bit depth (k_dither) on 4K frames, beside its yardsticks in the same job:
+  1. the kernel time of h2y_dither_batch over 64 distinct device frames per call (HIP events, median of five after a warm-up call,
+     out of place): 16 -> 10 4:2:0 ordered, 16 -> 10 4:2:0 noise, 16 -> 8 4:2:0 ordered and 16 -> 10 4:4:4 ordered; the 4 bytes a
+     sample it moves over that time and their share of the 8 TB/s HBM peak;
+  2. the yardsticks, timed the same way: h2y_compare_batch (k_compare, two 4:2:0 frames read: the same 4 bytes a sample) and
+     h2y_tiff_decode_batch (k_tiff_decode, 12 B/pixel) -- plain u16 streaming passes that this change does not touch;
+  3. h2y_convert_batch of 64 device-resident C2 frames (fp32 -> PQ -> BT.2020nc 4:2:0, FIR) at 10 bits against the same at 16 bits
+     followed by h2y_dither_batch to 10 in place: wall time of the calls, five of each taken in turn after a warm-up, and the
+     kernel variant each conversion ran;
+  4. frames/s from host memory of the .f32 ring (16-bit destination), unarmed and armed with h2y_stream_dither to 10 bits, and the
+     unarmed ring with a 10-bit destination, three runs of each in turn.
 Prints one line per figure, then one JSON line with all of them."""
 import os
 import sys
@@ -1703,6 +1716,148 @@ def scale_main():
     print(json.dumps({"streambench_scale": res}), flush=True)
 
 
+def dither_main():
+    import json
+
+    import torch
+
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    from tiff_files import write_tiff
+
+    w, hh, nb, reps = 3840, 2160, 64, 5
+    n, nc = w * hh, (w // 2) * (hh // 2)
+    nf = int(os.environ.get("N", "60"))
+    depth = 3
+    rng = np.random.default_rng(31)
+    ctx = h.Context(0)
+    res = {"width": w, "height": hh, "frames_per_call": nb, "reps": reps, "ring_frames": nf, "ring_depth": depth, "hbm_peak_tbs": 8.0}
+
+    def timed(key, label, nbytes, call):
+        ks = []
+        for r in range(reps + 1):  # the first call warms up
+            call()
+            if r:
+                ks.append(ctx.last_kernel_ms()[0] / nb)
+        k_ms = float(np.median(ks))
+        tbs = nbytes / (k_ms * 1e-3) / 1e12
+        res[key] = dict(kernel_us_per_frame=round(k_ms * 1e3, 2), min_us=round(min(ks) * 1e3, 2), max_us=round(max(ks) * 1e3, 2),
+                        bytes_per_frame=nbytes, kernel_tbs=round(tbs, 2), hbm_peak_fraction=round(tbs / 8.0, 3), variant=ctx.last_kernel_variant())
+        print(f"{label:34s} {nb} frames per call: {k_ms*1e3:7.2f} us/frame ({min(ks)*1e3:.2f}..{max(ks)*1e3:.2f})  {nbytes/1e6:6.1f} MB/frame  "
+              f"{tbs:5.2f} TB/s = {tbs/8.0*100:4.1f} % of 8 TB/s", flush=True)
+
+    # 1. k_dither over 64 distinct frames on the device
+    for key, chroma, D, mode in (("k_dither_16_10_420_ordered", h.CHROMA_420, 10, 1), ("k_dither_16_10_420_noise", h.CHROMA_420, 10, 2),
+                                 ("k_dither_16_8_420_ordered", h.CHROMA_420, 8, 1), ("k_dither_16_10_444_ordered", h.CHROMA_444, 10, 1)):
+        words = n + 2 * (nc if chroma == h.CHROMA_420 else n)
+        src = [torch.randint(-32768, 32768, (words,), dtype=torch.int16, device="cuda") for _ in range(nb)]
+        dst = [torch.empty(words, dtype=torch.int16, device="cuda") for _ in range(nb)]
+        torch.cuda.synchronize()
+        timed(key, key.replace("_", " ", 1), 4 * words, lambda: ctx.dither_batch(w, hh, chroma, 16, D, 0, 0, mode, 1, 0, 0, src, dst))
+        if key == "k_dither_16_10_420_ordered":
+            timed(key + "_in_place", "k dither 16_10_420_ordered in place", 4 * words, lambda: ctx.dither_batch(w, hh, chroma, 16, D, 0, 0, mode, 1, 0, 0, src))
+        del src, dst
+        torch.cuda.empty_cache()
+
+    # 2. the yardsticks
+    total = n + 2 * nc
+    a = [torch.randint(0, 1024, (total,), dtype=torch.int16, device="cuda") for _ in range(nb)]
+    b = [x + torch.randint(-2, 3, (total,), dtype=torch.int16, device="cuda") for x in a]
+    torch.cuda.synchronize()
+    timed("k_compare", "k_compare 4:2:0", 4 * total, lambda: ctx.compare_batch(w, hh, h.CHROMA_420, 0, a, b))
+    del a, b
+    torch.cuda.empty_cache()
+    tdata = write_tiff(rng.integers(0, 65536, (hh, w, 3), dtype=np.uint16))
+    tinfo, rows = h.parse_tiff(tdata)
+    tpay = np.frombuffer(b"".join(tdata[int(o):int(o) + int(tinfo.row_bytes)] for o in rows), np.uint8)
+    pays = [torch.from_numpy(tpay.copy()).cuda() for _ in range(nb)]
+    outs = [[torch.empty(n, dtype=torch.int16, device="cuda") for _ in range(3)] for _ in range(nb)]
+    torch.cuda.synchronize()
+    timed("k_tiff_decode", "k_tiff_decode", 12 * n, lambda: ctx.tiff_decode_batch(tinfo, 0, pays, outs))
+    del pays, outs
+    torch.cuda.empty_cache()
+    for k in ("k_dither_16_10_420_ordered", "k_dither_16_10_420_noise", "k_dither_16_8_420_ordered", "k_dither_16_10_444_ordered"):
+        res[k]["of_k_compare_rate"] = round(res[k]["kernel_tbs"] / res["k_compare"]["kernel_tbs"], 3)
+
+    # 3. the conversion at 10 bits against the conversion at 16 bits and the reduction, on device-resident frames
+    d10 = h.make_desc(w, hh, dst_depth=10, dst_matrix=h.MATRIX_BT2020NC, resampler=1)
+    d16 = h.make_desc(w, hh, dst_depth=16, dst_matrix=h.MATRIX_BT2020NC, resampler=1)
+    frames = [[torch.rand(n, device="cuda") for _ in range(3)] for _ in range(nb)]
+    for fr in frames:
+        for pl in fr:
+            pl[0], pl[1] = 0.0, 1.0  # floor 0, ceiling 1
+    outs = [torch.empty(total, dtype=torch.int16, device="cuda") for _ in range(nb)]
+    torch.cuda.synchronize()
+    variants = {}
+
+    def conv10():
+        t0 = time.perf_counter()
+        ctx.convert_batch(d10, frames, outs)  # synchronous: every frame final on return
+        variants["convert_10"] = ctx.last_kernel_variant()
+        return (time.perf_counter() - t0) * 1e6 / nb
+
+    def conv16_dither():
+        t0 = time.perf_counter()
+        ctx.convert_batch(d16, frames, outs)
+        variants["convert_16"] = ctx.last_kernel_variant()
+        t1 = time.perf_counter()
+        ctx.dither_batch(w, hh, h.CHROMA_420, 16, 10, 0, 0, 1, 0, 0, 0, outs)
+        return (time.perf_counter() - t0) * 1e6 / nb, (t1 - t0) * 1e6 / nb
+
+    conv10(), conv16_dither()  # warm-up
+    t10, t16, t16c = [], [], []
+    for _ in range(reps):
+        t10.append(conv10())
+        both, conv = conv16_dither()
+        t16.append(both)
+        t16c.append(conv)
+    m10, m16, m16c = float(np.median(t10)), float(np.median(t16)), float(np.median(t16c))
+    res["convert_batch_c2_fir"] = dict(at_10_us_per_frame=round(m10, 2), at_10_min=round(min(t10), 2), at_10_max=round(max(t10), 2),
+                                       at_16_plus_dither_us_per_frame=round(m16, 2), at_16_plus_dither_min=round(min(t16), 2),
+                                       at_16_plus_dither_max=round(max(t16), 2), at_16_conversion_alone_us_per_frame=round(m16c, 2),
+                                       ratio=round(m16 / m10, 3), **variants)
+    print(f"h2y_convert_batch C2 FIR, wall: 10-bit {m10:7.2f} us/frame ({min(t10):.2f}..{max(t10):.2f}) [{variants['convert_10']}]", flush=True)
+    print(f"  16-bit + h2y_dither_batch to 10: {m16:7.2f} us/frame ({min(t16):.2f}..{max(t16):.2f}), the conversion alone {m16c:7.2f} "
+          f"[{variants['convert_16']}]  ratio {m16/m10:.3f}", flush=True)
+    del frames, outs
+    torch.cuda.empty_cache()
+
+    # 4. the .f32 ring from host memory
+    planes = [rng.random(n, dtype=np.float32) for _ in range(3)]
+
+    def ring(d, arm):
+        ctx.stream_open(d, depth)
+        if arm:
+            ctx.stream_dither(10, 1, 0, 0, 0)
+        inflight = 0
+        t0 = time.perf_counter()
+        for _ in range(nf):
+            slot = ctx.stream_input()
+            for c in range(3):
+                slot[c][:] = planes[c]
+            ctx.stream_submit()
+            inflight += 1
+            if inflight == depth - 1:
+                ctx.stream_output()
+                inflight -= 1
+        while inflight:
+            ctx.stream_output()
+            inflight -= 1
+        dt = (time.perf_counter() - t0) / nf
+        ctx.stream_close()
+        return dt
+
+    ring(d16, False)  # warm-up
+    runs = {"unarmed_16": [], "armed_16_to_10": [], "unarmed_10": []}
+    for _ in range(3):
+        runs["unarmed_16"].append(ring(d16, False))
+        runs["armed_16_to_10"].append(ring(d16, True))
+        runs["unarmed_10"].append(ring(d10, False))
+    res["f32_ring"] = {k: dict(fps=round(1 / float(np.median(v)), 1), ms=[round(x * 1e3, 2) for x in v]) for k, v in runs.items()}
+    print("f32 ring from host memory: " + "   ".join(f"{k} {1/float(np.median(v)):6.1f} frames/s" for k, v in runs.items()), flush=True)
+    ctx.close()
+    print(json.dumps({"streambench_dither": res}), flush=True)
+
+
 def gamut_main():
     import json
 
@@ -1985,6 +2140,8 @@ if __name__ == "__main__":
         tonemap_main()
     elif sys.argv[1:] == ["scale"]:
         scale_main()
+    elif sys.argv[1:] == ["dither"]:
+        dither_main()
     elif sys.argv[1:] == ["inverse"]:
         inverse_main()
     elif sys.argv[1:] == ["dpx"]:
