@@ -47,6 +47,7 @@ EXPORTS = [
     "h2y_dither_offsets", "h2y_dither_batch", "h2y_stream_dither", "h2y_dither_stream_open",
     "h2y_gamut_matrix", "h2y_gamut_batch", "h2y_stream_gamut",
     "h2y_tonemap_curve", "h2y_tonemap_batch", "h2y_stream_tonemap",
+    "h2y_hlg_tables", "h2y_hlg_planes", "h2y_hlg_batch", "h2y_stream_hlg",
     "h2y_ctx_set_chroma_siting", "h2y_subsample_420_sited",
     "h2y_ctx_set_inverse_chroma_siting", "h2y_upsample_444_sited",
 ]
@@ -67,6 +68,8 @@ DELTAE_FRAMES_PER_LAUNCH = 4  # the same scratch again: four upsampled chroma pl
 SCALE_FRAMES_PER_LAUNCH = 64
 GAMUT_FRAMES_PER_LAUNCH = 64
 TONEMAP_FRAMES_PER_LAUNCH = 64
+HLG_FRAMES_PER_LAUNCH = 64
+HLG_PEAK_MIN, HLG_PEAK_MAX = 400, 2000
 SCALE_TAPS = 32  # coefficients per row of scale_taps' table
 DITHER_FRAMES_PER_LAUNCH = 64
 DITHER_CUT, DITHER_ORDERED, DITHER_NOISE = 0, 1, 2
@@ -557,6 +560,14 @@ def load_library():
     L.h2y_tonemap_curve.restype = C.c_int
     L.h2y_tonemap_batch.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.h2y_tonemap_batch.restype = C.c_int
+    L.h2y_hlg_tables.argtypes = [C.c_int] * 2 + [C.POINTER(C.c_float)] * 3 + [C.POINTER(C.c_double), C.POINTER(C.c_char_p)]
+    L.h2y_hlg_tables.restype = C.c_int
+    L.h2y_hlg_planes.argtypes = [C.c_int] * 6 + [C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.h2y_hlg_planes.restype = C.c_int
+    L.h2y_hlg_batch.argtypes = [C.c_void_p] + [C.c_int] * 9 + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.h2y_hlg_batch.restype = C.c_int
+    L.h2y_stream_hlg.argtypes = [C.c_void_p] + [C.c_int] * 2
+    L.h2y_stream_hlg.restype = C.c_int
     L.h2y_stream_tonemap.argtypes = [C.c_void_p] + [C.c_int] * 3
     L.h2y_stream_tonemap.restype = C.c_int
     L.h2y_stream_open.argtypes = [C.c_void_p, C.POINTER(H2YDesc), C.c_int]
@@ -791,6 +802,39 @@ def tonemap_curve(src_peak: int, dst_peak: int, relative: int):
     if rc != H2Y_OK:
         raise H2YError(rc, (why.value or b"").decode())
     return gain, np.float32(cap.value)
+
+
+def hlg_tables(peak: int, relative: int):
+    """h2y_hlg_tables (host only, no device): (gain, oetf, k, gamma) -- the two float32 tables of LIGHTDIST_BINS entries of the HLG pass
+    at a nominal peak of `peak` cd/m2 (the inverse OOTF's gain, the OETF), the float32 factor k that brings a sample to units of the
+    peak, and the system gamma as a float.  Raises H2YError (EINVAL: peak outside 400..2000, relative not 0 / 1)."""
+    gain = np.zeros(LIGHTDIST_BINS, dtype=np.float32)
+    oetf = np.zeros(LIGHTDIST_BINS, dtype=np.float32)
+    k, gamma, why = C.c_float(), C.c_double(), C.c_char_p()
+    fp = C.POINTER(C.c_float)
+    rc = load_library().h2y_hlg_tables(int(peak), int(relative), gain.ctypes.data_as(fp), oetf.ctypes.data_as(fp), C.byref(k),
+                                       C.byref(gamma), C.byref(why))
+    if rc != H2Y_OK:
+        raise H2YError(rc, (why.value or b"").decode())
+    return gain, oetf, np.float32(k.value), float(gamma.value)
+
+
+def hlg_planes(planes, peak: int, relative: int, dst_bit_depth: int, dst_full_range: int, dst_matrix: int):
+    """h2y_hlg_planes (host only, no device): the HLG pass on three numpy planes G, B, R of float32 or float16 display light; returns
+    the three float32 planes of code-valued samples k_hlg writes for them.  Raises H2YError as the library refuses."""
+    src = [np.ascontiguousarray(p) for p in planes]
+    dt = src[0].dtype
+    if len(src) != 3 or dt not in (np.float32, np.float16) or any(p.dtype != dt or p.shape != src[0].shape for p in src):
+        raise ValueError("three planes of one shape, float32 or float16")
+    out = [np.empty(p.shape, np.float32) for p in src]
+    ins = (C.c_void_p * 3)(*[p.ctypes.data for p in src])
+    outs = (C.c_void_p * 3)(*[p.ctypes.data for p in out])
+    lib = load_library()
+    rc = lib.h2y_hlg_planes(int(peak), int(relative), int(dst_bit_depth), int(dst_full_range), int(dst_matrix),
+                            SAMPLE_F16 if dt == np.float16 else SAMPLE_F32, src[0].size, ins, outs)
+    if rc != H2Y_OK:
+        raise H2YError(rc, (lib.h2y_last_error(None) or b"").decode())
+    return out
 
 
 def scale_frame_bytes(width: int, height: int, chroma: int) -> int:
@@ -1204,7 +1248,31 @@ class Context:
                 outs[3 * f + c] = self._ptr(frames_dst[f][c])
         self._check(self.lib.h2y_tonemap_batch(self.h, width, height, sample, src_peak, dst_peak, relative, n, ins, outs))
 
+    def hlg_batch(self, width, height, sample, peak, relative, dst_bit_depth, dst_full_range, dst_matrix, frames_src,
+                  frames_dst=None) -> None:
+        """k_hlg on device frames (frames_src[f] = three device planes G, B, R of float or half display light, 16-byte aligned):
+        frames_dst[f] receives the float planes of code-valued HLG samples at a nominal peak of `peak` cd/m2, scaled as a conversion
+        to (dst_bit_depth, dst_full_range, dst_matrix) scales; frames_dst None: in place (float planes only)."""
+        frames_dst = frames_src if frames_dst is None else frames_dst
+        n = len(frames_src)
+        if len(frames_dst) != n:
+            raise ValueError("frames_src and frames_dst differ in length")
+        ins = (C.c_void_p * max(3 * n, 1))()
+        outs = (C.c_void_p * max(3 * n, 1))()
+        for f in range(n):
+            for c in range(3):
+                ins[3 * f + c] = self._ptr(frames_src[f][c])
+                outs[3 * f + c] = self._ptr(frames_dst[f][c])
+        self._check(self.lib.h2y_hlg_batch(self.h, width, height, sample, peak, relative, dst_bit_depth, dst_full_range, dst_matrix, n,
+                                           ins, outs))
+
     # ---- host <-> device pipeline -----------------------------------------------------------
+    def stream_hlg(self, peak, relative) -> None:
+        """Arm an open forward ring of float planes (plain F32, DPX or PQ code) that was opened with src_transfer == dst_transfer == 8
+        and the 0 / 1 statistics override: every slot's decoded planes become code-valued HLG samples in place, after stream_gamut's
+        and stream_tonemap's passes, before the conversion (h2y_stream_hlg)."""
+        self._check(self.lib.h2y_stream_hlg(self.h, peak, relative))
+
     def stream_tonemap(self, src_peak, dst_peak, relative) -> None:
         """Arm an open forward ring of float or half planes (plain, DPX or EXR) that was opened with the 0 / 1 statistics override:
         every slot's decoded planes are tone-mapped in place, after stream_gamut's pass, before the conversion (h2y_stream_tonemap)."""

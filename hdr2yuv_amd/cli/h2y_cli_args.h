@@ -99,6 +99,22 @@
  *             the G,B,R limits for a .rgb, numbers the frames from --src_start_frame on as 0, 1, ... and works for any --gpus.  It
  *             prints dither_only: 1 and the four lines above.  Refused as above, and for a source that is not .yuv / .rgb, differing
  *             extensions, and a destination size other than the source's.
+ * --hlg 1 [--hlg_peak L] (an addition; the reference's transfer list ends at TRANSFER_RHO_GAMMA, its code 18, which in H.273 is HLG): the
+ *             forward flow writes a Hybrid Log-Gamma rung (ARIB STD-B67 / BT.2100, non-constant luminance).  The decoded source
+ *             planes, display light in BT.2020 primaries after --gamut_convert's and --tone_map's passes where those are given, go
+ *             through BT.2100's inverse OOTF at a nominal peak of L cd/m2 and its OETF on the device (include/hdr2yuv_hip.h, "HLG",
+ *             states every step), and the unchanged forward conversion takes it from the matrix on.  L is --tone_map_dst_peak beside
+ *             --tone_map 1, else 1000; beside --tone_map 1 the planes are taken as display-referred (1.0 = L), without it 1.0 is
+ *             10000 cd/m2.  The flag replaces the destination transfer: the run's becomes the source's 8 with floor 0 and ceiling 1,
+ *             and --dst_transfer_characteristics beside it is refused whatever its value (18 is RHO_GAMMA in this program).  From
+ *             .f32 and .dpx, and with --linearize 1 from a PQ .yuv / .rgb; beside --tone_map, --gamut_convert, --scale,
+ *             --dst_chroma_sample_loc_type 2, --dither, --ref_filename, --ssim and --histogram, for any --gpus, with or without
+ *             --dst_filename.  The banner carries hlg:, hlg_peak:, hlg_gamma:, hlg_input:, hlg_note: and hlg_encoder:.  Refused (exit
+ *             1, also under --dry_run): a value other than 0 or 1, --hlg_peak without --hlg 1 or outside 400..2000 or other than
+ *             --tone_map_dst_peak, .f16, .exr, .tiff, .rgb and .yuv input, a source transfer other than 8 or matrix other than 0,
+ *             primaries other than 8 / 9 at the pass, --dst_matrix_coeffs other than 0 / 9 (and 0 with primaries codes that
+ *             differ: the library refuses that descriptor as the reference does, convert.cpp:1195), .rgb / .tiff destinations and the .yuv ->
+ *             RGB flow, every *_only flow, --content_light, --dynamic_metadata and the scene flags (their light is PQ's), --delta_e.
  * --gamut_convert 1 [--gamut_clip 0|1] (an addition; the reference's matrix_to_primaries() is empty, convert.cpp:1991, and the two
  *             colour_primaries values only pick a branch of matrix_convert()): the decoded source planes are converted on the device
  *             from --src_colour_primaries to --dst_colour_primaries, in linear light, before the unchanged forward conversion
@@ -239,6 +255,11 @@ struct cli_args {
      * the output is display-referred (1.0 = tone_dst_peak) for every destination transfer but PQ */
     int tone_map = 0, tone_src_peak = 1000, tone_dst_peak = 100, tone_relative = 1;
     bool tone_map_given = false, tone_src_peak_given = false, tone_dst_peak_given = false;
+    /* --hlg 1 [--hlg_peak L]: the rung is HLG at a nominal peak of hlg_peak cd/m2; resolved: hlg_relative (the planes are
+     * display-referred, after --tone_map 1) and hlg_dst_transfer, what --dst_transfer_characteristics gave before the flag replaced
+     * it (-1: not given) */
+    int hlg = 0, hlg_peak = 1000, hlg_relative = 0, hlg_dst_transfer = -1;
+    bool hlg_given = false, hlg_peak_given = false;
     /* --dst_chroma_sample_loc_type: 0 as the resampler sites the 4:2:0 chroma, 2 top-left */
     int siting = 0;
     bool siting_given = false;
@@ -355,6 +376,9 @@ static inline void cli_help()
            "  tone mapping: [--tone_map 1 [--tone_map_src_peak S] [--tone_map_dst_peak D]] (float or half G,B,R source planes in linear\n"
            "  light brought from a mastering peak of S cd/m2, 1000 by default, down to D, 100 by default, on the GPU by the BT.2390\n"
            "  curve on max(R,G,B) before the conversion: the SDR rung of an HDR master, or a 1000 cd/m2 PQ rung of a 4000 cd/m2 one)\n"
+           "  HLG: [--hlg 1 [--hlg_peak L]] (the rung is Hybrid Log-Gamma, ARIB STD-B67 / BT.2100: float G,B,R source planes of display light\n"
+           "  in BT.2020 primaries through the inverse OOTF at a nominal peak of L cd/m2, 400..2000, 1000 by default, and the OETF on the\n"
+           "  GPU; it replaces --dst_transfer_characteristics, whose 18 is RHO_GAMMA in this program, not H.273's HLG)\n"
            "  chroma siting: [--dst_chroma_sample_loc_type 0|2] (2: 4:2:0 chroma co-sited with the top-left luma sample, as HDR10\n"
            "  assumes -- x265 --chromaloc 2, SVT-AV1 --chroma-sample-position topleft; needs the FIR resampler; 0: as without the flag)\n"
            "  [--src_chroma_sample_loc_type 0|2] (.yuv -> .rgb / .tiff with --src_chroma_format_idc 1; 2: the 4:2:0 chroma is co-sited\n"
@@ -408,6 +432,8 @@ static inline void cli_parse(cli_args &a, int argc, char **argv)
         else if (is("--tone_map")) { a.tone_map = atoi(val()); a.tone_map_given = true; }
         else if (is("--tone_map_src_peak")) { a.tone_src_peak = atoi(val()); a.tone_src_peak_given = true; }
         else if (is("--tone_map_dst_peak")) { a.tone_dst_peak = atoi(val()); a.tone_dst_peak_given = true; }
+        else if (is("--hlg")) { a.hlg = atoi(val()); a.hlg_given = true; }
+        else if (is("--hlg_peak")) { a.hlg_peak = atoi(val()); a.hlg_peak_given = true; }
         else if (is("--dst_chroma_sample_loc_type")) { a.siting = atoi(val()); a.siting_given = true; }
         else if (is("--src_chroma_sample_loc_type")) { a.src_siting = atoi(val()); a.src_siting_given = true; }
         else if (is("--histogram")) a.hist = val();
@@ -593,6 +619,7 @@ static inline int cli_resolve_scale_only(cli_args &a);
 static inline int cli_resolve_scale(cli_args &a);
 static inline int cli_resolve_gamut(cli_args &a, int src_matrix_arg);
 static inline int cli_resolve_tone_map(cli_args &a, int src_matrix_arg);
+static inline int cli_resolve_hlg(cli_args &a, int src_matrix_arg);
 static inline int cli_resolve_siting(cli_args &a);
 static inline int cli_resolve_src_siting(cli_args &a);
 static inline int cli_resolve_light_only(cli_args &a);
@@ -607,6 +634,10 @@ static inline int cli_resolve(cli_args &a)
     const bool dither_flags = a.dither_given || a.dither_temporal_given || a.dither_seed_given || a.dither_only_given;
     /* first, and without a line of its own yet: every later resolver sees a conversion at the working depth */
     if (dither_flags && cli_resolve_dither(a)) return 1;
+    if ((a.hlg_given || a.hlg_peak_given) && a.dither_only == 1) {
+        printf("hlg: %d\nWARNING: --hlg writes a conversion's rung: not with --dither_only 1\n", a.hlg);
+        return 1;
+    }
     const int arg_errors = a.dither_only == 1 ? cli_resolve_dither_only(a) : cli_resolve_all(a);
     if (arg_errors || !a.dithers()) return arg_errors;
     printf("dither: %d (%s)\ndither_depth: %d -> %d\ndither_temporal: %d\ndither_seed: %u\n", a.dither, a.dither == 1 ? "ordered" : "noise",
@@ -616,6 +647,10 @@ static inline int cli_resolve(cli_args &a)
 
 static inline int cli_resolve_all(cli_args &a)
 {
+    if (a.hlg == 1) { /* before anything resolves the destination: the flag is its transfer, and the run's becomes the source's 8 */
+        a.hlg_dst_transfer = a.out.transfer_characteristics;
+        a.out.transfer_characteristics = H2Y_TRANSFER_LINEAR;
+    }
     if (a.linearize_given) { /* first: what follows resolves the linearised source */
         printf("linearize: %d\n", a.linearize);
         if (a.linearize != 0 && a.linearize != 1) {
@@ -628,6 +663,10 @@ static inline int cli_resolve_all(cli_args &a)
         printf("light_only: %d\n", a.light_only);
         if (a.light_only != 0 && a.light_only != 1) {
             printf("WARNING: light_only(%d) not 0 or 1\n", a.light_only);
+            return 1;
+        }
+        if (a.light_only && (a.hlg_given || a.hlg_peak_given)) {
+            printf("hlg: %d\nWARNING: --hlg writes a conversion's rung: not with --light_only 1\n", a.hlg);
             return 1;
         }
         if (a.light_only) {
@@ -649,6 +688,7 @@ static inline int cli_resolve_all(cli_args &a)
     if (a.scale_given || a.scale_only || a.scale_taps_given) arg_errors += cli_resolve_scale(a);
     if (a.gamut_given || a.gamut_clip_given) arg_errors += cli_resolve_gamut(a, src_matrix_arg);
     if (a.tone_map_given || a.tone_src_peak_given || a.tone_dst_peak_given) arg_errors += cli_resolve_tone_map(a, src_matrix_arg);
+    if (a.hlg_given || a.hlg_peak_given) arg_errors += cli_resolve_hlg(a, src_matrix_arg);
     if (a.siting_given) arg_errors += cli_resolve_siting(a);
     const bool de_flags = a.delta_e_given || a.delta_e_threshold_given || a.delta_e_limit_given;
     /* (--linearize 1 resolved its own; under --compare_only 1 --delta_e 1 the flag chooses Delta E's upsampler, checked there) */
@@ -1310,7 +1350,7 @@ static inline int cli_resolve_tone_map(cli_args &a, int src_matrix_arg)
         printf("WARNING: --tone_map 1 needs a G,B,R source: src_matrix_coeffs(%d) is not %d\n", src_matrix_arg, H2Y_MATRIX_GBR);
         return 1;
     }
-    if (a.out.transfer_characteristics == H2Y_TRANSFER_LINEAR) {
+    if (a.out.transfer_characteristics == H2Y_TRANSFER_LINEAR && a.hlg != 1) { /* (--hlg 1 is the display's transfer) */
         printf("WARNING: --tone_map 1 maps light for a display: dst_transfer_characteristics(%d) keeps linear light\n",
                a.out.transfer_characteristics);
         return 1;
@@ -1325,6 +1365,106 @@ static inline int cli_resolve_tone_map(cli_args &a, int src_matrix_arg)
     }
     const double W = cli_pq_n(a.tone_src_peak / 10000.0), ks = 1.5 * (cli_pq_n(a.tone_dst_peak / 10000.0) / W) - 0.5;
     printf("tone_map_output: %s\ntone_map_knee: %.9g\n", a.tone_relative ? "relative" : "absolute", 10000.0 * cli_pq_n_inv(ks * W));
+    return 0;
+}
+
+/* --hlg / --hlg_peak: the forward flow's float G,B,R planes of display light in BT.2020 primaries, written as an HLG signal at a
+ * nominal peak the library's tables take (src_matrix_arg: --src_matrix_coeffs as given; cli_resolve_all replaced the destination
+ * transfer and kept what was given, cli_resolve_tone_map ran before); prints the peak, the system gamma, how the planes are
+ * referred, the note on code 18 and the encoder flags; returns the number of argument errors */
+static inline int cli_resolve_hlg(cli_args &a, int src_matrix_arg)
+{
+    printf("hlg: %d\n", a.hlg);
+    if (a.hlg != 0 && a.hlg != 1) {
+        printf("WARNING: hlg(%d) not 0 or 1\n", a.hlg);
+        return 1;
+    }
+    if (!a.hlg) {
+        if (a.hlg_peak_given) {
+            printf("WARNING: --hlg_peak needs --hlg 1\n");
+            return 1;
+        }
+        return 0;
+    }
+    if (a.tone_map == 1) {
+        if (a.hlg_peak_given && a.hlg_peak != a.tone_dst_peak) {
+            printf("WARNING: --hlg 1 beside --tone_map 1 writes the tone mapper's target: hlg_peak(%d) is not tone_map_dst_peak(%d)\n",
+                   a.hlg_peak, a.tone_dst_peak);
+            return 1;
+        }
+        if (!a.hlg_peak_given) a.hlg_peak = a.tone_dst_peak;
+    }
+    a.hlg_relative = a.tone_map == 1;
+    printf("hlg_peak: %d%s\n", a.hlg_peak, a.hlg_peak_given ? "" : " (default)");
+    int arg_errors = 0;
+    if (a.hlg_dst_transfer != -1) {
+        printf("WARNING: --hlg 1 is the destination's transfer: leave out --dst_transfer_characteristics (%d); 18 is RHO_GAMMA in this "
+               "program, H.273's 18 (HLG) is --hlg 1\n", a.hlg_dst_transfer);
+        arg_errors++;
+    }
+    if (a.compare_only || a.hist_only || a.scale_only) {
+        printf("WARNING: --hlg 1 writes a conversion's rung: not with --%s 1\n",
+               a.compare_only ? "compare_only" : a.hist_only ? "histogram_only" : "scale_only");
+        return arg_errors + 1;
+    }
+    if (a.inverse) {
+        printf("WARNING: --hlg 1 is the forward flow's (to .yuv), not the .yuv -> RGB flow's\n");
+        return arg_errors + 1;
+    }
+    if (a.out_type != CLI_OUT_YUV) {
+        printf("WARNING: --hlg 1 writes .yuv frames: not a .%s destination\n", cli_ext_of(a.dst ? a.dst : a.ref));
+        return arg_errors + 1;
+    }
+    if (a.in_type != CLI_IN_F32 && a.in_type != CLI_IN_DPX) {
+        printf("WARNING: --hlg 1 leaves code-valued samples in float planes (.f32 or .dpx input, or --linearize 1 from a PQ .yuv / .rgb), not "
+               ".%s input\n", a.in_type == CLI_IN_SYNTH ? "(synthetic)" : cli_ext_of(a.src));
+        return arg_errors + 1;
+    }
+    if (a.in.transfer_characteristics != H2Y_TRANSFER_LINEAR) {
+        printf("WARNING: --hlg 1 takes linear light: src_transfer_characteristics(%d) is not %d\n", a.in.transfer_characteristics,
+               H2Y_TRANSFER_LINEAR);
+        arg_errors++;
+    }
+    if (src_matrix_arg != H2Y_MATRIX_GBR) {
+        printf("WARNING: --hlg 1 needs a G,B,R source: src_matrix_coeffs(%d) is not %d\n", src_matrix_arg, H2Y_MATRIX_GBR);
+        arg_errors++;
+    }
+    const int sp = a.in.colour_primaries, dp = a.out.colour_primaries;
+    if ((dp != 8 && dp != 9) || (a.gamut != 1 && sp != dp)) {
+        printf("WARNING: --hlg 1 takes BT.2020 primaries: %s_colour_primaries(%d) is not 8 or 9%s\n", (dp != 8 && dp != 9) ? "dst" : "src",
+               (dp != 8 && dp != 9) ? dp : sp, a.gamut == 1 ? "" : " and the destination's (other primaries need --gamut_convert 1)");
+        arg_errors++;
+    }
+    const int m = a.out.matrix_coeffs;
+    if (m != H2Y_MATRIX_GBR && m != H2Y_MATRIX_BT2020NC) {
+        printf("WARNING: --hlg 1: dst_matrix_coeffs(%d) not %d (G,B,R) or %d (BT.2020nc)\n", m, H2Y_MATRIX_GBR, H2Y_MATRIX_BT2020NC);
+        arg_errors++;
+    } else if (m == H2Y_MATRIX_GBR && sp != dp) { /* convert.cpp:1159, :1195: no ring opens on such a descriptor; said here, before any device */
+        printf("WARNING: --hlg 1: dst_matrix_coeffs %d keeps G,B,R only where src_colour_primaries(%d) equals dst_colour_primaries(%d)\n", m,
+               sp, dp);
+        arg_errors++;
+    }
+    if (a.light || a.dynmeta || a.scene_detect_given || a.scene_threshold_given || a.scene_cuts || a.scene_qpfile) {
+        printf("WARNING: --hlg 1: --content_light, --dynamic_metadata and the scene flags measure PQ's light, not an HLG rung's\n");
+        arg_errors++;
+    }
+    if (a.delta_e_given || a.delta_e_threshold_given || a.delta_e_limit_given) {
+        printf("WARNING: --hlg 1: --delta_e judges PQ codes, not an HLG rung's\n");
+        arg_errors++;
+    }
+    std::vector<float> gain(H2Y_LIGHTDIST_BINS), oetf(H2Y_LIGHTDIST_BINS);
+    float k = 0.0f;
+    double gamma = 0.0;
+    const char *why = nullptr;
+    if (h2y_hlg_tables(a.hlg_peak, a.hlg_relative, gain.data(), oetf.data(), &k, &gamma, &why)) {
+        printf("WARNING: --hlg 1: hlg_peak(%d): %s\n", a.hlg_peak, why);
+        arg_errors++;
+    }
+    if (arg_errors) return arg_errors;
+    printf("hlg_gamma: %.9g\nhlg_input: %s\n", gamma, a.hlg_relative ? "relative" : "absolute");
+    printf("hlg_note: dst_transfer_characteristics 18 is RHO_GAMMA in this program; H.273's 18 (HLG) is --hlg 1\n");
+    printf("hlg_encoder: x265 --transfer arib-std-b67 --colorprim bt2020 --colormatrix %s; SvtAv1EncApp --transfer-characteristics 18 "
+           "--color-primaries 9 --matrix-coefficients %d\n", m == H2Y_MATRIX_GBR ? "gbr" : "bt2020nc", m);
     return 0;
 }
 
@@ -1714,8 +1854,9 @@ static inline void cli_make_desc(const cli_args &a, h2y_desc *d)
     d->dst_full_range = a.out.video_full_range_flag;
     d->dst_chroma_format_idc = a.out.chroma_format_idc;
     d->chroma_resampler_type = a.resampler;
-    if (a.tone_map || a.linearize == 1) { /* mapped planes are referred to their target, linearised ones lie in [0, 1] by definition: floor
-                                           * 0 and ceiling 1, not each frame's pic_stats */
+    if (a.tone_map || a.linearize == 1 || a.hlg == 1) { /* mapped planes are referred to their target, linearised ones lie in [0, 1] by
+                                                         * definition, HLG's are code-valued: floor 0 and ceiling 1, not each frame's
+                                                         * pic_stats */
         d->stats_override = 1;
         for (int c = 0; c < 3; c++) d->floor[c] = 0, d->ceiling[c] = 1;
     }

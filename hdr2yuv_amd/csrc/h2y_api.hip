@@ -285,6 +285,7 @@ void h2y_ctx_destroy(h2y_ctx *ctx)
     (void)hipFree(ctx->d_deltae);
     (void)hipFree(ctx->d_scale_tabs);
     (void)hipFree(ctx->d_tonemap_gain);
+    (void)hipFree(ctx->d_hlg_tables);
     (void)hipFree(ctx->d_in);
     (void)hipFree(ctx->d_out);
     if (ctx->fir_stream) {

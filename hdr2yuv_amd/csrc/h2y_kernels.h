@@ -448,6 +448,22 @@ struct tonemap_args {
 int h2y_tonemap_grid(int n_cu, uint64_t units); /* blocks for so many of k_gamut's units (h2y_gamut_chunks per frame) */
 hipError_t h2y_launch_tonemap(int in_kind, int grid, hipStream_t st, const tonemap_args &a, const gamut_frame *frames, int n_frames);
 
+/* k_hlg (h2y_hlg.hip): the HLG pass of include/hdr2yuv_hip.h on frames of three float or half planes G, B, R of display light,
+ * k_gamut's frame table; the destination planes are float (dst may be src for float planes: in place) */
+struct hlg_consts {
+    float k;                      /* 10000 / L_W rounded once, or 1 */
+    float mulY, addY, mulC, addC; /* the conversion's scale step (derive_params) */
+};
+struct hlg_args {
+    uint32_t npix;            /* pixels per frame (< 2^28) */
+    hlg_consts c;
+    const float *gain, *oetf; /* device: H2Y_LIGHTDIST_BINS entries each, h2y_hlg_tables' */
+};
+enum { H2Y_HLG_THREADS = 512 };
+uint32_t h2y_hlg_chunks(int in_kind, uint32_t npix); /* k_hlg's units of H2Y_HLG_THREADS threads per frame */
+int h2y_hlg_grid(int n_cu, uint64_t units);           /* blocks for so many units */
+hipError_t h2y_launch_hlg(int in_kind, int grid, hipStream_t st, const hlg_args &a, const gamut_frame *frames, int n_frames);
+
 /* k_scale (h2y_scale.hip): the Lanczos resampler of include/hdr2yuv_hip.h on frames of three u16 planes.  One axis' table on the
  * device: first[d] and count[d] (int32), then d rows of H2Y_SCALE_MAX_TAPS int16 coefficients (zero past count). */
 enum { H2Y_SCALE_MAX_TAPS = 32, H2Y_SCALE_TILE_W = 64, H2Y_SCALE_TILE_H = 32, H2Y_SCALE_STAGE_ROWS = 16 };

@@ -2297,6 +2297,197 @@ int h2y_stream_tonemap(h2y_ctx *ctx, int src_peak, int dst_peak, int relative)
     return stage_arm(ctx, STAGE_TONEMAP, std::move(st), "tone map");
 }
 
+/* ---- HLG (--hlg; the reference has no HLG transfer): include/hdr2yuv_hip.h states the definition ------------------------------------- */
+
+#include "h2y_hlg1.h"
+
+int h2y_hlg_tables(int peak, int relative, float gain[H2Y_LIGHTDIST_BINS], float oetf[H2Y_LIGHTDIST_BINS], float *k, double *gamma,
+                   const char **why)
+{
+    const char *dummy;
+    if (!why) why = &dummy;
+    *why = "";
+    if (!gain || !oetf || !k || !gamma) { *why = "null table, k or gamma"; return H2Y_EINVAL; }
+    if (peak < H2Y_HLG_PEAK_MIN || peak > H2Y_HLG_PEAK_MAX) { *why = "peak outside 400 <= peak <= 2000 cd/m2"; return H2Y_EINVAL; }
+    if (relative != 0 && relative != 1) { *why = "relative must be 0 or 1"; return H2Y_EINVAL; }
+    const double g = 1.2 + 0.42 * log10(peak / 1000.0), p = (1.0 - g) / g;
+    const double a = 0.17883277, b = 1.0 - 4.0 * a, c = 0.5 - a * log(4.0 * a);
+    for (uint32_t j = 1; j < H2Y_LIGHTDIST_BINS; j++) {
+        const uint32_t bits = H2Y_LIGHTDIST_FIRST_BITS + ((j - 1u) << 14);
+        float nf;
+        memcpy(&nf, &bits, sizeof nf);
+        const double node = nf;
+        gain[j] = (float)pow(node, p);
+        oetf[j] = j >= (uint32_t)H2Y_HLG_OETF_FIRST ? (float)(a * log(12.0 * node - b) + c) : 0.0f;
+    }
+    gain[0] = (float)pow(256.0, -p); /* the factor of the reads below the first node: Y^p = (256 Y)^p 256^-p */
+    oetf[0] = 0.0f;
+    *k = relative ? 1.0f : (float)(10000.0 / peak);
+    *gamma = g;
+    return H2Y_OK;
+}
+
+/* the pass's constants and tables for a peak and the scale step of (dst_bit_depth, dst_full_range, dst_matrix), which is
+ * derive_params' for a float source; the checks every entry shares */
+static int hlg_setup(h2y_ctx *ctx, int peak, int relative, int dst_bit_depth, int dst_full_range, int dst_matrix, hlg_consts &c,
+                     std::vector<float> &tables)
+{
+    if (dst_matrix != H2Y_MATRIX_GBR && dst_matrix != H2Y_MATRIX_BT2020NC)
+        return fail(ctx, H2Y_EUNSUPPORTED, "an HLG signal is G,B,R or BT.2020nc (dst_matrix 0 or 9), not dst_matrix %d", dst_matrix);
+    if (dst_bit_depth < 8 || dst_bit_depth > 16) return fail(ctx, H2Y_EINVAL, "dst_bit_depth %d outside 8..16", dst_bit_depth);
+    if (dst_full_range != 0 && dst_full_range != 1) return fail(ctx, H2Y_EINVAL, "dst_full_range must be 0 or 1");
+    tables.resize(2u * H2Y_LIGHTDIST_BINS);
+    const char *why;
+    double gamma;
+    const int rc = h2y_hlg_tables(peak, relative, tables.data(), tables.data() + H2Y_LIGHTDIST_BINS, &c.k, &gamma, &why);
+    if (rc) return fail(ctx, rc, "HLG at %d cd/m2, relative %d: %s", peak, relative, why);
+    h2y_desc d{};
+    d.in_sample_type = H2Y_SAMPLE_F32;
+    d.src_bit_depth = 32;
+    d.dst_bit_depth = dst_bit_depth;
+    d.dst_full_range = dst_full_range;
+    d.src_matrix = H2Y_MATRIX_GBR;
+    d.dst_matrix = dst_matrix;
+    d.src_transfer = d.dst_transfer = H2Y_TRANSFER_LINEAR;
+    pix_params pp;
+    derive_params(&d, &pp, false);
+    c.mulY = pp.mulY, c.addY = pp.addY, c.mulC = pp.mulC, c.addC = pp.addC;
+    return H2Y_OK;
+}
+
+int h2y_hlg_planes(int peak, int relative, int dst_bit_depth, int dst_full_range, int dst_matrix, int sample_type, size_t npix,
+                   const void *const src[3], float *const dst[3])
+{
+    if (sample_type != H2Y_SAMPLE_F32 && sample_type != H2Y_SAMPLE_F16)
+        return fail(nullptr, H2Y_EUNSUPPORTED, "the HLG pass reads float or half planes, not sample type %d", sample_type);
+    if (!src || !dst || !src[0] || !src[1] || !src[2] || !dst[0] || !dst[1] || !dst[2]) return fail(nullptr, H2Y_EINVAL, "null planes");
+    hlg_consts c{};
+    std::vector<float> tables;
+    const int rc = hlg_setup(nullptr, peak, relative, dst_bit_depth, dst_full_range, dst_matrix, c, tables);
+    if (rc) return rc;
+    const float *gain = tables.data(), *oetf_hi = tables.data() + H2Y_LIGHTDIST_BINS + H2Y_HLG_OETF_FIRST;
+    for (size_t i = 0; i < npix; i++) {
+        float v[3];
+        for (int p = 0; p < 3; p++) {
+            if (sample_type == H2Y_SAMPLE_F32) v[p] = static_cast<const float *>(src[p])[i];
+            else v[p] = (float)static_cast<const _Float16 *>(src[p])[i]; /* exact */
+        }
+        hlg_pixel(gain, oetf_hi, c, v[0], v[1], v[2]);
+        for (int p = 0; p < 3; p++) dst[p][i] = v[p];
+    }
+    return H2Y_OK;
+}
+
+/* k_hlg's arguments for frames of width x height, but for the device tables */
+static int hlg_args_of(h2y_ctx *ctx, int width, int height, int sample_type, int peak, int relative, int dst_bit_depth,
+                       int dst_full_range, int dst_matrix, hlg_args &a, std::vector<float> &tables)
+{
+    if (sample_type == H2Y_SAMPLE_U16)
+        return fail(ctx, H2Y_EUNSUPPORTED, "the HLG pass works on display light in float or half planes, not on U16 samples");
+    if (sample_type != H2Y_SAMPLE_F32 && sample_type != H2Y_SAMPLE_F16) return fail(ctx, H2Y_EINVAL, "bad sample type %d", sample_type);
+    if (width < 1 || height < 1 || (uint64_t)width * (uint64_t)height >= (1ull << 28)) return fail(ctx, H2Y_EINVAL, "bad picture size");
+    const int rc = hlg_setup(ctx, peak, relative, dst_bit_depth, dst_full_range, dst_matrix, a.c, tables);
+    if (rc) return rc;
+    a.npix = (uint32_t)width * (uint32_t)height;
+    return H2Y_OK;
+}
+
+int h2y_hlg_batch(h2y_ctx *ctx, int width, int height, int sample_type, int peak, int relative, int dst_bit_depth, int dst_full_range,
+                  int dst_matrix, int n_frames, const void *const *d_src, void *const *d_dst)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
+    hlg_args a{};
+    std::vector<float> tables;
+    int rc = hlg_args_of(ctx, width, height, sample_type, peak, relative, dst_bit_depth, dst_full_range, dst_matrix, a, tables);
+    if (rc) return rc;
+    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
+    if (!d_src || !d_dst) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
+    for (int f = 0; f < n_frames; f++)
+        for (int c = 0; c < 3; c++) {
+            const void *i = d_src[3 * f + c], *o = d_dst[3 * f + c];
+            if (!i || !o) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is null", f, c);
+            if (((uintptr_t)i | (uintptr_t)o) & 15u) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is not 16-byte aligned", f, c);
+            if (i == o && sample_type == H2Y_SAMPLE_F16)
+                return fail(ctx, H2Y_EINVAL, "frame %d: plane %d in place: half planes are widened, the float planes need room of their own", f, c);
+        }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    gamut_frame *h;
+    rc = frame_table(ctx, n_frames, h);
+    if (!rc) rc = ensure(ctx, ctx->d_hlg_tables, ctx->hlg_tables_cap, tables.size() * sizeof(float));
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpy(ctx->d_hlg_tables, tables.data(), tables.size() * sizeof(float), hipMemcpyHostToDevice));
+    a.gain = ctx->d_hlg_tables;
+    a.oetf = ctx->d_hlg_tables + H2Y_LIGHTDIST_BINS;
+    for (int f = 0; f < n_frames; f++)
+        for (int c = 0; c < 3; c++) h[f].src[c] = d_src[3 * f + c], h[f].dst[c] = d_dst[3 * f + c];
+    const int in_kind = sample_type == H2Y_SAMPLE_F16 ? H2Y_IN_F16 : H2Y_IN_F32;
+    const uint64_t per_frame = h2y_hlg_chunks(in_kind, a.npix);
+    rc = timed_launches(ctx, h, n_frames, H2Y_HLG_FRAMES_PER_LAUNCH, "k_hlg", [&](const gamut_frame *frames, int, int nf) {
+        return h2y_launch_hlg(in_kind, h2y_hlg_grid(ctx->n_cu, per_frame * nf), ctx->stream, a, frames, nf);
+    });
+    if (rc) return rc;
+    ctx->last_variant = std::string("k_hlg<") + (in_kind == H2Y_IN_F16 ? "F16" : "F32") + (relative ? ",RELATIVE>" : ",ABSOLUTE>");
+    return H2Y_OK;
+}
+
+/* The pass's ring stage, in place on a forward ring's decoded F32 planes after the gamut and tone-map stages' passes and before the
+ * conversion: k_hlg's arguments, the two tables and its frame table entry per slot.  It leaves nothing of its own behind. */
+struct hlg_stage : ring_stage {
+    hlg_args a{};
+    gamut_frame *tab = nullptr;
+    int grid = 1;
+    int decoded(h2y_ctx *ctx, int k) override
+    {
+        HIP_TRY(ctx, h2y_launch_hlg(H2Y_IN_F32, grid, ctx->stream, a, tab + k, 1));
+        return H2Y_OK;
+    }
+    int run(h2y_ctx *, int) override { return H2Y_OK; }
+};
+
+int h2y_stream_hlg(h2y_ctx *ctx, int peak, int relative)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    if (ctx->s_kind != h2y_ctx::RING_FORWARD) return fail(ctx, H2Y_EINVAL, "the HLG pass works on the forward rings only");
+    if (ctx->s_stage[STAGE_HLG]) return fail(ctx, H2Y_EINVAL, "the ring writes HLG already");
+    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    const h2y_desc *d = &ctx->s_desc;
+    if (d->in_sample_type != H2Y_SAMPLE_F32)
+        return fail(ctx, H2Y_EUNSUPPORTED, "the HLG pass leaves code-valued samples in the ring's decoded planes: they must be F32, not %s",
+                    d->in_sample_type == H2Y_SAMPLE_F16 ? "F16 (a half cannot hold them)" : "U16");
+    if (d->src_transfer != H2Y_TRANSFER_LINEAR || d->dst_transfer != H2Y_TRANSFER_LINEAR)
+        return fail(ctx, H2Y_EUNSUPPORTED, "the HLG pass is the ring's transfer: open it with src_transfer 8 and dst_transfer 8, not %d and %d",
+                    d->src_transfer, d->dst_transfer);
+    if (d->src_matrix != H2Y_MATRIX_GBR)
+        return fail(ctx, H2Y_EUNSUPPORTED, "the HLG pass needs a G,B,R source (src_matrix 0), not src_matrix %d", d->src_matrix);
+    auto st = std::make_unique<hlg_stage>();
+    std::vector<float> tables;
+    int rc = hlg_args_of(ctx, d->width, d->height, d->in_sample_type, peak, relative, d->dst_bit_depth, d->dst_full_range, d->dst_matrix,
+                         st->a, tables);
+    if (rc) return rc;
+    bool unit = d->stats_override == 1;
+    for (int c = 0; c < 3; c++) unit = unit && d->floor[c] == 0 && d->ceiling[c] == 1;
+    if (!unit)
+        return fail(ctx, H2Y_EINVAL, "the HLG pass is the passthrough flow's: open the ring with stats_override 1, floor 0 and ceiling 1 on "
+                                     "all three planes");
+    pix_params pp;
+    derive_params(d, &pp, false); /* the ring's own scale step, whatever else its descriptor says */
+    st->a.c.mulY = pp.mulY, st->a.c.addY = pp.addY, st->a.c.mulC = pp.mulC, st->a.c.addC = pp.addC;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    st->grid = h2y_hlg_grid(ctx->n_cu, h2y_hlg_chunks(H2Y_IN_F32, st->a.npix));
+    float *d_tables = nullptr;
+    st->table(d_tables, tables);
+    st->a.gain = d_tables;
+    st->a.oetf = d_tables + H2Y_LIGHTDIST_BINS;
+    const int depth = (int)ctx->ss.size();
+    std::vector<gamut_frame> tab(depth);
+    for (int k = 0; k < depth; k++)
+        for (int c = 0; c < 3; c++) tab[k].src[c] = tab[k].dst[c] = ctx->ss[k].d_in + c * ctx->s_plane_al;
+    st->table(st->tab, tab);
+    return stage_arm(ctx, STAGE_HLG, std::move(st), "HLG");
+}
+
 /* ---- dither: the reduction to the output bit depth (--dither; the reference's to-do list names it): include/hdr2yuv_hip.h states
  * the definition ------------------------------------------------------------------------------------------------------------------ */
 

@@ -196,7 +196,7 @@ struct ring_stage {
     virtual int run(h2y_ctx *ctx, int slot) = 0;          /* on the context's stream, after the frame was produced */
     virtual int download(h2y_ctx *, int) { return H2Y_OK; } /* the result, on s_d2h after the slot's ev_conv */
 };
-enum stage_id { STAGE_GAMUT, STAGE_TONEMAP, STAGE_LIGHT, STAGE_LIGHTDIST, STAGE_CODELIGHT, STAGE_SCENESIG, STAGE_COMPARE, STAGE_SSIM, STAGE_DELTAE, STAGE_HISTOGRAM, STAGE_SCALE, STAGE_DITHER, STAGE_COUNT };
+enum stage_id { STAGE_GAMUT, STAGE_TONEMAP, STAGE_HLG, STAGE_LIGHT, STAGE_LIGHTDIST, STAGE_CODELIGHT, STAGE_SCENESIG, STAGE_COMPARE, STAGE_SSIM, STAGE_DELTAE, STAGE_HISTOGRAM, STAGE_SCALE, STAGE_DITHER, STAGE_COUNT };
 
 struct h2y_ctx {
     int device = 0;
@@ -291,6 +291,9 @@ struct h2y_ctx {
     /* h2y_tonemap_batch's gain table on the device */
     float *d_tonemap_gain = nullptr;
     size_t tonemap_gain_cap = 0;
+    /* h2y_hlg_batch's two tables on the device: the gains, then the OETF's */
+    float *d_hlg_tables = nullptr;
+    size_t hlg_tables_cap = 0;
 
     /* staging for the host-buffer entry */
     void *d_in = nullptr;

@@ -1159,6 +1159,92 @@ int h2y_tonemap_batch(h2y_ctx *ctx, int width, int height, int sample_type, int 
  * a ring armed already, and for peaks or a `relative` out of range. */
 int h2y_stream_tonemap(h2y_ctx *ctx, int src_peak, int dst_peak, int relative);
 
+/* ---- HLG: display light written as a Hybrid Log-Gamma signal (ARIB STD-B67, Rec. ITU-R BT.2100; --hlg 1) --------------------------
+ * The reference has no HLG transfer (its transfer list ends at TRANSFER_RHO_GAMMA, and its code 18 is that, not H.273's HLG), so
+ * there are no bytes to match: this is the project's own definition, as tone mapping's is.  It is Rep. ITU-R BT.2408's conversion
+ * of display light to HLG at a nominal peak: the inverse OOTF with the system gamma of that peak and no black lift, then the OETF,
+ * both from BT.2100, non-constant luminance.  A pass over the decoded source planes, after h2y_stream_gamut's and
+ * h2y_stream_tonemap's where those are armed, which leaves CODE-VALUED floats: the conversion's own scale step is part of the pass.
+ * The ring is opened with equal transfers, and the unchanged forward conversion then takes the planes straight to its matrix
+ * (convert.cpp:930, :1012), the chroma resampler and write_yuv, as it does for any source whose transfer is the destination's.
+ * Input: planes G, B, R of display light in BT.2020 primaries.
+ * Parameters: an integer peak L_W in cd/m2, 400 <= L_W <= 2000 -- the range over which BT.2100 gives
+ *   gamma = 1.2 + 0.42 log10(L_W / 1000); outside it the Recommendation uses another formula, so other peaks are refused --,
+ *   `relative`: 1: the planes are display-referred, 1.0 = L_W (what h2y_stream_tonemap leaves for a destination that is not PQ);
+ *   0: 1.0 = 10000 cd/m2,
+ *   and four binary32 scale constants mulY, addY, mulC, addC: the conversion's own, what it derives from the descriptor's
+ *   dst_bit_depth, dst_full_range and dst_matrix for its scale step (convert.cpp:1123-1145).  The HLG rung therefore has the scale
+ *   step of the PQ rungs, the reference's habit of scaling B' and R' by the chroma range in video range included: that
+ *   is kept here on purpose, so that an HLG rung and a PQ rung of one run differ in the transfer alone.
+ * Host, binary64: gamma as above, p = (1 - gamma) / gamma; k = 10000 / L_W rounded once to binary32 (`relative` 0), or 1;
+ *   the OETF's constants a = 0.17883277, b = 1 - 4a, c = 0.5 - a ln(4a).
+ *   Two tables of H2Y_LIGHTDIST_BINS = 8706 binary32 entries on the nodes tone mapping uses: node j >= 1 is the float whose bits
+ *   are H2Y_LIGHTDIST_FIRST_BITS + ((j - 1) << 14); every entry is rounded once to binary32:
+ *     gain[j] = node_j^p for j >= 1, and gain[0] = 256^-p: the factor of the reads below the first node, where the table is read
+ *       at 256 Y, since Y^p = (256 Y)^p 256^-p.  The nodes then reach down to 2^-25 of L_W (3e-5 cd/m2 at 1000): a pure blue of
+ *       2^-17 has Y = 2^-21.1.  The inverse OOTF's gain grows without bound towards black; below 2^-25 of L_W it is held constant.
+ *       That is part of the definition.
+ *     oetf[j] = a ln(12 node_j - b) + c for every node >= 2^-4, and 0 below (never read: the logarithmic branch starts above 1/12);
+ *       oetf[8705] rounds to 1.0f.
+ * Pixel, in binary32; a half is widened first (exact).  Every product, sum and difference is one round-to-nearest operation, never
+ *   contracted into a fused multiply-add:
+ *   1. for each of G, B, R: c' = c > 0 ? min(c, 1) : +0.0 (NaN, -0.0 and negatives become +0.0, +inf becomes 1), then
+ *      s = min(c' k, 1);
+ *   2. Y = ((0.2627f s_R) + (0.6780f s_G)) + (0.0593f s_B);
+ *   3. the table read R(x) at x's bits e, x >= 2^-17, is tone mapping's steps 2-3: the bin is min(((e - 0x37000000) >> 14) + 1,
+ *      8705); R = gain[8705] in bin 8705, otherwise, with t = float(e & 0x3FFF) x 2^-14 (exact),
+ *      R = gain[bin] + (gain[bin + 1] - gain[bin]) t.  For Y >= 2^-17 (its bits >= 0x37000000) g = R(Y).  Otherwise Y' = 256 Y
+ *      (exact), g' = R(Y') where Y' >= 2^-17 and gain[1] below, and g = g' gain[0], one more product;
+ *   4. E_c = min(s_c g, 1).  The min is part of the definition: display light such as pure blue at the peak has a scene light of
+ *      1.6 and lies outside what an HLG signal can carry;
+ *   5. E'_c = sqrt(3.0f E_c), the correctly rounded square root, for E_c <= 1/12 (the binary32 nearest to it); otherwise oetf
+ *      interpolated at E_c's bits the same way; then min(E'_c, 1);
+ *   6. out_G = E'_G mulY + addY, out_B = E'_B mulC + addC, out_R = E'_R mulC + addC: the product, then the sum.
+ *   The outputs are F32 whatever the source's sample type: a half cannot hold code-valued samples.
+ * Accuracy: for greys, the three primaries and the three secondaries whose plane value runs over [2^-17, 1] (both modes; peaks
+ * 400, 1000 and 2000) E' stays within 0.012 of a 16-bit video-range luma step, 1 / (219 x 256), of the BT.2100 formulas evaluated
+ * in binary64 (tests/test_hlg_host.py holds it to half a step). */
+#define H2Y_HLG_FRAMES_PER_LAUNCH 64
+#define H2Y_HLG_PEAK_MIN 400
+#define H2Y_HLG_PEAK_MAX 2000
+
+/* The two tables, k and gamma of a peak.  Host only: no device, no context.  gain and oetf receive H2Y_LIGHTDIST_BINS floats each;
+ * `why` (may be NULL) receives a static string.  H2Y_EINVAL for a null gain, oetf, k or gamma, a peak outside 400..2000 and a
+ * `relative` other than 0 or 1. */
+int h2y_hlg_tables(int peak, int relative, float gain[H2Y_LIGHTDIST_BINS], float oetf[H2Y_LIGHTDIST_BINS], float *k, double *gamma,
+                   const char **why);
+
+/* The pixel function on planes in host memory: the host twin of k_hlg, which compiles the same lines (csrc/h2y_hlg1.h).  Host only.
+ * src[c] / dst[c]: plane c = G, B, R of npix samples, sample_type H2Y_SAMPLE_F32 or H2Y_SAMPLE_F16 in, binary32 out; a dst plane
+ * may be its F32 src plane.  The scale constants are those of (dst_bit_depth 8..16, dst_full_range 0 / 1, dst_matrix 0 / 9).
+ * H2Y_EINVAL for null planes and parameters out of range, H2Y_EUNSUPPORTED for another sample type or dst_matrix. */
+int h2y_hlg_planes(int peak, int relative, int dst_bit_depth, int dst_full_range, int dst_matrix, int sample_type, size_t npix,
+                   const void *const src[3], float *const dst[3]);
+
+/* k_hlg on n_frames device frames of width x height: d_src[f*3 + c] / d_dst[f*3 + c] are plane c = G, B, R of frame f, 16-byte
+ * aligned; the destination planes are F32.  With H2Y_SAMPLE_F32 a d_dst entry may equal its d_src entry (in place; no other
+ * overlap); with H2Y_SAMPLE_F16 the planes are widened, and in place is refused (H2Y_EINVAL).  H2Y_SAMPLE_U16 and a dst_matrix
+ * other than 0 (G,B,R) and 9 (BT.2020nc): H2Y_EUNSUPPORTED; a bad size, null or unaligned planes, a peak, `relative`,
+ * dst_bit_depth (8..16) or dst_full_range out of range, a pending batch or an open stream: H2Y_EINVAL.  Launches of up to
+ * H2Y_HLG_FRAMES_PER_LAUNCH frames (h2y_last_kernel_ms sums them, h2y_last_kernel_name "k_hlg", the variant
+ * "k_hlg<F32,RELATIVE>" .. "k_hlg<F16,ABSOLUTE>"); synchronous. */
+int h2y_hlg_batch(h2y_ctx *ctx, int width, int height, int sample_type, int peak, int relative, int dst_bit_depth, int dst_full_range,
+                  int dst_matrix, int n_frames, const void *const *d_src, void *const *d_dst);
+
+/* Arm an open forward ring whose decoded planes are F32 (h2y_stream_open with F32 planes, h2y_dpx_stream_open,
+ * h2y_pqcode_stream_open) before its first input, once: k_hlg then runs in place on every slot's decoded device planes, on the
+ * context's stream, after h2y_stream_gamut's and h2y_stream_tonemap's passes where those are armed (whichever was armed first), and
+ * before the conversion.  The scale constants are the ring's descriptor's.
+ * The descriptor must be the passthrough flow's: src_matrix 0, dst_matrix 0 or 9, src_transfer == dst_transfer == 8, and
+ * stats_override 1 with floor 0 and ceiling 1 on all three planes (what h2y_stream_tonemap beside it needs of the source side).
+ * (dst_matrix 0 goes with src_primaries == dst_primaries: no ring opens on another such descriptor, h2y_desc_check refuses it as
+ * the reference does, "can't determine color difference to use", convert.cpp:1195-1197.)
+ * h2y_stream_light and h2y_stream_lightdist refuse such a ring: their light is PQ's, and its dst_transfer is not 16.
+ * H2Y_EUNSUPPORTED where the planes are F16 or U16 (the EXR ring, .f16 planes, the TIFF ring: a half cannot hold code-valued
+ * samples) and for other transfers or matrices; H2Y_EINVAL on the other ring kinds, after the first input, on a ring armed
+ * already, without that statistics override, and for a peak or a `relative` out of range. */
+int h2y_stream_hlg(h2y_ctx *ctx, int peak, int relative);
+
 /* ---- chroma siting: 4:2:0 chroma co-sited with the top-left luma sample (chroma_sample_loc_type 2; HDR10, UHD Blu-ray) -----------
  * The reference carries chroma_sample_loc_type through pic_t and prints it (hdr2yuv.cpp:490, :505); it parses no flag for it and
  * never acts on it.  Its two resamplers site the chroma as they happen to: the 2x2 box in the centre of the block both ways (loc
@@ -1235,7 +1321,7 @@ int h2y_upsample_444_sited(h2y_ctx *ctx, int width, int height, int chroma_sampl
                            const uint16_t *d_src, uint16_t *d_dst);
 
 /* Timing of the last h2y_convert_batch*() (or h2y_inverse_*, h2y_dpx_decode_batch, h2y_tiff_decode_batch,
- * h2y_rgb_interleave_batch, h2y_exr_decode_batch, h2y_compare_batch, h2y_ssim_batch, h2y_light_batch, h2y_lightdist_batch, h2y_codelight_batch, h2y_scenesig_batch, h2y_codescenesig_batch, h2y_linearize_batch, h2y_scale_batch, h2y_gamut_batch, h2y_dither_batch) call measured with HIP events on
+ * h2y_rgb_interleave_batch, h2y_exr_decode_batch, h2y_compare_batch, h2y_ssim_batch, h2y_light_batch, h2y_lightdist_batch, h2y_codelight_batch, h2y_scenesig_batch, h2y_codescenesig_batch, h2y_linearize_batch, h2y_scale_batch, h2y_gamut_batch, h2y_tonemap_batch, h2y_hlg_batch, h2y_dither_batch) call measured with HIP events on
  * the stream the kernels ran on: total ms over the main kernels and how many
  * launches that covered. */
 int h2y_last_kernel_ms(const h2y_ctx *ctx, float *ms, int *launches);
@@ -1243,7 +1329,7 @@ int h2y_last_kernel_ms(const h2y_ctx *ctx, float *ms, int *launches);
 /* Name of the kernel those launches ran ("k_fused", "k_fused_t1", "k_fused_lut16",
  * "k_fused_narrow"; of the inverse entries "k_inverse", "k_inverse420", "k_inverse_batch", "k_inverse420_batch"; of
  * h2y_dpx_decode_batch "k_dpx_decode"; of h2y_tiff_decode_batch "k_tiff_decode", of h2y_rgb_interleave_batch
- * "k_rgb_interleave"; of h2y_exr_decode_batch "k_exr_decode"; of h2y_compare_batch "k_compare"; of h2y_scale_batch "k_scale"; of h2y_dither_batch "k_dither"; of h2y_gamut_batch "k_gamut"; of h2y_codelight_batch "k_codelight"; of h2y_scenesig_batch "k_scenesig"; of h2y_codescenesig_batch "k_codescenesig"; of h2y_linearize_batch "k_linearize"): the name to
+ * "k_rgb_interleave"; of h2y_exr_decode_batch "k_exr_decode"; of h2y_compare_batch "k_compare"; of h2y_scale_batch "k_scale"; of h2y_dither_batch "k_dither"; of h2y_gamut_batch "k_gamut"; of h2y_tonemap_batch "k_tonemap"; of h2y_hlg_batch "k_hlg"; of h2y_codelight_batch "k_codelight"; of h2y_scenesig_batch "k_scenesig"; of h2y_codescenesig_batch "k_codescenesig"; of h2y_linearize_batch "k_linearize"): the name to
  * look for in a rocprofv3 kernel trace. */
 const char *h2y_last_kernel_name(const h2y_ctx *ctx);
 /* The same with its template arguments and launch shape, e.g. "k_fused_t1<F32,420BOX,YCBCR,PQ_IDENT> groups=8 xcd=1";

@@ -143,6 +143,17 @@ Prints one line per figure, then one JSON line with all of them.
      h2y_stream_tonemap, three times in turn.
 Prints one line per figure, then one JSON line with all of them.
 
+`streambench.py hlg`: the HLG pass on 4K frames, beside k_tonemap and k_gamut in the same job:
+  1. the kernel time of h2y_hlg_batch (k_hlg, 1000 cd/m2, display-referred planes, 10-bit video-range BT.2020nc scale) on 64 distinct
+     device frames per call (HIP events, median of five after a warm-up call): F32 out of place, F32 in place (the light is put back
+     before every call: what the pass leaves is codes, not light) and F16 -> F32; beside them h2y_tonemap_batch (1000 -> 100 cd/m2)
+     and h2y_gamut_batch (BT.2020 -> BT.709) on the same F32 frames, out of place and in place; the algorithmic bytes per frame --
+     24 B/pixel for F32, 18 for F16 -> F32 -- over that time, their share of the 8 TB/s HBM peak, and k_hlg's time over
+     k_tonemap's.  The frames hold light up to the peak, most of it dark;
+  2. frames/s from host memory of the .f32 ring with equal transfers (the passthrough flow) to BT.2020nc 10-bit 4:2:0 with the 0 / 1
+     statistics override, unarmed and armed with h2y_stream_hlg, three times in turn.
+Prints one line per figure, then one JSON line with all of them.
+
 `streambench.py siting`: top-left co-sited 4:2:0 chroma (chroma siting 2) on 4K frames, in one job:
   1. k_fir420 and k_fir420_tl through h2y_subsample_420_sited (loc 0 / loc 2) over the 128 distinct chroma planes of 64 frames, one
      launch per plane (HIP events; the two planes of a frame added up), five passes: median and spread in us per frame, and the
@@ -2047,6 +2058,105 @@ def tonemap_main():
     print(json.dumps({"streambench_tonemap": res}), flush=True)
 
 
+def hlg_main():
+    import json
+
+    import torch
+
+    w, hh, nb, reps = 3840, 2160, 64, 5
+    n = w * hh
+    nf = int(os.environ.get("N", "60"))
+    depth = 3
+    ctx = h.Context(0)
+    res = {"width": w, "height": hh, "frames_per_call": nb, "reps": reps, "ring_frames": nf, "ring_depth": depth, "hbm_peak_tbs": 8.0}
+    hlg = (1000, 1, 10, 0, h.MATRIX_BT2020NC)
+
+    def timed(key, label, nbytes, call, before=None):
+        ks = []
+        for r in range(reps + 1):  # the first call warms up
+            if before:
+                before()
+            call()
+            if r:
+                ks.append(ctx.last_kernel_ms()[0] / nb)
+        k_ms = float(np.median(ks))
+        tbs = nbytes / (k_ms * 1e-3) / 1e12
+        res[key] = dict(kernel_us_per_frame=round(k_ms * 1e3, 2), min_us=round(min(ks) * 1e3, 2), max_us=round(max(ks) * 1e3, 2),
+                        bytes_per_frame=nbytes, kernel_tbs=round(tbs, 2), hbm_peak_fraction=round(tbs / 8.0, 3), variant=ctx.last_kernel_variant())
+        print(f"{label:32s} {nb} frames per call: {k_ms*1e3:7.2f} us/frame ({min(ks)*1e3:.2f}..{max(ks)*1e3:.2f})  {nbytes/1e6:6.1f} MB/frame  "
+              f"{tbs:5.2f} TB/s = {tbs/8.0*100:4.1f} % of 8 TB/s", flush=True)
+        return k_ms
+
+    # 1. the three kernels over the same 64 distinct F32 frames on the device, out of place, then in place
+    src = [[torch.rand(n, device="cuda") ** 3 for _ in range(3)] for _ in range(nb)]
+    dst = [[torch.empty(n, dtype=torch.float32, device="cuda") for _ in range(3)] for _ in range(nb)]
+    torch.cuda.synchronize()
+    b32 = 2 * 3 * n * 4
+    h_out = timed("k_hlg_f32_out_of_place", "k_hlg f32 out of place", b32, lambda: ctx.hlg_batch(w, hh, h.SAMPLE_F32, *hlg, src, dst))
+    t_out = timed("k_tonemap_f32_out_of_place", "k_tonemap f32 out of place", b32, lambda: ctx.tonemap_batch(w, hh, h.SAMPLE_F32, 1000, 100, 1, src, dst))
+    timed("k_gamut_f32_out_of_place", "k_gamut f32 out of place", b32, lambda: ctx.gamut_batch(w, hh, h.SAMPLE_F32, 9, 1, 1, src, dst))
+
+    def put_back():  # dst keeps the light for the in-place calls of k_hlg
+        for f, g in zip(src, dst):
+            for a, b in zip(f, g):
+                a.copy_(b)
+        torch.cuda.synchronize()
+
+    for f, g in zip(dst, src):
+        for a, b in zip(f, g):
+            a.copy_(b)
+    h_in = timed("k_hlg_f32_in_place", "k_hlg f32 in place", b32, lambda: ctx.hlg_batch(w, hh, h.SAMPLE_F32, *hlg, src), before=put_back)
+    put_back()
+    t_in = timed("k_tonemap_f32_in_place", "k_tonemap f32 in place", b32, lambda: ctx.tonemap_batch(w, hh, h.SAMPLE_F32, 1000, 100, 1, src))
+    timed("k_gamut_f32_in_place", "k_gamut f32 in place", b32, lambda: ctx.gamut_batch(w, hh, h.SAMPLE_F32, 9, 1, 1, src))
+    del src
+    torch.cuda.empty_cache()
+    half = [[(torch.rand(n, device="cuda") ** 3).to(torch.float16) for _ in range(3)] for _ in range(nb)]
+    torch.cuda.synchronize()
+    timed("k_hlg_f16_to_f32", "k_hlg f16 -> f32", 3 * n * (2 + 4), lambda: ctx.hlg_batch(w, hh, h.SAMPLE_F16, *hlg, half, dst))
+    res["k_hlg_over_k_tonemap_out_of_place"] = round(h_out / t_out, 3)
+    res["k_hlg_over_k_tonemap_in_place"] = round(h_in / t_in, 3)
+    print(f"k_hlg / k_tonemap: out of place {h_out/t_out:.3f}, in place {h_in/t_in:.3f}", flush=True)
+    del half, dst
+    torch.cuda.empty_cache()
+
+    # 2. the .f32 ring from host memory with equal transfers, unarmed and armed
+    planes = [(np.random.default_rng(31 + c).random(n, dtype=np.float32) ** 3) for c in range(3)]
+    d32 = h.make_desc(w, hh, dst_depth=10, src_transfer=8, dst_transfer=8, dst_matrix=h.MATRIX_BT2020NC, resampler=1, stats=[(0, 1)] * 3)
+
+    def ring(arm):
+        ctx.stream_open(d32, depth)
+        if arm:
+            ctx.stream_hlg(1000, 1)
+        inflight = 0
+        t0 = time.perf_counter()
+        for _ in range(nf):
+            slot = ctx.stream_input()
+            for c in range(3):
+                slot[c][:] = planes[c]
+            ctx.stream_submit()
+            inflight += 1
+            if inflight == depth - 1:
+                ctx.stream_output()
+                inflight -= 1
+        while inflight:
+            ctx.stream_output()
+            inflight -= 1
+        dt = (time.perf_counter() - t0) / nf
+        ctx.stream_close()
+        return dt
+
+    ring(False)  # warm-up
+    res["f32"] = []
+    for _ in range(3):  # unarmed and armed in turn: what the card drifts by shows in both alike
+        t_plain, t_armed = ring(False), ring(True)
+        res["f32"].append(dict(unarmed_fps=round(1 / t_plain, 1), armed_fps=round(1 / t_armed, 1), armed_share=round(t_plain / t_armed, 3)))
+        print(f"f32          ring from host memory: unarmed {1/t_plain:6.1f} frames/s   armed {1/t_armed:6.1f} frames/s "
+              f"({t_plain/t_armed*100:5.1f} %)", flush=True)
+    ctx.close()
+    print(json.dumps({"streambench_hlg": res}), flush=True)
+
+
 def siting_main():
     import json
 
@@ -2138,6 +2248,8 @@ if __name__ == "__main__":
         gamut_main()
     elif sys.argv[1:] == ["tonemap"]:
         tonemap_main()
+    elif sys.argv[1:] == ["hlg"]:
+        hlg_main()
     elif sys.argv[1:] == ["scale"]:
         scale_main()
     elif sys.argv[1:] == ["dither"]:
