@@ -48,6 +48,7 @@ EXPORTS = [
     "h2y_gamut_matrix", "h2y_gamut_batch", "h2y_stream_gamut",
     "h2y_tonemap_curve", "h2y_tonemap_batch", "h2y_stream_tonemap",
     "h2y_hlg_tables", "h2y_hlg_planes", "h2y_hlg_batch", "h2y_stream_hlg",
+    "h2y_hlg_inverse_tables", "h2y_hlg_inverse_planes", "h2y_hlg_linearize_batch", "h2y_hlgcode_stream_open",
     "h2y_ctx_set_chroma_siting", "h2y_subsample_420_sited",
     "h2y_ctx_set_inverse_chroma_siting", "h2y_upsample_444_sited",
 ]
@@ -564,6 +565,14 @@ def load_library():
     L.h2y_hlg_tables.restype = C.c_int
     L.h2y_hlg_planes.argtypes = [C.c_int] * 6 + [C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.h2y_hlg_planes.restype = C.c_int
+    L.h2y_hlg_inverse_tables.argtypes = [C.c_int] + [C.POINTER(C.c_float)] * 3 + [C.POINTER(C.c_double), C.POINTER(C.c_char_p)]
+    L.h2y_hlg_inverse_tables.restype = C.c_int
+    L.h2y_hlg_inverse_planes.argtypes = [C.c_int, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.h2y_hlg_inverse_planes.restype = C.c_int
+    L.h2y_hlg_linearize_batch.argtypes = [C.c_void_p, C.POINTER(H2YCodelightDesc), C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.h2y_hlg_linearize_batch.restype = C.c_int
+    L.h2y_hlgcode_stream_open.argtypes = [C.c_void_p, C.POINTER(H2YDesc), C.POINTER(H2YCodelightDesc), C.c_int, C.c_int]
+    L.h2y_hlgcode_stream_open.restype = C.c_int
     L.h2y_hlg_batch.argtypes = [C.c_void_p] + [C.c_int] * 9 + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.h2y_hlg_batch.restype = C.c_int
     L.h2y_stream_hlg.argtypes = [C.c_void_p] + [C.c_int] * 2
@@ -832,6 +841,37 @@ def hlg_planes(planes, peak: int, relative: int, dst_bit_depth: int, dst_full_ra
     lib = load_library()
     rc = lib.h2y_hlg_planes(int(peak), int(relative), int(dst_bit_depth), int(dst_full_range), int(dst_matrix),
                             SAMPLE_F16 if dt == np.float16 else SAMPLE_F32, src[0].size, ins, outs)
+    if rc != H2Y_OK:
+        raise H2YError(rc, (lib.h2y_last_error(None) or b"").decode())
+    return out
+
+
+def hlg_inverse_tables(peak: int):
+    """h2y_hlg_inverse_tables (host only, no device): (ootf, inv, kappa, gamma) -- the two float32 tables of LIGHTDIST_BINS entries of
+    the light of HLG code planes at a display peak of `peak` cd/m2 (the OOTF's gain, the OETF's inverse), the float32 factor kappa =
+    peak / 10000, and the system gamma as a float.  Raises H2YError (EINVAL: peak outside 400..2000)."""
+    ootf = np.zeros(LIGHTDIST_BINS, dtype=np.float32)
+    inv = np.zeros(LIGHTDIST_BINS, dtype=np.float32)
+    kappa, gamma, why = C.c_float(), C.c_double(), C.c_char_p()
+    fp = C.POINTER(C.c_float)
+    rc = load_library().h2y_hlg_inverse_tables(int(peak), ootf.ctypes.data_as(fp), inv.ctypes.data_as(fp), C.byref(kappa), C.byref(gamma),
+                                               C.byref(why))
+    if rc != H2Y_OK:
+        raise H2YError(rc, (why.value or b"").decode())
+    return ootf, inv, np.float32(kappa.value), float(gamma.value)
+
+
+def hlg_inverse_planes(planes, peak: int):
+    """h2y_hlg_inverse_planes (host only, no device): steps 4h-7h of the light of HLG code planes on three float32 numpy planes G', B',
+    R'; returns the three float32 planes of display light (1.0 = 10000 cd/m2) k_hlg_linearize writes for them."""
+    src = [np.ascontiguousarray(p) for p in planes]
+    if len(src) != 3 or any(p.dtype != np.float32 or p.shape != src[0].shape for p in src):
+        raise ValueError("three float32 planes of one shape")
+    out = [np.empty(p.shape, np.float32) for p in src]
+    ins = (C.c_void_p * 3)(*[p.ctypes.data for p in src])
+    outs = (C.c_void_p * 3)(*[p.ctypes.data for p in out])
+    lib = load_library()
+    rc = lib.h2y_hlg_inverse_planes(int(peak), src[0].size, ins, outs)
     if rc != H2Y_OK:
         raise H2YError(rc, (lib.h2y_last_error(None) or b"").decode())
     return out
@@ -1183,16 +1223,37 @@ class Context:
                 outs[3 * f + c] = self._ptr(planes_out[f][c])
         self._check(self.lib.h2y_linearize_batch(self.h, C.byref(d), n, pf, outs))
 
-    def pqcode_stream_open(self, d, src: H2YCodelightDesc, depth=3) -> None:
+    def hlg_linearize_batch(self, d: H2YCodelightDesc, peak: int, frames, planes_out) -> None:
+        """k_hlg_linearize on device frames of HLG codes at a display peak of `peak` cd/m2: linearize_batch's arguments and layout;
+        planes_out[f] receive the frame's display light (1.0 = 10000 cd/m2)."""
+        n = len(frames)
+        if len(planes_out) != n:
+            raise ValueError("frames and planes_out differ in length")
+        pf = (C.c_void_p * max(n, 1))(*[self._ptr(x) for x in frames])
+        outs = (C.c_void_p * max(3 * n, 1))()
+        for f in range(n):
+            for c in range(3):
+                outs[3 * f + c] = self._ptr(planes_out[f][c])
+        self._check(self.lib.h2y_hlg_linearize_batch(self.h, C.byref(d), int(peak), n, pf, outs))
+
+    def pqcode_stream_open(self, d, src: H2YCodelightDesc, depth=3, hlg_peak=None) -> None:
         """The forward ring on PQ code frames: stream_input gives one uint8 view of the pinned slot to fill with the frame's three
         u16 planes one after the other; the device linearises them (k_up444, k_linearize) into the F32 G,B,R planes d describes
-        (src_transfer 8, src_matrix 0, stats_override 1 with floor 0, ceiling 1); stream_output gives the .yuv frame."""
-        self._check(self.lib.h2y_pqcode_stream_open(self.h, C.byref(d), C.byref(src), depth))
+        (src_transfer 8, src_matrix 0, stats_override 1 with floor 0, ceiling 1); stream_output gives the .yuv frame.  With hlg_peak
+        the codes are HLG's at that display peak (h2y_hlgcode_stream_open: k_hlg_linearize)."""
+        if hlg_peak is None:
+            self._check(self.lib.h2y_pqcode_stream_open(self.h, C.byref(d), C.byref(src), depth))
+        else:
+            self._check(self.lib.h2y_hlgcode_stream_open(self.h, C.byref(d), C.byref(src), int(hlg_peak), depth))
         nc = (src.width >> 1) * (src.height >> 1) if src.chroma_format_idc == CHROMA_420 else src.width * src.height
         self._stream_desc = d
         self._stream_inverse = None
         self._stream_dpx = 2 * (src.width * src.height + 2 * nc)
         self._stream_rgb = False
+
+    def hlgcode_stream_open(self, d, src: H2YCodelightDesc, peak: int, depth=3) -> None:
+        """The forward ring on HLG code frames at a display peak of `peak` cd/m2: pqcode_stream_open with k_hlg_linearize as its decode."""
+        self.pqcode_stream_open(d, src, depth, hlg_peak=peak)
 
     def scale_batch(self, src_w, src_h, dst_w, dst_h, chroma, bit_depth, full_range, gbr, a, frames_src, frames_dst) -> None:
         """k_scale on device frames (tensors or pointers, each frame's planes contiguous from a 16-byte aligned base):

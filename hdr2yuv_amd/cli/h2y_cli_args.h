@@ -176,6 +176,14 @@
  *             matrix, 4:2:2, matrix 0 with 4:2:0 or with a .yuv, a .rgb with another matrix, odd 4:2:0 sizes, a .rgb / .tiff destination
  *             (the .yuv -> RGB flow), every *_only flag, --src_chroma_sample_loc_type 2 with --chroma_resampler_type 0 or with 4:4:4.
  *             Without the flag nothing changes: .yuv 4:4:4 -> .yuv stays the reference's integer flow.
+ * --src_hlg 1 [--src_hlg_peak L] (an addition), beside --linearize 1 only: the file's codes are HLG's (include/hdr2yuv_hip.h, "light of HLG
+ *             code planes"): the device turns them into display light at a peak of L cd/m2 (400..2000, 1000 by default) instead of
+ *             reading them as PQ.  The flag is the source's transfer: --src_transfer_characteristics beside it is refused whatever its
+ *             value (18 is RHO_GAMMA here, as for --hlg 1), and the destination's transfer must be given (or --hlg 1).  Everything else
+ *             --linearize 1 accepts and refuses stays so.  The banner carries src_hlg:, src_hlg_peak: ("(default)" where not given),
+ *             src_hlg_gamma: "%.4f", src_hlg_note:, and linearize_from: names HLG codes.  Refused (exit 1, also under --dry_run): a
+ *             value other than 0 or 1, --src_hlg_peak without --src_hlg 1 or outside 400..2000, --src_hlg 1 without --linearize 1 or
+ *             beside --light_only, --compare_only, --delta_e (those read PQ codes) or --dither_only.
  * --delta_e 1 [--delta_e_threshold X] [--delta_e_limit Y] (an addition): Delta E ITP (Rec. ITU-R BT.2124; include/hdr2yuv_hip.h, "Delta E
  *             ITP of PQ code planes", states every step) of every compared frame against the reference's, beside the PSNR, wherever a
  *             comparison runs on PQ code frames of BT.2020 primaries: with --compare_only 1 on two .yuv files (--src_chroma_format_idc
@@ -284,6 +292,10 @@ struct cli_args {
     bool linearize_given = false;
     cli_pic lin{};
     int lin_type = CLI_IN_NONE;
+    /* --src_hlg 1 [--src_hlg_peak L], beside --linearize 1: the file's codes are HLG's, linearised at a display peak of src_hlg_peak
+     * cd/m2; src_transfer_given: --src_transfer_characteristics was on the command line (refused beside the flag) */
+    int src_hlg = 0, src_hlg_peak = 1000;
+    bool src_hlg_given = false, src_hlg_peak_given = false, src_transfer_given = false;
     /* --delta_e 1: Delta E ITP beside the comparison; --delta_e_threshold (the `over` count), --delta_e_limit (exit status 5);
      * resolved by cli_resolve_delta_e: the compared frames as PQ code planes, and the inverse chroma siting their upsampler takes */
     int delta_e = 0;
@@ -370,6 +382,9 @@ static inline void cli_help()
            "  a PQ master as the source: [--linearize 1] (--src_filename, a PQ .yuv or .rgb as --light_only takes it, linearised on the\n"
            "  GPU into float G,B,R planes in linear light; from there the run is one from a .f32: --tone_map, --gamut_convert, --scale,\n"
            "  --content_light, --dynamic_metadata, --dst_chroma_sample_loc_type, --ref_filename, --ssim and --histogram apply)\n"
+           "  an HLG master as the source: [--linearize 1 --src_hlg 1 [--src_hlg_peak L]] (the .yuv / .rgb holds Hybrid Log-Gamma codes:\n"
+           "  the OETF's inverse and the OOTF at a display peak of L cd/m2, 400..2000, 1000 by default, on the GPU; it replaces\n"
+           "  --src_transfer_characteristics, whose 18 is RHO_GAMMA in this program; to PQ it is BT.2408's HLG -> PQ conversion)\n"
            "  primaries: [--gamut_convert 1 [--gamut_clip 0|1]] (float or half G,B,R source planes in linear light converted from\n"
            "  --src_colour_primaries to --dst_colour_primaries on the GPU before the conversion; 1 BT.709, 8 / 9 BT.2020, 12 P3-D65,\n"
            "  10 XYZ; what is not above 0 is clipped to 0 unless --gamut_clip 0)\n"
@@ -432,6 +447,8 @@ static inline void cli_parse(cli_args &a, int argc, char **argv)
         else if (is("--tone_map")) { a.tone_map = atoi(val()); a.tone_map_given = true; }
         else if (is("--tone_map_src_peak")) { a.tone_src_peak = atoi(val()); a.tone_src_peak_given = true; }
         else if (is("--tone_map_dst_peak")) { a.tone_dst_peak = atoi(val()); a.tone_dst_peak_given = true; }
+        else if (is("--src_hlg")) { a.src_hlg = atoi(val()); a.src_hlg_given = true; }
+        else if (is("--src_hlg_peak")) { a.src_hlg_peak = atoi(val()); a.src_hlg_peak_given = true; }
         else if (is("--hlg")) { a.hlg = atoi(val()); a.hlg_given = true; }
         else if (is("--hlg_peak")) { a.hlg_peak = atoi(val()); a.hlg_peak_given = true; }
         else if (is("--dst_chroma_sample_loc_type")) { a.siting = atoi(val()); a.siting_given = true; }
@@ -467,7 +484,7 @@ static inline void cli_parse(cli_args &a, int argc, char **argv)
         else if (is("--dst_colour_primaries")) a.out.colour_primaries = atoi(val());
         else if (is("--src_matrix_coeffs")) a.in.matrix_coeffs = atoi(val());
         else if (is("--dst_matrix_coeffs")) a.out.matrix_coeffs = atoi(val());
-        else if (is("--src_transfer_characteristics")) a.in.transfer_characteristics = atoi(val());
+        else if (is("--src_transfer_characteristics")) { a.in.transfer_characteristics = atoi(val()); a.src_transfer_given = true; }
         else if (is("--dst_transfer_characteristics")) a.out.transfer_characteristics = atoi(val());
         else if (is("--src_video_full_range_flag")) a.in.video_full_range_flag = atoi(val());
         else if (is("--dst_video_full_range_flag")) a.out.video_full_range_flag = atoi(val());
@@ -625,6 +642,7 @@ static inline int cli_resolve_src_siting(cli_args &a);
 static inline int cli_resolve_light_only(cli_args &a);
 static inline int cli_resolve_scenes(cli_args &a);
 static inline int cli_resolve_linearize(cli_args &a);
+static inline int cli_resolve_src_hlg(cli_args &a);
 static inline int cli_resolve_delta_e(cli_args &a);
 static inline int cli_resolve_dither(cli_args &a);
 static inline int cli_resolve_dither_only(cli_args &a);
@@ -636,6 +654,10 @@ static inline int cli_resolve(cli_args &a)
     if (dither_flags && cli_resolve_dither(a)) return 1;
     if ((a.hlg_given || a.hlg_peak_given) && a.dither_only == 1) {
         printf("hlg: %d\nWARNING: --hlg writes a conversion's rung: not with --dither_only 1\n", a.hlg);
+        return 1;
+    }
+    if ((a.src_hlg_given || a.src_hlg_peak_given) && a.dither_only == 1) {
+        printf("src_hlg: %d\nWARNING: --src_hlg goes with --linearize 1: not with --dither_only 1\n", a.src_hlg);
         return 1;
     }
     const int arg_errors = a.dither_only == 1 ? cli_resolve_dither_only(a) : cli_resolve_all(a);
@@ -657,8 +679,9 @@ static inline int cli_resolve_all(cli_args &a)
             printf("WARNING: linearize(%d) not 0 or 1\n", a.linearize);
             return 1;
         }
-        if (a.linearize && cli_resolve_linearize(a)) return 1;
     }
+    if ((a.src_hlg_given || a.src_hlg_peak_given) && cli_resolve_src_hlg(a)) return 1; /* the transfer of --linearize 1's source */
+    if (a.linearize == 1 && cli_resolve_linearize(a)) return 1;
     if (a.light_only_given) { /* its own flow: it resolves everything it takes and refuses the rest */
         printf("light_only: %d\n", a.light_only);
         if (a.light_only != 0 && a.light_only != 1) {
@@ -1053,6 +1076,56 @@ static inline int cli_resolve_light_only(cli_args &a)
     return 0;
 }
 
+/* --src_hlg / --src_hlg_peak: the codes --linearize 1 reads are HLG's (include/hdr2yuv_hip.h, "light of HLG code planes"), turned into
+ * display light at a peak of src_hlg_peak cd/m2.  Runs before cli_resolve_linearize, which then skips its transfer check; prints the
+ * src_hlg lines; returns the number of argument errors */
+static inline int cli_resolve_src_hlg(cli_args &a)
+{
+    printf("src_hlg: %d\n", a.src_hlg);
+    if (a.src_hlg != 0 && a.src_hlg != 1) {
+        printf("WARNING: src_hlg(%d) not 0 or 1\n", a.src_hlg);
+        return 1;
+    }
+    if (!a.src_hlg) {
+        if (a.src_hlg_peak_given) {
+            printf("WARNING: --src_hlg_peak needs --src_hlg 1\n");
+            return 1;
+        }
+        return 0;
+    }
+    int arg_errors = 0;
+    if (a.linearize != 1) {
+        printf("WARNING: --src_hlg 1 is the transfer of the source --linearize 1 reads: it needs --linearize 1\n");
+        arg_errors++;
+    }
+    if (a.light_only || a.compare_only || a.delta_e) {
+        printf("WARNING: --src_hlg 1: --%s reads PQ codes, not an HLG master's (MaxCLL and HDR10+ of one: --linearize 1 --src_hlg 1 --content_light 1 "
+               "--dynamic_metadata FILE to a PQ destination)\n", a.light_only ? "light_only" : a.compare_only ? "compare_only" : "delta_e");
+        arg_errors++;
+    }
+    if (a.src_transfer_given) {
+        printf("WARNING: --src_hlg 1 is the source's transfer: leave out --src_transfer_characteristics (%d); 18 is RHO_GAMMA in this program, "
+               "H.273's 18 (HLG) is --src_hlg 1\n", a.in.transfer_characteristics);
+        arg_errors++;
+    }
+    if (a.out.transfer_characteristics == -1) {
+        printf("WARNING: --src_hlg 1: the source has no transfer code for the destination to take: give --dst_transfer_characteristics (or --hlg 1)\n");
+        arg_errors++;
+    }
+    std::vector<float> ootf(H2Y_LIGHTDIST_BINS), inv(H2Y_LIGHTDIST_BINS);
+    float kappa;
+    double gamma = 0;
+    const char *why;
+    if (h2y_hlg_inverse_tables(a.src_hlg_peak, ootf.data(), inv.data(), &kappa, &gamma, &why)) {
+        printf("WARNING: --src_hlg 1: src_hlg_peak(%d): %s\n", a.src_hlg_peak, why);
+        arg_errors++;
+    }
+    if (arg_errors) return arg_errors;
+    printf("src_hlg_peak: %d%s\nsrc_hlg_gamma: %.4f\n", a.src_hlg_peak, a.src_hlg_peak_given ? "" : " (default)", gamma);
+    printf("src_hlg_note: src_transfer_characteristics 18 is RHO_GAMMA in this program; H.273's 18 (HLG) is --src_hlg 1\n");
+    return 0;
+}
+
 /* --linearize 1: a PQ .yuv or .rgb as the forward flow's source.  Checks the file's attributes as --light_only checks them, gives the
  * destination what it leaves unset from the source as parsed (hdr2yuv.cpp:265-318), keeps the file's attributes in a.lin and
  * rewrites a.in to the planes the ring decodes -- F32, LINEAR, G,B,R, 4:4:4 -- so that every resolver after this one sees a .f32
@@ -1085,7 +1158,7 @@ static inline int cli_resolve_linearize(cli_args &a)
         printf("WARNING: video_full_range_flag(%d) not 0 or 1\n", a.in.video_full_range_flag);
         arg_errors++;
     }
-    if (a.in.transfer_characteristics != 16) {
+    if (a.src_hlg != 1 && a.in.transfer_characteristics != 16) { /* (--src_hlg 1 is the source's transfer: cli_resolve_src_hlg) */
         printf("WARNING: --linearize 1 linearises PQ codes: src_transfer_characteristics(%d) is not 16\n", a.in.transfer_characteristics);
         arg_errors++;
     }
@@ -1130,7 +1203,7 @@ static inline int cli_resolve_linearize(cli_args &a)
     }
     if (arg_errors) return arg_errors;
     static const char *const kMatrix[10] = {"G,B,R", "BT.709", "", "", "", "", "", "", "", "BT.2020nc"};
-    printf("linearize_from: PQ codes, bit_depth %d %s range, matrix_coeffs %d (%s), chroma_format_idc %d, upsampler %s\n", a.in.bit_depth,
+    printf("linearize_from: %s codes, bit_depth %d %s range, matrix_coeffs %d (%s), chroma_format_idc %d, upsampler %s\n", a.src_hlg == 1 ? "HLG" : "PQ", a.in.bit_depth,
            a.in.video_full_range_flag ? "full" : "video", m, kMatrix[m], chroma,
            chroma == H2Y_CHROMA_444 ? "none" : !a.resampler ? "replicate" : a.src_siting == 2 ? "fir_top_left" : "fir");
     /* hdr2yuv.cpp:265-318: unset destination attributes <- the source's, as parsed */

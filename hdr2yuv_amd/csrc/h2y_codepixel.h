@@ -1,7 +1,7 @@
 /*
  * h2y_codepixel.h -- what the kernels that read PQ code planes share (k_codelight in h2y_codelight.hip, k_linearize in
  * h2y_linearize.hip): eight codes of a plane, and one pixel's three lights L_G, L_B, L_R as include/hdr2yuv_hip.h defines them
- * ("light of PQ code planes", steps 2-4).  Device code only; include after h2y_device.h and h2y_light1.h, in a file built
+ * ("light of PQ code planes", steps 2-4); k_hlg_linearize (h2y_hlgsrc.hip) takes steps 2-3, code_primes.  Device code only; include after h2y_device.h and h2y_light1.h, in a file built
  * -ffp-contract=off: every product and sum of the matrix is rounded by itself.
  */
 #pragma once
@@ -37,14 +37,13 @@ __device__ __forceinline__ void load8(const uint16_t *p, bool vec, uint32_t q, u
 
 __device__ __forceinline__ float clamp01(float v) { return v > 0.0f ? fminf(v, 1.0f) : 0.0f; }
 
-/* one pixel's codes -> its three lights: normalise, matrix, clamp, PQ10000_f through light1<true>'s tiers */
+/* one pixel's codes -> its primes G', B', R' before the clamp: normalise, matrix (steps 2-3; k_hlg_linearize in h2y_hlgsrc.hip
+ * goes on from here with its own transfer) */
 template <int MATRIX>
-__device__ __forceinline__ void code_lights(const codelight_args &a, const pq_recA *tab, uint32_t c0, uint32_t c1, uint32_t c2, float &lg, float &lb,
-                                            float &lr)
+__device__ __forceinline__ void code_primes(const codelight_args &a, uint32_t c0, uint32_t c1, uint32_t c2, float &g, float &b, float &r)
 {
     typedef ycc_coef<MATRIX> K;
     const float y = ((float)c0 - a.sub[0]) / a.div[0];
-    float g, b, r;
     if (MATRIX == H2Y_MATRIX_GBR) {
         g = y;
         b = ((float)c1 - a.sub[0]) / a.div[0];
@@ -55,7 +54,16 @@ __device__ __forceinline__ void code_lights(const codelight_args &a, const pq_re
         b = y + K::bu * cb;
         g = (y - K::gu * cb) - K::gv * cr;
     }
-    lg = light1<true>(a.pp, tab, 0, clamp01(g));
+}
+
+/* one pixel's codes -> its three lights: normalise, matrix, clamp, PQ10000_f through light1<true>'s tiers */
+template <int MATRIX>
+__device__ __forceinline__ void code_lights(const codelight_args &a, const pq_recA *tab, uint32_t c0, uint32_t c1, uint32_t c2, float &lg, float &lb,
+                                            float &lr)
+{
+    float g, b, r;
+    code_primes<MATRIX>(a, c0, c1, c2, g, b, r);
+    lg =light1<true>(a.pp, tab, 0, clamp01(g));
     lb = light1<true>(a.pp, tab, 1, clamp01(b));
     lr = light1<true>(a.pp, tab, 2, clamp01(r));
 }

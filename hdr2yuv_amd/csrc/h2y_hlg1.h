@@ -2,6 +2,8 @@
  * h2y_hlg1.h -- one pixel of the HLG pass as include/hdr2yuv_hip.h defines it ("HLG"): the clean-up, the luminance, the inverse
  * OOTF's gain and the OETF read from their tables, the scale step.  Host and device: k_hlg (h2y_hlg.hip) and its host twin
  * h2y_hlg_planes (h2y_measure.hip) compile the same lines.  Include after h2y_kernels.h (hlg_consts; H2Y_FN of h2y_math.h).
+ * And one pixel of the way back ("light of HLG code planes", steps 4h-7h): the OETF's inverse and the OOTF, from tables on the same
+ * nodes, for k_hlg_linearize (h2y_hlgsrc.hip) and its host twin h2y_hlg_inverse_planes.
  * Every product, sum and difference is rounded on its own: the device's __fmul_rn / __fadd_rn / __fsub_rn are never contracted,
  * and the host's plain operations stand under "fp contract(off)", whatever the build's flags.
  */
@@ -12,6 +14,8 @@ enum {
     H2Y_HLG_LAST = H2Y_LIGHTDIST_BINS - 1,
     H2Y_HLG_OETF_FIRST = 13 * 512 + 1,                                /* the node of 2^-4: the lowest entry of oetf that is read */
     H2Y_HLG_OETF_NODES = H2Y_LIGHTDIST_BINS - H2Y_HLG_OETF_FIRST,      /* 2049 */
+    H2Y_HLG_INV_FIRST = 16 * 512 + 1,                                 /* the node of 2^-1: the lowest entry of inv that is read */
+    H2Y_HLG_INV_NODES = H2Y_LIGHTDIST_BINS - H2Y_HLG_INV_FIRST,        /* 513 */
 };
 #define H2Y_HLG_TWELFTH 0x1.555556p-4f /* the binary32 nearest to 1/12 */
 
@@ -19,6 +23,7 @@ enum {
 H2Y_FN float hlg_mul(float a, float b) { return __fmul_rn(a, b); }
 H2Y_FN float hlg_add(float a, float b) { return __fadd_rn(a, b); }
 H2Y_FN float hlg_sub(float a, float b) { return __fsub_rn(a, b); }
+H2Y_FN float hlg_div(float a, float b) { return __fdiv_rn(a, b); }
 #else
 H2Y_FN float hlg_mul(float a, float b)
 {
@@ -35,6 +40,7 @@ H2Y_FN float hlg_sub(float a, float b)
 #pragma clang fp contract(off)
     return a - b;
 }
+H2Y_FN float hlg_div(float a, float b) { return a / b; }
 #endif
 
 /* c > 0 ? min(c, 1) : +0: a NaN, -0.0 and every negative become +0.0, +inf becomes 1 */
@@ -81,4 +87,23 @@ H2Y_FN void hlg_pixel(const float *gain, const float *oetf_hi, const hlg_consts 
     g = hlg_add(hlg_mul(hlg_signal(oetf_hi, sg, gn), c.mulY), c.addY);
     b = hlg_add(hlg_mul(hlg_signal(oetf_hi, sb, gn), c.mulC), c.addC);
     r = hlg_add(hlg_mul(hlg_signal(oetf_hi, sr, gn), c.mulC), c.addC);
+}
+
+/* E_c of one cleaned sample v' in [+0, 1], the OETF's inverse: the square's third up to 0.5, above it inv read at v'; inv_hi: inv's
+ * entries from H2Y_HLG_INV_FIRST up (v' > 0.5 lies in the binade of 2^-1 or is 1: its bin is H2Y_HLG_INV_FIRST at the least) */
+H2Y_FN float hlg_scene(const float *inv_hi, float v)
+{
+    return v <= 0.5f ? hlg_div(hlg_mul(v, v), 3.0f) : hlg_read(inv_hi, H2Y_HLG_INV_FIRST, v);
+}
+
+/* one pixel of the way back, in place in g, b, r: the primes G', B', R' of an HLG signal in, display light out (1.0 = 10000 cd/m2);
+ * ootf: the OOTF's gain, H2Y_LIGHTDIST_BINS entries read as hlg_gain reads the inverse OOTF's; kappa: L_W / 10000 */
+H2Y_FN void hlg_inverse_pixel(const float *ootf, const float *inv_hi, float kappa, float &g, float &b, float &r)
+{
+    const float eg = hlg_scene(inv_hi, hlg_clean(g)), eb = hlg_scene(inv_hi, hlg_clean(b)), er = hlg_scene(inv_hi, hlg_clean(r));
+    const float Y = hlg_add(hlg_add(hlg_mul(0.2627f, er), hlg_mul(0.6780f, eg)), hlg_mul(0.0593f, eb));
+    const float gn = hlg_gain(ootf, Y);
+    g = hlg_mul(hlg_mul(eg, gn), kappa);
+    b = hlg_mul(hlg_mul(eb, gn), kappa);
+    r = hlg_mul(hlg_mul(er, gn), kappa);
 }

@@ -464,6 +464,16 @@ uint32_t h2y_hlg_chunks(int in_kind, uint32_t npix); /* k_hlg's units of H2Y_HLG
 int h2y_hlg_grid(int n_cu, uint64_t units);           /* blocks for so many units */
 hipError_t h2y_launch_hlg(int in_kind, int grid, hipStream_t st, const hlg_args &a, const gamut_frame *frames, int n_frames);
 
+/* k_hlg_linearize (h2y_hlgsrc.hip): the display light of frames of three u16 HLG code planes as binary32 planes G, B, R
+ * (include/hdr2yuv_hip.h, "light of HLG code planes"); k_linearize's frame table */
+struct hlgsrc_args {
+    codelight_args c;        /* npix, n8, vec, sub, div (table and pp are not read) */
+    float kappa;             /* L_W / 10000 rounded once */
+    const float *ootf, *inv; /* device: H2Y_LIGHTDIST_BINS entries each, h2y_hlg_inverse_tables' */
+};
+int h2y_hlg_linearize_grid(int n_cu, uint32_t npix, int n_frames); /* blocks per frame */
+hipError_t h2y_launch_hlg_linearize(int matrix, int grid, hipStream_t st, const hlgsrc_args &a, const linearize_frame *frames, int n_frames);
+
 /* k_scale (h2y_scale.hip): the Lanczos resampler of include/hdr2yuv_hip.h on frames of three u16 planes.  One axis' table on the
  * device: first[d] and count[d] (int32), then d rows of H2Y_SCALE_MAX_TAPS int16 coefficients (zero past count). */
 enum { H2Y_SCALE_MAX_TAPS = 32, H2Y_SCALE_TILE_W = 64, H2Y_SCALE_TILE_H = 32, H2Y_SCALE_STAGE_ROWS = 16 };

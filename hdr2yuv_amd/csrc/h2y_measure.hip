@@ -1372,9 +1372,9 @@ int h2y_stream_deltae_result(h2y_ctx *ctx, h2y_deltae_stats *out)
 
 /* ---- linearised PQ code planes (h2y_linearize_batch, h2y_pqcode_stream_open): include/hdr2yuv_hip.h states the definition ------ */
 
-static std::string linearize_variant(const codelight_plan &p)
+static std::string linearize_variant(const codelight_plan &p, bool hlg)
 {
-    return std::string("k_linearize<") + (p.matrix == H2Y_MATRIX_GBR ? "GBR" : p.matrix == H2Y_MATRIX_BT709 ? "BT709" : "BT2020NC") + "," +
+    return std::string(hlg ? "k_hlg_linearize<" : "k_linearize<") + (p.matrix == H2Y_MATRIX_GBR ? "GBR" : p.matrix == H2Y_MATRIX_BT709 ? "BT709" : "BT2020NC") + "," +
            (!p.sub ? "444" : p.form == UP_FIR_TL ? "FIR_TL" : p.form == UP_FIR ? "FIR" : "REPLICATE") + ">";
 }
 
@@ -1385,7 +1385,9 @@ static linearize_frame linearize_entry(const codelight_plan &p, const uint16_t *
     return linearize_frame{{c.p[0], c.p[1], c.p[2]}, {static_cast<float *>(out[0]), static_cast<float *>(out[1]), static_cast<float *>(out[2])}};
 }
 
-int h2y_linearize_batch(h2y_ctx *ctx, const h2y_codelight_desc *d, int n_frames, const uint16_t *const *d_frames, void *const *d_planes_out)
+/* both batch entries: the codes are PQ's (hlg_peak null: k_linearize) or HLG's at *hlg_peak cd/m2 (k_hlg_linearize) */
+static int linearize_frames(h2y_ctx *ctx, const h2y_codelight_desc *d, const int *hlg_peak, int n_frames, const uint16_t *const *d_frames,
+                            void *const *d_planes_out)
 {
     if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
     if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
@@ -1405,23 +1407,36 @@ int h2y_linearize_batch(h2y_ctx *ctx, const h2y_codelight_desc *d, int n_frames,
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int per_launch = std::min(n_frames, H2Y_LINEARIZE_FRAMES_PER_LAUNCH);
     linearize_frame *h;
-    rc = codelight_tables(ctx, p);
+    hlgsrc_args ha{};
+    rc = hlg_peak ? hlgsrc_args_of(ctx, p, *hlg_peak, ha) : codelight_tables(ctx, p);
     if (!rc) rc = frame_table(ctx, n_frames, h);
     if (!rc && p.sub) rc = ensure(ctx, ctx->d_codelight_up, ctx->codelight_up_cap, (size_t)per_launch * 2u * p.plane_al);
     if (rc) return rc;
     /* frame f's upsampled chroma lies in the scratch of its place in its launch; the launches follow one another on one stream */
     for (int f = 0; f < n_frames; f++)
         h[f] = linearize_entry(p, d_frames[f], p.sub ? ctx->d_codelight_up + (size_t)(f % per_launch) * 2u * p.plane_al : nullptr, d_planes_out + 3 * f);
-    rc = timed_launches(ctx, h, n_frames, H2Y_LINEARIZE_FRAMES_PER_LAUNCH, "k_linearize", [&](const linearize_frame *frames, int f0, int nf) {
+    rc = timed_launches(ctx, h, n_frames, H2Y_LINEARIZE_FRAMES_PER_LAUNCH, hlg_peak ? "k_hlg_linearize" : "k_linearize", [&](const linearize_frame *frames, int f0, int nf) {
         for (int f = 0; p.sub && f < nf; f++) {
             const hipError_t e = codelight_upsample(ctx, p, d_frames[f0 + f], ctx->d_codelight_up + (size_t)f * 2u * p.plane_al);
             if (e != hipSuccess) return e;
         }
+        if (hlg_peak) return h2y_launch_hlg_linearize(p.matrix, h2y_hlg_linearize_grid(ctx->n_cu, p.a.npix, nf), ctx->stream, ha, frames, nf);
         return h2y_launch_linearize(p.matrix, h2y_linearize_grid(p.a.npix, nf), ctx->stream, p.a, frames, nf);
     });
     if (rc) return rc;
-    ctx->last_variant = linearize_variant(p);
+    ctx->last_variant = linearize_variant(p, hlg_peak != nullptr);
     return H2Y_OK;
+}
+
+int h2y_linearize_batch(h2y_ctx *ctx, const h2y_codelight_desc *d, int n_frames, const uint16_t *const *d_frames, void *const *d_planes_out)
+{
+    return linearize_frames(ctx, d, nullptr, n_frames, d_frames, d_planes_out);
+}
+
+int h2y_hlg_linearize_batch(h2y_ctx *ctx, const h2y_codelight_desc *d, int peak, int n_frames, const uint16_t *const *d_frames,
+                            void *const *d_planes_out)
+{
+    return linearize_frames(ctx, d, &peak, n_frames, d_frames, d_planes_out);
 }
 
 /* The forward ring's PQCODE decode.  One scratch of the context serves every slot: the frames follow one another on its stream. */
@@ -1441,7 +1456,9 @@ int pqcode_decode(h2y_ctx *ctx, int slot)
     const codelight_plan &p = ctx->s_src.code;
     if (p.sub)
         HIP_TRY(ctx, codelight_upsample(ctx, p, reinterpret_cast<const uint16_t *>(ctx->ss[slot].d_in + ctx->s_pay_off), ctx->d_codelight_up));
-    HIP_TRY(ctx, h2y_launch_linearize(p.matrix, h2y_linearize_grid(p.a.npix, 1), ctx->stream, p.a, static_cast<const linearize_frame *>(ctx->s_tab) + slot, 1));
+    const linearize_frame *fr = static_cast<const linearize_frame *>(ctx->s_tab) + slot;
+    if (ctx->s_src.hlg) HIP_TRY(ctx, h2y_launch_hlg_linearize(p.matrix, h2y_hlg_linearize_grid(ctx->n_cu, p.a.npix, 1), ctx->stream, ctx->s_src.hlgsrc, fr, 1));
+    else HIP_TRY(ctx, h2y_launch_linearize(p.matrix, h2y_linearize_grid(p.a.npix, 1), ctx->stream, p.a, fr, 1));
     return H2Y_OK;
 }
 
@@ -2486,6 +2503,67 @@ int h2y_stream_hlg(h2y_ctx *ctx, int peak, int relative)
         for (int c = 0; c < 3; c++) tab[k].src[c] = tab[k].dst[c] = ctx->ss[k].d_in + c * ctx->s_plane_al;
     st->table(st->tab, tab);
     return stage_arm(ctx, STAGE_HLG, std::move(st), "HLG");
+}
+
+/* ---- light of HLG code planes (--linearize 1 --src_hlg 1): include/hdr2yuv_hip.h states the definition ----------------------------- */
+
+int h2y_hlg_inverse_tables(int peak, float ootf[H2Y_LIGHTDIST_BINS], float inv[H2Y_LIGHTDIST_BINS], float *kappa, double *gamma,
+                           const char **why)
+{
+    const char *dummy;
+    if (!why) why = &dummy;
+    *why = "";
+    if (!ootf || !inv || !kappa || !gamma) { *why = "null table, kappa or gamma"; return H2Y_EINVAL; }
+    if (peak < H2Y_HLG_PEAK_MIN || peak > H2Y_HLG_PEAK_MAX) { *why = "peak outside 400 <= peak <= 2000 cd/m2"; return H2Y_EINVAL; }
+    const double g = 1.2 + 0.42 * log10(peak / 1000.0), q = g - 1.0;
+    const double a = 0.17883277, b = 1.0 - 4.0 * a, c = 0.5 - a * log(4.0 * a);
+    for (uint32_t j = 1; j < H2Y_LIGHTDIST_BINS; j++) {
+        const uint32_t bits = H2Y_LIGHTDIST_FIRST_BITS + ((j - 1u) << 14);
+        float nf;
+        memcpy(&nf, &bits, sizeof nf);
+        const double node = nf;
+        ootf[j] = (float)pow(node, q);
+        inv[j] = j >= (uint32_t)H2Y_HLG_INV_FIRST ? (float)((exp((node - c) / a) + b) / 12.0) : 0.0f;
+    }
+    ootf[0] = (float)pow(256.0, -q); /* the factor of the reads below the first node: Y^q = (256 Y)^q 256^-q */
+    inv[0] = 0.0f;
+    *kappa = (float)(peak / 10000.0);
+    *gamma = g;
+    return H2Y_OK;
+}
+
+int h2y_hlg_inverse_planes(int peak, size_t npix, const float *const src[3], float *const dst[3])
+{
+    if (!src || !dst || !src[0] || !src[1] || !src[2] || !dst[0] || !dst[1] || !dst[2]) return fail(nullptr, H2Y_EINVAL, "null planes");
+    std::vector<float> tables(2u * H2Y_LIGHTDIST_BINS);
+    float kappa;
+    double gamma;
+    const char *why;
+    const int rc = h2y_hlg_inverse_tables(peak, tables.data(), tables.data() + H2Y_LIGHTDIST_BINS, &kappa, &gamma, &why);
+    if (rc) return fail(nullptr, rc, "HLG source at %d cd/m2: %s", peak, why);
+    const float *ootf = tables.data(), *inv_hi = tables.data() + H2Y_LIGHTDIST_BINS + H2Y_HLG_INV_FIRST;
+    for (size_t i = 0; i < npix; i++) {
+        float g = src[0][i], b = src[1][i], r = src[2][i];
+        hlg_inverse_pixel(ootf, inv_hi, kappa, g, b, r);
+        dst[0][i] = g, dst[1][i] = b, dst[2][i] = r;
+    }
+    return H2Y_OK;
+}
+
+int hlgsrc_args_of(h2y_ctx *ctx, const codelight_plan &p, int peak, hlgsrc_args &a)
+{
+    std::vector<float> tables(2u * H2Y_LIGHTDIST_BINS);
+    double gamma;
+    const char *why;
+    int rc = h2y_hlg_inverse_tables(peak, tables.data(), tables.data() + H2Y_LIGHTDIST_BINS, &a.kappa, &gamma, &why);
+    if (rc) return fail(ctx, rc, "HLG source at %d cd/m2: %s", peak, why);
+    rc = ensure(ctx, ctx->d_hlgsrc_tables, ctx->hlgsrc_tables_cap, tables.size() * sizeof(float));
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpy(ctx->d_hlgsrc_tables, tables.data(), tables.size() * sizeof(float), hipMemcpyHostToDevice));
+    a.c = p.a;
+    a.ootf = ctx->d_hlgsrc_tables;
+    a.inv = ctx->d_hlgsrc_tables + H2Y_LIGHTDIST_BINS;
+    return H2Y_OK;
 }
 
 /* ---- dither: the reduction to the output bit depth (--dither; the reference's to-do list names it): include/hdr2yuv_hip.h states

@@ -72,7 +72,8 @@ struct codelight_plan {
 
 /* What a decode batch entry or a forward ring decodes: nothing (a ring's caller fills the planes), or one format's payload
  * described by the info its parser returned.  Each format's launch and variant lie beside its parser.  PQCODE (h2y_pqcode_stream_open):
- * the payload is a PQ code frame, the decode its linearisation (pqcode_decode, h2y_measure.hip) by the plan checked at the opening. */
+ * the payload is a PQ code frame, the decode its linearisation (pqcode_decode, h2y_measure.hip) by the plan checked at the opening.
+ * The same kind with hlg set (h2y_hlgcode_stream_open): the codes are HLG's, the decode k_hlg_linearize at hlg.kappa's peak. */
 struct decode_src {
     enum kind_t { NONE, DPX, TIFF, EXR, PQCODE } kind = NONE;
     bool has_info = true; /* false: the caller passed a null info, which check() refuses */
@@ -81,8 +82,11 @@ struct decode_src {
     h2y_tiff_info tiff{};
     h2y_exr_info exr{};
     codelight_plan code{};
+    bool hlg = false;     /* PQCODE: the frame holds HLG codes; hlgsrc: k_hlg_linearize's arguments, the tables in the context's d_hlgsrc_tables */
+    hlgsrc_args hlgsrc{};
     decode_src() = default;
     explicit decode_src(const codelight_plan &p) : kind(PQCODE), code(p) {}
+    decode_src(const codelight_plan &p, const hlgsrc_args &h) : kind(PQCODE), code(p), hlg(true), hlgsrc(h) {}
     explicit decode_src(const h2y_dpx_info *i) : kind(DPX), has_info(i != nullptr) { if (i) dpx = *i; }
     decode_src(const h2y_tiff_info *i, int clamp_video_range) : kind(TIFF), has_info(i != nullptr), clamp(clamp_video_range) { if (i) tiff = *i; }
     explicit decode_src(const h2y_exr_info *i) : kind(EXR), has_info(i != nullptr) { if (i) exr = *i; }
@@ -294,6 +298,9 @@ struct h2y_ctx {
     /* h2y_hlg_batch's two tables on the device: the gains, then the OETF's */
     float *d_hlg_tables = nullptr;
     size_t hlg_tables_cap = 0;
+    /* h2y_hlg_linearize_batch's and the HLG code ring's two tables on the device: the OOTF's gains, then the OETF's inverse */
+    float *d_hlgsrc_tables = nullptr;
+    size_t hlgsrc_tables_cap = 0;
 
     /* staging for the host-buffer entry */
     void *d_in = nullptr;
@@ -496,7 +503,8 @@ int codelight_check(h2y_ctx *ctx, const h2y_codelight_desc *d, codelight_plan &p
 int codelight_tables(h2y_ctx *ctx, codelight_plan &p);
 int pqcode_scratch(h2y_ctx *ctx, const codelight_plan &p);                    /* the context's scratch for one frame's upsampled chroma */
 linearize_frame pqcode_entry(const h2y_ctx *ctx, const codelight_plan &p, const char *payload, char *const planes[3]);
-int pqcode_decode(h2y_ctx *ctx, int slot);                                    /* k_up444 (4:2:0) and k_linearize on the slot's payload */
+int pqcode_decode(h2y_ctx *ctx, int slot);                                    /* k_up444 (4:2:0) and k_linearize (k_hlg_linearize) on the slot's payload */
+int hlgsrc_args_of(h2y_ctx *ctx, const codelight_plan &p, int peak, hlgsrc_args &a); /* the peak's tables into the context's, k_hlg_linearize's arguments */
 
 /* ---- h2y_ring.hip: what a measurement's arm and *_stream_open entries use ----------------------------------------------------------- */
 

@@ -1245,6 +1245,68 @@ int h2y_hlg_batch(h2y_ctx *ctx, int width, int height, int sample_type, int peak
  * already, without that statistics override, and for a peak or a `relative` out of range. */
 int h2y_stream_hlg(h2y_ctx *ctx, int peak, int relative);
 
+/* ---- light of HLG code planes: a finished HLG master as a LINEAR G,B,R F32 source of the forward flow (--linearize 1 --src_hlg 1) ---
+ * The way back from the section above: the OETF's inverse and the OOTF of Rec. ITU-R BT.2100 at a stated display peak, non-constant
+ * luminance, no black lift.  The project's own definition, as "HLG" is: the reference has no HLG transfer, so there are no bytes to
+ * match.  With a PQ destination it is Rep. ITU-R BT.2408's conversion of HLG to PQ (at 1000 cd/m2: --src_hlg_peak 1000).
+ * Frame: exactly what h2y_codelight_desc describes ("light of PQ code planes" above): three u16 code planes at bit_depth 8..16,
+ *   video or full range; matrix_coeffs 0, 1 or 9; chroma_format_idc 3, or 1 with even sizes (not with matrix 0); `algorithm` and the
+ *   context's inverse chroma siting select the upsampler.  The transfer is HLG, always.
+ * Parameter: an integer display peak L_W in cd/m2, H2Y_HLG_PEAK_MIN <= L_W <= H2Y_HLG_PEAK_MAX; gamma = 1.2 + 0.42 log10(L_W / 1000)
+ *   as above, in binary64.
+ * Host, binary64, every entry rounded once to binary32: two tables of H2Y_LIGHTDIST_BINS entries on the nodes of "HLG",
+ *     ootf[j] = node_j^(gamma - 1) for j >= 1, and ootf[0] = 256^-(gamma - 1), the factor of the reads below the first node;
+ *     inv[j] = (exp((node_j - c) / a) + b) / 12 for every node >= 2^-1 -- 513 entries, from node index 16 x 512 + 1 = 8193 up -- and 0
+ *       below (never read: the exponential branch starts above 0.5).  inv[8193] is the binary32 nearest to 1/12, which is also
+ *       (0.5f x 0.5f) / 3.0f, so the two branches meet; inv[8705] is 1.0f;
+ *   kappa = L_W / 10000 rounded once to binary32.
+ * Steps 1-3 are steps 1-3 of "light of PQ code planes", word for word: k_up444 for 4:2:0; the normalisation, one subtraction and one
+ *   IEEE division; the matrix, every product and sum rounded by itself.  Then per pixel, in binary32, every product, sum and
+ *   difference one round-to-nearest operation, never contracted:
+ *   4h. for each of G', B', R': v' = v > 0 ? min(v, 1) : +0.0.  Super-whites above the nominal peak are clipped: that is part of the
+ *       definition.
+ *   5h. the OETF's inverse: for v' <= 0.5f E_c = (v' v') / 3.0f, the product first, then the IEEE division; otherwise E_c = inv read
+ *       at the bits of v' by the table read of "HLG", step 3.
+ *   6h. Y_s = ((0.2627f E_R) + (0.6780f E_G)) + (0.0593f E_B); g = the OOTF's gain at Y_s, read from ootf exactly as "HLG" step 3
+ *       reads the inverse OOTF's gain: below 2^-17 at 256 Y_s, times entry 0; below 2^-25 the gain is held at ootf[1] ootf[0].
+ *       The exponent gamma - 1 is positive, so the held gain OVERSTATES a light that is already below 2^-25 of the peak (3e-5 cd/m2 at
+ *       1000): that is part of the definition.
+ *   7h. L_c = (E_c g) kappa, the product with g first.  The results lie in [+0, kappa]; 1.0 = 10000 cd/m2; the planes are G, B, R:
+ *       what k_linearize leaves for a PQ master, so everything behind it -- k_gamut, k_tonemap, k_hlg, k_light, the forward kernels,
+ *       with floor 0 and ceiling 1 by stats_override -- is untouched.
+ * Anchors (10-bit video range, Cb = Cr = 512, L_W = 1000): Y 64 -> 0; Y 502 (E' = 0.5) -> 50.697 cd/m2; Y 721 (75 %, BT.2408's
+ *   reference white) -> 203.152 cd/m2; Y 940 and 1023 -> 1000.0 cd/m2.
+ * Accuracy: for greys, the three primaries and the three secondaries whose E' runs over [0, 1] on a grid of 2^18 + 1 values, at peaks
+ *   400, 1000 and 2000, wherever Y_s >= 2^-25, L_c stays within 5.01e-6 of BT.2100's formulas in binary64 (relative; measured with the
+ *   host twin's arithmetic; 3.89e-6 at 400, 4.52e-6 at 1000, the worst at 2000), of which (2^-10 / a)^2 / 8 = 3.7e-6 is the linear
+ *   interpolation of exp over a step of 2^-10; tests/test_hlg_source_host.py holds it to 1e-5, a fourteenth of a 16-bit PQ code step
+ *   (1.4e-4 relative).  Below Y_s = 2^-25 only the absolute error is bounded: the worst absolute error over the whole grid is
+ *   9.65e-7 of 10000 cd/m2 (at 2000, near the top of the scale), and below the hold 1.4e-10 (at 400), where the light itself is at
+ *   most (2^-25 / 0.0593) (2^-25)^(gamma - 1) kappa = 1.1e-8. */
+
+/* The two tables, kappa and gamma of a peak.  Host only: no device, no context.  ootf and inv receive H2Y_LIGHTDIST_BINS floats
+ * each; `why` (may be NULL) receives a static string.  H2Y_EINVAL for a null ootf, inv, kappa or gamma and a peak outside 400..2000. */
+int h2y_hlg_inverse_tables(int peak, float ootf[H2Y_LIGHTDIST_BINS], float inv[H2Y_LIGHTDIST_BINS], float *kappa, double *gamma,
+                           const char **why);
+
+/* Steps 4h-7h on planes in host memory: the host twin of k_hlg_linearize, which compiles the same lines (csrc/h2y_hlg1.h).  Host
+ * only.  src[c] / dst[c]: plane c = G', B', R' in, G, B, R out, npix binary32 samples each; the primes may be clamped or not; a dst
+ * plane may be its src plane.  H2Y_EINVAL for null planes and a peak out of range. */
+int h2y_hlg_inverse_planes(int peak, size_t npix, const float *const src[3], float *const dst[3]);
+
+/* h2y_linearize_batch for HLG codes at a display peak of `peak` cd/m2: the layout, the scratch, the launches of up to
+ * H2Y_LINEARIZE_FRAMES_PER_LAUNCH frames (k_up444 per 4:2:0 frame, then one k_hlg_linearize) and the refusals are that entry's; a
+ * peak outside 400..2000 is H2Y_EINVAL.  h2y_last_kernel_name "k_hlg_linearize"; the variant names the matrix and the upsampling
+ * form, e.g. "k_hlg_linearize<BT2020NC,FIR>". */
+int h2y_hlg_linearize_batch(h2y_ctx *ctx, const h2y_codelight_desc *d, int peak, int n_frames, const uint16_t *const *d_frames,
+                            void *const *d_planes_out);
+
+/* h2y_pqcode_stream_open with this decode: a forward ring on HLG code frames of src, which the device takes through k_up444 (4:2:0)
+ * and k_hlg_linearize at `peak` into the slot's three planes.  Every arming entry behaves as on the PQ code ring, h2y_stream_hlg among
+ * them (an HLG master re-written at another nominal peak is a legitimate run).  Refusals as h2y_pqcode_stream_open, and H2Y_EINVAL
+ * for a peak outside 400..2000. */
+int h2y_hlgcode_stream_open(h2y_ctx *ctx, const h2y_desc *d, const h2y_codelight_desc *src, int peak, int depth);
+
 /* ---- chroma siting: 4:2:0 chroma co-sited with the top-left luma sample (chroma_sample_loc_type 2; HDR10, UHD Blu-ray) -----------
  * The reference carries chroma_sample_loc_type through pic_t and prints it (hdr2yuv.cpp:490, :505); it parses no flag for it and
  * never acts on it.  Its two resamplers site the chroma as they happen to: the 2x2 box in the centre of the block both ways (loc
@@ -1321,7 +1383,7 @@ int h2y_upsample_444_sited(h2y_ctx *ctx, int width, int height, int chroma_sampl
                            const uint16_t *d_src, uint16_t *d_dst);
 
 /* Timing of the last h2y_convert_batch*() (or h2y_inverse_*, h2y_dpx_decode_batch, h2y_tiff_decode_batch,
- * h2y_rgb_interleave_batch, h2y_exr_decode_batch, h2y_compare_batch, h2y_ssim_batch, h2y_light_batch, h2y_lightdist_batch, h2y_codelight_batch, h2y_scenesig_batch, h2y_codescenesig_batch, h2y_linearize_batch, h2y_scale_batch, h2y_gamut_batch, h2y_tonemap_batch, h2y_hlg_batch, h2y_dither_batch) call measured with HIP events on
+ * h2y_rgb_interleave_batch, h2y_exr_decode_batch, h2y_compare_batch, h2y_ssim_batch, h2y_light_batch, h2y_lightdist_batch, h2y_codelight_batch, h2y_scenesig_batch, h2y_codescenesig_batch, h2y_linearize_batch, h2y_hlg_linearize_batch, h2y_scale_batch, h2y_gamut_batch, h2y_tonemap_batch, h2y_hlg_batch, h2y_dither_batch) call measured with HIP events on
  * the stream the kernels ran on: total ms over the main kernels and how many
  * launches that covered. */
 int h2y_last_kernel_ms(const h2y_ctx *ctx, float *ms, int *launches);
@@ -1329,7 +1391,7 @@ int h2y_last_kernel_ms(const h2y_ctx *ctx, float *ms, int *launches);
 /* Name of the kernel those launches ran ("k_fused", "k_fused_t1", "k_fused_lut16",
  * "k_fused_narrow"; of the inverse entries "k_inverse", "k_inverse420", "k_inverse_batch", "k_inverse420_batch"; of
  * h2y_dpx_decode_batch "k_dpx_decode"; of h2y_tiff_decode_batch "k_tiff_decode", of h2y_rgb_interleave_batch
- * "k_rgb_interleave"; of h2y_exr_decode_batch "k_exr_decode"; of h2y_compare_batch "k_compare"; of h2y_scale_batch "k_scale"; of h2y_dither_batch "k_dither"; of h2y_gamut_batch "k_gamut"; of h2y_tonemap_batch "k_tonemap"; of h2y_hlg_batch "k_hlg"; of h2y_codelight_batch "k_codelight"; of h2y_scenesig_batch "k_scenesig"; of h2y_codescenesig_batch "k_codescenesig"; of h2y_linearize_batch "k_linearize"): the name to
+ * "k_rgb_interleave"; of h2y_exr_decode_batch "k_exr_decode"; of h2y_compare_batch "k_compare"; of h2y_scale_batch "k_scale"; of h2y_dither_batch "k_dither"; of h2y_gamut_batch "k_gamut"; of h2y_tonemap_batch "k_tonemap"; of h2y_hlg_batch "k_hlg"; of h2y_codelight_batch "k_codelight"; of h2y_scenesig_batch "k_scenesig"; of h2y_codescenesig_batch "k_codescenesig"; of h2y_linearize_batch "k_linearize"; of h2y_hlg_linearize_batch "k_hlg_linearize"): the name to
  * look for in a rocprofv3 kernel trace. */
 const char *h2y_last_kernel_name(const h2y_ctx *ctx);
 /* The same with its template arguments and launch shape, e.g. "k_fused_t1<F32,420BOX,YCBCR,PQ_IDENT> groups=8 xcd=1";
