@@ -22,6 +22,7 @@ CHROMA_420, CHROMA_444 = 1, 3
 TRANSFER_LINEAR, TRANSFER_PQ = 8, 16
 MATRIX_GBR, MATRIX_BT709, MATRIX_BT2020NC, MATRIX_YDZDX, MATRIX_Y500, MATRIX_Y100 = 0, 1, 9, 11, 12, 13
 MATRIX_YUVPRIME2 = 15  # destination only: Y'u'v' (include/hdr2yuv_hip.h)
+MATRIX_ICTCP = 14  # H2YCodelightDesc.matrix_coeffs only: PQ ICtCp codes (include/hdr2yuv_hip.h, "light of ICtCp code planes")
 
 H2Y_OK, H2Y_EINVAL, H2Y_EUNSUPPORTED, H2Y_EHIP, H2Y_ENOMEM = 0, 1, 2, 3, 4
 
@@ -49,6 +50,7 @@ EXPORTS = [
     "h2y_tonemap_curve", "h2y_tonemap_batch", "h2y_stream_tonemap",
     "h2y_hlg_tables", "h2y_hlg_planes", "h2y_hlg_batch", "h2y_stream_hlg",
     "h2y_hlg_inverse_tables", "h2y_hlg_inverse_planes", "h2y_hlg_linearize_batch", "h2y_hlgcode_stream_open",
+    "h2y_ictcp_batch", "h2y_stream_ictcp",
     "h2y_ctx_set_chroma_siting", "h2y_subsample_420_sited",
     "h2y_ctx_set_inverse_chroma_siting", "h2y_upsample_444_sited",
 ]
@@ -71,6 +73,7 @@ GAMUT_FRAMES_PER_LAUNCH = 64
 TONEMAP_FRAMES_PER_LAUNCH = 64
 HLG_FRAMES_PER_LAUNCH = 64
 HLG_PEAK_MIN, HLG_PEAK_MAX = 400, 2000
+ICTCP_FRAMES_PER_LAUNCH = 64
 SCALE_TAPS = 32  # coefficients per row of scale_taps' table
 DITHER_FRAMES_PER_LAUNCH = 64
 DITHER_CUT, DITHER_ORDERED, DITHER_NOISE = 0, 1, 2
@@ -577,6 +580,10 @@ def load_library():
     L.h2y_hlg_batch.restype = C.c_int
     L.h2y_stream_hlg.argtypes = [C.c_void_p] + [C.c_int] * 2
     L.h2y_stream_hlg.restype = C.c_int
+    L.h2y_ictcp_batch.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.h2y_ictcp_batch.restype = C.c_int
+    L.h2y_stream_ictcp.argtypes = [C.c_void_p]
+    L.h2y_stream_ictcp.restype = C.c_int
     L.h2y_stream_tonemap.argtypes = [C.c_void_p] + [C.c_int] * 3
     L.h2y_stream_tonemap.restype = C.c_int
     L.h2y_stream_open.argtypes = [C.c_void_p, C.POINTER(H2YDesc), C.c_int]
@@ -1327,7 +1334,29 @@ class Context:
         self._check(self.lib.h2y_hlg_batch(self.h, width, height, sample, peak, relative, dst_bit_depth, dst_full_range, dst_matrix, n,
                                            ins, outs))
 
+    def ictcp_batch(self, width, height, sample, dst_bit_depth, dst_full_range, frames_src, frames_dst=None) -> None:
+        """k_ictcp on device frames (frames_src[f] = three device planes G, B, R of float or half display light, 1.0 = 10000 cd/m2,
+        16-byte aligned): frames_dst[f] receives the float planes of code-valued PQ I, Ct, Cp samples on H.273's scale of
+        (dst_bit_depth, dst_full_range), the rounding half added; frames_dst None: in place (float planes only)."""
+        frames_dst = frames_src if frames_dst is None else frames_dst
+        n = len(frames_src)
+        if len(frames_dst) != n:
+            raise ValueError("frames_src and frames_dst differ in length")
+        ins = (C.c_void_p * max(3 * n, 1))()
+        outs = (C.c_void_p * max(3 * n, 1))()
+        for f in range(n):
+            for c in range(3):
+                ins[3 * f + c] = self._ptr(frames_src[f][c])
+                outs[3 * f + c] = self._ptr(frames_dst[f][c])
+        self._check(self.lib.h2y_ictcp_batch(self.h, width, height, sample, dst_bit_depth, dst_full_range, n, ins, outs))
+
     # ---- host <-> device pipeline -----------------------------------------------------------
+    def stream_ictcp(self) -> None:
+        """Arm an open forward ring of float planes (plain F32, DPX, PQ or HLG code) that was opened with src_transfer == dst_transfer
+        == 8, src_matrix == dst_matrix == 0 and the 0 / 1 statistics override: every slot's decoded planes become code-valued PQ
+        I, Ct, Cp samples in place, after stream_gamut's and stream_tonemap's passes, before the conversion (h2y_stream_ictcp)."""
+        self._check(self.lib.h2y_stream_ictcp(self.h))
+
     def stream_hlg(self, peak, relative) -> None:
         """Arm an open forward ring of float planes (plain F32, DPX or PQ code) that was opened with src_transfer == dst_transfer == 8
         and the 0 / 1 statistics override: every slot's decoded planes become code-valued HLG samples in place, after stream_gamut's

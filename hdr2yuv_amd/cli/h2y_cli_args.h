@@ -115,6 +115,22 @@
  *             primaries other than 8 / 9 at the pass, --dst_matrix_coeffs other than 0 / 9 (and 0 with primaries codes that
  *             differ: the library refuses that descriptor as the reference does, convert.cpp:1195), .rgb / .tiff destinations and the .yuv ->
  *             RGB flow, every *_only flow, --content_light, --dynamic_metadata and the scene flags (their light is PQ's), --delta_e.
+ * --ictcp 1 (an addition; the reference's matrix list has MATRIX_YUVPRIME1 at H.273's code 14, which is ICtCp): the forward flow writes a PQ
+ *             ICtCp rung (Rec. ITU-R BT.2100).  The decoded source planes, display light in BT.2020 primaries with 1.0 = 10000 cd/m2
+ *             after --gamut_convert's and --tone_map's passes where those are given (the mapper's output is then absolute), become
+ *             code-valued I, Ct, Cp on the device (include/hdr2yuv_hip.h, "ICtCp", states every step), and the unchanged forward
+ *             conversion casts, subsamples and writes them.  The flag IS the destination's matrix and transfer: the run's become the
+ *             passthrough descriptor's 0 and 8 with floor 0 and ceiling 1 and the source's primaries the destination's;
+ *             --dst_matrix_coeffs beside it is refused whatever its value, --dst_transfer_characteristics unless it is 16.  Accepted
+ *             and refused where --hlg 1 is, and refused beside --hlg 1; --content_light, --dynamic_metadata, the scene flags and
+ *             --delta_e on the same run are refused with the command that measures the written file.  The banner carries ictcp:,
+ *             ictcp_scale: (H.273's oY aY oC aC), ictcp_note: and ictcp_encoder:.
+ * --src_ictcp 1 (an addition), beside --linearize 1, --light_only 1 or --compare_only 1 --delta_e 1, on a .yuv (4:2:0 or 4:4:4): the file's
+ *             codes are PQ I, Ct, Cp (include/hdr2yuv_hip.h, "light of ICtCp code planes").  It replaces --src_matrix_coeffs, which is
+ *             refused beside it; --src_transfer_characteristics must be 16 and --src_colour_primaries 8 or 9; with --linearize 1 the
+ *             destination's matrix must be given (or --ictcp 1).  Everything else those flows accept and refuse stays so, and
+ *             linearize_from:, light_only_from: and delta_e_from: name matrix_coeffs 14 (ICtCp).  Refused: a value other than 0 or 1,
+ *             .rgb sources, --src_hlg 1 beside it, the flag without one of the three flows.
  * --gamut_convert 1 [--gamut_clip 0|1] (an addition; the reference's matrix_to_primaries() is empty, convert.cpp:1991, and the two
  *             colour_primaries values only pick a branch of matrix_convert()): the decoded source planes are converted on the device
  *             from --src_colour_primaries to --dst_colour_primaries, in linear light, before the unchanged forward conversion
@@ -295,6 +311,11 @@ struct cli_args {
     /* --src_hlg 1 [--src_hlg_peak L], beside --linearize 1: the file's codes are HLG's, linearised at a display peak of src_hlg_peak
      * cd/m2; src_transfer_given: --src_transfer_characteristics was on the command line (refused beside the flag) */
     int src_hlg = 0, src_hlg_peak = 1000;
+    /* --ictcp 1: the rung is PQ ICtCp (H.273 matrix_coeffs 14); resolved: ictcp_dst_transfer and ictcp_dst_matrix, what
+     * --dst_transfer_characteristics and --dst_matrix_coeffs gave before the flag replaced them with the passthrough descriptor's 8 and
+     * 0 (-1: not given).  --src_ictcp 1: the codes --linearize 1, --light_only 1 or --compare_only 1 --delta_e 1 read are PQ I, Ct, Cp */
+    int ictcp = 0, ictcp_dst_transfer = -1, ictcp_dst_matrix = -1, src_ictcp = 0;
+    bool ictcp_given = false, src_ictcp_given = false, src_matrix_given = false;
     bool src_hlg_given = false, src_hlg_peak_given = false, src_transfer_given = false;
     /* --delta_e 1: Delta E ITP beside the comparison; --delta_e_threshold (the `over` count), --delta_e_limit (exit status 5);
      * resolved by cli_resolve_delta_e: the compared frames as PQ code planes, and the inverse chroma siting their upsampler takes */
@@ -391,6 +412,9 @@ static inline void cli_help()
            "  tone mapping: [--tone_map 1 [--tone_map_src_peak S] [--tone_map_dst_peak D]] (float or half G,B,R source planes in linear\n"
            "  light brought from a mastering peak of S cd/m2, 1000 by default, down to D, 100 by default, on the GPU by the BT.2390\n"
            "  curve on max(R,G,B) before the conversion: the SDR rung of an HDR master, or a 1000 cd/m2 PQ rung of a 4000 cd/m2 one)\n"
+           "  ICtCp: [--ictcp 1] (the rung is PQ I, Ct, Cp, BT.2100 / H.273 matrix_coeffs 14, from float G,B,R planes of display light;\n"
+           "  it replaces --dst_matrix_coeffs and --dst_transfer_characteristics); [--src_ictcp 1] beside --linearize 1, --light_only 1 or\n"
+           "  --compare_only 1 --delta_e 1 (the .yuv holds PQ I, Ct, Cp codes; it replaces --src_matrix_coeffs)\n"
            "  HLG: [--hlg 1 [--hlg_peak L]] (the rung is Hybrid Log-Gamma, ARIB STD-B67 / BT.2100: float G,B,R source planes of display light\n"
            "  in BT.2020 primaries through the inverse OOTF at a nominal peak of L cd/m2, 400..2000, 1000 by default, and the OETF on the\n"
            "  GPU; it replaces --dst_transfer_characteristics, whose 18 is RHO_GAMMA in this program, not H.273's HLG)\n"
@@ -450,6 +474,8 @@ static inline void cli_parse(cli_args &a, int argc, char **argv)
         else if (is("--src_hlg")) { a.src_hlg = atoi(val()); a.src_hlg_given = true; }
         else if (is("--src_hlg_peak")) { a.src_hlg_peak = atoi(val()); a.src_hlg_peak_given = true; }
         else if (is("--hlg")) { a.hlg = atoi(val()); a.hlg_given = true; }
+        else if (is("--ictcp")) { a.ictcp = atoi(val()); a.ictcp_given = true; }
+        else if (is("--src_ictcp")) { a.src_ictcp = atoi(val()); a.src_ictcp_given = true; }
         else if (is("--hlg_peak")) { a.hlg_peak = atoi(val()); a.hlg_peak_given = true; }
         else if (is("--dst_chroma_sample_loc_type")) { a.siting = atoi(val()); a.siting_given = true; }
         else if (is("--src_chroma_sample_loc_type")) { a.src_siting = atoi(val()); a.src_siting_given = true; }
@@ -482,7 +508,7 @@ static inline void cli_parse(cli_args &a, int argc, char **argv)
         else if (is("--verbose_level")) a.verbose = atoi(val());
         else if (is("--src_colour_primaries")) a.in.colour_primaries = atoi(val());
         else if (is("--dst_colour_primaries")) a.out.colour_primaries = atoi(val());
-        else if (is("--src_matrix_coeffs")) a.in.matrix_coeffs = atoi(val());
+        else if (is("--src_matrix_coeffs")) { a.in.matrix_coeffs = atoi(val()); a.src_matrix_given = true; }
         else if (is("--dst_matrix_coeffs")) a.out.matrix_coeffs = atoi(val());
         else if (is("--src_transfer_characteristics")) { a.in.transfer_characteristics = atoi(val()); a.src_transfer_given = true; }
         else if (is("--dst_transfer_characteristics")) a.out.transfer_characteristics = atoi(val());
@@ -637,6 +663,10 @@ static inline int cli_resolve_scale(cli_args &a);
 static inline int cli_resolve_gamut(cli_args &a, int src_matrix_arg);
 static inline int cli_resolve_tone_map(cli_args &a, int src_matrix_arg);
 static inline int cli_resolve_hlg(cli_args &a, int src_matrix_arg);
+/* is m the matrix --src_ictcp 1 gave the source? (--src_matrix_coeffs 14 without the flag stays what it was: refused) */
+static inline bool cli_src_is_ictcp(const cli_args &a, int m) { return a.src_ictcp == 1 && m == H2Y_MATRIX_ICTCP; }
+static inline int cli_resolve_ictcp(cli_args &a, int src_matrix_arg);
+static inline int cli_resolve_src_ictcp(cli_args &a);
 static inline int cli_resolve_siting(cli_args &a);
 static inline int cli_resolve_src_siting(cli_args &a);
 static inline int cli_resolve_light_only(cli_args &a);
@@ -660,6 +690,11 @@ static inline int cli_resolve(cli_args &a)
         printf("src_hlg: %d\nWARNING: --src_hlg goes with --linearize 1: not with --dither_only 1\n", a.src_hlg);
         return 1;
     }
+    if ((a.ictcp_given || a.src_ictcp_given) && a.dither_only == 1) {
+        printf("%s: %d\nWARNING: --%s goes with a conversion or a measurement: not with --dither_only 1\n", a.ictcp_given ? "ictcp" : "src_ictcp",
+               a.ictcp_given ? a.ictcp : a.src_ictcp, a.ictcp_given ? "ictcp" : "src_ictcp");
+        return 1;
+    }
     const int arg_errors = a.dither_only == 1 ? cli_resolve_dither_only(a) : cli_resolve_all(a);
     if (arg_errors || !a.dithers()) return arg_errors;
     printf("dither: %d (%s)\ndither_depth: %d -> %d\ndither_temporal: %d\ndither_seed: %u\n", a.dither, a.dither == 1 ? "ordered" : "noise",
@@ -673,6 +708,12 @@ static inline int cli_resolve_all(cli_args &a)
         a.hlg_dst_transfer = a.out.transfer_characteristics;
         a.out.transfer_characteristics = H2Y_TRANSFER_LINEAR;
     }
+    if (a.ictcp == 1 && a.hlg != 1) { /* likewise: the flag is the destination's matrix and transfer; the run's is the passthrough's */
+        a.ictcp_dst_transfer = a.out.transfer_characteristics;
+        a.ictcp_dst_matrix = a.out.matrix_coeffs;
+        a.out.transfer_characteristics = H2Y_TRANSFER_LINEAR;
+        a.out.matrix_coeffs = H2Y_MATRIX_GBR;
+    }
     if (a.linearize_given) { /* first: what follows resolves the linearised source */
         printf("linearize: %d\n", a.linearize);
         if (a.linearize != 0 && a.linearize != 1) {
@@ -681,6 +722,7 @@ static inline int cli_resolve_all(cli_args &a)
         }
     }
     if ((a.src_hlg_given || a.src_hlg_peak_given) && cli_resolve_src_hlg(a)) return 1; /* the transfer of --linearize 1's source */
+    if (a.src_ictcp_given && cli_resolve_src_ictcp(a)) return 1; /* the matrix of the codes the three flows below read */
     if (a.linearize == 1 && cli_resolve_linearize(a)) return 1;
     if (a.light_only_given) { /* its own flow: it resolves everything it takes and refuses the rest */
         printf("light_only: %d\n", a.light_only);
@@ -690,6 +732,10 @@ static inline int cli_resolve_all(cli_args &a)
         }
         if (a.light_only && (a.hlg_given || a.hlg_peak_given)) {
             printf("hlg: %d\nWARNING: --hlg writes a conversion's rung: not with --light_only 1\n", a.hlg);
+            return 1;
+        }
+        if (a.light_only && a.ictcp_given) {
+            printf("ictcp: %d\nWARNING: --ictcp writes a conversion's rung: not with --light_only 1 (the light of an ICtCp file: --src_ictcp 1)\n", a.ictcp);
             return 1;
         }
         if (a.light_only) {
@@ -712,6 +758,7 @@ static inline int cli_resolve_all(cli_args &a)
     if (a.gamut_given || a.gamut_clip_given) arg_errors += cli_resolve_gamut(a, src_matrix_arg);
     if (a.tone_map_given || a.tone_src_peak_given || a.tone_dst_peak_given) arg_errors += cli_resolve_tone_map(a, src_matrix_arg);
     if (a.hlg_given || a.hlg_peak_given) arg_errors += cli_resolve_hlg(a, src_matrix_arg);
+    if (a.ictcp_given) arg_errors += cli_resolve_ictcp(a, src_matrix_arg);
     if (a.siting_given) arg_errors += cli_resolve_siting(a);
     const bool de_flags = a.delta_e_given || a.delta_e_threshold_given || a.delta_e_limit_given;
     /* (--linearize 1 resolved its own; under --compare_only 1 --delta_e 1 the flag chooses Delta E's upsampler, checked there) */
@@ -1023,7 +1070,7 @@ static inline int cli_resolve_light_only(cli_args &a)
         arg_errors++;
     }
     const int m = a.in.matrix_coeffs, chroma = a.in.chroma_format_idc;
-    if (m != H2Y_MATRIX_GBR && m != H2Y_MATRIX_BT709 && m != H2Y_MATRIX_BT2020NC) {
+    if (m != H2Y_MATRIX_GBR && m != H2Y_MATRIX_BT709 && m != H2Y_MATRIX_BT2020NC && !cli_src_is_ictcp(a, m)) {
         printf("WARNING: --light_only 1: src_matrix_coeffs(%d) not %d (G,B,R), %d (BT.709) or %d (BT.2020nc)\n", m, H2Y_MATRIX_GBR,
                H2Y_MATRIX_BT709, H2Y_MATRIX_BT2020NC);
         arg_errors++;
@@ -1067,12 +1114,58 @@ static inline int cli_resolve_light_only(cli_args &a)
     a.out = a.in;
     if (arg_errors) return arg_errors;
     a.light = 1; /* the run keeps and reports content light's figures */
-    static const char *const kMatrix[10] = {"G,B,R", "BT.709", "", "", "", "", "", "", "", "BT.2020nc"};
+    static const char *const kMatrix[15] = {"G,B,R", "BT.709", "", "", "", "", "", "", "", "BT.2020nc", "", "", "", "", "ICtCp"};
     printf("light_only_from: PQ codes, bit_depth %d %s range, matrix_coeffs %d (%s), chroma_format_idc %d, upsampler %s\n", a.in.bit_depth,
            a.in.video_full_range_flag ? "full" : "video", m, kMatrix[m], chroma,
            chroma == H2Y_CHROMA_444 ? "none" : !a.resampler ? "replicate" : a.src_siting == 2 ? "fir_top_left" : "fir");
     if (a.dynmeta)
         printf("dynamic_metadata_from: PQ codes; HDR10+ profile A, one scene, percentiles of max(R,G,B) in %d bins\n", H2Y_LIGHTDIST_BINS);
+    return 0;
+}
+
+/* --src_ictcp: the codes --linearize 1, --light_only 1 or --compare_only 1 --delta_e 1 read are PQ I, Ct, Cp (include/hdr2yuv_hip.h,
+ * "light of ICtCp code planes").  Runs before those flows' resolvers and gives the source matrix_coeffs 14, which they then accept;
+ * returns the number of argument errors */
+static inline int cli_resolve_src_ictcp(cli_args &a)
+{
+    printf("src_ictcp: %d\n", a.src_ictcp);
+    if (a.src_ictcp != 0 && a.src_ictcp != 1) {
+        printf("WARNING: src_ictcp(%d) not 0 or 1\n", a.src_ictcp);
+        return 1;
+    }
+    if (!a.src_ictcp) return 0;
+    int arg_errors = 0;
+    if (a.linearize != 1 && a.light_only != 1 && !(a.compare_only && a.delta_e == 1)) {
+        printf("WARNING: --src_ictcp 1 is the matrix of the codes a flow reads: it needs --linearize 1, --light_only 1 or --compare_only 1 --delta_e 1\n");
+        arg_errors++;
+    }
+    if (a.src_hlg == 1) {
+        printf("WARNING: --src_ictcp 1 reads PQ I, Ct, Cp: not with --src_hlg 1 (BT.2100's HLG form of ICtCp has other coefficients and is not built)\n");
+        arg_errors++;
+    }
+    if (a.src_matrix_given) {
+        printf("WARNING: --src_ictcp 1 is the source's matrix: leave out --src_matrix_coeffs (%d); 14 is YUVPrime1 in this program's list, "
+               "H.273's 14 (ICtCp) is --src_ictcp 1\n", a.in.matrix_coeffs);
+        arg_errors++;
+    }
+    if (!strcasecmp(cli_ext_of(a.src), "rgb")) {
+        printf("WARNING: --src_ictcp 1: a .rgb holds planes R, G, B, not I, Ct, Cp: the source must be a .yuv\n");
+        arg_errors++;
+    }
+    if (a.src_hlg != 1 && a.in.transfer_characteristics != 16) {
+        printf("WARNING: --src_ictcp 1 reads PQ I, Ct, Cp: src_transfer_characteristics(%d) is not 16\n", a.in.transfer_characteristics);
+        arg_errors++;
+    }
+    if (a.in.colour_primaries != 8 && a.in.colour_primaries != 9) {
+        printf("WARNING: --src_ictcp 1: ICtCp is defined on BT.2020 primaries: src_colour_primaries(%d) is not 8 or 9\n", a.in.colour_primaries);
+        arg_errors++;
+    }
+    if (a.linearize == 1 && a.ictcp != 1 && a.out.matrix_coeffs == -1) {
+        printf("WARNING: --src_ictcp 1: the source has no matrix code for the destination to take: give --dst_matrix_coeffs (or --ictcp 1)\n");
+        arg_errors++;
+    }
+    if (arg_errors) return arg_errors;
+    a.in.matrix_coeffs = H2Y_MATRIX_ICTCP;
     return 0;
 }
 
@@ -1163,7 +1256,7 @@ static inline int cli_resolve_linearize(cli_args &a)
         arg_errors++;
     }
     const int m = a.in.matrix_coeffs, chroma = a.in.chroma_format_idc;
-    if (m != H2Y_MATRIX_GBR && m != H2Y_MATRIX_BT709 && m != H2Y_MATRIX_BT2020NC) {
+    if (m != H2Y_MATRIX_GBR && m != H2Y_MATRIX_BT709 && m != H2Y_MATRIX_BT2020NC && !cli_src_is_ictcp(a, m)) {
         printf("WARNING: --linearize 1: src_matrix_coeffs(%d) not %d (G,B,R), %d (BT.709) or %d (BT.2020nc)\n", m, H2Y_MATRIX_GBR,
                H2Y_MATRIX_BT709, H2Y_MATRIX_BT2020NC);
         arg_errors++;
@@ -1202,7 +1295,7 @@ static inline int cli_resolve_linearize(cli_args &a)
         arg_errors++;
     }
     if (arg_errors) return arg_errors;
-    static const char *const kMatrix[10] = {"G,B,R", "BT.709", "", "", "", "", "", "", "", "BT.2020nc"};
+    static const char *const kMatrix[15] = {"G,B,R", "BT.709", "", "", "", "", "", "", "", "BT.2020nc", "", "", "", "", "ICtCp"};
     printf("linearize_from: %s codes, bit_depth %d %s range, matrix_coeffs %d (%s), chroma_format_idc %d, upsampler %s\n", a.src_hlg == 1 ? "HLG" : "PQ", a.in.bit_depth,
            a.in.video_full_range_flag ? "full" : "video", m, kMatrix[m], chroma,
            chroma == H2Y_CHROMA_444 ? "none" : !a.resampler ? "replicate" : a.src_siting == 2 ? "fir_top_left" : "fir");
@@ -1423,12 +1516,12 @@ static inline int cli_resolve_tone_map(cli_args &a, int src_matrix_arg)
         printf("WARNING: --tone_map 1 needs a G,B,R source: src_matrix_coeffs(%d) is not %d\n", src_matrix_arg, H2Y_MATRIX_GBR);
         return 1;
     }
-    if (a.out.transfer_characteristics == H2Y_TRANSFER_LINEAR && a.hlg != 1) { /* (--hlg 1 is the display's transfer) */
+    if (a.out.transfer_characteristics == H2Y_TRANSFER_LINEAR && a.hlg != 1 && a.ictcp != 1) { /* (--hlg 1 and --ictcp 1 are the display's transfer) */
         printf("WARNING: --tone_map 1 maps light for a display: dst_transfer_characteristics(%d) keeps linear light\n",
                a.out.transfer_characteristics);
         return 1;
     }
-    a.tone_relative = a.out.transfer_characteristics != 16;
+    a.tone_relative = a.out.transfer_characteristics != 16 && a.ictcp != 1; /* (an ICtCp rung is PQ) */
     std::vector<float> gain(H2Y_LIGHTDIST_BINS);
     float cap = 0.0f;
     const char *why = nullptr;
@@ -1538,6 +1631,83 @@ static inline int cli_resolve_hlg(cli_args &a, int src_matrix_arg)
     printf("hlg_note: dst_transfer_characteristics 18 is RHO_GAMMA in this program; H.273's 18 (HLG) is --hlg 1\n");
     printf("hlg_encoder: x265 --transfer arib-std-b67 --colorprim bt2020 --colormatrix %s; SvtAv1EncApp --transfer-characteristics 18 "
            "--color-primaries 9 --matrix-coefficients %d\n", m == H2Y_MATRIX_GBR ? "gbr" : "bt2020nc", m);
+    return 0;
+}
+
+/* --ictcp: the forward flow's float G,B,R planes of display light in BT.2020 primaries (1.0 = 10000 cd/m2), written as PQ I, Ct, Cp
+ * (include/hdr2yuv_hip.h, "ICtCp").  src_matrix_arg: --src_matrix_coeffs as given; cli_resolve_all replaced the destination's transfer
+ * and matrix with the passthrough descriptor's and kept what was given; prints the scale, the note on code 14 and the encoder flags;
+ * returns the number of argument errors */
+static inline int cli_resolve_ictcp(cli_args &a, int src_matrix_arg)
+{
+    printf("ictcp: %d\n", a.ictcp);
+    if (a.ictcp != 0 && a.ictcp != 1) {
+        printf("WARNING: ictcp(%d) not 0 or 1\n", a.ictcp);
+        return 1;
+    }
+    if (!a.ictcp) return 0;
+    if (a.hlg == 1) {
+        printf("WARNING: --ictcp 1 writes PQ I, Ct, Cp: not with --hlg 1 (BT.2100's HLG form of ICtCp has other coefficients and is not built)\n");
+        return 1;
+    }
+    int arg_errors = 0;
+    if (a.ictcp_dst_matrix != -1) {
+        printf("WARNING: --ictcp 1 is the destination's matrix: leave out --dst_matrix_coeffs (%d); 14 is YUVPrime1 in this program's list, "
+               "H.273's 14 (ICtCp) is --ictcp 1\n", a.ictcp_dst_matrix);
+        arg_errors++;
+    }
+    if (a.ictcp_dst_transfer != -1 && a.ictcp_dst_transfer != 16) {
+        printf("WARNING: --ictcp 1 writes PQ I, Ct, Cp: dst_transfer_characteristics(%d) is not 16\n", a.ictcp_dst_transfer);
+        arg_errors++;
+    }
+    if (a.compare_only || a.hist_only || a.scale_only) {
+        printf("WARNING: --ictcp 1 writes a conversion's rung: not with --%s 1\n",
+               a.compare_only ? "compare_only" : a.hist_only ? "histogram_only" : "scale_only");
+        return arg_errors + 1;
+    }
+    if (a.inverse) {
+        printf("WARNING: --ictcp 1 is the forward flow's (to .yuv), not the .yuv -> RGB flow's\n");
+        return arg_errors + 1;
+    }
+    if (a.out_type != CLI_OUT_YUV) {
+        printf("WARNING: --ictcp 1 writes .yuv frames: not a .%s destination\n", cli_ext_of(a.dst ? a.dst : a.ref));
+        return arg_errors + 1;
+    }
+    if (a.in_type != CLI_IN_F32 && a.in_type != CLI_IN_DPX) {
+        printf("WARNING: --ictcp 1 leaves code-valued samples in float planes (.f32 or .dpx input, or --linearize 1 from a .yuv / .rgb), not "
+               ".%s input\n", a.in_type == CLI_IN_SYNTH ? "(synthetic)" : cli_ext_of(a.src));
+        return arg_errors + 1;
+    }
+    if (a.in.transfer_characteristics != H2Y_TRANSFER_LINEAR) {
+        printf("WARNING: --ictcp 1 takes linear light: src_transfer_characteristics(%d) is not %d\n", a.in.transfer_characteristics,
+               H2Y_TRANSFER_LINEAR);
+        arg_errors++;
+    }
+    if (src_matrix_arg != H2Y_MATRIX_GBR) {
+        printf("WARNING: --ictcp 1 needs a G,B,R source: src_matrix_coeffs(%d) is not %d\n", src_matrix_arg, H2Y_MATRIX_GBR);
+        arg_errors++;
+    }
+    const int sp = a.in.colour_primaries, dp = a.out.colour_primaries;
+    if ((dp != 8 && dp != 9) || (a.gamut != 1 && sp != dp)) {
+        printf("WARNING: --ictcp 1 takes BT.2020 primaries: %s_colour_primaries(%d) is not 8 or 9%s\n", (dp != 8 && dp != 9) ? "dst" : "src",
+               (dp != 8 && dp != 9) ? dp : sp, a.gamut == 1 ? "" : " and the destination's (other primaries need --gamut_convert 1)");
+        arg_errors++;
+    }
+    if (a.light || a.dynmeta || a.scene_detect_given || a.scene_threshold_given || a.scene_cuts || a.scene_qpfile) {
+        printf("WARNING: --ictcp 1: --content_light, --dynamic_metadata and the scene flags read a ring whose dst_transfer is 16: measure the "
+               "written file with --light_only 1 --src_ictcp 1\n");
+        arg_errors++;
+    }
+    if (a.delta_e_given || a.delta_e_threshold_given || a.delta_e_limit_given) {
+        printf("WARNING: --ictcp 1: --delta_e on the same run is not built: judge the written file with --compare_only 1 --src_ictcp 1 --delta_e 1\n");
+        arg_errors++;
+    }
+    const int n = a.out.bit_depth, full = a.out.video_full_range_flag == 1;
+    if (arg_errors || n < 8 || n > 16) return arg_errors; /* (a depth out of range has been refused already) */
+    const long s = 1L << (n - 8), top = (1L << n) - 1;
+    printf("ictcp_scale: oY %ld aY %ld oC %ld aC %ld\n", full ? top : 219 * s, full ? 0L : 16 * s, full ? top : 224 * s, full ? 1L << (n - 1) : 128 * s);
+    printf("ictcp_note: dst_matrix_coeffs 14 is YUVPrime1, an unbuilt Y'u'v' variant, in this program's list; H.273's 14 (ICtCp) is --ictcp 1\n");
+    printf("ictcp_encoder: x265 --colormatrix ictcp --transfer smpte2084 --colorprim bt2020 (no encoder has checked this output)\n");
     return 0;
 }
 
@@ -1703,7 +1873,7 @@ static inline int cli_resolve_delta_e(cli_args &a)
                "first)\n", side, p.colour_primaries);
         arg_errors++;
     }
-    if (m != H2Y_MATRIX_GBR && m != H2Y_MATRIX_BT709 && m != H2Y_MATRIX_BT2020NC) {
+    if (m != H2Y_MATRIX_GBR && m != H2Y_MATRIX_BT709 && m != H2Y_MATRIX_BT2020NC && !(src && cli_src_is_ictcp(a, m))) {
         printf("WARNING: --delta_e 1: %s_matrix_coeffs(%d) not %d (G,B,R), %d (BT.709) or %d (BT.2020nc)\n", side, m, H2Y_MATRIX_GBR, H2Y_MATRIX_BT709,
                H2Y_MATRIX_BT2020NC);
         arg_errors++;
@@ -1748,7 +1918,7 @@ static inline int cli_resolve_delta_e(cli_args &a)
     if (arg_errors) return arg_errors;
     a.de = h2y_codelight_desc{p.width, p.height, chroma, p.bit_depth, p.video_full_range_flag, m, a.resampler};
     a.de_siting = siting == 2 ? 2 : 0;
-    static const char *const kMatrix[10] = {"G,B,R", "BT.709", "", "", "", "", "", "", "", "BT.2020nc"};
+    static const char *const kMatrix[15] = {"G,B,R", "BT.709", "", "", "", "", "", "", "", "BT.2020nc", "", "", "", "", "ICtCp"};
     printf("delta_e_from: %s PQ codes, bit_depth %d %s range, matrix_coeffs %d (%s), chroma_format_idc %d, upsampler %s, threshold %g%s\n",
            src ? "source" : "output", p.bit_depth, p.video_full_range_flag ? "full" : "video", m, kMatrix[m], chroma,
            chroma == H2Y_CHROMA_444 ? "none" : !a.resampler ? "replicate" : siting == 2 ? "fir_top_left" : "fir", (double)a.delta_e_threshold,
@@ -1922,12 +2092,13 @@ static inline void cli_make_desc(const cli_args &a, h2y_desc *d)
     d->dst_transfer = a.out.transfer_characteristics;
     d->src_matrix = a.in.matrix_coeffs;
     d->dst_matrix = a.out.matrix_coeffs;
-    d->src_primaries = a.in.colour_primaries;
+    d->src_primaries = a.ictcp == 1 ? a.out.colour_primaries : a.in.colour_primaries; /* the passthrough descriptor's are equal: --gamut_convert
+                                                                                          * has the source's (h2y_stream_gamut) */
     d->dst_primaries = a.out.colour_primaries;
     d->dst_full_range = a.out.video_full_range_flag;
     d->dst_chroma_format_idc = a.out.chroma_format_idc;
     d->chroma_resampler_type = a.resampler;
-    if (a.tone_map || a.linearize == 1 || a.hlg == 1) { /* mapped planes are referred to their target, linearised ones lie in [0, 1] by
+    if (a.tone_map || a.linearize == 1 || a.hlg == 1 || a.ictcp == 1) { /* mapped planes are referred to their target, linearised ones lie in [0, 1] by
                                                          * definition, HLG's are code-valued: floor 0 and ceiling 1, not each frame's
                                                          * pic_stats */
         d->stats_override = 1;

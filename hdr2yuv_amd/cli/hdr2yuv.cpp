@@ -137,6 +137,13 @@
  * --tone_map's passes, and the conversion takes them straight to its matrix.  The banner carries hlg:, hlg_peak: ("(default)" where
  * not given), hlg_gamma: "%.9g", hlg_input: absolute|relative, hlg_note: and hlg_encoder:.
  *
+ * ICtCp (--ictcp 1 on the same sources; h2y_cli_args.h): the run's destination matrix and transfer become the passthrough descriptor's
+ * 0 and 8 with equal primaries, each GPU thread opens its ring with floor 0 and ceiling 1 and arms it (h2y_stream_ictcp), so every
+ * slot's decoded planes become code-valued PQ I, Ct, Cp samples in place on the device, after --gamut_convert's and --tone_map's passes,
+ * and the conversion casts, subsamples and writes them.  The banner carries ictcp:, ictcp_scale:, ictcp_note: and ictcp_encoder:.
+ * --src_ictcp 1 gives the code frames that --linearize 1, --light_only 1 and --compare_only 1 --delta_e 1 read matrix_coeffs 14 in
+ * their h2y_codelight_desc; nothing else in those flows differs.
+ *
  * A PQ master as the source (--linearize 1 on the forward flow from a PQ .yuv or .rgb; h2y_cli_args.h): each GPU thread sets its
  * context's inverse chroma siting where --src_chroma_sample_loc_type 2 says so and opens the forward ring that decodes PQ code frames
  * (h2y_pqcode_stream_open): a frame is read whole into the pinned slot, as --light_only reads it, and linearised on the device into
@@ -412,7 +419,7 @@ static flow forward_flow(const job &j)
                (a.dynmeta && h2y_stream_lightdist(ctx)) || (a.scene_detect == 1 && h2y_stream_scenesig(ctx)) ||
                (a.gamut && h2y_stream_gamut(ctx, a.in.colour_primaries, a.out.colour_primaries, a.gamut_clip)) ||
                (a.tone_map && h2y_stream_tonemap(ctx, a.tone_src_peak, a.tone_dst_peak, a.tone_relative)) ||
-               (a.hlg == 1 && h2y_stream_hlg(ctx, a.hlg_peak, a.hlg_relative)) ||
+               (a.hlg == 1 && h2y_stream_hlg(ctx, a.hlg_peak, a.hlg_relative)) || (a.ictcp == 1 && h2y_stream_ictcp(ctx)) ||
                (a.scale && h2y_stream_scale(ctx, a.out.width, a.out.height, a.scale_taps)) ||
                (a.dithers() && h2y_stream_dither(ctx, a.dither_to, a.dither, a.dither_temporal, a.dither_seed, (uint32_t)first)); /* after scale */
     };

@@ -174,5 +174,6 @@ hipError_t h2y_launch_codelight(int matrix, int grid, hipStream_t st, const code
     if (matrix == H2Y_MATRIX_BT2020NC) return launch_m<H2Y_MATRIX_BT2020NC>(grid, st, a, frames, n_frames, acc, dacc, bins);
     if (matrix == H2Y_MATRIX_BT709) return launch_m<H2Y_MATRIX_BT709>(grid, st, a, frames, n_frames, acc, dacc, bins);
     if (matrix == H2Y_MATRIX_GBR) return launch_m<H2Y_MATRIX_GBR>(grid, st, a, frames, n_frames, acc, dacc, bins);
+    if (matrix == H2Y_MATRIX_ICTCP) return launch_m<H2Y_MATRIX_ICTCP>(grid, st, a, frames, n_frames, acc, dacc, bins);
     return hipErrorInvalidValue;
 }

@@ -1,7 +1,7 @@
 /*
  * h2y_codepixel.h -- what the kernels that read PQ code planes share (k_codelight in h2y_codelight.hip, k_linearize in
  * h2y_linearize.hip): eight codes of a plane, and one pixel's three lights L_G, L_B, L_R as include/hdr2yuv_hip.h defines them
- * ("light of PQ code planes", steps 2-4); k_hlg_linearize (h2y_hlgsrc.hip) takes steps 2-3, code_primes.  Device code only; include after h2y_device.h and h2y_light1.h, in a file built
+ * ("light of PQ code planes", steps 2-4; matrix 14: "light of ICtCp code planes"); k_hlg_linearize (h2y_hlgsrc.hip) takes steps 2-3, code_primes.  Device code only; include after h2y_device.h and h2y_light1.h, in a file built
  * -ffp-contract=off: every product and sum of the matrix is rounded by itself.
  */
 #pragma once
@@ -56,14 +56,42 @@ __device__ __forceinline__ void code_primes(const codelight_args &a, uint32_t c0
     }
 }
 
+/* matrix 14, ICtCp ("light of ICtCp code planes"): one pixel's codes I, Ct, Cp -> L', M', S' before the clamp.  The constants are
+ * the binary64 inverse of the forward matrix, each rounded once to binary32 (tests/test_ictcp_host.py recomputes them) */
+__device__ __forceinline__ void code_lms_primes(const codelight_args &a, uint32_t c0, uint32_t c1, uint32_t c2, float &lp, float &mp, float &sp)
+{
+    constexpr float ka = 0x1.1a19d6p-7f /* 0.00860903703793 */, kb = 0x1.c6c7p-4f /* 0.111029625003 */, kc = 0x1.1ebc6ep-1f /* 0.560031335711 */,
+                    kd = 0x1.48527ep-2f /* 0.320627174987 */;
+    const float i = ((float)c0 - a.sub[0]) / a.div[0];
+    const float ct = ((float)c1 - a.sub[1]) / a.div[1], cp = ((float)c2 - a.sub[1]) / a.div[1];
+    lp = (i + ka * ct) + kb * cp;
+    mp = (i - ka * ct) - kb * cp;
+    sp = (i + kc * ct) - kd * cp;
+}
+
+/* matrix 14: l, m, s -> the three lights in BT.2020 primaries, the inverse of the k / 4096 LMS matrix, clamped */
+__device__ __forceinline__ void lms_lights(float l, float m, float s, float &lg, float &lb, float &lr)
+{
+    lr = clamp01((0x1.b7e2bap+1f /* 3.43660669433 */ * l - 0x1.40d36cp+1f /* 2.50645211866 */ * m) + 0x1.1e163cp-4f /* 0.0698454243232 */ * s);
+    lg = clamp01((0x1.fbcd3ep+0f /* 1.98360045179 */ * m - 0x1.952926p-1f /* 0.791329555599 */ * l) - 0x1.89c552p-3f /* 0.192270896193 */ * s);
+    lb = clamp01((0x1.1ff71p+0f /* 1.1248636144 */ * s - 0x1.a929c4p-6f /* 0.0259498996906 */ * l) - 0x1.95268cp-4f /* 0.0989137147117 */ * m);
+}
+
 /* one pixel's codes -> its three lights: normalise, matrix, clamp, PQ10000_f through light1<true>'s tiers */
 template <int MATRIX>
 __device__ __forceinline__ void code_lights(const codelight_args &a, const pq_recA *tab, uint32_t c0, uint32_t c1, uint32_t c2, float &lg, float &lb,
                                             float &lr)
 {
-    float g, b, r;
-    code_primes<MATRIX>(a, c0, c1, c2, g, b, r);
-    lg =light1<true>(a.pp, tab, 0, clamp01(g));
-    lb = light1<true>(a.pp, tab, 1, clamp01(b));
-    lr = light1<true>(a.pp, tab, 2, clamp01(r));
+    if constexpr (MATRIX == H2Y_MATRIX_ICTCP) {
+        float lp, mp, sp;
+        code_lms_primes(a, c0, c1, c2, lp, mp, sp);
+        const float l = light1<true>(a.pp, tab, 0, clamp01(lp)), m = light1<true>(a.pp, tab, 1, clamp01(mp)), s = light1<true>(a.pp, tab, 2, clamp01(sp));
+        lms_lights(l, m, s, lg, lb, lr);
+    } else {
+        float g, b, r;
+        code_primes<MATRIX>(a, c0, c1, c2, g, b, r);
+        lg = light1<true>(a.pp, tab, 0, clamp01(g));
+        lb = light1<true>(a.pp, tab, 1, clamp01(b));
+        lr = light1<true>(a.pp, tab, 2, clamp01(r));
+    }
 }

@@ -160,6 +160,7 @@ hipError_t h2y_launch_deltae(int matrix, int grid, hipStream_t st, const deltae_
     if (matrix == H2Y_MATRIX_BT2020NC) hipLaunchKernelGGL((k_deltae<H2Y_MATRIX_BT2020NC>), dim3(grid, n_frames), dim3(kThreads), 0, st, a, frames, acc);
     else if (matrix == H2Y_MATRIX_BT709) hipLaunchKernelGGL((k_deltae<H2Y_MATRIX_BT709>), dim3(grid, n_frames), dim3(kThreads), 0, st, a, frames, acc);
     else if (matrix == H2Y_MATRIX_GBR) hipLaunchKernelGGL((k_deltae<H2Y_MATRIX_GBR>), dim3(grid, n_frames), dim3(kThreads), 0, st, a, frames, acc);
+    else if (matrix == H2Y_MATRIX_ICTCP) hipLaunchKernelGGL((k_deltae<H2Y_MATRIX_ICTCP>), dim3(grid, n_frames), dim3(kThreads), 0, st, a, frames, acc);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }

@@ -378,7 +378,7 @@ struct codelight_args {
 };
 int h2y_codelight_grid(uint32_t npix, int n_frames); /* blocks per frame */
 /* k_codelight over n_frames frames into acc[frame] and, where dacc is not NULL, dacc[frame] and bins[frame x H2Y_LIGHTDIST_BINS]
- * (all zeroed by the caller); matrix: H2Y_MATRIX_GBR, _BT709 or _BT2020NC */
+ * (all zeroed by the caller); matrix: H2Y_MATRIX_GBR, _BT709, _BT2020NC or _ICTCP */
 hipError_t h2y_launch_codelight(int matrix, int grid, hipStream_t st, const codelight_args &a, const codelight_frame *frames, int n_frames,
                                 light_acc *acc, lightdist_acc *dacc, uint32_t *bins);
 
@@ -421,7 +421,7 @@ struct deltae_args {
     float threshold;
 };
 int h2y_deltae_grid(uint32_t npix, int n_frames); /* blocks per pair */
-/* k_deltae over n_frames pairs into acc[pair] (zeroed by the caller); matrix: H2Y_MATRIX_GBR, _BT709 or _BT2020NC */
+/* k_deltae over n_frames pairs into acc[pair] (zeroed by the caller); matrix: H2Y_MATRIX_GBR, _BT709, _BT2020NC or _ICTCP */
 hipError_t h2y_launch_deltae(int matrix, int grid, hipStream_t st, const deltae_args &a, const deltae_frame *frames, int n_frames, deltae_acc *acc);
 
 /* k_gamut (h2y_gamut.hip): the conversion between colour primaries of include/hdr2yuv_hip.h on frames of three float or half
@@ -463,6 +463,20 @@ enum { H2Y_HLG_THREADS = 512 };
 uint32_t h2y_hlg_chunks(int in_kind, uint32_t npix); /* k_hlg's units of H2Y_HLG_THREADS threads per frame */
 int h2y_hlg_grid(int n_cu, uint64_t units);           /* blocks for so many units */
 hipError_t h2y_launch_hlg(int in_kind, int grid, hipStream_t st, const hlg_args &a, const gamut_frame *frames, int n_frames);
+
+/* k_ictcp (h2y_ictcp.hip): the ICtCp pass of include/hdr2yuv_hip.h on frames of three float or half planes G, B, R of display
+ * light, k_gamut's frame table; the destination planes are float (dst may be src for float planes: in place) */
+struct ictcp_args {
+    uint32_t npix;          /* pixels per frame (< 2^28) */
+    float oY, aY, oC, aC;   /* H.273's scale of dst_bit_depth and dst_full_range */
+    float top;              /* 2^n - 1 */
+    const void *table_r;    /* PQ10000_r's table (tfn_build_table of H2Y_TFN_PQ_R) */
+    h2y::pix_params pp;     /* what code1 reads: dst_tf PQ, dst_fn H2Y_TFN_PQ_R, tf_ext[1] */
+};
+enum { H2Y_ICTCP_THREADS = 512 };
+uint32_t h2y_ictcp_chunks(int in_kind, uint32_t npix); /* k_ictcp's units of H2Y_ICTCP_THREADS threads per frame */
+int h2y_ictcp_grid(int n_cu, uint64_t units);           /* blocks for so many units */
+hipError_t h2y_launch_ictcp(int in_kind, int grid, hipStream_t st, const ictcp_args &a, const gamut_frame *frames, int n_frames);
 
 /* k_hlg_linearize (h2y_hlgsrc.hip): the display light of frames of three u16 HLG code planes as binary32 planes G, B, R
  * (include/hdr2yuv_hip.h, "light of HLG code planes"); k_linearize's frame table */

@@ -8,7 +8,7 @@
  *                        reads a group with one 16-byte load per plane whose start is 16-byte aligned (u16 loads for a plane
  *                        that is not, and for the npix % 8 pixels behind the last group) and writes it with two 16-byte stores
  *                        per output plane, a half of four pixels as soon as it is worked out; the next step's codes are asked
- *                        for first.  MATRIX 0: G, B, R planes; 1: BT.709; 9: BT.2020nc.  No reduction, no LDS, no atomics.
+ *                        for first.  MATRIX 0: G, B, R planes; 1: BT.709; 9: BT.2020nc; 14: PQ ICtCp.  No reduction, no LDS, no atomics.
  *
  * Three table-tier PQ evaluations per pixel: the kernel is bound by them, not by its 18 bytes per pixel.  The next
  * kernel reads the planes at once, so the stores are plain ones (a 4K frame's 99.5 MB stays in the last-level cache).
@@ -112,5 +112,6 @@ hipError_t h2y_launch_linearize(int matrix, int grid, hipStream_t st, const code
     if (matrix == H2Y_MATRIX_BT2020NC) return launch_m<H2Y_MATRIX_BT2020NC>(grid, st, a, frames, n_frames);
     if (matrix == H2Y_MATRIX_BT709) return launch_m<H2Y_MATRIX_BT709>(grid, st, a, frames, n_frames);
     if (matrix == H2Y_MATRIX_GBR) return launch_m<H2Y_MATRIX_GBR>(grid, st, a, frames, n_frames);
+    if (matrix == H2Y_MATRIX_ICTCP) return launch_m<H2Y_MATRIX_ICTCP>(grid, st, a, frames, n_frames);
     return hipErrorInvalidValue;
 }

@@ -691,8 +691,9 @@ int codelight_check(h2y_ctx *ctx, const h2y_codelight_desc *d, codelight_plan &p
     if (d->chroma_format_idc == 2) return fail(ctx, H2Y_EUNSUPPORTED, "chroma_format_idc 2 (4:2:2) has no light on this path");
     if (d->chroma_format_idc != H2Y_CHROMA_420 && d->chroma_format_idc != H2Y_CHROMA_444)
         return fail(ctx, H2Y_EINVAL, "chroma_format_idc must be 1 or 3");
-    if (d->matrix_coeffs != H2Y_MATRIX_GBR && d->matrix_coeffs != H2Y_MATRIX_BT709 && d->matrix_coeffs != H2Y_MATRIX_BT2020NC)
-        return fail(ctx, H2Y_EUNSUPPORTED, "light of code planes: matrix_coeffs must be 0 (G,B,R), 1 (BT.709) or 9 (BT.2020nc), not %d", d->matrix_coeffs);
+    if (d->matrix_coeffs != H2Y_MATRIX_GBR && d->matrix_coeffs != H2Y_MATRIX_BT709 && d->matrix_coeffs != H2Y_MATRIX_BT2020NC &&
+        d->matrix_coeffs != H2Y_MATRIX_ICTCP)
+        return fail(ctx, H2Y_EUNSUPPORTED, "light of code planes: matrix_coeffs must be 0 (G,B,R), 1 (BT.709), 9 (BT.2020nc) or 14 (ICtCp), not %d", d->matrix_coeffs);
     if (d->width < 1 || d->height < 1 || (uint64_t)d->width * (uint64_t)d->height >= (1ull << 28)) return fail(ctx, H2Y_EINVAL, "bad picture size");
     if (d->bit_depth < 8 || d->bit_depth > 16) return fail(ctx, H2Y_EINVAL, "bit_depth must be 8..16");
     if (d->full_range != 0 && d->full_range != 1) return fail(ctx, H2Y_EINVAL, "full_range must be 0 or 1");
@@ -745,9 +746,14 @@ int codelight_tables(h2y_ctx *ctx, codelight_plan &p)
     return H2Y_OK;
 }
 
+static const char *matrix_name(int matrix)
+{
+    return matrix == H2Y_MATRIX_GBR ? "GBR" : matrix == H2Y_MATRIX_BT709 ? "BT709" : matrix == H2Y_MATRIX_ICTCP ? "ICTCP" : "BT2020NC";
+}
+
 static std::string codelight_variant(const codelight_plan &p, bool dist)
 {
-    return std::string("k_codelight<") + (p.matrix == H2Y_MATRIX_GBR ? "GBR" : p.matrix == H2Y_MATRIX_BT709 ? "BT709" : "BT2020NC") +
+    return std::string("k_codelight<") + matrix_name(p.matrix) +
            (dist ? ",DIST," : ",LIGHT,") + (!p.sub ? "444" : p.form == UP_FIR_TL ? "FIR_TL" : p.form == UP_FIR ? "FIR" : "REPLICATE") + ">";
 }
 
@@ -975,7 +981,7 @@ int h2y_codescenesig_batch(h2y_ctx *ctx, const h2y_codelight_desc *d, int n_fram
     });
     if (!rc) rc = scenesig_finish(ctx, ctx->d_scenesig, n_frames, p.a.npix, out);
     if (rc) return rc;
-    ctx->last_variant = std::string("k_codescenesig<") + (p.matrix == H2Y_MATRIX_GBR ? "GBR" : p.matrix == H2Y_MATRIX_BT709 ? "BT709" : "BT2020NC") + "," +
+    ctx->last_variant = std::string("k_codescenesig<") + matrix_name(p.matrix) + "," +
                         (!p.sub ? "444" : p.form == UP_FIR_TL ? "FIR_TL" : p.form == UP_FIR ? "FIR" : "REPLICATE") + ">";
     return H2Y_OK;
 }
@@ -1195,7 +1201,7 @@ static int deltae_args_of(h2y_ctx *ctx, codelight_plan &p, float threshold, delt
 
 static std::string deltae_variant(const codelight_plan &p)
 {
-    return std::string("k_deltae<") + (p.matrix == H2Y_MATRIX_GBR ? "GBR" : p.matrix == H2Y_MATRIX_BT709 ? "BT709" : "BT2020NC") + "," +
+    return std::string("k_deltae<") + matrix_name(p.matrix) + "," +
            (!p.sub ? "444" : p.form == UP_FIR_TL ? "FIR_TL" : p.form == UP_FIR ? "FIR" : "REPLICATE") + ">";
 }
 
@@ -1374,7 +1380,7 @@ int h2y_stream_deltae_result(h2y_ctx *ctx, h2y_deltae_stats *out)
 
 static std::string linearize_variant(const codelight_plan &p, bool hlg)
 {
-    return std::string(hlg ? "k_hlg_linearize<" : "k_linearize<") + (p.matrix == H2Y_MATRIX_GBR ? "GBR" : p.matrix == H2Y_MATRIX_BT709 ? "BT709" : "BT2020NC") + "," +
+    return std::string(hlg ? "k_hlg_linearize<" : "k_linearize<") + matrix_name(p.matrix) + "," +
            (!p.sub ? "444" : p.form == UP_FIR_TL ? "FIR_TL" : p.form == UP_FIR ? "FIR" : "REPLICATE") + ">";
 }
 
@@ -2468,6 +2474,7 @@ int h2y_stream_hlg(h2y_ctx *ctx, int peak, int relative)
     if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
     if (ctx->s_kind != h2y_ctx::RING_FORWARD) return fail(ctx, H2Y_EINVAL, "the HLG pass works on the forward rings only");
     if (ctx->s_stage[STAGE_HLG]) return fail(ctx, H2Y_EINVAL, "the ring writes HLG already");
+    if (ctx->s_stage[STAGE_ICTCP]) return fail(ctx, H2Y_EINVAL, "the ring writes ICtCp: its planes hold code values, not light");
     if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
     const h2y_desc *d = &ctx->s_desc;
     if (d->in_sample_type != H2Y_SAMPLE_F32)
@@ -2503,6 +2510,130 @@ int h2y_stream_hlg(h2y_ctx *ctx, int peak, int relative)
         for (int c = 0; c < 3; c++) tab[k].src[c] = tab[k].dst[c] = ctx->ss[k].d_in + c * ctx->s_plane_al;
     st->table(st->tab, tab);
     return stage_arm(ctx, STAGE_HLG, std::move(st), "HLG");
+}
+
+/* ---- ICtCp (--ictcp; the reference's matrix 14 is its unbuilt Y'u'v' variant): include/hdr2yuv_hip.h states the definition ------------ */
+
+/* k_ictcp's arguments for frames of width x height: H.273's scale of the depth and range, PQ10000_r's tables (what code1 reads of
+ * pix_params); the checks both entries share */
+static int ictcp_args_of(h2y_ctx *ctx, int width, int height, int sample_type, int dst_bit_depth, int dst_full_range, ictcp_args &a)
+{
+    if (sample_type == H2Y_SAMPLE_U16)
+        return fail(ctx, H2Y_EUNSUPPORTED, "the ICtCp pass works on display light in float or half planes, not on U16 samples");
+    if (sample_type != H2Y_SAMPLE_F32 && sample_type != H2Y_SAMPLE_F16) return fail(ctx, H2Y_EINVAL, "bad sample type %d", sample_type);
+    if (width < 1 || height < 1 || (uint64_t)width * (uint64_t)height >= (1ull << 28)) return fail(ctx, H2Y_EINVAL, "bad picture size");
+    if (dst_bit_depth < 8 || dst_bit_depth > 16) return fail(ctx, H2Y_EINVAL, "dst_bit_depth %d outside 8..16", dst_bit_depth);
+    if (dst_full_range != 0 && dst_full_range != 1) return fail(ctx, H2Y_EINVAL, "dst_full_range must be 0 or 1");
+    a = ictcp_args{};
+    a.npix = (uint32_t)width * (uint32_t)height;
+    const float s = (float)(1u << (dst_bit_depth - 8)), top = (float)((1u << dst_bit_depth) - 1u);
+    a.oY = dst_full_range ? top : 219.0f * s;
+    a.aY = dst_full_range ? 0.0f : 16.0f * s;
+    a.oC = dst_full_range ? top : 224.0f * s;
+    a.aC = dst_full_range ? (float)(1u << (dst_bit_depth - 1)) : 128.0f * s;
+    a.top = top;
+    return H2Y_OK;
+}
+
+/* PQ10000_r's tables into the arguments, on the context's device */
+static int ictcp_tables(h2y_ctx *ctx, ictcp_args &a)
+{
+    const int rc = ensure_tfn(ctx, H2Y_TFN_PQ_R);
+    if (rc) return rc;
+    a.pp = pix_params{};
+    a.pp.dst_tf = H2Y_TF_PQ;
+    a.pp.dst_fn = H2Y_TFN_PQ_R;
+    a.pp.tf_ext[1] = ctx->d_tfn_ext[H2Y_TFN_PQ_R];
+    a.table_r = ctx->d_tfn[H2Y_TFN_PQ_R];
+    return H2Y_OK;
+}
+
+int h2y_ictcp_batch(h2y_ctx *ctx, int width, int height, int sample_type, int dst_bit_depth, int dst_full_range, int n_frames,
+                    const void *const *d_src, void *const *d_dst)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
+    ictcp_args a{};
+    int rc = ictcp_args_of(ctx, width, height, sample_type, dst_bit_depth, dst_full_range, a);
+    if (rc) return rc;
+    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
+    if (!d_src || !d_dst) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
+    for (int f = 0; f < n_frames; f++)
+        for (int c = 0; c < 3; c++) {
+            const void *i = d_src[3 * f + c], *o = d_dst[3 * f + c];
+            if (!i || !o) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is null", f, c);
+            if (((uintptr_t)i | (uintptr_t)o) & 15u) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is not 16-byte aligned", f, c);
+            if (i == o && sample_type == H2Y_SAMPLE_F16)
+                return fail(ctx, H2Y_EINVAL, "frame %d: plane %d in place: half planes are widened, the float planes need room of their own", f, c);
+        }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    gamut_frame *h;
+    rc = frame_table(ctx, n_frames, h);
+    if (!rc) rc = ictcp_tables(ctx, a);
+    if (rc) return rc;
+    for (int f = 0; f < n_frames; f++)
+        for (int c = 0; c < 3; c++) h[f].src[c] = d_src[3 * f + c], h[f].dst[c] = d_dst[3 * f + c];
+    const int in_kind = sample_type == H2Y_SAMPLE_F16 ? H2Y_IN_F16 : H2Y_IN_F32;
+    const uint64_t per_frame = h2y_ictcp_chunks(in_kind, a.npix);
+    rc = timed_launches(ctx, h, n_frames, H2Y_ICTCP_FRAMES_PER_LAUNCH, "k_ictcp", [&](const gamut_frame *frames, int, int nf) {
+        return h2y_launch_ictcp(in_kind, h2y_ictcp_grid(ctx->n_cu, per_frame * nf), ctx->stream, a, frames, nf);
+    });
+    if (rc) return rc;
+    ctx->last_variant = in_kind == H2Y_IN_F16 ? "k_ictcp<F16>" : "k_ictcp<F32>";
+    return H2Y_OK;
+}
+
+/* The pass's ring stage, in place on a forward ring's decoded F32 planes after the gamut and tone-map stages' passes and before the
+ * conversion: k_ictcp's arguments (the table is the context's) and its frame table entry per slot. */
+struct ictcp_stage : ring_stage {
+    ictcp_args a{};
+    gamut_frame *tab = nullptr;
+    int grid = 1;
+    int decoded(h2y_ctx *ctx, int k) override
+    {
+        HIP_TRY(ctx, h2y_launch_ictcp(H2Y_IN_F32, grid, ctx->stream, a, tab + k, 1));
+        return H2Y_OK;
+    }
+    int run(h2y_ctx *, int) override { return H2Y_OK; }
+};
+
+int h2y_stream_ictcp(h2y_ctx *ctx)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    if (ctx->s_kind != h2y_ctx::RING_FORWARD) return fail(ctx, H2Y_EINVAL, "the ICtCp pass works on the forward rings only");
+    if (ctx->s_stage[STAGE_ICTCP]) return fail(ctx, H2Y_EINVAL, "the ring writes ICtCp already");
+    if (ctx->s_stage[STAGE_HLG]) return fail(ctx, H2Y_EINVAL, "the ring writes HLG: its planes hold code values, not light");
+    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    const h2y_desc *d = &ctx->s_desc;
+    if (d->in_sample_type != H2Y_SAMPLE_F32)
+        return fail(ctx, H2Y_EUNSUPPORTED, "the ICtCp pass leaves code-valued samples in the ring's decoded planes: they must be F32, not %s",
+                    d->in_sample_type == H2Y_SAMPLE_F16 ? "F16 (a half cannot hold them)" : "U16");
+    if (d->src_transfer != H2Y_TRANSFER_LINEAR || d->dst_transfer != H2Y_TRANSFER_LINEAR)
+        return fail(ctx, H2Y_EUNSUPPORTED, "the ICtCp pass is the ring's transfer: open it with src_transfer 8 and dst_transfer 8, not %d and %d",
+                    d->src_transfer, d->dst_transfer);
+    if (d->src_matrix != H2Y_MATRIX_GBR)
+        return fail(ctx, H2Y_EUNSUPPORTED, "the ICtCp pass needs a G,B,R source (src_matrix 0), not src_matrix %d", d->src_matrix);
+    if (d->dst_matrix != H2Y_MATRIX_GBR)
+        return fail(ctx, H2Y_EUNSUPPORTED, "the ICtCp pass is the ring's matrix: open it with dst_matrix 0, not dst_matrix %d", d->dst_matrix);
+    auto st = std::make_unique<ictcp_stage>();
+    int rc = ictcp_args_of(ctx, d->width, d->height, d->in_sample_type, d->dst_bit_depth, d->dst_full_range, st->a);
+    if (rc) return rc;
+    bool unit = d->stats_override == 1;
+    for (int c = 0; c < 3; c++) unit = unit && d->floor[c] == 0 && d->ceiling[c] == 1;
+    if (!unit)
+        return fail(ctx, H2Y_EINVAL, "the ICtCp pass is the passthrough flow's: open the ring with stats_override 1, floor 0 and ceiling 1 on "
+                                     "all three planes");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = ictcp_tables(ctx, st->a);
+    if (rc) return rc;
+    st->grid = h2y_ictcp_grid(ctx->n_cu, h2y_ictcp_chunks(H2Y_IN_F32, st->a.npix));
+    const int depth = (int)ctx->ss.size();
+    std::vector<gamut_frame> tab(depth);
+    for (int k = 0; k < depth; k++)
+        for (int c = 0; c < 3; c++) tab[k].src[c] = tab[k].dst[c] = ctx->ss[k].d_in + c * ctx->s_plane_al;
+    st->table(st->tab, tab);
+    return stage_arm(ctx, STAGE_ICTCP, std::move(st), "ICtCp");
 }
 
 /* ---- light of HLG code planes (--linearize 1 --src_hlg 1): include/hdr2yuv_hip.h states the definition ----------------------------- */
@@ -2552,6 +2683,8 @@ int h2y_hlg_inverse_planes(int peak, size_t npix, const float *const src[3], flo
 
 int hlgsrc_args_of(h2y_ctx *ctx, const codelight_plan &p, int peak, hlgsrc_args &a)
 {
+    if (p.matrix == H2Y_MATRIX_ICTCP)
+        return fail(ctx, H2Y_EUNSUPPORTED, "matrix_coeffs 14 (ICtCp) is PQ's here: BT.2100's HLG form of ICtCp has other coefficients and is not built");
     std::vector<float> tables(2u * H2Y_LIGHTDIST_BINS);
     double gamma;
     const char *why;

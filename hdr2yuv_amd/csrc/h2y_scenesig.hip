@@ -203,5 +203,6 @@ hipError_t h2y_launch_codescenesig(int matrix, hipStream_t st, const codelight_a
     if (matrix == H2Y_MATRIX_BT2020NC) return launch_m<H2Y_MATRIX_BT2020NC>(st, a, g, frames, n_frames, sig);
     if (matrix == H2Y_MATRIX_BT709) return launch_m<H2Y_MATRIX_BT709>(st, a, g, frames, n_frames, sig);
     if (matrix == H2Y_MATRIX_GBR) return launch_m<H2Y_MATRIX_GBR>(st, a, g, frames, n_frames, sig);
+    if (matrix == H2Y_MATRIX_ICTCP) return launch_m<H2Y_MATRIX_ICTCP>(st, a, g, frames, n_frames, sig);
     return hipErrorInvalidValue;
 }

@@ -200,7 +200,7 @@ struct ring_stage {
     virtual int run(h2y_ctx *ctx, int slot) = 0;          /* on the context's stream, after the frame was produced */
     virtual int download(h2y_ctx *, int) { return H2Y_OK; } /* the result, on s_d2h after the slot's ev_conv */
 };
-enum stage_id { STAGE_GAMUT, STAGE_TONEMAP, STAGE_HLG, STAGE_LIGHT, STAGE_LIGHTDIST, STAGE_CODELIGHT, STAGE_SCENESIG, STAGE_COMPARE, STAGE_SSIM, STAGE_DELTAE, STAGE_HISTOGRAM, STAGE_SCALE, STAGE_DITHER, STAGE_COUNT };
+enum stage_id { STAGE_GAMUT, STAGE_TONEMAP, STAGE_HLG, STAGE_ICTCP, STAGE_LIGHT, STAGE_LIGHTDIST, STAGE_CODELIGHT, STAGE_SCENESIG, STAGE_COMPARE, STAGE_SSIM, STAGE_DELTAE, STAGE_HISTOGRAM, STAGE_SCALE, STAGE_DITHER, STAGE_COUNT };
 
 struct h2y_ctx {
     int device = 0;

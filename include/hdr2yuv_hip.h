@@ -68,6 +68,10 @@ extern "C" {
  *    it emits.  Chroma resamplers 0 and 1 only: with any other value the reference reads uninitialised
  *    memory, and the descriptor is refused. */
 #define H2Y_MATRIX_YUVPRIME2 15
+/* H.273's matrix_coeffs 14, ICtCp (Rec. ITU-R BT.2100, PQ).  Accepted in h2y_codelight_desc.matrix_coeffs only ("light of ICtCp code
+ * planes" below): the reference's 14 is "YUVPrime1" (hdr.h:189), its unbuilt Y'u'v' variant, so h2y_desc_check goes on refusing it as a
+ * destination, and an ICtCp rung is written by the ICtCp pass ("ICtCp" below) on a passthrough descriptor. */
+#define H2Y_MATRIX_ICTCP 14
 
 /* error codes */
 #define H2Y_OK 0
@@ -754,7 +758,7 @@ typedef struct h2y_codelight_desc {
  * H2Y_CODELIGHT_FRAMES_PER_LAUNCH frames, each k_up444 per 4:2:0 frame and then one k_codelight (h2y_last_kernel_ms sums them,
  * upsampling included; h2y_last_kernel_name "k_codelight"; the variant names the matrix, DIST and the upsampling form, e.g.
  * "k_codelight<BT2020NC,DIST,FIR>"); synchronous.
- * H2Y_EUNSUPPORTED: chroma_format_idc 2, a matrix other than 0, 1, 9, siting 2 with replication.  H2Y_EINVAL: a bad size (4:2:0:
+ * H2Y_EUNSUPPORTED: chroma_format_idc 2, a matrix other than 0, 1, 9 and 14 (ICtCp, below), siting 2 with replication.  H2Y_EINVAL: a bad size (4:2:0:
  * odd, or above 32766), depth or alignment, full_range not 0 or 1, matrix 0 with 4:2:0. */
 int h2y_codelight_batch(h2y_ctx *ctx, const h2y_codelight_desc *d, int n_frames, const uint16_t *const *d_frames, h2y_light_stats *out,
                         h2y_lightdist_stats *dist_out, uint32_t *bins_out);
@@ -1307,6 +1311,75 @@ int h2y_hlg_linearize_batch(h2y_ctx *ctx, const h2y_codelight_desc *d, int peak,
  * for a peak outside 400..2000. */
 int h2y_hlgcode_stream_open(h2y_ctx *ctx, const h2y_desc *d, const h2y_codelight_desc *src, int peak, int depth);
 
+/* ---- ICtCp: display light written as a PQ ICtCp signal (Rec. ITU-R BT.2100; H.273 matrix_coeffs 14; --ictcp 1) -----------------------
+ * The reference has no ICtCp (its matrix 14 is its unbuilt Y'u'v' variant), so there are no bytes to match: this is the project's own
+ * definition, as HLG's is.  PQ constants only: BT.2100's HLG form of ICtCp has other coefficients and stays out.  A pass over the decoded
+ * source planes, after h2y_stream_gamut's and h2y_stream_tonemap's where those are armed, which leaves CODE-VALUED floats with the
+ * rounding half already added.  The ring is opened on the passthrough descriptor "HLG" uses with matrix 0 -- src_transfer ==
+ * dst_transfer == 8, src_matrix == dst_matrix == 0, equal primaries, stats_override 1 with floor 0 and ceiling 1 -- and the unchanged
+ * forward conversion then does the cast (convert.cpp:1159-1166), the chroma resampler on planes 1 and 2, top-left siting where set, and
+ * write_yuv.
+ * Input: planes G, B, R of display light in BT.2020 primaries, 1.0 = 10000 cd/m2.  A half is widened first (exact).
+ * Pixel, in binary32.  Every product, sum and difference is one round-to-nearest operation, left to right as written, never contracted
+ *   into a fused multiply-add:
+ *   1. for each of G, B, R: c' = c > 0 ? min(c, 1) : +0.0 (NaN, -0.0 and negatives become +0.0, +inf becomes 1);
+ *   2. l, m, s by step 2 of "Delta E ITP of PQ code planes" word for word, its clamp included:
+ *        l = clamp(((1688/4096 R) + (2146/4096 G)) + (262/4096 B)), m with 683, 2951, 462, s with 99, 309, 3688;
+ *   3. l' = PQ10000_r(l), m' and s' likewise: the forward conversion's own tiers (the table, the full-range table, the careful tier),
+ *      exactly as Delta E ITP's step 3;
+ *   4. I  = (0.5 l') + (0.5 m')
+ *      Ct = ((6610/4096 l') - (13613/4096 m')) + (7003/4096 s')      -- 2 T of Delta E ITP's step 4, bit for bit
+ *      Cp = ((17933/4096 l') - (17390/4096 m')) - (543/4096 s')      -- every constant is exact in binary32;
+ *   5. H.273's scale for n = dst_bit_depth, s = 2^(n-8): video range oY = 219 s, aY = 16 s, oC = 224 s, aC = 128 s; full range
+ *      oY = oC = 2^n - 1, aY = 0, aC = 2^(n-1).  These are NOT the conversion's mulY / addY (its habit of scaling B' and R' by the
+ *      chroma range): the ICtCp matrix acts on unscaled primes, and the way back normalises by H.273.
+ *        out0 = ((I oY) + aY) + 0.5,  out1 = ((Ct oC) + aC) + 0.5,  out2 = ((Cp oC) + aC) + 0.5,
+ *      each then min(max(v, 0), 2^n - 1).  The 0.5 makes the conversion's (unsigned int) cast a rounding; the clamp keeps a negative
+ *      from ever reaching that cast.
+ *   The outputs are F32 whatever the source's sample type: a half cannot hold code-valued samples.
+ * Anchors (10-bit video range): grey of 0 / 100 / 203 / 1000 / 10000 cd/m2 -> I 64 / 509 / 573 / 723 / 940 with Ct = Cp = 512; pure
+ *   BT.2020 red, green, blue at 1.0 -> (814, 334, 922), (895, 89, 408), (707, 766, 243) (tests/test_ictcp_host.py). */
+#define H2Y_ICTCP_FRAMES_PER_LAUNCH 64
+
+/* k_ictcp on n_frames device frames of width x height: d_src[f*3 + c] / d_dst[f*3 + c] are plane c = G, B, R of frame f, 16-byte
+ * aligned; the destination planes are F32 and receive I, Ct, Cp.  With H2Y_SAMPLE_F32 a d_dst entry may equal its d_src entry (in
+ * place; no other overlap); with H2Y_SAMPLE_F16 the planes are widened, and in place is refused (H2Y_EINVAL).  H2Y_SAMPLE_U16:
+ * H2Y_EUNSUPPORTED; a bad size, null or unaligned planes, dst_bit_depth (8..16) or dst_full_range out of range, a pending batch or an
+ * open stream: H2Y_EINVAL.  Launches of up to H2Y_ICTCP_FRAMES_PER_LAUNCH frames (h2y_last_kernel_ms sums them, h2y_last_kernel_name
+ * "k_ictcp", the variant "k_ictcp<F32>" or "k_ictcp<F16>"); synchronous. */
+int h2y_ictcp_batch(h2y_ctx *ctx, int width, int height, int sample_type, int dst_bit_depth, int dst_full_range, int n_frames,
+                    const void *const *d_src, void *const *d_dst);
+
+/* Arm an open forward ring whose decoded planes are F32 (h2y_stream_open with F32 planes, h2y_dpx_stream_open, h2y_pqcode_stream_open,
+ * h2y_hlgcode_stream_open) before its first input, once: k_ictcp then runs in place on every slot's decoded device planes, on the
+ * context's stream, after h2y_stream_gamut's and h2y_stream_tonemap's passes where those are armed (whichever was armed first), and
+ * before the conversion.  The scale is that of the ring's dst_bit_depth and dst_full_range.  The descriptor must be the passthrough
+ * flow's as stated above.  h2y_stream_light and h2y_stream_lightdist refuse such a ring (its dst_transfer is not 16): measure the
+ * written file ("light of ICtCp code planes").
+ * H2Y_EUNSUPPORTED where the planes are F16 or U16, for other transfers, a src_matrix other than 0 and a dst_matrix other than 0;
+ * H2Y_EINVAL on the other ring kinds, after the first input, on a ring armed already or armed with h2y_stream_hlg (which in turn
+ * refuses a ring armed here), and without that statistics override. */
+int h2y_stream_ictcp(h2y_ctx *ctx);
+
+/* ---- light of ICtCp code planes: h2y_codelight_desc.matrix_coeffs 14 (--src_ictcp 1) ----------------------------------------------
+ * The way back from the section above, for every entry that takes an h2y_codelight_desc for PQ codes: h2y_codelight_batch,
+ * h2y_codescenesig_batch, h2y_linearize_batch, h2y_deltae_batch, h2y_codelight_stream_open, h2y_pqcode_stream_open and
+ * h2y_stream_deltae accept matrix_coeffs H2Y_MATRIX_ICTCP, with chroma_format_idc 3, or 1 at even sizes; the variants are named ICTCP
+ * ("k_linearize<ICTCP,FIR>").  h2y_hlg_linearize_batch and h2y_hlgcode_stream_open refuse it (H2Y_EUNSUPPORTED): the HLG form of ICtCp
+ * is not built.  The project's own definition; every product, sum and difference is rounded by itself to binary32.
+ *   Steps 1-2 of "light of PQ code planes" are unchanged: I is normalised as Y is, Ct and Cp as cb and cr.
+ *   3i. L' = (I + a Ct) + b Cp;  M' = (I - a Ct) - b Cp;  S' = (I + c Ct) - d Cp, with a = 0.00860903703793, b = 0.111029625003,
+ *       c = 0.560031335711, d = 0.320627174987, each rounded once to binary32 (0x3C0D0CEB, 0x3DE36380, 0x3F0F5E37, 0x3EA4293F): the
+ *       exact inverse of step 4's matrix above.
+ *   4i. each of the three is clamped as step 4 of "light of PQ code planes" clamps and taken through PQ10000_f by the same tiers:
+ *       l, m, s.
+ *   5i. R = ((3.43660669433 l - 2.50645211866 m) + 0.0698454243232 s)     (0x405BF15D, 0x402069B6, 0x3D8F0B1E)
+ *       G = ((1.98360045179 m - 0.791329555599 l) - 0.192270896193 s)     (0x3FFDE69F, 0x3F4A9493, 0x3E44E2A9)
+ *       B = ((1.1248636144 s - 0.0259498996906 l) - 0.0989137147117 m)    (0x3F8FFB88, 0x3CD494E2, 0x3DCA9346)
+ *       the magnitudes rounded once to binary32: the exact inverse of the k / 4096 LMS matrix.  L_R, L_G, L_B are each
+ *       v > 0 ? min(v, 1) : +0.
+ *   From there nothing is new: the figures of k_codelight, the planes of k_linearize, the two sides of k_deltae. */
+
 /* ---- chroma siting: 4:2:0 chroma co-sited with the top-left luma sample (chroma_sample_loc_type 2; HDR10, UHD Blu-ray) -----------
  * The reference carries chroma_sample_loc_type through pic_t and prints it (hdr2yuv.cpp:490, :505); it parses no flag for it and
  * never acts on it.  Its two resamplers site the chroma as they happen to: the 2x2 box in the centre of the block both ways (loc
@@ -1383,7 +1456,7 @@ int h2y_upsample_444_sited(h2y_ctx *ctx, int width, int height, int chroma_sampl
                            const uint16_t *d_src, uint16_t *d_dst);
 
 /* Timing of the last h2y_convert_batch*() (or h2y_inverse_*, h2y_dpx_decode_batch, h2y_tiff_decode_batch,
- * h2y_rgb_interleave_batch, h2y_exr_decode_batch, h2y_compare_batch, h2y_ssim_batch, h2y_light_batch, h2y_lightdist_batch, h2y_codelight_batch, h2y_scenesig_batch, h2y_codescenesig_batch, h2y_linearize_batch, h2y_hlg_linearize_batch, h2y_scale_batch, h2y_gamut_batch, h2y_tonemap_batch, h2y_hlg_batch, h2y_dither_batch) call measured with HIP events on
+ * h2y_rgb_interleave_batch, h2y_exr_decode_batch, h2y_compare_batch, h2y_ssim_batch, h2y_light_batch, h2y_lightdist_batch, h2y_codelight_batch, h2y_scenesig_batch, h2y_codescenesig_batch, h2y_linearize_batch, h2y_hlg_linearize_batch, h2y_scale_batch, h2y_gamut_batch, h2y_tonemap_batch, h2y_hlg_batch, h2y_ictcp_batch, h2y_dither_batch) call measured with HIP events on
  * the stream the kernels ran on: total ms over the main kernels and how many
  * launches that covered. */
 int h2y_last_kernel_ms(const h2y_ctx *ctx, float *ms, int *launches);
@@ -1391,7 +1464,7 @@ int h2y_last_kernel_ms(const h2y_ctx *ctx, float *ms, int *launches);
 /* Name of the kernel those launches ran ("k_fused", "k_fused_t1", "k_fused_lut16",
  * "k_fused_narrow"; of the inverse entries "k_inverse", "k_inverse420", "k_inverse_batch", "k_inverse420_batch"; of
  * h2y_dpx_decode_batch "k_dpx_decode"; of h2y_tiff_decode_batch "k_tiff_decode", of h2y_rgb_interleave_batch
- * "k_rgb_interleave"; of h2y_exr_decode_batch "k_exr_decode"; of h2y_compare_batch "k_compare"; of h2y_scale_batch "k_scale"; of h2y_dither_batch "k_dither"; of h2y_gamut_batch "k_gamut"; of h2y_tonemap_batch "k_tonemap"; of h2y_hlg_batch "k_hlg"; of h2y_codelight_batch "k_codelight"; of h2y_scenesig_batch "k_scenesig"; of h2y_codescenesig_batch "k_codescenesig"; of h2y_linearize_batch "k_linearize"; of h2y_hlg_linearize_batch "k_hlg_linearize"): the name to
+ * "k_rgb_interleave"; of h2y_exr_decode_batch "k_exr_decode"; of h2y_compare_batch "k_compare"; of h2y_scale_batch "k_scale"; of h2y_dither_batch "k_dither"; of h2y_gamut_batch "k_gamut"; of h2y_tonemap_batch "k_tonemap"; of h2y_hlg_batch "k_hlg"; of h2y_ictcp_batch "k_ictcp"; of h2y_codelight_batch "k_codelight"; of h2y_scenesig_batch "k_scenesig"; of h2y_codescenesig_batch "k_codescenesig"; of h2y_linearize_batch "k_linearize"; of h2y_hlg_linearize_batch "k_hlg_linearize"): the name to
  * look for in a rocprofv3 kernel trace. */
 const char *h2y_last_kernel_name(const h2y_ctx *ctx);
 /* The same with its template arguments and launch shape, e.g. "k_fused_t1<F32,420BOX,YCBCR,PQ_IDENT> groups=8 xcd=1";

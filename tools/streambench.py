@@ -154,6 +154,18 @@ Prints one line per figure, then one JSON line with all of them.
      statistics override, unarmed and armed with h2y_stream_hlg, three times in turn.
 Prints one line per figure, then one JSON line with all of them.
 
+`streambench.py ictcp`: the ICtCp pass on 4K frames, beside k_hlg and k_gamut in the same job:
+  1. the kernel time of h2y_ictcp_batch (k_ictcp, 10-bit video-range scale) on 64 distinct device frames per call (HIP events, median
+     of five after a warm-up call): F32 out of place, F32 in place (the light is put back before every call) and F16 -> F32; beside
+     them h2y_hlg_batch (1000 cd/m2, absolute) and h2y_gamut_batch (BT.2020 -> BT.709) on the same F32 frames, out of place and in
+     place; the algorithmic bytes per frame -- 24 B/pixel for F32, 18 for F16 -> F32 -- over that time, their share of the 8 TB/s HBM
+     peak, and k_ictcp's time over k_hlg's and k_gamut's;
+  2. the way back: h2y_linearize_batch and h2y_codelight_batch (DIST) with matrix_coeffs 14 beside matrix_coeffs 9 on the same 64
+     10-bit 4:2:0 code frames (k_up444 included), taken in turn five times after a warm-up, and the ratios;
+  3. frames/s from host memory of the .f32 ring on the passthrough descriptor (equal transfers, matrix 0 -> 0) to 10-bit 4:2:0 with the
+     0 / 1 statistics override, unarmed and armed with h2y_stream_ictcp, three times in turn.
+Prints one line per figure, then one JSON line with all of them.
+
 `streambench.py siting`: top-left co-sited 4:2:0 chroma (chroma siting 2) on 4K frames, in one job:
   1. k_fir420 and k_fir420_tl through h2y_subsample_420_sited (loc 0 / loc 2) over the 128 distinct chroma planes of 64 frames, one
      launch per plane (HIP events; the two planes of a frame added up), five passes: median and spread in us per frame, and the
@@ -2264,6 +2276,133 @@ def hlg_main():
     print(json.dumps({"streambench_hlg": res}), flush=True)
 
 
+def ictcp_main():
+    import json
+
+    import torch
+
+    w, hh, nb, reps = 3840, 2160, 64, 5
+    n = w * hh
+    nf = int(os.environ.get("N", "60"))
+    depth = 3
+    ctx = h.Context(0)
+    res = {"width": w, "height": hh, "frames_per_call": nb, "reps": reps, "ring_frames": nf, "ring_depth": depth, "hbm_peak_tbs": 8.0}
+    hlg = (1000, 0, 10, 0, h.MATRIX_BT2020NC)
+
+    def timed(key, label, nbytes, call, before=None):
+        ks = []
+        for r in range(reps + 1):  # the first call warms up
+            if before:
+                before()
+            call()
+            if r:
+                ks.append(ctx.last_kernel_ms()[0] / nb)
+        k_ms = float(np.median(ks))
+        tbs = nbytes / (k_ms * 1e-3) / 1e12
+        res[key] = dict(kernel_us_per_frame=round(k_ms * 1e3, 2), min_us=round(min(ks) * 1e3, 2), max_us=round(max(ks) * 1e3, 2),
+                        bytes_per_frame=nbytes, kernel_tbs=round(tbs, 2), hbm_peak_fraction=round(tbs / 8.0, 3), variant=ctx.last_kernel_variant())
+        print(f"{label:34s} {nb} frames per call: {k_ms*1e3:7.2f} us/frame ({min(ks)*1e3:.2f}..{max(ks)*1e3:.2f})  {nbytes/1e6:6.1f} MB/frame  "
+              f"{tbs:5.2f} TB/s = {tbs/8.0*100:4.1f} % of 8 TB/s  {ctx.last_kernel_variant()}", flush=True)
+        return k_ms
+
+    # 1. k_ictcp beside k_hlg and k_gamut over the same 64 distinct F32 frames on the device, out of place, then in place; then F16
+    src = [[torch.rand(n, device="cuda") ** 3 for _ in range(3)] for _ in range(nb)]
+    dst = [[torch.empty(n, dtype=torch.float32, device="cuda") for _ in range(3)] for _ in range(nb)]
+    torch.cuda.synchronize()
+    b32 = 2 * 3 * n * 4  # 24 algorithmic bytes a pixel
+    i_out = timed("k_ictcp_f32_out_of_place", "k_ictcp f32 out of place", b32, lambda: ctx.ictcp_batch(w, hh, h.SAMPLE_F32, 10, 0, src, dst))
+    h_out = timed("k_hlg_f32_out_of_place", "k_hlg f32 out of place", b32, lambda: ctx.hlg_batch(w, hh, h.SAMPLE_F32, *hlg, src, dst))
+    g_out = timed("k_gamut_f32_out_of_place", "k_gamut f32 out of place", b32, lambda: ctx.gamut_batch(w, hh, h.SAMPLE_F32, 9, 1, 1, src, dst))
+    keep = [[p.clone() for p in f] for f in src]
+
+    def put_back():  # the in-place passes leave code values: the light comes back before each call
+        for f, g in zip(src, keep):
+            for a, b in zip(f, g):
+                a.copy_(b)
+        torch.cuda.synchronize()
+
+    i_in = timed("k_ictcp_f32_in_place", "k_ictcp f32 in place", b32, lambda: ctx.ictcp_batch(w, hh, h.SAMPLE_F32, 10, 0, src), before=put_back)
+    h_in = timed("k_hlg_f32_in_place", "k_hlg f32 in place", b32, lambda: ctx.hlg_batch(w, hh, h.SAMPLE_F32, *hlg, src), before=put_back)
+    put_back()
+    timed("k_gamut_f32_in_place", "k_gamut f32 in place", b32, lambda: ctx.gamut_batch(w, hh, h.SAMPLE_F32, 9, 1, 1, src))
+    del src, keep
+    torch.cuda.empty_cache()
+    half = [[(torch.rand(n, device="cuda") ** 3).to(torch.float16) for _ in range(3)] for _ in range(nb)]
+    torch.cuda.synchronize()
+    timed("k_ictcp_f16_to_f32", "k_ictcp f16 -> f32", 3 * n * (2 + 4), lambda: ctx.ictcp_batch(w, hh, h.SAMPLE_F16, 10, 0, half, dst))
+    res["k_ictcp_over_k_hlg"] = dict(out_of_place=round(i_out / h_out, 3), in_place=round(i_in / h_in, 3))
+    res["k_ictcp_over_k_gamut_out_of_place"] = round(i_out / g_out, 3)
+    print(f"k_ictcp / k_hlg: out of place {i_out/h_out:.3f}, in place {i_in/h_in:.3f}; k_ictcp / k_gamut out of place {i_out/g_out:.3f}", flush=True)
+    del half
+    torch.cuda.empty_cache()
+
+    # 2. the way back: k_linearize and k_codelight on ICtCp codes beside their BT.2020nc forms, the same code frames, in turn
+    def codes(count, lo, hi):
+        return torch.randint(lo, hi + 1, (count,), dtype=torch.int32, device="cuda").to(torch.int16)
+
+    frames = [torch.cat([codes(n, 64, 940), codes(n // 4, 384, 640), codes(n // 4, 384, 640)]) for _ in range(nb)]
+    torch.cuda.synchronize()
+    t, variants = {}, {}
+    descs = {"ICTCP": h.make_codelight_desc(w, hh, 1, 10, 0, h.MATRIX_ICTCP, 1), "BT2020NC": h.make_codelight_desc(w, hh, 1, 10, 0, h.MATRIX_BT2020NC, 1)}
+    for rep in range(reps + 1):  # the first round warms up
+        for name, d in descs.items():
+            for kernel, call in (("k_linearize", lambda: ctx.linearize_batch(d, frames, dst)), ("k_codelight", lambda: ctx.codelight_batch(d, frames, dist=True))):
+                call()
+                variants[kernel, name] = ctx.last_kernel_variant()
+                if rep:
+                    t.setdefault((kernel, name), []).append(ctx.last_kernel_ms()[0] / nb)
+    for kernel, nbytes in (("k_linearize", 23 * n), ("k_codelight", 11 * n)):
+        med = {}
+        for name in descs:
+            ks = t[kernel, name]
+            med[name] = float(np.median(ks))
+            tbs = nbytes / (med[name] * 1e-3) / 1e12
+            res[f"{kernel}_{name}_420_10"] = dict(kernel_us_per_frame=round(med[name] * 1e3, 2), min_us=round(min(ks) * 1e3, 2), max_us=round(max(ks) * 1e3, 2),
+                                                 bytes_per_frame=nbytes, kernel_tbs=round(tbs, 2), variant=variants[kernel, name])
+            print(f"{kernel} {name:9s} 4:2:0 10 bit, upsampling included: {med[name]*1e3:7.2f} us/frame ({min(ks)*1e3:.2f}..{max(ks)*1e3:.2f})  "
+                  f"{variants[kernel, name]}", flush=True)
+        res[f"{kernel}_ictcp_over_bt2020nc"] = round(med["ICTCP"] / med["BT2020NC"], 3)
+        print(f"{kernel}<ICTCP> / {kernel}<BT2020NC>: {med['ICTCP']/med['BT2020NC']:.3f}", flush=True)
+    del frames, dst
+    torch.cuda.empty_cache()
+
+    # 3. the .f32 ring from host memory on the passthrough descriptor, unarmed and armed
+    planes = [(np.random.default_rng(31 + c).random(n, dtype=np.float32) ** 3) for c in range(3)]
+    d32 = h.make_desc(w, hh, dst_depth=10, src_transfer=8, dst_transfer=8, dst_matrix=h.MATRIX_GBR, resampler=1, stats=[(0, 1)] * 3)
+
+    def ring(arm):
+        ctx.stream_open(d32, depth)
+        if arm:
+            ctx.stream_ictcp()
+        inflight = 0
+        t0 = time.perf_counter()
+        for _ in range(nf):
+            slot = ctx.stream_input()
+            for c in range(3):
+                slot[c][:] = planes[c]
+            ctx.stream_submit()
+            inflight += 1
+            if inflight == depth - 1:
+                ctx.stream_output()
+                inflight -= 1
+        while inflight:
+            ctx.stream_output()
+            inflight -= 1
+        dt = (time.perf_counter() - t0) / nf
+        ctx.stream_close()
+        return dt
+
+    ring(False)  # warm-up
+    res["f32"] = []
+    for _ in range(3):  # unarmed and armed in turn: what the card drifts by shows in both alike
+        t_plain, t_armed = ring(False), ring(True)
+        res["f32"].append(dict(unarmed_fps=round(1 / t_plain, 1), armed_fps=round(1 / t_armed, 1), armed_share=round(t_plain / t_armed, 3)))
+        print(f"f32          ring from host memory: unarmed {1/t_plain:6.1f} frames/s   armed {1/t_armed:6.1f} frames/s "
+              f"({t_plain/t_armed*100:5.1f} %)", flush=True)
+    ctx.close()
+    print(json.dumps({"streambench_ictcp": res}), flush=True)
+
+
 def siting_main():
     import json
 
@@ -2357,6 +2496,8 @@ if __name__ == "__main__":
         tonemap_main()
     elif sys.argv[1:] == ["hlg"]:
         hlg_main()
+    elif sys.argv[1:] == ["ictcp"]:
+        ictcp_main()
     elif sys.argv[1:] == ["hlgsrc"]:
         hlgsrc_main()
     elif sys.argv[1:] == ["scale"]:
