@@ -8,7 +8,7 @@ import subprocess
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-RESULTS = ("compare", "ssim", "histogram", "light")
+RESULTS = ("compare", "ssim", "deltae", "histogram", "light", "lightdist", "scenesig")
 
 
 # ---- the ring -------------------------------------------------------------------------------------------------------------
@@ -17,7 +17,9 @@ def drive_ring(ctx, inputs, depth, *, refs=None, results=()):
     """Every frame of inputs through the ring that ctx has open (and armed), with depth - 1 frames in flight; closes the ring.
     inputs[k]: one entry per plane of stream_input()'s slot, an array (dst[:] = src) or a callable src(dst); or one callable
     fill(slots).  refs[k] is written to stream_reference() before frame k's submit.  results: which stream_<name>_result() to
-    collect with each output, from RESULTS.  Returns per frame, in output order, {"out": a copy or None, <name>: the result}."""
+    collect with each output, from RESULTS ("histogram": the stats and a copy of the bins; "lightdist": the stats and a copy of
+    stream_lightdist_bins(); "light" and "lightdist" are also what a light-only ring returns).  Returns per frame, in output order,
+    {"out": a copy or None, <name>: the result}."""
     assert depth >= 2 and set(results) <= set(RESULTS), (depth, results)
     recs, inflight = [], 0
 
@@ -26,7 +28,11 @@ def drive_ring(ctx, inputs, depth, *, refs=None, results=()):
         rec = {"out": None if o is None else o.copy()}
         for name in results:
             r = getattr(ctx, f"stream_{name}_result")()
-            rec[name] = (r[0], r[1].copy()) if name == "histogram" else r  # the bins are the ring's own memory
+            if name == "histogram":
+                r = (r[0], r[1].copy())  # the bins are the ring's own memory
+            elif name == "lightdist":
+                r = (r, ctx.stream_lightdist_bins().copy())
+            rec[name] = r
         recs.append(rec)
 
     try:

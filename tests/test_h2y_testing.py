@@ -55,6 +55,20 @@ class FakeRing:
     def stream_light_result(self):
         return self._result("light")
 
+    def stream_deltae_result(self):
+        return self._result("deltae")
+
+    def stream_scenesig_result(self):
+        return self._result("scenesig")
+
+    def stream_lightdist_result(self):
+        return self._result("lightdist")
+
+    def stream_lightdist_bins(self):
+        self.calls.append("lightdist_bins")
+        self.dist_bins = np.full(3, self.last[0])
+        return self.dist_bins
+
     def stream_histogram_result(self):
         self.calls.append("histogram")
         self.bins = np.full(2, self.last[0])
@@ -110,6 +124,41 @@ def test_drive_ring_references_and_results(depth, n):
     for i, c in enumerate(ring.calls):  # the results follow their output
         if c == "output":
             assert ring.calls[i + 1:i + 3] == ["compare", "histogram"]
+
+
+@pytest.mark.parametrize("depth", [2, 3, 4])
+@pytest.mark.parametrize("n", [1, 2, 5])
+def test_drive_ring_every_result(depth, n):
+    """all of RESULTS at once, in the caller's order; the light distribution comes with a copy of its bins, as the histogram does"""
+    assert set(ht.RESULTS) == {"compare", "ssim", "deltae", "histogram", "light", "lightdist", "scenesig"}
+    ring = FakeRing(depth, has_output=False)
+    refs = [np.array([7 + k, 0]) for k in range(n)]
+    names = ("scenesig", "lightdist", "deltae", "light", "compare", "ssim", "histogram")
+    recs = ht.drive_ring(ring, _frames(n), depth, refs=refs, results=names)
+    assert ring.closed == 1 and len(recs) == n
+    for k, r in enumerate(recs):
+        assert set(r) == {"out", *names} and r["out"] is None
+        for name in ("scenesig", "deltae", "light", "compare", "ssim"):
+            assert r[name] == (name, k, 7 + k)  # frame k's result, and frame k's reference was in place at its submit
+        assert r["lightdist"][0] == ("lightdist", k, 7 + k) and list(r["lightdist"][1]) == [k, k, k]
+        assert r["lightdist"][1] is not ring.dist_bins  # a copy, whatever the ring does with its own
+        assert r["histogram"][0] == ("histogram", k) and list(r["histogram"][1]) == [k, k]
+        assert r["histogram"][1] is not ring.bins
+    for name in names + ("lightdist_bins",):
+        assert ring.calls.count(name) == n, name
+    for i, c in enumerate(ring.calls):  # the results follow their output, in the order asked for, the bins with their distribution
+        if c == "output":
+            assert ring.calls[i + 1:i + 9] == ["scenesig", "lightdist", "lightdist_bins", "deltae", "light", "compare", "ssim", "histogram"]
+
+
+def test_drive_ring_light_only_ring_results():
+    """a light-only ring has no output and no reference: light and the distribution are collected all the same"""
+    ring = FakeRing(3, has_output=False)
+    recs = ht.drive_ring(ring, _frames(4), 3, results=("light", "lightdist", "scenesig"))
+    assert "reference" not in ring.calls
+    for k, r in enumerate(recs):
+        assert r["out"] is None and r["light"][:2] == ("light", k) and r["scenesig"][:2] == ("scenesig", k)
+        assert r["lightdist"][0][:2] == ("lightdist", k) and list(r["lightdist"][1]) == [k] * 3
 
 
 def test_drive_ring_whole_slot_callable():
