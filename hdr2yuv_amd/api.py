@@ -48,6 +48,7 @@ EXPORTS = [
     "h2y_dither_offsets", "h2y_dither_batch", "h2y_stream_dither", "h2y_dither_stream_open",
     "h2y_gamut_matrix", "h2y_gamut_batch", "h2y_stream_gamut",
     "h2y_tonemap_curve", "h2y_tonemap_batch", "h2y_stream_tonemap",
+    "h2y_lut3d_parse", "h2y_lut3d_free", "h2y_lut3d_info", "h2y_lut3d_nodes", "h2y_lut3d_planes", "h2y_lut3d_batch", "h2y_stream_lut3d",
     "h2y_hlg_tables", "h2y_hlg_planes", "h2y_hlg_batch", "h2y_stream_hlg",
     "h2y_hlg_inverse_tables", "h2y_hlg_inverse_planes", "h2y_hlg_linearize_batch", "h2y_hlgcode_stream_open",
     "h2y_ictcp_batch", "h2y_stream_ictcp",
@@ -71,6 +72,9 @@ DELTAE_FRAMES_PER_LAUNCH = 4  # the same scratch again: four upsampled chroma pl
 SCALE_FRAMES_PER_LAUNCH = 64
 GAMUT_FRAMES_PER_LAUNCH = 64
 TONEMAP_FRAMES_PER_LAUNCH = 64
+LUT3D_FRAMES_PER_LAUNCH = 64
+LUT3D_TRILINEAR, LUT3D_TETRAHEDRAL = 0, 1
+LUT3D_PLANES, LUT3D_SIGNAL = 0, 1
 HLG_FRAMES_PER_LAUNCH = 64
 HLG_PEAK_MIN, HLG_PEAK_MAX = 400, 2000
 ICTCP_FRAMES_PER_LAUNCH = 64
@@ -564,6 +568,20 @@ def load_library():
     L.h2y_tonemap_curve.restype = C.c_int
     L.h2y_tonemap_batch.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.h2y_tonemap_batch.restype = C.c_int
+    L.h2y_lut3d_parse.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_char_p)]
+    L.h2y_lut3d_parse.restype = C.c_int
+    L.h2y_lut3d_free.argtypes = [C.c_void_p]
+    L.h2y_lut3d_free.restype = None
+    L.h2y_lut3d_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_char_p)]
+    L.h2y_lut3d_info.restype = C.c_int
+    L.h2y_lut3d_nodes.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    L.h2y_lut3d_nodes.restype = C.c_int
+    L.h2y_lut3d_planes.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.h2y_lut3d_planes.restype = C.c_int
+    L.h2y_lut3d_batch.argtypes = [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.h2y_lut3d_batch.restype = C.c_int
+    L.h2y_stream_lut3d.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+    L.h2y_stream_lut3d.restype = C.c_int
     L.h2y_hlg_tables.argtypes = [C.c_int] * 2 + [C.POINTER(C.c_float)] * 3 + [C.POINTER(C.c_double), C.POINTER(C.c_char_p)]
     L.h2y_hlg_tables.restype = C.c_int
     L.h2y_hlg_planes.argtypes = [C.c_int] * 6 + [C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
@@ -820,6 +838,61 @@ def tonemap_curve(src_peak: int, dst_peak: int, relative: int):
     return gain, np.float32(cap.value)
 
 
+class Lut3d:
+    """A parsed .cube table (h2y_lut3d_parse; host only, no device): n, lo and hi (float32 triples r, g, b), title, nodes() and
+    planes().  Raises H2YError with the parser's reason (EUNSUPPORTED: a 1D or shaper + 3D file; EINVAL: malformed)."""
+
+    def __init__(self, text):
+        data = text.encode() if isinstance(text, str) else bytes(text)
+        self.lib = load_library()
+        self.h = C.c_void_p()
+        why = C.c_char_p()
+        rc = self.lib.h2y_lut3d_parse(data, len(data), C.byref(self.h), C.byref(why))
+        if rc != H2Y_OK:
+            raise H2YError(rc, (why.value or b"").decode(errors="replace"))
+        n, dom, title = C.c_int(), (C.c_float * 6)(), C.c_char_p()
+        self.lib.h2y_lut3d_info(self.h, C.byref(n), dom, C.byref(title))
+        self.n = n.value
+        self.lo = np.array(dom[:3], np.float32)
+        self.hi = np.array(dom[3:], np.float32)
+        self.title = (title.value or b"").decode(errors="replace")
+
+    def close(self):
+        if self.h:
+            self.lib.h2y_lut3d_free(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def nodes(self):
+        """the float32 (n, n, n, 3) node values as parsed, indexed [b][g][r][channel r, g, b]: the file's order"""
+        out = np.zeros(3 * self.n ** 3, np.float32)
+        rc = self.lib.h2y_lut3d_nodes(self.h, out.ctypes.data_as(C.POINTER(C.c_float)))
+        if rc != H2Y_OK:
+            raise H2YError(rc, (self.lib.h2y_last_error(None) or b"").decode())
+        return out.reshape(self.n, self.n, self.n, 3)
+
+    def planes(self, planes, interp=1, signal=0, dst_bit_depth=10, dst_full_range=0, dst_matrix=9):
+        """h2y_lut3d_planes (host only, no device): the pass on three numpy planes G, B, R of float32 or float16; returns the three
+        planes k_lut3d writes for them: the source's type in planes mode, float32 in signal mode."""
+        src = [np.ascontiguousarray(p) for p in planes]
+        dt = src[0].dtype
+        if len(src) != 3 or dt not in (np.float32, np.float16) or any(p.dtype != dt or p.shape != src[0].shape for p in src):
+            raise ValueError("three planes of one shape, float32 or float16")
+        out = [np.empty(p.shape, np.float32 if signal else dt) for p in src]
+        ins = (C.c_void_p * 3)(*[p.ctypes.data for p in src])
+        outs = (C.c_void_p * 3)(*[p.ctypes.data for p in out])
+        rc = self.lib.h2y_lut3d_planes(self.h, int(interp), int(signal), int(dst_bit_depth), int(dst_full_range), int(dst_matrix),
+                                       SAMPLE_F16 if dt == np.float16 else SAMPLE_F32, src[0].size, ins, outs)
+        if rc != H2Y_OK:
+            raise H2YError(rc, (self.lib.h2y_last_error(None) or b"").decode())
+        return out
+
+
 def hlg_tables(peak: int, relative: int):
     """h2y_hlg_tables (host only, no device): (gain, oetf, k, gamma) -- the two float32 tables of LIGHTDIST_BINS entries of the HLG pass
     at a nominal peak of `peak` cd/m2 (the inverse OOTF's gain, the OETF), the float32 factor k that brings a sample to units of the
@@ -917,7 +990,7 @@ class Context:
             raise H2YError(rc, (self.lib.h2y_last_error(self.h) or b"").decode())
 
     def set_option(self, name: str, value) -> None:
-        """h2y_ctx_set_option: "t1", "groups", "cols8", "balance", "fir" (tuning / test knobs; output bytes never change)."""
+        """h2y_ctx_set_option: "t1", "groups", "cols8", "lut3d_lds", "balance", "fir" (tuning / test knobs; output bytes never change)."""
         self._check(self.lib.h2y_ctx_set_option(self.h, name.encode(), str(value).encode()))
 
     def set_chroma_siting(self, chroma_sample_loc_type: int) -> None:
@@ -1316,6 +1389,25 @@ class Context:
                 outs[3 * f + c] = self._ptr(frames_dst[f][c])
         self._check(self.lib.h2y_tonemap_batch(self.h, width, height, sample, src_peak, dst_peak, relative, n, ins, outs))
 
+    def lut3d_batch(self, width, height, sample, lut, interp, signal, dst_bit_depth, dst_full_range, dst_matrix, frames_src,
+                    frames_dst=None) -> None:
+        """k_lut3d on device frames (frames_src[f] = three device planes G, B, R of float or half samples, 16-byte aligned):
+        frames_dst[f] receives the Lut3d's value at every pixel, tetrahedral (interp 1) or trilinear (0); in planes mode (signal 0) in
+        the source's type, in signal mode as float planes of code values scaled as a conversion to (dst_bit_depth, dst_full_range,
+        dst_matrix) scales; frames_dst None: in place (signal mode: float planes only)."""
+        frames_dst = frames_src if frames_dst is None else frames_dst
+        n = len(frames_src)
+        if len(frames_dst) != n:
+            raise ValueError("frames_src and frames_dst differ in length")
+        ins = (C.c_void_p * max(3 * n, 1))()
+        outs = (C.c_void_p * max(3 * n, 1))()
+        for f in range(n):
+            for c in range(3):
+                ins[3 * f + c] = self._ptr(frames_src[f][c])
+                outs[3 * f + c] = self._ptr(frames_dst[f][c])
+        self._check(self.lib.h2y_lut3d_batch(self.h, width, height, sample, lut.h if lut is not None else None, interp, signal,
+                                             dst_bit_depth, dst_full_range, dst_matrix, n, ins, outs))
+
     def hlg_batch(self, width, height, sample, peak, relative, dst_bit_depth, dst_full_range, dst_matrix, frames_src,
                   frames_dst=None) -> None:
         """k_hlg on device frames (frames_src[f] = three device planes G, B, R of float or half display light, 16-byte aligned):
@@ -1356,6 +1448,13 @@ class Context:
         == 8, src_matrix == dst_matrix == 0 and the 0 / 1 statistics override: every slot's decoded planes become code-valued PQ
         I, Ct, Cp samples in place, after stream_gamut's and stream_tonemap's passes, before the conversion (h2y_stream_ictcp)."""
         self._check(self.lib.h2y_stream_ictcp(self.h))
+
+    def stream_lut3d(self, lut, interp=1, signal=0) -> None:
+        """Arm an open forward ring of float or half planes (plain, DPX, EXR, PQ or HLG code) that was opened with src_matrix 0 and the
+        0 / 1 statistics override: the Lut3d is applied to every slot's decoded planes in place, after stream_gamut's and
+        stream_tonemap's passes, before stream_hlg's / stream_ictcp's and the conversion; signal 1 needs float planes and equal
+        transfers (h2y_stream_lut3d)."""
+        self._check(self.lib.h2y_stream_lut3d(self.h, lut.h if lut is not None else None, interp, signal))
 
     def stream_hlg(self, peak, relative) -> None:
         """Arm an open forward ring of float planes (plain F32, DPX or PQ code) that was opened with src_transfer == dst_transfer == 8

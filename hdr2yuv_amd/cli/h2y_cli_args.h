@@ -115,6 +115,20 @@
  *             primaries other than 8 / 9 at the pass, --dst_matrix_coeffs other than 0 / 9 (and 0 with primaries codes that
  *             differ: the library refuses that descriptor as the reference does, convert.cpp:1195), .rgb / .tiff destinations and the .yuv ->
  *             RGB flow, every *_only flow, --content_light, --dynamic_metadata and the scene flags (their light is PQ's), --delta_e.
+ * --lut3d FILE.cube [--lut3d_interp 0|1] [--lut3d_signal 0|1] (an addition; the reference has no LUT step): the decoded source planes,
+ *             after --gamut_convert's and --tone_map's passes where those are given, go through the .cube table on the device
+ *             (include/hdr2yuv_hip.h, "3D LUT", states every step), tetrahedral (1, the default) or trilinear (0).  --lut3d_signal 0
+ *             (planes, the default): the result stands where the source's samples stood, in the source's transfer and normalisation,
+ *             and the unchanged forward conversion follows.  --lut3d_signal 1 (signal): the result is the destination's R'G'B' signal
+ *             in [0, 1]; the run becomes the passthrough flow, the way --hlg 1 makes it one: its destination transfer becomes the
+ *             source's, and a --dst_transfer_characteristics given is only printed, as lut3d_dst_transfer:.  Either way the run
+ *             takes floor 0 and ceiling 1 for every frame.  On the forward flow to .yuv from .f32, .f16, .exr, .dpx and --linearize 1
+ *             sources, beside every flag the --tone_map path accepts, for any --gpus, with or without --dst_filename.  The banner
+ *             carries lut3d:, lut3d_title:, lut3d_size:, lut3d_domain:, lut3d_interp: and lut3d_signal:.  Refused (exit 1, also
+ *             under --dry_run): an unreadable or malformed file, with the parser's reason; the sub-flags without --lut3d or other
+ *             than 0 / 1; .tiff, .rgb or .yuv input without --linearize 1; a source matrix other than 0; the .yuv -> RGB flow and
+ *             every *_only flag; --lut3d_signal 1 beside --hlg 1, --ictcp 1, --content_light 1, --dynamic_metadata, a half source,
+ *             or a --dst_matrix_coeffs other than 0 / 9.
  * --ictcp 1 (an addition; the reference's matrix list has MATRIX_YUVPRIME1 at H.273's code 14, which is ICtCp): the forward flow writes a PQ
  *             ICtCp rung (Rec. ITU-R BT.2100).  The decoded source planes, display light in BT.2020 primaries with 1.0 = 10000 cd/m2
  *             after --gamut_convert's and --tone_map's passes where those are given (the mapper's output is then absolute), become
@@ -284,6 +298,13 @@ struct cli_args {
      * it (-1: not given) */
     int hlg = 0, hlg_peak = 1000, hlg_relative = 0, hlg_dst_transfer = -1;
     bool hlg_given = false, hlg_peak_given = false;
+    /* --lut3d FILE.cube [--lut3d_interp 0|1] [--lut3d_signal 0|1]: the table is applied to the decoded source planes; resolved:
+     * lut3d_table (parsed by cli_resolve_lut3d, the run's until it ends) and lut3d_dst_transfer, what --dst_transfer_characteristics
+     * gave before signal mode replaced it with the source's (-1: not given) */
+    const char *lut3d = nullptr;
+    int lut3d_interp = 1, lut3d_signal = 0, lut3d_dst_transfer = -1;
+    bool lut3d_interp_given = false, lut3d_signal_given = false;
+    h2y_lut3d *lut3d_table = nullptr;
     /* --dst_chroma_sample_loc_type: 0 as the resampler sites the 4:2:0 chroma, 2 top-left */
     int siting = 0;
     bool siting_given = false;
@@ -415,6 +436,10 @@ static inline void cli_help()
            "  ICtCp: [--ictcp 1] (the rung is PQ I, Ct, Cp, BT.2100 / H.273 matrix_coeffs 14, from float G,B,R planes of display light;\n"
            "  it replaces --dst_matrix_coeffs and --dst_transfer_characteristics); [--src_ictcp 1] beside --linearize 1, --light_only 1 or\n"
            "  --compare_only 1 --delta_e 1 (the .yuv holds PQ I, Ct, Cp codes; it replaces --src_matrix_coeffs)\n"
+           "  3D LUT: [--lut3d FILE.cube [--lut3d_interp 0|1] [--lut3d_signal 0|1]] (a .cube table applied to the float or half G,B,R\n"
+           "  source planes on the GPU, after --gamut_convert's and --tone_map's passes, 1 tetrahedral by default, 0 trilinear; signal 0:\n"
+           "  the result stands where the source's samples stood and the conversion follows; signal 1: it is the destination's R'G'B'\n"
+           "  signal in [0, 1], float sources only, and the destination's transfer is the LUT's)\n"
            "  HLG: [--hlg 1 [--hlg_peak L]] (the rung is Hybrid Log-Gamma, ARIB STD-B67 / BT.2100: float G,B,R source planes of display light\n"
            "  in BT.2020 primaries through the inverse OOTF at a nominal peak of L cd/m2, 400..2000, 1000 by default, and the OETF on the\n"
            "  GPU; it replaces --dst_transfer_characteristics, whose 18 is RHO_GAMMA in this program, not H.273's HLG)\n"
@@ -477,6 +502,9 @@ static inline void cli_parse(cli_args &a, int argc, char **argv)
         else if (is("--ictcp")) { a.ictcp = atoi(val()); a.ictcp_given = true; }
         else if (is("--src_ictcp")) { a.src_ictcp = atoi(val()); a.src_ictcp_given = true; }
         else if (is("--hlg_peak")) { a.hlg_peak = atoi(val()); a.hlg_peak_given = true; }
+        else if (is("--lut3d")) a.lut3d = val();
+        else if (is("--lut3d_interp")) { a.lut3d_interp = atoi(val()); a.lut3d_interp_given = true; }
+        else if (is("--lut3d_signal")) { a.lut3d_signal = atoi(val()); a.lut3d_signal_given = true; }
         else if (is("--dst_chroma_sample_loc_type")) { a.siting = atoi(val()); a.siting_given = true; }
         else if (is("--src_chroma_sample_loc_type")) { a.src_siting = atoi(val()); a.src_siting_given = true; }
         else if (is("--histogram")) a.hist = val();
@@ -663,6 +691,7 @@ static inline int cli_resolve_scale(cli_args &a);
 static inline int cli_resolve_gamut(cli_args &a, int src_matrix_arg);
 static inline int cli_resolve_tone_map(cli_args &a, int src_matrix_arg);
 static inline int cli_resolve_hlg(cli_args &a, int src_matrix_arg);
+static inline int cli_resolve_lut3d(cli_args &a, int src_matrix_arg);
 /* is m the matrix --src_ictcp 1 gave the source? (--src_matrix_coeffs 14 without the flag stays what it was: refused) */
 static inline bool cli_src_is_ictcp(const cli_args &a, int m) { return a.src_ictcp == 1 && m == H2Y_MATRIX_ICTCP; }
 static inline int cli_resolve_ictcp(cli_args &a, int src_matrix_arg);
@@ -688,6 +717,10 @@ static inline int cli_resolve(cli_args &a)
     }
     if ((a.src_hlg_given || a.src_hlg_peak_given) && a.dither_only == 1) {
         printf("src_hlg: %d\nWARNING: --src_hlg goes with --linearize 1: not with --dither_only 1\n", a.src_hlg);
+        return 1;
+    }
+    if ((a.lut3d || a.lut3d_interp_given || a.lut3d_signal_given) && a.dither_only == 1) {
+        printf("lut3d: %s\nWARNING: --lut3d applies to a conversion's source: not with --dither_only 1\n", a.lut3d ? a.lut3d : "(none)");
         return 1;
     }
     if ((a.ictcp_given || a.src_ictcp_given) && a.dither_only == 1) {
@@ -724,10 +757,19 @@ static inline int cli_resolve_all(cli_args &a)
     if ((a.src_hlg_given || a.src_hlg_peak_given) && cli_resolve_src_hlg(a)) return 1; /* the transfer of --linearize 1's source */
     if (a.src_ictcp_given && cli_resolve_src_ictcp(a)) return 1; /* the matrix of the codes the three flows below read */
     if (a.linearize == 1 && cli_resolve_linearize(a)) return 1;
+    const bool lut3d_flags = a.lut3d || a.lut3d_interp_given || a.lut3d_signal_given;
+    if (a.lut3d && a.lut3d_signal == 1 && a.hlg != 1 && a.ictcp != 1) { /* the LUT is the destination's transfer: the run's becomes the source's */
+        a.lut3d_dst_transfer = a.out.transfer_characteristics;
+        a.out.transfer_characteristics = a.in.transfer_characteristics;
+    }
     if (a.light_only_given) { /* its own flow: it resolves everything it takes and refuses the rest */
         printf("light_only: %d\n", a.light_only);
         if (a.light_only != 0 && a.light_only != 1) {
             printf("WARNING: light_only(%d) not 0 or 1\n", a.light_only);
+            return 1;
+        }
+        if (a.light_only && lut3d_flags) {
+            printf("lut3d: %s\nWARNING: --lut3d applies to a conversion's source: not with --light_only 1\n", a.lut3d ? a.lut3d : "(none)");
             return 1;
         }
         if (a.light_only && (a.hlg_given || a.hlg_peak_given)) {
@@ -757,6 +799,7 @@ static inline int cli_resolve_all(cli_args &a)
     if (a.scale_given || a.scale_only || a.scale_taps_given) arg_errors += cli_resolve_scale(a);
     if (a.gamut_given || a.gamut_clip_given) arg_errors += cli_resolve_gamut(a, src_matrix_arg);
     if (a.tone_map_given || a.tone_src_peak_given || a.tone_dst_peak_given) arg_errors += cli_resolve_tone_map(a, src_matrix_arg);
+    if (lut3d_flags) arg_errors += cli_resolve_lut3d(a, src_matrix_arg);
     if (a.hlg_given || a.hlg_peak_given) arg_errors += cli_resolve_hlg(a, src_matrix_arg);
     if (a.ictcp_given) arg_errors += cli_resolve_ictcp(a, src_matrix_arg);
     if (a.siting_given) arg_errors += cli_resolve_siting(a);
@@ -1009,7 +1052,7 @@ static inline int cli_resolve_light(cli_args &a)
     if (!a.light) return 0;
     if (cli_light_scope(a, "--content_light 1")) return 1;
     printf("content_light_from: src_transfer_characteristics %d -> PQ, G,B,R, floor and ceiling %s\n", a.in.transfer_characteristics,
-           a.linearize == 1 ? "0 and 1 (--linearize 1)" : a.tone_map == 1 ? "0 and 1 (--tone_map 1)" : "of each frame's pic_stats");
+           a.linearize == 1 ? "0 and 1 (--linearize 1)" : a.tone_map == 1 ? "0 and 1 (--tone_map 1)" : a.lut3d ? "0 and 1 (--lut3d)" : "of each frame's pic_stats");
     return 0;
 }
 
@@ -1328,7 +1371,7 @@ static inline int cli_resolve_dynmeta(cli_args &a)
     }
     printf("dynamic_metadata_from: src_transfer_characteristics %d -> PQ, G,B,R, floor and ceiling %s; HDR10+ profile A, one scene, "
            "percentiles of max(R,G,B) in %d bins\n", a.in.transfer_characteristics,
-           a.linearize == 1 ? "0 and 1 (--linearize 1)" : a.tone_map == 1 ? "0 and 1 (--tone_map 1)" : "of each frame's pic_stats",
+           a.linearize == 1 ? "0 and 1 (--linearize 1)" : a.tone_map == 1 ? "0 and 1 (--tone_map 1)" : a.lut3d ? "0 and 1 (--lut3d)" : "of each frame's pic_stats",
            H2Y_LIGHTDIST_BINS);
     return 0;
 }
@@ -1516,7 +1559,8 @@ static inline int cli_resolve_tone_map(cli_args &a, int src_matrix_arg)
         printf("WARNING: --tone_map 1 needs a G,B,R source: src_matrix_coeffs(%d) is not %d\n", src_matrix_arg, H2Y_MATRIX_GBR);
         return 1;
     }
-    if (a.out.transfer_characteristics == H2Y_TRANSFER_LINEAR && a.hlg != 1 && a.ictcp != 1) { /* (--hlg 1 and --ictcp 1 are the display's transfer) */
+    const bool lut_signal = a.lut3d && a.lut3d_signal == 1; /* (--hlg 1, --ictcp 1 and a signal-mode LUT are the display's transfer) */
+    if (a.out.transfer_characteristics == H2Y_TRANSFER_LINEAR && a.hlg != 1 && a.ictcp != 1 && !lut_signal) {
         printf("WARNING: --tone_map 1 maps light for a display: dst_transfer_characteristics(%d) keeps linear light\n",
                a.out.transfer_characteristics);
         return 1;
@@ -1531,6 +1575,92 @@ static inline int cli_resolve_tone_map(cli_args &a, int src_matrix_arg)
     }
     const double W = cli_pq_n(a.tone_src_peak / 10000.0), ks = 1.5 * (cli_pq_n(a.tone_dst_peak / 10000.0) / W) - 0.5;
     printf("tone_map_output: %s\ntone_map_knee: %.9g\n", a.tone_relative ? "relative" : "absolute", 10000.0 * cli_pq_n_inv(ks * W));
+    return 0;
+}
+
+/* --lut3d / --lut3d_interp / --lut3d_signal: the forward flow's float or half G,B,R planes through a .cube table the library's
+ * parser reads (src_matrix_arg: --src_matrix_coeffs as given; in signal mode cli_resolve_all replaced the destination's transfer
+ * with the source's and kept what was given; cli_resolve_tone_map ran before); prints the file, the table's title, size and domain
+ * and the two modes; returns the number of argument errors */
+static inline int cli_resolve_lut3d(cli_args &a, int src_matrix_arg)
+{
+    printf("lut3d: %s\n", a.lut3d ? a.lut3d : "(none)");
+    if (!a.lut3d) {
+        printf("WARNING: --lut3d_interp and --lut3d_signal need --lut3d FILE.cube\n");
+        return 1;
+    }
+    int arg_errors = 0;
+    if (a.lut3d_interp != 0 && a.lut3d_interp != 1) { printf("WARNING: lut3d_interp(%d) not 0 or 1\n", a.lut3d_interp); arg_errors++; }
+    if (a.lut3d_signal != 0 && a.lut3d_signal != 1) { printf("WARNING: lut3d_signal(%d) not 0 or 1\n", a.lut3d_signal); arg_errors++; }
+    if (arg_errors) return arg_errors;
+    if (a.compare_only || a.hist_only || a.scale_only) {
+        printf("WARNING: --lut3d applies to a conversion's source: not with --%s 1\n",
+               a.compare_only ? "compare_only" : a.hist_only ? "histogram_only" : "scale_only");
+        return 1;
+    }
+    if (a.inverse) {
+        printf("WARNING: --lut3d applies to the forward flow's source (to .yuv), not the .yuv -> RGB flow\n");
+        return 1;
+    }
+    if (a.in_type != CLI_IN_F32 && a.in_type != CLI_IN_F16 && a.in_type != CLI_IN_EXR && a.in_type != CLI_IN_DPX) {
+        printf("WARNING: --lut3d applies to float or half planes (.f32, .f16, .exr, .dpx input, or --linearize 1 from a .yuv / .rgb), not "
+               ".%s input\n", a.in_type == CLI_IN_SYNTH ? "(synthetic)" : cli_ext_of(a.src));
+        return 1;
+    }
+    if (src_matrix_arg != H2Y_MATRIX_GBR) { /* the readers would override it: a source called Y'CbCr is not one to look up as R, G, B */
+        printf("WARNING: --lut3d needs a G,B,R source: src_matrix_coeffs(%d) is not %d\n", src_matrix_arg, H2Y_MATRIX_GBR);
+        return 1;
+    }
+    if (a.lut3d_signal == 1) {
+        if (a.hlg == 1 || a.ictcp == 1) {
+            printf("WARNING: --lut3d_signal 1 leaves the destination's signal: not with --%s 1, which writes its own\n", a.hlg == 1 ? "hlg" : "ictcp");
+            arg_errors++;
+        }
+        if (a.light || a.dynmeta) {
+            printf("WARNING: --lut3d_signal 1: --content_light and --dynamic_metadata measure light, not a LUT's signal\n");
+            arg_errors++;
+        }
+        if (a.in_type != CLI_IN_F32 && a.in_type != CLI_IN_DPX) {
+            printf("WARNING: --lut3d_signal 1 leaves code-valued samples in float planes (.f32 or .dpx input, or --linearize 1), not in the "
+                   "half planes of .%s input\n", cli_ext_of(a.src));
+            arg_errors++;
+        }
+        if (a.out_type != CLI_OUT_YUV) {
+            printf("WARNING: --lut3d_signal 1 writes .yuv frames: not a .%s destination\n", cli_ext_of(a.dst ? a.dst : a.ref));
+            arg_errors++;
+        }
+        const int m = a.out.matrix_coeffs;
+        if (m != H2Y_MATRIX_GBR && m != H2Y_MATRIX_BT2020NC) {
+            printf("WARNING: --lut3d_signal 1: dst_matrix_coeffs(%d) not %d (G,B,R) or %d (BT.2020nc)\n", m, H2Y_MATRIX_GBR, H2Y_MATRIX_BT2020NC);
+            arg_errors++;
+        }
+        if (arg_errors) return arg_errors;
+    }
+    /* the file, whole */
+    std::string text;
+    FILE *f = fopen(a.lut3d, "rb");
+    if (!f) {
+        printf("WARNING: --lut3d: unable to open file %s\n", a.lut3d);
+        return 1;
+    }
+    char buf[65536];
+    for (size_t got; (got = fread(buf, 1, sizeof buf, f)) > 0;) text.append(buf, got);
+    const bool bad = ferror(f) != 0;
+    fclose(f);
+    const char *why = "";
+    if (bad || h2y_lut3d_parse(text.data(), text.size(), &a.lut3d_table, &why)) {
+        printf("WARNING: --lut3d: file %s: %s\n", a.lut3d, bad ? "read error" : why);
+        return 1;
+    }
+    int n = 0;
+    float dom[6];
+    const char *title = "";
+    h2y_lut3d_info(a.lut3d_table, &n, dom, &title);
+    printf("lut3d_title: %s\nlut3d_size: %d\nlut3d_domain: %.9g %.9g %.9g .. %.9g %.9g %.9g\n", title, n, dom[0], dom[1], dom[2], dom[3], dom[4],
+           dom[5]);
+    printf("lut3d_interp: %d (%s)\nlut3d_signal: %d (%s)\n", a.lut3d_interp, a.lut3d_interp ? "tetrahedral" : "trilinear", a.lut3d_signal,
+           a.lut3d_signal ? "signal" : "planes");
+    if (a.lut3d_signal == 1 && a.lut3d_dst_transfer != -1) printf("lut3d_dst_transfer: %d\n", a.lut3d_dst_transfer);
     return 0;
 }
 
@@ -2092,13 +2222,14 @@ static inline void cli_make_desc(const cli_args &a, h2y_desc *d)
     d->dst_transfer = a.out.transfer_characteristics;
     d->src_matrix = a.in.matrix_coeffs;
     d->dst_matrix = a.out.matrix_coeffs;
-    d->src_primaries = a.ictcp == 1 ? a.out.colour_primaries : a.in.colour_primaries; /* the passthrough descriptor's are equal: --gamut_convert
+    const bool lut_signal = a.lut3d && a.lut3d_signal == 1; /* the LUT leaves the destination's signal, in its primaries */
+    d->src_primaries = a.ictcp == 1 || lut_signal ? a.out.colour_primaries : a.in.colour_primaries; /* the passthrough descriptor's are equal: --gamut_convert
                                                                                           * has the source's (h2y_stream_gamut) */
     d->dst_primaries = a.out.colour_primaries;
     d->dst_full_range = a.out.video_full_range_flag;
     d->dst_chroma_format_idc = a.out.chroma_format_idc;
     d->chroma_resampler_type = a.resampler;
-    if (a.tone_map || a.linearize == 1 || a.hlg == 1 || a.ictcp == 1) { /* mapped planes are referred to their target, linearised ones lie in [0, 1] by
+    if (a.tone_map || a.linearize == 1 || a.hlg == 1 || a.ictcp == 1 || a.lut3d) { /* (a LUT's planes are referred to its own range;) mapped planes are referred to their target, linearised ones lie in [0, 1] by
                                                          * definition, HLG's are code-valued: floor 0 and ceiling 1, not each frame's
                                                          * pic_stats */
         d->stats_override = 1;

@@ -137,6 +137,14 @@
  * --tone_map's passes, and the conversion takes them straight to its matrix.  The banner carries hlg:, hlg_peak: ("(default)" where
  * not given), hlg_gamma: "%.9g", hlg_input: absolute|relative, hlg_note: and hlg_encoder:.
  *
+ * 3D LUT (--lut3d FILE.cube [--lut3d_interp 0|1] [--lut3d_signal 0|1] on the forward flow from .f32, .f16, .exr, .dpx and --linearize 1
+ * sources; h2y_cli_args.h): the file is read and parsed once (h2y_lut3d_parse), each GPU thread opens its ring with floor 0 and
+ * ceiling 1 and arms it (h2y_stream_lut3d), so the table is applied to every slot's decoded planes in place on the device, after
+ * --gamut_convert's and --tone_map's passes and before --hlg's / --ictcp's.  In planes mode the run writes the bytes it would write had
+ * the source held the planes the LUT leaves; in signal mode the run's destination transfer becomes the source's and the conversion
+ * takes the LUT's code values straight to its matrix, as for --hlg 1.  The banner carries lut3d:, lut3d_title:, lut3d_size:,
+ * lut3d_domain:, lut3d_interp:, lut3d_signal: and, where --dst_transfer_characteristics was given in signal mode, lut3d_dst_transfer:.
+ *
  * ICtCp (--ictcp 1 on the same sources; h2y_cli_args.h): the run's destination matrix and transfer become the passthrough descriptor's
  * 0 and 8 with equal primaries, each GPU thread opens its ring with floor 0 and ceiling 1 and arms it (h2y_stream_ictcp), so every
  * slot's decoded planes become code-valued PQ I, Ct, Cp samples in place on the device, after --gamut_convert's and --tone_map's passes,
@@ -419,6 +427,7 @@ static flow forward_flow(const job &j)
                (a.dynmeta && h2y_stream_lightdist(ctx)) || (a.scene_detect == 1 && h2y_stream_scenesig(ctx)) ||
                (a.gamut && h2y_stream_gamut(ctx, a.in.colour_primaries, a.out.colour_primaries, a.gamut_clip)) ||
                (a.tone_map && h2y_stream_tonemap(ctx, a.tone_src_peak, a.tone_dst_peak, a.tone_relative)) ||
+               (a.lut3d_table && h2y_stream_lut3d(ctx, a.lut3d_table, a.lut3d_interp, a.lut3d_signal)) ||
                (a.hlg == 1 && h2y_stream_hlg(ctx, a.hlg_peak, a.hlg_relative)) || (a.ictcp == 1 && h2y_stream_ictcp(ctx)) ||
                (a.scale && h2y_stream_scale(ctx, a.out.width, a.out.height, a.scale_taps)) ||
                (a.dithers() && h2y_stream_dither(ctx, a.dither_to, a.dither, a.dither_temporal, a.dither_seed, (uint32_t)first)); /* after scale */

@@ -179,6 +179,7 @@ int h2y_ctx_create(int device, h2y_ctx **out)
  *   "t1"      "0" | "1"                 binary32 first tier off / on (default on)
  *   "groups"  "0" | "1" .. "64"         at most this many frame groups (rounded down to a power of two; 1 = off); "0": by the frame's size (default)
  *   "cols8"   "0" | "1"                 8-column thread tiles for half input (default on)
+ *   "lut3d_lds" "0" | "1"               a 3D LUT of up to 17 nodes per axis is read from LDS, k_lut3d_lds (default on); same bytes either way
  *   "balance" "adaptive" | "xcd" | "off" | "<xcd mask>,<ratio>"   slices by measured block speed / XCD speed only / even / fixed XCD weights (default adaptive)
  *   "tail"    "off" | "auto" | "on"     k_fused_t1: the last frame of every frame group drawn dynamically by the blocks that finish first
  *                                       (auto: groups of eight frames or more; on: two suffice; default off: measured neutral)
@@ -194,6 +195,7 @@ int h2y_ctx_set_option(h2y_ctx *ctx, const char *name, const char *value)
         ctx->opt_t1_steer = strcmp(value, "always") != 0; /* "always": stay on the first tier however many pixels it passes on (timing) */
     }
     else if (!strcmp(name, "cols8")) ctx->opt_cols8 = value[0] != '0';
+    else if (!strcmp(name, "lut3d_lds")) ctx->opt_lut3d_lds = value[0] != '0';
     else if (!strcmp(name, "firsync")) {
         int v = atoi(value), p = 1;
         if (!strcmp(value, "auto")) v = -1;
@@ -285,6 +287,7 @@ void h2y_ctx_destroy(h2y_ctx *ctx)
     (void)hipFree(ctx->d_deltae);
     (void)hipFree(ctx->d_scale_tabs);
     (void)hipFree(ctx->d_tonemap_gain);
+    (void)hipFree(ctx->d_lut3d);
     (void)hipFree(ctx->d_hlg_tables);
     (void)hipFree(ctx->d_hlgsrc_tables);
     (void)hipFree(ctx->d_in);

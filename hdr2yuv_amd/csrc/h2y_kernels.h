@@ -448,6 +448,31 @@ struct tonemap_args {
 int h2y_tonemap_grid(int n_cu, uint64_t units); /* blocks for so many of k_gamut's units (h2y_gamut_chunks per frame) */
 hipError_t h2y_launch_tonemap(int in_kind, int grid, hipStream_t st, const tonemap_args &a, const gamut_frame *frames, int n_frames);
 
+/* k_lut3d (h2y_lut3d.hip): the 3D LUT pass of include/hdr2yuv_hip.h on frames of three float or half planes G, B, R, k_gamut's
+ * frame table; in planes mode the destination planes have the source's type (dst may be src: in place), in signal mode they are
+ * float (dst may be src for float planes) */
+struct alignas(16) lut3d_node {
+    float r, g, b, pad; /* 16 bytes: one corner is one access */
+};
+struct lut3d_consts {
+    uint32_t n;                   /* nodes per axis, 2..128 */
+    float last;                   /* float(n - 1) */
+    float lo[3], s[3];            /* per channel r, g, b: the domain's lower end, (n - 1) / (hi - lo) rounded once */
+    float mulY, addY, mulC, addC; /* signal mode: the conversion's scale step (derive_params) */
+};
+struct lut3d_args {
+    uint32_t npix; /* pixels per frame (< 2^28) */
+    lut3d_consts c;
+    const lut3d_node *nodes; /* device: n^3 nodes, r fastest, then g, then b */
+};
+/* lds 1 (n <= H2Y_LUT3D_LDS_MAX_N only): k_lut3d_lds, blocks of H2Y_LUT3D_LDS_THREADS threads that read the table from their copy in LDS */
+enum { H2Y_LUT3D_LDS_MAX_N = 17, H2Y_LUT3D_LDS_THREADS = 1024 };
+uint32_t h2y_lut3d_chunks(int lds, int in_kind, uint32_t npix); /* the kernel's units per frame */
+int h2y_lut3d_grid(int n_cu, int lds, uint64_t units);          /* blocks for so many units */
+/* interp 0 trilinear, 1 tetrahedral; signal 0 planes, 1 signal */
+hipError_t h2y_launch_lut3d(int in_kind, int interp, int signal, int lds, int grid, hipStream_t st, const lut3d_args &a,
+                            const gamut_frame *frames, int n_frames);
+
 /* k_hlg (h2y_hlg.hip): the HLG pass of include/hdr2yuv_hip.h on frames of three float or half planes G, B, R of display light,
  * k_gamut's frame table; the destination planes are float (dst may be src for float planes: in place) */
 struct hlg_consts {

@@ -2320,6 +2320,349 @@ int h2y_stream_tonemap(h2y_ctx *ctx, int src_peak, int dst_peak, int relative)
     return stage_arm(ctx, STAGE_TONEMAP, std::move(st), "tone map");
 }
 
+/* ---- 3D LUT (--lut3d; the reference has no LUT step): include/hdr2yuv_hip.h states the definition ------------------------------------- */
+
+#include <cstdarg>
+
+#include "h2y_lut3d1.h"
+
+/* a parsed .cube table: the nodes as the kernel reads them */
+struct h2y_lut3d {
+    int n = 0;
+    float lo[3] = {0.0f, 0.0f, 0.0f}, hi[3] = {1.0f, 1.0f, 1.0f}, s[3] = {0.0f, 0.0f, 0.0f};
+    std::string title;
+    std::vector<lut3d_node> nodes;
+};
+
+namespace {
+
+thread_local std::string lut3d_why; /* h2y_lut3d_parse's reason, until the thread's next call */
+
+int lut3d_refuse(const char **why, int code, int line, const char *fmt, ...)
+{
+    char buf[256];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    lut3d_why = line > 0 ? "line " + std::to_string(line) + ": " + buf : std::string(buf);
+    *why = lut3d_why.c_str();
+    return code;
+}
+
+/* the whole token as one binary32 number (strtof: decimal, scientific; "nan" and "inf" too, which the caller refuses) */
+bool lut3d_number(const std::string &t, float *v)
+{
+    if (t.empty()) return false;
+    char *e = nullptr;
+    *v = strtof(t.c_str(), &e);
+    return e == t.c_str() + t.size();
+}
+
+/* k numbers, all finite, in tok[1..k] */
+bool lut3d_numbers(const std::vector<std::string> &tok, size_t k, float *v)
+{
+    if (tok.size() != k + 1) return false;
+    for (size_t i = 0; i < k; i++)
+        if (!lut3d_number(tok[i + 1], v + i) || !std::isfinite(v[i])) return false;
+    return true;
+}
+
+} // namespace
+
+int h2y_lut3d_parse(const char *text, size_t len, h2y_lut3d **out, const char **why)
+{
+    const char *dummy;
+    if (!why) why = &dummy;
+    *why = "";
+    if (!text || !out) return lut3d_refuse(why, H2Y_EINVAL, 0, "null text or lut");
+    *out = nullptr;
+    auto lut = std::make_unique<h2y_lut3d>();
+    size_t rows = 0, total = 0, pos = 0;
+    int line = 0;
+    const char *blank = " \t\r\f\v";
+    while (pos < len) {
+        size_t end = pos;
+        while (end < len && text[end] != '\n') end++;
+        std::string ln(text + pos, end - pos);
+        pos = end + 1;
+        line++;
+        const size_t b = ln.find_first_not_of(blank);
+        if (b == std::string::npos || ln[b] == '#') continue;
+        ln = ln.substr(b, ln.find_last_not_of(blank) - b + 1);
+        std::vector<std::string> tok;
+        for (size_t p = 0; p < ln.size();) {
+            const size_t q = ln.find_first_of(blank, p);
+            tok.push_back(ln.substr(p, q == std::string::npos ? q : q - p));
+            p = q == std::string::npos ? ln.size() : ln.find_first_not_of(blank, q);
+        }
+        float v[3];
+        if (lut3d_number(tok[0], v)) { /* a table row */
+            if (!lut->n) return lut3d_refuse(why, H2Y_EINVAL, line, "a table row before LUT_3D_SIZE");
+            if (tok.size() != 3) return lut3d_refuse(why, H2Y_EINVAL, line, "a table row of %zu numbers, not three", tok.size());
+            for (int c = 0; c < 3; c++) {
+                if (!lut3d_number(tok[c], v + c)) return lut3d_refuse(why, H2Y_EINVAL, line, "'%.40s' is not a number", tok[c].c_str());
+                if (!std::isfinite(v[c])) return lut3d_refuse(why, H2Y_EINVAL, line, "a value that is not finite");
+            }
+            if (rows == total) return lut3d_refuse(why, H2Y_EINVAL, line, "too many table rows: more than %d^3 = %zu", lut->n, total);
+            lut->nodes[rows++] = lut3d_node{v[0], v[1], v[2], 0.0f};
+            continue;
+        }
+        const std::string &key = tok[0];
+        if (key == "LUT_1D_SIZE" || key == "LUT_1D_INPUT_RANGE")
+            return lut3d_refuse(why, H2Y_EUNSUPPORTED, line, "%s: 1D LUTs and shaper + 3D files are not read", key.c_str());
+        if (rows) return lut3d_refuse(why, H2Y_EINVAL, line, "'%.40s' after the first table row", key.c_str());
+        if (key == "TITLE") {
+            const size_t q0 = ln.find('"'), q1 = ln.rfind('"');
+            if (q0 != std::string::npos && q1 > q0) lut->title = ln.substr(q0 + 1, q1 - q0 - 1);
+            else {
+                const size_t t = ln.find_first_not_of(blank, 5);
+                lut->title = t == std::string::npos ? "" : ln.substr(t);
+            }
+        } else if (key == "LUT_3D_SIZE") {
+            if (lut->n) return lut3d_refuse(why, H2Y_EINVAL, line, "LUT_3D_SIZE given twice");
+            char *e = nullptr;
+            const long n = tok.size() == 2 ? strtol(tok[1].c_str(), &e, 10) : 0;
+            if (tok.size() != 2 || tok[1].empty() || e != tok[1].c_str() + tok[1].size())
+                return lut3d_refuse(why, H2Y_EINVAL, line, "LUT_3D_SIZE takes one integer");
+            if (n < 2 || n > 128) return lut3d_refuse(why, H2Y_EINVAL, line, "LUT_3D_SIZE %ld outside 2..128", n);
+            lut->n = (int)n;
+            total = (size_t)n * (size_t)n * (size_t)n;
+            lut->nodes.resize(total);
+        } else if (key == "DOMAIN_MIN" || key == "DOMAIN_MAX") {
+            if (!lut3d_numbers(tok, 3, v)) return lut3d_refuse(why, H2Y_EINVAL, line, "%s takes three finite numbers", key.c_str());
+            for (int c = 0; c < 3; c++) (key == "DOMAIN_MIN" ? lut->lo : lut->hi)[c] = v[c];
+        } else if (key == "LUT_3D_INPUT_RANGE") {
+            if (!lut3d_numbers(tok, 2, v)) return lut3d_refuse(why, H2Y_EINVAL, line, "LUT_3D_INPUT_RANGE takes two finite numbers");
+            for (int c = 0; c < 3; c++) lut->lo[c] = v[0], lut->hi[c] = v[1];
+        } else
+            return lut3d_refuse(why, H2Y_EINVAL, line, "unknown keyword '%.40s'", key.c_str());
+    }
+    if (!lut->n) return lut3d_refuse(why, H2Y_EINVAL, 0, "no LUT_3D_SIZE");
+    if (rows != total) return lut3d_refuse(why, H2Y_EINVAL, 0, "too few table rows: %zu, not %d^3 = %zu", rows, lut->n, total);
+    for (int c = 0; c < 3; c++) {
+        if (!(lut->hi[c] > lut->lo[c]))
+            return lut3d_refuse(why, H2Y_EINVAL, 0, "the domain's maximum %.9g is not above its minimum %.9g (channel %c)", lut->hi[c], lut->lo[c], "rgb"[c]);
+        lut->s[c] = (float)((double)(lut->n - 1) / ((double)lut->hi[c] - (double)lut->lo[c]));
+        if (!std::isfinite(lut->s[c])) return lut3d_refuse(why, H2Y_EINVAL, 0, "the domain of channel %c is too narrow", "rgb"[c]);
+    }
+    *out = lut.release();
+    return H2Y_OK;
+}
+
+void h2y_lut3d_free(h2y_lut3d *lut) { delete lut; }
+
+int h2y_lut3d_info(const h2y_lut3d *lut, int *n, float domain[6], const char **title)
+{
+    if (!lut) return fail(nullptr, H2Y_EINVAL, "null lut");
+    if (n) *n = lut->n;
+    if (domain)
+        for (int c = 0; c < 3; c++) domain[c] = lut->lo[c], domain[3 + c] = lut->hi[c];
+    if (title) *title = lut->title.c_str();
+    return H2Y_OK;
+}
+
+int h2y_lut3d_nodes(const h2y_lut3d *lut, float *rgb)
+{
+    if (!lut || !rgb) return fail(nullptr, H2Y_EINVAL, "null lut or nodes");
+    for (size_t i = 0; i < lut->nodes.size(); i++) rgb[3 * i] = lut->nodes[i].r, rgb[3 * i + 1] = lut->nodes[i].g, rgb[3 * i + 2] = lut->nodes[i].b;
+    return H2Y_OK;
+}
+
+/* the pass's constants: the table's, and in signal mode the scale step of (dst_bit_depth, dst_full_range, dst_matrix) as hlg_setup
+ * derives it; the checks every entry shares */
+static int lut3d_setup(h2y_ctx *ctx, const h2y_lut3d *lut, int interp, int signal, int dst_bit_depth, int dst_full_range, int dst_matrix,
+                       lut3d_consts &c)
+{
+    if (!lut) return fail(ctx, H2Y_EINVAL, "null lut");
+    if (interp != 0 && interp != 1) return fail(ctx, H2Y_EINVAL, "interp must be 0 (trilinear) or 1 (tetrahedral)");
+    if (signal != 0 && signal != 1) return fail(ctx, H2Y_EINVAL, "signal must be 0 (planes) or 1 (signal)");
+    c = lut3d_consts{};
+    c.n = (uint32_t)lut->n;
+    c.last = (float)(lut->n - 1);
+    for (int k = 0; k < 3; k++) c.lo[k] = lut->lo[k], c.s[k] = lut->s[k];
+    if (!signal) return H2Y_OK;
+    if (dst_matrix != H2Y_MATRIX_GBR && dst_matrix != H2Y_MATRIX_BT2020NC)
+        return fail(ctx, H2Y_EUNSUPPORTED, "a LUT's signal is scaled as G,B,R or BT.2020nc (dst_matrix 0 or 9), not dst_matrix %d", dst_matrix);
+    if (dst_bit_depth < 8 || dst_bit_depth > 16) return fail(ctx, H2Y_EINVAL, "dst_bit_depth %d outside 8..16", dst_bit_depth);
+    if (dst_full_range != 0 && dst_full_range != 1) return fail(ctx, H2Y_EINVAL, "dst_full_range must be 0 or 1");
+    h2y_desc d{};
+    d.in_sample_type = H2Y_SAMPLE_F32;
+    d.src_bit_depth = 32;
+    d.dst_bit_depth = dst_bit_depth;
+    d.dst_full_range = dst_full_range;
+    d.src_matrix = H2Y_MATRIX_GBR;
+    d.dst_matrix = dst_matrix;
+    d.src_transfer = d.dst_transfer = H2Y_TRANSFER_LINEAR;
+    pix_params pp;
+    derive_params(&d, &pp, false);
+    c.mulY = pp.mulY, c.addY = pp.addY, c.mulC = pp.mulC, c.addC = pp.addC;
+    return H2Y_OK;
+}
+
+template <int INTERP, int SIGNAL>
+static void lut3d_host(const h2y_lut3d *lut, const lut3d_consts &c, int sample_type, size_t npix, const void *const src[3], void *const dst[3])
+{
+    for (size_t i = 0; i < npix; i++) {
+        float v[3];
+        for (int p = 0; p < 3; p++) {
+            if (sample_type == H2Y_SAMPLE_F32) v[p] = static_cast<const float *>(src[p])[i];
+            else v[p] = (float)static_cast<const _Float16 *>(src[p])[i]; /* exact */
+        }
+        lut3d_pixel<INTERP, SIGNAL>(lut3d_nodes16{lut->nodes.data()}, c, v[0], v[1], v[2]);
+        for (int p = 0; p < 3; p++) {
+            if (SIGNAL || sample_type == H2Y_SAMPLE_F32) static_cast<float *>(dst[p])[i] = v[p];
+            else static_cast<_Float16 *>(dst[p])[i] = (_Float16)v[p]; /* to nearest even */
+        }
+    }
+}
+
+int h2y_lut3d_planes(const h2y_lut3d *lut, int interp, int signal, int dst_bit_depth, int dst_full_range, int dst_matrix, int sample_type,
+                     size_t npix, const void *const src[3], void *const dst[3])
+{
+    if (sample_type != H2Y_SAMPLE_F32 && sample_type != H2Y_SAMPLE_F16)
+        return fail(nullptr, H2Y_EUNSUPPORTED, "the LUT pass reads float or half planes, not sample type %d", sample_type);
+    if (!src || !dst || !src[0] || !src[1] || !src[2] || !dst[0] || !dst[1] || !dst[2]) return fail(nullptr, H2Y_EINVAL, "null planes");
+    lut3d_consts c{};
+    const int rc = lut3d_setup(nullptr, lut, interp, signal, dst_bit_depth, dst_full_range, dst_matrix, c);
+    if (rc) return rc;
+    if (interp && signal) lut3d_host<1, 1>(lut, c, sample_type, npix, src, dst);
+    else if (interp) lut3d_host<1, 0>(lut, c, sample_type, npix, src, dst);
+    else if (signal) lut3d_host<0, 1>(lut, c, sample_type, npix, src, dst);
+    else lut3d_host<0, 0>(lut, c, sample_type, npix, src, dst);
+    return H2Y_OK;
+}
+
+/* k_lut3d's arguments for frames of width x height, but for the device table; the checks of both entries */
+static int lut3d_args_of(h2y_ctx *ctx, int width, int height, int sample_type, const h2y_lut3d *lut, int interp, int signal,
+                         int dst_bit_depth, int dst_full_range, int dst_matrix, lut3d_args &a)
+{
+    if (sample_type == H2Y_SAMPLE_U16)
+        return fail(ctx, H2Y_EUNSUPPORTED, "the LUT pass works on float or half planes, not on U16 samples");
+    if (sample_type != H2Y_SAMPLE_F32 && sample_type != H2Y_SAMPLE_F16) return fail(ctx, H2Y_EINVAL, "bad sample type %d", sample_type);
+    if (width < 1 || height < 1 || (uint64_t)width * (uint64_t)height >= (1ull << 28)) return fail(ctx, H2Y_EINVAL, "bad picture size");
+    const int rc = lut3d_setup(ctx, lut, interp, signal, dst_bit_depth, dst_full_range, dst_matrix, a.c);
+    if (rc) return rc;
+    a.npix = (uint32_t)width * (uint32_t)height;
+    return H2Y_OK;
+}
+
+static std::string lut3d_variant(int in_kind, int interp, int signal, int lds)
+{
+    return std::string(lds ? "k_lut3d_lds<" : "k_lut3d<") + (in_kind == H2Y_IN_F16 ? "F16" : "F32") + (interp ? ",TETRA" : ",TRILINEAR") +
+           (signal ? ",SIGNAL>" : ",PLANES>");
+}
+
+/* does the pass read this table from LDS? (the context's "lut3d_lds" option, for tables small enough) */
+static int lut3d_in_lds(const h2y_ctx *ctx, const h2y_lut3d *lut) { return ctx->opt_lut3d_lds && lut->n <= H2Y_LUT3D_LDS_MAX_N; }
+
+int h2y_lut3d_batch(h2y_ctx *ctx, int width, int height, int sample_type, const h2y_lut3d *lut, int interp, int signal, int dst_bit_depth,
+                    int dst_full_range, int dst_matrix, int n_frames, const void *const *d_src, void *const *d_dst)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
+    lut3d_args a{};
+    int rc = lut3d_args_of(ctx, width, height, sample_type, lut, interp, signal, dst_bit_depth, dst_full_range, dst_matrix, a);
+    if (rc) return rc;
+    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
+    if (!d_src || !d_dst) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
+    for (int f = 0; f < n_frames; f++)
+        for (int c = 0; c < 3; c++) {
+            const void *i = d_src[3 * f + c], *o = d_dst[3 * f + c];
+            if (!i || !o) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is null", f, c);
+            if (((uintptr_t)i | (uintptr_t)o) & 15u) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is not 16-byte aligned", f, c);
+            if (i == o && signal && sample_type == H2Y_SAMPLE_F16)
+                return fail(ctx, H2Y_EINVAL, "frame %d: plane %d in place: half planes are widened, the float planes need room of their own", f, c);
+        }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    gamut_frame *h;
+    const size_t table_bytes = lut->nodes.size() * sizeof(lut3d_node);
+    rc = frame_table(ctx, n_frames, h);
+    if (!rc) rc = ensure(ctx, ctx->d_lut3d, ctx->lut3d_cap, table_bytes);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpy(ctx->d_lut3d, lut->nodes.data(), table_bytes, hipMemcpyHostToDevice));
+    a.nodes = ctx->d_lut3d;
+    for (int f = 0; f < n_frames; f++)
+        for (int c = 0; c < 3; c++) h[f].src[c] = d_src[3 * f + c], h[f].dst[c] = d_dst[3 * f + c];
+    const int in_kind = sample_type == H2Y_SAMPLE_F16 ? H2Y_IN_F16 : H2Y_IN_F32;
+    const int lds = lut3d_in_lds(ctx, lut);
+    const uint64_t per_frame = h2y_lut3d_chunks(lds, in_kind, a.npix);
+    rc = timed_launches(ctx, h, n_frames, H2Y_LUT3D_FRAMES_PER_LAUNCH, "k_lut3d", [&](const gamut_frame *frames, int, int nf) {
+        return h2y_launch_lut3d(in_kind, interp, signal, lds, h2y_lut3d_grid(ctx->n_cu, lds, per_frame * nf), ctx->stream, a, frames, nf);
+    });
+    if (rc) return rc;
+    ctx->last_variant = lut3d_variant(in_kind, interp, signal, lds);
+    return H2Y_OK;
+}
+
+/* The pass's ring stage, in place on a forward ring's decoded planes after the gamut and tone-map stages' passes and before the HLG
+ * and ICtCp stages', pic_stats and the conversion: k_lut3d's arguments, the table and its frame table entry per slot.  It leaves
+ * nothing of its own behind: what follows reads the planes it left. */
+struct lut3d_stage : ring_stage {
+    lut3d_args a{};
+    gamut_frame *tab = nullptr;
+    int in_kind = H2Y_IN_F32, interp = 1, signal = 0, lds = 0;
+    int grid = 1;
+    int decoded(h2y_ctx *ctx, int k) override
+    {
+        HIP_TRY(ctx, h2y_launch_lut3d(in_kind, interp, signal, lds, grid, ctx->stream, a, tab + k, 1));
+        return H2Y_OK;
+    }
+    int run(h2y_ctx *, int) override { return H2Y_OK; }
+};
+
+/* does the open ring's LUT leave code values? (h2y_stream_hlg and h2y_stream_ictcp refuse such a ring) */
+static bool lut3d_leaves_codes(const h2y_ctx *ctx)
+{
+    const lut3d_stage *st = stage_of<lut3d_stage>(ctx, STAGE_LUT3D);
+    return st && st->signal;
+}
+
+int h2y_stream_lut3d(h2y_ctx *ctx, const h2y_lut3d *lut, int interp, int signal)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    if (ctx->s_kind != h2y_ctx::RING_FORWARD) return fail(ctx, H2Y_EINVAL, "a LUT is applied on the forward rings only");
+    if (ctx->s_stage[STAGE_LUT3D]) return fail(ctx, H2Y_EINVAL, "the ring applies a LUT already");
+    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    const h2y_desc *d = &ctx->s_desc;
+    auto st = std::make_unique<lut3d_stage>();
+    int rc = lut3d_args_of(ctx, d->width, d->height, d->in_sample_type, lut, interp, signal, d->dst_bit_depth, d->dst_full_range, d->dst_matrix,
+                           st->a);
+    if (rc) return rc;
+    if (d->src_matrix != H2Y_MATRIX_GBR)
+        return fail(ctx, H2Y_EUNSUPPORTED, "a LUT needs a G,B,R source (src_matrix 0), not src_matrix %d", d->src_matrix);
+    bool unit = d->stats_override == 1;
+    for (int c = 0; c < 3; c++) unit = unit && d->floor[c] == 0 && d->ceiling[c] == 1;
+    if (!unit)
+        return fail(ctx, H2Y_EINVAL, "a LUT's planes are referred to its own range: open the ring with stats_override 1, floor 0 and "
+                                     "ceiling 1 on all three planes");
+    if (signal) {
+        if (ctx->s_stage[STAGE_HLG] || ctx->s_stage[STAGE_ICTCP])
+            return fail(ctx, H2Y_EINVAL, "the ring writes %s: a LUT in signal mode leaves code values too", ctx->s_stage[STAGE_HLG] ? "HLG" : "ICtCp");
+        if (d->in_sample_type != H2Y_SAMPLE_F32)
+            return fail(ctx, H2Y_EUNSUPPORTED, "a LUT in signal mode leaves code-valued samples in the ring's decoded planes: they must be "
+                                               "F32, not F16 (a half cannot hold them)");
+        if (d->src_transfer != d->dst_transfer)
+            return fail(ctx, H2Y_EUNSUPPORTED, "a LUT in signal mode is the ring's transfer: open it with equal transfers, not %d and %d",
+                        d->src_transfer, d->dst_transfer);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    st->in_kind = in_kind_of(d);
+    st->interp = interp, st->signal = signal;
+    st->lds = lut3d_in_lds(ctx, lut);
+    st->grid = h2y_lut3d_grid(ctx->n_cu, st->lds, h2y_lut3d_chunks(st->lds, st->in_kind, st->a.npix));
+    lut3d_node *d_nodes = nullptr;
+    st->table(d_nodes, lut->nodes);
+    st->a.nodes = d_nodes;
+    const int depth = (int)ctx->ss.size();
+    std::vector<gamut_frame> tab(depth);
+    for (int k = 0; k < depth; k++)
+        for (int c = 0; c < 3; c++) tab[k].src[c] = tab[k].dst[c] = ctx->ss[k].d_in + c * ctx->s_plane_al;
+    st->table(st->tab, tab);
+    return stage_arm(ctx, STAGE_LUT3D, std::move(st), "3D LUT");
+}
+
 /* ---- HLG (--hlg; the reference has no HLG transfer): include/hdr2yuv_hip.h states the definition ------------------------------------- */
 
 #include "h2y_hlg1.h"
@@ -2475,6 +2818,7 @@ int h2y_stream_hlg(h2y_ctx *ctx, int peak, int relative)
     if (ctx->s_kind != h2y_ctx::RING_FORWARD) return fail(ctx, H2Y_EINVAL, "the HLG pass works on the forward rings only");
     if (ctx->s_stage[STAGE_HLG]) return fail(ctx, H2Y_EINVAL, "the ring writes HLG already");
     if (ctx->s_stage[STAGE_ICTCP]) return fail(ctx, H2Y_EINVAL, "the ring writes ICtCp: its planes hold code values, not light");
+    if (lut3d_leaves_codes(ctx)) return fail(ctx, H2Y_EINVAL, "the ring's LUT works in signal mode: its planes hold code values, not light");
     if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
     const h2y_desc *d = &ctx->s_desc;
     if (d->in_sample_type != H2Y_SAMPLE_F32)
@@ -2604,6 +2948,7 @@ int h2y_stream_ictcp(h2y_ctx *ctx)
     if (ctx->s_kind != h2y_ctx::RING_FORWARD) return fail(ctx, H2Y_EINVAL, "the ICtCp pass works on the forward rings only");
     if (ctx->s_stage[STAGE_ICTCP]) return fail(ctx, H2Y_EINVAL, "the ring writes ICtCp already");
     if (ctx->s_stage[STAGE_HLG]) return fail(ctx, H2Y_EINVAL, "the ring writes HLG: its planes hold code values, not light");
+    if (lut3d_leaves_codes(ctx)) return fail(ctx, H2Y_EINVAL, "the ring's LUT works in signal mode: its planes hold code values, not light");
     if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
     const h2y_desc *d = &ctx->s_desc;
     if (d->in_sample_type != H2Y_SAMPLE_F32)

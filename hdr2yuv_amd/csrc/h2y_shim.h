@@ -200,7 +200,7 @@ struct ring_stage {
     virtual int run(h2y_ctx *ctx, int slot) = 0;          /* on the context's stream, after the frame was produced */
     virtual int download(h2y_ctx *, int) { return H2Y_OK; } /* the result, on s_d2h after the slot's ev_conv */
 };
-enum stage_id { STAGE_GAMUT, STAGE_TONEMAP, STAGE_HLG, STAGE_ICTCP, STAGE_LIGHT, STAGE_LIGHTDIST, STAGE_CODELIGHT, STAGE_SCENESIG, STAGE_COMPARE, STAGE_SSIM, STAGE_DELTAE, STAGE_HISTOGRAM, STAGE_SCALE, STAGE_DITHER, STAGE_COUNT };
+enum stage_id { STAGE_GAMUT, STAGE_TONEMAP, STAGE_LUT3D, STAGE_HLG, STAGE_ICTCP, STAGE_LIGHT, STAGE_LIGHTDIST, STAGE_CODELIGHT, STAGE_SCENESIG, STAGE_COMPARE, STAGE_SSIM, STAGE_DELTAE, STAGE_HISTOGRAM, STAGE_SCALE, STAGE_DITHER, STAGE_COUNT };
 
 struct h2y_ctx {
     int device = 0;
@@ -238,6 +238,7 @@ struct h2y_ctx {
     bool opt_t1_steer = true;  /* ... and left for the binary64 tier's kernels while the pictures keep it busy passing pixels on */
     int opt_groups = 0;        /* "groups": at most this many frame groups (power of two; 1 = off); 0 = by the frame's size (groups_cap()) */
     bool opt_cols8 = true;     /* "cols8": 8-column tiles for half input where the planes allow */
+    bool opt_lut3d_lds = true; /* "lut3d_lds": a 3D LUT of up to 17 nodes per axis is read from the blocks' copies in LDS (k_lut3d_lds) */
     int opt_bal_mode = 0;      /* "balance": 0 adaptive, 1 off, 2 fixed */
     int opt_tail = 2;           /* "tail": 0 auto (groups of at least kTailMinFrames frames), 1 on (two frames suffice), 2 off (the default: measured
                                    neutral on 64 x 4K -- the blocks' finish times close up from +-30 us to +-15 us of a 1.5 ms launch, and the
@@ -295,6 +296,9 @@ struct h2y_ctx {
     /* h2y_tonemap_batch's gain table on the device */
     float *d_tonemap_gain = nullptr;
     size_t tonemap_gain_cap = 0;
+    /* h2y_lut3d_batch's table on the device */
+    lut3d_node *d_lut3d = nullptr;
+    size_t lut3d_cap = 0;
     /* h2y_hlg_batch's two tables on the device: the gains, then the OETF's */
     float *d_hlg_tables = nullptr;
     size_t hlg_tables_cap = 0;

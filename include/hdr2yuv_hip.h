@@ -1163,6 +1163,88 @@ int h2y_tonemap_batch(h2y_ctx *ctx, int width, int height, int sample_type, int 
  * a ring armed already, and for peaks or a `relative` out of range. */
 int h2y_stream_tonemap(h2y_ctx *ctx, int src_peak, int dst_peak, int relative);
 
+/* ---- 3D LUT: a .cube table applied to the decoded source planes (--lut3d FILE.cube) ------------------------------------------------
+ * The reference has no LUT step, so there are no bytes to match: this is the project's own definition, as primaries, tone mapping,
+ * scaling and dither are.  A pass over the decoded source planes, after h2y_stream_gamut's and h2y_stream_tonemap's where those are
+ * armed and before h2y_stream_hlg's / h2y_stream_ictcp's, after which the unchanged forward conversion writes the bytes it would
+ * write had the source file held the planes this pass leaves.
+ * The table: N nodes per axis, 2 <= N <= 128; per channel c of (r, g, b) a domain lo_c < hi_c, finite binary32; N^3 nodes of three
+ *   finite binary32 values in .cube file order, r fastest, then g, then b.  On the host, per channel,
+ *   s_c = (N - 1) / (hi_c - lo_c), evaluated in binary64 and rounded once to binary32.
+ * Pixel, in binary32.  Planes are 0 = G, 1 = B, 2 = R, so x_r = p2, x_g = p0, x_b = p1; a half is widened first (exact).  Every
+ *   difference, product and sum is one round-to-nearest operation, never contracted into a fused multiply-add:
+ *   1. t_c = (x_c - lo_c) s_c; then t_c = t_c > 0 ? min(t_c, float(N - 1)) : +0.0 (NaN, -0.0 and everything below the domain go to
+ *      the first node, +inf and everything above to the last);
+ *   2. i_c = (int)t_c (truncation, 0 .. N - 1), j_c = min(i_c + 1, N - 1), f_c = t_c - float(i_c) (exact, in [0, 1)).  The upper
+ *      neighbour is clamped, not the cell: an input exactly on a node, the last one included, has f = 0 and returns that node's
+ *      values exactly (i = min((int)t, N - 2) does not at the domain's maximum);
+ *   3. interp 1, tetrahedral (the default): the path is chosen by these comparisons exactly as written, ties take the else -- in
+ *      rounded arithmetic the paths differ, so the comparisons are part of the definition:
+ *          f_r > f_g ? (f_g > f_b ? rgb : (f_r > f_b ? rbg : brg))
+ *                    : (f_b > f_g ? bgr : (f_b > f_r ? gbr : grb))
+ *      for a path (a1, a2, a3): P0 is the node (i_r, i_g, i_b), P1 is P0 with axis a1 moved to its j, P2 is P1 with a2 moved too, P3
+ *      is (j_r, j_g, j_b); per output channel v = ((P0 + (P1 - P0) f_a1) + (P2 - P1) f_a2) + (P3 - P2) f_a3.
+ *      interp 0, trilinear, with lerp(a, b, w) = a + (b - a) w: four lerps along r, two along g, one along b;
+ *   4. signal 0 ("planes"): o_c = v_c.  The sample type does not change: F32 is stored as is, F16 is rounded to nearest even.  The
+ *      LUT's output stands where the source file's samples stood, in the source's transfer and normalisation;
+ *   5. signal 1 ("signal"): the LUT's output is the destination's R'G'B' signal in [0, 1]: v_c = v_c > 0 ? min(v_c, 1) : +0.0, then
+ *      step 6 of "HLG" below with the same four constants mulY, addY, mulC, addC, derived the same way from dst_bit_depth,
+ *      dst_full_range and dst_matrix (0 or 9): o_G = v_g mulY + addY, o_B = v_b mulC + addC, o_R = v_r mulC + addC, product first, then
+ *      sum.  The outputs are F32 whatever the input type.  The ring is the passthrough one (equal transfers), which takes
+ *      code-valued planes straight to its matrix (convert.cpp:930, :1012);
+ *   6. p0' = o_g, p1' = o_b, p2' = o_r.
+ * With M = max |node| and D = the largest difference between neighbouring nodes, either interpolation stays within
+ * 2^-24 (16 M + 12 (N - 1) D) of its evaluation in binary64: at most 15 rounded operations of magnitude <= M on the value path, and
+ * three index roundings of relative 2^-24 on each of three axes. */
+#define H2Y_LUT3D_FRAMES_PER_LAUNCH 64
+
+typedef struct h2y_lut3d h2y_lut3d; /* a parsed table; host memory only */
+
+/* Parse the `len` bytes of a .cube file.  Host only: no device, no context.  Read: '#' comments, blank lines, LF or CRLF, blanks and
+ * tabs; TITLE "...", DOMAIN_MIN r g b, DOMAIN_MAX r g b (default 0 0 0 and 1 1 1), LUT_3D_SIZE N, Resolve's LUT_3D_INPUT_RANGE lo hi
+ * (the same domain on all three channels), then N^3 rows of three numbers, scientific notation included, values outside [0, 1]
+ * allowed.  Refused, with `why` (may be NULL) receiving a reason that stays valid until the calling thread's next call:
+ * LUT_1D_SIZE / LUT_1D_INPUT_RANGE (1D LUTs and shaper + 3D files: H2Y_EUNSUPPORTED); H2Y_EINVAL for an unknown keyword, a keyword
+ * after the first row, a missing or repeated size, N outside 2..128, too few or too many rows, a row with other than three numbers,
+ * a value that is not finite, and hi_c <= lo_c.  On success *lut owns the table until h2y_lut3d_free. */
+int h2y_lut3d_parse(const char *text, size_t len, h2y_lut3d **lut, const char **why);
+void h2y_lut3d_free(h2y_lut3d *lut);
+/* N, the domain (lo_r, lo_g, lo_b, hi_r, hi_g, hi_b) and the title (the table's own memory); each may be NULL */
+int h2y_lut3d_info(const h2y_lut3d *lut, int *n, float domain[6], const char **title);
+/* the 3 N^3 node values as parsed, in file order */
+int h2y_lut3d_nodes(const h2y_lut3d *lut, float *rgb);
+
+/* The pass on npix pixels in host memory: k_lut3d's host twin, compiled from the same per-pixel lines.  src[c] / dst[c] are plane
+ * c = G, B, R; sample_type H2Y_SAMPLE_F32 or H2Y_SAMPLE_F16 (else H2Y_EUNSUPPORTED); dst holds the source's type in planes mode
+ * and floats in signal mode.  dst_bit_depth (8..16), dst_full_range and dst_matrix (0 or 9) are read in signal mode only. */
+int h2y_lut3d_planes(const h2y_lut3d *lut, int interp, int signal, int dst_bit_depth, int dst_full_range, int dst_matrix, int sample_type,
+                     size_t npix, const void *const src[3], void *const dst[3]);
+
+/* k_lut3d on n_frames device frames of width x height: d_src[f*3 + c] / d_dst[f*3 + c] are plane c = G, B, R of frame f, 16-byte
+ * aligned; a d_dst entry may equal its d_src entry (in place; no other overlap) but for F16 planes in signal mode, whose float
+ * output needs room of its own.  The table is uploaded once per call.  sample_type H2Y_SAMPLE_F32 or H2Y_SAMPLE_F16
+ * (H2Y_SAMPLE_U16: H2Y_EUNSUPPORTED); a bad size, null or unaligned planes, a null lut, an interp or signal other than 0 or 1, a
+ * pending batch or an open stream: H2Y_EINVAL.  Launches of up to H2Y_LUT3D_FRAMES_PER_LAUNCH frames (h2y_last_kernel_ms sums
+ * them, h2y_last_kernel_name "k_lut3d", the variant "k_lut3d<F32,TETRA,PLANES>" .. "k_lut3d<F16,TRILINEAR,SIGNAL>", or "k_lut3d_lds<...>" for a
+ * table of up to 17 nodes per axis, which the blocks read from a copy in LDS unless h2y_ctx_set_option "lut3d_lds" is "0": the
+ * same bytes either way); synchronous. */
+int h2y_lut3d_batch(h2y_ctx *ctx, int width, int height, int sample_type, const h2y_lut3d *lut, int interp, int signal, int dst_bit_depth,
+                    int dst_full_range, int dst_matrix, int n_frames, const void *const *d_src, void *const *d_dst);
+
+/* Arm an open forward ring whose decoded planes are float or half (h2y_stream_open with F32 or F16 planes, h2y_dpx_stream_open,
+ * h2y_exr_stream_open, h2y_pqcode_stream_open, h2y_hlgcode_stream_open) before its first input, once: k_lut3d then runs in place on
+ * every slot's decoded device planes, on the context's stream, after h2y_stream_gamut's and h2y_stream_tonemap's passes where those
+ * are armed (whichever was armed first), before h2y_stream_hlg's / h2y_stream_ictcp's, before pic_stats and the conversion;
+ * h2y_stream_light and h2y_stream_lightdist beside it measure what the LUT left.  The table is copied to the device here; `lut` may
+ * be freed once the call returns.
+ * The ring must have src_matrix 0 (H2Y_EUNSUPPORTED otherwise) and stats_override 1, floor 0 and ceiling 1 on all three planes
+ * (H2Y_EINVAL otherwise), for h2y_stream_tonemap's reason.  signal 1 takes the ring's dst_bit_depth, dst_full_range and dst_matrix
+ * and also needs F32 planes and equal transfers (the passthrough descriptor; H2Y_EUNSUPPORTED otherwise); it conflicts with
+ * h2y_stream_hlg and h2y_stream_ictcp in either arming order (H2Y_EINVAL), because each of them leaves code values.
+ * H2Y_EUNSUPPORTED where the planes are U16; H2Y_EINVAL on an inverse, compare-only, histogram-only, scale-only, dither-only or
+ * light-only ring, after the first input, and on a ring armed already. */
+int h2y_stream_lut3d(h2y_ctx *ctx, const h2y_lut3d *lut, int interp, int signal);
+
 /* ---- HLG: display light written as a Hybrid Log-Gamma signal (ARIB STD-B67, Rec. ITU-R BT.2100; --hlg 1) --------------------------
  * The reference has no HLG transfer (its transfer list ends at TRANSFER_RHO_GAMMA, and its code 18 is that, not H.273's HLG), so
  * there are no bytes to match: this is the project's own definition, as tone mapping's is.  It is Rep. ITU-R BT.2408's conversion

@@ -2177,6 +2177,131 @@ def tonemap_main():
     print(json.dumps({"streambench_tonemap": res}), flush=True)
 
 
+def lut3d_main():
+    """k_lut3d at N = 17, 33 and 65, F32 and F16, tetrahedral and trilinear, out of place and in place, beside k_tonemap and k_gamut
+    in the same job; then the .f32 ring from host memory armed against unarmed.  The bytes counted are the six plane streams only."""
+    import json
+
+    import torch
+
+    w, hh, nb, reps = 3840, 2160, 64, 5
+    n = w * hh
+    nf = int(os.environ.get("N", "60"))
+    depth = 3
+    ctx = h.Context(0)
+    res = {"width": w, "height": hh, "frames_per_call": nb, "reps": reps, "ring_frames": nf, "ring_depth": depth, "hbm_peak_tbs": 8.0}
+
+    def timed(key, label, nbytes, call):
+        ks = []
+        for r in range(reps + 1):  # the first call warms up
+            call()
+            if r:
+                ks.append(ctx.last_kernel_ms()[0] / nb)
+        k_ms = float(np.median(ks))
+        tbs = nbytes / (k_ms * 1e-3) / 1e12
+        res[key] = dict(kernel_us_per_frame=round(k_ms * 1e3, 2), min_us=round(min(ks) * 1e3, 2), max_us=round(max(ks) * 1e3, 2),
+                        bytes_per_frame=nbytes, kernel_tbs=round(tbs, 2), hbm_peak_fraction=round(tbs / 8.0, 3), variant=ctx.last_kernel_variant())
+        print(f"{label:40s} {nb} frames per call: {k_ms*1e3:7.2f} us/frame ({min(ks)*1e3:.2f}..{max(ks)*1e3:.2f})  {nbytes/1e6:6.1f} MB/frame  "
+              f"{tbs:5.2f} TB/s = {tbs/8.0*100:4.1f} % of 8 TB/s", flush=True)
+
+    def table(size):
+        """a look: the identity on the unit domain, every node moved a little"""
+        ax = np.linspace(0, 1, size)
+        b, g, r = np.meshgrid(ax, ax, ax, indexing="ij")
+        nodes = np.stack([r, g, b], -1).reshape(-1, 3) + np.random.default_rng(size).uniform(-0.02, 0.02, (size ** 3, 3))
+        return h.Lut3d(f"LUT_3D_SIZE {size}\n" + "\n".join("%.9g %.9g %.9g" % tuple(v) for v in nodes.astype(np.float32)) + "\n")
+
+    luts = {size: table(size) for size in (17, 33, 65)}
+    sc = (10, 0, h.MATRIX_BT2020NC)
+    # 1. the same 64 distinct frames for every kernel: uniformly random samples, so neighbouring pixels gather from unrelated cells of
+    # the table (a picture's neighbours mostly share a cell: the last line of the block times one such frame set)
+    for name, sample, dt in (("f32", h.SAMPLE_F32, torch.float32), ("f16", h.SAMPLE_F16, torch.float16)):
+        src = [[torch.rand(n, device="cuda").to(dt) for _ in range(3)] for _ in range(nb)]
+        dst = [[torch.empty(n, dtype=dt, device="cuda") for _ in range(3)] for _ in range(nb)]
+        torch.cuda.synchronize()
+        nbytes = 2 * 3 * n * (4 if sample == h.SAMPLE_F32 else 2)
+        timed(f"k_tonemap_{name}_out_of_place", f"k_tonemap {name} out of place", nbytes, lambda: ctx.tonemap_batch(w, hh, sample, 1000, 100, 1, src, dst))
+        timed(f"k_gamut_{name}_out_of_place", f"k_gamut {name} out of place", nbytes, lambda: ctx.gamut_batch(w, hh, sample, 9, 1, 1, src, dst))
+        for size, lut in luts.items():
+            for interp, iname in ((1, "tetra"), (0, "trilinear")):
+                timed(f"k_lut3d_{size}_{name}_{iname}_out_of_place", f"k_lut3d N={size} {name} {iname} out of place", nbytes,
+                      lambda: ctx.lut3d_batch(w, hh, sample, lut, interp, 0, *sc, src, dst))
+                if size == 17:  # the same table through L2, as the larger ones are read
+                    ctx.set_option("lut3d_lds", 0)
+                    timed(f"k_lut3d_{size}_{name}_{iname}_out_of_place_l2", f"k_lut3d N={size} {name} {iname} out of place, no LDS", nbytes,
+                          lambda: ctx.lut3d_batch(w, hh, sample, lut, interp, 0, *sc, src, dst))
+                    ctx.set_option("lut3d_lds", 1)
+        if sample == h.SAMPLE_F32:
+            timed("k_lut3d_33_f32_tetra_signal_out_of_place", "k_lut3d N=33 f32 tetra signal out of place", nbytes,
+                  lambda: ctx.lut3d_batch(w, hh, sample, luts[33], 1, 1, *sc, src, dst))
+        del dst
+        # in place: the look keeps the samples in the domain, call after call
+        for size, lut in luts.items():
+            for interp, iname in ((1, "tetra"), (0, "trilinear")):
+                timed(f"k_lut3d_{size}_{name}_{iname}_in_place", f"k_lut3d N={size} {name} {iname} in place", nbytes,
+                      lambda: ctx.lut3d_batch(w, hh, sample, lut, interp, 0, *sc, src))
+        timed(f"k_tonemap_{name}_in_place", f"k_tonemap {name} in place", nbytes, lambda: ctx.tonemap_batch(w, hh, sample, 1000, 100, 1, src))
+        if sample == h.SAMPLE_F32:  # a smooth picture: ramps with a little noise, neighbours in one cell
+            x = torch.arange(n, device="cuda") % w / w
+            y = torch.arange(n, device="cuda") // w / hh
+            for f in src:
+                f[0].copy_((x + 0.01 * torch.rand(n, device="cuda")).clamp(0, 1))
+                f[1].copy_((y + 0.01 * torch.rand(n, device="cuda")).clamp(0, 1))
+                f[2].copy_(((x + y) / 2 + 0.01 * torch.rand(n, device="cuda")).clamp(0, 1))
+            torch.cuda.synchronize()
+            for size, lut in luts.items():
+                timed(f"k_lut3d_{size}_f32_tetra_in_place_smooth", f"k_lut3d N={size} f32 tetra in place, smooth", nbytes,
+                      lambda: ctx.lut3d_batch(w, hh, sample, lut, 1, 0, *sc, src))
+            ctx.set_option("lut3d_lds", 0)
+            timed("k_lut3d_17_f32_tetra_in_place_smooth_l2", "k_lut3d N=17 f32 tetra in place, smooth, no LDS", nbytes,
+                  lambda: ctx.lut3d_batch(w, hh, sample, luts[17], 1, 0, *sc, src))
+            ctx.set_option("lut3d_lds", 1)
+        del src
+        torch.cuda.empty_cache()
+    t, l33, l65 = (res[k]["kernel_us_per_frame"] for k in ("k_tonemap_f32_out_of_place", "k_lut3d_33_f32_tetra_out_of_place",
+                                                          "k_lut3d_65_f32_tetra_out_of_place"))
+    res["lut3d_33_over_tonemap"] = round(l33 / t, 3)
+    res["lut3d_65_over_33"] = round(l65 / l33, 3)
+    print(f"k_lut3d N=33 tetra f32 / k_tonemap f32: {l33 / t:.3f};  N=65 / N=33: {l65 / l33:.3f}", flush=True)
+
+    # 2. the .f32 ring from host memory, unarmed and armed
+    planes = [np.random.default_rng(31 + c).random(n, dtype=np.float32) for c in range(3)]
+    d32 = h.make_desc(w, hh, dst_depth=10, src_transfer=16, dst_transfer=16, dst_matrix=h.MATRIX_BT2020NC, src_primaries=9, dst_primaries=9,
+                      resampler=1, stats=[(0, 1)] * 3)
+
+    def ring(arm):
+        ctx.stream_open(d32, depth)
+        if arm:
+            ctx.stream_lut3d(luts[33], 1, 0)
+        inflight = 0
+        t0 = time.perf_counter()
+        for _ in range(nf):
+            slot = ctx.stream_input()
+            for c in range(3):
+                slot[c][:] = planes[c]
+            ctx.stream_submit()
+            inflight += 1
+            if inflight == depth - 1:
+                ctx.stream_output()
+                inflight -= 1
+        while inflight:
+            ctx.stream_output()
+            inflight -= 1
+        dt = (time.perf_counter() - t0) / nf
+        ctx.stream_close()
+        return dt
+
+    ring(False)  # warm-up
+    res["f32"] = []
+    for _ in range(3):  # unarmed and armed in turn: what the card drifts by shows in both alike
+        t_plain, t_armed = ring(False), ring(True)
+        res["f32"].append(dict(unarmed_fps=round(1 / t_plain, 1), armed_fps=round(1 / t_armed, 1), armed_share=round(t_plain / t_armed, 3)))
+        print(f"f32          ring from host memory: unarmed {1/t_plain:6.1f} frames/s   armed {1/t_armed:6.1f} frames/s "
+              f"({t_plain/t_armed*100:5.1f} %)", flush=True)
+    ctx.close()
+    print(json.dumps({"streambench_lut3d": res}), flush=True)
+
+
 def hlg_main():
     import json
 
@@ -2494,6 +2619,8 @@ if __name__ == "__main__":
         gamut_main()
     elif sys.argv[1:] == ["tonemap"]:
         tonemap_main()
+    elif sys.argv[1:] == ["lut3d"]:
+        lut3d_main()
     elif sys.argv[1:] == ["hlg"]:
         hlg_main()
     elif sys.argv[1:] == ["ictcp"]:
