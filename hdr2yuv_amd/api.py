@@ -51,6 +51,7 @@ EXPORTS = [
     "h2y_lut3d_parse", "h2y_lut3d_free", "h2y_lut3d_info", "h2y_lut3d_nodes", "h2y_lut3d_planes", "h2y_lut3d_batch", "h2y_stream_lut3d",
     "h2y_hlg_tables", "h2y_hlg_planes", "h2y_hlg_batch", "h2y_stream_hlg",
     "h2y_hlg_inverse_tables", "h2y_hlg_inverse_planes", "h2y_hlg_linearize_batch", "h2y_hlgcode_stream_open",
+    "h2y_sdr_inverse_planes", "h2y_sdr_linearize_batch", "h2y_sdrcode_stream_open",
     "h2y_ictcp_batch", "h2y_stream_ictcp",
     "h2y_ctx_set_chroma_siting", "h2y_subsample_420_sited",
     "h2y_ctx_set_inverse_chroma_siting", "h2y_upsample_444_sited",
@@ -77,6 +78,7 @@ LUT3D_TRILINEAR, LUT3D_TETRAHEDRAL = 0, 1
 LUT3D_PLANES, LUT3D_SIGNAL = 0, 1
 HLG_FRAMES_PER_LAUNCH = 64
 HLG_PEAK_MIN, HLG_PEAK_MAX = 400, 2000
+SDR_WHITE_MIN, SDR_WHITE_MAX, SDR_WHITE_DEFAULT = 80, 1000, 203  # the reference white of an SDR code source, cd/m2
 ICTCP_FRAMES_PER_LAUNCH = 64
 SCALE_TAPS = 32  # coefficients per row of scale_taps' table
 DITHER_FRAMES_PER_LAUNCH = 64
@@ -594,6 +596,12 @@ def load_library():
     L.h2y_hlg_linearize_batch.restype = C.c_int
     L.h2y_hlgcode_stream_open.argtypes = [C.c_void_p, C.POINTER(H2YDesc), C.POINTER(H2YCodelightDesc), C.c_int, C.c_int]
     L.h2y_hlgcode_stream_open.restype = C.c_int
+    L.h2y_sdr_inverse_planes.argtypes = [C.c_int, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.h2y_sdr_inverse_planes.restype = C.c_int
+    L.h2y_sdr_linearize_batch.argtypes = [C.c_void_p, C.POINTER(H2YCodelightDesc), C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.h2y_sdr_linearize_batch.restype = C.c_int
+    L.h2y_sdrcode_stream_open.argtypes = [C.c_void_p, C.POINTER(H2YDesc), C.POINTER(H2YCodelightDesc), C.c_int, C.c_int]
+    L.h2y_sdrcode_stream_open.restype = C.c_int
     L.h2y_hlg_batch.argtypes = [C.c_void_p] + [C.c_int] * 9 + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.h2y_hlg_batch.restype = C.c_int
     L.h2y_stream_hlg.argtypes = [C.c_void_p] + [C.c_int] * 2
@@ -952,6 +960,23 @@ def hlg_inverse_planes(planes, peak: int):
     outs = (C.c_void_p * 3)(*[p.ctypes.data for p in out])
     lib = load_library()
     rc = lib.h2y_hlg_inverse_planes(int(peak), src[0].size, ins, outs)
+    if rc != H2Y_OK:
+        raise H2YError(rc, (lib.h2y_last_error(None) or b"").decode())
+    return out
+
+
+def sdr_inverse_planes(planes, white: int = SDR_WHITE_DEFAULT):
+    """h2y_sdr_inverse_planes (host only, no device): steps 4s-6s of the light of SDR code planes on three float32 numpy planes G', B',
+    R'; returns the three float32 planes of light (1.0 = 10000 cd/m2) k_sdr_linearize writes for them with the reference white at
+    `white` cd/m2.  Raises H2YError (EINVAL: white outside 80..1000)."""
+    src = [np.ascontiguousarray(p) for p in planes]
+    if len(src) != 3 or any(p.dtype != np.float32 or p.shape != src[0].shape for p in src):
+        raise ValueError("three float32 planes of one shape")
+    out = [np.empty(p.shape, np.float32) for p in src]
+    ins = (C.c_void_p * 3)(*[p.ctypes.data for p in src])
+    outs = (C.c_void_p * 3)(*[p.ctypes.data for p in out])
+    lib = load_library()
+    rc = lib.h2y_sdr_inverse_planes(int(white), src[0].size, ins, outs)
     if rc != H2Y_OK:
         raise H2YError(rc, (lib.h2y_last_error(None) or b"").decode())
     return out
@@ -1316,12 +1341,30 @@ class Context:
                 outs[3 * f + c] = self._ptr(planes_out[f][c])
         self._check(self.lib.h2y_hlg_linearize_batch(self.h, C.byref(d), int(peak), n, pf, outs))
 
-    def pqcode_stream_open(self, d, src: H2YCodelightDesc, depth=3, hlg_peak=None) -> None:
+    def sdr_linearize_batch(self, d: H2YCodelightDesc, white: int, frames, planes_out) -> None:
+        """k_sdr_linearize on device frames of SDR (BT.1886) codes with the reference white at `white` cd/m2: linearize_batch's
+        arguments and layout; planes_out[f] receive the frame's light (1.0 = 10000 cd/m2)."""
+        n = len(frames)
+        if len(planes_out) != n:
+            raise ValueError("frames and planes_out differ in length")
+        pf = (C.c_void_p * max(n, 1))(*[self._ptr(x) for x in frames])
+        outs = (C.c_void_p * max(3 * n, 1))()
+        for f in range(n):
+            for c in range(3):
+                outs[3 * f + c] = self._ptr(planes_out[f][c])
+        self._check(self.lib.h2y_sdr_linearize_batch(self.h, C.byref(d), int(white), n, pf, outs))
+
+    def pqcode_stream_open(self, d, src: H2YCodelightDesc, depth=3, hlg_peak=None, sdr_white=None) -> None:
         """The forward ring on PQ code frames: stream_input gives one uint8 view of the pinned slot to fill with the frame's three
         u16 planes one after the other; the device linearises them (k_up444, k_linearize) into the F32 G,B,R planes d describes
         (src_transfer 8, src_matrix 0, stats_override 1 with floor 0, ceiling 1); stream_output gives the .yuv frame.  With hlg_peak
-        the codes are HLG's at that display peak (h2y_hlgcode_stream_open: k_hlg_linearize)."""
-        if hlg_peak is None:
+        the codes are HLG's at that display peak (h2y_hlgcode_stream_open: k_hlg_linearize), with sdr_white SDR (BT.1886) codes whose
+        reference white lies at that many cd/m2 (h2y_sdrcode_stream_open: k_sdr_linearize)."""
+        if hlg_peak is not None and sdr_white is not None:
+            raise ValueError("hlg_peak and sdr_white exclude one another")
+        if sdr_white is not None:
+            self._check(self.lib.h2y_sdrcode_stream_open(self.h, C.byref(d), C.byref(src), int(sdr_white), depth))
+        elif hlg_peak is None:
             self._check(self.lib.h2y_pqcode_stream_open(self.h, C.byref(d), C.byref(src), depth))
         else:
             self._check(self.lib.h2y_hlgcode_stream_open(self.h, C.byref(d), C.byref(src), int(hlg_peak), depth))
@@ -1334,6 +1377,10 @@ class Context:
     def hlgcode_stream_open(self, d, src: H2YCodelightDesc, peak: int, depth=3) -> None:
         """The forward ring on HLG code frames at a display peak of `peak` cd/m2: pqcode_stream_open with k_hlg_linearize as its decode."""
         self.pqcode_stream_open(d, src, depth, hlg_peak=peak)
+
+    def sdrcode_stream_open(self, d, src: H2YCodelightDesc, white: int = SDR_WHITE_DEFAULT, depth=3) -> None:
+        """The forward ring on SDR code frames with the reference white at `white` cd/m2: pqcode_stream_open with k_sdr_linearize as its decode."""
+        self.pqcode_stream_open(d, src, depth, sdr_white=white)
 
     def scale_batch(self, src_w, src_h, dst_w, dst_h, chroma, bit_depth, full_range, gbr, a, frames_src, frames_dst) -> None:
         """k_scale on device frames (tensors or pointers, each frame's planes contiguous from a 16-byte aligned base):

@@ -214,6 +214,16 @@
  *             src_hlg_gamma: "%.4f", src_hlg_note:, and linearize_from: names HLG codes.  Refused (exit 1, also under --dry_run): a
  *             value other than 0 or 1, --src_hlg_peak without --src_hlg 1 or outside 400..2000, --src_hlg 1 without --linearize 1 or
  *             beside --light_only, --compare_only, --delta_e (those read PQ codes) or --dither_only.
+ * --src_sdr 1 [--src_sdr_white W] (an addition), beside --linearize 1 only: the file's codes are an SDR master's, coded with the BT.1886
+ *             transfer (include/hdr2yuv_hip.h, "light of SDR code planes"): the device places them in absolute light with the reference
+ *             white at W cd/m2 (80..1000, 203 by default: Rep. ITU-R BT.2408's display-referred direct mapping) instead of reading them
+ *             as PQ.  --src_transfer_characteristics may be left out or be one of this program's BT.1886 codes (1, 6, 14, 15); the
+ *             destination's transfer must be given (or --hlg 1 / --ictcp 1): it must not silently inherit BT.1886.  Everything else
+ *             --linearize 1 accepts and refuses stays so.  The banner carries src_sdr:, src_sdr_white: ("(default)" where not given),
+ *             src_sdr_gamma: 2.4, and linearize_from: names SDR (BT.1886) codes.  Refused (exit 1, also under --dry_run): a value
+ *             other than 0 or 1, --src_sdr_white without --src_sdr 1 or outside 80..1000, --src_sdr 1 without --linearize 1, beside
+ *             --src_hlg 1 or --src_ictcp 1, beside any *_only flag, a source transfer that is given and is not 1, 6, 14 or 15, no
+ *             destination transfer.
  * --delta_e 1 [--delta_e_threshold X] [--delta_e_limit Y] (an addition): Delta E ITP (Rec. ITU-R BT.2124; include/hdr2yuv_hip.h, "Delta E
  *             ITP of PQ code planes", states every step) of every compared frame against the reference's, beside the PSNR, wherever a
  *             comparison runs on PQ code frames of BT.2020 primaries: with --compare_only 1 on two .yuv files (--src_chroma_format_idc
@@ -332,6 +342,10 @@ struct cli_args {
     /* --src_hlg 1 [--src_hlg_peak L], beside --linearize 1: the file's codes are HLG's, linearised at a display peak of src_hlg_peak
      * cd/m2; src_transfer_given: --src_transfer_characteristics was on the command line (refused beside the flag) */
     int src_hlg = 0, src_hlg_peak = 1000;
+    /* --src_sdr 1 [--src_sdr_white W], beside --linearize 1: the file's codes are BT.1886's, placed with the reference white at
+     * src_sdr_white cd/m2 */
+    int src_sdr = 0, src_sdr_white = H2Y_SDR_WHITE_DEFAULT;
+    bool src_sdr_given = false, src_sdr_white_given = false;
     /* --ictcp 1: the rung is PQ ICtCp (H.273 matrix_coeffs 14); resolved: ictcp_dst_transfer and ictcp_dst_matrix, what
      * --dst_transfer_characteristics and --dst_matrix_coeffs gave before the flag replaced them with the passthrough descriptor's 8 and
      * 0 (-1: not given).  --src_ictcp 1: the codes --linearize 1, --light_only 1 or --compare_only 1 --delta_e 1 read are PQ I, Ct, Cp */
@@ -427,6 +441,10 @@ static inline void cli_help()
            "  an HLG master as the source: [--linearize 1 --src_hlg 1 [--src_hlg_peak L]] (the .yuv / .rgb holds Hybrid Log-Gamma codes:\n"
            "  the OETF's inverse and the OOTF at a display peak of L cd/m2, 400..2000, 1000 by default, on the GPU; it replaces\n"
            "  --src_transfer_characteristics, whose 18 is RHO_GAMMA in this program; to PQ it is BT.2408's HLG -> PQ conversion)\n"
+           "  an SDR master as the source: [--linearize 1 --src_sdr 1 [--src_sdr_white W]] (the .yuv / .rgb holds BT.709 or BT.2020 SDR\n"
+           "  codes of the BT.1886 transfer, --src_transfer_characteristics 1, 6, 14, 15 or left out: gamma 2.4 and the reference white\n"
+           "  at W cd/m2, 80..1000, 203 by default, on the GPU; BT.2408's display-referred mapping of SDR into a PQ or HLG container;\n"
+           "  give --dst_transfer_characteristics or --hlg 1 / --ictcp 1, and --gamut_convert 1 for BT.709 primaries)\n"
            "  primaries: [--gamut_convert 1 [--gamut_clip 0|1]] (float or half G,B,R source planes in linear light converted from\n"
            "  --src_colour_primaries to --dst_colour_primaries on the GPU before the conversion; 1 BT.709, 8 / 9 BT.2020, 12 P3-D65,\n"
            "  10 XYZ; what is not above 0 is clipped to 0 unless --gamut_clip 0)\n"
@@ -498,6 +516,8 @@ static inline void cli_parse(cli_args &a, int argc, char **argv)
         else if (is("--tone_map_dst_peak")) { a.tone_dst_peak = atoi(val()); a.tone_dst_peak_given = true; }
         else if (is("--src_hlg")) { a.src_hlg = atoi(val()); a.src_hlg_given = true; }
         else if (is("--src_hlg_peak")) { a.src_hlg_peak = atoi(val()); a.src_hlg_peak_given = true; }
+        else if (is("--src_sdr")) { a.src_sdr = atoi(val()); a.src_sdr_given = true; }
+        else if (is("--src_sdr_white")) { a.src_sdr_white = atoi(val()); a.src_sdr_white_given = true; }
         else if (is("--hlg")) { a.hlg = atoi(val()); a.hlg_given = true; }
         else if (is("--ictcp")) { a.ictcp = atoi(val()); a.ictcp_given = true; }
         else if (is("--src_ictcp")) { a.src_ictcp = atoi(val()); a.src_ictcp_given = true; }
@@ -702,6 +722,7 @@ static inline int cli_resolve_light_only(cli_args &a);
 static inline int cli_resolve_scenes(cli_args &a);
 static inline int cli_resolve_linearize(cli_args &a);
 static inline int cli_resolve_src_hlg(cli_args &a);
+static inline int cli_resolve_src_sdr(cli_args &a);
 static inline int cli_resolve_delta_e(cli_args &a);
 static inline int cli_resolve_dither(cli_args &a);
 static inline int cli_resolve_dither_only(cli_args &a);
@@ -717,6 +738,10 @@ static inline int cli_resolve(cli_args &a)
     }
     if ((a.src_hlg_given || a.src_hlg_peak_given) && a.dither_only == 1) {
         printf("src_hlg: %d\nWARNING: --src_hlg goes with --linearize 1: not with --dither_only 1\n", a.src_hlg);
+        return 1;
+    }
+    if ((a.src_sdr_given || a.src_sdr_white_given) && a.dither_only == 1) {
+        printf("src_sdr: %d\nWARNING: --src_sdr goes with --linearize 1: not with --dither_only 1\n", a.src_sdr);
         return 1;
     }
     if ((a.lut3d || a.lut3d_interp_given || a.lut3d_signal_given) && a.dither_only == 1) {
@@ -755,6 +780,7 @@ static inline int cli_resolve_all(cli_args &a)
         }
     }
     if ((a.src_hlg_given || a.src_hlg_peak_given) && cli_resolve_src_hlg(a)) return 1; /* the transfer of --linearize 1's source */
+    if ((a.src_sdr_given || a.src_sdr_white_given) && cli_resolve_src_sdr(a)) return 1; /* likewise: BT.1886 codes at a reference white */
     if (a.src_ictcp_given && cli_resolve_src_ictcp(a)) return 1; /* the matrix of the codes the three flows below read */
     if (a.linearize == 1 && cli_resolve_linearize(a)) return 1;
     const bool lut3d_flags = a.lut3d || a.lut3d_interp_given || a.lut3d_signal_given;
@@ -1262,6 +1288,56 @@ static inline int cli_resolve_src_hlg(cli_args &a)
     return 0;
 }
 
+/* --src_sdr / --src_sdr_white: the codes --linearize 1 reads are an SDR master's (include/hdr2yuv_hip.h, "light of SDR code planes"),
+ * placed in absolute light with the reference white at src_sdr_white cd/m2.  Runs before cli_resolve_linearize, which then skips its
+ * transfer check; prints the src_sdr lines; returns the number of argument errors */
+static inline int cli_resolve_src_sdr(cli_args &a)
+{
+    printf("src_sdr: %d\n", a.src_sdr);
+    if (a.src_sdr != 0 && a.src_sdr != 1) {
+        printf("WARNING: src_sdr(%d) not 0 or 1\n", a.src_sdr);
+        return 1;
+    }
+    if (!a.src_sdr) {
+        if (a.src_sdr_white_given) {
+            printf("WARNING: --src_sdr_white needs --src_sdr 1\n");
+            return 1;
+        }
+        return 0;
+    }
+    int arg_errors = 0;
+    if (a.linearize != 1) {
+        printf("WARNING: --src_sdr 1 is the transfer of the source --linearize 1 reads: it needs --linearize 1\n");
+        arg_errors++;
+    }
+    if (a.src_hlg == 1 || a.src_ictcp == 1) {
+        printf("WARNING: --src_sdr 1: the file's codes are BT.1886's: not with --%s 1\n", a.src_hlg == 1 ? "src_hlg" : "src_ictcp");
+        arg_errors++;
+    }
+    if (a.light_only || a.compare_only || a.hist_only || a.scale_only) {
+        printf("WARNING: --src_sdr 1 is the source of a conversion: not with --%s 1\n",
+               a.light_only ? "light_only" : a.compare_only ? "compare_only" : a.hist_only ? "histogram_only" : "scale_only");
+        arg_errors++;
+    }
+    const int t = a.in.transfer_characteristics;
+    if (a.src_transfer_given && t != 1 && t != 6 && t != 14 && t != 15) {
+        printf("WARNING: --src_sdr 1 reads BT.1886 codes: src_transfer_characteristics(%d) is not 1, 6, 14 or 15 (or leave it out)\n", t);
+        arg_errors++;
+    }
+    if (a.out.transfer_characteristics == -1) {
+        printf("WARNING: --src_sdr 1: the destination must not inherit BT.1886 from a source that becomes absolute light: give "
+               "--dst_transfer_characteristics (or --hlg 1 / --ictcp 1)\n");
+        arg_errors++;
+    }
+    if (a.src_sdr_white < H2Y_SDR_WHITE_MIN || a.src_sdr_white > H2Y_SDR_WHITE_MAX) {
+        printf("WARNING: --src_sdr 1: src_sdr_white(%d) outside %d <= white <= %d cd/m2\n", a.src_sdr_white, H2Y_SDR_WHITE_MIN, H2Y_SDR_WHITE_MAX);
+        arg_errors++;
+    }
+    if (arg_errors) return arg_errors;
+    printf("src_sdr_white: %d%s\nsrc_sdr_gamma: 2.4\n", a.src_sdr_white, a.src_sdr_white_given ? "" : " (default)");
+    return 0;
+}
+
 /* --linearize 1: a PQ .yuv or .rgb as the forward flow's source.  Checks the file's attributes as --light_only checks them, gives the
  * destination what it leaves unset from the source as parsed (hdr2yuv.cpp:265-318), keeps the file's attributes in a.lin and
  * rewrites a.in to the planes the ring decodes -- F32, LINEAR, G,B,R, 4:4:4 -- so that every resolver after this one sees a .f32
@@ -1294,7 +1370,7 @@ static inline int cli_resolve_linearize(cli_args &a)
         printf("WARNING: video_full_range_flag(%d) not 0 or 1\n", a.in.video_full_range_flag);
         arg_errors++;
     }
-    if (a.src_hlg != 1 && a.in.transfer_characteristics != 16) { /* (--src_hlg 1 is the source's transfer: cli_resolve_src_hlg) */
+    if (a.src_hlg != 1 && a.src_sdr != 1 && a.in.transfer_characteristics != 16) { /* (--src_hlg 1 and --src_sdr 1 are the source's transfer: their resolvers) */
         printf("WARNING: --linearize 1 linearises PQ codes: src_transfer_characteristics(%d) is not 16\n", a.in.transfer_characteristics);
         arg_errors++;
     }
@@ -1339,7 +1415,8 @@ static inline int cli_resolve_linearize(cli_args &a)
     }
     if (arg_errors) return arg_errors;
     static const char *const kMatrix[15] = {"G,B,R", "BT.709", "", "", "", "", "", "", "", "BT.2020nc", "", "", "", "", "ICtCp"};
-    printf("linearize_from: %s codes, bit_depth %d %s range, matrix_coeffs %d (%s), chroma_format_idc %d, upsampler %s\n", a.src_hlg == 1 ? "HLG" : "PQ", a.in.bit_depth,
+    printf("linearize_from: %s codes, bit_depth %d %s range, matrix_coeffs %d (%s), chroma_format_idc %d, upsampler %s\n",
+           a.src_hlg == 1 ? "HLG" : a.src_sdr == 1 ? "SDR (BT.1886)" : "PQ", a.in.bit_depth,
            a.in.video_full_range_flag ? "full" : "video", m, kMatrix[m], chroma,
            chroma == H2Y_CHROMA_444 ? "none" : !a.resampler ? "replicate" : a.src_siting == 2 ? "fir_top_left" : "fir");
     /* hdr2yuv.cpp:265-318: unset destination attributes <- the source's, as parsed */

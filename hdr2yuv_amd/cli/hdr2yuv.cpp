@@ -158,7 +158,9 @@
  * the slot's F32 G,B,R planes; everything armed on the ring sees those planes.  One more source kind of the forward flow, not a flow
  * of its own.  The banner carries linearize: and linearize_from:.  With --src_hlg 1 [--src_hlg_peak L] beside it the file's codes
  * are HLG's and the ring is h2y_hlgcode_stream_open's at that display peak; nothing else differs.  The banner then carries src_hlg:,
- * src_hlg_peak:, src_hlg_gamma: and src_hlg_note: too.
+ * src_hlg_peak:, src_hlg_gamma: and src_hlg_note: too.  With --src_sdr 1 [--src_sdr_white W] beside it the codes are an SDR
+ * master's (BT.1886) and the ring is h2y_sdrcode_stream_open's with the reference white at W cd/m2; the banner then carries src_sdr:,
+ * src_sdr_white: and src_sdr_gamma:.
  *
  * Chroma siting (--dst_chroma_sample_loc_type 0|2 on the forward flow to .yuv; h2y_cli_args.h): each GPU thread sets its context's
  * siting (h2y_ctx_set_chroma_siting) before it opens its ring, so every frame, and whatever is armed on the ring, has its 4:2:0
@@ -413,6 +415,7 @@ static flow forward_flow(const job &j)
             const h2y_codelight_desc code{a.lin.width, a.lin.height, a.lin.chroma_format_idc, a.lin.bit_depth, a.lin.video_full_range_flag,
                                           a.lin.matrix_coeffs, a.resampler};
             if (a.src_hlg == 1) return h2y_hlgcode_stream_open(ctx, &j.d, &code, a.src_hlg_peak, kRingDepth); /* the file's codes are HLG's */
+            if (a.src_sdr == 1) return h2y_sdrcode_stream_open(ctx, &j.d, &code, a.src_sdr_white, kRingDepth); /* the file's codes are BT.1886's */
             return h2y_pqcode_stream_open(ctx, &j.d, &code, kRingDepth);
         }
         return a.in_type == CLI_IN_DPX    ? h2y_dpx_stream_open(ctx, &j.d, &s.di, kRingDepth)

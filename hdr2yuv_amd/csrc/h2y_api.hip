@@ -1320,12 +1320,12 @@ int decode_src::planes_check(h2y_ctx *ctx, const h2y_desc *d) const
     case PQCODE: /* the linearised planes: F32 LINEAR G,B,R in [+0, 1], floor 0 and ceiling 1 whatever the frame holds */
         if (d->in_sample_type != H2Y_SAMPLE_F32 || d->src_transfer != 8 || d->src_matrix != H2Y_MATRIX_GBR)
             return fail(ctx, H2Y_EINVAL, "%s code stream linearises to F32 G,B,R planes: in_sample_type H2Y_SAMPLE_F32, src_transfer 8, src_matrix 0",
-                        hlg ? "an HLG" : "a PQ");
-        if (d->stats_override != 1) return fail(ctx, H2Y_EINVAL, "%s code stream needs stats_override 1 with floor 0 and ceiling 1", hlg ? "an HLG" : "a PQ");
+                        hlg ? "an HLG" : sdr ? "an SDR" : "a PQ");
+        if (d->stats_override != 1) return fail(ctx, H2Y_EINVAL, "%s code stream needs stats_override 1 with floor 0 and ceiling 1", hlg ? "an HLG" : sdr ? "an SDR" : "a PQ");
         for (int c = 0; c < 3; c++)
             if (d->floor[c] != 0 || d->ceiling[c] != 1)
-                return fail(ctx, H2Y_EINVAL, "%s code stream needs stats_override 1 with floor 0 and ceiling 1", hlg ? "an HLG" : "a PQ");
-        what = hlg ? "HLG code frame" : "PQ code frame", w = code.width, h = code.height;
+                return fail(ctx, H2Y_EINVAL, "%s code stream needs stats_override 1 with floor 0 and ceiling 1", hlg ? "an HLG" : sdr ? "an SDR" : "a PQ");
+        what = hlg ? "HLG code frame" : sdr ? "SDR code frame" : "PQ code frame", w = code.width, h = code.height;
         break;
     default: return H2Y_OK;
     }

@@ -1,7 +1,7 @@
 /*
  * h2y_codepixel.h -- what the kernels that read PQ code planes share (k_codelight in h2y_codelight.hip, k_linearize in
  * h2y_linearize.hip): eight codes of a plane, and one pixel's three lights L_G, L_B, L_R as include/hdr2yuv_hip.h defines them
- * ("light of PQ code planes", steps 2-4; matrix 14: "light of ICtCp code planes"); k_hlg_linearize (h2y_hlgsrc.hip) takes steps 2-3, code_primes.  Device code only; include after h2y_device.h and h2y_light1.h, in a file built
+ * ("light of PQ code planes", steps 2-4; matrix 14: "light of ICtCp code planes"); k_hlg_linearize (h2y_hlgsrc.hip) takes steps 2-3, code_primes; k_sdr_linearize (h2y_sdrsrc.hip) the lights of SDR codes, code_sdr_lights.  Device code only; include after h2y_device.h and h2y_light1.h, in a file built
  * -ffp-contract=off: every product and sum of the matrix is rounded by itself.
  */
 #pragma once
@@ -94,4 +94,17 @@ __device__ __forceinline__ void code_lights(const codelight_args &a, const pq_re
         lb = light1<true>(a.pp, tab, 1, clamp01(b));
         lr = light1<true>(a.pp, tab, 2, clamp01(r));
     }
+}
+
+/* one pixel's SDR codes -> its three lights ("light of SDR code planes", steps 2-6s; k_sdr_linearize in h2y_sdrsrc.hip): normalise,
+ * matrix, clamp, bt1886_f through light1<true>'s tiers (a.pp and tab are the BT.1886 stage's), then one product with kappa */
+template <int MATRIX>
+__device__ __forceinline__ void code_sdr_lights(const codelight_args &a, const pq_recA *tab, float kappa, uint32_t c0, uint32_t c1, uint32_t c2,
+                                                float &lg, float &lb, float &lr)
+{
+    float g, b, r;
+    code_primes<MATRIX>(a, c0, c1, c2, g, b, r);
+    lg = light1<true>(a.pp, tab, 0, clamp01(g)) * kappa;
+    lb = light1<true>(a.pp, tab, 1, clamp01(b)) * kappa;
+    lr = light1<true>(a.pp, tab, 2, clamp01(r)) * kappa;
 }

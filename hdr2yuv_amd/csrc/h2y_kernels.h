@@ -513,6 +513,16 @@ struct hlgsrc_args {
 int h2y_hlg_linearize_grid(int n_cu, uint32_t npix, int n_frames); /* blocks per frame */
 hipError_t h2y_launch_hlg_linearize(int matrix, int grid, hipStream_t st, const hlgsrc_args &a, const linearize_frame *frames, int n_frames);
 
+/* k_sdr_linearize (h2y_sdrsrc.hip): the light of frames of three u16 SDR (BT.1886) code planes as binary32 planes G, B, R
+ * (include/hdr2yuv_hip.h, "light of SDR code planes"); k_linearize's frame table */
+struct sdrsrc_args {
+    codelight_args c;        /* k_linearize's, with the BT.1886 stage in place of PQ's: table is H2Y_TFN_G24's, pp carries src_tf
+                                H2Y_TF_BT1886, src_fn H2Y_TFN_G24, tf_ext[0], norm_identity 1 */
+    float kappa;             /* W / 10000 rounded once */
+};
+int h2y_sdr_linearize_grid(uint32_t npix, int n_frames); /* blocks per frame */
+hipError_t h2y_launch_sdr_linearize(int matrix, int grid, hipStream_t st, const sdrsrc_args &a, const linearize_frame *frames, int n_frames);
+
 /* k_scale (h2y_scale.hip): the Lanczos resampler of include/hdr2yuv_hip.h on frames of three u16 planes.  One axis' table on the
  * device: first[d] and count[d] (int32), then d rows of H2Y_SCALE_MAX_TAPS int16 coefficients (zero past count). */
 enum { H2Y_SCALE_MAX_TAPS = 32, H2Y_SCALE_TILE_W = 64, H2Y_SCALE_TILE_H = 32, H2Y_SCALE_STAGE_ROWS = 16 };

@@ -1378,9 +1378,14 @@ int h2y_stream_deltae_result(h2y_ctx *ctx, h2y_deltae_stats *out)
 
 /* ---- linearised PQ code planes (h2y_linearize_batch, h2y_pqcode_stream_open): include/hdr2yuv_hip.h states the definition ------ */
 
-static std::string linearize_variant(const codelight_plan &p, bool hlg)
+static const char *linearize_kernel(code_tf tf)
 {
-    return std::string(hlg ? "k_hlg_linearize<" : "k_linearize<") + matrix_name(p.matrix) + "," +
+    return tf.kind == code_tf::HLG ? "k_hlg_linearize" : tf.kind == code_tf::SDR ? "k_sdr_linearize" : "k_linearize";
+}
+
+static std::string linearize_variant(const codelight_plan &p, code_tf tf)
+{
+    return std::string(linearize_kernel(tf)) + "<" + matrix_name(p.matrix) + "," +
            (!p.sub ? "444" : p.form == UP_FIR_TL ? "FIR_TL" : p.form == UP_FIR ? "FIR" : "REPLICATE") + ">";
 }
 
@@ -1391,8 +1396,9 @@ static linearize_frame linearize_entry(const codelight_plan &p, const uint16_t *
     return linearize_frame{{c.p[0], c.p[1], c.p[2]}, {static_cast<float *>(out[0]), static_cast<float *>(out[1]), static_cast<float *>(out[2])}};
 }
 
-/* both batch entries: the codes are PQ's (hlg_peak null: k_linearize) or HLG's at *hlg_peak cd/m2 (k_hlg_linearize) */
-static int linearize_frames(h2y_ctx *ctx, const h2y_codelight_desc *d, const int *hlg_peak, int n_frames, const uint16_t *const *d_frames,
+/* the three batch entries: the codes are PQ's (k_linearize), HLG's at a display peak (k_hlg_linearize) or SDR's at a reference
+ * white (k_sdr_linearize) */
+static int linearize_frames(h2y_ctx *ctx, const h2y_codelight_desc *d, code_tf tf, int n_frames, const uint16_t *const *d_frames,
                             void *const *d_planes_out)
 {
     if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
@@ -1414,35 +1420,44 @@ static int linearize_frames(h2y_ctx *ctx, const h2y_codelight_desc *d, const int
     const int per_launch = std::min(n_frames, H2Y_LINEARIZE_FRAMES_PER_LAUNCH);
     linearize_frame *h;
     hlgsrc_args ha{};
-    rc = hlg_peak ? hlgsrc_args_of(ctx, p, *hlg_peak, ha) : codelight_tables(ctx, p);
+    sdrsrc_args sa{};
+    rc = tf.kind == code_tf::HLG ? hlgsrc_args_of(ctx, p, tf.param, ha) : tf.kind == code_tf::SDR ? sdrsrc_tables(ctx, p, tf.param, sa.kappa) : codelight_tables(ctx, p);
+    sa.c = p.a;
     if (!rc) rc = frame_table(ctx, n_frames, h);
     if (!rc && p.sub) rc = ensure(ctx, ctx->d_codelight_up, ctx->codelight_up_cap, (size_t)per_launch * 2u * p.plane_al);
     if (rc) return rc;
     /* frame f's upsampled chroma lies in the scratch of its place in its launch; the launches follow one another on one stream */
     for (int f = 0; f < n_frames; f++)
         h[f] = linearize_entry(p, d_frames[f], p.sub ? ctx->d_codelight_up + (size_t)(f % per_launch) * 2u * p.plane_al : nullptr, d_planes_out + 3 * f);
-    rc = timed_launches(ctx, h, n_frames, H2Y_LINEARIZE_FRAMES_PER_LAUNCH, hlg_peak ? "k_hlg_linearize" : "k_linearize", [&](const linearize_frame *frames, int f0, int nf) {
+    rc = timed_launches(ctx, h, n_frames, H2Y_LINEARIZE_FRAMES_PER_LAUNCH, linearize_kernel(tf), [&](const linearize_frame *frames, int f0, int nf) {
         for (int f = 0; p.sub && f < nf; f++) {
             const hipError_t e = codelight_upsample(ctx, p, d_frames[f0 + f], ctx->d_codelight_up + (size_t)f * 2u * p.plane_al);
             if (e != hipSuccess) return e;
         }
-        if (hlg_peak) return h2y_launch_hlg_linearize(p.matrix, h2y_hlg_linearize_grid(ctx->n_cu, p.a.npix, nf), ctx->stream, ha, frames, nf);
+        if (tf.kind == code_tf::HLG) return h2y_launch_hlg_linearize(p.matrix, h2y_hlg_linearize_grid(ctx->n_cu, p.a.npix, nf), ctx->stream, ha, frames, nf);
+        if (tf.kind == code_tf::SDR) return h2y_launch_sdr_linearize(p.matrix, h2y_sdr_linearize_grid(p.a.npix, nf), ctx->stream, sa, frames, nf);
         return h2y_launch_linearize(p.matrix, h2y_linearize_grid(p.a.npix, nf), ctx->stream, p.a, frames, nf);
     });
     if (rc) return rc;
-    ctx->last_variant = linearize_variant(p, hlg_peak != nullptr);
+    ctx->last_variant = linearize_variant(p, tf);
     return H2Y_OK;
 }
 
 int h2y_linearize_batch(h2y_ctx *ctx, const h2y_codelight_desc *d, int n_frames, const uint16_t *const *d_frames, void *const *d_planes_out)
 {
-    return linearize_frames(ctx, d, nullptr, n_frames, d_frames, d_planes_out);
+    return linearize_frames(ctx, d, code_tf{}, n_frames, d_frames, d_planes_out);
 }
 
 int h2y_hlg_linearize_batch(h2y_ctx *ctx, const h2y_codelight_desc *d, int peak, int n_frames, const uint16_t *const *d_frames,
                             void *const *d_planes_out)
 {
-    return linearize_frames(ctx, d, &peak, n_frames, d_frames, d_planes_out);
+    return linearize_frames(ctx, d, code_tf{code_tf::HLG, peak}, n_frames, d_frames, d_planes_out);
+}
+
+int h2y_sdr_linearize_batch(h2y_ctx *ctx, const h2y_codelight_desc *d, int white, int n_frames, const uint16_t *const *d_frames,
+                            void *const *d_planes_out)
+{
+    return linearize_frames(ctx, d, code_tf{code_tf::SDR, white}, n_frames, d_frames, d_planes_out);
 }
 
 /* The forward ring's PQCODE decode.  One scratch of the context serves every slot: the frames follow one another on its stream. */
@@ -1464,6 +1479,7 @@ int pqcode_decode(h2y_ctx *ctx, int slot)
         HIP_TRY(ctx, codelight_upsample(ctx, p, reinterpret_cast<const uint16_t *>(ctx->ss[slot].d_in + ctx->s_pay_off), ctx->d_codelight_up));
     const linearize_frame *fr = static_cast<const linearize_frame *>(ctx->s_tab) + slot;
     if (ctx->s_src.hlg) HIP_TRY(ctx, h2y_launch_hlg_linearize(p.matrix, h2y_hlg_linearize_grid(ctx->n_cu, p.a.npix, 1), ctx->stream, ctx->s_src.hlgsrc, fr, 1));
+    else if (ctx->s_src.sdr) HIP_TRY(ctx, h2y_launch_sdr_linearize(p.matrix, h2y_sdr_linearize_grid(p.a.npix, 1), ctx->stream, sdrsrc_args{p.a, ctx->s_src.sdr_kappa}, fr, 1));
     else HIP_TRY(ctx, h2y_launch_linearize(p.matrix, h2y_linearize_grid(p.a.npix, 1), ctx->stream, p.a, fr, 1));
     return H2Y_OK;
 }
@@ -3041,6 +3057,44 @@ int hlgsrc_args_of(h2y_ctx *ctx, const codelight_plan &p, int peak, hlgsrc_args 
     a.c = p.a;
     a.ootf = ctx->d_hlgsrc_tables;
     a.inv = ctx->d_hlgsrc_tables + H2Y_LIGHTDIST_BINS;
+    return H2Y_OK;
+}
+
+/* ---- light of SDR code planes (--linearize 1 --src_sdr 1): include/hdr2yuv_hip.h states the definition ------------------------------ */
+
+static bool sdr_white_ok(int white) { return white >= H2Y_SDR_WHITE_MIN && white <= H2Y_SDR_WHITE_MAX; }
+
+int h2y_sdr_inverse_planes(int white, size_t npix, const float *const src[3], float *const dst[3])
+{
+    if (!src || !dst || !src[0] || !src[1] || !src[2] || !dst[0] || !dst[1] || !dst[2]) return fail(nullptr, H2Y_EINVAL, "null planes");
+    if (!sdr_white_ok(white)) return fail(nullptr, H2Y_EINVAL, "SDR source: white(%d) outside %d <= white <= %d cd/m2", white, H2Y_SDR_WHITE_MIN, H2Y_SDR_WHITE_MAX);
+    const float kappa = (float)(white / 10000.0);
+    for (int c = 0; c < 3; c++)
+        for (size_t i = 0; i < npix; i++) {
+            const float v = src[c][i], vc = v > 0.0f ? (v < 1.0f ? v : 1.0f) : 0.0f; /* step 4s */
+            dst[c][i] = tf_to_linear(H2Y_TF_BT1886, vc) * kappa; /* steps 5s (the careful tier's function), 6s: one product, one rounding */
+        }
+    return H2Y_OK;
+}
+
+/* bt1886_f's tables into the plan: what light1<true> reads of pix_params (codelight_tables with the BT.1886 stage) */
+int sdrsrc_tables(h2y_ctx *ctx, codelight_plan &p, int white, float &kappa)
+{
+    if (p.matrix == H2Y_MATRIX_ICTCP)
+        return fail(ctx, H2Y_EUNSUPPORTED, "matrix_coeffs 14 (ICtCp) is PQ's here: an SDR source is G,B,R (0), BT.709 (1) or BT.2020nc (9)");
+    if (!sdr_white_ok(white)) return fail(ctx, H2Y_EINVAL, "SDR source: white(%d) outside %d <= white <= %d cd/m2", white, H2Y_SDR_WHITE_MIN, H2Y_SDR_WHITE_MAX);
+    const int rc = ensure_tfn(ctx, H2Y_TFN_G24);
+    if (rc) return rc;
+    pix_params &pp = p.a.pp;
+    pp = pix_params{};
+    pp.convert_transfer = 2;
+    pp.src_tf = H2Y_TF_BT1886;
+    pp.src_fn = H2Y_TFN_G24;
+    pp.norm_identity = 1; /* the kernel normalises the codes itself */
+    for (int c = 0; c < 3; c++) pp.range[c] = 1.0f;
+    pp.tf_ext[0] = ctx->d_tfn_ext[H2Y_TFN_G24];
+    p.a.table = ctx->d_tfn[H2Y_TFN_G24];
+    kappa = (float)(white / 10000.0);
     return H2Y_OK;
 }
 

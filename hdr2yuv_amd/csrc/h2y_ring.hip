@@ -268,8 +268,8 @@ int h2y_exr_stream_open(h2y_ctx *ctx, const h2y_desc *d, const h2y_exr_info *inf
     return open_forward_ring(ctx, d, &src, depth);
 }
 
-/* the two code rings: the codes are PQ's (hlg_peak null) or HLG's at *hlg_peak cd/m2 */
-static int open_code_ring(h2y_ctx *ctx, const h2y_desc *d, const h2y_codelight_desc *code, const int *hlg_peak, int depth)
+/* the three code rings: the codes are PQ's, HLG's at a display peak or SDR's at a reference white */
+static int open_code_ring(h2y_ctx *ctx, const h2y_desc *d, const h2y_codelight_desc *code, code_tf tf, int depth)
 {
     int rc = ring_may_open(ctx);
     if (rc) return rc;
@@ -279,21 +279,27 @@ static int open_code_ring(h2y_ctx *ctx, const h2y_desc *d, const h2y_codelight_d
     if (!d) return fail(ctx, H2Y_EINVAL, "null h2y_desc");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hlgsrc_args ha{};
-    rc = hlg_peak ? hlgsrc_args_of(ctx, p, *hlg_peak, ha) : codelight_tables(ctx, p);
+    float kappa = 0.0f;
+    rc = tf.kind == code_tf::HLG ? hlgsrc_args_of(ctx, p, tf.param, ha) : tf.kind == code_tf::SDR ? sdrsrc_tables(ctx, p, tf.param, kappa) : codelight_tables(ctx, p);
     if (!rc) rc = pqcode_scratch(ctx, p);
     if (rc) return rc;
-    const decode_src src = hlg_peak ? decode_src(p, ha) : decode_src(p);
+    const decode_src src = tf.kind == code_tf::HLG ? decode_src(p, ha) : tf.kind == code_tf::SDR ? decode_src(p, kappa) : decode_src(p);
     return open_forward_ring(ctx, d, &src, depth);
 }
 
 int h2y_pqcode_stream_open(h2y_ctx *ctx, const h2y_desc *d, const h2y_codelight_desc *code, int depth)
 {
-    return open_code_ring(ctx, d, code, nullptr, depth);
+    return open_code_ring(ctx, d, code, code_tf{}, depth);
 }
 
 int h2y_hlgcode_stream_open(h2y_ctx *ctx, const h2y_desc *d, const h2y_codelight_desc *code, int peak, int depth)
 {
-    return open_code_ring(ctx, d, code, &peak, depth);
+    return open_code_ring(ctx, d, code, code_tf{code_tf::HLG, peak}, depth);
+}
+
+int h2y_sdrcode_stream_open(h2y_ctx *ctx, const h2y_desc *d, const h2y_codelight_desc *code, int white, int depth)
+{
+    return open_code_ring(ctx, d, code, code_tf{code_tf::SDR, white}, depth);
 }
 
 /* ---- the ring's frame by frame entries ------------------------------------------------------------------------------------------ */

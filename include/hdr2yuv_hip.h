@@ -1462,6 +1462,54 @@ int h2y_stream_ictcp(h2y_ctx *ctx);
  *       v > 0 ? min(v, 1) : +0.
  *   From there nothing is new: the figures of k_codelight, the planes of k_linearize, the two sides of k_deltae. */
 
+/* ---- light of SDR code planes: a finished SDR master (BT.1886) as a LINEAR G,B,R F32 source of the forward flow (--linearize 1
+ * --src_sdr 1) ---------------------------------------------------------------------------------------------------------------------
+ * Rep. ITU-R BT.2408's display-referred "direct mapping": an SDR picture placed in absolute light with its reference white at W
+ * cd/m2, ready for a PQ or HLG container.  The project's own definition of the flow: the reference has none that leaves the
+ * source's transfer for absolute light.  The transfer step, though, is the reference's own function, bt1886_f (convert.cpp:67-75).
+ * Frame: exactly what h2y_codelight_desc describes ("light of PQ code planes" above): three u16 code planes at bit_depth 8..16,
+ *   video or full range; matrix_coeffs 0, 1 or 9; chroma_format_idc 3, or 1 with even sizes (not with matrix 0); `algorithm` and the
+ *   context's inverse chroma siting select the upsampler.  matrix_coeffs 14 is H2Y_EUNSUPPORTED.  The transfer is BT.1886, always.
+ * Parameter: an integer reference white W in cd/m2, H2Y_SDR_WHITE_MIN <= W <= H2Y_SDR_WHITE_MAX; H2Y_SDR_WHITE_DEFAULT (203, BT.2408)
+ *   where a caller has none; W = 100 is BT.1886's nominal display.  kappa = W / 10000, computed in binary64 and rounded once to
+ *   binary32.
+ * Steps 1-3 are steps 1-3 of "light of PQ code planes", word for word: k_up444 for 4:2:0; the normalisation, one subtraction and one
+ *   IEEE division; the matrix, every product and sum rounded by itself (the file is built -ffp-contract=off).  Then per sample:
+ *   4s. for each of G', B', R': v' = v > 0 ? min(v, 1) : +0.0.  A NaN cannot arise from codes.  Super-whites (10-bit Y 941..1019)
+ *       are clipped at white: that is part of the definition, as it is for HLG.
+ *   5s. E_c = tf_to_linear(BT.1886 class, v'): the binary32 of pow((double)v', (double)2.4f), which is bt1886_f with a = 1 and b = 0.
+ *       The exponent is the reference's promoted float, 2.4000000953674316, not 2.4.  It is evaluated by the conversion's own
+ *       tiers -- the function's table (H2Y_TFN_G24), its full-range table, the careful tier -- and is therefore the very float the
+ *       forward conversion produces for a src_transfer 1 G,B,R sample of value v'.
+ *   6s. L_c = E_c x kappa, one rounding.  The results lie in [+0, kappa] and are never -0; 1.0 = 10000 cd/m2; the planes are G, B,
+ *       R: what k_linearize leaves for a PQ master, so everything behind it -- k_gamut (BT.709 primaries to BT.2020), k_tonemap,
+ *       k_hlg, k_ictcp, k_light, the forward kernels, with floor 0 and ceiling 1 by stats_override -- is untouched.
+ * Anchors (10-bit video range, Cb = Cr = 512, W = 203): Y 64 -> 0; Y 502 (v' = 0.5) -> 38.4613 cd/m2; Y 721 -> 101.7755 cd/m2;
+ *   Y 940 and 1019 -> 203.0000 cd/m2.  With W = 100, Y 502 -> 18.9465 cd/m2.
+ * Accuracy: wherever L_c is a normal number it stays within 2^-22 relative of (W / 10000) x v'^((double)2.4f) in binary64 on the
+ *   binary32 v': three roundings of 2^-24 each, E_c, kappa and the product (tests/test_sdr_source_host.py holds it). */
+#define H2Y_SDR_WHITE_MIN 80
+#define H2Y_SDR_WHITE_MAX 1000
+#define H2Y_SDR_WHITE_DEFAULT 203
+
+/* Steps 4s-6s on planes in host memory: the host twin of k_sdr_linearize, step 5s through the careful tier's function
+ * (csrc/h2y_math.h), which compiles on the host.  Host only: no device, no context.  src[c] / dst[c]: plane c = G', B', R' in, G, B,
+ * R out, npix binary32 samples each; the primes may be clamped or not; a dst plane may be its src plane.  H2Y_EINVAL for null planes
+ * and a white out of range. */
+int h2y_sdr_inverse_planes(int white, size_t npix, const float *const src[3], float *const dst[3]);
+
+/* h2y_linearize_batch for SDR codes with the reference white at `white` cd/m2: the layout, the scratch, the launches of up to
+ * H2Y_LINEARIZE_FRAMES_PER_LAUNCH frames (k_up444 per 4:2:0 frame, then one k_sdr_linearize) and the refusals are that entry's; a
+ * white outside 80..1000 is H2Y_EINVAL, matrix_coeffs 14 H2Y_EUNSUPPORTED.  h2y_last_kernel_name "k_sdr_linearize"; the variant
+ * names the matrix and the upsampling form, e.g. "k_sdr_linearize<BT709,FIR>" (444, FIR, FIR_TL, REPLICATE). */
+int h2y_sdr_linearize_batch(h2y_ctx *ctx, const h2y_codelight_desc *d, int white, int n_frames, const uint16_t *const *d_frames,
+                            void *const *d_planes_out);
+
+/* h2y_pqcode_stream_open with this decode: a forward ring on SDR code frames of src, which the device takes through k_up444 (4:2:0)
+ * and k_sdr_linearize at `white` into the slot's three planes.  Every arming entry behaves as on the PQ code ring.  Refusals as
+ * h2y_pqcode_stream_open, H2Y_EINVAL for a white outside 80..1000 and H2Y_EUNSUPPORTED for matrix_coeffs 14. */
+int h2y_sdrcode_stream_open(h2y_ctx *ctx, const h2y_desc *d, const h2y_codelight_desc *src, int white, int depth);
+
 /* ---- chroma siting: 4:2:0 chroma co-sited with the top-left luma sample (chroma_sample_loc_type 2; HDR10, UHD Blu-ray) -----------
  * The reference carries chroma_sample_loc_type through pic_t and prints it (hdr2yuv.cpp:490, :505); it parses no flag for it and
  * never acts on it.  Its two resamplers site the chroma as they happen to: the 2x2 box in the centre of the block both ways (loc
@@ -1538,7 +1586,7 @@ int h2y_upsample_444_sited(h2y_ctx *ctx, int width, int height, int chroma_sampl
                            const uint16_t *d_src, uint16_t *d_dst);
 
 /* Timing of the last h2y_convert_batch*() (or h2y_inverse_*, h2y_dpx_decode_batch, h2y_tiff_decode_batch,
- * h2y_rgb_interleave_batch, h2y_exr_decode_batch, h2y_compare_batch, h2y_ssim_batch, h2y_light_batch, h2y_lightdist_batch, h2y_codelight_batch, h2y_scenesig_batch, h2y_codescenesig_batch, h2y_linearize_batch, h2y_hlg_linearize_batch, h2y_scale_batch, h2y_gamut_batch, h2y_tonemap_batch, h2y_hlg_batch, h2y_ictcp_batch, h2y_dither_batch) call measured with HIP events on
+ * h2y_rgb_interleave_batch, h2y_exr_decode_batch, h2y_compare_batch, h2y_ssim_batch, h2y_light_batch, h2y_lightdist_batch, h2y_codelight_batch, h2y_scenesig_batch, h2y_codescenesig_batch, h2y_linearize_batch, h2y_hlg_linearize_batch, h2y_sdr_linearize_batch, h2y_scale_batch, h2y_gamut_batch, h2y_tonemap_batch, h2y_hlg_batch, h2y_ictcp_batch, h2y_dither_batch) call measured with HIP events on
  * the stream the kernels ran on: total ms over the main kernels and how many
  * launches that covered. */
 int h2y_last_kernel_ms(const h2y_ctx *ctx, float *ms, int *launches);
@@ -1546,7 +1594,7 @@ int h2y_last_kernel_ms(const h2y_ctx *ctx, float *ms, int *launches);
 /* Name of the kernel those launches ran ("k_fused", "k_fused_t1", "k_fused_lut16",
  * "k_fused_narrow"; of the inverse entries "k_inverse", "k_inverse420", "k_inverse_batch", "k_inverse420_batch"; of
  * h2y_dpx_decode_batch "k_dpx_decode"; of h2y_tiff_decode_batch "k_tiff_decode", of h2y_rgb_interleave_batch
- * "k_rgb_interleave"; of h2y_exr_decode_batch "k_exr_decode"; of h2y_compare_batch "k_compare"; of h2y_scale_batch "k_scale"; of h2y_dither_batch "k_dither"; of h2y_gamut_batch "k_gamut"; of h2y_tonemap_batch "k_tonemap"; of h2y_hlg_batch "k_hlg"; of h2y_ictcp_batch "k_ictcp"; of h2y_codelight_batch "k_codelight"; of h2y_scenesig_batch "k_scenesig"; of h2y_codescenesig_batch "k_codescenesig"; of h2y_linearize_batch "k_linearize"; of h2y_hlg_linearize_batch "k_hlg_linearize"): the name to
+ * "k_rgb_interleave"; of h2y_exr_decode_batch "k_exr_decode"; of h2y_compare_batch "k_compare"; of h2y_scale_batch "k_scale"; of h2y_dither_batch "k_dither"; of h2y_gamut_batch "k_gamut"; of h2y_tonemap_batch "k_tonemap"; of h2y_hlg_batch "k_hlg"; of h2y_ictcp_batch "k_ictcp"; of h2y_codelight_batch "k_codelight"; of h2y_scenesig_batch "k_scenesig"; of h2y_codescenesig_batch "k_codescenesig"; of h2y_linearize_batch "k_linearize"; of h2y_hlg_linearize_batch "k_hlg_linearize"; of h2y_sdr_linearize_batch "k_sdr_linearize"): the name to
  * look for in a rocprofv3 kernel trace. */
 const char *h2y_last_kernel_name(const h2y_ctx *ctx);
 /* The same with its template arguments and launch shape, e.g. "k_fused_t1<F32,420BOX,YCBCR,PQ_IDENT> groups=8 xcd=1";

@@ -201,6 +201,16 @@ Prints one line per figure, then one JSON line with all of them.
      (h2y_pqcode_stream_open) on the same 10-bit 4:2:0 frames of 24.9 MB, both with the 0 / 1 override, five times in turn.
 Prints one line per figure, then one JSON line with all of them.
 
+`streambench.py sdrsrc`: the light of SDR code planes (k_sdr_linearize) on 4K frames, beside its yardsticks in the same job:
+  1. h2y_sdr_linearize_batch (203 cd/m2), h2y_linearize_batch and h2y_hlg_linearize_batch (1000 cd/m2) over the same 64 distinct device
+     frames per call (HIP events round each launch of up to 8 frames, k_up444 included), the three taken in turn five times after a
+     warm-up: median and spread in us per frame for 10-bit 4:2:0 BT.709 FIR noise, the same as 10-bit 4:4:4, and 16-bit 4:4:4 matrix 0;
+     the algorithmic bytes per frame as `linearize` counts them (18 B/pixel, 23 for 4:2:0) over that time as a share of the 8 TB/s HBM
+     peak; and k_sdr_linearize's time over k_linearize's;
+  2. frames/s from host memory to PQ BT.2020nc 10-bit 4:2:0 of the SDR code ring (h2y_sdrcode_stream_open) beside the PQ code ring
+     (h2y_pqcode_stream_open) on the same 10-bit 4:2:0 frames of 24.9 MB, both with the 0 / 1 override, five times in turn.
+Prints one line per figure, then one JSON line with all of them.
+
 `streambench.py dither`: the reduction to the output bit depth (k_dither) on 4K frames, beside its yardsticks in the same job:
   1. the kernel time of h2y_dither_batch over 64 distinct device frames per call (HIP events, median of five after a warm-up call,
      out of place): 16 -> 10 4:2:0 ordered, 16 -> 10 4:2:0 noise, 16 -> 8 4:2:0 ordered and 16 -> 10 4:4:4 ordered; the 4 bytes a
@@ -1749,6 +1759,103 @@ def hlgsrc_main():
     print(json.dumps({"streambench_hlgsrc": res}), flush=True)
 
 
+def sdrsrc_main():
+    import json
+
+    import torch
+
+    w, hh, nb, reps = 3840, 2160, 64, 5
+    n = w * hh
+    nf = int(os.environ.get("N", "60"))
+    depth = 3
+    white, peak = h.SDR_WHITE_DEFAULT, 1000
+    ctx = h.Context(0)
+    res = {"width": w, "height": hh, "frames_per_call": nb, "frames_per_launch": h.api.LINEARIZE_FRAMES_PER_LAUNCH, "reps": reps,
+           "ring_frames": nf, "ring_depth": depth, "white": white, "hlg_peak": peak, "hbm_peak_tbs": 8.0}
+
+    def codes(count, lo, hi):
+        return torch.randint(lo, hi + 1, (count,), dtype=torch.int32, device="cuda").to(torch.int16)
+
+    def noise(chroma, bits):
+        s = 1 << (bits - 8)
+        nc = n // 4 if chroma == 1 else n
+        return torch.cat([codes(n, 16 * s, 235 * s), codes(nc, 16 * s, 240 * s), codes(nc, 16 * s, 240 * s)])
+
+    def report(key, label, t, nbytes, variant):
+        med = float(np.median(t))
+        tbs = nbytes / (med * 1e-3) / 1e12
+        res[key] = dict(kernel_us_per_frame=round(med * 1e3, 2), min_us=round(min(t) * 1e3, 2), max_us=round(max(t) * 1e3, 2),
+                        bytes_per_frame=nbytes, kernel_tbs=round(tbs, 2), hbm_peak_fraction=round(tbs / 8.0, 3), variant=variant)
+        print(f"{label:38s} {nb} frames per call: {med*1e3:7.2f} us/frame ({min(t)*1e3:.2f}..{max(t)*1e3:.2f})  {tbs:5.2f} TB/s = "
+              f"{tbs/8.0*100:4.1f} % of 8 TB/s  {variant}", flush=True)
+        return med
+
+    # 1. k_sdr_linearize, k_linearize and k_hlg_linearize on the same frames, in turn
+    outs = [[torch.empty(n, dtype=torch.float32, device="cuda") for _ in range(3)] for _ in range(nb)]
+    for name, chroma, bits, matrix in (("420_10_noise", 1, 10, h.MATRIX_BT709), ("444_10_noise", 3, 10, h.MATRIX_BT709),
+                                       ("444_16_gbr_noise", 3, 16, h.MATRIX_GBR)):
+        d = h.make_codelight_desc(w, hh, chroma, bits, 0, matrix, 1)
+        frames = [noise(chroma, bits) for _ in range(nb)]
+        torch.cuda.synchronize()
+        t = {"sdrsrc": [], "lin": [], "hlgsrc": []}
+        variants = {}
+        for rep in range(reps + 1):  # the first round warms up
+            for key, call in (("sdrsrc", lambda: ctx.sdr_linearize_batch(d, white, frames, outs)), ("lin", lambda: ctx.linearize_batch(d, frames, outs)),
+                              ("hlgsrc", lambda: ctx.hlg_linearize_batch(d, peak, frames, outs))):
+                call()
+                variants[key] = ctx.last_kernel_variant()
+                if rep:
+                    t[key].append(ctx.last_kernel_ms()[0] / nb)
+        nbytes = n * (23 if chroma == 1 else 18)
+        m_src = report(f"k_sdr_linearize_{name}", f"k_sdr_linearize {name}", t["sdrsrc"], nbytes, variants["sdrsrc"])
+        m_lin = report(f"k_linearize_{name}", f"k_linearize {name} (yardstick)", t["lin"], nbytes, variants["lin"])
+        report(f"k_hlg_linearize_{name}", f"k_hlg_linearize {name} (yardstick)", t["hlgsrc"], nbytes, variants["hlgsrc"])
+        res[f"k_sdr_linearize_over_k_linearize_{name}"] = round(m_src / m_lin, 3)
+        print(f"k_sdr_linearize / k_linearize {name}: {m_src/m_lin:5.3f}", flush=True)
+        del frames
+        torch.cuda.empty_cache()
+
+    # 2. the SDR code ring beside the PQ code ring on the same code frames
+    cd = h.make_codelight_desc(w, hh, 1, 10, 0, h.MATRIX_BT709, 1)
+    payload = noise(1, 10).cpu().numpy().view(np.uint8)
+    del outs
+    torch.cuda.empty_cache()
+    d32 = h.make_desc(w, hh, dst_depth=10, dst_matrix=h.MATRIX_BT2020NC, resampler=1, stats=[(0, 1)] * 3)
+
+    def ring(open_fn):
+        open_fn()
+        inflight = 0
+        t0 = time.perf_counter()
+        for _ in range(nf):
+            ctx.stream_input()[0][:] = payload
+            ctx.stream_submit()
+            inflight += 1
+            if inflight == depth - 1:
+                ctx.stream_output()
+                inflight -= 1
+        while inflight:
+            ctx.stream_output()
+            inflight -= 1
+        dt = (time.perf_counter() - t0) / nf
+        ctx.stream_close()
+        return dt
+
+    rings = (("sdrcode", lambda: ctx.sdrcode_stream_open(d32, cd, white, depth)), ("pqcode", lambda: ctx.pqcode_stream_open(d32, cd, depth)))
+    fps = {key: [] for key, _ in rings}
+    for rep in range(reps + 1):  # the first round warms up
+        for key, open_fn in rings:
+            dt = ring(open_fn)
+            if rep:
+                fps[key].append(1 / dt)
+    for key, _ in rings:
+        res[f"{key}_ring"] = dict(fps=round(float(np.median(fps[key])), 1), min_fps=round(min(fps[key]), 1), max_fps=round(max(fps[key]), 1),
+                                  upload_bytes_per_frame=3 * n)
+        print(f"{key:7s} ring from host memory to PQ BT.2020nc 10-bit 4:2:0: {np.median(fps[key]):6.1f} frames/s "
+              f"({min(fps[key]):.1f}..{max(fps[key]):.1f}), {3*n/1e6:5.1f} MB up per frame", flush=True)
+    ctx.close()
+    print(json.dumps({"streambench_sdrsrc": res}), flush=True)
+
+
 def scale_main():
     import json
 
@@ -2627,6 +2734,8 @@ if __name__ == "__main__":
         ictcp_main()
     elif sys.argv[1:] == ["hlgsrc"]:
         hlgsrc_main()
+    elif sys.argv[1:] == ["sdrsrc"]:
+        sdrsrc_main()
     elif sys.argv[1:] == ["scale"]:
         scale_main()
     elif sys.argv[1:] == ["dither"]:
