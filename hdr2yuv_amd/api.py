@@ -46,6 +46,7 @@ EXPORTS = [
     "h2y_deltae_batch", "h2y_stream_deltae", "h2y_stream_deltae_result",
     "h2y_scale_taps", "h2y_scale_frame_bytes", "h2y_scale_batch", "h2y_stream_scale", "h2y_scale_stream_open",
     "h2y_dither_offsets", "h2y_dither_batch", "h2y_stream_dither", "h2y_dither_stream_open",
+    "h2y_pack_frame_bytes", "h2y_pack_frame", "h2y_unpack_frame", "h2y_pack_batch", "h2y_unpack_batch", "h2y_stream_pack", "h2y_stream_unpack", "h2y_stream_unpack_ex",
     "h2y_gamut_matrix", "h2y_gamut_batch", "h2y_stream_gamut",
     "h2y_tonemap_curve", "h2y_tonemap_batch", "h2y_stream_tonemap",
     "h2y_lut3d_parse", "h2y_lut3d_free", "h2y_lut3d_info", "h2y_lut3d_nodes", "h2y_lut3d_planes", "h2y_lut3d_batch", "h2y_stream_lut3d",
@@ -82,6 +83,8 @@ SDR_WHITE_MIN, SDR_WHITE_MAX, SDR_WHITE_DEFAULT = 80, 1000, 203  # the reference
 ICTCP_FRAMES_PER_LAUNCH = 64
 SCALE_TAPS = 32  # coefficients per row of scale_taps' table
 DITHER_FRAMES_PER_LAUNCH = 64
+PACK_PLANAR16, PACK_PLANAR8, PACK_NV12, PACK_P010 = 0, 1, 2, 3  # the sample packings (include/hdr2yuv_hip.h)
+PACK_FRAMES_PER_LAUNCH = 64
 DITHER_CUT, DITHER_ORDERED, DITHER_NOISE = 0, 1, 2
 
 
@@ -560,6 +563,21 @@ def load_library():
     L.h2y_stream_dither.restype = C.c_int
     L.h2y_dither_stream_open.argtypes = [C.c_void_p] + [C.c_int] * 9 + [C.c_uint32] * 2 + [C.c_int]
     L.h2y_dither_stream_open.restype = C.c_int
+    L.h2y_pack_frame_bytes.argtypes = [C.c_int] * 4
+    L.h2y_pack_frame_bytes.restype = C.c_size_t
+    L.h2y_pack_frame.argtypes = [C.c_int] * 5 + [C.c_void_p, C.c_void_p]
+    L.h2y_pack_frame.restype = C.c_int
+    L.h2y_unpack_frame.argtypes = [C.c_int] * 5 + [C.c_void_p, C.c_void_p]
+    L.h2y_unpack_frame.restype = C.c_int
+    for fn in (L.h2y_pack_batch, L.h2y_unpack_batch):
+        fn.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+        fn.restype = C.c_int
+    L.h2y_stream_pack.argtypes = [C.c_void_p, C.c_int]
+    L.h2y_stream_pack.restype = C.c_int
+    L.h2y_stream_unpack.argtypes = [C.c_void_p, C.c_int]
+    L.h2y_stream_unpack.restype = C.c_int
+    L.h2y_stream_unpack_ex.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.h2y_stream_unpack_ex.restype = C.c_int
     L.h2y_gamut_matrix.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_char_p)]
     L.h2y_gamut_matrix.restype = C.c_int
     L.h2y_gamut_batch.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
@@ -757,6 +775,42 @@ def dither_offsets(mode: int, shift: int, temporal: int, seed: int, frame: int, 
     if rc != H2Y_OK:
         raise H2YError(rc, (lib.h2y_last_error(None) or b"").decode())
     return t
+
+
+def pack_frame_bytes(width: int, height: int, chroma: int, packing: int) -> int:
+    """h2y_pack_frame_bytes: the bytes of one packed frame; 0 for packing 0 and every combination the packing does not take."""
+    return int(load_library().h2y_pack_frame_bytes(width, height, chroma, packing))
+
+
+def _frame_samples(width, height, chroma):
+    return width * height + 2 * ((width >> 1) * (height >> 1) if chroma == CHROMA_420 else width * height)
+
+
+def pack_frame(width: int, height: int, chroma: int, bit_depth: int, packing: int, frame):
+    """h2y_pack_frame (host only, no device): the packed bytes (uint8) of one frame of three u16 planes, one after the other."""
+    lib = load_library()
+    src = np.ascontiguousarray(frame, dtype=np.uint16).reshape(-1)
+    if src.size != _frame_samples(width, height, chroma):
+        raise ValueError("the frame does not hold width x height samples and its two chroma planes")
+    dst = np.zeros(max(pack_frame_bytes(width, height, chroma, packing), 1), dtype=np.uint8)
+    rc = lib.h2y_pack_frame(width, height, chroma, bit_depth, packing, src.ctypes.data, dst.ctypes.data)
+    if rc != H2Y_OK:
+        raise H2YError(rc, (lib.h2y_last_error(None) or b"").decode())
+    return dst[:pack_frame_bytes(width, height, chroma, packing)]
+
+
+def unpack_frame(width: int, height: int, chroma: int, bit_depth: int, packing: int, packed):
+    """h2y_unpack_frame (host only, no device): the three u16 planes, one after the other, of one packed frame (bytes)."""
+    lib = load_library()
+    src = np.ascontiguousarray(np.frombuffer(packed, dtype=np.uint8) if isinstance(packed, (bytes, bytearray)) else packed).view(np.uint8).reshape(-1)
+    need = pack_frame_bytes(width, height, chroma, packing)
+    if need and src.size != need:
+        raise ValueError("the packed frame does not hold h2y_pack_frame_bytes bytes")
+    dst = np.zeros(max(_frame_samples(width, height, chroma), 1), dtype=np.uint16)
+    rc = lib.h2y_unpack_frame(width, height, chroma, bit_depth, packing, src.ctypes.data if src.size else None, dst.ctypes.data)
+    if rc != H2Y_OK:
+        raise H2YError(rc, (lib.h2y_last_error(None) or b"").decode())
+    return dst[:_frame_samples(width, height, chroma)]
 
 
 def lightdist_json(stats, first_frame_index: int = 0) -> str:
@@ -1302,6 +1356,7 @@ class Context:
         self._stream_dpx = None
         self._stream_rgb = False
         self._stream_cmp_planes = (d.width * d.height, nc, nc)
+        self._stream_in_geom = (d.width, d.height, d.chroma_format_idc)
 
     def deltae_batch(self, d: H2YCodelightDesc, frames_a, frames_b, threshold=1.0):
         """k_deltae on device frame pairs of PQ codes (as codelight_batch takes each frame): a list of H2YDeltaeStats, one per
@@ -1370,8 +1425,10 @@ class Context:
             self._check(self.lib.h2y_hlgcode_stream_open(self.h, C.byref(d), C.byref(src), int(hlg_peak), depth))
         nc = (src.width >> 1) * (src.height >> 1) if src.chroma_format_idc == CHROMA_420 else src.width * src.height
         self._stream_desc = d
+        self._stream_out_geom = (d.width, d.height, d.dst_chroma_format_idc)
         self._stream_inverse = None
         self._stream_dpx = 2 * (src.width * src.height + 2 * nc)
+        self._stream_in_geom = (src.width, src.height, src.chroma_format_idc)
         self._stream_rgb = False
 
     def hlgcode_stream_open(self, d, src: H2YCodelightDesc, peak: int, depth=3) -> None:
@@ -1405,6 +1462,25 @@ class Context:
         pd = (C.c_void_p * max(n, 1))(*[self._ptr(x) for x in frames_dst])
         self._check(self.lib.h2y_dither_batch(self.h, width, height, chroma, src_depth, dst_depth, full_range, gbr, mode, temporal,
                                               seed & 0xFFFFFFFF, first_frame & 0xFFFFFFFF, n, ps, pd))
+
+    def pack_batch(self, width, height, chroma, bit_depth, packing, frames_src, frames_dst) -> None:
+        """k_pack on device frames (tensors or pointers from 16-byte aligned bases): frames_dst[f] receives frames_src[f], three
+        u16 planes one after the other, packed (PACK_PLANAR8, PACK_NV12 or PACK_P010).  No overlap of a frame's two sides."""
+        n = len(frames_src)
+        if len(frames_dst) != n:
+            raise ValueError("frames_src and frames_dst differ in length")
+        ps = (C.c_void_p * max(n, 1))(*[self._ptr(x) for x in frames_src])
+        pd = (C.c_void_p * max(n, 1))(*[self._ptr(x) for x in frames_dst])
+        self._check(self.lib.h2y_pack_batch(self.h, width, height, chroma, bit_depth, packing, n, ps, pd))
+
+    def unpack_batch(self, width, height, chroma, bit_depth, packing, frames_src, frames_dst) -> None:
+        """k_unpack on device frames: frames_dst[f] receives the three u16 planes of the packed frame frames_src[f]."""
+        n = len(frames_src)
+        if len(frames_dst) != n:
+            raise ValueError("frames_src and frames_dst differ in length")
+        ps = (C.c_void_p * max(n, 1))(*[self._ptr(x) for x in frames_src])
+        pd = (C.c_void_p * max(n, 1))(*[self._ptr(x) for x in frames_dst])
+        self._check(self.lib.h2y_unpack_batch(self.h, width, height, chroma, bit_depth, packing, n, ps, pd))
 
     def gamut_batch(self, width, height, sample, src_primaries, dst_primaries, clip, frames_src, frames_dst=None) -> None:
         """k_gamut on device frames (frames_src[f] = three device planes G, B, R of float or half samples, 16-byte aligned):
@@ -1523,6 +1599,7 @@ class Context:
         """Arm an open forward ring (plain, DPX, TIFF or EXR): stream_output then returns the frame scaled to dst_w x dst_h."""
         self._check(self.lib.h2y_stream_scale(self.h, dst_w, dst_h, a))
         self._stream_out_words = scale_frame_bytes(dst_w, dst_h, self._stream_desc.dst_chroma_format_idc) // 2
+        self._stream_out_geom = (dst_w, dst_h, self._stream_desc.dst_chroma_format_idc)
 
     def scale_stream_open(self, src_w, src_h, chroma, bit_depth, full_range, gbr, dst_w, dst_h, a=3, depth=3) -> None:
         """A ring that only scales: stream_input lends the frame's three planes, stream_output returns the scaled frame."""
@@ -1533,6 +1610,7 @@ class Context:
         self._stream_rgb = False
         self._stream_cmp_planes = (src_w * src_h, nc, nc)
         self._stream_out_words = scale_frame_bytes(dst_w, dst_h, chroma) // 2
+        self._stream_in_geom, self._stream_out_geom = (src_w, src_h, chroma), (dst_w, dst_h, chroma)
 
     def stream_dither(self, dst_depth, mode, temporal=0, seed=0, first_frame=0) -> None:
         """Arm an open forward ring (plain, DPX, TIFF, EXR or PQ code), after stream_scale where the ring scales: stream_output
@@ -1550,6 +1628,24 @@ class Context:
         self._stream_rgb = False
         self._stream_cmp_planes = (width * height, nc, nc)
         self._stream_out_words = width * height + 2 * nc
+        self._stream_in_geom = self._stream_out_geom = (width, height, chroma)
+
+    def stream_pack(self, packing) -> None:
+        """Arm an open forward, scale-only or dither-only ring, after stream_scale and stream_dither where the ring has them:
+        stream_output then returns the frame that would go down packed, as a uint8 view of h2y_pack_frame_bytes bytes
+        (h2y_stream_pack)."""
+        self._check(self.lib.h2y_stream_pack(self.h, packing))
+        self._stream_pack_bytes = pack_frame_bytes(*self._stream_out_geom, packing)  # (the library refused every ring without a .yuv frame)
+
+    def stream_unpack(self, packing, bit_depth=None) -> None:
+        """Arm an open inverse, planes or code ring: stream_input (and a compare-only ring's stream_reference) then lends one
+        uint8 view of a packed frame (h2y_stream_unpack; with bit_depth given h2y_stream_unpack_ex, which a compare-only ring needs
+        for PACK_P010)."""
+        if bit_depth is None:
+            self._check(self.lib.h2y_stream_unpack(self.h, packing))
+        else:
+            self._check(self.lib.h2y_stream_unpack_ex(self.h, packing, int(bit_depth)))
+        self._stream_unpack_bytes = pack_frame_bytes(*self._stream_in_geom, packing)  # (the library refused every ring without code planes)
 
     def stream_histogram(self, bits=0, bit_depth=None, full_range=None, gbr=None) -> None:
         """Arm the open ring: every frame is counted on the device (h2y_stream_histogram; with bit_depth, full_range and gbr
@@ -1578,6 +1674,7 @@ class Context:
         self._stream_dpx = None
         self._stream_rgb = False
         self._stream_cmp_planes = (width * height, nc, nc)
+        self._stream_in_geom = (width, height, chroma)
 
     def stream_compare(self, sigma, keep_output=1) -> None:
         """Arm the open ring: every frame is compared with the reference stream_reference lends for it."""
@@ -1593,6 +1690,8 @@ class Context:
         forward rings, G | B | R on the inverse rings, the three planes of a compare-only ring)."""
         p = C.c_void_p()
         self._check(self.lib.h2y_stream_reference(self.h, C.byref(p)))
+        if getattr(self, "_stream_unpack_bytes", None) and getattr(self, "_stream_cmp_planes", None):
+            return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(self._stream_unpack_bytes,))  # a compare-only ring's, packed
         return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint16)), shape=self._stream_ref_shape)
 
     def stream_compare_result(self) -> H2YCompareStats:
@@ -1664,11 +1763,13 @@ class Context:
         self._stream_dpx = None
         self._stream_rgb = False
         self._stream_cmp_planes = (width * height, nc, nc)
+        self._stream_in_geom = (width, height, chroma)
         self._stream_ref_shape = (width * height + 2 * nc,)
 
     def stream_open(self, d, depth=3) -> None:
         self._check(self.lib.h2y_stream_open(self.h, C.byref(d), depth))
         self._stream_desc = d
+        self._stream_out_geom = (d.width, d.height, d.dst_chroma_format_idc)
         self._stream_inverse = None
         self._stream_dpx = None
         self._stream_rgb = False
@@ -1678,6 +1779,7 @@ class Context:
         the decoded rows; stream_output gives the .yuv frame as on a forward stream."""
         self._check(self.lib.h2y_tiff_stream_open(self.h, C.byref(d), C.byref(info), int(clamp_video_range), depth))
         self._stream_desc = d
+        self._stream_out_geom = (d.width, d.height, d.dst_chroma_format_idc)
         self._stream_inverse = None
         self._stream_dpx = int(info.payload_bytes)
         self._stream_rgb = False
@@ -1687,6 +1789,7 @@ class Context:
         with exr_unpack; stream_output gives the .yuv frame as on a forward stream."""
         self._check(self.lib.h2y_exr_stream_open(self.h, C.byref(d), C.byref(info), depth))
         self._stream_desc = d
+        self._stream_out_geom = (d.width, d.height, d.dst_chroma_format_idc)
         self._stream_inverse = None
         self._stream_dpx = int(info.payload_bytes)
         self._stream_rgb = False
@@ -1698,6 +1801,7 @@ class Context:
         self._check(self.lib.h2y_tiff_inverse_stream_open(self.h, width, height, in_chroma, in_depth, in_full_range, in_matrix,
                                                           out_depth, algorithm, depth))
         self._stream_inverse = (width, height, in_chroma)
+        self._stream_in_geom = (width, height, in_chroma)
         self._stream_dpx = None
         self._stream_rgb = True
 
@@ -1706,6 +1810,7 @@ class Context:
         with the file's bytes from info.data_offset on; stream_output gives the .yuv frame as on a forward stream."""
         self._check(self.lib.h2y_dpx_stream_open(self.h, C.byref(d), C.byref(info), depth))
         self._stream_desc = d
+        self._stream_out_geom = (d.width, d.height, d.dst_chroma_format_idc)
         self._stream_inverse = None
         self._stream_dpx = int(info.payload_bytes)
         self._stream_rgb = False
@@ -1715,6 +1820,7 @@ class Context:
         self._check(self.lib.h2y_inverse_stream_open(self.h, width, height, in_chroma, in_depth, in_full_range, in_matrix, out_depth,
                                                      algorithm, depth))
         self._stream_inverse = (width, height, in_chroma)
+        self._stream_in_geom = (width, height, in_chroma)
         self._stream_dpx = None
         self._stream_rgb = False
 
@@ -1725,6 +1831,8 @@ class Context:
 
         ptrs = (C.c_void_p * 3)()
         self._check(self.lib.h2y_stream_input(self.h, ptrs))
+        if getattr(self, "_stream_unpack_bytes", None):
+            return [np.ctypeslib.as_array(C.cast(ptrs[0], C.POINTER(C.c_uint8)), shape=(self._stream_unpack_bytes,))]
         if getattr(self, "_stream_cmp_planes", None):
             return [np.ctypeslib.as_array(C.cast(ptrs[c], C.POINTER(C.c_uint16)), shape=(n,)) for c, n in enumerate(self._stream_cmp_planes)]
         if getattr(self, "_stream_dpx", None):
@@ -1750,6 +1858,8 @@ class Context:
         self._check(self.lib.h2y_stream_output(self.h, C.byref(p)))
         if not p:  # an armed ring with keep_output 0, or a compare-only ring: the frame stayed on the device
             return None
+        if getattr(self, "_stream_pack_bytes", None):  # a ring that packs
+            return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(self._stream_pack_bytes,))
         if getattr(self, "_stream_out_words", None):  # a ring that scales
             return np.ctypeslib.as_array(p, shape=(self._stream_out_words,))
         if getattr(self, "_stream_inverse", None):
@@ -1763,6 +1873,10 @@ class Context:
         self._check(self.lib.h2y_stream_close(self.h))
         self._stream_cmp_planes = None
         self._stream_out_words = None
+        self._stream_pack_bytes = None
+        self._stream_unpack_bytes = None
+        self._stream_in_geom = None
+        self._stream_out_geom = None
         self._stream_inverse = None
         self._stream_dpx = None
         self._stream_rgb = False

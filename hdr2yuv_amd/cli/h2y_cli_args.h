@@ -240,6 +240,23 @@
  *             other, 4:2:2, matrix 0 with 4:2:0, the .yuv -> RGB flow, --histogram_only, --scale_only and --light_only, siting 2 with
  *             --chroma_resampler_type 0, and with --linearize 1 a 4:2:0 source and destination whose sitings differ (one context siting
  *             serves both upsamplers).  Without the flag not a line changes.
+ * --dst_pack NAME, --src_pack NAME (additions): how the samples of a .yuv file are packed, NAME one of planar16 (the default, the
+ *             reference's write_yuv() form: nothing changes), planar8 (8 bits: one byte a sample, ffmpeg's yuv420p / yuv444p), nv12
+ *             (8 bits, 4:2:0: Cb and Cr interleaved) and p010 (10..16 bits, 4:2:0: 16-bit words, the sample in the high bits, Cb and Cr
+ *             interleaved; p010le / p012le / p016le at 10, 12, 16 bits); include/hdr2yuv_hip.h, "sample packings", states them.  The
+ *             repack runs on the device (h2y_stream_pack, h2y_stream_unpack), and only the packed bytes cross the bus.  --dst_pack goes
+ *             with every flow that writes a .yuv through a ring: the forward flow from every input type, with --linearize, --scale,
+ *             --dither and the passes in front, --scale_only 1 and --dither_only 1, for any --gpus and appending (frame k lies at
+ *             base + k x h2y_pack_frame_bytes); its depth is --dst_bit_depth.  --src_pack goes wherever a .yuv is the source of the
+ *             .yuv -> .rgb / .tiff flow, --compare_only (R is packed the same way; the ring learns the depth from --src_bit_depth, which
+ *             p010 needs: h2y_stream_unpack_ex), --histogram_only, --light_only, --scale_only,
+ *             --dither_only and --linearize 1 (with or without --src_hlg / --src_sdr / --src_ictcp); --src_start_frame and the
+ *             file-length check use the packed frame's size.  With --scale_only / --dither_only the two flags are independent.  The
+ *             banner ends with src_pack: NAME (ffmpeg -pix_fmt X) and / or dst_pack: ..., only when the flag is given (p010 at 11, 13,
+ *             14 or 15 bits has no such name, and the line says so).  Refused (exit 1, also under --dry_run): an unknown NAME, a packing
+ *             the side's depth or chroma format does not take, a file on that side that is not a .yuv, --dst_pack without
+ *             --dst_filename, beside --ref_filename, --histogram, --ssim or --delta_e, or with --dst_matrix_coeffs 15, --src_pack on
+ *             the integer .yuv -> .yuv flow without --linearize 1, and --compare_only 1 --src_pack p010 without --src_bit_depth.
  * Only user_args_t.chroma_resampler_type has no defined default there (never initialised): FIR here, as in
  * make.sh's example.  The reference calls exit(0) on its argument errors; this program returns 1.
  */
@@ -368,6 +385,11 @@ struct cli_args {
     bool dither_given = false, dither_temporal_given = false, dither_seed_given = false, dither_only_given = false;
     int dither_from = 0, dither_to = 0;
     bool dithers() const { return dither == 1 || dither == 2; }
+    /* --dst_pack / --src_pack NAME: how the .yuv written / read packs its samples; resolved by cli_resolve_pack: H2Y_PACK_* (0, planar16:
+     * no packing).  src_depth_given: --src_bit_depth was on the command line */
+    const char *dst_pack_name = nullptr, *src_pack_name = nullptr;
+    int dst_pack = 0, src_pack = 0;
+    bool src_depth_given = false;
     std::vector<int> devices;
     /* resolved */
     int in_type = CLI_IN_NONE, out_type = CLI_OUT_NONE;
@@ -473,6 +495,9 @@ static inline void cli_help()
            "  ordered pattern, 2 by uniform noise, where the program otherwise cuts the low bits; at most 8 bits; the pattern is the same\n"
            "  in every frame unless --dither_temporal 1), [--dither_only 1] (a .yuv or .rgb source at --src_bit_depth into a destination\n"
            "  of the same extension at --dst_bit_depth, no conversion)\n"
+           "  packings: [--dst_pack planar16|planar8|nv12|p010] [--src_pack ...] (how the .yuv written / read packs its samples: 16-bit planar\n"
+           "  words as the reference writes them, bytes (8 bits: yuv420p / yuv444p), NV12 (8 bits, 4:2:0), P010 (10..16 bits, 4:2:0,\n"
+           "  samples in the words' high bits); repacked on the GPU)\n"
            "input by extension: .yuv .rgb (16-bit planar), .f32 .f16 (raw planar float / half, plane order G,B,R: what\n"
            "  dpx_read() / read_exr() leave in memory), .dpx (10-bit, 16-bit or float DPX) and .tiff (16-bit R,G,B, uncompressed; centre-cropped\n"
            "  to 3840 wide, [--cutout_hd 1] 1920x1080, [--cutout_qhd 1] 960x540) and .exr (scanline OpenEXR: NONE, RLE, ZIPS or ZIP;\n"
@@ -545,7 +570,9 @@ static inline void cli_parse(cli_args &a, int argc, char **argv)
         else if (is("--src_pic_height")) a.in.height = atoi(val());
         else if (is("--dst_pic_width")) a.out.width = atoi(val());
         else if (is("--dst_pic_height")) a.out.height = atoi(val());
-        else if (is("--src_bit_depth")) a.in.bit_depth = atoi(val());
+        else if (is("--src_bit_depth")) { a.in.bit_depth = atoi(val()); a.src_depth_given = true; }
+        else if (is("--dst_pack")) a.dst_pack_name = val();
+        else if (is("--src_pack")) a.src_pack_name = val();
         else if (is("--dst_bit_depth")) a.out.bit_depth = atoi(val());
         else if (is("--src_half_float_flag")) a.in.half_float_flag = atoi(val());
         else if (is("--dst_half_float_flag")) a.out.half_float_flag = atoi(val());
@@ -727,7 +754,110 @@ static inline int cli_resolve_delta_e(cli_args &a);
 static inline int cli_resolve_dither(cli_args &a);
 static inline int cli_resolve_dither_only(cli_args &a);
 static inline int cli_resolve_all(cli_args &a);
+static inline int cli_resolve_flows(cli_args &a);
+static inline int cli_resolve_pack(cli_args &a);
 static inline int cli_resolve(cli_args &a)
+{
+    /* (before the comparison's own resolver, which refuses the depth it was not given in words of its own) */
+    if (a.compare_only && a.src_pack_name && !strcasecmp(a.src_pack_name, "p010") && !a.src_depth_given) {
+        printf("WARNING: --compare_only 1 --src_pack p010 needs --src_bit_depth: the samples lie in the words' high bits\n");
+        return 1;
+    }
+    const int arg_errors = cli_resolve_flows(a);
+    /* last: the packings are those of the files the resolved run reads and writes */
+    return arg_errors || !(a.dst_pack_name || a.src_pack_name) ? arg_errors : cli_resolve_pack(a);
+}
+
+/* the ffmpeg -pix_fmt of a .yuv of this chroma format and depth packed so; "" where ffmpeg has no name for it */
+static inline std::string cli_pix_fmt(int chroma, int bit_depth, int packing)
+{
+    const std::string planar = chroma == H2Y_CHROMA_420 ? "yuv420p" : chroma == H2Y_CHROMA_444 ? "yuv444p" : "";
+    if (packing == H2Y_PACK_PLANAR8) return planar;
+    if (packing == H2Y_PACK_NV12) return "nv12";
+    if (packing == H2Y_PACK_P010) return bit_depth == 10 ? "p010le" : bit_depth == 12 ? "p012le" : bit_depth == 16 ? "p016le" : "";
+    return planar.empty() || bit_depth < 8 || bit_depth > 16 ? "" : bit_depth == 8 ? planar : planar + std::to_string(bit_depth) + "le";
+}
+
+/* --dst_pack / --src_pack: the names, the refusals and the banner's lines; returns the number of argument errors */
+static inline int cli_resolve_pack(cli_args &a)
+{
+    static const char *const kNames[4] = {"planar16", "planar8", "nv12", "p010"};
+    auto packing_of = [](const char *name) {
+        for (int p = 0; p < 4; p++)
+            if (!strcasecmp(name, kNames[p])) return p;
+        return -1;
+    };
+    /* is the packing one this depth and chroma format take?  The warning where not. */
+    auto legal = [](const char *flag, int packing, int depth, int chroma) { /* (4:2:2 never gets here: every flow's resolver refuses it) */
+        if ((packing == H2Y_PACK_NV12 || packing == H2Y_PACK_P010) && chroma != H2Y_CHROMA_420) {
+            printf("WARNING: %s %s is 4:2:0: not with chroma_format_idc %d\n", flag, kNames[packing], chroma);
+            return false;
+        }
+        if ((packing == H2Y_PACK_PLANAR8 || packing == H2Y_PACK_NV12) && depth != 8) {
+            printf("WARNING: %s %s holds one byte a sample: it needs a bit depth of 8, not %d\n", flag, kNames[packing], depth);
+            return false;
+        }
+        if (packing == H2Y_PACK_P010 && (depth < 10 || depth > 16)) {
+            printf("WARNING: %s p010 holds 16-bit words: it needs a bit depth of 10..16, not %d (8 bits: planar8 or nv12)\n", flag, depth);
+            return false;
+        }
+        return true;
+    };
+    auto line = [](const char *key, int packing, int depth, int chroma) {
+        const std::string fmt = cli_pix_fmt(chroma, depth, packing);
+        if (fmt.empty()) printf("%s: %s (no ffmpeg -pix_fmt at %d bits)\n", key, kNames[packing], depth);
+        else printf("%s: %s (ffmpeg -pix_fmt %s)\n", key, kNames[packing], fmt.c_str());
+    };
+    if (a.src_pack_name) {
+        const int p = packing_of(a.src_pack_name);
+        if (p < 0) { printf("WARNING: --src_pack %s: not one of planar16, planar8, nv12, p010\n", a.src_pack_name); return 1; }
+        const cli_pic &pic = a.linearize == 1 ? a.lin : a.in;
+        const int type = a.linearize == 1 ? a.lin_type : a.in_type;
+        const int depth = a.dither_only == 1 ? a.dither_from : pic.bit_depth;
+        if (type != CLI_IN_YUV || strcasecmp(cli_ext_of(a.src), "yuv")) {
+            printf("WARNING: --src_pack is how a .yuv packs its samples: source file (%s) is a .%s\n", a.src ? a.src : "(none)", cli_ext_of(a.src));
+            return 1;
+        }
+        if (p != H2Y_PACK_PLANAR16) {
+            const bool reads_codes = a.inverse || a.compare_only || a.hist_only || a.light_only == 1 || a.scale_only || a.dither_only == 1 || a.linearize == 1;
+            if (!reads_codes) {
+                printf("WARNING: --src_pack: the integer .yuv -> .yuv flow reads the reference's 16-bit planar frames; a packed source goes "
+                       "through --linearize 1\n");
+                return 1;
+            }
+            if (!legal("--src_pack", p, depth, pic.chroma_format_idc)) return 1;
+        }
+        a.src_pack = p;
+        line("src_pack", p, depth, pic.chroma_format_idc);
+    }
+    if (a.dst_pack_name) {
+        const int p = packing_of(a.dst_pack_name);
+        if (p < 0) { printf("WARNING: --dst_pack %s: not one of planar16, planar8, nv12, p010\n", a.dst_pack_name); return 1; }
+        if (!a.dst) { printf("WARNING: --dst_pack needs --dst_filename\n"); return 1; }
+        if (a.out_type != CLI_OUT_YUV || strcasecmp(cli_ext_of(a.dst), "yuv")) {
+            printf("WARNING: --dst_pack is how a .yuv packs its samples: destination file (%s) is a .%s\n", a.dst, cli_ext_of(a.dst));
+            return 1;
+        }
+        const int depth = a.dithers() ? a.dither_to : a.out.bit_depth;
+        if (p != H2Y_PACK_PLANAR16) {
+            if (a.ref || a.hist || a.ssim || a.delta_e) {
+                printf("WARNING: --dst_pack is not combined with --ref_filename, --histogram, --ssim or --delta_e: compare or count the written "
+                       "file (--compare_only 1, --histogram_only 1, with --src_pack)\n");
+                return 1;
+            }
+            if (a.out.matrix_coeffs == H2Y_MATRIX_YUVPRIME2) {
+                printf("WARNING: --dst_pack: dst_matrix_coeffs %d (Y'u'v') is not packed\n", H2Y_MATRIX_YUVPRIME2);
+                return 1;
+            }
+            if (!legal("--dst_pack", p, depth, a.out.chroma_format_idc)) return 1;
+        }
+        a.dst_pack = p;
+        line("dst_pack", p, depth, a.out.chroma_format_idc);
+    }
+    return 0;
+}
+
+static inline int cli_resolve_flows(cli_args &a)
 {
     const bool dither_flags = a.dither_given || a.dither_temporal_given || a.dither_seed_given || a.dither_only_given;
     /* first, and without a line of its own yet: every later resolver sees a conversion at the working depth */

@@ -162,6 +162,11 @@
  * master's (BT.1886) and the ring is h2y_sdrcode_stream_open's with the reference white at W cd/m2; the banner then carries src_sdr:,
  * src_sdr_white: and src_sdr_gamma:.
  *
+ * Packings (--dst_pack / --src_pack planar8|nv12|p010; h2y_cli_args.h): each GPU thread arms its ring last with h2y_stream_pack, so the
+ * frame that comes down is the .yuv frame packed on the device, written at `size of the file at start + k x h2y_pack_frame_bytes`; and
+ * right after opening it with h2y_stream_unpack, so a frame of the source (and of R under --compare_only) is read whole, packed, into
+ * the pinned slot and unpacked on the device.  The file offsets, the length check and R's frame size are the packed frame's.
+ *
  * Chroma siting (--dst_chroma_sample_loc_type 0|2 on the forward flow to .yuv; h2y_cli_args.h): each GPU thread sets its context's
  * siting (h2y_ctx_set_chroma_siting) before it opens its ring, so every frame, and whatever is armed on the ring, has its 4:2:0
  * chroma where the flag says.  The banner carries dst_chroma_sample_loc_type: only when the flag is given, and with 2 it ends with
@@ -200,6 +205,14 @@ static bool write_at(int fd, const void *buf, size_t n, off_t at)
 static size_t planar16_bytes(const cli_pic &p)
 {
     return h2y_scale_frame_bytes(p.width, p.height, p.chroma_format_idc);
+}
+
+/* what every flow's open ends with: the ring just opened (rc 0) takes the source's frames packed where --src_pack says so */
+static int opened(int rc, const cli_args &a, h2y_ctx *ctx)
+{
+    if (rc || !a.src_pack) return rc;
+    /* a compare-only ring does not know its frames' depth: --src_bit_depth says it (P010 needs it, and cli_resolve insists on it) */
+    return a.compare_only ? h2y_stream_unpack_ex(ctx, a.src_pack, a.in.bit_depth) : h2y_stream_unpack(ctx, a.src_pack);
 }
 
 struct block { /* one thread's share: frames [first, first + count) of the run, on `device` */
@@ -414,9 +427,9 @@ static flow forward_flow(const job &j)
         if (a.linearize) { /* the file's PQ codes, linearised on the device into the planes j.d describes */
             const h2y_codelight_desc code{a.lin.width, a.lin.height, a.lin.chroma_format_idc, a.lin.bit_depth, a.lin.video_full_range_flag,
                                           a.lin.matrix_coeffs, a.resampler};
-            if (a.src_hlg == 1) return h2y_hlgcode_stream_open(ctx, &j.d, &code, a.src_hlg_peak, kRingDepth); /* the file's codes are HLG's */
-            if (a.src_sdr == 1) return h2y_sdrcode_stream_open(ctx, &j.d, &code, a.src_sdr_white, kRingDepth); /* the file's codes are BT.1886's */
-            return h2y_pqcode_stream_open(ctx, &j.d, &code, kRingDepth);
+            if (a.src_hlg == 1) return opened(h2y_hlgcode_stream_open(ctx, &j.d, &code, a.src_hlg_peak, kRingDepth), a, ctx); /* the file's codes are HLG's */
+            if (a.src_sdr == 1) return opened(h2y_sdrcode_stream_open(ctx, &j.d, &code, a.src_sdr_white, kRingDepth), a, ctx); /* the file's codes are BT.1886's */
+            return opened(h2y_pqcode_stream_open(ctx, &j.d, &code, kRingDepth), a, ctx);
         }
         return a.in_type == CLI_IN_DPX    ? h2y_dpx_stream_open(ctx, &j.d, &s.di, kRingDepth)
                : a.in_type == CLI_IN_TIFF ? h2y_tiff_stream_open(ctx, &j.d, &s.ti, a.in.video_full_range_flag == 0, kRingDepth)
@@ -433,7 +446,8 @@ static flow forward_flow(const job &j)
                (a.lut3d_table && h2y_stream_lut3d(ctx, a.lut3d_table, a.lut3d_interp, a.lut3d_signal)) ||
                (a.hlg == 1 && h2y_stream_hlg(ctx, a.hlg_peak, a.hlg_relative)) || (a.ictcp == 1 && h2y_stream_ictcp(ctx)) ||
                (a.scale && h2y_stream_scale(ctx, a.out.width, a.out.height, a.scale_taps)) ||
-               (a.dithers() && h2y_stream_dither(ctx, a.dither_to, a.dither, a.dither_temporal, a.dither_seed, (uint32_t)first)); /* after scale */
+               (a.dithers() && h2y_stream_dither(ctx, a.dither_to, a.dither, a.dither_temporal, a.dither_seed, (uint32_t)first)) || /* after scale */
+               (a.dst_pack && h2y_stream_pack(ctx, a.dst_pack));                                                                      /* last */
     };
     if (a.linearize) { /* the code frame whole, as whole_frame_flow reads it: one read, a .rgb with its planes put in G, B, R order */
         const bool rgb = a.lin_type == CLI_IN_RGB;
@@ -516,18 +530,20 @@ static flow inverse_flow(const job &j)
     flow f;
     f.open = [&a, tiff](h2y_ctx *ctx, long) {
         if (a.src_siting && h2y_ctx_set_inverse_chroma_siting(ctx, a.src_siting)) return (int)H2Y_EINVAL; /* before the ring is opened */
-        return (tiff ? h2y_tiff_inverse_stream_open : h2y_inverse_stream_open)(ctx, a.in.width, a.in.height, a.in.chroma_format_idc,
-                                                                              a.in.bit_depth, a.in.video_full_range_flag, a.in.matrix_coeffs,
-                                                                              a.out.bit_depth, a.resampler, kRingDepth);
+        return opened((tiff ? h2y_tiff_inverse_stream_open : h2y_inverse_stream_open)(ctx, a.in.width, a.in.height, a.in.chroma_format_idc,
+                                                                                     a.in.bit_depth, a.in.video_full_range_flag, a.in.matrix_coeffs,
+                                                                                     a.out.bit_depth, a.resampler, kRingDepth), a, ctx);
     };
     f.arm = [&a](h2y_ctx *ctx, long) {
         return (a.ref && h2y_stream_compare(ctx, a.sigma, a.dst ? 1 : 0)) || (a.ssim && h2y_stream_ssim(ctx, -1)) ||
                (a.hist && h2y_stream_histogram(ctx, a.hist_bits));
     };
     f.src_frame_bytes = j.in_frame_bytes;
-    f.fill = [&a, luma, chroma](long, FILE *src, void *const *planes) {
-        const size_t got = fread(planes[0], 1, luma, src) + fread(planes[1], 1, chroma, src) + fread(planes[2], 1, chroma, src);
-        return got == luma + 2 * chroma ? "" : std::string("short read from ") + a.src;
+    const size_t packed = a.src_pack ? j.in_frame_bytes : 0; /* --src_pack: the slot lends one packed frame */
+    f.fill = [&a, luma, chroma, packed](long, FILE *src, void *const *planes) {
+        const size_t got = packed ? fread(planes[0], 1, packed, src)
+                                  : fread(planes[0], 1, luma, src) + fread(planes[1], 1, chroma, src) + fread(planes[2], 1, chroma, src);
+        return got == (packed ? packed : luma + 2 * chroma) ? "" : std::string("short read from ") + a.src;
     };
     f.ref_rgb = true, f.ref_plane_bytes = luma, f.ref_frame_bytes = out_frame;
     f.out_bytes = out_frame;
@@ -567,7 +583,7 @@ static flow compare_flow(const job &j)
     flow f = whole_frame_flow(j);
     f.open = [&a](h2y_ctx *ctx, long) {
         if (a.delta_e && a.de_siting && h2y_ctx_set_inverse_chroma_siting(ctx, a.de_siting)) return (int)H2Y_EINVAL; /* before the ring is opened */
-        return h2y_compare_stream_open(ctx, a.in.width, a.in.height, a.in.chroma_format_idc, a.sigma, kRingDepth);
+        return opened(h2y_compare_stream_open(ctx, a.in.width, a.in.height, a.in.chroma_format_idc, a.sigma, kRingDepth), a, ctx);
     };
     f.arm = [&a](h2y_ctx *ctx, long) {
         return (a.ssim && h2y_stream_ssim(ctx, a.in.bit_depth)) || (a.delta_e && h2y_stream_deltae(ctx, &a.de, a.delta_e_threshold)) ||
@@ -582,8 +598,8 @@ static flow histogram_flow(const job &j)
     const cli_args &a = j.a;
     flow f = whole_frame_flow(j);
     f.open = [&a](h2y_ctx *ctx, long) {
-        return h2y_histogram_stream_open(ctx, a.in.width, a.in.height, a.in.chroma_format_idc, a.hist_depth, a.hist_full, a.hist_gbr, a.hist_bits,
-                                         kRingDepth);
+        return opened(h2y_histogram_stream_open(ctx, a.in.width, a.in.height, a.in.chroma_format_idc, a.hist_depth, a.hist_full, a.hist_gbr,
+                                                a.hist_bits, kRingDepth), a, ctx);
     };
     return f;
 }
@@ -597,7 +613,7 @@ static flow light_flow(const job &j)
         if (a.src_siting && h2y_ctx_set_inverse_chroma_siting(ctx, a.src_siting)) return (int)H2Y_EINVAL; /* before the ring is opened */
         const h2y_codelight_desc d{a.in.width, a.in.height, a.in.chroma_format_idc, a.in.bit_depth, a.in.video_full_range_flag,
                                    a.in.matrix_coeffs, a.resampler};
-        return h2y_codelight_stream_open(ctx, &d, a.dynmeta ? 1 : 0, kRingDepth);
+        return opened(h2y_codelight_stream_open(ctx, &d, a.dynmeta ? 1 : 0, kRingDepth), a, ctx);
     };
     if (a.scene_detect == 1) f.arm = [](h2y_ctx *ctx, long) { return h2y_stream_scenesig(ctx); };
     return f;
@@ -610,9 +626,10 @@ static flow scale_flow(const job &j)
     const bool rgb = a.in_type == CLI_IN_RGB;
     flow f = whole_frame_flow(j);
     f.open = [&a, rgb](h2y_ctx *ctx, long) {
-        return h2y_scale_stream_open(ctx, a.in.width, a.in.height, a.in.chroma_format_idc, a.in.bit_depth, a.in.video_full_range_flag, rgb ? 1 : 0,
-                                     a.out.width, a.out.height, a.scale_taps, kRingDepth);
+        return opened(h2y_scale_stream_open(ctx, a.in.width, a.in.height, a.in.chroma_format_idc, a.in.bit_depth, a.in.video_full_range_flag,
+                                            rgb ? 1 : 0, a.out.width, a.out.height, a.scale_taps, kRingDepth), a, ctx);
     };
+    if (a.dst_pack) f.arm = [&a](h2y_ctx *ctx, long) { return h2y_stream_pack(ctx, a.dst_pack); };
     f.out_bytes = j.out_frame_bytes;
     f.write = rgb ? write_rgb(j, (size_t)a.out.width * a.out.height * 2) : write_plain(j, f.out_bytes);
     f.says_written = a.verbose > 0;
@@ -626,9 +643,11 @@ static flow dither_flow(const job &j)
     const bool rgb = a.in_type == CLI_IN_RGB;
     flow f = whole_frame_flow(j);
     f.open = [&a, rgb](h2y_ctx *ctx, long first) {
-        return h2y_dither_stream_open(ctx, a.in.width, a.in.height, a.in.chroma_format_idc, a.dither_from, a.dither_to, a.in.video_full_range_flag,
-                                      rgb ? 1 : 0, a.dither, a.dither_temporal, a.dither_seed, (uint32_t)first, kRingDepth);
+        return opened(h2y_dither_stream_open(ctx, a.in.width, a.in.height, a.in.chroma_format_idc, a.dither_from, a.dither_to,
+                                             a.in.video_full_range_flag, rgb ? 1 : 0, a.dither, a.dither_temporal, a.dither_seed, (uint32_t)first,
+                                             kRingDepth), a, ctx);
     };
+    if (a.dst_pack) f.arm = [&a](h2y_ctx *ctx, long) { return h2y_stream_pack(ctx, a.dst_pack); };
     f.out_bytes = j.out_frame_bytes;
     f.write = rgb ? write_rgb(j, (size_t)a.in.width * a.in.height * 2) : write_plain(j, f.out_bytes);
     f.says_written = a.verbose > 0;
@@ -973,6 +992,12 @@ int main(int argc, char **argv)
         out_frame_bytes = h2y_frame_bytes(&j.d);
     }
     if (scaling) out_frame_bytes = h2y_scale_frame_bytes(a.out.width, a.out.height, a.out.chroma_format_idc); /* the scaled frame's */
+    if (a.src_pack) { /* the source's frames, and under --compare_only R's, as the file packs them */
+        const cli_pic &file = a.linearize ? a.lin : a.in;
+        in_frame_bytes = h2y_pack_frame_bytes(file.width, file.height, file.chroma_format_idc, a.src_pack);
+        if (a.compare_only) out_frame_bytes = in_frame_bytes;
+    }
+    if (a.dst_pack) out_frame_bytes = h2y_pack_frame_bytes(a.out.width, a.out.height, a.out.chroma_format_idc, a.dst_pack);
 
     /* how many frames there are to do: --n_frames, or what the file holds from --src_start_frame on if that is fewer */
     long frames = a.n_frames > 0 ? a.n_frames : 1;

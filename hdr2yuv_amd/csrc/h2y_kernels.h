@@ -574,4 +574,29 @@ dither_plane h2y_dither_plane(uint32_t w, uint32_t rows, uint32_t off, uint32_t 
 /* k_dither<mode> over (frame, plane, chunk) units; mode: H2Y_DITHER_CUT, _ORDERED or _NOISE (h2y_dither1.h) */
 hipError_t h2y_launch_dither(int mode, int grid, hipStream_t st, const dither_args &a, const dither_frame *frames, int n_frames);
 
+/* k_pack / k_unpack (h2y_pack.hip): the sample packings of include/hdr2yuv_hip.h between a frame of three u16 planes ("planar")
+ * and its packed form.  A job is one plane that becomes bytes or words, or the two chroma planes that become one block of
+ * (P1, P2) pairs; offsets count samples from the planar base and elements (bytes, P010: words) from the packed base. */
+struct pack_job {
+    uint32_t n;       /* the plane's samples, or the chroma block's pairs */
+    uint32_t pl, pl2; /* planar: where the plane starts (a chroma block: P1 and P2) */
+    uint32_t pk;      /* packed: where its elements start */
+    uint32_t sh;      /* indices of the first group that lie before the job */
+    uint32_t vec;     /* whole groups lie on 16-byte boundaries on every side: 16-byte accesses */
+    uint32_t chunks;  /* the kernels' units of the job */
+};
+struct pack_args {
+    pack_job j[3];  /* PLANAR8: the three planes; NV12, P010: plane 0 and the chroma block (j[2] empty) */
+    uint32_t maxv;  /* M = 2^D - 1 */
+    uint32_t shift; /* P010: 16 - D; else 0 */
+};
+struct pack_frame { /* one frame; both bases 16-byte aligned */
+    const void *planar, *packed; /* k_pack writes packed, k_unpack planar */
+};
+/* the jobs of a w x h frame (w x h < 2^28) of a legal (chroma, bit_depth, packing) whose planar planes start off[] samples from
+ * the planar base (one after the other in a frame; padded apart in an inverse ring's slot) */
+pack_args h2y_pack_args(uint32_t w, uint32_t h, int chroma, int bit_depth, int packing, const uint32_t off[3]);
+/* k_pack<packing> or k_unpack<packing> over (frame, job, chunk) units */
+hipError_t h2y_launch_pack(int packing, bool unpack, int grid, hipStream_t st, const pack_args &a, const pack_frame *frames, int n_frames);
+
 #endif

@@ -94,6 +94,10 @@ struct cmp_stage : ring_stage {
     cmp_geom g{};
     cmp_frame *tab = nullptr;
     size_t ref_bytes = 0, stats_off = 0; /* the pinned reference's bytes; where the stats lie in its device twin */
+    /* a compare-only ring armed with h2y_stream_unpack: the lent reference holds a packed frame of packed_bytes, which goes up as it
+     * is into packed_to[slot]; the unpack stage's k_unpack writes the device twin from there */
+    size_t packed_bytes = 0;
+    std::vector<char *> packed_to;
     h2y_compare_stats *dev_stats(int k) const { return reinterpret_cast<h2y_compare_stats *>(ss[k].d_ref + stats_off); }
     int ready(h2y_ctx *ctx, int k) override
     {
@@ -103,7 +107,8 @@ struct cmp_stage : ring_stage {
     int upload(h2y_ctx *ctx, int k) override
     {
         slot &s = ss[k];
-        if (g.b_off[1] == g.n[0] && g.b_off[2] == g.n[0] + g.n[1]) /* the device twin is contiguous too: one copy */
+        if (packed_bytes) HIP_TRY(ctx, hipMemcpyAsync(packed_to[k], s.h_ref, packed_bytes, hipMemcpyHostToDevice, ctx->s_h2d));
+        else if (g.b_off[1] == g.n[0] && g.b_off[2] == g.n[0] + g.n[1]) /* the device twin is contiguous too: one copy */
             HIP_TRY(ctx, hipMemcpyAsync(s.d_ref, s.h_ref, ref_bytes, hipMemcpyHostToDevice, ctx->s_h2d));
         else /* padded apart as the inverse ring's output planes */
             for (size_t c = 0, h_off = 0; c < 3; h_off += g.n[c] * sizeof(uint16_t), c++)
@@ -161,6 +166,9 @@ int h2y_stream_compare(h2y_ctx *ctx, int sigma, int keep_output)
     if (ctx->s_stage[STAGE_CODELIGHT]) return fail(ctx, H2Y_EINVAL, "a light-only ring takes no other stage");
     if (ctx->s_stage[STAGE_SCALE]) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that scales is not compared: compare the written file instead");
     if (ctx->s_stage[STAGE_DITHER]) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that dithers is not compared: compare the written file instead");
+    if (ctx->s_stage[STAGE_PACK]) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that packs is not compared: compare the written file instead");
+    if (ctx->s_stage[STAGE_UNPACK] && ctx->s_kind == h2y_ctx::RING_PLANES)
+        return fail(ctx, H2Y_EINVAL, "the ring unpacks already: arm the comparison before unpack, so that its reference is unpacked too");
     if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
     if (keep_output != 0 && keep_output != 1) return fail(ctx, H2Y_EINVAL, "keep_output must be 0 or 1");
     return cmp_arm(ctx, sigma, keep_output);
@@ -302,6 +310,7 @@ int h2y_stream_ssim(h2y_ctx *ctx, int bit_depth)
     if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
     if (ctx->s_stage[STAGE_SCALE]) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that scales computes no SSIM: compare the written file instead");
     if (ctx->s_stage[STAGE_DITHER]) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that dithers computes no SSIM: compare the written file instead");
+    if (ctx->s_stage[STAGE_PACK]) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that packs computes no SSIM: compare the written file instead");
     const cmp_stage *cmp = stage_of<cmp_stage>(ctx, STAGE_COMPARE);
     if (!cmp) return fail(ctx, H2Y_EINVAL, "the ring is not armed for comparison: h2y_stream_compare first");
     if (ctx->s_stage[STAGE_SSIM]) return fail(ctx, H2Y_EINVAL, "the ring computes SSIM already");
@@ -715,7 +724,7 @@ int codelight_check(h2y_ctx *ctx, const h2y_codelight_desc *d, codelight_plan &p
     a.sub[1] = d->full_range ? (float)(1u << (d->bit_depth - 1)) : 128.0f * s;
     a.div[1] = d->full_range ? top : 224.0f * s;
     contiguous_planes(d->width, d->height, d->chroma_format_idc, p.off);
-    p.width = d->width, p.height = d->height;
+    p.width = d->width, p.height = d->height, p.bit_depth = d->bit_depth;
     p.samples = p.off[2] + (p.off[2] - p.off[1]); /* the last plane is as long as the second */
     /* the frames' bases are 16-byte aligned, and so is the scratch: a plane takes 16-byte loads where its start is */
     a.vec = 1u;
@@ -1325,6 +1334,7 @@ int h2y_stream_deltae(h2y_ctx *ctx, const h2y_codelight_desc *d, float threshold
     if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
     if (ctx->s_stage[STAGE_CODELIGHT]) return fail(ctx, H2Y_EINVAL, "a light-only ring takes no other stage");
     if (ctx->s_stage[STAGE_DITHER]) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that dithers computes no Delta E: compare the written file instead");
+    if (ctx->s_stage[STAGE_PACK]) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that packs computes no Delta E: compare the written file instead");
     const cmp_stage *cmp = stage_of<cmp_stage>(ctx, STAGE_COMPARE);
     if (!cmp) return fail(ctx, H2Y_EINVAL, "the ring is not armed for comparison: h2y_stream_compare first");
     if (ctx->s_stage[STAGE_DELTAE]) return fail(ctx, H2Y_EINVAL, "the ring computes Delta E already");
@@ -1653,6 +1663,7 @@ int h2y_stream_histogram_ex(h2y_ctx *ctx, int bits, int bit_depth, int full_rang
     if (ctx->s_stage[STAGE_CODELIGHT]) return fail(ctx, H2Y_EINVAL, "a light-only ring takes no other stage");
     if (ctx->s_stage[STAGE_SCALE]) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that scales counts no histograms: count the written file instead");
     if (ctx->s_stage[STAGE_DITHER]) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that dithers counts no histograms: count the written file instead");
+    if (ctx->s_stage[STAGE_PACK]) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that packs counts no histograms: count the written file instead");
     if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
     const ring_frame &f = ctx->s_frame;
     if (!f.depth && (bit_depth < 0 || full_range < 0 || gbr < 0))
@@ -1899,7 +1910,7 @@ struct scale_stage : ring_stage {
     char *tabs = nullptr;
     scale_frame *tab = nullptr;
     size_t bytes = 0; /* of the scaled frame */
-    bool down = true; /* false: a dither stage armed behind this one sends its own frame down instead */
+    bool down = true; /* false: a dither or pack stage armed behind this one sends its own frame down instead */
     int run(h2y_ctx *ctx, int k) override
     {
         HIP_TRY(ctx, h2y_launch_scale(scale_grid(ctx, g, 1), ctx->stream, g, tab + k, 1));
@@ -1954,6 +1965,7 @@ int h2y_stream_scale(h2y_ctx *ctx, int dst_w, int dst_h, int a)
     if (ctx->s_kind != h2y_ctx::RING_FORWARD) return fail(ctx, H2Y_EINVAL, "only a forward ring is armed for scaling");
     if (ctx->s_stage[STAGE_SCALE]) return fail(ctx, H2Y_EINVAL, "the ring scales already");
     if (ctx->s_stage[STAGE_DITHER]) return fail(ctx, H2Y_EINVAL, "the ring dithers already: arm scaling before dither");
+    if (ctx->s_stage[STAGE_PACK]) return fail(ctx, H2Y_EINVAL, "the ring packs already: arm scaling before pack");
     if (ctx->s_stage[STAGE_COMPARE] || ctx->s_stage[STAGE_HISTOGRAM] || ctx->s_stage[STAGE_SSIM])
         return fail(ctx, H2Y_EUNSUPPORTED, "a ring armed for comparison, histograms or SSIM is not scaled: compare or count the written file instead");
     if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
@@ -3215,6 +3227,7 @@ struct dither_stage : ring_stage {
     size_t bytes = 0; /* of the frame */
     int mode = 0;
     uint32_t submitted = 0;
+    bool down = true; /* false: a pack stage armed behind this one sends its own frame down instead */
     int run(h2y_ctx *ctx, int k) override
     {
         dither_args b = a;
@@ -3224,7 +3237,7 @@ struct dither_stage : ring_stage {
     }
     int download(h2y_ctx *ctx, int k) override
     {
-        if (ss[k].d) HIP_TRY(ctx, hipMemcpyAsync(ss[k].h, ss[k].d, bytes, hipMemcpyDeviceToHost, ctx->s_d2h));
+        if (ss[k].d && down) HIP_TRY(ctx, hipMemcpyAsync(ss[k].h, ss[k].d, bytes, hipMemcpyDeviceToHost, ctx->s_d2h));
         return H2Y_OK;
     }
 };
@@ -3270,6 +3283,7 @@ int h2y_stream_dither(h2y_ctx *ctx, int dst_depth, int mode, int temporal, uint3
     if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
     if (ctx->s_kind != h2y_ctx::RING_FORWARD) return fail(ctx, H2Y_EINVAL, "only a forward ring is armed for dither");
     if (ctx->s_stage[STAGE_DITHER]) return fail(ctx, H2Y_EINVAL, "the ring dithers already");
+    if (ctx->s_stage[STAGE_PACK]) return fail(ctx, H2Y_EINVAL, "the ring packs already: arm dither before pack");
     if (ctx->s_stage[STAGE_COMPARE] || ctx->s_stage[STAGE_HISTOGRAM] || ctx->s_stage[STAGE_SSIM] || ctx->s_stage[STAGE_DELTAE])
         return fail(ctx, H2Y_EUNSUPPORTED, "a ring armed for comparison, histograms, SSIM or Delta E is not dithered: compare or count the written file instead");
     if (ctx->s_desc.dst_matrix == H2Y_MATRIX_YUVPRIME2) return fail(ctx, H2Y_EUNSUPPORTED, "a Y'u'v' ring (dst_matrix_coeffs 15) is not dithered");
@@ -3290,4 +3304,291 @@ int h2y_dither_stream_open(h2y_ctx *ctx, int width, int height, int chroma_forma
     rc = dither_arm(ctx, dst_depth, gbr, mode, temporal, seed, first_frame);
     if (rc) stream_free(ctx);
     return rc;
+}
+
+/* ---- sample packings: byte and semi-planar frames (--dst_pack, --src_pack): include/hdr2yuv_hip.h states the definition ------------ */
+
+#include "h2y_pack1.h"
+
+static const char *const kPackName[4] = {"PLANAR16", "PLANAR8", "NV12", "P010"};
+
+size_t h2y_pack_frame_bytes(int width, int height, int chroma_format_idc, int packing)
+{
+    if (width < 1 || height < 1 || !pack_legal(chroma_format_idc, 0, packing)) return 0;
+    const size_t n = (size_t)width * (size_t)height;
+    const size_t nc = (size_t)pack_cw((uint32_t)width, chroma_format_idc) * (size_t)pack_ch((uint32_t)height, chroma_format_idc);
+    return (n + 2 * nc) * pack_elem_bytes(packing);
+}
+
+static int pack_check(h2y_ctx *ctx, int width, int height, int chroma, int bit_depth, int packing)
+{
+    if (chroma == 2) return fail(ctx, H2Y_EUNSUPPORTED, "chroma_format_idc 2 (4:2:2) is not packed");
+    if (chroma != H2Y_CHROMA_420 && chroma != H2Y_CHROMA_444) return fail(ctx, H2Y_EINVAL, "chroma_format_idc must be 1 or 3");
+    if (width < 1 || height < 1 || (uint64_t)width * (uint64_t)height >= (1ull << 28)) return fail(ctx, H2Y_EINVAL, "pack: bad picture size");
+    if (packing == H2Y_PACK_PLANAR16) return fail(ctx, H2Y_EINVAL, "packing 0 (planar16) is the frame as it is: nothing to pack or unpack");
+    if (packing < 0 || packing > H2Y_PACK_P010) return fail(ctx, H2Y_EINVAL, "packing must be 1 (planar8), 2 (nv12) or 3 (p010)");
+    if (!pack_legal(chroma, bit_depth, packing))
+        return fail(ctx, H2Y_EINVAL, "packing %s does not take bit depth %d with chroma_format_idc %d (planar8: 8 bits; nv12: 8 bits, 4:2:0; p010: 10..16 bits, 4:2:0)",
+                    kPackName[packing], bit_depth, chroma);
+    return H2Y_OK;
+}
+
+int h2y_pack_frame(int width, int height, int chroma_format_idc, int bit_depth, int packing, const uint16_t *src, void *dst)
+{
+    if (!src || !dst) return fail(nullptr, H2Y_EINVAL, "null frame");
+    const int rc = pack_check(nullptr, width, height, chroma_format_idc, bit_depth, packing);
+    if (rc) return rc;
+    const size_t n = (size_t)width * height, nc = (size_t)pack_cw((uint32_t)width, chroma_format_idc) * pack_ch((uint32_t)height, chroma_format_idc);
+    const uint32_t M = (1u << bit_depth) - 1u, s = packing == H2Y_PACK_P010 ? 16u - (uint32_t)bit_depth : 0u;
+    uint8_t *b = static_cast<uint8_t *>(dst);
+    uint16_t *w = static_cast<uint16_t *>(dst);
+    const size_t planar = packing == H2Y_PACK_PLANAR8 ? n + 2 * nc : n; /* these go over element for element */
+    for (size_t i = 0; i < planar; i++) {
+        if (packing == H2Y_PACK_P010) w[i] = (uint16_t)pack_code(src[i], M, s);
+        else b[i] = (uint8_t)pack_code(src[i], M, s);
+    }
+    if (packing != H2Y_PACK_PLANAR8)
+        for (size_t i = 0; i < nc; i++)
+            for (size_t c = 0; c < 2; c++) {
+                const uint32_t e = pack_code(src[n + c * nc + i], M, s);
+                if (packing == H2Y_PACK_P010) w[n + 2 * i + c] = (uint16_t)e;
+                else b[n + 2 * i + c] = (uint8_t)e;
+            }
+    return H2Y_OK;
+}
+
+int h2y_unpack_frame(int width, int height, int chroma_format_idc, int bit_depth, int packing, const void *src, uint16_t *dst)
+{
+    if (!src || !dst) return fail(nullptr, H2Y_EINVAL, "null frame");
+    const int rc = pack_check(nullptr, width, height, chroma_format_idc, bit_depth, packing);
+    if (rc) return rc;
+    const size_t n = (size_t)width * height, nc = (size_t)pack_cw((uint32_t)width, chroma_format_idc) * pack_ch((uint32_t)height, chroma_format_idc);
+    const uint32_t s = packing == H2Y_PACK_P010 ? 16u - (uint32_t)bit_depth : 0u;
+    const uint8_t *b = static_cast<const uint8_t *>(src);
+    const uint16_t *w = static_cast<const uint16_t *>(src);
+    const size_t planar = packing == H2Y_PACK_PLANAR8 ? n + 2 * nc : n;
+    for (size_t i = 0; i < planar; i++) dst[i] = (uint16_t)unpack_code(packing == H2Y_PACK_P010 ? (uint32_t)w[i] : (uint32_t)b[i], s);
+    if (packing != H2Y_PACK_PLANAR8)
+        for (size_t i = 0; i < nc; i++)
+            for (size_t c = 0; c < 2; c++)
+                dst[n + c * nc + i] = (uint16_t)unpack_code(packing == H2Y_PACK_P010 ? (uint32_t)w[n + 2 * i + c] : (uint32_t)b[n + 2 * i + c], s);
+    return H2Y_OK;
+}
+
+static int pack_grid(const h2y_ctx *ctx, const pack_args &a, int n_frames)
+{
+    return unit_grid(ctx, (uint64_t)n_frames * (a.j[0].chunks + a.j[1].chunks + a.j[2].chunks));
+}
+
+/* both batches: planar[f] and packed[f] are the frames' two sides, whichever is written */
+static int pack_batch(h2y_ctx *ctx, bool unpack, int width, int height, int chroma, int bit_depth, int packing, int n_frames,
+                      const void *const *planar, const void *const *packed)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
+    int rc = pack_check(ctx, width, height, chroma, bit_depth, packing);
+    if (rc) return rc;
+    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
+    if (!planar || !packed) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
+    for (int f = 0; f < n_frames; f++) {
+        if (!planar[f] || !packed[f]) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is null", f);
+        if (((uintptr_t)planar[f] | (uintptr_t)packed[f]) & 15u) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is not 16-byte aligned", f);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    uint32_t off[3];
+    contiguous_planes(width, height, chroma, off);
+    const pack_args a = h2y_pack_args((uint32_t)width, (uint32_t)height, chroma, bit_depth, packing, off);
+    pack_frame *h;
+    rc = frame_table(ctx, n_frames, h);
+    if (rc) return rc;
+    for (int f = 0; f < n_frames; f++) h[f] = pack_frame{planar[f], packed[f]};
+    rc = timed_launches(ctx, h, n_frames, H2Y_PACK_FRAMES_PER_LAUNCH, unpack ? "k_unpack" : "k_pack", [&](const pack_frame *frames, int, int nf) {
+        return h2y_launch_pack(packing, unpack, pack_grid(ctx, a, nf), ctx->stream, a, frames, nf);
+    });
+    if (rc) return rc;
+    ctx->last_variant = std::string(unpack ? "k_unpack<" : "k_pack<") + kPackName[packing] + ">";
+    return H2Y_OK;
+}
+
+int h2y_pack_batch(h2y_ctx *ctx, int width, int height, int chroma_format_idc, int bit_depth, int packing, int n_frames,
+                   const uint16_t *const *d_src, void *const *d_dst)
+{
+    return pack_batch(ctx, false, width, height, chroma_format_idc, bit_depth, packing, n_frames, reinterpret_cast<const void *const *>(d_src), d_dst);
+}
+
+int h2y_unpack_batch(h2y_ctx *ctx, int width, int height, int chroma_format_idc, int bit_depth, int packing, int n_frames,
+                     const void *const *d_src, uint16_t *const *d_dst)
+{
+    return pack_batch(ctx, true, width, height, chroma_format_idc, bit_depth, packing, n_frames, reinterpret_cast<const void *const *>(d_dst), d_src);
+}
+
+/* Packing's ring stage, the last of a slot's: k_pack packs the frame that would go down -- the ring's, the scale stage's or the
+ * dither stage's -- into a frame of its own, on the device and pinned, which goes down and is handed out in that frame's place */
+struct pack_stage : ring_stage {
+    struct slot {
+        char *d = nullptr, *h = nullptr;
+    };
+    std::vector<slot> ss;
+    pack_args a{};
+    pack_frame *tab = nullptr;
+    size_t bytes = 0; /* of the packed frame */
+    int packing = 0;
+    int run(h2y_ctx *ctx, int k) override
+    {
+        HIP_TRY(ctx, h2y_launch_pack(packing, false, pack_grid(ctx, a, 1), ctx->stream, a, tab + k, 1));
+        return H2Y_OK;
+    }
+    int download(h2y_ctx *ctx, int k) override
+    {
+        HIP_TRY(ctx, hipMemcpyAsync(ss[k].h, ss[k].d, bytes, hipMemcpyDeviceToHost, ctx->s_d2h));
+        return H2Y_OK;
+    }
+};
+
+int h2y_stream_pack(h2y_ctx *ctx, int packing)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    const ring_frame &f = ctx->s_frame;
+    scale_stage *sc = stage_of<scale_stage>(ctx, STAGE_SCALE);
+    dither_stage *di = stage_of<dither_stage>(ctx, STAGE_DITHER);
+    /* a .yuv frame comes out of a forward ring, and out of a ring without a producer that scales or dithers its input */
+    if (ctx->s_kind != h2y_ctx::RING_FORWARD && !(ctx->s_kind == h2y_ctx::RING_PLANES && (sc || di)))
+        return fail(ctx, H2Y_EUNSUPPORTED, "the ring's output is no .yuv frame: only a forward, scale-only or dither-only ring packs");
+    if (ctx->s_stage[STAGE_PACK]) return fail(ctx, H2Y_EINVAL, "the ring packs already");
+    if (ctx->s_stage[STAGE_COMPARE] || ctx->s_stage[STAGE_HISTOGRAM] || ctx->s_stage[STAGE_SSIM] || ctx->s_stage[STAGE_DELTAE])
+        return fail(ctx, H2Y_EUNSUPPORTED, "a ring armed for comparison, histograms, SSIM or Delta E is not packed: compare or count the written file instead");
+    if (ctx->s_kind == h2y_ctx::RING_FORWARD && ctx->s_desc.dst_matrix == H2Y_MATRIX_YUVPRIME2)
+        return fail(ctx, H2Y_EUNSUPPORTED, "a Y'u'v' ring (dst_matrix_coeffs 15) is not packed");
+    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    const int width = sc ? (int)sc->g.p[0].dw : f.width, height = sc ? (int)sc->g.p[0].dh : f.height;
+    const int bit_depth = f.depth - (di ? (int)di->a.shift : 0);
+    int rc = pack_check(ctx, width, height, f.chroma, bit_depth, packing);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    auto st = std::make_unique<pack_stage>();
+    pack_stage *pk = st.get();
+    uint32_t off[3];
+    contiguous_planes(width, height, f.chroma, off);
+    pk->a = h2y_pack_args((uint32_t)width, (uint32_t)height, f.chroma, bit_depth, packing, off);
+    pk->packing = packing;
+    pk->bytes = h2y_pack_frame_bytes(width, height, f.chroma, packing);
+    const int depth = (int)ctx->ss.size();
+    std::vector<pack_frame> tab(depth);
+    pk->ss.resize(depth);
+    for (int k = 0; k < depth; k++) {
+        pk->dev_alloc(pk->ss[k].d, std::max<size_t>(pk->bytes, 16));
+        pk->pin_alloc(pk->ss[k].h, std::max<size_t>(pk->bytes, 16));
+        /* where the frame that would go down lies: a ring without a producer has its stage write the slot's output */
+        const uint16_t *src = f.in_input ? ctx->ss[k].d_out : di ? di->ss[k].d : sc ? sc->ss[k].d : ctx->ss[k].d_out;
+        tab[k] = pack_frame{src, pk->ss[k].d};
+    }
+    pk->table(pk->tab, tab);
+    rc = stage_arm(ctx, STAGE_PACK, std::move(st), "pack");
+    if (rc) return rc;
+    if (sc) sc->down = false; /* the frames in front stay on the device: the packed one goes down */
+    if (di) di->down = false;
+    ring_frame_stays(ctx);
+    for (int k = 0; k < depth; k++) ctx->ss[k].result = reinterpret_cast<const uint16_t *>(pk->ss[k].h);
+    return H2Y_OK;
+}
+
+/* Unpacking's ring stage, the first of a slot's: it lends its pinned packed frame as the slot's input, takes it up in the place of
+ * ring_upload's copy, and k_unpack writes the planes where that copy would have put them, before the ring's producer.  On the
+ * compare-only ring the comparison's reference goes the same way (cmp_stage::packed_to). */
+struct unpack_stage : ring_stage {
+    struct slot {
+        char *d = nullptr, *h = nullptr, *d_ref = nullptr;
+    };
+    std::vector<slot> ss;
+    pack_args a{}, a_ref{};
+    pack_frame *tab = nullptr, *tab_ref = nullptr;
+    size_t bytes = 0; /* of the packed frame */
+    int packing = 0;
+    void *lend(h2y_ctx *, int k) override { return ss[k].h; }
+    int upload(h2y_ctx *ctx, int k) override
+    {
+        if (bytes) HIP_TRY(ctx, hipMemcpyAsync(ss[k].d, ss[k].h, bytes, hipMemcpyHostToDevice, ctx->s_h2d));
+        return H2Y_OK;
+    }
+    int unpack(h2y_ctx *ctx, int k) override
+    {
+        HIP_TRY(ctx, h2y_launch_pack(packing, true, pack_grid(ctx, a, 1), ctx->stream, a, tab + k, 1));
+        if (tab_ref) HIP_TRY(ctx, h2y_launch_pack(packing, true, pack_grid(ctx, a_ref, 1), ctx->stream, a_ref, tab_ref + k, 1));
+        return H2Y_OK;
+    }
+    int run(h2y_ctx *, int) override { return H2Y_OK; }
+};
+
+int h2y_stream_unpack(h2y_ctx *ctx, int packing) { return h2y_stream_unpack_ex(ctx, packing, 0); }
+
+int h2y_stream_unpack_ex(h2y_ctx *ctx, int packing, int depth_given)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    if (ctx->s_stage[STAGE_UNPACK]) return fail(ctx, H2Y_EINVAL, "the ring unpacks already");
+    /* where the planes the upload brings lie in the slot's device input, which frame they are, and its depth */
+    const ring_frame &f = ctx->s_frame;
+    int width, height, chroma, bit_depth;
+    uint32_t off[3];
+    size_t base = 0;
+    if (ctx->s_kind == h2y_ctx::RING_FORWARD) {
+        if (ctx->s_src.kind == decode_src::NONE && ctx->s_desc.in_sample_type == H2Y_SAMPLE_U16)
+            return fail(ctx, H2Y_EUNSUPPORTED, "a forward ring on U16 planes (the integer .yuv -> .yuv flow) takes its planes as the reference does: not unpacked");
+        if (ctx->s_src.kind != decode_src::PQCODE)
+            return fail(ctx, H2Y_EINVAL, "the ring's input is not u16 code planes: only an inverse, planes or code ring unpacks");
+        const codelight_plan &p = ctx->s_src.code;
+        width = p.width, height = p.height, chroma = p.sub ? H2Y_CHROMA_420 : H2Y_CHROMA_444, bit_depth = p.bit_depth;
+        for (int c = 0; c < 3; c++) off[c] = p.off[c];
+        base = ctx->s_pay_off;
+    } else if (ctx->s_kind == h2y_ctx::RING_INVERSE) {
+        const inv_params &p = ctx->s_inv;
+        width = p.width, height = p.height, chroma = p.chroma, bit_depth = p.in_depth;
+        for (int c = 0; c < 3; c++) off[c] = (uint32_t)(ctx->s_in_off[c] / sizeof(uint16_t));
+    } else {
+        width = f.width, height = f.height, chroma = f.chroma, bit_depth = f.depth;
+        for (int c = 0; c < 3; c++) off[c] = f.off[c];
+    }
+    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    if (depth_given < 0) return fail(ctx, H2Y_EINVAL, "unpack: bit_depth must be 0 (the ring's own) or the frames' depth");
+    if (depth_given > 0 && bit_depth > 0 && depth_given != bit_depth)
+        return fail(ctx, H2Y_EINVAL, "unpack: bit_depth %d given, but the ring's input depth is %d", depth_given, bit_depth);
+    if (depth_given > 0) bit_depth = depth_given; /* a compare-only ring learns its frames' depth here */
+    if (packing == H2Y_PACK_P010 && bit_depth == 0)
+        return fail(ctx, H2Y_EINVAL, "packing P010 needs the bit depth, which a compare-only ring does not know: give it to h2y_stream_unpack_ex");
+    int rc = pack_check(ctx, width, height, chroma, bit_depth, packing);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    auto st = std::make_unique<unpack_stage>();
+    unpack_stage *un = st.get();
+    const int depth_bits = bit_depth ? bit_depth : 8; /* unknown: a byte packing, whose codes are the bytes */
+    un->a = h2y_pack_args((uint32_t)width, (uint32_t)height, chroma, depth_bits, packing, off);
+    un->packing = packing;
+    un->bytes = h2y_pack_frame_bytes(width, height, chroma, packing);
+    cmp_stage *cmp = ctx->s_kind == h2y_ctx::RING_PLANES ? stage_of<cmp_stage>(ctx, STAGE_COMPARE) : nullptr; /* the compare-only ring */
+    const int depth = (int)ctx->ss.size();
+    std::vector<pack_frame> tab(depth), tab_ref(depth);
+    un->ss.resize(depth);
+    for (int k = 0; k < depth; k++) {
+        un->dev_alloc(un->ss[k].d, std::max<size_t>(un->bytes, 16));
+        un->pin_alloc(un->ss[k].h, std::max<size_t>(un->bytes, 16));
+        tab[k] = pack_frame{ctx->ss[k].d_in + base, un->ss[k].d};
+        if (cmp) {
+            un->dev_alloc(un->ss[k].d_ref, std::max<size_t>(un->bytes, 16));
+            tab_ref[k] = pack_frame{cmp->ss[k].d_ref, un->ss[k].d_ref};
+        }
+    }
+    un->table(un->tab, tab);
+    if (cmp) {
+        un->a_ref = h2y_pack_args((uint32_t)width, (uint32_t)height, chroma, depth_bits, packing, cmp->g.b_off);
+        un->table(un->tab_ref, tab_ref);
+    }
+    rc = stage_arm(ctx, STAGE_UNPACK, std::move(st), "unpack");
+    if (rc) return rc;
+    if (cmp) { /* the lent reference holds a packed frame: it goes up as it is, into the stage's frame */
+        cmp->packed_bytes = un->bytes;
+        cmp->packed_to.resize(depth);
+        for (int k = 0; k < depth; k++) cmp->packed_to[k] = un->ss[k].d_ref;
+    }
+    return H2Y_OK;
 }

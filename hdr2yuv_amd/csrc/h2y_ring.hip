@@ -307,6 +307,7 @@ int h2y_sdrcode_stream_open(h2y_ctx *ctx, const h2y_desc *d, const h2y_codelight
 /* the slot's input goes up on s_h2d */
 static int ring_upload(h2y_ctx *ctx, h2y_ctx::stream_slot &s)
 {
+    if (ctx->s_stage[STAGE_UNPACK]) return H2Y_OK; /* the stage's own upload brings the packed frame instead */
     if (ctx->s_kind != h2y_ctx::RING_FORWARD) { /* the planes as the slot holds them: one copy (none of an empty frame) */
         if (ctx->s_in_bytes) HIP_TRY(ctx, hipMemcpyAsync(s.d_in, s.h_in, ctx->s_in_bytes, hipMemcpyHostToDevice, ctx->s_h2d));
     } else if (ctx->s_src.kind != decode_src::NONE) /* the payload goes up; the decode writes the three planes below it */
@@ -414,6 +415,11 @@ int h2y_stream_input(h2y_ctx *ctx, void *planes[3])
     } else if (s.state != 0) return fail(ctx, H2Y_EINVAL, "all %d slots are in flight: take an output first", (int)ctx->ss.size());
     s.state = 1;
     ctx->s_started = true;
+    if (ring_stage *un = ctx->s_stage[STAGE_UNPACK].get()) { /* the packed frame, as the file holds it */
+        planes[0] = un->lend(ctx, ctx->s_tail);
+        planes[1] = planes[2] = nullptr;
+        return H2Y_OK;
+    }
     if (ctx->s_src.kind != decode_src::NONE) { /* the payload, as the file holds it (TIFF: the decoded rows, packed; EXR: unpacked) */
         planes[0] = s.h_in;
         planes[1] = planes[2] = nullptr;
@@ -424,7 +430,7 @@ int h2y_stream_input(h2y_ctx *ctx, void *planes[3])
 }
 
 /* One frame through the ring: its upload and the armed stages' on s_h2d; on the context's stream the ring's producer, then the
- * stages in their order; on s_d2h the frame (where it goes down) and the stages' results */
+ * stages in their order (an unpack stage's k_unpack in front of the producer); on s_d2h the frame (where it goes down) and the stages' results */
 int h2y_stream_submit(h2y_ctx *ctx)
 {
     if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
@@ -443,6 +449,9 @@ int h2y_stream_submit(h2y_ctx *ctx)
     if (rc) return rc;
     HIP_TRY(ctx, hipEventRecord(s.ev_h2d, ctx->s_h2d));
     HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s.ev_h2d, 0));
+    for (auto &st : ctx->s_stage) /* the planes of a packed input, before anything reads them */
+        if (!rc && st) rc = st->unpack(ctx, slot);
+    if (rc) return rc;
     if (ctx->s_kind == h2y_ctx::RING_FORWARD) rc = forward_produce(ctx, slot);
     else if (ctx->s_kind == h2y_ctx::RING_INVERSE) rc = inverse_produce(ctx, slot);
     for (auto &st : ctx->s_stage)

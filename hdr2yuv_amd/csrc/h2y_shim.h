@@ -61,7 +61,7 @@ struct inv_params {
 /* what a checked h2y_codelight_desc comes to (codelight_check, h2y_measure.hip) */
 struct codelight_plan {
     codelight_args a{};
-    int width = 0, height = 0;
+    int width = 0, height = 0, bit_depth = 0;
     int matrix = 0, form = UP_REPLICATE;
     bool sub = false;      /* 4:2:0: planes 1 and 2 come from the scratch */
     size_t plane_al = 0;   /* 4:2:0: the bytes from one upsampled plane to the next (256-byte aligned) */
@@ -199,12 +199,16 @@ struct ring_stage {
     }
     virtual int ready(h2y_ctx *, int) { return H2Y_OK; }  /* may the slot be submitted? */
     virtual int upload(h2y_ctx *, int) { return H2Y_OK; } /* on s_h2d, before the slot's ev_h2d */
+    /* STAGE_UNPACK only: what h2y_stream_input lends in the place of the slot's planes (its upload() then stands for ring_upload's
+     * copy), and, on the context's stream before the ring's producer, the planes written where that copy would have put them */
+    virtual void *lend(h2y_ctx *, int) { return nullptr; }
+    virtual int unpack(h2y_ctx *, int) { return H2Y_OK; }
     /* on the context's stream, on a forward ring's decoded planes: after the decode, before pic_stats and the conversion */
     virtual int decoded(h2y_ctx *, int) { return H2Y_OK; }
     virtual int run(h2y_ctx *ctx, int slot) = 0;          /* on the context's stream, after the frame was produced */
     virtual int download(h2y_ctx *, int) { return H2Y_OK; } /* the result, on s_d2h after the slot's ev_conv */
 };
-enum stage_id { STAGE_GAMUT, STAGE_TONEMAP, STAGE_LUT3D, STAGE_HLG, STAGE_ICTCP, STAGE_LIGHT, STAGE_LIGHTDIST, STAGE_CODELIGHT, STAGE_SCENESIG, STAGE_COMPARE, STAGE_SSIM, STAGE_DELTAE, STAGE_HISTOGRAM, STAGE_SCALE, STAGE_DITHER, STAGE_COUNT };
+enum stage_id { STAGE_UNPACK, STAGE_GAMUT, STAGE_TONEMAP, STAGE_LUT3D, STAGE_HLG, STAGE_ICTCP, STAGE_LIGHT, STAGE_LIGHTDIST, STAGE_CODELIGHT, STAGE_SCENESIG, STAGE_COMPARE, STAGE_SSIM, STAGE_DELTAE, STAGE_HISTOGRAM, STAGE_SCALE, STAGE_DITHER, STAGE_PACK, STAGE_COUNT };
 
 struct h2y_ctx {
     int device = 0;

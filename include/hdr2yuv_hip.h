@@ -1057,6 +1057,76 @@ int h2y_stream_dither(h2y_ctx *ctx, int dst_depth, int mode, int temporal, uint3
 int h2y_dither_stream_open(h2y_ctx *ctx, int width, int height, int chroma_format_idc, int src_depth, int dst_depth, int full_range, int gbr,
                            int mode, int temporal, uint32_t seed, uint32_t first_frame, int depth /* 2..16 slots */);
 
+/* ---- sample packings: byte and semi-planar frames (--dst_pack, --src_pack) ----------------------------------------------------------
+ * Every raw frame above is the reference's write_yuv() form: three planes of 16-bit little-endian words ("planar16").  Encoders and
+ * hardware codecs read other forms of the same samples; these are the project's own definitions of three of them, in integers.
+ * A frame is three planes P0, P1, P2 of u16 codes at bit depth D, M = 2^D - 1.  P0 is w x h; P1 and P2 are cw x ch with
+ * cw = w >> 1, ch = h >> 1 for 4:2:0 and cw = w, ch = h for 4:4:4 (h2y_scale_batch's layout: the planes one after the other).
+ * 4:2:2 is refused as everywhere.
+ *   0  H2Y_PACK_PLANAR16  every depth and format: the form above.  Packing and unpacking refuse it (H2Y_EINVAL); the command line
+ *                         reads it as "no packing".
+ *   1  H2Y_PACK_PLANAR8   D = 8, 4:2:0 or 4:4:4: P0, P1, P2, one byte a sample, rows without padding: w h + 2 cw ch bytes
+ *   2  H2Y_PACK_NV12      D = 8, 4:2:0: P0 as bytes, then ch rows of cw byte pairs (P1[i], P2[i]): w h + 2 cw ch bytes
+ *   3  H2Y_PACK_P010      D = 10..16, 4:2:0: P0 as little-endian u16 words, then ch rows of cw word pairs (P1[i], P2[i]), the sample
+ *                         in a word's high bits: 2 (w h + 2 cw ch) bytes
+ * Pack: the byte is min(v, M); P010's word is min(v, M) << (16 - D).  The library's own frames never exceed M; a caller's buffer
+ * may, and here such a code saturates.  Unpack: v = the byte; for P010 v = word >> (16 - D), the low 16 - D bits ignored (decoders
+ * differ in what they leave there).  So unpack(pack(x)) = min(x, M); pack(unpack(y)) = y for packings 1 and 2, and y with the low
+ * 16 - D bits of every word cleared for packing 3.
+ * As an ffmpeg -pix_fmt (the command line's banner): packing 1 is yuv420p or yuv444p, packing 2 nv12, packing 3 p010le, p012le or
+ * p016le at D = 10, 12, 16 and has no such name at the other depths; planar16 is yuv420p10le and the like. */
+enum { H2Y_PACK_PLANAR16 = 0, H2Y_PACK_PLANAR8 = 1, H2Y_PACK_NV12 = 2, H2Y_PACK_P010 = 3 };
+#define H2Y_PACK_FRAMES_PER_LAUNCH 64
+
+/* The bytes of one packed frame (the table's last column); 0 for packing 0, an unknown packing, a chroma format the packing does
+ * not take (4:2:2 among them) and sizes below 1.  The depth does not enter. */
+size_t h2y_pack_frame_bytes(int width, int height, int chroma_format_idc, int packing);
+
+/* One frame on the host: no device, no context; the CPU-testable twins of k_pack and k_unpack, compiled from the same per-sample
+ * lines.  src and dst must not overlap.  H2Y_EINVAL for a null pointer, sizes below 1 or of 2^28 pixels and more, packing 0 and
+ * every (chroma format, bit_depth, packing) the table does not list; H2Y_EUNSUPPORTED for 4:2:2. */
+int h2y_pack_frame(int width, int height, int chroma_format_idc, int bit_depth, int packing, const uint16_t *src, void *dst);
+int h2y_unpack_frame(int width, int height, int chroma_format_idc, int bit_depth, int packing, const void *src, uint16_t *dst);
+
+/* k_pack / k_unpack on n_frames device frames: d_dst[f] receives d_src[f] packed (unpacked).  The planar16 side is in
+ * h2y_scale_batch's layout; both frames start on 16-byte boundaries (the planes inside them need not: the kernels take no access
+ * wider than its address's alignment).  A frame's source and destination must not overlap; that is not checked.  Launches of up to
+ * H2Y_PACK_FRAMES_PER_LAUNCH frames (h2y_last_kernel_ms sums them, h2y_last_kernel_name "k_pack" / "k_unpack", the variant
+ * "k_pack<PLANAR8>", "<NV12>" or "<P010>"); synchronous.  The refusals of h2y_pack_frame, and H2Y_EINVAL for n_frames below 1, null
+ * or misaligned frames, while a batch is pending or a stream open. */
+int h2y_pack_batch(h2y_ctx *ctx, int width, int height, int chroma_format_idc, int bit_depth, int packing, int n_frames,
+                   const uint16_t *const *d_src, void *const *d_dst);
+int h2y_unpack_batch(h2y_ctx *ctx, int width, int height, int chroma_format_idc, int bit_depth, int packing, int n_frames,
+                     const void *const *d_src, uint16_t *const *d_dst);
+
+/* Arm an open ring that hands out a u16 .yuv frame, before its first input: a forward ring (plain, DPX, TIFF, EXR, code), the
+ * scale-only ring or the dither-only ring.  The ring's last stage, after h2y_stream_scale's and h2y_stream_dither's: k_pack packs
+ * the frame that would go down -- the conversion's, the scale stage's or the dither stage's, at that frame's depth D -- into a frame
+ * of the stage's own, which goes down and is what h2y_stream_output returns: the pointer's type stays, and on such a ring it points
+ * to h2y_pack_frame_bytes bytes.  H2Y_EINVAL for packing 0 or an unknown one, a packing the frame's depth or chroma format does not
+ * take, after the first input, on a ring armed already, and for h2y_stream_scale / h2y_stream_dither after this call;
+ * H2Y_EUNSUPPORTED on a ring armed with h2y_stream_compare / _histogram / _ssim / _deltae, as is arming any of those afterwards
+ * (compare or count the written file instead), on dst_matrix_coeffs 15, and on every ring whose output is no .yuv frame (inverse,
+ * compare-only, histogram-only, light-only). */
+int h2y_stream_pack(h2y_ctx *ctx, int packing);
+
+/* Arm an open ring whose h2y_stream_input lends u16 code planes, before its first input: the inverse rings, the planes rings
+ * (compare-only, histogram-only, scale-only, dither-only, h2y_codelight_stream_open) and the three code rings (h2y_pqcode_ /
+ * h2y_hlgcode_ / h2y_sdrcode_stream_open).  From then on h2y_stream_input lends one packed frame (h2y_pack_frame_bytes bytes) in
+ * planes[0], planes[1] = planes[2] = null, as the payload rings do; only those bytes go up, and k_unpack writes the planes where the
+ * upload would have put them, before the ring's producer and every stage: all that follows sees the same planes.  On the
+ * compare-only ring the reference h2y_stream_reference lends is packed the same way.  D is the ring's input depth.  H2Y_EINVAL for
+ * packing 0 or an unknown one, a packing the ring's input depth or chroma format does not take, H2Y_PACK_P010 on a compare-only ring
+ * (whose depth is unknown: h2y_stream_unpack_ex takes it), after the first input, on a ring armed already, and on rings whose input is not u16 code planes (float
+ * and half forward rings, DPX / TIFF / EXR rings); H2Y_EUNSUPPORTED on a forward ring opened on U16 planes (the reference's integer
+ * .yuv -> .yuv flow stays the reference's). */
+int h2y_stream_unpack(h2y_ctx *ctx, int packing);
+
+/* The same with the frames' bit depth given: what a compare-only ring, which does not know it, needs for H2Y_PACK_P010 (A and the
+ * reference are both shifted down by 16 - bit_depth, so the comparison sees codes of that depth).  bit_depth 0: the ring's own, as
+ * h2y_stream_unpack.  H2Y_EINVAL for a negative bit_depth and for one that differs from the depth a ring knows. */
+int h2y_stream_unpack_ex(h2y_ctx *ctx, int packing, int bit_depth);
+
 /* ---- conversion between colour primaries, in linear light, before the forward conversion (--gamut_convert 1) ---------------------
  * The reference parses --src_colour_primaries / --dst_colour_primaries and never converts between them: matrix_to_primaries() is an
  * empty function (convert.cpp:1991), and the two values only choose between the identity and the colour-difference branch of
@@ -1586,7 +1656,7 @@ int h2y_upsample_444_sited(h2y_ctx *ctx, int width, int height, int chroma_sampl
                            const uint16_t *d_src, uint16_t *d_dst);
 
 /* Timing of the last h2y_convert_batch*() (or h2y_inverse_*, h2y_dpx_decode_batch, h2y_tiff_decode_batch,
- * h2y_rgb_interleave_batch, h2y_exr_decode_batch, h2y_compare_batch, h2y_ssim_batch, h2y_light_batch, h2y_lightdist_batch, h2y_codelight_batch, h2y_scenesig_batch, h2y_codescenesig_batch, h2y_linearize_batch, h2y_hlg_linearize_batch, h2y_sdr_linearize_batch, h2y_scale_batch, h2y_gamut_batch, h2y_tonemap_batch, h2y_hlg_batch, h2y_ictcp_batch, h2y_dither_batch) call measured with HIP events on
+ * h2y_rgb_interleave_batch, h2y_exr_decode_batch, h2y_compare_batch, h2y_ssim_batch, h2y_light_batch, h2y_lightdist_batch, h2y_codelight_batch, h2y_scenesig_batch, h2y_codescenesig_batch, h2y_linearize_batch, h2y_hlg_linearize_batch, h2y_sdr_linearize_batch, h2y_scale_batch, h2y_gamut_batch, h2y_tonemap_batch, h2y_hlg_batch, h2y_ictcp_batch, h2y_dither_batch, h2y_pack_batch, h2y_unpack_batch) call measured with HIP events on
  * the stream the kernels ran on: total ms over the main kernels and how many
  * launches that covered. */
 int h2y_last_kernel_ms(const h2y_ctx *ctx, float *ms, int *launches);
@@ -1594,7 +1664,7 @@ int h2y_last_kernel_ms(const h2y_ctx *ctx, float *ms, int *launches);
 /* Name of the kernel those launches ran ("k_fused", "k_fused_t1", "k_fused_lut16",
  * "k_fused_narrow"; of the inverse entries "k_inverse", "k_inverse420", "k_inverse_batch", "k_inverse420_batch"; of
  * h2y_dpx_decode_batch "k_dpx_decode"; of h2y_tiff_decode_batch "k_tiff_decode", of h2y_rgb_interleave_batch
- * "k_rgb_interleave"; of h2y_exr_decode_batch "k_exr_decode"; of h2y_compare_batch "k_compare"; of h2y_scale_batch "k_scale"; of h2y_dither_batch "k_dither"; of h2y_gamut_batch "k_gamut"; of h2y_tonemap_batch "k_tonemap"; of h2y_hlg_batch "k_hlg"; of h2y_ictcp_batch "k_ictcp"; of h2y_codelight_batch "k_codelight"; of h2y_scenesig_batch "k_scenesig"; of h2y_codescenesig_batch "k_codescenesig"; of h2y_linearize_batch "k_linearize"; of h2y_hlg_linearize_batch "k_hlg_linearize"; of h2y_sdr_linearize_batch "k_sdr_linearize"): the name to
+ * "k_rgb_interleave"; of h2y_exr_decode_batch "k_exr_decode"; of h2y_compare_batch "k_compare"; of h2y_scale_batch "k_scale"; of h2y_dither_batch "k_dither"; of h2y_pack_batch "k_pack"; of h2y_unpack_batch "k_unpack"; of h2y_gamut_batch "k_gamut"; of h2y_tonemap_batch "k_tonemap"; of h2y_hlg_batch "k_hlg"; of h2y_ictcp_batch "k_ictcp"; of h2y_codelight_batch "k_codelight"; of h2y_scenesig_batch "k_scenesig"; of h2y_codescenesig_batch "k_codescenesig"; of h2y_linearize_batch "k_linearize"; of h2y_hlg_linearize_batch "k_hlg_linearize"; of h2y_sdr_linearize_batch "k_sdr_linearize"): the name to
  * look for in a rocprofv3 kernel trace. */
 const char *h2y_last_kernel_name(const h2y_ctx *ctx);
 /* The same with its template arguments and launch shape, e.g. "k_fused_t1<F32,420BOX,YCBCR,PQ_IDENT> groups=8 xcd=1";

@@ -222,6 +222,19 @@ Prints one line per figure, then one JSON line with all of them.
      kernel variant each conversion ran;
   4. frames/s from host memory of the .f32 ring (16-bit destination), unarmed and armed with h2y_stream_dither to 10 bits, and the
      unarmed ring with a 10-bit destination, three runs of each in turn.
+Prints one line per figure, then one JSON line with all of them.
+
+`streambench.py pack`: the sample packings (k_pack, k_unpack) on 4K frames, beside their yardsticks in the same job:
+  1. the kernel time of h2y_pack_batch and h2y_unpack_batch over 64 distinct device frames per call (HIP events, median of five after
+     a warm-up call) per packing: PLANAR8, NV12 and P010 (10 bits) in 4:2:0, PLANAR8 also in 4:4:4; the 3 bytes a sample (P010: 4) they
+     move over that time and their share of the 8 TB/s HBM peak; and NV12 and P010 at 3838 x 2158, where w h is no multiple of 16 and the
+     chroma block takes the kernels' narrow path (one element an access);
+  2. the yardsticks, timed the same way: h2y_dither_batch 16 -> 8 4:2:0 ordered (k_dither, 4 bytes a sample) and
+     h2y_tiff_decode_batch (k_tiff_decode, 12 B/pixel) -- same-shaped streaming passes that this change does not touch;
+  3. frames/s from host memory of the .f32 ring (16-bit destination) armed with h2y_stream_dither to 8 bits, without and with
+     h2y_stream_pack(PLANAR8) behind it, three runs of each in turn;
+  4. frames/s of the compare-only ring on 8-bit 4:2:0 frames, fed planar16 frames and, armed with h2y_stream_unpack(PLANAR8), the same
+     frames as bytes, three runs of each in turn.
 Prints one line per figure, then one JSON line with all of them."""
 import os
 import sys
@@ -2095,6 +2108,152 @@ def dither_main():
     print(json.dumps({"streambench_dither": res}), flush=True)
 
 
+def pack_main():
+    import json
+
+    import torch
+
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    from tiff_files import write_tiff
+
+    w, hh, nb, reps = 3840, 2160, 64, 5
+    n, nc = w * hh, (w // 2) * (hh // 2)
+    nf = int(os.environ.get("N", "60"))
+    depth = 3
+    rng = np.random.default_rng(41)
+    ctx = h.Context(0)
+    res = {"width": w, "height": hh, "frames_per_call": nb, "reps": reps, "ring_frames": nf, "ring_depth": depth, "hbm_peak_tbs": 8.0}
+
+    def timed(key, label, nbytes, call):
+        ks = []
+        for r in range(reps + 1):  # the first call warms up
+            call()
+            if r:
+                ks.append(ctx.last_kernel_ms()[0] / nb)
+        k_ms = float(np.median(ks))
+        tbs = nbytes / (k_ms * 1e-3) / 1e12
+        res[key] = dict(kernel_us_per_frame=round(k_ms * 1e3, 2), min_us=round(min(ks) * 1e3, 2), max_us=round(max(ks) * 1e3, 2),
+                        bytes_per_frame=nbytes, kernel_tbs=round(tbs, 2), hbm_peak_fraction=round(tbs / 8.0, 3), variant=ctx.last_kernel_variant())
+        print(f"{label:34s} {nb} frames per call: {k_ms*1e3:7.2f} us/frame ({min(ks)*1e3:.2f}..{max(ks)*1e3:.2f})  {nbytes/1e6:6.1f} MB/frame  "
+              f"{tbs:5.2f} TB/s = {tbs/8.0*100:4.1f} % of 8 TB/s", flush=True)
+
+    # 1. k_pack and k_unpack over 64 distinct frames on the device
+    for name, packing, chroma, D in (("planar8_420", h.PACK_PLANAR8, h.CHROMA_420, 8), ("planar8_444", h.PACK_PLANAR8, h.CHROMA_444, 8),
+                                     ("nv12", h.PACK_NV12, h.CHROMA_420, 8), ("p010", h.PACK_P010, h.CHROMA_420, 10)):
+        words = n + 2 * (nc if chroma == h.CHROMA_420 else n)
+        pbytes = h.pack_frame_bytes(w, hh, chroma, packing)
+        planar = [torch.randint(0, 1 << D, (words,), dtype=torch.int16, device="cuda") for _ in range(nb)]
+        packed = [torch.empty(pbytes, dtype=torch.uint8, device="cuda") for _ in range(nb)]
+        torch.cuda.synchronize()
+        timed("k_pack_" + name, "k_pack " + name, 2 * words + pbytes, lambda: ctx.pack_batch(w, hh, chroma, D, packing, planar, packed))
+        timed("k_unpack_" + name, "k_unpack " + name, 2 * words + pbytes, lambda: ctx.unpack_batch(w, hh, chroma, D, packing, packed, planar))
+        del planar, packed
+        torch.cuda.empty_cache()
+    # the narrow path: 3838 x 2158 has w h = 8282404, no multiple of 16, so the chroma block (a third of the samples) takes one
+    # element an access where the luma plane still takes vectors
+    w2, h2 = 3838, 2158
+    for name, packing, D in (("nv12", h.PACK_NV12, 8), ("p010", h.PACK_P010, 10)):
+        words = w2 * h2 + 2 * (w2 // 2) * (h2 // 2)
+        pbytes = h.pack_frame_bytes(w2, h2, h.CHROMA_420, packing)
+        planar = [torch.randint(0, 1 << D, (words + 8,), dtype=torch.int16, device="cuda") for _ in range(nb)]
+        packed = [torch.empty(pbytes + 16, dtype=torch.uint8, device="cuda") for _ in range(nb)]
+        torch.cuda.synchronize()
+        timed(f"k_pack_{name}_3838x2158", f"k_pack {name} 3838x2158 (narrow chroma)", 2 * words + pbytes,
+              lambda: ctx.pack_batch(w2, h2, h.CHROMA_420, D, packing, planar, packed))
+        timed(f"k_unpack_{name}_3838x2158", f"k_unpack {name} 3838x2158 (narrow chroma)", 2 * words + pbytes,
+              lambda: ctx.unpack_batch(w2, h2, h.CHROMA_420, D, packing, packed, planar))
+        del planar, packed
+        torch.cuda.empty_cache()
+
+    # 2. the yardsticks
+    words = n + 2 * nc
+    src = [torch.randint(-32768, 32768, (words,), dtype=torch.int16, device="cuda") for _ in range(nb)]
+    dst = [torch.empty(words, dtype=torch.int16, device="cuda") for _ in range(nb)]
+    torch.cuda.synchronize()
+    timed("k_dither_16_8_420_ordered", "k_dither 16_8_420_ordered", 4 * words, lambda: ctx.dither_batch(w, hh, h.CHROMA_420, 16, 8, 0, 0, 1, 1, 0, 0, src, dst))
+    del src, dst
+    torch.cuda.empty_cache()
+    tdata = write_tiff(rng.integers(0, 65536, (hh, w, 3), dtype=np.uint16))
+    tinfo, rows = h.parse_tiff(tdata)
+    tpay = np.frombuffer(b"".join(tdata[int(o):int(o) + int(tinfo.row_bytes)] for o in rows), np.uint8)
+    pays = [torch.from_numpy(tpay.copy()).cuda() for _ in range(nb)]
+    outs = [[torch.empty(n, dtype=torch.int16, device="cuda") for _ in range(3)] for _ in range(nb)]
+    torch.cuda.synchronize()
+    timed("k_tiff_decode", "k_tiff_decode", 12 * n, lambda: ctx.tiff_decode_batch(tinfo, 0, pays, outs))
+    del pays, outs
+    torch.cuda.empty_cache()
+
+    def drive(fill):
+        """nf frames through the ring ctx has open; seconds a frame"""
+        inflight = 0
+        t0 = time.perf_counter()
+        for _ in range(nf):
+            fill(ctx.stream_input())
+            ctx.stream_submit()
+            inflight += 1
+            if inflight == depth - 1:
+                ctx.stream_output()
+                inflight -= 1
+        while inflight:
+            ctx.stream_output()
+            inflight -= 1
+        dt = (time.perf_counter() - t0) / nf
+        ctx.stream_close()
+        return dt
+
+    # 3. the .f32 ring from host memory, dithered to 8 bits
+    d16 = h.make_desc(w, hh, dst_depth=16, dst_transfer=1, dst_matrix=h.MATRIX_BT709, resampler=1)
+    planes = [rng.random(n, dtype=np.float32) for _ in range(3)]
+
+    def fill_planes(slot):
+        for c in range(3):
+            slot[c][:] = planes[c]
+
+    def f32_ring(pack):
+        ctx.stream_open(d16, depth)
+        ctx.stream_dither(8, 1, 0, 0, 0)
+        if pack:
+            ctx.stream_pack(h.PACK_PLANAR8)
+        return drive(fill_planes)
+
+    f32_ring(False)  # warm-up
+    runs = {"dither_to_8": [], "dither_to_8_pack_planar8": []}
+    for _ in range(3):
+        runs["dither_to_8"].append(f32_ring(False))
+        runs["dither_to_8_pack_planar8"].append(f32_ring(True))
+    res["f32_ring"] = {k: dict(fps=round(1 / float(np.median(v)), 1), ms=[round(x * 1e3, 2) for x in v]) for k, v in runs.items()}
+    print("f32 ring from host memory: " + "   ".join(f"{k} {1/float(np.median(v)):6.1f} frames/s" for k, v in runs.items()), flush=True)
+
+    # 4. the compare-only ring at 8 bits
+    a16 = rng.integers(16, 236, words, dtype=np.uint16)
+    b16 = np.clip(a16.astype(np.int32) + rng.integers(-2, 3, words), 0, 255).astype(np.uint16)
+    a8, b8 = a16.astype(np.uint8), b16.astype(np.uint8)
+
+    def cmp_ring(unpack):
+        ctx.compare_stream_open(w, hh, h.CHROMA_420, 0, depth)
+        if unpack:
+            ctx.stream_unpack(h.PACK_PLANAR8)
+
+        def fill(slot):
+            if unpack:
+                slot[0][:] = a8
+                ctx.stream_reference()[:] = b8
+            else:
+                slot[0][:], slot[1][:], slot[2][:] = a16[:n], a16[n:n + nc], a16[n + nc:]
+                ctx.stream_reference()[:] = b16
+        return drive(fill)
+
+    cmp_ring(False)  # warm-up
+    runs = {"planar16": [], "unpack_planar8": []}
+    for _ in range(3):
+        runs["planar16"].append(cmp_ring(False))
+        runs["unpack_planar8"].append(cmp_ring(True))
+    res["compare_only_ring_8bit"] = {k: dict(fps=round(1 / float(np.median(v)), 1), ms=[round(x * 1e3, 2) for x in v]) for k, v in runs.items()}
+    print("compare-only ring at 8 bits from host memory: " + "   ".join(f"{k} {1/float(np.median(v)):6.1f} frames/s" for k, v in runs.items()), flush=True)
+    ctx.close()
+    print(json.dumps({"streambench_pack": res}), flush=True)
+
+
 def gamut_main():
     import json
 
@@ -2740,6 +2899,8 @@ if __name__ == "__main__":
         scale_main()
     elif sys.argv[1:] == ["dither"]:
         dither_main()
+    elif sys.argv[1:] == ["pack"]:
+        pack_main()
     elif sys.argv[1:] == ["inverse"]:
         inverse_main()
     elif sys.argv[1:] == ["dpx"]:
