@@ -37,6 +37,7 @@ EXPORTS = [
     "h2y_compare_batch", "h2y_stream_compare", "h2y_stream_reference", "h2y_stream_compare_result", "h2y_compare_stream_open",
     "h2y_histogram_batch", "h2y_stream_histogram", "h2y_stream_histogram_ex", "h2y_stream_histogram_result",
     "h2y_histogram_stream_open", "h2y_ssim_batch", "h2y_stream_ssim", "h2y_stream_ssim_result",
+    "h2y_regions_host", "h2y_regions_batch", "h2y_stream_regions", "h2y_stream_regions_result",
     "h2y_light_batch", "h2y_stream_light", "h2y_stream_light_result",
     "h2y_lightdist_batch", "h2y_stream_lightdist", "h2y_stream_lightdist_result", "h2y_lightdist_json",
     "h2y_codelight_batch", "h2y_codelight_stream_open",
@@ -61,6 +62,7 @@ EXPORTS = [
 COMPARE_FRAMES_PER_LAUNCH = 64
 HISTOGRAM_FRAMES_PER_LAUNCH = 64
 SSIM_FRAMES_PER_LAUNCH = 64
+REGIONS_FRAMES_PER_LAUNCH = 64
 LIGHT_FRAMES_PER_LAUNCH = 64
 LIGHTDIST_FRAMES_PER_LAUNCH = 64
 LIGHTDIST_BINS = 8706  # bins of max(L_G, L_B, L_R) by its binary32 bits: below 2^-17, 512 per binade up to 1, and 1 itself
@@ -219,6 +221,24 @@ class H2YSsimStats(C.Structure):
 
     def __repr__(self):
         return f"H2YSsimStats({self.as_dict()})"
+
+
+class H2YRegionsStats(C.Structure):
+    """h2y_regions_stats: per plane and class (0 flat, 1 busy) the 8x8 tiles, their samples, sum (a - b)^2 and sum |a - b|; per
+    plane the samples above (below) the reference's local range, by how much in all and at most; flat_var and radius as given."""
+
+    _fields_ = [("tiles", (C.c_uint64 * 2) * 3), ("samples", (C.c_uint64 * 2) * 3), ("sse", (C.c_uint64 * 2) * 3), ("sad", (C.c_uint64 * 2) * 3),
+                ("over", C.c_uint64 * 3), ("over_sum", C.c_uint64 * 3), ("under", C.c_uint64 * 3), ("under_sum", C.c_uint64 * 3),
+                ("over_max", C.c_uint32 * 3), ("under_max", C.c_uint32 * 3), ("flat_var", C.c_uint32), ("radius", C.c_uint32)]
+
+    def as_dict(self):
+        """Every field as plain ints: [plane][class] lists, [plane] lists, and the two settings."""
+        def plain(v):
+            return v if isinstance(v, int) else [plain(x) for x in v]
+        return {k: plain(getattr(self, k)) for k, _ in self._fields_}
+
+    def __repr__(self):
+        return f"H2YRegionsStats({self.as_dict()})"
 
 
 class H2YLightStats(C.Structure):
@@ -496,6 +516,15 @@ def load_library():
     L.h2y_stream_ssim.restype = C.c_int
     L.h2y_stream_ssim_result.argtypes = [C.c_void_p, C.POINTER(H2YSsimStats)]
     L.h2y_stream_ssim_result.restype = C.c_int
+    L.h2y_regions_host.argtypes = [C.c_int] * 3 + [C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(H2YRegionsStats)]
+    L.h2y_regions_host.restype = C.c_int
+    L.h2y_regions_batch.argtypes = [C.c_void_p] + [C.c_int] * 3 + [C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                    C.POINTER(H2YRegionsStats)]
+    L.h2y_regions_batch.restype = C.c_int
+    L.h2y_stream_regions.argtypes = [C.c_void_p, C.c_uint32, C.c_int]
+    L.h2y_stream_regions.restype = C.c_int
+    L.h2y_stream_regions_result.argtypes = [C.c_void_p, C.POINTER(H2YRegionsStats)]
+    L.h2y_stream_regions_result.restype = C.c_int
     L.h2y_light_batch.argtypes = [C.c_void_p, C.POINTER(H2YDesc), C.c_int, C.POINTER(C.c_void_p), C.POINTER(H2YLightStats)]
     L.h2y_light_batch.restype = C.c_int
     L.h2y_stream_light.argtypes = [C.c_void_p]
@@ -775,6 +804,23 @@ def dither_offsets(mode: int, shift: int, temporal: int, seed: int, frame: int, 
     if rc != H2Y_OK:
         raise H2YError(rc, (lib.h2y_last_error(None) or b"").decode())
     return t
+
+
+def regions_host(width: int, height: int, chroma: int, flat_var: int, radius: int, a, b) -> H2YRegionsStats:
+    """h2y_regions_host (host only, no device): the figures of frame a against frame b, each three u16 planes one after the other."""
+    lib = load_library()
+    fa = None if a is None else np.ascontiguousarray(a, dtype=np.uint16).reshape(-1)
+    fb = None if b is None else np.ascontiguousarray(b, dtype=np.uint16).reshape(-1)
+    if width >= 1 and height >= 1 and chroma in (CHROMA_420, CHROMA_444):
+        for f in (fa, fb):
+            if f is not None and f.size != _frame_samples(width, height, chroma):
+                raise ValueError("a frame does not hold width x height samples and its two chroma planes")
+    st = H2YRegionsStats()
+    rc = lib.h2y_regions_host(width, height, chroma, flat_var, radius, None if fa is None else fa.ctypes.data,
+                              None if fb is None else fb.ctypes.data, C.byref(st))
+    if rc != H2Y_OK:
+        raise H2YError(rc, (lib.h2y_last_error(None) or b"").decode())
+    return st
 
 
 def pack_frame_bytes(width: int, height: int, chroma: int, packing: int) -> int:
@@ -1289,6 +1335,18 @@ class Context:
         self._check(self.lib.h2y_ssim_batch(self.h, width, height, chroma, bit_depth, n, pa, pb, out))
         return list(out[:n])
 
+    def regions_batch(self, width, height, chroma, flat_var, radius, frames_a, frames_b):
+        """k_regions on device frame pairs (tensors or pointers, each frame's planes contiguous from a 16-byte aligned base):
+        a list of H2YRegionsStats, one per pair."""
+        n = len(frames_a)
+        if len(frames_b) != n:
+            raise ValueError("frames_a and frames_b differ in length")
+        pa = (C.c_void_p * max(n, 1))(*[self._ptr(x) for x in frames_a])
+        pb = (C.c_void_p * max(n, 1))(*[self._ptr(x) for x in frames_b])
+        out = (H2YRegionsStats * max(n, 1))()
+        self._check(self.lib.h2y_regions_batch(self.h, width, height, chroma, flat_var, radius, n, pa, pb, out))
+        return list(out[:n])
+
     def light_batch(self, d: H2YDesc, frames_in):
         """k_light on device frames (frames_in[f] = three device planes G, B, R, 16-byte aligned): a list of H2YLightStats, one
         per frame, with the floor and ceiling the conversion of d takes for each."""
@@ -1702,6 +1760,16 @@ class Context:
     def stream_ssim(self, bit_depth=-1) -> None:
         """Arm a compare-armed ring for SSIM too (bit_depth -1: the ring's own; a compare-only ring needs it given)."""
         self._check(self.lib.h2y_stream_ssim(self.h, bit_depth))
+
+    def stream_regions(self, flat_var, radius=1) -> None:
+        """Arm a compare-armed ring to measure flat and busy areas, over- and undershoot too (h2y_stream_regions)."""
+        self._check(self.lib.h2y_stream_regions(self.h, flat_var, radius))
+
+    def stream_regions_result(self) -> H2YRegionsStats:
+        """The H2YRegionsStats of the frame stream_output returned last."""
+        st = H2YRegionsStats()
+        self._check(self.lib.h2y_stream_regions_result(self.h, C.byref(st)))
+        return st
 
     def stream_deltae(self, d: H2YCodelightDesc, threshold=1.0) -> None:
         """Arm a compare-armed ring for Delta E ITP too: d describes the ring's frames as PQ code planes."""

@@ -36,6 +36,16 @@
  * --ssim 1 (an addition: the "SNR, etc." hdr2yuv.cpp:826 leaves a TODO): SSIM of every compared frame beside its PSNR, on the
  *             frames the comparison reads (8x8 windows at a stride of 4 on code values, include/hdr2yuv_hip.h).  Refused (exit 1)
  *             without a comparison, for 4:2:2 frames and for a plane under 8x8 samples.
+ * --regions 1 [--regions_flat_var V] [--regions_radius R] (an addition: "measure undershoot and overshoot" and "measure PSNR on flat
+ *             areas separate from busy areas" of the reference's NOTES): of every compared frame, on the frames the comparison reads,
+ *             the PSNR of its flat and of its busy 8x8 tiles -- a tile of the reference is flat when its variance is at most V squared
+ *             code values -- and the samples that lie above (below) the reference's largest (smallest) sample within R samples
+ *             (include/hdr2yuv_hip.h, h2y_regions_stats).  R is 1..4, 1 by default; V is 4 x 4^(d - 8) by default at the compared
+ *             frames' bit depth d (a standard deviation of two 8-bit steps: a choice, not tuned on programmes; the report's flat_share
+ *             is there to tune it by).  Accepted wherever a comparison runs (--ref_filename with or without --dst_filename,
+ *             --compare_only 1), beside --ssim, --delta_e and --histogram, for any --gpus; the exit status does not change.  Refused
+ *             (exit 1, also under --dry_run): a value other than 0 or 1, --regions_flat_var or --regions_radius without --regions 1, R
+ *             outside 1..4, V negative or above 2^32 - 1, no comparison in the run, 4:2:2 frames.
  * --histogram FILE [--histogram_bits B] [--check_range 1] [--histogram_only 1] (additions: the "hist" and "check video range" the
  *             reference leaves a TODO at hdr2yuv.cpp:658 and :797): every frame the run produces is counted on the device -- the .yuv
  *             frames (destination depth and range, Y,Cb,Cr limits), the G,B,R planes of the inverse flow (destination depth, source
@@ -300,6 +310,12 @@ struct cli_args {
     /* --ssim 1: SSIM beside the comparison */
     int ssim = 0;
     bool ssim_given = false;
+    /* --regions 1: flat and busy areas, over- and undershoot beside the comparison; --regions_flat_var (-1: the default of the compared
+     * frames' depth, resolved by cli_resolve_regions), --regions_radius */
+    int regions = 0, regions_radius = 1;
+    long long regions_flat_var_arg = -1;
+    uint32_t regions_flat_var = 0;
+    bool regions_given = false, regions_flat_var_given = false, regions_radius_given = false;
     /* --content_light 1: MaxCLL / MaxFALL of the forward flow */
     int light = 0;
     bool light_given = false;
@@ -442,7 +458,9 @@ static inline void cli_help()
            "  additional: [--synthetic SEEDFRAME] [--device D] [--gpus N [--devices d0,d1,..]] [--dry_run 1]\n"
            "  compare: [--ref_filename R.yuv|R.rgb [--sigma_compare S]] (the output against R, frame by frame; without\n"
            "  --dst_filename nothing is written), [--compare_only 1] (--src_filename against R, no conversion), [--ssim 1] (SSIM\n"
-           "  beside the PSNR), [--delta_e 1 [--delta_e_threshold X] [--delta_e_limit Y]] (Delta E ITP, BT.2124, of compared PQ BT.2020\n"
+           "  beside the PSNR), [--regions 1 [--regions_flat_var V] [--regions_radius R]] (PSNR of flat and of busy 8x8 tiles, a tile\n"
+           "  being flat up to a variance of V squared codes; samples beyond the reference's range within R samples, 1..4),\n"
+           "  [--delta_e 1 [--delta_e_threshold X] [--delta_e_limit Y]] (Delta E ITP, BT.2124, of compared PQ BT.2020\n"
            "  frames: per frame the mean, the max and the pixels above X, 1 by default; exit status 5 when a frame's mean exceeds Y)\n"
            "  histogram: [--histogram FILE [--histogram_bits B] [--check_range 1]] (code values of every frame the run produces,\n"
            "  totals into FILE; exit status 4 on a sample outside the legal range), [--histogram_only 1] (--src_filename, no conversion)\n"
@@ -523,6 +541,9 @@ static inline void cli_parse(cli_args &a, int argc, char **argv)
         else if (is("--sigma_compare")) { a.sigma = atoi(val()); a.sigma_given = true; }
         else if (is("--compare_only")) a.compare_only = atoi(val());
         else if (is("--ssim")) { a.ssim = atoi(val()); a.ssim_given = true; }
+        else if (is("--regions")) { a.regions = atoi(val()); a.regions_given = true; }
+        else if (is("--regions_flat_var")) { a.regions_flat_var_arg = strtoll(val(), nullptr, 10); a.regions_flat_var_given = true; }
+        else if (is("--regions_radius")) { a.regions_radius = atoi(val()); a.regions_radius_given = true; }
         else if (is("--delta_e")) { a.delta_e = atoi(val()); a.delta_e_given = true; }
         else if (is("--delta_e_threshold")) { a.delta_e_threshold = strtof(val(), nullptr); a.delta_e_threshold_given = true; }
         else if (is("--delta_e_limit")) { a.delta_e_limit = strtod(val(), nullptr); a.delta_e_limit_given = true; }
@@ -731,6 +752,7 @@ static inline int cli_resolve_histogram(cli_args &a)
  * errors */
 static inline int cli_resolve_convert(cli_args &a);
 static inline int cli_resolve_ssim(cli_args &a);
+static inline int cli_resolve_regions(cli_args &a);
 static inline int cli_resolve_light(cli_args &a);
 static inline int cli_resolve_dynmeta(cli_args &a);
 static inline int cli_resolve_scale_only(cli_args &a);
@@ -763,7 +785,9 @@ static inline int cli_resolve(cli_args &a)
         printf("WARNING: --compare_only 1 --src_pack p010 needs --src_bit_depth: the samples lie in the words' high bits\n");
         return 1;
     }
-    const int arg_errors = cli_resolve_flows(a);
+    int arg_errors = cli_resolve_flows(a);
+    /* (after every flow's resolver: whichever flow runs, the flags are refused where it compares nothing) */
+    if (a.regions_given || a.regions_flat_var_given || a.regions_radius_given) arg_errors += cli_resolve_regions(a);
     /* last: the packings are those of the files the resolved run reads and writes */
     return arg_errors || !(a.dst_pack_name || a.src_pack_name) ? arg_errors : cli_resolve_pack(a);
 }
@@ -2155,6 +2179,47 @@ static inline int cli_resolve_ssim(cli_args &a)
                a.out.height, chroma);
         return 1;
     }
+    return 0;
+}
+
+/* --regions: valid wherever a comparison runs, on frames of 4:2:0 or 4:4:4; resolves V's default; returns the number of argument
+ * errors */
+static inline int cli_resolve_regions(cli_args &a)
+{
+    printf("regions: %d\n", a.regions);
+    if (a.regions != 0 && a.regions != 1) {
+        printf("WARNING: regions(%d) not 0 or 1\n", a.regions);
+        a.regions = 0;
+        return 1;
+    }
+    if (!a.regions) {
+        if (a.regions_flat_var_given || a.regions_radius_given) {
+            printf("WARNING: --regions_flat_var and --regions_radius need --regions 1\n");
+            return 1;
+        }
+        return 0;
+    }
+    int arg_errors = 0;
+    if (a.regions_radius < 1 || a.regions_radius > 4) { printf("WARNING: regions_radius(%d) outside range [1,4]\n", a.regions_radius); arg_errors++; }
+    if (a.regions_flat_var_given && (a.regions_flat_var_arg < 0 || a.regions_flat_var_arg > 4294967295ll)) {
+        printf("WARNING: regions_flat_var(%lld) outside range [0,4294967295]\n", a.regions_flat_var_arg);
+        arg_errors++;
+    }
+    const bool compares = a.ref && !a.hist_only && !a.scale_only && !a.light_only && !a.dither_only;
+    if (!compares) {
+        printf("WARNING: --regions 1 needs a comparison: --ref_filename R (with or without --dst_filename, or with --compare_only 1)\n");
+        return arg_errors + 1;
+    }
+    const bool yuv = a.compare_only ? a.in_type == CLI_IN_YUV : a.out_type == CLI_OUT_YUV;
+    const int chroma = yuv ? a.out.chroma_format_idc : H2Y_CHROMA_444;
+    if (chroma != H2Y_CHROMA_420 && chroma != H2Y_CHROMA_444) {
+        printf("WARNING: --regions 1 compares 4:2:0 or 4:4:4 frames, not chroma_format_idc %d\n", chroma);
+        return arg_errors + 1;
+    }
+    if (arg_errors) return arg_errors;
+    const int d = a.out.bit_depth < 8 ? 8 : a.out.bit_depth > 16 ? 16 : a.out.bit_depth; /* (a depth outside 8..16 is refused by its flow) */
+    a.regions_flat_var = a.regions_flat_var_given ? (uint32_t)a.regions_flat_var_arg : 4u << (2 * (d - 8));
+    printf("regions_flat_var: %u%s\nregions_radius: %d\n", a.regions_flat_var, a.regions_flat_var_given ? "" : " (default)", a.regions_radius);
     return 0;
 }
 

@@ -56,6 +56,15 @@
  *   ssim summary frames <N> <P0> <m> <P1> <m> <P2> <m> all <m> db ...     the means over frames (summed in frame order), dB of them
  *   ssim worst frame <k> all <v>                                          the lowest all, the first such frame on ties
  *
+ * Flat and busy areas, over- and undershoot (--regions 1 [--regions_flat_var V] [--regions_radius R] beside a comparison;
+ * h2y_cli_args.h): each GPU thread arms its ring for them too (h2y_stream_regions) and keeps the figures of frame k by its index; the
+ * report follows the SSIM report, so it is the same for any --gpus.  Planes and PSNR as in the comparison's report, of a class's
+ * samples and sse ("-" for a class of no samples); flat_share = flat samples / samples "%.6f"; *_mean = sum / count "%.4f" ("-" for
+ * a count of 0); the summary's figures come from the sums over the run:
+ *   regions frame <k> flat_share <P0> <s> <P1> <s> <P2> <s> psnr_flat <P0> <v> .. psnr_busy <P0> <v> .. over <c0> <c1> <c2> over_max <m0> <m1> <m2> under <c0> <c1> <c2> under_max <m0> <m1> <m2>
+ *   regions summary frames <N> flat_share .. global_psnr_flat .. global_psnr_busy .. over .. over_mean <P0> <x> .. over_max .. under .. under_mean .. under_max ..
+ * The exit status is unchanged: the figures gate nothing.
+ *
  * Delta E ITP (--delta_e 1 [--delta_e_threshold X] [--delta_e_limit Y] beside a comparison of PQ code frames; h2y_cli_args.h): each GPU
  * thread sets its context's inverse chroma siting where the frames' siting flag says 2 and arms its ring for Delta E too
  * (h2y_stream_deltae) and keeps the figures of frame k by its index; the report follows the SSIM report, so it is the same for any
@@ -237,6 +246,7 @@ static bool read_ref(FILE *f, bool rgb, size_t plane_bytes, size_t frame_bytes, 
 struct results {
     std::vector<h2y_compare_stats> compare;
     std::vector<h2y_ssim_stats> ssim;
+    std::vector<h2y_regions_stats> regions;
     std::vector<h2y_deltae_stats> deltae;
     std::vector<h2y_light_stats> light;
     std::vector<h2y_lightdist_stats> lightdist;
@@ -248,7 +258,7 @@ struct results {
     std::vector<uint64_t> total;                   /* per GPU thread: its sums */
     size_t nbins = 0;
     results(const cli_args &a, long frames)
-        : compare(a.ref ? (size_t)frames : 0), ssim(a.ssim ? (size_t)frames : 0), deltae(a.delta_e ? (size_t)frames : 0), light(a.light ? (size_t)frames : 0),
+        : compare(a.ref ? (size_t)frames : 0), ssim(a.ssim ? (size_t)frames : 0), regions(a.regions ? (size_t)frames : 0), deltae(a.delta_e ? (size_t)frames : 0), light(a.light ? (size_t)frames : 0),
           lightdist(a.dynmeta ? (size_t)frames : 0), scenesig(a.scene_detect == 1 ? (size_t)frames : 0),
           dist_bins(a.scenes() ? (size_t)frames * H2Y_LIGHTDIST_BINS : 0), hist(a.hist ? (size_t)frames : 0), occupied(hist.size())
     {
@@ -262,6 +272,7 @@ struct results {
     {
         if (a.ref && h2y_stream_compare_result(ctx, &compare[k])) return false;
         if (a.ssim && h2y_stream_ssim_result(ctx, &ssim[k])) return false;
+        if (a.regions && h2y_stream_regions_result(ctx, &regions[k])) return false;
         if (a.delta_e && h2y_stream_deltae_result(ctx, &deltae[k])) return false;
         if (a.hist) {
             uint32_t *b = &bins[(size_t)r * 3 * nbins];
@@ -437,7 +448,7 @@ static flow forward_flow(const job &j)
                                           : h2y_stream_open(ctx, &j.d, kRingDepth);
     };
     f.arm = [&a](h2y_ctx *ctx, long first) {
-        return (a.ref && h2y_stream_compare(ctx, a.sigma, a.dst ? 1 : 0)) || (a.ssim && h2y_stream_ssim(ctx, -1)) ||
+        return (a.ref && h2y_stream_compare(ctx, a.sigma, a.dst ? 1 : 0)) || (a.ssim && h2y_stream_ssim(ctx, -1)) || (a.regions && h2y_stream_regions(ctx, a.regions_flat_var, a.regions_radius)) ||
                (a.delta_e && h2y_stream_deltae(ctx, &a.de, a.delta_e_threshold)) ||
                (a.hist && h2y_stream_histogram(ctx, a.hist_bits)) || (a.light && h2y_stream_light(ctx)) ||
                (a.dynmeta && h2y_stream_lightdist(ctx)) || (a.scene_detect == 1 && h2y_stream_scenesig(ctx)) ||
@@ -535,7 +546,7 @@ static flow inverse_flow(const job &j)
                                                                                      a.out.bit_depth, a.resampler, kRingDepth), a, ctx);
     };
     f.arm = [&a](h2y_ctx *ctx, long) {
-        return (a.ref && h2y_stream_compare(ctx, a.sigma, a.dst ? 1 : 0)) || (a.ssim && h2y_stream_ssim(ctx, -1)) ||
+        return (a.ref && h2y_stream_compare(ctx, a.sigma, a.dst ? 1 : 0)) || (a.ssim && h2y_stream_ssim(ctx, -1)) || (a.regions && h2y_stream_regions(ctx, a.regions_flat_var, a.regions_radius)) ||
                (a.hist && h2y_stream_histogram(ctx, a.hist_bits));
     };
     f.src_frame_bytes = j.in_frame_bytes;
@@ -586,7 +597,7 @@ static flow compare_flow(const job &j)
         return opened(h2y_compare_stream_open(ctx, a.in.width, a.in.height, a.in.chroma_format_idc, a.sigma, kRingDepth), a, ctx);
     };
     f.arm = [&a](h2y_ctx *ctx, long) {
-        return (a.ssim && h2y_stream_ssim(ctx, a.in.bit_depth)) || (a.delta_e && h2y_stream_deltae(ctx, &a.de, a.delta_e_threshold)) ||
+        return (a.ssim && h2y_stream_ssim(ctx, a.in.bit_depth)) || (a.regions && h2y_stream_regions(ctx, a.regions_flat_var, a.regions_radius)) || (a.delta_e && h2y_stream_deltae(ctx, &a.de, a.delta_e_threshold)) ||
                (a.hist && h2y_stream_histogram_ex(ctx, a.hist_bits, a.hist_depth, a.hist_full, a.hist_gbr));
     };
     return f;
@@ -787,6 +798,58 @@ static void ssim_report(bool yuv, const std::vector<h2y_ssim_stats> &st)
     printf("ssim summary frames %zu", st.size());
     line(mean, mean_all / (double)st.size());
     printf("ssim worst frame %zu all %.6f\n", worst, st[worst].all);
+}
+
+/* the regions report of the header comment */
+static void regions_report(bool yuv, int bit_depth, const std::vector<h2y_regions_stats> &st)
+{
+    static const char *const kYuv[3] = {"Y", "Cb", "Cr"}, *const kRgb[3] = {"G", "B", "R"};
+    const char *const *name = yuv ? kYuv : kRgb;
+    const uint64_t maxv = (1ull << bit_depth) - 1;
+    auto ratio = [](uint64_t num, uint64_t den, const char *fmt) -> std::string {
+        if (!den) return "-";
+        char buf[64];
+        snprintf(buf, sizeof buf, fmt, (double)num / (double)den);
+        return buf;
+    };
+    auto triple = [](const char *key, const uint64_t (&v)[3]) {
+        printf(" %s %llu %llu %llu", key, (unsigned long long)v[0], (unsigned long long)v[1], (unsigned long long)v[2]);
+    };
+    /* flat_share and the two PSNRs of one set of per-class sums */
+    auto classes = [&](const uint64_t (&n)[3][2], const uint64_t (&sse)[3][2], const char *flat, const char *busy) {
+        printf(" flat_share");
+        for (int p = 0; p < 3; p++) printf(" %s %s", name[p], ratio(n[p][0], n[p][0] + n[p][1], "%.6f").c_str());
+        for (int c = 0; c < 2; c++) {
+            printf(" %s", c ? busy : flat);
+            for (int p = 0; p < 3; p++) printf(" %s %s", name[p], n[p][c] ? psnr_str(maxv, n[p][c], sse[p][c]).c_str() : "-");
+        }
+    };
+    h2y_regions_stats t{};
+    for (size_t k = 0; k < st.size(); k++) {
+        const h2y_regions_stats &s = st[k];
+        printf("regions frame %zu", k);
+        classes(s.samples, s.sse, "psnr_flat", "psnr_busy");
+        triple("over", s.over);
+        printf(" over_max %u %u %u", s.over_max[0], s.over_max[1], s.over_max[2]);
+        triple("under", s.under);
+        printf(" under_max %u %u %u\n", s.under_max[0], s.under_max[1], s.under_max[2]);
+        for (int p = 0; p < 3; p++) {
+            for (int c = 0; c < 2; c++) t.samples[p][c] += s.samples[p][c], t.sse[p][c] += s.sse[p][c];
+            t.over[p] += s.over[p], t.over_sum[p] += s.over_sum[p], t.under[p] += s.under[p], t.under_sum[p] += s.under_sum[p];
+            t.over_max[p] = std::max(t.over_max[p], s.over_max[p]), t.under_max[p] = std::max(t.under_max[p], s.under_max[p]);
+        }
+    }
+    if (st.empty()) return;
+    printf("regions summary frames %zu", st.size());
+    classes(t.samples, t.sse, "global_psnr_flat", "global_psnr_busy");
+    triple("over", t.over);
+    printf(" over_mean");
+    for (int p = 0; p < 3; p++) printf(" %s %s", name[p], ratio(t.over_sum[p], t.over[p], "%.4f").c_str());
+    printf(" over_max %u %u %u", t.over_max[0], t.over_max[1], t.over_max[2]);
+    triple("under", t.under);
+    printf(" under_mean");
+    for (int p = 0; p < 3; p++) printf(" %s %s", name[p], ratio(t.under_sum[p], t.under[p], "%.4f").c_str());
+    printf(" under_max %u %u %u\n", t.under_max[0], t.under_max[1], t.under_max[2]);
 }
 
 /* the Delta E report of the header comment; returns the exit status (5: --delta_e_limit given and a frame's mean above it) */
@@ -1112,6 +1175,7 @@ int main(int argc, char **argv)
     const bool compared = !rc && a.ref;
     if (compared) rc = compare_report(a, cmp_yuv, a.out.bit_depth, res.compare);
     if (compared && a.ssim) ssim_report(cmp_yuv, res.ssim);
+    if (compared && a.regions) regions_report(cmp_yuv, a.out.bit_depth, res.regions);
     if ((!rc || rc == 3) && a.hist) {
         const int hrc = histogram_report(a, res.hist, res.occupied, res.histogram_total());
         if (hrc == 1 || !rc) rc = hrc;

@@ -278,6 +278,8 @@ void h2y_ctx_destroy(h2y_ctx *ctx)
     (void)hipFree(ctx->d_hist);
     (void)hipFree(ctx->d_ssim_part);
     (void)hipFree(ctx->d_ssim_stats);
+    (void)hipFree(ctx->d_regions_part);
+    (void)hipFree(ctx->d_regions_stats);
     (void)hipFree(ctx->d_light_as);
     (void)hipFree(ctx->d_light_acc);
     (void)hipFree(ctx->d_lightdist);

@@ -332,6 +332,26 @@ int h2y_ssim_grid(int n_cu, const ssim_geom &g, int n_frames);
 hipError_t h2y_launch_ssim(int grid, hipStream_t st, const ssim_geom &g, const cmp_frame *frames, int n_frames, int64_t *partials,
                            h2y_ssim_stats *stats);
 
+/* k_regions and k_regions_sum (h2y_regions.hip): the error of flat and of busy 8x8 tiles, and over- and undershoot, of two frames of
+ * u16 planes, per plane, as exact integer sums */
+struct regions_geom {
+    uint32_t pw[3], ph[3];        /* plane width and height */
+    uint32_t a_off[3], b_off[3];  /* plane start in samples from the frame base, per side */
+    uint32_t strips[3], units[3]; /* k_regions' strips and units (strips x segments) per frame and plane */
+    uint32_t flat_var, radius;    /* a tile is flat when act <= flat_var x n x n; the window's radius, 1..4 */
+};
+struct regions_partial { /* one k_regions unit: every tile's sums, and the flat tiles' */
+    uint64_t sse_all, sse_flat, sad_all, sad_flat, over_sum, under_sum;
+    uint32_t tiles_all, tiles_flat, samples_all, samples_flat, over, under, over_max, under_max;
+};
+struct h2y_regions_stats;
+uint32_t h2y_regions_strips(uint32_t plane_width);    /* k_regions' strips of a plane */
+uint32_t h2y_regions_segments(uint32_t plane_height); /* and its segments */
+int h2y_regions_grid(int n_cu, const regions_geom &g, int n_frames);
+/* k_regions over n_frames pairs into partials[frame x units per frame + unit], then k_regions_sum into stats[frame] */
+hipError_t h2y_launch_regions(int grid, hipStream_t st, const regions_geom &g, const cmp_frame *frames, int n_frames, regions_partial *partials,
+                              h2y_regions_stats *stats);
+
 /* k_light (h2y_light.hip): the content light of frames of the forward conversion's input (include/hdr2yuv_hip.h, h2y_light_stats) */
 struct light_frame { /* one frame: its G, B, R planes (16-byte aligned) and the floor / ceiling its conversion used */
     const void *in[3];

@@ -1,5 +1,5 @@
 /*
- * h2y_measure.hip -- the measurements of the C-ABI shim: the comparison with a reference, SSIM, content light, the light distribution, the light of PQ code planes, Delta E ITP, histograms, the
+ * h2y_measure.hip -- the measurements of the C-ABI shim: the comparison with a reference, SSIM, flat and busy areas, content light, the light distribution, the light of PQ code planes, Delta E ITP, histograms, the
  * scaler and the conversion between colour primaries.  Each has its checks and geometry, its batch entry, its ring stage (ring_stage, h2y_shim.h), and its arm, result and
  * *_stream_open entries.
  */
@@ -341,6 +341,177 @@ int h2y_stream_ssim_result(h2y_ctx *ctx, h2y_ssim_stats *out)
     if (!ctx || !out) return fail(ctx, H2Y_EINVAL, "null argument");
     const ssim_stage *st = ctx->streaming ? stage_of<ssim_stage>(ctx, STAGE_SSIM) : nullptr;
     if (!st) return fail(ctx, H2Y_EINVAL, "no stream open that computes SSIM");
+    if (ctx->s_lent < 0) return fail(ctx, H2Y_EINVAL, "no output taken yet: h2y_stream_output first");
+    *out = *st->ss[ctx->s_lent].h;
+    return H2Y_OK;
+}
+
+/* ---- PSNR of flat and of busy areas, over- and undershoot, beside the comparison ------------------------------------------------ */
+
+/* k_regions' geometry: the comparison's planes starting at a_off / b_off samples from the two frames' bases */
+static regions_geom regions_geom_of(int width, int height, int chroma, uint32_t flat_var, int radius, const uint32_t a_off[3], const uint32_t b_off[3])
+{
+    regions_geom g{};
+    const bool sub = chroma == H2Y_CHROMA_420;
+    for (int p = 0; p < 3; p++) {
+        g.pw[p] = p && sub ? (uint32_t)(width >> 1) : (uint32_t)width;
+        g.ph[p] = p && sub ? (uint32_t)(height >> 1) : (uint32_t)height;
+        g.a_off[p] = a_off[p];
+        g.b_off[p] = b_off[p];
+        g.strips[p] = h2y_regions_strips(g.pw[p]);
+        g.units[p] = g.strips[p] * h2y_regions_segments(g.ph[p]);
+    }
+    g.flat_var = flat_var;
+    g.radius = (uint32_t)radius;
+    return g;
+}
+
+static int regions_check(h2y_ctx *ctx, int width, int height, int chroma, int radius)
+{
+    if (width < 1 || height < 1 || (uint64_t)width * (uint64_t)height >= (1ull << 28)) return fail(ctx, H2Y_EINVAL, "bad picture size");
+    if (chroma == 2) return fail(ctx, H2Y_EUNSUPPORTED, "chroma_format_idc 2 (4:2:2) has no flat and busy areas on this path");
+    if (chroma != H2Y_CHROMA_420 && chroma != H2Y_CHROMA_444) return fail(ctx, H2Y_EINVAL, "chroma_format_idc must be 1 or 3");
+    if (radius < 1 || radius > 4) return fail(ctx, H2Y_EINVAL, "radius must be 1..4");
+    return H2Y_OK;
+}
+
+/* k_regions' partials for n_frames frames of g */
+static int regions_partials(h2y_ctx *ctx, const regions_geom &g, int n_frames)
+{
+    return ensure(ctx, ctx->d_regions_part, ctx->regions_part_cap,
+                  std::max<size_t>(1, (size_t)n_frames * (g.units[0] + g.units[1] + g.units[2])) * sizeof(regions_partial));
+}
+
+/* The definition of h2y_regions_stats, step by step, on one plane of pw x ph samples */
+static void regions_host_plane(const uint16_t *a, const uint16_t *b, int pw, int ph, uint32_t flat_var, int r, int p, h2y_regions_stats *o)
+{
+    for (int ty = 0; ty < ph; ty += 8)
+        for (int tx = 0; tx < pw; tx += 8) {
+            const int tw = std::min(8, pw - tx), th = std::min(8, ph - ty);
+            uint64_t s = 0, ss = 0, sse = 0, sad = 0;
+            for (int y = ty; y < ty + th; y++)
+                for (int x = tx; x < tx + tw; x++) {
+                    const uint64_t bv = b[(size_t)y * pw + x], av = a[(size_t)y * pw + x], d = av > bv ? av - bv : bv - av;
+                    s += bv, ss += bv * bv, sse += d * d, sad += d;
+                }
+            const uint64_t n = (uint64_t)tw * th, act = n * ss - s * s;
+            const int c = act <= (uint64_t)flat_var * n * n ? 0 : 1;
+            o->tiles[p][c] += 1, o->samples[p][c] += n, o->sse[p][c] += sse, o->sad[p][c] += sad;
+        }
+    for (int y = 0; y < ph; y++)
+        for (int x = 0; x < pw; x++) {
+            uint32_t m = 65535u, M = 0u;
+            for (int yy = std::max(0, y - r); yy <= std::min(ph - 1, y + r); yy++)
+                for (int xx = std::max(0, x - r); xx <= std::min(pw - 1, x + r); xx++) {
+                    const uint32_t bv = b[(size_t)yy * pw + xx];
+                    m = std::min(m, bv), M = std::max(M, bv);
+                }
+            const uint32_t av = a[(size_t)y * pw + x];
+            if (av > M) o->over[p] += 1, o->over_sum[p] += av - M, o->over_max[p] = std::max(o->over_max[p], av - M);
+            if (av < m) o->under[p] += 1, o->under_sum[p] += m - av, o->under_max[p] = std::max(o->under_max[p], m - av);
+        }
+}
+
+int h2y_regions_host(int width, int height, int chroma_format_idc, uint32_t flat_var, int radius, const uint16_t *a, const uint16_t *b,
+                     h2y_regions_stats *out)
+{
+    const int rc = regions_check(nullptr, width, height, chroma_format_idc, radius);
+    if (rc) return rc;
+    if (!a || !b || !out) return fail(nullptr, H2Y_EINVAL, "null pointer");
+    uint32_t off[3];
+    contiguous_planes(width, height, chroma_format_idc, off);
+    const bool sub = chroma_format_idc == H2Y_CHROMA_420;
+    *out = h2y_regions_stats{};
+    out->flat_var = flat_var;
+    out->radius = (uint32_t)radius;
+    for (int p = 0; p < 3; p++) regions_host_plane(a + off[p], b + off[p], p && sub ? width >> 1 : width, p && sub ? height >> 1 : height, flat_var, radius, p, out);
+    return H2Y_OK;
+}
+
+int h2y_regions_batch(h2y_ctx *ctx, int width, int height, int chroma_format_idc, uint32_t flat_var, int radius, int n_frames,
+                      const uint16_t *const *d_a, const uint16_t *const *d_b, h2y_regions_stats *out)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
+    int rc = regions_check(ctx, width, height, chroma_format_idc, radius);
+    if (rc) return rc;
+    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
+    if (!d_a || !d_b || !out) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
+    for (int f = 0; f < n_frames; f++) {
+        if (!d_a[f] || !d_b[f]) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is null", f);
+        if (((uintptr_t)d_a[f] | (uintptr_t)d_b[f]) & 15u) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is not 16-byte aligned", f);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    uint32_t off[3];
+    contiguous_planes(width, height, chroma_format_idc, off);
+    const regions_geom g = regions_geom_of(width, height, chroma_format_idc, flat_var, radius, off, off);
+    const int per_launch = std::min(n_frames, H2Y_REGIONS_FRAMES_PER_LAUNCH);
+    cmp_frame *h;
+    rc = frame_table(ctx, n_frames, h);
+    if (!rc) rc = regions_partials(ctx, g, per_launch);
+    if (!rc) rc = ensure(ctx, ctx->d_regions_stats, ctx->regions_stats_cap, (size_t)n_frames * sizeof(h2y_regions_stats));
+    if (rc) return rc;
+    for (int f = 0; f < n_frames; f++) h[f] = cmp_frame{d_a[f], d_b[f]};
+    rc = timed_launches(ctx, h, n_frames, H2Y_REGIONS_FRAMES_PER_LAUNCH, "k_regions", [&](const cmp_frame *frames, int f0, int nf) {
+        return h2y_launch_regions(h2y_regions_grid(ctx->n_cu, g, nf), ctx->stream, g, frames, nf, ctx->d_regions_part, ctx->d_regions_stats + f0);
+    });
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpy(out, ctx->d_regions_stats, (size_t)n_frames * sizeof(h2y_regions_stats), hipMemcpyDeviceToHost));
+    ctx->last_variant = std::string("k_regions<") + (chroma_format_idc == H2Y_CHROMA_420 ? "420" : "444") + ",R" + std::to_string(radius) + ">";
+    return H2Y_OK;
+}
+
+/* The regions' ring stage: k_regions after k_compare (and k_ssim, k_deltae), on the comparison's table entry of the slot, the
+ * frame's figures on the device and pinned */
+struct regions_stage : ring_stage {
+    struct slot {
+        h2y_regions_stats *d = nullptr, *h = nullptr;
+    };
+    std::vector<slot> ss;
+    regions_geom g{};
+    const cmp_frame *tab = nullptr; /* the comparison's stage's */
+    int run(h2y_ctx *ctx, int k) override
+    {
+        HIP_TRY(ctx, h2y_launch_regions(h2y_regions_grid(ctx->n_cu, g, 1), ctx->stream, g, tab + k, 1, ctx->d_regions_part, ss[k].d));
+        return H2Y_OK;
+    }
+    int download(h2y_ctx *ctx, int k) override
+    {
+        HIP_TRY(ctx, hipMemcpyAsync(ss[k].h, ss[k].d, sizeof(h2y_regions_stats), hipMemcpyDeviceToHost, ctx->s_d2h));
+        return H2Y_OK;
+    }
+};
+
+int h2y_stream_regions(h2y_ctx *ctx, uint32_t flat_var, int radius)
+{
+    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
+    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    const cmp_stage *cmp = stage_of<cmp_stage>(ctx, STAGE_COMPARE);
+    if (!cmp) return fail(ctx, H2Y_EINVAL, "the ring is not armed for comparison: h2y_stream_compare first");
+    if (ctx->s_stage[STAGE_REGIONS]) return fail(ctx, H2Y_EINVAL, "the ring measures flat and busy areas already");
+    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    const ring_frame &f = ctx->s_frame;
+    int rc = regions_check(ctx, f.width, f.height, f.chroma, radius);
+    if (rc) return rc;
+    auto st = std::make_unique<regions_stage>();
+    st->g = regions_geom_of(f.width, f.height, f.chroma, flat_var, radius, f.off, f.off);
+    st->tab = cmp->tab;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = regions_partials(ctx, st->g, 1);
+    if (rc) return rc;
+    st->ss.resize(ctx->ss.size());
+    for (auto &s : st->ss) {
+        st->dev_alloc(s.d, sizeof(h2y_regions_stats));
+        st->pin_alloc(s.h, sizeof(h2y_regions_stats));
+    }
+    return stage_arm(ctx, STAGE_REGIONS, std::move(st), "regions");
+}
+
+int h2y_stream_regions_result(h2y_ctx *ctx, h2y_regions_stats *out)
+{
+    if (!ctx || !out) return fail(ctx, H2Y_EINVAL, "null argument");
+    const regions_stage *st = ctx->streaming ? stage_of<regions_stage>(ctx, STAGE_REGIONS) : nullptr;
+    if (!st) return fail(ctx, H2Y_EINVAL, "no stream open that measures flat and busy areas");
     if (ctx->s_lent < 0) return fail(ctx, H2Y_EINVAL, "no output taken yet: h2y_stream_output first");
     *out = *st->ss[ctx->s_lent].h;
     return H2Y_OK;

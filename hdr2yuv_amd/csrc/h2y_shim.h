@@ -208,7 +208,7 @@ struct ring_stage {
     virtual int run(h2y_ctx *ctx, int slot) = 0;          /* on the context's stream, after the frame was produced */
     virtual int download(h2y_ctx *, int) { return H2Y_OK; } /* the result, on s_d2h after the slot's ev_conv */
 };
-enum stage_id { STAGE_UNPACK, STAGE_GAMUT, STAGE_TONEMAP, STAGE_LUT3D, STAGE_HLG, STAGE_ICTCP, STAGE_LIGHT, STAGE_LIGHTDIST, STAGE_CODELIGHT, STAGE_SCENESIG, STAGE_COMPARE, STAGE_SSIM, STAGE_DELTAE, STAGE_HISTOGRAM, STAGE_SCALE, STAGE_DITHER, STAGE_PACK, STAGE_COUNT };
+enum stage_id { STAGE_UNPACK, STAGE_GAMUT, STAGE_TONEMAP, STAGE_LUT3D, STAGE_HLG, STAGE_ICTCP, STAGE_LIGHT, STAGE_LIGHTDIST, STAGE_CODELIGHT, STAGE_SCENESIG, STAGE_COMPARE, STAGE_SSIM, STAGE_DELTAE, STAGE_REGIONS, STAGE_HISTOGRAM, STAGE_SCALE, STAGE_DITHER, STAGE_PACK, STAGE_COUNT };
 
 struct h2y_ctx {
     int device = 0;
@@ -281,6 +281,11 @@ struct h2y_ctx {
     size_t ssim_part_cap = 0;
     h2y_ssim_stats *d_ssim_stats = nullptr;
     size_t ssim_stats_cap = 0;
+    /* h2y_regions_batch's (and an armed ring's) k_regions partials, and the batch's stats */
+    regions_partial *d_regions_part = nullptr;
+    size_t regions_part_cap = 0;
+    h2y_regions_stats *d_regions_stats = nullptr;
+    size_t regions_stats_cap = 0;
     /* h2y_light_batch's floor / ceiling per frame and k_light's accumulators */
     assumed_stats *d_light_as = nullptr;
     size_t light_as_cap = 0;

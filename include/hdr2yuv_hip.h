@@ -613,6 +613,49 @@ int h2y_stream_ssim(h2y_ctx *ctx, int bit_depth);
 /* The SSIM of the frame that h2y_stream_output returned last. */
 int h2y_stream_ssim_result(h2y_ctx *ctx, h2y_ssim_stats *out);
 
+/* ---- PSNR of flat and of busy areas, over- and undershoot ("measure undershoot and overshoot", "measure PSNR on flat areas
+ * separate from busy areas": entries 2 and 3 of the reference's NOTES) -------------------------------------------------------------
+ * Two frames A and B of u16 samples in the comparison's geometry and layout, measured per plane: A is the produced or decoded
+ * picture, B the reference (k_compare's a and b).  chroma_format_idc 1 or 3.
+ * Tiles and classes.  A plane is cut into 8x8 tiles at (8i, 8j); the last column and row of tiles are cut to the plane, so a tile
+ * has n = tw x th samples, 1 <= tw, th <= 8, and every sample belongs to exactly one tile.  From B alone, in uint64:
+ *   S = sum b,  SS = sum b^2,  act = n x SS - S x S          (n^2 times the tile's variance; below 2^45 at 16 bits)
+ * and the tile is flat (class 0) when act <= flat_var x n x n, busy (class 1) otherwise; flat_var is in squared code values.  Per
+ * plane and class c: tiles[c], samples[c], sse[c] = sum (a - b)^2 and sad[c] = sum |a - b| over the class's tiles.  Summed over
+ * the two classes, samples, sse and sad equal h2y_compare_stats' samples, sse and sad of the same pair.
+ * Over- and undershoot.  For a sample at (x, y), m and M are the smallest and the largest b over the window
+ * [x - r, x + r] x [y - r, y + r] cut to the plane, r = radius (1..4); o = max(a - M, 0), u = max(m - a, 0).  Per plane: over the
+ * samples with o > 0, over_sum the sum of o, over_max the largest o; under, under_sum, under_max the same for u.
+ * Every figure is an exact integer: nothing depends on how the work is dealt. */
+#define H2Y_REGIONS_FRAMES_PER_LAUNCH 64
+
+typedef struct h2y_regions_stats {
+    uint64_t tiles[3][2], samples[3][2], sse[3][2], sad[3][2];   /* [plane][0 flat, 1 busy] */
+    uint64_t over[3], over_sum[3], under[3], under_sum[3];
+    uint32_t over_max[3], under_max[3];
+    uint32_t flat_var, radius;                                    /* what the figures are of */
+} h2y_regions_stats;
+
+/* The figures of one pair of frames in host memory (each frame's planes one after the other), in plain C++ on the CPU: the twin of
+ * k_regions, as h2y_dither_offsets is k_dither's.  H2Y_EINVAL: a size below 1 or of 2^28 samples or more, chroma_format_idc other
+ * than 1, 2 or 3, radius outside 1..4, a null pointer; H2Y_EUNSUPPORTED: chroma_format_idc 2. */
+int h2y_regions_host(int width, int height, int chroma_format_idc, uint32_t flat_var, int radius, const uint16_t *a, const uint16_t *b,
+                     h2y_regions_stats *out);
+
+/* n_frames pairs of device frames in h2y_compare_batch's layout and alignment: out[f] (host memory) receives the figures of d_a[f]
+ * against d_b[f].  chroma_format_idc 1 or 3 (2: H2Y_EUNSUPPORTED), radius 1..4, n_frames >= 1.  Launches of up to
+ * H2Y_REGIONS_FRAMES_PER_LAUNCH frames (h2y_last_kernel_ms sums them, h2y_last_kernel_name "k_regions"); synchronous. */
+int h2y_regions_batch(h2y_ctx *ctx, int width, int height, int chroma_format_idc, uint32_t flat_var, int radius, int n_frames,
+                      const uint16_t *const *d_a, const uint16_t *const *d_b, h2y_regions_stats *out);
+
+/* Arm a ring that h2y_stream_compare (or h2y_compare_stream_open) has armed, before its first input, beside h2y_stream_ssim,
+ * h2y_stream_deltae and h2y_stream_histogram: k_regions then runs on the kernel stream after k_compare, on the same device frame and
+ * reference; the output bytes and every other stage's results do not change.  H2Y_EINVAL when the ring is not armed for
+ * comparison, when it is armed for this already, after the first input, or for a radius outside 1..4. */
+int h2y_stream_regions(h2y_ctx *ctx, uint32_t flat_var, int radius);
+/* The figures of the frame that h2y_stream_output returned last. */
+int h2y_stream_regions_result(h2y_ctx *ctx, h2y_regions_stats *out);
+
 /* ---- content light level (MaxCLL / MaxFALL, CTA-861.3) of a forward conversion to PQ ------------------------------------------
  * Scope: dst_transfer 16 (PQ), src_transfer another transfer the conversion linearises (8 LINEAR, 18 RHO_GAMMA, 1/6/14/15
  * BT.1886), src_matrix 0 (G, B, R); anything else is H2Y_EUNSUPPORTED.  Light is taken where matrix_convert() defines it
@@ -1656,7 +1699,7 @@ int h2y_upsample_444_sited(h2y_ctx *ctx, int width, int height, int chroma_sampl
                            const uint16_t *d_src, uint16_t *d_dst);
 
 /* Timing of the last h2y_convert_batch*() (or h2y_inverse_*, h2y_dpx_decode_batch, h2y_tiff_decode_batch,
- * h2y_rgb_interleave_batch, h2y_exr_decode_batch, h2y_compare_batch, h2y_ssim_batch, h2y_light_batch, h2y_lightdist_batch, h2y_codelight_batch, h2y_scenesig_batch, h2y_codescenesig_batch, h2y_linearize_batch, h2y_hlg_linearize_batch, h2y_sdr_linearize_batch, h2y_scale_batch, h2y_gamut_batch, h2y_tonemap_batch, h2y_hlg_batch, h2y_ictcp_batch, h2y_dither_batch, h2y_pack_batch, h2y_unpack_batch) call measured with HIP events on
+ * h2y_rgb_interleave_batch, h2y_exr_decode_batch, h2y_compare_batch, h2y_ssim_batch, h2y_regions_batch, h2y_light_batch, h2y_lightdist_batch, h2y_codelight_batch, h2y_scenesig_batch, h2y_codescenesig_batch, h2y_linearize_batch, h2y_hlg_linearize_batch, h2y_sdr_linearize_batch, h2y_scale_batch, h2y_gamut_batch, h2y_tonemap_batch, h2y_hlg_batch, h2y_ictcp_batch, h2y_dither_batch, h2y_pack_batch, h2y_unpack_batch) call measured with HIP events on
  * the stream the kernels ran on: total ms over the main kernels and how many
  * launches that covered. */
 int h2y_last_kernel_ms(const h2y_ctx *ctx, float *ms, int *launches);

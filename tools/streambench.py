@@ -67,6 +67,14 @@ Prints one line per figure, then one JSON line with all of them.
   3. frames/s of the compare-only ring on the 10-bit 4:2:0 frames, without and with SSIM.
 Prints one line per figure, then one JSON line with all of them.
 
+`streambench.py regions`: flat and busy areas, over- and undershoot beside the comparison on 4K frames:
+  1. the kernel times of h2y_regions_batch (k_regions and k_regions_sum), h2y_compare_batch and h2y_ssim_batch over the same 64
+     distinct frame pairs per call, five calls each taken in turn after a warm-up (HIP events, the median per frame, the smallest and
+     largest beside it), the bytes per pair each reads once over that time and their share of the 8 TB/s HBM peak: 10-bit 4:2:0
+     pairs (49.8 MB) at radius 1 and 4, 16-bit 4:4:4 pairs (99.5 MB) at radius 1; and k_regions' time over k_ssim's;
+  2. frames/s of the compare-only ring on the 10-bit 4:2:0 frames from host memory, unarmed and armed with h2y_stream_regions.
+Prints one line per figure, then one JSON line with all of them.
+
 `streambench.py light`: the content light level on 4K frames:
   1. the kernel time of h2y_light_batch (k_light) over 64 distinct frames per call (HIP events, median of five; floor and
      ceiling given, so no k_stats runs), the bytes per frame it reads over that time and their share of the 8 TB/s HBM peak, for
@@ -976,6 +984,105 @@ def ssim_main():
     print(f"compare-only ring from host memory: {1/t_c:6.1f} frames/s, with ssim {1/t_s:6.1f} frames/s", flush=True)
     ctx.close()
     print(json.dumps({"streambench_ssim": res}), flush=True)
+
+
+def regions_main():
+    import json
+
+    import torch
+
+    w, hh, nb, reps = 3840, 2160, 64, 5
+    nf = int(os.environ.get("N", "60"))
+    depth = 3
+    ctx = h.Context(0)
+    res = {"width": w, "height": hh, "frames_per_call": nb, "reps": reps, "ring_frames": nf, "ring_depth": depth, "hbm_peak_tbs": 8.0}
+
+    def timed(calls):
+        """every call of calls in turn, reps times after a warm-up: per call its kernel times in ms per frame"""
+        out = [[] for _ in calls]
+        for rep in range(reps + 1):
+            for k, call in enumerate(calls):
+                call()
+                if rep:
+                    out[k].append(ctx.last_kernel_ms()[0] / nb)
+        return out
+
+    def report(key, label, t, nbytes, variant):
+        med = float(np.median(t))
+        tbs = nbytes / (med * 1e-3) / 1e12
+        res[key] = dict(kernel_us_per_frame=round(med * 1e3, 2), min_us=round(min(t) * 1e3, 2), max_us=round(max(t) * 1e3, 2),
+                        bytes_per_frame=nbytes, kernel_tbs=round(tbs, 2), hbm_peak_fraction=round(tbs / 8.0, 3), variant=variant)
+        print(f"{label:30s} {nb} pairs per call: {med*1e3:7.2f} us/frame ({min(t)*1e3:.2f}..{max(t)*1e3:.2f})  {tbs:5.2f} TB/s = "
+              f"{tbs/8.0*100:4.1f} % of 8 TB/s  {variant}", flush=True)
+        return med
+
+    # 1. the kernels over 64 distinct frame pairs on the device, in turn; each reads both sides once: 4 bytes a sample pair
+    for name, chroma, bits, radii in (("10bit_420", h.CHROMA_420, 10, (1, 4)), ("16bit_444", h.CHROMA_444, 16, (1,))):
+        total = w * hh + 2 * ((w // 2) * (hh // 2) if chroma == h.CHROMA_420 else w * hh)
+        hi, v = 1 << bits, 4 * 4 ** (bits - 8)
+        b = [torch.randint(0, hi, (total,), dtype=torch.int32, device="cuda").to(torch.int16) for _ in range(nb)]
+        a = [x + torch.randint(-2, 3, (total,), dtype=torch.int16, device="cuda") for x in b]
+        torch.cuda.synchronize()
+        variants = {}
+        note = lambda key: variants.setdefault(key, ctx.last_kernel_variant())  # noqa: E731
+        calls = [(lambda r: lambda: (ctx.regions_batch(w, hh, chroma, v, r, a, b), note(f"r{r}")))(r) for r in radii]
+        calls += [lambda: (ctx.compare_batch(w, hh, chroma, 0, a, b), note("cmp")), lambda: (ctx.ssim_batch(w, hh, chroma, bits, a, b), note("ssim"))]
+        t = timed(calls)
+        nbytes = 2 * 2 * total
+        m_reg = [report(f"k_regions_{name}_r{r}", f"k_regions {name} r={r}", t[k], nbytes, variants[f"r{r}"]) for k, r in enumerate(radii)]
+        report(f"k_compare_{name}", f"k_compare {name}", t[len(radii)], nbytes, variants["cmp"])
+        m_ssim = report(f"k_ssim_{name}", f"k_ssim {name}", t[len(radii) + 1], nbytes, variants["ssim"])
+        for r, m in zip(radii, m_reg):
+            res[f"ratio_to_k_ssim_{name}_r{r}"] = round(m / m_ssim, 3)
+            print(f"k_regions / k_ssim {name} r={r}: {m/m_ssim:5.3f}", flush=True)
+        del a, b
+        torch.cuda.empty_cache()
+
+    # 2. the compare-only ring on 10-bit 4:2:0 frames from host memory, unarmed and armed
+    n, nc = w * hh, (w // 2) * (hh // 2)
+    rng = np.random.default_rng(23)
+    ref = rng.integers(0, 1024, n + 2 * nc, dtype=np.uint16)
+    pic = np.clip(ref.astype(np.int32) + rng.integers(-2, 3, ref.size), 0, 1023).astype(np.uint16)
+    planes = [pic[:n], pic[n:n + nc], pic[n + nc:]]
+
+    def ring(regions):
+        ctx.compare_stream_open(w, hh, h.CHROMA_420, 0, depth)
+        if regions:
+            ctx.stream_regions(64, regions)
+        inflight = 0
+
+        def take():
+            ctx.stream_output()
+            ctx.stream_compare_result()
+            if regions:
+                ctx.stream_regions_result()
+
+        t0 = time.perf_counter()
+        for _ in range(nf):
+            slot = ctx.stream_input()
+            for c in range(3):
+                slot[c][:] = planes[c]
+            ctx.stream_reference()[:] = ref
+            ctx.stream_submit()
+            inflight += 1
+            if inflight == depth - 1:
+                take()
+                inflight -= 1
+        while inflight:
+            take()
+            inflight -= 1
+        dt = (time.perf_counter() - t0) / nf
+        ctx.stream_close()
+        return dt
+
+    ring(0)  # warm-up
+    t_c = float(np.median([ring(0) for _ in range(3)]))
+    t_r = {r: float(np.median([ring(r) for _ in range(3)])) for r in (1, 4)}
+    res["compare_only_ring"] = dict(fps=round(1 / t_c, 1), ms=round(t_c * 1e3, 2), regions_r1_fps=round(1 / t_r[1], 1), regions_r1_ms=round(t_r[1] * 1e3, 2),
+                                    regions_r4_fps=round(1 / t_r[4], 1), regions_r4_ms=round(t_r[4] * 1e3, 2))
+    print(f"compare-only ring from host memory: {1/t_c:6.1f} frames/s, with regions r=1 {1/t_r[1]:6.1f}, r=4 {1/t_r[4]:6.1f} frames/s", flush=True)
+    ctx.close()
+    print(json.dumps({"streambench_regions": res}), flush=True)
 
 
 def light_main():
@@ -2915,6 +3022,8 @@ if __name__ == "__main__":
         histogram_main()
     elif sys.argv[1:] == ["ssim"]:
         ssim_main()
+    elif sys.argv[1:] == ["regions"]:
+        regions_main()
     elif sys.argv[1:] == ["light"]:
         light_main()
     elif sys.argv[1:] == ["lightdist"]:
