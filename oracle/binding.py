@@ -131,6 +131,8 @@ class Oracle:
         L.h2y_oracle_powf25.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.h2y_oracle_to_linear.restype = None
         L.h2y_oracle_to_linear.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.h2y_oracle_from_linear.restype = None
+        L.h2y_oracle_from_linear.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
 
     def powf25(self, v: np.ndarray) -> np.ndarray:
         """powf(25, v) of every binary32 of `v`: the float RHO_GAMMA_f's outer pow starts from."""
@@ -145,6 +147,14 @@ class Oracle:
         v = np.ascontiguousarray(v, dtype=np.float32)
         out = np.empty_like(v)
         self.lib.h2y_oracle_to_linear(int(src_transfer), v.ctypes.data, out.ctypes.data, v.size)
+        return out
+
+    def from_linear(self, v: np.ndarray, dst_transfer: int) -> np.ndarray:
+        """Linear light -> destination transfer of every binary32 of `v` (16: PQ10000_r; what the transfer chain computes after the
+        source function): binary32, the shape of `v`.  One C call: it releases the GIL, as to_linear does."""
+        v = np.ascontiguousarray(v, dtype=np.float32)
+        out = np.empty_like(v)
+        self.lib.h2y_oracle_from_linear(int(dst_transfer), v.ctypes.data, out.ctypes.data, v.size)
         return out
 
     def pq(self, x: float) -> float:

@@ -110,6 +110,18 @@ void h2y_oracle_to_linear(int src_transfer, const float *in, float *out, size_t 
     for (size_t i = 0; i < n; i++) out[i] = o_transfer_chain(src_transfer, 8, in[i]);
 }
 
+/* the destination half of the chain over n samples: linear light -> destination transfer (dst 8 adds nothing); for 16 a plain loop
+ * over h2y_oracle_pq10000_r */
+void h2y_oracle_from_linear(int dst_transfer, const float *in, float *out, size_t n)
+{
+    switch (tf_class(dst_transfer)) {
+    case 1: for (size_t i = 0; i < n; i++) out[i] = h2y_oracle_pq10000_r(in[i]); break;
+    case 2: for (size_t i = 0; i < n; i++) out[i] = o_rho_gamma_r(in[i]); break;
+    case 3: for (size_t i = 0; i < n; i++) out[i] = o_bt1886_r(in[i]); break;
+    default: for (size_t i = 0; i < n; i++) out[i] = in[i]; break;
+    }
+}
+
 /* ---- pic_stats(), common.cpp:66-168 ------------------------------------ */
 void h2y_oracle_stats_f32(const float *const planes[3], size_t n, float mm[6],
                           int32_t floor_[3], int32_t ceil_[3])

@@ -45,6 +45,9 @@ float h2y_oracle_pq10000_r(float L);
 float h2y_oracle_transfer_chain(int src_transfer, int dst_transfer, float x);
 /* h2y_oracle_transfer_chain(src_transfer, 8, .) over n samples: source transfer -> linear light; in and out may be the same array */
 void h2y_oracle_to_linear(int src_transfer, const float *in, float *out, size_t n);
+/* h2y_oracle_transfer_chain(8, dst_transfer, .) over n samples: linear light -> destination transfer (16: h2y_oracle_pq10000_r of
+ * every sample); in and out may be the same array */
+void h2y_oracle_from_linear(int dst_transfer, const float *in, float *out, size_t n);
 /* powf(25.0f, .) over n samples: the inner pow of RHO_GAMMA_f, convert.cpp:12-27 */
 void h2y_oracle_powf25(const float *in, float *out, size_t n);
 

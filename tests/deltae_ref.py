@@ -1,7 +1,8 @@
 """A numpy restatement of the Delta E ITP of PQ code planes of include/hdr2yuv_hip.h ("Delta E ITP of PQ code planes"), for the tests:
-codelight_ref.py's planes444 and lights for steps 1-4 of the light of PQ code planes, then BT.2100 LMS, PQ10000_r (the oracle's scalar
-pq() over the distinct arguments: keep the pictures small), I, T, P and d, in float32 arrays with one operation per statement, and the
-per-frame figures of h2y_deltae_stats.  A plain module: numpy, plus the oracle the caller hands in."""
+codelight_ref.py's planes444 and lights for steps 1-4 of the light of PQ code planes, then BT.2100 LMS, PQ10000_r (the oracle's
+vector export from_linear(v, 16), one C call a plane: a picture may be as large as a sweep needs), I, T, P and d, in float32 arrays
+with one operation per statement, and the per-frame figures of h2y_deltae_stats.  A plain module: numpy, plus the oracle the caller
+hands in."""
 from fractions import Fraction
 
 import numpy as np
@@ -32,11 +33,8 @@ PC = tuple(const(k, P_DEN) for k in P_NUM)
 
 
 def pq_r(oracle, x):
-    """PQ10000_r of a float32 array through the oracle's scalar statement, once per distinct argument"""
-    x = np.ascontiguousarray(x, F32)
-    u, inv = np.unique(x.view(np.uint32), return_inverse=True)
-    vals = np.array([oracle.pq(float(v)) for v in u.view(F32)], F32)
-    return vals[inv.reshape(-1)].reshape(x.shape)
+    """PQ10000_r of a float32 array through the oracle's vector statement (h2y_oracle_from_linear: a plain loop over the scalar one)"""
+    return oracle.from_linear(np.ascontiguousarray(x, F32), clr.PQ)
 
 
 def lms(lights):
@@ -76,8 +74,8 @@ def itp(oracle, planes444, depth, full_range, matrix):
     return itp_of_lms(oracle, lms(clr.lights(oracle, planes444, depth, full_range, matrix)))
 
 
-def distance(a, b):
-    """d of two (I, T, P) triples"""
+def radicand(a, b):
+    """q = (dI dI + dT dT) + dP dP of two (I, T, P) triples: what the square root is taken of"""
     di = (a[0] - b[0]).astype(F32)
     dt = (a[1] - b[1]).astype(F32)
     dp = (a[2] - b[2]).astype(F32)
@@ -85,9 +83,17 @@ def distance(a, b):
     tt = (dt * dt).astype(F32)
     pp = (dp * dp).astype(F32)
     q = (ii + tt).astype(F32)
-    q = (q + pp).astype(F32)
+    return (q + pp).astype(F32)
+
+
+def d_of_radicand(q):
     root = np.sqrt(q).astype(F32)
     return (SCALE * root).astype(F32)
+
+
+def distance(a, b):
+    """d of two (I, T, P) triples"""
+    return d_of_radicand(radicand(a, b))
 
 
 def pixel_d(oracle, planes_a, planes_b, width, height, chroma, depth, full_range, matrix, form=clr.FIR):
