@@ -273,25 +273,6 @@ void h2y_ctx_destroy(h2y_ctx *ctx)
     (void)hipFree(ctx->d_lin);
     (void)hipFree(ctx->d_tab);
     (void)hipHostFree(ctx->h_tab);
-    (void)hipFree(ctx->d_cmp_part);
-    (void)hipFree(ctx->d_cmp_stats);
-    (void)hipFree(ctx->d_hist);
-    (void)hipFree(ctx->d_ssim_part);
-    (void)hipFree(ctx->d_ssim_stats);
-    (void)hipFree(ctx->d_regions_part);
-    (void)hipFree(ctx->d_regions_stats);
-    (void)hipFree(ctx->d_light_as);
-    (void)hipFree(ctx->d_light_acc);
-    (void)hipFree(ctx->d_lightdist);
-    (void)hipFree(ctx->d_codelight);
-    (void)hipFree(ctx->d_codelight_up);
-    (void)hipFree(ctx->d_scenesig);
-    (void)hipFree(ctx->d_deltae);
-    (void)hipFree(ctx->d_scale_tabs);
-    (void)hipFree(ctx->d_tonemap_gain);
-    (void)hipFree(ctx->d_lut3d);
-    (void)hipFree(ctx->d_hlg_tables);
-    (void)hipFree(ctx->d_hlgsrc_tables);
     (void)hipFree(ctx->d_in);
     (void)hipFree(ctx->d_out);
     if (ctx->fir_stream) {
@@ -303,7 +284,7 @@ void h2y_ctx_destroy(h2y_ctx *ctx)
         if (ctx->ev_fir[i]) (void)hipEventDestroy(ctx->ev_fir[i]);
     }
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
-    delete ctx;
+    delete ctx; /* and with it the measurements' workspaces (dev_buf) */
 }
 
 int h2y_ctx_set_stream(h2y_ctx *ctx, void *hip_stream)
@@ -346,9 +327,8 @@ void inverse420_setup(inv420_args &a, int width, int height, int in_bit_depth, i
 int h2y_matrix_inverse(h2y_ctx *ctx, int width, int height, int in_bit_depth, int in_full_range, int in_matrix_coeffs,
                        int out_bit_depth, const uint16_t *const d_in[3], uint16_t *const d_out[3])
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
-    if (width < 1 || height < 1 || (uint64_t)width * height >= (1ull << 28)) return fail(ctx, H2Y_EINVAL, "bad picture size");
+    if (const int rc = batch_enter(ctx)) return rc;
+    if (const int rc = picture_size_check(ctx, width, height)) return rc;
     if (in_bit_depth < 8 || in_bit_depth > 16 || out_bit_depth < 8 || out_bit_depth > 16) return fail(ctx, H2Y_EINVAL, "bit depths must be 8..16");
     if (in_matrix_coeffs == H2Y_MATRIX_GBR) /* convert.cpp:1733-1736: "Can't determine color difference to use?" and exit(0) */
         return fail(ctx, H2Y_EUNSUPPORTED, "matrix_coeffs 0 (GBR) has no inverse in the reference (it exits)");
@@ -395,8 +375,7 @@ static int upsample_launch(h2y_ctx *ctx, int width, int height, int algorithm, u
 static int upsample_444(h2y_ctx *ctx, int width, int height, int algorithm /* UP_* */, unsigned min_cv, unsigned max_cv,
                         const uint16_t *d_src, uint16_t *d_dst)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
+    if (const int rc = batch_enter(ctx)) return rc;
     /* odd sizes: the reference's FIR branch reads rows of its intermediate it never wrote (convert.cpp:1949 walks
      * j < height over 2 * (height / 2) written rows): no defined bytes */
     if (width < 2 || height < 2 || (width & 1) || (height & 1) || width > 32766 || height > 32766)
@@ -451,8 +430,7 @@ int inverse_form(h2y_ctx *ctx, int chroma, int algorithm, int *form)
 int h2y_inverse_420(h2y_ctx *ctx, int width, int height, int in_bit_depth, int in_full_range, int in_matrix_coeffs, int out_bit_depth,
                     int algorithm, const uint16_t *const d_in[3], uint16_t *const d_out[3])
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
+    if (const int rc = batch_enter(ctx)) return rc;
     if (width < 2 || height < 2 || (width & 3) || (height & 1) || width > 32766 || height > 32766)
         return fail(ctx, H2Y_EINVAL, "4:2:0 inverse: width a multiple of 4 and height even, up to 32766"); /* the upsampled planes feed 8-byte loads */
     if (in_bit_depth < 8 || in_bit_depth > 16) return fail(ctx, H2Y_EINVAL, "bit depths must be 8..16");
@@ -490,11 +468,10 @@ int h2y_inverse_420(h2y_ctx *ctx, int width, int height, int in_bit_depth, int i
 int h2y_inverse_frame(h2y_ctx *ctx, int width, int height, int in_chroma_format_idc, int in_bit_depth, int in_full_range,
                       int in_matrix_coeffs, int out_bit_depth, int algorithm, const uint16_t *const in_planes[3], uint16_t *const out_planes[3])
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
+    if (const int rc = batch_enter(ctx)) return rc;
     if (in_chroma_format_idc != H2Y_CHROMA_444 && in_chroma_format_idc != H2Y_CHROMA_420)
         return fail(ctx, H2Y_EUNSUPPORTED, "inverse flow: input chroma_format_idc must be 3 (4:4:4) or 1 (4:2:0)");
-    if (width < 1 || height < 1 || (uint64_t)width * height >= (1ull << 28)) return fail(ctx, H2Y_EINVAL, "bad picture size");
+    if (const int rc = picture_size_check(ctx, width, height)) return rc;
     if (!in_planes || !out_planes) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
     for (int c = 0; c < 3; c++)
         if (!in_planes[c] || !out_planes[c]) return fail(ctx, H2Y_EINVAL, "plane %d is null", c);
@@ -533,8 +510,8 @@ int inverse_check(h2y_ctx *ctx, const inv_params &p)
     if (p.chroma == H2Y_CHROMA_420) {
         if (p.width < 2 || p.height < 2 || (p.width & 3) || (p.height & 1) || p.width > 32766 || p.height > 32766)
             return fail(ctx, H2Y_EINVAL, "4:2:0 inverse: width a multiple of 4 and height even, up to 32766");
-    } else if (p.width < 1 || p.height < 1 || (uint64_t)p.width * p.height >= (1ull << 28))
-        return fail(ctx, H2Y_EINVAL, "bad picture size");
+    } else if (const int rc = picture_size_check(ctx, p.width, p.height))
+        return rc;
     if (p.in_depth < 8 || p.in_depth > 16 || p.out_depth < 8 || p.out_depth > 16) return fail(ctx, H2Y_EINVAL, "bit depths must be 8..16");
     if (p.matrix == H2Y_MATRIX_GBR) return fail(ctx, H2Y_EUNSUPPORTED, "matrix_coeffs 0 (GBR) has no inverse in the reference (it exits)");
     return H2Y_OK;
@@ -544,8 +521,7 @@ int inverse_check(h2y_ctx *ctx, const inv_params &p)
 template <typename P>
 static int decode_batch(h2y_ctx *ctx, const decode_src &src, int per_launch, int n_frames, const void *const *d_payload, P *const *d_planes)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
+    if (const int rc = batch_enter(ctx)) return rc;
     int rc = src.check(ctx);
     if (rc) return rc;
     if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
@@ -579,8 +555,7 @@ int h2y_inverse_batch(h2y_ctx *ctx, int width, int height, int in_chroma_format_
                       int in_matrix_coeffs, int out_bit_depth, int algorithm, int n_frames, const uint16_t *const *d_in,
                       uint16_t *const *d_out)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
+    if (const int rc = batch_enter(ctx)) return rc;
     const inv_params p{width, height, in_chroma_format_idc, in_bit_depth, in_full_range, in_matrix_coeffs, out_bit_depth, algorithm};
     int rc = inverse_check(ctx, p);
     if (rc) return rc;
@@ -940,17 +915,10 @@ int h2y_tiff_decode_batch(h2y_ctx *ctx, const h2y_tiff_info *info, int clamp_vid
     return decode_batch(ctx, decode_src(info, clamp_video_range), H2Y_TIFF_FRAMES_PER_LAUNCH, n_frames, d_payload, d_planes);
 }
 
-static int rgb_size_check(h2y_ctx *ctx, int width, int height)
-{
-    if (width < 1 || height < 1 || (uint64_t)width * (uint64_t)height >= (1ull << 28)) return fail(ctx, H2Y_EINVAL, "bad picture size");
-    return H2Y_OK;
-}
-
 int h2y_rgb_interleave_batch(h2y_ctx *ctx, int width, int height, int n_frames, const uint16_t *const *d_planes, uint16_t *const *d_rgb)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
-    int rc = rgb_size_check(ctx, width, height);
+    int rc = batch_enter(ctx);
+    if (!rc) rc = picture_size_check(ctx, width, height);
     if (rc) return rc;
     if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
     if (!d_planes || !d_rgb) return fail(ctx, H2Y_EINVAL, "null pointer arrays");

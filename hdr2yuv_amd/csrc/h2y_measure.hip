@@ -1,9 +1,18 @@
 /*
- * h2y_measure.hip -- the measurements of the C-ABI shim: the comparison with a reference, SSIM, flat and busy areas, content light, the light distribution, the light of PQ code planes, Delta E ITP, histograms, the
- * scaler and the conversion between colour primaries.  Each has its checks and geometry, its batch entry, its ring stage (ring_stage, h2y_shim.h), and its arm, result and
- * *_stream_open entries.
+ * h2y_measure.hip -- the measurements and passes of the C-ABI shim, in four families.  A frame against a reference (cmp_frame
+ * entries): the comparison, SSIM, flat and busy areas.  Light and code planes (codelight_plan): content light, the light
+ * distribution, the light of PQ code planes, scene signatures and cuts, Delta E ITP, the three linearisers, and further down the
+ * HLG and SDR inverses' host twins.  Whole u16 frames: histograms and the scaler, and at the end dither and the sample packings.
+ * Passes in place over float planes (gamut_frame entries): the conversion between colour primaries, the tone map, the 3D LUT, HLG,
+ * ICtCp.  Each has its checks and geometry, its batch entry, its ring stage (ring_stage, h2y_shim.h), and its arm, result and
+ * *_stream_open entries; what they share is in h2y_entry.h and at the head of each family.
  */
 #include "h2y_shim.h"
+
+#include "h2y_lut3d1.h"
+#include "h2y_hlg1.h"
+#include "h2y_dither1.h"
+#include "h2y_pack1.h"
 
 /* ---- comparison with a reference (--ref_filename, hdr2yuv.cpp:91-100, :827-833) ---------------------------------------- */
 
@@ -12,11 +21,10 @@
 static cmp_geom cmp_geom_of(int width, int height, int chroma, int sigma, const uint32_t a_off[3], const uint32_t b_off[3])
 {
     cmp_geom g{};
-    const bool sub = chroma == H2Y_CHROMA_420;
     for (int p = 0; p < 3; p++) {
-        const uint32_t w = p && sub ? (uint32_t)(width >> 1) : (uint32_t)width, h = p && sub ? (uint32_t)(height >> 1) : (uint32_t)height;
-        g.n[p] = w * h;
-        g.width[p] = w;
+        const plane_dim d = plane_dims(width, height, chroma, p);
+        g.n[p] = d.w * d.h;
+        g.width[p] = d.w;
         g.a_off[p] = a_off[p];
         g.b_off[p] = b_off[p];
         const bool vec = (a_off[p] & 7u) == (b_off[p] & 7u);
@@ -30,7 +38,8 @@ static cmp_geom cmp_geom_of(int width, int height, int chroma, int sigma, const 
 
 static int cmp_check(h2y_ctx *ctx, int width, int height, int chroma, int sigma)
 {
-    if (width < 1 || height < 1 || (uint64_t)width * (uint64_t)height >= (1ull << 28)) return fail(ctx, H2Y_EINVAL, "bad picture size");
+    const int rc = picture_size_check(ctx, width, height);
+    if (rc) return rc;
     if (chroma != H2Y_CHROMA_420 && chroma != H2Y_CHROMA_444) return fail(ctx, H2Y_EINVAL, "chroma_format_idc must be 1 or 3");
     if (sigma < 0) return fail(ctx, H2Y_EINVAL, "sigma must be >= 0");
     return H2Y_OK;
@@ -39,8 +48,7 @@ static int cmp_check(h2y_ctx *ctx, int width, int height, int chroma, int sigma)
 /* k_compare's partials for n_frames frames of g */
 static int cmp_partials(h2y_ctx *ctx, const cmp_geom &g, int n_frames)
 {
-    return ensure(ctx, ctx->d_cmp_part, ctx->cmp_part_cap,
-                  std::max<size_t>(1, (size_t)n_frames * (g.chunks[0] + g.chunks[1] + g.chunks[2])) * sizeof(cmp_partial));
+    return ensure(ctx, ctx->cmp_part, std::max<size_t>(1, (size_t)n_frames * (g.chunks[0] + g.chunks[1] + g.chunks[2])) * sizeof(cmp_partial));
 }
 
 static int cmp_grid(const h2y_ctx *ctx, const cmp_geom &g, int n_frames)
@@ -51,32 +59,18 @@ static int cmp_grid(const h2y_ctx *ctx, const cmp_geom &g, int n_frames)
 int h2y_compare_batch(h2y_ctx *ctx, int width, int height, int chroma_format_idc, int sigma, int n_frames, const uint16_t *const *d_a,
                       const uint16_t *const *d_b, h2y_compare_stats *out)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
-    int rc = cmp_check(ctx, width, height, chroma_format_idc, sigma);
+    int rc = batch_enter(ctx);
+    if (!rc) rc = cmp_check(ctx, width, height, chroma_format_idc, sigma);
     if (rc) return rc;
-    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
-    if (!d_a || !d_b || !out) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
-    for (int f = 0; f < n_frames; f++) {
-        if (!d_a[f] || !d_b[f]) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is null", f);
-        if (((uintptr_t)d_a[f] | (uintptr_t)d_b[f]) & 15u) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is not 16-byte aligned", f);
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     uint32_t off[3];
     contiguous_planes(width, height, chroma_format_idc, off);
     const cmp_geom g = cmp_geom_of(width, height, chroma_format_idc, sigma, off, off);
-    const int per_launch = std::min(n_frames, H2Y_COMPARE_FRAMES_PER_LAUNCH);
-    cmp_frame *h;
-    rc = frame_table(ctx, n_frames, h);
-    if (!rc) rc = cmp_partials(ctx, g, per_launch);
-    if (!rc) rc = ensure(ctx, ctx->d_cmp_stats, ctx->cmp_stats_cap, (size_t)n_frames * sizeof(h2y_compare_stats));
+    rc = pair_batch(ctx, n_frames, d_a, d_b, out, ctx->cmp_stats, H2Y_COMPARE_FRAMES_PER_LAUNCH, "k_compare",
+                    [&](int nf) { return cmp_partials(ctx, g, nf); },
+                    [&](const cmp_frame *frames, int f0, int nf) {
+                        return h2y_launch_compare(cmp_grid(ctx, g, nf), ctx->stream, g, frames, nf, ctx->cmp_part.p, ctx->cmp_stats.p + f0);
+                    });
     if (rc) return rc;
-    for (int f = 0; f < n_frames; f++) h[f] = cmp_frame{d_a[f], d_b[f]};
-    rc = timed_launches(ctx, h, n_frames, H2Y_COMPARE_FRAMES_PER_LAUNCH, "k_compare", [&](const cmp_frame *frames, int f0, int nf) {
-        return h2y_launch_compare(cmp_grid(ctx, g, nf), ctx->stream, g, frames, nf, ctx->d_cmp_part, ctx->d_cmp_stats + f0);
-    });
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpy(out, ctx->d_cmp_stats, (size_t)n_frames * sizeof(h2y_compare_stats), hipMemcpyDeviceToHost));
     ctx->last_variant = std::string("k_compare<") + (chroma_format_idc == H2Y_CHROMA_420 ? "420" : "444") + ">";
     return H2Y_OK;
 }
@@ -119,7 +113,7 @@ struct cmp_stage : ring_stage {
     }
     int run(h2y_ctx *ctx, int k) override
     {
-        HIP_TRY(ctx, h2y_launch_compare(cmp_grid(ctx, g, 1), ctx->stream, g, tab + k, 1, ctx->d_cmp_part, dev_stats(k)));
+        HIP_TRY(ctx, h2y_launch_compare(cmp_grid(ctx, g, 1), ctx->stream, g, tab + k, 1, ctx->cmp_part.p, dev_stats(k)));
         return H2Y_OK;
     }
     int download(h2y_ctx *ctx, int k) override
@@ -160,8 +154,8 @@ static int cmp_arm(h2y_ctx *ctx, int sigma, int keep_output)
 
 int h2y_stream_compare(h2y_ctx *ctx, int sigma, int keep_output)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    int rc = arm_enter(ctx);
+    if (rc) return rc;
     if (ctx->s_stage[STAGE_COMPARE]) return fail(ctx, H2Y_EINVAL, "the ring is armed already");
     if (ctx->s_stage[STAGE_CODELIGHT]) return fail(ctx, H2Y_EINVAL, "a light-only ring takes no other stage");
     if (ctx->s_stage[STAGE_SCALE]) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that scales is not compared: compare the written file instead");
@@ -169,7 +163,8 @@ int h2y_stream_compare(h2y_ctx *ctx, int sigma, int keep_output)
     if (ctx->s_stage[STAGE_PACK]) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that packs is not compared: compare the written file instead");
     if (ctx->s_stage[STAGE_UNPACK] && ctx->s_kind == h2y_ctx::RING_PLANES)
         return fail(ctx, H2Y_EINVAL, "the ring unpacks already: arm the comparison before unpack, so that its reference is unpacked too");
-    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    rc = arm_unstarted(ctx);
+    if (rc) return rc;
     if (keep_output != 0 && keep_output != 1) return fail(ctx, H2Y_EINVAL, "keep_output must be 0 or 1");
     return cmp_arm(ctx, sigma, keep_output);
 }
@@ -189,12 +184,7 @@ int h2y_stream_reference(h2y_ctx *ctx, void **ref)
 
 int h2y_stream_compare_result(h2y_ctx *ctx, h2y_compare_stats *out)
 {
-    if (!ctx || !out) return fail(ctx, H2Y_EINVAL, "null argument");
-    const cmp_stage *st = ctx->streaming ? stage_of<cmp_stage>(ctx, STAGE_COMPARE) : nullptr;
-    if (!st) return fail(ctx, H2Y_EINVAL, "no armed stream open");
-    if (ctx->s_lent < 0) return fail(ctx, H2Y_EINVAL, "no output taken yet: h2y_stream_output first");
-    *out = *st->ss[ctx->s_lent].h_stats;
-    return H2Y_OK;
+    return stream_result<cmp_stage>(ctx, out, STAGE_COMPARE, "no armed stream open", [&](const cmp_stage &st, int k) { *out = *st.ss[k].h_stats; });
 }
 
 /* A ring that only compares: the slot's input is A's three planes, the device output unused */
@@ -216,10 +206,10 @@ int h2y_compare_stream_open(h2y_ctx *ctx, int width, int height, int chroma_form
 static ssim_geom ssim_geom_of(int width, int height, int chroma, int bit_depth, const uint32_t a_off[3], const uint32_t b_off[3])
 {
     ssim_geom g{};
-    const bool sub = chroma == H2Y_CHROMA_420;
     for (int p = 0; p < 3; p++) {
-        g.pw[p] = p && sub ? (uint32_t)(width >> 1) : (uint32_t)width;
-        g.ph[p] = p && sub ? (uint32_t)(height >> 1) : (uint32_t)height;
+        const plane_dim d = plane_dims(width, height, chroma, p);
+        g.pw[p] = d.w;
+        g.ph[p] = d.h;
         g.a_off[p] = a_off[p];
         g.b_off[p] = b_off[p];
         g.strips[p] = h2y_ssim_strips(g.pw[p]);
@@ -234,7 +224,8 @@ static ssim_geom ssim_geom_of(int width, int height, int chroma, int bit_depth, 
 
 static int ssim_check(h2y_ctx *ctx, int width, int height, int chroma, int bit_depth)
 {
-    if (width < 1 || height < 1 || (uint64_t)width * (uint64_t)height >= (1ull << 28)) return fail(ctx, H2Y_EINVAL, "bad picture size");
+    const int rc = picture_size_check(ctx, width, height);
+    if (rc) return rc;
     if (chroma == 2) return fail(ctx, H2Y_EUNSUPPORTED, "chroma_format_idc 2 (4:2:2) has no SSIM on this path");
     if (chroma != H2Y_CHROMA_420 && chroma != H2Y_CHROMA_444) return fail(ctx, H2Y_EINVAL, "chroma_format_idc must be 1 or 3");
     if (bit_depth < 8 || bit_depth > 16) return fail(ctx, H2Y_EINVAL, "bit_depth must be 8..16");
@@ -247,80 +238,57 @@ static int ssim_check(h2y_ctx *ctx, int width, int height, int chroma, int bit_d
 /* k_ssim's partials for n_frames frames of g */
 static int ssim_partials(h2y_ctx *ctx, const ssim_geom &g, int n_frames)
 {
-    return ensure(ctx, ctx->d_ssim_part, ctx->ssim_part_cap, (size_t)n_frames * (g.units[0] + g.units[1] + g.units[2]) * sizeof(int64_t));
+    return ensure(ctx, ctx->ssim_part, (size_t)n_frames * (g.units[0] + g.units[1] + g.units[2]) * sizeof(int64_t));
 }
 
 int h2y_ssim_batch(h2y_ctx *ctx, int width, int height, int chroma_format_idc, int bit_depth, int n_frames, const uint16_t *const *d_a,
                    const uint16_t *const *d_b, h2y_ssim_stats *out)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
-    int rc = ssim_check(ctx, width, height, chroma_format_idc, bit_depth);
+    int rc = batch_enter(ctx);
+    if (!rc) rc = ssim_check(ctx, width, height, chroma_format_idc, bit_depth);
     if (rc) return rc;
-    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
-    if (!d_a || !d_b || !out) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
-    for (int f = 0; f < n_frames; f++) {
-        if (!d_a[f] || !d_b[f]) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is null", f);
-        if (((uintptr_t)d_a[f] | (uintptr_t)d_b[f]) & 15u) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is not 16-byte aligned", f);
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     uint32_t off[3];
     contiguous_planes(width, height, chroma_format_idc, off);
     const ssim_geom g = ssim_geom_of(width, height, chroma_format_idc, bit_depth, off, off);
-    const int per_launch = std::min(n_frames, H2Y_SSIM_FRAMES_PER_LAUNCH);
-    cmp_frame *h;
-    rc = frame_table(ctx, n_frames, h);
-    if (!rc) rc = ssim_partials(ctx, g, per_launch);
-    if (!rc) rc = ensure(ctx, ctx->d_ssim_stats, ctx->ssim_stats_cap, (size_t)n_frames * sizeof(h2y_ssim_stats));
+    rc = pair_batch(ctx, n_frames, d_a, d_b, out, ctx->ssim_stats, H2Y_SSIM_FRAMES_PER_LAUNCH, "k_ssim",
+                    [&](int nf) { return ssim_partials(ctx, g, nf); },
+                    [&](const cmp_frame *frames, int f0, int nf) {
+                        return h2y_launch_ssim(h2y_ssim_grid(ctx->n_cu, g, nf), ctx->stream, g, frames, nf, ctx->ssim_part.p, ctx->ssim_stats.p + f0);
+                    });
     if (rc) return rc;
-    for (int f = 0; f < n_frames; f++) h[f] = cmp_frame{d_a[f], d_b[f]};
-    rc = timed_launches(ctx, h, n_frames, H2Y_SSIM_FRAMES_PER_LAUNCH, "k_ssim", [&](const cmp_frame *frames, int f0, int nf) {
-        return h2y_launch_ssim(h2y_ssim_grid(ctx->n_cu, g, nf), ctx->stream, g, frames, nf, ctx->d_ssim_part, ctx->d_ssim_stats + f0);
-    });
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpy(out, ctx->d_ssim_stats, (size_t)n_frames * sizeof(h2y_ssim_stats), hipMemcpyDeviceToHost));
     ctx->last_variant = std::string("k_ssim<") + (chroma_format_idc == H2Y_CHROMA_420 ? "420" : "444") + "," + (g.wide ? "U64" : "U32") + ">";
     return H2Y_OK;
 }
 
 /* SSIM's ring stage: k_ssim after k_compare, on the comparison's table entry of the slot, the frame's SSIM on the device and
  * pinned */
-struct ssim_stage : ring_stage {
-    struct slot {
-        h2y_ssim_stats *d = nullptr, *h = nullptr;
-    };
-    std::vector<slot> ss;
+struct ssim_stage : result_stage<h2y_ssim_stats> {
     ssim_geom g{};
     const cmp_frame *tab = nullptr; /* the comparison's stage's */
     int run(h2y_ctx *ctx, int k) override
     {
-        HIP_TRY(ctx, h2y_launch_ssim(h2y_ssim_grid(ctx->n_cu, g, 1), ctx->stream, g, tab + k, 1, ctx->d_ssim_part, ss[k].d));
-        return H2Y_OK;
-    }
-    int download(h2y_ctx *ctx, int k) override
-    {
-        HIP_TRY(ctx, hipMemcpyAsync(ss[k].h, ss[k].d, sizeof(h2y_ssim_stats), hipMemcpyDeviceToHost, ctx->s_d2h));
+        HIP_TRY(ctx, h2y_launch_ssim(h2y_ssim_grid(ctx->n_cu, g, 1), ctx->stream, g, tab + k, 1, ctx->ssim_part.p, ss[k].d));
         return H2Y_OK;
     }
 };
 
 int h2y_stream_ssim(h2y_ctx *ctx, int bit_depth)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    int rc = arm_enter(ctx);
+    if (rc) return rc;
     if (ctx->s_stage[STAGE_SCALE]) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that scales computes no SSIM: compare the written file instead");
     if (ctx->s_stage[STAGE_DITHER]) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that dithers computes no SSIM: compare the written file instead");
     if (ctx->s_stage[STAGE_PACK]) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that packs computes no SSIM: compare the written file instead");
     const cmp_stage *cmp = stage_of<cmp_stage>(ctx, STAGE_COMPARE);
     if (!cmp) return fail(ctx, H2Y_EINVAL, "the ring is not armed for comparison: h2y_stream_compare first");
-    if (ctx->s_stage[STAGE_SSIM]) return fail(ctx, H2Y_EINVAL, "the ring computes SSIM already");
-    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    rc = arm_free(ctx, STAGE_SSIM, "the ring computes SSIM already");
+    if (rc) return rc;
     const ring_frame &f = ctx->s_frame;
     if (bit_depth < 0) {
         if (!f.depth) return fail(ctx, H2Y_EINVAL, "a compare-only ring does not know its frames' bit depth: give it to h2y_stream_ssim");
         bit_depth = f.depth;
     }
-    int rc = ssim_check(ctx, f.width, f.height, f.chroma, bit_depth);
+    rc = ssim_check(ctx, f.width, f.height, f.chroma, bit_depth);
     if (rc) return rc;
     auto st = std::make_unique<ssim_stage>();
     st->g = ssim_geom_of(f.width, f.height, f.chroma, bit_depth, f.off, f.off);
@@ -328,22 +296,13 @@ int h2y_stream_ssim(h2y_ctx *ctx, int bit_depth)
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     rc = ssim_partials(ctx, st->g, 1);
     if (rc) return rc;
-    st->ss.resize(ctx->ss.size());
-    for (auto &s : st->ss) {
-        st->dev_alloc(s.d, sizeof(h2y_ssim_stats));
-        st->pin_alloc(s.h, sizeof(h2y_ssim_stats));
-    }
+    st->slots(ctx->ss.size());
     return stage_arm(ctx, STAGE_SSIM, std::move(st), "SSIM");
 }
 
 int h2y_stream_ssim_result(h2y_ctx *ctx, h2y_ssim_stats *out)
 {
-    if (!ctx || !out) return fail(ctx, H2Y_EINVAL, "null argument");
-    const ssim_stage *st = ctx->streaming ? stage_of<ssim_stage>(ctx, STAGE_SSIM) : nullptr;
-    if (!st) return fail(ctx, H2Y_EINVAL, "no stream open that computes SSIM");
-    if (ctx->s_lent < 0) return fail(ctx, H2Y_EINVAL, "no output taken yet: h2y_stream_output first");
-    *out = *st->ss[ctx->s_lent].h;
-    return H2Y_OK;
+    return stream_result<ssim_stage>(ctx, out, STAGE_SSIM, "no stream open that computes SSIM", [&](const ssim_stage &st, int k) { *out = *st.ss[k].h; });
 }
 
 /* ---- PSNR of flat and of busy areas, over- and undershoot, beside the comparison ------------------------------------------------ */
@@ -352,10 +311,10 @@ int h2y_stream_ssim_result(h2y_ctx *ctx, h2y_ssim_stats *out)
 static regions_geom regions_geom_of(int width, int height, int chroma, uint32_t flat_var, int radius, const uint32_t a_off[3], const uint32_t b_off[3])
 {
     regions_geom g{};
-    const bool sub = chroma == H2Y_CHROMA_420;
     for (int p = 0; p < 3; p++) {
-        g.pw[p] = p && sub ? (uint32_t)(width >> 1) : (uint32_t)width;
-        g.ph[p] = p && sub ? (uint32_t)(height >> 1) : (uint32_t)height;
+        const plane_dim d = plane_dims(width, height, chroma, p);
+        g.pw[p] = d.w;
+        g.ph[p] = d.h;
         g.a_off[p] = a_off[p];
         g.b_off[p] = b_off[p];
         g.strips[p] = h2y_regions_strips(g.pw[p]);
@@ -368,7 +327,8 @@ static regions_geom regions_geom_of(int width, int height, int chroma, uint32_t 
 
 static int regions_check(h2y_ctx *ctx, int width, int height, int chroma, int radius)
 {
-    if (width < 1 || height < 1 || (uint64_t)width * (uint64_t)height >= (1ull << 28)) return fail(ctx, H2Y_EINVAL, "bad picture size");
+    const int rc = picture_size_check(ctx, width, height);
+    if (rc) return rc;
     if (chroma == 2) return fail(ctx, H2Y_EUNSUPPORTED, "chroma_format_idc 2 (4:2:2) has no flat and busy areas on this path");
     if (chroma != H2Y_CHROMA_420 && chroma != H2Y_CHROMA_444) return fail(ctx, H2Y_EINVAL, "chroma_format_idc must be 1 or 3");
     if (radius < 1 || radius > 4) return fail(ctx, H2Y_EINVAL, "radius must be 1..4");
@@ -378,8 +338,7 @@ static int regions_check(h2y_ctx *ctx, int width, int height, int chroma, int ra
 /* k_regions' partials for n_frames frames of g */
 static int regions_partials(h2y_ctx *ctx, const regions_geom &g, int n_frames)
 {
-    return ensure(ctx, ctx->d_regions_part, ctx->regions_part_cap,
-                  std::max<size_t>(1, (size_t)n_frames * (g.units[0] + g.units[1] + g.units[2])) * sizeof(regions_partial));
+    return ensure(ctx, ctx->regions_part, std::max<size_t>(1, (size_t)n_frames * (g.units[0] + g.units[1] + g.units[2])) * sizeof(regions_partial));
 }
 
 /* The definition of h2y_regions_stats, step by step, on one plane of pw x ph samples */
@@ -420,78 +379,58 @@ int h2y_regions_host(int width, int height, int chroma_format_idc, uint32_t flat
     if (!a || !b || !out) return fail(nullptr, H2Y_EINVAL, "null pointer");
     uint32_t off[3];
     contiguous_planes(width, height, chroma_format_idc, off);
-    const bool sub = chroma_format_idc == H2Y_CHROMA_420;
     *out = h2y_regions_stats{};
     out->flat_var = flat_var;
     out->radius = (uint32_t)radius;
-    for (int p = 0; p < 3; p++) regions_host_plane(a + off[p], b + off[p], p && sub ? width >> 1 : width, p && sub ? height >> 1 : height, flat_var, radius, p, out);
+    for (int p = 0; p < 3; p++) {
+        const plane_dim d = plane_dims(width, height, chroma_format_idc, p);
+        regions_host_plane(a + off[p], b + off[p], (int)d.w, (int)d.h, flat_var, radius, p, out);
+    }
     return H2Y_OK;
 }
 
 int h2y_regions_batch(h2y_ctx *ctx, int width, int height, int chroma_format_idc, uint32_t flat_var, int radius, int n_frames,
                       const uint16_t *const *d_a, const uint16_t *const *d_b, h2y_regions_stats *out)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
-    int rc = regions_check(ctx, width, height, chroma_format_idc, radius);
+    int rc = batch_enter(ctx);
+    if (!rc) rc = regions_check(ctx, width, height, chroma_format_idc, radius);
     if (rc) return rc;
-    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
-    if (!d_a || !d_b || !out) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
-    for (int f = 0; f < n_frames; f++) {
-        if (!d_a[f] || !d_b[f]) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is null", f);
-        if (((uintptr_t)d_a[f] | (uintptr_t)d_b[f]) & 15u) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is not 16-byte aligned", f);
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     uint32_t off[3];
     contiguous_planes(width, height, chroma_format_idc, off);
     const regions_geom g = regions_geom_of(width, height, chroma_format_idc, flat_var, radius, off, off);
-    const int per_launch = std::min(n_frames, H2Y_REGIONS_FRAMES_PER_LAUNCH);
-    cmp_frame *h;
-    rc = frame_table(ctx, n_frames, h);
-    if (!rc) rc = regions_partials(ctx, g, per_launch);
-    if (!rc) rc = ensure(ctx, ctx->d_regions_stats, ctx->regions_stats_cap, (size_t)n_frames * sizeof(h2y_regions_stats));
+    rc = pair_batch(ctx, n_frames, d_a, d_b, out, ctx->regions_stats, H2Y_REGIONS_FRAMES_PER_LAUNCH, "k_regions",
+                    [&](int nf) { return regions_partials(ctx, g, nf); },
+                    [&](const cmp_frame *frames, int f0, int nf) {
+                        return h2y_launch_regions(h2y_regions_grid(ctx->n_cu, g, nf), ctx->stream, g, frames, nf, ctx->regions_part.p,
+                                                  ctx->regions_stats.p + f0);
+                    });
     if (rc) return rc;
-    for (int f = 0; f < n_frames; f++) h[f] = cmp_frame{d_a[f], d_b[f]};
-    rc = timed_launches(ctx, h, n_frames, H2Y_REGIONS_FRAMES_PER_LAUNCH, "k_regions", [&](const cmp_frame *frames, int f0, int nf) {
-        return h2y_launch_regions(h2y_regions_grid(ctx->n_cu, g, nf), ctx->stream, g, frames, nf, ctx->d_regions_part, ctx->d_regions_stats + f0);
-    });
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpy(out, ctx->d_regions_stats, (size_t)n_frames * sizeof(h2y_regions_stats), hipMemcpyDeviceToHost));
     ctx->last_variant = std::string("k_regions<") + (chroma_format_idc == H2Y_CHROMA_420 ? "420" : "444") + ",R" + std::to_string(radius) + ">";
     return H2Y_OK;
 }
 
 /* The regions' ring stage: k_regions after k_compare (and k_ssim, k_deltae), on the comparison's table entry of the slot, the
  * frame's figures on the device and pinned */
-struct regions_stage : ring_stage {
-    struct slot {
-        h2y_regions_stats *d = nullptr, *h = nullptr;
-    };
-    std::vector<slot> ss;
+struct regions_stage : result_stage<h2y_regions_stats> {
     regions_geom g{};
     const cmp_frame *tab = nullptr; /* the comparison's stage's */
     int run(h2y_ctx *ctx, int k) override
     {
-        HIP_TRY(ctx, h2y_launch_regions(h2y_regions_grid(ctx->n_cu, g, 1), ctx->stream, g, tab + k, 1, ctx->d_regions_part, ss[k].d));
-        return H2Y_OK;
-    }
-    int download(h2y_ctx *ctx, int k) override
-    {
-        HIP_TRY(ctx, hipMemcpyAsync(ss[k].h, ss[k].d, sizeof(h2y_regions_stats), hipMemcpyDeviceToHost, ctx->s_d2h));
+        HIP_TRY(ctx, h2y_launch_regions(h2y_regions_grid(ctx->n_cu, g, 1), ctx->stream, g, tab + k, 1, ctx->regions_part.p, ss[k].d));
         return H2Y_OK;
     }
 };
 
 int h2y_stream_regions(h2y_ctx *ctx, uint32_t flat_var, int radius)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    int rc = arm_enter(ctx);
+    if (rc) return rc;
     const cmp_stage *cmp = stage_of<cmp_stage>(ctx, STAGE_COMPARE);
     if (!cmp) return fail(ctx, H2Y_EINVAL, "the ring is not armed for comparison: h2y_stream_compare first");
-    if (ctx->s_stage[STAGE_REGIONS]) return fail(ctx, H2Y_EINVAL, "the ring measures flat and busy areas already");
-    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    rc = arm_free(ctx, STAGE_REGIONS, "the ring measures flat and busy areas already");
+    if (rc) return rc;
     const ring_frame &f = ctx->s_frame;
-    int rc = regions_check(ctx, f.width, f.height, f.chroma, radius);
+    rc = regions_check(ctx, f.width, f.height, f.chroma, radius);
     if (rc) return rc;
     auto st = std::make_unique<regions_stage>();
     st->g = regions_geom_of(f.width, f.height, f.chroma, flat_var, radius, f.off, f.off);
@@ -499,22 +438,14 @@ int h2y_stream_regions(h2y_ctx *ctx, uint32_t flat_var, int radius)
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     rc = regions_partials(ctx, st->g, 1);
     if (rc) return rc;
-    st->ss.resize(ctx->ss.size());
-    for (auto &s : st->ss) {
-        st->dev_alloc(s.d, sizeof(h2y_regions_stats));
-        st->pin_alloc(s.h, sizeof(h2y_regions_stats));
-    }
+    st->slots(ctx->ss.size());
     return stage_arm(ctx, STAGE_REGIONS, std::move(st), "regions");
 }
 
 int h2y_stream_regions_result(h2y_ctx *ctx, h2y_regions_stats *out)
 {
-    if (!ctx || !out) return fail(ctx, H2Y_EINVAL, "null argument");
-    const regions_stage *st = ctx->streaming ? stage_of<regions_stage>(ctx, STAGE_REGIONS) : nullptr;
-    if (!st) return fail(ctx, H2Y_EINVAL, "no stream open that measures flat and busy areas");
-    if (ctx->s_lent < 0) return fail(ctx, H2Y_EINVAL, "no output taken yet: h2y_stream_output first");
-    *out = *st->ss[ctx->s_lent].h;
-    return H2Y_OK;
+    return stream_result<regions_stage>(ctx, out, STAGE_REGIONS, "no stream open that measures flat and busy areas",
+                                        [&](const regions_stage &st, int k) { *out = *st.ss[k].h; });
 }
 
 /* ---- content light level (MaxCLL / MaxFALL) of a forward conversion to PQ ------------------------------------------------------ */
@@ -560,11 +491,6 @@ static std::string light_variant(const h2y_desc *d, const light_args &a)
 }
 
 /* the stats of one frame of npix pixels, width wide, from its accumulator */
-static void light_finish(const light_acc &acc, uint32_t width, uint32_t npix, h2y_light_stats *o);
-/* a light-only ring (h2y_codelight_stream_open, below): its lent frame's figures; false on any other ring */
-static bool codelight_light_result(const h2y_ctx *ctx, h2y_light_stats *out);
-static int codelight_dist_result(h2y_ctx *ctx, h2y_lightdist_stats *out, bool *mine);
-
 static void light_finish(const light_acc &acc, uint32_t width, uint32_t npix, h2y_light_stats *o)
 {
     *o = h2y_light_stats{};
@@ -579,13 +505,12 @@ static void light_finish(const light_acc &acc, uint32_t width, uint32_t npix, h2
 }
 
 /* What h2y_light_batch and h2y_lightdist_batch share: the checks, k_light's arguments, every frame's floor and ceiling on the device
- * (d_light_as: the descriptor's override, or pic_stats of each frame) and the frame table h */
+ * (light_as: the descriptor's override, or pic_stats of each frame) and the frame table h */
 static int light_batch_prepare(h2y_ctx *ctx, const h2y_desc *d, int n_frames, const void *const *d_planes, const void *out, light_args &a,
                                light_frame *&h)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
-    int rc = light_check(ctx, d);
+    int rc = batch_enter(ctx);
+    if (!rc) rc = light_check(ctx, d);
     if (rc) return rc;
     if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
     if (!d_planes || !out) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
@@ -596,22 +521,23 @@ static int light_batch_prepare(h2y_ctx *ctx, const h2y_desc *d, int n_frames, co
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     rc = light_args_of(ctx, d, a);
     if (!rc) rc = frame_table(ctx, n_frames, h);
-    if (!rc) rc = ensure(ctx, ctx->d_light_as, ctx->light_as_cap, (size_t)n_frames * sizeof(assumed_stats));
+    if (!rc) rc = ensure(ctx, ctx->light_as, (size_t)n_frames * sizeof(assumed_stats));
     if (rc) return rc;
+    assumed_stats *d_as = ctx->light_as.p;
     if (d->stats_override) { /* the same six integers for every frame */
         std::vector<assumed_stats> as(n_frames);
         for (auto &x : as)
             for (int c = 0; c < 3; c++) x.floor_[c] = d->floor[c], x.ceil_[c] = d->ceiling[c];
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_light_as, as.data(), (size_t)n_frames * sizeof(assumed_stats), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(d_as, as.data(), (size_t)n_frames * sizeof(assumed_stats), hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     } else /* pic_stats of every frame, as h2y_convert_batch ends up taking it */
         for (int f = 0; f < n_frames; f++) {
-            rc = run_stats(ctx, d, d_planes + 3 * f, (int)ctx->b->frames_cap, ctx->d_light_as + f);
+            rc = run_stats(ctx, d, d_planes + 3 * f, (int)ctx->b->frames_cap, d_as + f);
             if (rc) return rc;
         }
     ctx->b->dev_assumed_ok = false; /* run_stats used the batch state's scratch slot */
     for (int f = 0; f < n_frames; f++)
-        h[f] = light_frame{{d_planes[3 * f], d_planes[3 * f + 1], d_planes[3 * f + 2]}, ctx->d_light_as + f};
+        h[f] = light_frame{{d_planes[3 * f], d_planes[3 * f + 1], d_planes[3 * f + 2]}, d_as + f};
     return H2Y_OK;
 }
 
@@ -620,16 +546,17 @@ int h2y_light_batch(h2y_ctx *ctx, const h2y_desc *d, int n_frames, const void *c
     light_args a;
     light_frame *h;
     int rc = light_batch_prepare(ctx, d, n_frames, d_planes, out, a, h);
-    if (!rc) rc = ensure(ctx, ctx->d_light_acc, ctx->light_acc_cap, (size_t)n_frames * sizeof(light_acc));
+    if (!rc) rc = ensure(ctx, ctx->light_accs, (size_t)n_frames * sizeof(light_acc));
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_light_acc, 0, (size_t)n_frames * sizeof(light_acc), ctx->stream));
+    light_acc *d_acc = ctx->light_accs.p;
+    HIP_TRY(ctx, hipMemsetAsync(d_acc, 0, (size_t)n_frames * sizeof(light_acc), ctx->stream));
     const int in_kind = in_kind_of(d);
     rc = timed_launches(ctx, h, n_frames, H2Y_LIGHT_FRAMES_PER_LAUNCH, "k_light", [&](const light_frame *frames, int f0, int nf) {
-        return h2y_launch_light(in_kind, h2y_light_grid(a.npix, nf), ctx->stream, a, frames, nf, ctx->d_light_acc + f0);
+        return h2y_launch_light(in_kind, h2y_light_grid(a.npix, nf), ctx->stream, a, frames, nf, d_acc + f0);
     });
     if (rc) return rc;
     std::vector<light_acc> acc(n_frames);
-    HIP_TRY(ctx, hipMemcpy(acc.data(), ctx->d_light_acc, (size_t)n_frames * sizeof(light_acc), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(acc.data(), d_acc, (size_t)n_frames * sizeof(light_acc), hipMemcpyDeviceToHost));
     for (int f = 0; f < n_frames; f++) light_finish(acc[f], (uint32_t)d->width, a.npix, out + f);
     ctx->last_variant = light_variant(d, a);
     return H2Y_OK;
@@ -637,11 +564,7 @@ int h2y_light_batch(h2y_ctx *ctx, const h2y_desc *d, int n_frames, const void *c
 
 /* Content light's ring stage, on the forward ring's decoded planes with the floor and ceiling the conversion just used
  * (d_assumed): k_light's arguments, its table entry per slot, and the frame's accumulator on the device and pinned */
-struct light_stage : ring_stage {
-    struct slot {
-        light_acc *d = nullptr, *h = nullptr;
-    };
-    std::vector<slot> ss;
+struct light_stage : result_stage<light_acc> {
     light_args a{};
     light_frame *tab = nullptr;
     int run(h2y_ctx *ctx, int k) override
@@ -650,49 +573,25 @@ struct light_stage : ring_stage {
         HIP_TRY(ctx, h2y_launch_light(in_kind_of(&ctx->s_desc), h2y_light_grid(a.npix, 1), ctx->stream, a, tab + k, 1, ss[k].d));
         return H2Y_OK;
     }
-    int download(h2y_ctx *ctx, int k) override
-    {
-        HIP_TRY(ctx, hipMemcpyAsync(ss[k].h, ss[k].d, sizeof(light_acc), hipMemcpyDeviceToHost, ctx->s_d2h));
-        return H2Y_OK;
-    }
 };
 
 int h2y_stream_light(h2y_ctx *ctx)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    int rc = arm_enter(ctx);
+    if (rc) return rc;
     if (ctx->s_kind != h2y_ctx::RING_FORWARD) return fail(ctx, H2Y_EINVAL, "content light is measured on the forward rings only");
-    if (ctx->s_stage[STAGE_LIGHT]) return fail(ctx, H2Y_EINVAL, "the ring measures content light already");
-    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    rc = arm_free(ctx, STAGE_LIGHT, "the ring measures content light already");
+    if (rc) return rc;
     const h2y_desc *d = &ctx->s_desc;
-    int rc = light_check(ctx, d);
+    rc = light_check(ctx, d);
     if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     auto st = std::make_unique<light_stage>();
     rc = light_args_of(ctx, d, st->a);
     if (rc) return rc;
-    const int depth = (int)ctx->ss.size();
-    std::vector<light_frame> tab(depth);
-    st->ss.resize(depth);
-    for (int k = 0; k < depth; k++) {
-        for (int c = 0; c < 3; c++) tab[k].in[c] = ctx->ss[k].d_in + c * ctx->s_plane_al;
-        tab[k].assumed = ctx->b->d_assumed;
-        st->dev_alloc(st->ss[k].d, sizeof(light_acc));
-        st->pin_alloc(st->ss[k].h, sizeof(light_acc));
-    }
-    st->table(st->tab, tab);
+    st->slots(ctx->ss.size());
+    st->table(st->tab, light_ring_table(ctx));
     return stage_arm(ctx, STAGE_LIGHT, std::move(st), "content light");
-}
-
-int h2y_stream_light_result(h2y_ctx *ctx, h2y_light_stats *out)
-{
-    if (!ctx || !out) return fail(ctx, H2Y_EINVAL, "null argument");
-    const light_stage *st = ctx->streaming ? stage_of<light_stage>(ctx, STAGE_LIGHT) : nullptr;
-    if (!st && !(ctx->streaming && ctx->s_stage[STAGE_CODELIGHT])) return fail(ctx, H2Y_EINVAL, "no stream open that measures content light");
-    if (ctx->s_lent < 0) return fail(ctx, H2Y_EINVAL, "no output taken yet: h2y_stream_output first");
-    if (codelight_light_result(ctx, out)) return H2Y_OK;
-    light_finish(*st->ss[ctx->s_lent].h, (uint32_t)ctx->s_desc.width, st->a.npix, out);
-    return H2Y_OK;
 }
 
 /* ---- light distribution (ST 2094-40 dynamic metadata) of a forward conversion to PQ ------------------------------------------- */
@@ -740,11 +639,11 @@ int h2y_lightdist_batch(h2y_ctx *ctx, const h2y_desc *d, int n_frames, const voi
     light_frame *h;
     int rc = light_batch_prepare(ctx, d, n_frames, d_planes, out, a, h);
     const lightdist_layout L = lightdist_layout_of(n_frames > 0 ? n_frames : 1);
-    if (!rc) rc = ensure(ctx, ctx->d_lightdist, ctx->lightdist_cap, L.total);
+    if (!rc) rc = ensure(ctx, ctx->lightdist, L.total);
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_lightdist, 0, L.total, ctx->stream));
-    lightdist_acc *d_acc = reinterpret_cast<lightdist_acc *>(ctx->d_lightdist);
-    uint32_t *d_bins = reinterpret_cast<uint32_t *>(ctx->d_lightdist + L.bins);
+    HIP_TRY(ctx, hipMemsetAsync(ctx->lightdist.p, 0, L.total, ctx->stream));
+    lightdist_acc *d_acc = reinterpret_cast<lightdist_acc *>(ctx->lightdist.p);
+    uint32_t *d_bins = reinterpret_cast<uint32_t *>(ctx->lightdist.p + L.bins);
     const int in_kind = in_kind_of(d);
     rc = timed_launches(ctx, h, n_frames, H2Y_LIGHTDIST_FRAMES_PER_LAUNCH, "k_lightdist", [&](const light_frame *frames, int f0, int nf) {
         return h2y_launch_lightdist(in_kind, h2y_lightdist_grid(a.npix, nf), ctx->stream, a, frames, nf, d_acc + f0,
@@ -787,44 +686,26 @@ struct lightdist_stage : ring_stage {
 
 int h2y_stream_lightdist(h2y_ctx *ctx)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    int rc = arm_enter(ctx);
+    if (rc) return rc;
     if (ctx->s_kind != h2y_ctx::RING_FORWARD) return fail(ctx, H2Y_EINVAL, "the light distribution is measured on the forward rings only");
-    if (ctx->s_stage[STAGE_LIGHTDIST]) return fail(ctx, H2Y_EINVAL, "the ring measures the light distribution already");
-    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    rc = arm_free(ctx, STAGE_LIGHTDIST, "the ring measures the light distribution already");
+    if (rc) return rc;
     const h2y_desc *d = &ctx->s_desc;
-    int rc = light_check(ctx, d);
+    rc = light_check(ctx, d);
     if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     auto st = std::make_unique<lightdist_stage>();
     rc = light_args_of(ctx, d, st->a);
     if (rc) return rc;
-    const int depth = (int)ctx->ss.size();
     const lightdist_layout L = lightdist_layout_of(1);
-    std::vector<light_frame> tab(depth);
-    st->ss.resize(depth);
-    for (int k = 0; k < depth; k++) {
-        for (int c = 0; c < 3; c++) tab[k].in[c] = ctx->ss[k].d_in + c * ctx->s_plane_al;
-        tab[k].assumed = ctx->b->d_assumed;
-        st->dev_alloc(st->ss[k].d, L.total);
-        st->pin_alloc(st->ss[k].h, L.total);
+    st->ss.resize(ctx->ss.size());
+    for (auto &s : st->ss) {
+        st->dev_alloc(s.d, L.total);
+        st->pin_alloc(s.h, L.total);
     }
-    st->table(st->tab, tab);
+    st->table(st->tab, light_ring_table(ctx));
     return stage_arm(ctx, STAGE_LIGHTDIST, std::move(st), "light distribution");
-}
-
-int h2y_stream_lightdist_result(h2y_ctx *ctx, h2y_lightdist_stats *out)
-{
-    if (!ctx || !out) return fail(ctx, H2Y_EINVAL, "null argument");
-    bool mine = false;
-    const int crc = codelight_dist_result(ctx, out, &mine);
-    if (mine) return crc;
-    const lightdist_stage *st = ctx->streaming ? stage_of<lightdist_stage>(ctx, STAGE_LIGHTDIST) : nullptr;
-    if (!st) return fail(ctx, H2Y_EINVAL, "no stream open that measures the light distribution");
-    if (ctx->s_lent < 0) return fail(ctx, H2Y_EINVAL, "no output taken yet: h2y_stream_output first");
-    const char *h = st->ss[ctx->s_lent].h;
-    lightdist_finish(*reinterpret_cast<const lightdist_acc *>(h), reinterpret_cast<const uint32_t *>(h + lightdist_layout_of(1).bins), st->a.npix, out);
-    return H2Y_OK;
 }
 
 /* 0.1 cd/m2 of a light L in [0, 1] given as bits: rint(100000 x (double)L), half to even */
@@ -874,7 +755,8 @@ int codelight_check(h2y_ctx *ctx, const h2y_codelight_desc *d, codelight_plan &p
     if (d->matrix_coeffs != H2Y_MATRIX_GBR && d->matrix_coeffs != H2Y_MATRIX_BT709 && d->matrix_coeffs != H2Y_MATRIX_BT2020NC &&
         d->matrix_coeffs != H2Y_MATRIX_ICTCP)
         return fail(ctx, H2Y_EUNSUPPORTED, "light of code planes: matrix_coeffs must be 0 (G,B,R), 1 (BT.709), 9 (BT.2020nc) or 14 (ICtCp), not %d", d->matrix_coeffs);
-    if (d->width < 1 || d->height < 1 || (uint64_t)d->width * (uint64_t)d->height >= (1ull << 28)) return fail(ctx, H2Y_EINVAL, "bad picture size");
+    int rc = picture_size_check(ctx, d->width, d->height);
+    if (rc) return rc;
     if (d->bit_depth < 8 || d->bit_depth > 16) return fail(ctx, H2Y_EINVAL, "bit_depth must be 8..16");
     if (d->full_range != 0 && d->full_range != 1) return fail(ctx, H2Y_EINVAL, "full_range must be 0 or 1");
     p.sub = d->chroma_format_idc == H2Y_CHROMA_420;
@@ -883,7 +765,7 @@ int codelight_check(h2y_ctx *ctx, const h2y_codelight_desc *d, codelight_plan &p
         if ((d->width & 1) || (d->height & 1) || d->width > 32766 || d->height > 32766)
             return fail(ctx, H2Y_EINVAL, "4:2:0: width and height must be even, up to 32766");
     }
-    const int rc = inverse_form(ctx, d->chroma_format_idc, d->algorithm, &p.form); /* siting 2 with replication: the inverse entries' refusal */
+    rc = inverse_form(ctx, d->chroma_format_idc, d->algorithm, &p.form); /* siting 2 with replication: the inverse entries' refusal */
     if (rc) return rc;
     p.matrix = d->matrix_coeffs;
     codelight_args &a = p.a;
@@ -961,17 +843,11 @@ static size_t codelight_dist_off(int nf) { return ((size_t)nf * sizeof(light_acc
 int h2y_codelight_batch(h2y_ctx *ctx, const h2y_codelight_desc *d, int n_frames, const uint16_t *const *d_frames, h2y_light_stats *out,
                         h2y_lightdist_stats *dist_out, uint32_t *bins_out)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
     codelight_plan p;
-    int rc = codelight_check(ctx, d, p);
+    int rc = batch_enter(ctx);
+    if (!rc) rc = codelight_check(ctx, d, p);
+    if (!rc) rc = frames_check(ctx, n_frames, d_frames, out != nullptr);
     if (rc) return rc;
-    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
-    if (!d_frames || !out) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
-    for (int f = 0; f < n_frames; f++) {
-        if (!d_frames[f]) return fail(ctx, H2Y_EINVAL, "frame %d is null", f);
-        if ((uintptr_t)d_frames[f] & 15u) return fail(ctx, H2Y_EINVAL, "frame %d is not 16-byte aligned", f);
-    }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const bool dist = dist_out || bins_out;
     const int per_launch = std::min(n_frames, H2Y_CODELIGHT_FRAMES_PER_LAUNCH);
@@ -980,19 +856,19 @@ int h2y_codelight_batch(h2y_ctx *ctx, const h2y_codelight_desc *d, int n_frames,
     codelight_frame *h;
     rc = codelight_tables(ctx, p);
     if (!rc) rc = frame_table(ctx, n_frames, h);
-    if (!rc) rc = ensure(ctx, ctx->d_codelight, ctx->codelight_cap, ws);
-    if (!rc && p.sub) rc = ensure(ctx, ctx->d_codelight_up, ctx->codelight_up_cap, (size_t)per_launch * 2u * p.plane_al);
+    if (!rc) rc = ensure(ctx, ctx->codelight, ws);
+    if (!rc && p.sub) rc = ensure(ctx, ctx->codelight_up, (size_t)per_launch * 2u * p.plane_al);
     if (rc) return rc;
+    char *d_ws = ctx->codelight.p, *d_up = ctx->codelight_up.p;
     /* frame f's upsampled chroma lies in the scratch of its place in its launch; the launches follow one another on one stream */
-    for (int f = 0; f < n_frames; f++)
-        h[f] = codelight_entry(p, d_frames[f], p.sub ? ctx->d_codelight_up + (size_t)(f % per_launch) * 2u * p.plane_al : nullptr);
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_codelight, 0, ws, ctx->stream));
-    light_acc *d_acc = reinterpret_cast<light_acc *>(ctx->d_codelight);
-    lightdist_acc *d_dacc = dist ? reinterpret_cast<lightdist_acc *>(ctx->d_codelight + dist_off) : nullptr;
-    uint32_t *d_bins = dist ? reinterpret_cast<uint32_t *>(ctx->d_codelight + dist_off + L.bins) : nullptr;
+    for (int f = 0; f < n_frames; f++) h[f] = codelight_entry(p, d_frames[f], p.sub ? d_up + (size_t)(f % per_launch) * 2u * p.plane_al : nullptr);
+    HIP_TRY(ctx, hipMemsetAsync(d_ws, 0, ws, ctx->stream));
+    light_acc *d_acc = reinterpret_cast<light_acc *>(d_ws);
+    lightdist_acc *d_dacc = dist ? reinterpret_cast<lightdist_acc *>(d_ws + dist_off) : nullptr;
+    uint32_t *d_bins = dist ? reinterpret_cast<uint32_t *>(d_ws + dist_off + L.bins) : nullptr;
     rc = timed_launches(ctx, h, n_frames, H2Y_CODELIGHT_FRAMES_PER_LAUNCH, "k_codelight", [&](const codelight_frame *frames, int f0, int nf) {
         for (int f = 0; p.sub && f < nf; f++) {
-            const hipError_t e = codelight_upsample(ctx, p, d_frames[f0 + f], ctx->d_codelight_up + (size_t)f * 2u * p.plane_al);
+            const hipError_t e = codelight_upsample(ctx, p, d_frames[f0 + f], d_up + (size_t)f * 2u * p.plane_al);
             if (e != hipSuccess) return e;
         }
         return h2y_launch_codelight(p.matrix, h2y_codelight_grid(p.a.npix, nf), ctx->stream, p.a, frames, nf, d_acc + f0,
@@ -1042,23 +918,32 @@ struct codelight_stage : ring_stage {
     }
 };
 
-static bool codelight_light_result(const h2y_ctx *ctx, h2y_light_stats *out)
+/* The light and the distribution of the frame handed out last: a forward ring's stages', or the light-only ring's */
+int h2y_stream_light_result(h2y_ctx *ctx, h2y_light_stats *out)
 {
-    const codelight_stage *st = ctx->streaming ? stage_of<codelight_stage>(ctx, STAGE_CODELIGHT) : nullptr;
-    if (!st || ctx->s_lent < 0) return false;
-    light_finish(*reinterpret_cast<const light_acc *>(st->ss[ctx->s_lent].h), (uint32_t)ctx->s_frame.width, st->p.a.npix, out);
-    return true;
+    if (!ctx || !out) return fail(ctx, H2Y_EINVAL, "null argument");
+    const light_stage *st = ctx->streaming ? stage_of<light_stage>(ctx, STAGE_LIGHT) : nullptr;
+    const codelight_stage *cl = ctx->streaming ? stage_of<codelight_stage>(ctx, STAGE_CODELIGHT) : nullptr;
+    if (!st && !cl) return fail(ctx, H2Y_EINVAL, "no stream open that measures content light");
+    const int rc = output_taken(ctx);
+    if (rc) return rc;
+    if (cl) light_finish(*reinterpret_cast<const light_acc *>(cl->ss[ctx->s_lent].h), (uint32_t)ctx->s_frame.width, cl->p.a.npix, out);
+    else light_finish(*st->ss[ctx->s_lent].h, (uint32_t)ctx->s_desc.width, st->a.npix, out);
+    return H2Y_OK;
 }
 
-static int codelight_dist_result(h2y_ctx *ctx, h2y_lightdist_stats *out, bool *mine)
+int h2y_stream_lightdist_result(h2y_ctx *ctx, h2y_lightdist_stats *out)
 {
-    const codelight_stage *st = ctx->streaming ? stage_of<codelight_stage>(ctx, STAGE_CODELIGHT) : nullptr;
-    *mine = st != nullptr;
-    if (!st) return H2Y_OK;
-    if (!st->dist) return fail(ctx, H2Y_EINVAL, "the light-only ring was opened without want_dist");
-    if (ctx->s_lent < 0) return fail(ctx, H2Y_EINVAL, "no output taken yet: h2y_stream_output first");
-    const char *h = st->ss[ctx->s_lent].h + codelight_dist_off(1);
-    lightdist_finish(*reinterpret_cast<const lightdist_acc *>(h), reinterpret_cast<const uint32_t *>(h + lightdist_layout_of(1).bins), st->p.a.npix, out);
+    if (!ctx || !out) return fail(ctx, H2Y_EINVAL, "null argument");
+    const codelight_stage *cl = ctx->streaming ? stage_of<codelight_stage>(ctx, STAGE_CODELIGHT) : nullptr;
+    const lightdist_stage *st = ctx->streaming ? stage_of<lightdist_stage>(ctx, STAGE_LIGHTDIST) : nullptr;
+    if (cl && !cl->dist) return fail(ctx, H2Y_EINVAL, "the light-only ring was opened without want_dist");
+    if (!cl && !st) return fail(ctx, H2Y_EINVAL, "no stream open that measures the light distribution");
+    const int rc = output_taken(ctx);
+    if (rc) return rc;
+    const char *h = cl ? cl->ss[ctx->s_lent].h + codelight_dist_off(1) : st->ss[ctx->s_lent].h;
+    lightdist_finish(*reinterpret_cast<const lightdist_acc *>(h), reinterpret_cast<const uint32_t *>(h + lightdist_layout_of(1).bins),
+                     cl ? cl->p.a.npix : st->a.npix, out);
     return H2Y_OK;
 }
 
@@ -1113,15 +998,16 @@ int h2y_scenesig_batch(h2y_ctx *ctx, const h2y_desc *d, int n_frames, const void
     light_args a;
     light_frame *h;
     int rc = light_batch_prepare(ctx, d, n_frames, d_planes, out, a, h);
-    if (!rc) rc = ensure(ctx, ctx->d_scenesig, ctx->scenesig_cap, (size_t)n_frames * kSigBytes);
+    if (!rc) rc = ensure(ctx, ctx->scenesig, (size_t)n_frames * kSigBytes);
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_scenesig, 0, (size_t)n_frames * kSigBytes, ctx->stream));
+    unsigned long long *d_sig = ctx->scenesig.p;
+    HIP_TRY(ctx, hipMemsetAsync(d_sig, 0, (size_t)n_frames * kSigBytes, ctx->stream));
     const int in_kind = in_kind_of(d);
     rc = timed_launches(ctx, h, n_frames, H2Y_SCENESIG_FRAMES_PER_LAUNCH, "k_scenesig", [&](const light_frame *frames, int f0, int nf) {
         return h2y_launch_scenesig(in_kind, ctx->stream, a, h2y_scenesig_geom((uint32_t)d->width, (uint32_t)d->height, 4u, nf), frames, nf,
-                                   ctx->d_scenesig + (size_t)f0 * kSigCells);
+                                   d_sig + (size_t)f0 * kSigCells);
     });
-    if (!rc) rc = scenesig_finish(ctx, ctx->d_scenesig, n_frames, a.npix, out);
+    if (!rc) rc = scenesig_finish(ctx, d_sig, n_frames, a.npix, out);
     if (rc) return rc;
     ctx->last_variant = "k_scenesig" + light_variant(d, a).substr(strlen("k_light"));
     return H2Y_OK;
@@ -1129,37 +1015,33 @@ int h2y_scenesig_batch(h2y_ctx *ctx, const h2y_desc *d, int n_frames, const void
 
 int h2y_codescenesig_batch(h2y_ctx *ctx, const h2y_codelight_desc *d, int n_frames, const uint16_t *const *d_frames, h2y_scenesig *out)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
     codelight_plan p;
-    int rc = codelight_check(ctx, d, p);
+    int rc = batch_enter(ctx);
+    if (!rc) rc = codelight_check(ctx, d, p);
+    if (!rc) rc = frames_check(ctx, n_frames, d_frames, out != nullptr);
     if (rc) return rc;
-    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
-    if (!d_frames || !out) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
-    for (int f = 0; f < n_frames; f++) {
-        if (!d_frames[f]) return fail(ctx, H2Y_EINVAL, "frame %d is null", f);
-        if ((uintptr_t)d_frames[f] & 15u) return fail(ctx, H2Y_EINVAL, "frame %d is not 16-byte aligned", f);
-    }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int per_launch = std::min(n_frames, H2Y_CODELIGHT_FRAMES_PER_LAUNCH);
     codelight_frame *h;
     rc = codelight_tables(ctx, p);
     if (!rc) rc = frame_table(ctx, n_frames, h);
-    if (!rc) rc = ensure(ctx, ctx->d_scenesig, ctx->scenesig_cap, (size_t)n_frames * kSigBytes);
-    if (!rc && p.sub) rc = ensure(ctx, ctx->d_codelight_up, ctx->codelight_up_cap, (size_t)per_launch * 2u * p.plane_al);
+    if (!rc) rc = ensure(ctx, ctx->scenesig, (size_t)n_frames * kSigBytes);
+    if (!rc && p.sub) rc = ensure(ctx, ctx->codelight_up, (size_t)per_launch * 2u * p.plane_al);
     if (rc) return rc;
+    unsigned long long *d_sig = ctx->scenesig.p;
+    char *d_up = ctx->codelight_up.p;
     for (int f = 0; f < n_frames; f++) /* as h2y_codelight_batch: the upsampled chroma in the scratch of the frame's place in its launch */
-        h[f] = codelight_entry(p, d_frames[f], p.sub ? ctx->d_codelight_up + (size_t)(f % per_launch) * 2u * p.plane_al : nullptr);
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_scenesig, 0, (size_t)n_frames * kSigBytes, ctx->stream));
+        h[f] = codelight_entry(p, d_frames[f], p.sub ? d_up + (size_t)(f % per_launch) * 2u * p.plane_al : nullptr);
+    HIP_TRY(ctx, hipMemsetAsync(d_sig, 0, (size_t)n_frames * kSigBytes, ctx->stream));
     rc = timed_launches(ctx, h, n_frames, H2Y_CODELIGHT_FRAMES_PER_LAUNCH, "k_codescenesig", [&](const codelight_frame *frames, int f0, int nf) {
         for (int f = 0; p.sub && f < nf; f++) {
-            const hipError_t e = codelight_upsample(ctx, p, d_frames[f0 + f], ctx->d_codelight_up + (size_t)f * 2u * p.plane_al);
+            const hipError_t e = codelight_upsample(ctx, p, d_frames[f0 + f], d_up + (size_t)f * 2u * p.plane_al);
             if (e != hipSuccess) return e;
         }
         return h2y_launch_codescenesig(p.matrix, ctx->stream, p.a, h2y_scenesig_geom((uint32_t)p.width, (uint32_t)p.height, 8u, nf), frames, nf,
-                                       ctx->d_scenesig + (size_t)f0 * kSigCells);
+                                       d_sig + (size_t)f0 * kSigCells);
     });
-    if (!rc) rc = scenesig_finish(ctx, ctx->d_scenesig, n_frames, p.a.npix, out);
+    if (!rc) rc = scenesig_finish(ctx, d_sig, n_frames, p.a.npix, out);
     if (rc) return rc;
     ctx->last_variant = std::string("k_codescenesig<") + matrix_name(p.matrix) + "," +
                         (!p.sub ? "444" : p.form == UP_FIR_TL ? "FIR_TL" : p.form == UP_FIR ? "FIR" : "REPLICATE") + ">";
@@ -1198,16 +1080,15 @@ struct scenesig_stage : ring_stage {
 
 int h2y_stream_scenesig(h2y_ctx *ctx)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    int rc = arm_enter(ctx);
+    if (rc) return rc;
     const codelight_stage *cl = stage_of<codelight_stage>(ctx, STAGE_CODELIGHT);
     if (!cl && ctx->s_kind != h2y_ctx::RING_FORWARD)
         return fail(ctx, H2Y_EINVAL, "the scene signature is measured on the forward rings and the light-only ring only");
-    if (ctx->s_stage[STAGE_SCENESIG]) return fail(ctx, H2Y_EINVAL, "the ring measures the scene signature already");
-    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    rc = arm_free(ctx, STAGE_SCENESIG, "the ring measures the scene signature already");
+    if (rc) return rc;
     auto st = std::make_unique<scenesig_stage>();
     const int depth = (int)ctx->ss.size();
-    std::vector<light_frame> tab(depth);
     if (cl) {
         st->code = true;
         st->npix = cl->p.a.npix;
@@ -1215,36 +1096,30 @@ int h2y_stream_scenesig(h2y_ctx *ctx)
         HIP_TRY(ctx, hipSetDevice(ctx->device));
     } else {
         const h2y_desc *d = &ctx->s_desc;
-        int rc = light_check(ctx, d);
+        rc = light_check(ctx, d);
         if (rc) return rc;
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         rc = light_args_of(ctx, d, st->a);
         if (rc) return rc;
         st->npix = st->a.npix;
         st->g = h2y_scenesig_geom((uint32_t)d->width, (uint32_t)d->height, 4u, 1);
-        for (int k = 0; k < depth; k++) {
-            for (int c = 0; c < 3; c++) tab[k].in[c] = ctx->ss[k].d_in + c * ctx->s_plane_al;
-            tab[k].assumed = ctx->b->d_assumed;
-        }
     }
     st->ss.resize(depth);
     for (int k = 0; k < depth; k++) {
         st->dev_alloc(st->ss[k].d, kSigBytes);
         st->pin_alloc(st->ss[k].h, kSigBytes);
     }
-    if (!cl) st->table(st->tab, tab);
+    if (!cl) st->table(st->tab, light_ring_table(ctx));
     return stage_arm(ctx, STAGE_SCENESIG, std::move(st), "scene signature");
 }
 
 int h2y_stream_scenesig_result(h2y_ctx *ctx, h2y_scenesig *out)
 {
-    if (!ctx || !out) return fail(ctx, H2Y_EINVAL, "null argument");
-    const scenesig_stage *st = ctx->streaming ? stage_of<scenesig_stage>(ctx, STAGE_SCENESIG) : nullptr;
-    if (!st) return fail(ctx, H2Y_EINVAL, "no stream open that measures the scene signature");
-    if (ctx->s_lent < 0) return fail(ctx, H2Y_EINVAL, "no output taken yet: h2y_stream_output first");
-    for (size_t c = 0; c < kSigCells; c++) out->cell[c] = st->ss[ctx->s_lent].h[c];
-    out->pixels = st->npix;
-    return H2Y_OK;
+    return stream_result<scenesig_stage>(ctx, out, STAGE_SCENESIG, "no stream open that measures the scene signature",
+                                         [&](const scenesig_stage &st, int k) {
+                                             for (size_t c = 0; c < kSigCells; c++) out->cell[c] = st.ss[k].h[c];
+                                             out->pixels = st.npix;
+                                         });
 }
 
 int h2y_stream_lightdist_bins(h2y_ctx *ctx, uint32_t *bins)
@@ -1253,7 +1128,8 @@ int h2y_stream_lightdist_bins(h2y_ctx *ctx, uint32_t *bins)
     const codelight_stage *cl = ctx->streaming ? stage_of<codelight_stage>(ctx, STAGE_CODELIGHT) : nullptr;
     const lightdist_stage *st = ctx->streaming ? stage_of<lightdist_stage>(ctx, STAGE_LIGHTDIST) : nullptr;
     if (!(cl && cl->dist) && !st) return fail(ctx, H2Y_EINVAL, "no stream open that measures the light distribution");
-    if (ctx->s_lent < 0) return fail(ctx, H2Y_EINVAL, "no output taken yet: h2y_stream_output first");
+    const int rc = output_taken(ctx);
+    if (rc) return rc;
     const char *h = cl ? cl->ss[ctx->s_lent].h + codelight_dist_off(1) : st->ss[ctx->s_lent].h;
     memcpy(bins, h + lightdist_layout_of(1).bins, H2Y_LIGHTDIST_BINS * sizeof(uint32_t));
     return H2Y_OK;
@@ -1429,42 +1305,37 @@ static void deltae_finish(const deltae_acc &acc, uint32_t width, uint32_t npix, 
 int h2y_deltae_batch(h2y_ctx *ctx, const h2y_codelight_desc *d, float threshold, int n_frames, const uint16_t *const *d_a,
                      const uint16_t *const *d_b, h2y_deltae_stats *out)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
     codelight_plan p;
-    int rc = codelight_check(ctx, d, p);
+    int rc = batch_enter(ctx);
+    if (!rc) rc = codelight_check(ctx, d, p);
+    if (!rc) rc = pairs_check(ctx, n_frames, d_a, d_b, out != nullptr);
     if (rc) return rc;
-    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
-    if (!d_a || !d_b || !out) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
-    for (int f = 0; f < n_frames; f++) {
-        if (!d_a[f] || !d_b[f]) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is null", f);
-        if (((uintptr_t)d_a[f] | (uintptr_t)d_b[f]) & 15u) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is not 16-byte aligned", f);
-    }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int per_launch = std::min(n_frames, H2Y_DELTAE_FRAMES_PER_LAUNCH);
     deltae_args a;
     deltae_frame *h;
     rc = deltae_args_of(ctx, p, threshold, a);
     if (!rc) rc = frame_table(ctx, n_frames, h);
-    if (!rc) rc = ensure(ctx, ctx->d_deltae, ctx->deltae_cap, (size_t)n_frames * sizeof(deltae_acc));
-    if (!rc && p.sub) rc = ensure(ctx, ctx->d_codelight_up, ctx->codelight_up_cap, (size_t)per_launch * 4u * p.plane_al);
+    if (!rc) rc = ensure(ctx, ctx->deltae, (size_t)n_frames * sizeof(deltae_acc));
+    if (!rc && p.sub) rc = ensure(ctx, ctx->codelight_up, (size_t)per_launch * 4u * p.plane_al);
     if (rc) return rc;
+    deltae_acc *d_acc = ctx->deltae.p;
+    char *d_up = ctx->codelight_up.p;
     /* pair f's upsampled chroma lies in the scratch of its place in its launch; the launches follow one another on one stream */
     for (int f = 0; f < n_frames; f++)
-        h[f] = deltae_entry(p, p.off, d_a[f], d_b[f], p.sub ? ctx->d_codelight_up + (size_t)(f % per_launch) * 4u * p.plane_al : nullptr);
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_deltae, 0, (size_t)n_frames * sizeof(deltae_acc), ctx->stream));
+        h[f] = deltae_entry(p, p.off, d_a[f], d_b[f], p.sub ? d_up + (size_t)(f % per_launch) * 4u * p.plane_al : nullptr);
+    HIP_TRY(ctx, hipMemsetAsync(d_acc, 0, (size_t)n_frames * sizeof(deltae_acc), ctx->stream));
     rc = timed_launches(ctx, h, n_frames, H2Y_DELTAE_FRAMES_PER_LAUNCH, "k_deltae", [&](const deltae_frame *frames, int f0, int nf) {
         for (int f = 0; p.sub && f < nf; f++) {
             const uint16_t *xa = d_a[f0 + f], *xb = d_b[f0 + f];
-            const hipError_t e = deltae_upsample(ctx, p, xa + p.off[1], xa + p.off[2], xb + p.off[1], xb + p.off[2],
-                                                 ctx->d_codelight_up + (size_t)f * 4u * p.plane_al);
+            const hipError_t e = deltae_upsample(ctx, p, xa + p.off[1], xa + p.off[2], xb + p.off[1], xb + p.off[2], d_up + (size_t)f * 4u * p.plane_al);
             if (e != hipSuccess) return e;
         }
-        return h2y_launch_deltae(p.matrix, h2y_deltae_grid(a.c.npix, nf), ctx->stream, a, frames, nf, ctx->d_deltae + f0);
+        return h2y_launch_deltae(p.matrix, h2y_deltae_grid(a.c.npix, nf), ctx->stream, a, frames, nf, d_acc + f0);
     });
     if (rc) return rc;
     std::vector<deltae_acc> acc(n_frames);
-    HIP_TRY(ctx, hipMemcpy(acc.data(), ctx->d_deltae, (size_t)n_frames * sizeof(deltae_acc), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(acc.data(), d_acc, (size_t)n_frames * sizeof(deltae_acc), hipMemcpyDeviceToHost));
     for (int f = 0; f < n_frames; f++) deltae_finish(acc[f], (uint32_t)d->width, a.c.npix, threshold, out + f);
     ctx->last_variant = deltae_variant(p);
     return H2Y_OK;
@@ -1501,17 +1372,17 @@ struct deltae_stage : ring_stage {
 
 int h2y_stream_deltae(h2y_ctx *ctx, const h2y_codelight_desc *d, float threshold)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    int rc = arm_enter(ctx);
+    if (rc) return rc;
     if (ctx->s_stage[STAGE_CODELIGHT]) return fail(ctx, H2Y_EINVAL, "a light-only ring takes no other stage");
     if (ctx->s_stage[STAGE_DITHER]) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that dithers computes no Delta E: compare the written file instead");
     if (ctx->s_stage[STAGE_PACK]) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that packs computes no Delta E: compare the written file instead");
     const cmp_stage *cmp = stage_of<cmp_stage>(ctx, STAGE_COMPARE);
     if (!cmp) return fail(ctx, H2Y_EINVAL, "the ring is not armed for comparison: h2y_stream_compare first");
-    if (ctx->s_stage[STAGE_DELTAE]) return fail(ctx, H2Y_EINVAL, "the ring computes Delta E already");
-    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    rc = arm_free(ctx, STAGE_DELTAE, "the ring computes Delta E already");
+    if (rc) return rc;
     auto st = std::make_unique<deltae_stage>();
-    int rc = codelight_check(ctx, d, st->p); /* the inverse chroma siting is read here */
+    rc = codelight_check(ctx, d, st->p); /* the inverse chroma siting is read here */
     if (rc) return rc;
     const ring_frame &f = ctx->s_frame;
     if (d->width != f.width || d->height != f.height || d->chroma_format_idc != f.chroma)
@@ -1549,12 +1420,9 @@ int h2y_stream_deltae(h2y_ctx *ctx, const h2y_codelight_desc *d, float threshold
 
 int h2y_stream_deltae_result(h2y_ctx *ctx, h2y_deltae_stats *out)
 {
-    if (!ctx || !out) return fail(ctx, H2Y_EINVAL, "null argument");
-    const deltae_stage *st = ctx->streaming ? stage_of<deltae_stage>(ctx, STAGE_DELTAE) : nullptr;
-    if (!st) return fail(ctx, H2Y_EINVAL, "no stream open that computes Delta E");
-    if (ctx->s_lent < 0) return fail(ctx, H2Y_EINVAL, "no output taken yet: h2y_stream_output first");
-    deltae_finish(*st->ss[ctx->s_lent].h, (uint32_t)ctx->s_frame.width, st->a.c.npix, st->a.threshold, out);
-    return H2Y_OK;
+    return stream_result<deltae_stage>(ctx, out, STAGE_DELTAE, "no stream open that computes Delta E", [&](const deltae_stage &st, int k) {
+        deltae_finish(*st.ss[k].h, (uint32_t)ctx->s_frame.width, st.a.c.npix, st.a.threshold, out);
+    });
 }
 
 /* ---- linearised PQ code planes (h2y_linearize_batch, h2y_pqcode_stream_open): include/hdr2yuv_hip.h states the definition ------ */
@@ -1582,21 +1450,18 @@ static linearize_frame linearize_entry(const codelight_plan &p, const uint16_t *
 static int linearize_frames(h2y_ctx *ctx, const h2y_codelight_desc *d, code_tf tf, int n_frames, const uint16_t *const *d_frames,
                             void *const *d_planes_out)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
     codelight_plan p;
-    int rc = codelight_check(ctx, d, p);
+    int rc = batch_enter(ctx);
+    if (!rc) rc = codelight_check(ctx, d, p);
+    if (!rc)
+        rc = frames_check(ctx, n_frames, d_frames, d_planes_out != nullptr, [&](int f) {
+            for (int c = 0; c < 3; c++) {
+                if (!d_planes_out[3 * f + c]) return fail(ctx, H2Y_EINVAL, "frame %d: output plane %d is null", f, c);
+                if ((uintptr_t)d_planes_out[3 * f + c] & 15u) return fail(ctx, H2Y_EINVAL, "frame %d: output plane %d is not 16-byte aligned", f, c);
+            }
+            return (int)H2Y_OK;
+        });
     if (rc) return rc;
-    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
-    if (!d_frames || !d_planes_out) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
-    for (int f = 0; f < n_frames; f++) {
-        if (!d_frames[f]) return fail(ctx, H2Y_EINVAL, "frame %d is null", f);
-        if ((uintptr_t)d_frames[f] & 15u) return fail(ctx, H2Y_EINVAL, "frame %d is not 16-byte aligned", f);
-        for (int c = 0; c < 3; c++) {
-            if (!d_planes_out[3 * f + c]) return fail(ctx, H2Y_EINVAL, "frame %d: output plane %d is null", f, c);
-            if ((uintptr_t)d_planes_out[3 * f + c] & 15u) return fail(ctx, H2Y_EINVAL, "frame %d: output plane %d is not 16-byte aligned", f, c);
-        }
-    }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int per_launch = std::min(n_frames, H2Y_LINEARIZE_FRAMES_PER_LAUNCH);
     linearize_frame *h;
@@ -1605,14 +1470,15 @@ static int linearize_frames(h2y_ctx *ctx, const h2y_codelight_desc *d, code_tf t
     rc = tf.kind == code_tf::HLG ? hlgsrc_args_of(ctx, p, tf.param, ha) : tf.kind == code_tf::SDR ? sdrsrc_tables(ctx, p, tf.param, sa.kappa) : codelight_tables(ctx, p);
     sa.c = p.a;
     if (!rc) rc = frame_table(ctx, n_frames, h);
-    if (!rc && p.sub) rc = ensure(ctx, ctx->d_codelight_up, ctx->codelight_up_cap, (size_t)per_launch * 2u * p.plane_al);
+    if (!rc && p.sub) rc = ensure(ctx, ctx->codelight_up, (size_t)per_launch * 2u * p.plane_al);
     if (rc) return rc;
+    char *d_up = ctx->codelight_up.p;
     /* frame f's upsampled chroma lies in the scratch of its place in its launch; the launches follow one another on one stream */
     for (int f = 0; f < n_frames; f++)
-        h[f] = linearize_entry(p, d_frames[f], p.sub ? ctx->d_codelight_up + (size_t)(f % per_launch) * 2u * p.plane_al : nullptr, d_planes_out + 3 * f);
+        h[f] = linearize_entry(p, d_frames[f], p.sub ? d_up + (size_t)(f % per_launch) * 2u * p.plane_al : nullptr, d_planes_out + 3 * f);
     rc = timed_launches(ctx, h, n_frames, H2Y_LINEARIZE_FRAMES_PER_LAUNCH, linearize_kernel(tf), [&](const linearize_frame *frames, int f0, int nf) {
         for (int f = 0; p.sub && f < nf; f++) {
-            const hipError_t e = codelight_upsample(ctx, p, d_frames[f0 + f], ctx->d_codelight_up + (size_t)f * 2u * p.plane_al);
+            const hipError_t e = codelight_upsample(ctx, p, d_frames[f0 + f], d_up + (size_t)f * 2u * p.plane_al);
             if (e != hipSuccess) return e;
         }
         if (tf.kind == code_tf::HLG) return h2y_launch_hlg_linearize(p.matrix, h2y_hlg_linearize_grid(ctx->n_cu, p.a.npix, nf), ctx->stream, ha, frames, nf);
@@ -1644,20 +1510,20 @@ int h2y_sdr_linearize_batch(h2y_ctx *ctx, const h2y_codelight_desc *d, int white
 /* The forward ring's PQCODE decode.  One scratch of the context serves every slot: the frames follow one another on its stream. */
 int pqcode_scratch(h2y_ctx *ctx, const codelight_plan &p)
 {
-    return p.sub ? ensure(ctx, ctx->d_codelight_up, ctx->codelight_up_cap, 2u * p.plane_al) : H2Y_OK;
+    return p.sub ? ensure(ctx, ctx->codelight_up, 2u * p.plane_al) : H2Y_OK;
 }
 
 linearize_frame pqcode_entry(const h2y_ctx *ctx, const codelight_plan &p, const char *payload, char *const planes[3])
 {
     void *const out[3] = {planes[0], planes[1], planes[2]};
-    return linearize_entry(p, reinterpret_cast<const uint16_t *>(payload), ctx->d_codelight_up, out);
+    return linearize_entry(p, reinterpret_cast<const uint16_t *>(payload), ctx->codelight_up.p, out);
 }
 
 int pqcode_decode(h2y_ctx *ctx, int slot)
 {
     const codelight_plan &p = ctx->s_src.code;
     if (p.sub)
-        HIP_TRY(ctx, codelight_upsample(ctx, p, reinterpret_cast<const uint16_t *>(ctx->ss[slot].d_in + ctx->s_pay_off), ctx->d_codelight_up));
+        HIP_TRY(ctx, codelight_upsample(ctx, p, reinterpret_cast<const uint16_t *>(ctx->ss[slot].d_in + ctx->s_pay_off), ctx->codelight_up.p));
     const linearize_frame *fr = static_cast<const linearize_frame *>(ctx->s_tab) + slot;
     if (ctx->s_src.hlg) HIP_TRY(ctx, h2y_launch_hlg_linearize(p.matrix, h2y_hlg_linearize_grid(ctx->n_cu, p.a.npix, 1), ctx->stream, ctx->s_src.hlgsrc, fr, 1));
     else if (ctx->s_src.sdr) HIP_TRY(ctx, h2y_launch_sdr_linearize(p.matrix, h2y_sdr_linearize_grid(p.a.npix, 1), ctx->stream, sdrsrc_args{p.a, ctx->s_src.sdr_kappa}, fr, 1));
@@ -1672,11 +1538,10 @@ int pqcode_decode(h2y_ctx *ctx, int slot)
 static hist_geom hist_geom_of(int width, int height, int chroma, int bit_depth, int full_range, int gbr, int bits, const uint32_t off[3])
 {
     hist_geom g{};
-    const bool sub = chroma == H2Y_CHROMA_420;
     const clip_limits c = make_clip(bit_depth, full_range);
     for (int p = 0; p < 3; p++) {
-        const uint32_t w = p && sub ? (uint32_t)(width >> 1) : (uint32_t)width, h = p && sub ? (uint32_t)(height >> 1) : (uint32_t)height;
-        g.n[p] = w * h;
+        const plane_dim d = plane_dims(width, height, chroma, p);
+        g.n[p] = d.w * d.h;
         g.off[p] = off[p];
         g.shift[p] = off[p] & 7u;
         g.vec |= 1u << p; /* one side: the groups can always follow the plane's start */
@@ -1692,7 +1557,8 @@ static hist_geom hist_geom_of(int width, int height, int chroma, int bit_depth, 
 
 static int hist_check(h2y_ctx *ctx, int width, int height, int chroma, int bit_depth, int full_range, int gbr, int bits)
 {
-    if (width < 1 || height < 1 || (uint64_t)width * (uint64_t)height >= (1ull << 28)) return fail(ctx, H2Y_EINVAL, "bad picture size");
+    const int rc = picture_size_check(ctx, width, height);
+    if (rc) return rc;
     if (chroma == 2) return fail(ctx, H2Y_EUNSUPPORTED, "chroma_format_idc 2 (4:2:2) is not counted on this path");
     if (chroma != H2Y_CHROMA_420 && chroma != H2Y_CHROMA_444) return fail(ctx, H2Y_EINVAL, "chroma_format_idc must be 1 or 3");
     if (bit_depth < 8 || bit_depth > 16) return fail(ctx, H2Y_EINVAL, "bit_depth must be 8..16");
@@ -1727,16 +1593,10 @@ static int hist_enqueue(h2y_ctx *ctx, const hist_geom &g, const hist_frame *fram
 int h2y_histogram_batch(h2y_ctx *ctx, int width, int height, int chroma_format_idc, int bit_depth, int full_range, int gbr, int bits,
                         int n_frames, const uint16_t *const *d_frames, h2y_histogram_stats *out_stats, uint32_t *out_bins)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
-    int rc = hist_check(ctx, width, height, chroma_format_idc, bit_depth, full_range, gbr, bits);
+    int rc = batch_enter(ctx);
+    if (!rc) rc = hist_check(ctx, width, height, chroma_format_idc, bit_depth, full_range, gbr, bits);
+    if (!rc) rc = frames_check(ctx, n_frames, d_frames, out_stats != nullptr);
     if (rc) return rc;
-    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
-    if (!d_frames || !out_stats) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
-    for (int f = 0; f < n_frames; f++) {
-        if (!d_frames[f]) return fail(ctx, H2Y_EINVAL, "frame %d is null", f);
-        if ((uintptr_t)d_frames[f] & 15u) return fail(ctx, H2Y_EINVAL, "frame %d is not 16-byte aligned", f);
-    }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     uint32_t off[3];
     contiguous_planes(width, height, chroma_format_idc, off);
@@ -1745,8 +1605,9 @@ int h2y_histogram_batch(h2y_ctx *ctx, int width, int height, int chroma_format_i
     const hist_layout L = hist_layout_of(g.nbins, per_launch);
     hist_frame *h;
     rc = frame_table(ctx, n_frames, h);
-    if (!rc) rc = ensure(ctx, ctx->d_hist, ctx->hist_cap, L.total);
+    if (!rc) rc = ensure(ctx, ctx->hist, L.total);
     if (rc) return rc;
+    char *d_hist = ctx->hist.p;
     for (int f = 0; f < n_frames; f++) h[f].base = d_frames[f];
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_tab, h, (size_t)n_frames * sizeof(hist_frame), hipMemcpyHostToDevice, ctx->stream));
     const hist_frame *frames = static_cast<const hist_frame *>(ctx->d_tab);
@@ -1758,13 +1619,13 @@ int h2y_histogram_batch(h2y_ctx *ctx, int width, int height, int chroma_format_i
         const int nf = std::min(per_launch, n_frames - f0);
         const hist_layout Ln = hist_layout_of(g.nbins, nf);
         HIP_TRY(ctx, hipEventRecord(ev[0], ctx->stream));
-        rc = hist_enqueue(ctx, g, frames + f0, nf, ctx->d_hist);
+        rc = hist_enqueue(ctx, g, frames + f0, nf, d_hist);
         if (rc) return rc;
         HIP_TRY(ctx, hipEventRecord(ev[1], ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(out_stats + f0, ctx->d_hist + Ln.stats, (size_t)nf * sizeof(h2y_histogram_stats), hipMemcpyDeviceToHost,
+        HIP_TRY(ctx, hipMemcpyAsync(out_stats + f0, d_hist + Ln.stats, (size_t)nf * sizeof(h2y_histogram_stats), hipMemcpyDeviceToHost,
                                     ctx->stream));
         if (out_bins)
-            HIP_TRY(ctx, hipMemcpyAsync(out_bins + (size_t)f0 * 3u * g.nbins, ctx->d_hist + Ln.bins, (size_t)nf * 3u * g.nbins * sizeof(uint32_t),
+            HIP_TRY(ctx, hipMemcpyAsync(out_bins + (size_t)f0 * 3u * g.nbins, d_hist + Ln.bins, (size_t)nf * 3u * g.nbins * sizeof(uint32_t),
                                         hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         float t = 0.f;
@@ -1828,14 +1689,15 @@ static int hist_arm(h2y_ctx *ctx, int bit_depth, int full_range, int gbr, int bi
 
 int h2y_stream_histogram_ex(h2y_ctx *ctx, int bits, int bit_depth, int full_range, int gbr)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    int rc = arm_enter(ctx);
+    if (rc) return rc;
     if (ctx->s_stage[STAGE_HISTOGRAM]) return fail(ctx, H2Y_EINVAL, "the ring counts histograms already");
     if (ctx->s_stage[STAGE_CODELIGHT]) return fail(ctx, H2Y_EINVAL, "a light-only ring takes no other stage");
     if (ctx->s_stage[STAGE_SCALE]) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that scales counts no histograms: count the written file instead");
     if (ctx->s_stage[STAGE_DITHER]) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that dithers counts no histograms: count the written file instead");
     if (ctx->s_stage[STAGE_PACK]) return fail(ctx, H2Y_EUNSUPPORTED, "a ring that packs counts no histograms: count the written file instead");
-    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    rc = arm_unstarted(ctx);
+    if (rc) return rc;
     const ring_frame &f = ctx->s_frame;
     if (!f.depth && (bit_depth < 0 || full_range < 0 || gbr < 0))
         return fail(ctx, H2Y_EINVAL, "a compare-only ring does not know its frames' bit depth and range: h2y_stream_histogram_ex");
@@ -1848,14 +1710,10 @@ int h2y_stream_histogram(h2y_ctx *ctx, int bits) { return h2y_stream_histogram_e
 
 int h2y_stream_histogram_result(h2y_ctx *ctx, h2y_histogram_stats *out_stats, uint32_t *out_bins)
 {
-    if (!ctx || !out_stats) return fail(ctx, H2Y_EINVAL, "null argument");
-    const hist_stage *st = ctx->streaming ? stage_of<hist_stage>(ctx, STAGE_HISTOGRAM) : nullptr;
-    if (!st) return fail(ctx, H2Y_EINVAL, "no stream open that counts histograms");
-    if (ctx->s_lent < 0) return fail(ctx, H2Y_EINVAL, "no output taken yet: h2y_stream_output first");
-    const hist_stage::slot &s = st->ss[ctx->s_lent];
-    *out_stats = *s.h_stats;
-    if (out_bins) memcpy(out_bins, s.h_bins, (size_t)3u * st->g.nbins * sizeof(uint32_t));
-    return H2Y_OK;
+    return stream_result<hist_stage>(ctx, out_stats, STAGE_HISTOGRAM, "no stream open that counts histograms", [&](const hist_stage &st, int k) {
+        *out_stats = *st.ss[k].h_stats;
+        if (out_bins) memcpy(out_bins, st.ss[k].h_bins, (size_t)3u * st.g.nbins * sizeof(uint32_t));
+    });
 }
 
 /* A ring that only counts: the slot's input is the frame's three planes, the device output unused */
@@ -2037,16 +1895,10 @@ static std::string scale_variant(int chroma, int a)
 int h2y_scale_batch(h2y_ctx *ctx, int src_w, int src_h, int dst_w, int dst_h, int chroma_format_idc, int bit_depth, int full_range,
                     int gbr, int a, int n_frames, const uint16_t *const *d_src, uint16_t *const *d_dst)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
-    int rc = scale_check(ctx, src_w, src_h, dst_w, dst_h, chroma_format_idc, bit_depth, full_range, gbr, a);
+    int rc = batch_enter(ctx);
+    if (!rc) rc = scale_check(ctx, src_w, src_h, dst_w, dst_h, chroma_format_idc, bit_depth, full_range, gbr, a);
+    if (!rc) rc = pairs_check(ctx, n_frames, d_src, d_dst);
     if (rc) return rc;
-    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
-    if (!d_src || !d_dst) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
-    for (int f = 0; f < n_frames; f++) {
-        if (!d_src[f] || !d_dst[f]) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is null", f);
-        if (((uintptr_t)d_src[f] | (uintptr_t)d_dst[f]) & 15u) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is not 16-byte aligned", f);
-    }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     uint32_t src_off[3], dst_off[3];
     contiguous_planes(src_w, src_h, chroma_format_idc, src_off);
@@ -2056,10 +1908,10 @@ int h2y_scale_batch(h2y_ctx *ctx, int src_w, int src_h, int dst_w, int dst_h, in
     if (rc) return rc;
     scale_frame *h;
     rc = frame_table(ctx, n_frames, h);
-    if (!rc) rc = ensure(ctx, ctx->d_scale_tabs, ctx->scale_tabs_cap, H.blob.size());
+    if (!rc) rc = ensure(ctx, ctx->scale_tabs, H.blob.size());
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpy(ctx->d_scale_tabs, H.blob.data(), H.blob.size(), hipMemcpyHostToDevice));
-    scale_bind(H, ctx->d_scale_tabs);
+    HIP_TRY(ctx, hipMemcpy(ctx->scale_tabs.p, H.blob.data(), H.blob.size(), hipMemcpyHostToDevice));
+    scale_bind(H, ctx->scale_tabs.p);
     for (int f = 0; f < n_frames; f++) h[f] = scale_frame{d_src[f], d_dst[f]};
     rc = timed_launches(ctx, h, n_frames, H2Y_SCALE_FRAMES_PER_LAUNCH, "k_scale", [&](const scale_frame *frames, int, int nf) {
         return h2y_launch_scale(scale_grid(ctx, H.g, nf), ctx->stream, H.g, frames, nf);
@@ -2131,20 +1983,21 @@ static int scale_arm(h2y_ctx *ctx, int dw, int dh, int a)
 
 int h2y_stream_scale(h2y_ctx *ctx, int dst_w, int dst_h, int a)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    int rc = arm_enter(ctx);
+    if (rc) return rc;
     if (ctx->s_kind != h2y_ctx::RING_FORWARD) return fail(ctx, H2Y_EINVAL, "only a forward ring is armed for scaling");
     if (ctx->s_stage[STAGE_SCALE]) return fail(ctx, H2Y_EINVAL, "the ring scales already");
     if (ctx->s_stage[STAGE_DITHER]) return fail(ctx, H2Y_EINVAL, "the ring dithers already: arm scaling before dither");
     if (ctx->s_stage[STAGE_PACK]) return fail(ctx, H2Y_EINVAL, "the ring packs already: arm scaling before pack");
     if (ctx->s_stage[STAGE_COMPARE] || ctx->s_stage[STAGE_HISTOGRAM] || ctx->s_stage[STAGE_SSIM])
         return fail(ctx, H2Y_EUNSUPPORTED, "a ring armed for comparison, histograms or SSIM is not scaled: compare or count the written file instead");
-    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    rc = arm_unstarted(ctx);
+    if (rc) return rc;
     const ring_frame &f = ctx->s_frame;
     /* k_scale aligns sample centres: it would move a top-left sited chroma plane again (the setting cannot change while the ring is open) */
     if (ctx->opt_siting == 2 && f.chroma == H2Y_CHROMA_420)
         return fail(ctx, H2Y_EUNSUPPORTED, "a ring with chroma siting 2 (top-left) is not scaled: the resampler aligns sample centres");
-    int rc = scale_check(ctx, f.width, f.height, dst_w, dst_h, f.chroma, f.depth, f.full_range, f.gbr, a);
+    rc = scale_check(ctx, f.width, f.height, dst_w, dst_h, f.chroma, f.depth, f.full_range, f.gbr, a);
     if (rc) return rc;
     return scale_arm(ctx, dst_w, dst_h, a);
 }
@@ -2278,10 +2131,11 @@ static int gamut_args_of(h2y_ctx *ctx, int width, int height, int sample_type, i
     if (sample_type == H2Y_SAMPLE_U16)
         return fail(ctx, H2Y_EUNSUPPORTED, "primaries are converted in linear light on float or half planes, not on U16 samples");
     if (sample_type != H2Y_SAMPLE_F32 && sample_type != H2Y_SAMPLE_F16) return fail(ctx, H2Y_EINVAL, "bad sample type %d", sample_type);
-    if (width < 1 || height < 1 || (uint64_t)width * (uint64_t)height >= (1ull << 28)) return fail(ctx, H2Y_EINVAL, "bad picture size");
+    int rc = picture_size_check(ctx, width, height);
+    if (rc) return rc;
     if (clip != 0 && clip != 1) return fail(ctx, H2Y_EINVAL, "clip must be 0 or 1");
     const char *why;
-    const int rc = h2y_gamut_matrix(src_primaries, dst_primaries, a.m, &why);
+    rc = h2y_gamut_matrix(src_primaries, dst_primaries, a.m, &why);
     if (rc) return fail(ctx, rc, "primaries %d -> %d: %s", src_primaries, dst_primaries, why);
     a.npix = (uint32_t)width * (uint32_t)height;
     a.clip = (uint32_t)clip;
@@ -2296,25 +2150,12 @@ static std::string gamut_variant(int in_kind, const gamut_args &a)
 int h2y_gamut_batch(h2y_ctx *ctx, int width, int height, int sample_type, int src_primaries, int dst_primaries, int clip, int n_frames,
                     const void *const *d_src, void *const *d_dst)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
     gamut_args a{};
-    int rc = gamut_args_of(ctx, width, height, sample_type, src_primaries, dst_primaries, clip, a);
-    if (rc) return rc;
-    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
-    if (!d_src || !d_dst) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
-    for (int f = 0; f < n_frames; f++)
-        for (int c = 0; c < 3; c++) {
-            const void *i = d_src[3 * f + c], *o = d_dst[3 * f + c];
-            if (!i || !o) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is null", f, c);
-            if (((uintptr_t)i | (uintptr_t)o) & 15u) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is not 16-byte aligned", f, c);
-        }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     gamut_frame *h;
-    rc = frame_table(ctx, n_frames, h);
+    int rc = batch_enter(ctx);
+    if (!rc) rc = gamut_args_of(ctx, width, height, sample_type, src_primaries, dst_primaries, clip, a);
+    if (!rc) rc = pass_frames(ctx, n_frames, d_src, d_dst, false, h);
     if (rc) return rc;
-    for (int f = 0; f < n_frames; f++)
-        for (int c = 0; c < 3; c++) h[f].src[c] = d_src[3 * f + c], h[f].dst[c] = d_dst[3 * f + c];
     const int in_kind = sample_type == H2Y_SAMPLE_F16 ? H2Y_IN_F16 : H2Y_IN_F32;
     const uint64_t per_frame = h2y_gamut_chunks(in_kind, a.npix);
     rc = timed_launches(ctx, h, n_frames, H2Y_GAMUT_FRAMES_PER_LAUNCH, "k_gamut", [&](const gamut_frame *frames, int, int nf) {
@@ -2325,31 +2166,18 @@ int h2y_gamut_batch(h2y_ctx *ctx, int width, int height, int sample_type, int sr
     return H2Y_OK;
 }
 
-/* The conversion's ring stage, in place on a forward ring's decoded planes before pic_stats: k_gamut's arguments and its table entry
- * per slot.  It leaves nothing of its own behind: what follows reads the converted planes. */
-struct gamut_stage : ring_stage {
-    gamut_args a{};
-    gamut_frame *tab = nullptr;
-    int in_kind = H2Y_IN_F32;
-    int grid = 1;
-    int decoded(h2y_ctx *ctx, int k) override
-    {
-        HIP_TRY(ctx, h2y_launch_gamut(in_kind, grid, ctx->stream, a, tab + k, 1));
-        return H2Y_OK;
-    }
-    int run(h2y_ctx *, int) override { return H2Y_OK; }
-};
-
+/* The conversion's ring stage: the first pass, k_gamut on the decoded planes */
 int h2y_stream_gamut(h2y_ctx *ctx, int src_primaries, int dst_primaries, int clip)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    int rc = arm_enter(ctx);
+    if (rc) return rc;
     if (ctx->s_kind != h2y_ctx::RING_FORWARD) return fail(ctx, H2Y_EINVAL, "primaries are converted on the forward rings only");
-    if (ctx->s_stage[STAGE_GAMUT]) return fail(ctx, H2Y_EINVAL, "the ring converts primaries already");
-    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    rc = arm_free(ctx, STAGE_GAMUT, "the ring converts primaries already");
+    if (rc) return rc;
     const h2y_desc *d = &ctx->s_desc;
-    auto st = std::make_unique<gamut_stage>();
-    int rc = gamut_args_of(ctx, d->width, d->height, d->in_sample_type, src_primaries, dst_primaries, clip, st->a);
+    auto st = std::make_unique<pass_stage<gamut_args>>();
+    st->launch = h2y_launch_gamut;
+    rc = gamut_args_of(ctx, d->width, d->height, d->in_sample_type, src_primaries, dst_primaries, clip, st->a);
     if (rc) return rc;
     if (d->src_transfer != H2Y_TRANSFER_LINEAR)
         return fail(ctx, H2Y_EUNSUPPORTED, "primaries are converted in linear light (src_transfer 8), not src_transfer %d", d->src_transfer);
@@ -2358,11 +2186,7 @@ int h2y_stream_gamut(h2y_ctx *ctx, int src_primaries, int dst_primaries, int cli
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     st->in_kind = in_kind_of(d);
     st->grid = unit_grid(ctx, h2y_gamut_chunks(st->in_kind, st->a.npix));
-    const int depth = (int)ctx->ss.size();
-    std::vector<gamut_frame> tab(depth);
-    for (int k = 0; k < depth; k++)
-        for (int c = 0; c < 3; c++) tab[k].src[c] = tab[k].dst[c] = ctx->ss[k].d_in + c * ctx->s_plane_al;
-    st->table(st->tab, tab);
+    st->table(st->tab, ring_planes_table(ctx));
     return stage_arm(ctx, STAGE_GAMUT, std::move(st), "gamut");
 }
 
@@ -2424,10 +2248,11 @@ static int tonemap_args_of(h2y_ctx *ctx, int width, int height, int sample_type,
     if (sample_type == H2Y_SAMPLE_U16)
         return fail(ctx, H2Y_EUNSUPPORTED, "tone mapping works in linear light on float or half planes, not on U16 samples");
     if (sample_type != H2Y_SAMPLE_F32 && sample_type != H2Y_SAMPLE_F16) return fail(ctx, H2Y_EINVAL, "bad sample type %d", sample_type);
-    if (width < 1 || height < 1 || (uint64_t)width * (uint64_t)height >= (1ull << 28)) return fail(ctx, H2Y_EINVAL, "bad picture size");
+    int rc = picture_size_check(ctx, width, height);
+    if (rc) return rc;
     gain.resize(H2Y_LIGHTDIST_BINS);
     const char *why;
-    const int rc = h2y_tonemap_curve(src_peak, dst_peak, relative, gain.data(), &a.cap, &why);
+    rc = h2y_tonemap_curve(src_peak, dst_peak, relative, gain.data(), &a.cap, &why);
     if (rc) return fail(ctx, rc, "tone map %d -> %d cd/m2, relative %d: %s", src_peak, dst_peak, relative, why);
     a.npix = (uint32_t)width * (uint32_t)height;
     return H2Y_OK;
@@ -2436,29 +2261,16 @@ static int tonemap_args_of(h2y_ctx *ctx, int width, int height, int sample_type,
 int h2y_tonemap_batch(h2y_ctx *ctx, int width, int height, int sample_type, int src_peak, int dst_peak, int relative, int n_frames,
                       const void *const *d_src, void *const *d_dst)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
     tonemap_args a{};
     std::vector<float> gain;
-    int rc = tonemap_args_of(ctx, width, height, sample_type, src_peak, dst_peak, relative, a, gain);
-    if (rc) return rc;
-    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
-    if (!d_src || !d_dst) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
-    for (int f = 0; f < n_frames; f++)
-        for (int c = 0; c < 3; c++) {
-            const void *i = d_src[3 * f + c], *o = d_dst[3 * f + c];
-            if (!i || !o) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is null", f, c);
-            if (((uintptr_t)i | (uintptr_t)o) & 15u) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is not 16-byte aligned", f, c);
-        }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     gamut_frame *h;
-    rc = frame_table(ctx, n_frames, h);
-    if (!rc) rc = ensure(ctx, ctx->d_tonemap_gain, ctx->tonemap_gain_cap, gain.size() * sizeof(float));
+    int rc = batch_enter(ctx);
+    if (!rc) rc = tonemap_args_of(ctx, width, height, sample_type, src_peak, dst_peak, relative, a, gain);
+    if (!rc) rc = pass_frames(ctx, n_frames, d_src, d_dst, false, h);
+    if (!rc) rc = ensure(ctx, ctx->tonemap_gain, gain.size() * sizeof(float));
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpy(ctx->d_tonemap_gain, gain.data(), gain.size() * sizeof(float), hipMemcpyHostToDevice));
-    a.gain = ctx->d_tonemap_gain;
-    for (int f = 0; f < n_frames; f++)
-        for (int c = 0; c < 3; c++) h[f].src[c] = d_src[3 * f + c], h[f].dst[c] = d_dst[3 * f + c];
+    HIP_TRY(ctx, hipMemcpy(ctx->tonemap_gain.p, gain.data(), gain.size() * sizeof(float), hipMemcpyHostToDevice));
+    a.gain = ctx->tonemap_gain.p;
     const int in_kind = sample_type == H2Y_SAMPLE_F16 ? H2Y_IN_F16 : H2Y_IN_F32;
     const uint64_t per_frame = h2y_gamut_chunks(in_kind, a.npix);
     rc = timed_launches(ctx, h, n_frames, H2Y_TONEMAP_FRAMES_PER_LAUNCH, "k_tonemap", [&](const gamut_frame *frames, int, int nf) {
@@ -2469,61 +2281,37 @@ int h2y_tonemap_batch(h2y_ctx *ctx, int width, int height, int sample_type, int 
     return H2Y_OK;
 }
 
-/* The curve's ring stage, in place on a forward ring's decoded planes after the gamut stage's pass and before the conversion:
- * k_tonemap's arguments, the gain table and its frame table entry per slot.  It leaves nothing of its own behind. */
-struct tonemap_stage : ring_stage {
-    tonemap_args a{};
-    gamut_frame *tab = nullptr;
-    int in_kind = H2Y_IN_F32;
-    int grid = 1;
-    int decoded(h2y_ctx *ctx, int k) override
-    {
-        HIP_TRY(ctx, h2y_launch_tonemap(in_kind, grid, ctx->stream, a, tab + k, 1));
-        return H2Y_OK;
-    }
-    int run(h2y_ctx *, int) override { return H2Y_OK; }
-};
-
+/* The curve's ring stage: k_tonemap after the gamut stage's pass, with the gain table of its own */
 int h2y_stream_tonemap(h2y_ctx *ctx, int src_peak, int dst_peak, int relative)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    int rc = arm_enter(ctx);
+    if (rc) return rc;
     if (ctx->s_kind != h2y_ctx::RING_FORWARD) return fail(ctx, H2Y_EINVAL, "tone mapping works on the forward rings only");
-    if (ctx->s_stage[STAGE_TONEMAP]) return fail(ctx, H2Y_EINVAL, "the ring maps tones already");
-    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    rc = arm_free(ctx, STAGE_TONEMAP, "the ring maps tones already");
+    if (rc) return rc;
     const h2y_desc *d = &ctx->s_desc;
-    auto st = std::make_unique<tonemap_stage>();
+    auto st = std::make_unique<pass_stage<tonemap_args>>();
+    st->launch = h2y_launch_tonemap;
     std::vector<float> gain;
-    int rc = tonemap_args_of(ctx, d->width, d->height, d->in_sample_type, src_peak, dst_peak, relative, st->a, gain);
+    rc = tonemap_args_of(ctx, d->width, d->height, d->in_sample_type, src_peak, dst_peak, relative, st->a, gain);
     if (rc) return rc;
     if (d->src_transfer != H2Y_TRANSFER_LINEAR)
         return fail(ctx, H2Y_EUNSUPPORTED, "tone mapping works in linear light (src_transfer 8), not src_transfer %d", d->src_transfer);
     if (d->src_matrix != H2Y_MATRIX_GBR)
         return fail(ctx, H2Y_EUNSUPPORTED, "tone mapping needs a G,B,R source (src_matrix 0), not src_matrix %d", d->src_matrix);
-    bool unit = d->stats_override == 1;
-    for (int c = 0; c < 3; c++) unit = unit && d->floor[c] == 0 && d->ceiling[c] == 1;
-    if (!unit)
-        return fail(ctx, H2Y_EINVAL, "tone-mapped planes are referred to their target: open the ring with stats_override 1, floor 0 and "
-                                     "ceiling 1 on all three planes");
+    rc = unit_range_check(ctx, d, "tone-mapped planes are referred to their target");
+    if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     st->in_kind = in_kind_of(d);
     st->grid = h2y_tonemap_grid(ctx->n_cu, h2y_gamut_chunks(st->in_kind, st->a.npix));
     float *d_gain = nullptr;
     st->table(d_gain, gain);
     st->a.gain = d_gain;
-    const int depth = (int)ctx->ss.size();
-    std::vector<gamut_frame> tab(depth);
-    for (int k = 0; k < depth; k++)
-        for (int c = 0; c < 3; c++) tab[k].src[c] = tab[k].dst[c] = ctx->ss[k].d_in + c * ctx->s_plane_al;
-    st->table(st->tab, tab);
+    st->table(st->tab, ring_planes_table(ctx));
     return stage_arm(ctx, STAGE_TONEMAP, std::move(st), "tone map");
 }
 
 /* ---- 3D LUT (--lut3d; the reference has no LUT step): include/hdr2yuv_hip.h states the definition ------------------------------------- */
-
-#include <cstdarg>
-
-#include "h2y_lut3d1.h"
 
 /* a parsed .cube table: the nodes as the kernel reads them */
 struct h2y_lut3d {
@@ -2739,8 +2527,8 @@ static int lut3d_args_of(h2y_ctx *ctx, int width, int height, int sample_type, c
     if (sample_type == H2Y_SAMPLE_U16)
         return fail(ctx, H2Y_EUNSUPPORTED, "the LUT pass works on float or half planes, not on U16 samples");
     if (sample_type != H2Y_SAMPLE_F32 && sample_type != H2Y_SAMPLE_F16) return fail(ctx, H2Y_EINVAL, "bad sample type %d", sample_type);
-    if (width < 1 || height < 1 || (uint64_t)width * (uint64_t)height >= (1ull << 28)) return fail(ctx, H2Y_EINVAL, "bad picture size");
-    const int rc = lut3d_setup(ctx, lut, interp, signal, dst_bit_depth, dst_full_range, dst_matrix, a.c);
+    int rc = picture_size_check(ctx, width, height);
+    if (!rc) rc = lut3d_setup(ctx, lut, interp, signal, dst_bit_depth, dst_full_range, dst_matrix, a.c);
     if (rc) return rc;
     a.npix = (uint32_t)width * (uint32_t)height;
     return H2Y_OK;
@@ -2758,31 +2546,17 @@ static int lut3d_in_lds(const h2y_ctx *ctx, const h2y_lut3d *lut) { return ctx->
 int h2y_lut3d_batch(h2y_ctx *ctx, int width, int height, int sample_type, const h2y_lut3d *lut, int interp, int signal, int dst_bit_depth,
                     int dst_full_range, int dst_matrix, int n_frames, const void *const *d_src, void *const *d_dst)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
     lut3d_args a{};
-    int rc = lut3d_args_of(ctx, width, height, sample_type, lut, interp, signal, dst_bit_depth, dst_full_range, dst_matrix, a);
-    if (rc) return rc;
-    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
-    if (!d_src || !d_dst) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
-    for (int f = 0; f < n_frames; f++)
-        for (int c = 0; c < 3; c++) {
-            const void *i = d_src[3 * f + c], *o = d_dst[3 * f + c];
-            if (!i || !o) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is null", f, c);
-            if (((uintptr_t)i | (uintptr_t)o) & 15u) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is not 16-byte aligned", f, c);
-            if (i == o && signal && sample_type == H2Y_SAMPLE_F16)
-                return fail(ctx, H2Y_EINVAL, "frame %d: plane %d in place: half planes are widened, the float planes need room of their own", f, c);
-        }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     gamut_frame *h;
-    const size_t table_bytes = lut->nodes.size() * sizeof(lut3d_node);
-    rc = frame_table(ctx, n_frames, h);
-    if (!rc) rc = ensure(ctx, ctx->d_lut3d, ctx->lut3d_cap, table_bytes);
+    int rc = batch_enter(ctx);
+    if (!rc) rc = lut3d_args_of(ctx, width, height, sample_type, lut, interp, signal, dst_bit_depth, dst_full_range, dst_matrix, a);
+    if (!rc) rc = pass_frames(ctx, n_frames, d_src, d_dst, signal && sample_type == H2Y_SAMPLE_F16, h);
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpy(ctx->d_lut3d, lut->nodes.data(), table_bytes, hipMemcpyHostToDevice));
-    a.nodes = ctx->d_lut3d;
-    for (int f = 0; f < n_frames; f++)
-        for (int c = 0; c < 3; c++) h[f].src[c] = d_src[3 * f + c], h[f].dst[c] = d_dst[3 * f + c];
+    const size_t table_bytes = lut->nodes.size() * sizeof(lut3d_node);
+    rc = ensure(ctx, ctx->lut3d, table_bytes);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpy(ctx->lut3d.p, lut->nodes.data(), table_bytes, hipMemcpyHostToDevice));
+    a.nodes = ctx->lut3d.p;
     const int in_kind = sample_type == H2Y_SAMPLE_F16 ? H2Y_IN_F16 : H2Y_IN_F32;
     const int lds = lut3d_in_lds(ctx, lut);
     const uint64_t per_frame = h2y_lut3d_chunks(lds, in_kind, a.npix);
@@ -2794,9 +2568,8 @@ int h2y_lut3d_batch(h2y_ctx *ctx, int width, int height, int sample_type, const 
     return H2Y_OK;
 }
 
-/* The pass's ring stage, in place on a forward ring's decoded planes after the gamut and tone-map stages' passes and before the HLG
- * and ICtCp stages', pic_stats and the conversion: k_lut3d's arguments, the table and its frame table entry per slot.  It leaves
- * nothing of its own behind: what follows reads the planes it left. */
+/* The LUT's ring stage, after the gamut and tone-map stages' passes and before the HLG and ICtCp stages': as pass_stage, with
+ * k_lut3d's three more launch parameters and the table of its own (its launch wrapper takes them, so it is a stage of its own) */
 struct lut3d_stage : ring_stage {
     lut3d_args a{};
     gamut_frame *tab = nullptr;
@@ -2819,23 +2592,20 @@ static bool lut3d_leaves_codes(const h2y_ctx *ctx)
 
 int h2y_stream_lut3d(h2y_ctx *ctx, const h2y_lut3d *lut, int interp, int signal)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    int rc = arm_enter(ctx);
+    if (rc) return rc;
     if (ctx->s_kind != h2y_ctx::RING_FORWARD) return fail(ctx, H2Y_EINVAL, "a LUT is applied on the forward rings only");
-    if (ctx->s_stage[STAGE_LUT3D]) return fail(ctx, H2Y_EINVAL, "the ring applies a LUT already");
-    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    rc = arm_free(ctx, STAGE_LUT3D, "the ring applies a LUT already");
+    if (rc) return rc;
     const h2y_desc *d = &ctx->s_desc;
     auto st = std::make_unique<lut3d_stage>();
-    int rc = lut3d_args_of(ctx, d->width, d->height, d->in_sample_type, lut, interp, signal, d->dst_bit_depth, d->dst_full_range, d->dst_matrix,
+    rc = lut3d_args_of(ctx, d->width, d->height, d->in_sample_type, lut, interp, signal, d->dst_bit_depth, d->dst_full_range, d->dst_matrix,
                            st->a);
     if (rc) return rc;
     if (d->src_matrix != H2Y_MATRIX_GBR)
         return fail(ctx, H2Y_EUNSUPPORTED, "a LUT needs a G,B,R source (src_matrix 0), not src_matrix %d", d->src_matrix);
-    bool unit = d->stats_override == 1;
-    for (int c = 0; c < 3; c++) unit = unit && d->floor[c] == 0 && d->ceiling[c] == 1;
-    if (!unit)
-        return fail(ctx, H2Y_EINVAL, "a LUT's planes are referred to its own range: open the ring with stats_override 1, floor 0 and "
-                                     "ceiling 1 on all three planes");
+    rc = unit_range_check(ctx, d, "a LUT's planes are referred to its own range");
+    if (rc) return rc;
     if (signal) {
         if (ctx->s_stage[STAGE_HLG] || ctx->s_stage[STAGE_ICTCP])
             return fail(ctx, H2Y_EINVAL, "the ring writes %s: a LUT in signal mode leaves code values too", ctx->s_stage[STAGE_HLG] ? "HLG" : "ICtCp");
@@ -2854,17 +2624,11 @@ int h2y_stream_lut3d(h2y_ctx *ctx, const h2y_lut3d *lut, int interp, int signal)
     lut3d_node *d_nodes = nullptr;
     st->table(d_nodes, lut->nodes);
     st->a.nodes = d_nodes;
-    const int depth = (int)ctx->ss.size();
-    std::vector<gamut_frame> tab(depth);
-    for (int k = 0; k < depth; k++)
-        for (int c = 0; c < 3; c++) tab[k].src[c] = tab[k].dst[c] = ctx->ss[k].d_in + c * ctx->s_plane_al;
-    st->table(st->tab, tab);
+    st->table(st->tab, ring_planes_table(ctx));
     return stage_arm(ctx, STAGE_LUT3D, std::move(st), "3D LUT");
 }
 
 /* ---- HLG (--hlg; the reference has no HLG transfer): include/hdr2yuv_hip.h states the definition ------------------------------------- */
-
-#include "h2y_hlg1.h"
 
 int h2y_hlg_tables(int peak, int relative, float gain[H2Y_LIGHTDIST_BINS], float oetf[H2Y_LIGHTDIST_BINS], float *k, double *gamma,
                    const char **why)
@@ -2950,8 +2714,8 @@ static int hlg_args_of(h2y_ctx *ctx, int width, int height, int sample_type, int
     if (sample_type == H2Y_SAMPLE_U16)
         return fail(ctx, H2Y_EUNSUPPORTED, "the HLG pass works on display light in float or half planes, not on U16 samples");
     if (sample_type != H2Y_SAMPLE_F32 && sample_type != H2Y_SAMPLE_F16) return fail(ctx, H2Y_EINVAL, "bad sample type %d", sample_type);
-    if (width < 1 || height < 1 || (uint64_t)width * (uint64_t)height >= (1ull << 28)) return fail(ctx, H2Y_EINVAL, "bad picture size");
-    const int rc = hlg_setup(ctx, peak, relative, dst_bit_depth, dst_full_range, dst_matrix, a.c, tables);
+    int rc = picture_size_check(ctx, width, height);
+    if (!rc) rc = hlg_setup(ctx, peak, relative, dst_bit_depth, dst_full_range, dst_matrix, a.c, tables);
     if (rc) return rc;
     a.npix = (uint32_t)width * (uint32_t)height;
     return H2Y_OK;
@@ -2960,32 +2724,17 @@ static int hlg_args_of(h2y_ctx *ctx, int width, int height, int sample_type, int
 int h2y_hlg_batch(h2y_ctx *ctx, int width, int height, int sample_type, int peak, int relative, int dst_bit_depth, int dst_full_range,
                   int dst_matrix, int n_frames, const void *const *d_src, void *const *d_dst)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
     hlg_args a{};
     std::vector<float> tables;
-    int rc = hlg_args_of(ctx, width, height, sample_type, peak, relative, dst_bit_depth, dst_full_range, dst_matrix, a, tables);
-    if (rc) return rc;
-    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
-    if (!d_src || !d_dst) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
-    for (int f = 0; f < n_frames; f++)
-        for (int c = 0; c < 3; c++) {
-            const void *i = d_src[3 * f + c], *o = d_dst[3 * f + c];
-            if (!i || !o) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is null", f, c);
-            if (((uintptr_t)i | (uintptr_t)o) & 15u) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is not 16-byte aligned", f, c);
-            if (i == o && sample_type == H2Y_SAMPLE_F16)
-                return fail(ctx, H2Y_EINVAL, "frame %d: plane %d in place: half planes are widened, the float planes need room of their own", f, c);
-        }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     gamut_frame *h;
-    rc = frame_table(ctx, n_frames, h);
-    if (!rc) rc = ensure(ctx, ctx->d_hlg_tables, ctx->hlg_tables_cap, tables.size() * sizeof(float));
+    int rc = batch_enter(ctx);
+    if (!rc) rc = hlg_args_of(ctx, width, height, sample_type, peak, relative, dst_bit_depth, dst_full_range, dst_matrix, a, tables);
+    if (!rc) rc = pass_frames(ctx, n_frames, d_src, d_dst, sample_type == H2Y_SAMPLE_F16, h);
+    if (!rc) rc = ensure(ctx, ctx->hlg_tables, tables.size() * sizeof(float));
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpy(ctx->d_hlg_tables, tables.data(), tables.size() * sizeof(float), hipMemcpyHostToDevice));
-    a.gain = ctx->d_hlg_tables;
-    a.oetf = ctx->d_hlg_tables + H2Y_LIGHTDIST_BINS;
-    for (int f = 0; f < n_frames; f++)
-        for (int c = 0; c < 3; c++) h[f].src[c] = d_src[3 * f + c], h[f].dst[c] = d_dst[3 * f + c];
+    HIP_TRY(ctx, hipMemcpy(ctx->hlg_tables.p, tables.data(), tables.size() * sizeof(float), hipMemcpyHostToDevice));
+    a.gain = ctx->hlg_tables.p;
+    a.oetf = ctx->hlg_tables.p + H2Y_LIGHTDIST_BINS;
     const int in_kind = sample_type == H2Y_SAMPLE_F16 ? H2Y_IN_F16 : H2Y_IN_F32;
     const uint64_t per_frame = h2y_hlg_chunks(in_kind, a.npix);
     rc = timed_launches(ctx, h, n_frames, H2Y_HLG_FRAMES_PER_LAUNCH, "k_hlg", [&](const gamut_frame *frames, int, int nf) {
@@ -2996,29 +2745,18 @@ int h2y_hlg_batch(h2y_ctx *ctx, int width, int height, int sample_type, int peak
     return H2Y_OK;
 }
 
-/* The pass's ring stage, in place on a forward ring's decoded F32 planes after the gamut and tone-map stages' passes and before the
- * conversion: k_hlg's arguments, the two tables and its frame table entry per slot.  It leaves nothing of its own behind. */
-struct hlg_stage : ring_stage {
-    hlg_args a{};
-    gamut_frame *tab = nullptr;
-    int grid = 1;
-    int decoded(h2y_ctx *ctx, int k) override
-    {
-        HIP_TRY(ctx, h2y_launch_hlg(H2Y_IN_F32, grid, ctx->stream, a, tab + k, 1));
-        return H2Y_OK;
-    }
-    int run(h2y_ctx *, int) override { return H2Y_OK; }
-};
-
+/* The HLG pass's ring stage: k_hlg on F32 planes (pass_stage's in_kind as it stands) after the gamut, tone-map and LUT stages' passes,
+ * with the two tables of its own */
 int h2y_stream_hlg(h2y_ctx *ctx, int peak, int relative)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    int rc = arm_enter(ctx);
+    if (rc) return rc;
     if (ctx->s_kind != h2y_ctx::RING_FORWARD) return fail(ctx, H2Y_EINVAL, "the HLG pass works on the forward rings only");
     if (ctx->s_stage[STAGE_HLG]) return fail(ctx, H2Y_EINVAL, "the ring writes HLG already");
     if (ctx->s_stage[STAGE_ICTCP]) return fail(ctx, H2Y_EINVAL, "the ring writes ICtCp: its planes hold code values, not light");
     if (lut3d_leaves_codes(ctx)) return fail(ctx, H2Y_EINVAL, "the ring's LUT works in signal mode: its planes hold code values, not light");
-    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    rc = arm_unstarted(ctx);
+    if (rc) return rc;
     const h2y_desc *d = &ctx->s_desc;
     if (d->in_sample_type != H2Y_SAMPLE_F32)
         return fail(ctx, H2Y_EUNSUPPORTED, "the HLG pass leaves code-valued samples in the ring's decoded planes: they must be F32, not %s",
@@ -3028,16 +2766,12 @@ int h2y_stream_hlg(h2y_ctx *ctx, int peak, int relative)
                     d->src_transfer, d->dst_transfer);
     if (d->src_matrix != H2Y_MATRIX_GBR)
         return fail(ctx, H2Y_EUNSUPPORTED, "the HLG pass needs a G,B,R source (src_matrix 0), not src_matrix %d", d->src_matrix);
-    auto st = std::make_unique<hlg_stage>();
+    auto st = std::make_unique<pass_stage<hlg_args>>();
+    st->launch = h2y_launch_hlg;
     std::vector<float> tables;
-    int rc = hlg_args_of(ctx, d->width, d->height, d->in_sample_type, peak, relative, d->dst_bit_depth, d->dst_full_range, d->dst_matrix,
-                         st->a, tables);
+    rc = hlg_args_of(ctx, d->width, d->height, d->in_sample_type, peak, relative, d->dst_bit_depth, d->dst_full_range, d->dst_matrix, st->a, tables);
+    if (!rc) rc = unit_range_check(ctx, d, "the HLG pass is the passthrough flow's");
     if (rc) return rc;
-    bool unit = d->stats_override == 1;
-    for (int c = 0; c < 3; c++) unit = unit && d->floor[c] == 0 && d->ceiling[c] == 1;
-    if (!unit)
-        return fail(ctx, H2Y_EINVAL, "the HLG pass is the passthrough flow's: open the ring with stats_override 1, floor 0 and ceiling 1 on "
-                                     "all three planes");
     pix_params pp;
     derive_params(d, &pp, false); /* the ring's own scale step, whatever else its descriptor says */
     st->a.c.mulY = pp.mulY, st->a.c.addY = pp.addY, st->a.c.mulC = pp.mulC, st->a.c.addC = pp.addC;
@@ -3047,11 +2781,7 @@ int h2y_stream_hlg(h2y_ctx *ctx, int peak, int relative)
     st->table(d_tables, tables);
     st->a.gain = d_tables;
     st->a.oetf = d_tables + H2Y_LIGHTDIST_BINS;
-    const int depth = (int)ctx->ss.size();
-    std::vector<gamut_frame> tab(depth);
-    for (int k = 0; k < depth; k++)
-        for (int c = 0; c < 3; c++) tab[k].src[c] = tab[k].dst[c] = ctx->ss[k].d_in + c * ctx->s_plane_al;
-    st->table(st->tab, tab);
+    st->table(st->tab, ring_planes_table(ctx));
     return stage_arm(ctx, STAGE_HLG, std::move(st), "HLG");
 }
 
@@ -3064,7 +2794,8 @@ static int ictcp_args_of(h2y_ctx *ctx, int width, int height, int sample_type, i
     if (sample_type == H2Y_SAMPLE_U16)
         return fail(ctx, H2Y_EUNSUPPORTED, "the ICtCp pass works on display light in float or half planes, not on U16 samples");
     if (sample_type != H2Y_SAMPLE_F32 && sample_type != H2Y_SAMPLE_F16) return fail(ctx, H2Y_EINVAL, "bad sample type %d", sample_type);
-    if (width < 1 || height < 1 || (uint64_t)width * (uint64_t)height >= (1ull << 28)) return fail(ctx, H2Y_EINVAL, "bad picture size");
+    const int rc = picture_size_check(ctx, width, height);
+    if (rc) return rc;
     if (dst_bit_depth < 8 || dst_bit_depth > 16) return fail(ctx, H2Y_EINVAL, "dst_bit_depth %d outside 8..16", dst_bit_depth);
     if (dst_full_range != 0 && dst_full_range != 1) return fail(ctx, H2Y_EINVAL, "dst_full_range must be 0 or 1");
     a = ictcp_args{};
@@ -3094,28 +2825,13 @@ static int ictcp_tables(h2y_ctx *ctx, ictcp_args &a)
 int h2y_ictcp_batch(h2y_ctx *ctx, int width, int height, int sample_type, int dst_bit_depth, int dst_full_range, int n_frames,
                     const void *const *d_src, void *const *d_dst)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
     ictcp_args a{};
-    int rc = ictcp_args_of(ctx, width, height, sample_type, dst_bit_depth, dst_full_range, a);
-    if (rc) return rc;
-    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
-    if (!d_src || !d_dst) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
-    for (int f = 0; f < n_frames; f++)
-        for (int c = 0; c < 3; c++) {
-            const void *i = d_src[3 * f + c], *o = d_dst[3 * f + c];
-            if (!i || !o) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is null", f, c);
-            if (((uintptr_t)i | (uintptr_t)o) & 15u) return fail(ctx, H2Y_EINVAL, "frame %d: plane %d is not 16-byte aligned", f, c);
-            if (i == o && sample_type == H2Y_SAMPLE_F16)
-                return fail(ctx, H2Y_EINVAL, "frame %d: plane %d in place: half planes are widened, the float planes need room of their own", f, c);
-        }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     gamut_frame *h;
-    rc = frame_table(ctx, n_frames, h);
+    int rc = batch_enter(ctx);
+    if (!rc) rc = ictcp_args_of(ctx, width, height, sample_type, dst_bit_depth, dst_full_range, a);
+    if (!rc) rc = pass_frames(ctx, n_frames, d_src, d_dst, sample_type == H2Y_SAMPLE_F16, h);
     if (!rc) rc = ictcp_tables(ctx, a);
     if (rc) return rc;
-    for (int f = 0; f < n_frames; f++)
-        for (int c = 0; c < 3; c++) h[f].src[c] = d_src[3 * f + c], h[f].dst[c] = d_dst[3 * f + c];
     const int in_kind = sample_type == H2Y_SAMPLE_F16 ? H2Y_IN_F16 : H2Y_IN_F32;
     const uint64_t per_frame = h2y_ictcp_chunks(in_kind, a.npix);
     rc = timed_launches(ctx, h, n_frames, H2Y_ICTCP_FRAMES_PER_LAUNCH, "k_ictcp", [&](const gamut_frame *frames, int, int nf) {
@@ -3126,29 +2842,18 @@ int h2y_ictcp_batch(h2y_ctx *ctx, int width, int height, int sample_type, int ds
     return H2Y_OK;
 }
 
-/* The pass's ring stage, in place on a forward ring's decoded F32 planes after the gamut and tone-map stages' passes and before the
- * conversion: k_ictcp's arguments (the table is the context's) and its frame table entry per slot. */
-struct ictcp_stage : ring_stage {
-    ictcp_args a{};
-    gamut_frame *tab = nullptr;
-    int grid = 1;
-    int decoded(h2y_ctx *ctx, int k) override
-    {
-        HIP_TRY(ctx, h2y_launch_ictcp(H2Y_IN_F32, grid, ctx->stream, a, tab + k, 1));
-        return H2Y_OK;
-    }
-    int run(h2y_ctx *, int) override { return H2Y_OK; }
-};
-
+/* The ICtCp pass's ring stage: k_ictcp on F32 planes (pass_stage's in_kind as it stands) after the gamut, tone-map and LUT stages'
+ * passes; the table is the context's */
 int h2y_stream_ictcp(h2y_ctx *ctx)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    int rc = arm_enter(ctx);
+    if (rc) return rc;
     if (ctx->s_kind != h2y_ctx::RING_FORWARD) return fail(ctx, H2Y_EINVAL, "the ICtCp pass works on the forward rings only");
     if (ctx->s_stage[STAGE_ICTCP]) return fail(ctx, H2Y_EINVAL, "the ring writes ICtCp already");
     if (ctx->s_stage[STAGE_HLG]) return fail(ctx, H2Y_EINVAL, "the ring writes HLG: its planes hold code values, not light");
     if (lut3d_leaves_codes(ctx)) return fail(ctx, H2Y_EINVAL, "the ring's LUT works in signal mode: its planes hold code values, not light");
-    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    rc = arm_unstarted(ctx);
+    if (rc) return rc;
     const h2y_desc *d = &ctx->s_desc;
     if (d->in_sample_type != H2Y_SAMPLE_F32)
         return fail(ctx, H2Y_EUNSUPPORTED, "the ICtCp pass leaves code-valued samples in the ring's decoded planes: they must be F32, not %s",
@@ -3160,23 +2865,16 @@ int h2y_stream_ictcp(h2y_ctx *ctx)
         return fail(ctx, H2Y_EUNSUPPORTED, "the ICtCp pass needs a G,B,R source (src_matrix 0), not src_matrix %d", d->src_matrix);
     if (d->dst_matrix != H2Y_MATRIX_GBR)
         return fail(ctx, H2Y_EUNSUPPORTED, "the ICtCp pass is the ring's matrix: open it with dst_matrix 0, not dst_matrix %d", d->dst_matrix);
-    auto st = std::make_unique<ictcp_stage>();
-    int rc = ictcp_args_of(ctx, d->width, d->height, d->in_sample_type, d->dst_bit_depth, d->dst_full_range, st->a);
+    auto st = std::make_unique<pass_stage<ictcp_args>>();
+    st->launch = h2y_launch_ictcp;
+    rc = ictcp_args_of(ctx, d->width, d->height, d->in_sample_type, d->dst_bit_depth, d->dst_full_range, st->a);
+    if (!rc) rc = unit_range_check(ctx, d, "the ICtCp pass is the passthrough flow's");
     if (rc) return rc;
-    bool unit = d->stats_override == 1;
-    for (int c = 0; c < 3; c++) unit = unit && d->floor[c] == 0 && d->ceiling[c] == 1;
-    if (!unit)
-        return fail(ctx, H2Y_EINVAL, "the ICtCp pass is the passthrough flow's: open the ring with stats_override 1, floor 0 and ceiling 1 on "
-                                     "all three planes");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     rc = ictcp_tables(ctx, st->a);
     if (rc) return rc;
     st->grid = h2y_ictcp_grid(ctx->n_cu, h2y_ictcp_chunks(H2Y_IN_F32, st->a.npix));
-    const int depth = (int)ctx->ss.size();
-    std::vector<gamut_frame> tab(depth);
-    for (int k = 0; k < depth; k++)
-        for (int c = 0; c < 3; c++) tab[k].src[c] = tab[k].dst[c] = ctx->ss[k].d_in + c * ctx->s_plane_al;
-    st->table(st->tab, tab);
+    st->table(st->tab, ring_planes_table(ctx));
     return stage_arm(ctx, STAGE_ICTCP, std::move(st), "ICtCp");
 }
 
@@ -3234,12 +2932,12 @@ int hlgsrc_args_of(h2y_ctx *ctx, const codelight_plan &p, int peak, hlgsrc_args 
     const char *why;
     int rc = h2y_hlg_inverse_tables(peak, tables.data(), tables.data() + H2Y_LIGHTDIST_BINS, &a.kappa, &gamma, &why);
     if (rc) return fail(ctx, rc, "HLG source at %d cd/m2: %s", peak, why);
-    rc = ensure(ctx, ctx->d_hlgsrc_tables, ctx->hlgsrc_tables_cap, tables.size() * sizeof(float));
+    rc = ensure(ctx, ctx->hlgsrc_tables, tables.size() * sizeof(float));
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpy(ctx->d_hlgsrc_tables, tables.data(), tables.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(ctx->hlgsrc_tables.p, tables.data(), tables.size() * sizeof(float), hipMemcpyHostToDevice));
     a.c = p.a;
-    a.ootf = ctx->d_hlgsrc_tables;
-    a.inv = ctx->d_hlgsrc_tables + H2Y_LIGHTDIST_BINS;
+    a.ootf = ctx->hlgsrc_tables.p;
+    a.inv = ctx->hlgsrc_tables.p + H2Y_LIGHTDIST_BINS;
     return H2Y_OK;
 }
 
@@ -3283,8 +2981,6 @@ int sdrsrc_tables(h2y_ctx *ctx, codelight_plan &p, int white, float &kappa)
 
 /* ---- dither: the reduction to the output bit depth (--dither; the reference's to-do list names it): include/hdr2yuv_hip.h states
  * the definition ------------------------------------------------------------------------------------------------------------------ */
-
-#include "h2y_dither1.h"
 
 static const char *const kDitherMode[3] = {"cut", "ordered", "noise"};
 
@@ -3335,11 +3031,10 @@ static dither_args dither_args_of(int width, int height, int chroma, int src_dep
     uint32_t off[3];
     contiguous_planes(width, height, chroma, off);
     const clip_limits c = make_clip(dst_depth, full_range);
-    const bool sub = chroma == H2Y_CHROMA_420;
     for (int p = 0; p < 3; p++) {
         const bool luma_like = p == 0 || gbr;
-        a.p[p] = h2y_dither_plane((uint32_t)(p && sub ? width >> 1 : width), (uint32_t)(p && sub ? height >> 1 : height), off[p],
-                                  luma_like ? c.minVR : c.minVRC, luma_like ? c.maxVR : c.maxVRC);
+        const plane_dim d = plane_dims(width, height, chroma, p);
+        a.p[p] = h2y_dither_plane(d.w, d.h, off[p], luma_like ? c.minVR : c.minVRC, luma_like ? c.maxVR : c.maxVRC);
     }
     a.shift = (uint32_t)(src_depth - dst_depth);
     a.key = seed ^ 0x9E3779B9u;
@@ -3358,16 +3053,10 @@ int h2y_dither_batch(h2y_ctx *ctx, int width, int height, int chroma_format_idc,
                      int mode, int temporal, uint32_t seed, uint32_t first_frame, int n_frames, const uint16_t *const *d_src,
                      uint16_t *const *d_dst)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
-    int rc = dither_check(ctx, width, height, chroma_format_idc, src_depth, dst_depth, full_range, gbr, mode, temporal);
+    int rc = batch_enter(ctx);
+    if (!rc) rc = dither_check(ctx, width, height, chroma_format_idc, src_depth, dst_depth, full_range, gbr, mode, temporal);
+    if (!rc) rc = pairs_check(ctx, n_frames, d_src, d_dst);
     if (rc) return rc;
-    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
-    if (!d_src || !d_dst) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
-    for (int f = 0; f < n_frames; f++) {
-        if (!d_src[f] || !d_dst[f]) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is null", f);
-        if (((uintptr_t)d_src[f] | (uintptr_t)d_dst[f]) & 15u) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is not 16-byte aligned", f);
-    }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const dither_args a = dither_args_of(width, height, chroma_format_idc, src_depth, dst_depth, full_range, gbr, temporal, seed);
     dither_frame *h;
@@ -3450,15 +3139,16 @@ static int dither_arm(h2y_ctx *ctx, int dst_depth, int gbr, int mode, int tempor
 
 int h2y_stream_dither(h2y_ctx *ctx, int dst_depth, int mode, int temporal, uint32_t seed, uint32_t first_frame)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    int rc = arm_enter(ctx);
+    if (rc) return rc;
     if (ctx->s_kind != h2y_ctx::RING_FORWARD) return fail(ctx, H2Y_EINVAL, "only a forward ring is armed for dither");
     if (ctx->s_stage[STAGE_DITHER]) return fail(ctx, H2Y_EINVAL, "the ring dithers already");
     if (ctx->s_stage[STAGE_PACK]) return fail(ctx, H2Y_EINVAL, "the ring packs already: arm dither before pack");
     if (ctx->s_stage[STAGE_COMPARE] || ctx->s_stage[STAGE_HISTOGRAM] || ctx->s_stage[STAGE_SSIM] || ctx->s_stage[STAGE_DELTAE])
         return fail(ctx, H2Y_EUNSUPPORTED, "a ring armed for comparison, histograms, SSIM or Delta E is not dithered: compare or count the written file instead");
     if (ctx->s_desc.dst_matrix == H2Y_MATRIX_YUVPRIME2) return fail(ctx, H2Y_EUNSUPPORTED, "a Y'u'v' ring (dst_matrix_coeffs 15) is not dithered");
-    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    rc = arm_unstarted(ctx);
+    if (rc) return rc;
     return dither_arm(ctx, dst_depth, 0, mode, temporal, seed, first_frame);
 }
 
@@ -3478,8 +3168,6 @@ int h2y_dither_stream_open(h2y_ctx *ctx, int width, int height, int chroma_forma
 }
 
 /* ---- sample packings: byte and semi-planar frames (--dst_pack, --src_pack): include/hdr2yuv_hip.h states the definition ------------ */
-
-#include "h2y_pack1.h"
 
 static const char *const kPackName[4] = {"PLANAR16", "PLANAR8", "NV12", "P010"};
 
@@ -3555,16 +3243,10 @@ static int pack_grid(const h2y_ctx *ctx, const pack_args &a, int n_frames)
 static int pack_batch(h2y_ctx *ctx, bool unpack, int width, int height, int chroma, int bit_depth, int packing, int n_frames,
                       const void *const *planar, const void *const *packed)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if ((ctx->q_count > 0) || ctx->streaming) return fail(ctx, H2Y_EINVAL, "a batch is pending or a stream is open");
-    int rc = pack_check(ctx, width, height, chroma, bit_depth, packing);
+    int rc = batch_enter(ctx);
+    if (!rc) rc = pack_check(ctx, width, height, chroma, bit_depth, packing);
+    if (!rc) rc = pairs_check(ctx, n_frames, planar, packed);
     if (rc) return rc;
-    if (n_frames < 1) return fail(ctx, H2Y_EINVAL, "n_frames must be >= 1");
-    if (!planar || !packed) return fail(ctx, H2Y_EINVAL, "null pointer arrays");
-    for (int f = 0; f < n_frames; f++) {
-        if (!planar[f] || !packed[f]) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is null", f);
-        if (((uintptr_t)planar[f] | (uintptr_t)packed[f]) & 15u) return fail(ctx, H2Y_EINVAL, "frame %d: a frame is not 16-byte aligned", f);
-    }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     uint32_t off[3];
     contiguous_planes(width, height, chroma, off);
@@ -3618,8 +3300,8 @@ struct pack_stage : ring_stage {
 
 int h2y_stream_pack(h2y_ctx *ctx, int packing)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    int rc = arm_enter(ctx);
+    if (rc) return rc;
     const ring_frame &f = ctx->s_frame;
     scale_stage *sc = stage_of<scale_stage>(ctx, STAGE_SCALE);
     dither_stage *di = stage_of<dither_stage>(ctx, STAGE_DITHER);
@@ -3631,10 +3313,11 @@ int h2y_stream_pack(h2y_ctx *ctx, int packing)
         return fail(ctx, H2Y_EUNSUPPORTED, "a ring armed for comparison, histograms, SSIM or Delta E is not packed: compare or count the written file instead");
     if (ctx->s_kind == h2y_ctx::RING_FORWARD && ctx->s_desc.dst_matrix == H2Y_MATRIX_YUVPRIME2)
         return fail(ctx, H2Y_EUNSUPPORTED, "a Y'u'v' ring (dst_matrix_coeffs 15) is not packed");
-    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    rc = arm_unstarted(ctx);
+    if (rc) return rc;
     const int width = sc ? (int)sc->g.p[0].dw : f.width, height = sc ? (int)sc->g.p[0].dh : f.height;
     const int bit_depth = f.depth - (di ? (int)di->a.shift : 0);
-    int rc = pack_check(ctx, width, height, f.chroma, bit_depth, packing);
+    rc = pack_check(ctx, width, height, f.chroma, bit_depth, packing);
     if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     auto st = std::make_unique<pack_stage>();
@@ -3695,8 +3378,8 @@ int h2y_stream_unpack(h2y_ctx *ctx, int packing) { return h2y_stream_unpack_ex(c
 
 int h2y_stream_unpack_ex(h2y_ctx *ctx, int packing, int depth_given)
 {
-    if (!ctx) return fail(nullptr, H2Y_EINVAL, "null ctx");
-    if (!ctx->streaming) return fail(ctx, H2Y_EINVAL, "no stream open");
+    int rc = arm_enter(ctx);
+    if (rc) return rc;
     if (ctx->s_stage[STAGE_UNPACK]) return fail(ctx, H2Y_EINVAL, "the ring unpacks already");
     /* where the planes the upload brings lie in the slot's device input, which frame they are, and its depth */
     const ring_frame &f = ctx->s_frame;
@@ -3720,14 +3403,15 @@ int h2y_stream_unpack_ex(h2y_ctx *ctx, int packing, int depth_given)
         width = f.width, height = f.height, chroma = f.chroma, bit_depth = f.depth;
         for (int c = 0; c < 3; c++) off[c] = f.off[c];
     }
-    if (ctx->s_started) return fail(ctx, H2Y_EINVAL, "arm the ring before its first input");
+    rc = arm_unstarted(ctx);
+    if (rc) return rc;
     if (depth_given < 0) return fail(ctx, H2Y_EINVAL, "unpack: bit_depth must be 0 (the ring's own) or the frames' depth");
     if (depth_given > 0 && bit_depth > 0 && depth_given != bit_depth)
         return fail(ctx, H2Y_EINVAL, "unpack: bit_depth %d given, but the ring's input depth is %d", depth_given, bit_depth);
     if (depth_given > 0) bit_depth = depth_given; /* a compare-only ring learns its frames' depth here */
     if (packing == H2Y_PACK_P010 && bit_depth == 0)
         return fail(ctx, H2Y_EINVAL, "packing P010 needs the bit depth, which a compare-only ring does not know: give it to h2y_stream_unpack_ex");
-    int rc = pack_check(ctx, width, height, chroma, bit_depth, packing);
+    rc = pack_check(ctx, width, height, chroma, bit_depth, packing);
     if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     auto st = std::make_unique<unpack_stage>();

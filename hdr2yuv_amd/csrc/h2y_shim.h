@@ -1,6 +1,7 @@
 /*
  * h2y_shim.h -- what the shim's translation units share (h2y_api.hip, h2y_forward.hip, h2y_ring.hip, h2y_measure.hip): the context,
- * the streaming ring's stage interface, and the helpers every entry uses.  Internal: not installed, no part of the ABI.
+ * the streaming ring's stage interface, and the helpers every entry uses (those of the entries' refusals and the shared stages in
+ * h2y_entry.h, included at the end).  Internal: not installed, no part of the ABI.
  */
 #pragma once
 
@@ -53,6 +54,21 @@ inline clip_limits make_clip(int bit_depth, int full_range)
 
 const int kMaxEvents = 64;
 
+/* A grow-only device workspace of the context: ensure() grows it, and it is freed when h2y_ctx_destroy deletes the context, on the
+ * context's device, after the last work on its streams was waited for.  No workspace depends on another, so their order (the reverse
+ * of their declaration) does not matter.  One declaration in h2y_ctx is all a new one needs. */
+template <typename T> struct dev_buf {
+    T *p = nullptr;
+    size_t cap = 0; /* bytes */
+    dev_buf() = default;
+    dev_buf(const dev_buf &) = delete;
+    dev_buf &operator=(const dev_buf &) = delete;
+    ~dev_buf()
+    {
+        if (p) (void)hipFree(p);
+    }
+};
+
 /* The parameters of one .yuv -> G,B,R flow (h2y_inverse_batch, h2y_inverse_stream_open) */
 struct inv_params {
     int width, height, chroma, in_depth, in_full_range, matrix, out_depth, algorithm;
@@ -83,7 +99,7 @@ struct decode_src {
     h2y_tiff_info tiff{};
     h2y_exr_info exr{};
     codelight_plan code{};
-    bool hlg = false;     /* PQCODE: the frame holds HLG codes; hlgsrc: k_hlg_linearize's arguments, the tables in the context's d_hlgsrc_tables */
+    bool hlg = false;     /* PQCODE: the frame holds HLG codes; hlgsrc: k_hlg_linearize's arguments, the tables in the context's hlgsrc_tables */
     hlgsrc_args hlgsrc{};
     bool sdr = false;     /* PQCODE: the frame holds SDR (BT.1886) codes; code.a carries that stage's tables (sdrsrc_tables), sdr_kappa W / 10000 */
     float sdr_kappa = 0.0f;
@@ -268,56 +284,27 @@ struct h2y_ctx {
      * beside another batch or a stream): pinned on the host, and its device copy the kernels read (frame_table) */
     void *d_tab = nullptr, *h_tab = nullptr;
     size_t d_tab_cap = 0, h_tab_cap = 0; /* bytes */
-    /* k_compare's partials (h2y_compare_batch and an armed ring), and h2y_compare_batch's device stats */
-    cmp_partial *d_cmp_part = nullptr;
-    size_t cmp_part_cap = 0;
-    h2y_compare_stats *d_cmp_stats = nullptr;
-    size_t cmp_stats_cap = 0;
-    /* h2y_histogram_batch's device workspace: per launch the counts, the bins and the stats (hist_layout) */
-    char *d_hist = nullptr;
-    size_t hist_cap = 0;
-    /* h2y_ssim_batch's (and an armed ring's) k_ssim partials, and the batch's stats */
-    int64_t *d_ssim_part = nullptr;
-    size_t ssim_part_cap = 0;
-    h2y_ssim_stats *d_ssim_stats = nullptr;
-    size_t ssim_stats_cap = 0;
-    /* h2y_regions_batch's (and an armed ring's) k_regions partials, and the batch's stats */
-    regions_partial *d_regions_part = nullptr;
-    size_t regions_part_cap = 0;
-    h2y_regions_stats *d_regions_stats = nullptr;
-    size_t regions_stats_cap = 0;
-    /* h2y_light_batch's floor / ceiling per frame and k_light's accumulators */
-    assumed_stats *d_light_as = nullptr;
-    size_t light_as_cap = 0;
-    light_acc *d_light_acc = nullptr;
-    size_t light_acc_cap = 0;
-    /* h2y_lightdist_batch's device workspace: per launch k_lightdist's accumulators, then the bins (lightdist_layout) */
-    char *d_lightdist = nullptr;
-    size_t lightdist_cap = 0;
-    /* h2y_codelight_batch's device workspace (light_acc, then lightdist_layout) and its launches' upsampled 4:2:0 chroma */
-    char *d_codelight = nullptr, *d_codelight_up = nullptr;
-    size_t codelight_cap = 0, codelight_up_cap = 0;
-    /* h2y_scenesig_batch's and h2y_codescenesig_batch's cells on the device: 144 uint64 a frame */
-    unsigned long long *d_scenesig = nullptr;
-    size_t scenesig_cap = 0;
-    /* h2y_deltae_batch's accumulators (its launches' upsampled 4:2:0 chroma lies in d_codelight_up) */
-    deltae_acc *d_deltae = nullptr;
-    size_t deltae_cap = 0;
-    /* h2y_scale_batch's tap tables on the device */
-    char *d_scale_tabs = nullptr;
-    size_t scale_tabs_cap = 0;
-    /* h2y_tonemap_batch's gain table on the device */
-    float *d_tonemap_gain = nullptr;
-    size_t tonemap_gain_cap = 0;
-    /* h2y_lut3d_batch's table on the device */
-    lut3d_node *d_lut3d = nullptr;
-    size_t lut3d_cap = 0;
-    /* h2y_hlg_batch's two tables on the device: the gains, then the OETF's */
-    float *d_hlg_tables = nullptr;
-    size_t hlg_tables_cap = 0;
-    /* h2y_hlg_linearize_batch's and the HLG code ring's two tables on the device: the OOTF's gains, then the OETF's inverse */
-    float *d_hlgsrc_tables = nullptr;
-    size_t hlgsrc_tables_cap = 0;
+    /* The grow-only device workspaces of the batch entries and of the armed stages that share one: each is named here, grown by its
+     * user (ensure) and released with the context */
+    dev_buf<cmp_partial> cmp_part;             /* k_compare's partials (h2y_compare_batch and an armed ring) */
+    dev_buf<h2y_compare_stats> cmp_stats;      /* h2y_compare_batch's stats */
+    dev_buf<char> hist;                        /* h2y_histogram_batch: per launch the counts, the bins and the stats (hist_layout) */
+    dev_buf<int64_t> ssim_part;                /* k_ssim's partials (h2y_ssim_batch and an armed ring) */
+    dev_buf<h2y_ssim_stats> ssim_stats;        /* h2y_ssim_batch's stats */
+    dev_buf<regions_partial> regions_part;     /* k_regions' partials (h2y_regions_batch and an armed ring) */
+    dev_buf<h2y_regions_stats> regions_stats;  /* h2y_regions_batch's stats */
+    dev_buf<assumed_stats> light_as;           /* h2y_light_batch's floor / ceiling per frame */
+    dev_buf<light_acc> light_accs;             /* h2y_light_batch's accumulators */
+    dev_buf<char> lightdist;                   /* h2y_lightdist_batch: per launch k_lightdist's accumulators, then the bins (lightdist_layout) */
+    dev_buf<char> codelight;                   /* h2y_codelight_batch: light_acc, then lightdist_layout */
+    dev_buf<char> codelight_up;                /* the code-plane launches' upsampled 4:2:0 chroma (code light, the linearisers, Delta E, the code rings) */
+    dev_buf<unsigned long long> scenesig;      /* h2y_scenesig_batch's and h2y_codescenesig_batch's cells: 144 uint64 a frame */
+    dev_buf<deltae_acc> deltae;                /* h2y_deltae_batch's accumulators */
+    dev_buf<char> scale_tabs;                  /* h2y_scale_batch's tap tables */
+    dev_buf<float> tonemap_gain;               /* h2y_tonemap_batch's gain table */
+    dev_buf<lut3d_node> lut3d;                 /* h2y_lut3d_batch's table */
+    dev_buf<float> hlg_tables;                 /* h2y_hlg_batch's two tables: the gains, then the OETF's */
+    dev_buf<float> hlgsrc_tables;              /* h2y_hlg_linearize_batch's and the HLG code ring's: the OOTF's gains, then the OETF's inverse */
 
     /* staging for the host-buffer entry */
     void *d_in = nullptr;
@@ -394,6 +381,7 @@ template <typename T> int ensure(h2y_ctx *ctx, T *&p, size_t &cap, size_t need_b
     cap = need_bytes;
     return 0;
 }
+template <typename T> int ensure(h2y_ctx *ctx, dev_buf<T> &b, size_t need_bytes) { return ensure(ctx, b.p, b.cap, need_bytes); }
 
 /* the offsets, in samples, of three planes one after the other (4:2:0: two chroma planes of (width >> 1) x (height >> 1)) */
 inline void contiguous_planes(int width, int height, int chroma, uint32_t off[3])
@@ -538,5 +526,6 @@ int ring_may_open(h2y_ctx *ctx);
 int open_planes_ring(h2y_ctx *ctx, int width, int height, int chroma, int bit_depth, int full_range, int gbr, size_t out_bytes, int depth);
 int stage_arm(h2y_ctx *ctx, int id, std::unique_ptr<ring_stage> st, const char *what);
 void ring_frame_stays(h2y_ctx *ctx);
+#include "h2y_entry.h"
 
 #pragma GCC visibility pop
