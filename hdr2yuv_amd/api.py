@@ -49,6 +49,7 @@ EXPORTS = [
     "h2y_dither_offsets", "h2y_dither_batch", "h2y_stream_dither", "h2y_dither_stream_open",
     "h2y_pack_frame_bytes", "h2y_pack_frame", "h2y_unpack_frame", "h2y_pack_batch", "h2y_unpack_batch", "h2y_stream_pack", "h2y_stream_unpack", "h2y_stream_unpack_ex",
     "h2y_gamut_matrix", "h2y_gamut_batch", "h2y_stream_gamut",
+    "h2y_gamut_compress_curve", "h2y_gamut_compress_planes", "h2y_gamut_compress_batch", "h2y_stream_gamut_compress",
     "h2y_tonemap_curve", "h2y_tonemap_batch", "h2y_stream_tonemap",
     "h2y_lut3d_parse", "h2y_lut3d_free", "h2y_lut3d_info", "h2y_lut3d_nodes", "h2y_lut3d_planes", "h2y_lut3d_batch", "h2y_stream_lut3d",
     "h2y_hlg_tables", "h2y_hlg_planes", "h2y_hlg_batch", "h2y_stream_hlg",
@@ -239,6 +240,25 @@ class H2YRegionsStats(C.Structure):
 
     def __repr__(self):
         return f"H2YRegionsStats({self.as_dict()})"
+
+
+GAMUT_COMPRESS_FRAMES_PER_LAUNCH = 64  # H2Y_GAMUT_COMPRESS_FRAMES_PER_LAUNCH
+GAMUT_COMPRESS_NODES = 1025  # H2Y_GAMUT_COMPRESS_NODES: entries of one channel's table
+GAMUT_COMPRESS_THRESHOLD = 0.8  # H2Y_GAMUT_COMPRESS_THRESHOLD (rounded to binary32 on the way in)
+GAMUT_COMPRESS_POWER = 1.2  # H2Y_GAMUT_COMPRESS_POWER
+
+
+class H2YGamutCompressTables(C.Structure):
+    """h2y_gamut_compress_tables"""
+
+    _fields_ = [
+        ("m", C.c_float * 9),
+        ("threshold", C.c_float),
+        ("power", C.c_float),
+        ("limit", C.c_float * 3),
+        ("scale", C.c_float * 3),
+        ("table", (C.c_float * GAMUT_COMPRESS_NODES) * 3),
+    ]
 
 
 class H2YLightStats(C.Structure):
@@ -613,6 +633,16 @@ def load_library():
     L.h2y_gamut_batch.restype = C.c_int
     L.h2y_stream_gamut.argtypes = [C.c_void_p] + [C.c_int] * 3
     L.h2y_stream_gamut.restype = C.c_int
+    L.h2y_gamut_compress_curve.argtypes = [C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(H2YGamutCompressTables), C.POINTER(C.c_char_p)]
+    L.h2y_gamut_compress_curve.restype = C.c_int
+    L.h2y_gamut_compress_planes.argtypes = [C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_size_t, C.POINTER(C.c_void_p),
+                                            C.POINTER(C.c_void_p)]
+    L.h2y_gamut_compress_planes.restype = C.c_int
+    L.h2y_gamut_compress_batch.argtypes = ([C.c_void_p] + [C.c_int] * 5 + [C.c_float, C.c_float, C.c_int]
+                                           + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)])
+    L.h2y_gamut_compress_batch.restype = C.c_int
+    L.h2y_stream_gamut_compress.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float]
+    L.h2y_stream_gamut_compress.restype = C.c_int
     L.h2y_tonemap_curve.argtypes = [C.c_int] * 3 + [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_char_p)]
     L.h2y_tonemap_curve.restype = C.c_int
     L.h2y_tonemap_batch.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
@@ -931,6 +961,46 @@ def gamut_matrix(src_primaries: int, dst_primaries: int) -> np.ndarray:
     if rc != H2Y_OK:
         raise H2YError(rc, (why.value or b"").decode())
     return m.reshape(3, 3)
+
+
+def gamut_compress_curve(src_primaries: int, dst_primaries: int, threshold: float = GAMUT_COMPRESS_THRESHOLD,
+                         power: float = GAMUT_COMPRESS_POWER):
+    """h2y_gamut_compress_curve (host only, no device): a dict of the float32 matrix (3, 3), the limits and scales (R, G, B) and the
+    three tables (3, GAMUT_COMPRESS_NODES) of the gamut compression from src_primaries to dst_primaries.  Raises H2YError (EINVAL:
+    threshold or power out of range, equal chromaticities; EUNSUPPORTED: XYZ, primaries it does not know)."""
+    out = H2YGamutCompressTables()
+    why = C.c_char_p()
+    rc = load_library().h2y_gamut_compress_curve(int(src_primaries), int(dst_primaries), float(threshold), float(power), C.byref(out),
+                                                 C.byref(why))
+    if rc != H2Y_OK:
+        raise H2YError(rc, (why.value or b"").decode())
+    return {
+        "matrix": np.array(out.m, np.float32).reshape(3, 3),
+        "threshold": np.float32(out.threshold),
+        "power": np.float32(out.power),
+        "limit": np.array(out.limit, np.float32),
+        "scale": np.array(out.scale, np.float32),
+        "table": np.ctypeslib.as_array(out.table).astype(np.float32).reshape(3, GAMUT_COMPRESS_NODES),
+    }
+
+
+def gamut_compress_planes(planes, src_primaries: int, dst_primaries: int, threshold: float = GAMUT_COMPRESS_THRESHOLD,
+                          power: float = GAMUT_COMPRESS_POWER):
+    """h2y_gamut_compress_planes (host only, no device): k_gamut_compress' CPU twin on three numpy planes G, B, R of float32 or
+    float16; returns the three planes the kernel writes for them, in the source's type."""
+    src = [np.ascontiguousarray(p) for p in planes]
+    dt = src[0].dtype
+    if len(src) != 3 or dt not in (np.float32, np.float16) or any(p.dtype != dt or p.shape != src[0].shape for p in src):
+        raise ValueError("three planes of one shape, float32 or float16")
+    out = [np.empty(p.shape, dt) for p in src]
+    ins = (C.c_void_p * 3)(*[p.ctypes.data for p in src])
+    outs = (C.c_void_p * 3)(*[p.ctypes.data for p in out])
+    lib = load_library()
+    rc = lib.h2y_gamut_compress_planes(int(src_primaries), int(dst_primaries), float(threshold), float(power),
+                                       SAMPLE_F16 if dt == np.float16 else SAMPLE_F32, src[0].size, ins, outs)
+    if rc != H2Y_OK:
+        raise H2YError(rc, (lib.h2y_last_error(None) or b"").decode())
+    return out
 
 
 def tonemap_curve(src_peak: int, dst_peak: int, relative: int):
@@ -1555,6 +1625,24 @@ class Context:
                 outs[3 * f + c] = self._ptr(frames_dst[f][c])
         self._check(self.lib.h2y_gamut_batch(self.h, width, height, sample, src_primaries, dst_primaries, clip, n, ins, outs))
 
+    def gamut_compress_batch(self, width, height, sample, src_primaries, dst_primaries, frames_src, frames_dst=None,
+                             threshold=GAMUT_COMPRESS_THRESHOLD, power=GAMUT_COMPRESS_POWER) -> None:
+        """k_gamut_compress on device frames (frames_src[f] = three device planes G, B, R of float or half samples, 16-byte aligned):
+        frames_dst[f] receives them converted from src_primaries to dst_primaries, out-of-gamut colours compressed; frames_dst None:
+        in place."""
+        frames_dst = frames_src if frames_dst is None else frames_dst
+        n = len(frames_src)
+        if len(frames_dst) != n:
+            raise ValueError("frames_src and frames_dst differ in length")
+        ins = (C.c_void_p * max(3 * n, 1))()
+        outs = (C.c_void_p * max(3 * n, 1))()
+        for f in range(n):
+            for c in range(3):
+                ins[3 * f + c] = self._ptr(frames_src[f][c])
+                outs[3 * f + c] = self._ptr(frames_dst[f][c])
+        self._check(self.lib.h2y_gamut_compress_batch(self.h, width, height, sample, src_primaries, dst_primaries, threshold, power, n,
+                                                      ins, outs))
+
     def tonemap_batch(self, width, height, sample, src_peak, dst_peak, relative, frames_src, frames_dst=None) -> None:
         """k_tonemap on device frames (frames_src[f] = three device planes G, B, R of float or half samples in linear light, 16-byte
         aligned): frames_dst[f] receives them mapped from src_peak to dst_peak cd/m2; frames_dst None: in place."""
@@ -1652,6 +1740,12 @@ class Context:
         """Arm an open forward ring of float or half planes (plain, DPX or EXR): every slot's decoded planes are converted in
         place from src_primaries to dst_primaries before pic_stats and the conversion (h2y_stream_gamut)."""
         self._check(self.lib.h2y_stream_gamut(self.h, src_primaries, dst_primaries, clip))
+
+    def stream_gamut_compress(self, src_primaries, dst_primaries, threshold=GAMUT_COMPRESS_THRESHOLD,
+                              power=GAMUT_COMPRESS_POWER) -> None:
+        """Arm an open forward ring as stream_gamut arms it, with k_gamut_compress in k_gamut's place: out-of-gamut colours are
+        compressed, not clipped (h2y_stream_gamut_compress)."""
+        self._check(self.lib.h2y_stream_gamut_compress(self.h, src_primaries, dst_primaries, threshold, power))
 
     def stream_scale(self, dst_w, dst_h, a=3) -> None:
         """Arm an open forward ring (plain, DPX, TIFF or EXR): stream_output then returns the frame scaled to dst_w x dst_h."""

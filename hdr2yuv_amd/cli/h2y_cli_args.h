@@ -164,6 +164,15 @@
  *             (exit 1, also under --dry_run): a value other than 0 or 1, --gamut_clip without --gamut_convert 1, a source transfer
  *             other than 8 (LINEAR), a source matrix other than 0 (G,B,R), primaries other than 1, 8, 9, 10 and 12 or a pair of equal
  *             chromaticities, .rgb, .tiff and .yuv input, the .yuv -> RGB flow, --compare_only, --histogram_only and --scale_only.
+ * --gamut_compress 1 [--gamut_compress_threshold T] [--gamut_compress_power P] (an addition, beside --gamut_convert 1, wherever that is
+ *             valid): the pass does the same matrix and, in the same trip through memory, rolls the channels that it left far below
+ *             the pixel's largest channel off toward 0 along a curve, not into a clip (include/hdr2yuv_hip.h, "gamut compression":
+ *             the distance-from-achromatic form of the ACES 1.3 Reference Gamut Compression, limits from the source primaries).  T,
+ *             0.5 .. 0.95, 0.8 by default: the distance from the largest channel up to which a channel keeps its bits; P, 1 .. 4, 1.2
+ *             by default: the curve's power.  The banner carries gamut_compress:, both parameters and gamut_compress_limits: (none
+ *             for a channel without a curve, which is clipped at 0).  Refused (exit 1, also under --dry_run): a value other than 0 or
+ *             1, the flag without --gamut_convert 1, a parameter without the flag, out of range or not a number, --gamut_clip beside
+ *             the flag (the pass has its own rule at 0), XYZ (primaries 10) on either side.
  * --tone_map 1 [--tone_map_src_peak S] [--tone_map_dst_peak D] (an addition; the reference has no tone mapper, its README sends the
  *             user to ctlrender): the decoded source planes, after --gamut_convert's pass where that is given, are brought from a
  *             mastering peak of S cd/m2 (1000 by default) down to a target peak of D cd/m2 (100 by default) on the device by the
@@ -279,6 +288,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <strings.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -332,6 +342,13 @@ struct cli_args {
     /* --gamut_convert 1: the source planes go from the source's to the destination's primaries; --gamut_clip (1 by default) */
     int gamut = 0, gamut_clip = 1;
     bool gamut_given = false, gamut_clip_given = false;
+    /* --gamut_compress 1 beside --gamut_convert 1: out-of-gamut colours are rolled off, not clipped; the threshold and the power
+     * as given (strtof leaves a text that is no number at NaN's place: gamut_compress_*_bad) */
+    int gamut_compress = 0;
+    bool gamut_compress_given = false, gamut_compress_threshold_given = false, gamut_compress_power_given = false;
+    bool gamut_compress_threshold_bad = false, gamut_compress_power_bad = false;
+    float gamut_compress_threshold = H2Y_GAMUT_COMPRESS_THRESHOLD, gamut_compress_power = H2Y_GAMUT_COMPRESS_POWER;
+    bool gamut_compress_any() const { return gamut_compress_given || gamut_compress_threshold_given || gamut_compress_power_given; }
     /* --tone_map 1: the source planes go from a mastering peak of tone_src_peak cd/m2 down to tone_dst_peak; tone_relative, resolved:
      * the output is display-referred (1.0 = tone_dst_peak) for every destination transfer but PQ */
     int tone_map = 0, tone_src_peak = 1000, tone_dst_peak = 100, tone_relative = 1;
@@ -488,6 +505,9 @@ static inline void cli_help()
            "  primaries: [--gamut_convert 1 [--gamut_clip 0|1]] (float or half G,B,R source planes in linear light converted from\n"
            "  --src_colour_primaries to --dst_colour_primaries on the GPU before the conversion; 1 BT.709, 8 / 9 BT.2020, 12 P3-D65,\n"
            "  10 XYZ; what is not above 0 is clipped to 0 unless --gamut_clip 0)\n"
+           "  gamut compression: beside --gamut_convert 1, [--gamut_compress 1 [--gamut_compress_threshold T] [--gamut_compress_power P]]\n"
+           "  (out-of-gamut colours are rolled off toward the pixel's largest channel in the same pass, not clipped; T 0.5 .. 0.95, 0.8 by\n"
+           "  default; P 1 .. 4, 1.2 by default; not with --gamut_clip, not with XYZ)\n"
            "  tone mapping: [--tone_map 1 [--tone_map_src_peak S] [--tone_map_dst_peak D]] (float or half G,B,R source planes in linear\n"
            "  light brought from a mastering peak of S cd/m2, 1000 by default, down to D, 100 by default, on the GPU by the BT.2390\n"
            "  curve on max(R,G,B) before the conversion: the SDR rung of an HDR master, or a 1000 cd/m2 PQ rung of a 4000 cd/m2 one)\n"
@@ -557,6 +577,21 @@ static inline void cli_parse(cli_args &a, int argc, char **argv)
         else if (is("--scene_qpfile")) a.scene_qpfile = val();
         else if (is("--gamut_convert")) { a.gamut = atoi(val()); a.gamut_given = true; }
         else if (is("--gamut_clip")) { a.gamut_clip = atoi(val()); a.gamut_clip_given = true; }
+        else if (is("--gamut_compress")) { a.gamut_compress = atoi(val()); a.gamut_compress_given = true; }
+        else if (is("--gamut_compress_threshold")) {
+            const char *v = val();
+            char *end = nullptr;
+            a.gamut_compress_threshold = strtof(v, &end);
+            a.gamut_compress_threshold_bad = end == v || *end != 0;
+            a.gamut_compress_threshold_given = true;
+        }
+        else if (is("--gamut_compress_power")) {
+            const char *v = val();
+            char *end = nullptr;
+            a.gamut_compress_power = strtof(v, &end);
+            a.gamut_compress_power_bad = end == v || *end != 0;
+            a.gamut_compress_power_given = true;
+        }
         else if (is("--tone_map")) { a.tone_map = atoi(val()); a.tone_map_given = true; }
         else if (is("--tone_map_src_peak")) { a.tone_src_peak = atoi(val()); a.tone_src_peak_given = true; }
         else if (is("--tone_map_dst_peak")) { a.tone_dst_peak = atoi(val()); a.tone_dst_peak_given = true; }
@@ -758,6 +793,7 @@ static inline int cli_resolve_dynmeta(cli_args &a);
 static inline int cli_resolve_scale_only(cli_args &a);
 static inline int cli_resolve_scale(cli_args &a);
 static inline int cli_resolve_gamut(cli_args &a, int src_matrix_arg);
+static inline int cli_resolve_gamut_compress(cli_args &a);
 static inline int cli_resolve_tone_map(cli_args &a, int src_matrix_arg);
 static inline int cli_resolve_hlg(cli_args &a, int src_matrix_arg);
 static inline int cli_resolve_lut3d(cli_args &a, int src_matrix_arg);
@@ -977,7 +1013,7 @@ static inline int cli_resolve_all(cli_args &a)
     if (a.dynmeta) arg_errors += cli_resolve_dynmeta(a);
     if (a.scene_detect_given || a.scene_threshold_given || a.scene_cuts || a.scene_qpfile) arg_errors += cli_resolve_scenes(a);
     if (a.scale_given || a.scale_only || a.scale_taps_given) arg_errors += cli_resolve_scale(a);
-    if (a.gamut_given || a.gamut_clip_given) arg_errors += cli_resolve_gamut(a, src_matrix_arg);
+    if (a.gamut_given || a.gamut_clip_given || a.gamut_compress_any()) arg_errors += cli_resolve_gamut(a, src_matrix_arg);
     if (a.tone_map_given || a.tone_src_peak_given || a.tone_dst_peak_given) arg_errors += cli_resolve_tone_map(a, src_matrix_arg);
     if (lut3d_flags) arg_errors += cli_resolve_lut3d(a, src_matrix_arg);
     if (a.hlg_given || a.hlg_peak_given) arg_errors += cli_resolve_hlg(a, src_matrix_arg);
@@ -1261,7 +1297,7 @@ static inline int cli_resolve_light_only(cli_args &a)
     }
     if (a.dst) { printf("WARNING: --light_only writes no frames: leave out --dst_filename\n"); arg_errors++; }
     if (a.ref || a.hist || a.hist_bits_given || a.check_range || a.ssim_given || a.scale_given || a.scale_taps_given || a.gamut_given ||
-        a.gamut_clip_given || a.light_given || a.siting_given) {
+        a.gamut_clip_given || a.gamut_compress_any() || a.light_given || a.siting_given) {
         printf("WARNING: --light_only measures one file's light: leave out --ref_filename, --histogram, --ssim, --scale, --gamut_convert, "
                "--content_light and --dst_chroma_sample_loc_type\n");
         arg_errors++;
@@ -1696,8 +1732,21 @@ static inline int cli_resolve_gamut(cli_args &a, int src_matrix_arg)
         printf("WARNING: gamut_clip(%d) not 0 or 1\n", a.gamut_clip);
         return 1;
     }
+    if (a.gamut_compress_given && a.gamut_compress != 0 && a.gamut_compress != 1) {
+        printf("WARNING: gamut_compress(%d) not 0 or 1\n", a.gamut_compress);
+        return 1;
+    }
+    if (a.gamut_compress_threshold_bad || a.gamut_compress_power_bad) {
+        printf("WARNING: --gamut_compress_%s is not a number\n", a.gamut_compress_threshold_bad ? "threshold" : "power");
+        return 1;
+    }
+    if (!a.gamut_compress && (a.gamut_compress_threshold_given || a.gamut_compress_power_given)) {
+        printf("WARNING: --gamut_compress_%s needs --gamut_compress 1\n", a.gamut_compress_threshold_given ? "threshold" : "power");
+        return 1;
+    }
     if (!a.gamut) {
         if (a.gamut_clip_given) { printf("WARNING: --gamut_clip needs --gamut_convert 1\n"); return 1; }
+        if (a.gamut_compress) { printf("WARNING: --gamut_compress 1 needs --gamut_convert 1\n"); return 1; }
         return 0;
     }
     if (a.compare_only || a.hist_only || a.scale_only) {
@@ -1732,6 +1781,33 @@ static inline int cli_resolve_gamut(cli_args &a, int src_matrix_arg)
     }
     printf("gamut_matrix:");
     for (int i = 0; i < 9; i++) printf(" %.9g", m[i]);
+    printf("\n");
+    return a.gamut_compress ? cli_resolve_gamut_compress(a) : 0;
+}
+
+/* --gamut_compress 1 and its two parameters beside a --gamut_convert 1 that resolved: prints the setting and the limits; returns the
+ * number of argument errors */
+static inline int cli_resolve_gamut_compress(cli_args &a)
+{
+    printf("gamut_compress: 1\ngamut_compress_threshold: %.9g%s\ngamut_compress_power: %.9g%s\n", a.gamut_compress_threshold,
+           a.gamut_compress_threshold_given ? "" : " (default)", a.gamut_compress_power, a.gamut_compress_power_given ? "" : " (default)");
+    if (a.gamut_clip_given) {
+        printf("WARNING: --gamut_compress 1 has its own rule at 0: leave out --gamut_clip\n");
+        return 1;
+    }
+    std::unique_ptr<h2y_gamut_compress_tables> c(new h2y_gamut_compress_tables);
+    const char *why = nullptr;
+    if (h2y_gamut_compress_curve(a.in.colour_primaries, a.out.colour_primaries, a.gamut_compress_threshold, a.gamut_compress_power, c.get(),
+                                 &why)) {
+        printf("WARNING: --gamut_compress 1: src_colour_primaries(%d) -> dst_colour_primaries(%d), threshold %g, power %g: %s\n",
+               a.in.colour_primaries, a.out.colour_primaries, a.gamut_compress_threshold, a.gamut_compress_power, why);
+        return 1;
+    }
+    printf("gamut_compress_limits:");
+    for (int i = 0; i < 3; i++) {
+        if (c->limit[i] > 1.0f) printf(" %.9g", c->limit[i]);
+        else printf(" none");
+    }
     printf("\n");
     return 0;
 }

@@ -131,7 +131,10 @@
  * arms its ring (h2y_stream_gamut) with --src_colour_primaries and --dst_colour_primaries, so every slot's decoded planes are
  * converted in place on the device before pic_stats and the conversion: the run writes the bytes it would write had the source
  * held the converted planes, and --content_light beside it measures the converted light.  The banner carries gamut_convert:,
- * gamut_clip: and the nine entries of gamut_matrix: as "%.9g".
+ * gamut_clip: and the nine entries of gamut_matrix: as "%.9g".  With --gamut_compress 1 [--gamut_compress_threshold T]
+ * [--gamut_compress_power P] beside it the ring is armed with h2y_stream_gamut_compress instead: the same matrix, and out-of-gamut
+ * colours rolled off toward the pixel's largest channel, not clipped; the banner carries gamut_compress:, the two parameters and
+ * gamut_compress_limits:.
  *
  * Tone mapping (--tone_map 1 [--tone_map_src_peak S] [--tone_map_dst_peak D] on the forward flow from .f32, .f16, .exr and .dpx;
  * h2y_cli_args.h): each GPU thread opens its ring with floor 0 and ceiling 1 for every frame and arms it (h2y_stream_tonemap), so
@@ -452,7 +455,9 @@ static flow forward_flow(const job &j)
                (a.delta_e && h2y_stream_deltae(ctx, &a.de, a.delta_e_threshold)) ||
                (a.hist && h2y_stream_histogram(ctx, a.hist_bits)) || (a.light && h2y_stream_light(ctx)) ||
                (a.dynmeta && h2y_stream_lightdist(ctx)) || (a.scene_detect == 1 && h2y_stream_scenesig(ctx)) ||
-               (a.gamut && h2y_stream_gamut(ctx, a.in.colour_primaries, a.out.colour_primaries, a.gamut_clip)) ||
+               (a.gamut && !a.gamut_compress && h2y_stream_gamut(ctx, a.in.colour_primaries, a.out.colour_primaries, a.gamut_clip)) ||
+               (a.gamut && a.gamut_compress && h2y_stream_gamut_compress(ctx, a.in.colour_primaries, a.out.colour_primaries,
+                                                                         a.gamut_compress_threshold, a.gamut_compress_power)) ||
                (a.tone_map && h2y_stream_tonemap(ctx, a.tone_src_peak, a.tone_dst_peak, a.tone_relative)) ||
                (a.lut3d_table && h2y_stream_lut3d(ctx, a.lut3d_table, a.lut3d_interp, a.lut3d_signal)) ||
                (a.hlg == 1 && h2y_stream_hlg(ctx, a.hlg_peak, a.hlg_relative)) || (a.ictcp == 1 && h2y_stream_ictcp(ctx)) ||

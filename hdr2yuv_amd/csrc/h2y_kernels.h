@@ -458,6 +458,22 @@ struct gamut_args {
 uint32_t h2y_gamut_chunks(int in_kind, uint32_t npix); /* k_gamut's units of 256 threads per frame */
 hipError_t h2y_launch_gamut(int in_kind, int grid, hipStream_t st, const gamut_args &a, const gamut_frame *frames, int n_frames);
 
+/* k_gamut_compress (h2y_gamut_compress.hip): the gamut compression pass of include/hdr2yuv_hip.h on frames of three float or half
+ * planes G, B, R, k_gamut's frame table and units (dst may be src: in place) */
+struct gamut_compress_consts {
+    float m[9];       /* row-major, on (R, G, B) columns: h2y_gamut_matrix's */
+    float t;          /* the threshold */
+    float q;          /* at least 1 - t (1 - 2^-20): a pixel whose smallest channel is fl(a q) or more is inside the threshold */
+    float l[3], k[3]; /* per channel R, G, B: the limit (a curve where it is above 1) and the table's scale */
+};
+struct gamut_compress_args {
+    uint32_t npix; /* pixels per frame (< 2^28) */
+    gamut_compress_consts c;
+    const float *tables; /* device: 3 x H2Y_GAMUT_COMPRESS_NODES entries, R's, G's, B's */
+};
+hipError_t h2y_launch_gamut_compress(int in_kind, int grid, hipStream_t st, const gamut_compress_args &a, const gamut_frame *frames,
+                                     int n_frames);
+
 /* k_tonemap (h2y_tonemap.hip): the tone curve of include/hdr2yuv_hip.h on frames of three float or half planes G, B, R in linear
  * light, k_gamut's frame table (dst may be src: in place) */
 struct tonemap_args {

@@ -11,6 +11,7 @@
 
 #include "h2y_lut3d1.h"
 #include "h2y_hlg1.h"
+#include "h2y_gamut1.h"
 #include "h2y_dither1.h"
 #include "h2y_pack1.h"
 
@@ -2186,6 +2187,159 @@ int h2y_stream_gamut(h2y_ctx *ctx, int src_primaries, int dst_primaries, int cli
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     st->in_kind = in_kind_of(d);
     st->grid = unit_grid(ctx, h2y_gamut_chunks(st->in_kind, st->a.npix));
+    st->table(st->tab, ring_planes_table(ctx));
+    return stage_arm(ctx, STAGE_GAMUT, std::move(st), "gamut");
+}
+
+/* ---- gamut compression (--gamut_compress; the reference has no such step): include/hdr2yuv_hip.h states the definition --------------- */
+
+int h2y_gamut_compress_curve(int src_primaries, int dst_primaries, float threshold, float power, h2y_gamut_compress_tables *out,
+                             const char **why)
+{
+    const char *dummy;
+    if (!why) why = &dummy;
+    *why = "";
+    if (!out) { *why = "null tables"; return H2Y_EINVAL; }
+    if (!(threshold >= 0.5f && threshold <= 0.95f)) { *why = "threshold outside 0.5 <= threshold <= 0.95"; return H2Y_EINVAL; }
+    if (!(power >= 1.0f && power <= 4.0f)) { *why = "power outside 1 <= power <= 4"; return H2Y_EINVAL; }
+    if (src_primaries == 10 || dst_primaries == 10) {
+        *why = "XYZ (colour primaries 10) has no gamut to take limits from: convert it with the clip";
+        return H2Y_EUNSUPPORTED;
+    }
+    memset(out, 0, sizeof *out);
+    const int rc = h2y_gamut_matrix(src_primaries, dst_primaries, out->m, why);
+    if (rc) return rc;
+    out->threshold = threshold, out->power = power;
+    static const double kCorner[6][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}, {0, 1, 1}, {1, 0, 1}, {1, 1, 0}};
+    double lim[3] = {0.0, 0.0, 0.0};
+    for (const double *x : kCorner) {
+        double o[3];
+        for (int i = 0; i < 3; i++) o[i] = ((double)out->m[3 * i] * x[0] + (double)out->m[3 * i + 1] * x[1]) + (double)out->m[3 * i + 2] * x[2];
+        const double a = std::max(std::max(o[0], o[1]), o[2]);
+        for (int i = 0; i < 3; i++) lim[i] = std::max(lim[i], (a - o[i]) / a);
+    }
+    const double t = threshold, p = power;
+    for (int i = 0; i < 3; i++) {
+        out->limit[i] = (float)lim[i];
+        if (!(out->limit[i] > 1.0f)) continue;
+        const double w = (double)out->limit[i] - t, s = w / pow(pow((1.0 - t) / w, -p) - 1.0, 1.0 / p);
+        out->scale[i] = (float)(1024.0 / w);
+        float *T = out->table[i];
+        for (int k = 1; k < H2Y_GAMUT_COMPRESS_NODES - 1; k++) {
+            const double u = (w * k) / 1024.0;
+            T[k] = (float)(t + u / pow(1.0 + pow(u / s, p), 1.0 / p));
+        }
+        T[0] = threshold, T[H2Y_GAMUT_COMPRESS_NODES - 1] = 1.0f;
+    }
+    return H2Y_OK;
+}
+
+/* the pixel's constants of a curve */
+static void gamut_compress_consts_of(const h2y_gamut_compress_tables &c, gamut_compress_consts &k)
+{
+    memcpy(k.m, c.m, sizeof k.m);
+    k.t = c.threshold;
+    const double q = 1.0 - (double)c.threshold * (1.0 - 0x1p-20);
+    k.q = (float)q;
+    if ((double)k.q < q) k.q = nextafterf(k.q, 2.0f);
+    for (int i = 0; i < 3; i++) k.l[i] = c.limit[i], k.k[i] = c.scale[i];
+}
+
+int h2y_gamut_compress_planes(int src_primaries, int dst_primaries, float threshold, float power, int sample_type, size_t npix,
+                              const void *const src[3], void *const dst[3])
+{
+    if (sample_type != H2Y_SAMPLE_F32 && sample_type != H2Y_SAMPLE_F16)
+        return fail(nullptr, H2Y_EUNSUPPORTED, "gamut compression reads float or half planes, not sample type %d", sample_type);
+    if (!src || !dst || !src[0] || !src[1] || !src[2] || !dst[0] || !dst[1] || !dst[2]) return fail(nullptr, H2Y_EINVAL, "null planes");
+    auto c = std::make_unique<h2y_gamut_compress_tables>();
+    const char *why;
+    const int rc = h2y_gamut_compress_curve(src_primaries, dst_primaries, threshold, power, c.get(), &why);
+    if (rc) return fail(nullptr, rc, "gamut compression %d -> %d: %s", src_primaries, dst_primaries, why);
+    gamut_compress_consts k{};
+    gamut_compress_consts_of(*c, k);
+    const float *T = &c->table[0][0];
+    for (size_t i = 0; i < npix; i++) {
+        float v[3], o[3]; /* v: G, B, R; o: R, G, B */
+        for (int p = 0; p < 3; p++) {
+            if (sample_type == H2Y_SAMPLE_F32) v[p] = static_cast<const float *>(src[p])[i];
+            else v[p] = (float)static_cast<const _Float16 *>(src[p])[i]; /* exact */
+        }
+        gamut_compress_pixel(k, T, v[2], v[0], v[1], o);
+        const float w[3] = {o[1], o[2], o[0]};
+        for (int p = 0; p < 3; p++) {
+            if (sample_type == H2Y_SAMPLE_F32) static_cast<float *>(dst[p])[i] = w[p];
+            else static_cast<_Float16 *>(dst[p])[i] = (_Float16)w[p]; /* to nearest even */
+        }
+    }
+    return H2Y_OK;
+}
+
+/* k_gamut_compress' arguments for frames of width x height, but for the device tables; the checks of both entries */
+static int gamut_compress_args_of(h2y_ctx *ctx, int width, int height, int sample_type, int src_primaries, int dst_primaries,
+                                  float threshold, float power, gamut_compress_args &a, std::vector<float> &tables)
+{
+    if (sample_type == H2Y_SAMPLE_U16)
+        return fail(ctx, H2Y_EUNSUPPORTED, "gamut compression works in linear light on float or half planes, not on U16 samples");
+    if (sample_type != H2Y_SAMPLE_F32 && sample_type != H2Y_SAMPLE_F16) return fail(ctx, H2Y_EINVAL, "bad sample type %d", sample_type);
+    int rc = picture_size_check(ctx, width, height);
+    if (rc) return rc;
+    auto c = std::make_unique<h2y_gamut_compress_tables>();
+    const char *why;
+    rc = h2y_gamut_compress_curve(src_primaries, dst_primaries, threshold, power, c.get(), &why);
+    if (rc) return fail(ctx, rc, "gamut compression %d -> %d, threshold %g, power %g: %s", src_primaries, dst_primaries, threshold, power, why);
+    gamut_compress_consts_of(*c, a.c);
+    tables.assign(&c->table[0][0], &c->table[0][0] + 3 * H2Y_GAMUT_COMPRESS_NODES);
+    a.npix = (uint32_t)width * (uint32_t)height;
+    return H2Y_OK;
+}
+
+int h2y_gamut_compress_batch(h2y_ctx *ctx, int width, int height, int sample_type, int src_primaries, int dst_primaries, float threshold,
+                             float power, int n_frames, const void *const *d_src, void *const *d_dst)
+{
+    gamut_compress_args a{};
+    std::vector<float> tables;
+    gamut_frame *h;
+    int rc = batch_enter(ctx);
+    if (!rc) rc = gamut_compress_args_of(ctx, width, height, sample_type, src_primaries, dst_primaries, threshold, power, a, tables);
+    if (!rc) rc = pass_frames(ctx, n_frames, d_src, d_dst, false, h);
+    if (!rc) rc = ensure(ctx, ctx->gamut_compress_tables, tables.size() * sizeof(float));
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpy(ctx->gamut_compress_tables.p, tables.data(), tables.size() * sizeof(float), hipMemcpyHostToDevice));
+    a.tables = ctx->gamut_compress_tables.p;
+    const int in_kind = sample_type == H2Y_SAMPLE_F16 ? H2Y_IN_F16 : H2Y_IN_F32;
+    const uint64_t per_frame = h2y_gamut_chunks(in_kind, a.npix);
+    rc = timed_launches(ctx, h, n_frames, H2Y_GAMUT_COMPRESS_FRAMES_PER_LAUNCH, "k_gamut_compress", [&](const gamut_frame *frames, int, int nf) {
+        return h2y_launch_gamut_compress(in_kind, unit_grid(ctx, per_frame * nf), ctx->stream, a, frames, nf);
+    });
+    if (rc) return rc;
+    ctx->last_variant = std::string("k_gamut_compress<") + (in_kind == H2Y_IN_F16 ? "F16>" : "F32>");
+    return H2Y_OK;
+}
+
+/* The compression's ring stage: the gamut stage's place, k_gamut_compress on the decoded planes with the tables of its own */
+int h2y_stream_gamut_compress(h2y_ctx *ctx, int src_primaries, int dst_primaries, float threshold, float power)
+{
+    int rc = arm_enter(ctx);
+    if (rc) return rc;
+    if (ctx->s_kind != h2y_ctx::RING_FORWARD) return fail(ctx, H2Y_EINVAL, "primaries are converted on the forward rings only");
+    rc = arm_free(ctx, STAGE_GAMUT, "the ring converts primaries already");
+    if (rc) return rc;
+    const h2y_desc *d = &ctx->s_desc;
+    auto st = std::make_unique<pass_stage<gamut_compress_args>>();
+    st->launch = h2y_launch_gamut_compress;
+    std::vector<float> tables;
+    rc = gamut_compress_args_of(ctx, d->width, d->height, d->in_sample_type, src_primaries, dst_primaries, threshold, power, st->a, tables);
+    if (rc) return rc;
+    if (d->src_transfer != H2Y_TRANSFER_LINEAR)
+        return fail(ctx, H2Y_EUNSUPPORTED, "primaries are converted in linear light (src_transfer 8), not src_transfer %d", d->src_transfer);
+    if (d->src_matrix != H2Y_MATRIX_GBR)
+        return fail(ctx, H2Y_EUNSUPPORTED, "converting primaries needs a G,B,R source (src_matrix 0), not src_matrix %d", d->src_matrix);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    st->in_kind = in_kind_of(d);
+    st->grid = unit_grid(ctx, h2y_gamut_chunks(st->in_kind, st->a.npix));
+    float *d_tables = nullptr;
+    st->table(d_tables, tables);
+    st->a.tables = d_tables;
     st->table(st->tab, ring_planes_table(ctx));
     return stage_arm(ctx, STAGE_GAMUT, std::move(st), "gamut");
 }

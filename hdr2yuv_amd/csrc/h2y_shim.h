@@ -301,6 +301,7 @@ struct h2y_ctx {
     dev_buf<unsigned long long> scenesig;      /* h2y_scenesig_batch's and h2y_codescenesig_batch's cells: 144 uint64 a frame */
     dev_buf<deltae_acc> deltae;                /* h2y_deltae_batch's accumulators */
     dev_buf<char> scale_tabs;                  /* h2y_scale_batch's tap tables */
+    dev_buf<float> gamut_compress_tables;      /* h2y_gamut_compress_batch's three tables */
     dev_buf<float> tonemap_gain;               /* h2y_tonemap_batch's gain table */
     dev_buf<lut3d_node> lut3d;                 /* h2y_lut3d_batch's table */
     dev_buf<float> hlg_tables;                 /* h2y_hlg_batch's two tables: the gains, then the OETF's */

@@ -1215,6 +1215,86 @@ int h2y_gamut_batch(h2y_ctx *ctx, int width, int height, int sample_type, int sr
  * first input, on a ring armed already, for equal chromaticities and a clip other than 0 or 1. */
 int h2y_stream_gamut(h2y_ctx *ctx, int src_primaries, int dst_primaries, int clip);
 
+/* ---- gamut compression: out-of-gamut colours rolled off, not clipped (--gamut_convert 1 --gamut_compress 1) ------------------------
+ * The conversion above clips at 0: a saturated colour of the source loses the detail of its smallest channels, and its hue moves,
+ * because one channel stops while the other two go on.  This pass does the same matrix and, in the same trip through memory, brings
+ * the channels that the matrix left far below the pixel's largest channel back above 0 along a smooth curve.  It stands where
+ * h2y_stream_gamut's pass stands, in its place.  The reference has no such step: this is the project's own definition, as the
+ * conversion, tone mapping and the LUT are.
+ * The model is the distance-from-achromatic form of the ACES 1.3 Reference Gamut Compression: per pixel a = max(R, G, B) is the
+ * achromatic axis, per channel d = (a - c) / a is the distance from it (0 on the axis, 1 at the destination gamut's boundary, above
+ * 1 outside), and a curve C brings the distances t .. l onto t .. 1 while those below t stay.  The limits l come from the source
+ * primaries, not from camera gamuts.
+ * Parameters, both binary32: the threshold t, 0.5 <= t <= 0.95, and the power p, 1 <= p <= 4; every formula below takes their
+ *   exact values.  H2Y_GAMUT_COMPRESS_THRESHOLD and _POWER are the defaults: choices in the range ACES uses, no measurements.
+ * Host, in binary64; each operation as written, pow is the C library's:
+ *   1. M = h2y_gamut_matrix(src, dst), nine binary32 entries, widened.
+ *   2. Limits.  For each of the six corners x of the source cube, in the order (1,0,0) (0,1,0) (0,0,1) (0,1,1) (1,0,1) (1,1,0):
+ *      o_i = ((m[i][0] x0) + (m[i][1] x1)) + (m[i][2] x2), a = max(o0, o1, o2), d_i = (a - o_i) / a.  The limit of channel i is the
+ *      largest d_i of the six, rounded once to binary32: l_i.  From here on l_i is that binary32 value, widened.
+ *   3. A channel with l_i <= 1 has no curve: its scale and its table are zeros, and the pixel rule clips it at 0 as k_gamut does.
+ *   4. For a channel with a curve: w = l - t,  s = w / pow(pow((1 - t) / w, -p) - 1, 1 / p),
+ *      C(u) = t + u / pow(1 + pow(u / s, p), 1 / p) for a distance t + u, so that C(0) = t and C(w) = 1.
+ *   5. Table: H2Y_GAMUT_COMPRESS_NODES = 1025 binary32 entries, T[k] = C((w k) / 1024) rounded once, but T[0] = t and T[1024] = 1
+ *      exactly.  Scale: k = 1024 / w, rounded once to binary32.
+ *   XYZ (code 10) on either side is H2Y_EUNSUPPORTED: a cube of XYZ has no gamut to take limits from.
+ * Pixel, in binary32; a half is widened first (exact).  Every product, sum, difference and quotient is one round-to-nearest
+ *   operation in the order written, no fused multiply-add; subnormals are kept:
+ *   1. o_i as h2y_gamut_batch's pixel computes them, without its clip.
+ *   2. An o_i that is a NaN becomes +0.0, one that is +inf becomes the largest finite binary32 (-inf stays: it is a negative).
+ *   3. a = max(max(o_0, o_1), o_2).  Where a is not above 0, all three outputs are +0.0.
+ *   4. Otherwise, per channel, d = (a - o_i) / a:
+ *      d <= t: the output is o_i, bit for bit (the largest channel has d = 0: it never changes);
+ *      otherwise, a channel without a curve: o_i where o_i > 0, else +0.0 -- the clip;
+ *      otherwise, d >= l_i: +0.0;
+ *      otherwise x = (d - t) k_i, n = min((int)x, 1023), f = x - n, cd = T_i[n] + (T_i[n + 1] - T_i[n]) f, v = a - cd a,
+ *      and the output is v where v > 0, else +0.0.
+ *   p0' = out_1, p1' = out_2, p2' = out_0.  F32 is stored as is; F16 is rounded to nearest even.  The sample type does not change.
+ * What follows: no output is negative or a NaN, whatever the input; greys and every colour within the threshold keep their bits;
+ *   max(R, G, B) of a pixel is what h2y_gamut_batch with clip 1 leaves (but for step 2: there +inf stays +inf); each channel's map is
+ *   continuous at t and at l and does not decrease.  The six corners are not the extremes of d over the whole cube: between two
+ *   corners d passes l (0.8 % of uniformly random BT.2020 pixels going to BT.709 in a numpy prototype), and such a channel is +0.0,
+ *   continuously, as the clip leaves it.  Where no channel has a curve (BT.709 -> BT.2020) the pass equals h2y_gamut_batch with
+ *   clip 1 but for step 2's +inf: a NaN becomes +0.0 in both, a sum of +inf stays there and is the largest finite binary32 here (in
+ *   an F16 plane that is +inf again).
+ * With the defaults the interpolated table stays within 2^-18 of C on every channel of 9 -> 1, 12 -> 1 and 9 -> 12. */
+#define H2Y_GAMUT_COMPRESS_NODES 1025
+#define H2Y_GAMUT_COMPRESS_THRESHOLD 0.8f
+#define H2Y_GAMUT_COMPRESS_POWER 1.2f
+#define H2Y_GAMUT_COMPRESS_FRAMES_PER_LAUNCH 64
+
+typedef struct h2y_gamut_compress_tables {
+    float m[9];                                /* h2y_gamut_matrix's */
+    float threshold, power;                    /* as given */
+    float limit[3];                            /* R, G, B: l_i; a curve where it is above 1 */
+    float scale[3];                            /* k_i; 0 without a curve */
+    float table[3][H2Y_GAMUT_COMPRESS_NODES];  /* T_i; zeros without a curve */
+} h2y_gamut_compress_tables;
+
+/* The matrix, the limits, the scales and the tables of a pair of primaries.  Host only: no device, no context.  `why` (may be NULL)
+ * receives a static string.  H2Y_EINVAL for a null out, a threshold or power out of range or not finite and for what
+ * h2y_gamut_matrix refuses so; H2Y_EUNSUPPORTED for XYZ on either side and for what h2y_gamut_matrix refuses so. */
+int h2y_gamut_compress_curve(int src_primaries, int dst_primaries, float threshold, float power, h2y_gamut_compress_tables *out,
+                             const char **why);
+
+/* The pass on host planes, k_gamut_compress' CPU twin: src[c] / dst[c] are plane c = G, B, R of npix samples of sample_type
+ * H2Y_SAMPLE_F32 or H2Y_SAMPLE_F16 (anything else: H2Y_EUNSUPPORTED); dst[c] may be src[c].  Host only. */
+int h2y_gamut_compress_planes(int src_primaries, int dst_primaries, float threshold, float power, int sample_type, size_t npix,
+                              const void *const src[3], void *const dst[3]);
+
+/* k_gamut_compress on n_frames device frames of width x height, as h2y_gamut_batch takes them: d_src[f*3 + c] / d_dst[f*3 + c] are
+ * plane c = G, B, R of frame f, 16-byte aligned; a d_dst entry may equal its d_src entry (in place; no other overlap).  sample_type
+ * H2Y_SAMPLE_F32 or H2Y_SAMPLE_F16 (H2Y_SAMPLE_U16: H2Y_EUNSUPPORTED).  Launches of up to H2Y_GAMUT_COMPRESS_FRAMES_PER_LAUNCH frames
+ * (h2y_last_kernel_ms sums them, h2y_last_kernel_name "k_gamut_compress"); synchronous. */
+int h2y_gamut_compress_batch(h2y_ctx *ctx, int width, int height, int sample_type, int src_primaries, int dst_primaries, float threshold,
+                             float power, int n_frames, const void *const *d_src, void *const *d_dst);
+
+/* Arm an open forward ring as h2y_stream_gamut arms it, on the same kinds of ring, with k_gamut_compress in k_gamut's place: in
+ * place on every slot's decoded device planes, after the decode, before h2y_stream_tonemap's, h2y_stream_lut3d's, h2y_stream_hlg's
+ * and h2y_stream_ictcp's passes, pic_stats and the conversion.  A ring takes one of the two gamut stages: H2Y_EINVAL on a ring armed
+ * with either already, and after the first input.  Otherwise h2y_stream_gamut's refusals, and h2y_gamut_compress_curve's. */
+int h2y_stream_gamut_compress(h2y_ctx *ctx, int src_primaries, int dst_primaries, float threshold, float power);
+
 /* ---- tone mapping: the light of an HDR master brought down to a target peak, in linear light (--tone_map 1) ----------------------
  * The reference has no tone mapper (its README sends the user to ctlrender), so there are no bytes to match: this is the project's
  * own definition, as scaling, primaries, siting and the light figures are.  A pass over the decoded source planes, after
@@ -1265,8 +1345,9 @@ int h2y_tonemap_batch(h2y_ctx *ctx, int width, int height, int sample_type, int 
 
 /* Arm an open forward ring whose decoded planes are float or half (h2y_stream_open with F32 or F16 planes, h2y_dpx_stream_open,
  * h2y_exr_stream_open) before its first input, once: k_tonemap then runs in place on every slot's decoded device planes, on the
- * context's stream, after the decode and after h2y_stream_gamut's pass where that is armed (whichever was armed first) -- so it
- * sees the converted, clipped planes, and no channel leaves [0, cap] in the destination's primaries -- and before the conversion;
+ * context's stream, after the decode and after h2y_stream_gamut's or h2y_stream_gamut_compress' pass where one of the two is armed
+ * (whichever was armed first) -- so it sees the converted, clipped or compressed planes, and no channel leaves [0, cap] in the
+ * destination's primaries -- and before the conversion;
  * h2y_stream_light and h2y_stream_lightdist beside it measure the mapped light.
  * The ring must have been opened with stats_override 1, floor 0 and ceiling 1 on all three planes (H2Y_EINVAL otherwise): mapped
  * planes are referred to their target by definition, and the measured pic_stats of such a frame -- (int)max, 0 below 1.0 -- would

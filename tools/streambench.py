@@ -142,6 +142,14 @@ Prints one line per figure, then one JSON line with all of them.
      h2y_stream_gamut.
 Prints one line per figure, then one JSON line with all of them.
 
+`streambench.py gamut_compress`: gamut compression on 4K frames, beside k_gamut and k_tonemap in the same job: the kernel time of
+h2y_gamut_compress_batch (k_gamut_compress, BT.2020 -> BT.709, the default threshold and power), of h2y_gamut_batch (clip on) and of
+h2y_tonemap_batch (1000 -> 100 cd/m2, relative) over the same 64 distinct device frames per call (HIP events, median of five after a
+warm-up call), F32 and F16, out of place and in place (the frames put back before every in-place call), on uniformly random BT.2020
+pixels and on a smooth, mostly in-gamut picture; each picture's share of pixels with a channel past the threshold; the algorithmic
+bytes per frame over the time, their share of the 8 TB/s HBM peak, and k_gamut_compress' time over k_gamut's and k_tonemap's.
+Prints one line per figure, then one JSON line with all of them.
+
 `streambench.py tonemap`: the tone curve on 4K frames, beside k_gamut in the same job:
   1. the kernel time of h2y_tonemap_batch (k_tonemap, 1000 -> 100 cd/m2, relative) and of h2y_gamut_batch (k_gamut, BT.2020 ->
      BT.709, clip on) on the same 64 distinct device frames per call (HIP events, median of five after a warm-up call), F32 and
@@ -2550,6 +2558,95 @@ def tonemap_main():
     print(json.dumps({"streambench_tonemap": res}), flush=True)
 
 
+def gamut_compress_main():
+    """k_gamut_compress (BT.2020 -> BT.709, the default parameters) F32 and F16, out of place and in place, beside k_gamut and
+    k_tonemap on the same 64 distinct 4K device frames in the same job, on two pictures: uniformly random BT.2020 pixels (the worst
+    case: more than half of them have a channel in a curve) and a smooth, mostly in-gamut picture.  An in-place pass changes what the
+    next repetition would read, so the frames are put back from a copy before every in-place call (untimed: the times are the
+    kernels' HIP events)."""
+    import json
+
+    import torch
+
+    w, hh, nb, reps = 3840, 2160, 64, 5
+    n = w * hh
+    ctx = h.Context(0)
+    res = {"width": w, "height": hh, "frames_per_call": nb, "reps": reps, "hbm_peak_tbs": 8.0}
+    m = torch.tensor(h.gamut_matrix(9, 1), device="cuda")
+    t = float(np.float32(h.GAMUT_COMPRESS_THRESHOLD))
+
+    def timed(key, label, nbytes, call, before=None):
+        ks = []
+        for r in range(reps + 1):  # the first call warms up
+            if before:
+                before()
+            call()
+            if r:
+                ks.append(ctx.last_kernel_ms()[0] / nb)
+        k_ms = float(np.median(ks))
+        tbs = nbytes / (k_ms * 1e-3) / 1e12
+        res[key] = dict(kernel_us_per_frame=round(k_ms * 1e3, 2), min_us=round(min(ks) * 1e3, 2), max_us=round(max(ks) * 1e3, 2),
+                        bytes_per_frame=nbytes, kernel_tbs=round(tbs, 2), hbm_peak_fraction=round(tbs / 8.0, 3), variant=ctx.last_kernel_variant())
+        print(f"{label:44s} {nb} frames per call: {k_ms*1e3:7.2f} us/frame ({min(ks)*1e3:.2f}..{max(ks)*1e3:.2f})  {nbytes/1e6:6.1f} MB/frame  "
+              f"{tbs:5.2f} TB/s = {tbs/8.0*100:4.1f} % of 8 TB/s", flush=True)
+        return k_ms
+
+    def random_frame():
+        return [torch.rand(n, device="cuda") for _ in range(3)]  # G, B, R
+
+    def smooth_frame():
+        # a luminance ramp with slow waves, and a chroma of a few percent of it: every pixel far inside the threshold
+        x = torch.linspace(0, 1, n, device="cuda")
+        y = 0.05 + 0.6 * x + 0.1 * torch.sin(x * (37.0 + 3.0 * torch.rand(1, device="cuda")))
+        return [y * (1.0 + 0.04 * torch.sin(x * f)) for f in (11.0, 17.0, 23.0)]
+
+    def curve_share(f):
+        """the share of a frame's pixels with a channel past the threshold (in a curve or beyond its limit), in torch's binary32"""
+        v = torch.stack([f[2].float(), f[0].float(), f[1].float()])
+        o = m @ v
+        a = o.max(dim=0).values
+        return float((((a - o) / a > t).any(dim=0) & (a > 0)).float().mean())
+
+    for pic, make in (("random", random_frame), ("smooth", smooth_frame)):
+        for name, sample, dt in (("f32", h.SAMPLE_F32, torch.float32), ("f16", h.SAMPLE_F16, torch.float16)):
+            keep = [[x.to(dt) for x in make()] for _ in range(nb)]
+            src = [[x.clone() for x in f] for f in keep]
+            dst = [[torch.empty(n, dtype=dt, device="cuda") for _ in range(3)] for _ in range(nb)]
+            torch.cuda.synchronize()
+            res[f"{pic}_{name}_share_past_threshold"] = round(curve_share(keep[0]), 4)
+            print(f"{pic} {name}: {res[f'{pic}_{name}_share_past_threshold']*100:.1f} % of the pixels have a channel past the threshold", flush=True)
+            nbytes = 2 * 3 * n * (4 if sample == h.SAMPLE_F32 else 2)
+
+            def restore():
+                for fs, fk in zip(src, keep):
+                    for a, b in zip(fs, fk):
+                        a.copy_(b)
+                torch.cuda.synchronize()
+
+            tag = f"{pic}_{name}"
+            c_out = timed(f"k_gamut_compress_{tag}_out_of_place", f"k_gamut_compress {pic} {name} out of place", nbytes,
+                          lambda: ctx.gamut_compress_batch(w, hh, sample, 9, 1, src, dst))
+            g_out = timed(f"k_gamut_{tag}_out_of_place", f"k_gamut {pic} {name} out of place", nbytes,
+                          lambda: ctx.gamut_batch(w, hh, sample, 9, 1, 1, src, dst))
+            t_out = timed(f"k_tonemap_{tag}_out_of_place", f"k_tonemap {pic} {name} out of place", nbytes,
+                          lambda: ctx.tonemap_batch(w, hh, sample, 1000, 100, 1, src, dst))
+            del dst
+            c_in = timed(f"k_gamut_compress_{tag}_in_place", f"k_gamut_compress {pic} {name} in place", nbytes,
+                         lambda: ctx.gamut_compress_batch(w, hh, sample, 9, 1, src), restore)
+            g_in = timed(f"k_gamut_{tag}_in_place", f"k_gamut {pic} {name} in place", nbytes,
+                         lambda: ctx.gamut_batch(w, hh, sample, 9, 1, 1, src), restore)
+            t_in = timed(f"k_tonemap_{tag}_in_place", f"k_tonemap {pic} {name} in place", nbytes,
+                         lambda: ctx.tonemap_batch(w, hh, sample, 1000, 100, 1, src), restore)
+            res[f"{tag}_compress_over_gamut"] = dict(out_of_place=round(c_out / g_out, 3), in_place=round(c_in / g_in, 3))
+            res[f"{tag}_compress_over_tonemap"] = dict(out_of_place=round(c_out / t_out, 3), in_place=round(c_in / t_in, 3))
+            print(f"{tag}: k_gamut_compress / k_gamut out of place {c_out/g_out:.3f}, in place {c_in/g_in:.3f}; / k_tonemap out of place "
+                  f"{c_out/t_out:.3f}, in place {c_in/t_in:.3f}", flush=True)
+            del src, keep
+            torch.cuda.empty_cache()
+    ctx.close()
+    print(json.dumps({"streambench_gamut_compress": res}), flush=True)
+
+
 def lut3d_main():
     """k_lut3d at N = 17, 33 and 65, F32 and F16, tetrahedral and trilinear, out of place and in place, beside k_tonemap and k_gamut
     in the same job; then the .f32 ring from host memory armed against unarmed.  The bytes counted are the six plane streams only."""
@@ -2990,6 +3087,8 @@ if __name__ == "__main__":
         siting_main()
     elif sys.argv[1:] == ["gamut"]:
         gamut_main()
+    elif sys.argv[1:] == ["gamut_compress"]:
+        gamut_compress_main()
     elif sys.argv[1:] == ["tonemap"]:
         tonemap_main()
     elif sys.argv[1:] == ["lut3d"]:
