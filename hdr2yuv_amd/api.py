@@ -55,6 +55,7 @@ EXPORTS = [
     "h2y_hlg_tables", "h2y_hlg_planes", "h2y_hlg_batch", "h2y_stream_hlg",
     "h2y_hlg_inverse_tables", "h2y_hlg_inverse_planes", "h2y_hlg_linearize_batch", "h2y_hlgcode_stream_open",
     "h2y_sdr_inverse_planes", "h2y_sdr_linearize_batch", "h2y_sdrcode_stream_open",
+    "h2y_code_signal_planes", "h2y_code_signal_batch", "h2y_sigcode_stream_open",
     "h2y_ictcp_batch", "h2y_stream_ictcp",
     "h2y_ctx_set_chroma_siting", "h2y_subsample_420_sited",
     "h2y_ctx_set_inverse_chroma_siting", "h2y_upsample_444_sited",
@@ -679,6 +680,12 @@ def load_library():
     L.h2y_sdr_linearize_batch.restype = C.c_int
     L.h2y_sdrcode_stream_open.argtypes = [C.c_void_p, C.POINTER(H2YDesc), C.POINTER(H2YCodelightDesc), C.c_int, C.c_int]
     L.h2y_sdrcode_stream_open.restype = C.c_int
+    L.h2y_code_signal_planes.argtypes = [C.POINTER(H2YCodelightDesc), C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.h2y_code_signal_planes.restype = C.c_int
+    L.h2y_code_signal_batch.argtypes = [C.c_void_p, C.POINTER(H2YCodelightDesc), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.h2y_code_signal_batch.restype = C.c_int
+    L.h2y_sigcode_stream_open.argtypes = [C.c_void_p, C.POINTER(H2YDesc), C.POINTER(H2YCodelightDesc), C.c_void_p, C.c_int, C.c_int]
+    L.h2y_sigcode_stream_open.restype = C.c_int
     L.h2y_hlg_batch.argtypes = [C.c_void_p] + [C.c_int] * 9 + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.h2y_hlg_batch.restype = C.c_int
     L.h2y_stream_hlg.argtypes = [C.c_void_p] + [C.c_int] * 2
@@ -1152,6 +1159,23 @@ def sdr_inverse_planes(planes, white: int = SDR_WHITE_DEFAULT):
     return out
 
 
+def code_signal_planes(d: H2YCodelightDesc, planes):
+    """h2y_code_signal_planes (host only, no device): the signal of code planes on three uint16 numpy planes of 4:4:4 codes (Y, Cb, Cr
+    or G, B, R as d's matrix_coeffs says); returns the three float32 planes G', B', R' in [+0, 1] k_code_signal writes for them.
+    Raises H2YError with the descriptor's refusal (EUNSUPPORTED: matrix_coeffs 14)."""
+    src = [np.ascontiguousarray(p) for p in planes]
+    if len(src) != 3 or any(p.dtype != np.uint16 or p.shape != src[0].shape for p in src):
+        raise ValueError("three uint16 planes of one shape")
+    out = [np.empty(p.shape, np.float32) for p in src]
+    ins = (C.c_void_p * 3)(*[p.ctypes.data for p in src])
+    outs = (C.c_void_p * 3)(*[p.ctypes.data for p in out])
+    lib = load_library()
+    rc = lib.h2y_code_signal_planes(C.byref(d), src[0].size, ins, outs)
+    if rc != H2Y_OK:
+        raise H2YError(rc, (lib.h2y_last_error(None) or b"").decode())
+    return out
+
+
 def scale_frame_bytes(width: int, height: int, chroma: int) -> int:
     """h2y_scale_frame_bytes: bytes of a frame of three u16 planes (0 for an unsupported geometry)."""
     return int(load_library().h2y_scale_frame_bytes(width, height, chroma))
@@ -1537,15 +1561,32 @@ class Context:
                 outs[3 * f + c] = self._ptr(planes_out[f][c])
         self._check(self.lib.h2y_sdr_linearize_batch(self.h, C.byref(d), int(white), n, pf, outs))
 
-    def pqcode_stream_open(self, d, src: H2YCodelightDesc, depth=3, hlg_peak=None, sdr_white=None) -> None:
+    def code_signal_batch(self, d: H2YCodelightDesc, frames, planes_out) -> None:
+        """k_code_signal on device frames of codes, no transfer applied: linearize_batch's arguments and layout; planes_out[f] receive
+        the frame's signal G', B', R' in [+0, 1]."""
+        n = len(frames)
+        if len(planes_out) != n:
+            raise ValueError("frames and planes_out differ in length")
+        pf = (C.c_void_p * max(n, 1))(*[self._ptr(x) for x in frames])
+        outs = (C.c_void_p * max(3 * n, 1))()
+        for f in range(n):
+            for c in range(3):
+                outs[3 * f + c] = self._ptr(planes_out[f][c])
+        self._check(self.lib.h2y_code_signal_batch(self.h, C.byref(d), n, pf, outs))
+
+    def pqcode_stream_open(self, d, src: H2YCodelightDesc, depth=3, hlg_peak=None, sdr_white=None, signal_lut=None) -> None:
         """The forward ring on PQ code frames: stream_input gives one uint8 view of the pinned slot to fill with the frame's three
         u16 planes one after the other; the device linearises them (k_up444, k_linearize) into the F32 G,B,R planes d describes
         (src_transfer 8, src_matrix 0, stats_override 1 with floor 0, ceiling 1); stream_output gives the .yuv frame.  With hlg_peak
         the codes are HLG's at that display peak (h2y_hlgcode_stream_open: k_hlg_linearize), with sdr_white SDR (BT.1886) codes whose
-        reference white lies at that many cd/m2 (h2y_sdrcode_stream_open: k_sdr_linearize)."""
-        if hlg_peak is not None and sdr_white is not None:
-            raise ValueError("hlg_peak and sdr_white exclude one another")
-        if sdr_white is not None:
+        reference white lies at that many cd/m2 (h2y_sdrcode_stream_open: k_sdr_linearize), with signal_lut = (Lut3d or None, interp)
+        the codes stay signal for that table, armed in signal mode in the same call (h2y_sigcode_stream_open: k_code_signal)."""
+        if (hlg_peak is not None) + (sdr_white is not None) + (signal_lut is not None) > 1:
+            raise ValueError("hlg_peak, sdr_white and signal_lut exclude one another")
+        if signal_lut is not None:
+            lut, interp = signal_lut
+            self._check(self.lib.h2y_sigcode_stream_open(self.h, C.byref(d), C.byref(src), lut.h if lut is not None else None, int(interp), depth))
+        elif sdr_white is not None:
             self._check(self.lib.h2y_sdrcode_stream_open(self.h, C.byref(d), C.byref(src), int(sdr_white), depth))
         elif hlg_peak is None:
             self._check(self.lib.h2y_pqcode_stream_open(self.h, C.byref(d), C.byref(src), depth))
@@ -1566,6 +1607,12 @@ class Context:
     def sdrcode_stream_open(self, d, src: H2YCodelightDesc, white: int = SDR_WHITE_DEFAULT, depth=3) -> None:
         """The forward ring on SDR code frames with the reference white at `white` cd/m2: pqcode_stream_open with k_sdr_linearize as its decode."""
         self.pqcode_stream_open(d, src, depth, sdr_white=white)
+
+    def sigcode_stream_open(self, d, src: H2YCodelightDesc, lut, interp=1, depth=3) -> None:
+        """The forward ring on code frames that stay signal (no transfer applied), armed with the Lut3d in signal mode in the same
+        call: pqcode_stream_open with k_code_signal as its decode; d is the passthrough descriptor stream_lut3d(signal=1) arms on
+        (src_transfer 8 = dst_transfer, dst_matrix 0 or 9)."""
+        self.pqcode_stream_open(d, src, depth, signal_lut=(lut, interp))
 
     def scale_batch(self, src_w, src_h, dst_w, dst_h, chroma, bit_depth, full_range, gbr, a, frames_src, frames_dst) -> None:
         """k_scale on device frames (tensors or pointers, each frame's planes contiguous from a 16-byte aligned base):

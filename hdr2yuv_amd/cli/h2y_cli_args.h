@@ -243,6 +243,17 @@
  *             other than 0 or 1, --src_sdr_white without --src_sdr 1 or outside 80..1000, --src_sdr 1 without --linearize 1, beside
  *             --src_hlg 1 or --src_ictcp 1, beside any *_only flag, a source transfer that is given and is not 1, 6, 14 or 15, no
  *             destination transfer.
+ * --src_signal 1 (an addition), beside --linearize 1 --lut3d FILE.cube --lut3d_signal 1 only: the file's codes reach the table as the
+ *             non-linear R'G'B' signal they are (include/hdr2yuv_hip.h, "signal of code planes"): normalised, through the matrix,
+ *             clamped to [0, 1], and no transfer applied.  A trim built on PQ signal is so applied to the HDR10 .yuv it was built for;
+ *             the table decides what the codes mean, so PQ, HLG and SDR masters go the same way.  --src_transfer_characteristics and
+ *             --dst_transfer_characteristics are labels and are not checked (the latter is printed as lut3d_dst_transfer:).
+ *             Everything else --linearize 1 with a signal-mode LUT accepts and refuses stays so.  The banner carries src_signal: 1
+ *             and linearize_from: names "signal (no transfer applied)".  Refused (exit 1, also under --dry_run): a value other than
+ *             0 or 1, --src_signal 1 without --linearize 1, without --lut3d or with --lut3d_signal 0 (unscaled signal cannot reach a
+ *             passthrough conversion), beside --src_hlg 1, --src_sdr 1 or --src_ictcp 1, beside --tone_map 1 or --gamut_convert 1
+ *             (they act on light), beside any *_only flag.  Without the flag --linearize 1 --lut3d F --lut3d_signal 1 keeps feeding
+ *             the table linear light.
  * --delta_e 1 [--delta_e_threshold X] [--delta_e_limit Y] (an addition): Delta E ITP (Rec. ITU-R BT.2124; include/hdr2yuv_hip.h, "Delta E
  *             ITP of PQ code planes", states every step) of every compared frame against the reference's, beside the PSNR, wherever a
  *             comparison runs on PQ code frames of BT.2020 primaries: with --compare_only 1 on two .yuv files (--src_chroma_format_idc
@@ -396,6 +407,9 @@ struct cli_args {
      * src_sdr_white cd/m2 */
     int src_sdr = 0, src_sdr_white = H2Y_SDR_WHITE_DEFAULT;
     bool src_sdr_given = false, src_sdr_white_given = false;
+    /* --src_signal 1, beside --linearize 1 --lut3d FILE --lut3d_signal 1: the file's codes stay signal for the table, no transfer applied */
+    int src_signal = 0;
+    bool src_signal_given = false;
     /* --ictcp 1: the rung is PQ ICtCp (H.273 matrix_coeffs 14); resolved: ictcp_dst_transfer and ictcp_dst_matrix, what
      * --dst_transfer_characteristics and --dst_matrix_coeffs gave before the flag replaced them with the passthrough descriptor's 8 and
      * 0 (-1: not given).  --src_ictcp 1: the codes --linearize 1, --light_only 1 or --compare_only 1 --delta_e 1 read are PQ I, Ct, Cp */
@@ -502,6 +516,9 @@ static inline void cli_help()
            "  codes of the BT.1886 transfer, --src_transfer_characteristics 1, 6, 14, 15 or left out: gamma 2.4 and the reference white\n"
            "  at W cd/m2, 80..1000, 203 by default, on the GPU; BT.2408's display-referred mapping of SDR into a PQ or HLG container;\n"
            "  give --dst_transfer_characteristics or --hlg 1 / --ictcp 1, and --gamut_convert 1 for BT.709 primaries)\n"
+           "  a code master into a signal-domain LUT: [--linearize 1 --src_signal 1 --lut3d FILE.cube --lut3d_signal 1] (the .yuv / .rgb's\n"
+           "  codes reach the table as the R'G'B' signal they are, in [0, 1], with no transfer applied: a trim built on PQ signal applied\n"
+           "  to the HDR10 .yuv it was built for; the transfer flags are labels; not with --tone_map 1 or --gamut_convert 1)\n"
            "  primaries: [--gamut_convert 1 [--gamut_clip 0|1]] (float or half G,B,R source planes in linear light converted from\n"
            "  --src_colour_primaries to --dst_colour_primaries on the GPU before the conversion; 1 BT.709, 8 / 9 BT.2020, 12 P3-D65,\n"
            "  10 XYZ; what is not above 0 is clipped to 0 unless --gamut_clip 0)\n"
@@ -599,6 +616,7 @@ static inline void cli_parse(cli_args &a, int argc, char **argv)
         else if (is("--src_hlg_peak")) { a.src_hlg_peak = atoi(val()); a.src_hlg_peak_given = true; }
         else if (is("--src_sdr")) { a.src_sdr = atoi(val()); a.src_sdr_given = true; }
         else if (is("--src_sdr_white")) { a.src_sdr_white = atoi(val()); a.src_sdr_white_given = true; }
+        else if (is("--src_signal")) { a.src_signal = atoi(val()); a.src_signal_given = true; }
         else if (is("--hlg")) { a.hlg = atoi(val()); a.hlg_given = true; }
         else if (is("--ictcp")) { a.ictcp = atoi(val()); a.ictcp_given = true; }
         else if (is("--src_ictcp")) { a.src_ictcp = atoi(val()); a.src_ictcp_given = true; }
@@ -808,6 +826,7 @@ static inline int cli_resolve_scenes(cli_args &a);
 static inline int cli_resolve_linearize(cli_args &a);
 static inline int cli_resolve_src_hlg(cli_args &a);
 static inline int cli_resolve_src_sdr(cli_args &a);
+static inline int cli_resolve_src_signal(cli_args &a);
 static inline int cli_resolve_delta_e(cli_args &a);
 static inline int cli_resolve_dither(cli_args &a);
 static inline int cli_resolve_dither_only(cli_args &a);
@@ -934,6 +953,10 @@ static inline int cli_resolve_flows(cli_args &a)
         printf("src_sdr: %d\nWARNING: --src_sdr goes with --linearize 1: not with --dither_only 1\n", a.src_sdr);
         return 1;
     }
+    if (a.src_signal_given && a.dither_only == 1) {
+        printf("src_signal: %d\nWARNING: --src_signal goes with --linearize 1: not with --dither_only 1\n", a.src_signal);
+        return 1;
+    }
     if ((a.lut3d || a.lut3d_interp_given || a.lut3d_signal_given) && a.dither_only == 1) {
         printf("lut3d: %s\nWARNING: --lut3d applies to a conversion's source: not with --dither_only 1\n", a.lut3d ? a.lut3d : "(none)");
         return 1;
@@ -971,6 +994,7 @@ static inline int cli_resolve_all(cli_args &a)
     }
     if ((a.src_hlg_given || a.src_hlg_peak_given) && cli_resolve_src_hlg(a)) return 1; /* the transfer of --linearize 1's source */
     if ((a.src_sdr_given || a.src_sdr_white_given) && cli_resolve_src_sdr(a)) return 1; /* likewise: BT.1886 codes at a reference white */
+    if (a.src_signal_given && cli_resolve_src_signal(a)) return 1; /* likewise: no transfer at all, the codes stay signal for the LUT */
     if (a.src_ictcp_given && cli_resolve_src_ictcp(a)) return 1; /* the matrix of the codes the three flows below read */
     if (a.linearize == 1 && cli_resolve_linearize(a)) return 1;
     const bool lut3d_flags = a.lut3d || a.lut3d_interp_given || a.lut3d_signal_given;
@@ -1528,6 +1552,44 @@ static inline int cli_resolve_src_sdr(cli_args &a)
     return 0;
 }
 
+/* --src_signal: the codes --linearize 1 reads reach the signal-mode LUT as the signal they are (include/hdr2yuv_hip.h, "signal of code
+ * planes").  Runs before cli_resolve_linearize, which then skips its transfer check; prints the src_signal line; returns the number
+ * of argument errors */
+static inline int cli_resolve_src_signal(cli_args &a)
+{
+    printf("src_signal: %d\n", a.src_signal);
+    if (a.src_signal != 0 && a.src_signal != 1) {
+        printf("WARNING: src_signal(%d) not 0 or 1\n", a.src_signal);
+        return 1;
+    }
+    if (!a.src_signal) return 0;
+    int arg_errors = 0;
+    if (a.linearize != 1) {
+        printf("WARNING: --src_signal 1 is what becomes of the source --linearize 1 reads: it needs --linearize 1\n");
+        arg_errors++;
+    }
+    if (!a.lut3d || a.lut3d_signal != 1) {
+        printf("WARNING: --src_signal 1 needs --lut3d FILE.cube --lut3d_signal 1: unscaled signal cannot reach a passthrough conversion, the "
+               "table's scale step must stand between them\n");
+        arg_errors++;
+    }
+    if (a.src_hlg == 1 || a.src_sdr == 1 || a.src_ictcp == 1) {
+        printf("WARNING: --src_signal 1 applies no transfer and reads R'G'B' signal: not with --%s 1\n",
+               a.src_hlg == 1 ? "src_hlg" : a.src_sdr == 1 ? "src_sdr" : "src_ictcp");
+        arg_errors++;
+    }
+    if (a.tone_map == 1 || a.gamut == 1) {
+        printf("WARNING: --src_signal 1: the planes hold signal, and --%s 1 acts on light: not together\n", a.tone_map == 1 ? "tone_map" : "gamut_convert");
+        arg_errors++;
+    }
+    if (a.light_only || a.compare_only || a.hist_only || a.scale_only) {
+        printf("WARNING: --src_signal 1 is the source of a conversion: not with --%s 1\n",
+               a.light_only ? "light_only" : a.compare_only ? "compare_only" : a.hist_only ? "histogram_only" : "scale_only");
+        arg_errors++;
+    }
+    return arg_errors;
+}
+
 /* --linearize 1: a PQ .yuv or .rgb as the forward flow's source.  Checks the file's attributes as --light_only checks them, gives the
  * destination what it leaves unset from the source as parsed (hdr2yuv.cpp:265-318), keeps the file's attributes in a.lin and
  * rewrites a.in to the planes the ring decodes -- F32, LINEAR, G,B,R, 4:4:4 -- so that every resolver after this one sees a .f32
@@ -1560,7 +1622,7 @@ static inline int cli_resolve_linearize(cli_args &a)
         printf("WARNING: video_full_range_flag(%d) not 0 or 1\n", a.in.video_full_range_flag);
         arg_errors++;
     }
-    if (a.src_hlg != 1 && a.src_sdr != 1 && a.in.transfer_characteristics != 16) { /* (--src_hlg 1 and --src_sdr 1 are the source's transfer: their resolvers) */
+    if (a.src_hlg != 1 && a.src_sdr != 1 && a.src_signal != 1 && a.in.transfer_characteristics != 16) { /* (--src_hlg 1 and --src_sdr 1 are the source's transfer: their resolvers; --src_signal 1 applies none) */
         printf("WARNING: --linearize 1 linearises PQ codes: src_transfer_characteristics(%d) is not 16\n", a.in.transfer_characteristics);
         arg_errors++;
     }
@@ -1605,8 +1667,8 @@ static inline int cli_resolve_linearize(cli_args &a)
     }
     if (arg_errors) return arg_errors;
     static const char *const kMatrix[15] = {"G,B,R", "BT.709", "", "", "", "", "", "", "", "BT.2020nc", "", "", "", "", "ICtCp"};
-    printf("linearize_from: %s codes, bit_depth %d %s range, matrix_coeffs %d (%s), chroma_format_idc %d, upsampler %s\n",
-           a.src_hlg == 1 ? "HLG" : a.src_sdr == 1 ? "SDR (BT.1886)" : "PQ", a.in.bit_depth,
+    printf("linearize_from: %s, bit_depth %d %s range, matrix_coeffs %d (%s), chroma_format_idc %d, upsampler %s\n",
+           a.src_hlg == 1 ? "HLG codes" : a.src_sdr == 1 ? "SDR (BT.1886) codes" : a.src_signal == 1 ? "signal (no transfer applied)" : "PQ codes", a.in.bit_depth,
            a.in.video_full_range_flag ? "full" : "video", m, kMatrix[m], chroma,
            chroma == H2Y_CHROMA_444 ? "none" : !a.resampler ? "replicate" : a.src_siting == 2 ? "fir_top_left" : "fir");
     /* hdr2yuv.cpp:265-318: unset destination attributes <- the source's, as parsed */

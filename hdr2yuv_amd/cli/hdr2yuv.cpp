@@ -172,7 +172,9 @@
  * are HLG's and the ring is h2y_hlgcode_stream_open's at that display peak; nothing else differs.  The banner then carries src_hlg:,
  * src_hlg_peak:, src_hlg_gamma: and src_hlg_note: too.  With --src_sdr 1 [--src_sdr_white W] beside it the codes are an SDR
  * master's (BT.1886) and the ring is h2y_sdrcode_stream_open's with the reference white at W cd/m2; the banner then carries src_sdr:,
- * src_sdr_white: and src_sdr_gamma:.
+ * src_sdr_white: and src_sdr_gamma:.  With --src_signal 1 --lut3d FILE.cube --lut3d_signal 1 beside it no transfer is applied: the ring
+ * is h2y_sigcode_stream_open's, whose decode leaves the codes' R'G'B' signal for the table it arms in the same call; the banner then
+ * carries src_signal: and linearize_from: names the signal.
  *
  * Packings (--dst_pack / --src_pack planar8|nv12|p010; h2y_cli_args.h): each GPU thread arms its ring last with h2y_stream_pack, so the
  * frame that comes down is the .yuv frame packed on the device, written at `size of the file at start + k x h2y_pack_frame_bytes`; and
@@ -443,6 +445,8 @@ static flow forward_flow(const job &j)
                                           a.lin.matrix_coeffs, a.resampler};
             if (a.src_hlg == 1) return opened(h2y_hlgcode_stream_open(ctx, &j.d, &code, a.src_hlg_peak, kRingDepth), a, ctx); /* the file's codes are HLG's */
             if (a.src_sdr == 1) return opened(h2y_sdrcode_stream_open(ctx, &j.d, &code, a.src_sdr_white, kRingDepth), a, ctx); /* the file's codes are BT.1886's */
+            if (a.src_signal == 1) /* the codes stay signal for the LUT, which this ring arms as it opens */
+                return opened(h2y_sigcode_stream_open(ctx, &j.d, &code, a.lut3d_table, a.lut3d_interp, kRingDepth), a, ctx);
             return opened(h2y_pqcode_stream_open(ctx, &j.d, &code, kRingDepth), a, ctx);
         }
         return a.in_type == CLI_IN_DPX    ? h2y_dpx_stream_open(ctx, &j.d, &s.di, kRingDepth)
@@ -459,7 +463,7 @@ static flow forward_flow(const job &j)
                (a.gamut && a.gamut_compress && h2y_stream_gamut_compress(ctx, a.in.colour_primaries, a.out.colour_primaries,
                                                                          a.gamut_compress_threshold, a.gamut_compress_power)) ||
                (a.tone_map && h2y_stream_tonemap(ctx, a.tone_src_peak, a.tone_dst_peak, a.tone_relative)) ||
-               (a.lut3d_table && h2y_stream_lut3d(ctx, a.lut3d_table, a.lut3d_interp, a.lut3d_signal)) ||
+               (a.lut3d_table && a.src_signal != 1 && h2y_stream_lut3d(ctx, a.lut3d_table, a.lut3d_interp, a.lut3d_signal)) ||
                (a.hlg == 1 && h2y_stream_hlg(ctx, a.hlg_peak, a.hlg_relative)) || (a.ictcp == 1 && h2y_stream_ictcp(ctx)) ||
                (a.scale && h2y_stream_scale(ctx, a.out.width, a.out.height, a.scale_taps)) ||
                (a.dithers() && h2y_stream_dither(ctx, a.dither_to, a.dither, a.dither_temporal, a.dither_seed, (uint32_t)first)) || /* after scale */

@@ -1287,15 +1287,16 @@ int decode_src::planes_check(h2y_ctx *ctx, const h2y_desc *d) const
         if (d->in_sample_type != H2Y_SAMPLE_F16) return fail(ctx, H2Y_EINVAL, "an EXR stream decodes to half planes: in_sample_type must be H2Y_SAMPLE_F16");
         what = "EXR data window", w = exr.width, h = exr.height;
         break;
-    case PQCODE: /* the linearised planes: F32 LINEAR G,B,R in [+0, 1], floor 0 and ceiling 1 whatever the frame holds */
+    case PQCODE: /* the linearised planes: F32 LINEAR G,B,R in [+0, 1], floor 0 and ceiling 1 whatever the frame holds (signal: G', B', R' for
+                    the ring's signal-mode LUT, under the same descriptor) */
         if (d->in_sample_type != H2Y_SAMPLE_F32 || d->src_transfer != 8 || d->src_matrix != H2Y_MATRIX_GBR)
             return fail(ctx, H2Y_EINVAL, "%s code stream linearises to F32 G,B,R planes: in_sample_type H2Y_SAMPLE_F32, src_transfer 8, src_matrix 0",
-                        hlg ? "an HLG" : sdr ? "an SDR" : "a PQ");
-        if (d->stats_override != 1) return fail(ctx, H2Y_EINVAL, "%s code stream needs stats_override 1 with floor 0 and ceiling 1", hlg ? "an HLG" : sdr ? "an SDR" : "a PQ");
+                        hlg ? "an HLG" : sdr ? "an SDR" : signal ? "a signal" : "a PQ");
+        if (d->stats_override != 1) return fail(ctx, H2Y_EINVAL, "%s code stream needs stats_override 1 with floor 0 and ceiling 1", hlg ? "an HLG" : sdr ? "an SDR" : signal ? "a signal" : "a PQ");
         for (int c = 0; c < 3; c++)
             if (d->floor[c] != 0 || d->ceiling[c] != 1)
-                return fail(ctx, H2Y_EINVAL, "%s code stream needs stats_override 1 with floor 0 and ceiling 1", hlg ? "an HLG" : sdr ? "an SDR" : "a PQ");
-        what = hlg ? "HLG code frame" : sdr ? "SDR code frame" : "PQ code frame", w = code.width, h = code.height;
+                return fail(ctx, H2Y_EINVAL, "%s code stream needs stats_override 1 with floor 0 and ceiling 1", hlg ? "an HLG" : sdr ? "an SDR" : signal ? "a signal" : "a PQ");
+        what = hlg ? "HLG code frame" : sdr ? "SDR code frame" : signal ? "signal code frame" : "PQ code frame", w = code.width, h = code.height;
         break;
     default: return H2Y_OK;
     }

@@ -1,7 +1,7 @@
 /*
  * h2y_codepixel.h -- what the kernels that read PQ code planes share (k_codelight in h2y_codelight.hip, k_linearize in
  * h2y_linearize.hip): eight codes of a plane, and one pixel's three lights L_G, L_B, L_R as include/hdr2yuv_hip.h defines them
- * ("light of PQ code planes", steps 2-4; matrix 14: "light of ICtCp code planes"); k_hlg_linearize (h2y_hlgsrc.hip) takes steps 2-3, code_primes; k_sdr_linearize (h2y_sdrsrc.hip) the lights of SDR codes, code_sdr_lights.  Device code only; include after h2y_device.h and h2y_light1.h, in a file built
+ * ("light of PQ code planes", steps 2-4; matrix 14: "light of ICtCp code planes"); k_hlg_linearize (h2y_hlgsrc.hip) takes steps 2-3, code_primes; k_sdr_linearize (h2y_sdrsrc.hip) the lights of SDR codes, code_sdr_lights; k_code_signal (h2y_sigsrc.hip) and its host twin stop at code_primes and clamp01, which therefore compile for the host too.  Otherwise device code only; include after h2y_device.h and h2y_light1.h, in a file built
  * -ffp-contract=off: every product and sum of the matrix is rounded by itself.
  */
 #pragma once
@@ -35,12 +35,12 @@ __device__ __forceinline__ void load8(const uint16_t *p, bool vec, uint32_t q, u
     }
 }
 
-__device__ __forceinline__ float clamp01(float v) { return v > 0.0f ? fminf(v, 1.0f) : 0.0f; }
+__host__ __device__ __forceinline__ float clamp01(float v) { return v > 0.0f ? fminf(v, 1.0f) : 0.0f; }
 
 /* one pixel's codes -> its primes G', B', R' before the clamp: normalise, matrix (steps 2-3; k_hlg_linearize in h2y_hlgsrc.hip
  * goes on from here with its own transfer) */
 template <int MATRIX>
-__device__ __forceinline__ void code_primes(const codelight_args &a, uint32_t c0, uint32_t c1, uint32_t c2, float &g, float &b, float &r)
+__host__ __device__ __forceinline__ void code_primes(const codelight_args &a, uint32_t c0, uint32_t c1, uint32_t c2, float &g, float &b, float &r)
 {
     typedef ycc_coef<MATRIX> K;
     const float y = ((float)c0 - a.sub[0]) / a.div[0];

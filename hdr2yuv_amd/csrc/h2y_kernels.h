@@ -559,6 +559,14 @@ struct sdrsrc_args {
 int h2y_sdr_linearize_grid(uint32_t npix, int n_frames); /* blocks per frame */
 hipError_t h2y_launch_sdr_linearize(int matrix, int grid, hipStream_t st, const sdrsrc_args &a, const linearize_frame *frames, int n_frames);
 
+/* k_code_signal (h2y_sigsrc.hip): the signal G', B', R' in [+0, 1] of frames of three u16 code planes as binary32 planes, no transfer
+ * applied (include/hdr2yuv_hip.h, "signal of code planes"); k_linearize's frame table; of a it reads npix, n8, vec, sub and div
+ * (table and pp are not read) */
+int h2y_code_signal_grid(uint32_t npix, int n_frames); /* blocks per frame */
+hipError_t h2y_launch_code_signal(int matrix, int grid, hipStream_t st, const codelight_args &a, const linearize_frame *frames, int n_frames);
+/* the same arithmetic on 4:4:4 planes in host memory (h2y_code_signal_planes); false for a matrix other than 0, 1 or 9 */
+bool h2y_code_signal_host(int matrix, const codelight_args &a, size_t npix, const uint16_t *const src[3], float *const dst[3]);
+
 /* k_scale (h2y_scale.hip): the Lanczos resampler of include/hdr2yuv_hip.h on frames of three u16 planes.  One axis' table on the
  * device: first[d] and count[d] (int32), then d rows of H2Y_SCALE_MAX_TAPS int16 coefficients (zero past count). */
 enum { H2Y_SCALE_MAX_TAPS = 32, H2Y_SCALE_TILE_W = 64, H2Y_SCALE_TILE_H = 32, H2Y_SCALE_STAGE_ROWS = 16 };

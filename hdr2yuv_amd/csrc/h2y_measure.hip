@@ -747,7 +747,8 @@ size_t h2y_lightdist_json(const h2y_lightdist_stats *stats, int n_frames, long f
 
 /* ---- light of PQ code planes (h2y_codelight_batch, h2y_codelight_stream_open): include/hdr2yuv_hip.h states the definition ------ */
 
-int codelight_check(h2y_ctx *ctx, const h2y_codelight_desc *d, codelight_plan &p)
+/* what codelight_check refuses of the descriptor alone, without a context: the host twin of k_code_signal refuses the same */
+static int codelight_desc_check(h2y_ctx *ctx, const h2y_codelight_desc *d)
 {
     if (!d) return fail(ctx, H2Y_EINVAL, "null h2y_codelight_desc");
     if (d->chroma_format_idc == 2) return fail(ctx, H2Y_EUNSUPPORTED, "chroma_format_idc 2 (4:2:2) has no light on this path");
@@ -760,23 +761,36 @@ int codelight_check(h2y_ctx *ctx, const h2y_codelight_desc *d, codelight_plan &p
     if (rc) return rc;
     if (d->bit_depth < 8 || d->bit_depth > 16) return fail(ctx, H2Y_EINVAL, "bit_depth must be 8..16");
     if (d->full_range != 0 && d->full_range != 1) return fail(ctx, H2Y_EINVAL, "full_range must be 0 or 1");
-    p.sub = d->chroma_format_idc == H2Y_CHROMA_420;
-    if (p.sub) {
+    if (d->chroma_format_idc == H2Y_CHROMA_420) {
         if (d->matrix_coeffs == H2Y_MATRIX_GBR) return fail(ctx, H2Y_EINVAL, "G,B,R planes (matrix_coeffs 0) are 4:4:4");
         if ((d->width & 1) || (d->height & 1) || d->width > 32766 || d->height > 32766)
             return fail(ctx, H2Y_EINVAL, "4:2:0: width and height must be even, up to 32766");
     }
+    return H2Y_OK;
+}
+
+/* step 2's constants: what a code of plane 0 (G, B, R planes: of every plane) and of planes 1 and 2 is taken from and divided by */
+static void codelight_norm(const h2y_codelight_desc *d, codelight_args &a)
+{
+    const float s = (float)(1u << (d->bit_depth - 8)), top = (float)((1u << d->bit_depth) - 1u);
+    a.sub[0] = d->full_range ? 0.0f : 16.0f * s;
+    a.div[0] = d->full_range ? top : 219.0f * s;
+    a.sub[1] = d->full_range ? (float)(1u << (d->bit_depth - 1)) : 128.0f * s;
+    a.div[1] = d->full_range ? top : 224.0f * s;
+}
+
+int codelight_check(h2y_ctx *ctx, const h2y_codelight_desc *d, codelight_plan &p)
+{
+    int rc = codelight_desc_check(ctx, d);
+    if (rc) return rc;
+    p.sub = d->chroma_format_idc == H2Y_CHROMA_420;
     rc = inverse_form(ctx, d->chroma_format_idc, d->algorithm, &p.form); /* siting 2 with replication: the inverse entries' refusal */
     if (rc) return rc;
     p.matrix = d->matrix_coeffs;
     codelight_args &a = p.a;
     a.npix = (uint32_t)d->width * (uint32_t)d->height;
     a.n8 = a.npix / 8u;
-    const float s = (float)(1u << (d->bit_depth - 8)), top = (float)((1u << d->bit_depth) - 1u);
-    a.sub[0] = d->full_range ? 0.0f : 16.0f * s;
-    a.div[0] = d->full_range ? top : 219.0f * s;
-    a.sub[1] = d->full_range ? (float)(1u << (d->bit_depth - 1)) : 128.0f * s;
-    a.div[1] = d->full_range ? top : 224.0f * s;
+    codelight_norm(d, a);
     contiguous_planes(d->width, d->height, d->chroma_format_idc, p.off);
     p.width = d->width, p.height = d->height, p.bit_depth = d->bit_depth;
     p.samples = p.off[2] + (p.off[2] - p.off[1]); /* the last plane is as long as the second */
@@ -1430,7 +1444,7 @@ int h2y_stream_deltae_result(h2y_ctx *ctx, h2y_deltae_stats *out)
 
 static const char *linearize_kernel(code_tf tf)
 {
-    return tf.kind == code_tf::HLG ? "k_hlg_linearize" : tf.kind == code_tf::SDR ? "k_sdr_linearize" : "k_linearize";
+    return tf.kind == code_tf::HLG ? "k_hlg_linearize" : tf.kind == code_tf::SDR ? "k_sdr_linearize" : tf.kind == code_tf::SIGNAL ? "k_code_signal" : "k_linearize";
 }
 
 static std::string linearize_variant(const codelight_plan &p, code_tf tf)
@@ -1446,8 +1460,8 @@ static linearize_frame linearize_entry(const codelight_plan &p, const uint16_t *
     return linearize_frame{{c.p[0], c.p[1], c.p[2]}, {static_cast<float *>(out[0]), static_cast<float *>(out[1]), static_cast<float *>(out[2])}};
 }
 
-/* the three batch entries: the codes are PQ's (k_linearize), HLG's at a display peak (k_hlg_linearize) or SDR's at a reference
- * white (k_sdr_linearize) */
+/* the four batch entries: the codes are PQ's (k_linearize), HLG's at a display peak (k_hlg_linearize), SDR's at a reference
+ * white (k_sdr_linearize), or stay signal whatever they are (k_code_signal) */
 static int linearize_frames(h2y_ctx *ctx, const h2y_codelight_desc *d, code_tf tf, int n_frames, const uint16_t *const *d_frames,
                             void *const *d_planes_out)
 {
@@ -1468,7 +1482,8 @@ static int linearize_frames(h2y_ctx *ctx, const h2y_codelight_desc *d, code_tf t
     linearize_frame *h;
     hlgsrc_args ha{};
     sdrsrc_args sa{};
-    rc = tf.kind == code_tf::HLG ? hlgsrc_args_of(ctx, p, tf.param, ha) : tf.kind == code_tf::SDR ? sdrsrc_tables(ctx, p, tf.param, sa.kappa) : codelight_tables(ctx, p);
+    rc = tf.kind == code_tf::HLG ? hlgsrc_args_of(ctx, p, tf.param, ha) : tf.kind == code_tf::SDR ? sdrsrc_tables(ctx, p, tf.param, sa.kappa) :
+         tf.kind == code_tf::SIGNAL ? sigsrc_check(ctx, p) : codelight_tables(ctx, p);
     sa.c = p.a;
     if (!rc) rc = frame_table(ctx, n_frames, h);
     if (!rc && p.sub) rc = ensure(ctx, ctx->codelight_up, (size_t)per_launch * 2u * p.plane_al);
@@ -1484,6 +1499,7 @@ static int linearize_frames(h2y_ctx *ctx, const h2y_codelight_desc *d, code_tf t
         }
         if (tf.kind == code_tf::HLG) return h2y_launch_hlg_linearize(p.matrix, h2y_hlg_linearize_grid(ctx->n_cu, p.a.npix, nf), ctx->stream, ha, frames, nf);
         if (tf.kind == code_tf::SDR) return h2y_launch_sdr_linearize(p.matrix, h2y_sdr_linearize_grid(p.a.npix, nf), ctx->stream, sa, frames, nf);
+        if (tf.kind == code_tf::SIGNAL) return h2y_launch_code_signal(p.matrix, h2y_code_signal_grid(p.a.npix, nf), ctx->stream, p.a, frames, nf);
         return h2y_launch_linearize(p.matrix, h2y_linearize_grid(p.a.npix, nf), ctx->stream, p.a, frames, nf);
     });
     if (rc) return rc;
@@ -1508,6 +1524,11 @@ int h2y_sdr_linearize_batch(h2y_ctx *ctx, const h2y_codelight_desc *d, int white
     return linearize_frames(ctx, d, code_tf{code_tf::SDR, white}, n_frames, d_frames, d_planes_out);
 }
 
+int h2y_code_signal_batch(h2y_ctx *ctx, const h2y_codelight_desc *d, int n_frames, const uint16_t *const *d_frames, void *const *d_planes_out)
+{
+    return linearize_frames(ctx, d, code_tf{code_tf::SIGNAL, 0}, n_frames, d_frames, d_planes_out);
+}
+
 /* The forward ring's PQCODE decode.  One scratch of the context serves every slot: the frames follow one another on its stream. */
 int pqcode_scratch(h2y_ctx *ctx, const codelight_plan &p)
 {
@@ -1528,6 +1549,7 @@ int pqcode_decode(h2y_ctx *ctx, int slot)
     const linearize_frame *fr = static_cast<const linearize_frame *>(ctx->s_tab) + slot;
     if (ctx->s_src.hlg) HIP_TRY(ctx, h2y_launch_hlg_linearize(p.matrix, h2y_hlg_linearize_grid(ctx->n_cu, p.a.npix, 1), ctx->stream, ctx->s_src.hlgsrc, fr, 1));
     else if (ctx->s_src.sdr) HIP_TRY(ctx, h2y_launch_sdr_linearize(p.matrix, h2y_sdr_linearize_grid(p.a.npix, 1), ctx->stream, sdrsrc_args{p.a, ctx->s_src.sdr_kappa}, fr, 1));
+    else if (ctx->s_src.signal) HIP_TRY(ctx, h2y_launch_code_signal(p.matrix, h2y_code_signal_grid(p.a.npix, 1), ctx->stream, p.a, fr, 1));
     else HIP_TRY(ctx, h2y_launch_linearize(p.matrix, h2y_linearize_grid(p.a.npix, 1), ctx->stream, p.a, fr, 1));
     return H2Y_OK;
 }
@@ -2173,6 +2195,7 @@ int h2y_stream_gamut(h2y_ctx *ctx, int src_primaries, int dst_primaries, int cli
     int rc = arm_enter(ctx);
     if (rc) return rc;
     if (ctx->s_kind != h2y_ctx::RING_FORWARD) return fail(ctx, H2Y_EINVAL, "primaries are converted on the forward rings only");
+    if (ring_holds_signal(ctx)) return fail(ctx, H2Y_EINVAL, "the ring's planes hold signal, not light: primaries are converted in linear light");
     rc = arm_free(ctx, STAGE_GAMUT, "the ring converts primaries already");
     if (rc) return rc;
     const h2y_desc *d = &ctx->s_desc;
@@ -2322,6 +2345,7 @@ int h2y_stream_gamut_compress(h2y_ctx *ctx, int src_primaries, int dst_primaries
     int rc = arm_enter(ctx);
     if (rc) return rc;
     if (ctx->s_kind != h2y_ctx::RING_FORWARD) return fail(ctx, H2Y_EINVAL, "primaries are converted on the forward rings only");
+    if (ring_holds_signal(ctx)) return fail(ctx, H2Y_EINVAL, "the ring's planes hold signal, not light: primaries are converted in linear light");
     rc = arm_free(ctx, STAGE_GAMUT, "the ring converts primaries already");
     if (rc) return rc;
     const h2y_desc *d = &ctx->s_desc;
@@ -2441,6 +2465,7 @@ int h2y_stream_tonemap(h2y_ctx *ctx, int src_peak, int dst_peak, int relative)
     int rc = arm_enter(ctx);
     if (rc) return rc;
     if (ctx->s_kind != h2y_ctx::RING_FORWARD) return fail(ctx, H2Y_EINVAL, "tone mapping works on the forward rings only");
+    if (ring_holds_signal(ctx)) return fail(ctx, H2Y_EINVAL, "the ring's planes hold signal, not light: tone mapping works in linear light");
     rc = arm_free(ctx, STAGE_TONEMAP, "the ring maps tones already");
     if (rc) return rc;
     const h2y_desc *d = &ctx->s_desc;
@@ -3130,6 +3155,30 @@ int sdrsrc_tables(h2y_ctx *ctx, codelight_plan &p, int white, float &kappa)
     pp.tf_ext[0] = ctx->d_tfn_ext[H2Y_TFN_G24];
     p.a.table = ctx->d_tfn[H2Y_TFN_G24];
     kappa = (float)(white / 10000.0);
+    return H2Y_OK;
+}
+
+/* ---- signal of code planes (--linearize 1 --src_signal 1): include/hdr2yuv_hip.h states the definition ------------------------------- */
+
+static const char *const kSignalIctcp = "matrix_coeffs 14 (ICtCp) gives L'M'S', not R'G'B': the signal of code planes is G,B,R (0), BT.709 (1) or BT.2020nc (9)";
+
+int sigsrc_check(h2y_ctx *ctx, const codelight_plan &p)
+{
+    if (p.matrix == H2Y_MATRIX_ICTCP) return fail(ctx, H2Y_EUNSUPPORTED, "%s", kSignalIctcp);
+    return H2Y_OK;
+}
+
+bool ring_holds_signal(const h2y_ctx *ctx) { return ctx->s_kind == h2y_ctx::RING_FORWARD && ctx->s_src.kind == decode_src::PQCODE && ctx->s_src.signal; }
+
+int h2y_code_signal_planes(const h2y_codelight_desc *d, size_t npix, const uint16_t *const src[3], float *const dst[3])
+{
+    int rc = codelight_desc_check(nullptr, d);
+    if (rc) return rc;
+    if (d->matrix_coeffs == H2Y_MATRIX_ICTCP) return fail(nullptr, H2Y_EUNSUPPORTED, "%s", kSignalIctcp);
+    if (!src || !dst || !src[0] || !src[1] || !src[2] || !dst[0] || !dst[1] || !dst[2]) return fail(nullptr, H2Y_EINVAL, "null planes");
+    codelight_args a{};
+    codelight_norm(d, a);
+    h2y_code_signal_host(d->matrix_coeffs, a, npix, src, dst);
     return H2Y_OK;
 }
 

@@ -268,7 +268,7 @@ int h2y_exr_stream_open(h2y_ctx *ctx, const h2y_desc *d, const h2y_exr_info *inf
     return open_forward_ring(ctx, d, &src, depth);
 }
 
-/* the three code rings: the codes are PQ's, HLG's at a display peak or SDR's at a reference white */
+/* the four code rings: the codes are PQ's, HLG's at a display peak, SDR's at a reference white, or stay signal (no transfer) */
 static int open_code_ring(h2y_ctx *ctx, const h2y_desc *d, const h2y_codelight_desc *code, code_tf tf, int depth)
 {
     int rc = ring_may_open(ctx);
@@ -280,10 +280,12 @@ static int open_code_ring(h2y_ctx *ctx, const h2y_desc *d, const h2y_codelight_d
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hlgsrc_args ha{};
     float kappa = 0.0f;
-    rc = tf.kind == code_tf::HLG ? hlgsrc_args_of(ctx, p, tf.param, ha) : tf.kind == code_tf::SDR ? sdrsrc_tables(ctx, p, tf.param, kappa) : codelight_tables(ctx, p);
+    rc = tf.kind == code_tf::HLG ? hlgsrc_args_of(ctx, p, tf.param, ha) : tf.kind == code_tf::SDR ? sdrsrc_tables(ctx, p, tf.param, kappa) :
+         tf.kind == code_tf::SIGNAL ? sigsrc_check(ctx, p) : codelight_tables(ctx, p);
     if (!rc) rc = pqcode_scratch(ctx, p);
     if (rc) return rc;
-    const decode_src src = tf.kind == code_tf::HLG ? decode_src(p, ha) : tf.kind == code_tf::SDR ? decode_src(p, kappa) : decode_src(p);
+    const decode_src src = tf.kind == code_tf::HLG ? decode_src(p, ha) : tf.kind == code_tf::SDR ? decode_src(p, kappa) :
+                           tf.kind == code_tf::SIGNAL ? decode_src(p, decode_src::signal_tag{}) : decode_src(p);
     return open_forward_ring(ctx, d, &src, depth);
 }
 
@@ -300,6 +302,18 @@ int h2y_hlgcode_stream_open(h2y_ctx *ctx, const h2y_desc *d, const h2y_codelight
 int h2y_sdrcode_stream_open(h2y_ctx *ctx, const h2y_desc *d, const h2y_codelight_desc *code, int white, int depth)
 {
     return open_code_ring(ctx, d, code, code_tf{code_tf::SDR, white}, depth);
+}
+
+/* The code ring whose planes stay signal, and the signal-mode LUT that reads them, in one call: without the LUT's scale step the
+ * passthrough conversion would scale nothing, so the ring never exists unarmed.  What h2y_pqcode_stream_open refuses of d and code
+ * it refuses, then what h2y_stream_lut3d(signal 1) refuses of d and the table; the ring is closed again if the arming fails. */
+int h2y_sigcode_stream_open(h2y_ctx *ctx, const h2y_desc *d, const h2y_codelight_desc *code, const h2y_lut3d *lut, int interp, int depth)
+{
+    int rc = open_code_ring(ctx, d, code, code_tf{code_tf::SIGNAL, 0}, depth);
+    if (rc) return rc;
+    rc = h2y_stream_lut3d(ctx, lut, interp, 1);
+    if (rc) stream_free(ctx); /* nothing has run on it; the context keeps the arming's message */
+    return rc;
 }
 
 /* ---- the ring's frame by frame entries ------------------------------------------------------------------------------------------ */

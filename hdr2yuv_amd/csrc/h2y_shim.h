@@ -90,7 +90,9 @@ struct codelight_plan {
  * described by the info its parser returned.  Each format's launch and variant lie beside its parser.  PQCODE (h2y_pqcode_stream_open):
  * the payload is a PQ code frame, the decode its linearisation (pqcode_decode, h2y_measure.hip) by the plan checked at the opening.
  * The same kind with hlg set (h2y_hlgcode_stream_open): the codes are HLG's, the decode k_hlg_linearize at hlg.kappa's peak; with sdr
- * set (h2y_sdrcode_stream_open): the codes are BT.1886's, the decode k_sdr_linearize at sdr_kappa's reference white. */
+ * set (h2y_sdrcode_stream_open): the codes are BT.1886's, the decode k_sdr_linearize at sdr_kappa's reference white; with signal set
+ * (h2y_sigcode_stream_open): no transfer is applied, the decode is k_code_signal and the planes hold G', B', R' for the signal-mode
+ * LUT that opener arms. */
 struct decode_src {
     enum kind_t { NONE, DPX, TIFF, EXR, PQCODE } kind = NONE;
     bool has_info = true; /* false: the caller passed a null info, which check() refuses */
@@ -103,10 +105,13 @@ struct decode_src {
     hlgsrc_args hlgsrc{};
     bool sdr = false;     /* PQCODE: the frame holds SDR (BT.1886) codes; code.a carries that stage's tables (sdrsrc_tables), sdr_kappa W / 10000 */
     float sdr_kappa = 0.0f;
+    bool signal = false;  /* PQCODE: the planes are the codes' signal, no transfer applied (k_code_signal; code.a's table and pp stay unset) */
+    struct signal_tag {};
     decode_src() = default;
     explicit decode_src(const codelight_plan &p) : kind(PQCODE), code(p) {}
     decode_src(const codelight_plan &p, const hlgsrc_args &h) : kind(PQCODE), code(p), hlg(true), hlgsrc(h) {}
     decode_src(const codelight_plan &p, float kappa) : kind(PQCODE), code(p), sdr(true), sdr_kappa(kappa) {}
+    decode_src(const codelight_plan &p, signal_tag) : kind(PQCODE), code(p), signal(true) {}
     explicit decode_src(const h2y_dpx_info *i) : kind(DPX), has_info(i != nullptr) { if (i) dpx = *i; }
     decode_src(const h2y_tiff_info *i, int clamp_video_range) : kind(TIFF), has_info(i != nullptr), clamp(clamp_video_range) { if (i) tiff = *i; }
     explicit decode_src(const h2y_exr_info *i) : kind(EXR), has_info(i != nullptr) { if (i) exr = *i; }
@@ -509,14 +514,17 @@ int codelight_check(h2y_ctx *ctx, const h2y_codelight_desc *d, codelight_plan &p
 int codelight_tables(h2y_ctx *ctx, codelight_plan &p);
 int pqcode_scratch(h2y_ctx *ctx, const codelight_plan &p);                    /* the context's scratch for one frame's upsampled chroma */
 linearize_frame pqcode_entry(const h2y_ctx *ctx, const codelight_plan &p, const char *payload, char *const planes[3]);
-int pqcode_decode(h2y_ctx *ctx, int slot);                                    /* k_up444 (4:2:0) and k_linearize (k_hlg_linearize, k_sdr_linearize) on the slot's payload */
+int pqcode_decode(h2y_ctx *ctx, int slot);                                    /* k_up444 (4:2:0) and k_linearize (k_hlg_linearize, k_sdr_linearize, k_code_signal) on the slot's payload */
 int hlgsrc_args_of(h2y_ctx *ctx, const codelight_plan &p, int peak, hlgsrc_args &a); /* the peak's tables into the context's, k_hlg_linearize's arguments */
 int sdrsrc_tables(h2y_ctx *ctx, codelight_plan &p, int white, float &kappa); /* bt1886_f's tables into the plan, as codelight_tables puts PQ10000_f's; kappa of the white */
+int sigsrc_check(h2y_ctx *ctx, const codelight_plan &p);                     /* the signal of code planes needs no tables: its one refusal, matrix_coeffs 14 */
+bool ring_holds_signal(const h2y_ctx *ctx);                                  /* the open ring is h2y_sigcode_stream_open's: its planes hold signal, not light */
 
 /* what the codes of a code-plane source are (linearize_frames in h2y_measure.hip, open_code_ring in h2y_ring.hip): PQ's, HLG's at a
- * display peak of param cd/m2, or SDR (BT.1886) with its reference white at param cd/m2 */
+ * display peak of param cd/m2, SDR (BT.1886) with its reference white at param cd/m2, or SIGNAL: whatever they are, they stay signal
+ * (no transfer applied, no param) */
 struct code_tf {
-    enum kind_t { PQ, HLG, SDR } kind = PQ;
+    enum kind_t { PQ, HLG, SDR, SIGNAL } kind = PQ;
     int param = 0;
 };
 

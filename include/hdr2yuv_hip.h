@@ -1704,6 +1704,50 @@ int h2y_sdr_linearize_batch(h2y_ctx *ctx, const h2y_codelight_desc *d, int white
  * h2y_pqcode_stream_open, H2Y_EINVAL for a white outside 80..1000 and H2Y_EUNSUPPORTED for matrix_coeffs 14. */
 int h2y_sdrcode_stream_open(h2y_ctx *ctx, const h2y_desc *d, const h2y_codelight_desc *src, int white, int depth);
 
+/* ---- signal of code planes: a finished master's codes as the R'G'B' signal a signal-domain 3D LUT reads (--linearize 1
+ * --src_signal 1 --lut3d FILE.cube --lut3d_signal 1) ---------------------------------------------------------------------------------
+ * A colourist's HDR -> SDR trim or a show look is a .cube whose input is non-linear R'G'B' signal in [0, 1].  This decode hands a
+ * code master to such a table as what it is: no transfer is applied, so one decode serves PQ, HLG and SDR masters alike, and the
+ * table decides what the codes mean.  Nothing in the arithmetic is new: it is "light of PQ code planes" above with its last step
+ * taken out.
+ * Frame: exactly what h2y_codelight_desc describes: three u16 code planes at bit_depth 8..16, video or full range; matrix_coeffs 0,
+ *   1 or 9; chroma_format_idc 3, or 1 with even sizes (not with matrix 0).  matrix_coeffs 14 is H2Y_EUNSUPPORTED: I, Ct, Cp give
+ *   L'M'S', not R'G'B'.
+ *   Step 1 is step 1 of "light of PQ code planes", unchanged: k_up444 in the form `algorithm` and the context's inverse chroma siting
+ *     select.
+ *   Steps 2 and 3 are unchanged too: the normalisation, one subtraction and one IEEE division; the matrix, every product and sum
+ *     rounded by itself (the file is built -ffp-contract=off).
+ *   Last step, for each of G', B', R': v' = v > 0 ? min(v, 1) : +0.0.  Super-whites and sub-blacks are clipped: a .cube's domain
+ *     ends there.
+ * Output: three binary32 planes G', B', R' in [+0, 1].  Never -0, never NaN (none can arise from codes).
+ * Anchors: 10-bit video range with Cb = Cr = 512: Y 64 -> 0, Y 940 -> 1.0, Y 1023 -> 1.0 (clamped), Y 0 -> +0.0.  Full range:
+ *   Y 1023 -> 1.0.  (tests/test_signal_source_host.py asserts each.) */
+
+/* Steps 2, 3 and the clamp on 4:4:4 planes in host memory: the host twin of k_code_signal, the same two functions of
+ * csrc/h2y_codepixel.h compiled for the host without contraction.  Host only: no device, no context.  src[c]: plane c of the frame
+ * (Y, Cb, Cr or G, B, R), npix codes; dst[c]: plane c = G', B', R', npix binary32 samples.  d's chroma_format_idc and `algorithm`
+ * describe the file the planes came from and are only checked.  Refusals are the descriptor's, as h2y_codelight_batch states them,
+ * H2Y_EUNSUPPORTED for matrix_coeffs 14 and H2Y_EINVAL for null planes. */
+int h2y_code_signal_planes(const h2y_codelight_desc *d, size_t npix, const uint16_t *const src[3], float *const dst[3]);
+
+/* h2y_linearize_batch with this decode: the layout, the scratch, the launches of up to H2Y_LINEARIZE_FRAMES_PER_LAUNCH frames (k_up444
+ * per 4:2:0 frame, then one k_code_signal) and the refusals are that entry's; matrix_coeffs 14 is H2Y_EUNSUPPORTED.
+ * h2y_last_kernel_name "k_code_signal"; the variant names the matrix and the upsampling form, e.g. "k_code_signal<BT709,FIR>" (GBR,
+ * BT709, BT2020NC; 444, FIR, FIR_TL, REPLICATE). */
+int h2y_code_signal_batch(h2y_ctx *ctx, const h2y_codelight_desc *d, int n_frames, const uint16_t *const *d_frames, void *const *d_planes_out);
+
+/* h2y_pqcode_stream_open with this decode, armed with `lut` in signal mode (h2y_stream_lut3d(ctx, lut, interp, 1)) in the same call:
+ * the device takes a code frame of src through k_up444 (4:2:0) and k_code_signal into the slot's three planes, k_lut3d maps them and
+ * ends with the conversion's scale step, and the passthrough conversion writes the frame.  Planes in [0, 1] that met no scale step
+ * would be written as garbage, so no state exists in which this ring runs without its LUT.  d is the descriptor on which
+ * h2y_stream_lut3d(signal 1) arms a PQ code ring: in_sample_type H2Y_SAMPLE_F32, src_matrix 0, src_transfer 8 and dst_transfer 8 (the
+ * table is the transfer), dst_matrix 0 or 9, stats_override 1 with floor 0 and ceiling 1, width and height of src.  Anything else
+ * gets the code and message of h2y_pqcode_stream_open or of h2y_stream_lut3d, in that order, and leaves no ring open.
+ * h2y_stream_lut3d on this ring is H2Y_EINVAL (it applies a LUT already), and so are h2y_stream_hlg, h2y_stream_ictcp,
+ * h2y_stream_gamut, h2y_stream_gamut_compress and h2y_stream_tonemap, which act on light.  The arming entries a PQ code ring with a
+ * signal-mode LUT takes work on it unchanged (compare, SSIM, histogram, dither, pack, unpack). */
+int h2y_sigcode_stream_open(h2y_ctx *ctx, const h2y_desc *d, const h2y_codelight_desc *src, const h2y_lut3d *lut, int interp, int depth);
+
 /* ---- chroma siting: 4:2:0 chroma co-sited with the top-left luma sample (chroma_sample_loc_type 2; HDR10, UHD Blu-ray) -----------
  * The reference carries chroma_sample_loc_type through pic_t and prints it (hdr2yuv.cpp:490, :505); it parses no flag for it and
  * never acts on it.  Its two resamplers site the chroma as they happen to: the 2x2 box in the centre of the block both ways (loc
@@ -1780,7 +1824,7 @@ int h2y_upsample_444_sited(h2y_ctx *ctx, int width, int height, int chroma_sampl
                            const uint16_t *d_src, uint16_t *d_dst);
 
 /* Timing of the last h2y_convert_batch*() (or h2y_inverse_*, h2y_dpx_decode_batch, h2y_tiff_decode_batch,
- * h2y_rgb_interleave_batch, h2y_exr_decode_batch, h2y_compare_batch, h2y_ssim_batch, h2y_regions_batch, h2y_light_batch, h2y_lightdist_batch, h2y_codelight_batch, h2y_scenesig_batch, h2y_codescenesig_batch, h2y_linearize_batch, h2y_hlg_linearize_batch, h2y_sdr_linearize_batch, h2y_scale_batch, h2y_gamut_batch, h2y_tonemap_batch, h2y_hlg_batch, h2y_ictcp_batch, h2y_dither_batch, h2y_pack_batch, h2y_unpack_batch) call measured with HIP events on
+ * h2y_rgb_interleave_batch, h2y_exr_decode_batch, h2y_compare_batch, h2y_ssim_batch, h2y_regions_batch, h2y_light_batch, h2y_lightdist_batch, h2y_codelight_batch, h2y_scenesig_batch, h2y_codescenesig_batch, h2y_linearize_batch, h2y_hlg_linearize_batch, h2y_sdr_linearize_batch, h2y_code_signal_batch, h2y_scale_batch, h2y_gamut_batch, h2y_tonemap_batch, h2y_hlg_batch, h2y_ictcp_batch, h2y_dither_batch, h2y_pack_batch, h2y_unpack_batch) call measured with HIP events on
  * the stream the kernels ran on: total ms over the main kernels and how many
  * launches that covered. */
 int h2y_last_kernel_ms(const h2y_ctx *ctx, float *ms, int *launches);
@@ -1788,7 +1832,7 @@ int h2y_last_kernel_ms(const h2y_ctx *ctx, float *ms, int *launches);
 /* Name of the kernel those launches ran ("k_fused", "k_fused_t1", "k_fused_lut16",
  * "k_fused_narrow"; of the inverse entries "k_inverse", "k_inverse420", "k_inverse_batch", "k_inverse420_batch"; of
  * h2y_dpx_decode_batch "k_dpx_decode"; of h2y_tiff_decode_batch "k_tiff_decode", of h2y_rgb_interleave_batch
- * "k_rgb_interleave"; of h2y_exr_decode_batch "k_exr_decode"; of h2y_compare_batch "k_compare"; of h2y_scale_batch "k_scale"; of h2y_dither_batch "k_dither"; of h2y_pack_batch "k_pack"; of h2y_unpack_batch "k_unpack"; of h2y_gamut_batch "k_gamut"; of h2y_tonemap_batch "k_tonemap"; of h2y_hlg_batch "k_hlg"; of h2y_ictcp_batch "k_ictcp"; of h2y_codelight_batch "k_codelight"; of h2y_scenesig_batch "k_scenesig"; of h2y_codescenesig_batch "k_codescenesig"; of h2y_linearize_batch "k_linearize"; of h2y_hlg_linearize_batch "k_hlg_linearize"; of h2y_sdr_linearize_batch "k_sdr_linearize"): the name to
+ * "k_rgb_interleave"; of h2y_exr_decode_batch "k_exr_decode"; of h2y_compare_batch "k_compare"; of h2y_scale_batch "k_scale"; of h2y_dither_batch "k_dither"; of h2y_pack_batch "k_pack"; of h2y_unpack_batch "k_unpack"; of h2y_gamut_batch "k_gamut"; of h2y_tonemap_batch "k_tonemap"; of h2y_hlg_batch "k_hlg"; of h2y_ictcp_batch "k_ictcp"; of h2y_codelight_batch "k_codelight"; of h2y_scenesig_batch "k_scenesig"; of h2y_codescenesig_batch "k_codescenesig"; of h2y_linearize_batch "k_linearize"; of h2y_hlg_linearize_batch "k_hlg_linearize"; of h2y_sdr_linearize_batch "k_sdr_linearize"; of h2y_code_signal_batch "k_code_signal"): the name to
  * look for in a rocprofv3 kernel trace. */
 const char *h2y_last_kernel_name(const h2y_ctx *ctx);
 /* The same with its template arguments and launch shape, e.g. "k_fused_t1<F32,420BOX,YCBCR,PQ_IDENT> groups=8 xcd=1";

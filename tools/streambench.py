@@ -227,6 +227,17 @@ Prints one line per figure, then one JSON line with all of them.
      (h2y_pqcode_stream_open) on the same 10-bit 4:2:0 frames of 24.9 MB, both with the 0 / 1 override, five times in turn.
 Prints one line per figure, then one JSON line with all of them.
 
+`streambench.py sigsrc`: the signal of code planes (k_code_signal) on 4K frames, beside its yardsticks in the same job:
+  1. h2y_code_signal_batch over 64 distinct device frames per call (HIP events round each launch of up to 8 frames, k_up444 included)
+     for 10-bit 4:2:0 BT.2020nc FIR noise, the same as 10-bit 4:4:4, and 16-bit 4:4:4 matrix 0; h2y_linearize_batch on the 10-bit
+     4:4:4 frames; h2y_tiff_decode_batch (k_tiff_decode, 6 B in and 6 B out per pixel) on 64 payloads; h2y_lut3d_batch (k_lut3d, F32,
+     tetrahedral, signal mode, a 17-node table, in place) on the planes just written; each taken in turn five times after a warm-up:
+     median and spread in us per frame, the algorithmic bytes per frame over that time as a share of the 8 TB/s HBM peak, and
+     k_code_signal's 4:4:4 time over k_tiff_decode's;
+  2. frames/s from host memory to BT.2020nc 10-bit 4:2:0 of the signal code ring (h2y_sigcode_stream_open) beside the PQ code ring
+     (h2y_pqcode_stream_open) armed with the same table in signal mode, on the same 10-bit 4:2:0 frames of 24.9 MB, five times in turn.
+Prints one line per figure, then one JSON line with all of them.
+
 `streambench.py dither`: the reduction to the output bit depth (k_dither) on 4K frames, beside its yardsticks in the same job:
   1. the kernel time of h2y_dither_batch over 64 distinct device frames per call (HIP events, median of five after a warm-up call,
      out of place): 16 -> 10 4:2:0 ordered, 16 -> 10 4:2:0 noise, 16 -> 8 4:2:0 ordered and 16 -> 10 4:4:4 ordered; the 4 bytes a
@@ -1984,6 +1995,120 @@ def sdrsrc_main():
     print(json.dumps({"streambench_sdrsrc": res}), flush=True)
 
 
+def sigsrc_main():
+    import json
+
+    import torch
+
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    from cube_files import random_nodes, write_cube
+    from tiff_files import write_tiff
+
+    w, hh, nb, reps = 3840, 2160, 64, 5
+    n = w * hh
+    nf = int(os.environ.get("N", "60"))
+    depth = 3
+    rng = np.random.default_rng(33)
+    ctx = h.Context(0)
+    lut = h.Lut3d(write_cube(random_nodes(rng, 17, 0.0, 1.0), (0, 0, 0), (1, 1, 1)))
+    res = {"width": w, "height": hh, "frames_per_call": nb, "frames_per_launch": h.api.LINEARIZE_FRAMES_PER_LAUNCH, "reps": reps,
+           "ring_frames": nf, "ring_depth": depth, "lut_nodes": 17, "hbm_peak_tbs": 8.0}
+
+    def codes(count, lo, hi):
+        return torch.randint(lo, hi + 1, (count,), dtype=torch.int32, device="cuda").to(torch.int16)
+
+    def noise(chroma, bits):
+        s = 1 << (bits - 8)
+        nc = n // 4 if chroma == 1 else n
+        return torch.cat([codes(n, 16 * s, 235 * s), codes(nc, 16 * s, 240 * s), codes(nc, 16 * s, 240 * s)])
+
+    def report(key, label, t, nbytes, variant):
+        med = float(np.median(t))
+        tbs = nbytes / (med * 1e-3) / 1e12
+        res[key] = dict(kernel_us_per_frame=round(med * 1e3, 2), min_us=round(min(t) * 1e3, 2), max_us=round(max(t) * 1e3, 2),
+                        bytes_per_frame=nbytes, kernel_tbs=round(tbs, 2), hbm_peak_fraction=round(tbs / 8.0, 3), variant=variant)
+        print(f"{label:38s} {nb} frames per call: {med*1e3:7.2f} us/frame ({min(t)*1e3:.2f}..{max(t)*1e3:.2f})  {tbs:5.2f} TB/s = "
+              f"{tbs/8.0*100:4.1f} % of 8 TB/s  {variant}", flush=True)
+        return med
+
+    # 1. k_code_signal on three kinds of frames, k_linearize, k_tiff_decode and k_lut3d (signal mode), in turn
+    outs = [[torch.empty(n, dtype=torch.float32, device="cuda") for _ in range(3)] for _ in range(nb)]
+    shapes = (("420_10_noise", 1, 10, h.MATRIX_BT2020NC), ("444_10_noise", 3, 10, h.MATRIX_BT2020NC), ("444_16_gbr_noise", 3, 16, h.MATRIX_GBR))
+    descs = {name: h.make_codelight_desc(w, hh, chroma, bits, 0, matrix, 1) for name, chroma, bits, matrix in shapes}
+    frames = {name: [noise(chroma, bits) for _ in range(nb)] for name, chroma, bits, _ in shapes}
+    tdata = write_tiff(rng.integers(0, 65536, (hh, w, 3), dtype=np.uint16))
+    tinfo, rows = h.parse_tiff(tdata)
+    tpay = np.frombuffer(b"".join(tdata[int(o):int(o) + int(tinfo.row_bytes)] for o in rows), np.uint8)
+    pays = [torch.from_numpy(tpay.copy()).cuda() for _ in range(nb)]
+    touts = [[torch.empty(n, dtype=torch.int16, device="cuda") for _ in range(3)] for _ in range(nb)]
+    torch.cuda.synchronize()
+    calls = [(f"sig_{name}", (lambda name=name: ctx.code_signal_batch(descs[name], frames[name], outs))) for name, _, _, _ in shapes]
+    calls += [("lut3d", lambda: ctx.lut3d_batch(w, hh, h.SAMPLE_F32, lut, 1, 1, 10, 0, h.MATRIX_BT2020NC, outs)),  # on the signal just written
+              ("lin", lambda: ctx.linearize_batch(descs["444_10_noise"], frames["444_10_noise"], outs)),
+              ("tiff", lambda: ctx.tiff_decode_batch(tinfo, 0, pays, touts))]
+    t = {key: [] for key, _ in calls}
+    variants = {}
+    for rep in range(reps + 1):  # the first round warms up
+        for key, call in calls:
+            call()
+            variants[key] = ctx.last_kernel_variant()
+            if rep:
+                t[key].append(ctx.last_kernel_ms()[0] / nb)
+    med = {}
+    for name, chroma, _, _ in shapes:
+        med[name] = report(f"k_code_signal_{name}", f"k_code_signal {name}", t[f"sig_{name}"], n * (23 if chroma == 1 else 18), variants[f"sig_{name}"])
+    m_tiff = report("k_tiff_decode", "k_tiff_decode (yardstick)", t["tiff"], 12 * n, variants["tiff"])
+    report("k_linearize_444_10_noise", "k_linearize 444_10_noise", t["lin"], 18 * n, variants["lin"])
+    report("k_lut3d_f32_signal", "k_lut3d F32 tetrahedral signal", t["lut3d"], 24 * n, variants["lut3d"])
+    for name in ("444_10_noise", "444_16_gbr_noise"):
+        res[f"k_code_signal_over_k_tiff_decode_{name}"] = round(med[name] / m_tiff, 3)
+        print(f"k_code_signal / k_tiff_decode {name}: {med[name]/m_tiff:5.3f}", flush=True)
+
+    # 2. the signal code ring beside the PQ code ring armed with the same table in signal mode, on the same code frames
+    cd = descs["420_10_noise"]
+    payload = frames["420_10_noise"][0].cpu().numpy().view(np.uint8)
+    del outs, frames, pays, touts
+    torch.cuda.empty_cache()
+    d32 = h.make_desc(w, hh, dst_depth=10, src_transfer=8, dst_transfer=8, dst_matrix=h.MATRIX_BT2020NC, resampler=1, stats=[(0, 1)] * 3)
+
+    def ring(open_fn):
+        open_fn()
+        inflight = 0
+        t0 = time.perf_counter()
+        for _ in range(nf):
+            ctx.stream_input()[0][:] = payload
+            ctx.stream_submit()
+            inflight += 1
+            if inflight == depth - 1:
+                ctx.stream_output()
+                inflight -= 1
+        while inflight:
+            ctx.stream_output()
+            inflight -= 1
+        dt = (time.perf_counter() - t0) / nf
+        ctx.stream_close()
+        return dt
+
+    def open_pq():
+        ctx.pqcode_stream_open(d32, cd, depth)
+        ctx.stream_lut3d(lut, 1, 1)
+
+    rings = (("sigcode", lambda: ctx.sigcode_stream_open(d32, cd, lut, 1, depth)), ("pqcode", open_pq))
+    fps = {key: [] for key, _ in rings}
+    for rep in range(reps + 1):  # the first round warms up
+        for key, open_fn in rings:
+            dt = ring(open_fn)
+            if rep:
+                fps[key].append(1 / dt)
+    for key, _ in rings:
+        res[f"{key}_ring"] = dict(fps=round(float(np.median(fps[key])), 1), min_fps=round(min(fps[key]), 1), max_fps=round(max(fps[key]), 1),
+                                  upload_bytes_per_frame=3 * n)
+        print(f"{key:7s} ring with a signal-mode LUT, host memory to BT.2020nc 10-bit 4:2:0: {np.median(fps[key]):6.1f} frames/s "
+              f"({min(fps[key]):.1f}..{max(fps[key]):.1f}), {3*n/1e6:5.1f} MB up per frame", flush=True)
+    ctx.close()
+    print(json.dumps({"streambench_sigsrc": res}), flush=True)
+
+
 def scale_main():
     import json
 
@@ -3101,6 +3226,8 @@ if __name__ == "__main__":
         hlgsrc_main()
     elif sys.argv[1:] == ["sdrsrc"]:
         sdrsrc_main()
+    elif sys.argv[1:] == ["sigsrc"]:
+        sigsrc_main()
     elif sys.argv[1:] == ["scale"]:
         scale_main()
     elif sys.argv[1:] == ["dither"]:
