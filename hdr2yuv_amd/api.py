@@ -41,6 +41,7 @@ EXPORTS = [
     "h2y_light_batch", "h2y_stream_light", "h2y_stream_light_result",
     "h2y_lightdist_batch", "h2y_stream_lightdist", "h2y_stream_lightdist_result", "h2y_lightdist_json",
     "h2y_codelight_batch", "h2y_codelight_stream_open",
+    "h2y_gamutcheck_planes", "h2y_gamutcheck_batch", "h2y_stream_gamutcheck", "h2y_stream_gamutcheck_result",
     "h2y_scenesig_batch", "h2y_codescenesig_batch", "h2y_stream_scenesig", "h2y_stream_scenesig_result", "h2y_stream_lightdist_bins",
     "h2y_scene_distance", "h2y_scene_cuts", "h2y_scene_merge", "h2y_lightdist_json_scenes",
     "h2y_linearize_batch", "h2y_pqcode_stream_open",
@@ -74,6 +75,8 @@ SCENESIG_COLS, SCENESIG_ROWS = 16, 9  # the scene signature's grid of cells
 SCENESIG_FRAMES_PER_LAUNCH = 64
 CODELIGHT_FRAMES_PER_LAUNCH = 8  # a launch's 4:2:0 scratch stays at 253 MiB for 3840 x 2160
 LINEARIZE_FRAMES_PER_LAUNCH = 8  # the same rule, the same scratch
+GAMUTCHECK_MAX_SETS = 2  # check sets of one gamut containment check
+GAMUTCHECK_RATIO, GAMUTCHECK_FLOOR = 0.02, 0.02  # its defaults: the relative tolerance, and the floor in cd/m2
 DELTAE_FRAMES_PER_LAUNCH = 4  # the same scratch again: four upsampled chroma planes a pair
 SCALE_FRAMES_PER_LAUNCH = 64
 GAMUT_FRAMES_PER_LAUNCH = 64
@@ -303,6 +306,34 @@ class H2YScenesig(C.Structure):
 
     def __repr__(self):
         return f"H2YScenesig({self.as_dict()})"
+
+
+class H2YGamutcheckSet(C.Structure):
+    """h2y_gamutcheck_set: one check set's figures of a frame -- the set's code, the first pixel that holds the largest excursion
+    ((-1, -1) when no pixel is outside), that excursion as binary32 bits, the pixels outside and beyond, the sum over the pixels of
+    rint(e x 2^32), and the host's doubles."""
+
+    _fields_ = [("primaries", C.c_int32), ("max_x", C.c_int32), ("max_y", C.c_int32), ("max_bits", C.c_uint32),
+                ("outside", C.c_uint64), ("beyond", C.c_uint64), ("sum_q", C.c_uint64),
+                ("max_cdm2", C.c_double), ("mean_cdm2", C.c_double), ("beyond_share", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+    def __repr__(self):
+        return f"H2YGamutcheckSet({self.as_dict()})"
+
+
+class H2YGamutcheckStats(C.Structure):
+    """h2y_gamutcheck_stats: a frame's gamut containment check -- its pixel count and the figures of its n_sets check sets."""
+
+    _fields_ = [("pixels", C.c_uint64), ("n_sets", C.c_int32), ("reserved", C.c_int32), ("set", H2YGamutcheckSet * GAMUTCHECK_MAX_SETS)]
+
+    def as_dict(self):
+        return dict(pixels=self.pixels, n_sets=self.n_sets, sets=[self.set[s].as_dict() for s in range(self.n_sets)])
+
+    def __repr__(self):
+        return f"H2YGamutcheckStats({self.as_dict()})"
 
 
 class H2YSceneStats(C.Structure):
@@ -580,6 +611,16 @@ def load_library():
     L.h2y_scenesig_batch.restype = C.c_int
     L.h2y_codescenesig_batch.argtypes = [C.c_void_p, C.POINTER(H2YCodelightDesc), C.c_int, C.POINTER(C.c_void_p), C.POINTER(H2YScenesig)]
     L.h2y_codescenesig_batch.restype = C.c_int
+    L.h2y_gamutcheck_planes.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.c_double, C.c_double, C.c_int, C.c_int,
+                                        C.POINTER(C.c_void_p), C.POINTER(H2YGamutcheckStats)]
+    L.h2y_gamutcheck_planes.restype = C.c_int
+    L.h2y_gamutcheck_batch.argtypes = [C.c_void_p, C.POINTER(H2YCodelightDesc), C.c_int, C.c_int, C.POINTER(C.c_int), C.c_double,
+                                       C.c_double, C.c_int, C.POINTER(C.c_void_p), C.POINTER(H2YGamutcheckStats)]
+    L.h2y_gamutcheck_batch.restype = C.c_int
+    L.h2y_stream_gamutcheck.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_double, C.c_double]
+    L.h2y_stream_gamutcheck.restype = C.c_int
+    L.h2y_stream_gamutcheck_result.argtypes = [C.c_void_p, C.POINTER(H2YGamutcheckStats)]
+    L.h2y_stream_gamutcheck_result.restype = C.c_int
     L.h2y_stream_scenesig.argtypes = [C.c_void_p]
     L.h2y_stream_scenesig.restype = C.c_int
     L.h2y_stream_scenesig_result.argtypes = [C.c_void_p, C.POINTER(H2YScenesig)]
@@ -968,6 +1009,28 @@ def gamut_matrix(src_primaries: int, dst_primaries: int) -> np.ndarray:
     if rc != H2Y_OK:
         raise H2YError(rc, (why.value or b"").decode())
     return m.reshape(3, 3)
+
+
+def _int_array(values):
+    values = [int(v) for v in values]
+    return (C.c_int * max(len(values), 1))(*values), len(values)
+
+
+def gamutcheck_planes(lights, file_primaries: int, sets, ratio: float = GAMUTCHECK_RATIO, floor: float = GAMUTCHECK_FLOOR):
+    """h2y_gamutcheck_planes (host only, no device): k_gamutcheck's CPU twin from the matrix on, on three numpy light planes G, B, R
+    of float32 and one (height, width) shape (a flat plane counts as one row); returns the frame's H2YGamutcheckStats."""
+    src = [np.ascontiguousarray(p, dtype=np.float32) for p in lights]
+    if len(src) != 3 or any(p.shape != src[0].shape for p in src):
+        raise ValueError("three float32 planes of one shape")
+    height, width = src[0].shape if src[0].ndim == 2 else (1, src[0].size)
+    ins = (C.c_void_p * 3)(*[p.ctypes.data for p in src])
+    arr, n = _int_array(sets)
+    out = H2YGamutcheckStats()
+    lib = load_library()
+    rc = lib.h2y_gamutcheck_planes(int(file_primaries), n, arr, float(ratio), float(floor), width, height, ins, C.byref(out))
+    if rc != H2Y_OK:
+        raise H2YError(rc, (lib.h2y_last_error(None) or b"").decode())
+    return out
 
 
 def gamut_compress_curve(src_primaries: int, dst_primaries: int, threshold: float = GAMUT_COMPRESS_THRESHOLD,
@@ -1499,6 +1562,17 @@ class Context:
         self._check(self.lib.h2y_codescenesig_batch(self.h, C.byref(d), n, pf, out))
         return list(out[:n])
 
+    def gamutcheck_batch(self, d: H2YCodelightDesc, frames, file_primaries: int, sets, ratio: float = GAMUTCHECK_RATIO,
+                         floor: float = GAMUTCHECK_FLOOR):
+        """k_gamutcheck on device frames of PQ codes (as codelight_batch takes them): a list of H2YGamutcheckStats, one per frame --
+        how much of each frame lies outside each of the check sets `sets`, the file being coded in `file_primaries`."""
+        n = len(frames)
+        pf = (C.c_void_p * max(n, 1))(*[self._ptr(x) for x in frames])
+        arr, ns = _int_array(sets)
+        out = (H2YGamutcheckStats * max(n, 1))()
+        self._check(self.lib.h2y_gamutcheck_batch(self.h, C.byref(d), int(file_primaries), ns, arr, float(ratio), float(floor), n, pf, out))
+        return list(out[:n])
+
     def codelight_stream_open(self, d: H2YCodelightDesc, want_dist=0, depth=3) -> None:
         """A ring that only measures light: stream_input lends the frame's three planes, stream_output returns None,
         stream_light_result (and with want_dist stream_lightdist_result) the frame's figures."""
@@ -1929,6 +2003,17 @@ class Context:
     def stream_lightdist(self) -> None:
         """Arm an open forward ring to measure every frame's light distribution (h2y_stream_lightdist)."""
         self._check(self.lib.h2y_stream_lightdist(self.h))
+
+    def stream_gamutcheck(self, file_primaries: int, sets, ratio: float = GAMUTCHECK_RATIO, floor: float = GAMUTCHECK_FLOOR) -> None:
+        """Arm an open light-only ring to check every frame's gamut containment (h2y_stream_gamutcheck)."""
+        arr, ns = _int_array(sets)
+        self._check(self.lib.h2y_stream_gamutcheck(self.h, int(file_primaries), ns, arr, float(ratio), float(floor)))
+
+    def stream_gamutcheck_result(self) -> H2YGamutcheckStats:
+        """The gamut containment check of the frame stream_output returned last (h2y_stream_gamutcheck_result)."""
+        st = H2YGamutcheckStats()
+        self._check(self.lib.h2y_stream_gamutcheck_result(self.h, C.byref(st)))
+        return st
 
     def stream_scenesig(self) -> None:
         """Arm an open forward ring or light-only ring to measure every frame's scene signature (h2y_stream_scenesig)."""

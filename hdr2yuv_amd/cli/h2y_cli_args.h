@@ -211,6 +211,17 @@
  *             other than 16, any other matrix, matrix 0 with 4:2:0, 4:2:2, a source that is not .yuv / .rgb, --dst_filename,
  *             --ref_filename, --histogram, --ssim, --scale, --gamut_convert, --content_light or another *_only flag beside it, and
  *             --src_chroma_sample_loc_type 2 with --chroma_resampler_type 0 or with 4:4:4.
+ * --gamut_check 1 [--gamut_check_ratio T] [--gamut_check_floor A] [--gamut_check_against P] [--gamut_check_limit S] (additions), beside
+ *             --light_only 1: how much of every frame of the PQ master lies outside a primaries set narrower than the file's own
+ *             (include/hdr2yuv_hip.h, "gamut containment of PQ code planes", states every step).  The checked sets follow from
+ *             --src_colour_primaries: 8 / 9 (BT.2020) gives 12 (P3-D65) and 1 (BT.709), 12 gives 1.  T (0..1, 0.02 by default) is the
+ *             tolerance relative to the pixel's largest channel, A (cd/m2, 0.02 by default) the absolute floor.  The banner carries
+ *             gamut_check: and gamut_check_from:; the run prints one "gamut_check: frame" line per frame and set and one "gamut_check:
+ *             summary" line per set.  --gamut_check_limit S (0..1) makes the exit status 6 when the share of pixels beyond set P exceeds
+ *             S in any frame; P is --gamut_check_against, by default the widest checked set.  Accepted beside --dynamic_metadata, the
+ *             scene flags and --src_ictcp 1, for any --gpus.  Refused (exit 1, also under --dry_run): the flag or a sub-flag, whatever its value, without --light_only 1 on any flow,
+ *             a value other than 0 or 1, a sub-flag without it, --src_colour_primaries 1, unset or unknown (nothing narrower is known), P
+ *             not among the checked sets, T, A or S out of range or not finite.
  * --linearize 1 (an addition): a finished PQ master as the source of the forward flow to .yuv (include/hdr2yuv_hip.h, "linearised PQ code
  *             planes", states every step): a .yuv (--src_chroma_format_idc 1 or 3, --src_matrix_coeffs 1 or 9) or a .rgb (4:4:4, matrix
  *             0, its planes assigned to G, B, R as the .rgb forward reader assigns them) with --src_bit_depth 8..16, the source range flag
@@ -394,6 +405,16 @@ struct cli_args {
     /* --light_only 1: the light of a PQ .yuv or .rgb from its codes, no conversion */
     int light_only = 0;
     bool light_only_given = false;
+    /* --gamut_check 1 beside it: the gamut containment check; resolved: the checked sets (gamut_check_sets, the widest first) and the
+     * set the limit judges (gamut_check_against) */
+    int gamut_check = 0, gamut_check_against = 0, gamut_check_n_sets = 0, gamut_check_sets[H2Y_GAMUTCHECK_MAX_SETS] = {0, 0};
+    double gamut_check_ratio = H2Y_GAMUTCHECK_RATIO, gamut_check_floor = H2Y_GAMUTCHECK_FLOOR, gamut_check_limit = 0.0;
+    bool gamut_check_given = false, gamut_check_ratio_given = false, gamut_check_floor_given = false, gamut_check_against_given = false,
+         gamut_check_limit_given = false;
+    bool gamut_check_any() const
+    {
+        return gamut_check_given || gamut_check_ratio_given || gamut_check_floor_given || gamut_check_against_given || gamut_check_limit_given;
+    }
     /* --linearize 1: a PQ .yuv or .rgb linearised on the device as the forward flow's source; resolved: `lin` and lin_type keep the
      * file's own attributes and type, while `in` and in_type become those of the F32 LINEAR G,B,R planes the ring decodes */
     int linearize = 0;
@@ -506,6 +527,10 @@ static inline void cli_help()
            "  light of a PQ master: [--light_only 1] (--src_filename, a PQ .yuv -- 4:2:0 or 4:4:4, --src_matrix_coeffs 1 or 9 -- or .rgb,\n"
            "  --src_transfer_characteristics 16: MaxCLL / MaxFALL from its codes, no conversion; with --dynamic_metadata FILE the HDR10+\n"
            "  JSON too; --src_chroma_sample_loc_type 2 for top-left sited 4:2:0 chroma)\n"
+           "  gamut containment of a PQ master: beside --light_only 1, [--gamut_check 1 [--gamut_check_ratio T] [--gamut_check_floor A]\n"
+           "  [--gamut_check_against P] [--gamut_check_limit S]] (per frame the pixels outside P3-D65 and BT.709 for --src_colour_primaries\n"
+           "  8 / 9, outside BT.709 for 12, counted on the GPU: strictly, and beyond a tolerance of T of the pixel's largest channel, 0.02\n"
+           "  by default, and A cd/m2, 0.02 by default; exit status 6 when the share of pixels beyond set P exceeds S in any frame)\n"
            "  a PQ master as the source: [--linearize 1] (--src_filename, a PQ .yuv or .rgb as --light_only takes it, linearised on the\n"
            "  GPU into float G,B,R planes in linear light; from there the run is one from a .f32: --tone_map, --gamut_convert, --scale,\n"
            "  --content_light, --dynamic_metadata, --dst_chroma_sample_loc_type, --ref_filename, --ssim and --histogram apply)\n"
@@ -587,6 +612,11 @@ static inline void cli_parse(cli_args &a, int argc, char **argv)
         else if (is("--content_light")) { a.light = atoi(val()); a.light_given = true; }
         else if (is("--light_only")) { a.light_only = atoi(val()); a.light_only_given = true; }
         else if (is("--linearize")) { a.linearize = atoi(val()); a.linearize_given = true; }
+        else if (is("--gamut_check")) { a.gamut_check = atoi(val()); a.gamut_check_given = true; }
+        else if (is("--gamut_check_ratio")) { a.gamut_check_ratio = strtod(val(), nullptr); a.gamut_check_ratio_given = true; }
+        else if (is("--gamut_check_floor")) { a.gamut_check_floor = strtod(val(), nullptr); a.gamut_check_floor_given = true; }
+        else if (is("--gamut_check_against")) { a.gamut_check_against = atoi(val()); a.gamut_check_against_given = true; }
+        else if (is("--gamut_check_limit")) { a.gamut_check_limit = strtod(val(), nullptr); a.gamut_check_limit_given = true; }
         else if (is("--dynamic_metadata")) a.dynmeta = val();
         else if (is("--scene_detect")) { a.scene_detect = atoi(val()); a.scene_detect_given = true; }
         else if (is("--scene_threshold")) { a.scene_threshold = strtod(val(), nullptr); a.scene_threshold_given = true; }
@@ -822,6 +852,7 @@ static inline int cli_resolve_src_ictcp(cli_args &a);
 static inline int cli_resolve_siting(cli_args &a);
 static inline int cli_resolve_src_siting(cli_args &a);
 static inline int cli_resolve_light_only(cli_args &a);
+static inline int cli_resolve_gamut_check(cli_args &a);
 static inline int cli_resolve_scenes(cli_args &a);
 static inline int cli_resolve_linearize(cli_args &a);
 static inline int cli_resolve_src_hlg(cli_args &a);
@@ -966,6 +997,10 @@ static inline int cli_resolve_flows(cli_args &a)
                a.ictcp_given ? a.ictcp : a.src_ictcp, a.ictcp_given ? "ictcp" : "src_ictcp");
         return 1;
     }
+    if (a.gamut_check_any() && a.light_only != 1) { /* whatever the flow and the value: its one refusal, in the resolver's words */
+        cli_resolve_gamut_check(a);
+        return 1;
+    }
     const int arg_errors = a.dither_only == 1 ? cli_resolve_dither_only(a) : cli_resolve_all(a);
     if (arg_errors || !a.dithers()) return arg_errors;
     printf("dither: %d (%s)\ndither_depth: %d -> %d\ndither_temporal: %d\ndither_seed: %u\n", a.dither, a.dither == 1 ? "ordered" : "noise",
@@ -1023,6 +1058,7 @@ static inline int cli_resolve_all(cli_args &a)
         if (a.light_only) {
             int arg_errors = cli_resolve_light_only(a);
             if (a.scene_detect_given || a.scene_threshold_given || a.scene_cuts || a.scene_qpfile) arg_errors += cli_resolve_scenes(a);
+            if (a.gamut_check_any()) arg_errors += cli_resolve_gamut_check(a);
             return arg_errors + (a.delta_e_given || a.delta_e_threshold_given || a.delta_e_limit_given ? cli_resolve_delta_e(a) : 0);
         }
     }
@@ -1403,6 +1439,75 @@ static inline int cli_resolve_light_only(cli_args &a)
            chroma == H2Y_CHROMA_444 ? "none" : !a.resampler ? "replicate" : a.src_siting == 2 ? "fir_top_left" : "fir");
     if (a.dynmeta)
         printf("dynamic_metadata_from: PQ codes; HDR10+ profile A, one scene, percentiles of max(R,G,B) in %d bins\n", H2Y_LIGHTDIST_BINS);
+    return 0;
+}
+
+static inline const char *cli_primaries_name(int p)
+{
+    return p == 1 ? "BT.709" : p == 8 || p == 9 ? "BT.2020" : p == 12 ? "P3-D65" : "unknown";
+}
+
+/* --gamut_check 1 and its sub-flags, beside --light_only 1: the checked sets from --src_colour_primaries, the widest first, T, A, the
+ * set the limit judges; returns the number of argument errors */
+static inline int cli_resolve_gamut_check(cli_args &a)
+{
+    int arg_errors = 0;
+    printf("gamut_check: %d\n", a.gamut_check);
+    if (a.gamut_check != 0 && a.gamut_check != 1) {
+        printf("WARNING: gamut_check(%d) not 0 or 1\n", a.gamut_check);
+        return 1;
+    }
+    if (a.light_only != 1) {
+        printf("WARNING: --gamut_check and its sub-flags check a finished PQ master: they need --light_only 1 (a conversion's output: check the "
+               "written file)\n");
+        return 1;
+    }
+    if (a.gamut_check != 1) {
+        if (a.gamut_check_ratio_given || a.gamut_check_floor_given || a.gamut_check_against_given || a.gamut_check_limit_given) {
+            printf("WARNING: --gamut_check_ratio, --gamut_check_floor, --gamut_check_against and --gamut_check_limit need --gamut_check 1\n");
+            arg_errors++;
+        }
+        return arg_errors;
+    }
+    const int f = a.in.colour_primaries;
+    if (f == 8 || f == 9) a.gamut_check_n_sets = 2, a.gamut_check_sets[0] = 12, a.gamut_check_sets[1] = 1;
+    else if (f == 12) a.gamut_check_n_sets = 1, a.gamut_check_sets[0] = 1;
+    else {
+        printf("WARNING: --gamut_check 1: src_colour_primaries(%d) must be 8 or 9 (BT.2020: checked against P3-D65 and BT.709) or 12 (P3-D65: "
+               "against BT.709)%s\n", f, f == 1 ? "; nothing narrower than BT.709 is known" : "");
+        arg_errors++;
+    }
+    if (!(a.gamut_check_ratio >= 0.0 && a.gamut_check_ratio <= 1.0)) {
+        printf("WARNING: gamut_check_ratio(%g) outside range [0,1]\n", a.gamut_check_ratio);
+        arg_errors++;
+    }
+    if (!(a.gamut_check_floor >= 0.0 && a.gamut_check_floor <= 1.7e308)) { /* negative, a NaN or an infinity */
+        printf("WARNING: gamut_check_floor(%g) is not a finite number of cd/m2, 0 or more\n", a.gamut_check_floor);
+        arg_errors++;
+    }
+    if (a.gamut_check_limit_given && !(a.gamut_check_limit >= 0.0 && a.gamut_check_limit <= 1.0)) {
+        printf("WARNING: gamut_check_limit(%g) outside range [0,1]\n", a.gamut_check_limit);
+        arg_errors++;
+    }
+    if (a.gamut_check_n_sets) {
+        if (!a.gamut_check_against_given) a.gamut_check_against = a.gamut_check_sets[0];
+        bool found = false;
+        for (int s = 0; s < a.gamut_check_n_sets; s++) found = found || a.gamut_check_sets[s] == a.gamut_check_against;
+        if (!found) {
+            printf("WARNING: gamut_check_against(%d) is not among the checked sets (%d%s)\n", a.gamut_check_against, a.gamut_check_sets[0],
+                   a.gamut_check_n_sets == 2 ? ", 1" : "");
+            arg_errors++;
+        }
+    }
+    if (arg_errors) return arg_errors;
+    printf("gamut_check_from: primaries %d (%s) against", f, cli_primaries_name(f));
+    for (int s = 0; s < a.gamut_check_n_sets; s++)
+        printf("%s %d (%s)", s ? "," : "", a.gamut_check_sets[s], cli_primaries_name(a.gamut_check_sets[s]));
+    printf("; ratio %g%s, floor %g cd/m2%s", a.gamut_check_ratio, a.gamut_check_ratio_given ? "" : " (default)", a.gamut_check_floor,
+           a.gamut_check_floor_given ? "" : " (default)");
+    if (a.gamut_check_limit_given)
+        printf("; limit %g of the pixels beyond %d%s", a.gamut_check_limit, a.gamut_check_against, a.gamut_check_against_given ? "" : " (default)");
+    printf("\n");
     return 0;
 }
 

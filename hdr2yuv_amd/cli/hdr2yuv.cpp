@@ -113,7 +113,8 @@
  * Light of a PQ master (--light_only 1 [--dynamic_metadata FILE]; h2y_cli_args.h): each GPU thread sets its context's inverse chroma
  * siting where --src_chroma_sample_loc_type 2 says so and opens a light-only ring (h2y_codelight_stream_open) on the source's code
  * planes; the figures of frame k are kept by its index and reported by the two reports above, word for word, so the lines and FILE
- * are the same for any --gpus.  The banner carries light_only: and light_only_from:.
+ * are the same for any --gpus.  The banner carries light_only: and light_only_from:.  With --gamut_check 1 the ring is armed with
+ * h2y_stream_gamutcheck too and the run prints the gamut_check: lines (gamutcheck_report); --gamut_check_limit makes the exit status 6.
  *
  * Scaling (--scale 1 [--scale_taps A] with --dst_pic_width / --dst_pic_height on the forward flow; h2y_cli_args.h): each GPU thread
  * arms its ring (h2y_stream_scale), so the frame that comes down is the converted frame resampled on the device to the destination
@@ -256,6 +257,7 @@ struct results {
     std::vector<h2y_light_stats> light;
     std::vector<h2y_lightdist_stats> lightdist;
     std::vector<h2y_scenesig> scenesig; /* --scene_detect 1: frame k's signature */
+    std::vector<h2y_gamutcheck_stats> gamutcheck; /* --gamut_check 1: frame k's check */
     std::vector<uint32_t> dist_bins;    /* a scene flag: frame k's H2Y_LIGHTDIST_BINS bins, for the scenes' percentiles */
     std::vector<h2y_histogram_stats> hist;
     std::vector<std::array<uint32_t, 3>> occupied; /* the non-zero bins of frame k's planes */
@@ -265,6 +267,7 @@ struct results {
     results(const cli_args &a, long frames)
         : compare(a.ref ? (size_t)frames : 0), ssim(a.ssim ? (size_t)frames : 0), regions(a.regions ? (size_t)frames : 0), deltae(a.delta_e ? (size_t)frames : 0), light(a.light ? (size_t)frames : 0),
           lightdist(a.dynmeta ? (size_t)frames : 0), scenesig(a.scene_detect == 1 ? (size_t)frames : 0),
+          gamutcheck(a.gamut_check == 1 ? (size_t)frames : 0),
           dist_bins(a.scenes() ? (size_t)frames * H2Y_LIGHTDIST_BINS : 0), hist(a.hist ? (size_t)frames : 0), occupied(hist.size())
     {
         if (!a.hist) return;
@@ -296,6 +299,7 @@ struct results {
         if (a.light && h2y_stream_light_result(ctx, &light[k])) return false;
         if (a.dynmeta && h2y_stream_lightdist_result(ctx, &lightdist[k])) return false;
         if (a.scene_detect == 1 && h2y_stream_scenesig_result(ctx, &scenesig[k])) return false;
+        if (a.gamut_check == 1 && h2y_stream_gamutcheck_result(ctx, &gamutcheck[k])) return false;
         if (a.scenes() && h2y_stream_lightdist_bins(ctx, &dist_bins[(size_t)k * H2Y_LIGHTDIST_BINS])) return false;
         return true;
     }
@@ -635,7 +639,12 @@ static flow light_flow(const job &j)
                                    a.in.matrix_coeffs, a.resampler};
         return opened(h2y_codelight_stream_open(ctx, &d, a.dynmeta ? 1 : 0, kRingDepth), a, ctx);
     };
-    if (a.scene_detect == 1) f.arm = [](h2y_ctx *ctx, long) { return h2y_stream_scenesig(ctx); };
+    if (a.scene_detect == 1 || a.gamut_check == 1)
+        f.arm = [&a](h2y_ctx *ctx, long) {
+            return (a.scene_detect == 1 && h2y_stream_scenesig(ctx)) ||
+                   (a.gamut_check == 1 && h2y_stream_gamutcheck(ctx, a.in.colour_primaries, a.gamut_check_n_sets, a.gamut_check_sets,
+                                                                a.gamut_check_ratio, a.gamut_check_floor));
+        };
     return f;
 }
 
@@ -884,6 +893,36 @@ static int deltae_report(const cli_args &a, const std::vector<h2y_deltae_stats> 
            mean / (double)st.size(), worst, st[worst].mean, st[top].max, top, st[top].max_x, st[top].max_y, (unsigned long long)over,
            share(over, pixels));
     return a.delta_e_limit_given && beyond ? 5 : 0;
+}
+
+/* The gamut containment report (--gamut_check 1): per frame and set the pixels outside and beyond with their shares, the largest
+ * excursion in cd/m2 with its pixel and the mean; per set a summary.  Returns the exit status (6: --gamut_check_limit given and the
+ * share of pixels beyond --gamut_check_against above it in a frame) */
+static int gamutcheck_report(const cli_args &a, const std::vector<h2y_gamutcheck_stats> &st)
+{
+    bool over = false;
+    for (size_t k = 0; k < st.size(); k++)
+        for (int s = 0; s < st[k].n_sets; s++) {
+            const h2y_gamutcheck_set &t = st[k].set[s];
+            printf("gamut_check: frame %zu against %d outside %llu share %.6f beyond %llu share %.6f max %.4f at %d %d mean %.6f\n", k,
+                   t.primaries, (unsigned long long)t.outside, (double)t.outside / (double)st[k].pixels, (unsigned long long)t.beyond,
+                   t.beyond_share, t.max_cdm2, t.max_x, t.max_y, t.mean_cdm2);
+            over = over || (t.primaries == a.gamut_check_against && t.beyond_share > a.gamut_check_limit);
+        }
+    if (st.empty()) return 0;
+    for (int s = 0; s < st[0].n_sets; s++) {
+        size_t worst = 0, top = 0, with = 0;
+        for (size_t k = 0; k < st.size(); k++) {
+            const h2y_gamutcheck_set &t = st[k].set[s];
+            with += t.beyond > 0;
+            if (t.beyond_share > st[worst].set[s].beyond_share) worst = k;
+            if (t.max_bits > st[top].set[s].max_bits) top = k;
+        }
+        printf("gamut_check: summary against %d frames %zu frames_beyond %zu worst frame %zu share %.6f max %.4f frame %zu at %d %d\n",
+               st[0].set[s].primaries, st.size(), with, worst, st[worst].set[s].beyond_share, st[top].set[s].max_cdm2, top,
+               st[top].set[s].max_x, st[top].set[s].max_y);
+    }
+    return a.gamut_check_limit_given && over ? 6 : 0;
 }
 
 /* the content light report of the header comment */
@@ -1195,5 +1234,9 @@ int main(int argc, char **argv)
     }
     if (ran && a.light) light_report(res.light);
     if (ran && a.dynmeta && lightdist_report(a, res)) rc = 1;
+    if (ran && a.gamut_check == 1) {
+        const int grc = gamutcheck_report(a, res.gamutcheck);
+        if (!rc) rc = grc;
+    }
     return rc;
 }

@@ -402,6 +402,27 @@ int h2y_codelight_grid(uint32_t npix, int n_frames); /* blocks per frame */
 hipError_t h2y_launch_codelight(int matrix, int grid, hipStream_t st, const codelight_args &a, const codelight_frame *frames, int n_frames,
                                 light_acc *acc, lightdist_acc *dacc, uint32_t *bins);
 
+/* k_gamutcheck (h2y_gamutcheck.hip): the gamut containment check of the same frames (include/hdr2yuv_hip.h, "gamut containment of PQ
+ * code planes"), with k_codelight's frame table */
+struct gamutcheck_acc { /* one frame and set: zeroed before k_gamutcheck */
+    unsigned long long key; /* max over pixels of (e bits << 32) | ~index: the largest excursion, the first pixel on ties */
+    unsigned long long sum; /* sum over pixels of rint(e x 2^32) */
+    uint32_t outside;       /* pixels with e > 0 */
+    uint32_t beyond;        /* pixels with e > t m and e > a */
+};
+struct gamutcheck_frame_acc { /* one frame: its sets' accumulators (H2Y_GAMUTCHECK_MAX_SETS of them, the first n_sets used) */
+    gamutcheck_acc set[2];
+};
+struct gamutcheck_args {
+    codelight_args c;        /* k_codelight's */
+    uint32_t n_sets;         /* 1 or 2 */
+    float m[2][9];           /* per set h2y_gamut_matrix(file, set): row-major, on (R, G, B) columns */
+    float t, a;              /* the ratio, and the floor in units of 10000 cd/m2 */
+};
+/* k_gamutcheck over n_frames frames into acc[frame] (zeroed by the caller), on a grid of h2y_codelight_grid's blocks per frame; matrix: H2Y_MATRIX_GBR, _BT709, _BT2020NC or _ICTCP */
+hipError_t h2y_launch_gamutcheck(int matrix, int grid, hipStream_t st, const gamutcheck_args &a, const codelight_frame *frames, int n_frames,
+                                 gamutcheck_frame_acc *acc);
+
 /* k_scenesig and k_codescenesig (h2y_scenesig.hip): the scene signature (include/hdr2yuv_hip.h, h2y_scenesig) of the frames k_lightdist
  * and k_codelight measure, with their frame tables and arguments */
 struct scenesig_geom {

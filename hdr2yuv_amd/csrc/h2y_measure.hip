@@ -12,6 +12,7 @@
 #include "h2y_lut3d1.h"
 #include "h2y_hlg1.h"
 #include "h2y_gamut1.h"
+#include "h2y_gamutcheck1.h"
 #include "h2y_dither1.h"
 #include "h2y_pack1.h"
 
@@ -989,6 +990,177 @@ int h2y_codelight_stream_open(h2y_ctx *ctx, const h2y_codelight_desc *d, int wan
     rc = stage_arm(ctx, STAGE_CODELIGHT, std::move(st), "code light");
     if (rc) stream_free(ctx);
     return rc;
+}
+
+/* ---- gamut containment of PQ code planes (h2y_gamutcheck_planes, h2y_gamutcheck_batch, h2y_stream_gamutcheck): include/hdr2yuv_hip.h
+ * states the definition --------------------------------------------------------------------------------------------------------------- */
+
+/* a checked request: the sets as given, their matrices, t and a */
+struct gamutcheck_plan {
+    int n_sets = 0;
+    int sets[H2Y_GAMUTCHECK_MAX_SETS] = {0, 0};
+    float m[H2Y_GAMUTCHECK_MAX_SETS][9] = {};
+    float t = 0.0f, a = 0.0f;
+};
+
+/* the refusals of the check's own arguments, in the order every entry reports them */
+static int gamutcheck_check(h2y_ctx *ctx, int file_primaries, int n_sets, const int *sets, double ratio, double floor, gamutcheck_plan &g)
+{
+    if (n_sets < 1 || n_sets > H2Y_GAMUTCHECK_MAX_SETS) return fail(ctx, H2Y_EINVAL, "gamut check: n_sets must be 1..%d, not %d", H2Y_GAMUTCHECK_MAX_SETS, n_sets);
+    if (!sets) return fail(ctx, H2Y_EINVAL, "gamut check: null sets");
+    if (!(ratio >= 0.0 && ratio <= 1.0)) return fail(ctx, H2Y_EINVAL, "gamut check: ratio must be 0..1, not %g", ratio);
+    if (!(floor >= 0.0) || !std::isfinite(floor)) return fail(ctx, H2Y_EINVAL, "gamut check: floor must be a finite number of cd/m2, 0 or more, not %g", floor);
+    auto same = [](int a, int b) { return (a == 8 ? 9 : a) == (b == 8 ? 9 : b); };
+    for (int s = 0; s < n_sets; s++) {
+        if (file_primaries == 10 || sets[s] == 10)
+            return fail(ctx, H2Y_EUNSUPPORTED, "gamut check %d against %d: XYZ (colour primaries 10) has no gamut to be contained in", file_primaries, sets[s]);
+        const char *why;
+        const int rc = h2y_gamut_matrix(file_primaries, sets[s], g.m[s], &why);
+        if (rc) return fail(ctx, rc, "gamut check %d against %d: %s", file_primaries, sets[s], why);
+        for (int u = 0; u < s; u++)
+            if (same(sets[u], sets[s])) return fail(ctx, H2Y_EINVAL, "gamut check: set %d is listed twice", sets[s]);
+        g.sets[s] = sets[s];
+    }
+    g.n_sets = n_sets;
+    g.t = (float)ratio;
+    g.a = (float)(floor / 10000.0);
+    return H2Y_OK;
+}
+
+/* a frame's accumulators into the caller's struct: the doubles of step 5 */
+static void gamutcheck_finish(const gamutcheck_plan &g, const gamutcheck_frame_acc &acc, uint32_t width, uint32_t npix, h2y_gamutcheck_stats *out)
+{
+    memset(out, 0, sizeof *out);
+    out->pixels = npix;
+    out->n_sets = g.n_sets;
+    for (int s = 0; s < g.n_sets; s++) {
+        const gamutcheck_acc &a = acc.set[s];
+        h2y_gamutcheck_set &o = out->set[s];
+        o.primaries = g.sets[s];
+        o.max_bits = (uint32_t)(a.key >> 32);
+        const uint32_t index = ~(uint32_t)a.key;
+        o.max_x = a.outside ? (int32_t)(index % width) : -1;
+        o.max_y = a.outside ? (int32_t)(index / width) : -1;
+        o.outside = a.outside, o.beyond = a.beyond, o.sum_q = a.sum;
+        float e;
+        memcpy(&e, &o.max_bits, sizeof e);
+        o.max_cdm2 = 10000.0 * (double)e;
+        o.mean_cdm2 = ((10000.0 * (double)a.sum) * 0x1p-32) / (double)npix;
+        o.beyond_share = (double)a.beyond / (double)npix;
+    }
+}
+
+int h2y_gamutcheck_planes(int file_primaries, int n_sets, const int *sets, double ratio, double floor, int width, int height,
+                          const float *const lights[3], h2y_gamutcheck_stats *out)
+{
+    gamutcheck_plan g;
+    int rc = gamutcheck_check(nullptr, file_primaries, n_sets, sets, ratio, floor, g);
+    if (!rc) rc = picture_size_check(nullptr, width, height);
+    if (rc) return rc;
+    if (!lights || !lights[0] || !lights[1] || !lights[2] || !out) return fail(nullptr, H2Y_EINVAL, "null argument");
+    const uint32_t npix = (uint32_t)width * (uint32_t)height;
+    gamutcheck_regs k[H2Y_GAMUTCHECK_MAX_SETS] = {};
+    for (uint32_t i = 0; i < npix; i++) {
+        const float lg = lights[0][i], lb = lights[1][i], lr = lights[2][i], mx = fmaxf(fmaxf(lg, lb), lr);
+        if (!(lg >= 0.0f && lg <= 1.0f && lb >= 0.0f && lb <= 1.0f && lr >= 0.0f && lr <= 1.0f)) /* a NaN too: e < 1 rests on it */
+            return fail(nullptr, H2Y_EINVAL, "gamut check: pixel %u holds a light outside [0, 1]", i);
+        for (int s = 0; s < g.n_sets; s++) gamutcheck_keep(g.m[s], g.t, g.a, lg, lb, lr, mx, i, k[s]);
+    }
+    gamutcheck_frame_acc acc{};
+    for (int s = 0; s < g.n_sets; s++) acc.set[s] = gamutcheck_acc{k[s].key, k[s].sum, k[s].outside, k[s].beyond};
+    gamutcheck_finish(g, acc, (uint32_t)width, npix, out);
+    return H2Y_OK;
+}
+
+/* k_gamutcheck's arguments: the plan's codelight_args (tables set) and the check's */
+static gamutcheck_args gamutcheck_args_of(const codelight_plan &p, const gamutcheck_plan &g)
+{
+    gamutcheck_args a{};
+    a.c = p.a;
+    a.n_sets = (uint32_t)g.n_sets;
+    memcpy(a.m, g.m, sizeof a.m);
+    a.t = g.t, a.a = g.a;
+    return a;
+}
+
+int h2y_gamutcheck_batch(h2y_ctx *ctx, const h2y_codelight_desc *d, int file_primaries, int n_sets, const int *sets, double ratio,
+                         double floor, int n_frames, const uint16_t *const *d_frames, h2y_gamutcheck_stats *out)
+{
+    codelight_plan p;
+    gamutcheck_plan g;
+    int rc = batch_enter(ctx);
+    if (!rc) rc = codelight_check(ctx, d, p);
+    if (!rc) rc = gamutcheck_check(ctx, file_primaries, n_sets, sets, ratio, floor, g);
+    if (!rc) rc = frames_check(ctx, n_frames, d_frames, out != nullptr);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int per_launch = std::min(n_frames, H2Y_CODELIGHT_FRAMES_PER_LAUNCH);
+    codelight_frame *h;
+    rc = codelight_tables(ctx, p);
+    if (!rc) rc = frame_table(ctx, n_frames, h);
+    if (!rc) rc = ensure(ctx, ctx->gamutcheck, (size_t)n_frames * sizeof(gamutcheck_frame_acc));
+    if (!rc && p.sub) rc = ensure(ctx, ctx->codelight_up, (size_t)per_launch * 2u * p.plane_al);
+    if (rc) return rc;
+    gamutcheck_frame_acc *d_acc = ctx->gamutcheck.p;
+    char *d_up = ctx->codelight_up.p;
+    for (int f = 0; f < n_frames; f++) /* as h2y_codelight_batch: the upsampled chroma in the scratch of the frame's place in its launch */
+        h[f] = codelight_entry(p, d_frames[f], p.sub ? d_up + (size_t)(f % per_launch) * 2u * p.plane_al : nullptr);
+    HIP_TRY(ctx, hipMemsetAsync(d_acc, 0, (size_t)n_frames * sizeof(gamutcheck_frame_acc), ctx->stream));
+    const gamutcheck_args a = gamutcheck_args_of(p, g);
+    rc = timed_launches(ctx, h, n_frames, H2Y_CODELIGHT_FRAMES_PER_LAUNCH, "k_gamutcheck", [&](const codelight_frame *frames, int f0, int nf) {
+        for (int f = 0; p.sub && f < nf; f++) {
+            const hipError_t e = codelight_upsample(ctx, p, d_frames[f0 + f], d_up + (size_t)f * 2u * p.plane_al);
+            if (e != hipSuccess) return e;
+        }
+        return h2y_launch_gamutcheck(p.matrix, h2y_codelight_grid(p.a.npix, nf), ctx->stream, a, frames, nf, d_acc + f0);
+    });
+    if (rc) return rc;
+    std::vector<gamutcheck_frame_acc> acc(n_frames);
+    HIP_TRY(ctx, hipMemcpy(acc.data(), d_acc, (size_t)n_frames * sizeof(gamutcheck_frame_acc), hipMemcpyDeviceToHost));
+    for (int f = 0; f < n_frames; f++) gamutcheck_finish(g, acc[f], (uint32_t)d->width, p.a.npix, out + f);
+    ctx->last_variant = std::string("k_gamutcheck<") + matrix_name(p.matrix) + "," + std::to_string(g.n_sets) + "," +
+                        (!p.sub ? "444" : p.form == UP_FIR_TL ? "FIR_TL" : p.form == UP_FIR ? "FIR" : "REPLICATE") + ">";
+    return H2Y_OK;
+}
+
+/* The check's stage on the light-only ring: k_gamutcheck on the planes of the ring's codelight_stage, which ran before it (stage_id
+ * order) and left the slot's upsampled chroma where its table entry points.  Per slot the frame's accumulators on the device and
+ * pinned. */
+struct gamutcheck_stage : result_stage<gamutcheck_frame_acc> {
+    gamutcheck_plan g;
+    gamutcheck_args a{};
+    int run(h2y_ctx *ctx, int k) override
+    {
+        const codelight_stage *cl = stage_of<codelight_stage>(ctx, STAGE_CODELIGHT);
+        HIP_TRY(ctx, hipMemsetAsync(ss[k].d, 0, sizeof(gamutcheck_frame_acc), ctx->stream));
+        HIP_TRY(ctx, h2y_launch_gamutcheck(cl->p.matrix, h2y_codelight_grid(a.c.npix, 1), ctx->stream, a, cl->tab + k, 1, ss[k].d));
+        return H2Y_OK;
+    }
+};
+
+int h2y_stream_gamutcheck(h2y_ctx *ctx, int file_primaries, int n_sets, const int *sets, double ratio, double floor)
+{
+    int rc = arm_enter(ctx);
+    if (rc) return rc;
+    const codelight_stage *cl = stage_of<codelight_stage>(ctx, STAGE_CODELIGHT);
+    if (!cl) return fail(ctx, H2Y_EINVAL, "gamut containment is checked on the light-only ring only");
+    rc = arm_free(ctx, STAGE_GAMUTCHECK, "the ring checks gamut containment already");
+    if (rc) return rc;
+    auto st = std::make_unique<gamutcheck_stage>();
+    rc = gamutcheck_check(ctx, file_primaries, n_sets, sets, ratio, floor, st->g);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    st->a = gamutcheck_args_of(cl->p, st->g);
+    st->slots(ctx->ss.size());
+    return stage_arm(ctx, STAGE_GAMUTCHECK, std::move(st), "gamut check");
+}
+
+int h2y_stream_gamutcheck_result(h2y_ctx *ctx, h2y_gamutcheck_stats *out)
+{
+    return stream_result<gamutcheck_stage>(ctx, out, STAGE_GAMUTCHECK, "no stream open that checks gamut containment",
+                                           [&](const gamutcheck_stage &st, int k) {
+                                               gamutcheck_finish(st.g, *st.ss[k].h, (uint32_t)ctx->s_frame.width, st.a.c.npix, out);
+                                           });
 }
 
 /* ---- scene signature and scene cuts (h2y_scenesig_batch, h2y_codescenesig_batch, h2y_stream_scenesig, and the host-only merge and

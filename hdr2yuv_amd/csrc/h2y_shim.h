@@ -229,7 +229,7 @@ struct ring_stage {
     virtual int run(h2y_ctx *ctx, int slot) = 0;          /* on the context's stream, after the frame was produced */
     virtual int download(h2y_ctx *, int) { return H2Y_OK; } /* the result, on s_d2h after the slot's ev_conv */
 };
-enum stage_id { STAGE_UNPACK, STAGE_GAMUT, STAGE_TONEMAP, STAGE_LUT3D, STAGE_HLG, STAGE_ICTCP, STAGE_LIGHT, STAGE_LIGHTDIST, STAGE_CODELIGHT, STAGE_SCENESIG, STAGE_COMPARE, STAGE_SSIM, STAGE_DELTAE, STAGE_REGIONS, STAGE_HISTOGRAM, STAGE_SCALE, STAGE_DITHER, STAGE_PACK, STAGE_COUNT };
+enum stage_id { STAGE_UNPACK, STAGE_GAMUT, STAGE_TONEMAP, STAGE_LUT3D, STAGE_HLG, STAGE_ICTCP, STAGE_LIGHT, STAGE_LIGHTDIST, STAGE_CODELIGHT, STAGE_GAMUTCHECK, STAGE_SCENESIG, STAGE_COMPARE, STAGE_SSIM, STAGE_DELTAE, STAGE_REGIONS, STAGE_HISTOGRAM, STAGE_SCALE, STAGE_DITHER, STAGE_PACK, STAGE_COUNT };
 
 struct h2y_ctx {
     int device = 0;
@@ -303,6 +303,7 @@ struct h2y_ctx {
     dev_buf<char> lightdist;                   /* h2y_lightdist_batch: per launch k_lightdist's accumulators, then the bins (lightdist_layout) */
     dev_buf<char> codelight;                   /* h2y_codelight_batch: light_acc, then lightdist_layout */
     dev_buf<char> codelight_up;                /* the code-plane launches' upsampled 4:2:0 chroma (code light, the linearisers, Delta E, the code rings) */
+    dev_buf<gamutcheck_frame_acc> gamutcheck;  /* h2y_gamutcheck_batch's accumulators */
     dev_buf<unsigned long long> scenesig;      /* h2y_scenesig_batch's and h2y_codescenesig_batch's cells: 144 uint64 a frame */
     dev_buf<deltae_acc> deltae;                /* h2y_deltae_batch's accumulators */
     dev_buf<char> scale_tabs;                  /* h2y_scale_batch's tap tables */

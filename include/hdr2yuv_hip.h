@@ -809,7 +809,7 @@ int h2y_codelight_batch(h2y_ctx *ctx, const h2y_codelight_desc *d, int n_frames,
 /* A ring that only measures light: h2y_stream_input lends the frame's three planes (contiguous, as above), h2y_stream_output
  * returns *yuv = NULL, h2y_stream_light_result the frame's light and, when want_dist is 1, h2y_stream_lightdist_result its
  * distribution.  The inverse chroma siting is read when the ring opens.  Every arming entry (h2y_stream_compare, _ssim, _histogram,
- * _histogram_ex, _light, _lightdist, _scale, _gamut) but h2y_stream_scenesig is H2Y_EINVAL on this ring.  Refusals as h2y_codelight_batch; want_dist other
+ * _histogram_ex, _light, _lightdist, _scale, _gamut) but h2y_stream_scenesig and h2y_stream_gamutcheck is H2Y_EINVAL on this ring.  Refusals as h2y_codelight_batch; want_dist other
  * than 0 or 1 and depth outside 2..16 are H2Y_EINVAL. */
 int h2y_codelight_stream_open(h2y_ctx *ctx, const h2y_codelight_desc *d, int want_dist, int depth);
 
@@ -1294,6 +1294,80 @@ int h2y_gamut_compress_batch(h2y_ctx *ctx, int width, int height, int sample_typ
  * and h2y_stream_ictcp's passes, pic_stats and the conversion.  A ring takes one of the two gamut stages: H2Y_EINVAL on a ring armed
  * with either already, and after the first input.  Otherwise h2y_stream_gamut's refusals, and h2y_gamut_compress_curve's. */
 int h2y_stream_gamut_compress(h2y_ctx *ctx, int src_primaries, int dst_primaries, float threshold, float power);
+
+/* ---- gamut containment of PQ code planes: how much of a finished PQ master lies outside a narrower primaries set (--light_only 1
+ * --gamut_check 1) -------------------------------------------------------------------------------------------------------------------
+ * An HDR10 file is coded in BT.2020 primaries and is almost always required to stay inside P3-D65, the mastering display's gamut;
+ * before an SDR rung is cut the same question is asked of BT.709.  This section counts, per frame, the pixels whose colour lies
+ * outside a check set, and by how much.  It is the project's own definition: the reference has nothing to match.
+ * Frame: exactly what "light of PQ code planes" takes: h2y_codelight_desc, matrix_coeffs 0, 1, 9 and 14, 4:4:4 or 4:2:0 with the
+ *   context's inverse chroma siting.  The file's primaries F are 1, 8 / 9 or 12.  Between one and H2Y_GAMUTCHECK_MAX_SETS check sets
+ *   C_s, each one of 1, 8 / 9, 12, with chromaticities different from F's and from each other's.  XYZ (10) on either side is
+ *   H2Y_EUNSUPPORTED; everything else is refused as h2y_gamut_matrix refuses it.
+ *   1. Steps 1-4 of "light of PQ code planes" give L_G, L_B, L_R in [+0, 1]; m = max(L_G, L_B, L_R), as there.
+ *   2. Per set, M = h2y_gamut_matrix(F, C_s).  For i in R, G, B: v_i = (M[3i] L_R + M[3i+1] L_G) + M[3i+2] L_B, every product and
+ *      sum rounded to binary32 by itself: k_gamut's row form.
+ *   3. lo = min(v_R, v_G, v_B); the excursion is e = lo < 0 ? -lo : +0.  No NaN can arise.  For the known sets the negative entries
+ *      of a row sum to at least -0.67, so e < 1, e x 2^32 is exact and rint(e x 2^32) <= 2^32.
+ *   4. Two classes.  A pixel is outside when e > 0.  It is beyond when e > t m (one binary32 product) and e > a, where t = (float)T
+ *      and a = (float)(A / 10000.0), the division done in binary64 and rounded once.  T is `ratio`, 0 <= T <= 1, by default
+ *      H2Y_GAMUTCHECK_RATIO; A is `floor` in cd/m2, A >= 0, by default H2Y_GAMUTCHECK_FLOOR.
+ *   5. Per frame and set, every figure an exact integer, whatever the order of the work: pixels, outside, beyond; the largest e as
+ *      its binary32 bits with the first pixel that holds it (the key (bits(e) << 32) | ~index, as content light keeps its peak; the
+ *      position is (-1, -1) when outside is 0); sum_q = the sum over all pixels of rint(e x 2^32).  The host finishes, in binary64:
+ *      max_cdm2 = 10000 x e_max, mean_cdm2 = ((10000 x (double)sum_q) x 2^-32) / pixels (over all the frame's pixels), beyond_share =
+ *      beyond / pixels.
+ * Why two classes.  A strict count is useless on real files: colours that lie exactly on the BT.709 or P3-D65 boundary, expressed in
+ *   BT.2020 and coded as 10-bit video-range BT.2020nc, come back strictly outside their own gamut about half of the time, by
+ *   quantisation alone -- by up to 0.68 cd/m2 at 10-100 cd/m2 and 5.9 cd/m2 at 100-1000 cd/m2, yet by no more than 1.9 % of the
+ *   pixel's largest channel above 1 cd/m2 and no more than 0.016 cd/m2 below it.  Hence a relative tolerance and an absolute floor,
+ *   and the strict count reported beside the tolerant one.  With the defaults none of such boundary colours is beyond its own set
+ *   (tests/test_gamutcheck_host.py repeats the experiment on the binary32 path), and the BT.2020 primaries, cyan and magenta are
+ *   beyond P3-D65 and BT.709 at 1, 100 and 1000 cd/m2.  BT.2020 yellow sits 1.7 % from P3-D65's yellow edge: it is outside P3-D65 and
+ *   not beyond it.  The defaults are choices from that experiment; they have not been tuned on real programmes.
+ * The out-of-gamut pixels that 4:2:0 chroma upsampling itself creates at saturated edges are counted, as they are in the picture a
+ *   display shows. */
+#define H2Y_GAMUTCHECK_MAX_SETS 2
+#define H2Y_GAMUTCHECK_RATIO 0.02
+#define H2Y_GAMUTCHECK_FLOOR 0.02
+
+typedef struct h2y_gamutcheck_set {
+    int32_t  primaries;          /* the check set's code, as given */
+    int32_t  max_x, max_y;       /* the first pixel, in raster order, that holds the largest excursion; (-1, -1) when outside is 0 */
+    uint32_t max_bits;           /* the largest excursion, as binary32 bits (units of 10000 cd/m2) */
+    uint64_t outside, beyond;    /* pixels with e > 0; with e > t m and e > a */
+    uint64_t sum_q;              /* sum over the frame's pixels of rint(e x 2^32) */
+    double   max_cdm2, mean_cdm2, beyond_share;
+} h2y_gamutcheck_set;
+
+typedef struct h2y_gamutcheck_stats {
+    uint64_t pixels;             /* width x height */
+    int32_t  n_sets, reserved;
+    h2y_gamutcheck_set set[H2Y_GAMUTCHECK_MAX_SETS]; /* the first n_sets, in the order given; the rest zeros */
+} h2y_gamutcheck_stats;
+
+/* The check from step 2 on, on host light planes such as h2y_linearize_batch writes: lights[c] is plane c = G, B, R of width x height
+ * binary32 samples in [+0, 1]; a sample outside that range, a NaN included, is H2Y_EINVAL (step 3's e < 1 rests on it), and *out is
+ * then left as it was.  k_gamutcheck's CPU twin.  Host only: no device, no context.  H2Y_EINVAL for n_sets outside
+ * 1..H2Y_GAMUTCHECK_MAX_SETS, a set of the file's chromaticities or listed twice, a ratio that is not finite or outside [0, 1], a
+ * floor that is negative or not finite, a bad size and null arguments; H2Y_EUNSUPPORTED for XYZ (10), code 11 and every other
+ * unknown code. */
+int h2y_gamutcheck_planes(int file_primaries, int n_sets, const int *sets, double ratio, double floor, int width, int height,
+                          const float *const lights[3], h2y_gamutcheck_stats *out);
+
+/* The check of n_frames device frames of d, laid out and refused exactly as h2y_codelight_batch takes them; out[f] (host memory).
+ * Launches of up to H2Y_CODELIGHT_FRAMES_PER_LAUNCH frames, each k_up444 per 4:2:0 frame and then one k_gamutcheck (h2y_last_kernel_ms
+ * sums them, upsampling included; h2y_last_kernel_name "k_gamutcheck"; the variant names the matrix, the number of sets and the
+ * upsampling form, e.g. "k_gamutcheck<BT2020NC,2,FIR>"); synchronous.  The check's own refusals as h2y_gamutcheck_planes. */
+int h2y_gamutcheck_batch(h2y_ctx *ctx, const h2y_codelight_desc *d, int file_primaries, int n_sets, const int *sets, double ratio,
+                         double floor, int n_frames, const uint16_t *const *d_frames, h2y_gamutcheck_stats *out);
+
+/* Arm the ring of h2y_codelight_stream_open before its first input: k_gamutcheck then runs directly behind k_codelight, on the planes
+ * that kernel read (the slot's upsampled chroma included).  Every other ring is H2Y_EINVAL, and so is arming twice.  The light, the
+ * distribution and the scene signature of the ring do not change. */
+int h2y_stream_gamutcheck(h2y_ctx *ctx, int file_primaries, int n_sets, const int *sets, double ratio, double floor);
+/* The check of the frame that h2y_stream_output returned last. */
+int h2y_stream_gamutcheck_result(h2y_ctx *ctx, h2y_gamutcheck_stats *out);
 
 /* ---- tone mapping: the light of an HDR master brought down to a target peak, in linear light (--tone_map 1) ----------------------
  * The reference has no tone mapper (its README sends the user to ctlrender), so there are no bytes to match: this is the project's

@@ -124,6 +124,16 @@ Prints one line per figure, then one JSON line with all of them.
   3. frames/s of the light-only ring from host memory, 10-bit 4:2:0, without and with want_dist.
 Prints one line per figure, then one JSON line with all of them.
 
+`streambench.py gamutcheck`: the gamut containment check of PQ code planes (k_gamutcheck) on 4K frames, in one job:
+  1. h2y_gamutcheck_batch of a BT.2020 file against one set (P3-D65) and against two (P3-D65, BT.709), and h2y_codelight_batch without
+     the distribution on the same 64 distinct device frames, five calls of each taken in turn after a warm-up (HIP events round each
+     launch of up to 8 frames, k_up444 included): the median and spread in us per frame for 10-bit 4:2:0 and 4:4:4 BT.2020nc noise and
+     16-bit G,B,R noise, the bytes per frame as `codelight` counts them, the ratios to k_codelight, and the k_up444 share of the
+     4:2:0 time from the 4:4:4 figure;
+  2. frames/s of the light-only ring from host memory, 10-bit 4:2:0, unarmed and armed with h2y_stream_gamutcheck (two sets), three
+     runs of each in turn.
+Prints one line per figure, then one JSON line with all of them.
+
 `streambench.py scale`: the Lanczos resampler:
   1. the kernel time of h2y_scale_batch (k_scale) over 64 distinct device frames per call (HIP events, median of five after a
      warm-up call), the bytes per frame -- the source read once plus the output written -- over that time and their share of the
@@ -1581,6 +1591,121 @@ def codelight_main():
     print(f"light-only ring from host memory, 10-bit 4:2:0: {1/t_light:6.1f} frames/s   with want_dist {1/t_dist:6.1f} frames/s", flush=True)
     ctx.close()
     print(json.dumps({"streambench_codelight": res}), flush=True)
+
+
+def gamutcheck_main():
+    import json
+
+    import torch
+
+    w, hh, nb, reps = 3840, 2160, 64, 5
+    n = w * hh
+    nf = int(os.environ.get("N", "60"))
+    depth = 3
+    ctx = h.Context(0)
+    res = {"width": w, "height": hh, "frames_per_call": nb, "frames_per_launch": h.CODELIGHT_FRAMES_PER_LAUNCH, "reps": reps,
+           "ring_frames": nf, "ring_depth": depth, "hbm_peak_tbs": 8.0}
+
+    def codes(count, lo, hi):
+        return torch.randint(lo, hi + 1, (count,), dtype=torch.int32, device="cuda").to(torch.int16)
+
+    def noise(chroma, bits):
+        s = 1 << (bits - 8)
+        nc = n // 4 if chroma == 1 else n
+        return lambda: torch.cat([codes(n, 16 * s, 235 * s), codes(nc, 16 * s, 240 * s), codes(nc, 16 * s, 240 * s)])
+
+    def timed(calls):
+        """every call of calls in turn, reps times after a warm-up: per call its kernel times in ms per frame"""
+        out = [[] for _ in calls]
+        for rep in range(reps + 1):
+            for k, call in enumerate(calls):
+                call()
+                if rep:
+                    out[k].append(ctx.last_kernel_ms()[0] / nb)
+        return out
+
+    def report(key, label, t, nbytes, variant, **more):
+        med = float(np.median(t))
+        tbs = nbytes / (med * 1e-3) / 1e12
+        res[key] = dict(kernel_us_per_frame=round(med * 1e3, 2), min_us=round(min(t) * 1e3, 2), max_us=round(max(t) * 1e3, 2),
+                        bytes_per_frame=nbytes, kernel_tbs=round(tbs, 2), hbm_peak_fraction=round(tbs / 8.0, 3), variant=variant, **more)
+        print(f"{label:34s} {nb} frames per call: {med*1e3:7.2f} us/frame ({min(t)*1e3:.2f}..{max(t)*1e3:.2f})  {tbs:5.2f} TB/s = "
+              f"{tbs/8.0*100:4.1f} % of 8 TB/s  {variant}", flush=True)
+        return med
+
+    # 1. k_gamutcheck with one and with two sets beside k_codelight (LIGHT) on the same frames, in turn
+    med = {}
+    for name, chroma, bits, matrix in (("420_10_noise", 1, 10, h.MATRIX_BT2020NC), ("444_10_noise", 3, 10, h.MATRIX_BT2020NC),
+                                       ("444_16_gbr_noise", 3, 16, h.MATRIX_GBR)):
+        d = h.make_codelight_desc(w, hh, chroma, bits, 0, matrix, 1)
+        frames = [noise(chroma, bits)() for _ in range(nb)]
+        torch.cuda.synchronize()
+        variants = {}
+        note = lambda key: variants.setdefault(key, ctx.last_kernel_variant())
+        one, two, light = timed([lambda: (ctx.gamutcheck_batch(d, frames, 9, [12]), note(1)), lambda: (ctx.gamutcheck_batch(d, frames, 9, [12, 1]), note(2)),
+                                 lambda: (ctx.codelight_batch(d, frames), note(0))])
+        nbytes = n * (11 if chroma == 1 else 6)
+        med[name, 1] = report(f"k_gamutcheck_{name}_1set", f"k_gamutcheck {name} 1 set", one, nbytes, variants[1])
+        med[name, 2] = report(f"k_gamutcheck_{name}_2sets", f"k_gamutcheck {name} 2 sets", two, nbytes, variants[2])
+        med[name, 0] = report(f"k_codelight_{name}", f"k_codelight {name} (yardstick)", light, nbytes, variants[0])
+        for sets in (1, 2):
+            res[f"ratio_to_k_codelight_{name}_{sets}"] = round(med[name, sets] / med[name, 0], 3)
+        res[f"ratio_2sets_to_1set_{name}"] = round(med[name, 2] / med[name, 1], 3)
+        print(f"k_gamutcheck / k_codelight {name}: 1 set {med[name, 1]/med[name, 0]:5.3f}   2 sets {med[name, 2]/med[name, 0]:5.3f}   "
+              f"2 sets / 1 set {med[name, 2]/med[name, 1]:5.3f}", flush=True)
+        del frames
+        torch.cuda.empty_cache()
+    for sets in (1, 2):
+        share = 1.0 - med["444_10_noise", sets] / med["420_10_noise", sets]
+        res[f"k_up444_share_{sets}"] = round(share, 3)
+        print(f"k_up444 share of the 4:2:0 time ({sets} set{'s' if sets > 1 else ''}): {share*100:4.1f} %", flush=True)
+
+    # 2. the light-only ring from host memory, unarmed and armed
+    d = h.make_codelight_desc(w, hh, 1, 10, 0, h.MATRIX_BT2020NC, 1)
+    host = noise(1, 10)().cpu().numpy().view(np.uint16)
+    parts = [host[:n], host[n:n + n // 4], host[n + n // 4:]]
+
+    def ring(armed):
+        ctx.codelight_stream_open(d, 0, depth)
+        if armed:
+            ctx.stream_gamutcheck(9, [12, 1])
+        inflight = 0
+        t0 = time.perf_counter()
+
+        def take():
+            ctx.stream_output()
+            ctx.stream_light_result()
+            if armed:
+                ctx.stream_gamutcheck_result()
+
+        for _ in range(nf):
+            slot = ctx.stream_input()
+            for c in range(3):
+                slot[c][:] = parts[c]
+            ctx.stream_submit()
+            inflight += 1
+            if inflight == depth - 1:
+                take()
+                inflight -= 1
+        while inflight:
+            take()
+            inflight -= 1
+        dt = (time.perf_counter() - t0) / nf
+        ctx.stream_close()
+        return dt
+
+    ring(0)  # warm-up
+    ring(1)
+    t = {0: [], 1: []}
+    for _ in range(3):
+        for armed in (0, 1):
+            t[armed].append(ring(armed))
+    plain, armed = float(np.median(t[0])), float(np.median(t[1]))
+    res["light_only_ring"] = dict(unarmed_fps=round(1 / plain, 1), armed_fps=round(1 / armed, 1), bytes_per_frame=3 * n)
+    print(f"light-only ring from host memory, 10-bit 4:2:0: {1/plain:6.1f} frames/s   armed with h2y_stream_gamutcheck (2 sets) {1/armed:6.1f} frames/s",
+          flush=True)
+    ctx.close()
+    print(json.dumps({"streambench_gamutcheck": res}), flush=True)
 
 
 def deltae_main():
@@ -3256,6 +3381,8 @@ if __name__ == "__main__":
         lightdist_main()
     elif sys.argv[1:] == ["codelight"]:
         codelight_main()
+    elif sys.argv[1:] == ["gamutcheck"]:
+        gamutcheck_main()
     elif sys.argv[1:] == ["scenes"]:
         scenes_main()
     elif sys.argv[1:] == ["linearize"]:
